@@ -20,6 +20,9 @@ BASELINE.json's configs:
 Clips shard by global index across ranks (weak scaling, no data-path collective); the only collectives are a SUM of
 the counters and a MAX of the wall time.  Rank 0 prints ONE JSON line.
 
+`--dump-outputs DIR` writes what rank 0's last timed step returned as .npy files, so that two builds can be compared output for
+output on the same seeded inputs.
+
 `--gpus N` without a torchrun environment starts N child ranks itself (one process per GPU) BEFORE anything
 touches the GPU; the parent only waits for them.  A world size that differs from --gpus is an error.
 """
@@ -213,6 +216,30 @@ def pmc_traffic_per_launch(per_gpu, kernel_substr):
     return None, reason
 
 
+DUMP_BUDGET_BYTES = 64_000_000
+
+
+def dump_outputs(dirpath, arrays):
+    """Write {name: tensor} as dirpath/<name>.npy, in the given order: floating arrays keep float32 / float64, integer ones
+    become float64 (exact).  All files together stay within DUMP_BUDGET_BYTES: an array that does not fit whole is replaced by
+    the elements at a seeded sample of its flat indices (the same indices on every run), which go to <name>_sample_index.npy."""
+    import numpy as np
+    os.makedirs(dirpath, exist_ok=True)
+    left = DUMP_BUDGET_BYTES
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        a = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+        if a.nbytes + 128 > left:                                # 128: the .npy header
+            k = max(0, (left - 256) // (a.itemsize + 8))
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=k, replace=False))
+            np.save(os.path.join(dirpath, f"{name}_sample_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+            left -= idx.size * 8 + 128
+        np.save(os.path.join(dirpath, f"{name}.npy"), a)
+        left -= a.nbytes + 128
+    log(f"outputs of the last timed step written to {dirpath} ({DUMP_BUDGET_BYTES - left} bytes)")
+
+
 def run_stub(args, rank, world):
     """No GPU: the launcher, the barrier and the reductions only (tests/test_bench_launcher.py)."""
     from aware_amd import parallel
@@ -260,11 +287,13 @@ def run_train(args, rank, world):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss, _ = tr.step(audio, bits)
+        loss, vals = tr.step(audio, bits)
     torch.cuda.synchronize()
     parallel.barrier()
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"loss": torch.tensor(loss, dtype=torch.float64), "values": vals, "parameters": tr.flat})
     sums, maxes = parallel.reduce_metrics({"seconds": args.steps * per_gpu * args.seconds}, {"wall": wall}, device=dev)
     import torch.distributed as dist
     if dist.is_available() and dist.is_initialized():
@@ -309,9 +338,15 @@ def main():
     ap.add_argument("--conv-pipe", default="f16x2", choices=("f16x2", "bf16x3", "f32"),
                     help="arithmetic of the conv-block GEMMs (aware_amd.runtime.CONV_PIPES); the default also times bf16x3 beside it")
     ap.add_argument("--no-profile", action="store_true", help="skip the per-kernel HIP-event pass (roofline = null)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what rank 0's last timed step returned as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.workload == "stub":
+        ap.error("--dump-outputs: the stub workload computes nothing")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # no torchrun environment: become the launcher (nothing has touched the GPU in this process)
@@ -322,12 +357,17 @@ def main():
     if world != args.gpus:
         log(f"world size {world} (WORLD_SIZE) differs from --gpus {args.gpus}")
         sys.exit(2)
+    # config5's bandstop and cut attacks draw on the host's global generators (the reference's random / np.random): seeded so
+    # that the same arguments give the same inputs on every run
+    import random
+    import numpy as np
+    random.seed(20250905)
+    np.random.seed(20250905)
     if args.workload == "stub":
         sys.exit(run_stub(args, rank, world))
     if args.workload == "train":
         sys.exit(run_train(args, rank, world))
 
-    import numpy as np
     import torch
     from aware_amd._lib import require_gpu
     require_gpu()
@@ -396,6 +436,11 @@ def main():
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
     log(f"timed region done: {wall:.3f} s for {args.steps} steps")
+    if args.dump_outputs and rank == 0:
+        # before the profile and exact-pipe passes below, which run on the same sessions
+        dump_outputs(args.dump_outputs, {
+            "bits": res.bits, "values": res.values, "bit_errors": res.bit_errors, "clean_bit_errors": res.clean_bit_errors,
+            "watermarked_lengths": torch.tensor(res.watermarked.lengths), "watermarked": res.watermarked.data})
     sums, maxes = parallel.reduce_metrics(
         {"bit_errors": int(errs), "clean_bit_errors": int(clean), "bits": args.steps * len(n16) * 20, "seconds": secs_done},
         {"wall": wall}, device=dev)

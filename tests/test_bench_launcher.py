@@ -53,3 +53,23 @@ def test_single_rank_stub_line():
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1 and json.loads(lines[0])["n_gpus"] == 1
+
+
+def test_dump_outputs_stays_in_budget_with_a_seeded_sample(tmp_path):
+    """--dump-outputs' writer: small arrays whole (integers as float64), an array past the 64 MB budget as a seeded sample of
+    its flat indices -- the same indices on every call -- with the indices beside it."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    big = torch.arange(9_000_000, dtype=torch.float64)                       # 72 MB: over the budget on its own
+    for d in (tmp_path / "a", tmp_path / "b"):
+        bench.dump_outputs(str(d), {"bits": torch.tensor([[0, 1], [1, 1]], dtype=torch.int32), "big": big})
+    total = sum(f.stat().st_size for f in (tmp_path / "a").iterdir())
+    assert sorted(f.name for f in (tmp_path / "a").iterdir()) == ["big.npy", "big_sample_index.npy", "bits.npy"]
+    assert total <= bench.DUMP_BUDGET_BYTES and total > 0.99 * bench.DUMP_BUDGET_BYTES
+    bits = np.load(tmp_path / "a" / "bits.npy")
+    assert bits.dtype == np.float64 and bits.tolist() == [[0, 1], [1, 1]]
+    idx, val = np.load(tmp_path / "a" / "big_sample_index.npy"), np.load(tmp_path / "a" / "big.npy")
+    assert val.dtype == np.float64 and np.array_equal(val, idx) and np.all(np.diff(idx) > 0)
+    assert np.array_equal(idx, np.load(tmp_path / "b" / "big_sample_index.npy"))

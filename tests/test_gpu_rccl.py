@@ -96,6 +96,28 @@ def test_default_bench_line_carries_the_contract_objects():
     assert e["conv_pipe"] == "bf16x3" and 0 < e["value"] <= 1.2 * out["value"] and e["ber_percent"] == 0.0
 
 
+def test_bench_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """`bench.py --dump-outputs DIR`: the arrays the pipeline returned in the last timed step, whole at this size (32 x 3 s
+    clips: 6.1 MB of watermarked audio), float32 / float64, consistent with one another and with the JSON line."""
+    import numpy as np
+    env = {k: v for k, v in _env(0).items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT",
+                                                         "AWARE_FORCE_COLLECTIVES")}
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "0", "--clips-per-gpu", "32",
+                        "--no-cpu-baseline", "--no-profile", "--dump-outputs", str(tmp_path)],
+                       env=env, capture_output=True, text=True, timeout=900)
+    assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-3000:])
+    out = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
+    assert out["steps"] == 2
+    d = {f.stem: np.load(f) for f in tmp_path.iterdir()}
+    assert sorted(d) == ["bit_errors", "bits", "clean_bit_errors", "values", "watermarked", "watermarked_lengths"]
+    assert all(a.dtype in (np.float32, np.float64) for a in d.values())
+    n_out = -(-132300 * 160 // 441) // 256 * 256                               # 16 kHz clip length, whole hops (istft)
+    assert d["bits"].shape == d["values"].shape == (32, 20) and d["watermarked_lengths"].tolist() == [n_out] * 32
+    assert d["watermarked"].dtype == np.float32 and d["watermarked"].shape == (32 * n_out,) and np.all(np.isfinite(d["watermarked"]))
+    assert np.array_equal(d["bits"], (d["values"] > 0).astype(np.float64))       # the detector's threshold is 0
+    assert float(d["clean_bit_errors"]) == 0.0 and float(d["bit_errors"]) <= out["ber_percent"] / 100 * 2 * 32 * 20 + 0.01
+
+
 def test_training_workload_with_rccl_all_reduce():
     """`bench.py --workload train` under torch.distributed.run with one rank and the collectives forced on: the gradient bucket's
     all-reduce and the metric reductions run on RCCL inside the timed region."""
