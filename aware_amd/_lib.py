@@ -7,6 +7,7 @@ package goes through this library and raises if it is missing or if no GPU is pr
 from __future__ import annotations
 
 import ctypes as C
+import glob
 import os
 import subprocess
 
@@ -28,7 +29,7 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
     without a GPU).  Each source is compiled to an object under csrc/build/ (only those older than
     their inputs, in parallel), then linked."""
     from concurrent.futures import ThreadPoolExecutor
-    hdrs = [os.path.join(CSRC, h) for h in ("common.hpp", "fft512.hpp", "kernels.h", "dsp_args.hpp", "split_bf16.hpp")] + [
+    hdrs = glob.glob(os.path.join(CSRC, "*.hpp")) + glob.glob(os.path.join(CSRC, "*.h")) + [
         os.path.join(_HERE, "..", "include", "aware_hip.h")]
     hdr_t = max(os.path.getmtime(h) for h in hdrs)
     bdir = os.path.join(CSRC, "build")

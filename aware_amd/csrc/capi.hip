@@ -792,7 +792,7 @@ static int det_forward(const aware_detector* d, const aware_batch* b, const floa
                                     nwm, b->uniform_tp, co, ci, 1, o.rstd[l], nullptr, st, emit ? d->lastpk : nullptr,
                                     emit ? o.zpart : nullptr, d->ch[d->n_layers]);
                 cur_max = next_h2;
-                if (emit) o.zslabs = co / gemm_clip_h2_slab_width(nwm, co, b->B);
+                if (emit) o.zslabs = co / 128;
                 LAUNCHCHK(); PROF(K_GEMM_X3_FWD);
                 x = o.act[l];
                 continue;

@@ -30,6 +30,7 @@
 #include "kernels.h"
 #include "common.hpp"
 #include "split_bf16.hpp"
+#include "conv_block.hpp"
 
 namespace aware {
 
@@ -236,387 +237,30 @@ __device__ __forceinline__ void x3_tile_gemm(const float* __restrict__ A, int ld
 #undef X3_PIN
 }
 
+// the bf16x3 operand format of the shared conv block bodies (conv_block.hpp)
+struct X3Ops {
+    static constexpr bool kScaled = false;
+    static constexpr int kWeightBytes = 6;        // three bf16 terms
+    static constexpr int kTerms = 3;
+    template <int RG>
+    __device__ static __forceinline__ void tile_gemm(const float* __restrict__ A, int lda, const u32x4* __restrict__ Bpk, int K,
+                                                     int bm, int bn, unsigned char* lds, f32x4 (&acc)[2 * RG][1], int row_limit,
+                                                     float) {
+        x3_tile_gemm<RG, 8>(A, lda, Bpk, K, bm, bn, lds, acc, row_limit);
+    }
+};
+
 // (RG <= 3: two 8-wave workgroups per CU = four waves per SIMD need <= 128 VGPRs; RG = 4 does not fit that)
-template <int RG, int EPI, int NW>
-__global__ __launch_bounds__(64 * NW, (RG <= 3 && NW == 8) ? 4 : 2) void gemm_clip_x3_kernel(const float* __restrict__ A, int lda,
+template <int RG, int EPI>
+__global__ __launch_bounds__(512, RG <= 3 ? 4 : 2) void gemm_clip_x3_kernel(const float* __restrict__ A, int lda,
                                                                  const u32x4* __restrict__ Bpk, const float* __restrict__ bias,
                                                                  float* __restrict__ C, int ldc, int Tp, int N, int K,
                                                                  int tiles_n, int ntiles, float* __restrict__ rstd_io,
                                                                  const float* __restrict__ act,
                                                                  const u32x4* __restrict__ Lpk, float* __restrict__ zpart,
                                                                  int CL, int Mrows) {
-    // Mrows (X3_PLAIN only): rows of A and C that exist; the last row block may be partial (reads clamped, stores masked)
-    constexpr int NTW = 8 / NW;           // 16-column tiles per wave (slab = 128 columns)
-    constexpr int MT = 2 * RG;            // 16-row tiles per clip
-    constexpr int MH = RG;
-    constexpr int FRAG = 1024;
-    constexpr int BUF = 2 * 3 * MT * FRAG;
-    __shared__ __attribute__((aligned(16))) unsigned char lds[2 * BUF];
-
-    // Blocks b and b + 8 share an XCD (observed round-robin placement; speed only).  An XCD takes a contiguous range of clips and
-    // walks it slab-group-major: `sg` column slabs at a time whose packed weights (sg * 128 * K * 6 bytes) fit its 4 MB L2
-    // together with the activation rows in flight, all clips of the range for that group, then the next group.  Clip-major
-    // order streamed all 6.3 MB of a 1024 x 1024 layer through the L2 for every clip (PMC: 565 MB fetched per launch for 206 MB
-    // of operands); this order fetches the weights once per XCD and the activation rows once per group.
-    int id = blockIdx.x;
-    int clip, slab_;
-    if ((ntiles & 7) == 0) {
-        const int x = id & 7, j = id >> 3, R = ntiles >> 3;          // XCD, index inside its range, workgroups per XCD
-        const int nclip = R / tiles_n;                                // clips per XCD (ntiles = clips * tiles_n, clips % 8 == 0 here
-        if (nclip * tiles_n == R && nclip > 0) {                     //  whenever the batch size is a multiple of 8)
-            int sg = (int)(3355443u / (unsigned)(128 * K * 6));      // slabs whose weights fit 3.2 MB
-            sg = sg < 1 ? 1 : (sg > tiles_n ? tiles_n : sg);
-            while (tiles_n % sg) --sg;
-            const int per_group = nclip * sg;
-            const int grp = j / per_group, r = j % per_group;
-            clip = x * nclip + r / sg;
-            slab_ = grp * sg + r % sg;
-        } else {
-            id = x * R + j;
-            clip = id / tiles_n;
-            slab_ = id % tiles_n;
-        }
-    } else {
-        clip = id / tiles_n;
-        slab_ = id % tiles_n;
-    }
-    const int bm = clip * 32 * RG;
-    const int bn = slab_ * 128;
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r16 = lane & 15, kg = lane >> 4;
-
-    f32x4 acc[MT][NTW];
-    x3_tile_gemm<RG, NW>(A, lda, Bpk, K, bm, bn, lds, acc, EPI == X3_PLAIN ? min(32 * RG, Mrows - bm) : 32 * RG);
-
-    // ---- epilogue: lane holds rows m*16 + 4*kg + e (e = 0..3) of columns cb + n*16 + r16 ----
-    const int cb = bn + wave * (16 * NTW) + r16;
-    const float invT = 1.0f / (float)Tp;
-    if (EPI == X3_PLAIN && NTW == 1 && (ldc & 3) == 0) {
-        // The tile leaves in ROW-MAJOR order (16 bytes per lane, half a wave = one 512-byte row segment), not in the
-        // accumulator's layout (4 rows x 64 bytes per wave instruction, which streams at about half the rate: measured on
-        // the read-out kernel, 3.0 vs 6 TB/s).  The staging LDS is free now; pitch 132 floats keeps both sides conflict-free.
-        float (*T)[132] = reinterpret_cast<float (*)[132]>(lds);
-        const float bv = bias ? bias[cb] : 0.f;
-        __syncthreads();                                // every wave has left the K loop
-#pragma unroll
-        for (int m = 0; m < MT; ++m)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) T[16 * m + 4 * kg + e][16 * wave + r16] = acc[m][0][e] + bv;
-        __syncthreads();
-        const int c4 = (lane & 31) * 4, rr = 2 * wave + (lane >> 5);
-#pragma unroll
-        for (int j = 0; j < MT; ++j) {
-            const int row = rr + 16 * j;
-            float4 o = *reinterpret_cast<const float4*>(&T[row][c4]);
-            if (row >= Tp) o = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (bm + row < Mrows) *reinterpret_cast<float4*>(C + (size_t)(bm + row) * ldc + bn + c4) = o;
-        }
-        return;
-    }
-    // (the forward / backward epilogues keep the accumulator-layout stores: behind the K loop of a second resident workgroup
-    //  they are hidden -- the row-major form measured the same time on the three conv blocks)
-#pragma unroll
-    for (int n = 0; n < NTW; ++n) {
-        const int col = cb + n * 16;
-        if (EPI == X3_PLAIN) {
-            const float bv = bias ? bias[col] : 0.f;
-#pragma unroll
-            for (int m = 0; m < MT; ++m)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int row = m * 16 + 4 * kg + e;
-                    if (bm + row < Mrows) C[(size_t)(bm + row) * ldc + col] = row < Tp ? acc[m][n][e] + bv : 0.f;
-                }
-        } else if (EPI == X3_FWD || EPI == X3_FWD_LAST) {
-            const float bv = bias ? bias[col] : 0.f;
-            float s = 0.f;
-#pragma unroll
-            for (int m = 0; m < MT; ++m)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int row = m * 16 + 4 * kg + e;
-                    acc[m][n][e] += bv;
-                    if (row < Tp) s += acc[m][n][e];
-                }
-            s += __shfl_xor(s, 16);
-            s += __shfl_xor(s, 32);
-            const float mean = s * invT;
-            float qq = 0.f;
-#pragma unroll
-            for (int m = 0; m < MT; ++m)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int row = m * 16 + 4 * kg + e;
-                    if (row < Tp) { const float d = acc[m][n][e] - mean; qq += d * d; }
-                }
-            qq += __shfl_xor(qq, 16);
-            qq += __shfl_xor(qq, 32);
-            const float rs = 1.0f / sqrtf(qq * invT + 1e-5f);      // biased variance, eps 1e-5 (InstanceNorm1d defaults)
-            if (kg == 0) rstd_io[(size_t)clip * N + col] = rs;
-#pragma unroll
-            for (int m = 0; m < MT; ++m)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int row = m * 16 + 4 * kg + e;
-                    const float u = (acc[m][n][e] - mean) * rs;
-                    const float o = row < Tp ? (u > 0.f ? u : 0.2f * u) : 0.f;
-                    acc[m][n][e] = o;
-                    C[(size_t)(bm + row) * ldc + col] = o;
-                }
-        } else {
-            // X3_BWD: acc = dL/dA of the previous block's output (read from `act`, post-activation);
-            //         C = dL/dZ = rstd * (dU - mean_t dU - u * mean_t(dU*u)),  dU = acc * lrelu'(u)
-            const float rs = rstd_io[(size_t)clip * N + col];
-            float s1 = 0.f, s2 = 0.f;
-            float u[MT][4];
-#pragma unroll
-            for (int m = 0; m < MT; ++m)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int row = m * 16 + 4 * kg + e;
-                    // unconditional load (padding rows exist and hold zeros): a branch here would serialise the loads
-                    const float av = act[(size_t)(bm + row) * ldc + col];
-                    const bool valid = row < Tp;
-                    const float uv = valid ? (av > 0.f ? av : av * 5.0f) : 0.f;                 // invert LeakyReLU(0.2)
-                    const float du = valid ? acc[m][n][e] * (av > 0.f ? 1.f : 0.2f) : 0.f;
-                    acc[m][n][e] = du;
-                    u[m][e] = uv;
-                    s1 += du;
-                    s2 += du * uv;
-                }
-            s1 += __shfl_xor(s1, 16);
-            s1 += __shfl_xor(s1, 32);
-            s2 += __shfl_xor(s2, 16);
-            s2 += __shfl_xor(s2, 32);
-            const float m1 = s1 * invT, m2 = s2 * invT;
-#pragma unroll
-            for (int m = 0; m < MT; ++m)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int row = m * 16 + 4 * kg + e;
-                    C[(size_t)(bm + row) * ldc + col] = row < Tp ? rs * (acc[m][n][e] - m1 - u[m][e] * m2) : 0.f;
-                }
-        }
-    }
-    if (EPI == X3_FWD_LAST && NTW == 1) {
-        // acc[m][0][e] holds this block's output (zero in padding rows).  The next conv block is the skinny last one
-        // (CL <= 64 channels): its K = this N is split over the column slabs, so this workgroup contributes the partial
-        // z_part[slab] = out[:, slab] * Wlast[:, slab]^T.  The output tile is re-laid as A fragments (k = column) in LDS.
-        // Work split: wave w takes K32 step t = w>>1 of the slab's 128 columns and half mh = w&1 of the row tiles (all
-        // column tiles of the last conv, CL <= 48); the four t-partials are then summed through LDS.
-        const int slab = bn >> 7, KS2L = N >> 5, ncl = (CL + 15) >> 4;
-        const int tq = wave >> 1, mh = wave & 1;
-        bf16x8 bl[3][3];
-#pragma unroll
-        for (int n = 0; n < 3; ++n)
-            if (n < ncl) {
-#pragma unroll
-                for (int p = 0; p < 3; ++p)
-                    bl[n][p] = __builtin_bit_cast(bf16x8, Lpk[(((size_t)n * KS2L + 4 * slab + tq) * 3 + p) * 64 + lane]);
-            }
-        __syncthreads();                                  // every wave is done with the staging buffers
-        // the output tile goes through LDS as f32 [row][column], row pitch 132 floats (conflict-free 4-byte stores from
-        // the accumulator layout); each wave reads its A fragments back as 8 consecutive columns per lane and splits them
-        float* const T = reinterpret_cast<float*>(lds);
-        constexpr int TP = 132;
-#pragma unroll
-        for (int m = 0; m < MT; ++m)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) T[(16 * m + 4 * kg + e) * TP + 16 * wave + r16] = acc[m][0][e];
-        __syncthreads();
-        f32x4 zt[MH][3];
-#pragma unroll
-        for (int mm = 0; mm < MH; ++mm) {
-#pragma unroll
-            for (int n = 0; n < 3; ++n) zt[mm][n] = f32x4{0.f, 0.f, 0.f, 0.f};
-            const float* src = T + (16 * (mh * MH + mm) + r16) * TP + 32 * tq + 8 * kg;
-            const float4 x0 = *reinterpret_cast<const float4*>(src), x1 = *reinterpret_cast<const float4*>(src + 4);
-            uint4 q0, q1, q2;
-            split_pair(x0.x, x0.y, q0.x, q1.x, q2.x);
-            split_pair(x0.z, x0.w, q0.y, q1.y, q2.y);
-            split_pair(x1.x, x1.y, q0.z, q1.z, q2.z);
-            split_pair(x1.z, x1.w, q0.w, q1.w, q2.w);
-            bf16x8 a[3];
-            a[0] = __builtin_bit_cast(bf16x8, q0); a[1] = __builtin_bit_cast(bf16x8, q1); a[2] = __builtin_bit_cast(bf16x8, q2);
-#pragma unroll
-            for (int term = 0; term < 6; ++term) {
-                const int pa = term == 0 ? 2 : (term == 1 || term == 3) ? 1 : 0;
-                const int pb = term == 2 ? 2 : (term == 1 || term == 4) ? 1 : 0;
-#pragma unroll
-                for (int n = 0; n < 3; ++n)
-                    if (n < ncl) zt[mm][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[pa], bl[n][pb], zt[mm][n], 0, 0, 0);
-            }
-        }
-        __syncthreads();                                  // all fragment reads done: the buffer becomes the partial store
-#pragma unroll
-        for (int mm = 0; mm < MH; ++mm)
-#pragma unroll
-            for (int n = 0; n < 3; ++n)
-                *reinterpret_cast<f32x4*>(lds + (size_t)((wave * MH + mm) * 3 + n) * FRAG + lane * 16) = zt[mm][n];
-        __syncthreads();
-        if (wave < MT) {
-            const int smh = wave / MH, smm = wave % MH;   // this wave finishes row tile `wave`
-            float* zp = zpart + (size_t)slab * ((size_t)(ntiles / tiles_n) * 32 * RG * CL) + (size_t)(bm + 16 * wave + 4 * kg) * CL;
-#pragma unroll
-            for (int n = 0; n < 3; ++n)
-                if (n < ncl) {
-                    f32x4 t = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                    for (int q = 0; q < 4; ++q)
-                        t += *reinterpret_cast<const f32x4*>(lds + (size_t)(((2 * q + smh) * MH + smm) * 3 + n) * FRAG + lane * 16);
-                    if (16 * n + r16 < CL) {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) zp[(size_t)e * CL + 16 * n + r16] = t[e];
-                    }
-                }
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------
-// Ragged batches: the same conv block (or data-gradient GEMM) for clips of ANY length in ONE launch.
-// A workgroup owns one clip x 128 columns, as above, but takes the clip's rows from the batch tables (pool_off is
-// 32-aligned per clip, Tp = frames / 2) and walks them in chunks of at most three 32-row groups (72 KB of staging memory
-// and <= 128 VGPRs: two workgroups per CU at any clip length).  A clip that fits one chunk gets the same single-pass
-// epilogue as the uniform kernel (bit-identical results).  A longer clip is done in two passes over its chunks:
-//   pass 1  GEMM of the chunk, raw result to C, per-column statistics carried in registers across the chunks
-//           (forward: count / mean / M2 merged with Chan's formula; backward: the two sums of the InstanceNorm backward);
-//   pass 2  the workgroup re-reads its own raw tile (L2-resident, written by the same lanes) and applies the
-//           normalisation + LeakyReLU (forward) or the InstanceNorm backward (backward) in place.
-// No second launch, no inter-workgroup traffic, the per-(clip, channel) statistics never leave the registers.
-// Reference: detection/modules/conv1d.py:38-42 and its autograd.
-// ---------------------------------------------------------------------------------------------------
-constexpr int kRaggedRG = 3;           // largest chunk, in 32-row groups
-
-// one chunk: rows [bm, bm + 32 RG) of which `rows` are valid.  SINGLE: the clip is this chunk.
-// st0/st1/st2: forward (count, mean, M2) of the column; backward (unused, sum dU, sum dU*u) in-lane partial sums
-extern __shared__ __attribute__((aligned(16))) unsigned char x3_dyn_lds[];    // the ragged kernel's staging memory (dynamic LDS)
-
-template <class T>
-__device__ __forceinline__ T* uniform_ptr(T* p) {
-    // a wave-uniform pointer to GLOBAL memory that arrived as a function argument: in VGPRs and in the generic address
-    // space (flat loads count on vmcnt AND lgkmcnt, so every wait in the K loop became a full drain of both).  Back to an
-    // SGPR pair, and through address space 1 so that the loads are global_load again.
-    const unsigned long long v = (unsigned long long)p;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    return (T*)(__attribute__((address_space(1))) T*)(((unsigned long long)hi << 32) | lo);
-}
-
-// (not inlined: each tile height keeps its own register allocation -- inlined side by side the two K loops cost the
-// kernel 20-40 spilled VGPRs inside the loop)
-template <int RG, int EPI>
-__device__ __attribute__((noinline)) void x3_ragged_chunk(const bool SINGLE, const float* __restrict__ A, int lda, const u32x4* __restrict__ Bpk,
-                                                const float* __restrict__ bias, float* __restrict__ C, int ldc, int N, int K,
-                                                int bm, int rows, int store_rows, int bn,
-                                                float* __restrict__ rstd_clip, const float* __restrict__ act, float& st0,
-                                                float& st1, float& st2) {
-    unsigned char* lds = x3_dyn_lds;
-    // the arguments of a non-inlined function arrive in VGPRs; all of these are wave-uniform and go back to SGPRs (the K
-    // loop runs at the 128-VGPR limit: left in VGPRs they were spilled and reloaded inside it)
-    A = uniform_ptr(A); Bpk = uniform_ptr(Bpk); bias = uniform_ptr(bias); C = uniform_ptr(C);
-    rstd_clip = uniform_ptr(rstd_clip); act = uniform_ptr(act);
-    lda = __builtin_amdgcn_readfirstlane(lda); ldc = __builtin_amdgcn_readfirstlane(ldc);
-    N = __builtin_amdgcn_readfirstlane(N); K = __builtin_amdgcn_readfirstlane(K);
-    bm = __builtin_amdgcn_readfirstlane(bm); bn = __builtin_amdgcn_readfirstlane(bn);
-    rows = __builtin_amdgcn_readfirstlane(rows); store_rows = __builtin_amdgcn_readfirstlane(store_rows);
-    // rows: valid rows of the chunk; store_rows (a multiple of 32, <= 32 RG): rows of the clip's allocation under this tile
-    constexpr int MT = 2 * RG;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int r16 = lane & 15, kg = lane >> 4;
-    f32x4 acc[MT][1];
-    x3_tile_gemm<RG, 8>(A, lda, Bpk, K, bm, bn, lds, acc, store_rows);
-    const int col = bn + wave * 16 + r16;
-    const float invR = 1.0f / (float)rows;
-    if (EPI == X3_FWD) {
-        const float bv = bias ? bias[col] : 0.f;
-        float s = 0.f;
-#pragma unroll
-        for (int m = 0; m < MT; ++m)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                acc[m][0][e] += bv;
-                if (m * 16 + 4 * kg + e < rows) s += acc[m][0][e];
-            }
-        s += __shfl_xor(s, 16);
-        s += __shfl_xor(s, 32);
-        const float mean = s * invR;
-        float qq = 0.f;
-#pragma unroll
-        for (int m = 0; m < MT; ++m)
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (m * 16 + 4 * kg + e < rows) { const float d = acc[m][0][e] - mean; qq += d * d; }
-        qq += __shfl_xor(qq, 16);
-        qq += __shfl_xor(qq, 32);
-        if (SINGLE) {
-            const float rs = 1.0f / sqrtf(qq * invR + 1e-5f);      // biased variance, eps 1e-5 (InstanceNorm1d defaults)
-            if (kg == 0) rstd_clip[col] = rs;
-#pragma unroll
-            for (int m = 0; m < MT; ++m)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int row = m * 16 + 4 * kg + e;
-                    const float u = (acc[m][0][e] - mean) * rs;
-                    if (row < store_rows) C[(size_t)(bm + row) * ldc + col] = row < rows ? (u > 0.f ? u : 0.2f * u) : 0.f;
-                }
-        } else {
-            // raw conv output now, statistics merged across the clip's chunks (Chan et al.)
-#pragma unroll
-            for (int m = 0; m < MT; ++m)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int row = m * 16 + 4 * kg + e;
-                    if (row < store_rows) C[(size_t)(bm + row) * ldc + col] = row < rows ? acc[m][0][e] : 0.f;
-                }
-            const float nc = (float)rows, nt = st0 + nc, dl = mean - st1;
-            st2 = st2 + qq + dl * dl * (st0 * nc / nt);
-            st1 = st1 + dl * (nc / nt);
-            st0 = nt;
-        }
-    } else {      // X3_BWD
-        float s1 = 0.f, s2 = 0.f;
-        float u[MT][4];
-#pragma unroll
-        for (int m = 0; m < MT; ++m)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int row = m * 16 + 4 * kg + e;
-                const float av = act[(size_t)(bm + min(row, store_rows - 1)) * ldc + col];   // unconditional (clamped, masked below)
-                const bool valid = row < rows;
-                const float uv = valid ? (av > 0.f ? av : av * 5.0f) : 0.f;                 // invert LeakyReLU(0.2)
-                const float du = valid ? acc[m][0][e] * (av > 0.f ? 1.f : 0.2f) : 0.f;
-                acc[m][0][e] = du;
-                u[m][e] = uv;
-                s1 += du;
-                s2 += du * uv;
-            }
-        if (SINGLE) {
-            const float rs = rstd_clip[col];
-            s1 += __shfl_xor(s1, 16);
-            s1 += __shfl_xor(s1, 32);
-            s2 += __shfl_xor(s2, 16);
-            s2 += __shfl_xor(s2, 32);
-            const float m1 = s1 * invR, m2 = s2 * invR;
-#pragma unroll
-            for (int m = 0; m < MT; ++m)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int row = m * 16 + 4 * kg + e;
-                    if (row < store_rows) C[(size_t)(bm + row) * ldc + col] = row < rows ? rs * (acc[m][0][e] - m1 - u[m][e] * m2) : 0.f;
-                }
-        } else {
-#pragma unroll
-            for (int m = 0; m < MT; ++m)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int row = m * 16 + 4 * kg + e;
-                    if (row < store_rows) C[(size_t)(bm + row) * ldc + col] = acc[m][0][e];          // dU (zero in padding rows)
-                }
-            st1 += s1;
-            st2 += s2;
-        }
-    }
+    conv_block_uniform<X3Ops, RG, EPI>(A, lda, Bpk, nullptr, nullptr, nullptr, bias, C, ldc, Tp, N, K, tiles_n, ntiles, rstd_io,
+                                       act, Lpk, zpart, CL, Mrows);
 }
 
 template <int EPI>
@@ -625,112 +269,8 @@ __global__ __launch_bounds__(512, 4) void gemm_ragged_x3_kernel(const float* __r
                                                                 const int* __restrict__ frame_off, const int* __restrict__ pool_off,
                                                                 const int* __restrict__ order, int N, int K, int tiles_n, int ntiles,
                                                                 float* __restrict__ rstd_io, const float* __restrict__ act) {
-    // blocks b and b + 8 share an XCD (observed round-robin placement; speed only): the slabs of one clip stay on one XCD
-    // (its rows are read once into that L2), and clips are dealt to the XCDs round-robin -- batches arrive sorted by
-    // length, a contiguous range per XCD would give one XCD all the long clips
-    int clip, slab;
-    {
-        const int id = blockIdx.x, nclips = ntiles / tiles_n;
-        if ((nclips & 7) == 0) {
-            const int j = id >> 3;
-            clip = (j / tiles_n) * 8 + (id & 7);
-            slab = j % tiles_n;
-        } else {
-            clip = id / tiles_n;
-            slab = id % tiles_n;
-        }
-        if (order) clip = order[clip];                              // dispatch position -> clip: longest clips first
-    }
-    const int bn = slab * 128;
-    const int Tp = (frame_off[clip + 1] - frame_off[clip]) / 2;
-    const int row0 = pool_off[clip];
-    if (Tp < 1) return;
-    const int G = (Tp + 31) >> 5;                                   // 32-row groups of the clip
-    const int nchunk = (G + kRaggedRG - 1) / kRaggedRG;
-    const int gbase = G / nchunk, grem = G % nchunk;                // balanced: the first `grem` chunks take one group more
-    float* rstd_clip = rstd_io + (size_t)clip * N;
-    float st0 = 0.f, st1 = 0.f, st2 = 0.f;
-    const bool single = nchunk == 1;
-    int g0 = 0;
-    for (int c = 0; c < nchunk; ++c) {
-        const int ng = gbase + (c < grem ? 1 : 0);
-        const int bm = row0 + 32 * g0;
-        const int rows = min(32 * ng, Tp - 32 * g0);
-        if (c) __syncthreads();                                     // every wave is done with the previous chunk's staging memory
-        // two tile heights only (a one-group chunk runs as a two-group tile whose second group is padding: the K-order of
-        // every output element is the same at any tile height, so the results do not depend on the choice)
-        if (ng <= 2) x3_ragged_chunk<2, EPI>(single, A, lda, Bpk, bias, C, ldc, N, K, bm, rows, 32 * ng, bn, rstd_clip, act, st0, st1, st2);
-        else x3_ragged_chunk<3, EPI>(single, A, lda, Bpk, bias, C, ldc, N, K, bm, rows, 32 * ng, bn, rstd_clip, act, st0, st1, st2);
-        g0 += ng;
-    }
-    if (single) return;
-    // ---- pass 2 over the raw tile this workgroup wrote: ROW-MAJOR (lane = 4 consecutive columns, half a wave = one 512-byte
-    // row segment), the per-column statistics handed over through LDS.  In the accumulator's layout (the lane that wrote a
-    // value reads it back: 4 rows x 64 bytes per wave instruction) this pass streamed at about half the rate. ----
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int r16 = lane & 15, kg = lane >> 4;
-    const int col = bn + wave * 16 + r16;
-    const float invT = 1.0f / (float)Tp;
-    const int npad = 32 * G;
-    float* cstat = reinterpret_cast<float*>(x3_dyn_lds);           // [2][128]; the staging memory is free now
-    __syncthreads();                                                // ... once every wave has left its last chunk
-    if (EPI == X3_FWD) {
-        const float rs = 1.0f / sqrtf(st2 * invT + 1e-5f);
-        if (kg == 0) { rstd_clip[col] = rs; cstat[wave * 16 + r16] = st1; cstat[128 + wave * 16 + r16] = rs; }
-    } else {
-        float s1 = st1, s2 = st2;
-        s1 += __shfl_xor(s1, 16);
-        s1 += __shfl_xor(s1, 32);
-        s2 += __shfl_xor(s2, 16);
-        s2 += __shfl_xor(s2, 32);
-        if (kg == 0) { cstat[wave * 16 + r16] = s1 * invT; cstat[128 + wave * 16 + r16] = s2 * invT; }
-    }
-    __syncthreads();                                                // statistics in LDS; every wave's raw rows are visible
-    const int c4 = (lane & 31) * 4, rr = 2 * wave + (lane >> 5);
-    const float4 q0 = *reinterpret_cast<const float4*>(cstat + c4), q1 = *reinterpret_cast<const float4*>(cstat + 128 + c4);
-    float* const Cw = C + (size_t)row0 * ldc + bn + c4;
-    if (EPI == X3_FWD) {
-        for (int r0 = rr; r0 < npad; r0 += 64) {                    // four rows per lane in flight
-            float4 z[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) z[j] = *reinterpret_cast<const float4*>(Cw + (size_t)min(r0 + 16 * j, npad - 1) * ldc);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int r = r0 + 16 * j;
-                if (r >= npad) continue;
-                auto f = [&](float v, float mean, float rs) {
-                    const float u = (v - mean) * rs;
-                    return (r < Tp) ? (u > 0.f ? u : 0.2f * u) : 0.f;
-                };
-                *reinterpret_cast<float4*>(Cw + (size_t)r * ldc) =
-                    make_float4(f(z[j].x, q0.x, q1.x), f(z[j].y, q0.y, q1.y), f(z[j].z, q0.z, q1.z), f(z[j].w, q0.w, q1.w));
-            }
-        }
-    } else {
-        const float4 rs4 = *reinterpret_cast<const float4*>(rstd_clip + bn + c4);
-        const float* const Aw = act + (size_t)row0 * ldc + bn + c4;
-        for (int r0 = rr; r0 < npad; r0 += 64) {
-            float4 du[4], av[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const size_t o = (size_t)min(r0 + 16 * j, npad - 1) * ldc;
-                du[j] = *reinterpret_cast<const float4*>(Cw + o);
-                av[j] = *reinterpret_cast<const float4*>(Aw + o);
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int r = r0 + 16 * j;
-                if (r >= npad) continue;
-                auto f = [&](float d, float a, float rs, float m1, float m2) {
-                    const float uv = a > 0.f ? a : a * 5.0f;
-                    return (r < Tp) ? rs * (d - m1 - uv * m2) : 0.f;
-                };
-                *reinterpret_cast<float4*>(Cw + (size_t)r * ldc) =
-                    make_float4(f(du[j].x, av[j].x, rs4.x, q0.x, q1.x), f(du[j].y, av[j].y, rs4.y, q0.y, q1.y),
-                                f(du[j].z, av[j].z, rs4.z, q0.z, q1.z), f(du[j].w, av[j].w, rs4.w, q0.w, q1.w));
-            }
-        }
-    }
+    conv_block_ragged<X3Ops, EPI>(A, lda, Bpk, nullptr, nullptr, nullptr, bias, C, ldc, frame_off, pool_off, order, N, K, tiles_n,
+                                  ntiles, rstd_io, act);
 }
 
 // epi: 1 forward (conv + InstanceNorm + LeakyReLU), 2 backward (data gradient + InstanceNorm/LeakyReLU backward of the
@@ -739,7 +279,7 @@ void launch_gemm_ragged_x3(const float* A, int lda, const void* Bpk, const float
                            const int* frame_off, const int* pool_off, const int* order, int N, int K, int epi, float* rstd_io,
                            const float* act, hipStream_t st) {
     const int tn = N / 128;
-    constexpr size_t kLds = 2 * 2 * 3 * (2 * kRaggedRG) * 1024;      // two K tiles of the tallest chunk
+    constexpr size_t kLds = ragged_lds_bytes<X3Ops>();
     if (epi == X3_FWD)
         hipLaunchKernelGGL((gemm_ragged_x3_kernel<X3_FWD>), dim3(tn * B), dim3(512), kLds, st, A, lda, (const u32x4*)Bpk, bias, C, ldc,
                            frame_off, pool_off, order, N, K, tn, tn * B, rstd_io, act);
@@ -913,7 +453,7 @@ void launch_gemm_clip_x3(const float* A, int lda, const void* Bpk, const float* 
         return;
     }
     if (epi == X3_FWD && lastpk && zpart) epi = X3_FWD_LAST;
-#define XK(M_, E_) hipLaunchKernelGGL((gemm_clip_x3_kernel<M_, E_, 8>), dim3(tn * B), dim3(512), 0, st, A, lda,          \
+#define XK(M_, E_) hipLaunchKernelGGL((gemm_clip_x3_kernel<M_, E_>), dim3(tn * B), dim3(512), 0, st, A, lda,          \
                                       (const u32x4*)Bpk, bias, C, ldc, Tp, N, K, tn, tn * B, rstd_io, act,                \
                                       (const u32x4*)lastpk, zpart, CL, Mrows)
 #define XM(E_) switch (nwm) { case 1: XK(1, E_); break; case 2: XK(2, E_); break; case 3: XK(3, E_); break; default: XK(4, E_); break; }

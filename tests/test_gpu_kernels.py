@@ -76,7 +76,7 @@ def _block_reference(a, w, bias, act, rstd, B, RP, Tp, epi):
 
 
 # grids below 128 workgroups (B * N/128) run gemm_clip_x3_small_kernel, the latency variant; the others run
-# gemm_clip_x3_kernel<RG, EPI, 8>, the throughput kernel the bench times: plain tile walk when B * N/128 is not a multiple
+# gemm_clip_x3_kernel<RG, EPI>, the throughput kernel the bench times: plain tile walk when B * N/128 is not a multiple
 # of 8 (B = 21), slab-group-major walk otherwise; RG = 1..4 (Tp = 31, 63, 94, 128); the bench's own three forward shapes
 # and two data-gradient shapes at B = 256 / 64 / 40.
 X3_SMALL = [(5, 94, 512, 128, 1), (3, 94, 1024, 512, 1), (4, 94, 1024, 1024, 2), (2, 31, 128, 64, 0),
@@ -173,7 +173,7 @@ def test_gemm_clip_h2_wide_dynamic_range(rt, B, Tp, N, K, epi, arange, wrange):
 @pytest.mark.parametrize("B,Tp,N,K,CL", [(16, 94, 1024, 1024, 40), (21, 94, 1024, 1024, 40), (64, 94, 1024, 1024, 40),
                                          (32, 63, 1024, 512, 40), (40, 94, 512, 256, 32), (128, 31, 1024, 128, 16)])
 def test_gemm_clip_last_partials(rt, B, Tp, N, K, CL):
-    """gemm_clip_x3_kernel<RG, X3_FWD_LAST, 8> -- block 2 of the embed loop: conv + InstanceNorm + LeakyReLU AND the split-K
+    """gemm_clip_x3_kernel<RG, X3_FWD_LAST> -- block 2 of the embed loop: conv + InstanceNorm + LeakyReLU AND the split-K
     partials of the skinny last conv from the output tile -- against fp64 (conv1d.py:38-42, multibit_detector_net.py:58-70)."""
     RP = 32 * ((Tp + 31) // 32)
     g = torch.Generator().manual_seed(B + Tp + N + K + CL)
@@ -857,7 +857,7 @@ def _oracle_first_iteration(O, emb, clip, wm_row):
                                         (33000, 193, [0, 64, 192])])                      # 129 frames: RG = 3, odd T
 def test_first_iteration_gradient_large_uniform_batch(rt, plan, det, O, n, B, sample):
     """The bench's own kernels under the oracle: a uniform batch of >= 192 clips runs mel_front_x3_kernel,
-    gemm_clip_x3_kernel<RG, FWD / FWD_LAST / BWD, 8> (slab-group-major walk when B % 8 == 0), readout_head_x3_kernel,
+    gemm_clip_x3_kernel<RG, FWD / FWD_LAST / BWD> (slab-group-major walk when B % 8 == 0), readout_head_x3_kernel,
     readout_grad_x3_kernel and mel_back_x3_kernel.  Loss, prediction and dL/dcoef of a sample of the clips against torch
     autograd on the oracle (multibit_embedder.py:95-111, multibit_detector_net.py:109-140, conv1d.py:38-42): 5e-5
     relative L2, kink-aware as in test_first_iteration_gradient."""
