@@ -5,8 +5,9 @@
 //
 // An operand-format policy P provides:
 //   kScaled        false (x3): the products are the values.  true (h2): the clip's scale comes from the producer's partial
-//                  maxima (amax_in), the epilogue multiplies by unscale = 2^-sa * binv[col], and the output's partial maxima go
-//                  to amax_out for the next GEMM;
+//                  maxima (amax_in), the epilogue multiplies by 2^-sa and then by binv[col] (two exact steps: their product
+//                  underflows for a tiny clip against a small weight row while the output is still a normal number), and the
+//                  output's partial maxima go to amax_out for the next GEMM;
 //   kWeightBytes   packed bytes per weight (the slab-group size of the uniform walk);
 //   kTerms         A terms staged in LDS (the staging buffer of one K tile is 2 kTerms MT KiB);
 //   tile_gemm<RG>  the K loop: acc[m][0] = A[bm + 16 m ..][0..K) * B^T for the wave's 16 columns (scaled by ascale when kScaled);
@@ -80,7 +81,7 @@ __device__ __forceinline__ void conv_block_uniform(const float* __restrict__ A, 
     const int r16 = lane & 15, kg = lane >> 4;
     const int col = bn + wave * 16 + r16;
 
-    float ascale = 1.f, unscale = 1.f;
+    float ascale = 1.f, ainv = 1.f, bcol = 1.f;
     if constexpr (P::kScaled) {
         // the clip's scale from the producer's partial maxima (K/16 of them: one per wave of each of its workgroups)
         float am = lane < (K >> 4) ? amax_in[(size_t)clip * 64 + lane] : 0.f;
@@ -94,7 +95,7 @@ __device__ __forceinline__ void conv_block_uniform(const float* __restrict__ A, 
                               (!P::kScaled && EPI == X3_PLAIN) ? min(32 * RG, Mrows - bm) : 32 * RG, ascale);
 
     // ---- epilogue: lane holds rows m*16 + 4*kg + e (e = 0..3) of column col ----
-    if constexpr (P::kScaled) unscale = P::pow2_inverse(ascale) * binv[col];
+    if constexpr (P::kScaled) { ainv = P::pow2_inverse(ascale); bcol = binv[col]; }
     const float invT = 1.0f / (float)Tp;
     float omax = 0.f;                                   // max |output| of this wave's 16 columns, for the next GEMM's scale
     if constexpr (!P::kScaled && EPI == X3_PLAIN) {
@@ -130,7 +131,7 @@ __device__ __forceinline__ void conv_block_uniform(const float* __restrict__ A, 
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const int row = m * 16 + 4 * kg + e;
-                const float o = row < Tp ? acc[m][0][e] * unscale + bv : 0.f;
+                const float o = row < Tp ? fmaf(acc[m][0][e] * ainv, bcol, bv) : 0.f;
                 omax = fmaxf(omax, fabsf(o));
                 if (P::kScaled || bm + row < Mrows) C[(size_t)(bm + row) * ldc + col] = o;
             }
@@ -142,7 +143,7 @@ __device__ __forceinline__ void conv_block_uniform(const float* __restrict__ A, 
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const int row = m * 16 + 4 * kg + e;
-                acc[m][0][e] = acc[m][0][e] * unscale + bv;
+                acc[m][0][e] = fmaf(acc[m][0][e] * ainv, bcol, bv);
                 if (row < Tp) s += acc[m][0][e];
             }
         s += __shfl_xor(s, 16);
@@ -197,7 +198,7 @@ __device__ __forceinline__ void conv_block_uniform(const float* __restrict__ A, 
                 const float av = act[(size_t)(bm + row) * ldc + col];
                 const bool valid = row < Tp;
                 const float uv = valid ? (av > 0.f ? av : av * 5.0f) : 0.f;                 // invert LeakyReLU(0.2)
-                const float du = valid ? acc[m][0][e] * unscale * (av > 0.f ? 1.f : 0.2f) : 0.f;
+                const float du = valid ? acc[m][0][e] * ainv * bcol * (av > 0.f ? 1.f : 0.2f) : 0.f;
                 acc[m][0][e] = du;
                 u[m][e] = uv;
                 s1 += du;
@@ -333,8 +334,8 @@ __device__ __forceinline__ T* uniform_ptr(T* p) {
 
 // one chunk: rows [bm, bm + 32 RG) of which `rows` are valid.  SINGLE: the clip is this chunk.
 // st0/st1/st2: forward (count, mean, M2) of the column; backward (unused, sum dU, sum dU*u) in-lane partial sums;
-// ascale / unscale / omax (kScaled only): the clip's scale, the epilogue's factor, the running max |stored value| of this
-// lane's column (single-pass clips).
+// ascale / ainv / bcol / omax (kScaled only): the clip's scale, the epilogue's two factors (2^-sa, binv[col]), the running
+// max |stored value| of this lane's column (single-pass clips).
 // (not inlined: each tile height keeps its own register allocation -- inlined side by side the two K loops cost the
 // kernel 20-40 spilled VGPRs inside the loop)
 template <class P, int RG, int EPI>
@@ -342,7 +343,7 @@ __device__ __attribute__((noinline)) void ragged_chunk(const bool SINGLE, const 
                                                        const u32x4* __restrict__ Bpk, const float* __restrict__ bias,
                                                        float* __restrict__ C, int ldc, int N, int K, int bm, int rows,
                                                        int store_rows, int bn, float* __restrict__ rstd_clip,
-                                                       const float* __restrict__ act, float ascale, float unscale, float& st0,
+                                                       const float* __restrict__ act, float ascale, float ainv, float bcol, float& st0,
                                                        float& st1, float& st2, float& omax) {
     unsigned char* lds = conv_dyn_lds;
     // the arguments of a non-inlined function arrive in VGPRs; all of these are wave-uniform and go back to SGPRs (the K
@@ -355,7 +356,7 @@ __device__ __attribute__((noinline)) void ragged_chunk(const bool SINGLE, const 
     rows = __builtin_amdgcn_readfirstlane(rows); store_rows = __builtin_amdgcn_readfirstlane(store_rows);
     // rows: valid rows of the chunk; store_rows (a multiple of 32, <= 32 RG): rows of the clip's allocation under this tile
     if constexpr (P::kScaled) ascale = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(ascale)));
-    else unscale = 1.f;
+    else { ainv = 1.f; bcol = 1.f; }
     constexpr int MT = 2 * RG;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int r16 = lane & 15, kg = lane >> 4;
@@ -371,7 +372,7 @@ __device__ __attribute__((noinline)) void ragged_chunk(const bool SINGLE, const 
         for (int m = 0; m < MT; ++m)
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                acc[m][0][e] = acc[m][0][e] * unscale + bv;
+                acc[m][0][e] = fmaf(acc[m][0][e] * ainv, bcol, bv);
                 if (m * 16 + 4 * kg + e < rows) s += acc[m][0][e];
             }
         s += __shfl_xor(s, 16);
@@ -425,7 +426,7 @@ __device__ __attribute__((noinline)) void ragged_chunk(const bool SINGLE, const 
                 const float av = act[(size_t)(bm + min(row, store_rows - 1)) * ldc + col];   // unconditional (clamped, masked below)
                 const bool valid = row < rows;
                 const float uv = valid ? (av > 0.f ? av : av * 5.0f) : 0.f;                 // invert LeakyReLU(0.2)
-                const float du = valid ? acc[m][0][e] * unscale * (av > 0.f ? 1.f : 0.2f) : 0.f;
+                const float du = valid ? acc[m][0][e] * ainv * bcol * (av > 0.f ? 1.f : 0.2f) : 0.f;
                 acc[m][0][e] = du;
                 u[m][e] = uv;
                 s1 += du;
@@ -493,13 +494,14 @@ __device__ __forceinline__ void conv_block_ragged(const float* __restrict__ A, i
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int r16 = lane & 15, kg = lane >> 4;
     const int col = bn + wave * 16 + r16;
-    float ascale = 1.f, unscale = 1.f;
+    float ascale = 1.f, ainv = 1.f, bcol = 1.f;
     if constexpr (P::kScaled) {
         float am = lane < (K >> 4) ? amax_in[(size_t)clip * 64 + lane] : 0.f;
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) am = fmaxf(am, __shfl_xor(am, o));
         ascale = P::scale_for(am);
-        unscale = P::pow2_inverse(ascale) * binv[col];
+        ainv = P::pow2_inverse(ascale);
+        bcol = binv[col];
     }
     const int G = (Tp + 31) >> 5;                                   // 32-row groups of the clip
     const int nchunk = (G + kRaggedRG - 1) / kRaggedRG;
@@ -515,8 +517,8 @@ __device__ __forceinline__ void conv_block_ragged(const float* __restrict__ A, i
         if (c) __syncthreads();                                     // every wave is done with the previous chunk's staging memory
         // two tile heights only (a one-group chunk runs as a two-group tile whose second group is padding: the K-order of
         // every output element is the same at any tile height, so the results do not depend on the choice)
-        if (ng <= 2) ragged_chunk<P, 2, EPI>(single, A, lda, Bpk, bias, C, ldc, N, K, bm, rows, 32 * ng, bn, rstd_clip, act, ascale, unscale, st0, st1, st2, omax);
-        else ragged_chunk<P, 3, EPI>(single, A, lda, Bpk, bias, C, ldc, N, K, bm, rows, 32 * ng, bn, rstd_clip, act, ascale, unscale, st0, st1, st2, omax);
+        if (ng <= 2) ragged_chunk<P, 2, EPI>(single, A, lda, Bpk, bias, C, ldc, N, K, bm, rows, 32 * ng, bn, rstd_clip, act, ascale, ainv, bcol, st0, st1, st2, omax);
+        else ragged_chunk<P, 3, EPI>(single, A, lda, Bpk, bias, C, ldc, N, K, bm, rows, 32 * ng, bn, rstd_clip, act, ascale, ainv, bcol, st0, st1, st2, omax);
         g0 += ng;
     }
     if (single) {

@@ -45,10 +45,14 @@ static inline size_t h2_plane_bytes(int N, int K) { return (size_t)N * (size_t)(
 size_t h2_packed_bytes(int N, int K) { return h2_plane_bytes(N, K) + (size_t)N * sizeof(float); }
 const float* h2_inv_scale(const void* packed, int N, int K) { return (const float*)((const char*)packed + h2_plane_bytes(N, K)); }
 
-// power-of-two scale that brings a maximum magnitude `amax` into [2^13, 2^14); 1 for zero / tiny maxima
+// power-of-two scale that brings a maximum magnitude `amax` into [2^13, 2^14), at most 2^126 (so that its inverse is a normal
+// number): maxima below 2^-113 -- zero and subnormal f32 included -- get 2^126 and land below 2^13.  h + l then still holds
+// every f32 value to within one unit in its last place, as above: a subnormal value is a multiple of 2^-149, i.e. of 2^-23
+// after the scale, on or next to binary16's subnormal grid (2^-24).  (A scale of 1 for maxima below 2^-107 rounded such clips
+// and weight rows to h = l = 0: the block put out its bias alone.)
 __device__ __forceinline__ float h2_scale_for(float amax) {
     const int e = (int)((__float_as_uint(amax) >> 23) & 0xFFu);
-    return e < 20 ? 1.0f : __uint_as_float((unsigned)(267 - e) << 23);
+    return __uint_as_float((unsigned)(267 - max(e, 14)) << 23);
 }
 __device__ __forceinline__ float h2_pow2_inverse(float s) {            // s is a power of two
     const unsigned e = (__float_as_uint(s) >> 23) & 0xFFu;

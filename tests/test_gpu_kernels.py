@@ -432,8 +432,8 @@ def test_embed_full_1s_bits_exact(rt, plan, det, O):
 def test_first_iteration_x3_vs_f32_pipe(rt, plan, det, O, nclips):
     """Whole first loop body with the conv blocks on the three matrix pipes -- f16 two-term (default; takes the conv blocks
     from 32 clips on, below that it is the bf16x3 configuration), bf16 three-term, f32-input MFMA: loss, prediction and
-    dL/dcoef agree to f32 rounding.  (40 clips: the f16 kernel with its scales from the clip_amax pre-pass, the mel block in
-    two launches.)"""
+    dL/dcoef agree to f32 rounding: 2e-5 relative L2 per clip, 2e-2 on a clip with a LeakyReLU argument within 2e-6 of its kink.
+    (40 clips: the f16 kernel with its scales from the clip_amax pre-pass, the mel block in two launches.)"""
     lengths = [48000] * nclips
     pairs = [make_clip(40 + i, n) for i, n in enumerate(lengths)]
     wm = np.stack([O.bits_to_bipolar(p[1]) for p in pairs]).astype(np.float32)
@@ -446,17 +446,24 @@ def test_first_iteration_x3_vs_f32_pipe(rt, plan, det, O, nclips):
         torch.cuda.synchronize()
         res[pipe] = (g.cpu().double(), sess.loss.cpu().numpy().copy(), sess.pred.cpu().numpy().copy())
     g0, l0, p0 = res["f32"]
+    emb = O.Embedder()
+    kinks = []
+    for c, _ in pairs:
+        mag0, phase = emb.analyse(torch.from_numpy(c)[None])
+        kinks.append(_min_kink_distance(emb, mag0, phase))
+    kinks = np.asarray(kinks)
     for pipe in ("f16x2", "bf16x3"):
         g4, l4, p4 = res[pipe]
         assert np.max(np.abs(l4 - l0)) < 2e-6
         assert np.max(np.abs(p4 - p0)) < 2e-6
         sl = [slice(batch.frame_offsets[i], batch.frame_offsets[i + 1]) for i in range(nclips)]
         rel = np.asarray([((g4[s_] - g0[s_]).norm() / g0[s_].norm()).item() for s_ in sl])
-        print(f"relative L2 difference of the gradients per clip, {pipe} vs f32 MFMA: median {np.median(rel):.2e} max {rel.max():.2e}")
-        # A clip with a LeakyReLU argument within rounding of its kink may take the other sub-gradient: isolated, finite.  Expected
-        # count: 244 000 pre-activations per clip, standard normal, the pipes 2e-7 apart -> about 0.04 flips per clip, Poisson
-        # mean 1.6 at 40 clips; the bound is its 99.5 % quantile (5), not "at most two" (which fails one run in five).
-        assert np.median(rel) < 2e-5 and int((rel > 2e-5).sum()) <= max(2, nclips // 8), rel
+        print(f"relative L2 difference of the gradients per clip, {pipe} vs f32 MFMA: median {np.median(rel):.2e} max {rel.max():.2e}; "
+              f"clips within 2e-6 of a LeakyReLU kink: {int((kinks <= 2e-6).sum())}")
+        # A clip with a LeakyReLU argument within rounding of its kink may take the other sub-gradient there: finite, and only
+        # on such a clip (kink-aware per clip as test_ragged_fused_conv_blocks; no count-based allowance)
+        bad = [(i, rel[i], kinks[i]) for i in range(nclips) if not rel[i] < (2e-5 if kinks[i] > 2e-6 else 2e-2)]
+        assert not bad, (pipe, bad)
 
 
 @pytest.mark.parametrize("lengths", [[48000] * 6, [16000, 52000, 31000, 48000], [160000, 20000]])
