@@ -14,7 +14,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AWARE_HIP_LIB") or os.path.join(_HERE, "libaware_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["capi.hip", "dsp_kernels.hip", "dsp_stream.hip", "seam_kernels.hip", "detector_kernels.hip", "gemm_x3.hip", "gemm_h2.hip", "attack_kernels.hip"]
+SOURCES = ["capi.hip", "dsp_kernels.hip", "dsp_stream.hip", "seam_kernels.hip", "detector_kernels.hip", "gemm_x3.hip", "gemm_h2.hip", "attack_kernels.hip", "stft_any.hip"]
 
 AWARE_OK = 0
 ERRORS = {-1: "bad argument", -2: "unsupported configuration", -3: "HIP runtime error", -4: "workspace too small"}
@@ -82,6 +82,10 @@ SIGNATURES = {
     "aware_last_hip_error": (C.c_char_p, []),
     "aware_plan_create": (_i, [C.POINTER(_vp), _i, _i, _i, _i, _i, _i]),
     "aware_plan_destroy": (None, [_vp]),
+    "aware_plan_create_ex": (_i, [C.POINTER(_vp), _i, _i, _i, _i, _i, _i, _i]),
+    "aware_plan_spectrum_stride": (_i, [_vp]),
+    "aware_plan_is_general": (_i, [_vp]),
+    "aware_nola_check": (_i, [_i, _i, _i, _i, _i]),
     "aware_batch_create": (_i, [C.POINTER(_vp), _i, _pi, _pi]),
     "aware_batch_destroy": (None, [_vp]),
     "aware_batch_total_frames": (_i, [_vp]),
@@ -90,6 +94,7 @@ SIGNATURES = {
     "aware_batch_out_offset": (_i, [_vp, _i]),
     "aware_batch_out_length": (_i, [_vp, _i]),
     "aware_batch_frames": (_i, [_vp, _i]),
+    "aware_batch_create_for_plan": (_i, [C.POINTER(_vp), _vp, _i, _pi, _pi]),
     "aware_batch_scratch_bytes": (_sz, [_vp]),
     "aware_stft": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "aware_istft": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp]),

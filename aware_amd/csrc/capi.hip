@@ -56,6 +56,12 @@ static int absmax_into_scratch(const float* in, const int* off, const int* len, 
 struct aware_plan {
     PlanDev dev;
     void* mem = nullptr;
+    // general-geometry plans (stft_any.hip): every geometry other than the card's, or any geometry created with
+    // AWARE_PLAN_GENERAL.  Only the four transform entry points accept them.
+    int general = 0;
+    int n_fft = kNfft, hop = kHop, win_length = kNfft, window = 0;
+    GenPlanDev gdev;
+    std::vector<float> w2h, envh;       // host copies of the squared window and the envelope tables (NOLA check)
 };
 
 struct aware_batch {
@@ -75,6 +81,12 @@ struct aware_batch {
     std::vector<int> an_wg, syn_wg;
     int* d_order = nullptr;            // clips longest first (dispatch order of the ragged GEMM: short clips fill the tail)
     std::vector<int> order;
+    // batch built by aware_batch_create_for_plan for a general plan: its geometry, whether every clip passes the NOLA
+    // condition, and the frame buffer of the synthesis direction [NF][n_fft] floats
+    int general = 0;
+    int g_nfft = 0, g_hop = 0, g_win = 0, g_window = 0, nola_ok = 1;
+    int* d_pc_out = nullptr;
+    float* d_frames = nullptr;
 };
 
 struct aware_detector {
@@ -112,14 +124,120 @@ struct aware_detector {
     unsigned char* melf_s = nullptr;
 };
 
-extern "C" int aware_version(void) { return 300; }
+extern "C" int aware_version(void) { return 310; }
 extern "C" const char* aware_last_hip_error(void) { return g_last_err.c_str(); }
 
 // ---------------------------------------------------------------------------------------------
+// ---- general-geometry tables (host) ----
+static bool gen_nfft_supported(int n) { return n == 256 || n == 512 || n == 1024 || n == 2048 || n == 4096; }
+static int gen_stride(int n_fft) { return (n_fft / 2 + 1 + 7) & ~7; }
+
+// torch.hann_window / torch.hamming_window(win_length) (periodic), zero-padded to n_fft with left pad
+// (n_fft - win_length) / 2 as torch.stft / torch.istft do; its square; the envelope tables of gen_env (kernels.h)
+static void gen_host_tables(int N, int hop, int win, int window, std::vector<float>& w, std::vector<float>& w2,
+                            std::vector<float>& env) {
+    const double PI = 3.14159265358979323846;
+    w.assign(N, 0.f);
+    w2.assign(N, 0.f);
+    const int lpad = (N - win) / 2;
+    for (int i = 0; i < win; ++i) {
+        const double c = cos(2 * PI * i / win);
+        w[lpad + i] = (float)(window == 0 ? 0.5 - 0.5 * c : 0.54 - 0.46 * c);
+    }
+    for (int i = 0; i < N; ++i) w2[i] = w[i] * w[i];
+    env.assign(N + hop + N / 2, 0.f);
+    const int big = N / hop + 2;                               // any T with T*hop >= N
+    for (int p = 0; p < N; ++p) env[p] = gen_env_loop(w2.data(), N, hop, p, big);
+    for (int r = 0; r < hop; ++r) env[N + r] = gen_env_loop(w2.data(), N, hop, N + ((r - N % hop) % hop + hop) % hop, big);
+    for (int q = 0; q < N / 2; ++q) env[N + hop + q] = gen_env_loop(w2.data(), N, hop, big * hop + q, big);
+}
+
+// torch.istft's NOLA condition for a clip of T frames: the envelope stays >= 1e-11 over the trimmed output
+// [N/2, N/2 + hop (T - 1)).  Interior positions repeat with period hop, so one period of them is checked.
+static bool gen_nola_ok(const float* env, const float* w2, int N, int hop, int T) {
+    const int lo = N / 2, hi = N / 2 + hop * (T - 1);
+    const bool tables = (long)T * hop >= N;
+    for (int p = lo; p < hi; ++p) {
+        if (tables && p == N + hop && p < T * hop) {
+            p = T * hop - 1;
+            continue;
+        }
+        if (!(gen_env(env, w2, N, hop, p, T) >= 1e-11f)) return false;
+    }
+    return true;
+}
+
+static int gen_validate(int n_fft, int hop, int win_length, int window) {
+    if (!gen_nfft_supported(n_fft)) return AWARE_E_UNSUPPORTED;
+    if (hop < 1 || hop > n_fft || win_length < 1 || win_length > n_fft || (window != 0 && window != 1)) return AWARE_E_BADARG;
+    return AWARE_OK;
+}
+
+static int gen_plan_create(aware_plan** out, int n_fft, int hop, int win_length, int window, int band_lo_bin,
+                           int band_hi_bin) {
+    const int rc = gen_validate(n_fft, hop, win_length, window);
+    if (rc != AWARE_OK) return rc;
+    const int N = n_fft, M = N / 2;
+    const double PI = 3.14159265358979323846;
+    std::vector<float> w, w2, env;
+    gen_host_tables(N, hop, win_length, window, w, w2, env);
+    // device image (floats, every part 16-byte aligned): th [M/2] cf, twN [M + 1 -> M + 2] cf, window, window2, env
+    std::vector<float> h;
+    auto put = [&](const float* src, size_t n) {
+        const size_t o = h.size();
+        h.insert(h.end(), src, src + n);
+        h.resize((h.size() + 3) & ~(size_t)3, 0.f);
+        return o;
+    };
+    std::vector<float> th(M), twN(2 * (M + 2), 0.f);
+    for (int j = 0; j < M / 2; ++j) {
+        th[2 * j] = (float)cos(2 * PI * j / M);
+        th[2 * j + 1] = (float)-sin(2 * PI * j / M);
+    }
+    for (int k = 0; k <= M; ++k) {
+        twN[2 * k] = (float)cos(2 * PI * k / N);
+        twN[2 * k + 1] = (float)-sin(2 * PI * k / N);
+    }
+    twN[0] = 1.f; twN[1] = 0.f;                   // exact at 0, -pi/2, -pi: DC and Nyquist come out purely real
+    twN[M] = 0.f; twN[M + 1] = -1.f;
+    twN[2 * M] = -1.f; twN[2 * M + 1] = 0.f;
+    const size_t o_th = put(th.data(), th.size()), o_tw = put(twN.data(), twN.size());
+    const size_t o_w = put(w.data(), w.size()), o_w2 = put(w2.data(), w2.size()), o_env = put(env.data(), env.size());
+    aware_plan* p = new aware_plan();
+    if (hipMalloc(&p->mem, h.size() * sizeof(float)) != hipSuccess ||
+        hipMemcpy(p->mem, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+        g_last_err = "aware_plan_create: device tables";
+        if (p->mem) (void)hipFree(p->mem);
+        delete p;
+        return AWARE_E_HIP;
+    }
+    const float* d = (const float*)p->mem;
+    p->general = 1;
+    p->n_fft = N; p->hop = hop; p->win_length = win_length; p->window = window;
+    p->gdev.n_fft = N; p->gdev.hop = hop; p->gdev.stride = gen_stride(N);
+    p->gdev.th = (const cf*)(d + o_th);
+    p->gdev.twN = (const cf*)(d + o_tw);
+    p->gdev.window = d + o_w;
+    p->gdev.window2 = d + o_w2;
+    p->gdev.env = d + o_env;
+    p->dev.band_lo = band_lo_bin;                 // (not used by the general kernels)
+    p->dev.nband = band_hi_bin - band_lo_bin + 1;
+    p->w2h = w2;
+    p->envh = env;
+    *out = p;
+    return AWARE_OK;
+}
+
 extern "C" int aware_plan_create(aware_plan** out, int n_fft, int hop, int win_length, int window, int band_lo_bin,
                                  int band_hi_bin) {
-    if (!out) return AWARE_E_BADARG;
-    if (n_fft != kNfft || hop != kHop || win_length != kNfft) return AWARE_E_UNSUPPORTED;
+    return aware_plan_create_ex(out, n_fft, hop, win_length, window, band_lo_bin, band_hi_bin, 0);
+}
+
+extern "C" int aware_plan_create_ex(aware_plan** out, int n_fft, int hop, int win_length, int window, int band_lo_bin,
+                                    int band_hi_bin, int flags) {
+    if (!out || (flags & ~AWARE_PLAN_GENERAL)) return AWARE_E_BADARG;
+    if (n_fft != kNfft || hop != kHop || win_length != kNfft || (flags & AWARE_PLAN_GENERAL))
+        return gen_plan_create(out, n_fft, hop, win_length, window, band_lo_bin, band_hi_bin);
     if (window != 0 && window != 1) return AWARE_E_BADARG;
     const int nband = band_hi_bin - band_lo_bin + 1;
     if (band_lo_bin < 1 || band_hi_bin > 511 || nband < 1 || nband > kFS) return AWARE_E_UNSUPPORTED;
@@ -172,6 +290,19 @@ extern "C" void aware_plan_destroy(aware_plan* p) {
     if (!p) return;
     if (p->mem) (void)hipFree(p->mem);
     delete p;
+}
+extern "C" int aware_plan_spectrum_stride(const aware_plan* p) {
+    return p ? (p->general ? p->gdev.stride : AWARE_FULL_STRIDE) : AWARE_E_BADARG;
+}
+extern "C" int aware_plan_is_general(const aware_plan* p) { return p ? p->general : AWARE_E_BADARG; }
+
+extern "C" int aware_nola_check(int n_fft, int hop, int win_length, int window, int n_samples) {
+    const int rc = gen_validate(n_fft, hop, win_length, window);
+    if (rc != AWARE_OK) return rc;
+    if (n_samples < 0) return AWARE_E_BADARG;
+    std::vector<float> w, w2, env;
+    gen_host_tables(n_fft, hop, win_length, window, w, w2, env);
+    return gen_nola_ok(env.data(), w2.data(), n_fft, hop, 1 + n_samples / hop) ? AWARE_OK : AWARE_E_BADARG;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -288,9 +419,78 @@ extern "C" int aware_batch_create(aware_batch** out, int B, const int* n_samples
     *out = b;
     return AWARE_OK;
 }
+static int gen_batch_create(aware_batch** out, const aware_plan* plan, int B, const int* n_samples, const int* in_offsets) {
+    const int N = plan->n_fft, hop = plan->hop;
+    for (int i = 0; i < B; ++i)
+        if (n_samples[i] <= N / 2) return AWARE_E_BADARG;      // torch.stft's reflect padding needs n > n_fft/2
+    aware_batch* b = new aware_batch();
+    b->general = 1;
+    b->g_nfft = N; b->g_hop = hop; b->g_win = plan->win_length; b->g_window = plan->window;
+    b->B = B;
+    b->n.assign(n_samples, n_samples + B);
+    b->in_off.resize(B); b->T.resize(B); b->frame_off.assign(B + 1, 0); b->pool_off.assign(B + 1, 0);
+    b->out_off.resize(B); b->out_len.resize(B); b->pc_in.resize(B); b->pc_syn.resize(B);
+    std::vector<int> pc_out(B);
+    long acc = 0;
+    int max_pc = 1;
+    for (int i = 0; i < B; ++i) {
+        const int n = n_samples[i], T = 1 + n / hop;
+        b->in_off[i] = in_offsets ? in_offsets[i] : (int)acc;
+        acc += n;
+        b->T[i] = T;
+        b->frame_off[i + 1] = b->frame_off[i] + T;
+        b->out_off[i] = hop * (b->frame_off[i] - i);
+        b->out_len[i] = hop * (T - 1);
+        b->pc_in[i] = (n + 4095) / 4096;
+        pc_out[i] = (b->out_len[i] + 4095) / 4096;
+        b->max_frames = std::max(b->max_frames, T);
+        b->max_len = std::max(b->max_len, n);
+        max_pc = std::max(max_pc, b->pc_in[i]);
+        b->nola_ok = b->nola_ok && gen_nola_ok(plan->envh.data(), plan->w2h.data(), N, hop, T);
+    }
+    b->NF = b->frame_off[B];
+    b->NS = hop * (b->NF - B);
+    b->pstride = max_pc;
+    const size_t ints = (size_t)(B + 1) + (size_t)B * 6;
+    if (hipMalloc((void**)&b->d_mem, ints * sizeof(int)) != hipSuccess ||
+        hipMalloc((void**)&b->d_frames, (size_t)b->NF * N * sizeof(float)) != hipSuccess) {
+        g_last_err = "aware_batch_create_for_plan: device memory";
+        aware_batch_destroy(b);
+        return AWARE_E_HIP;
+    }
+    int* d = b->d_mem;
+    auto up = [&](int*& dst, const std::vector<int>& v) -> hipError_t {
+        dst = d;
+        d += v.size();
+        return hipMemcpy(dst, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice);
+    };
+    hipError_t e = up(b->d_frame_off, b->frame_off);
+    if (e == hipSuccess) e = up(b->d_in_off, b->in_off);
+    if (e == hipSuccess) e = up(b->d_in_len, b->n);
+    if (e == hipSuccess) e = up(b->d_out_off, b->out_off);
+    if (e == hipSuccess) e = up(b->d_out_len, b->out_len);
+    if (e == hipSuccess) e = up(b->d_pc_in, b->pc_in);
+    if (e == hipSuccess) e = up(b->d_pc_out, pc_out);
+    if (e != hipSuccess) {
+        g_last_err = std::string("aware_batch_create_for_plan: ") + hipGetErrorString(e);
+        aware_batch_destroy(b);
+        return AWARE_E_HIP;
+    }
+    *out = b;
+    return AWARE_OK;
+}
+
+extern "C" int aware_batch_create_for_plan(aware_batch** out, const aware_plan* plan, int B, const int* n_samples,
+                                           const int* in_offsets) {
+    if (!out || !plan || B < 1 || !n_samples) return AWARE_E_BADARG;
+    if (!plan->general) return aware_batch_create(out, B, n_samples, in_offsets);
+    return gen_batch_create(out, plan, B, n_samples, in_offsets);
+}
+
 extern "C" void aware_batch_destroy(aware_batch* b) {
     if (!b) return;
     if (b->d_mem) (void)hipFree(b->d_mem);
+    if (b->d_frames) (void)hipFree(b->d_frames);
     delete b;
 }
 extern "C" int aware_batch_total_frames(const aware_batch* b) { return b ? b->NF : AWARE_E_BADARG; }
@@ -307,6 +507,53 @@ extern "C" int aware_batch_frames(const aware_batch* b, int i) {
 }
 extern "C" size_t aware_batch_scratch_bytes(const aware_batch* b) {
     return b ? (size_t)b->B * b->pstride * sizeof(unsigned long long) + 256 : 0;
+}
+
+// ---- general-geometry dispatch (stft_any.hip) ----
+static bool gen_batch_matches(const aware_plan* plan, const aware_batch* b) {
+    return b->general && b->g_nfft == plan->n_fft && b->g_hop == plan->hop && b->g_win == plan->win_length &&
+           b->g_window == plan->window;
+}
+static GenLaunch gen_launch(const aware_plan* plan, const aware_batch* b) {
+    GenLaunch L;
+    L.plan = plan->gdev;
+    L.B = b->B; L.NF = b->NF; L.max_len = b->max_len;
+    L.frame_off = b->d_frame_off;
+    L.sig_off = b->d_in_off; L.sig_len = b->d_in_len;
+    L.out_off = b->d_out_off; L.out_len = b->d_out_len;
+    L.pstride = b->pstride;
+    L.frames = b->d_frames;
+    return L;
+}
+static int gen_stft(const aware_plan* plan, const aware_batch* b, const float* audio, int normalize, void* spec,
+                    void* scratch, hipStream_t st) {
+    if (!gen_batch_matches(plan, b)) return AWARE_E_BADARG;
+    GenLaunch L = gen_launch(plan, b);
+    if (normalize) {
+        unsigned long long* pmax = (unsigned long long*)scratch;
+        launch_absmax_partials(audio, b->d_in_off, b->d_in_len, pmax, b->pstride, b->B, b->max_len, st);
+        LAUNCHCHK();
+        L.pmax = pmax; L.pcount = b->d_pc_in;
+    }
+    launch_gen_analysis(L, audio, spec, 0, st);
+    LAUNCHCHK();
+    return AWARE_OK;
+}
+static int gen_istft(const aware_plan* plan, const aware_batch* b, const void* spec, int normalize, float* out,
+                     void* scratch, hipStream_t st) {
+    if (!gen_batch_matches(plan, b) || !b->nola_ok) return AWARE_E_BADARG;
+    GenLaunch L = gen_launch(plan, b);
+    launch_gen_synthesis(L, spec, out, 0, st);
+    LAUNCHCHK();
+    if (normalize) {
+        unsigned long long* pmax = (unsigned long long*)scratch;
+        launch_absmax_partials(out, b->d_out_off, b->d_out_len, pmax, b->pstride, b->B, b->max_len, st);
+        LAUNCHCHK();
+        L.pmax = pmax; L.pcount = b->d_pc_out;
+        launch_gen_normalize(L, out, st);
+        LAUNCHCHK();
+    }
+    return AWARE_OK;
 }
 
 // The DSP kernels exist in two forms: streaming wave kernels (dsp_stream.hip; default wherever the band lies inside bins
@@ -342,6 +589,8 @@ extern "C" int aware_stft(const aware_plan* plan, const aware_batch* b, const fl
                           void* scratch, void* stream) {
     if (!plan || !b || !audio || !spec || (normalize && !scratch)) return AWARE_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
+    if (plan->general) return gen_stft(plan, b, audio, normalize, spec, scratch, st);
+    if (b->general) return AWARE_E_BADARG;
     unsigned long long* pmax = (unsigned long long*)scratch;
     if (normalize) {
         launch_absmax_partials(audio, b->d_in_off, b->d_in_len, pmax, b->pstride, b->B, b->max_len, st);
@@ -360,6 +609,8 @@ extern "C" int aware_stft(const aware_plan* plan, const aware_batch* b, const fl
 extern "C" int aware_stft_band(const aware_plan* plan, const aware_batch* b, const float* audio, int normalize,
                                float* mag, void* phasor, void* scratch, void* stream) {
     if (!plan || !b || !audio || (!mag && !phasor) || (normalize && !scratch)) return AWARE_E_BADARG;
+    if (plan->general) return AWARE_E_UNSUPPORTED;
+    if (b->general) return AWARE_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
     unsigned long long* pmax = (unsigned long long*)scratch;
     if (normalize) {
@@ -380,6 +631,8 @@ extern "C" int aware_istft(const aware_plan* plan, const aware_batch* b, const v
                            void* scratch, void* stream) {
     if (!plan || !b || !spec || !out || (normalize && !scratch)) return AWARE_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
+    if (plan->general) return gen_istft(plan, b, spec, normalize, out, scratch, st);
+    if (b->general) return AWARE_E_BADARG;
     unsigned long long* pmax = (unsigned long long*)scratch;
     SynthLaunch S;
     S.plan = plan->dev; S.frame_off = b->d_frame_off; S.B = b->B; S.max_frames = b->max_frames; S.run_blocks = b->synth_run; S.wg_tab = b->d_syn_wg; S.n_wg = b->n_syn_wg;
@@ -398,6 +651,13 @@ extern "C" int aware_istft(const aware_plan* plan, const aware_batch* b, const v
 extern "C" int aware_stft_bwd(const aware_plan* plan, const aware_batch* b, const void* grad_spec, float* grad_audio,
                               void* stream) {
     if (!plan || !b || !grad_spec || !grad_audio) return AWARE_E_BADARG;
+    if (plan->general) {
+        if (!gen_batch_matches(plan, b)) return AWARE_E_BADARG;
+        launch_gen_synthesis(gen_launch(plan, b), grad_spec, grad_audio, 1, (hipStream_t)stream);
+        LAUNCHCHK();
+        return AWARE_OK;
+    }
+    if (b->general) return AWARE_E_BADARG;
     // the staged synthesis kernel in adjoint mode: overlap-add of the windowed rfft adjoints, then the fold of the two reflect
     // pads for a clip of any length n > 512 at the clip's offset in the caller's ragged array
     if (b->synth_run > 0)
@@ -417,6 +677,13 @@ extern "C" int aware_stft_bwd(const aware_plan* plan, const aware_batch* b, cons
 extern "C" int aware_istft_bwd(const aware_plan* plan, const aware_batch* b, const float* grad_audio, void* grad_spec,
                                void* stream) {
     if (!plan || !b || !grad_audio || !grad_spec) return AWARE_E_BADARG;
+    if (plan->general) {
+        if (!gen_batch_matches(plan, b) || !b->nola_ok) return AWARE_E_BADARG;
+        launch_gen_analysis(gen_launch(plan, b), grad_audio, grad_spec, 1, (hipStream_t)stream);
+        LAUNCHCHK();
+        return AWARE_OK;
+    }
+    if (b->general) return AWARE_E_BADARG;
     AnalysisLaunch L;
     L.plan = plan->dev; L.frame_off = b->d_frame_off; L.B = b->B; L.max_frames = b->max_frames; L.run_frames = b->an_run; L.wg_tab = b->d_an_wg; L.n_wg = b->n_an_wg;
     L.sig = grad_audio; L.sig_off = b->d_out_off; L.sig_len = b->d_out_len;
@@ -594,6 +861,7 @@ extern "C" int aware_detector_create(aware_detector** out, const aware_plan* pla
                                      int n_layers, const int* channels, const float* const* weights,
                                      const float* const* biases) {
     if (!out || !plan || !mel_basis || !channels || !weights) return AWARE_E_BADARG;
+    if (plan->general) return AWARE_E_UNSUPPORTED;       // the detector runs on the card geometry only
     if (n_mels != 128 || n_layers < 1 || n_layers > 7 || channels[0] != n_mels) return AWARE_E_UNSUPPORTED;
     const int cl = channels[n_layers];
     if (cl % 2 || cl > 64) return AWARE_E_UNSUPPORTED;
@@ -841,7 +1109,7 @@ extern "C" size_t aware_detect_workspace_bytes(const aware_batch* b, const aware
 
 extern "C" int aware_detector_forward(const aware_detector* d, const aware_batch* b, const float* mag, float* values,
                                       void* workspace, size_t workspace_bytes, void* stream) {
-    if (!d || !b || !mag || !values || !workspace) return AWARE_E_BADARG;
+    if (!d || !b || b->general || !mag || !values || !workspace) return AWARE_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
     Carver c(workspace, workspace_bytes);
     DetBufs o;
@@ -862,6 +1130,8 @@ extern "C" int aware_detector_forward(const aware_detector* d, const aware_batch
 extern "C" int aware_detect(const aware_plan* plan, const aware_detector* d, const aware_batch* b, const float* audio,
                             float* values, void* workspace, size_t workspace_bytes, void* stream) {
     if (!plan || !d || !b || !audio || !values || !workspace) return AWARE_E_BADARG;
+    if (plan->general) return AWARE_E_UNSUPPORTED;
+    if (b->general) return AWARE_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
     Carver c(workspace, workspace_bytes);
     DetBufs o;
@@ -1059,7 +1329,7 @@ extern "C" size_t aware_detector_backward_workspace_bytes(const aware_batch* b, 
 extern "C" int aware_detector_backward(const aware_detector* d, const aware_batch* b, const float* mag,
                                        const float* grad_values, float* values, float* grad_mag, void* workspace,
                                        size_t workspace_bytes, void* stream) {
-    if (!d || !b || !mag || !grad_values || !grad_mag || !workspace) return AWARE_E_BADARG;
+    if (!d || !b || b->general || !mag || !grad_values || !grad_mag || !workspace) return AWARE_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
     Carver c(workspace, workspace_bytes);
     DetBufs o;
@@ -1115,6 +1385,7 @@ extern "C" int aware_detector_weight_gradients(const aware_detector* d, const aw
 static int detector_train_core(const aware_detector* d, const aware_batch* b, const float* mag, const float* target, int loss_kind,
                                float* loss_out, float* values, float* grad_mag, float* const* grad_weights,
                                float* const* grad_biases, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!d || !b || b->general) return AWARE_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
     Carver c(workspace, workspace_bytes);
     DetBufs o;
@@ -1271,6 +1542,8 @@ extern "C" int aware_embed_create(aware_embed** out, const aware_plan* plan, con
                                   const aware_batch* b, const aware_embed_config* cfg, void* workspace,
                                   size_t workspace_bytes, void* stream) {
     if (!out || !plan || !det || !b || !cfg || !workspace) return AWARE_E_BADARG;
+    if (plan->general) return AWARE_E_UNSUPPORTED;       // the embed loop runs on the card geometry only
+    if (b->general) return AWARE_E_BADARG;
     if (cfg->num_iterations < 1 || cfg->num_iterations > 4096 || cfg->loss < 0 || cfg->loss > AWARE_LOSS_PUSH_L1) return AWARE_E_BADARG;
     if (cfg->conv_pipe < 0 || cfg->conv_pipe > 2 || cfg->readout < 0 || cfg->readout > 1 || cfg->mel < 0 || cfg->mel > 1)
         return AWARE_E_BADARG;

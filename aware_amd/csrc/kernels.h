@@ -236,4 +236,54 @@ void launch_decimate_interp(const float* in, const int* off, const int* len, dou
 void launch_segment_copy(const float* in, const int* in_off, float* out, const int* out_off, const int* out_len,
                          const int* cut_start, const int* cut_len, int zero_fill, int B, int max_len, hipStream_t st);
 
+// ---- stft_any.hip: the general-geometry STFT path (any n_fft in 256..4096, hop, win_length) ------------------------
+struct GenPlanDev {
+    int n_fft = 0, hop = 0, stride = 0;   // stride: complex values per spectrum row (n_fft/2 + 1 rounded up to 8)
+    const cf* th = nullptr;               // W_M^j = exp(-2 pi i j / M), j < M/2 (M = n_fft/2)
+    const cf* twN = nullptr;              // exp(-2 pi i k / n_fft), k <= M
+    const float* window = nullptr;        // [n_fft] periodic window of win_length samples, zero-padded and centred
+    const float* window2 = nullptr;       // its square
+    const float* env = nullptr;           // overlap-add envelope: head [n_fft], interior [hop], tail [n_fft/2]
+};
+
+// Overlap-add envelope sum_t w^2[p - hop t] at padded position p of a clip of T frames, frames in ascending order.
+AW_HD float gen_env_loop(const float* w2, int N, int hop, int p, int T) {
+    const int tlo = p - N + 1 > 0 ? (p - N + hop) / hop : 0;
+    const int thi = (p / hop < T - 1) ? p / hop : T - 1;
+    float e = 0.f;
+    for (int t = tlo; t <= thi; ++t) e += w2[p - hop * t];
+    return e;
+}
+// The same value from the plan's tables (built with gen_env_loop): with T*hop >= N the envelope depends only on p
+// below N (head), on p mod hop in between (interior), and on p - T*hop from T*hop on (tail).
+AW_HD float gen_env(const float* env, const float* w2, int N, int hop, int p, int T) {
+    if ((long)T * hop < N) return gen_env_loop(w2, N, hop, p, T);
+    if (p < N) return env[p];
+    const int q = p - T * hop;
+    if (q >= 0) return env[N + hop + (q < N / 2 ? q : N / 2 - 1)];
+    return env[N + p % hop];
+}
+
+struct GenLaunch {
+    GenPlanDev plan;
+    int B = 0, NF = 0, max_len = 0;
+    const int* frame_off = nullptr;       // [B+1]
+    const int* sig_off = nullptr;         // clip signals (aware_stft input, aware_stft_bwd output)
+    const int* sig_len = nullptr;
+    const int* out_off = nullptr;         // istft-length signals (aware_istft output, aware_istft_bwd input)
+    const int* out_len = nullptr;
+    const unsigned long long* pmax = nullptr;   // per-clip |x| partial maxima (normalisation) or null
+    const int* pcount = nullptr;
+    int pstride = 0;
+    float* frames = nullptr;              // [NF][n_fft] windowed frames between the transform and the overlap-add
+};
+// analysis: frames -> window -> rFFT -> spectrum rows.  adjoint = 0: aware_stft (reflect pads, optional normaliser);
+// 1: aware_istft_bwd (the trimmed gradient over the envelope, irfft's adjoint weights on the bins)
+void launch_gen_analysis(const GenLaunch& L, const float* sig, void* spec, int adjoint, hipStream_t st);
+// synthesis: spectrum rows -> irFFT -> window -> L.frames, then overlap-add.  adjoint = 0: aware_istft (divide by the
+// envelope, trim); 1: aware_stft_bwd (no envelope, reflect pads folded back in)
+void launch_gen_synthesis(const GenLaunch& L, const void* spec, float* out, int adjoint, hipStream_t st);
+// out /= max|out| + 1e-8 per clip over the istft-length signals (L.pmax: partials of `out`)
+void launch_gen_normalize(const GenLaunch& L, float* out, hipStream_t st);
+
 }  // namespace aware

@@ -16,11 +16,12 @@ class AWAREDetector(BaseDetector):
     def __init__(self, model, threshold: float = 0.0, frame_length: int = 1024, hop_length: int = 256,
                  window: str = "hann", win_length: int = 1024, pattern_mode: str = "bits2bipolar",
                  embedding_bands=(500, 4000)):
+        rt.require_card_geometry("AWAREDetector", frame_length, hop_length, win_length)
         self.threshold = threshold
         self.device = torch.device("cuda")
         self.pattern_mode = pattern_mode
         self.embedding_bands = tuple(embedding_bands)
-        self.win_length = frame_length
+        self.win_length = win_length
         self.frame_length = frame_length
         self.hop_length = hop_length
         self.window = window
@@ -29,8 +30,9 @@ class AWAREDetector(BaseDetector):
                                           STFTDecomposer()]
 
     def _plan(self, sample_rate):
+        rt.require_card_geometry("AWAREDetector", self.frame_length, self.hop_length, self.win_length)
         return get_plan(self.frame_length, self.hop_length, self.window,
-                        band_bins(sample_rate, self.frame_length, self.embedding_bands))
+                        band_bins(sample_rate, self.frame_length, self.embedding_bands), win_length=self.win_length)
 
     def detect_batch(self, clips, sample_rate: int) -> torch.Tensor:
         """list of 1-D float arrays (any lengths) -> device tensor [B, n_bits] of raw values."""

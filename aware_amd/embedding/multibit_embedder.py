@@ -27,6 +27,7 @@ class AWAREEmbedder(BaseEmbedder):
                  pattern_mode: str = "bits2bipolar", embedding_bands=(500, 4000), tolerance_db: float = 6.0,
                  num_iterations: int = 400, detection_net_cfg: dict = None, optimizer_cfg: dict = None,
                  scheduler_cfg: dict = None, loss: str = "push", verbose: bool = True, use_graph: bool = True):
+        rt.require_card_geometry("AWAREEmbedder", frame_length, hop_length, win_length)
         self.frame_length, self.hop_length, self.window, self.win_length = frame_length, hop_length, window, win_length
         self.device = torch.device("cuda")
         self.embedding_bands = tuple(embedding_bands)
@@ -55,8 +56,9 @@ class AWAREEmbedder(BaseEmbedder):
         return allb[mask], allb[~mask]
 
     def _plan(self, sample_rate):
+        rt.require_card_geometry("AWAREEmbedder", self.frame_length, self.hop_length, self.win_length)
         return get_plan(self.frame_length, self.hop_length, self.window,
-                        band_bins(sample_rate, self.frame_length, self.embedding_bands))
+                        band_bins(sample_rate, self.frame_length, self.embedding_bands), win_length=self.win_length)
 
     # ---- batched hot path ----------------------------------------------------------------------
     def start_session(self, batch: "rt.Batch", sample_rate: int) -> "rt.EmbedSession":

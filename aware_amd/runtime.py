@@ -32,21 +32,68 @@ def _dev():
     return torch.device("cuda", torch.cuda.current_device())
 
 
-class Plan:
-    """FFT tables + window + embedding band (aware_plan)."""
+GENERAL_NFFT = (256, 512, 1024, 2048, 4096)
+PLAN_GENERAL = 1          # aware_plan_create_ex flag: the general kernels even for the card geometry
+WINDOWS = {"hann": 0, "hamming": 1}
 
-    def __init__(self, n_fft=1024, hop=256, win_length=1024, window="hann", band_bins=(32, 256)):
+
+def check_geometry(n_fft: int, hop: int, win_length: int, window: str = "hann"):
+    """The STFT geometries the library serves (no GPU needed): NotImplementedError for an n_fft outside
+    GENERAL_NFFT, ValueError for a hop / win_length outside 1..n_fft or an unknown window."""
+    if window not in WINDOWS:
+        raise ValueError(f"Invalid window type: {window}")       # utils/audio/stft.py:25
+    if int(n_fft) not in GENERAL_NFFT:
+        raise NotImplementedError(f"n_fft = {n_fft} is not supported: the HIP STFT kernels serve n_fft in {GENERAL_NFFT}")
+    if not 1 <= int(hop) <= int(n_fft):
+        raise ValueError(f"hop_length must lie in 1..n_fft = {n_fft}, got {hop}")
+    if not 1 <= int(win_length) <= int(n_fft):
+        raise ValueError(f"win_length must lie in 1..n_fft = {n_fft}, got {win_length}")
+
+
+def nola_ok(n_fft: int, hop: int, win_length: int, window: str, n_samples: int) -> bool:
+    """torch.istft's NOLA condition for a clip of n_samples samples (host-side, aware_nola_check): False where torch.istft
+    raises because the window's overlap-add envelope drops below 1e-11 inside the trimmed output."""
+    check_geometry(n_fft, hop, win_length, window)
+    rc = load_library().aware_nola_check(int(n_fft), int(hop), int(win_length), WINDOWS[window], int(n_samples))
+    if rc not in (0, -1):
+        check(rc, "aware_nola_check")
+    return rc == 0
+
+
+CARD_GEOMETRY = (1024, 256, 1024)
+
+
+def require_card_geometry(who: str, n_fft: int, hop: int, win_length: int):
+    """The embed / detect loop runs on the model card's STFT geometry only (the general path serves the transforms)."""
+    if (int(n_fft), int(hop), int(win_length)) != CARD_GEOMETRY:
+        raise NotImplementedError(f"{who}: frame_length / hop_length / win_length {n_fft} / {hop} / {win_length} is not "
+                                  f"supported; the embed and detect kernels run on the model card's geometry "
+                                  f"{CARD_GEOMETRY[0]} / {CARD_GEOMETRY[1]} / {CARD_GEOMETRY[2]} only")
+
+
+class Plan:
+    """FFT tables + window + embedding band (aware_plan).  The card geometry (1024 / 256 / 1024) gives the plan of the
+    embed / detect loop; any other supported geometry (or general=True) a general plan, which serves stft / istft /
+    stft_bwd / istft_bwd only (spectra of `spectrum_stride` complex values per row)."""
+
+    def __init__(self, n_fft=1024, hop=256, win_length=1024, window="hann", band_bins=(32, 256), general=False):
         require_gpu()
         self.lib = load_library()
-        wid = {"hann": 0, "hamming": 1}.get(window)
+        wid = WINDOWS.get(window)
         if wid is None:
             raise ValueError(f"Invalid window type: {window}")       # utils/audio/stft.py:25
         h = C.c_void_p()
-        check(self.lib.aware_plan_create(C.byref(h), n_fft, hop, win_length, wid, int(band_bins[0]), int(band_bins[1])),
-              "aware_plan_create")
+        rc = self.lib.aware_plan_create_ex(C.byref(h), n_fft, hop, win_length, wid, int(band_bins[0]), int(band_bins[1]),
+                                           PLAN_GENERAL if general else 0)
+        if rc == -2 and int(n_fft) not in GENERAL_NFFT:
+            raise NotImplementedError(f"n_fft = {n_fft} is not supported: the HIP STFT kernels serve n_fft in {GENERAL_NFFT}")
+        check(rc, "aware_plan_create")
         self.h = h
         self.n_fft, self.hop, self.band_bins = n_fft, hop, (int(band_bins[0]), int(band_bins[1]))
+        self.win_length, self.window = win_length, window
         self.nband = self.band_bins[1] - self.band_bins[0] + 1
+        self.spectrum_stride = self.lib.aware_plan_spectrum_stride(h)
+        self.general = bool(self.lib.aware_plan_is_general(h))
 
     def __del__(self):
         try:
@@ -60,7 +107,9 @@ class Plan:
 class Batch:
     """Ragged batch geometry (aware_batch)."""
 
-    def __init__(self, lengths: Sequence[int], in_offsets: Sequence[int] | None = None):
+    def __init__(self, lengths: Sequence[int], in_offsets: Sequence[int] | None = None, plan: Plan | None = None):
+        """plan: build the geometry for that plan (frames by its hop, length rule by its n_fft: the batch a general plan
+        needs); None: the card geometry."""
         require_gpu()
         self.lib = load_library()
         self.lengths = [int(x) for x in lengths]
@@ -73,9 +122,14 @@ class Batch:
             self.in_offsets = [int(x) for x in in_offsets]
             off = (C.c_int * self.B)(*self.in_offsets)
         h = C.c_void_p()
-        rc = self.lib.aware_batch_create(C.byref(h), self.B, arr, off)
+        if plan is None:
+            rc = self.lib.aware_batch_create(C.byref(h), self.B, arr, off)
+        else:
+            rc = self.lib.aware_batch_create_for_plan(C.byref(h), plan.h, self.B, arr, off)
+        self.plan = plan
         if rc == -1:
-            raise ValueError("every clip needs more than n_fft/2 = 512 samples")
+            half = 512 if plan is None else plan.n_fft // 2
+            raise ValueError(f"every clip needs more than n_fft/2 = {half} samples")
         check(rc, "aware_batch_create")
         self.h = h
         self.total_frames = self.lib.aware_batch_total_frames(h)
@@ -113,8 +167,9 @@ class Batch:
 
 
 def stft(plan: Plan, batch: Batch, audio: torch.Tensor, normalize=False) -> torch.Tensor:
-    """Full one-sided spectrum, frame-major [total_frames, 520] complex64 (bins 0..512 valid)."""
-    spec = torch.empty((batch.total_frames, FULL_STRIDE), dtype=torch.complex64, device=audio.device)
+    """Full one-sided spectrum, frame-major [total_frames, plan.spectrum_stride] complex64 (bins 0..n_fft/2 valid; 520 and
+    0..512 for the card plan)."""
+    spec = torch.empty((batch.total_frames, plan.spectrum_stride), dtype=torch.complex64, device=audio.device)
     scr = batch.scratch()
     check(plan.lib.aware_stft(plan.h, batch.h, _ptr(audio), int(normalize), _ptr(spec), _ptr(scr), _stream()), "aware_stft")
     return spec
@@ -123,8 +178,19 @@ def stft(plan: Plan, batch: Batch, audio: torch.Tensor, normalize=False) -> torc
 def istft(plan: Plan, batch: Batch, spec: torch.Tensor, normalize=False) -> torch.Tensor:
     out = torch.empty(batch.total_out, dtype=torch.float32, device=spec.device)
     scr = batch.scratch()
-    check(plan.lib.aware_istft(plan.h, batch.h, _ptr(spec), int(normalize), _ptr(out), _ptr(scr), _stream()), "aware_istft")
+    rc = plan.lib.aware_istft(plan.h, batch.h, _ptr(spec), int(normalize), _ptr(out), _ptr(scr), _stream())
+    _check_nola(rc, plan, batch)
+    check(rc, "aware_istft")
     return out
+
+
+def _check_nola(rc: int, plan: Plan, batch: Batch):
+    if rc == -1 and plan.general and batch.plan is plan:
+        bad = [n for n in batch.lengths if not nola_ok(plan.n_fft, plan.hop, plan.win_length, plan.window, n)]
+        if bad:
+            raise RuntimeError(f"istft: window overlap-add envelope is below 1e-11 (NOLA condition violated) for n_fft "
+                               f"{plan.n_fft}, hop {plan.hop}, win_length {plan.win_length}, {plan.window} window; torch.istft "
+                               f"raises for this geometry too")
 
 
 def stft_band(plan: Plan, batch: Batch, audio: torch.Tensor, normalize=True):
@@ -137,17 +203,20 @@ def stft_band(plan: Plan, batch: Batch, audio: torch.Tensor, normalize=True):
 
 
 def stft_bwd(plan: Plan, batch: Batch, grad_spec: torch.Tensor) -> torch.Tensor:
-    """Backward of `stft` (normalize=False): grad_spec [total_frames, 520] complex64 -> grad_audio f32 laid out like the
-    audio `stft` takes (clip b: lengths[b] samples at in_offsets[b]); any clip length > 512."""
+    """Backward of `stft` (normalize=False): grad_spec [total_frames, plan.spectrum_stride] complex64 -> grad_audio f32 laid
+    out like the audio `stft` takes (clip b: lengths[b] samples at in_offsets[b]); any clip length > n_fft/2."""
     out = torch.zeros(batch.total_in, dtype=torch.float32, device=grad_spec.device)
     check(plan.lib.aware_stft_bwd(plan.h, batch.h, _ptr(grad_spec), _ptr(out), _stream()), "aware_stft_bwd")
     return out
 
 
 def istft_bwd(plan: Plan, batch: Batch, grad_audio: torch.Tensor) -> torch.Tensor:
-    """Backward of `istft` (normalize=False): grad_audio [total_out] -> grad_spec [total_frames, 520] complex64."""
-    gs = torch.empty((batch.total_frames, FULL_STRIDE), dtype=torch.complex64, device=grad_audio.device)
-    check(plan.lib.aware_istft_bwd(plan.h, batch.h, _ptr(grad_audio), _ptr(gs), _stream()), "aware_istft_bwd")
+    """Backward of `istft` (normalize=False): grad_audio [total_out] -> grad_spec [total_frames, plan.spectrum_stride]
+    complex64."""
+    gs = torch.empty((batch.total_frames, plan.spectrum_stride), dtype=torch.complex64, device=grad_audio.device)
+    rc = plan.lib.aware_istft_bwd(plan.h, batch.h, _ptr(grad_audio), _ptr(gs), _stream())
+    _check_nola(rc, plan, batch)
+    check(rc, "aware_istft_bwd")
     return gs
 
 

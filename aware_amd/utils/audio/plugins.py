@@ -26,10 +26,13 @@ def band_bins(sample_rate: int, n_fft: int, bands) -> tuple:
     return int(idx[0]), int(idx[-1])
 
 
-def get_plan(n_fft=1024, hop=256, window="hann", bins=(32, 256)) -> "rt.Plan":
-    key = (n_fft, hop, window, tuple(bins), torch.cuda.current_device() if torch.cuda.is_available() else -1)
+def get_plan(n_fft=1024, hop=256, window="hann", bins=(32, 256), win_length=None) -> "rt.Plan":
+    """Cached plan per geometry (win_length None = n_fft): the card plan for 1024 / 256 / 1024, a general plan (transforms
+    only) for any other geometry rt.check_geometry accepts."""
+    win_length = n_fft if win_length is None else win_length
+    key = (n_fft, hop, win_length, window, tuple(bins), torch.cuda.current_device() if torch.cuda.is_available() else -1)
     if key not in _PLANS:
-        _PLANS[key] = rt.Plan(n_fft, hop, n_fft, window, bins)
+        _PLANS[key] = rt.Plan(n_fft, hop, win_length, window, bins)
     return _PLANS[key]
 
 
@@ -44,14 +47,18 @@ def _as_device(x: torch.Tensor) -> torch.Tensor:
 _BATCHES = {}
 
 
-def get_batch(lengths) -> "rt.Batch":
-    """Geometry handles are cached per (device, lengths): a plug-in call does no hipMalloc / host-to-device table copy
-    after its first use of a shape."""
-    key = (torch.cuda.current_device(),) + tuple(int(n) for n in lengths)
+def get_batch(lengths, plan: "rt.Plan | None" = None) -> "rt.Batch":
+    """Geometry handles are cached per (device, plan geometry, lengths): a plug-in call does no hipMalloc / host-to-device
+    table copy after its first use of a shape.  plan: a general plan's batch (None or the card plan: the card batch)."""
+    lengths = tuple(int(n) for n in lengths)
+    if plan is not None and not plan.general:
+        plan = None
+    geom = None if plan is None else (plan.n_fft, plan.hop, plan.win_length, plan.window)
+    key = (torch.cuda.current_device(), geom, lengths)
     if key not in _BATCHES:
         if len(_BATCHES) > 256:
             _BATCHES.clear()
-        _BATCHES[key] = rt.Batch(list(key[1:]))
+        _BATCHES[key] = rt.Batch(list(lengths), plan=plan)
     return _BATCHES[key]
 
 
@@ -73,39 +80,62 @@ class _NormalizeFn(torch.autograd.Function):
 
 
 class _STFTFn(torch.autograd.Function):
+    """x (L) or (B, L) -> (F, T) or (B, F, T), F = n_fft/2 + 1: the rows of a 2-D input are one uniform batch."""
+
     @staticmethod
-    def forward(ctx, x, n_fft, hop, window):
-        plan = get_plan(n_fft, hop, window)
-        batch = get_batch([x.numel()])
-        ctx.geom = (plan, batch, n_fft)
-        spec = rt.stft(plan, batch, x, normalize=False)
-        return spec[:, : n_fft // 2 + 1].transpose(0, 1).contiguous()        # [F, T]
+    def forward(ctx, x, n_fft, hop, window, win_length):
+        plan = get_plan(n_fft, hop, window, win_length=win_length)
+        rows = x.reshape(-1, x.shape[-1]) if x.dim() == 2 else x.reshape(1, -1)
+        B, L = rows.shape
+        batch = get_batch([L] * B, plan)
+        ctx.geom = (plan, batch, n_fft, x.shape)
+        spec = rt.stft(plan, batch, rows.contiguous().reshape(-1), normalize=False)
+        F = n_fft // 2 + 1
+        out = spec.view(B, -1, plan.spectrum_stride)[:, :, :F].transpose(1, 2).contiguous()   # [B, F, T]
+        return out if x.dim() == 2 else out[0]
 
     @staticmethod
     def backward(ctx, g):
-        plan, batch, n_fft = ctx.geom
+        plan, batch, n_fft, shape = ctx.geom
         F = n_fft // 2 + 1
-        gs = torch.zeros((batch.total_frames, rt.FULL_STRIDE), dtype=torch.complex64, device=g.device)
-        gs[:, :F] = g.transpose(0, 1)
-        return rt.stft_bwd(plan, batch, gs), None, None, None
+        gs = torch.zeros((batch.total_frames, plan.spectrum_stride), dtype=torch.complex64, device=g.device)
+        g3 = g if g.dim() == 3 else g[None]
+        gs.view(g3.shape[0], -1, plan.spectrum_stride)[:, :, :F] = g3.transpose(1, 2)
+        return rt.stft_bwd(plan, batch, gs).reshape(shape), None, None, None, None
 
 
 class _ISTFTFn(torch.autograd.Function):
+    """X (F, T) or (B, F, T) -> (hop (T - 1)) or (B, hop (T - 1))."""
+
     @staticmethod
-    def forward(ctx, X, n_fft, hop, window):
-        F, T = X.shape
-        plan = get_plan(n_fft, hop, window)
-        batch = get_batch([max(hop * (T - 1), n_fft // 2 + 1)])
-        ctx.geom = (plan, batch, F)
-        spec = torch.zeros((T, rt.FULL_STRIDE), dtype=torch.complex64, device=X.device)
-        spec[:, :F] = X.transpose(0, 1)
-        return rt.istft(plan, batch, spec, normalize=False)
+    def forward(ctx, X, n_fft, hop, window, win_length):
+        plan = get_plan(n_fft, hop, window, win_length=win_length)
+        X3 = X if X.dim() == 3 else X[None]
+        B, F, T = X3.shape
+        if plan.general:
+            # any clip length with T = 1 + n // hop frames serves: the output has hop (T - 1) samples either way
+            n = hop * (T - 1) if hop * (T - 1) > n_fft // 2 else hop * T - 1
+            if n <= n_fft // 2:
+                raise ValueError(f"istft: {T} frames are too few for n_fft {n_fft} and hop {hop}")
+            if not rt.nola_ok(n_fft, hop, win_length, window, n):
+                raise RuntimeError(f"istft: window overlap-add envelope is below 1e-11 (NOLA condition violated) for "
+                                   f"n_fft {n_fft}, hop {hop}, win_length {win_length}, {window} window and {T} frames; "
+                                   f"torch.istft raises for this geometry too")
+            batch = get_batch([n] * B, plan)
+        else:
+            batch = get_batch([max(hop * (T - 1), n_fft // 2 + 1)] * B)
+        ctx.geom = (plan, batch, F, X.dim())
+        spec = torch.zeros((B * T, plan.spectrum_stride), dtype=torch.complex64, device=X.device)
+        spec.view(B, T, -1)[:, :, :F] = X3.transpose(1, 2)
+        out = rt.istft(plan, batch, spec, normalize=False)
+        return out.view(B, -1) if X.dim() == 3 else out
 
     @staticmethod
     def backward(ctx, g):
-        plan, batch, F = ctx.geom
-        gs = rt.istft_bwd(plan, batch, g.contiguous().float())
-        return gs[:, :F].transpose(0, 1).contiguous(), None, None, None
+        plan, batch, F, dim = ctx.geom
+        gs = rt.istft_bwd(plan, batch, g.contiguous().float().reshape(-1))
+        out = gs.view(batch.B, -1, plan.spectrum_stride)[:, :, :F].transpose(1, 2).contiguous()
+        return (out if dim == 3 else out[0]), None, None, None, None
 
 
 class _DecomposeFn(torch.autograd.Function):
@@ -147,28 +177,29 @@ class WaveformNormalizer(BaseAudioProcessor):
 
 
 class STFT(BaseAudioProcessor):
-    """torch.stft(center=True, window, return_complex=True) (stft.py:14-28); differentiable for every input it accepts
+    """torch.stft(center=True, window, return_complex=True) (stft.py:14-28) for n_fft in rt.GENERAL_NFFT, any hop and
+    win_length in 1..n_fft; input (L) -> (F, T) or (B, L) -> (B, F, T); differentiable for every input it accepts
     (more than n_fft/2 samples)."""
 
     def __init__(self, n_fft: int = 2048, hop_length: int = 512, window: str = "hann", win_length: int = 2048):
-        if window not in ("hann", "hamming"):
-            raise ValueError(f"Invalid window type: {window}")
+        rt.check_geometry(n_fft, hop_length, win_length, window)
         self.n_fft, self.hop_length, self.window_name, self.win_length = n_fft, hop_length, window, win_length
 
     def __call__(self, data: torch.Tensor) -> torch.Tensor:
-        return _STFTFn.apply(_as_device(data), self.n_fft, self.hop_length, self.window_name)
+        return _STFTFn.apply(_as_device(data), self.n_fft, self.hop_length, self.window_name, self.win_length)
 
 
 class ISTFT(BaseAudioProcessor):
-    """torch.istft(center=True, window) without `length` (stft.py:34-48); differentiable."""
+    """torch.istft(center=True, window) without `length` (stft.py:34-48): (F, T) -> (hop (T-1)) or (B, F, T) ->
+    (B, hop (T-1)); RuntimeError where torch.istft's NOLA check fails; differentiable."""
 
     def __init__(self, n_fft: int = 2048, hop_length: int = 512, window: str = "hann", win_length: int = 2048):
-        if window not in ("hann", "hamming"):
-            raise ValueError(f"Invalid window type: {window}")
+        rt.check_geometry(n_fft, hop_length, win_length, window)
         self.n_fft, self.hop_length, self.window_name, self.win_length = n_fft, hop_length, window, win_length
 
     def __call__(self, data: torch.Tensor) -> torch.Tensor:
-        return _ISTFTFn.apply(data.to("cuda", torch.complex64), self.n_fft, self.hop_length, self.window_name)
+        return _ISTFTFn.apply(data.to("cuda", torch.complex64), self.n_fft, self.hop_length, self.window_name,
+                              self.win_length)
 
 
 class STFTDecomposer(BaseAudioProcessor):

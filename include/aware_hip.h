@@ -33,7 +33,7 @@ extern "C" {
 
 #define AWARE_OK 0
 #define AWARE_E_BADARG (-1)
-#define AWARE_E_UNSUPPORTED (-2)   /* e.g. n_fft != 1024, hop != 256, band wider than 256 bins */
+#define AWARE_E_UNSUPPORTED (-2)   /* e.g. n_fft outside {256, ..., 4096}, a general plan where only the card's geometry runs */
 #define AWARE_E_HIP (-3)           /* a HIP runtime call failed; see aware_last_hip_error() */
 #define AWARE_E_WORKSPACE (-4)     /* caller's workspace too small */
 
@@ -56,7 +56,9 @@ typedef struct aware_batch aware_batch;
 typedef struct aware_embed aware_embed;
 
 /* ABI version (200: no process-global knobs, the kernel choices live in aware_embed_config; 300: conv_pipe 0 = f16 two-term
- * kernels, optimiser / scheduler registries, device-side detector training, aware_stft_bwd for any clip length) */
+ * kernels, optimiser / scheduler registries, device-side detector training, aware_stft_bwd for any clip length; 310: general
+ * STFT geometry -- aware_plan_create_ex, aware_plan_spectrum_stride, aware_plan_is_general, aware_batch_create_for_plan,
+ * aware_nola_check) */
 int aware_version(void);
 /* text of the last failed HIP runtime call on the calling thread (thread-local) */
 const char* aware_last_hip_error(void);
@@ -72,6 +74,26 @@ const char* aware_last_hip_error(void);
 int aware_plan_create(aware_plan** out, int n_fft, int hop, int win_length, int window,
                       int band_lo_bin, int band_hi_bin);
 void aware_plan_destroy(aware_plan* plan);
+/* Geometries.  The model card's (n_fft 1024, hop 256, win_length 1024) gives a card plan: the kernels of the embed / detect
+ * loop.  Every other geometry with n_fft in {256, 512, 1024, 2048, 4096} (else AWARE_E_UNSUPPORTED), 1 <= hop <= n_fft and
+ * 1 <= win_length <= n_fft (else AWARE_E_BADARG) gives a GENERAL plan (csrc/stft_any.hip): the window of win_length samples
+ * is zero-padded to n_fft and centred as torch.stft does.  A general plan serves only aware_stft, aware_istft,
+ * aware_stft_bwd and aware_istft_bwd, on batches made by aware_batch_create_for_plan; the band arguments are not used, and
+ * every other entry point that takes a plan returns AWARE_E_UNSUPPORTED for it.
+ * aware_plan_create_ex: flags AWARE_PLAN_GENERAL builds a general plan even for the card geometry (tests hold the two
+ * paths against each other).  aware_plan_create(...) == aware_plan_create_ex(..., 0). */
+#define AWARE_PLAN_GENERAL 1
+int aware_plan_create_ex(aware_plan** out, int n_fft, int hop, int win_length, int window, int band_lo_bin,
+                         int band_hi_bin, int flags);
+/* complex values per frame row of the plan's spectra: AWARE_FULL_STRIDE (520) for the card plan, n_fft/2 + 1 rounded up
+ * to a multiple of 8 for a general plan (bins 0..n_fft/2 valid, the rest written as zero) */
+int aware_plan_spectrum_stride(const aware_plan* plan);
+/* 1 for a general plan, 0 for the card plan */
+int aware_plan_is_general(const aware_plan* plan);
+/* torch.istft's NOLA condition (host only, no device): AWARE_OK when the overlap-add envelope of this geometry stays
+ * >= 1e-11 over the trimmed output of a clip of n_samples samples (T = 1 + n_samples/hop frames), AWARE_E_BADARG when
+ * torch.istft would raise for it (aware_istft / aware_istft_bwd refuse such a batch with AWARE_E_BADARG) */
+int aware_nola_check(int n_fft, int hop, int win_length, int window, int n_samples);
 
 /* ---- batch geometry ----------------------------------------------------------------------
  * n_samples[B] (host): clip lengths.  in_offsets[B] (host, may be NULL = densely packed):
@@ -84,6 +106,12 @@ int aware_batch_total_out(const aware_batch* batch);      /* sum 256*(T_b-1)  */
 int aware_batch_out_offset(const aware_batch* batch, int b); /* float offset of clip b's output */
 int aware_batch_out_length(const aware_batch* batch, int b);
 int aware_batch_frames(const aware_batch* batch, int b);
+/* a batch for a plan: frames T_b = 1 + n_b/hop by the plan's hop, istft outputs hop*(T_b - 1) samples, clips need more than
+ * n_fft/2 samples (AWARE_E_BADARG otherwise).  For the card plan the same as aware_batch_create.  A general batch also holds
+ * the overlap-add frame buffer of the synthesis direction ([total frames][n_fft] floats, allocated here), so one general batch
+ * must not be used on two streams at the same time; total_pooled is 0 and the detector / embed entry points refuse it. */
+int aware_batch_create_for_plan(aware_batch** out, const aware_plan* plan, int B, const int* n_samples,
+                                const int* in_offsets);
 
 /* ---- DSP plug-ins ---------------------------------------------------------------------------
  * aware_stft: WaveformNormalizer (optional) + STFT.__call__  (utils/audio/waveform.py:18-19,
@@ -109,7 +137,10 @@ int aware_stft_band(const aware_plan* plan, const aware_batch* batch, const floa
  * aware_stft_bwd: grad_spec dev complex64 [total frames][AWARE_FULL_STRIDE] -> grad_audio dev f32, laid out like the audio
  *   aware_stft takes (clip b: n_b samples at in_offsets[b]): any clip length n > 512, ragged batches (the reflect pads fold
  *   about sample 0 and sample n - 1).
- * aware_istft_bwd: grad_audio dev f32 [total out] -> grad_spec dev complex64 [total frames][AWARE_FULL_STRIDE]. */
+ * aware_istft_bwd: grad_audio dev f32 [total out] -> grad_spec dev complex64 [total frames][AWARE_FULL_STRIDE].
+ * General plans: the four transforms take spectra of aware_plan_spectrum_stride(plan) complex values per row, clips of any
+ * length n > n_fft/2, hop*(T-1) output samples per clip; aware_istft / aware_istft_bwd return AWARE_E_BADARG for a batch
+ * that violates the NOLA condition (aware_nola_check) and every entry point returns it for a batch not made for the plan. */
 int aware_stft_bwd(const aware_plan* plan, const aware_batch* batch, const void* grad_spec, float* grad_audio,
                    void* stream);
 int aware_istft_bwd(const aware_plan* plan, const aware_batch* batch, const float* grad_audio, void* grad_spec,
