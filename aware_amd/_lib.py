@@ -67,6 +67,11 @@ class EmbedConfig(C.Structure):
                 ("dsp_path", C.c_int), ("l1_weight", C.c_float), ("mel", C.c_int)]
 
 
+class DetectorArch(C.Structure):
+    _fields_ = [("activation", C.c_int), ("norm", C.c_int), ("final_activation", C.c_int),
+                ("norm_scale", C.POINTER(C.c_void_p)), ("norm_shift", C.POINTER(C.c_void_p))]
+
+
 class OptimizerConfig(C.Structure):
     _fields_ = [("kind", C.c_int), ("hyp", C.c_float * 8), ("weight_decay", C.c_double), ("table", C.POINTER(C.c_double)),
                 ("plateau", C.c_int), ("patience", C.c_int), ("factor", C.c_double), ("threshold", C.c_double),
@@ -116,6 +121,9 @@ SIGNATURES = {
     "aware_detector_train_gradients": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), _vp, _sz, _vp]),
     "aware_detector_update_device": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), _vp]),
     "aware_detector_create": (_i, [C.POINTER(_vp), _vp, _vp, _i, _i, _pi, C.POINTER(_vp), C.POINTER(_vp)]),
+    "aware_detector_create_ex": (_i, [C.POINTER(_vp), _vp, _vp, _i, _i, _pi, C.POINTER(_vp), C.POINTER(_vp),
+                                     C.POINTER(DetectorArch)]),
+    "aware_detector_is_card": (_i, [_vp]),
     "aware_detector_destroy": (None, [_vp]),
     "aware_detect_workspace_bytes": (_sz, [_vp, _vp]),
     "aware_detect": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -122,9 +122,24 @@ struct aware_detector {
     // when a filter's support is longer than the folded analysis kernel takes (kMelTapsA / kMelTapsB columns)
     float* melf_w = nullptr;
     unsigned char* melf_s = nullptr;
+    // architecture (aware_detector_arch).  card_arch: InstanceNorm + LeakyReLU(0.2) blocks and a tanh read-out, the model card's
+    // network and the only one the fused kernels serve (conv-block epilogues, read-out, tail); every other detector takes the
+    // staged route: plain GEMM + bias, launch_norm_act_fwd / _bwd, launch_head
+    bool card_arch = true;
+    int act = kActLRelu, norm = kNormInstance, final_act = kActTanh;
+    float* nscale[8] = {nullptr};   // affine norm (BatchNorm1d in eval mode, folded): u = z * nscale[l][c] + nshift[l][c]
+    float* nshift[8] = {nullptr};
+    float* normmem = nullptr;
 };
+static_assert(AWARE_ACT_RELU == kActRelu && AWARE_ACT_LEAKY_RELU == kActLRelu && AWARE_ACT_GELU == kActGelu &&
+              AWARE_ACT_SWISH == kActSwish && AWARE_FINAL_TANH == kActTanh && AWARE_FINAL_SIGMOID == kActSigmoid &&
+              AWARE_FINAL_RELU == kActRelu && AWARE_FINAL_LEAKY_RELU == kActLRelu && AWARE_FINAL_GELU == kActGelu &&
+              AWARE_FINAL_SWISH == kActSwish, "activation enums");
+static_assert(AWARE_NORM_INSTANCE == kNormInstance && AWARE_NORM_BATCH == kNormAffine && AWARE_NORM_NONE == kNormNone, "norm enums");
+// whether the staged route keeps the pre-activation of every block for the backward (DetBufs::stash)
+static bool det_needs_stash(const aware_detector* d) { return !d->card_arch && norm_act_needs_stash(d->norm, d->act); }
 
-extern "C" int aware_version(void) { return 310; }
+extern "C" int aware_version(void) { return 320; }
 extern "C" const char* aware_last_hip_error(void) { return g_last_err.c_str(); }
 
 // ---------------------------------------------------------------------------------------------
@@ -857,9 +872,9 @@ static int detector_upload(aware_detector* d, const float* mel_basis, const floa
     return AWARE_OK;
 }
 
-extern "C" int aware_detector_create(aware_detector** out, const aware_plan* plan, const float* mel_basis, int n_mels,
-                                     int n_layers, const int* channels, const float* const* weights,
-                                     const float* const* biases) {
+static int detector_create(aware_detector** out, const aware_plan* plan, const float* mel_basis, int n_mels, int n_layers,
+                           const int* channels, const float* const* weights, const float* const* biases,
+                           const aware_detector_arch* arch) {
     if (!out || !plan || !mel_basis || !channels || !weights) return AWARE_E_BADARG;
     if (plan->general) return AWARE_E_UNSUPPORTED;       // the detector runs on the card geometry only
     if (n_mels != 128 || n_layers < 1 || n_layers > 7 || channels[0] != n_mels) return AWARE_E_UNSUPPORTED;
@@ -871,17 +886,65 @@ extern "C" int aware_detector_create(aware_detector** out, const aware_plan* pla
     d->n_mels = n_mels; d->n_layers = n_layers; d->nbits = cl / 2;
     d->band_lo = plan->dev.band_lo; d->nband = plan->dev.nband;
     for (int i = 0; i <= n_layers; ++i) { d->ch[i] = channels[i]; if (channels[i] > d->maxc) d->maxc = channels[i]; }
+    if (arch) {
+        d->act = arch->activation; d->norm = arch->norm; d->final_act = arch->final_activation;
+        d->card_arch = d->act == kActLRelu && d->norm == kNormInstance && d->final_act == kActTanh;
+    }
     int rc = detector_upload(d, mel_basis, weights, biases, true);
+    if (rc == AWARE_OK && d->norm == kNormAffine) {
+        size_t n = 0;
+        for (int l = 0; l < n_layers; ++l) n += 2 * (size_t)channels[l + 1];
+        std::vector<float> h(n);
+        size_t o = 0;
+        for (int l = 0; l < n_layers; ++l) {
+            const int co = channels[l + 1];
+            memcpy(h.data() + o, arch->norm_scale[l], co * sizeof(float));
+            memcpy(h.data() + o + co, arch->norm_shift[l], co * sizeof(float));
+            o += 2 * (size_t)co;
+        }
+        if (hipMalloc((void**)&d->normmem, n * sizeof(float)) != hipSuccess ||
+            hipMemcpy(d->normmem, h.data(), n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+            rc = AWARE_E_HIP;
+        } else {
+            o = 0;
+            for (int l = 0; l < n_layers; ++l) {
+                d->nscale[l] = d->normmem + o;
+                d->nshift[l] = d->normmem + o + channels[l + 1];
+                o += 2 * (size_t)channels[l + 1];
+            }
+        }
+    }
     if (rc) { aware_detector_destroy(d); return rc; }
     *out = d;
     return AWARE_OK;
 }
+extern "C" int aware_detector_create(aware_detector** out, const aware_plan* plan, const float* mel_basis, int n_mels,
+                                     int n_layers, const int* channels, const float* const* weights,
+                                     const float* const* biases) {
+    return detector_create(out, plan, mel_basis, n_mels, n_layers, channels, weights, biases, nullptr);
+}
+extern "C" int aware_detector_create_ex(aware_detector** out, const aware_plan* plan, const float* mel_basis, int n_mels,
+                                        int n_layers, const int* channels, const float* const* weights,
+                                        const float* const* biases, const aware_detector_arch* arch) {
+    if (!arch) return AWARE_E_BADARG;
+    if (arch->activation < AWARE_ACT_RELU || arch->activation > AWARE_ACT_SWISH) return AWARE_E_BADARG;
+    if (arch->norm < AWARE_NORM_INSTANCE || arch->norm > AWARE_NORM_NONE) return AWARE_E_BADARG;
+    if (arch->final_activation < AWARE_FINAL_RELU || arch->final_activation > AWARE_FINAL_SIGMOID) return AWARE_E_BADARG;
+    if (arch->norm == AWARE_NORM_BATCH) {
+        if (!arch->norm_scale || !arch->norm_shift || n_layers < 1 || n_layers > 7) return AWARE_E_BADARG;
+        for (int l = 0; l < n_layers; ++l)
+            if (!arch->norm_scale[l] || !arch->norm_shift[l]) return AWARE_E_BADARG;
+    }
+    return detector_create(out, plan, mel_basis, n_mels, n_layers, channels, weights, biases, arch);
+}
+extern "C" int aware_detector_is_card(const aware_detector* d) { return d ? (d->card_arch ? 1 : 0) : AWARE_E_BADARG; }
 // EXTENSION (detector training, BASELINE north_star; the reference never changes the weights): replace the parameters of a
 // detector in place (same layer shapes).  Host arrays as for aware_detector_create.  Synchronous (blocking copies); the
 // caller makes sure no work using the detector is in flight.
 extern "C" int aware_detector_update(aware_detector* d, const float* mel_basis, const float* const* weights,
                                      const float* const* biases) {
     if (!d || !mel_basis || !weights) return AWARE_E_BADARG;
+    if (!d->card_arch) return AWARE_E_UNSUPPORTED;       // the training extension serves the model card's network only
     return detector_upload(d, mel_basis, weights, biases, false);
 }
 // EXTENSION (detector training): the same refresh from DEVICE arrays, asynchronous on `stream` -- no host round trip of the
@@ -890,6 +953,7 @@ extern "C" int aware_detector_update(aware_detector* d, const float* mel_basis, 
 extern "C" int aware_detector_update_device(aware_detector* d, const float* const* dev_weights, const float* const* dev_biases,
                                             void* stream) {
     if (!d || !dev_weights) return AWARE_E_BADARG;
+    if (!d->card_arch) return AWARE_E_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
     const int nl = d->n_layers;
     for (int l = 0; l < nl; ++l) {
@@ -919,6 +983,7 @@ extern "C" void aware_detector_destroy(aware_detector* d) {
     if (d->pkmem) (void)hipFree(d->pkmem);
     if (d->h2mem) (void)hipFree(d->h2mem);
     if (d->mel2mem) (void)hipFree(d->mel2mem);
+    if (d->normmem) (void)hipFree(d->normmem);
     delete d;
 }
 
@@ -944,6 +1009,7 @@ struct DetBufs {
     float* x0;        // [NP][128]
     float* act[8];    // [NP][C_l+1]
     float* rstd[8];   // [B][C_l+1]
+    float* stash[8];  // [NP][C_l+1] pre-activations of a staged-route block (det_needs_stash), else null
     float *mstats, *gstat, *mpart;   // mel statistics [B][128][4], [B][4], chunk partials
     int mstride;
     float* pred;      // [B][nbits]
@@ -967,6 +1033,7 @@ static void carve_det(Carver& c, const aware_batch* b, const aware_detector* d, 
     for (int l = 0; l < d->n_layers; ++l) {
         o.act[l] = c.take<float>((size_t)b->NP * d->ch[l + 1]);
         o.rstd[l] = c.take<float>((size_t)b->B * d->ch[l + 1]);
+        o.stash[l] = det_needs_stash(d) ? c.take<float>((size_t)b->NP * d->ch[l + 1]) : nullptr;
     }
     o.mstats = c.take<float>((size_t)b->B * 128 * 4);
     o.gstat = c.take<float>((size_t)b->B * 4);
@@ -983,9 +1050,11 @@ static size_t det_bytes(const aware_batch* b, const aware_detector* d) {
     size_t f = (size_t)b->NF * 128 + (size_t)b->NP * 128 + (size_t)b->B * (128 * 4 + 4 + d->nbits) +
                (size_t)b->B * ((b->max_frames + 31) / 32) * 256;
     for (int l = 0; l < d->n_layers; ++l) f += (size_t)(b->NP + b->B) * d->ch[l + 1];
+    if (det_needs_stash(d))
+        for (int l = 0; l < d->n_layers; ++l) f += (size_t)b->NP * d->ch[l + 1];
     f += (size_t)zpart_slabs(d) * b->NP * d->ch[d->n_layers];
     f += (size_t)b->B * 64 * (d->n_layers + 3);
-    return f * sizeof(float) + 256 * (12 + 3 * d->n_layers);
+    return f * sizeof(float) + 256 * (12 + 4 * d->n_layers);
 }
 
 // number of 32-row groups per clip when the fused clip-aligned GEMM applies (uniform batch,
@@ -1045,6 +1114,16 @@ static int det_forward(const aware_detector* d, const aware_batch* b, const floa
     o.tail = 0;
     for (int l = 0; l < d->n_layers - (skip_last ? 1 : 0); ++l) {
         const int ci = d->ch[l], co = d->ch[l + 1];
+        if (!d->card_arch) {
+            // architecture variant: conv + bias, then the block's norm and activation (pre-activation kept in the stash)
+            gemm_plain(pipe, x, ci, d->w[l], ci, d->wpk[l], d->bias[l], o.act[l], co, b->NP, co, ci, st);
+            LAUNCHCHK(); PROF(K_GEMM);
+            launch_norm_act_fwd(d->norm, d->act, o.act[l], b->d_frame_off, b->d_pool_off, o.rstd[l], d->nscale[l], d->nshift[l],
+                                o.stash[l], co, b->B, b->max_frames / 2, st);
+            LAUNCHCHK(); PROF(K_INLRELU);
+            x = o.act[l];
+            continue;
+        }
         if (l == d->n_layers - 1 && co <= 64 && b->max_frames / 2 <= 320) {
             // skinny last conv: split-K partial slabs, summed inside the fused tail kernel
             launch_gemm_nt_splitk(x, ci, d->w[l], ci, o.zpart, co, b->NP, co, ci, kTailSplit, st);
@@ -1115,6 +1194,7 @@ extern "C" int aware_detector_forward(const aware_detector* d, const aware_batch
     DetBufs o;
     carve_det(c, b, d, o);
     if (!c.ok) return AWARE_E_WORKSPACE;
+    for (int l = 0; l < d->n_layers; ++l) o.stash[l] = nullptr;      // forward only: no backward reads the pre-activations
     int rc = det_forward(d, b, mag, o, st);
     if (rc) return rc;
     if (o.tail)
@@ -1122,7 +1202,7 @@ extern "C" int aware_detector_forward(const aware_detector* d, const aware_batch
                     b->d_pool_off, nullptr, values, nullptr, nullptr, nullptr, nullptr, nullptr, 0, d->nbits, b->B, b->max_frames / 2, st);
     else
         launch_head(o.act[d->n_layers - 1], b->d_frame_off, b->d_pool_off, nullptr, values, nullptr, nullptr, nullptr,
-                    nullptr, nullptr, 0, d->nbits, b->B, st);
+                    nullptr, nullptr, 0, d->nbits, b->B, st, nullptr, d->final_act);
     LAUNCHCHK();
     return AWARE_OK;
 }
@@ -1139,6 +1219,7 @@ extern "C" int aware_detect(const aware_plan* plan, const aware_detector* d, con
     float* mag = c.take<float>((size_t)b->NF * kFS);
     unsigned long long* pmax = c.take<unsigned long long>((size_t)b->B * b->pstride);
     if (!c.ok) return AWARE_E_WORKSPACE;
+    for (int l = 0; l < d->n_layers; ++l) o.stash[l] = nullptr;
     int rc = aware_stft_band(plan, b, audio, 1, mag, nullptr, pmax, stream);
     if (rc) return rc;
     rc = det_forward(d, b, mag, o, st);
@@ -1148,7 +1229,7 @@ extern "C" int aware_detect(const aware_plan* plan, const aware_detector* d, con
                     b->d_pool_off, nullptr, values, nullptr, nullptr, nullptr, nullptr, nullptr, 0, d->nbits, b->B, b->max_frames / 2, st);
     else
         launch_head(o.act[d->n_layers - 1], b->d_frame_off, b->d_pool_off, nullptr, values, nullptr, nullptr, nullptr,
-                    nullptr, nullptr, 0, d->nbits, b->B, st);
+                    nullptr, nullptr, 0, d->nbits, b->B, st, nullptr, d->final_act);
     LAUNCHCHK();
     return AWARE_OK;
 }
@@ -1184,7 +1265,7 @@ static int det_forward_backward(const aware_detector* d, const aware_batch* b, c
     // one kernel for the last conv block, the BRH head, the loss, their backward and the data gradient of the last
     // conv (uniform batches, bf16x3 configuration); otherwise split-K GEMM + tail kernel + data-gradient GEMM
     const int pipe = G.pipe;
-    const bool fused_readout = G.readout == 0 && !G.wgrad && pipe != 1 && nwm && nl >= 2 && d->lastpk && G.target &&
+    const bool fused_readout = d->card_arch && G.readout == 0 && !G.wgrad && pipe != 1 && nwm && nl >= 2 && d->lastpk && G.target &&
                                readout_x3_supported(nwm, d->ch[nl - 1], d->ch[nl]) && d->wpk[nl - 2] &&
                                gemm_clip_x3_supported(nwm, d->ch[nl - 1], d->ch[nl - 2], d->ch[nl - 2]);
     int rc = det_forward(d, b, mag, db, st, pipe, fused_readout, G.xm_ready);
@@ -1229,11 +1310,21 @@ static int det_forward_backward(const aware_detector* d, const aware_batch* b, c
         dz_ready = true;
     } else {
         launch_head(db.act[nl - 1], b->d_frame_off, b->d_pool_off, G.target, db.pred, G.loss, G.best_loss,
-                    G.improved, dA, G.step, G.loss_kind, d->nbits, b->B, st, G.loss_add);
+                    G.improved, dA, G.step, G.loss_kind, d->nbits, b->B, st, G.loss_add, d->final_act);
     }
     LAUNCHCHK(); PROF(K_HEAD);
     for (int l = l_top; l >= 0; --l) {
         const int ci = d->ch[l], co = d->ch[l + 1];
+        if (!d->card_arch) {
+            // architecture variant (staged route): backward of the block's activation and norm, then the data-gradient GEMM
+            launch_norm_act_bwd(d->norm, d->act, dA, db.act[l], db.stash[l], b->d_frame_off, b->d_pool_off, db.rstd[l],
+                                d->nscale[l], co, b->B, b->max_frames / 2, st);
+            LAUNCHCHK(); PROF(K_INLRELU);
+            gemm_plain(pipe, dA, co, d->wT[l], co, d->wTpk[l], nullptr, dB, ci, b->NP, ci, co, st);
+            LAUNCHCHK(); PROF(K_GEMM);
+            float* t = dA; dA = dB; dB = t;
+            continue;
+        }
         if (!dz_ready) {
             launch_in_lrelu_bwd(dA, db.act[l], b->d_frame_off, b->d_pool_off, db.rstd[l], co, b->B, b->max_frames / 2, st);
             LAUNCHCHK(); PROF(K_INLRELU);
@@ -1386,6 +1477,7 @@ static int detector_train_core(const aware_detector* d, const aware_batch* b, co
                                float* loss_out, float* values, float* grad_mag, float* const* grad_weights,
                                float* const* grad_biases, void* workspace, size_t workspace_bytes, void* stream) {
     if (!d || !b || b->general) return AWARE_E_BADARG;
+    if (!d->card_arch) return AWARE_E_UNSUPPORTED;       // the training extension serves the model card's network only
     hipStream_t st = (hipStream_t)stream;
     Carver c(workspace, workspace_bytes);
     DetBufs o;

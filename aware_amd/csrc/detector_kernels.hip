@@ -912,10 +912,213 @@ __global__ __launch_bounds__(256) void in_lrelu_bwd_kernel(float* __restrict__ d
 }
 
 // ---------------------------------------------------------------------------------
+// Architecture variants (modules/conv1d.py:8-36, multibit_detector_net.py:82-96): the activation, its derivative (torch's
+// values at the kinks: ReLU'(0) = 0, LeakyReLU'(0) = 0.2) and the norm of a conv block, as a compile-time policy.  The
+// model card's blocks (InstanceNorm + LeakyReLU) keep the in_lrelu kernels above and the fused GEMM epilogues.
+// ---------------------------------------------------------------------------------
+template <int ACT>
+__device__ __forceinline__ float act_fwd(float u) {
+    if (ACT == kActRelu) return u > 0.f ? u : 0.f;
+    if (ACT == kActLRelu) return u > 0.f ? u : 0.2f * u;
+    if (ACT == kActGelu) return 0.5f * u * (1.f + erff(u * 0.70710678118654752f));      // exact GELU (approximate='none')
+    if (ACT == kActSwish) return u / (1.f + expf(-u));                                   // SiLU
+    if (ACT == kActTanh) return tanhf(u);
+    return 1.f / (1.f + expf(-u));                                                       // sigmoid
+}
+// f'(u); a = f(u)
+template <int ACT>
+__device__ __forceinline__ float act_grad(float u, float a) {
+    if (ACT == kActRelu) return u > 0.f ? 1.f : 0.f;
+    if (ACT == kActLRelu) return u > 0.f ? 1.f : 0.2f;
+    if (ACT == kActGelu)
+        return 0.5f * (1.f + erff(u * 0.70710678118654752f)) + u * 0.39894228040143268f * expf(-0.5f * u * u);
+    if (ACT == kActSwish) {
+        const float s = 1.f / (1.f + expf(-u));
+        return s * (1.f + u * (1.f - s));
+    }
+    if (ACT == kActTanh) return 1.f - a * a;
+    return a * (1.f - a);
+}
+
+// Conv block tail of a variant, in place: u = norm(z), z = act(u), u -> stash (if given).  Workgroup = (64 channels) x
+// (4 row groups) of one clip, as in_lrelu_fwd_kernel.  R > 0: InstanceNorm with the clip's column in registers (clips of up
+// to 4 R pooled frames); R = 0: from memory (any length; the only form of the element-wise norms).
+template <int NORM, int ACT, int R>
+__global__ __launch_bounds__(256) void norm_act_fwd_kernel(float* __restrict__ z, const int* __restrict__ frame_off,
+                                                           const int* __restrict__ pool_off, float* __restrict__ rstd,
+                                                           const float* __restrict__ scale, const float* __restrict__ shift,
+                                                           float* __restrict__ stash, int C) {
+    __shared__ float s[4][64];
+    const int b = blockIdx.y, c0 = blockIdx.x * 64;
+    const int r0 = pool_off[b], Tp = (frame_off[b + 1] - frame_off[b]) / 2;   // rows are 32-aligned per clip
+    const int cl = threadIdx.x & 63, g = threadIdx.x >> 6, c = c0 + cl;
+    if (Tp <= 0) return;
+    const bool ok = c < C;
+    float* x = z + (size_t)r0 * C + c;
+    float* sx = stash ? stash + (size_t)r0 * C + c : nullptr;
+    float v[R > 0 ? R : 1];
+    float mu = 0.f, rs = 1.f, sc = 1.f, sh = 0.f;
+    if (NORM == kNormInstance) {
+        float a = 0.f;
+        if (R > 0) {
+#pragma unroll
+            for (int i = 0; i < R; ++i) {
+                const int t = g + 4 * i;
+                v[i] = (ok && t < Tp) ? x[(size_t)t * C] : 0.f;
+                a += v[i];
+            }
+        } else if (ok) {
+            for (int t = g; t < Tp; t += 4) a += x[(size_t)t * C];
+        }
+        s[g][cl] = a;
+        __syncthreads();
+        mu = (s[0][cl] + s[1][cl] + s[2][cl] + s[3][cl]) / (float)Tp;
+        __syncthreads();
+        float q = 0.f;
+        if (R > 0) {
+#pragma unroll
+            for (int i = 0; i < R; ++i)
+                if (g + 4 * i < Tp) { const float d = v[i] - mu; q += d * d; }
+        } else if (ok) {
+            for (int t = g; t < Tp; t += 4) { const float d = x[(size_t)t * C] - mu; q += d * d; }
+        }
+        s[g][cl] = q;
+        __syncthreads();
+        rs = 1.0f / sqrtf((s[0][cl] + s[1][cl] + s[2][cl] + s[3][cl]) / (float)Tp + 1e-5f);
+        if (ok && g == 0) rstd[(size_t)b * C + c] = rs;
+    } else if (NORM == kNormAffine) {
+        if (ok) { sc = scale[c]; sh = shift[c]; }
+    }
+    if (!ok) return;
+    auto apply = [&](float zv, int t) {
+        const float u = NORM == kNormInstance ? (zv - mu) * rs : (NORM == kNormAffine ? zv * sc + sh : zv);
+        if (sx) sx[(size_t)t * C] = u;
+        x[(size_t)t * C] = act_fwd<ACT>(u);
+    };
+    if (NORM == kNormInstance && R > 0) {
+#pragma unroll
+        for (int i = 0; i < R; ++i)
+            if (g + 4 * i < Tp) apply(v[i], g + 4 * i);
+    } else {
+        for (int t = g; t < Tp; t += 4) apply(x[(size_t)t * C], t);
+    }
+}
+
+// backward of norm_act_fwd_kernel, in place on dA.  u from the stash, or from the output A where the activation can be
+// inverted (LeakyReLU; ReLU after an element-wise norm, whose derivative only needs the sign of u).
+template <int NORM, int ACT, int R>
+__global__ __launch_bounds__(256) void norm_act_bwd_kernel(float* __restrict__ dA, const float* __restrict__ A,
+                                                           const float* __restrict__ stash, const int* __restrict__ frame_off,
+                                                           const int* __restrict__ pool_off, const float* __restrict__ rstd,
+                                                           const float* __restrict__ scale, int C) {
+    __shared__ float s1[4][64], s2[4][64];
+    const int b = blockIdx.y, c0 = blockIdx.x * 64;
+    const int r0 = pool_off[b], Tp = (frame_off[b + 1] - frame_off[b]) / 2;   // rows are 32-aligned per clip
+    const int cl = threadIdx.x & 63, g = threadIdx.x >> 6, c = c0 + cl;
+    if (Tp <= 0) return;
+    const bool ok = c < C;
+    const int cc = ok ? c : C - 1;
+    float* d = dA + (size_t)r0 * C + cc;
+    const float* a = A + (size_t)r0 * C + cc;
+    const float* su = stash ? stash + (size_t)r0 * C + cc : nullptr;
+    // (u, dL/du) at row t
+    // (with a stash the output is not read: the block activations' derivatives need u only)
+    auto load = [&](int t, float& u, float& du) {
+        const float av = su ? 0.f : a[(size_t)t * C];
+        u = su ? su[(size_t)t * C] : (ACT == kActLRelu ? (av > 0.f ? av : av * 5.0f) : av);
+        du = d[(size_t)t * C] * act_grad<ACT>(u, av);
+    };
+    if (NORM != kNormInstance) {
+        if (!ok) return;
+        const float sc = NORM == kNormAffine ? scale[c] : 1.f;
+        for (int t = g; t < Tp; t += 4) {
+            float u, du;
+            load(t, u, du);
+            d[(size_t)t * C] = NORM == kNormAffine ? sc * du : du;
+        }
+        return;
+    }
+    float uu[R > 0 ? R : 1], dd[R > 0 ? R : 1];
+    float p1 = 0.f, p2 = 0.f;
+    if (R > 0) {
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+            const int t = g + 4 * i;
+            const bool valid = ok && t < Tp;
+            load(t < Tp ? t : Tp - 1, uu[i], dd[i]);
+            if (!valid) { uu[i] = 0.f; dd[i] = 0.f; }
+            p1 += dd[i]; p2 += dd[i] * uu[i];
+        }
+    } else if (ok) {
+        for (int t = g; t < Tp; t += 4) {
+            float u, du;
+            load(t, u, du);
+            p1 += du; p2 += du * u;
+        }
+    }
+    s1[g][cl] = p1; s2[g][cl] = p2;
+    __syncthreads();
+    const float m1 = (s1[0][cl] + s1[1][cl] + s1[2][cl] + s1[3][cl]) / (float)Tp;
+    const float m2 = (s2[0][cl] + s2[1][cl] + s2[2][cl] + s2[3][cl]) / (float)Tp;
+    if (!ok) return;
+    const float rs = rstd[(size_t)b * C + c];
+    if (R > 0) {
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+            const int t = g + 4 * i;
+            if (t < Tp) d[(size_t)t * C] = rs * (dd[i] - m1 - uu[i] * m2);
+        }
+    } else {
+        for (int t = g; t < Tp; t += 4) {
+            float u, du;
+            load(t, u, du);
+            d[(size_t)t * C] = rs * (du - m1 - u * m2);
+        }
+    }
+}
+
+template <int NORM, int ACT>
+static void norm_act_launch(bool fwd, float* z, const float* A, const int* frame_off, const int* pool_off, float* rstd,
+                            const float* scale, const float* shift, float* stash, int C, int B, int max_pooled, hipStream_t st) {
+    const dim3 grid((C + 63) / 64, B), block(256);
+    if (NORM == kNormInstance && max_pooled <= 128) {
+        if (fwd) hipLaunchKernelGGL((norm_act_fwd_kernel<NORM, ACT, 32>), grid, block, 0, st, z, frame_off, pool_off, rstd, scale, shift, stash, C);
+        else hipLaunchKernelGGL((norm_act_bwd_kernel<NORM, ACT, 32>), grid, block, 0, st, z, A, stash, frame_off, pool_off, rstd, scale, C);
+    } else if (NORM == kNormInstance && max_pooled <= 320) {
+        if (fwd) hipLaunchKernelGGL((norm_act_fwd_kernel<NORM, ACT, 80>), grid, block, 0, st, z, frame_off, pool_off, rstd, scale, shift, stash, C);
+        else hipLaunchKernelGGL((norm_act_bwd_kernel<NORM, ACT, 80>), grid, block, 0, st, z, A, stash, frame_off, pool_off, rstd, scale, C);
+    } else {
+        if (fwd) hipLaunchKernelGGL((norm_act_fwd_kernel<NORM, ACT, 0>), grid, block, 0, st, z, frame_off, pool_off, rstd, scale, shift, stash, C);
+        else hipLaunchKernelGGL((norm_act_bwd_kernel<NORM, ACT, 0>), grid, block, 0, st, z, A, stash, frame_off, pool_off, rstd, scale, C);
+    }
+}
+template <int NORM>
+static void norm_act_dispatch(int act, bool fwd, float* z, const float* A, const int* frame_off, const int* pool_off, float* rstd,
+                              const float* scale, const float* shift, float* stash, int C, int B, int max_pooled, hipStream_t st) {
+    switch (act) {
+        case kActRelu: norm_act_launch<NORM, kActRelu>(fwd, z, A, frame_off, pool_off, rstd, scale, shift, stash, C, B, max_pooled, st); break;
+        case kActLRelu: norm_act_launch<NORM, kActLRelu>(fwd, z, A, frame_off, pool_off, rstd, scale, shift, stash, C, B, max_pooled, st); break;
+        case kActGelu: norm_act_launch<NORM, kActGelu>(fwd, z, A, frame_off, pool_off, rstd, scale, shift, stash, C, B, max_pooled, st); break;
+        default: norm_act_launch<NORM, kActSwish>(fwd, z, A, frame_off, pool_off, rstd, scale, shift, stash, C, B, max_pooled, st); break;
+    }
+}
+static void norm_act(int norm, int act, bool fwd, float* z, const float* A, const int* frame_off, const int* pool_off, float* rstd,
+                     const float* scale, const float* shift, float* stash, int C, int B, int max_pooled, hipStream_t st) {
+    if (norm == kNormInstance)
+        norm_act_dispatch<kNormInstance>(act, fwd, z, A, frame_off, pool_off, rstd, scale, shift, stash, C, B, max_pooled, st);
+    else if (norm == kNormAffine)
+        norm_act_dispatch<kNormAffine>(act, fwd, z, A, frame_off, pool_off, rstd, scale, shift, stash, C, B, max_pooled, st);
+    else
+        norm_act_dispatch<kNormNone>(act, fwd, z, A, frame_off, pool_off, rstd, scale, shift, stash, C, B, max_pooled, st);
+}
+
+// ---------------------------------------------------------------------------------
 // BRH read-out + loss + gradient seed.  One 64-thread workgroup per clip.
 // loss_kind: 0 push_extremes, 1 mse, 2 hinge, 3 sign, 4 push_sigmoid, 5 ber  (embedding/losses.py)
+// FA: the final activation (act_fwd / act_grad; the model card's tanh is written out as it always was).
 // If dA3 == nullptr only the prediction is produced (detect path).
 // ---------------------------------------------------------------------------------
+template <int FA>
 __global__ __launch_bounds__(256) void head_kernel(const float* __restrict__ a3, const int* __restrict__ frame_off, const int* __restrict__ pool_off,
                                                     const float* __restrict__ target, float* __restrict__ pred,
                                                     float* __restrict__ loss_out, float* __restrict__ best_loss,
@@ -932,9 +1135,10 @@ __global__ __launch_bounds__(256) void head_kernel(const float* __restrict__ a3,
     __syncthreads();
     if (g == 0) mean[c] = (part[0][c] + part[1][c] + part[2][c] + part[3][c]) / (float)Tp;
     __syncthreads();
-    float lterm = 0.f, dp = 0.f, p = 0.f;
+    float lterm = 0.f, dp = 0.f, p = 0.f, xd = 0.f;
     if (g == 0 && c < nbits) {
-        p = tanhf(mean[2 * c] - mean[2 * c + 1]);
+        xd = mean[2 * c] - mean[2 * c + 1];
+        p = FA == kActTanh ? tanhf(xd) : act_fwd<FA>(xd);
         pred[b * nbits + c] = p;
         if (target) {
             const float tg = target[b * nbits + c];
@@ -957,7 +1161,7 @@ __global__ __launch_bounds__(256) void head_kernel(const float* __restrict__ a3,
             if (step && b == 0) *step += 1;
         }
         if (dA3 && c < nbits) {
-            const float dpre = dp * (1.f - p * p);             // tanh'
+            const float dpre = dp * (FA == kActTanh ? 1.f - p * p : act_grad<FA>(xd, p));   // tanh' on the card
             dm[2 * c] = dpre; dm[2 * c + 1] = -dpre;
         }
     }
@@ -1277,9 +1481,28 @@ void launch_in_lrelu_bwd(float* dA, const float* A, const int* frame_off, const 
 }
 void launch_head(const float* a3, const int* frame_off, const int* pool_off, const float* target, float* pred, float* loss,
                  float* best_loss, int* improved, float* dA3, int* step, int loss_kind, int nbits, int B,
-                 hipStream_t st, const float* loss_add) {
-    hipLaunchKernelGGL(head_kernel, dim3(B), dim3(256), 0, st, a3, frame_off, pool_off, target, pred, loss, best_loss, improved, dA3,
-                       step, loss_kind, nbits, loss_add);
+                 hipStream_t st, const float* loss_add, int final_act) {
+#define AW_HEAD(FA)                                                                                                         \
+    hipLaunchKernelGGL(head_kernel<FA>, dim3(B), dim3(256), 0, st, a3, frame_off, pool_off, target, pred, loss, best_loss, improved, \
+                       dA3, step, loss_kind, nbits, loss_add)
+    switch (final_act) {
+        case kActRelu: AW_HEAD(kActRelu); break;
+        case kActLRelu: AW_HEAD(kActLRelu); break;
+        case kActGelu: AW_HEAD(kActGelu); break;
+        case kActSwish: AW_HEAD(kActSwish); break;
+        case kActSigmoid: AW_HEAD(kActSigmoid); break;
+        default: AW_HEAD(kActTanh); break;
+    }
+#undef AW_HEAD
+}
+void launch_norm_act_fwd(int norm, int act, float* z, const int* frame_off, const int* pool_off, float* rstd, const float* scale,
+                         const float* shift, float* stash, int C, int B, int max_pooled, hipStream_t st) {
+    norm_act(norm, act, true, z, nullptr, frame_off, pool_off, rstd, scale, shift, stash, C, B, max_pooled, st);
+}
+void launch_norm_act_bwd(int norm, int act, float* dA, const float* A, const float* stash, const int* frame_off, const int* pool_off,
+                         const float* rstd, const float* scale, int C, int B, int max_pooled, hipStream_t st) {
+    norm_act(norm, act, false, dA, A, frame_off, pool_off, const_cast<float*>(rstd), scale, nullptr, const_cast<float*>(stash), C, B,
+             max_pooled, st);
 }
 
 }  // namespace aware

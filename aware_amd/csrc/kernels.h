@@ -180,10 +180,26 @@ void launch_in_lrelu_fwd(float* z, const int* frame_off, const int* pool_off, fl
 // backward of the same, in place on dA (A is the post-activation output of the forward)
 void launch_in_lrelu_bwd(float* dA, const float* A, const int* frame_off, const int* pool_off, const float* rstd, int C, int B,
                          int max_pooled, hipStream_t st);
-// BRH + loss + dL/dA3; also best-loss tracking
+// ---- architecture variants of the detector (aware_detector_arch; the values are the header's AWARE_ACT_* / AWARE_NORM_* /
+// AWARE_FINAL_*): the norm and activation of every conv block and the read-out's final activation
+constexpr int kActRelu = 0, kActLRelu = 1, kActGelu = 2, kActSwish = 3, kActTanh = 4, kActSigmoid = 5;
+constexpr int kNormInstance = 0, kNormAffine = 1, kNormNone = 2;
+// whether the backward of a block needs its pre-activation u (the norm's output) kept from the forward: every activation but
+// LeakyReLU can not be inverted from its output, and the InstanceNorm backward needs u at every position (also where ReLU gave 0)
+AW_HD bool norm_act_needs_stash(int norm, int act) {
+    return !(act == kActLRelu || (act == kActRelu && norm != kNormInstance));
+}
+// conv block tail of a variant, in place on z [NP][C]: u = norm(z) (InstanceNorm over time, saves rstd [B][C]; affine
+// u = z * scale[c] + shift[c]; or identity), z = act(u); stash [NP][C] receives u (null: not written)
+void launch_norm_act_fwd(int norm, int act, float* z, const int* frame_off, const int* pool_off, float* rstd, const float* scale,
+                         const float* shift, float* stash, int C, int B, int max_pooled, hipStream_t st);
+// backward of the same, in place on dA: u read from stash, or recovered from the output A (norm_act_needs_stash false)
+void launch_norm_act_bwd(int norm, int act, float* dA, const float* A, const float* stash, const int* frame_off, const int* pool_off,
+                         const float* rstd, const float* scale, int C, int B, int max_pooled, hipStream_t st);
+// BRH + loss + dL/dA3; also best-loss tracking.  final_act: kActRelu .. kActSigmoid applied to even - odd (the card: tanh)
 void launch_head(const float* a3, const int* frame_off, const int* pool_off, const float* target, float* pred, float* loss,
                  float* best_loss, int* improved, float* dA3, int* step, int loss_kind, int nbits, int B,
-                 hipStream_t st, const float* loss_add = nullptr);
+                 hipStream_t st, const float* loss_add = nullptr, int final_act = kActTanh);
 void launch_gemm_nt_splitk(const float* A, int lda, const float* Bt, int ldb, float* Cpart, int ldc, int M, int N, int K,
                            int ksplit, hipStream_t st);
 void launch_tail(const float* zpart, int nsplit, size_t slab, const float* bias, const int* frame_off, const int* pool_off,

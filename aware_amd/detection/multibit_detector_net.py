@@ -1,5 +1,9 @@
 """AWAREDetectorNet: frozen, seed-initialised detector (mel -> InstanceNorm -> global standardise
--> pool -> 4 x [conv1x1, InstanceNorm, LeakyReLU] -> bitwise read-out head).
+-> pool -> 4 x [conv1x1, norm, activation] -> bitwise read-out head with its final activation).
+
+The model card's blocks are InstanceNorm + LeakyReLU with a tanh read-out; the other choices of the
+reference's detection_net_cfg (activation, norm_layer, final_activation; modules/conv1d.py:8-36,
+multibit_detector_net.py:82-96) run the staged route of the C ABI (aware_detector_create_ex).
 
 Reference: src/AWARE/detection/multibit_detector_net.py:17-140.  The weights are never trained
 anywhere in the reference (multibit_embedder.py:76-77 freezes them; there is no checkpoint), so
@@ -15,6 +19,35 @@ from .mel import mel_filter_bank
 
 DETECTOR_SEED = 328656719      # multibit_detector_net.py:78
 
+# Conv1dBlock._get_activation (modules/conv1d.py:27-36): an unknown name silently becomes ReLU
+BLOCK_ACTIVATIONS = {"relu": 0, "leaky_relu": 1, "gelu": 2, "swish": 3}
+# Conv1dBlock._get_norm_layer (:17-25)
+NORM_LAYERS = {"instance": 0, "batch": 1, "none": 2}
+# AWAREDetectorNet._get_activation (multibit_detector_net.py:82-96): anything else raises ValueError
+FINAL_ACTIVATIONS = {"relu": 0, "leaky_relu": 1, "gelu": 2, "swish": 3, "tanh": 4, "sigmoid": 5}
+CARD_ARCH = ("leaky_relu", "instance", "tanh")
+BATCH_NORM_EPS = 1e-5          # nn.BatchNorm1d default
+
+
+def block_activation(name: str) -> str:
+    """The activation a Conv1dBlock builds for `name` (case-insensitive; unknown -> relu, as the reference)."""
+    n = name.lower()
+    return n if n in BLOCK_ACTIVATIONS else "relu"
+
+
+def norm_layer_name(name: str) -> str:
+    n = name.lower()
+    if n not in NORM_LAYERS:
+        raise ValueError(f"Invalid norm layer: {name}")
+    return n
+
+
+def final_activation_name(name: str) -> str:
+    n = name.lower()
+    if n not in FINAL_ACTIVATIONS:
+        raise ValueError(f"Invalid activation: {name}")
+    return n
+
 
 class AWAREDetectorNet(BaseDetectorNet):
     def __init__(self, sample_rate: int = 16000, n_fft: int = 1024, n_mels: int = 128,
@@ -24,18 +57,19 @@ class AWAREDetectorNet(BaseDetectorNet):
                  final_activation: str = "tanh"):
         n_filters = list(n_filters)
         assert len(n_filters) == num_blocks, "Number of filters must match number of blocks"
+        # the reference's own validation, in its order: the blocks' norm layers (ValueError), then the final activation
+        self.norm_layer = norm_layer_name(norm_layer)
+        self.activation = block_activation(activation)
+        self.final_activation = final_activation_name(final_activation)
         unsupported = []
         if (kernel_size, stride, padding) != (1, 1, 0):
             unsupported.append("kernel_size/stride/padding other than 1/1/0")
         if (initial_pool_size, initial_pool_stride) != (2, 2):
             unsupported.append("initial pool other than (2, 2)")
-        if norm_layer.lower() != "instance" or activation.lower() != "leaky_relu" or final_activation.lower() != "tanh":
-            unsupported.append("norm/activation other than instance/leaky_relu/tanh")
         if unsupported:
-            raise NotImplementedError("the HIP detector implements the reference's model card only: " + "; ".join(unsupported))
+            raise NotImplementedError("the HIP detector implements 1x1 convolutions after a (2, 2) pool only: " + "; ".join(unsupported))
         self.sample_rate, self.n_fft, self.n_mels = sample_rate, n_fft, n_mels
         self.num_blocks, self.initial_pool_size, self.output_length = num_blocks, initial_pool_size, output_length
-        self.final_activation = final_activation
         self.channels = [n_mels] + n_filters + [2 * output_length]
         self.mel_basis = mel_filter_bank(sample_rate, n_fft, n_mels)
         # torch.manual_seed(seed); self.apply(_init_weights): xavier-uniform on each Conv1d weight
@@ -48,7 +82,33 @@ class AWAREDetectorNet(BaseDetectorNet):
             torch.nn.init.xavier_uniform_(w, generator=gen)
             self.weights.append(w[:, :, 0].contiguous().numpy())
             self.biases.append(np.zeros(cout, dtype=np.float32))
+        # BatchNorm1d parameters and running statistics of every block (eval mode: both reference entry points call .eval());
+        # a fresh net's values.  BatchNorm has no Conv / Linear weight, so the xavier draws above do not depend on the norm
+        self.batch_norm = None
+        if self.norm_layer == "batch":
+            self.batch_norm = [{"weight": np.ones(c, np.float32), "bias": np.zeros(c, np.float32),
+                                "running_mean": np.zeros(c, np.float32), "running_var": np.ones(c, np.float32),
+                                "eps": BATCH_NORM_EPS} for c in self.channels[1:]]
         self._dev = None
+
+    @property
+    def is_card_arch(self) -> bool:
+        """Whether the blocks and the read-out are the model card's (the fused kernels); else the staged route."""
+        return (self.activation, self.norm_layer, self.final_activation) == CARD_ARCH
+
+    def architecture(self):
+        """The aware_detector_arch of this network: enum values, and for BatchNorm the folded eval-mode map
+        scale = weight / sqrt(running_var + eps), shift = bias - running_mean * scale per block (computed in float64)."""
+        arch = {"activation": BLOCK_ACTIVATIONS[self.activation], "norm": NORM_LAYERS[self.norm_layer],
+                "final_activation": FINAL_ACTIVATIONS[self.final_activation], "scale": None, "shift": None}
+        if self.batch_norm is not None:
+            arch["scale"], arch["shift"] = [], []
+            for bn in self.batch_norm:
+                sc = np.asarray(bn["weight"], np.float64) / np.sqrt(np.asarray(bn["running_var"], np.float64) + bn["eps"])
+                arch["scale"].append(sc.astype(np.float32))
+                arch["shift"].append((np.asarray(bn["bias"], np.float64) -
+                                      np.asarray(bn["running_mean"], np.float64) * sc).astype(np.float32))
+        return arch
 
     def eval(self):
         return self
@@ -60,12 +120,15 @@ class AWAREDetectorNet(BaseDetectorNet):
         for w, b in zip(self.weights, self.biases):
             yield w
             yield b
+        for bn in self.batch_norm or ():
+            yield bn["weight"]
+            yield bn["bias"]
 
     def device_weights(self, plan):
         """Device copy (aware_detector) bound to a plan; created on first use."""
         from ..runtime import DetectorWeights
         if self._dev is None or self._dev.plan is not plan:
-            self._dev = DetectorWeights(plan, self.mel_basis, self.weights, self.biases)
+            self._dev = DetectorWeights(plan, self.mel_basis, self.weights, self.biases, arch=self.architecture())
         return self._dev
 
     def forward(self, stft_magnitude: torch.Tensor) -> torch.Tensor:
@@ -80,6 +143,7 @@ class AWAREDetectorNet(BaseDetectorNet):
         total = int(sum(int(np.prod(p.shape)) for p in self.parameters()))
         return {"sample_rate": self.sample_rate, "n_fft": self.n_fft, "n_mels": self.n_mels,
                 "num_blocks": self.num_blocks, "output_length": self.output_length,
+                "activation": self.activation, "norm_layer": self.norm_layer,
                 "final_activation": self.final_activation, "total_parameters": total, "trainable_parameters": 0}
 
 

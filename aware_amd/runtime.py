@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import AwareHipError, EmbedConfig, check, load_library, require_gpu
+from ._lib import AwareHipError, DetectorArch, EmbedConfig, check, load_library, require_gpu
 
 SPEC_STRIDE = 256
 FULL_STRIDE = 520
@@ -325,9 +325,17 @@ def detector_backward(plan: Plan, det: "DetectorWeights", batch: Batch, mag: tor
     return vals, gmag
 
 
+def require_card_arch(det: "DetectorWeights", what: str):
+    """The detector-training extension serves the model card's architecture only (the C ABI returns AWARE_E_UNSUPPORTED)."""
+    if not det.is_card:
+        raise NotImplementedError(f"{what}: detector training supports the model card's architecture only "
+                                  "(instance norm, leaky_relu blocks, tanh read-out)")
+
+
 def detector_weight_gradients(plan: Plan, det: "DetectorWeights", batch: Batch, mag: torch.Tensor, grad_values: torch.Tensor):
     """EXTENSION (detector training): (values, grad_mag, [dL/dW_l], [dL/db_l]) of the network for the upstream gradient
     grad_values [B, n_bits] (aware_detector_weight_gradients)."""
+    require_card_arch(det, "aware_detector_weight_gradients")
     lib = plan.lib
     nbytes = lib.aware_detector_train_workspace_bytes(batch.h, det.h)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=mag.device)
@@ -349,6 +357,7 @@ def detector_train_gradients(plan: Plan, det: "DetectorWeights", batch: Batch, m
     """EXTENSION (detector training): ONE forward + backward of the network with the loss evaluated on the device
     (aware_detector_train_gradients): (values [B, n_bits], per-clip losses [B], [dL/dW_l], [dL/db_l]) -- gradients of the SUM
     of the per-clip losses.  grad_weights / grad_biases: tensors to write into (e.g. views of one flat bucket)."""
+    require_card_arch(det, "aware_detector_train_gradients")
     lib = plan.lib
     nbytes = lib.aware_detector_train_workspace_bytes(batch.h, det.h)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=mag.device)
@@ -368,7 +377,8 @@ def detector_train_gradients(plan: Plan, det: "DetectorWeights", batch: Batch, m
 class DetectorWeights:
     """Device copy of the frozen detector (aware_detector)."""
 
-    def __init__(self, plan: Plan, mel_basis: np.ndarray, weights, biases):
+    def __init__(self, plan: Plan, mel_basis: np.ndarray, weights, biases, arch: dict = None):
+        """arch: AWAREDetectorNet.architecture() (aware_detector_create_ex), or None for the model card's network."""
         require_gpu()
         self.lib = load_library()
         self.plan = plan
@@ -383,13 +393,25 @@ class DetectorWeights:
         wp = (C.c_void_p * nl)(*[w.ctypes.data for w in ws])
         bp = (C.c_void_p * nl)(*[b.ctypes.data for b in bs])
         h = C.c_void_p()
-        rc = self.lib.aware_detector_create(C.byref(h), plan.h, C.c_void_p(mel.ctypes.data), mel.shape[0], nl,
-                                            (C.c_int * (nl + 1))(*chans), wp, bp)
-        check(rc, "aware_detector_create")
+        if arch is None:
+            rc = self.lib.aware_detector_create(C.byref(h), plan.h, C.c_void_p(mel.ctypes.data), mel.shape[0], nl,
+                                                (C.c_int * (nl + 1))(*chans), wp, bp)
+            check(rc, "aware_detector_create")
+        else:
+            a = DetectorArch(arch["activation"], arch["norm"], arch["final_activation"], None, None)
+            if arch.get("scale") is not None:
+                self._norm = [np.ascontiguousarray(v, dtype=np.float32) for v in list(arch["scale"]) + list(arch["shift"])]
+                a.norm_scale = (C.c_void_p * nl)(*[v.ctypes.data for v in self._norm[:nl]])
+                a.norm_shift = (C.c_void_p * nl)(*[v.ctypes.data for v in self._norm[nl:]])
+            rc = self.lib.aware_detector_create_ex(C.byref(h), plan.h, C.c_void_p(mel.ctypes.data), mel.shape[0], nl,
+                                                   (C.c_int * (nl + 1))(*chans), wp, bp, C.byref(a))
+            check(rc, "aware_detector_create_ex")
         self.h = h
+        self.is_card = bool(self.lib.aware_detector_is_card(h))
 
     def update(self, weights, biases):
         """EXTENSION (detector training): replace the parameters in place (same shapes), aware_detector_update."""
+        require_card_arch(self, "aware_detector_update")
         torch.cuda.synchronize()
         ws = [np.ascontiguousarray(w, dtype=np.float32) for w in weights]
         bs = [np.ascontiguousarray(b, dtype=np.float32) for b in biases]
@@ -400,6 +422,7 @@ class DetectorWeights:
     def update_device(self, weights, biases):
         """EXTENSION (detector training): the same from DEVICE tensors, asynchronous on the current stream -- no host round trip
         (aware_detector_update_device: copies, transposes and both packed images rebuilt by kernels)."""
+        require_card_arch(self, "aware_detector_update_device")
         ws = [w if w.is_contiguous() else w.contiguous() for w in weights]
         bs = [b if b.is_contiguous() else b.contiguous() for b in biases]
         wp = (C.c_void_p * len(ws))(*[w.data_ptr() for w in ws])

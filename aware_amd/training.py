@@ -34,6 +34,9 @@ class DetectorTrainer:
         from .embedding.optimizers import get_optimizer, step_table
         self.detector = detector
         self.net = detector.detection_net
+        if not getattr(self.net, "is_card_arch", True):
+            raise NotImplementedError("DetectorTrainer supports the model card's detector architecture only "
+                                      "(instance norm, leaky_relu blocks, tanh read-out)")
         self.sample_rate = sample_rate
         shapes = [np.asarray(w).shape for w in self.net.weights] + [np.asarray(b).shape for b in self.net.biases]
         sizes = [int(np.prod(sh)) for sh in shapes]

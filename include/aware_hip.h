@@ -58,7 +58,7 @@ typedef struct aware_embed aware_embed;
 /* ABI version (200: no process-global knobs, the kernel choices live in aware_embed_config; 300: conv_pipe 0 = f16 two-term
  * kernels, optimiser / scheduler registries, device-side detector training, aware_stft_bwd for any clip length; 310: general
  * STFT geometry -- aware_plan_create_ex, aware_plan_spectrum_stride, aware_plan_is_general, aware_batch_create_for_plan,
- * aware_nola_check) */
+ * aware_nola_check; 320: detector architecture variants -- aware_detector_create_ex, aware_detector_is_card) */
 int aware_version(void);
 /* text of the last failed HIP runtime call on the calling thread (thread-local) */
 const char* aware_last_hip_error(void);
@@ -177,6 +177,47 @@ int aware_detector_create(aware_detector** out, const aware_plan* plan, const fl
                           int n_layers, const int* channels, const float* const* weights,
                           const float* const* biases);
 void aware_detector_destroy(aware_detector* det);
+
+/* Architecture variants of the network (detection_net_cfg of the model card; modules/conv1d.py:8-36 and
+ * multibit_detector_net.py:82-96).  activation: the activation of every conv block; norm: its norm -- INSTANCE =
+ * InstanceNorm1d (no affine, biased variance, eps 1e-5, per clip over time), BATCH = BatchNorm1d in eval mode, given as the
+ * per-channel affine map u = z * norm_scale[l][c] + norm_shift[l][c] (scale = gamma / sqrt(running_var + eps), shift =
+ * beta - running_mean * scale; host arrays of channels[l+1] floats for every l < n_layers, BATCH only, may be NULL
+ * otherwise), NONE = identity (the conv bias reaches the activation); final_activation: the activation of the bitwise
+ * read-out head, applied to even - odd.  LEAKY_RELU has slope 0.2, GELU is the exact erf form, SWISH is SiLU; at the kinks
+ * the derivatives are torch's (ReLU'(0) = 0, LeakyReLU'(0) = 0.2).
+ * aware_detector_create_ex(..., arch) with {LEAKY_RELU, INSTANCE, TANH} is aware_detector_create: the model card's network,
+ * served by the fused conv-block, read-out and tail kernels.  Every other architecture runs the staged route (plain GEMM +
+ * bias, a norm / activation kernel, the read-out kernel; a batch-sized stash of pre-activations per block in the workspace,
+ * counted by the *_workspace_bytes functions) through aware_detect, aware_detector_forward / _backward and the aware_embed_*
+ * loop, with no other entry point.  The training extension (aware_detector_train_gradients, _weight_gradients, _update,
+ * _update_device) returns AWARE_E_UNSUPPORTED for it.  Enum values out of range: AWARE_E_BADARG; a general plan:
+ * AWARE_E_UNSUPPORTED. */
+#define AWARE_ACT_RELU 0
+#define AWARE_ACT_LEAKY_RELU 1
+#define AWARE_ACT_GELU 2
+#define AWARE_ACT_SWISH 3
+#define AWARE_NORM_INSTANCE 0
+#define AWARE_NORM_BATCH 1
+#define AWARE_NORM_NONE 2
+#define AWARE_FINAL_RELU 0
+#define AWARE_FINAL_LEAKY_RELU 1
+#define AWARE_FINAL_GELU 2
+#define AWARE_FINAL_SWISH 3
+#define AWARE_FINAL_TANH 4
+#define AWARE_FINAL_SIGMOID 5
+typedef struct aware_detector_arch {
+    int activation;                      /* AWARE_ACT_*   */
+    int norm;                            /* AWARE_NORM_*  */
+    int final_activation;                /* AWARE_FINAL_* */
+    const float* const* norm_scale;      /* AWARE_NORM_BATCH: [n_layers] host arrays [channels[l+1]] */
+    const float* const* norm_shift;
+} aware_detector_arch;
+int aware_detector_create_ex(aware_detector** out, const aware_plan* plan, const float* mel_basis, int n_mels,
+                             int n_layers, const int* channels, const float* const* weights,
+                             const float* const* biases, const aware_detector_arch* arch);
+/* 1 when the detector has the model card's architecture (fused kernels), 0 for a variant (staged route) */
+int aware_detector_is_card(const aware_detector* det);
 
 /* AWAREDetector.detect (detection/multibit_detector.py:28-42), batched: normalise, STFT, |.|,
  * zero the out-of-band bins, network forward.  values: dev f32 [B][n_bits].
