@@ -90,6 +90,7 @@ SIGNATURES = {
     "aware_plan_create_ex": (_i, [C.POINTER(_vp), _i, _i, _i, _i, _i, _i, _i]),
     "aware_plan_spectrum_stride": (_i, [_vp]),
     "aware_plan_is_general": (_i, [_vp]),
+    "aware_plan_band_stride": (_i, [_vp]),
     "aware_nola_check": (_i, [_i, _i, _i, _i, _i]),
     "aware_batch_create": (_i, [C.POINTER(_vp), _i, _pi, _pi]),
     "aware_batch_destroy": (None, [_vp]),

@@ -92,11 +92,12 @@ struct aware_batch {
 struct aware_detector {
     int n_mels = 0, n_layers = 0, nbits = 0;
     int band_lo = 0, nband = 0;
+    int stride = kFS;        // floats per band row of the plan the detector was created for
     int ch[8] = {0};
     int maxc = 0;
     float* mem = nullptr;
-    float* melT = nullptr;   // [n_mels][256]  (Bt of the forward mel GEMM)
-    float* melB = nullptr;   // [256][n_mels]  (Bt of its data-gradient)
+    float* melT = nullptr;   // [n_mels][stride]  (Bt of the forward mel GEMM)
+    float* melB = nullptr;   // [stride][n_mels]  (Bt of its data-gradient)
     float* w[8] = {nullptr};   // [Cout][Cin]
     float* wT[8] = {nullptr};  // [Cin][Cout]
     // the same two operands split into three bf16 planes in MFMA fragment order (gemm_x3.hip); null when the
@@ -114,7 +115,8 @@ struct aware_detector {
     void* h2mem = nullptr;
     float* bias[8] = {nullptr};
     // the mel filter bank as two taps per band column (a triangular bank has at most two adjacent non-zero weights per bin):
-    // melw [kFS] float2, melm [kFS] first tap's mel index (<= 126); null when the basis handed over is not of that form
+    // melw [kFS] float2, melm [kFS] first tap's mel index (<= 126); null when the basis handed over is not of that form or the
+    // band has the wide layout (which takes the dense mel GEMMs)
     void* mel2mem = nullptr;
     float2* melw = nullptr;
     unsigned char* melm = nullptr;
@@ -139,7 +141,7 @@ static_assert(AWARE_NORM_INSTANCE == kNormInstance && AWARE_NORM_BATCH == kNormA
 // whether the staged route keeps the pre-activation of every block for the backward (DetBufs::stash)
 static bool det_needs_stash(const aware_detector* d) { return !d->card_arch && norm_act_needs_stash(d->norm, d->act); }
 
-extern "C" int aware_version(void) { return 320; }
+extern "C" int aware_version(void) { return 330; }
 extern "C" const char* aware_last_hip_error(void) { return g_last_err.c_str(); }
 
 // ---------------------------------------------------------------------------------------------
@@ -237,6 +239,7 @@ static int gen_plan_create(aware_plan** out, int n_fft, int hop, int win_length,
     p->gdev.env = d + o_env;
     p->dev.band_lo = band_lo_bin;                 // (not used by the general kernels)
     p->dev.nband = band_hi_bin - band_lo_bin + 1;
+    p->dev.stride = kFS;
     p->w2h = w2;
     p->envh = env;
     *out = p;
@@ -255,7 +258,8 @@ extern "C" int aware_plan_create_ex(aware_plan** out, int n_fft, int hop, int wi
         return gen_plan_create(out, n_fft, hop, win_length, window, band_lo_bin, band_hi_bin);
     if (window != 0 && window != 1) return AWARE_E_BADARG;
     const int nband = band_hi_bin - band_lo_bin + 1;
-    if (band_lo_bin < 1 || band_hi_bin > 511 || nband < 1 || nband > kFS) return AWARE_E_UNSUPPORTED;
+    // any band of the one-sided spectrum: narrow layout (kFS columns) inside bins 1..511 up to 256 bins wide, else wide
+    if (band_lo_bin < 0 || band_hi_bin > kNfft / 2 || nband < 1) return AWARE_E_UNSUPPORTED;
     const double PI = 3.14159265358979323846;
     std::vector<float> h(2 * 512 + 2 * 512 + 1024 + 1024 + 3 * 768);
     float* tw512 = h.data();
@@ -298,6 +302,7 @@ extern "C" int aware_plan_create_ex(aware_plan** out, int n_fft, int hop, int wi
     p->dev.env_tab = d + 4096;
     p->dev.band_lo = band_lo_bin;
     p->dev.nband = nband;
+    p->dev.stride = band_stride_for(band_lo_bin, band_hi_bin);
     *out = p;
     return AWARE_OK;
 }
@@ -310,6 +315,7 @@ extern "C" int aware_plan_spectrum_stride(const aware_plan* p) {
     return p ? (p->general ? p->gdev.stride : AWARE_FULL_STRIDE) : AWARE_E_BADARG;
 }
 extern "C" int aware_plan_is_general(const aware_plan* p) { return p ? p->general : AWARE_E_BADARG; }
+extern "C" int aware_plan_band_stride(const aware_plan* p) { return p ? p->dev.stride : AWARE_E_BADARG; }
 
 extern "C" int aware_nola_check(int n_fft, int hop, int win_length, int window, int n_samples) {
     const int rc = gen_validate(n_fft, hop, win_length, window);
@@ -717,27 +723,28 @@ static int detector_upload(aware_detector* d, const float* mel_basis, const floa
                            const float* const* biases, bool alloc) {
     const int n_mels = d->n_mels, n_layers = d->n_layers;
     const int* channels = d->ch;
-    size_t total = (size_t)n_mels * kFS * 2;
+    const int S = d->stride;
+    size_t total = (size_t)n_mels * S * 2;
     for (int i = 0; i < n_layers; ++i) total += (size_t)channels[i] * channels[i + 1] * 2 + channels[i + 1];
     std::vector<float> h(total, 0.f);
     size_t o = 0;
     const int nbins = kNfft / 2 + 1;
     const int lo = d->band_lo, nb = d->nband;
-    size_t o_melT = o; o += (size_t)n_mels * kFS;
-    size_t o_melB = o; o += (size_t)kFS * n_mels;
+    size_t o_melT = o; o += (size_t)n_mels * S;
+    size_t o_melB = o; o += (size_t)S * n_mels;
     // only the in-band columns of the mel basis ever multiply non-zero magnitudes
     // (multibit_embedder.py:104, multibit_detector.py:34-37 zero the rest)
     for (int j = 0; j < n_mels; ++j)
         for (int f = 0; f < nb; ++f) {
             float v = mel_basis[(size_t)j * nbins + lo + f];
-            h[o_melT + (size_t)j * kFS + f] = v;
+            h[o_melT + (size_t)j * S + f] = v;
             h[o_melB + (size_t)f * n_mels + j] = v;
         }
     {
         // two-tap form of the band's columns, if the basis has it (any triangular filter bank does)
         std::vector<float2> tw(kFS, make_float2(0.f, 0.f));
         std::vector<unsigned char> tm(kFS, 0);
-        bool sparse = n_mels == 128;
+        bool sparse = n_mels == 128 && S == kFS;
         for (int f = 0; f < nb && sparse; ++f) {
             int first = -1, count = 0, lastnz = -1;
             for (int j = 0; j < n_mels; ++j)
@@ -755,13 +762,13 @@ static int detector_upload(aware_detector* d, const float* mel_basis, const floa
         for (int m = 0; m < n_mels && runs; ++m) {
             int first = -1, lastnz = -1;
             for (int f = 0; f < nb; ++f)
-                if (h[o_melT + (size_t)m * kFS + f] != 0.f) { if (first < 0) first = f; lastnz = f; }
+                if (h[o_melT + (size_t)m * S + f] != 0.f) { if (first < 0) first = f; lastnz = f; }
             if (first < 0) continue;
             const int taps = m < 64 ? kMelTapsA : kMelTapsB;
             const int start = first <= kFS - kMelTapsB ? first : kFS - kMelTapsB;
             if (lastnz - start >= taps) { runs = false; break; }
             fs[m] = (unsigned char)start;
-            for (int j = 0; j < taps; ++j) fw[(size_t)m * kMelTapsB + j] = h[o_melT + (size_t)m * kFS + start + j];
+            for (int j = 0; j < taps; ++j) fw[(size_t)m * kMelTapsB + j] = h[o_melT + (size_t)m * S + start + j];
         }
         if (sparse) {
             const size_t bytes = kFS * (sizeof(float2) + 1) + 128 * (kMelTapsB * sizeof(float) + 1) + 64;
@@ -810,8 +817,8 @@ static int detector_upload(aware_detector* d, const float* mel_basis, const floa
             if (co % 128 == 0 && ci % 64 == 0) { o_pk[l] = pk_total; pk_total += x3_packed_bytes(co, ci); }
             if (ci % 128 == 0 && co % 64 == 0) { o_pkT[l] = pk_total; pk_total += x3_packed_bytes(ci, co); }
         }
-        const size_t o_mT = pk_total; pk_total += x3_packed_bytes(n_mels, kFS);
-        const size_t o_mB = pk_total; pk_total += x3_packed_bytes(kFS, n_mels);
+        const size_t o_mT = pk_total; pk_total += x3_packed_bytes(n_mels, S);
+        const size_t o_mB = pk_total; pk_total += x3_packed_bytes(S, n_mels);
         // read-out kernel operands (last conv block, C <= 64 channels)
         const int cil = channels[n_layers - 1], col = channels[n_layers], colp = 16 * ((col + 15) / 16);
         const bool ro = n_layers >= 2 && readout_x3_supported(1, cil, col);
@@ -832,8 +839,8 @@ static int detector_upload(aware_detector* d, const float* mel_basis, const floa
             x3_pack(wp.data(), colp, cil, hp.data() + o_lp / 2);
             x3_pack(wt.data(), cil, 64, hp.data() + o_lT / 2);
         }
-        x3_pack(h.data() + o_melT, n_mels, kFS, hp.data() + o_mT / 2);
-        x3_pack(h.data() + o_melB, kFS, n_mels, hp.data() + o_mB / 2);
+        x3_pack(h.data() + o_melT, n_mels, S, hp.data() + o_mT / 2);
+        x3_pack(h.data() + o_melB, S, n_mels, hp.data() + o_mB / 2);
         for (int l = 0; l < n_layers; ++l) {
             const int ci = channels[l], co = channels[l + 1];
             if (o_pk[l] != (size_t)-1) x3_pack(h.data() + o_w[l], co, ci, hp.data() + o_pk[l] / 2);
@@ -884,7 +891,7 @@ static int detector_create(aware_detector** out, const aware_plan* plan, const f
         if (channels[i] % 4) return AWARE_E_UNSUPPORTED;
     aware_detector* d = new aware_detector();
     d->n_mels = n_mels; d->n_layers = n_layers; d->nbits = cl / 2;
-    d->band_lo = plan->dev.band_lo; d->nband = plan->dev.nband;
+    d->band_lo = plan->dev.band_lo; d->nband = plan->dev.nband; d->stride = plan->dev.stride;
     for (int i = 0; i <= n_layers; ++i) { d->ch[i] = channels[i]; if (channels[i] > d->maxc) d->maxc = channels[i]; }
     if (arch) {
         d->act = arch->activation; d->norm = arch->norm; d->final_act = arch->final_activation;
@@ -1073,7 +1080,7 @@ constexpr int kH2MinGrid = 128;
 static bool mel_front_applies(const aware_detector* d, const aware_batch* b, int pipe) {
     bool same_T = true;
     for (int i = 1; i < b->B; ++i) same_T = same_T && b->T[i] == b->T[0];
-    return pipe != 1 && d->melTpk && same_T && b->B >= kMelFrontMinClips && mel_front_x3_supported(b->T[0], kFS, kFS);
+    return pipe != 1 && d->melTpk && same_T && b->B >= kMelFrontMinClips && mel_front_x3_supported(b->T[0], d->stride, d->stride);
 }
 
 // forward through the network; mag [NF][256] -> act[last], pred
@@ -1098,12 +1105,12 @@ static int det_forward(const aware_detector* d, const aware_batch* b, const floa
         LAUNCHCHK(); PROF(K_MELNORM);
     } else if (mel_front_applies(d, b, pipe)) {
         // uniform batch that fills the chip with one workgroup per clip: the whole mel block in one launch
-        launch_mel_front_x3(mag, kFS, d->melTpk, b->d_frame_off, b->d_pool_off, o.xm, o.x0, o.mstats, o.gstat, b->B, b->T[0],
-                            kFS, st, o.amax[0]);
+        launch_mel_front_x3(mag, d->stride, d->melTpk, b->d_frame_off, b->d_pool_off, o.xm, o.x0, o.mstats, o.gstat, b->B, b->T[0],
+                            d->stride, st, o.amax[0]);
         cur_max = true;
         LAUNCHCHK(); PROF(K_MELNORM);
     } else {
-        gemm_plain(pipe, mag, kFS, d->melT, kFS, d->melTpk, nullptr, o.xm, 128, b->NF, 128, kFS, st);
+        gemm_plain(pipe, mag, d->stride, d->melT, d->stride, d->melTpk, nullptr, o.xm, 128, b->NF, 128, d->stride, st);
         LAUNCHCHK(); PROF(K_GEMM);
         launch_mel_norm_fwd(o.xm, b->d_frame_off, b->d_pool_off, o.x0, o.mstats, o.gstat, o.mpart, o.mstride, b->B,
                             b->max_frames, st);
@@ -1183,7 +1190,7 @@ static int det_forward(const aware_detector* d, const aware_batch* b, const floa
 
 extern "C" size_t aware_detect_workspace_bytes(const aware_batch* b, const aware_detector* d) {
     if (!b || !d) return 0;
-    return det_bytes(b, d) + (size_t)b->NF * kFS * sizeof(float) + aware_batch_scratch_bytes(b) + 1024;
+    return det_bytes(b, d) + (size_t)b->NF * d->stride * sizeof(float) + aware_batch_scratch_bytes(b) + 1024;
 }
 
 extern "C" int aware_detector_forward(const aware_detector* d, const aware_batch* b, const float* mag, float* values,
@@ -1212,11 +1219,13 @@ extern "C" int aware_detect(const aware_plan* plan, const aware_detector* d, con
     if (!plan || !d || !b || !audio || !values || !workspace) return AWARE_E_BADARG;
     if (plan->general) return AWARE_E_UNSUPPORTED;
     if (b->general) return AWARE_E_BADARG;
+    // the magnitude rows are carved at the detector's stride and written at the plan's: one band layout
+    if (d->band_lo != plan->dev.band_lo || d->nband != plan->dev.nband || d->stride != plan->dev.stride) return AWARE_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
     Carver c(workspace, workspace_bytes);
     DetBufs o;
     carve_det(c, b, d, o);
-    float* mag = c.take<float>((size_t)b->NF * kFS);
+    float* mag = c.take<float>((size_t)b->NF * d->stride);
     unsigned long long* pmax = c.take<unsigned long long>((size_t)b->B * b->pstride);
     if (!c.ok) return AWARE_E_WORKSPACE;
     for (int l = 0; l < d->n_layers; ++l) o.stash[l] = nullptr;
@@ -1406,7 +1415,7 @@ static int det_forward_backward(const aware_detector* d, const aware_batch* b, c
         LAUNCHCHK(); PROF(K_MELNORM);
     }
     if (!G.mel_grad_only) {
-        gemm_plain(pipe, db.xm, 128, d->melB, 128, d->melBpk, nullptr, G.gmag, kFS, b->NF, kFS, 128, st);
+        gemm_plain(pipe, db.xm, 128, d->melB, 128, d->melBpk, nullptr, G.gmag, d->stride, b->NF, d->stride, 128, st);
         LAUNCHCHK(); PROF(K_GEMM);
     }
     return AWARE_OK;
@@ -1445,7 +1454,7 @@ extern "C" int aware_detector_backward(const aware_detector* d, const aware_batc
 extern "C" size_t aware_detector_train_workspace_bytes(const aware_batch* b, const aware_detector* d) {
     if (!b || !d) return 0;
     return aware_detector_backward_workspace_bytes(b, d) + (size_t)b->NP * d->maxc * sizeof(float) * 2 +
-           (size_t)b->NF * kFS * sizeof(float) + 2048;
+           (size_t)b->NF * d->stride * sizeof(float) + 2048;
 }
 static int detector_train_core(const aware_detector* d, const aware_batch* b, const float* mag, const float* target, int loss_kind,
                                float* loss_out, float* values, float* grad_mag, float* const* grad_weights,
@@ -1478,6 +1487,7 @@ static int detector_train_core(const aware_detector* d, const aware_batch* b, co
                                float* const* grad_biases, void* workspace, size_t workspace_bytes, void* stream) {
     if (!d || !b || b->general) return AWARE_E_BADARG;
     if (!d->card_arch) return AWARE_E_UNSUPPORTED;       // the training extension serves the model card's network only
+    if (d->stride != kFS) return AWARE_E_UNSUPPORTED;    // ... on a band of the narrow layout
     hipStream_t st = (hipStream_t)stream;
     Carver c(workspace, workspace_bytes);
     DetBufs o;
@@ -1488,7 +1498,7 @@ static int detector_train_core(const aware_detector* d, const aware_batch* b, co
     G.tr1 = c.take<float>((size_t)b->NP * d->maxc);
     G.tr2 = c.take<float>((size_t)b->NP * d->maxc);
     G.loss = loss_out ? loss_out : c.take<float>(b->B);
-    if (!grad_mag) grad_mag = c.take<float>((size_t)b->NF * kFS);
+    if (!grad_mag) grad_mag = c.take<float>((size_t)b->NF * d->stride);
     if (!c.ok) return AWARE_E_WORKSPACE;
     // padding rows of the gradient ping-pong buffers take part in the row contraction: keep them finite
     HIPCHK(hipMemsetAsync(G.d1, 0, (size_t)b->NP * d->maxc * sizeof(float) * 2, st));
@@ -1546,11 +1556,11 @@ struct aware_embed {
 
 static size_t embed_bytes(const aware_batch* b, const aware_detector* d, int iters) {
     size_t bytes = det_bytes(b, d);
-    bytes += (size_t)b->NF * kFS * sizeof(float) * 8;
-    bytes += (size_t)b->NF * kFS * sizeof(cf) * 2;
+    bytes += (size_t)b->NF * d->stride * sizeof(float) * 8;
+    bytes += (size_t)b->NF * d->stride * sizeof(cf) * 2;
     bytes += (size_t)b->NS * sizeof(float) * 3;
     bytes += (size_t)b->B * 1024 * sizeof(float);
-    bytes += (size_t)b->NF * kFS * sizeof(float) + (size_t)b->B * b->pstride * 8 + (size_t)b->B * sizeof(float) + 1024;   // L1 term
+    bytes += (size_t)b->NF * d->stride * sizeof(float) + (size_t)b->B * b->pstride * 8 + (size_t)b->B * sizeof(float) + 1024;   // L1 term
     bytes += (size_t)b->NP * d->maxc * sizeof(float) * 2;
     bytes += (size_t)b->B * (3 * d->nbits + 8) * sizeof(float);
     bytes += (size_t)(iters + 1) * sizeof(float4) + (size_t)iters * 5 * sizeof(double) + (size_t)b->B * 4 * sizeof(double) + 1024;
@@ -1640,12 +1650,14 @@ extern "C" int aware_embed_create(aware_embed** out, const aware_plan* plan, con
     if (cfg->conv_pipe < 0 || cfg->conv_pipe > 2 || cfg->readout < 0 || cfg->readout > 1 || cfg->mel < 0 || cfg->mel > 1)
         return AWARE_E_BADARG;
     if (cfg->dsp_path < 0 || cfg->dsp_path > 1) return AWARE_E_BADARG;
+    // the detector's mel operands have the layout of the plan it was created for
+    if (det->band_lo != plan->dev.band_lo || det->nband != plan->dev.nband || det->stride != plan->dev.stride) return AWARE_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
     aware_embed* e = new aware_embed();
     e->plan = plan; e->det = det; e->b = b; e->cfg = *cfg;
     Carver c(workspace, workspace_bytes);
     carve_det(c, b, det, e->db);
-    const size_t nsp = (size_t)b->NF * kFS;
+    const size_t nsp = (size_t)b->NF * plan->dev.stride;
     e->coef = c.take<float>(nsp); e->lo = c.take<float>(nsp); e->hi = c.take<float>(nsp);
     e->mom = c.take<float>(nsp); e->vel = c.take<float>(nsp); e->best = c.take<float>(nsp);
     e->mag = c.take<float>(nsp); e->gmag = c.take<float>(nsp);
@@ -1671,7 +1683,7 @@ extern "C" int aware_embed_create(aware_embed** out, const aware_plan* plan, con
         e->l1term = c.take<float>(b->B);
     }
     if (!c.ok) { delete e; return AWARE_E_WORKSPACE; }
-    // columns nband..255 of every spectral row are padding: zeroed once here, never written by the loop kernels
+    // columns nband..stride-1 of every spectral row are padding: zeroed once here, never written by the loop kernels
     HIPCHK(hipMemsetAsync(e->mag, 0, nsp * sizeof(float), st));
     HIPCHK(hipMemsetAsync(e->U, 0, nsp * sizeof(cf), st));
     HIPCHK(hipMemsetAsync(e->gpad, 0, (size_t)b->B * 1024 * sizeof(float), st));
@@ -1696,8 +1708,9 @@ extern "C" int aware_embed_create(aware_embed** out, const aware_plan* plan, con
         auto f32_shape = [&](int M, int N, int K, int lda) {
             return !(cfg->conv_pipe != 1 && M % 32 == 0 && gemm_clip_x3_supported(1, N, K, lda));
         };
-        if (f32_shape(b->NF, 128, kFS, kFS)) gemm_autotune(e->mag, kFS, det->melT, kFS, e->db.xm, 128, b->NF, 128, kFS, st);
-        if (f32_shape(b->NF, kFS, 128, 128)) gemm_autotune(e->db.xm, 128, det->melB, 128, e->gmag, kFS, b->NF, kFS, 128, st);
+        const int S = det->stride;
+        if (f32_shape(b->NF, 128, S, S)) gemm_autotune(e->mag, S, det->melT, S, e->db.xm, 128, b->NF, 128, S, st);
+        if (f32_shape(b->NF, S, 128, 128)) gemm_autotune(e->db.xm, 128, det->melB, 128, e->gmag, S, b->NF, S, 128, st);
         for (int l = 0; l < det->n_layers; ++l) {
             const int ci = det->ch[l], co = det->ch[l + 1];
             if (f32_shape(b->NP, co, ci, ci)) gemm_autotune(e->d1, ci, det->w[l], ci, e->d2, co, b->NP, co, ci, st);
@@ -1785,7 +1798,7 @@ extern "C" int aware_embed_begin(aware_embed* e, const float* audio, const float
                         b->max_frames, st);
     LAUNCHCHK();
     const float ratio = (float)pow(10.0, -(double)e->cfg.tolerance_db / 20.0);
-    launch_embed_prepare(e->mag, e->coef, e->lo, e->hi, e->mom, e->vel, e->best, e->c0, ratio, (size_t)b->NF * kFS, st);
+    launch_embed_prepare(e->mag, e->coef, e->lo, e->hi, e->mom, e->vel, e->best, e->c0, ratio, (size_t)b->NF * e->plan->dev.stride, st);
     LAUNCHCHK();
     HIPCHK(hipMemcpyAsync(e->target, target, (size_t)b->B * e->det->nbits * sizeof(float), hipMemcpyDeviceToDevice, st));
     HIPCHK(hipMemsetAsync(e->step, 0, 4 * sizeof(int), st));
@@ -1870,7 +1883,7 @@ static int embed_iteration(aware_embed* e, hipStream_t st, int do_step, float* g
         const auto& o = e->opt;
         launch_opt_rows(o.kind, e->coef, e->gmag, e->mom, e->vel, e->c0, LA.box_ratio, e->best, e->improved, b->d_frame_off, b->B,
                         b->NF, o.d_tab, e->cfg.num_iterations, e->step, o.plateau ? o.d_lr : nullptr, o.wd, o.hyp,
-                        e->plan->dev.nband, st);
+                        e->plan->dev.nband, e->plan->dev.stride, st);
         if (o.plateau)
             launch_plateau(e->loss, o.d_state, o.d_lr, b->B, o.factor, o.patience, o.threshold, o.min_lr, o.eps, st);
         LAUNCHCHK(); PROF(K_MISC);

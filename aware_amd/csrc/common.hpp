@@ -6,10 +6,16 @@
 
 namespace aware {
 
-// Band-limited spectral arrays are frame-major: [global frame][kFS] with the first
-// `nband` entries valid (bin k = band_lo + f) and the tail zero.  kFS = 256 keeps
-// every frame row 1 KiB-aligned and makes the row the K dimension of the mel GEMM.
+// Band-limited spectral arrays are frame-major: [global frame][stride] with the first
+// `nband` entries valid (bin k = band_lo + f) and the tail zero.  The stride is kFS = 256 for
+// every band inside bins 1..511 that is at most 256 bins wide (the narrow layout: each row
+// 1 KiB-aligned and the K dimension of the mel GEMM), and kFSWide = 576 for any other band
+// inside bins 0..512 (the wide layout: 9 bins per lane of a wave, K % 64 == 0 for the mel GEMMs).
 constexpr int kFS = 256;
+constexpr int kFSWide = 576;
+__host__ __device__ constexpr int band_stride_for(int band_lo, int band_hi) {
+    return (band_lo >= 1 && band_hi <= 511 && band_hi - band_lo + 1 <= kFS) ? kFS : kFSWide;
+}
 // longest support (adjacent band columns) of mel filters 0..63 / 64..127 that the analysis kernel with the mel projection
 // folded in takes (dsp_stream.hip; the card's bank: 5 and 12)
 constexpr int kMelTapsA = 6;
@@ -31,6 +37,7 @@ struct PlanDev {
     const float* env_tab; // overlap-add envelope: head[768], interior[768 (256 used)], tail[768]
     int band_lo;          // first band bin (32)
     int nband;            // number of band bins (225)
+    int stride;           // floats per band row: kFS or kFSWide (band_stride_for)
 };
 
 // A clip's "istft-length" signal (Ny_b = 256*(T_b-1) samples) lives at float offset

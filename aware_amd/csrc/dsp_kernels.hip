@@ -148,6 +148,7 @@ __global__ __launch_bounds__(kThreads) void analysis_kernel(AnalysisArgs a) {
         wr[2 * r + 1] = a.plan.window[2 * (lane + 64 * r) + 1];
     }
     const int band_lo = a.plan.band_lo, nband = a.plan.nband;
+    const int S = a.plan.stride;                    // floats per band row (kFS or kFSWide)
     float4 sc = make_float4(0.f, 0.f, 1.f, 0.f);
     float inv_bc2 = 1.f;
     int improved = 0;
@@ -175,7 +176,7 @@ __global__ __launch_bounds__(kThreads) void analysis_kernel(AnalysisArgs a) {
                 const int f = lane + 64 * r - band_lo;
                 preP[r] = mk(0.f, 0.f); preM[r] = preV[r] = preC[r] = preL[r] = preH[r] = 0.f;
                 if (pre_ok && f >= 0 && f < nband) {
-                    const size_t idx = row * kFS + f;
+                    const size_t idx = row * S + f;
                     preP[r] = a.phasor[idx]; preM[r] = a.mom[idx]; preV[r] = a.vel[idx]; preC[r] = a.coef[idx];
                     preL[r] = a.lo[idx]; preH[r] = a.hi[idx];
                 }
@@ -206,13 +207,15 @@ __global__ __launch_bounds__(kThreads) void analysis_kernel(AnalysisArgs a) {
             if (lane == 0) out[512] = mk(rfft_split_nyquist(s) * se, 0.f);
         }
         if (!FULLOUT) {
-            // band bins k = band_lo + f, f < nband (<= 256)
+            // band bins k = band_lo + f, f < nband (<= 256 in the narrow layout; in the wide layout up to 513 bins, the
+            // Nyquist bin 512 taken by lane 0 after the loop)
 #pragma unroll
-            for (int r = 0; r < 8; ++r) {
+            for (int r = 0; r < 9; ++r) {
+                if (r == 8 && (lane != 0 || band_lo + nband != 513)) continue;
                 const int k = lane + 64 * r;
                 const int f = k - band_lo;
-                if (f < 0 || f >= kFS) continue;
-                const size_t idx = row * kFS + f;
+                if (f < 0 || f >= S) continue;
+                const size_t idx = row * S + f;
                 if (f >= nband) {
                     if (MODE == AN_NORM) {
                         if (a.mag) a.mag[idx] = 0.f;
@@ -220,7 +223,7 @@ __global__ __launch_bounds__(kThreads) void analysis_kernel(AnalysisArgs a) {
                     }
                     continue;
                 }
-                cf X = rfft_split_bin(k, v[r], s, a.plan.tw1024);
+                cf X = (r < 8) ? rfft_split_bin(k, v[r < 8 ? r : 0], s, a.plan.tw1024) : mk(rfft_split_nyquist(s), 0.f);
                 if (MODE == AN_NORM) {
                     const float mg = fast_sqrt(X.x * X.x + X.y * X.y);
                     const float im = fast_rcp(mg);
@@ -231,6 +234,8 @@ __global__ __launch_bounds__(kThreads) void analysis_kernel(AnalysisArgs a) {
                     const bool pre = pre_ok && r < 5;
                     cf P = pre ? preP[r < 5 ? r : 0] : a.phasor[idx];
                     float g = (X.x * P.x + X.y * P.y) * (1.0f / 512.0f);
+                    // DC / Nyquist (wide layout): irfft takes their real parts once, dL/dc = Re(G) Re(P) / 1024
+                    if (k == 0 || k == 512) g = (X.x * P.x) * (1.0f / 1024.0f);
                     if (a.grad_out) a.grad_out[idx] = g;
                     if (a.do_step) {
                         // torch.optim.NAdam single-tensor step + clamp + best snapshot
@@ -244,6 +249,13 @@ __global__ __launch_bounds__(kThreads) void analysis_kernel(AnalysisArgs a) {
                     }
                 }
             }
+            // wide layout: the columns from bin 512 on that the loop above leaves (beyond the band) are padding as well
+            if (MODE == AN_NORM && S > kFS)
+                for (int f = max(nband, 512 - band_lo) + lane; f < S; f += 64) {
+                    const size_t idx = row * S + f;
+                    if (a.mag) a.mag[idx] = 0.f;
+                    if (a.unit) a.unit[idx] = mk(0.f, 0.f);
+                }
         }
         wave_sync();
     }
@@ -363,8 +375,8 @@ __global__ __launch_bounds__(kThreads) void synth_kernel(SynthArgs a) {
                 }
                 if (r4 < kSynthRounds - 1 && fi + 1 < nfr) load_band(fi + 1);
             } else {
-                const float* A = a.amp + row * kFS;
-                const cf* P = a.ph + row * kFS;
+                const float* A = a.amp + row * a.plan.stride;
+                const cf* P = a.ph + row * a.plan.stride;
 #pragma unroll
                 for (int r = 0; r < 8; ++r) {
                     const int k = lane + 64 * r;
@@ -372,6 +384,10 @@ __global__ __launch_bounds__(kThreads) void synth_kernel(SynthArgs a) {
                     cf xk = mk(0.f, 0.f), xp = mk(0.f, 0.f);
                     if (f >= 0 && f < nband) { float am = A[f]; cf p = P[f]; xk = mk(am * p.x, am * p.y); }
                     if (fp >= 0 && fp < nband) { float am = A[fp]; cf p = P[fp]; xp = mk(am * p.x, am * p.y); }
+                    if (k == 0) {                   // DC / Nyquist (wide layout): as the full-spectrum input above
+                        xk.y = 0.f; xp.y = 0.f;
+                        if (MODE == SY_ADJ) { xk.x *= 2.f; xp.x *= 2.f; }
+                    }
                     v[r] = irfft_merge_bin(k, xk, xp, a.plan.tw1024);
                 }
             }

@@ -24,7 +24,14 @@
 // the loop, registers sized for five to six waves per SIMD.
 //
 // Same reference operations as dsp_kernels.hip (utils/audio/stft.py:27-28,47-48,54-55,61-62, utils/audio/waveform.py:18-19,
-// embedding/multibit_embedder.py:95-122); serves plans whose band lies inside bins 1..256 (the model card: 32..256).
+// embedding/multibit_embedder.py:95-122); serves plans whose band lies inside bins 1..256 (the model card: 32..256) and, as
+// the WIDE instantiations, every band of the wide layout (kFSWide columns per row, any band inside bins 0..512).
+//
+// Lane <-> bin map.  The 512-point complex FFT leaves Z[k] in lane k & 63, register k >> 6.  The narrow form takes the bins
+// k = lane + 64 r for r < 4 plus lane 0 at r = 4 (bins 0..256).  The wide form takes r < 8 (bins 0..511) plus the Nyquist bin
+// 512 in an extra slot r = 8 of lane 0: 9 bins per lane.  DC and Nyquist are real for a real signal; the inverse transform
+// ignores their imaginary parts and enters them once where an interior bin enters twice (torch's C2R), which the wide
+// synthesis and both adjoints restate.
 #include "common.hpp"
 #include "dsp_args.hpp"
 #include "kernels.h"
@@ -74,8 +81,12 @@ __device__ __forceinline__ float env_at(const PlanDev& pl, int p, int T) {
 // MELF (AN_NORM only): the magnitudes go through the mel filter bank here -- a filter is a run of at most kMelTapsB adjacent
 // band columns, 450 non-zero weights in all for the card's bank -- and the frame's 128 mel values are written instead of its
 // 256 magnitudes (the dense K = 256 GEMM of the mel block and its operand never exist)
-template <int MODE, bool L1, bool MELF = false>
-__global__ __launch_bounds__(kSThreads, MODE == AN_ADJ ? 3 : 4) void analysis_stream_kernel(AnalysisArgs a, int run_frames) {
+// WIDE: the wide layout (see the top of the file): 9 bin slots per lane, rows of kFSWide columns, no mel fold
+template <int MODE, bool L1, bool MELF = false, bool WIDE = false>
+__global__ __launch_bounds__(kSThreads, MODE == AN_ADJ ? (WIDE ? 2 : 3) : 4) void analysis_stream_kernel(AnalysisArgs a, int run_frames) {
+    static_assert(!(WIDE && MELF), "the wide layout takes the dense mel GEMM");
+    constexpr int S = WIDE ? kFSWide : kFS;        // floats per band row
+    constexpr int NS = WIDE ? 9 : 5;               // bin slots per lane
     __shared__ float magrow_s[MELF ? kSW : 1][MELF ? kFS : 1];
     __shared__ cf tw1s[512];
     __shared__ cf tw2s[64];
@@ -178,9 +189,9 @@ __global__ __launch_bounds__(kSThreads, MODE == AN_ADJ ? 3 : 4) void analysis_st
 
     cf* s = scratch[wave];
     const int band_lo = a.plan.band_lo, nband = a.plan.nband;
-    cf w1024[5];
+    cf w1024[NS];
 #pragma unroll
-    for (int r = 0; r < 5; ++r) w1024[r] = a.plan.tw1024[lane + 64 * r];
+    for (int r = 0; r < NS; ++r) w1024[r] = (r < 8) ? a.plan.tw1024[lane + 64 * r] : mk(-1.f, 0.f);   // W^512 = -1
     float4 sc = make_float4(0.f, 0.f, 1.f, 0.f);
     float inv_bc2 = 1.f;
     int improved = 0;
@@ -217,13 +228,13 @@ __global__ __launch_bounds__(kSThreads, MODE == AN_ADJ ? 3 : 4) void analysis_st
         const int t = t0 + fr;
         const size_t row = (size_t)(f0 + t);
         // operands of the optimiser epilogue do not depend on the transform: request them first
-        cf preP[5];
-        float preM[5], preV[5], preC[5], pre0[5];
+        cf preP[NS];
+        float preM[NS], preV[NS], preC[NS], pre0[NS];
         if (MODE == AN_ADJ) {
 #pragma unroll
-            for (int r = 0; r < 5; ++r) {
+            for (int r = 0; r < NS; ++r) {
                 const int f = lane + 64 * r - band_lo;
-                const size_t idx = row * kFS + (size_t)min(max(f, 0), kFS - 1);       // clamped, masked at use
+                const size_t idx = row * S + (size_t)min(max(f, 0), S - 1);           // clamped, masked at use
                 preP[r] = a.phasor[idx];
                 if (a.do_step) { preM[r] = a.mom[idx]; preV[r] = a.vel[idx]; preC[r] = a.coef[idx]; }
                 else { preM[r] = preV[r] = 0.f; preC[r] = L1 ? a.coef[idx] : 0.f; }
@@ -245,21 +256,22 @@ __global__ __launch_bounds__(kSThreads, MODE == AN_ADJ ? 3 : 4) void analysis_st
         raw[7] = load_half(kHop * (t + 1) + 896);
         fft512_wave_t<-1>(lane, v, tw1s, tw2s, s);
 
-        // real-FFT split: X[k] needs Z[k] (own register) and Z[512-k] = lane (64-L)&63, register 7-r (lane 0: own 8-r)
+        // real-FFT split: X[k] needs Z[k] (own register) and Z[512-k] = lane (64-L)&63, register 7-r (lane 0: own 8-r);
+        // the wide form's slot 8 (lane 0, Nyquist) splits Z[0] with itself and W^512 = -1
         const int src_lane = (64 - lane) & 63;
 #pragma unroll
-        for (int r = 0; r < 5; ++r) {
-            cf zp = mk(__shfl(v[7 - r].x, src_lane), __shfl(v[7 - r].y, src_lane));
-            if (lane == 0) zp = (r == 0) ? v[0] : v[8 - r];
+        for (int r = 0; r < NS; ++r) {
+            cf zp = (r < 8) ? mk(__shfl(v[7 - r].x, src_lane), __shfl(v[7 - r].y, src_lane)) : v[0];
+            if (lane == 0) zp = (r == 0 || r == 8) ? v[0] : v[8 - r];
             const int k = lane + 64 * r;
             const int f = k - band_lo;
-            if (f < 0 || f >= nband) continue;
-            const cf zk = v[r];
+            if (f < 0 || f >= nband || (r == 8 && lane != 0)) continue;
+            const cf zk = v[r < 8 ? r : 0];
             const cf e = mk(0.5f * (zk.x + zp.x), 0.5f * (zk.y - zp.y));
             const cf d = mk(0.5f * (zk.x - zp.x), 0.5f * (zk.y + zp.y));
             const cf wd = cmul(w1024[r], d);
             const cf X = mk(e.x + wd.y, e.y - wd.x);
-            const size_t idx = row * kFS + f;
+            const size_t idx = row * S + f;
             if (MODE == AN_NORM) {
                 const float mg = fast_sqrt(X.x * X.x + X.y * X.y);
                 const float im = fast_rcp(mg);
@@ -270,6 +282,8 @@ __global__ __launch_bounds__(kSThreads, MODE == AN_ADJ ? 3 : 4) void analysis_st
                 // dL/dc = Re(G conj P) with G = (2/N) rfft(.)  [adjoint of irfft on interior bins]
                 const cf P = preP[r];
                 float g = (X.x * P.x + X.y * P.y) * (1.0f / 512.0f);
+                // DC / Nyquist (wide form only): irfft takes their real parts once, dL/dc = Re(G) Re(P) / 1024
+                if (WIDE && (k == 0 || k == 512)) g = (X.x * P.x) * (1.0f / 1024.0f);
                 if (L1) {
                     // EXTENSION: + l1_weight * d/dc mean|c - c0| (mean over the clip's nband * T variables; sign(0) = 0)
                     const float dc = preC[r] - pre0[r];
@@ -301,14 +315,22 @@ __global__ __launch_bounds__(kSThreads, MODE == AN_ADJ ? 3 : 4) void analysis_st
             mo[lane + 64] = m1;
         }
         if (MODE == AN_NORM && a.write_pad) {
-            // zero tail of the row (columns nband..255); the embed loop keeps it zero from aware_embed_create on
-#pragma unroll
-            for (int r = 0; r < 8; ++r) {
-                const int f = lane + 64 * r - band_lo;
-                if (f >= nband && f < kFS) {
-                    const size_t idx = row * kFS + f;
+            // zero tail of the row (columns nband..S-1); the embed loop keeps it zero from aware_embed_create on
+            if (WIDE) {
+                for (int f = nband + lane; f < S; f += 64) {
+                    const size_t idx = row * S + f;
                     if (a.mag) a.mag[idx] = 0.f;
                     if (a.unit) a.unit[idx] = mk(0.f, 0.f);
+                }
+            } else {
+#pragma unroll
+                for (int r = 0; r < 8; ++r) {
+                    const int f = lane + 64 * r - band_lo;
+                    if (f >= nband && f < kFS) {
+                        const size_t idx = row * kFS + f;
+                        if (a.mag) a.mag[idx] = 0.f;
+                        if (a.unit) a.unit[idx] = mk(0.f, 0.f);
+                    }
                 }
             }
         }
@@ -321,14 +343,19 @@ __global__ __launch_bounds__(kSThreads, MODE == AN_ADJ ? 3 : 4) void analysis_st
 // L1 (SY_FWD only): also emit the per-run sums of |amp - c0| for the loss value of the push_extremes + L1 objective
 // MELG (SY_ADJ only): the amplitudes are dL/d|S| = (dL/dmel) * melB, expanded here from the 128 mel gradients of the frame
 // through the filter bank's two taps per bin (the dense K = 128 GEMM and its [NF][256] result never exist)
-template <int MODE, bool L1, bool MELG = false>
-__global__ __launch_bounds__(kSThreads, 4) void synth_stream_kernel(SynthArgs a) {
+// WIDE: the wide layout -- slot r of a lane loads its own bin k = lane + 64 r (and lane 0 the Nyquist bin in slot 8), the
+// partner bin 512 - k of the irfft merge comes from lane (64 - L) & 63 (cross-lane read, like the analysis split)
+template <int MODE, bool L1, bool MELG = false, bool WIDE = false>
+__global__ __launch_bounds__(kSThreads, WIDE ? 3 : 4) void synth_stream_kernel(SynthArgs a) {
+    static_assert(!(WIDE && MELG), "the wide layout takes the dense mel GEMM");
+    constexpr int S = WIDE ? kFSWide : kFS;        // floats per band row
+    constexpr int NS = WIDE ? 9 : 8;               // input slots per lane
     __shared__ float2 melw_s[MELG ? kFS : 1];
     __shared__ float melrow_s[MELG ? kSW : 1][MELG ? 128 : 1];
     __shared__ cf tw1s[512];
     __shared__ cf tw2s[64];
     __shared__ float2 wins[512];             // window * irfft scale, as sample pairs
-    __shared__ cf mcs[512];                  // irfft merge constants of bin k (band inside bins 1..256)
+    __shared__ cf mcs[512];                  // irfft merge constants of bin k (narrow: band inside bins 1..256; wide: A_k)
     __shared__ cf scratch[kSW][kFftScratch];
     const int tid = threadIdx.x;
     // irfft's 1/1024 (1/2 in the merge, 1/512 here); the adjoint of the forward rfft is 512*irfft
@@ -337,7 +364,8 @@ __global__ __launch_bounds__(kSThreads, 4) void synth_stream_kernel(SynthArgs a)
     for (int i = tid; i < 512; i += kSThreads) {
         wins[i] = make_float2(a.plan.window[2 * i] * scale, a.plan.window[2 * i + 1] * scale);
         const cf w = a.plan.tw1024[i];                                   // (cos t, -sin t), t = 2 pi k / 1024
-        mcs[i] = (i < 256) ? mk(0.5f * (1.f + w.y), 0.5f * w.x) : mk(0.5f * (1.f - w.y), -0.5f * w.x);
+        // narrow: A_k = (1 + i conj W^k)/2 below 256, B_k = (1 - i conj W^k)/2 = 1 - A_k from 256 on; wide: A_k for every k
+        mcs[i] = (WIDE || i < 256) ? mk(0.5f * (1.f + w.y), 0.5f * w.x) : mk(0.5f * (1.f - w.y), -0.5f * w.x);
     }
     if (MELG)
         for (int i = tid; i < kFS; i += kSThreads) melw_s[i] = a.melw[i];
@@ -374,16 +402,16 @@ __global__ __launch_bounds__(kSThreads, 4) void synth_stream_kernel(SynthArgs a)
 
     // band inputs of one frame: register slot r needs exactly one input bin -- its own bin k = lane+64r for k <= 256,
     // the partner 512-k otherwise; loads are unconditional from a clamped index, the amplitude masks the rest
-    float inA[8];
-    cf inP[8];
-    unsigned fo[8];                          // lane-constant column of slot r (clamped) and whether it lies in the band
+    float inA[NS];
+    cf inP[NS];
+    unsigned fo[NS];                         // lane-constant column of slot r (clamped) and whether it lies in the band
     unsigned inband = 0;
 #pragma unroll
-    for (int r = 0; r < 8; ++r) {
+    for (int r = 0; r < NS; ++r) {
         const int k = lane + 64 * r;
-        const int f = ((k <= 256) ? k : 512 - k) - band_lo;
-        fo[r] = (unsigned)min(max(f, 0), kFS - 1);
-        if (f >= 0 && f < nband) inband |= 1u << r;
+        const int f = (WIDE ? k : ((k <= 256) ? k : 512 - k)) - band_lo;
+        fo[r] = (unsigned)min(max(f, 0), S - 1);
+        if (f >= 0 && f < nband && !(r == 8 && lane != 0)) inband |= 1u << r;
     }
     // MELG: the first mel tap of slot r's column, four per register
     unsigned mtap[2] = {0u, 0u};
@@ -394,15 +422,15 @@ __global__ __launch_bounds__(kSThreads, 4) void synth_stream_kernel(SynthArgs a)
     }
     auto load_band = [&](int t) {
         const size_t row = (size_t)(f0 + t);
-        const float* A = MELG ? nullptr : a.amp + row * kFS;
-        const cf* P = a.ph + row * kFS;
+        const float* A = MELG ? nullptr : a.amp + row * S;
+        const cf* P = a.ph + row * S;
         if (MELG) {
             const float* D = a.dmel + row * 128;
             drow[0] = D[lane];
             drow[1] = D[lane + 64];
         }
 #pragma unroll
-        for (int r = 0; r < 8; ++r) {
+        for (int r = 0; r < NS; ++r) {
             inP[r] = P[fo[r]];
             if (!MELG) {
                 const float am = A[fo[r]];
@@ -524,16 +552,39 @@ __global__ __launch_bounds__(kSThreads, 4) void synth_stream_kernel(SynthArgs a)
         {
             if (MELG) expand_mel();
             if (MODE == SY_FWD && L1 && ((t >= jb0 && t < jb1) || (last && t == T - 1))) {
-                // own bins of the slots: k = lane + 64 r <= 256 (r < 4, and lane 0 of r = 4)
-                const float* C0 = a.c0 + (size_t)(f0 + t) * kFS;
+                // own bins of the slots: narrow k = lane + 64 r <= 256 (r < 4, and lane 0 of r = 4); wide: every slot
+                const float* C0 = a.c0 + (size_t)(f0 + t) * S;
 #pragma unroll
-                for (int r = 0; r < 5; ++r) {
+                for (int r = 0; r < (WIDE ? NS : 5); ++r) {
                     const int f = lane + 64 * r - band_lo;
-                    const float cv = C0[min(max(f, 0), kFS - 1)];
-                    if (f >= 0 && f < nband && (r < 4 || lane == 0)) l1 += fabsf(inA[r] - cv);
+                    const float cv = C0[min(max(f, 0), S - 1)];
+                    if (f >= 0 && f < nband && (WIDE ? (r < 8 || lane == 0) : (r < 4 || lane == 0))) l1 += fabsf(inA[r] - cv);
                 }
             }
             cf v[8];
+            if (WIDE) {
+                // full irfft merge Z[k] = X[k] A_k + conj(X[512-k]) (1 - A_k); X[512-k] is slot 7-r of lane (64-L)&63
+                // (lane 0: own slot 8-r).  DC / Nyquist: real parts only; the adjoint of rfft enters them twice as large
+                cf xo[NS];
+#pragma unroll
+                for (int r = 0; r < NS; ++r) {
+                    const bool edge = (r == 0 || r == 8) && lane == 0;
+                    xo[r] = mk(inA[r] * inP[r].x, edge ? 0.f : inA[r] * inP[r].y);
+                    if (MODE == SY_ADJ && edge) xo[r].x *= 2.f;
+                }
+                const int src_lane = (64 - lane) & 63;
+#pragma unroll
+                for (int r = 0; r < 8; ++r) {
+                    cf xp = mk(__shfl(xo[7 - r].x, src_lane), __shfl(xo[7 - r].y, src_lane));
+                    if (lane == 0) xp = xo[8 - r];
+                    const cf A = mcs[lane + 64 * r];
+                    const cf Bm = mk(1.f - A.x, -A.y);
+                    const cf xk = xo[r];
+                    // xk * A + conj(xp) * Bm
+                    v[r] = mk(xk.x * A.x - xk.y * A.y + xp.x * Bm.x + xp.y * Bm.y,
+                              xk.x * A.y + xk.y * A.x + xp.x * Bm.y - xp.y * Bm.x);
+                }
+            } else {
             // irfft merge with one of the two inputs known to be zero (band inside bins 1..256):
             //   k < 256:  Z[k] = X[k] * (1 + i conj W^k)/2        k >= 256:  Z[k] = conj(X[512-k]) * (1 - i conj W^k)/2
 #pragma unroll
@@ -541,6 +592,7 @@ __global__ __launch_bounds__(kSThreads, 4) void synth_stream_kernel(SynthArgs a)
                 const cf mc = mcs[lane + 64 * r];
                 const float xr = inA[r] * inP[r].x, xi = (r < 4) ? inA[r] * inP[r].y : -(inA[r] * inP[r].y);
                 v[r] = mk(xr * mc.x - xi * mc.y, xr * mc.y + xi * mc.x);
+            }
             }
             load_band(min(t + 1, T - 1));           // unconditional (clamped): no register copies around a branch
             fft512_wave_t<1>(lane, v, tw1s, tw2s, s);
@@ -595,7 +647,9 @@ void launch_l1_reduce(const double* pl1, const int* pcount, int pstride, const i
 // ---------------------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------------------
-bool stream_supported(const PlanDev& plan) { return plan.band_lo >= 1 && plan.band_lo + plan.nband <= 257; }
+bool stream_supported(const PlanDev& plan) {
+    return plan.stride == kFSWide || (plan.band_lo >= 1 && plan.band_lo + plan.nband <= 257);
+}
 
 void launch_analysis_stream(const AnalysisLaunch& L, hipStream_t st) {
     AnalysisArgs a{};
@@ -632,7 +686,11 @@ void launch_analysis_stream(const AnalysisLaunch& L, hipStream_t st) {
         const int runs = (L.max_frames + R - 1) / R;
         grid = dim3((unsigned)((runs + kSW - 1) / kSW), (unsigned)L.B, 1);
     }
-    if (L.adjoint && a.l1_weight != 0.f) hipLaunchKernelGGL((analysis_stream_kernel<AN_ADJ, true>), grid, dim3(kSThreads), 0, st, a, R);
+    if (L.plan.stride == kFSWide) {
+        if (L.adjoint && a.l1_weight != 0.f) hipLaunchKernelGGL((analysis_stream_kernel<AN_ADJ, true, false, true>), grid, dim3(kSThreads), 0, st, a, R);
+        else if (L.adjoint) hipLaunchKernelGGL((analysis_stream_kernel<AN_ADJ, false, false, true>), grid, dim3(kSThreads), 0, st, a, R);
+        else hipLaunchKernelGGL((analysis_stream_kernel<AN_NORM, false, false, true>), grid, dim3(kSThreads), 0, st, a, R);
+    } else if (L.adjoint && a.l1_weight != 0.f) hipLaunchKernelGGL((analysis_stream_kernel<AN_ADJ, true>), grid, dim3(kSThreads), 0, st, a, R);
     else if (L.adjoint) hipLaunchKernelGGL((analysis_stream_kernel<AN_ADJ, false>), grid, dim3(kSThreads), 0, st, a, R);
     else if (L.mel_out && L.melf_w && L.melf_s) {
         a.mel_out = L.mel_out; a.melf_w = L.melf_w; a.melf_s = L.melf_s; a.mag = nullptr;
@@ -658,7 +716,11 @@ void launch_synth_stream(const SynthLaunch& L, hipStream_t st) {
         grid = dim3((unsigned)L.n_wg, 1, 1);
     }
     a.dmel = L.dmel; a.melw = (const float2*)L.melw; a.melm = L.melm;
-    if (L.adjoint && L.dmel && L.melw && L.melm) hipLaunchKernelGGL((synth_stream_kernel<SY_ADJ, false, true>), grid, dim3(kSThreads), 0, st, a);
+    if (L.plan.stride == kFSWide) {
+        if (L.adjoint) hipLaunchKernelGGL((synth_stream_kernel<SY_ADJ, false, false, true>), grid, dim3(kSThreads), 0, st, a);
+        else if (a.pl1) hipLaunchKernelGGL((synth_stream_kernel<SY_FWD, true, false, true>), grid, dim3(kSThreads), 0, st, a);
+        else hipLaunchKernelGGL((synth_stream_kernel<SY_FWD, false, false, true>), grid, dim3(kSThreads), 0, st, a);
+    } else if (L.adjoint && L.dmel && L.melw && L.melm) hipLaunchKernelGGL((synth_stream_kernel<SY_ADJ, false, true>), grid, dim3(kSThreads), 0, st, a);
     else if (L.adjoint) hipLaunchKernelGGL((synth_stream_kernel<SY_ADJ, false>), grid, dim3(kSThreads), 0, st, a);
     else if (a.pl1) hipLaunchKernelGGL((synth_stream_kernel<SY_FWD, true>), grid, dim3(kSThreads), 0, st, a);
     else hipLaunchKernelGGL((synth_stream_kernel<SY_FWD, false>), grid, dim3(kSThreads), 0, st, a);

@@ -43,7 +43,7 @@ struct AnalysisLaunch {
     float* grad_out = nullptr;
     int do_step = 0;
     float hyp[4] = {0.1f, 0.999f, 0.001f, 1e-8f};
-    // stream = 1: barrier-free streaming wave kernels (dsp_stream.hip; band inside bins 1..256 only)
+    // stream = 1: barrier-free streaming wave kernels (dsp_stream.hip; narrow bands inside bins 1..256 and every wide band)
     int stream = 0;
     const float* gpad = nullptr;      // stream + adjoint: reflect-pad parts written by the streaming synthesis adjoint
     int write_pad = 1;                // stream, forward: write the zero tail of the mag / unit rows
@@ -223,7 +223,7 @@ void launch_opt_clamp(int kind, float* p, const float* g, float* m, float* v, co
                       const float* c4, const float* h8, hipStream_t st);
 void launch_opt_rows(int kind, float* coef, const float* grad, float* mom, float* vel, const float* c0, float ratio, float* best,
                      const int* improved, const int* frame_off, int B, int NF, const double* tab, int tab_len, const int* step,
-                     const double* lr_clip, double wd, const float* h8, int nband, hipStream_t st);
+                     const double* lr_clip, double wd, const float* h8, int nband, int stride, hipStream_t st);
 void launch_plateau(const float* loss, double* state, double* lr_clip, int B, double factor, int patience, double threshold,
                     double min_lr, double eps, hipStream_t st);
 

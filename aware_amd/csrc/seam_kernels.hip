@@ -140,15 +140,16 @@ __global__ __launch_bounds__(256) void opt_rows_kernel(int kind, float* __restri
                                                        const float* __restrict__ c0, float ratio, float* __restrict__ best,
                                                        const int* __restrict__ improved, const int* __restrict__ frame_off, int B,
                                                        const double* __restrict__ tab, int tab_len, const int* __restrict__ step,
-                                                       const double* __restrict__ lr_clip, double wd, OptHyp H, int nband) {
-    const int row = blockIdx.x, f = threadIdx.x;
+                                                       const double* __restrict__ lr_clip, double wd, OptHyp H, int nband,
+                                                       int stride) {
+    const int row = blockIdx.x;
     int lo_ = 0, hi_ = B;                               // clip of this row: frame_off[clip] <= row < frame_off[clip + 1]
     while (hi_ - lo_ > 1) {
         const int mid = (lo_ + hi_) >> 1;
         if (frame_off[mid] <= row) lo_ = mid; else hi_ = mid;
     }
     const int clip = lo_;
-    if (f >= nband) return;
+    if ((int)threadIdx.x >= nband) return;
     const int t = min(max(*step - 1, 0), tab_len - 1);  // the read-out kernel already advanced the counter
     const double* e = tab + (size_t)t * 5;
     const double lr = lr_clip ? lr_clip[clip] : e[3];
@@ -158,20 +159,22 @@ __global__ __launch_bounds__(256) void opt_rows_kernel(int kind, float* __restri
     c.y = kind == OPT_SGD ? (float)e[1] : (float)(lr * e[1]);
     c.z = (float)e[2];
     c.w = (float)(1.0 - lr * wd);
-    const size_t idx = (size_t)row * kFS + f;
-    float p = coef[idx], mo = mom[idx], ve = vel[idx], blo, bhi;
-    box_bounds(c0[idx], ratio, blo, bhi);
-    opt_clamp_update(kind, p, mo, ve, grad[idx], blo, bhi, c, H);
-    coef[idx] = p; mom[idx] = mo; vel[idx] = ve;
-    if (improved[clip]) best[idx] = p;
+    for (int f = threadIdx.x; f < nband; f += blockDim.x) {         // (a wide-layout row has up to 513 band columns)
+        const size_t idx = (size_t)row * stride + f;
+        float p = coef[idx], mo = mom[idx], ve = vel[idx], blo, bhi;
+        box_bounds(c0[idx], ratio, blo, bhi);
+        opt_clamp_update(kind, p, mo, ve, grad[idx], blo, bhi, c, H);
+        coef[idx] = p; mom[idx] = mo; vel[idx] = ve;
+        if (improved[clip]) best[idx] = p;
+    }
 }
 void launch_opt_rows(int kind, float* coef, const float* grad, float* mom, float* vel, const float* c0, float ratio, float* best,
                      const int* improved, const int* frame_off, int B, int NF, const double* tab, int tab_len, const int* step,
-                     const double* lr_clip, double wd, const float* h8, int nband, hipStream_t st) {
+                     const double* lr_clip, double wd, const float* h8, int nband, int stride, hipStream_t st) {
     OptHyp H;
     for (int i = 0; i < 8; ++i) H.h[i] = h8[i];
     hipLaunchKernelGGL(opt_rows_kernel, dim3(NF), dim3(256), 0, st, kind, coef, grad, mom, vel, c0, ratio, best, improved, frame_off,
-                       B, tab, tab_len, step, lr_clip, wd, H, nband);
+                       B, tab, tab_len, step, lr_clip, wd, H, nband, stride);
 }
 
 // torch.optim.lr_scheduler.ReduceLROnPlateau(mode 'min', threshold_mode 'rel', cooldown 0), one state per clip, stepped with

@@ -90,6 +90,8 @@ class AWAREDetectorNet(BaseDetectorNet):
                                 "running_mean": np.zeros(c, np.float32), "running_var": np.ones(c, np.float32),
                                 "eps": BATCH_NORM_EPS} for c in self.channels[1:]]
         self._dev = None
+        # the band the plug-in seam (forward) hands to the network: set by the embedder / detector that owns the net
+        self.embedding_bands = None
 
     @property
     def is_card_arch(self) -> bool:
@@ -124,6 +126,13 @@ class AWAREDetectorNet(BaseDetectorNet):
             yield bn["weight"]
             yield bn["bias"]
 
+    def band_plan(self):
+        """Card plan of the net's embedding band (`embedding_bands`, Hz at `sample_rate`; None: the default plan)."""
+        from ..utils.audio import band_bins, default_plan, get_plan
+        if self.embedding_bands is None:
+            return default_plan()
+        return get_plan(bins=band_bins(self.sample_rate, self.n_fft, self.embedding_bands))
+
     def device_weights(self, plan):
         """Device copy (aware_detector) bound to a plan; created on first use."""
         from ..runtime import DetectorWeights
@@ -135,8 +144,8 @@ class AWAREDetectorNet(BaseDetectorNet):
         """[B, n_fft/2+1, T] magnitudes -> [B, output_length, 1]  (net :109-140).
 
         Only the embedding band reaches the network (callers zero the rest,
-        multibit_embedder.py:104, multibit_detector.py:34-37); the band is taken from the
-        default plan (500-4000 Hz at 16 kHz)."""
+        multibit_embedder.py:104, multibit_detector.py:34-37): `embedding_bands` (Hz, set by the
+        AWAREEmbedder / AWAREDetector that owns the net), or 500-4000 Hz when it is None."""
         return _DetectorNetFn.apply(stft_magnitude.to("cuda", torch.float32), self)
 
     def get_model_info(self):
@@ -154,11 +163,10 @@ def _frames_batch(B, T):
 
 
 def _band_rows(stft_magnitude, plan):
-    """[B, F, T] -> frame-major band rows [B*T, 256] (layout conversion at the seam)."""
-    from .. import runtime as rt
+    """[B, F, T] -> frame-major band rows [B*T, plan.band_stride] (layout conversion at the seam)."""
     B, F, T = stft_magnitude.shape
     lo, hi = plan.band_bins
-    mag = torch.zeros((B * T, rt.SPEC_STRIDE), dtype=torch.float32, device=stft_magnitude.device)
+    mag = torch.zeros((B * T, plan.band_stride), dtype=torch.float32, device=stft_magnitude.device)
     mag[:, : hi - lo + 1] = stft_magnitude[:, lo:hi + 1, :].permute(0, 2, 1).reshape(B * T, -1)
     return mag
 
@@ -171,7 +179,7 @@ class _DetectorNetFn(torch.autograd.Function):
     def forward(ctx, stft_magnitude, net):
         from .. import runtime as rt
         from ..utils.audio import default_plan
-        plan = default_plan()
+        plan = net.band_plan()
         B, F, T = stft_magnitude.shape
         batch = _frames_batch(B, T)
         mag = _band_rows(stft_magnitude, plan)

@@ -35,6 +35,7 @@ class AWAREEmbedder(BaseEmbedder):
         self.num_iterations = num_iterations
         self.pattern_mode = pattern_mode
         self.detection_net = AWAREDetectorNet(**(detection_net_cfg or {}))
+        self.detection_net.embedding_bands = self.embedding_bands
         optimizer_cfg = optimizer_cfg or {"name": "nadam", "params": {"lr": 0.1}}
         scheduler_cfg = scheduler_cfg or {"name": "reduce_lr_on_plateau", "params": {"factor": 0.9, "patience": 500}}
         self.optimizer_name, self.optimizer_params = optimizer_cfg["name"], optimizer_cfg.get("params", {}) or {}

@@ -14,10 +14,17 @@ import torch
 from . import _lib
 from ._lib import AwareHipError, DetectorArch, EmbedConfig, check, load_library, require_gpu
 
-SPEC_STRIDE = 256
+SPEC_STRIDE = 256         # floats per band row, narrow layout (a plan's own value: Plan.band_stride)
+SPEC_STRIDE_WIDE = 576    # ... wide layout: a band outside bins 1..511 or wider than 256 bins
 FULL_STRIDE = 520
 CONV_PIPES = {"f16x2": 0, "f32": 1, "bf16x3": 2}
 LOSS_KINDS = {"push_extremes": 0, "mse": 1, "hinge": 2, "sign": 3, "push_sigmoid": 4, "ber": 5, "push_extremes_l1": 6}
+
+
+def band_stride(band_lo: int, band_hi: int) -> int:
+    """Row layout of a card plan's band-limited arrays (band_stride_for, csrc/common.hpp): SPEC_STRIDE for a band inside bins
+    1..511 at most 256 bins wide, SPEC_STRIDE_WIDE for any other band inside bins 0..512."""
+    return SPEC_STRIDE if band_lo >= 1 and band_hi <= 511 and band_hi - band_lo + 1 <= SPEC_STRIDE else SPEC_STRIDE_WIDE
 
 
 def _stream():
@@ -93,6 +100,7 @@ class Plan:
         self.win_length, self.window = win_length, window
         self.nband = self.band_bins[1] - self.band_bins[0] + 1
         self.spectrum_stride = self.lib.aware_plan_spectrum_stride(h)
+        self.band_stride = self.lib.aware_plan_band_stride(h)      # floats per row of the band-limited arrays
         self.general = bool(self.lib.aware_plan_is_general(h))
 
     def __del__(self):
@@ -194,8 +202,8 @@ def _check_nola(rc: int, plan: Plan, batch: Batch):
 
 
 def stft_band(plan: Plan, batch: Batch, audio: torch.Tensor, normalize=True):
-    mag = torch.empty((batch.total_frames, SPEC_STRIDE), dtype=torch.float32, device=audio.device)
-    ph = torch.empty((batch.total_frames, SPEC_STRIDE), dtype=torch.complex64, device=audio.device)
+    mag = torch.empty((batch.total_frames, plan.band_stride), dtype=torch.float32, device=audio.device)
+    ph = torch.empty((batch.total_frames, plan.band_stride), dtype=torch.complex64, device=audio.device)
     scr = batch.scratch()
     check(plan.lib.aware_stft_band(plan.h, batch.h, _ptr(audio), int(normalize), _ptr(mag), _ptr(ph), _ptr(scr), _stream()),
           "aware_stft_band")
@@ -314,11 +322,11 @@ class NAdamClamp:
 
 
 def detector_backward(plan: Plan, det: "DetectorWeights", batch: Batch, mag: torch.Tensor, grad_values: torch.Tensor):
-    """(values [B, n_bits], grad_mag [total_frames, 256]) = forward and J^T grad_values of the frozen network."""
+    """(values [B, n_bits], grad_mag [total_frames, plan.band_stride]) = forward and J^T grad_values of the frozen network."""
     nbytes = plan.lib.aware_detector_backward_workspace_bytes(batch.h, det.h)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=mag.device)
     vals = torch.empty((batch.B, det.n_bits), dtype=torch.float32, device=mag.device)
-    gmag = torch.empty((batch.total_frames, SPEC_STRIDE), dtype=torch.float32, device=mag.device)
+    gmag = torch.empty((batch.total_frames, plan.band_stride), dtype=torch.float32, device=mag.device)
     gv = grad_values.contiguous().float()
     check(plan.lib.aware_detector_backward(det.h, batch.h, _ptr(mag), _ptr(gv), _ptr(vals), _ptr(gmag), _ptr(ws), nbytes, _stream()),
           "aware_detector_backward")
@@ -326,10 +334,14 @@ def detector_backward(plan: Plan, det: "DetectorWeights", batch: Batch, mag: tor
 
 
 def require_card_arch(det: "DetectorWeights", what: str):
-    """The detector-training extension serves the model card's architecture only (the C ABI returns AWARE_E_UNSUPPORTED)."""
+    """The detector-training extension serves the model card's architecture on a band of the narrow layout only (the C ABI
+    returns AWARE_E_UNSUPPORTED)."""
     if not det.is_card:
         raise NotImplementedError(f"{what}: detector training supports the model card's architecture only "
                                   "(instance norm, leaky_relu blocks, tanh read-out)")
+    if det.plan.band_stride != SPEC_STRIDE:
+        raise NotImplementedError(f"{what}: detector training supports bands inside bins 1..511 at most 256 bins wide only; "
+                                  f"the band {det.plan.band_bins} has the wide layout")
 
 
 def detector_weight_gradients(plan: Plan, det: "DetectorWeights", batch: Batch, mag: torch.Tensor, grad_values: torch.Tensor):
@@ -340,7 +352,7 @@ def detector_weight_gradients(plan: Plan, det: "DetectorWeights", batch: Batch, 
     nbytes = lib.aware_detector_train_workspace_bytes(batch.h, det.h)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=mag.device)
     vals = torch.empty((batch.B, det.n_bits), dtype=torch.float32, device=mag.device)
-    gmag = torch.empty((batch.total_frames, SPEC_STRIDE), dtype=torch.float32, device=mag.device)
+    gmag = torch.empty((batch.total_frames, plan.band_stride), dtype=torch.float32, device=mag.device)
     ch = det.channels
     gw = [torch.empty((ch[i + 1], ch[i]), dtype=torch.float32, device=mag.device) for i in range(len(ch) - 1)]
     gb = [torch.empty((ch[i + 1],), dtype=torch.float32, device=mag.device) for i in range(len(ch) - 1)]
@@ -522,7 +534,7 @@ class EmbedSession:
         check(rc, "aware_embed_iterate")
 
     def gradient(self) -> torch.Tensor:
-        g = torch.zeros((self.batch.total_frames, SPEC_STRIDE), dtype=torch.float32, device=self.ws.device)
+        g = torch.zeros((self.batch.total_frames, self.plan.band_stride), dtype=torch.float32, device=self.ws.device)
         check(self.lib.aware_embed_gradient(self.h, _ptr(g), _stream()), "aware_embed_gradient")
         return g
 
@@ -552,16 +564,16 @@ class EmbedSession:
 
     @property
     def coef(self):
-        return self._view(3, (self.batch.total_frames, SPEC_STRIDE))
+        return self._view(3, (self.batch.total_frames, self.plan.band_stride))
 
     @property
     def best_coef(self):
-        return self._view(4, (self.batch.total_frames, SPEC_STRIDE))
+        return self._view(4, (self.batch.total_frames, self.plan.band_stride))
 
     @property
     def bounds(self):
-        return (self._view(5, (self.batch.total_frames, SPEC_STRIDE)),
-                self._view(6, (self.batch.total_frames, SPEC_STRIDE)))
+        return (self._view(5, (self.batch.total_frames, self.plan.band_stride)),
+                self._view(6, (self.batch.total_frames, self.plan.band_stride)))
 
     @property
     def step(self):

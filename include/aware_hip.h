@@ -18,8 +18,13 @@
  *   - all arithmetic is IEEE fp32 unless a parameter says f64;
  *   - a "batch" is a ragged set of B mono clips; clip b has n_b samples,
  *     T_b = 1 + n_b/256 frames, Ny_b = 256*(T_b-1) output samples, T_b/2 pooled frames.
- *   - band-limited spectra are frame-major [total frames][256] (first 225 columns are
- *     bins 32..256 = 500..4000 Hz at 16 kHz, n_fft 1024; the tail is zero).
+ *   - band-limited spectra are frame-major [total frames][aware_plan_band_stride(plan)] (column f
+ *     is bin band_lo + f; the model card's band: 225 columns, bins 32..256 = 500..4000 Hz at 16 kHz,
+ *     n_fft 1024, of 256; the tail is zero).  The stride is AWARE_SPEC_STRIDE = 256 for a band
+ *     inside bins 1..511 at most 256 bins wide (the narrow layout), AWARE_SPEC_STRIDE_WIDE = 576
+ *     for any other band inside bins 0..512 (the wide layout).  Every band-limited array of this
+ *     header -- aware_stft_band's mag / phasor, aware_detector_forward / _backward's mag /
+ *     grad_mag, aware_embed_gradient's grad and the embed views -- has that many floats per row.
  */
 #ifndef AWARE_HIP_H
 #define AWARE_HIP_H
@@ -47,7 +52,8 @@ extern "C" {
 #define AWARE_LOSS_PUSH_L1 6        /* EXTENSION (BASELINE config 3 "BER+L1"): push_extremes + l1_weight * mean|c - c0| */
 #define AWARE_LOSS_EXTERNAL 7       /* internal: `target` holds dL/dpred (aware_detector_backward) */
 
-#define AWARE_SPEC_STRIDE 256      /* floats per frame row of a band-limited array */
+#define AWARE_SPEC_STRIDE 256      /* floats per frame row of a band-limited array (narrow layout) */
+#define AWARE_SPEC_STRIDE_WIDE 576 /* ... of a band with the wide layout (aware_plan_band_stride) */
 #define AWARE_FULL_STRIDE 520      /* complex values per frame row of a full one-sided spectrum */
 
 typedef struct aware_plan aware_plan;
@@ -58,7 +64,8 @@ typedef struct aware_embed aware_embed;
 /* ABI version (200: no process-global knobs, the kernel choices live in aware_embed_config; 300: conv_pipe 0 = f16 two-term
  * kernels, optimiser / scheduler registries, device-side detector training, aware_stft_bwd for any clip length; 310: general
  * STFT geometry -- aware_plan_create_ex, aware_plan_spectrum_stride, aware_plan_is_general, aware_batch_create_for_plan,
- * aware_nola_check; 320: detector architecture variants -- aware_detector_create_ex, aware_detector_is_card) */
+ * aware_nola_check; 320: detector architecture variants -- aware_detector_create_ex, aware_detector_is_card; 330: any
+ * embedding band inside bins 0..512 -- the wide layout, aware_plan_band_stride) */
 int aware_version(void);
 /* text of the last failed HIP runtime call on the calling thread (thread-local) */
 const char* aware_last_hip_error(void);
@@ -70,7 +77,8 @@ const char* aware_last_hip_error(void);
  * Replaces the constructor state of STFT / ISTFT (src/AWARE/utils/audio/stft.py:14-25,
  * :34-45: n_fft, hop_length, window "hann"|"hamming", win_length) and
  * AWAREEmbedder._get_embedding_frequency_indices (embedding/multibit_embedder.py:43-47).
- * window: 0 = hann (periodic), 1 = hamming (periodic).  band_lo_bin/band_hi_bin inclusive. */
+ * window: 0 = hann (periodic), 1 = hamming (periodic).  band_lo_bin/band_hi_bin inclusive, any band with
+ * 0 <= band_lo_bin <= band_hi_bin <= n_fft/2 (else AWARE_E_UNSUPPORTED); aware_plan_band_stride gives its row layout. */
 int aware_plan_create(aware_plan** out, int n_fft, int hop, int win_length, int window,
                       int band_lo_bin, int band_hi_bin);
 void aware_plan_destroy(aware_plan* plan);
@@ -90,6 +98,9 @@ int aware_plan_create_ex(aware_plan** out, int n_fft, int hop, int win_length, i
 int aware_plan_spectrum_stride(const aware_plan* plan);
 /* 1 for a general plan, 0 for the card plan */
 int aware_plan_is_general(const aware_plan* plan);
+/* floats per row of the plan's band-limited arrays: AWARE_SPEC_STRIDE or AWARE_SPEC_STRIDE_WIDE (card plans; a general plan,
+ * which has no band kernels, reports AWARE_SPEC_STRIDE).  The *_workspace_bytes functions count rows of this stride. */
+int aware_plan_band_stride(const aware_plan* plan);
 /* torch.istft's NOLA condition (host only, no device): AWARE_OK when the overlap-add envelope of this geometry stays
  * >= 1e-11 over the trimmed output of a clip of n_samples samples (T = 1 + n_samples/hop frames), AWARE_E_BADARG when
  * torch.istft would raise for it (aware_istft / aware_istft_bwd refuse such a batch with AWARE_E_BADARG) */
@@ -126,7 +137,8 @@ int aware_stft(const aware_plan* plan, const aware_batch* batch, const float* au
 int aware_istft(const aware_plan* plan, const aware_batch* batch, const void* spec, int normalize,
                 float* out, void* scratch, void* stream);
 /* aware_stft_band: normalise + STFT + STFTDecomposer restricted to the embedding band:
- * mag [total frames][256] and unit phasor (cos, sin of the phase) [total frames][256] complex64. */
+ * mag [total frames][stride] and unit phasor (cos, sin of the phase) [total frames][stride] complex64, stride =
+ * aware_plan_band_stride(plan).  DC and Nyquist, when in the band, have phasor (+-1, 0) as torch.angle gives 0 / pi. */
 int aware_stft_band(const aware_plan* plan, const aware_batch* batch, const float* audio, int normalize,
                     float* mag, void* phasor, void* scratch, void* stream);
 
@@ -230,7 +242,7 @@ int aware_detector_forward(const aware_detector* det, const aware_batch* batch, 
                            float* values, void* workspace, size_t workspace_bytes, void* stream);
 
 /* forward + backward of the network for the differentiable seam (BaseDetectorNet.forward, interfaces/detection.py:10-14,
- * under autograd): values [B][n_bits] (may be NULL) and grad_mag [total frames][256] = J^T grad_values; data gradients
+ * under autograd): values [B][n_bits] (may be NULL) and grad_mag [total frames][band stride] = J^T grad_values; data gradients
  * only (the reference freezes the weights, multibit_embedder.py:76-77). */
 size_t aware_detector_backward_workspace_bytes(const aware_batch* batch, const aware_detector* det);
 int aware_detector_backward(const aware_detector* det, const aware_batch* batch, const float* mag,
@@ -242,7 +254,8 @@ int aware_detector_backward(const aware_detector* det, const aware_batch* batch,
  * by torch autograd on the oracle's Detector).  aware_detector_weight_gradients = aware_detector_backward plus
  * dL/dW_l [Cout][Cin] and dL/db_l [Cout] of every conv block (grad_weights / grad_biases: host arrays of n_layers device
  * pointers, entries may be NULL); the caller all-reduces them over its ranks, applies its optimiser and writes the new
- * parameters back with aware_detector_update (host arrays as for aware_detector_create, same shapes, synchronous). */
+ * parameters back with aware_detector_update (host arrays as for aware_detector_create, same shapes, synchronous).
+ * The gradient entry points serve detectors of a narrow-layout band only: AWARE_E_UNSUPPORTED for the wide layout. */
 size_t aware_detector_train_workspace_bytes(const aware_batch* batch, const aware_detector* det);
 int aware_detector_weight_gradients(const aware_detector* det, const aware_batch* batch, const float* mag,
                                     const float* grad_values, float* values, float* grad_mag,
@@ -290,7 +303,7 @@ typedef struct aware_embed_config {
     int readout;
     /* dsp_path 0: streaming wave kernels for the framed STFT / iSTFT and their adjoints (csrc/dsp_stream.hip: one wave
      *   streams a run of frames, overlap-add and frame overlap in registers, no barrier) wherever the band lies inside
-     *   bins 1..256; 1: workgroup-staged kernels (csrc/dsp_kernels.hip: any band; the form the streaming kernels are
+     *   bins 1..256 or has the wide layout; 1: workgroup-staged kernels (csrc/dsp_kernels.hip: any band; the form the streaming kernels are
      *   tested against). */
     int dsp_path;
     /* loss AWARE_LOSS_PUSH_L1 only (EXTENSION, BASELINE config 3 "BER + L1"; the reference's imperceptibility device is
@@ -298,7 +311,8 @@ typedef struct aware_embed_config {
     float l1_weight;
     /* mel 0: the mel projection's backward runs as two taps per bin inside the streaming synthesis adjoint (a triangular filter
      *   bank -- detection/modules/mel.py:105-149 -- has at most two adjacent non-zero weights per FFT bin; dL/d|S| is never
-     *   stored) whenever dsp_path is 0 and the detector's basis has that form; 1: the dense [NF][128] x [128][256] GEMM
+     *   stored) whenever dsp_path is 0, the band has the narrow layout and the detector's basis has that form; 1: the dense
+     *   [NF][128] x [128][stride] GEMM (the only form of a band with the wide layout)
      *   (what the fused form is tested against). */
     int mel;
 } aware_embed_config;
@@ -348,7 +362,7 @@ int aware_embed_begin(aware_embed* e, const float* audio, const float* target, v
  * cfg.num_iterations steps would have run since aware_embed_begin (the reference's loop runs exactly that many). */
 int aware_embed_iterate(aware_embed* e, int n_iters, void* stream);
 /* forward + backward without the optimiser step and without best-loss bookkeeping; grad: dev f32
- * [total frames][256] = dL/dcoef; loss[] and pred[] (aware_embed_buffer 0, 2) are refreshed */
+ * [total frames][band stride] = dL/dcoef; loss[] and pred[] (aware_embed_buffer 0, 2) are refreshed */
 int aware_embed_gradient(aware_embed* e, float* grad, void* stream);
 /* Timing aid for the roofline report: runs n_iters loop bodies eagerly with a HIP event recorded on
  * `stream` after every kernel launch; writes the elapsed milliseconds between consecutive events and
@@ -362,7 +376,7 @@ int aware_embed_profile(aware_embed* e, int n_iters, int max_entries, float* ms_
  * (service/embed.py:69,73): out[b] = rescale[b] * normalise(istft(...)).  rescale: dev f32 [B] or NULL. */
 int aware_embed_finish(aware_embed* e, const float* rescale, float* out, void* stream);
 /* device pointers to internal state for inspection: 0 loss[B], 1 best_loss[B], 2 pred[B][n_bits],
- * 3 coef [frames][256], 4 best coef, 5 lo, 6 hi, 7 phasor (complex64), 8 step counter (int32), 9 un-normalised synthesis,
+ * 3 coef [frames][band stride], 4 best coef, 5 lo, 6 hi, 7 phasor (complex64), 8 step counter (int32), 9 un-normalised synthesis,
  * 10 band magnitudes of the last analysis, 11 per-clip learning rates (f64 [B]; NULL unless aware_embed_set_optimizer ran) */
 void* aware_embed_buffer(aware_embed* e, int which);
 
