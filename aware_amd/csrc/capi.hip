@@ -93,6 +93,8 @@ struct aware_detector {
     int n_mels = 0, n_layers = 0, nbits = 0;
     int band_lo = 0, nband = 0;
     int stride = kFS;        // floats per band row of the plan the detector was created for
+    // channel counts as stored: ch[n_layers] is the last block's padded count Cp >= 2 * nbits (last_block_channels); its
+    // padding channels have zero weights and bias, are never read out and get a zero gradient
     int ch[8] = {0};
     int maxc = 0;
     float* mem = nullptr;
@@ -141,7 +143,7 @@ static_assert(AWARE_NORM_INSTANCE == kNormInstance && AWARE_NORM_BATCH == kNormA
 // whether the staged route keeps the pre-activation of every block for the backward (DetBufs::stash)
 static bool det_needs_stash(const aware_detector* d) { return !d->card_arch && norm_act_needs_stash(d->norm, d->act); }
 
-extern "C" int aware_version(void) { return 330; }
+extern "C" int aware_version(void) { return 340; }
 extern "C" const char* aware_last_hip_error(void) { return g_last_err.c_str(); }
 
 // ---------------------------------------------------------------------------------------------
@@ -717,6 +719,15 @@ extern "C" int aware_istft_bwd(const aware_plan* plan, const aware_batch* b, con
 
 // ---------------------------------------------------------------------------------------------
 extern "C" void aware_detector_destroy(aware_detector* d);
+// the widest last block (payloads of up to 512 bits)
+constexpr int kMaxOutChannels = 1024;
+// channels the last block is stored with for C = 2 * payload bits: C itself where the read-out kernels for C <= 64 take it
+// (a multiple of 4), C rounded up to a multiple of 4 below that, and above 64 C rounded up to a multiple of 128 so that the
+// conv-block kernels take the block and the wide read-out (launch_readout_wide) reads it out
+static int last_block_channels(int C) {
+    if (C <= 64) return (C + 3) & ~3;
+    return (C + 127) & ~127;
+}
 // host staging of the detector's parameters (plain + transposed f32 copies, bf16x3 fragment images) and upload; `alloc`
 // = false re-uses the device buffers of a detector created with the same shapes (aware_detector_update)
 static int detector_upload(aware_detector* d, const float* mel_basis, const float* const* weights,
@@ -793,16 +804,17 @@ static int detector_upload(aware_detector* d, const float* mel_basis, const floa
     size_t o_w[8], o_wT[8], o_b[8];
     for (int l = 0; l < n_layers; ++l) {
         const int ci = channels[l], co = channels[l + 1];
+        const int rows = l == n_layers - 1 ? 2 * d->nbits : co;   // the caller's rows; padding rows stay zero
         o_w[l] = o; o += (size_t)ci * co;
         o_wT[l] = o; o += (size_t)ci * co;
         o_b[l] = o; o += co;
-        for (int r = 0; r < co; ++r)
+        for (int r = 0; r < rows; ++r)
             for (int c = 0; c < ci; ++c) {
                 float v = weights[l][(size_t)r * ci + c];
                 h[o_w[l] + (size_t)r * ci + c] = v;
                 h[o_wT[l] + (size_t)c * co + r] = v;
             }
-        for (int r = 0; r < co; ++r) h[o_b[l] + r] = biases && biases[l] ? biases[l][r] : 0.f;
+        for (int r = 0; r < rows; ++r) h[o_b[l] + r] = biases && biases[l] ? biases[l][r] : 0.f;
     }
     if (alloc) HIPCHK(hipMalloc((void**)&d->mem, total * sizeof(float)));
     HIPCHK(hipMemcpy(d->mem, h.data(), total * sizeof(float), hipMemcpyHostToDevice));
@@ -832,7 +844,7 @@ static int detector_upload(aware_detector* d, const float* mel_basis, const floa
             std::vector<float> wp((size_t)colp * cil, 0.f), wt((size_t)cil * 64, 0.f);
             for (int r = 0; r < col; ++r)
                 for (int c = 0; c < cil; ++c) {
-                    const float v = weights[n_layers - 1][(size_t)r * cil + c];
+                    const float v = h[o_w[n_layers - 1] + (size_t)r * cil + c];
                     wp[(size_t)r * cil + c] = v;
                     wt[(size_t)c * 64 + r] = v;
                 }
@@ -886,27 +898,32 @@ static int detector_create(aware_detector** out, const aware_plan* plan, const f
     if (plan->general) return AWARE_E_UNSUPPORTED;       // the detector runs on the card geometry only
     if (n_mels != 128 || n_layers < 1 || n_layers > 7 || channels[0] != n_mels) return AWARE_E_UNSUPPORTED;
     const int cl = channels[n_layers];
-    if (cl % 2 || cl > 64) return AWARE_E_UNSUPPORTED;
-    for (int i = 0; i <= n_layers; ++i)
+    if (cl % 2 || cl < 2 || cl > kMaxOutChannels) return AWARE_E_UNSUPPORTED;
+    for (int i = 0; i < n_layers; ++i)
         if (channels[i] % 4) return AWARE_E_UNSUPPORTED;
     aware_detector* d = new aware_detector();
     d->n_mels = n_mels; d->n_layers = n_layers; d->nbits = cl / 2;
     d->band_lo = plan->dev.band_lo; d->nband = plan->dev.nband; d->stride = plan->dev.stride;
-    for (int i = 0; i <= n_layers; ++i) { d->ch[i] = channels[i]; if (channels[i] > d->maxc) d->maxc = channels[i]; }
+    for (int i = 0; i <= n_layers; ++i) {
+        d->ch[i] = i == n_layers ? last_block_channels(cl) : channels[i];
+        if (d->ch[i] > d->maxc) d->maxc = d->ch[i];
+    }
     if (arch) {
         d->act = arch->activation; d->norm = arch->norm; d->final_act = arch->final_activation;
         d->card_arch = d->act == kActLRelu && d->norm == kNormInstance && d->final_act == kActTanh;
     }
     int rc = detector_upload(d, mel_basis, weights, biases, true);
     if (rc == AWARE_OK && d->norm == kNormAffine) {
+        // the padding channels of the last block get scale 0 and shift 0: their pre-activation is 0 and their output
+        // act(0) = 0 for every block activation.  They are never read out and their gradient is zero.
         size_t n = 0;
-        for (int l = 0; l < n_layers; ++l) n += 2 * (size_t)channels[l + 1];
-        std::vector<float> h(n);
+        for (int l = 0; l < n_layers; ++l) n += 2 * (size_t)d->ch[l + 1];
+        std::vector<float> h(n, 0.f);
         size_t o = 0;
         for (int l = 0; l < n_layers; ++l) {
-            const int co = channels[l + 1];
-            memcpy(h.data() + o, arch->norm_scale[l], co * sizeof(float));
-            memcpy(h.data() + o + co, arch->norm_shift[l], co * sizeof(float));
+            const int co = d->ch[l + 1];
+            memcpy(h.data() + o, arch->norm_scale[l], channels[l + 1] * sizeof(float));
+            memcpy(h.data() + o + co, arch->norm_shift[l], channels[l + 1] * sizeof(float));
             o += 2 * (size_t)co;
         }
         if (hipMalloc((void**)&d->normmem, n * sizeof(float)) != hipSuccess ||
@@ -916,8 +933,8 @@ static int detector_create(aware_detector** out, const aware_plan* plan, const f
             o = 0;
             for (int l = 0; l < n_layers; ++l) {
                 d->nscale[l] = d->normmem + o;
-                d->nshift[l] = d->normmem + o + channels[l + 1];
-                o += 2 * (size_t)channels[l + 1];
+                d->nshift[l] = d->normmem + o + d->ch[l + 1];
+                o += 2 * (size_t)d->ch[l + 1];
             }
         }
     }
@@ -965,10 +982,11 @@ extern "C" int aware_detector_update_device(aware_detector* d, const float* cons
     const int nl = d->n_layers;
     for (int l = 0; l < nl; ++l) {
         const int ci = d->ch[l], co = d->ch[l + 1];
+        const int rows = l == nl - 1 ? 2 * d->nbits : co;   // the caller's rows; the padding rows stay zero
         if (!dev_weights[l]) return AWARE_E_BADARG;
-        HIPCHK(hipMemcpyAsync(d->w[l], dev_weights[l], (size_t)ci * co * sizeof(float), hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipMemcpyAsync(d->w[l], dev_weights[l], (size_t)ci * rows * sizeof(float), hipMemcpyDeviceToDevice, st));
         if (dev_biases && dev_biases[l])
-            HIPCHK(hipMemcpyAsync(d->bias[l], dev_biases[l], (size_t)co * sizeof(float), hipMemcpyDeviceToDevice, st));
+            HIPCHK(hipMemcpyAsync(d->bias[l], dev_biases[l], (size_t)rows * sizeof(float), hipMemcpyDeviceToDevice, st));
         launch_transpose(d->w[l], d->wT[l], co, ci, st);
         if (d->wpk[l]) launch_x3_pack_dev(d->w[l], ci, co, ci, co, ci, d->wpk[l], st);
         if (d->wTpk[l]) launch_x3_pack_dev(d->wT[l], co, ci, co, ci, co, d->wTpk[l], st);
@@ -1188,6 +1206,20 @@ static int det_forward(const aware_detector* d, const aware_batch* b, const floa
     return AWARE_OK;
 }
 
+// read-out of a forward-only call: values [B][nbits]
+static void readout_forward(const aware_detector* d, const aware_batch* b, const DetBufs& o, float* values, hipStream_t st) {
+    const int nl = d->n_layers, C = d->ch[nl];
+    if (o.tail)
+        launch_tail(o.zpart, kTailSplit, (size_t)b->NP * C, d->bias[nl - 1], b->d_frame_off, b->d_pool_off, nullptr, values,
+                    nullptr, nullptr, nullptr, nullptr, nullptr, 0, d->nbits, b->B, b->max_frames / 2, st, nullptr, 0, C);
+    else if (C > 64)
+        launch_readout_wide(o.act[nl - 1], C, b->d_frame_off, b->d_pool_off, nullptr, nullptr, values, nullptr, nullptr, nullptr,
+                            nullptr, nullptr, nullptr, 0, d->nbits, b->B, st, nullptr, d->final_act, false);
+    else
+        launch_head(o.act[nl - 1], b->d_frame_off, b->d_pool_off, nullptr, values, nullptr, nullptr, nullptr, nullptr, nullptr, 0,
+                    d->nbits, b->B, st, nullptr, d->final_act, C);
+}
+
 extern "C" size_t aware_detect_workspace_bytes(const aware_batch* b, const aware_detector* d) {
     if (!b || !d) return 0;
     return det_bytes(b, d) + (size_t)b->NF * d->stride * sizeof(float) + aware_batch_scratch_bytes(b) + 1024;
@@ -1204,12 +1236,7 @@ extern "C" int aware_detector_forward(const aware_detector* d, const aware_batch
     for (int l = 0; l < d->n_layers; ++l) o.stash[l] = nullptr;      // forward only: no backward reads the pre-activations
     int rc = det_forward(d, b, mag, o, st);
     if (rc) return rc;
-    if (o.tail)
-        launch_tail(o.zpart, kTailSplit, (size_t)b->NP * d->ch[d->n_layers], d->bias[d->n_layers - 1], b->d_frame_off,
-                    b->d_pool_off, nullptr, values, nullptr, nullptr, nullptr, nullptr, nullptr, 0, d->nbits, b->B, b->max_frames / 2, st);
-    else
-        launch_head(o.act[d->n_layers - 1], b->d_frame_off, b->d_pool_off, nullptr, values, nullptr, nullptr, nullptr,
-                    nullptr, nullptr, 0, d->nbits, b->B, st, nullptr, d->final_act);
+    readout_forward(d, b, o, values, st);
     LAUNCHCHK();
     return AWARE_OK;
 }
@@ -1233,12 +1260,7 @@ extern "C" int aware_detect(const aware_plan* plan, const aware_detector* d, con
     if (rc) return rc;
     rc = det_forward(d, b, mag, o, st);
     if (rc) return rc;
-    if (o.tail)
-        launch_tail(o.zpart, kTailSplit, (size_t)b->NP * d->ch[d->n_layers], d->bias[d->n_layers - 1], b->d_frame_off,
-                    b->d_pool_off, nullptr, values, nullptr, nullptr, nullptr, nullptr, nullptr, 0, d->nbits, b->B, b->max_frames / 2, st);
-    else
-        launch_head(o.act[d->n_layers - 1], b->d_frame_off, b->d_pool_off, nullptr, values, nullptr, nullptr, nullptr,
-                    nullptr, nullptr, 0, d->nbits, b->B, st, nullptr, d->final_act);
+    readout_forward(d, b, o, values, st);
     LAUNCHCHK();
     return AWARE_OK;
 }
@@ -1275,7 +1297,7 @@ static int det_forward_backward(const aware_detector* d, const aware_batch* b, c
     // conv (uniform batches, bf16x3 configuration); otherwise split-K GEMM + tail kernel + data-gradient GEMM
     const int pipe = G.pipe;
     const bool fused_readout = d->card_arch && G.readout == 0 && !G.wgrad && pipe != 1 && nwm && nl >= 2 && d->lastpk && G.target &&
-                               readout_x3_supported(nwm, d->ch[nl - 1], d->ch[nl]) && d->wpk[nl - 2] &&
+                               d->ch[nl] == 2 * d->nbits && readout_x3_supported(nwm, d->ch[nl - 1], d->ch[nl]) && d->wpk[nl - 2] &&
                                gemm_clip_x3_supported(nwm, d->ch[nl - 1], d->ch[nl - 2], d->ch[nl - 2]);
     int rc = det_forward(d, b, mag, db, st, pipe, fused_readout, G.xm_ready);
     if (rc) return rc;
@@ -1315,11 +1337,22 @@ static int det_forward_backward(const aware_detector* d, const aware_batch* b, c
         last_k64 = !nwm && pipe != 1 && !G.wgrad && nl >= 2 && d->lastTpk && d->ch[nl] <= 64 && d->ch[nl - 1] % 128 == 0;
         launch_tail(db.zpart, kTailSplit, (size_t)b->NP * d->ch[nl], d->bias[nl - 1], b->d_frame_off, b->d_pool_off,
                     G.target, db.pred, G.loss, G.best_loss, G.improved, dA, G.step, G.loss_kind, d->nbits, b->B,
-                    b->max_frames / 2, st, G.loss_add, last_k64 ? 64 : 0);
+                    b->max_frames / 2, st, G.loss_add, last_k64 ? 64 : 0, d->ch[nl]);
         dz_ready = true;
+    } else if (d->ch[nl] > 64) {
+        // wide last block (payloads above 32 bits): one read-out kernel per clip.  On the card it writes dL/dZ of the last
+        // block (InstanceNorm + LeakyReLU backward folded in) and, when the next data-gradient GEMM runs on the f16 two-term
+        // kernel, the per-clip maxima of that gradient; on the staged route it writes dL/dA for launch_norm_act_bwd
+        const bool card = d->card_arch;
+        const bool gm = card && (h2_bwd(nl - 1) || h2_rag_bwd(nl - 1));
+        launch_readout_wide(db.act[nl - 1], d->ch[nl], b->d_frame_off, b->d_pool_off, db.rstd[nl - 1], G.target, db.pred, G.loss,
+                            G.best_loss, G.improved, dA, gm ? gA : nullptr, G.step, G.loss_kind, d->nbits, b->B, st, G.loss_add,
+                            d->final_act, card);
+        g_cur = gm;
+        dz_ready = card;
     } else {
         launch_head(db.act[nl - 1], b->d_frame_off, b->d_pool_off, G.target, db.pred, G.loss, G.best_loss,
-                    G.improved, dA, G.step, G.loss_kind, d->nbits, b->B, st, G.loss_add, d->final_act);
+                    G.improved, dA, G.step, G.loss_kind, d->nbits, b->B, st, G.loss_add, d->final_act, d->ch[nl]);
     }
     LAUNCHCHK(); PROF(K_HEAD);
     for (int l = l_top; l >= 0; --l) {
@@ -1342,11 +1375,19 @@ static int det_forward_backward(const aware_detector* d, const aware_batch* b, c
             // dA = dL/dZ_l [NP][co] (zero in padding rows), X = input of the block [NP][ci]:  dW = dZ^T X as an NT GEMM over
             // the transposed operands (K = NP contiguous); db = column sums of dZ (zero up to rounding: the InstanceNorm
             // behind the convolution removes any per-channel constant)
+            // (the last block's padding channels: only the caller's 2 * nbits rows of dW and db are written)
             const float* X = l > 0 ? db.act[l - 1] : db.x0;
+            const int rows = l == nl - 1 ? 2 * d->nbits : co;
             launch_transpose(dA, G.tr1, b->NP, co, st);
             launch_transpose(X, G.tr2, b->NP, ci, st);
-            launch_gemm_nt(G.tr1, b->NP, G.tr2, b->NP, nullptr, G.wgrad[l], ci, co, ci, b->NP, st);
-            if (G.bgrad && G.bgrad[l]) launch_colsum(dA, G.bgrad[l], b->NP, co, st);
+            launch_gemm_nt(G.tr1, b->NP, G.tr2, b->NP, nullptr, G.wgrad[l], ci, rows, ci, b->NP, st);
+            if (G.bgrad && G.bgrad[l]) {
+                if (rows == co) launch_colsum(dA, G.bgrad[l], b->NP, co, st);
+                else {
+                    launch_colsum(dA, G.tr2, b->NP, co, st);      // tr2 is free once the GEMM above has read it
+                    HIPCHK(hipMemcpyAsync(G.bgrad[l], G.tr2, (size_t)rows * sizeof(float), hipMemcpyDeviceToDevice, st));
+                }
+            }
             LAUNCHCHK(); PROF(K_MISC);
         }
         if (nwm && l > 0 && ci >= 128) {

@@ -1123,11 +1123,12 @@ __global__ __launch_bounds__(256) void head_kernel(const float* __restrict__ a3,
                                                     const float* __restrict__ target, float* __restrict__ pred,
                                                     float* __restrict__ loss_out, float* __restrict__ best_loss,
                                                     int* __restrict__ improved, float* __restrict__ dA3, int* __restrict__ step,
-                                                    int loss_kind, int nbits, const float* __restrict__ loss_add) {
+                                                    int loss_kind, int nbits, const float* __restrict__ loss_add, int C) {
+    // C: channel pitch of a3 / dA3, 2 * nbits or the detector's padded count (channels 2 * nbits .. C-1 are never read out;
+    // their dA3 is zero)
     __shared__ float part[4][64], mean[64], dm[64];
     const int b = blockIdx.x, c = threadIdx.x & 63, g = threadIdx.x >> 6;
     const int r0 = pool_off[b], Tp = (frame_off[b + 1] - frame_off[b]) / 2;   // rows are 32-aligned per clip
-    const int C = 2 * nbits;
     float m = 0.f;
     if (c < C)
         for (int t = g; t < Tp; t += 4) m += a3[(size_t)(r0 + t) * C + c];
@@ -1168,7 +1169,7 @@ __global__ __launch_bounds__(256) void head_kernel(const float* __restrict__ a3,
     if (!dA3) return;
     __syncthreads();
     if (c < C) {
-        const float gv = dm[c] / (float)Tp;
+        const float gv = c < 2 * nbits ? dm[c] / (float)Tp : 0.f;
         for (int t = g; t < Tp; t += 4) dA3[(size_t)(r0 + t) * C + c] = gv;
     }
 }
@@ -1188,12 +1189,13 @@ __global__ __launch_bounds__(256) void tail_kernel(const float* __restrict__ zpa
                                                     float* __restrict__ pred, float* __restrict__ loss_out,
                                                     float* __restrict__ best_loss, int* __restrict__ improved,
                                                     float* __restrict__ dZ, int* __restrict__ step, int loss_kind, int nbits,
-                                                    const float* __restrict__ loss_add, int ldz) {
-    // ldz: row pitch of dZ, C or 64 (columns C..63 are then written as zeros: K padding of the data-gradient GEMM)
+                                                    const float* __restrict__ loss_add, int ldz, int C) {
+    // C: channel pitch of zpart, 2 * nbits or the detector's padded count (padding channels: zero weights and bias, never
+    // read out, dZ zero).  ldz: row pitch of dZ, C or 64 (columns C..63 are then written as zeros: K padding of the
+    // data-gradient GEMM)
     __shared__ float red[4][64], red2[4][64], mean_s[64], dm[64];
     const int b = blockIdx.x, c = threadIdx.x & 63, g = threadIdx.x >> 6;
     const int r0 = pool_off[b], Tp = (frame_off[b + 1] - frame_off[b]) / 2;
-    const int C = 2 * nbits;
     const bool ok = c < C;
     const float invT = 1.0f / (float)Tp;
     float z[R];
@@ -1269,7 +1271,7 @@ __global__ __launch_bounds__(256) void tail_kernel(const float* __restrict__ zpa
     if (!dZ) return;
     __syncthreads();
     // dA[t][c] = dm[c]/Tp ; dU = dA * lrelu'(u) ; InstanceNorm backward
-    const float ga = ok ? dm[c] * invT : 0.f;
+    const float ga = c < 2 * nbits ? dm[c] * invT : 0.f;
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int i = 0; i < R; ++i)
@@ -1291,13 +1293,187 @@ __global__ __launch_bounds__(256) void tail_kernel(const float* __restrict__ zpa
 
 void launch_tail(const float* zpart, int nsplit, size_t slab, const float* bias, const int* frame_off, const int* pool_off,
                  const float* target, float* pred, float* loss, float* best_loss, int* improved, float* dZ, int* step,
-                 int loss_kind, int nbits, int B, int max_pooled, hipStream_t st, const float* loss_add, int ldz) {
-    if (ldz < 2 * nbits) ldz = 2 * nbits;
+                 int loss_kind, int nbits, int B, int max_pooled, hipStream_t st, const float* loss_add, int ldz, int C) {
+    if (C < 2 * nbits) C = 2 * nbits;
+    if (ldz < C) ldz = C;
 #define TL(S_, R_) hipLaunchKernelGGL((tail_kernel<S_, R_>), dim3(B), dim3(256), 0, st, zpart, slab, bias, frame_off, pool_off, \
-                                      target, pred, loss, best_loss, improved, dZ, step, loss_kind, nbits, loss_add, ldz)
+                                      target, pred, loss, best_loss, improved, dZ, step, loss_kind, nbits, loss_add, ldz, C)
     if (max_pooled <= 128) { if (nsplit == 4) TL(4, 32); else TL(1, 32); }
     else { if (nsplit == 4) TL(4, 80); else TL(1, 80); }
 #undef TL
+}
+// ---------------------------------------------------------------------------------
+// Wide BRH read-out for detectors whose last block has 64 < C <= 1024 channels (payloads of 33 .. 512 bits; the block is
+// stored with Cp = C rounded up to a multiple of 128, padding channels all zero).  One 256-thread workgroup per clip; it
+// walks the clip's pooled frames in a loop, so any clip length is served with a fixed register budget.  Thread = channel
+// slot cl of CW = min(Cp, 256) and time group g of 256 / CW; it owns channels cl, cl + CW, ... (at most kWideNJ).
+//   pass 1: per-channel time sums of the block output A (card: also of lrelu'(u) and lrelu'(u) u, u recovered from A)
+//   read-out: mean -> even - odd -> final activation -> loss / best-loss bookkeeping / step counter, as head_kernel
+//   pass 2: MODE 1: dL/dA [rows][Cp] (staged route: launch_norm_act_bwd consumes it)
+//           MODE 2: dL/dZ of the card block, the InstanceNorm + LeakyReLU backward folded in (dA is constant in time, so
+//                   mean_t dU = dA mean_t lrelu' and mean_t dU u = dA mean_t lrelu' u come from pass 1), and the per-clip
+//                   partial maxima of |dZ| for the f16 two-term data-gradient GEMM (gmax [B][64]: entry 0 the maximum,
+//                   entries 1 .. Cp/16 - 1 zero), when gmax is given
+// Rows Tp .. Tp rounded up to 32 (the clip's padding rows) and padding channels get a zero gradient.  MODE 0: pred only.
+// ---------------------------------------------------------------------------------
+constexpr int kWideNJ = 4;
+constexpr int kWideMaxC = 1024;
+template <int FA, int MODE>
+__global__ __launch_bounds__(256) void readout_wide_kernel(const float* __restrict__ A, int Cp, const int* __restrict__ frame_off,
+                                                            const int* __restrict__ pool_off, const float* __restrict__ rstd,
+                                                            const float* __restrict__ target, float* __restrict__ pred,
+                                                            float* __restrict__ loss_out, float* __restrict__ best_loss,
+                                                            int* __restrict__ improved, float* __restrict__ dout,
+                                                            float* __restrict__ gmax, int* __restrict__ step, int loss_kind,
+                                                            int nbits, const float* __restrict__ loss_add) {
+    __shared__ float s_a[kWideMaxC], s_l[kWideMaxC], s_lu[kWideMaxC];
+    __shared__ float red[4];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int CW = Cp < 256 ? Cp : 256, NG = 256 / CW;
+    const int cl = tid % CW, g = tid / CW;
+    const int r0 = pool_off[b], Tp = (frame_off[b + 1] - frame_off[b]) / 2;   // rows are 32-aligned per clip
+    const int C = 2 * nbits;
+    const float invT = 1.0f / (float)Tp;
+    float sa[kWideNJ], sl[kWideNJ], slu[kWideNJ];
+#pragma unroll
+    for (int j = 0; j < kWideNJ; ++j) { sa[j] = 0.f; sl[j] = 0.f; slu[j] = 0.f; }
+    for (int t = g; t < Tp; t += NG) {
+        const float* row = A + (size_t)(r0 + t) * Cp;
+#pragma unroll
+        for (int j = 0; j < kWideNJ; ++j) {
+            const int c = cl + CW * j;
+            if (c < Cp) {
+                const float a = row[c];
+                sa[j] += a;
+                if (MODE == 2) {
+                    const float sg = a > 0.f ? 1.f : 0.2f;
+                    sl[j] += sg;
+                    slu[j] += sg * (a > 0.f ? a : a * 5.0f);   // lrelu'(u) u, u = LeakyReLU(0.2)^-1 (a)
+                }
+            }
+        }
+    }
+    // time groups -> per-channel sums in LDS (g = 0 writes, the others add in order)
+    for (int gg = 0; gg < NG; ++gg) {
+        if (g == gg) {
+#pragma unroll
+            for (int j = 0; j < kWideNJ; ++j) {
+                const int c = cl + CW * j;
+                if (c < Cp) {
+                    s_a[c] = gg ? s_a[c] + sa[j] : sa[j];
+                    if (MODE == 2) { s_l[c] = gg ? s_l[c] + sl[j] : sl[j]; s_lu[c] = gg ? s_lu[c] + slu[j] : slu[j]; }
+                }
+            }
+        }
+        __syncthreads();
+    }
+    // read-out and loss; dmv = dL/d(even - odd) of the bits this thread owns
+    float lterm = 0.f;
+    float dmv[(kWideMaxC / 2 + 255) / 256];
+#pragma unroll
+    for (int i = 0; i < (kWideMaxC / 2 + 255) / 256; ++i) {
+        const int k = tid + 256 * i;
+        dmv[i] = 0.f;
+        if (k < nbits) {
+            const float xd = s_a[2 * k] * invT - s_a[2 * k + 1] * invT;
+            const float p = FA == kActTanh ? tanhf(xd) : act_fwd<FA>(xd);
+            pred[(size_t)b * nbits + k] = p;
+            if (MODE != 0) {
+                const float tg = target[(size_t)b * nbits + k];
+                float lt = 0.f, dp = 0.f;
+                loss_term(loss_kind, p, tg, 1.0f / (float)nbits, lt, dp);
+                lterm += lt;
+                dmv[i] = dp * (FA == kActTanh ? 1.f - p * p : act_grad<FA>(xd, p));
+            }
+        }
+    }
+    if (MODE == 0) return;
+    float Ls = block_sum(lterm, red);
+    if (tid == 0) {
+        if (loss_add) Ls += loss_add[b];                          // per-clip term computed elsewhere (L1 on the coefficients)
+        loss_out[b] = Ls;
+        if (best_loss) {                                          // null: gradient-only call, no bookkeeping
+            const float bl = best_loss[b];
+            const int imp = Ls < bl;
+            improved[b] = imp;
+            if (imp) best_loss[b] = Ls;
+        }
+        if (step && b == 0) *step += 1;
+    }
+    if (!dout) return;
+    // s_a is free from here on: it takes dL/dA = dm / Tp per channel (zero for padding channels)
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < (kWideMaxC / 2 + 255) / 256; ++i) {
+        const int k = tid + 256 * i;
+        if (k < nbits) { s_a[2 * k] = dmv[i] * invT; s_a[2 * k + 1] = -dmv[i] * invT; }
+    }
+    for (int c = C + tid; c < Cp; c += 256) s_a[c] = 0.f;
+    __syncthreads();
+    float ga[kWideNJ], m1[kWideNJ], m2[kWideNJ], rs[kWideNJ];
+#pragma unroll
+    for (int j = 0; j < kWideNJ; ++j) {
+        const int c = cl + CW * j;
+        const bool ok = c < Cp;
+        ga[j] = ok ? s_a[c] : 0.f;
+        m1[j] = MODE == 2 && ok ? ga[j] * (s_l[c] * invT) : 0.f;
+        m2[j] = MODE == 2 && ok ? ga[j] * (s_lu[c] * invT) : 0.f;
+        rs[j] = MODE == 2 && ok ? rstd[(size_t)b * Cp + c] : 0.f;
+    }
+    const int Tpad = (Tp + 31) & ~31;
+    float mx = 0.f;
+    for (int t = g; t < Tpad; t += NG) {
+        const float* row = A + (size_t)(r0 + t) * Cp;
+        float* drow = dout + (size_t)(r0 + t) * Cp;
+#pragma unroll
+        for (int j = 0; j < kWideNJ; ++j) {
+            const int c = cl + CW * j;
+            if (c < Cp) {
+                float v = 0.f;
+                if (t < Tp) {
+                    if (MODE == 2) {
+                        const float a = row[c];
+                        const float u = a > 0.f ? a : a * 5.0f;
+                        const float du = ga[j] * (a > 0.f ? 1.f : 0.2f);
+                        v = rs[j] * (du - m1[j] - u * m2[j]);
+                        mx = fmaxf(mx, fabsf(v));
+                    } else {
+                        v = ga[j];
+                    }
+                }
+                drow[c] = v;
+            }
+        }
+    }
+    if (MODE == 2 && gmax) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+        __syncthreads();
+        if ((tid & 63) == 0) red[tid >> 6] = mx;
+        __syncthreads();
+        if (tid < Cp / 16) gmax[(size_t)b * 64 + tid] = tid == 0 ? fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])) : 0.f;
+    }
+}
+
+void launch_readout_wide(const float* A, int Cp, const int* frame_off, const int* pool_off, const float* rstd, const float* target,
+                         float* pred, float* loss, float* best_loss, int* improved, float* dout, float* gmax, int* step,
+                         int loss_kind, int nbits, int B, hipStream_t st, const float* loss_add, int final_act, bool card_bwd) {
+    const int mode = !target ? 0 : (card_bwd ? 2 : 1);
+#define AW_WIDE(FA, M)                                                                                                       \
+    hipLaunchKernelGGL((readout_wide_kernel<FA, M>), dim3(B), dim3(256), 0, st, A, Cp, frame_off, pool_off, rstd, target, pred, \
+                       loss, best_loss, improved, dout, gmax, step, loss_kind, nbits, loss_add)
+#define AW_WIDE_FA(FA) \
+    do { if (mode == 0) AW_WIDE(FA, 0); else if (mode == 1) AW_WIDE(FA, 1); else AW_WIDE(FA, 2); } while (0)
+    switch (final_act) {
+        case kActRelu: AW_WIDE_FA(kActRelu); break;
+        case kActLRelu: AW_WIDE_FA(kActLRelu); break;
+        case kActGelu: AW_WIDE_FA(kActGelu); break;
+        case kActSwish: AW_WIDE_FA(kActSwish); break;
+        case kActSigmoid: AW_WIDE_FA(kActSigmoid); break;
+        default: AW_WIDE_FA(kActTanh); break;
+    }
+#undef AW_WIDE_FA
+#undef AW_WIDE
 }
 // ---------------------------------------------------------------------------------
 // The same mel block for clips of at most 192 frames in ONE launch per direction: one 512-thread workgroup per clip
@@ -1481,10 +1657,11 @@ void launch_in_lrelu_bwd(float* dA, const float* A, const int* frame_off, const 
 }
 void launch_head(const float* a3, const int* frame_off, const int* pool_off, const float* target, float* pred, float* loss,
                  float* best_loss, int* improved, float* dA3, int* step, int loss_kind, int nbits, int B,
-                 hipStream_t st, const float* loss_add, int final_act) {
+                 hipStream_t st, const float* loss_add, int final_act, int C) {
+    if (C < 2 * nbits) C = 2 * nbits;
 #define AW_HEAD(FA)                                                                                                         \
     hipLaunchKernelGGL(head_kernel<FA>, dim3(B), dim3(256), 0, st, a3, frame_off, pool_off, target, pred, loss, best_loss, improved, \
-                       dA3, step, loss_kind, nbits, loss_add)
+                       dA3, step, loss_kind, nbits, loss_add, C)
     switch (final_act) {
         case kActRelu: AW_HEAD(kActRelu); break;
         case kActLRelu: AW_HEAD(kActLRelu); break;

@@ -199,13 +199,23 @@ void launch_norm_act_bwd(int norm, int act, float* dA, const float* A, const flo
 // BRH + loss + dL/dA3; also best-loss tracking.  final_act: kActRelu .. kActSigmoid applied to even - odd (the card: tanh)
 void launch_head(const float* a3, const int* frame_off, const int* pool_off, const float* target, float* pred, float* loss,
                  float* best_loss, int* improved, float* dA3, int* step, int loss_kind, int nbits, int B,
-                 hipStream_t st, const float* loss_add = nullptr, int final_act = kActTanh);
+                 hipStream_t st, const float* loss_add = nullptr, int final_act = kActTanh, int C = 0);
+// (C: channel pitch of a3 / dA3; 0 = 2*nbits.  Channels 2*nbits .. C-1 are padding: never read out, dA3 zero)
 void launch_gemm_nt_splitk(const float* A, int lda, const float* Bt, int ldb, float* Cpart, int ldc, int M, int N, int K,
                            int ksplit, hipStream_t st);
 void launch_tail(const float* zpart, int nsplit, size_t slab, const float* bias, const int* frame_off, const int* pool_off,
                  const float* target, float* pred, float* loss, float* best_loss, int* improved, float* dZ, int* step,
-                 int loss_kind, int nbits, int B, int max_pooled, hipStream_t st, const float* loss_add = nullptr, int ldz = 0);
-// (ldz: row pitch of dZ; 0 = 2*nbits, 64 = zero-padded to the K of the bf16x3 data-gradient GEMM)
+                 int loss_kind, int nbits, int B, int max_pooled, hipStream_t st, const float* loss_add = nullptr, int ldz = 0,
+                 int C = 0);
+// (ldz: row pitch of dZ; 0 = C, 64 = zero-padded to the K of the bf16x3 data-gradient GEMM.  C: channel pitch of zpart;
+//  0 = 2*nbits.  Channels 2*nbits .. C-1 are padding: never read out, dZ zero)
+
+// wide read-out (64 < Cp <= 1024 channels, multiple of 128; 2*nbits of them read out): pred, and with a target the loss,
+// best-loss bookkeeping and step counter as launch_head, and dout = dL/dA (staged route) or, card_bwd, dL/dZ of the card
+// block with its InstanceNorm + LeakyReLU backward folded in (rstd of the block) plus gmax [B][64] partial maxima (or null)
+void launch_readout_wide(const float* A, int Cp, const int* frame_off, const int* pool_off, const float* rstd, const float* target,
+                         float* pred, float* loss, float* best_loss, int* improved, float* dout, float* gmax, int* step,
+                         int loss_kind, int nbits, int B, hipStream_t st, const float* loss_add, int final_act, bool card_bwd);
 
 // ---- seam_kernels.hip: element-wise pieces of the differentiable plug-in seam -----------------------------
 void launch_polar_decompose(const void* spec, float* mag, float* phase, size_t n, hipStream_t st);

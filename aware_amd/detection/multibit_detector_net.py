@@ -49,6 +49,10 @@ def final_activation_name(name: str) -> str:
     return n
 
 
+# the longest payload the read-out kernels serve (aware_detector_create: a last block of at most 1024 channels)
+MAX_OUTPUT_LENGTH = 512
+
+
 class AWAREDetectorNet(BaseDetectorNet):
     def __init__(self, sample_rate: int = 16000, n_fft: int = 1024, n_mels: int = 128,
                  initial_pool_size: int = 2, initial_pool_stride: int = 2, num_blocks: int = 3,
@@ -68,6 +72,9 @@ class AWAREDetectorNet(BaseDetectorNet):
             unsupported.append("initial pool other than (2, 2)")
         if unsupported:
             raise NotImplementedError("the HIP detector implements 1x1 convolutions after a (2, 2) pool only: " + "; ".join(unsupported))
+        if output_length > MAX_OUTPUT_LENGTH:
+            raise NotImplementedError(f"output_length = {output_length}: the HIP detector reads out payloads of at most "
+                                      f"{MAX_OUTPUT_LENGTH} bits (a last block of at most {2 * MAX_OUTPUT_LENGTH} channels)")
         self.sample_rate, self.n_fft, self.n_mels = sample_rate, n_fft, n_mels
         self.num_blocks, self.initial_pool_size, self.output_length = num_blocks, initial_pool_size, output_length
         self.channels = [n_mels] + n_filters + [2 * output_length]

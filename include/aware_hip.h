@@ -65,7 +65,8 @@ typedef struct aware_embed aware_embed;
  * kernels, optimiser / scheduler registries, device-side detector training, aware_stft_bwd for any clip length; 310: general
  * STFT geometry -- aware_plan_create_ex, aware_plan_spectrum_stride, aware_plan_is_general, aware_batch_create_for_plan,
  * aware_nola_check; 320: detector architecture variants -- aware_detector_create_ex, aware_detector_is_card; 330: any
- * embedding band inside bins 0..512 -- the wide layout, aware_plan_band_stride) */
+ * embedding band inside bins 0..512 -- the wide layout, aware_plan_band_stride; 340: payloads of 1..512 bits --
+ * aware_detector_create accepts any even channels[n_layers] from 2 to 1024) */
 int aware_version(void);
 /* text of the last failed HIP runtime call on the calling thread (thread-local) */
 const char* aware_last_hip_error(void);
@@ -184,7 +185,11 @@ int aware_nadam_clamp_step(float* param, const float* grad, float* exp_avg, floa
  * AWAREDetectorNet (detection/multibit_detector_net.py:17-80).  All arrays are host fp32:
  * mel_basis [n_mels][n_fft/2+1] (detection/modules/mel.py:105-149), conv weights
  * [channels[i+1]][channels[i]] and biases [channels[i+1]] for i < n_layers
- * (channels = {128, 512, 1024, 1024, 40}).  The library uploads and pre-transposes them. */
+ * (channels = {128, 512, 1024, 1024, 40}).  The library uploads and pre-transposes them.
+ * channels[0] = n_mels = 128; channels[1 .. n_layers-1] multiples of 4; channels[n_layers] = 2 * payload bits, any even
+ * value from 2 to 1024 (payloads of 1..512 bits), else AWARE_E_UNSUPPORTED.  The last block is stored with its channels
+ * padded (to a multiple of 4 up to 64, to a multiple of 128 above): zero weights and biases, never read out.  Every array
+ * the caller passes or receives keeps the caller's shapes. */
 int aware_detector_create(aware_detector** out, const aware_plan* plan, const float* mel_basis, int n_mels,
                           int n_layers, const int* channels, const float* const* weights,
                           const float* const* biases);
