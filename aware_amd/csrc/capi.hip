@@ -93,32 +93,30 @@ struct aware_detector {
     int n_mels = 0, n_layers = 0, nbits = 0;
     int band_lo = 0, nband = 0;
     int stride = kFS;        // floats per band row of the plan the detector was created for
-    // channel counts as stored: ch[n_layers] is the last block's padded count Cp >= 2 * nbits (last_block_channels); its
-    // padding channels have zero weights and bias, are never read out and get a zero gradient
-    int ch[8] = {0};
+    // channel counts as the caller gave them (uch) and as stored (ch, stored_channels): ch[0] = Mp >= n_mels is the row
+    // stride of the mel stage; padding channels have zero weights, bias and melT rows and get a zero gradient
+    std::vector<int> uch, ch;
     int maxc = 0;
     float* mem = nullptr;
-    float* melT = nullptr;   // [n_mels][stride]  (Bt of the forward mel GEMM)
-    float* melB = nullptr;   // [stride][n_mels]  (Bt of its data-gradient)
-    float* w[8] = {nullptr};   // [Cout][Cin]
-    float* wT[8] = {nullptr};  // [Cin][Cout]
+    float* melT = nullptr;   // [Mp][stride]  (Bt of the forward mel GEMM; rows n_mels .. Mp-1 zero)
+    float* melB = nullptr;   // [stride][Mp]  (Bt of its data-gradient)
+    std::vector<float*> w;    // [Cout][Cin]
+    std::vector<float*> wT;   // [Cin][Cout]
     // the same two operands split into three bf16 planes in MFMA fragment order (gemm_x3.hip); null when the
     // shape is not served by that kernel
-    void* wpk[8] = {nullptr};
-    void* wTpk[8] = {nullptr};
+    std::vector<void*> wpk, wTpk;
     void* melTpk = nullptr;
     void* melBpk = nullptr;
     void* lastpk = nullptr;    // last conv, rows zero-padded to a multiple of 16 (read-out kernel)
     void* lastTpk = nullptr;   // its transpose [Cin][64], k zero-padded to 64
     void* pkmem = nullptr;
     // the conv blocks' two operands as f16 two-term images (gemm_h2.hip: planes + per-channel inverse scales)
-    void* wh2[8] = {nullptr};
-    void* wTh2[8] = {nullptr};
+    std::vector<void*> wh2, wTh2;
     void* h2mem = nullptr;
-    float* bias[8] = {nullptr};
+    std::vector<float*> bias;
     // the mel filter bank as two taps per band column (a triangular bank has at most two adjacent non-zero weights per bin):
-    // melw [kFS] float2, melm [kFS] first tap's mel index (<= 126); null when the basis handed over is not of that form or the
-    // band has the wide layout (which takes the dense mel GEMMs)
+    // melw [kFS] float2, melm [kFS] first tap's mel index (<= 126); null when the basis handed over is not of that form, the
+    // bank is not 128 bands or the band has the wide layout (which takes the dense mel GEMMs)
     void* mel2mem = nullptr;
     float2* melw = nullptr;
     unsigned char* melm = nullptr;
@@ -131,8 +129,7 @@ struct aware_detector {
     // staged route: plain GEMM + bias, launch_norm_act_fwd / _bwd, launch_head
     bool card_arch = true;
     int act = kActLRelu, norm = kNormInstance, final_act = kActTanh;
-    float* nscale[8] = {nullptr};   // affine norm (BatchNorm1d in eval mode, folded): u = z * nscale[l][c] + nshift[l][c]
-    float* nshift[8] = {nullptr};
+    std::vector<float*> nscale, nshift;   // affine norm (BatchNorm1d in eval mode, folded): u = z * nscale[l][c] + nshift[l][c]
     float* normmem = nullptr;
 };
 static_assert(AWARE_ACT_RELU == kActRelu && AWARE_ACT_LEAKY_RELU == kActLRelu && AWARE_ACT_GELU == kActGelu &&
@@ -143,7 +140,7 @@ static_assert(AWARE_NORM_INSTANCE == kNormInstance && AWARE_NORM_BATCH == kNormA
 // whether the staged route keeps the pre-activation of every block for the backward (DetBufs::stash)
 static bool det_needs_stash(const aware_detector* d) { return !d->card_arch && norm_act_needs_stash(d->norm, d->act); }
 
-extern "C" int aware_version(void) { return 340; }
+extern "C" int aware_version(void) { return 350; }
 extern "C" const char* aware_last_hip_error(void) { return g_last_err.c_str(); }
 
 // ---------------------------------------------------------------------------------------------
@@ -719,37 +716,58 @@ extern "C" int aware_istft_bwd(const aware_plan* plan, const aware_batch* b, con
 
 // ---------------------------------------------------------------------------------------------
 extern "C" void aware_detector_destroy(aware_detector* d);
-// the widest last block (payloads of up to 512 bits)
+// the widest last block (payloads of up to 512 bits), the largest mel bank and hidden width, the deepest network
 constexpr int kMaxOutChannels = 1024;
-// channels the last block is stored with for C = 2 * payload bits: C itself where the read-out kernels for C <= 64 take it
-// (a multiple of 4), C rounded up to a multiple of 4 below that, and above 64 C rounded up to a multiple of 128 so that the
-// conv-block kernels take the block and the wide read-out (launch_readout_wide) reads it out
-static int last_block_channels(int C) {
+constexpr int kMaxMels = 512;
+constexpr int kMaxHidden = 4096;
+constexpr int kMaxLayers = 33;
+// The storage rule: the channel count layer boundary i (0 = the mel bank, n_layers = the last block) is stored with, for the
+// caller's count C.  The only place that knows the padding.
+//  - i = n_layers (C = 2 * payload bits): C itself where the read-out kernels for C <= 64 take it (a multiple of 4), C
+//    rounded up to a multiple of 4 below that, and above 64 C rounded up to a multiple of 128 so that the conv-block kernels
+//    take the block and the wide read-out (launch_readout_wide) reads it out;
+//  - i < n_layers (mel bank and hidden widths): a multiple of 4 as is, else rounded up to a multiple of 4 up to 64 and to a
+//    multiple of 128 above, so that the fused conv-block kernels take the block.
+// Stored widths are multiples of 4 (the f32 GEMMs load K in float4).  Padding channels have zero weights, zero bias, zero
+// weight columns in the next block and zero melT rows (and scale 0, shift 0 for BatchNorm): through every norm and
+// activation they stay exactly 0 and their gradient is 0.
+static int stored_channels(int i, int n_layers, int C) {
+    if (i < n_layers && C % 4 == 0) return C;
     if (C <= 64) return (C + 3) & ~3;
     return (C + 127) & ~127;
+}
+// whether the training extension serves the detector: the model card's architecture on 128 mel bands, hidden widths stored
+// as given and at most 7 layers (it adds no padding logic of its own)
+static bool det_trainable(const aware_detector* d) {
+    if (!d->card_arch || d->n_mels != 128 || d->n_layers > 7) return false;
+    for (int i = 0; i < d->n_layers; ++i)
+        if (d->ch[i] != d->uch[i]) return false;
+    return true;
 }
 // host staging of the detector's parameters (plain + transposed f32 copies, bf16x3 fragment images) and upload; `alloc`
 // = false re-uses the device buffers of a detector created with the same shapes (aware_detector_update)
 static int detector_upload(aware_detector* d, const float* mel_basis, const float* const* weights,
                            const float* const* biases, bool alloc) {
     const int n_mels = d->n_mels, n_layers = d->n_layers;
-    const int* channels = d->ch;
+    const int* channels = d->ch.data();
+    const int* uch = d->uch.data();
+    const int Mp = channels[0];
     const int S = d->stride;
-    size_t total = (size_t)n_mels * S * 2;
+    size_t total = (size_t)Mp * S * 2;
     for (int i = 0; i < n_layers; ++i) total += (size_t)channels[i] * channels[i + 1] * 2 + channels[i + 1];
     std::vector<float> h(total, 0.f);
     size_t o = 0;
     const int nbins = kNfft / 2 + 1;
     const int lo = d->band_lo, nb = d->nband;
-    size_t o_melT = o; o += (size_t)n_mels * S;
-    size_t o_melB = o; o += (size_t)S * n_mels;
+    size_t o_melT = o; o += (size_t)Mp * S;
+    size_t o_melB = o; o += (size_t)S * Mp;
     // only the in-band columns of the mel basis ever multiply non-zero magnitudes
     // (multibit_embedder.py:104, multibit_detector.py:34-37 zero the rest)
     for (int j = 0; j < n_mels; ++j)
         for (int f = 0; f < nb; ++f) {
             float v = mel_basis[(size_t)j * nbins + lo + f];
             h[o_melT + (size_t)j * S + f] = v;
-            h[o_melB + (size_t)f * n_mels + j] = v;
+            h[o_melB + (size_t)f * Mp + j] = v;
         }
     {
         // two-tap form of the band's columns, if the basis has it (any triangular filter bank does)
@@ -759,12 +777,12 @@ static int detector_upload(aware_detector* d, const float* mel_basis, const floa
         for (int f = 0; f < nb && sparse; ++f) {
             int first = -1, count = 0, lastnz = -1;
             for (int j = 0; j < n_mels; ++j)
-                if (h[o_melB + (size_t)f * n_mels + j] != 0.f) { if (first < 0) first = j; lastnz = j; ++count; }
+                if (h[o_melB + (size_t)f * Mp + j] != 0.f) { if (first < 0) first = j; lastnz = j; ++count; }
             if (count == 0) continue;
             if (count > 2 || lastnz - first > 1) { sparse = false; break; }
             const int m1 = first < n_mels - 1 ? first : n_mels - 2;
             tm[f] = (unsigned char)m1;
-            tw[f] = make_float2(h[o_melB + (size_t)f * n_mels + m1], h[o_melB + (size_t)f * n_mels + m1 + 1]);
+            tw[f] = make_float2(h[o_melB + (size_t)f * Mp + m1], h[o_melB + (size_t)f * Mp + m1 + 1]);
         }
         // forward: filter m as kMelTapsA (m < 64) / kMelTapsB adjacent columns starting at fs[m]
         std::vector<float> fw((size_t)128 * kMelTapsB, 0.f);
@@ -801,16 +819,16 @@ static int detector_upload(aware_detector* d, const float* mel_basis, const floa
             d->melf_s = nullptr;
         }
     }
-    size_t o_w[8], o_wT[8], o_b[8];
+    std::vector<size_t> o_w(n_layers), o_wT(n_layers), o_b(n_layers);
     for (int l = 0; l < n_layers; ++l) {
         const int ci = channels[l], co = channels[l + 1];
-        const int rows = l == n_layers - 1 ? 2 * d->nbits : co;   // the caller's rows; padding rows stay zero
+        const int uci = uch[l], rows = uch[l + 1];   // the caller's shape [rows][uci]; padding rows and columns stay zero
         o_w[l] = o; o += (size_t)ci * co;
         o_wT[l] = o; o += (size_t)ci * co;
         o_b[l] = o; o += co;
         for (int r = 0; r < rows; ++r)
-            for (int c = 0; c < ci; ++c) {
-                float v = weights[l][(size_t)r * ci + c];
+            for (int c = 0; c < uci; ++c) {
+                float v = weights[l][(size_t)r * uci + c];
                 h[o_w[l] + (size_t)r * ci + c] = v;
                 h[o_wT[l] + (size_t)c * co + r] = v;
             }
@@ -822,15 +840,18 @@ static int detector_upload(aware_detector* d, const float* mel_basis, const floa
     d->melB = d->mem + o_melB;
     for (int l = 0; l < n_layers; ++l) { d->w[l] = d->mem + o_w[l]; d->wT[l] = d->mem + o_wT[l]; d->bias[l] = d->mem + o_b[l]; }
     {
-        size_t pk_total = 0, o_pk[8], o_pkT[8];
+        size_t pk_total = 0;
+        std::vector<size_t> o_pk(n_layers), o_pkT(n_layers);
         for (int l = 0; l < n_layers; ++l) {
             const int ci = channels[l], co = channels[l + 1];
             o_pk[l] = o_pkT[l] = (size_t)-1;
             if (co % 128 == 0 && ci % 64 == 0) { o_pk[l] = pk_total; pk_total += x3_packed_bytes(co, ci); }
             if (ci % 128 == 0 && co % 64 == 0) { o_pkT[l] = pk_total; pk_total += x3_packed_bytes(ci, co); }
         }
-        const size_t o_mT = pk_total; pk_total += x3_packed_bytes(n_mels, S);
-        const size_t o_mB = pk_total; pk_total += x3_packed_bytes(S, n_mels);
+        // the mel operands where the bf16x3 kernel can take them (N % 128, K % 64): always for 128 bands
+        const bool mT = Mp % 128 == 0, mB = Mp % 64 == 0;
+        const size_t o_mT = pk_total; if (mT) pk_total += x3_packed_bytes(Mp, S);
+        const size_t o_mB = pk_total; if (mB) pk_total += x3_packed_bytes(S, Mp);
         // read-out kernel operands (last conv block, C <= 64 channels)
         const int cil = channels[n_layers - 1], col = channels[n_layers], colp = 16 * ((col + 15) / 16);
         const bool ro = n_layers >= 2 && readout_x3_supported(1, cil, col);
@@ -851,8 +872,8 @@ static int detector_upload(aware_detector* d, const float* mel_basis, const floa
             x3_pack(wp.data(), colp, cil, hp.data() + o_lp / 2);
             x3_pack(wt.data(), cil, 64, hp.data() + o_lT / 2);
         }
-        x3_pack(h.data() + o_melT, n_mels, S, hp.data() + o_mT / 2);
-        x3_pack(h.data() + o_melB, S, n_mels, hp.data() + o_mB / 2);
+        if (mT) x3_pack(h.data() + o_melT, Mp, S, hp.data() + o_mT / 2);
+        if (mB) x3_pack(h.data() + o_melB, S, Mp, hp.data() + o_mB / 2);
         for (int l = 0; l < n_layers; ++l) {
             const int ci = channels[l], co = channels[l + 1];
             if (o_pk[l] != (size_t)-1) x3_pack(h.data() + o_w[l], co, ci, hp.data() + o_pk[l] / 2);
@@ -861,8 +882,8 @@ static int detector_upload(aware_detector* d, const float* mel_basis, const floa
         if (alloc) HIPCHK(hipMalloc(&d->pkmem, pk_total + 16));
         HIPCHK(hipMemcpy(d->pkmem, hp.data(), pk_total, hipMemcpyHostToDevice));
         if (ro) { d->lastpk = (char*)d->pkmem + o_lp; d->lastTpk = (char*)d->pkmem + o_lT; }
-        d->melTpk = (char*)d->pkmem + o_mT;
-        d->melBpk = (char*)d->pkmem + o_mB;
+        d->melTpk = mT ? (char*)d->pkmem + o_mT : nullptr;
+        d->melBpk = mB ? (char*)d->pkmem + o_mB : nullptr;
         for (int l = 0; l < n_layers; ++l) {
             if (o_pk[l] != (size_t)-1) d->wpk[l] = (char*)d->pkmem + o_pk[l];
             if (o_pkT[l] != (size_t)-1) d->wTpk[l] = (char*)d->pkmem + o_pkT[l];
@@ -870,7 +891,8 @@ static int detector_upload(aware_detector* d, const float* mel_basis, const floa
     }
     {
         // f16 two-term images, packed on the device from the f32 copies just uploaded
-        size_t total2 = 0, o_h[8], o_hT[8];
+        size_t total2 = 0;
+        std::vector<size_t> o_h(n_layers), o_hT(n_layers);
         for (int l = 0; l < n_layers; ++l) {
             const int ci = channels[l], co = channels[l + 1];
             o_h[l] = o_hT[l] = (size_t)-1;
@@ -896,26 +918,32 @@ static int detector_create(aware_detector** out, const aware_plan* plan, const f
                            const aware_detector_arch* arch) {
     if (!out || !plan || !mel_basis || !channels || !weights) return AWARE_E_BADARG;
     if (plan->general) return AWARE_E_UNSUPPORTED;       // the detector runs on the card geometry only
-    if (n_mels != 128 || n_layers < 1 || n_layers > 7 || channels[0] != n_mels) return AWARE_E_UNSUPPORTED;
+    if (n_mels < 1 || n_mels > kMaxMels || n_layers < 1 || n_layers > kMaxLayers || channels[0] != n_mels) return AWARE_E_UNSUPPORTED;
     const int cl = channels[n_layers];
     if (cl % 2 || cl < 2 || cl > kMaxOutChannels) return AWARE_E_UNSUPPORTED;
-    for (int i = 0; i < n_layers; ++i)
-        if (channels[i] % 4) return AWARE_E_UNSUPPORTED;
+    for (int i = 1; i < n_layers; ++i)
+        if (channels[i] < 1 || channels[i] > kMaxHidden) return AWARE_E_UNSUPPORTED;
     aware_detector* d = new aware_detector();
     d->n_mels = n_mels; d->n_layers = n_layers; d->nbits = cl / 2;
     d->band_lo = plan->dev.band_lo; d->nband = plan->dev.nband; d->stride = plan->dev.stride;
+    d->uch.assign(channels, channels + n_layers + 1);
+    d->ch.resize(n_layers + 1);
     for (int i = 0; i <= n_layers; ++i) {
-        d->ch[i] = i == n_layers ? last_block_channels(cl) : channels[i];
+        d->ch[i] = stored_channels(i, n_layers, channels[i]);
         if (d->ch[i] > d->maxc) d->maxc = d->ch[i];
     }
+    d->w.assign(n_layers, nullptr); d->wT.assign(n_layers, nullptr); d->bias.assign(n_layers, nullptr);
+    d->wpk.assign(n_layers, nullptr); d->wTpk.assign(n_layers, nullptr);
+    d->wh2.assign(n_layers, nullptr); d->wTh2.assign(n_layers, nullptr);
+    d->nscale.assign(n_layers, nullptr); d->nshift.assign(n_layers, nullptr);
     if (arch) {
         d->act = arch->activation; d->norm = arch->norm; d->final_act = arch->final_activation;
         d->card_arch = d->act == kActLRelu && d->norm == kNormInstance && d->final_act == kActTanh;
     }
     int rc = detector_upload(d, mel_basis, weights, biases, true);
     if (rc == AWARE_OK && d->norm == kNormAffine) {
-        // the padding channels of the last block get scale 0 and shift 0: their pre-activation is 0 and their output
-        // act(0) = 0 for every block activation.  They are never read out and their gradient is zero.
+        // padding channels (stored_channels) get scale 0 and shift 0: their pre-activation is 0 and their output act(0) = 0
+        // for every block activation.  They are never read out and their gradient is zero.
         size_t n = 0;
         for (int l = 0; l < n_layers; ++l) n += 2 * (size_t)d->ch[l + 1];
         std::vector<float> h(n, 0.f);
@@ -955,7 +983,7 @@ extern "C" int aware_detector_create_ex(aware_detector** out, const aware_plan* 
     if (arch->norm < AWARE_NORM_INSTANCE || arch->norm > AWARE_NORM_NONE) return AWARE_E_BADARG;
     if (arch->final_activation < AWARE_FINAL_RELU || arch->final_activation > AWARE_FINAL_SIGMOID) return AWARE_E_BADARG;
     if (arch->norm == AWARE_NORM_BATCH) {
-        if (!arch->norm_scale || !arch->norm_shift || n_layers < 1 || n_layers > 7) return AWARE_E_BADARG;
+        if (!arch->norm_scale || !arch->norm_shift || n_layers < 1 || n_layers > kMaxLayers) return AWARE_E_BADARG;
         for (int l = 0; l < n_layers; ++l)
             if (!arch->norm_scale[l] || !arch->norm_shift[l]) return AWARE_E_BADARG;
     }
@@ -968,7 +996,7 @@ extern "C" int aware_detector_is_card(const aware_detector* d) { return d ? (d->
 extern "C" int aware_detector_update(aware_detector* d, const float* mel_basis, const float* const* weights,
                                      const float* const* biases) {
     if (!d || !mel_basis || !weights) return AWARE_E_BADARG;
-    if (!d->card_arch) return AWARE_E_UNSUPPORTED;       // the training extension serves the model card's network only
+    if (!det_trainable(d)) return AWARE_E_UNSUPPORTED;   // the training extension serves the model card's network only
     return detector_upload(d, mel_basis, weights, biases, false);
 }
 // EXTENSION (detector training): the same refresh from DEVICE arrays, asynchronous on `stream` -- no host round trip of the
@@ -977,7 +1005,7 @@ extern "C" int aware_detector_update(aware_detector* d, const float* mel_basis, 
 extern "C" int aware_detector_update_device(aware_detector* d, const float* const* dev_weights, const float* const* dev_biases,
                                             void* stream) {
     if (!d || !dev_weights) return AWARE_E_BADARG;
-    if (!d->card_arch) return AWARE_E_UNSUPPORTED;
+    if (!det_trainable(d)) return AWARE_E_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
     const int nl = d->n_layers;
     for (int l = 0; l < nl; ++l) {
@@ -1030,12 +1058,12 @@ static void gemm_plain(int pipe, const float* A, int lda, const float* Bt, int l
 
 // detector activations carved from a workspace
 struct DetBufs {
-    float* xm;        // [NF][128]
-    float* x0;        // [NP][128]
-    float* act[8];    // [NP][C_l+1]
-    float* rstd[8];   // [B][C_l+1]
-    float* stash[8];  // [NP][C_l+1] pre-activations of a staged-route block (det_needs_stash), else null
-    float *mstats, *gstat, *mpart;   // mel statistics [B][128][4], [B][4], chunk partials
+    float* xm;        // [NF][Mp]
+    float* x0;        // [NP][Mp]
+    std::vector<float*> act;    // [NP][C_l+1]
+    std::vector<float*> rstd;   // [B][C_l+1]
+    std::vector<float*> stash;  // [NP][C_l+1] pre-activations of a staged-route block (det_needs_stash), else null
+    float *mstats, *gstat, *mpart;   // mel statistics [B][Mp][4], [B][4], chunk partials [B][mstride][2 Mp]
     int mstride;
     float* pred;      // [B][nbits]
     float* zpart;     // split-K partial slabs of the last conv [kTailSplit][NP][C_last]
@@ -1043,7 +1071,7 @@ struct DetBufs {
     int zslabs;       // partial slabs the forward epilogue left in zpart (fused read-out)
     // per-clip partial maxima [B][64] for the f16 two-term GEMM's scales: of x0 (index 0), of act[l] (index l + 1), and of
     // the two gradient ping-pong buffers (gmax)
-    float* amax[9];
+    std::vector<float*> amax;
     float* gmax[2];
 };
 constexpr int kTailSplit = 4;
@@ -1053,17 +1081,20 @@ static int zpart_slabs(const aware_detector* d) {
     return s > kTailSplit ? s : kTailSplit;
 }
 static void carve_det(Carver& c, const aware_batch* b, const aware_detector* d, DetBufs& o) {
-    o.xm = c.take<float>((size_t)b->NF * 128);
-    o.x0 = c.take<float>((size_t)b->NP * 128);
+    const int Mp = d->ch[0];
+    o.act.assign(d->n_layers, nullptr); o.rstd.assign(d->n_layers, nullptr); o.stash.assign(d->n_layers, nullptr);
+    o.amax.assign(d->n_layers + 1, nullptr);
+    o.xm = c.take<float>((size_t)b->NF * Mp);
+    o.x0 = c.take<float>((size_t)b->NP * Mp);
     for (int l = 0; l < d->n_layers; ++l) {
         o.act[l] = c.take<float>((size_t)b->NP * d->ch[l + 1]);
         o.rstd[l] = c.take<float>((size_t)b->B * d->ch[l + 1]);
         o.stash[l] = det_needs_stash(d) ? c.take<float>((size_t)b->NP * d->ch[l + 1]) : nullptr;
     }
-    o.mstats = c.take<float>((size_t)b->B * 128 * 4);
+    o.mstats = c.take<float>((size_t)b->B * Mp * 4);
     o.gstat = c.take<float>((size_t)b->B * 4);
     o.mstride = (b->max_frames + 31) / 32;
-    o.mpart = c.take<float>((size_t)b->B * o.mstride * 256);
+    o.mpart = c.take<float>((size_t)b->B * o.mstride * 2 * Mp);
     o.pred = c.take<float>((size_t)b->B * d->nbits);
     o.zpart = c.take<float>((size_t)zpart_slabs(d) * b->NP * d->ch[d->n_layers]);
     o.tail = 0;
@@ -1072,8 +1103,9 @@ static void carve_det(Carver& c, const aware_batch* b, const aware_detector* d, 
     o.gmax[1] = c.take<float>((size_t)b->B * 64);
 }
 static size_t det_bytes(const aware_batch* b, const aware_detector* d) {
-    size_t f = (size_t)b->NF * 128 + (size_t)b->NP * 128 + (size_t)b->B * (128 * 4 + 4 + d->nbits) +
-               (size_t)b->B * ((b->max_frames + 31) / 32) * 256;
+    const size_t Mp = d->ch[0];
+    size_t f = (size_t)b->NF * Mp + (size_t)b->NP * Mp + (size_t)b->B * (Mp * 4 + 4 + d->nbits) +
+               (size_t)b->B * ((b->max_frames + 31) / 32) * 2 * Mp;
     for (int l = 0; l < d->n_layers; ++l) f += (size_t)(b->NP + b->B) * d->ch[l + 1];
     if (det_needs_stash(d))
         for (int l = 0; l < d->n_layers; ++l) f += (size_t)b->NP * d->ch[l + 1];
@@ -1098,7 +1130,8 @@ constexpr int kH2MinGrid = 128;
 static bool mel_front_applies(const aware_detector* d, const aware_batch* b, int pipe) {
     bool same_T = true;
     for (int i = 1; i < b->B; ++i) same_T = same_T && b->T[i] == b->T[0];
-    return pipe != 1 && d->melTpk && same_T && b->B >= kMelFrontMinClips && mel_front_x3_supported(b->T[0], d->stride, d->stride);
+    return pipe != 1 && d->n_mels == 128 && d->melTpk && same_T && b->B >= kMelFrontMinClips &&
+           mel_front_x3_supported(b->T[0], d->stride, d->stride);
 }
 
 // forward through the network; mag [NF][256] -> act[last], pred
@@ -1128,10 +1161,15 @@ static int det_forward(const aware_detector* d, const aware_batch* b, const floa
         cur_max = true;
         LAUNCHCHK(); PROF(K_MELNORM);
     } else {
-        gemm_plain(pipe, mag, d->stride, d->melT, d->stride, d->melTpk, nullptr, o.xm, 128, b->NF, 128, d->stride, st);
+        const int Mp = d->ch[0];
+        gemm_plain(pipe, mag, d->stride, d->melT, d->stride, d->melTpk, nullptr, o.xm, Mp, b->NF, Mp, d->stride, st);
         LAUNCHCHK(); PROF(K_GEMM);
-        launch_mel_norm_fwd(o.xm, b->d_frame_off, b->d_pool_off, o.x0, o.mstats, o.gstat, o.mpart, o.mstride, b->B,
-                            b->max_frames, st);
+        if (d->n_mels == 128)
+            launch_mel_norm_fwd(o.xm, b->d_frame_off, b->d_pool_off, o.x0, o.mstats, o.gstat, o.mpart, o.mstride, b->B,
+                                b->max_frames, st);
+        else
+            launch_mel_norm_fwd_any(o.xm, b->d_frame_off, b->d_pool_off, o.x0, o.mstats, o.gstat, o.mpart, o.mstride, b->B,
+                                    b->max_frames, d->n_mels, Mp, st);
         LAUNCHCHK(); PROF(K_MELNORM);
     }
     const float* x = o.x0;
@@ -1438,7 +1476,7 @@ static int det_forward_backward(const aware_detector* d, const aware_batch* b, c
             launch_gemm_ragged_x3(dA, co, d->wTpk[l], nullptr, dB, ci, b->B, b->d_frame_off, b->d_pool_off, b->d_order, ci, co, 2,
                                   db.rstd[l - 1], db.act[l - 1], st);
             LAUNCHCHK(); PROF(K_GEMM_X3_BWD);
-        } else if (l == 0 && mel_fused && dz_ready && !G.wgrad && d->wTpk[0] && co % 64 == 0 && ci == 128) {
+        } else if (l == 0 && mel_fused && dz_ready && !G.wgrad && d->wTpk[0] && co % 64 == 0 && d->n_mels == 128) {
             // large uniform batch: block 0's data gradient and the backward of the mel block's normalisations in one launch
             launch_mel_back_x3(dA, co, d->wTpk[0], b->d_frame_off, b->d_pool_off, db.xm, db.mstats, db.gstat, b->B, b->T[0], co, st);
             LAUNCHCHK(); PROF(K_MELNORM);
@@ -1450,13 +1488,18 @@ static int det_forward_backward(const aware_detector* d, const aware_batch* b, c
         }
         float* t = dA; dA = dB; dB = t;
     }
+    const int Mp = d->ch[0];
     if (!mel_bwd_done) {
-        launch_mel_norm_bwd(dA, db.xm, b->d_frame_off, b->d_pool_off, db.mstats, db.gstat, db.mpart, db.mstride, b->B,
-                            b->max_frames, st);
+        if (d->n_mels == 128)
+            launch_mel_norm_bwd(dA, db.xm, b->d_frame_off, b->d_pool_off, db.mstats, db.gstat, db.mpart, db.mstride, b->B,
+                                b->max_frames, st);
+        else
+            launch_mel_norm_bwd_any(dA, db.xm, b->d_frame_off, b->d_pool_off, db.mstats, db.gstat, db.mpart, db.mstride, b->B,
+                                    b->max_frames, d->n_mels, Mp, st);
         LAUNCHCHK(); PROF(K_MELNORM);
     }
     if (!G.mel_grad_only) {
-        gemm_plain(pipe, db.xm, 128, d->melB, 128, d->melBpk, nullptr, G.gmag, d->stride, b->NF, d->stride, 128, st);
+        gemm_plain(pipe, db.xm, Mp, d->melB, Mp, d->melBpk, nullptr, G.gmag, d->stride, b->NF, d->stride, Mp, st);
         LAUNCHCHK(); PROF(K_GEMM);
     }
     return AWARE_OK;
@@ -1527,7 +1570,7 @@ static int detector_train_core(const aware_detector* d, const aware_batch* b, co
                                float* loss_out, float* values, float* grad_mag, float* const* grad_weights,
                                float* const* grad_biases, void* workspace, size_t workspace_bytes, void* stream) {
     if (!d || !b || b->general) return AWARE_E_BADARG;
-    if (!d->card_arch) return AWARE_E_UNSUPPORTED;       // the training extension serves the model card's network only
+    if (!det_trainable(d)) return AWARE_E_UNSUPPORTED;   // the training extension serves the model card's network only
     if (d->stride != kFS) return AWARE_E_UNSUPPORTED;    // ... on a band of the narrow layout
     hipStream_t st = (hipStream_t)stream;
     Carver c(workspace, workspace_bytes);
@@ -1750,8 +1793,9 @@ extern "C" int aware_embed_create(aware_embed** out, const aware_plan* plan, con
             return !(cfg->conv_pipe != 1 && M % 32 == 0 && gemm_clip_x3_supported(1, N, K, lda));
         };
         const int S = det->stride;
-        if (f32_shape(b->NF, 128, S, S)) gemm_autotune(e->mag, S, det->melT, S, e->db.xm, 128, b->NF, 128, S, st);
-        if (f32_shape(b->NF, S, 128, 128)) gemm_autotune(e->db.xm, 128, det->melB, 128, e->gmag, S, b->NF, S, 128, st);
+        const int Mp = det->ch[0];
+        if (f32_shape(b->NF, Mp, S, S)) gemm_autotune(e->mag, S, det->melT, S, e->db.xm, Mp, b->NF, Mp, S, st);
+        if (f32_shape(b->NF, S, Mp, Mp)) gemm_autotune(e->db.xm, Mp, det->melB, Mp, e->gmag, S, b->NF, S, Mp, st);
         for (int l = 0; l < det->n_layers; ++l) {
             const int ci = det->ch[l], co = det->ch[l + 1];
             if (f32_shape(b->NP, co, ci, ci)) gemm_autotune(e->d1, ci, det->w[l], ci, e->d2, co, b->NP, co, ci, st);
@@ -1877,7 +1921,8 @@ static int embed_iteration(aware_embed* e, hipStream_t st, int do_step, float* g
     L.mag = e->mag; L.unit = e->U; L.unit_default = 0.f; L.write_pad = 0;
     // the mel projection as short runs of adjacent bins inside the streaming analysis kernel (no magnitude array), and its
     // backward as two taps per bin inside the synthesis adjoint (below): streaming DSP path and a filter bank of that form
-    const bool mel_taps = dsp == 0 && d->melw && d->melm && stream_supported(e->plan->dev) && e->cfg.mel == 0;
+    // (the tap forms serve 128 bands only: the synthesis adjoint reads dmel with a row stride of 128)
+    const bool mel_taps = dsp == 0 && d->n_mels == 128 && d->melw && d->melm && stream_supported(e->plan->dev) && e->cfg.mel == 0;
     const bool mel_fold = mel_taps && d->melf_w && d->melf_s && d->n_mels == 128;
     if (mel_fold) { L.mel_out = e->db.xm; L.melf_w = d->melf_w; L.melf_s = d->melf_s; }
     run_analysis(L, dsp, st);

@@ -1638,6 +1638,375 @@ void launch_mel_norm_bwd(const float* dx0, float* xm, const int* frame_off, cons
     hipLaunchKernelGGL(mel_bwd_apply_kernel, dim3(nx, B), dim3(256), 0, st, dx0, xm, frame_off, pool_off, stats, gstat, part,
                        pstride);
 }
+// ---------------------------------------------------------------------------------
+// The mel block for any bank of n_mels <= 512 bands, rows of Mp >= n_mels floats (Mp a multiple of 4; stored_channels in
+// capi.hip).  Same maths as the 128-band kernels above: channels are taken in groups of 128 (thread c of a group: channel
+// 128 j + c), each group's statistics are complete before the next starts, and the clip-wide GlobalStandardize sum runs over
+// the n_mels real channels only.  Padding channels n_mels .. Mp-1 get zero statistics, zero x0 columns and zero dL/dxm.
+// Short clips (<= kMelClipFrames): one 512-thread workgroup per clip (4 row groups; the passes over the clip's rows -- mean,
+// M2, output -- re-read it from L2).  Longer clips: the chunked two-launch form, partials
+// [B][pstride][2 Mp] = {mean | D1, M2 | D2} per 32-frame chunk.
+// ---------------------------------------------------------------------------------
+constexpr int kMelGroups = 4;                       // 128-channel groups: Mp <= 512
+
+__global__ __launch_bounds__(512) void mel_any_clip_fwd_kernel(const float* __restrict__ xm, const int* __restrict__ frame_off,
+                                                                const int* __restrict__ pool_off, float* __restrict__ x0,
+                                                                float* __restrict__ stats, float* __restrict__ gstat, int n_mels,
+                                                                int Mp) {
+    __shared__ float red[4][128];
+    __shared__ float red8[8];
+    __shared__ float smu[kMelGroups][128], srs[kMelGroups][128];   // the statistics of the output pass
+    const int b = blockIdx.x;
+    const int f0 = frame_off[b], T = frame_off[b + 1] - f0, Tp = T / 2;
+    const int c = threadIdx.x & 127, g = threadIdx.x >> 7;
+    const int ng = (Mp + 127) / 128;
+    float suu = 0.f;
+#pragma unroll 1
+    for (int j = 0; j < ng; ++j) {                                     // ng is uniform across the workgroup
+        const int ch = 128 * j + c;
+        const bool on = ch < n_mels;
+        // row group g takes frames g, g + 4, ...: two passes over the clip's column (mean, then M2); the clip stays in L2
+        const float* x = xm + (size_t)f0 * Mp + min(ch, n_mels - 1);
+        float sm = 0.f;
+        for (int t = g; t < T; t += 4) sm += x[(size_t)t * Mp];
+        const float mu = mel_chan_sum(sm, red, c, g) / (float)T;
+        float q = 0.f;
+        for (int t = g; t < T; t += 4) { const float d = x[(size_t)t * Mp] - mu; q += d * d; }
+        const float M2 = mel_chan_sum(q, red, c, g);
+        const float rs = 1.0f / sqrtf(M2 / (float)T + 1e-5f);        // biased var, eps 1e-5 (InstanceNorm1d)
+        if (g == 0 && ch < Mp) {
+            float* so = stats + ((size_t)b * Mp + ch) * 4;
+            so[0] = on ? mu : 0.f; so[1] = on ? rs : 0.f; so[2] = on ? M2 : 0.f; so[3] = 0.f;
+        }
+        if (on && g == 0) suu += rs * rs * M2;
+        if (g == 0) { smu[j][c] = on ? mu : 0.f; srs[j][c] = on ? rs : 0.f; }
+    }
+    suu = mel_block_sum(suu, red8);
+    const float n = (float)T * (float)n_mels;
+    const float gs = sqrtf(suu / (n - 1.f));                          // unbiased std of u (mean 0): GlobalStandardize
+    const float ginv = 1.0f / (gs + 1e-8f);
+    if (threadIdx.x == 0) { gstat[b * 4 + 0] = ginv; gstat[b * 4 + 1] = gs; gstat[b * 4 + 2] = n; gstat[b * 4 + 3] = (float)T; }
+    const int Tpad = (Tp + 31) & ~31;
+#pragma unroll 1
+    for (int j = 0; j < ng; ++j) {
+        const int ch = 128 * j + c;
+        if (ch >= Mp) continue;
+        const float* x = xm + (size_t)f0 * Mp + ch;
+        float* o = x0 + (size_t)pool_off[b] * Mp + ch;
+        const float mu = smu[j][c], rs = srs[j][c];
+        for (int tp = g; tp < Tpad; tp += 4) {
+            float v = 0.f;                                            // pad rows and padding channels stay zero
+            if (tp < Tp && ch < n_mels) {
+                const float u0 = (x[(size_t)(2 * tp) * Mp] - mu) * rs, u1 = (x[(size_t)(2 * tp + 1) * Mp] - mu) * rs;
+                v = 0.5f * (u0 * ginv + u1 * ginv);                   // AvgPool1d(2, 2)
+            }
+            o[(size_t)tp * Mp] = v;
+        }
+    }
+}
+
+__global__ __launch_bounds__(512) void mel_any_clip_bwd_kernel(const float* __restrict__ dx0, float* __restrict__ xm,
+                                                                const int* __restrict__ frame_off, const int* __restrict__ pool_off,
+                                                                const float* __restrict__ stats, const float* __restrict__ gstat,
+                                                                int n_mels, int Mp) {
+    __shared__ float red[4][128];
+    __shared__ float red8[8];
+    const int b = blockIdx.x;
+    const int f0 = frame_off[b], T = frame_off[b + 1] - f0, Tp = T / 2;
+    const int c = threadIdx.x & 127, g = threadIdx.x >> 7;
+    const int ng = (Mp + 127) / 128;
+    const float ginv = gstat[b * 4 + 0], gs = gstat[b * 4 + 1], n = gstat[b * 4 + 2];
+    float d1s[kMelGroups], d2s[kMelGroups];
+    float sa = 0.f, sb = 0.f;
+#pragma unroll
+    for (int j = 0; j < kMelGroups; ++j) {
+        d1s[j] = 0.f; d2s[j] = 0.f;
+        if (j >= ng) continue;                                         // uniform across the workgroup
+        const int ch = 128 * j + c;
+        const bool on = ch < n_mels;
+        const int cc = min(ch, n_mels - 1);
+        const float* so = stats + ((size_t)b * Mp + cc) * 4;
+        const float mu = so[0], rs = so[1];
+        const float* x = xm + (size_t)f0 * Mp + cc;
+        const float* d0 = dx0 + (size_t)pool_off[b] * Mp + cc;
+        float a1 = 0.f, a2 = 0.f;
+#pragma unroll
+        for (int i = 0; i < kMelClipR; ++i) {
+            const int tp = g + 4 * i, t = 2 * tp;
+            if (tp < Tp) {
+                const float dv = 0.5f * d0[(size_t)tp * Mp];           // d(avg pool): half the pooled gradient to each frame
+                const float u0 = (x[(size_t)t * Mp] - mu) * rs, u1 = (x[(size_t)(t + 1) * Mp] - mu) * rs;
+                a1 += 2.f * dv;
+                a2 += dv * u0 + dv * u1;
+            }
+        }
+        const float D1 = mel_chan_sum(a1, red, c, g), D2 = mel_chan_sum(a2, red, c, g);
+        if (on && g == 0) { sa += D1; sb += D2; }
+        d1s[j] = D1; d2s[j] = D2;
+    }
+    sa = mel_block_sum(sa, red8);
+    sb = mel_block_sum(sb, red8);
+    const float mdv = sa / n;
+    const float Q = (gs > 0.f) ? sb * ginv * ginv / ((n - 1.f) * gs) : 0.f;
+    // every read of the clip's xm above is complete (the block sums hold barriers): the in-place writes start here
+#pragma unroll
+    for (int j = 0; j < kMelGroups; ++j) {
+        const int ch = 128 * j + c;
+        if (j >= ng || ch >= Mp) continue;
+        float* x = xm + (size_t)f0 * Mp + ch;
+        if (ch >= n_mels) {
+            for (int t = g; t < T; t += 4) x[(size_t)t * Mp] = 0.f;
+            continue;
+        }
+        const float* so = stats + ((size_t)b * Mp + ch) * 4;
+        const float mu = so[0], rs = so[1], M2 = so[2];
+        const float* d0 = dx0 + (size_t)pool_off[b] * Mp + ch;
+        const float m1 = ginv * (d1s[j] / (float)T - mdv);
+        const float m2 = (ginv * d2s[j] - Q * rs * rs * M2) / (float)T;
+        for (int t = g; t < T; t += 4) {
+            const float dv = (t < 2 * Tp) ? 0.5f * d0[(size_t)(t >> 1) * Mp] : 0.f;
+            const float u = (x[(size_t)t * Mp] - mu) * rs;
+            x[(size_t)t * Mp] = rs * (((dv - mdv) * ginv - u * Q) - m1 - u * m2);
+        }
+    }
+}
+
+// chunked form: per-chunk (mean, M2) of every channel
+__global__ __launch_bounds__(256) void mel_any_partial_stats_kernel(const float* __restrict__ xm, const int* __restrict__ frame_off,
+                                                                     float* __restrict__ part, int pstride, int n_mels, int Mp) {
+    __shared__ float s1[2][128];
+    const int b = blockIdx.y;
+    const int f0 = frame_off[b], T = frame_off[b + 1] - f0;
+    const int t0 = blockIdx.x * kMelChunk;
+    if (t0 >= T) return;
+    const int nt = min(kMelChunk, T - t0);
+    const int c = threadIdx.x & 127, g = threadIdx.x >> 7;
+    const int ng = (Mp + 127) / 128;
+    float* o = part + ((size_t)b * pstride + blockIdx.x) * 2 * Mp;
+    for (int j = 0; j < ng; ++j) {
+        const int ch = 128 * j + c;
+        const bool on = ch < n_mels;
+        const float* x = xm + (size_t)(f0 + t0) * Mp + min(ch, n_mels - 1);
+        float v[kMelChunk / 2];
+        float a = 0.f;
+#pragma unroll
+        for (int i = 0; i < kMelChunk / 2; ++i) {
+            const int t = 2 * i + g;
+            v[i] = (t < nt) ? x[(size_t)t * Mp] : 0.f;
+            a += v[i];
+        }
+        s1[g][c] = a;
+        __syncthreads();
+        const float mean = (s1[0][c] + s1[1][c]) / (float)nt;
+        __syncthreads();
+        float q = 0.f;
+#pragma unroll
+        for (int i = 0; i < kMelChunk / 2; ++i) {
+            const int t = 2 * i + g;
+            if (t < nt) { float d = v[i] - mean; q += d * d; }
+        }
+        s1[g][c] = q;
+        __syncthreads();
+        if (g == 0 && ch < Mp) {
+            o[ch] = on ? mean : 0.f;
+            o[Mp + ch] = on ? s1[0][c] + s1[1][c] : 0.f;
+        }
+        __syncthreads();
+    }
+}
+
+// merge the chunk partials of channel ch (row pitch 2 Mp)
+__device__ __forceinline__ void mel_any_merge(const float* __restrict__ part, int nchunk, int T, int ch, int Mp, float& mean,
+                                              float& M2) {
+    float n = 0.f;
+    mean = 0.f; M2 = 0.f;
+    for (int k = 0; k < nchunk; ++k) {
+        const float nk = (float)min(kMelChunk, T - k * kMelChunk);
+        const float mk = part[(size_t)k * 2 * Mp + ch], qk = part[(size_t)k * 2 * Mp + Mp + ch];
+        const float d = mk - mean, nn = n + nk;
+        mean += d * (nk / nn);
+        M2 += qk + d * d * (n * nk / nn);
+        n = nn;
+    }
+}
+
+__global__ __launch_bounds__(256) void mel_any_apply_pool_kernel(const float* __restrict__ xm, const int* __restrict__ frame_off,
+                                                                  const int* __restrict__ pool_off, const float* __restrict__ part,
+                                                                  int pstride, float* __restrict__ x0, float* __restrict__ stats,
+                                                                  float* __restrict__ gstat, int n_mels, int Mp) {
+    __shared__ float red[4];
+    const int b = blockIdx.y;
+    const int f0 = frame_off[b], T = frame_off[b + 1] - f0;
+    const int t0 = blockIdx.x * kMelChunk;
+    if (t0 >= T) return;
+    const int nchunk = (T + kMelChunk - 1) / kMelChunk;
+    const int c = threadIdx.x & 127, g = threadIdx.x >> 7;
+    const int ng = (Mp + 127) / 128;
+    const float* pp = part + (size_t)b * pstride * 2 * Mp;
+    float mus[kMelGroups], rss[kMelGroups];
+    float suu = 0.f;
+#pragma unroll
+    for (int j = 0; j < kMelGroups; ++j) {
+        mus[j] = 0.f; rss[j] = 0.f;
+        const int ch = 128 * j + c;
+        if (j >= ng || ch >= n_mels) continue;
+        float mu, M2;
+        mel_any_merge(pp, nchunk, T, ch, Mp, mu, M2);
+        const float rs = 1.0f / sqrtf(M2 / (float)T + 1e-5f);        // biased var, eps 1e-5
+        mus[j] = mu; rss[j] = rs;
+        if (g == 0) suu += rs * rs * M2;
+        if (blockIdx.x == 0 && g == 0) { float* so = stats + ((size_t)b * Mp + ch) * 4; so[0] = mu; so[1] = rs; so[2] = M2; so[3] = 0.f; }
+    }
+    suu = block_sum(suu, red);
+    const float n = (float)T * (float)n_mels;
+    const float gs = sqrtf(suu / (n - 1.f));                          // unbiased std of u (mean 0)
+    const float ginv = 1.0f / (gs + 1e-8f);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        gstat[b * 4 + 0] = ginv; gstat[b * 4 + 1] = gs; gstat[b * 4 + 2] = n; gstat[b * 4 + 3] = (float)T;
+    }
+    const int Tp = T / 2;
+    const int tp0 = t0 / 2, tp1 = min(Tp, tp0 + kMelChunk / 2);
+    const bool last = (int)blockIdx.x == nchunk - 1;
+#pragma unroll
+    for (int j = 0; j < kMelGroups; ++j) {
+        const int ch = 128 * j + c;
+        if (j >= ng || ch >= Mp) continue;
+        if (blockIdx.x == 0 && g == 0 && ch >= n_mels) {
+            float* so = stats + ((size_t)b * Mp + ch) * 4; so[0] = 0.f; so[1] = 0.f; so[2] = 0.f; so[3] = 0.f;
+        }
+        const float* x = xm + (size_t)f0 * Mp + ch;
+        float* o = x0 + (size_t)pool_off[b] * Mp + ch;
+        const float mu = mus[j], rs = rss[j];
+        for (int tp = tp0 + g; tp < tp1; tp += 2) {
+            float v = 0.f;                                            // padding channels stay zero
+            if (ch < n_mels) {
+                const float u0 = (x[(size_t)(2 * tp) * Mp] - mu) * rs, u1 = (x[(size_t)(2 * tp + 1) * Mp] - mu) * rs;
+                v = 0.5f * (u0 * ginv + u1 * ginv);
+            }
+            o[(size_t)tp * Mp] = v;
+        }
+        // pooled rows are 32-aligned per clip: keep the pad rows finite (they flow through the GEMMs)
+        if (last)
+            for (int tp = Tp + g; tp < ((Tp + 31) & ~31); tp += 2) o[(size_t)tp * Mp] = 0.f;
+    }
+}
+
+// backward partials: D1_c = sum_t dv, D2_c = sum_t dv*u over the chunk (dv = dx0/2 on pooled frames)
+__global__ __launch_bounds__(256) void mel_any_bwd_partial_kernel(const float* __restrict__ dx0, const float* __restrict__ xm,
+                                                                   const int* __restrict__ frame_off, const int* __restrict__ pool_off,
+                                                                   const float* __restrict__ stats, float* __restrict__ part,
+                                                                   int pstride, int n_mels, int Mp) {
+    __shared__ float s1[2][128], s2[2][128];
+    const int b = blockIdx.y;
+    const int f0 = frame_off[b], T = frame_off[b + 1] - f0, Tp = T / 2;
+    const int t0 = blockIdx.x * kMelChunk;
+    if (t0 >= T) return;
+    const int c = threadIdx.x & 127, g = threadIdx.x >> 7;
+    const int ng = (Mp + 127) / 128;
+    const int tp0 = t0 / 2, tp1 = min(Tp, tp0 + kMelChunk / 2);
+    float* o = part + ((size_t)b * pstride + blockIdx.x) * 2 * Mp;
+    for (int j = 0; j < ng; ++j) {
+        const int ch = 128 * j + c;
+        const int cc = min(ch, n_mels - 1);
+        const float* so = stats + ((size_t)b * Mp + cc) * 4;
+        const float mu = so[0], rs = so[1];
+        const float* x = xm + (size_t)f0 * Mp + cc;
+        const float* d0 = dx0 + (size_t)pool_off[b] * Mp + cc;
+        float a1 = 0.f, a2 = 0.f;
+        for (int tp = tp0 + g; tp < tp1; tp += 2) {
+            const float dv = 0.5f * d0[(size_t)tp * Mp];
+            const float u0 = (x[(size_t)(2 * tp) * Mp] - mu) * rs, u1 = (x[(size_t)(2 * tp + 1) * Mp] - mu) * rs;
+            a1 += 2.f * dv;
+            a2 += dv * u0 + dv * u1;
+        }
+        s1[g][c] = a1; s2[g][c] = a2;
+        __syncthreads();
+        if (g == 0 && ch < Mp) {
+            const bool on = ch < n_mels;
+            o[ch] = on ? s1[0][c] + s1[1][c] : 0.f;
+            o[Mp + ch] = on ? s2[0][c] + s2[1][c] : 0.f;
+        }
+        __syncthreads();
+    }
+}
+
+// backward apply, in place on xm (xm <- dL/dxm; zero in the padding channels)
+__global__ __launch_bounds__(256) void mel_any_bwd_apply_kernel(const float* __restrict__ dx0, float* __restrict__ xm,
+                                                                 const int* __restrict__ frame_off, const int* __restrict__ pool_off,
+                                                                 const float* __restrict__ stats, const float* __restrict__ gstat,
+                                                                 const float* __restrict__ part, int pstride, int n_mels, int Mp) {
+    __shared__ float red[4];
+    const int b = blockIdx.y;
+    const int f0 = frame_off[b], T = frame_off[b + 1] - f0, Tp = T / 2;
+    const int t0 = blockIdx.x * kMelChunk;
+    if (t0 >= T) return;
+    const int nchunk = (T + kMelChunk - 1) / kMelChunk;
+    const int c = threadIdx.x & 127, g = threadIdx.x >> 7;
+    const int ng = (Mp + 127) / 128;
+    const float ginv = gstat[b * 4 + 0], gs = gstat[b * 4 + 1], n = gstat[b * 4 + 2];
+    const float* pp = part + (size_t)b * pstride * 2 * Mp;
+    float d1s[kMelGroups], d2s[kMelGroups];
+    float sa = 0.f, sb = 0.f;
+#pragma unroll
+    for (int j = 0; j < kMelGroups; ++j) {
+        d1s[j] = 0.f; d2s[j] = 0.f;
+        const int ch = 128 * j + c;
+        if (j >= ng || ch >= n_mels) continue;
+        float D1 = 0.f, D2 = 0.f;
+        for (int k = 0; k < nchunk; ++k) { D1 += pp[(size_t)k * 2 * Mp + ch]; D2 += pp[(size_t)k * 2 * Mp + Mp + ch]; }
+        d1s[j] = D1; d2s[j] = D2;
+        if (g == 0) { sa += D1; sb += D2; }
+    }
+    sa = block_sum(sa, red);
+    sb = block_sum(sb, red);
+    const float mdv = sa / n;
+    const float Q = (gs > 0.f) ? sb * ginv * ginv / ((n - 1.f) * gs) : 0.f;
+    const int t1 = min(T, t0 + kMelChunk);
+#pragma unroll
+    for (int j = 0; j < kMelGroups; ++j) {
+        const int ch = 128 * j + c;
+        if (j >= ng || ch >= Mp) continue;
+        float* x = xm + (size_t)f0 * Mp + ch;
+        if (ch >= n_mels) {
+            for (int t = t0 + g; t < t1; t += 2) x[(size_t)t * Mp] = 0.f;
+            continue;
+        }
+        const float* so = stats + ((size_t)b * Mp + ch) * 4;
+        const float mu = so[0], rs = so[1], M2 = so[2];
+        const float m1 = ginv * (d1s[j] / (float)T - mdv);
+        const float m2 = (ginv * d2s[j] - Q * rs * rs * M2) / (float)T;
+        const float* d0 = dx0 + (size_t)pool_off[b] * Mp + ch;
+        for (int t = t0 + g; t < t1; t += 2) {
+            const float dv = (t < 2 * Tp) ? 0.5f * d0[(size_t)(t >> 1) * Mp] : 0.f;
+            const float u = (x[(size_t)t * Mp] - mu) * rs;
+            x[(size_t)t * Mp] = rs * (((dv - mdv) * ginv - u * Q) - m1 - u * m2);
+        }
+    }
+}
+
+void launch_mel_norm_fwd_any(const float* xm, const int* frame_off, const int* pool_off, float* x0, float* stats, float* gstat,
+                             float* part, int pstride, int B, int max_frames, int n_mels, int Mp, hipStream_t st) {
+    if (max_frames <= kMelClipFrames) {
+        hipLaunchKernelGGL(mel_any_clip_fwd_kernel, dim3(B), dim3(512), 0, st, xm, frame_off, pool_off, x0, stats, gstat, n_mels, Mp);
+        return;
+    }
+    const int nx = (max_frames + kMelChunk - 1) / kMelChunk;
+    hipLaunchKernelGGL(mel_any_partial_stats_kernel, dim3(nx, B), dim3(256), 0, st, xm, frame_off, part, pstride, n_mels, Mp);
+    hipLaunchKernelGGL(mel_any_apply_pool_kernel, dim3(nx, B), dim3(256), 0, st, xm, frame_off, pool_off, part, pstride, x0, stats,
+                       gstat, n_mels, Mp);
+}
+void launch_mel_norm_bwd_any(const float* dx0, float* xm, const int* frame_off, const int* pool_off, const float* stats,
+                             const float* gstat, float* part, int pstride, int B, int max_frames, int n_mels, int Mp, hipStream_t st) {
+    if (max_frames <= kMelClipFrames) {
+        hipLaunchKernelGGL(mel_any_clip_bwd_kernel, dim3(B), dim3(512), 0, st, dx0, xm, frame_off, pool_off, stats, gstat, n_mels, Mp);
+        return;
+    }
+    const int nx = (max_frames + kMelChunk - 1) / kMelChunk;
+    hipLaunchKernelGGL(mel_any_bwd_partial_kernel, dim3(nx, B), dim3(256), 0, st, dx0, xm, frame_off, pool_off, stats, part, pstride,
+                       n_mels, Mp);
+    hipLaunchKernelGGL(mel_any_bwd_apply_kernel, dim3(nx, B), dim3(256), 0, st, dx0, xm, frame_off, pool_off, stats, gstat, part,
+                       pstride, n_mels, Mp);
+}
 void launch_in_lrelu_fwd(float* z, const int* frame_off, const int* pool_off, float* rstd, int C, int B, int max_pooled, hipStream_t st) {
     if (max_pooled <= 128)
         hipLaunchKernelGGL(in_lrelu_fwd_reg_kernel<32>, dim3((C + 63) / 64, B), dim3(256), 0, st, z, frame_off, pool_off, rstd, C);

@@ -174,6 +174,12 @@ bool launch_mel_norm_fwd(const float* xm, const int* frame_off, const int* pool_
                          float* amax_out = nullptr);   // (amax_out as launch_mel_front_x3; returns whether it was written)
 void launch_mel_norm_bwd(const float* dx0, float* xm_inout, const int* frame_off, const int* pool_off, const float* stats,
                          const float* gstat, float* part, int pstride, int B, int max_frames, hipStream_t st);
+// the same for any bank: n_mels <= 512 bands in rows of Mp >= n_mels floats (Mp % 4 == 0); stats [B][Mp][4], part
+// [B][pstride][2 Mp].  Padding channels get zero statistics, zero x0 columns and zero dL/dxm
+void launch_mel_norm_fwd_any(const float* xm, const int* frame_off, const int* pool_off, float* x0, float* stats, float* gstat,
+                             float* part, int pstride, int B, int max_frames, int n_mels, int Mp, hipStream_t st);
+void launch_mel_norm_bwd_any(const float* dx0, float* xm_inout, const int* frame_off, const int* pool_off, const float* stats,
+                             const float* gstat, float* part, int pstride, int B, int max_frames, int n_mels, int Mp, hipStream_t st);
 // conv block tail: InstanceNorm over time + LeakyReLU(0.2), in place; saves rstd
 void launch_in_lrelu_fwd(float* z, const int* frame_off, const int* pool_off, float* rstd, int C, int B, int max_pooled,
                          hipStream_t st);

@@ -51,6 +51,10 @@ def final_activation_name(name: str) -> str:
 
 # the longest payload the read-out kernels serve (aware_detector_create: a last block of at most 1024 channels)
 MAX_OUTPUT_LENGTH = 512
+# the largest mel bank, hidden width and depth aware_detector_create takes
+MAX_N_MELS = 512
+MAX_FILTERS = 4096
+MAX_NUM_BLOCKS = 32
 
 
 class AWAREDetectorNet(BaseDetectorNet):
@@ -72,6 +76,16 @@ class AWAREDetectorNet(BaseDetectorNet):
             unsupported.append("initial pool other than (2, 2)")
         if unsupported:
             raise NotImplementedError("the HIP detector implements 1x1 convolutions after a (2, 2) pool only: " + "; ".join(unsupported))
+        if n_mels < 1 or num_blocks < 0 or any(f < 1 for f in n_filters) or output_length < 1:
+            raise ValueError(f"detector sizes must be positive: n_mels = {n_mels}, num_blocks = {num_blocks}, "
+                             f"n_filters = {n_filters}, output_length = {output_length}")
+        if n_mels > MAX_N_MELS:
+            raise NotImplementedError(f"n_mels = {n_mels}: the HIP detector serves mel banks of at most {MAX_N_MELS} bands")
+        if num_blocks > MAX_NUM_BLOCKS:
+            raise NotImplementedError(f"num_blocks = {num_blocks}: the HIP detector serves at most {MAX_NUM_BLOCKS} blocks")
+        if any(f > MAX_FILTERS for f in n_filters):
+            raise NotImplementedError(f"n_filters = {n_filters}: the HIP detector serves blocks of at most {MAX_FILTERS} "
+                                      "channels")
         if output_length > MAX_OUTPUT_LENGTH:
             raise NotImplementedError(f"output_length = {output_length}: the HIP detector reads out payloads of at most "
                                       f"{MAX_OUTPUT_LENGTH} bits (a last block of at most {2 * MAX_OUTPUT_LENGTH} channels)")

@@ -27,6 +27,34 @@ def band_stride(band_lo: int, band_hi: int) -> int:
     return SPEC_STRIDE if band_lo >= 1 and band_hi <= 511 and band_hi - band_lo + 1 <= SPEC_STRIDE else SPEC_STRIDE_WIDE
 
 
+def stored_channels(channels: Sequence[int]) -> list[int]:
+    """Channel counts a detector stores for the caller's `channels` = [n_mels, hidden widths..., 2 * payload bits]
+    (stored_channels, csrc/capi.hip): the mel bank and every hidden width as is when a multiple of 4, else rounded up to a
+    multiple of 4 up to 64 and of 128 above; the last block rounded up to a multiple of 4 up to 64 and of 128 above.  The
+    padding channels are zero and invisible in every result."""
+    n = len(channels) - 1
+    out = []
+    for i, c in enumerate(channels):
+        if i < n and c % 4 == 0:
+            out.append(c)
+        else:
+            out.append((c + 3) // 4 * 4 if c <= 64 else (c + 127) // 128 * 128)
+    return out
+
+
+def training_refusal(channels: Sequence[int]) -> str | None:
+    """Why the detector-training extension refuses a network of these channels (None: it serves them): it runs 128 mel bands,
+    hidden widths that need no padding and at most 6 hidden blocks only (the C ABI returns AWARE_E_UNSUPPORTED)."""
+    if channels[0] != 128:
+        return f"n_mels = {channels[0]} (detector training supports 128 mel bands only)"
+    if len(channels) - 1 > 7:
+        return f"num_blocks = {len(channels) - 2} (detector training supports at most 6 blocks)"
+    st = stored_channels(channels)
+    if any(a != b for a, b in zip(channels[1:-1], st[1:-1])):
+        return f"n_filters = {list(channels[1:-1])} (detector training supports hidden widths that are multiples of 4 only)"
+    return None
+
+
 def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
@@ -334,14 +362,17 @@ def detector_backward(plan: Plan, det: "DetectorWeights", batch: Batch, mag: tor
 
 
 def require_card_arch(det: "DetectorWeights", what: str):
-    """The detector-training extension serves the model card's architecture on a band of the narrow layout only (the C ABI
-    returns AWARE_E_UNSUPPORTED)."""
+    """The detector-training extension serves the model card's architecture on a band of the narrow layout, with the sizes of
+    training_refusal, only (the C ABI returns AWARE_E_UNSUPPORTED)."""
     if not det.is_card:
         raise NotImplementedError(f"{what}: detector training supports the model card's architecture only "
                                   "(instance norm, leaky_relu blocks, tanh read-out)")
     if det.plan.band_stride != SPEC_STRIDE:
         raise NotImplementedError(f"{what}: detector training supports bands inside bins 1..511 at most 256 bins wide only; "
                                   f"the band {det.plan.band_bins} has the wide layout")
+    why = training_refusal(det.channels)
+    if why:
+        raise NotImplementedError(f"{what}: {why}")
 
 
 def detector_weight_gradients(plan: Plan, det: "DetectorWeights", batch: Batch, mag: torch.Tensor, grad_values: torch.Tensor):

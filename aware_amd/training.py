@@ -37,6 +37,9 @@ class DetectorTrainer:
         if not getattr(self.net, "is_card_arch", True):
             raise NotImplementedError("DetectorTrainer supports the model card's detector architecture only "
                                       "(instance norm, leaky_relu blocks, tanh read-out)")
+        why = rt.training_refusal(getattr(self.net, "channels", [128, 1]))
+        if why:
+            raise NotImplementedError(f"DetectorTrainer: {why}")
         self.sample_rate = sample_rate
         shapes = [np.asarray(w).shape for w in self.net.weights] + [np.asarray(b).shape for b in self.net.biases]
         sizes = [int(np.prod(sh)) for sh in shapes]

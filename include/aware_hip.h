@@ -66,7 +66,8 @@ typedef struct aware_embed aware_embed;
  * STFT geometry -- aware_plan_create_ex, aware_plan_spectrum_stride, aware_plan_is_general, aware_batch_create_for_plan,
  * aware_nola_check; 320: detector architecture variants -- aware_detector_create_ex, aware_detector_is_card; 330: any
  * embedding band inside bins 0..512 -- the wide layout, aware_plan_band_stride; 340: payloads of 1..512 bits --
- * aware_detector_create accepts any even channels[n_layers] from 2 to 1024) */
+ * aware_detector_create accepts any even channels[n_layers] from 2 to 1024; 350: detector sizes -- n_mels 1..512, hidden
+ * widths 1..4096, n_layers 1..33) */
 int aware_version(void);
 /* text of the last failed HIP runtime call on the calling thread (thread-local) */
 const char* aware_last_hip_error(void);
@@ -186,10 +187,14 @@ int aware_nadam_clamp_step(float* param, const float* grad, float* exp_avg, floa
  * mel_basis [n_mels][n_fft/2+1] (detection/modules/mel.py:105-149), conv weights
  * [channels[i+1]][channels[i]] and biases [channels[i+1]] for i < n_layers
  * (channels = {128, 512, 1024, 1024, 40}).  The library uploads and pre-transposes them.
- * channels[0] = n_mels = 128; channels[1 .. n_layers-1] multiples of 4; channels[n_layers] = 2 * payload bits, any even
- * value from 2 to 1024 (payloads of 1..512 bits), else AWARE_E_UNSUPPORTED.  The last block is stored with its channels
- * padded (to a multiple of 4 up to 64, to a multiple of 128 above): zero weights and biases, never read out.  Every array
- * the caller passes or receives keeps the caller's shapes. */
+ * channels[0] = n_mels, 1..512; channels[1 .. n_layers-1] (hidden widths) 1..4096; n_layers 1..33 (num_blocks 0..32);
+ * channels[n_layers] = 2 * payload bits, any even value from 2 to 1024 (payloads of 1..512 bits), else AWARE_E_UNSUPPORTED.
+ * Storage rule: n_mels and every hidden width are stored as given when a multiple of 4, else rounded up to a multiple of 4
+ * (up to 64) or of 128 (above 64); the last block is rounded up to a multiple of 4 up to 64 and of 128 above.  Padding
+ * channels have zero weights, biases and mel rows (BatchNorm: scale 0, shift 0), are never read out and get a zero
+ * gradient.  Every array the caller passes or receives keeps the caller's shapes.  The training extension
+ * (aware_detector_update*, aware_detector_*_gradients) serves n_mels = 128, hidden widths that are multiples of 4 and at
+ * most 7 layers only (AWARE_E_UNSUPPORTED otherwise). */
 int aware_detector_create(aware_detector** out, const aware_plan* plan, const float* mel_basis, int n_mels,
                           int n_layers, const int* channels, const float* const* weights,
                           const float* const* biases);
