@@ -591,13 +591,13 @@ static void run_synth(SynthLaunch& S, int dsp_path, hipStream_t st) {
 // ---------------------------------------------------------------------------------------------
 // workspace carving
 struct Carver {
-    char* base;
+    char* base;       // null: only count (off is then the workspace size)
     size_t off = 0, cap;
     bool ok = true;
     Carver(void* p, size_t c) : base((char*)p), cap(c) {}
     template <typename Tp> Tp* take(size_t count) {
         off = (off + 255) & ~(size_t)255;
-        Tp* r = (Tp*)(base + off);
+        Tp* r = base ? (Tp*)(base + off) : nullptr;
         off += count * sizeof(Tp);
         if (off > cap) ok = false;
         return r;
@@ -1062,15 +1062,13 @@ struct DetBufs {
     float* x0;        // [NP][Mp]
     std::vector<float*> act;    // [NP][C_l+1]
     std::vector<float*> rstd;   // [B][C_l+1]
-    std::vector<float*> stash;  // [NP][C_l+1] pre-activations of a staged-route block (det_needs_stash), else null
+    std::vector<float*> stash;  // [NP][C_l+1] pre-activations of a variant's block (det_needs_stash), else null
     float *mstats, *gstat, *mpart;   // mel statistics [B][Mp][4], [B][4], chunk partials [B][mstride][2 Mp]
     int mstride;
     float* pred;      // [B][nbits]
-    float* zpart;     // split-K partial slabs of the last conv [kTailSplit][NP][C_last]
-    int tail;         // 1: the last conv was left as partials for the fused tail kernel
-    int zslabs;       // partial slabs the forward epilogue left in zpart (fused read-out)
-    // per-clip partial maxima [B][64] for the f16 two-term GEMM's scales: of x0 (index 0), of act[l] (index l + 1), and of
-    // the two gradient ping-pong buffers (gmax)
+    float* zpart;     // split-K partial slabs of the last conv [zpart_slabs][NP][C_last]
+    // per-clip partial maxima [B][64] for the f16 two-term GEMM's scales: of x0 (index 0) and of act[l] (index l + 1); of
+    // dL/dZ_l in gmax[l & 1]
     std::vector<float*> amax;
     float* gmax[2];
 };
@@ -1080,6 +1078,8 @@ static int zpart_slabs(const aware_detector* d) {
     const int s = d->n_layers >= 1 ? d->ch[d->n_layers - 1] / 128 : 0;
     return s > kTailSplit ? s : kTailSplit;
 }
+// Workspace carving.  Each entry point carves its workspace in one function, and its *_workspace_bytes runs the same
+// function on a Carver without a base, which only counts.
 static void carve_det(Carver& c, const aware_batch* b, const aware_detector* d, DetBufs& o) {
     const int Mp = d->ch[0];
     o.act.assign(d->n_layers, nullptr); o.rstd.assign(d->n_layers, nullptr); o.stash.assign(d->n_layers, nullptr);
@@ -1097,21 +1097,9 @@ static void carve_det(Carver& c, const aware_batch* b, const aware_detector* d, 
     o.mpart = c.take<float>((size_t)b->B * o.mstride * 2 * Mp);
     o.pred = c.take<float>((size_t)b->B * d->nbits);
     o.zpart = c.take<float>((size_t)zpart_slabs(d) * b->NP * d->ch[d->n_layers]);
-    o.tail = 0;
     for (int l = 0; l <= d->n_layers; ++l) o.amax[l] = c.take<float>((size_t)b->B * 64);
     o.gmax[0] = c.take<float>((size_t)b->B * 64);
     o.gmax[1] = c.take<float>((size_t)b->B * 64);
-}
-static size_t det_bytes(const aware_batch* b, const aware_detector* d) {
-    const size_t Mp = d->ch[0];
-    size_t f = (size_t)b->NF * Mp + (size_t)b->NP * Mp + (size_t)b->B * (Mp * 4 + 4 + d->nbits) +
-               (size_t)b->B * ((b->max_frames + 31) / 32) * 2 * Mp;
-    for (int l = 0; l < d->n_layers; ++l) f += (size_t)(b->NP + b->B) * d->ch[l + 1];
-    if (det_needs_stash(d))
-        for (int l = 0; l < d->n_layers; ++l) f += (size_t)b->NP * d->ch[l + 1];
-    f += (size_t)zpart_slabs(d) * b->NP * d->ch[d->n_layers];
-    f += (size_t)b->B * 64 * (d->n_layers + 3);
-    return f * sizeof(float) + 256 * (12 + 4 * d->n_layers);
 }
 
 // number of 32-row groups per clip when the fused clip-aligned GEMM applies (uniform batch,
@@ -1127,116 +1115,213 @@ constexpr int kMelFrontMinClips = 192;
 // fewer workgroups than this: the latency variant of the bf16x3 kernel serves the conv block (gemm_x3.hip, kSmallGrid)
 constexpr int kH2MinGrid = 128;
 
-static bool mel_front_applies(const aware_detector* d, const aware_batch* b, int pipe) {
+// The kernels of one detector call, chosen once by det_plan and launched by det_forward / det_forward_backward.
+enum class MelFwd : unsigned char {
+    Folded,   // the analysis kernel left the raw mel tile in xm: the norms and pooling only
+    Front,    // mel GEMM, norms and pooling in one launch (launch_mel_front_x3)
+    Gemm,     // mel GEMM, then the norms and pooling (the 128-band kernels or the any-bank form)
+};
+// a conv block's forward (GEMM + norm + activation), or its data-gradient GEMM with the previous block's norm and activation
+// backward fused in where the kind is not Plain
+enum class Conv : unsigned char {
+    Plain,         // gemm_plain, then launch_norm_act_fwd (forward) / launch_norm_act_bwd of block l - 1 (next layer down)
+    ClipF32,       // clip-aligned GEMM, norm / activation in the epilogue (uniform batch, f32 MFMA)
+    ClipX3,        // the same on the bf16 three-term kernel
+    ClipH2,        // the same on the f16 two-term kernel (per-clip operand scales from partial maxima)
+    RaggedX3,      // ragged batch / long clips, clips walked in chunks of rows: bf16 three-term
+    RaggedH2,      // the same on the f16 two-term kernel
+    SplitK,        // forward of a skinny last block: split-K partial slabs, summed by the tail read-out
+    ReadoutGrad,   // data gradient of the last block from the tail's pitch-64 dL/dZ (launch_readout_grad_ragged_x3)
+    MelBack,       // data gradient of block 0 + the mel stage's backward in one launch (launch_mel_back_x3)
+};
+enum class Readout : unsigned char {
+    X3,     // the last block, read-out, loss and their backward in one kernel (launch_readout_x3)
+    Tail,   // sum of the split-K slabs + read-out (launch_tail)
+    Wide,   // more than 64 channels: one workgroup per clip (launch_readout_wide)
+    Head,   // launch_head
+};
+struct DetPlan {
+    int pipe = 0, nwm = 0;    // conv pipe (aware_embed_config::conv_pipe); clip_tile_groups
+    MelFwd mel = MelFwd::Gemm;
+    bool mel_amax = false;    // the mel kernel is handed amax[0]
+    bool mel_any = false;     // not 128 bands: the any-bank norm kernels
+    bool mag_grad = true;     // the backward ends with the GEMM to dL/d|S| (else the caller expands dL/d(mel) itself)
+    int n_fwd = 0;            // blocks the forward runs (the fused read-out computes the last one itself)
+    int top = 0;              // first block the backward loop differentiates
+    Readout readout = Readout::Head;
+    bool tail_k64 = false;    // the tail writes dL/dZ of the last block with a row pitch of 64, for Conv::ReadoutGrad
+    Conv fwd[kMaxLayers] = {}, bwd[kMaxLayers] = {};
+    // x_max[l]: the kernel that writes block l's input also leaves its per-clip maxima in amax[l], for an f16 two-term block
+    // l (otherwise that block launches the maxima kernel first); g_max[l]: the same for dL/dZ_l in gmax[l & 1]
+    bool x_max[kMaxLayers + 1] = {}, g_max[kMaxLayers] = {};
+    // dz[l]: the backward reaches block l with dL/dZ_l (its norm and activation backward fused into the kernel before), else
+    // with dL/dA_l and launches launch_norm_act_bwd first
+    bool dz[kMaxLayers] = {};
+};
+static bool is_h2(Conv k) { return k == Conv::ClipH2 || k == Conv::RaggedH2; }
+
+// readout: aware_embed_config::readout (1: never the fused read-out); training: the parameter gradients are wanted too;
+// mel_folded: the analysis kernel writes the raw mel tile (xm); mel_grad_only: the backward stops at dL/d(mel)
+static DetPlan det_plan(const aware_detector* d, const aware_batch* b, int pipe, int readout, bool training, bool mel_folded,
+                        bool mel_grad_only) {
+    DetPlan p;
+    const int nl = d->n_layers;
+    const std::vector<int>& ch = d->ch;
+    const bool card = d->card_arch;        // the fused kinds serve the model card's blocks only
+    const int nwm = clip_tile_groups(b);
+    p.pipe = pipe; p.nwm = nwm;
+    // uniform batch that fills the chip with one workgroup per clip: the whole mel block in one launch, and its backward with
+    // block 0's data gradient
     bool same_T = true;
     for (int i = 1; i < b->B; ++i) same_T = same_T && b->T[i] == b->T[0];
-    return pipe != 1 && d->n_mels == 128 && d->melTpk && same_T && b->B >= kMelFrontMinClips &&
-           mel_front_x3_supported(b->T[0], d->stride, d->stride);
+    const bool mel_front = pipe != 1 && d->n_mels == 128 && d->melTpk && same_T && b->B >= kMelFrontMinClips &&
+                           mel_front_x3_supported(b->T[0], d->stride, d->stride);
+    p.mel = mel_folded ? MelFwd::Folded : mel_front ? MelFwd::Front : MelFwd::Gemm;
+    p.mel_amax = p.mel == MelFwd::Front || (p.mel == MelFwd::Folded && pipe == 0 && nwm);
+    p.mel_any = d->n_mels != 128;
+    p.mag_grad = !mel_grad_only;
+    // one kernel for the last conv block, the BRH head, the loss, their backward and the data gradient of the last conv
+    // (uniform batches, bf16x3 configuration); otherwise split-K GEMM + tail kernel + data-gradient GEMM
+    const bool fused_readout = card && readout == 0 && !training && pipe != 1 && nwm && nl >= 2 && d->lastpk &&
+                               ch[nl] == 2 * d->nbits && readout_x3_supported(nwm, ch[nl - 1], ch[nl]) && d->wpk[nl - 2] &&
+                               gemm_clip_x3_supported(nwm, ch[nl - 1], ch[nl - 2], ch[nl - 2]);
+    p.n_fwd = fused_readout ? nl - 1 : nl;
+    for (int l = 0; l < nl; ++l) {
+        const int ci = ch[l], co = ch[l + 1];
+        Conv k = Conv::Plain;
+        if (!card) {
+        } else if (l == nl - 1 && co <= 64 && b->max_frames / 2 <= 320) {
+            k = Conv::SplitK;
+        } else if (nwm && co >= 128) {
+            if (pipe == 0 && d->wh2[l] && (co / 128) * b->B >= kH2MinGrid && gemm_clip_h2_supported(nwm, co, ci, ci))
+                k = Conv::ClipH2;
+            else if (pipe != 1 && d->wpk[l] && gemm_clip_x3_supported(nwm, co, ci, ci))
+                k = Conv::ClipX3;
+            else
+                k = Conv::ClipF32;
+        } else if (pipe == 0 && !nwm && d->wh2[l] && co >= 128 && gemm_clip_h2_supported(1, co, ci, ci)) {
+            k = Conv::RaggedH2;
+        } else if (pipe != 1 && !nwm && co >= 128 && d->wpk[l] && gemm_clip_x3_supported(1, co, ci, ci)) {
+            k = Conv::RaggedX3;
+        }
+        p.fwd[l] = k;
+    }
+    // the clip form of the mel norm kernel leaves the maxima of x0 when handed amax[0]; the chunked form does not
+    const bool mel_writes_max = p.mel == MelFwd::Front || (p.mel_amax && b->max_frames <= kMelClipFrames);
+    for (int l = 0; l < p.n_fwd; ++l) p.x_max[l] = is_h2(p.fwd[l]) && (l == 0 ? mel_writes_max : is_h2(p.fwd[l - 1]));
+
+    p.readout = fused_readout ? Readout::X3 : p.fwd[nl - 1] == Conv::SplitK ? Readout::Tail
+              : ch[nl] > 64 ? Readout::Wide : Readout::Head;
+    // ragged batch on the bf16x3 pipe: dL/dZ of the last block with a pitch of 64 (zero K padding), so that its data gradient
+    // runs on the ragged conv kernel with the previous block's InstanceNorm + LeakyReLU backward fused
+    p.tail_k64 = p.readout == Readout::Tail && !nwm && pipe != 1 && !training && nl >= 2 && d->lastTpk && ch[nl] <= 64 &&
+                 ch[nl - 1] % 128 == 0;
+    p.top = fused_readout ? nl - 2 : nl - 1;
+    // the wide read-out writes dL/dZ of the last block on the card (dL/dA on a variant)
+    const bool readout_dz = p.readout != Readout::Head && (p.readout != Readout::Wide || card);
+    for (int l = p.top; l >= 0; --l) {
+        const int ci = ch[l], co = ch[l + 1];
+        p.dz[l] = l == p.top ? readout_dz : p.bwd[l + 1] != Conv::Plain;
+        Conv k = Conv::Plain;
+        if (!card) {
+        } else if (nwm && l > 0 && ci >= 128) {
+            if (pipe == 0 && d->wTh2[l] && (ci / 128) * b->B >= kH2MinGrid && gemm_clip_h2_supported(nwm, ci, co, co))
+                k = Conv::ClipH2;
+            else if (pipe != 1 && d->wTpk[l] && gemm_clip_x3_supported(nwm, ci, co, co))
+                k = Conv::ClipX3;
+            else
+                k = Conv::ClipF32;
+        } else if (l == nl - 1 && p.tail_k64) {
+            k = Conv::ReadoutGrad;
+        } else if (pipe == 0 && !nwm && l > 0 && d->wTh2[l] && ci >= 128 && co >= 128 && gemm_clip_h2_supported(1, ci, co, co)) {
+            k = Conv::RaggedH2;
+        } else if (pipe != 1 && !nwm && l > 0 && ci >= 128 && d->wTpk[l] && gemm_clip_x3_supported(1, ci, co, co)) {
+            k = Conv::RaggedX3;
+        } else if (l == 0 && mel_front && p.dz[0] && !training && d->wTpk[0] && co % 64 == 0 && d->n_mels == 128) {
+            k = Conv::MelBack;
+        }
+        p.bwd[l] = k;
+        // the fused and wide read-outs, the f16 two-term kernels and the ragged read-out gradient leave the maxima of the
+        // gradient they write for an f16 two-term consumer
+        const bool writes_max = l == p.top ? p.readout == Readout::X3 || p.readout == Readout::Wide
+                                           : is_h2(p.bwd[l + 1]) || p.bwd[l + 1] == Conv::ReadoutGrad;
+        p.g_max[l] = is_h2(k) && writes_max;
+    }
+    return p;
 }
 
-// forward through the network; mag [NF][256] -> act[last], pred
-// xm_ready: o.xm already holds the raw mel tile (the analysis kernel wrote it: mel projection folded in); mag is not read
-static int det_forward(const aware_detector* d, const aware_batch* b, const float* mag, DetBufs& o, hipStream_t st,
-                       int pipe = 0, bool skip_last = false, bool xm_ready = false) {
-    // conv blocks of a uniform batch that fills the chip: the f16 two-term kernel (default pipe); its per-clip scale comes
-    // from partial maxima that the producer of each operand leaves behind (x0_max: whether o.amax[0] is current)
-    const int nwm0 = clip_tile_groups(b);
-    auto h2_fwd = [&](int l) {
-        return pipe == 0 && nwm0 && d->wh2[l] && d->ch[l + 1] >= 128 && (d->ch[l + 1] / 128) * b->B >= kH2MinGrid &&
-               gemm_clip_h2_supported(nwm0, d->ch[l + 1], d->ch[l], d->ch[l]);
-    };
-    auto h2_rag = [&](int l) {
-        return pipe == 0 && !nwm0 && d->wh2[l] && d->ch[l + 1] >= 128 && gemm_clip_h2_supported(1, d->ch[l + 1], d->ch[l], d->ch[l]) &&
-               !(l == d->n_layers - 1 && d->ch[l + 1] <= 64);
-    };
-    bool cur_max = false;            // o.amax[l] holds the maxima of the current layer input
-    if (xm_ready) {
-        cur_max = launch_mel_norm_fwd(o.xm, b->d_frame_off, b->d_pool_off, o.x0, o.mstats, o.gstat, o.mpart, o.mstride, b->B,
-                                      b->max_frames, st, (pipe == 0 && clip_tile_groups(b)) ? o.amax[0] : nullptr);
-        LAUNCHCHK(); PROF(K_MELNORM);
-    } else if (mel_front_applies(d, b, pipe)) {
-        // uniform batch that fills the chip with one workgroup per clip: the whole mel block in one launch
+// forward through the network; mag [NF][stride] -> act, pred (mag is not read when the plan's mel stage is folded)
+static int det_forward(const aware_detector* d, const aware_batch* b, const DetPlan& p, const float* mag, DetBufs& o,
+                       hipStream_t st) {
+    const int nl = d->n_layers, Mp = d->ch[0];
+    if (p.mel == MelFwd::Folded) {
+        launch_mel_norm_fwd(o.xm, b->d_frame_off, b->d_pool_off, o.x0, o.mstats, o.gstat, o.mpart, o.mstride, b->B, b->max_frames,
+                            st, p.mel_amax ? o.amax[0] : nullptr);
+    } else if (p.mel == MelFwd::Front) {
         launch_mel_front_x3(mag, d->stride, d->melTpk, b->d_frame_off, b->d_pool_off, o.xm, o.x0, o.mstats, o.gstat, b->B, b->T[0],
                             d->stride, st, o.amax[0]);
-        cur_max = true;
-        LAUNCHCHK(); PROF(K_MELNORM);
     } else {
-        const int Mp = d->ch[0];
-        gemm_plain(pipe, mag, d->stride, d->melT, d->stride, d->melTpk, nullptr, o.xm, Mp, b->NF, Mp, d->stride, st);
+        gemm_plain(p.pipe, mag, d->stride, d->melT, d->stride, d->melTpk, nullptr, o.xm, Mp, b->NF, Mp, d->stride, st);
         LAUNCHCHK(); PROF(K_GEMM);
-        if (d->n_mels == 128)
-            launch_mel_norm_fwd(o.xm, b->d_frame_off, b->d_pool_off, o.x0, o.mstats, o.gstat, o.mpart, o.mstride, b->B,
-                                b->max_frames, st);
-        else
+        if (p.mel_any)
             launch_mel_norm_fwd_any(o.xm, b->d_frame_off, b->d_pool_off, o.x0, o.mstats, o.gstat, o.mpart, o.mstride, b->B,
                                     b->max_frames, d->n_mels, Mp, st);
-        LAUNCHCHK(); PROF(K_MELNORM);
+        else
+            launch_mel_norm_fwd(o.xm, b->d_frame_off, b->d_pool_off, o.x0, o.mstats, o.gstat, o.mpart, o.mstride, b->B,
+                                b->max_frames, st);
     }
+    LAUNCHCHK(); PROF(K_MELNORM);
     const float* x = o.x0;
-    const int nwm = clip_tile_groups(b);
-    o.tail = 0;
-    for (int l = 0; l < d->n_layers - (skip_last ? 1 : 0); ++l) {
+    for (int l = 0; l < p.n_fwd; ++l) {
         const int ci = d->ch[l], co = d->ch[l + 1];
-        if (!d->card_arch) {
-            // architecture variant: conv + bias, then the block's norm and activation (pre-activation kept in the stash)
-            gemm_plain(pipe, x, ci, d->w[l], ci, d->wpk[l], d->bias[l], o.act[l], co, b->NP, co, ci, st);
-            LAUNCHCHK(); PROF(K_GEMM);
-            launch_norm_act_fwd(d->norm, d->act, o.act[l], b->d_frame_off, b->d_pool_off, o.rstd[l], d->nscale[l], d->nshift[l],
-                                o.stash[l], co, b->B, b->max_frames / 2, st);
-            LAUNCHCHK(); PROF(K_INLRELU);
-            x = o.act[l];
-            continue;
-        }
-        if (l == d->n_layers - 1 && co <= 64 && b->max_frames / 2 <= 320) {
-            // skinny last conv: split-K partial slabs, summed inside the fused tail kernel
+        float* amax_out = p.x_max[l + 1] ? o.amax[l + 1] : nullptr;
+        const bool emit = p.readout == Readout::X3 && l == nl - 2;   // + split-K partials of the last conv (fused read-out)
+        switch (p.fwd[l]) {
+        case Conv::SplitK:
             launch_gemm_nt_splitk(x, ci, d->w[l], ci, o.zpart, co, b->NP, co, ci, kTailSplit, st);
             LAUNCHCHK(); PROF(K_GEMM);
-            o.tail = 1;
-        } else if (nwm && co >= 128) {
-            // conv + InstanceNorm + LeakyReLU in one kernel (clip-aligned tiles)
-            if (h2_fwd(l)) {
-                const bool emit = skip_last && l == d->n_layers - 2;   // + split-K partials of the last conv
-                if (!cur_max) { launch_clip_amax(x, ci, ci, 32 * nwm, b->B, o.amax[l], st); LAUNCHCHK(); PROF(K_MISC); }
-                const bool next_h2 = l + 1 < d->n_layers && h2_fwd(l + 1);
-                launch_gemm_clip_h2(x, ci, d->wh2[l], o.amax[l], next_h2 ? o.amax[l + 1] : nullptr, d->bias[l], o.act[l], co, b->B,
-                                    nwm, b->uniform_tp, co, ci, 1, o.rstd[l], nullptr, st, emit ? d->lastpk : nullptr,
-                                    emit ? o.zpart : nullptr, d->ch[d->n_layers]);
-                cur_max = next_h2;
-                if (emit) o.zslabs = co / 128;
-                LAUNCHCHK(); PROF(K_GEMM_X3_FWD);
-                x = o.act[l];
-                continue;
-            }
-            cur_max = false;
-            if (pipe != 1 && d->wpk[l] && gemm_clip_x3_supported(nwm, co, ci, ci)) {
-                const bool emit = skip_last && l == d->n_layers - 2;   // + split-K partials of the last conv
-                if (emit) o.zslabs = co / 128;
-                launch_gemm_clip_x3(x, ci, d->wpk[l], d->bias[l], o.act[l], co, b->B, nwm, b->uniform_tp, co, ci, 1, o.rstd[l],
-                                    nullptr, st, emit ? d->lastpk : nullptr, emit ? o.zpart : nullptr, d->ch[d->n_layers]);
-                LAUNCHCHK(); PROF(K_GEMM_X3_FWD);
-            } else {
-                launch_gemm_clip(x, ci, d->w[l], ci, d->bias[l], o.act[l], co, b->B, nwm, b->uniform_tp, co, ci, 1, o.rstd[l],
-                                 nullptr, st);
-                LAUNCHCHK(); PROF(K_GEMM_CLIP_FWD);
-            }
-        } else if (h2_rag(l)) {
-            // ragged batch / long clips on the default pipe: the f16 two-term kernel, clips walked in chunks of rows
-            if (!cur_max) { launch_ragged_amax(x, ci, ci, b->d_frame_off, b->d_pool_off, b->B, o.amax[l], st); LAUNCHCHK(); PROF(K_MISC); }
-            const bool next_h2 = l + 1 < d->n_layers && h2_rag(l + 1);
-            launch_gemm_ragged_h2(x, ci, d->wh2[l], o.amax[l], next_h2 ? o.amax[l + 1] : nullptr, d->bias[l], o.act[l], co, b->B,
-                                  b->d_frame_off, b->d_pool_off, b->d_order, co, ci, 1, o.rstd[l], nullptr, st);
-            cur_max = next_h2;
+            break;
+        case Conv::ClipH2:
+            if (!p.x_max[l]) { launch_clip_amax(x, ci, ci, 32 * p.nwm, b->B, o.amax[l], st); LAUNCHCHK(); PROF(K_MISC); }
+            launch_gemm_clip_h2(x, ci, d->wh2[l], o.amax[l], amax_out, d->bias[l], o.act[l], co, b->B, p.nwm, b->uniform_tp, co, ci,
+                                1, o.rstd[l], nullptr, st, emit ? d->lastpk : nullptr, emit ? o.zpart : nullptr, d->ch[nl]);
             LAUNCHCHK(); PROF(K_GEMM_X3_FWD);
-        } else if (!nwm && pipe != 1 && co >= 128 && d->wpk[l] && gemm_clip_x3_supported(1, co, ci, ci)) {
-            // ragged batch / clips longer than the uniform kernel's tile: conv + InstanceNorm + LeakyReLU in one launch,
-            // clips walked in chunks of rows (gemm_ragged_x3_kernel)
-            launch_gemm_ragged_x3(x, ci, d->wpk[l], d->bias[l], o.act[l], co, b->B, b->d_frame_off, b->d_pool_off, b->d_order, co, ci, 1,
-                                  o.rstd[l], nullptr, st);
+            break;
+        case Conv::ClipX3:
+            launch_gemm_clip_x3(x, ci, d->wpk[l], d->bias[l], o.act[l], co, b->B, p.nwm, b->uniform_tp, co, ci, 1, o.rstd[l],
+                                nullptr, st, emit ? d->lastpk : nullptr, emit ? o.zpart : nullptr, d->ch[nl]);
             LAUNCHCHK(); PROF(K_GEMM_X3_FWD);
-        } else {
-            gemm_plain(pipe, x, ci, d->w[l], ci, d->wpk[l], d->bias[l], o.act[l], co, b->NP, co, ci, st);
+            break;
+        case Conv::ClipF32:
+            launch_gemm_clip(x, ci, d->w[l], ci, d->bias[l], o.act[l], co, b->B, p.nwm, b->uniform_tp, co, ci, 1, o.rstd[l],
+                             nullptr, st);
+            LAUNCHCHK(); PROF(K_GEMM_CLIP_FWD);
+            break;
+        case Conv::RaggedH2:
+            if (!p.x_max[l]) {
+                launch_ragged_amax(x, ci, ci, b->d_frame_off, b->d_pool_off, b->B, o.amax[l], st);
+                LAUNCHCHK(); PROF(K_MISC);
+            }
+            launch_gemm_ragged_h2(x, ci, d->wh2[l], o.amax[l], amax_out, d->bias[l], o.act[l], co, b->B, b->d_frame_off,
+                                  b->d_pool_off, b->d_order, co, ci, 1, o.rstd[l], nullptr, st);
+            LAUNCHCHK(); PROF(K_GEMM_X3_FWD);
+            break;
+        case Conv::RaggedX3:
+            launch_gemm_ragged_x3(x, ci, d->wpk[l], d->bias[l], o.act[l], co, b->B, b->d_frame_off, b->d_pool_off, b->d_order, co,
+                                  ci, 1, o.rstd[l], nullptr, st);
+            LAUNCHCHK(); PROF(K_GEMM_X3_FWD);
+            break;
+        default:
+            // conv + bias, then the block's norm and activation (a variant's pre-activation kept in the stash).  The card's
+            // InstanceNorm + LeakyReLU keeps its own kernels: norm_act_bwd_kernel<0, 1, 80> holds the clip in AGPRs too and
+            // runs one wave per SIMD where in_lrelu_bwd_reg_kernel<80> runs two
+            gemm_plain(p.pipe, x, ci, d->w[l], ci, d->wpk[l], d->bias[l], o.act[l], co, b->NP, co, ci, st);
             LAUNCHCHK(); PROF(K_GEMM);
-            launch_in_lrelu_fwd(o.act[l], b->d_frame_off, b->d_pool_off, o.rstd[l], co, b->B, b->max_frames / 2, st);
+            if (d->card_arch)
+                launch_in_lrelu_fwd(o.act[l], b->d_frame_off, b->d_pool_off, o.rstd[l], co, b->B, b->max_frames / 2, st);
+            else
+                launch_norm_act_fwd(d->norm, d->act, o.act[l], b->d_frame_off, b->d_pool_off, o.rstd[l], d->nscale[l],
+                                    d->nshift[l], o.stash[l], co, b->B, b->max_frames / 2, st);
             LAUNCHCHK(); PROF(K_INLRELU);
         }
         x = o.act[l];
@@ -1245,12 +1330,13 @@ static int det_forward(const aware_detector* d, const aware_batch* b, const floa
 }
 
 // read-out of a forward-only call: values [B][nbits]
-static void readout_forward(const aware_detector* d, const aware_batch* b, const DetBufs& o, float* values, hipStream_t st) {
+static void readout_forward(const aware_detector* d, const aware_batch* b, const DetPlan& p, const DetBufs& o, float* values,
+                            hipStream_t st) {
     const int nl = d->n_layers, C = d->ch[nl];
-    if (o.tail)
+    if (p.readout == Readout::Tail)
         launch_tail(o.zpart, kTailSplit, (size_t)b->NP * C, d->bias[nl - 1], b->d_frame_off, b->d_pool_off, nullptr, values,
                     nullptr, nullptr, nullptr, nullptr, nullptr, 0, d->nbits, b->B, b->max_frames / 2, st, nullptr, 0, C);
-    else if (C > 64)
+    else if (p.readout == Readout::Wide)
         launch_readout_wide(o.act[nl - 1], C, b->d_frame_off, b->d_pool_off, nullptr, nullptr, values, nullptr, nullptr, nullptr,
                             nullptr, nullptr, nullptr, 0, d->nbits, b->B, st, nullptr, d->final_act, false);
     else
@@ -1258,9 +1344,21 @@ static void readout_forward(const aware_detector* d, const aware_batch* b, const
                     d->nbits, b->B, st, nullptr, d->final_act, C);
 }
 
+// aware_detect: the detector's buffers, the band magnitudes and the analysis's partial maxima
+static void carve_detect(Carver& c, const aware_batch* b, const aware_detector* d, DetBufs& o, float*& mag,
+                         unsigned long long*& pmax) {
+    carve_det(c, b, d, o);
+    mag = c.take<float>((size_t)b->NF * d->stride);
+    pmax = c.take<unsigned long long>((size_t)b->B * b->pstride);
+}
 extern "C" size_t aware_detect_workspace_bytes(const aware_batch* b, const aware_detector* d) {
     if (!b || !d) return 0;
-    return det_bytes(b, d) + (size_t)b->NF * d->stride * sizeof(float) + aware_batch_scratch_bytes(b) + 1024;
+    Carver c(nullptr, 0);
+    DetBufs o;
+    float* mag;
+    unsigned long long* pmax;
+    carve_detect(c, b, d, o, mag, pmax);
+    return c.off;
 }
 
 extern "C" int aware_detector_forward(const aware_detector* d, const aware_batch* b, const float* mag, float* values,
@@ -1272,9 +1370,10 @@ extern "C" int aware_detector_forward(const aware_detector* d, const aware_batch
     carve_det(c, b, d, o);
     if (!c.ok) return AWARE_E_WORKSPACE;
     for (int l = 0; l < d->n_layers; ++l) o.stash[l] = nullptr;      // forward only: no backward reads the pre-activations
-    int rc = det_forward(d, b, mag, o, st);
+    const DetPlan p = det_plan(d, b, 0, 1, false, false, false);
+    int rc = det_forward(d, b, p, mag, o, st);
     if (rc) return rc;
-    readout_forward(d, b, o, values, st);
+    readout_forward(d, b, p, o, values, st);
     LAUNCHCHK();
     return AWARE_OK;
 }
@@ -1289,16 +1388,17 @@ extern "C" int aware_detect(const aware_plan* plan, const aware_detector* d, con
     hipStream_t st = (hipStream_t)stream;
     Carver c(workspace, workspace_bytes);
     DetBufs o;
-    carve_det(c, b, d, o);
-    float* mag = c.take<float>((size_t)b->NF * d->stride);
-    unsigned long long* pmax = c.take<unsigned long long>((size_t)b->B * b->pstride);
+    float* mag;
+    unsigned long long* pmax;
+    carve_detect(c, b, d, o, mag, pmax);
     if (!c.ok) return AWARE_E_WORKSPACE;
     for (int l = 0; l < d->n_layers; ++l) o.stash[l] = nullptr;
     int rc = aware_stft_band(plan, b, audio, 1, mag, nullptr, pmax, stream);
     if (rc) return rc;
-    rc = det_forward(d, b, mag, o, st);
+    const DetPlan p = det_plan(d, b, 0, 1, false, false, false);
+    rc = det_forward(d, b, p, mag, o, st);
     if (rc) return rc;
-    readout_forward(d, b, o, values, st);
+    readout_forward(d, b, p, o, values, st);
     LAUNCHCHK();
     return AWARE_OK;
 }
@@ -1306,7 +1406,6 @@ extern "C" int aware_detect(const aware_plan* plan, const aware_detector* d, con
 // Detector forward (multibit_detector_net.py:109-140), loss / gradient seed at the read-out, and the backward pass
 // down to dL/d(band magnitudes) (data gradients only: the weights are frozen, multibit_embedder.py:76-77).
 struct DetGradCtx {
-    int pipe = 0, readout = 0;
     const float* target = nullptr;    // [B][n_bits]: bipolar watermark, or dL/dpred when loss_kind == AWARE_LOSS_EXTERNAL
     int loss_kind = 0;
     float* loss = nullptr;            // [B]
@@ -1314,99 +1413,56 @@ struct DetGradCtx {
     int* improved = nullptr;
     int* step = nullptr;              // device step counter to advance, or null
     float *d1 = nullptr, *d2 = nullptr;   // gradient ping-pong [NP][maxc]
-    float* gmag = nullptr;            // out: [NF][256]
+    float* gmag = nullptr;            // out: [NF][stride] (not written when the plan has no mag_grad: dL/d(mel) is left in
+                                      // DetBufs::xm)
     const float* loss_add = nullptr;  // [B] per-clip term added to the loss before the best-loss bookkeeping (L1 part), or null
     // EXTENSION (detector training): also the parameter gradients dL/dW_l [Cout][Cin], dL/db_l [Cout]; tr1 / tr2 are
-    // scratch for the transposed operands, [maxc][NP] each.  Forces the three-kernel read-out (it writes dL/dZ of the
-    // last block to memory).
+    // scratch for the transposed operands, [maxc][NP] each (plan made with training = true: the three-kernel read-out, which
+    // writes dL/dZ of the last block to memory)
     float* const* wgrad = nullptr;
     float* const* bgrad = nullptr;
     float *tr1 = nullptr, *tr2 = nullptr;
-    // the caller expands dL/d(mel) (left in DetBufs::xm) to dL/d|S| itself (streaming synthesis adjoint, two taps per bin):
-    // the K = 128 GEMM into gmag is skipped
-    bool mel_grad_only = false;
-    bool xm_ready = false;            // DetBufs::xm holds the raw mel tile on entry (det_forward)
 };
-static int det_forward_backward(const aware_detector* d, const aware_batch* b, const float* mag, DetBufs& db,
+static int det_forward_backward(const aware_detector* d, const aware_batch* b, const DetPlan& p, const float* mag, DetBufs& db,
                                 const DetGradCtx& G, hipStream_t st) {
     const int nl = d->n_layers;
-    const int nwm = clip_tile_groups(b);
-    // one kernel for the last conv block, the BRH head, the loss, their backward and the data gradient of the last
-    // conv (uniform batches, bf16x3 configuration); otherwise split-K GEMM + tail kernel + data-gradient GEMM
-    const int pipe = G.pipe;
-    const bool fused_readout = d->card_arch && G.readout == 0 && !G.wgrad && pipe != 1 && nwm && nl >= 2 && d->lastpk && G.target &&
-                               d->ch[nl] == 2 * d->nbits && readout_x3_supported(nwm, d->ch[nl - 1], d->ch[nl]) && d->wpk[nl - 2] &&
-                               gemm_clip_x3_supported(nwm, d->ch[nl - 1], d->ch[nl - 2], d->ch[nl - 2]);
-    int rc = det_forward(d, b, mag, db, st, pipe, fused_readout, G.xm_ready);
+    int rc = det_forward(d, b, p, mag, db, st);
     if (rc) return rc;
     float* dA = G.d1;
     float* dB = G.d2;
-    bool dz_ready = false;      // dA already holds dL/dZ of layer l (fused into the producing kernel)
-    int l_top = nl - 1;         // first layer the backward loop below still has to differentiate
-    bool last_k64 = false;      // dL/dZ of the last block was written with a row pitch of 64
-    bool mel_bwd_done = false;
-    const bool mel_fused = mel_front_applies(d, b, pipe);
-    // data-gradient GEMMs of a uniform batch that fills the chip: the f16 two-term kernel; gA / gB travel with dA / dB and hold
-    // the partial maxima of the gradient in them (g_cur: whether gA is current)
-    float* gA = db.gmax[0];
-    float* gB = db.gmax[1];
-    bool g_cur = false;
-    auto h2_bwd = [&](int l) {
-        return pipe == 0 && nwm && l > 0 && d->wTh2[l] && d->ch[l] >= 128 && (d->ch[l] / 128) * b->B >= kH2MinGrid &&
-               gemm_clip_h2_supported(nwm, d->ch[l], d->ch[l + 1], d->ch[l + 1]);
-    };
-    auto h2_rag_bwd = [&](int l) {
-        return pipe == 0 && !nwm && l > 0 && l < nl && d->wTh2[l] && d->ch[l] >= 128 && d->ch[l + 1] >= 128 &&
-               gemm_clip_h2_supported(1, d->ch[l], d->ch[l + 1], d->ch[l + 1]);
-    };
-    if (fused_readout) {
-        launch_readout_x3(db.act[nl - 2], d->ch[nl - 1], db.zpart, db.zslabs, d->bias[nl - 1], d->lastTpk,
-                          db.rstd[nl - 2], G.target, db.pred, G.loss, G.best_loss, G.improved, G.step, dA, b->B,
-                          nwm, b->uniform_tp, d->ch[nl], d->nbits, G.loss_kind, st, G.loss_add, dB,
-                          h2_bwd(nl - 2) ? gA : nullptr);
-        g_cur = h2_bwd(nl - 2);
+    // maxima of dL/dZ_l for an f16 two-term data-gradient GEMM (written by the kernel before it, or read here first)
+    auto gmax = [&](int l, bool wanted) { return wanted ? db.gmax[l & 1] : nullptr; };
+    switch (p.readout) {
+    case Readout::X3:
         // (dB, the other half of the gradient ping-pong, is free until the next data-gradient GEMM writes it: it holds the
         //  read-out's fragment image, readout_x3_image_bytes = 36 KB per 3 s clip, far below NP * maxc floats)
-        dz_ready = true;
-        l_top = nl - 2;
-    } else if (db.tail) {
-        // ragged batch on the bf16x3 pipe: dL/dZ of the last block with a pitch of 64 (zero K padding), so that its data
-        // gradient runs on the ragged conv kernel with the previous block's InstanceNorm + LeakyReLU backward fused
-        last_k64 = !nwm && pipe != 1 && !G.wgrad && nl >= 2 && d->lastTpk && d->ch[nl] <= 64 && d->ch[nl - 1] % 128 == 0;
+        launch_readout_x3(db.act[nl - 2], d->ch[nl - 1], db.zpart, d->ch[nl - 1] / 128, d->bias[nl - 1], d->lastTpk,
+                          db.rstd[nl - 2], G.target, db.pred, G.loss, G.best_loss, G.improved, G.step, dA, b->B, p.nwm,
+                          b->uniform_tp, d->ch[nl], d->nbits, G.loss_kind, st, G.loss_add, dB, gmax(nl - 2, p.g_max[nl - 2]));
+        break;
+    case Readout::Tail:
         launch_tail(db.zpart, kTailSplit, (size_t)b->NP * d->ch[nl], d->bias[nl - 1], b->d_frame_off, b->d_pool_off,
                     G.target, db.pred, G.loss, G.best_loss, G.improved, dA, G.step, G.loss_kind, d->nbits, b->B,
-                    b->max_frames / 2, st, G.loss_add, last_k64 ? 64 : 0, d->ch[nl]);
-        dz_ready = true;
-    } else if (d->ch[nl] > 64) {
-        // wide last block (payloads above 32 bits): one read-out kernel per clip.  On the card it writes dL/dZ of the last
-        // block (InstanceNorm + LeakyReLU backward folded in) and, when the next data-gradient GEMM runs on the f16 two-term
-        // kernel, the per-clip maxima of that gradient; on the staged route it writes dL/dA for launch_norm_act_bwd
-        const bool card = d->card_arch;
-        const bool gm = card && (h2_bwd(nl - 1) || h2_rag_bwd(nl - 1));
+                    b->max_frames / 2, st, G.loss_add, p.tail_k64 ? 64 : 0, d->ch[nl]);
+        break;
+    case Readout::Wide:
         launch_readout_wide(db.act[nl - 1], d->ch[nl], b->d_frame_off, b->d_pool_off, db.rstd[nl - 1], G.target, db.pred, G.loss,
-                            G.best_loss, G.improved, dA, gm ? gA : nullptr, G.step, G.loss_kind, d->nbits, b->B, st, G.loss_add,
-                            d->final_act, card);
-        g_cur = gm;
-        dz_ready = card;
-    } else {
+                            G.best_loss, G.improved, dA, gmax(nl - 1, p.g_max[nl - 1]), G.step, G.loss_kind, d->nbits, b->B, st,
+                            G.loss_add, d->final_act, p.dz[nl - 1]);
+        break;
+    default:
         launch_head(db.act[nl - 1], b->d_frame_off, b->d_pool_off, G.target, db.pred, G.loss, G.best_loss,
                     G.improved, dA, G.step, G.loss_kind, d->nbits, b->B, st, G.loss_add, d->final_act, d->ch[nl]);
     }
     LAUNCHCHK(); PROF(K_HEAD);
-    for (int l = l_top; l >= 0; --l) {
+    for (int l = p.top; l >= 0; --l) {
         const int ci = d->ch[l], co = d->ch[l + 1];
-        if (!d->card_arch) {
-            // architecture variant (staged route): backward of the block's activation and norm, then the data-gradient GEMM
-            launch_norm_act_bwd(d->norm, d->act, dA, db.act[l], db.stash[l], b->d_frame_off, b->d_pool_off, db.rstd[l],
-                                d->nscale[l], co, b->B, b->max_frames / 2, st);
-            LAUNCHCHK(); PROF(K_INLRELU);
-            gemm_plain(pipe, dA, co, d->wT[l], co, d->wTpk[l], nullptr, dB, ci, b->NP, ci, co, st);
-            LAUNCHCHK(); PROF(K_GEMM);
-            float* t = dA; dA = dB; dB = t;
-            continue;
-        }
-        if (!dz_ready) {
-            launch_in_lrelu_bwd(dA, db.act[l], b->d_frame_off, b->d_pool_off, db.rstd[l], co, b->B, b->max_frames / 2, st);
+        if (!p.dz[l]) {
+            if (d->card_arch)
+                launch_in_lrelu_bwd(dA, db.act[l], b->d_frame_off, b->d_pool_off, db.rstd[l], co, b->B, b->max_frames / 2, st);
+            else
+                launch_norm_act_bwd(d->norm, d->act, dA, db.act[l], db.stash[l], b->d_frame_off, b->d_pool_off, db.rstd[l],
+                                    d->nscale[l], co, b->B, b->max_frames / 2, st);
             LAUNCHCHK(); PROF(K_INLRELU);
         }
         if (G.wgrad && G.wgrad[l]) {
@@ -1428,87 +1484,99 @@ static int det_forward_backward(const aware_detector* d, const aware_batch* b, c
             }
             LAUNCHCHK(); PROF(K_MISC);
         }
-        if (nwm && l > 0 && ci >= 128) {
-            // data-gradient GEMM whose epilogue is the backward of block l-1's InstanceNorm+LeakyReLU
-            dz_ready = true;
-            if (h2_bwd(l)) {
-                if (!g_cur) { launch_clip_amax(dA, co, co, 32 * nwm, b->B, gA, st); LAUNCHCHK(); PROF(K_MISC); }
-                const bool next_h2 = h2_bwd(l - 1);
-                launch_gemm_clip_h2(dA, co, d->wTh2[l], gA, next_h2 ? gB : nullptr, nullptr, dB, ci, b->B, nwm, b->uniform_tp, ci, co, 2,
-                                    db.rstd[l - 1], db.act[l - 1], st);
-                g_cur = next_h2;
-                LAUNCHCHK(); PROF(K_GEMM_X3_BWD);
-                float* t = dA; dA = dB; dB = t;
-                t = gA; gA = gB; gB = t;
-                continue;
-            }
-            g_cur = false;
-            if (pipe != 1 && d->wTpk[l] && gemm_clip_x3_supported(nwm, ci, co, co)) {
-                launch_gemm_clip_x3(dA, co, d->wTpk[l], nullptr, dB, ci, b->B, nwm, b->uniform_tp, ci, co, 2,
-                                    db.rstd[l - 1], db.act[l - 1], st);
-                LAUNCHCHK(); PROF(K_GEMM_X3_BWD);
-            } else {
-                launch_gemm_clip(dA, co, d->wT[l], co, nullptr, dB, ci, b->B, nwm, b->uniform_tp, ci, co, 2, db.rstd[l - 1],
-                                 db.act[l - 1], st);
-                LAUNCHCHK(); PROF(K_GEMM_CLIP_BWD);
-            }
-        } else if (l == nl - 1 && last_k64) {
-            dz_ready = true;
-            const bool next_h2 = h2_rag_bwd(l - 1);
+        // the data gradient of block l; every kind but Plain also runs the backward of block l-1's norm and activation
+        float* g_out = l > 0 ? gmax(l - 1, p.g_max[l - 1]) : nullptr;
+        switch (p.bwd[l]) {
+        case Conv::ClipH2:
+            if (!p.g_max[l]) { launch_clip_amax(dA, co, co, 32 * p.nwm, b->B, db.gmax[l & 1], st); LAUNCHCHK(); PROF(K_MISC); }
+            launch_gemm_clip_h2(dA, co, d->wTh2[l], db.gmax[l & 1], g_out, nullptr, dB, ci, b->B, p.nwm, b->uniform_tp, ci, co, 2,
+                                db.rstd[l - 1], db.act[l - 1], st);
+            LAUNCHCHK(); PROF(K_GEMM_X3_BWD);
+            break;
+        case Conv::ClipX3:
+            launch_gemm_clip_x3(dA, co, d->wTpk[l], nullptr, dB, ci, b->B, p.nwm, b->uniform_tp, ci, co, 2, db.rstd[l - 1],
+                                db.act[l - 1], st);
+            LAUNCHCHK(); PROF(K_GEMM_X3_BWD);
+            break;
+        case Conv::ClipF32:
+            launch_gemm_clip(dA, co, d->wT[l], co, nullptr, dB, ci, b->B, p.nwm, b->uniform_tp, ci, co, 2, db.rstd[l - 1],
+                             db.act[l - 1], st);
+            LAUNCHCHK(); PROF(K_GEMM_CLIP_BWD);
+            break;
+        case Conv::ReadoutGrad:
             launch_readout_grad_ragged_x3(db.act[l - 1], ci, dA, d->lastTpk, db.rstd[l - 1], dB, b->d_frame_off, b->d_pool_off,
-                                          b->d_order, b->B, st, next_h2 ? gB : nullptr);
-            g_cur = next_h2;
+                                          b->d_order, b->B, st, g_out);
             LAUNCHCHK(); PROF(K_GEMM_X3_BWD);
-            float* t2 = gA; gA = gB; gB = t2;
-        } else if (h2_rag_bwd(l)) {
-            // ragged batch: data-gradient GEMM + backward of block l-1's InstanceNorm + LeakyReLU in one launch (f16 two-term)
-            dz_ready = true;
-            if (!g_cur) { launch_ragged_amax(dA, co, co, b->d_frame_off, b->d_pool_off, b->B, gA, st); LAUNCHCHK(); PROF(K_MISC); }
-            const bool next_h2 = h2_rag_bwd(l - 1);
-            launch_gemm_ragged_h2(dA, co, d->wTh2[l], gA, next_h2 ? gB : nullptr, nullptr, dB, ci, b->B, b->d_frame_off, b->d_pool_off,
+            break;
+        case Conv::RaggedH2:
+            if (!p.g_max[l]) {
+                launch_ragged_amax(dA, co, co, b->d_frame_off, b->d_pool_off, b->B, db.gmax[l & 1], st);
+                LAUNCHCHK(); PROF(K_MISC);
+            }
+            launch_gemm_ragged_h2(dA, co, d->wTh2[l], db.gmax[l & 1], g_out, nullptr, dB, ci, b->B, b->d_frame_off, b->d_pool_off,
                                   b->d_order, ci, co, 2, db.rstd[l - 1], db.act[l - 1], st);
-            g_cur = next_h2;
             LAUNCHCHK(); PROF(K_GEMM_X3_BWD);
-            float* t2 = gA; gA = gB; gB = t2;
-        } else if (!nwm && pipe != 1 && l > 0 && ci >= 128 && d->wTpk[l] && gemm_clip_x3_supported(1, ci, co, co)) {
-            // ragged batch: data-gradient GEMM + backward of block l-1's InstanceNorm + LeakyReLU in one launch
-            dz_ready = true;
+            break;
+        case Conv::RaggedX3:
             launch_gemm_ragged_x3(dA, co, d->wTpk[l], nullptr, dB, ci, b->B, b->d_frame_off, b->d_pool_off, b->d_order, ci, co, 2,
                                   db.rstd[l - 1], db.act[l - 1], st);
             LAUNCHCHK(); PROF(K_GEMM_X3_BWD);
-        } else if (l == 0 && mel_fused && dz_ready && !G.wgrad && d->wTpk[0] && co % 64 == 0 && d->n_mels == 128) {
-            // large uniform batch: block 0's data gradient and the backward of the mel block's normalisations in one launch
+            break;
+        case Conv::MelBack:
             launch_mel_back_x3(dA, co, d->wTpk[0], b->d_frame_off, b->d_pool_off, db.xm, db.mstats, db.gstat, b->B, b->T[0], co, st);
             LAUNCHCHK(); PROF(K_MELNORM);
-            mel_bwd_done = true;
-        } else {
-            gemm_plain(pipe, dA, co, d->wT[l], co, d->wTpk[l], nullptr, dB, ci, b->NP, ci, co, st);
-            dz_ready = false;
+            break;
+        default:
+            gemm_plain(p.pipe, dA, co, d->wT[l], co, d->wTpk[l], nullptr, dB, ci, b->NP, ci, co, st);
             LAUNCHCHK(); PROF(K_GEMM);
         }
         float* t = dA; dA = dB; dB = t;
     }
     const int Mp = d->ch[0];
-    if (!mel_bwd_done) {
-        if (d->n_mels == 128)
-            launch_mel_norm_bwd(dA, db.xm, b->d_frame_off, b->d_pool_off, db.mstats, db.gstat, db.mpart, db.mstride, b->B,
-                                b->max_frames, st);
-        else
+    if (p.bwd[0] != Conv::MelBack) {
+        if (p.mel_any)
             launch_mel_norm_bwd_any(dA, db.xm, b->d_frame_off, b->d_pool_off, db.mstats, db.gstat, db.mpart, db.mstride, b->B,
                                     b->max_frames, d->n_mels, Mp, st);
+        else
+            launch_mel_norm_bwd(dA, db.xm, b->d_frame_off, b->d_pool_off, db.mstats, db.gstat, db.mpart, db.mstride, b->B,
+                                b->max_frames, st);
         LAUNCHCHK(); PROF(K_MELNORM);
     }
-    if (!G.mel_grad_only) {
-        gemm_plain(pipe, db.xm, Mp, d->melB, Mp, d->melBpk, nullptr, G.gmag, d->stride, b->NF, d->stride, Mp, st);
+    if (p.mag_grad) {
+        gemm_plain(p.pipe, db.xm, Mp, d->melB, Mp, d->melBpk, nullptr, G.gmag, d->stride, b->NF, d->stride, Mp, st);
         LAUNCHCHK(); PROF(K_GEMM);
     }
     return AWARE_OK;
 }
 
+// aware_detector_backward, and with training the detector-training entry points: the gradient ping-pong, the transposed
+// operands of the weight gradients, and the per-clip losses / dL/d|S| where the caller passes none (own_*)
+static void carve_grad(Carver& c, const aware_batch* b, const aware_detector* d, DetBufs& o, DetGradCtx& G, bool training,
+                       bool own_loss, bool own_gmag) {
+    carve_det(c, b, d, o);
+    G.d1 = c.take<float>((size_t)b->NP * d->maxc);
+    G.d2 = c.take<float>((size_t)b->NP * d->maxc);
+    if (training) {
+        G.tr1 = c.take<float>((size_t)b->NP * d->maxc);
+        G.tr2 = c.take<float>((size_t)b->NP * d->maxc);
+    }
+    if (own_loss) G.loss = c.take<float>(b->B);
+    if (own_gmag) G.gmag = c.take<float>((size_t)b->NF * d->stride);
+}
+// training: the larger of the two entry points' own buffers, dL/d|S| of aware_detector_train_gradients with grad_mag NULL
+// (aware_detector_weight_gradients carves the per-clip losses instead, B floats)
+static size_t grad_bytes(const aware_batch* b, const aware_detector* d, bool training) {
+    Carver c(nullptr, 0);
+    DetBufs o;
+    DetGradCtx G;
+    carve_grad(c, b, d, o, G, training, !training, training);
+    return c.off;
+}
+
 // detector forward + backward for the differentiable plug-in seam: values = net(mag), grad_mag = (d values / d mag)^T grad_values
 extern "C" size_t aware_detector_backward_workspace_bytes(const aware_batch* b, const aware_detector* d) {
     if (!b || !d) return 0;
-    return det_bytes(b, d) + (size_t)b->NP * d->maxc * sizeof(float) * 2 + (size_t)b->B * 8 * sizeof(float) + 4096;
+    return grad_bytes(b, d, false);
 }
 extern "C" int aware_detector_backward(const aware_detector* d, const aware_batch* b, const float* mag,
                                        const float* grad_values, float* values, float* grad_mag, void* workspace,
@@ -1517,14 +1585,11 @@ extern "C" int aware_detector_backward(const aware_detector* d, const aware_batc
     hipStream_t st = (hipStream_t)stream;
     Carver c(workspace, workspace_bytes);
     DetBufs o;
-    carve_det(c, b, d, o);
     DetGradCtx G;
-    G.d1 = c.take<float>((size_t)b->NP * d->maxc);
-    G.d2 = c.take<float>((size_t)b->NP * d->maxc);
-    G.loss = c.take<float>(b->B);
+    carve_grad(c, b, d, o, G, false, true, false);
     if (!c.ok) return AWARE_E_WORKSPACE;
     G.target = grad_values; G.loss_kind = AWARE_LOSS_EXTERNAL; G.gmag = grad_mag;
-    int rc = det_forward_backward(d, b, mag, o, G, st);
+    int rc = det_forward_backward(d, b, det_plan(d, b, 0, 0, false, false, false), mag, o, G, st);
     if (rc) return rc;
     if (values) HIPCHK(hipMemcpyAsync(values, o.pred, (size_t)b->B * d->nbits * sizeof(float), hipMemcpyDeviceToDevice, st));
     return AWARE_OK;
@@ -1537,8 +1602,7 @@ extern "C" int aware_detector_backward(const aware_detector* d, const aware_batc
 // pointers ([Cout][Cin] and [Cout] f32; entries may be NULL).
 extern "C" size_t aware_detector_train_workspace_bytes(const aware_batch* b, const aware_detector* d) {
     if (!b || !d) return 0;
-    return aware_detector_backward_workspace_bytes(b, d) + (size_t)b->NP * d->maxc * sizeof(float) * 2 +
-           (size_t)b->NF * d->stride * sizeof(float) + 2048;
+    return grad_bytes(b, d, true);
 }
 static int detector_train_core(const aware_detector* d, const aware_batch* b, const float* mag, const float* target, int loss_kind,
                                float* loss_out, float* values, float* grad_mag, float* const* grad_weights,
@@ -1575,20 +1639,16 @@ static int detector_train_core(const aware_detector* d, const aware_batch* b, co
     hipStream_t st = (hipStream_t)stream;
     Carver c(workspace, workspace_bytes);
     DetBufs o;
-    carve_det(c, b, d, o);
     DetGradCtx G;
-    G.d1 = c.take<float>((size_t)b->NP * d->maxc);
-    G.d2 = c.take<float>((size_t)b->NP * d->maxc);
-    G.tr1 = c.take<float>((size_t)b->NP * d->maxc);
-    G.tr2 = c.take<float>((size_t)b->NP * d->maxc);
-    G.loss = loss_out ? loss_out : c.take<float>(b->B);
-    if (!grad_mag) grad_mag = c.take<float>((size_t)b->NF * d->stride);
+    G.loss = loss_out; G.gmag = grad_mag;
+    carve_grad(c, b, d, o, G, true, !loss_out, !grad_mag);
     if (!c.ok) return AWARE_E_WORKSPACE;
     // padding rows of the gradient ping-pong buffers take part in the row contraction: keep them finite
     HIPCHK(hipMemsetAsync(G.d1, 0, (size_t)b->NP * d->maxc * sizeof(float) * 2, st));
-    G.target = target; G.loss_kind = loss_kind; G.gmag = grad_mag;
-    G.wgrad = grad_weights; G.bgrad = grad_biases; G.readout = 1; G.pipe = 1;      // exact-f32 pipe for the training step
-    int rc = det_forward_backward(d, b, mag, o, G, st);
+    G.target = target; G.loss_kind = loss_kind;
+    G.wgrad = grad_weights; G.bgrad = grad_biases;
+    // exact-f32 pipe and the three-kernel read-out for the training step
+    int rc = det_forward_backward(d, b, det_plan(d, b, 1, 1, true, false, false), mag, o, G, st);
     if (rc) return rc;
     if (values) HIPCHK(hipMemcpyAsync(values, o.pred, (size_t)b->B * d->nbits * sizeof(float), hipMemcpyDeviceToDevice, st));
     return AWARE_OK;
@@ -1638,22 +1698,39 @@ struct aware_embed {
     } opt;
 };
 
-static size_t embed_bytes(const aware_batch* b, const aware_detector* d, int iters) {
-    size_t bytes = det_bytes(b, d);
-    bytes += (size_t)b->NF * d->stride * sizeof(float) * 8;
-    bytes += (size_t)b->NF * d->stride * sizeof(cf) * 2;
-    bytes += (size_t)b->NS * sizeof(float) * 3;
-    bytes += (size_t)b->B * 1024 * sizeof(float);
-    bytes += (size_t)b->NF * d->stride * sizeof(float) + (size_t)b->B * b->pstride * 8 + (size_t)b->B * sizeof(float) + 1024;   // L1 term
-    bytes += (size_t)b->NP * d->maxc * sizeof(float) * 2;
-    bytes += (size_t)b->B * (3 * d->nbits + 8) * sizeof(float);
-    bytes += (size_t)(iters + 1) * sizeof(float4) + (size_t)iters * 5 * sizeof(double) + (size_t)b->B * 4 * sizeof(double) + 1024;
-    bytes += (size_t)b->B * b->pstride * 8 * 3;
-    return bytes + 256 * 40;
+// the embed loop's workspace: the detector's buffers, then the loop state; iters: num_iterations, l1: the L1 term's buffers
+static void carve_embed(Carver& c, const aware_batch* b, const aware_detector* det, int iters, bool l1, aware_embed* e) {
+    carve_det(c, b, det, e->db);
+    const size_t nsp = (size_t)b->NF * det->stride;
+    e->coef = c.take<float>(nsp); e->lo = c.take<float>(nsp); e->hi = c.take<float>(nsp);
+    e->mom = c.take<float>(nsp); e->vel = c.take<float>(nsp); e->best = c.take<float>(nsp);
+    e->mag = c.take<float>(nsp); e->gmag = c.take<float>(nsp);
+    e->P = c.take<cf>(nsp); e->U = c.take<cf>(nsp);
+    e->yraw = c.take<float>(b->NS); e->oob = c.take<float>(b->NS); e->gy = c.take<float>(b->NS);
+    e->gpad = c.take<float>((size_t)b->B * 1024);
+    e->d1 = c.take<float>((size_t)b->NP * det->maxc); e->d2 = c.take<float>((size_t)b->NP * det->maxc);
+    e->loss = c.take<float>(b->B); e->best_loss = c.take<float>(b->B);
+    e->target = c.take<float>((size_t)b->B * det->nbits);
+    e->improved = c.take<int>(b->B); e->step = c.take<int>(4);
+    e->sched = c.take<float4>(iters + 1);
+    e->pmaxA = c.take<unsigned long long>((size_t)b->B * b->pstride);
+    e->pmaxY = c.take<unsigned long long>((size_t)b->B * b->pstride);
+    e->pdot = c.take<double>((size_t)b->B * b->pstride);
+    e->c0 = c.take<float>(nsp);
+    e->opt.d_tab = c.take<double>((size_t)iters * 5);
+    e->opt.d_lr = c.take<double>(b->B);
+    e->opt.d_state = c.take<double>((size_t)b->B * 3);
+    if (l1) {
+        e->pl1 = c.take<double>((size_t)b->B * b->pstride);
+        e->l1term = c.take<float>(b->B);
+    }
 }
 extern "C" size_t aware_embed_workspace_bytes(const aware_batch* b, const aware_detector* d) {
     if (!b || !d) return 0;
-    return embed_bytes(b, d, 4096);
+    Carver c(nullptr, 0);
+    aware_embed e;
+    carve_embed(c, b, d, 4096, true, &e);      // the largest loop aware_embed_create accepts, with the L1 term
+    return c.off;
 }
 
 // torch.optim.NAdam's per-step scalars (torch/optim/nadam.py _single_tensor_nadam): mu_product lives in a float32
@@ -1736,37 +1813,16 @@ extern "C" int aware_embed_create(aware_embed** out, const aware_plan* plan, con
     if (cfg->dsp_path < 0 || cfg->dsp_path > 1) return AWARE_E_BADARG;
     // the detector's mel operands have the layout of the plan it was created for
     if (det->band_lo != plan->dev.band_lo || det->nband != plan->dev.nband || det->stride != plan->dev.stride) return AWARE_E_BADARG;
+    // the L1 term lives in the streaming DSP kernels only
+    const bool l1 = cfg->loss == AWARE_LOSS_PUSH_L1;
+    if (l1 && (cfg->dsp_path != 0 || !stream_supported(plan->dev))) return AWARE_E_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
     aware_embed* e = new aware_embed();
     e->plan = plan; e->det = det; e->b = b; e->cfg = *cfg;
     Carver c(workspace, workspace_bytes);
-    carve_det(c, b, det, e->db);
-    const size_t nsp = (size_t)b->NF * plan->dev.stride;
-    e->coef = c.take<float>(nsp); e->lo = c.take<float>(nsp); e->hi = c.take<float>(nsp);
-    e->mom = c.take<float>(nsp); e->vel = c.take<float>(nsp); e->best = c.take<float>(nsp);
-    e->mag = c.take<float>(nsp); e->gmag = c.take<float>(nsp);
-    e->P = c.take<cf>(nsp); e->U = c.take<cf>(nsp);
-    e->yraw = c.take<float>(b->NS); e->oob = c.take<float>(b->NS); e->gy = c.take<float>(b->NS);
-    e->gpad = c.take<float>((size_t)b->B * 1024);
-    e->d1 = c.take<float>((size_t)b->NP * det->maxc); e->d2 = c.take<float>((size_t)b->NP * det->maxc);
-    e->loss = c.take<float>(b->B); e->best_loss = c.take<float>(b->B);
-    e->target = c.take<float>((size_t)b->B * det->nbits);
-    e->improved = c.take<int>(b->B); e->step = c.take<int>(4);
-    e->sched = c.take<float4>(cfg->num_iterations + 1);
-    e->pmaxA = c.take<unsigned long long>((size_t)b->B * b->pstride);
-    e->pmaxY = c.take<unsigned long long>((size_t)b->B * b->pstride);
-    e->pdot = c.take<double>((size_t)b->B * b->pstride);
-    e->c0 = c.take<float>(nsp);
-    e->opt.d_tab = c.take<double>((size_t)cfg->num_iterations * 5);
-    e->opt.d_lr = c.take<double>(b->B);
-    e->opt.d_state = c.take<double>((size_t)b->B * 3);
-    if (cfg->loss == AWARE_LOSS_PUSH_L1) {
-        // the L1 term lives in the streaming DSP kernels only
-        if (cfg->dsp_path != 0 || !stream_supported(plan->dev)) { delete e; return AWARE_E_UNSUPPORTED; }
-        e->pl1 = c.take<double>((size_t)b->B * b->pstride);
-        e->l1term = c.take<float>(b->B);
-    }
+    carve_embed(c, b, det, cfg->num_iterations, l1, e);
     if (!c.ok) { delete e; return AWARE_E_WORKSPACE; }
+    const size_t nsp = (size_t)b->NF * plan->dev.stride;
     // columns nband..stride-1 of every spectral row are padding: zeroed once here, never written by the loop kernels
     HIPCHK(hipMemsetAsync(e->mag, 0, nsp * sizeof(float), st));
     HIPCHK(hipMemsetAsync(e->U, 0, nsp * sizeof(cf), st));
@@ -1929,16 +1985,15 @@ static int embed_iteration(aware_embed* e, hipStream_t st, int do_step, float* g
     LAUNCHCHK(); PROF(K_ANALYSIS);
     // :107 detector forward, :109 loss, :120-122 best tracking, :111 backward through the detector
     DetGradCtx G;
-    G.pipe = e->cfg.conv_pipe; G.readout = e->cfg.readout; G.target = e->target; G.loss_kind = e->cfg.loss;
+    G.target = e->target; G.loss_kind = e->cfg.loss;
     G.loss = e->loss; G.d1 = e->d1; G.d2 = e->d2; G.gmag = e->gmag; G.loss_add = e->l1term;
     G.step = do_step ? e->step : nullptr;               // the read-out kernel advances the step counter
     // aware_embed_gradient (do_step == 0) leaves the best-loss bookkeeping alone: the reference snapshots only
     // inside the optimiser loop (multibit_embedder.py:120-122)
     G.best_loss = do_step ? e->best_loss : nullptr;
     G.improved = do_step ? e->improved : nullptr;
-    G.mel_grad_only = mel_taps;
-    G.xm_ready = mel_fold;
-    int rc = det_forward_backward(d, b, e->mag, e->db, G, st);
+    const DetPlan p = det_plan(d, b, e->cfg.conv_pipe, e->cfg.readout, false, mel_fold, mel_taps);
+    int rc = det_forward_backward(d, b, p, e->mag, e->db, G, st);
     if (rc) return rc;
     // backward through |.|, STFT, reflect padding
     SynthLaunch SA;

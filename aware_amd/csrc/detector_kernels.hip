@@ -1480,7 +1480,6 @@ void launch_readout_wide(const float* A, int Cp, const int* frame_off, const int
 // keeps the clip's [T][128] tile in registers (thread = channel c, pooled rows g, g+4, ...: the frame pair
 // (2tp, 2tp+1)), so the statistics need no second pass over memory and no partial buffers.
 // ---------------------------------------------------------------------------------
-constexpr int kMelClipFrames = 192;
 constexpr int kMelClipR = kMelClipFrames / 8;       // frame pairs per thread
 
 // sum over the 4 row groups of a channel (threads c, c+128, c+256, c+384), result for every thread
@@ -1614,18 +1613,16 @@ __global__ __launch_bounds__(512) void mel_norm_clip_bwd_kernel(const float* __r
     }
 }
 
-// returns true when amax_out was written (single-kernel form only)
-bool launch_mel_norm_fwd(const float* xm, const int* frame_off, const int* pool_off, float* x0, float* stats,
+void launch_mel_norm_fwd(const float* xm, const int* frame_off, const int* pool_off, float* x0, float* stats,
                          float* gstat, float* part, int pstride, int B, int max_frames, hipStream_t st, float* amax_out) {
     if (max_frames <= kMelClipFrames) {
         hipLaunchKernelGGL(mel_norm_clip_fwd_kernel, dim3(B), dim3(512), 0, st, xm, frame_off, pool_off, x0, stats, gstat, amax_out);
-        return amax_out != nullptr;
+        return;
     }
     const int nx = (max_frames + kMelChunk - 1) / kMelChunk;
     hipLaunchKernelGGL(mel_partial_stats_kernel, dim3(nx, B), dim3(256), 0, st, xm, frame_off, part, pstride);
     hipLaunchKernelGGL(mel_apply_pool_kernel, dim3(nx, B), dim3(256), 0, st, xm, frame_off, pool_off, part, pstride, x0, stats,
                        gstat);
-    return false;
 }
 void launch_mel_norm_bwd(const float* dx0, float* xm, const int* frame_off, const int* pool_off, const float* stats,
                          const float* gstat, float* part, int pstride, int B, int max_frames, hipStream_t st) {

@@ -168,10 +168,12 @@ size_t readout_x3_image_bytes(int B, int nwm);      // scratch `img` of launch_r
 void launch_readout_grad_ragged_x3(const float* hin, int ci, const float* dZl, const void* WTpk, const float* rstd_prev, float* dZ,
                                    const int* frame_off, const int* pool_off, const int* order, int B, hipStream_t st,
                                    float* amax_out = nullptr);
-// mel block: InstanceNorm over time, per-clip GlobalStandardize, AvgPool(2,2)
-bool launch_mel_norm_fwd(const float* xm, const int* frame_off, const int* pool_off, float* x0, float* stats,
+// mel block: InstanceNorm over time, per-clip GlobalStandardize, AvgPool(2,2).  Clips of up to kMelClipFrames frames take one
+// workgroup per clip, which also writes amax_out (as launch_mel_front_x3) when given; longer clips a chunked form, which does not
+constexpr int kMelClipFrames = 192;
+void launch_mel_norm_fwd(const float* xm, const int* frame_off, const int* pool_off, float* x0, float* stats,
                          float* gstat, float* part, int pstride, int B, int max_frames, hipStream_t st,
-                         float* amax_out = nullptr);   // (amax_out as launch_mel_front_x3; returns whether it was written)
+                         float* amax_out = nullptr);
 void launch_mel_norm_bwd(const float* dx0, float* xm_inout, const int* frame_off, const int* pool_off, const float* stats,
                          const float* gstat, float* part, int pstride, int B, int max_frames, hipStream_t st);
 // the same for any bank: n_mels <= 512 bands in rows of Mp >= n_mels floats (Mp % 4 == 0); stats [B][Mp][4], part

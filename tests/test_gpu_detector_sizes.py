@@ -342,3 +342,48 @@ def test_stereo_service_round_trip_with_an_edited_card(rt, tmp_path):
     got = detect_watermark(out, 16000, det)
     for ch in (got if isinstance(got, (list, tuple)) else [got]):
         np.testing.assert_array_equal(np.asarray(ch).reshape(-1)[:20].astype(np.int32), bits)
+
+
+@pytest.mark.parametrize("name", ["card", "m64_gelu_batch_sigmoid", "m13_odd"])
+@pytest.mark.parametrize("lengths", [[16000] * 32, RAGGED])
+def test_workspace_bytes_are_exact(rt, plan, name, lengths):
+    """aware_detect and aware_detector_backward run in exactly the size their *_workspace_bytes reports and refuse 256 bytes
+    less (AWARE_E_WORKSPACE).  For the card (the training entry points refuse other detectors) the same holds for
+    aware_detector_train_gradients with grad_mag NULL, the largest case of aware_detector_train_workspace_bytes, and
+    aware_detector_weight_gradients runs in that size too."""
+    from aware_amd.detection import AWAREDetectorNet
+    net = AWAREDetectorNet() if name == "card" else make_net(name)
+    L = net.output_length
+    dev = net.device_weights(plan)
+    batch = rt.Batch(lengths)
+    lib = plan.lib
+    audio = batch.pack([make_clip(i, n)[0] for i, n in enumerate(lengths)])
+    rows = band_rows(rt, batch, band_mags(np.random.default_rng(5), batch.frames))
+    gv = torch.from_numpy(payload(3, batch.B, L)).cuda()
+    vals = torch.empty((batch.B, L), dtype=torch.float32, device="cuda")
+    gmag = torch.empty_like(rows)
+
+    def run(nbytes, call):
+        ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+        return call(rt._ptr(ws), nbytes - 256), call(rt._ptr(ws), nbytes)
+
+    n = lib.aware_detect_workspace_bytes(batch.h, dev.h)
+    assert run(n, lambda ws, nb: lib.aware_detect(plan.h, dev.h, batch.h, rt._ptr(audio), rt._ptr(vals), ws, nb,
+                                                  rt._stream())) == (-4, 0)
+    n = lib.aware_detector_backward_workspace_bytes(batch.h, dev.h)
+    assert run(n, lambda ws, nb: lib.aware_detector_backward(dev.h, batch.h, rt._ptr(rows), rt._ptr(gv), rt._ptr(vals),
+                                                             rt._ptr(gmag), ws, nb, rt._stream())) == (-4, 0)
+    if name == "card":
+        ch = dev.channels
+        gw = [torch.empty((ch[i + 1], ch[i]), dtype=torch.float32, device="cuda") for i in range(len(ch) - 1)]
+        pw = (C.c_void_p * len(gw))(*[t.data_ptr() for t in gw])
+        loss = torch.empty(batch.B, dtype=torch.float32, device="cuda")
+        n = lib.aware_detector_train_workspace_bytes(batch.h, dev.h)
+        assert run(n, lambda ws, nb: lib.aware_detector_train_gradients(dev.h, batch.h, rt._ptr(rows), rt._ptr(gv), 0,
+                                                                        rt._ptr(loss), rt._ptr(vals), None, pw, None, ws, nb,
+                                                                        rt._stream())) == (-4, 0)
+        assert run(n, lambda ws, nb: lib.aware_detector_weight_gradients(dev.h, batch.h, rt._ptr(rows), rt._ptr(gv),
+                                                                         rt._ptr(vals), rt._ptr(gmag), pw, None, ws, nb,
+                                                                         rt._stream()))[1] == 0
+    torch.cuda.synchronize()
+    assert torch.isfinite(vals).all() and torch.isfinite(gmag).all()
