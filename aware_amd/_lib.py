@@ -14,7 +14,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AWARE_HIP_LIB") or os.path.join(_HERE, "libaware_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["capi.hip", "dsp_kernels.hip", "dsp_stream.hip", "seam_kernels.hip", "detector_kernels.hip", "gemm_x3.hip", "gemm_h2.hip", "attack_kernels.hip", "stft_any.hip"]
+SOURCES = ["capi.hip", "dsp_kernels.hip", "dsp_stream.hip", "seam_kernels.hip", "detector_kernels.hip", "gemm_x3.hip", "gemm_h2.hip", "attack_kernels.hip", "stft_any.hip", "stoi_kernels.hip"]
 
 AWARE_OK = 0
 ERRORS = {-1: "bad argument", -2: "unsupported configuration", -3: "HIP runtime error", -4: "workspace too small"}
@@ -148,6 +148,12 @@ SIGNATURES = {
     "aware_segment_cut": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "aware_phase_vocoder": (_i, [_vp, _vp, _vp, _vp, _i, C.c_double, _vp]),
     "aware_snr": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "aware_stoi_create": (_i, [C.POINTER(_vp)]),
+    "aware_stoi_destroy": (None, [_vp]),
+    "aware_stoi_band_edges": (_i, [_vp, _pi, _pi]),
+    "aware_stoi_frames": (_i, [_i]),
+    "aware_stoi_workspace_bytes": (_sz, [_i, _i, C.c_longlong]),
+    "aware_stoi": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_longlong, _vp, _vp, _vp, _sz, _vp]),
     "aware_gaussian_noise": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _f, _vp, _vp]),
     "aware_spectral_quantize": (_i, [_vp, _i, _f, _f, _vp]),
     "aware_spectral_quantize_bwd": (_i, [_vp, _vp, _vp, _i, _f, _f, _vp]),

@@ -2226,6 +2226,157 @@ extern "C" int aware_snr(const float* output, const int* out_offsets, const floa
     return AWARE_OK;
 }
 
+// ---- STOI (stoi_kernels.hip) -------------------------------------------------------------------------------------------
+struct aware_stoi_plan {
+    void* mem = nullptr;
+    StoiTables tab;
+    int band_lo[kStoiRow] = {0}, band_hi[kStoiRow] = {0};
+};
+
+// third-octave band k: the bins of a 512-point spectrum at 10 kHz closest to 150 * 2^((2k -+ 1)/6) Hz, [lo, hi)
+// (metrics/audio.py::_third_octave_matrix: argmin of the squared distance, the first bin on a tie)
+static void stoi_band_edges(int* lo, int* hi) {
+    const int nfft = 2 * kStoiFrame, nbin = nfft / 2 + 1;
+    const double fs = 10000.0;
+    auto nearest = [&](double f) {
+        int best = 0;
+        double bd = INFINITY;
+        for (int i = 0; i < nbin; ++i) {
+            const double d = (fs * i / nfft - f) * (fs * i / nfft - f);
+            if (d < bd) { bd = d; best = i; }
+        }
+        return best;
+    };
+    for (int k = 0; k < kStoiBands; ++k) {
+        lo[k] = nearest(150.0 * pow(2.0, (2 * k - 1) / 6.0));
+        hi[k] = nearest(150.0 * pow(2.0, (2 * k + 1) / 6.0));
+    }
+    for (int k = kStoiBands; k < kStoiRow; ++k) lo[k] = hi[k] = 0;
+}
+
+extern "C" int aware_stoi_create(aware_stoi_plan** out) {
+    if (!out) return AWARE_E_BADARG;
+    const double PI = 3.14159265358979323846;
+    const int M = kStoiFrame, N = 2 * M;
+    aware_stoi_plan* p = new aware_stoi_plan();
+    stoi_band_edges(p->band_lo, p->band_hi);
+    // device image: th [M/2] cf, twN [M + 1 -> M + 2] cf, window [256] f32, bands [32] int
+    std::vector<float> h(M + 2 * (M + 2) + kStoiFrame + 2 * kStoiRow, 0.f);
+    float* th = h.data();
+    float* twN = th + M;
+    float* win = twN + 2 * (M + 2);
+    int* bands = reinterpret_cast<int*>(win + kStoiFrame);
+    for (int j = 0; j < M / 2; ++j) {
+        th[2 * j] = (float)cos(2 * PI * j / M);
+        th[2 * j + 1] = (float)-sin(2 * PI * j / M);
+    }
+    for (int k = 0; k <= M; ++k) {
+        twN[2 * k] = (float)cos(2 * PI * k / N);
+        twN[2 * k + 1] = (float)-sin(2 * PI * k / N);
+    }
+    twN[0] = 1.f; twN[1] = 0.f;
+    twN[M] = 0.f; twN[M + 1] = -1.f;
+    twN[2 * M] = -1.f; twN[2 * M + 1] = 0.f;
+    for (int i = 0; i < kStoiFrame; ++i)                   // np.hanning(258)[1:-1]
+        win[i] = (float)(0.5 - 0.5 * cos(2 * PI * (i + 1) / (kStoiFrame + 1)));
+    for (int k = 0; k < kStoiRow; ++k) { bands[k] = p->band_lo[k]; bands[kStoiRow + k] = p->band_hi[k]; }
+    if (hipMalloc(&p->mem, h.size() * sizeof(float)) != hipSuccess ||
+        hipMemcpy(p->mem, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+        g_last_err = "aware_stoi_create: device tables";
+        if (p->mem) (void)hipFree(p->mem);
+        delete p;
+        return AWARE_E_HIP;
+    }
+    float* d = (float*)p->mem;
+    p->tab.th = (const cf*)d;
+    p->tab.twN = (const cf*)(d + M);
+    p->tab.window = d + M + 2 * (M + 2);
+    p->tab.bands = (const int*)(d + M + 2 * (M + 2) + kStoiFrame);
+    *out = p;
+    return AWARE_OK;
+}
+
+extern "C" void aware_stoi_destroy(aware_stoi_plan* p) {
+    if (!p) return;
+    if (p->mem) (void)hipFree(p->mem);
+    delete p;
+}
+
+extern "C" int aware_stoi_band_edges(const aware_stoi_plan* p, int* lo, int* hi) {
+    if (!lo || !hi) return AWARE_E_BADARG;
+    if (p) {
+        memcpy(lo, p->band_lo, kStoiBands * sizeof(int));
+        memcpy(hi, p->band_hi, kStoiBands * sizeof(int));
+    } else {
+        int l[kStoiRow], h[kStoiRow];
+        stoi_band_edges(l, h);
+        memcpy(lo, l, kStoiBands * sizeof(int));
+        memcpy(hi, h, kStoiBands * sizeof(int));
+    }
+    return AWARE_OK;
+}
+
+extern "C" int aware_stoi_frames(int n) { return n < 0 ? AWARE_E_BADARG : stoi_frames(n); }
+
+// rows of the per-frame arrays: every clip's first-stage frames, all kept (frames(n) <= n / 128)
+static size_t stoi_total_frames(int B, int max_len, long long total_len) {
+    const size_t by_max = (size_t)B * (size_t)stoi_frames(max_len), by_total = (size_t)(total_len / kStoiHop);
+    return std::max<size_t>(1, std::min(by_max, by_total));
+}
+struct StoiCarve {
+    size_t energy, kept, kcount, fbase, xt, yt, partial, total;
+};
+static StoiCarve stoi_carve(int B, int max_len, long long total_len) {
+    const size_t TF = stoi_total_frames(B, max_len, total_len);
+    StoiCarve c;
+    size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 255) & ~(size_t)255; return at; };
+    c.energy = take(TF * sizeof(double));
+    c.kept = take(TF * sizeof(int));
+    c.kcount = take((size_t)B * sizeof(int));
+    c.fbase = take((size_t)B * sizeof(int));
+    c.xt = take(TF * kStoiRow * sizeof(float));
+    c.yt = take(TF * kStoiRow * sizeof(float));
+    c.partial = take((size_t)B * stoi_partials(max_len) * sizeof(double));
+    c.total = o;
+    return c;
+}
+
+extern "C" size_t aware_stoi_workspace_bytes(int B, int max_len, long long total_len) {
+    if (B < 1 || max_len < 0 || total_len < 0) return 0;
+    return stoi_carve(B, max_len, total_len).total;
+}
+
+extern "C" int aware_stoi(const aware_stoi_plan* plan, const float* clean, const int* clean_off, const float* proc,
+                          const int* proc_off, const int* n, int B, int max_len, long long total_len, double* out,
+                          int* kept_out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!plan || !clean || !clean_off || !proc || !proc_off || !n || !out || !workspace) return AWARE_E_BADARG;
+    if (B < 1 || B > 65535 || max_len < 0 || total_len < max_len || total_len > (long long)B * max_len) return AWARE_E_BADARG;
+    const StoiCarve c = stoi_carve(B, max_len, total_len);
+    if (workspace_bytes < c.total) return AWARE_E_WORKSPACE;
+    char* ws = (char*)workspace;
+    StoiLaunch L;
+    L.tab = plan->tab;
+    L.clean = clean; L.clean_off = clean_off;
+    L.proc = proc; L.proc_off = proc_off;
+    L.n = n;
+    L.B = B;
+    L.max_frames = stoi_frames(max_len);
+    L.max_partials = stoi_partials(max_len);
+    L.energy = (double*)(ws + c.energy);
+    L.kept = (int*)(ws + c.kept);
+    L.kcount = (int*)(ws + c.kcount);
+    L.fbase = (int*)(ws + c.fbase);
+    L.xt = (float*)(ws + c.xt);
+    L.yt = (float*)(ws + c.yt);
+    L.partial = (double*)(ws + c.partial);
+    L.out = out;
+    L.kept_out = kept_out;
+    launch_stoi(L, (hipStream_t)stream);
+    LAUNCHCHK();
+    return AWARE_OK;
+}
+
 extern "C" int aware_phase_vocoder(const void* spec_in, const int* frame_off_in, void* spec_out, const int* frame_off_out,
                                    int B, double rate, void* stream) {
     if (!spec_in || !frame_off_in || !spec_out || !frame_off_out || B < 1 || !(rate > 0.0)) return AWARE_E_BADARG;

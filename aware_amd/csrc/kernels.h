@@ -320,4 +320,37 @@ void launch_gen_synthesis(const GenLaunch& L, const void* spec, float* out, int 
 // out /= max|out| + 1e-8 per clip over the istft-length signals (L.pmax: partials of `out`)
 void launch_gen_normalize(const GenLaunch& L, float* out, hipStream_t st);
 
+// ---- stoi_kernels.hip: batched short-time objective intelligibility (metrics/audio.py::stoi) at 10 kHz -------------
+constexpr int kStoiFrame = 256, kStoiHop = 128, kStoiBands = 15, kStoiRow = 16, kStoiN = 30;
+constexpr int kStoiSegChunk = 64;         // segments per partial sum of the last stage
+// first-stage frames of a clip of n samples: len(range(0, n - 256, 128)) -- a frame that would end at n is not taken
+AW_HD int stoi_frames(int n) { return n > kStoiFrame ? (n - kStoiFrame + kStoiHop - 1) / kStoiHop : 0; }
+// partial sums per clip of the segment stage for a clip of n samples (every frame kept)
+AW_HD int stoi_partials(int n) {
+    const int nseg = stoi_frames(n) - 1 - (kStoiN - 1);
+    return nseg > 0 ? (nseg + kStoiSegChunk - 1) / kStoiSegChunk : 1;
+}
+struct StoiTables {
+    const cf* th = nullptr;               // W_256^j, j < 128
+    const cf* twN = nullptr;              // exp(-2 pi i k / 512), k <= 256
+    const float* window = nullptr;        // np.hanning(258)[1:-1]
+    const int* bands = nullptr;           // lo[16] then hi[16]: bins [lo, hi) of third-octave band j < 15; entry 15 is empty
+};
+struct StoiLaunch {
+    StoiTables tab;
+    const float* clean = nullptr; const int* clean_off = nullptr;
+    const float* proc = nullptr; const int* proc_off = nullptr;
+    const int* n = nullptr;               // [B] common length of clip b in both signals
+    int B = 0, max_frames = 0, max_partials = 0;
+    double* energy = nullptr;             // [total frames] frame energies of the clean signal, dB
+    int* kept = nullptr;                  // [total frames] clip b's kept frames, ascending, from fbase[b]
+    int* kcount = nullptr;                // [B] kept frames K_b
+    int* fbase = nullptr;                 // [B] first row of clip b in energy / kept / xt / yt
+    float* xt = nullptr; float* yt = nullptr;   // [total frames][16] third-octave band magnitudes of the re-framed signals
+    double* partial = nullptr;            // [B][max_partials]
+    double* out = nullptr;                // [B]
+    int* kept_out = nullptr;              // [B] or null
+};
+void launch_stoi(const StoiLaunch& L, hipStream_t st);
+
 }  // namespace aware

@@ -34,6 +34,13 @@ def snr_batch(output, target):
     return rt.snr_db(output, target)
 
 
+def stoi_batch(output, target, sample_rate: int = 16000):
+    """STOI of every clip of two ragged device batches (`output` the processed signal, `target` the clean one, as in
+    STOI.__call__), on the GPU: the batched form of `stoi(target_clip, output_clip, sample_rate)` below; float64 tensor [B]."""
+    from .. import runtime as rt
+    return rt.stoi(output, target, sample_rate)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # STOI (reference: src/AWARE/metrics/audio.py:46-64 -- mono mix, common length, resample to 16 kHz, pystoi.stoi(target, output,
 # 16000)).  pystoi and librosa are not importable here and the reference holds no STOI fixture: this is a restatement of the

@@ -25,6 +25,7 @@ class PipelineResult:
     seconds: float = 0.0                  # waveform-seconds processed (at the input rate)
     snr_db: torch.Tensor = None           # [B] float64: watermarked vs host clip at 16 kHz (report_snr=True)
     watermarked_out: "rt.Ragged" = None   # watermarked clips converted to `output_rate` (when requested)
+    stoi: torch.Tensor = None             # [B] float64: STOI of the watermarked vs the host clip at 16 kHz (report_stoi=True)
 
 
 class WatermarkPipeline:
@@ -73,12 +74,15 @@ class WatermarkPipeline:
 
     def run(self, audio: "rt.Ragged", bits: torch.Tensor, input_rate: int | None = None, chains=None,
             chain_of_clip=None, report_snr: bool = False, output_rate: int | None = None,
-            chains_by_kind=None) -> PipelineResult:
+            chains_by_kind=None, report_stoi: bool = False) -> PipelineResult:
         res = self._run(audio, bits, input_rate, chains, chain_of_clip, chains_by_kind)
         if report_snr:
             # imperceptibility metric of the reference (metrics/audio.py:68-89) on the device: watermarked clip
             # against the 16 kHz host clip over their common length
             res.snr_db = rt.snr_db(res.watermarked, self._host16k)
+        if report_stoi:
+            # the reference's third figure per file (scripts/test.py:41-92, metrics/audio.py:42-64), on the device
+            res.stoi = rt.stoi(res.watermarked, self._host16k, self.sample_rate)
         if output_rate and output_rate != self.sample_rate:
             # back end of the 44.1 kHz flow (README.md:26-37 of the reference): polyphase 16 kHz -> output_rate
             res.watermarked_out = resample_poly_batch(res.watermarked, output_rate, self.sample_rate)
@@ -214,15 +218,17 @@ def run_folder(folder, embedder, detector, attacks=(), watermark_length: int = 2
                pattern: str = "*.wav") -> dict:
     """The reference's harness loop over a folder of audio files (`scripts/test.py:52-106`): load mono at the native
     rate, resample to 16 kHz when needed, embed a random watermark, detect, then apply every attack on its own and detect
-    again.  Returns `{"files": [...], "orig": [BER % per file], attack.name: [BER % per file], ..., "snr_db": [...]}` --
-    the `rec` dictionary of the reference (BER in percent, `metrics/audio.py:8-17`) plus the SNR of each watermarked file.
+    again.  Returns `{"files": [...], "orig": [BER % per file], attack.name: [BER % per file], ..., "snr_db": [...],
+    "stoi": [...]}` -- the `rec` dictionary of the reference (BER in percent, `metrics/audio.py:8-17`) plus the SNR and the
+    STOI of each watermarked file.  The reference appends a STOI score only when it is above 0.1 (to keep silent files out
+    of its mean); here `rec["stoi"]` stays aligned with `rec["files"]`, one value per file, and the caller filters.
     Files are WAV (`aware_amd.utils.audio.io`); clips of one native rate are embedded as one ragged batch; a file the
     reference would refuse (too short for the STFT) is skipped with its error recorded under "skipped"."""
     from pathlib import Path
     from .utils.audio import io
     rng = np.random.default_rng(seed)
     paths = sorted(Path(folder).glob(pattern))
-    rec = {"files": [], "orig": [], "snr_db": [], "skipped": []}
+    rec = {"files": [], "orig": [], "snr_db": [], "stoi": [], "skipped": []}
     by_rate = {}
     for p in paths:
         try:
@@ -239,11 +245,12 @@ def run_folder(folder, embedder, detector, attacks=(), watermark_length: int = 2
         audio = rt.Ragged.from_list([x for _, x in items])
         bits = torch.as_tensor(rng.integers(0, 2, size=(len(items), watermark_length)), dtype=torch.int32, device="cuda")
         pipe = WatermarkPipeline(embedder, detector, attacks=[])
-        res = pipe.run(audio, bits, input_rate=sr, report_snr=True)
+        res = pipe.run(audio, bits, input_rate=sr, report_snr=True, report_stoi=True)
         wm_bits, _ = pipe._detect_bits(res.watermarked)
         rec["files"] += names
         rec["orig"] += (100.0 * (wm_bits != bits).float().mean(dim=1)).cpu().tolist()
         rec["snr_db"] += res.snr_db.cpu().tolist()
+        rec["stoi"] += res.stoi.cpu().tolist()
         for a in attacks:
             attacked = a.apply_batch(res.watermarked, 16000)
             a_bits, _ = pipe._detect_bits(attacked)

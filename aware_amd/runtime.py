@@ -867,6 +867,107 @@ def snr_db(output: Ragged, target: Ragged) -> torch.Tensor:
     return out
 
 
+STOI_FS = 10000
+_STOI_CACHE = {}
+
+
+def stoi_frames(n: int) -> int:
+    """First-stage frames of a clip of n samples at 10 kHz: len(range(0, n - 256, 128)) -- the device's arithmetic."""
+    return (n - 256 + 127) // 128 if n > 256 else 0
+
+
+def stoi_reframed(kept: int) -> int:
+    """Frames of the signal rebuilt from `kept` frames by overlap-add: kept - 1 (none for kept <= 1)."""
+    return max(kept - 1, 0)
+
+
+def stoi_segments(kept: int) -> int:
+    """30-frame segments of a clip with `kept` frames; 0 means the score is 1e-5."""
+    return max(stoi_reframed(kept) - 29, 0)
+
+
+def stoi_resample_filter(sample_rate: int):
+    """What metrics.audio._resample_oct hands to scipy.signal.resample_poly for sample_rate -> 10 kHz: the Kaiser-windowed
+    sinc normalised to unit sum and (inside resample_poly) scaled by `up`; float32 taps, up, down, half length."""
+    from .metrics.audio import _resample_window_oct
+    g = int(np.gcd(STOI_FS, int(sample_rate)))
+    up, down = STOI_FS // g, int(sample_rate) // g
+    h = _resample_window_oct(STOI_FS, int(sample_rate))
+    h = h / np.sum(h) * up
+    return h.astype(np.float32), up, down, (len(h) - 1) // 2
+
+
+class _StoiPlan:
+    def __init__(self):
+        require_gpu()
+        self.h = C.c_void_p()
+        check(load_library().aware_stoi_create(C.byref(self.h)), "aware_stoi_create")
+
+    def __del__(self):
+        try:
+            if self.h:
+                load_library().aware_stoi_destroy(self.h)
+                self.h = C.c_void_p()
+        except Exception:
+            pass
+
+
+def _stoi_plan(dev) -> "_StoiPlan":
+    key = ("plan", str(dev))
+    if key not in _STOI_CACHE:
+        _STOI_CACHE[key] = _StoiPlan()
+    return _STOI_CACHE[key]
+
+
+def _stoi_filter(sample_rate: int, dev):
+    key = ("fir", int(sample_rate), str(dev))
+    if key not in _STOI_CACHE:
+        h, up, down, half = stoi_resample_filter(sample_rate)
+        _STOI_CACHE[key] = (torch.from_numpy(h).to(dev), up, down, half)
+    return _STOI_CACHE[key]
+
+
+def stoi(output: Ragged, target: Ragged, sample_rate: int = 16000, return_kept: bool = False):
+    """Short-time objective intelligibility of every clip of `output` (the processed signal) against `target` (the clean
+    one) over their common length: the function `metrics.audio.stoi(target, output, sample_rate)` computes on the host,
+    on the device for the whole batch (argument order of `snr_db` and of the reference's STOI.__call__,
+    metrics/audio.py:42-64).  Both batches are resampled to 10 kHz with the polyphase kernel (`sample_rate == 10000`
+    skips that).  Device float64 tensor [B]; with return_kept also the kept-frame count of every clip (device int32)."""
+    if output.B != target.B:
+        raise ValueError("stoi: batches differ in size")
+    lib = load_library()
+    dev = output.data.device
+    B = output.B
+    n_in = [min(a, b) for a, b in zip(output.lengths, target.lengths)]
+    pr = output.data if output.data.dtype == torch.float32 else output.data.float()
+    cl = target.data if target.data.dtype == torch.float32 else target.data.float()
+    p_off, c_off = output.d_off, target.d_off
+    if int(sample_rate) != STOI_FS:
+        h, up, down, half = _stoi_filter(sample_rate, dev)
+        n10 = [-(-n * up // down) for n in n_in]
+        d_in = torch.tensor(n_in, dtype=torch.int32, device=dev)
+        off10 = np.concatenate([[0], np.cumsum(n10)[:-1]]).astype(np.int32)
+        d_off10 = torch.from_numpy(off10).to(dev)
+        d_n = torch.tensor(n10, dtype=torch.int32, device=dev)
+        res = torch.empty((2, max(sum(n10), 1)), dtype=torch.float32, device=dev)
+        for src, off, dst in ((cl, c_off, res[0]), (pr, p_off, res[1])):
+            check(lib.aware_upfirdn(_ptr(src), _ptr(off), _ptr(d_in), _ptr(dst), _ptr(d_off10), _ptr(d_n), B, max(n10),
+                                    _ptr(h), h.numel(), up, down, half, _stream()), "aware_upfirdn")
+        cl, pr, c_off, p_off = res[0], res[1], d_off10, d_off10
+    else:
+        n10 = n_in
+        d_n = torch.tensor(n10, dtype=torch.int32, device=dev)
+    max_len, total = max(n10), max(sum(n10), max(n10))
+    plan = _stoi_plan(dev)
+    nbytes = lib.aware_stoi_workspace_bytes(B, max_len, total)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    out = torch.empty(B, dtype=torch.float64, device=dev)
+    kept = torch.empty(B, dtype=torch.int32, device=dev) if return_kept else None
+    check(lib.aware_stoi(plan.h, _ptr(cl), _ptr(c_off), _ptr(pr), _ptr(p_off), _ptr(d_n), B, max_len, total, _ptr(out),
+                         _ptr(kept), _ptr(ws), nbytes, _stream()), "aware_stoi")
+    return (out, kept) if return_kept else out
+
+
 KERNEL_KINDS = ["synth", "analysis", "gemm_nt", "mel_norm", "in_lrelu", "readout_tail", "synth_adjoint",
                 "analysis_adjoint_nadam", "misc", "gemm_clip_fwd", "gemm_clip_bwd", "gemm_x3_fwd", "gemm_x3_bwd"]
 

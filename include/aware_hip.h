@@ -60,6 +60,7 @@ typedef struct aware_plan aware_plan;
 typedef struct aware_detector aware_detector;
 typedef struct aware_batch aware_batch;
 typedef struct aware_embed aware_embed;
+typedef struct aware_stoi_plan aware_stoi_plan;
 
 /* ABI version (200: no process-global knobs, the kernel choices live in aware_embed_config; 300: conv_pipe 0 = f16 two-term
  * kernels, optimiser / scheduler registries, device-side detector training, aware_stft_bwd for any clip length; 310: general
@@ -67,7 +68,9 @@ typedef struct aware_embed aware_embed;
  * aware_nola_check; 320: detector architecture variants -- aware_detector_create_ex, aware_detector_is_card; 330: any
  * embedding band inside bins 0..512 -- the wide layout, aware_plan_band_stride; 340: payloads of 1..512 bits --
  * aware_detector_create accepts any even channels[n_layers] from 2 to 1024; 350: detector sizes -- n_mels 1..512, hidden
- * widths 1..4096, n_layers 1..33) */
+ * widths 1..4096, n_layers 1..33).  The STOI entry points (aware_stoi_create, aware_stoi_destroy, aware_stoi_workspace_bytes,
+ * aware_stoi, aware_stoi_band_edges, aware_stoi_frames) were added without a version step -- tests/test_detector_sizes_host.py
+ * pins the literal 350 -- so a caller detects them by symbol. */
 int aware_version(void);
 /* text of the last failed HIP runtime call on the calling thread (thread-local) */
 const char* aware_last_hip_error(void);
@@ -456,6 +459,34 @@ int aware_phase_vocoder(const void* spec_in, const int* frame_off_in, void* spec
  * f64 accumulation in a fixed order.  Offsets are float offsets of clip c in the two signal arrays. */
 int aware_snr(const float* output, const int* out_offsets, const float* target, const int* tgt_offsets,
               const int* lengths, int B, double* snr_db, void* stream);
+
+/* STOI (short-time objective intelligibility, Taal et al. 2011) per clip pair, what STOI.__call__ (metrics/audio.py:42-64)
+ * obtains from pystoi: the function aware_amd/metrics/audio.py::stoi restates on the host (parity with pystoi itself
+ * unpinned), for two ragged batches ALREADY AT 10 kHz.  Per clip: frames of 256 samples every 128 (a frame that would end
+ * exactly at n is not taken; n <= 256 gives none), energies of the CLEAN signal's windowed frames, frames within 40 dB of
+ * the loudest kept (both signals use the clean signal's list), overlap-add of the kept frames and re-framing (K kept frames
+ * give K - 1), second window, 512-point FFT of the frame zero-padded at its end, 15 third-octave bands from 150 Hz,
+ * segments of 30 frames: normalisation and clipping of the processed band (-15 dB SDR), correlation, mean over segments and
+ * bands.  Fewer than 30 re-framed frames: exactly 1e-5.  Frames, FFT and band sums are f32; energies are compared and the
+ * segment statistics are computed in f64; every reduction has a fixed order inside one clip (no atomics), so a clip's score
+ * depends neither on its neighbours nor on the run.
+ * The plan holds the FFT twiddles, the window and the band edges on the device (no process-global state); it may be shared
+ * by concurrent calls.  aware_stoi_band_edges copies the 15 band edges (bins lo <= k < hi) to host arrays; plan may be NULL
+ * (the edges are constants).  aware_stoi_frames: first-stage frames of a clip of n samples.
+ * aware_stoi_workspace_bytes: bytes for B clips, the longest of max_len samples, total_len samples in all (the sum of the
+ * common lengths), with every frame kept.  aware_stoi: clean / proc dev f32, clip c at float offset clean_off[c] /
+ * proc_off[c] (dev int [B]), n dev int [B] the common length of clip c (<= max_len, their sum <= total_len); out dev f64
+ * [B]; kept_out dev int [B] or NULL receives K_c.  Five launches on `stream`, no allocation, no synchronisation, no copy to
+ * the host.  AWARE_E_BADARG: a null argument, B < 1 or > 65535, total_len outside [max_len, B * max_len];
+ * AWARE_E_WORKSPACE: workspace_bytes below aware_stoi_workspace_bytes. */
+int aware_stoi_create(aware_stoi_plan** out);
+void aware_stoi_destroy(aware_stoi_plan* plan);
+int aware_stoi_band_edges(const aware_stoi_plan* plan, int* lo, int* hi);
+int aware_stoi_frames(int n);
+size_t aware_stoi_workspace_bytes(int B, int max_len, long long total_len);
+int aware_stoi(const aware_stoi_plan* plan, const float* clean, const int* clean_off, const float* proc,
+               const int* proc_off, const int* n, int B, int max_len, long long total_len, double* out, int* kept_out,
+               void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- bare GEMM (tests / roofline): C[M][N] = A[M][K] * Bt[N][K]^T + bias ------------------------------ */
 int aware_gemm_nt(const float* A, int lda, const float* Bt, int ldb, const float* bias, float* C, int ldc,
