@@ -3,6 +3,7 @@
 // workspace carving, launch sequences, optional hipGraph capture of one optimiser iteration.
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <cmath>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -1696,6 +1697,21 @@ struct aware_embed {
         double* d_state = nullptr;    // [B][3] plateau state
         std::vector<double> lr_init, state_init;
     } opt;
+    // attack-aware embedding (aware_embed_set_loop_attacks; EXTENSION): the chain and its buffers in the caller's second
+    // workspace.  n == 0: the loop issues exactly the launches of the plain loop
+    struct {
+        int n = 0;
+        int kind[kMaxLoopAttacks] = {0}, k[kMaxLoopAttacks] = {0};
+        double inv_snr[kMaxLoopAttacks] = {0};
+        float prob[kMaxLoopAttacks] = {0};
+        float* z = nullptr;                       // [NS] the attacked signal
+        unsigned long long* pmaxZ = nullptr;      // [B][pstride]
+        double* psq = nullptr;                    // [kMaxLoopAttacks][B][pstride] partial sums of squares per noise entry
+        double* pdot = nullptr;                   // [B][pstride] partial sums of dL/dx * x for the analysis adjoint
+        float* gpad0 = nullptr;                   // [B][2][512] zeros: the pads are folded before the analysis adjoint
+        unsigned* seeds = nullptr;                // [B]
+        bool locked = false;                      // an optimiser step has run: the chain stays what it is
+    } la;
 };
 
 // the embed loop's workspace: the detector's buffers, then the loop state; iters: num_iterations, l1: the L1 term's buffers
@@ -1885,6 +1901,62 @@ extern "C" int aware_embed_set_optimizer(aware_embed* e, const aware_optimizer_c
     return AWARE_OK;
 }
 
+// Attack-aware embedding (EXTENSION): the chain's buffers live in a workspace of their own, so that
+// aware_embed_workspace_bytes and the layout of the loop's workspace stay what they were
+template <typename LA> static void carve_loop_attacks(Carver& c, const aware_batch* b, LA& la) {
+    const size_t np = (size_t)b->B * b->pstride;
+    la.z = c.take<float>(b->NS);
+    la.pmaxZ = c.take<unsigned long long>(np);
+    la.psq = c.take<double>(np * kMaxLoopAttacks);
+    la.pdot = c.take<double>(np);
+    la.gpad0 = c.take<float>((size_t)b->B * 1024);
+    la.seeds = c.take<unsigned>(b->B);
+}
+extern "C" size_t aware_embed_loop_attack_workspace_bytes(const aware_batch* b, int n_attacks) {
+    if (!b || b->general || n_attacks < 1 || n_attacks > kMaxLoopAttacks) return 0;
+    Carver c(nullptr, 0);
+    aware_embed e;
+    carve_loop_attacks(c, b, e.la);
+    return c.off;
+}
+extern "C" int aware_embed_set_loop_attacks(aware_embed* e, const aware_loop_attack* attacks, int n_attacks,
+                                            const uint32_t* seeds, void* workspace, size_t workspace_bytes, void* stream) {
+    static_assert(AWARE_LOOP_GAUSSIAN_NOISE == kLoopGaussianNoise && AWARE_LOOP_SAMPLE_SUPPRESSION == kLoopSampleSuppression, "");
+    if (!e || n_attacks < 0 || n_attacks > kMaxLoopAttacks) return AWARE_E_BADARG;
+    if (e->gexec || e->la.locked) return AWARE_E_BADARG;          // before the first aware_embed_iterate, as aware_embed_set_optimizer
+    if (n_attacks == 0) { e->la.n = 0; e->la.z = nullptr; return AWARE_OK; }
+    if (!attacks || !seeds || !workspace || ((uintptr_t)workspace & 255)) return AWARE_E_BADARG;
+    const aware_batch* b = e->b;
+    auto la = e->la;
+    for (int j = 0; j < n_attacks; ++j) {
+        const aware_loop_attack& a = attacks[j];
+        if (!(a.prob >= 0.f && a.prob <= 1.f)) return AWARE_E_BADARG;
+        la.kind[j] = a.kind; la.prob[j] = a.prob; la.k[j] = 0; la.inv_snr[j] = 0.0;
+        if (a.kind == AWARE_LOOP_GAUSSIAN_NOISE) {
+            if (!std::isfinite(a.param)) return AWARE_E_BADARG;
+            la.inv_snr[j] = pow(10.0, -(double)a.param / 10.0);
+        } else if (a.kind == AWARE_LOOP_SAMPLE_SUPPRESSION) {
+            if (!(a.param >= 1.f) || a.param > 2147483520.f || a.param != floorf(a.param)) return AWARE_E_BADARG;
+            la.k[j] = (int)a.param;
+        } else {
+            return AWARE_E_BADARG;
+        }
+    }
+    for (int j = 0; j < n_attacks; ++j)
+        for (int i = 0; i < b->B; ++i)
+            if (la.kind[j] == AWARE_LOOP_SAMPLE_SUPPRESSION && la.k[j] >= b->out_len[i]) return AWARE_E_UNSUPPORTED;
+    Carver c(workspace, workspace_bytes);
+    carve_loop_attacks(c, b, la);
+    if (!c.ok) return AWARE_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    HIPCHK(hipMemsetAsync(la.gpad0, 0, (size_t)b->B * 1024 * sizeof(float), st));
+    HIPCHK(hipMemcpyAsync(la.seeds, seeds, (size_t)b->B * sizeof(unsigned), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    la.n = n_attacks;
+    e->la = la;
+    return AWARE_OK;
+}
+
 extern "C" void aware_embed_destroy(aware_embed* e) {
     if (!e) return;
 
@@ -1911,6 +1983,7 @@ extern "C" void* aware_embed_buffer(aware_embed* e, int which) {
         case 9: return e->yraw;
         case 10: return e->mag;
         case 11: return e->opt.active ? e->opt.d_lr : nullptr;      // per-clip learning rate (double; ReduceLROnPlateau state)
+        case 12: return e->la.n ? e->la.z : nullptr;                // the attacked signal of the last forward pass
         default: return nullptr;
     }
 }
@@ -1974,6 +2047,19 @@ static int embed_iteration(aware_embed* e, hipStream_t st, int do_step, float* g
     L.plan = e->plan->dev; L.frame_off = b->d_frame_off; L.B = b->B; L.max_frames = b->max_frames; L.run_frames = b->an_run; L.wg_tab = b->d_an_wg; L.n_wg = b->n_an_wg;
     L.sig = e->yraw; L.sig_off = b->d_out_off; L.sig_len = b->d_out_len;
     L.pmax = e->pmaxY; L.pcount = b->d_pc_syn; L.pstride = b->pstride; L.double_norm = 1;
+    // attack-aware embedding (EXTENSION): the chain turns the normalised synthesis into z; the analysis reads z
+    const bool attacked = e->la.n > 0;
+    LoopAttackLaunch A;
+    if (attacked) {
+        const auto& la = e->la;
+        A.frame_off = b->d_frame_off; A.pcount = b->d_pc_syn; A.B = b->B; A.pstride = b->pstride; A.run_blocks = b->synth_run;
+        A.step = e->step; A.seeds = la.seeds; A.n = la.n;
+        for (int j = 0; j < la.n; ++j) { A.kind[j] = la.kind[j]; A.k[j] = la.k[j]; A.inv_snr[j] = la.inv_snr[j]; A.prob[j] = la.prob[j]; }
+        A.yraw = e->yraw; A.pmaxY = e->pmaxY; A.psq = la.psq; A.z = la.z; A.pmaxZ = la.pmaxZ;
+        launch_loop_attack_forward(A, st);
+        LAUNCHCHK(); PROF(K_MISC);
+        L.sig = la.z; L.pmax = la.pmaxZ;
+    }
     L.mag = e->mag; L.unit = e->U; L.unit_default = 0.f; L.write_pad = 0;
     // the mel projection as short runs of adjacent bins inside the streaming analysis kernel (no magnitude array), and its
     // backward as two taps per bin inside the synthesis adjoint (below): streaming DSP path and a filter bank of that form
@@ -2001,8 +2087,18 @@ static int embed_iteration(aware_embed* e, hipStream_t st, int do_step, float* g
     SA.amp = e->gmag; SA.ph = e->U; SA.out = e->gy; SA.adjoint = 1; SA.yraw = e->yraw; SA.pmax_in = e->pmaxY;
     SA.pcount = b->d_pc_syn; SA.pdot = e->pdot; SA.pstride = b->pstride; SA.gpad = e->gpad;
     if (mel_taps) { SA.dmel = e->db.xm; SA.melw = d->melw; SA.melm = d->melm; }
+    if (attacked) { SA.yraw = e->la.z; SA.pmax_in = e->la.pmaxZ; }
     run_synth(SA, dsp, st);
     LAUNCHCHK(); PROF(K_SYNTH_ADJ);
+    if (attacked) {
+        // gy: dL/d N(N(z)) -> dL/dx (normalisers at z, mask of the suppressions); the reflect-pad parts of the streaming
+        // adjoint are folded in here, so the analysis adjoint below gets a block of zeros for them
+        const bool streamed = dsp == 0 && stream_supported(e->plan->dev);
+        A.step_back = do_step ? 1 : 0;                  // the read-out kernel has advanced the counter
+        A.gy = e->gy; A.gpad = streamed ? e->gpad : nullptr; A.pdot_in = e->pdot; A.pdot_out = e->la.pdot;
+        launch_loop_attack_backward(A, st);
+        LAUNCHCHK(); PROF(K_MISC);
+    }
     // backward through the normalisers, ISTFT and the assembler; :112-117 NAdam + clamp
     AnalysisLaunch LA;
     LA.plan = e->plan->dev; LA.frame_off = b->d_frame_off; LA.B = b->B; LA.max_frames = b->max_frames; LA.run_frames = b->an_run; LA.wg_tab = b->d_an_wg; LA.n_wg = b->n_an_wg;
@@ -2018,6 +2114,7 @@ static int embed_iteration(aware_embed* e, hipStream_t st, int do_step, float* g
     memcpy(LA.hyp, e->hyp, sizeof(LA.hyp));
     LA.gpad = e->gpad; LA.c0 = e->c0; LA.box_ratio = (float)pow(10.0, -(double)e->cfg.tolerance_db / 20.0);
     LA.l1_weight = e->pl1 ? e->cfg.l1_weight : 0.f;
+    if (attacked) { LA.pdot = e->la.pdot; LA.gpad = e->la.gpad0; }
     run_analysis(LA, dsp, st);
     LAUNCHCHK(); PROF(K_ANALYSIS_ADJ);
     if (own_step) {
@@ -2038,6 +2135,7 @@ extern "C" int aware_embed_iterate(aware_embed* e, int n_iters, void* stream) {
     // multibit_embedder.py:95): more than that since aware_embed_begin is a caller error
     if (e->steps_done + n_iters > e->cfg.num_iterations) return AWARE_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
+    if (n_iters > 0) e->la.locked = true;
     if (!e->cfg.use_graph) {
         for (int i = 0; i < n_iters; ++i) {
             int rc = embed_iteration(e, st, 1, nullptr);

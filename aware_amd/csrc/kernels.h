@@ -353,4 +353,35 @@ struct StoiLaunch {
 };
 void launch_stoi(const StoiLaunch& L, hipStream_t st);
 
+// ---- loop_attack_kernels.hip: attack-aware embedding (EXTENSION): a chain of attacks between the embed loop's synthesis and
+// its analysis, drawn afresh at every optimiser step (aware_embed_set_loop_attacks) --------------------------------------
+constexpr int kMaxLoopAttacks = 4;
+constexpr int kLoopGaussianNoise = 0, kLoopSampleSuppression = 1;      // AWARE_LOOP_* of aware_hip.h
+struct LoopAttackLaunch {
+    const int* frame_off = nullptr;
+    const int* pcount = nullptr;          // [B] synthesis runs per clip: the partials' layout
+    int B = 0, pstride = 0, run_blocks = 0;
+    const int* step = nullptr;            // device step counter; step_back = 1 once the read-out kernel has advanced it
+    int step_back = 0;
+    const unsigned* seeds = nullptr;      // [B]
+    int n = 0;
+    int kind[kMaxLoopAttacks] = {0};
+    int k[kMaxLoopAttacks] = {0};         // suppression: samples
+    double inv_snr[kMaxLoopAttacks] = {0};   // noise: 10^(-snr_db / 10)
+    float prob[kMaxLoopAttacks] = {0};
+    const float* yraw = nullptr;          // the raw synthesis and its partial maxima
+    const unsigned long long* pmaxY = nullptr;
+    double* psq = nullptr;                // [kMaxLoopAttacks][B][pstride]
+    float* z = nullptr;                   // the attacked signal (layout of yraw) and its partial maxima
+    unsigned long long* pmaxZ = nullptr;
+    float* gy = nullptr;                  // backward: gradient in / out
+    const float* gpad = nullptr;          // reflect-pad parts of the streaming synthesis adjoint (null: already folded)
+    const double* pdot_in = nullptr;
+    double* pdot_out = nullptr;
+};
+// x = N(N(yraw)), the chain, z and the partial maxima of |z|: one reduction launch per noise entry, then one pass
+void launch_loop_attack_forward(const LoopAttackLaunch& L, hipStream_t st);
+// gy: dL/d N(N(z)) -> dL/dx in place, pdot_out: partial sums of dL/dx * x
+void launch_loop_attack_backward(const LoopAttackLaunch& L, hipStream_t st);
+
 }  // namespace aware

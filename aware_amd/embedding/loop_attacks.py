@@ -1,0 +1,162 @@
+"""Attack-aware embedding (EXTENSION, parity unpinned: the reference optimises against the clean synthesis only).
+
+A chain of up to four attacks applied to the normalised synthesis inside every iteration of the embed loop, so that the
+optimiser sees what an attacker does to the signal.  This module parses / validates the chain and restates the model in torch:
+`apply_chain` is the specification the device kernels (csrc/loop_attack_kernels.hip) are tested against and the CPU twin of
+the loop's new stage.  For clip b (length Ny) at optimiser step s with seed_b:
+
+    entry j:  r = philox4x32_10(counter (0, s, 1 + j, 1), key (seed_b, 0x5EED));  on = (r[0] + 0.5) / 2^32 < prob
+      sample_suppression(seconds), k = int(seconds * sample_rate):  start = (r[1] * (Ny - k)) >> 32;  on: x[start:start+k] = 0
+      gaussian_noise(snr_db):  sigma = sqrt(mean(x^2) / 10^(snr_db / 10)) of the current x, detached;  on: x += sigma * eps,
+        eps_i from philox4x32_10((i // 4, s, 0, j), (seed_b, 0x5EED)), lanes paired through Box-Muller as the post-hoc
+        GaussianNoise attack pairs them (at s = 0, j = 0 the two draw the same noise)
+
+In the loop x = N(N(y)) of the raw synthesis y, N(v) = v / (max|v| + 1e-8), and the analysis (N, N, STFT, band magnitudes)
+runs on the chain's output."""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+import torch
+
+MAX_ATTACKS = 4
+KINDS = {"gaussian_noise": 0, "sample_suppression": 1}          # AWARE_LOOP_* of include/aware_hip.h
+_KEYS = {"gaussian_noise": {"kind", "snr_db", "prob"}, "sample_suppression": {"kind", "seconds", "prob"}}
+_KEY1 = 0x5EED
+
+
+def parse_chain(chain) -> list[dict]:
+    """Validated copy of a chain such as [{"kind": "gaussian_noise", "snr_db": 10.0, "prob": 1.0},
+    {"kind": "sample_suppression", "seconds": 0.3, "prob": 0.75}] (None / empty: no chain).  ValueError: unknown kind or key,
+    a missing parameter, prob outside [0, 1], a non-finite snr_db, seconds <= 0, more than four entries."""
+    if not chain:
+        return []
+    if isinstance(chain, dict) or not isinstance(chain, (list, tuple)):
+        raise ValueError("loop_attacks: a list of {kind: ...} entries is expected")
+    if len(chain) > MAX_ATTACKS:
+        raise ValueError(f"loop_attacks: at most {MAX_ATTACKS} entries, got {len(chain)}")
+    out = []
+    for j, a in enumerate(chain):
+        if not isinstance(a, dict) or a.get("kind") not in KINDS:
+            raise ValueError(f"loop_attacks[{j}]: unknown kind {a.get('kind') if isinstance(a, dict) else a!r}; "
+                             f"available: {list(KINDS)}")
+        kind = a["kind"]
+        extra = set(a) - _KEYS[kind]
+        if extra:
+            raise ValueError(f"loop_attacks[{j}] ({kind}): unknown key(s) {sorted(extra)}")
+        prob = float(a.get("prob", 1.0))
+        if not 0.0 <= prob <= 1.0:
+            raise ValueError(f"loop_attacks[{j}] ({kind}): prob = {prob} outside [0, 1]")
+        e = {"kind": kind, "prob": prob}
+        if kind == "gaussian_noise":
+            if "snr_db" not in a or not math.isfinite(float(a["snr_db"])):
+                raise ValueError(f"loop_attacks[{j}] (gaussian_noise): a finite snr_db is required")
+            e["snr_db"] = float(a["snr_db"])
+        else:
+            if "seconds" not in a or not math.isfinite(float(a["seconds"])) or float(a["seconds"]) <= 0.0:
+                raise ValueError(f"loop_attacks[{j}] (sample_suppression): seconds > 0 is required")
+            e["seconds"] = float(a["seconds"])
+        out.append(e)
+    return out
+
+
+def suppression_samples(entry: dict, sample_rate: int) -> int:
+    """k = int(seconds * sample_rate), as SampleSupression.apply counts them."""
+    return int(entry["seconds"] * sample_rate)
+
+
+def check_lengths(chain: list[dict], sample_rate: int, out_lengths) -> None:
+    """ValueError naming the first clip that a suppression would not fit into (0 < k < Ny_b is required)."""
+    for j, a in enumerate(chain):
+        if a["kind"] != "sample_suppression":
+            continue
+        k = suppression_samples(a, sample_rate)
+        if k < 1:
+            raise ValueError(f"loop_attacks[{j}] (sample_suppression): {a['seconds']} s is less than one sample at {sample_rate} Hz")
+        for b, ny in enumerate(out_lengths):
+            if k >= int(ny):
+                raise ValueError(f"loop_attacks[{j}] (sample_suppression): clip {b} has {int(ny)} output samples, "
+                                 f"not more than the {k} to be suppressed")
+
+
+def philox4x32(counter: np.ndarray, key, rounds: int = 10) -> np.ndarray:
+    """Philox-4x32 (Salmon et al. 2011) on `counter` [n, 4] uint32 with key (k0, k1); returns [n, 4] uint32."""
+    c = np.asarray(counter, dtype=np.uint64) & np.uint64(0xFFFFFFFF)
+    c0, c1, c2, c3 = c[:, 0], c[:, 1], c[:, 2], c[:, 3]
+    k0, k1 = int(key[0]) & 0xFFFFFFFF, int(key[1]) & 0xFFFFFFFF
+    mask, sh = np.uint64(0xFFFFFFFF), np.uint64(32)
+    for _ in range(rounds):
+        p0 = np.uint64(0xD2511F53) * c0
+        p1 = np.uint64(0xCD9E8D57) * c2
+        c0, c1, c2, c3 = (p1 >> sh) ^ c1 ^ np.uint64(k0), p1 & mask, (p0 >> sh) ^ c3 ^ np.uint64(k1), p0 & mask
+        k0 = (k0 + 0x9E3779B9) & 0xFFFFFFFF
+        k1 = (k1 + 0xBB67AE85) & 0xFFFFFFFF
+    return np.stack([c0, c1, c2, c3], axis=1).astype(np.uint32)
+
+
+def entry_draw(seed: int, step: int, j: int) -> np.ndarray:
+    """The four uint32 lanes that decide whether entry j fires at this step (lane 0) and where a suppression starts (lane 1)."""
+    return philox4x32(np.array([[0, step, 1 + j, 1]], dtype=np.uint64), (seed, _KEY1))[0]
+
+
+def fires(r0: int, prob: float) -> bool:
+    """(r0 + 0.5) / 2^32 < prob, with prob at the float32 precision the device holds it in."""
+    return (float(r0) + 0.5) / 4294967296.0 < float(np.float32(prob))
+
+
+def suppression_start(r1: int, ny: int, k: int) -> int:
+    return (int(r1) * (int(ny) - int(k))) >> 32
+
+
+def normal_draws(n: int, seed: int, step: int, j: int) -> np.ndarray:
+    """n standard normal draws (float64) of noise entry j at this step: counter (i // 4, step, 0, j), key (seed, 0x5EED),
+    u = (r + 0.5) / 2^32, z0 = sqrt(-2 ln u0) cos(2 pi u1), z1 = sqrt(-2 ln u0) sin(2 pi u1), z2 / z3 from lanes 2 and 3."""
+    nblk = (n + 3) // 4
+    ctr = np.zeros((nblk, 4), dtype=np.uint64)
+    ctr[:, 0] = np.arange(nblk, dtype=np.uint64)
+    ctr[:, 1] = step
+    ctr[:, 3] = j
+    u = (philox4x32(ctr, (seed, _KEY1)).astype(np.float64) + 0.5) / 4294967296.0
+    r0, r1 = np.sqrt(-2.0 * np.log(u[:, 0])), np.sqrt(-2.0 * np.log(u[:, 2]))
+    z = np.stack([r0 * np.cos(2 * np.pi * u[:, 1]), r0 * np.sin(2 * np.pi * u[:, 1]),
+                  r1 * np.cos(2 * np.pi * u[:, 3]), r1 * np.sin(2 * np.pi * u[:, 3])], axis=1)
+    return z.reshape(-1)[:n]
+
+
+def apply_chain(x, chain, seeds, step: int, sample_rate: int = 16000):
+    """The chain on x: a tensor [B, Ny] or a list of B 1-D tensors (ragged), float32 or float64; differentiable (the noise
+    amplitude is detached, a suppression multiplies by a 0/1 mask).  seeds: B integers; step: the optimiser step.  Returns the
+    same container type."""
+    chain = parse_chain(chain)
+    clips = list(x) if not torch.is_tensor(x) else [x[b] for b in range(x.shape[0])]
+    if len(seeds) != len(clips):
+        raise ValueError(f"apply_chain: {len(clips)} clips but {len(seeds)} seeds")
+    check_lengths(chain, sample_rate, [c.shape[-1] for c in clips])
+    out = []
+    for xb, seed in zip(clips, seeds):
+        ny = xb.shape[-1]
+        seed = int(seed) & 0xFFFFFFFF
+        for j, a in enumerate(chain):
+            r = entry_draw(seed, step, j)
+            on = fires(r[0], a["prob"])
+            if a["kind"] == "sample_suppression":
+                k = suppression_samples(a, sample_rate)
+                start = suppression_start(r[1], ny, k)
+                if on:
+                    mask = torch.ones(ny, dtype=xb.dtype, device=xb.device)
+                    mask[start:start + k] = 0
+                    xb = xb * mask
+            elif on:
+                power = float(np.mean(xb.detach().double().cpu().numpy() ** 2))
+                sigma = math.sqrt(power / (10.0 ** (a["snr_db"] / 10.0)))
+                noise = torch.as_tensor(sigma * normal_draws(ny, seed, step, j)).to(dtype=xb.dtype, device=xb.device)
+                xb = xb + noise
+        out.append(xb)
+    return torch.stack(out) if torch.is_tensor(x) else out
+
+
+def device_entries(chain: list[dict], sample_rate: int):
+    """(kind, param, prob) triples of the C ABI (aware_loop_attack): param = snr_db or the suppression length in samples."""
+    return [(KINDS[a["kind"]], a["snr_db"] if a["kind"] == "gaussian_noise" else float(suppression_samples(a, sample_rate)),
+             a["prob"]) for a in chain]

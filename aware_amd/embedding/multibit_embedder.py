@@ -17,6 +17,7 @@ from ..interfaces import BaseEmbedder
 from ..utils.audio import ISTFT, STFT, STFTAssembler, STFTDecomposer, WaveformNormalizer, band_bins, get_plan
 from ..utils.logger import logger
 from .. import runtime as rt
+from .loop_attacks import parse_chain
 from .losses import get_loss_fn
 from .optimizers import get_optimizer, is_card_default
 from .schedulers import get_scheduler
@@ -26,7 +27,11 @@ class AWAREEmbedder(BaseEmbedder):
     def __init__(self, frame_length: int = 1024, hop_length: int = 256, window: str = "hann", win_length: int = 1024,
                  pattern_mode: str = "bits2bipolar", embedding_bands=(500, 4000), tolerance_db: float = 6.0,
                  num_iterations: int = 400, detection_net_cfg: dict = None, optimizer_cfg: dict = None,
-                 scheduler_cfg: dict = None, loss: str = "push", verbose: bool = True, use_graph: bool = True):
+                 scheduler_cfg: dict = None, loss: str = "push", verbose: bool = True, use_graph: bool = True,
+                 loop_attacks=None, loop_attack_seed: int = 0):
+        """loop_attacks (EXTENSION, see embedding/loop_attacks.py): a chain of attacks applied inside the optimisation loop,
+        e.g. [{"kind": "gaussian_noise", "snr_db": 10.0}, {"kind": "sample_suppression", "seconds": 0.3, "prob": 0.75}];
+        clip i of a batch draws with seed loop_attack_seed + i.  None: the reference's loop (clean synthesis only)."""
         rt.require_card_geometry("AWAREEmbedder", frame_length, hop_length, win_length)
         self.frame_length, self.hop_length, self.window, self.win_length = frame_length, hop_length, window, win_length
         self.device = torch.device("cuda")
@@ -45,6 +50,8 @@ class AWAREEmbedder(BaseEmbedder):
         self._sched = get_scheduler(self.scheduler_name, self._opt, num_iterations, **self.scheduler_params)
         self.verbose = verbose
         self.use_graph = use_graph
+        self.loop_attacks = parse_chain(loop_attacks)     # ValueError on an unknown kind / key, prob outside [0, 1], > 4 entries
+        self.loop_attack_seed = int(loop_attack_seed)
         self.conv_pipe = "f16x2"                       # runtime.CONV_PIPES: arithmetic of the detector's conv-block GEMMs
         self.audio_preprocess_pipeline = [WaveformNormalizer(), STFT(frame_length, hop_length, window, win_length), STFTDecomposer()]
         self.audio_postprocess_pipeline = [STFTAssembler(), ISTFT(frame_length, hop_length, window, win_length), WaveformNormalizer()]
@@ -62,7 +69,14 @@ class AWAREEmbedder(BaseEmbedder):
                         band_bins(sample_rate, self.frame_length, self.embedding_bands), win_length=self.win_length)
 
     # ---- batched hot path ----------------------------------------------------------------------
-    def start_session(self, batch: "rt.Batch", sample_rate: int) -> "rt.EmbedSession":
+    def start_session(self, batch: "rt.Batch", sample_rate: int, attack_seeds=None) -> "rt.EmbedSession":
+        sess = self._start_session(batch, sample_rate)
+        if self.loop_attacks:
+            seeds = attack_seeds if attack_seeds is not None else [self.loop_attack_seed + i for i in range(batch.B)]
+            sess.set_loop_attacks(self.loop_attacks, seeds, sample_rate)
+        return sess
+
+    def _start_session(self, batch: "rt.Batch", sample_rate: int) -> "rt.EmbedSession":
         plan = self._plan(sample_rate)
         common = dict(num_iterations=self.num_iterations, tolerance_db=self.tolerance_db, loss=self.loss.name,
                       use_graph=self.use_graph, l1_weight=getattr(self.loss, "l1_weight", 0.0), conv_pipe=self.conv_pipe)
@@ -81,10 +95,11 @@ class AWAREEmbedder(BaseEmbedder):
         return sess
 
     def embed_device(self, audio: torch.Tensor, batch: "rt.Batch", sample_rate: int, watermarks: torch.Tensor,
-                     rescale: torch.Tensor | None = None, session: "rt.EmbedSession" = None):
+                     rescale: torch.Tensor | None = None, session: "rt.EmbedSession" = None, attack_seeds=None):
         """audio: device f32 ragged at batch.in_offsets; watermarks: device [B, n_bits] bipolar.
-        Returns (flat device output at batch.out_offsets, session)."""
-        sess = session or self.start_session(batch, sample_rate)
+        attack_seeds: per-clip seeds of the loop attacks (default loop_attack_seed + clip index; a session passed in keeps
+        the seeds it was started with).  Returns (flat device output at batch.out_offsets, session)."""
+        sess = session or self.start_session(batch, sample_rate, attack_seeds)
         sess.begin(audio, watermarks)
         sess.iterate(self.num_iterations)
         return sess.finish(rescale), sess

@@ -554,6 +554,40 @@ class EmbedSession:
         check(self.lib.aware_embed_set_optimizer(self.h, C.byref(oc), _stream()), "aware_embed_set_optimizer")
         self._opt_table = tab
 
+    def set_loop_attacks(self, chain, seeds, sample_rate: int = 16000):
+        """Attack-aware embedding (EXTENSION; aware_embed_set_loop_attacks): a chain of embedding.loop_attacks entries
+        applied to the normalised synthesis inside every iteration, drawn afresh per step from the per-clip `seeds`
+        (B integers).  Before the first iterate(); an empty chain clears it.  The attacked signal of the last forward pass
+        is `attacked`."""
+        from .embedding import loop_attacks as la
+        chain = la.parse_chain(chain)
+        if not chain:
+            check(self.lib.aware_embed_set_loop_attacks(self.h, None, 0, None, None, 0, _stream()), "aware_embed_set_loop_attacks")
+            self.loop_attacks, self._la_ws = [], None
+            return
+        if len(seeds) != self.batch.B:
+            raise ValueError(f"set_loop_attacks: {self.batch.B} clips but {len(seeds)} seeds")
+        la.check_lengths(chain, sample_rate, self.batch.out_lengths)      # ValueError naming the clip, before any launch
+        ent = la.device_entries(chain, sample_rate)
+        arr = (_lib.LoopAttack * len(ent))(*[_lib.LoopAttack(k, p, pr) for k, p, pr in ent])
+        sd = (C.c_uint32 * self.batch.B)(*[int(s) & 0xFFFFFFFF for s in seeds])
+        nbytes = self.lib.aware_embed_loop_attack_workspace_bytes(self.batch.h, len(ent))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=_dev())
+        rc = self.lib.aware_embed_set_loop_attacks(self.h, arr, len(ent), sd, _ptr(ws), nbytes, _stream())
+        if rc == -1:
+            raise ValueError("set_loop_attacks: refused (it has to precede the first iterate(); see aware_hip.h)")
+        check(rc, "aware_embed_set_loop_attacks")
+        self.loop_attacks, self._la_ws = chain, ws
+
+    @property
+    def attacked(self):
+        """The attacked signal z of the last forward pass (flat, clip b at batch.out_offsets[b]); None without a chain."""
+        p = self.lib.aware_embed_buffer(self.h, 12)
+        if not p:
+            return None
+        off = p - self._la_ws.data_ptr()
+        return self._la_ws[off: off + 4 * self.batch.total_out].view(torch.float32)
+
     def begin(self, audio: torch.Tensor, target: torch.Tensor):
         self._audio, self._target = audio, target.contiguous().float()
         check(self.lib.aware_embed_begin(self.h, _ptr(audio), _ptr(self._target), _stream()), "aware_embed_begin")

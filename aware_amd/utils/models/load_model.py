@@ -17,7 +17,9 @@ _EMBEDDER = {"pattern_mode": ("pattern_mode", "bits2bipolar"), "tolerance_db": (
              "num_iterations": ("num_iterations", 400), "detection_net_cfg": ("detection_net_cfg", {}),
              "optimizer_cfg": ("optimizer_cfg", {"name": "nadam", "params": {"lr": 0.1}}),
              "scheduler_cfg": ("scheduler_cfg", {"name": "reduce_lr_on_plateau", "params": {"factor": 0.9, "patience": 500}}),
-             "loss": ("loss", "push_extremes"), "verbose": ("verbose", True)}
+             "loss": ("loss", "push_extremes"), "verbose": ("verbose", True),
+             # EXTENSION (embedding/loop_attacks.py): attacks inside the optimisation loop; absent = none
+             "loop_attacks": ("loop_attacks", None), "loop_attack_seed": ("loop_attack_seed", 0)}
 _DETECTOR = {"threshold": ("threshold", 0.0), "pattern_mode": ("pattern_mode", "bipolar")}
 
 

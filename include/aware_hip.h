@@ -390,7 +390,8 @@ int aware_embed_profile(aware_embed* e, int n_iters, int max_entries, float* ms_
 int aware_embed_finish(aware_embed* e, const float* rescale, float* out, void* stream);
 /* device pointers to internal state for inspection: 0 loss[B], 1 best_loss[B], 2 pred[B][n_bits],
  * 3 coef [frames][band stride], 4 best coef, 5 lo, 6 hi, 7 phasor (complex64), 8 step counter (int32), 9 un-normalised synthesis,
- * 10 band magnitudes of the last analysis, 11 per-clip learning rates (f64 [B]; NULL unless aware_embed_set_optimizer ran) */
+ * 10 band magnitudes of the last analysis, 11 per-clip learning rates (f64 [B]; NULL unless aware_embed_set_optimizer ran),
+ * 12 the attacked signal z of the last forward pass (layout of 9; NULL unless aware_embed_set_loop_attacks set a chain) */
 void* aware_embed_buffer(aware_embed* e, int which);
 
 /* ---- attacks (scripts/attacks.py) ------------------------------------------------------------------
@@ -487,6 +488,34 @@ size_t aware_stoi_workspace_bytes(int B, int max_len, long long total_len);
 int aware_stoi(const aware_stoi_plan* plan, const float* clean, const int* clean_off, const float* proc,
                const int* proc_off, const int* n, int B, int max_len, long long total_len, double* out, int* kept_out,
                void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- attack-aware embedding (EXTENSION, parity unpinned: the reference optimises against the clean synthesis only) -------
+ * A chain of up to four attacks applied to the normalised synthesis inside every loop iteration, so that the optimiser sees
+ * the attacked signal: for clip b (output length Ny_b) at optimiser step s (the device step counter, aware_embed_buffer 8,
+ * before the iteration advances it; aware_embed_gradient evaluates the current value), seed_b = seeds[b]:
+ *   x = N(N(y)),  N(v) = v / (max|v| + 1e-8),  y the raw synthesis (buffer 9)
+ *   entry j:  r = philox4x32_10(counter (0, s, 1 + j, 1), key (seed_b, 0x5EED));  on = (r[0] + 0.5) / 2^32 < prob
+ *     AWARE_LOOP_SAMPLE_SUPPRESSION, param = samples k:  start = (r[1] * (Ny_b - k)) >> 32;  on: x[start : start + k] = 0
+ *     AWARE_LOOP_GAUSSIAN_NOISE, param = snr_db:  sigma = sqrt(mean(x^2) / 10^(snr_db / 10)) of the current x, a CONSTANT
+ *       in the backward pass;  on: x += sigma * eps, eps_i from philox4x32_10((i / 4, s, 0, j), (seed_b, 0x5EED)) through
+ *       Box-Muller with the lane pairing of aware_gaussian_noise (at s = 0, j = 0 the same noise)
+ *   z = x (buffer 12); the loop's analysis (two normalisers, STFT, band magnitudes) runs on z instead of y.
+ * loss[] and best_loss[] are those of the attacked forward; the backward pass is the exact adjoint with sigma detached;
+ * aware_embed_finish is unchanged (the clean synthesis of the best coefficients).  Works with every loss, optimiser, conv
+ * pipe, read-out, dsp_path, mel form, band layout and batch shape; the step is read from device memory, so the recorded
+ * graphs replay with fresh draws.
+ * To be called after aware_embed_create and before the first aware_embed_iterate (later: AWARE_E_BADARG); n_attacks = 0
+ * clears the chain (workspace and seeds may then be NULL).  seeds: HOST uint32 [B].  workspace: device,
+ * >= aware_embed_loop_attack_workspace_bytes(batch, n_attacks) bytes, 256-byte aligned, alive as long as the handle.
+ * AWARE_E_BADARG: unknown kind, n_attacks outside 0..4, prob outside [0, 1], non-finite snr_db, k < 1 or not an integer;
+ * AWARE_E_UNSUPPORTED: k >= Ny_b for some clip; AWARE_E_WORKSPACE: workspace too small.  Added without a version step:
+ * callers detect the feature by symbol. */
+#define AWARE_LOOP_GAUSSIAN_NOISE 0      /* param = snr_db */
+#define AWARE_LOOP_SAMPLE_SUPPRESSION 1  /* param = samples k (the host converts seconds * sample_rate) */
+typedef struct aware_loop_attack { int kind; float param; float prob; } aware_loop_attack;
+size_t aware_embed_loop_attack_workspace_bytes(const aware_batch* batch, int n_attacks);
+int aware_embed_set_loop_attacks(aware_embed* e, const aware_loop_attack* attacks, int n_attacks, const uint32_t* seeds,
+                                 void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- bare GEMM (tests / roofline): C[M][N] = A[M][K] * Bt[N][K]^T + bias ------------------------------ */
 int aware_gemm_nt(const float* A, int lda, const float* Bt, int ldb, const float* bias, float* C, int ldc,

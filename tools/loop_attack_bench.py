@@ -1,0 +1,102 @@
+"""Attack-aware embedding: what a chain of loop attacks costs per iteration, and what it buys.
+
+  (a) config-3 batch (256 x 3 s): per-iteration time of the graph-replayed loop with no chain, noise only, suppression only and
+      both, from device events over --steps steps (>= 200) after a warm-up, the variants alternating in one process
+      (--rounds rounds; the median over rounds is reported);
+  (b) the BER table at that size: 400-step embeddings without a chain, with noise at 10 dB and with 0.5 s suppression
+      (prob 0.75) in the loop, then clean / Gaussian noise at 10 and 5 dB / 0.5 s and 0.3 s zeroed (--no-ber skips it).
+`--only-loop` runs a few steps of every variant and nothing else, for a per-kernel trace
+(rocprofv3 --kernel-trace --stats -- python tools/loop_attack_bench.py --only-loop)."""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+import torch
+
+from aware_amd import attacks as A
+from aware_amd import runtime as rt
+from aware_amd.utils.models import load
+
+VARIANTS = {
+    "none": None,
+    "noise": [{"kind": "gaussian_noise", "snr_db": 10.0}],
+    "suppression": [{"kind": "sample_suppression", "seconds": 0.5, "prob": 0.75}],
+    "both": [{"kind": "sample_suppression", "seconds": 0.3}, {"kind": "gaussian_noise", "snr_db": 10.0}],
+}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--clips", type=int, default=256)
+    ap.add_argument("--seconds", type=float, default=3.0)
+    ap.add_argument("--steps", type=int, default=208)
+    ap.add_argument("--warmup", type=int, default=32)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--no-ber", action="store_true")
+    ap.add_argument("--only-loop", action="store_true")
+    args = ap.parse_args()
+    B, n = args.clips, int(args.seconds * 16000)
+    emb, det = load()
+    emb.verbose = False
+    g = torch.Generator(device="cuda").manual_seed(3)
+    audio = 0.1 * torch.randn(B * n, generator=g, device="cuda")
+    bits = torch.randint(0, 2, (B, 20), generator=g, device="cuda")
+    target = bits.float() * 2 - 1
+    batch = rt.Batch([n] * B)
+    result = {"clips": B, "seconds": args.seconds, "steps": args.steps}
+
+    sessions = {}
+    for name, chain in VARIANTS.items():
+        emb.loop_attacks = chain or []
+        sessions[name] = emb.start_session(batch, 16000)
+    steps = 16 if args.only_loop else args.steps
+    times = {name: [] for name in VARIANTS}
+    for _ in range(1 if args.only_loop else args.rounds):
+        for name, sess in sessions.items():
+            sess.begin(audio, target)
+            sess.iterate(args.warmup)
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            sess.iterate(steps)
+            b.record()
+            b.synchronize()
+            times[name].append(1e3 * a.elapsed_time(b) / steps)
+    for name in VARIANTS:
+        result[f"us_per_iteration/{name}"] = round(float(np.median(times[name])), 2)
+        print(f"{name:12s} {np.median(times[name]):8.1f} us per iteration (rounds: {', '.join(f'{t:.1f}' for t in times[name])})")
+    base = result["us_per_iteration/none"]
+    for name in ("noise", "suppression", "both"):
+        result[f"extra_us/{name}"] = round(result[f"us_per_iteration/{name}"] - base, 2)
+    del sessions
+
+    if not (args.no_ber or args.only_loop):
+        bits_h = bits.cpu().numpy()
+
+        def ber(x):
+            vals = det.detect_device(x.data, rt.Batch(x.lengths), 16000).cpu().numpy()
+            return 100.0 * float(((vals > 0).astype(np.int64) != bits_h).mean())
+
+        table = {}
+        for name in ("none", "noise", "suppression"):
+            emb.loop_attacks = VARIANTS[name] or []
+            out, _ = emb.embed_device(audio, batch, 16000, target)
+            y = rt.Ragged(torch.cat(batch.unpack_out(out)), batch.out_lengths)
+            row = {"clean": ber(y)}
+            for snr in (10.0, 5.0):
+                row[f"noise_{int(snr)}dB"] = float(np.mean([ber(A.GaussianNoise(snr).apply_batch(y, 16000, seeds=[100000 * s + i for i in range(B)]))
+                                                            for s in range(2)]))
+            for sec in (0.5, 0.3):
+                ny = batch.out_lengths[0]
+                starts = [0, (ny - int(sec * 16000)) // 2, ny - int(sec * 16000) - 1]
+                row[f"zeroed_{sec}s"] = float(np.mean([ber(A.SampleSupression(sec).apply_batch(y, 16000, starts=[st] * B)) for st in starts]))
+            table[name] = {k: round(v, 3) for k, v in row.items()}
+            print(f"BER % embedded with {name:12s}: " + ", ".join(f"{k} {v:.2f}" for k, v in row.items()))
+        result["ber_percent"] = table
+    print(json.dumps(result))
+
+
+if __name__ == "__main__":
+    main()
