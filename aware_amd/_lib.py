@@ -14,7 +14,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AWARE_HIP_LIB") or os.path.join(_HERE, "libaware_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["capi.hip", "dsp_kernels.hip", "dsp_stream.hip", "seam_kernels.hip", "detector_kernels.hip", "gemm_x3.hip", "gemm_h2.hip", "attack_kernels.hip", "stft_any.hip", "stoi_kernels.hip", "loop_attack_kernels.hip"]
+SOURCES = ["capi.hip", "dsp_kernels.hip", "dsp_stream.hip", "seam_kernels.hip", "detector_kernels.hip", "gemm_x3.hip", "gemm_h2.hip", "attack_kernels.hip", "stft_any.hip", "stoi_kernels.hip", "loop_attack_kernels.hip", "loop_reverb_kernels.hip"]
 
 AWARE_OK = 0
 ERRORS = {-1: "bad argument", -2: "unsupported configuration", -3: "HIP runtime error", -4: "workspace too small"}
@@ -74,6 +74,10 @@ class DetectorArch(C.Structure):
 
 class LoopAttack(C.Structure):
     _fields_ = [("kind", C.c_int), ("param", C.c_float), ("prob", C.c_float)]
+
+
+class LoopAttackEx(C.Structure):
+    _fields_ = [("kind", C.c_int), ("prob", C.c_float), ("param", C.c_float * 4)]
 
 
 class OptimizerConfig(C.Structure):
@@ -139,6 +143,11 @@ SIGNATURES = {
     "aware_embed_set_optimizer": (_i, [_vp, C.POINTER(OptimizerConfig), _vp]),
     "aware_embed_loop_attack_workspace_bytes": (_sz, [_vp, _i]),
     "aware_embed_set_loop_attacks": (_i, [_vp, C.POINTER(LoopAttack), _i, C.POINTER(C.c_uint32), _vp, _sz, _vp]),
+    "aware_embed_loop_attack_workspace_bytes_ex": (_sz, [_vp, C.POINTER(LoopAttackEx), _i]),
+    "aware_embed_set_loop_attacks_ex": (_i, [_vp, C.POINTER(LoopAttackEx), _i, C.POINTER(C.c_uint32), _vp, _sz, _vp]),
+    "aware_convolve_workspace_bytes": (_sz, [_i, _i, C.c_longlong, _i]),
+    "aware_convolve": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _sz, _vp]),
+    "aware_reverb_ir": (_i, [_vp, _i, _i, _i, _i, _i, _f, _vp, _i, _vp, _vp]),
     "aware_opt_clamp_step": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(C.c_float), C.POINTER(C.c_float), _vp]),
     "aware_embed_begin": (_i, [_vp, _vp, _vp, _vp]),
     "aware_embed_iterate": (_i, [_vp, _i, _vp]),

@@ -218,6 +218,26 @@ class GaussianNoise(Attack):
 
 
 @register
+class Reverberation(Attack):
+    """EXTENSION (not in the reference, parity unpinned): a synthetic room response -- an exponentially decaying Gaussian
+    tail of int(rt60 * sr) taps, 60 dB down at its end, behind a direct path drr_db above the tail's energy -- convolved with
+    the clip, causal, truncated to the clip's length, not normalised.  Clip i draws the response of seed + i that
+    embedding.loop_attacks.reverb_ir specifies at step 0, entry 0: what a {"kind": "reverberation", "rt60": rt60} entry of
+    the embed loop applies at its first step."""
+
+    def __init__(self, rt60=0.3, drr_db=-3.0, seed=0):
+        self.rt60, self.drr_db, self.seed = float(rt60), float(drr_db), int(seed)
+        self.name = f"reverb_{rt60}"
+
+    def apply_batch(self, x, sr, seeds=None):
+        if seeds is None:
+            seeds = [self.seed + i for i in range(x.B)]
+        n = int(self.rt60 * sr)
+        h, nh = rt.reverb_ir(seeds, 0, 0, n, n, self.drr_db)
+        return rt.convolve(x, h, nh)
+
+
+@register
 class MP3Surrogate(Attack):
     """EXTENSION (not in the reference; BASELINE.json north_star): MP3-like quantisation surrogate
     -- STFT -> per-frame log-magnitude quantisation (`step_db` grid, bins more than `-floor_db` below

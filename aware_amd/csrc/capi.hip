@@ -1710,6 +1710,15 @@ struct aware_embed {
         double* pdot = nullptr;                   // [B][pstride] partial sums of dL/dx * x for the analysis adjoint
         float* gpad0 = nullptr;                   // [B][2][512] zeros: the pads are folded before the analysis adjoint
         unsigned* seeds = nullptr;                // [B]
+        // reverberation (aware_embed_set_loop_attacks_ex): entry rv of the chain, -1 without one
+        int rv = -1, n_lo = 0, n_hi = 0, kmax = 0;
+        double gain = 0;                          // 10^(drr_db / 20)
+        float* u = nullptr;                       // [NS] the convolution's input: the entries in front of it on N(N(yraw))
+        float* h = nullptr;                       // [B][8192] the impulse responses of the last forward pass
+        int* nh = nullptr;                        // [B] their lengths, 0 where the entry did not fire
+        cf* tables = nullptr;                     // W_2048 half table, W_4096 table
+        cf* hspec = nullptr;                      // [B][4][2056]
+        cf* xspec = nullptr;                      // [B][kmax][2056]
         bool locked = false;                      // an optimiser step has run: the chain stays what it is
     } la;
 };
@@ -1912,6 +1921,38 @@ template <typename LA> static void carve_loop_attacks(Carver& c, const aware_bat
     la.gpad0 = c.take<float>((size_t)b->B * 1024);
     la.seeds = c.take<unsigned>(b->B);
 }
+// the reverberation's part of that workspace, behind the chain's
+static int reverb_kmax(const aware_batch* b) {
+    int m = 0;
+    for (int i = 0; i < b->B; ++i) m = std::max(m, b->out_len[i]);
+    return reverb_blocks(m);
+}
+template <typename LA> static void carve_loop_reverb(Carver& c, const aware_batch* b, LA& la) {
+    la.kmax = reverb_kmax(b);
+    la.u = c.take<float>(b->NS);
+    la.h = c.take<float>((size_t)b->B * kReverbMaxIr);
+    la.nh = c.take<int>(b->B);
+    la.tables = c.take<cf>(kReverbTwHalf + kReverbBins);
+    la.hspec = c.take<cf>((size_t)b->B * kReverbParts * kReverbBins);
+    la.xspec = c.take<cf>((size_t)b->B * la.kmax * kReverbBins);
+}
+// W_2048^j, j < 1024, then W_4096^k, k <= 2048 (padded to 2056), from float64
+static const std::vector<cf>& reverb_tables() {
+    static const std::vector<cf> t = [] {
+        std::vector<cf> v(kReverbTwHalf + kReverbBins, mk(0.f, 0.f));
+        const double pi = 3.14159265358979323846;
+        for (int j = 0; j < kReverbTwHalf; ++j) v[j] = mk((float)cos(-2.0 * pi * j / 2048.0), (float)sin(-2.0 * pi * j / 2048.0));
+        for (int k = 0; k <= kReverbBlock; ++k)
+            v[kReverbTwHalf + k] = mk((float)cos(-2.0 * pi * k / 4096.0), (float)sin(-2.0 * pi * k / 4096.0));
+        return v;
+    }();
+    return t;
+}
+static bool has_reverb(const aware_loop_attack_ex* attacks, int n) {
+    for (int j = 0; attacks && j < n; ++j)
+        if (attacks[j].kind == AWARE_LOOP_REVERBERATION) return true;
+    return false;
+}
 extern "C" size_t aware_embed_loop_attack_workspace_bytes(const aware_batch* b, int n_attacks) {
     if (!b || b->general || n_attacks < 1 || n_attacks > kMaxLoopAttacks) return 0;
     Carver c(nullptr, 0);
@@ -1919,25 +1960,43 @@ extern "C" size_t aware_embed_loop_attack_workspace_bytes(const aware_batch* b, 
     carve_loop_attacks(c, b, e.la);
     return c.off;
 }
-extern "C" int aware_embed_set_loop_attacks(aware_embed* e, const aware_loop_attack* attacks, int n_attacks,
-                                            const uint32_t* seeds, void* workspace, size_t workspace_bytes, void* stream) {
-    static_assert(AWARE_LOOP_GAUSSIAN_NOISE == kLoopGaussianNoise && AWARE_LOOP_SAMPLE_SUPPRESSION == kLoopSampleSuppression, "");
+extern "C" size_t aware_embed_loop_attack_workspace_bytes_ex(const aware_batch* b, const aware_loop_attack_ex* attacks,
+                                                             int n_attacks) {
+    if (!b || b->general || !attacks || n_attacks < 1 || n_attacks > kMaxLoopAttacks) return 0;
+    Carver c(nullptr, 0);
+    aware_embed e;
+    carve_loop_attacks(c, b, e.la);
+    if (has_reverb(attacks, n_attacks)) carve_loop_reverb(c, b, e.la);
+    return c.off;
+}
+static int set_loop_attacks(aware_embed* e, const aware_loop_attack_ex* attacks, int n_attacks, bool allow_reverb,
+                            const uint32_t* seeds, void* workspace, size_t workspace_bytes, void* stream) {
+    static_assert(AWARE_LOOP_GAUSSIAN_NOISE == kLoopGaussianNoise && AWARE_LOOP_SAMPLE_SUPPRESSION == kLoopSampleSuppression &&
+                  AWARE_LOOP_REVERBERATION == kLoopReverberation, "");
     if (!e || n_attacks < 0 || n_attacks > kMaxLoopAttacks) return AWARE_E_BADARG;
     if (e->gexec || e->la.locked) return AWARE_E_BADARG;          // before the first aware_embed_iterate, as aware_embed_set_optimizer
-    if (n_attacks == 0) { e->la.n = 0; e->la.z = nullptr; return AWARE_OK; }
+    if (n_attacks == 0) { e->la.n = 0; e->la.z = nullptr; e->la.rv = -1; e->la.h = nullptr; return AWARE_OK; }
     if (!attacks || !seeds || !workspace || ((uintptr_t)workspace & 255)) return AWARE_E_BADARG;
     const aware_batch* b = e->b;
     auto la = e->la;
+    la.rv = -1; la.h = nullptr;
     for (int j = 0; j < n_attacks; ++j) {
-        const aware_loop_attack& a = attacks[j];
+        const aware_loop_attack_ex& a = attacks[j];
         if (!(a.prob >= 0.f && a.prob <= 1.f)) return AWARE_E_BADARG;
         la.kind[j] = a.kind; la.prob[j] = a.prob; la.k[j] = 0; la.inv_snr[j] = 0.0;
         if (a.kind == AWARE_LOOP_GAUSSIAN_NOISE) {
-            if (!std::isfinite(a.param)) return AWARE_E_BADARG;
-            la.inv_snr[j] = pow(10.0, -(double)a.param / 10.0);
+            if (!std::isfinite(a.param[0])) return AWARE_E_BADARG;
+            la.inv_snr[j] = pow(10.0, -(double)a.param[0] / 10.0);
         } else if (a.kind == AWARE_LOOP_SAMPLE_SUPPRESSION) {
-            if (!(a.param >= 1.f) || a.param > 2147483520.f || a.param != floorf(a.param)) return AWARE_E_BADARG;
-            la.k[j] = (int)a.param;
+            if (!(a.param[0] >= 1.f) || a.param[0] > 2147483520.f || a.param[0] != floorf(a.param[0])) return AWARE_E_BADARG;
+            la.k[j] = (int)a.param[0];
+        } else if (a.kind == AWARE_LOOP_REVERBERATION && allow_reverb) {
+            const float lo = a.param[0], hi = a.param[1], drr = a.param[2];
+            if (la.rv >= 0) return AWARE_E_BADARG;                   // one reverberation per chain
+            if (!(lo >= 2.f) || !(hi <= (float)kReverbMaxIr) || !(lo <= hi) || lo != floorf(lo) || hi != floorf(hi) ||
+                !std::isfinite(drr))
+                return AWARE_E_BADARG;
+            la.rv = j; la.n_lo = (int)lo; la.n_hi = (int)hi; la.gain = pow(10.0, (double)drr / 20.0);
         } else {
             return AWARE_E_BADARG;
         }
@@ -1947,13 +2006,79 @@ extern "C" int aware_embed_set_loop_attacks(aware_embed* e, const aware_loop_att
             if (la.kind[j] == AWARE_LOOP_SAMPLE_SUPPRESSION && la.k[j] >= b->out_len[i]) return AWARE_E_UNSUPPORTED;
     Carver c(workspace, workspace_bytes);
     carve_loop_attacks(c, b, la);
+    if (la.rv >= 0) carve_loop_reverb(c, b, la);
     if (!c.ok) return AWARE_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     HIPCHK(hipMemsetAsync(la.gpad0, 0, (size_t)b->B * 1024 * sizeof(float), st));
     HIPCHK(hipMemcpyAsync(la.seeds, seeds, (size_t)b->B * sizeof(unsigned), hipMemcpyHostToDevice, st));
+    if (la.rv >= 0) {
+        const std::vector<cf>& t = reverb_tables();
+        HIPCHK(hipMemcpyAsync(la.tables, t.data(), t.size() * sizeof(cf), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemsetAsync(la.h, 0, (size_t)b->B * kReverbMaxIr * sizeof(float), st));
+        HIPCHK(hipMemsetAsync(la.nh, 0, (size_t)b->B * sizeof(int), st));
+    }
     HIPCHK(hipStreamSynchronize(st));
     la.n = n_attacks;
     e->la = la;
+    return AWARE_OK;
+}
+extern "C" int aware_embed_set_loop_attacks(aware_embed* e, const aware_loop_attack* attacks, int n_attacks,
+                                            const uint32_t* seeds, void* workspace, size_t workspace_bytes, void* stream) {
+    aware_loop_attack_ex ex[kMaxLoopAttacks] = {};
+    for (int j = 0; attacks && j < n_attacks && j < kMaxLoopAttacks; ++j) {
+        ex[j].kind = attacks[j].kind; ex[j].prob = attacks[j].prob; ex[j].param[0] = attacks[j].param;
+    }
+    return set_loop_attacks(e, attacks ? ex : nullptr, n_attacks, false, seeds, workspace, workspace_bytes, stream);
+}
+extern "C" int aware_embed_set_loop_attacks_ex(aware_embed* e, const aware_loop_attack_ex* attacks, int n_attacks,
+                                               const uint32_t* seeds, void* workspace, size_t workspace_bytes, void* stream) {
+    return set_loop_attacks(e, attacks, n_attacks, true, seeds, workspace, workspace_bytes, stream);
+}
+
+// ---- the convolution and the impulse-response draw alone (EXTENSION; attacks.Reverberation, tests) ------------------------
+static void carve_convolve(Carver& c, int B, int kmax, int parts, ConvolveLaunch& L) {
+    L.tables = c.take<cf>(kReverbTwHalf + kReverbBins);
+    L.hspec = c.take<cf>((size_t)B * parts * kReverbBins);
+    L.xspec = c.take<cf>((size_t)B * kmax * kReverbBins);
+}
+static int convolve_parts(int nh_max) { return std::min(kReverbParts, reverb_blocks(nh_max)); }
+extern "C" size_t aware_convolve_workspace_bytes(int B, int max_len, long long total_len, int nh_max) {
+    if (B < 1 || B > 65535 || max_len < 1 || nh_max < 1 || nh_max > kReverbMaxIr || total_len < max_len ||
+        total_len > (long long)B * max_len)
+        return 0;
+    Carver c(nullptr, 0);
+    ConvolveLaunch L;
+    carve_convolve(c, B, reverb_blocks(max_len), convolve_parts(nh_max), L);
+    return c.off;
+}
+extern "C" int aware_convolve(const float* in, const int* off, const int* len, int B, int max_len, const float* h,
+                              int h_stride, const int* nh, int adjoint, float* out, void* workspace, size_t workspace_bytes,
+                              void* stream) {
+    if (!in || !off || !len || !h || !nh || !out || !workspace || ((uintptr_t)workspace & 255)) return AWARE_E_BADARG;
+    if (B < 1 || B > 65535 || max_len < 1 || h_stride < 1 || h_stride > kReverbMaxIr || adjoint < 0 || adjoint > 1)
+        return AWARE_E_BADARG;
+    ConvolveLaunch L;
+    L.B = B; L.kmax = reverb_blocks(max_len); L.parts = convolve_parts(h_stride);
+    Carver c(workspace, workspace_bytes);
+    carve_convolve(c, B, L.kmax, L.parts, L);
+    if (!c.ok) return AWARE_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const std::vector<cf>& t = reverb_tables();
+    HIPCHK(hipMemcpyAsync(const_cast<cf*>(L.tables), t.data(), t.size() * sizeof(cf), hipMemcpyHostToDevice, st));
+    L.in = in; L.out = out; L.off = off; L.len = len; L.h = h; L.h_stride = h_stride; L.nh = nh; L.adjoint = adjoint;
+    launch_convolve(L, st);
+    LAUNCHCHK();
+    return AWARE_OK;
+}
+extern "C" int aware_reverb_ir(const uint32_t* seeds, int B, int step, int entry, int n_lo, int n_hi, float drr_db, float* h,
+                               int h_stride, int* nh, void* stream) {
+    if (!seeds || !h || !nh || B < 1 || B > 65535 || step < 0 || entry < 0 || entry >= kMaxLoopAttacks) return AWARE_E_BADARG;
+    if (n_lo < 2 || n_hi > kReverbMaxIr || n_lo > n_hi || h_stride < n_hi || !std::isfinite(drr_db)) return AWARE_E_BADARG;
+    ReverbIrLaunch L;
+    L.seeds = seeds; L.step_imm = step; L.entry = entry; L.B = B; L.n_lo = n_lo; L.n_hi = n_hi;
+    L.gain = pow(10.0, (double)drr_db / 20.0); L.prob = 1.f; L.h = h; L.h_stride = h_stride; L.nh = nh;
+    launch_reverb_ir(L, (hipStream_t)stream);
+    LAUNCHCHK();
     return AWARE_OK;
 }
 
@@ -1984,6 +2109,7 @@ extern "C" void* aware_embed_buffer(aware_embed* e, int which) {
         case 10: return e->mag;
         case 11: return e->opt.active ? e->opt.d_lr : nullptr;      // per-clip learning rate (double; ReduceLROnPlateau state)
         case 12: return e->la.n ? e->la.z : nullptr;                // the attacked signal of the last forward pass
+        case 13: return (e->la.n && e->la.rv >= 0) ? e->la.h : nullptr;      // its impulse responses, f32 [B][8192]
         default: return nullptr;
     }
 }
@@ -2026,6 +2152,15 @@ extern "C" int aware_embed_begin(aware_embed* e, const float* audio, const float
     return AWARE_OK;
 }
 
+static ConvolveLaunch reverb_launch(const aware_embed* e, const float* in, float* out, int adjoint) {
+    const auto& la = e->la;
+    ConvolveLaunch C;
+    C.tables = la.tables; C.in = in; C.out = out; C.frame_off = e->b->d_frame_off; C.B = e->b->B; C.kmax = la.kmax;
+    C.h = la.h; C.h_stride = kReverbMaxIr; C.nh = la.nh; C.parts = kReverbParts; C.adjoint = adjoint; C.skip_h = adjoint;
+    C.hspec = la.hspec; C.xspec = la.xspec;
+    return C;
+}
+
 // one loop body of AWAREEmbedder._optimize (multibit_embedder.py:95-122)
 static int embed_iteration(aware_embed* e, hipStream_t st, int do_step, float* grad_out) {
     const aware_batch* b = e->b;
@@ -2056,7 +2191,19 @@ static int embed_iteration(aware_embed* e, hipStream_t st, int do_step, float* g
         A.step = e->step; A.seeds = la.seeds; A.n = la.n;
         for (int j = 0; j < la.n; ++j) { A.kind[j] = la.kind[j]; A.k[j] = la.k[j]; A.inv_snr[j] = la.inv_snr[j]; A.prob[j] = la.prob[j]; }
         A.yraw = e->yraw; A.pmaxY = e->pmaxY; A.psq = la.psq; A.z = la.z; A.pmaxZ = la.pmaxZ;
-        launch_loop_attack_forward(A, st);
+        if (la.rv >= 0) { A.idle_plain = 1; A.gpad_out = la.gpad0; }
+        if (la.rv < 0) {
+            launch_loop_attack_forward(A, st);
+        } else {
+            // the entries in front of the reverberation on N(N(yraw)), the convolution, the entries behind it
+            launch_loop_attack_stage(A, 0, la.rv, e->yraw, 1, la.u, nullptr, st);
+            ReverbIrLaunch R;
+            R.seeds = la.seeds; R.step = e->step; R.entry = la.rv; R.B = b->B; R.n_lo = la.n_lo; R.n_hi = la.n_hi;
+            R.gain = la.gain; R.prob = la.prob[la.rv]; R.h = la.h; R.h_stride = kReverbMaxIr; R.nh = la.nh;
+            launch_reverb_ir(R, st);
+            launch_convolve(reverb_launch(e, la.u, la.z, 0), st);
+            launch_loop_attack_stage(A, la.rv + 1, la.n, la.z, 0, la.z, la.pmaxZ, st);
+        }
         LAUNCHCHK(); PROF(K_MISC);
         L.sig = la.z; L.pmax = la.pmaxZ;
     }
@@ -2096,7 +2243,15 @@ static int embed_iteration(aware_embed* e, hipStream_t st, int do_step, float* g
         const bool streamed = dsp == 0 && stream_supported(e->plan->dev);
         A.step_back = do_step ? 1 : 0;                  // the read-out kernel has advanced the counter
         A.gy = e->gy; A.gpad = streamed ? e->gpad : nullptr; A.pdot_in = e->pdot; A.pdot_out = e->la.pdot;
-        launch_loop_attack_backward(A, st);
+        if (e->la.rv < 0) {
+            launch_loop_attack_backward(A, st);
+        } else {
+            // the mirror: normalisers at z and the masks behind the reverberation, the correlation with the same
+            // responses (their spectra are still there), the masks in front of it and the partial sums against x
+            launch_loop_attack_stage_bwd(A, e->la.rv + 1, e->la.n, 1, 0, st);
+            launch_convolve(reverb_launch(e, e->gy, e->gy, 1), st);
+            launch_loop_attack_stage_bwd(A, 0, e->la.rv, 0, 1, st);
+        }
         LAUNCHCHK(); PROF(K_MISC);
     }
     // backward through the normalisers, ISTFT and the assembler; :112-117 NAdam + clamp

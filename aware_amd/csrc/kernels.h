@@ -356,7 +356,7 @@ void launch_stoi(const StoiLaunch& L, hipStream_t st);
 // ---- loop_attack_kernels.hip: attack-aware embedding (EXTENSION): a chain of attacks between the embed loop's synthesis and
 // its analysis, drawn afresh at every optimiser step (aware_embed_set_loop_attacks) --------------------------------------
 constexpr int kMaxLoopAttacks = 4;
-constexpr int kLoopGaussianNoise = 0, kLoopSampleSuppression = 1;      // AWARE_LOOP_* of aware_hip.h
+constexpr int kLoopGaussianNoise = 0, kLoopSampleSuppression = 1, kLoopReverberation = 2;      // AWARE_LOOP_* of aware_hip.h
 struct LoopAttackLaunch {
     const int* frame_off = nullptr;
     const int* pcount = nullptr;          // [B] synthesis runs per clip: the partials' layout
@@ -378,10 +378,56 @@ struct LoopAttackLaunch {
     const float* gpad = nullptr;          // reflect-pad parts of the streaming synthesis adjoint (null: already folded)
     const double* pdot_in = nullptr;
     double* pdot_out = nullptr;
+    // chains with a reverberation: a clip on which no entry fires at a step leaves the plain loop's bits (its maxima are
+    // recorded as 1, the backward stages pass gradient, partial sums and reflect pads through); gpad_out: [B][2][512], the
+    // pads the analysis adjoint then reads (zeros for every other clip)
+    int idle_plain = 0;
+    float* gpad_out = nullptr;
 };
 // x = N(N(yraw)), the chain, z and the partial maxima of |z|: one reduction launch per noise entry, then one pass
 void launch_loop_attack_forward(const LoopAttackLaunch& L, hipStream_t st);
 // gy: dL/d N(N(z)) -> dL/dx in place, pdot_out: partial sums of dL/dx * x
 void launch_loop_attack_backward(const LoopAttackLaunch& L, hipStream_t st);
+// the same in stages, for a chain that a reverberation splits: entries [j0, j1) on src (norm 1: src is the raw synthesis and
+// x = N(N(src)); 0: src is x itself) -> dst (may be src) and, unless null, the partial maxima of |dst|
+void launch_loop_attack_stage(const LoopAttackLaunch& L, int j0, int j1, const float* src, int norm, float* dst,
+                              unsigned long long* pmax, hipStream_t st);
+// backward of entries [j0, j1) on gy in place; at_z: the normalisers' backward at z and the reflect pads come first;
+// dot: the partial sums of the result against x go to pdot_out
+void launch_loop_attack_stage_bwd(const LoopAttackLaunch& L, int j0, int j1, int at_z, int dot, hipStream_t st);
+
+// ---- loop_reverb_kernels.hip: reverberation (EXTENSION): a drawn impulse response per clip and the partitioned FFT
+// convolution that applies it, inside the embed loop (chain kind 2) and stand-alone (aware_convolve, aware_reverb_ir) ----
+constexpr int kReverbMaxIr = 8192;        // taps
+constexpr int kReverbBlock = 2048;        // output samples per block; the transform has 4096 points
+constexpr int kReverbBins = 2056;         // complex values per spectrum row: bins 0..2048 and padding
+constexpr int kReverbParts = 4;           // partitions of 2048 taps
+constexpr int kReverbTwHalf = 1024;       // W_2048^j, j < 1024; then W_4096^k, k <= 2048, padded to kReverbBins
+inline int reverb_blocks(int n) { return (n + kReverbBlock - 1) / kReverbBlock; }
+struct ReverbIrLaunch {
+    const unsigned* seeds = nullptr;      // [B]
+    const int* step = nullptr;            // device step counter, or null: step_imm
+    int step_imm = 0, entry = 0, B = 0;
+    int n_lo = 0, n_hi = 0;               // taps, drawn uniformly in [n_lo, n_hi]
+    double gain = 0;                      // 10^(drr_db / 20)
+    float prob = 1.f;
+    float* h = nullptr; int h_stride = 0; // [B][h_stride], zero beyond the drawn length
+    int* nh = nullptr;                    // [B] the drawn length; 0: the entry does not fire (h is then the unit impulse)
+};
+void launch_reverb_ir(const ReverbIrLaunch& L, hipStream_t st);
+struct ConvolveLaunch {
+    const cf* tables = nullptr;           // kReverbTwHalf + kReverbBins values
+    const float* in = nullptr; float* out = nullptr;     // out may be in
+    const int* off = nullptr; const int* len = nullptr;  // [B] float offset and length of clip b, or
+    const int* frame_off = nullptr;       // the embed loop's layout (common.hpp sig_offset), when off is null
+    int B = 0, kmax = 0;                  // kmax >= blocks of the longest clip
+    const float* h = nullptr; int h_stride = 0; const int* nh = nullptr;
+    int parts = kReverbParts;             // partitions hspec has room for
+    int adjoint = 0;                      // 0: out = (h * in)[0 : len]; 1: out[i] = sum_k h[k] in[i + k]
+    int skip_h = 0;                       // hspec is that of an earlier launch with the same h
+    cf* hspec = nullptr;                  // [B][parts][kReverbBins]
+    cf* xspec = nullptr;                  // [B][kmax][kReverbBins]
+};
+void launch_convolve(const ConvolveLaunch& L, hipStream_t st);
 
 }  // namespace aware

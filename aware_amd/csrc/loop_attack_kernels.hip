@@ -16,6 +16,7 @@
 //   chain_bwd_kernel     the synthesis adjoint's gradient with respect to N(N(z)) -> the gradient with respect to x
 #include "common.hpp"
 #include "kernels.h"
+#include "loop_rng.hpp"
 
 namespace aware {
 
@@ -31,7 +32,14 @@ struct ChainArgs {
     int step_back;                        // 1 when the read-out kernel has advanced the counter since the forward pass
     const unsigned* seeds;                // [B]
     int n;                                // chain entries
-    int upto;                             // chain_kernel: entries applied (sums of squares: the entries in front of `upto`)
+    int j0;                               // first entry of this stage (0 unless a reverberation splits the chain)
+    int upto;                             // entries [j0, upto) are applied (sums of squares: those in front of noise entry `upto`)
+    const float* src;                     // the stage's input, layout of yraw
+    int norm;                             // 1: src is the raw synthesis, x = N(N(src)); 0: src is x itself
+    int at_z;                             // chain_bwd_kernel: the stage ends at z (normalisers' backward, reflect pads folded)
+    int dot;                              // chain_bwd_kernel: the stage starts at x (partial sums of dL/dx * x)
+    int idle_plain;                       // a clip on which no entry fires takes the plain loop's path (chain_idle below)
+    float* gpad_out;                      // [B][2][512] with idle_plain: the pads the analysis adjoint reads, per clip
     int kind[kMaxLoopAttacks];
     int k[kMaxLoopAttacks];               // suppression: samples
     double inv_snr[kMaxLoopAttacks];      // noise: 10^(-snr_db / 10)
@@ -48,47 +56,6 @@ struct ChainArgs {
     const double* pdot_in;                // [B][pstride] partial sums of gy * N(N(z))
     double* pdot_out;                     // [B][pstride] partial sums of dL/dx * x
 };
-
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
-                                              unsigned (&r)[4]) {
-#pragma unroll
-    for (int i = 0; i < 10; ++i) {
-        const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        const unsigned n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-        c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    r[0] = c0; r[1] = c1; r[2] = c2; r[3] = c3;
-}
-
-// Box-Muller in f32 from the 32-bit lanes, arguments reduced in integers so that no bit of the draw is lost where it counts:
-// radius sqrt(-2 ln u), u = (r + 0.5) / 2^32: the upper half of the range goes through log1p of the exact complement
-__device__ __forceinline__ float bm_radius(unsigned r) {
-    float w;
-    if (r & 0x80000000u) w = -log1pf(-(((float)(0u - r) - 0.5f) * 2.3283064365386963e-10f));
-    else w = -logf(((float)r + 0.5f) * 2.3283064365386963e-10f);
-    return sqrtf(2.f * w);
-}
-// (cos, sin) of 2 pi (r + 0.5) / 2^32: the quadrant from the two top bits, the rest as a fraction of a quarter turn
-__device__ __forceinline__ void bm_angle(unsigned r, float& c, float& s) {
-    const float t = ((float)(r & 0x3FFFFFFFu) + 0.5f) * 9.313225746154785e-10f;      // / 2^30
-    float sn, cs;
-    sincospif(0.5f * t, &sn, &cs);
-    const unsigned q = r >> 30;
-    c = (q == 0) ? cs : (q == 1) ? -sn : (q == 2) ? -cs : sn;
-    s = (q == 0) ? sn : (q == 1) ? cs : (q == 2) ? -sn : -cs;
-}
-__device__ __forceinline__ void normal4(unsigned blk, unsigned step, unsigned j, unsigned seed, float (&e)[4]) {
-    unsigned r[4];
-    philox4x32_10(blk, step, 0u, j, seed, 0x5EEDu, r);
-    const float ra = bm_radius(r[0]), rb = bm_radius(r[2]);
-    float c, s;
-    bm_angle(r[1], c, s);
-    e[0] = ra * c; e[1] = ra * s;
-    bm_angle(r[3], c, s);
-    e[2] = rb * c; e[3] = rb * s;
-}
 
 // sum of a clip's f64 partials in a fixed order; all threads of the block call this
 __device__ __forceinline__ double block_sum_d(const double* part, int n, double* dred) {
@@ -108,13 +75,13 @@ struct ChainState {
     float sigma[kMaxLoopAttacks];
 };
 template <bool SIGMA>
-__device__ __forceinline__ ChainState chain_state(const ChainArgs& a, int b, int upto, int Ny, unsigned step, unsigned seed,
-                                                  double* dred) {
+__device__ __forceinline__ ChainState chain_state(const ChainArgs& a, int b, int j0, int upto, int Ny, unsigned step,
+                                                  unsigned seed, double* dred) {
     ChainState cs;
 #pragma unroll
     for (int j = 0; j < kMaxLoopAttacks; ++j) {
         cs.on[j] = false; cs.start[j] = 0; cs.sigma[j] = 0.f;
-        if (j < upto) {
+        if (j >= j0 && j < upto && a.kind[j] != kLoopReverberation) {
             unsigned r[4];
             philox4x32_10(0u, step, 1u + (unsigned)j, 1u, seed, 0x5EEDu, r);
             cs.on[j] = ((double)r[0] + 0.5) * 2.3283064365386963e-10 < (double)a.prob[j];
@@ -127,6 +94,25 @@ __device__ __forceinline__ ChainState chain_state(const ChainArgs& a, int b, int
         }
     }
     return cs;
+}
+
+// With idle_plain (the chains with a reverberation): true when no entry of the whole chain fires for this clip at this step.
+// Such a clip is to leave the plain loop's bits.  Forward: z = N(N(y)) as always, but its maxima are recorded as 1 -- what
+// max|N(N(y))| is to within an ulp -- so the analysis' two normalisers of z are exactly the identity and it sees the bits the
+// plain loop's analysis computes from y.  Backward: the stages hand the synthesis adjoint's gradient, its partial sums
+// and its reflect pads through untouched, so the analysis adjoint gets what it gets without a chain.
+__device__ __forceinline__ bool chain_idle(const ChainArgs& a, unsigned step, unsigned seed) {
+    if (!a.idle_plain) return false;
+    bool any = false;
+#pragma unroll
+    for (int j = 0; j < kMaxLoopAttacks; ++j) {
+        if (j < a.n) {
+            unsigned r[4];
+            philox4x32_10(0u, step, 1u + (unsigned)j, 1u, seed, 0x5EEDu, r);
+            any = any || ((double)r[0] + 0.5) * 2.3283064365386963e-10 < (double)a.prob[j];
+        }
+    }
+    return !any;
 }
 
 // WRITE = false: partial sums of x^2 with the entries in front of `upto` applied; true: the whole chain, z and max|z|
@@ -142,11 +128,11 @@ __global__ __launch_bounds__(kLaThreads) void chain_kernel(ChainArgs a) {
     const int Ny = kHop * nblk;
     const int so = sig_offset(a.frame_off, b);
     const ClipNorm cn = clip_norm_from_partials(a.pmaxY + (size_t)b * a.pstride, a.pcount[b], red);
-    const float inv_m = 1.0f / cn.m, inv_m2 = 1.0f / cn.m2;
+    const float inv_m = a.norm ? 1.0f / cn.m : 1.0f, inv_m2 = a.norm ? 1.0f / cn.m2 : 1.0f;
     const unsigned step = (unsigned)(*a.step - a.step_back), seed = a.seeds[b];
-    const ChainState cs = chain_state<true>(a, b, a.upto, Ny, step, seed, dred);
+    const ChainState cs = chain_state<true>(a, b, a.j0, a.upto, Ny, step, seed, dred);
 
-    const float4* y4 = reinterpret_cast<const float4*>(a.yraw + so);
+    const float4* y4 = reinterpret_cast<const float4*>(a.src + so);
     float4* z4 = reinterpret_cast<float4*>(a.z + so);
     unsigned long long best = 0;
     double acc = 0.0;
@@ -156,7 +142,7 @@ __global__ __launch_bounds__(kLaThreads) void chain_kernel(ChainArgs a) {
         const int i0 = 4 * q;
 #pragma unroll
         for (int j = 0; j < kMaxLoopAttacks; ++j) {
-            if (j < a.upto && cs.on[j]) {
+            if (j >= a.j0 && j < a.upto && cs.on[j]) {
                 if (a.kind[j] == kLoopSampleSuppression) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e)
@@ -182,7 +168,11 @@ __global__ __launch_bounds__(kLaThreads) void chain_kernel(ChainArgs a) {
         best = wave_max64(best);
         if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = best;
         __syncthreads();
-        if (threadIdx.x == 0) a.pmaxZ[(size_t)b * a.pstride + blockIdx.x] = umax64(umax64(red[0], red[1]), umax64(red[2], red[3]));
+        if (threadIdx.x == 0 && a.pmaxZ) {
+            unsigned long long m = umax64(umax64(red[0], red[1]), umax64(red[2], red[3]));
+            if (chain_idle(a, step, seed)) m = (0x3F800000ull << 32) | (m & 0xFFFFFFFFull);      // max|z| := 1.0f
+            a.pmaxZ[(size_t)b * a.pstride + blockIdx.x] = m;
+        }
     } else {
         acc = wave_sum_d(acc);
         __syncthreads();
@@ -207,18 +197,38 @@ __global__ __launch_bounds__(kLaThreads) void chain_bwd_kernel(ChainArgs a) {
     const int Ny = kHop * nblk;
     const int so = sig_offset(a.frame_off, b);
     const ClipNorm cy = clip_norm_from_partials(a.pmaxY + (size_t)b * a.pstride, a.pcount[b], red);
-    const ClipNorm cz = clip_norm_from_partials(a.pmaxZ + (size_t)b * a.pstride, a.pcount[b], red);
+    ClipNorm cz = clip_norm_from_partials(a.pmaxZ + (size_t)b * a.pstride, a.pcount[b], red);
     const float inv_m = 1.0f / cy.m, inv_m2 = 1.0f / cy.m2;
-    const float inv_mm2 = 1.0f / (cz.m * cz.m2);
-    const float adot = (float)block_sum_d(a.pdot_in + (size_t)b * a.pstride, a.pcount[b], dred);
-    const float zk = a.z[so + min(cz.k, (unsigned)(Ny - 1))];
-    const float corr = adot * ((zk > 0.f) ? 1.f : ((zk < 0.f) ? -1.f : 0.f));
+    float inv_mm2 = 1.0f / (cz.m * cz.m2);
+    float corr = 0.f;
+    if (a.at_z) {
+        const float adot = (float)block_sum_d(a.pdot_in + (size_t)b * a.pstride, a.pcount[b], dred);
+        const float zk = a.z[so + min(cz.k, (unsigned)(Ny - 1))];
+        corr = adot * ((zk > 0.f) ? 1.f : ((zk < 0.f) ? -1.f : 0.f));
+    } else {
+        cz.k = 0xFFFFFFFFu;                  // a stage in front of a reverberation: masks and the dot product only
+        inv_mm2 = 1.0f;
+    }
     const unsigned step = (unsigned)(*a.step - a.step_back), seed = a.seeds[b];
-    const ChainState cs = chain_state<false>(a, b, a.n, Ny, step, seed, dred);
+    const bool idle = chain_idle(a, step, seed);
+    if (a.dot && a.gpad_out && blockIdx.x == 0) {
+        // the pads the analysis adjoint reads: folded into gy already (zeros), or the synthesis adjoint's own for an idle clip
+        float* po = a.gpad_out + (size_t)b * 1024;
+        const float* pi = (idle && a.gpad) ? a.gpad + (size_t)b * 1024 : nullptr;
+        for (int i = threadIdx.x; i < 1024; i += kLaThreads) po[i] = pi ? pi[i] : 0.f;
+    }
+    if (idle) {
+        if (a.dot && threadIdx.x == 0) {
+            const size_t i = (size_t)b * a.pstride + blockIdx.x;
+            a.pdot_out[i] = a.pdot_in[i];
+        }
+        return;
+    }
+    const ChainState cs = chain_state<false>(a, b, a.j0, a.upto, Ny, step, seed, dred);
 
     const float4* y4 = reinterpret_cast<const float4*>(a.yraw + so);
     float4* g4 = reinterpret_cast<float4*>(a.gy + so);
-    const float* gpL = a.gpad ? a.gpad + (size_t)b * 1024 : nullptr;
+    const float* gpL = (a.gpad && a.at_z) ? a.gpad + (size_t)b * 1024 : nullptr;
     const float* gpR = gpL ? gpL + 512 : nullptr;
     double dot = 0.0;
     for (int q = jb0 * (kHop / 4) + threadIdx.x; q < jb1 * (kHop / 4); q += kLaThreads) {
@@ -244,7 +254,7 @@ __global__ __launch_bounds__(kLaThreads) void chain_bwd_kernel(ChainArgs a) {
         }
 #pragma unroll
         for (int j = 0; j < kMaxLoopAttacks; ++j) {
-            if (j < a.n && cs.on[j] && a.kind[j] == kLoopSampleSuppression) {
+            if (j >= a.j0 && j < a.upto && cs.on[j] && a.kind[j] == kLoopSampleSuppression) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
                     if ((unsigned)(i0 + e - cs.start[j]) < (unsigned)a.k[j]) g[e] = 0.f;
@@ -254,6 +264,7 @@ __global__ __launch_bounds__(kLaThreads) void chain_bwd_kernel(ChainArgs a) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) dot += (double)g[e] * (double)x[e];
     }
+    if (!a.dot) return;
     dot = wave_sum_d(dot);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) dred[threadIdx.x >> 6] = dot;
@@ -264,7 +275,8 @@ __global__ __launch_bounds__(kLaThreads) void chain_bwd_kernel(ChainArgs a) {
 ChainArgs chain_args(const LoopAttackLaunch& L) {
     ChainArgs a{};
     a.frame_off = L.frame_off; a.pcount = L.pcount; a.pstride = L.pstride; a.run_blocks = L.run_blocks;
-    a.step = L.step; a.step_back = L.step_back; a.seeds = L.seeds; a.n = L.n; a.upto = L.n; a.B = L.B;
+    a.step = L.step; a.step_back = L.step_back; a.seeds = L.seeds; a.n = L.n; a.j0 = 0; a.upto = L.n; a.B = L.B;
+    a.src = L.yraw; a.norm = 1; a.at_z = 1; a.dot = 1; a.idle_plain = L.idle_plain; a.gpad_out = L.gpad_out;
     for (int j = 0; j < kMaxLoopAttacks; ++j) {
         a.kind[j] = j < L.n ? L.kind[j] : 0;
         a.k[j] = j < L.n ? L.k[j] : 0;
@@ -278,22 +290,33 @@ ChainArgs chain_args(const LoopAttackLaunch& L) {
 
 }  // namespace
 
-void launch_loop_attack_forward(const LoopAttackLaunch& L, hipStream_t st) {
+void launch_loop_attack_stage(const LoopAttackLaunch& L, int j0, int j1, const float* src, int norm, float* dst,
+                              unsigned long long* pmax, hipStream_t st) {
     ChainArgs a = chain_args(L);
+    a.j0 = j0; a.src = src; a.norm = norm; a.z = dst; a.pmaxZ = pmax;
     const dim3 grid((unsigned)L.pstride, (unsigned)L.B, 1);
     // a noise entry's amplitude follows the power of the signal in front of it: one reduction per noise entry, in order
-    for (int j = 0; j < L.n; ++j) {
+    for (int j = j0; j < j1; ++j) {
         if (L.kind[j] != kLoopGaussianNoise) continue;
         a.upto = j;
         hipLaunchKernelGGL(chain_kernel<false>, grid, dim3(kLaThreads), 0, st, a);
     }
-    a.upto = L.n;
+    a.upto = j1;
     hipLaunchKernelGGL(chain_kernel<true>, grid, dim3(kLaThreads), 0, st, a);
 }
 
-void launch_loop_attack_backward(const LoopAttackLaunch& L, hipStream_t st) {
-    const ChainArgs a = chain_args(L);
+void launch_loop_attack_stage_bwd(const LoopAttackLaunch& L, int j0, int j1, int at_z, int dot, hipStream_t st) {
+    ChainArgs a = chain_args(L);
+    a.j0 = j0; a.upto = j1; a.at_z = at_z; a.dot = dot;
     hipLaunchKernelGGL(chain_bwd_kernel, dim3((unsigned)L.pstride, (unsigned)L.B, 1), dim3(kLaThreads), 0, st, a);
+}
+
+void launch_loop_attack_forward(const LoopAttackLaunch& L, hipStream_t st) {
+    launch_loop_attack_stage(L, 0, L.n, L.yraw, 1, L.z, L.pmaxZ, st);
+}
+
+void launch_loop_attack_backward(const LoopAttackLaunch& L, hipStream_t st) {
+    launch_loop_attack_stage_bwd(L, 0, L.n, 1, 1, st);
 }
 
 }  // namespace aware

@@ -11,6 +11,13 @@ the loop's new stage.  For clip b (length Ny) at optimiser step s with seed_b:
         eps_i from philox4x32_10((i // 4, s, 0, j), (seed_b, 0x5EED)), lanes paired through Box-Muller as the post-hoc
         GaussianNoise attack pairs them (at s = 0, j = 0 the two draw the same noise)
 
+      reverberation(rt60 = lo or [lo, hi] seconds, drr_db), n_lo = int(lo * sample_rate), n_hi = int(hi * sample_rate):
+        n_h = n_lo + ((r[2] * (n_hi - n_lo + 1)) >> 32) taps;  tail t_i = eps_i exp(-ln(1000) i / n_h), 1 <= i < n_h, eps the
+        normals of normal_draws with the third counter word 8 (index 0 drawn and discarded);  direct path
+        h_0 = 10^(drr_db / 20) sqrt(sum t_i^2);  on: x = (h * x)[0:Ny], h detached (the backward pass is the correlation with
+        h).  At most one per chain; a noise entry behind it takes its sigma from the convolved signal.  At s = 0, j = 0 and a
+        scalar rt60 this is the post-hoc attacks.Reverberation of the same seed.
+
 In the loop x = N(N(y)) of the raw synthesis y, N(v) = v / (max|v| + 1e-8), and the analysis (N, N, STFT, band magnitudes)
 runs on the chain's output."""
 from __future__ import annotations
@@ -21,15 +28,20 @@ import numpy as np
 import torch
 
 MAX_ATTACKS = 4
-KINDS = {"gaussian_noise": 0, "sample_suppression": 1}          # AWARE_LOOP_* of include/aware_hip.h
-_KEYS = {"gaussian_noise": {"kind", "snr_db", "prob"}, "sample_suppression": {"kind", "seconds", "prob"}}
+KINDS = {"gaussian_noise": 0, "sample_suppression": 1, "reverberation": 2}          # AWARE_LOOP_* of include/aware_hip.h
+_KEYS = {"gaussian_noise": {"kind", "snr_db", "prob"}, "sample_suppression": {"kind", "seconds", "prob"},
+         "reverberation": {"kind", "rt60", "drr_db", "prob"}}
 _KEY1 = 0x5EED
+MAX_IR = 8192                   # taps of the longest impulse response
+_IR_WORD = 8                    # third Philox counter word of the impulse responses (0: noise, 1..4: entry draws)
 
 
 def parse_chain(chain) -> list[dict]:
     """Validated copy of a chain such as [{"kind": "gaussian_noise", "snr_db": 10.0, "prob": 1.0},
     {"kind": "sample_suppression", "seconds": 0.3, "prob": 0.75}] (None / empty: no chain).  ValueError: unknown kind or key,
-    a missing parameter, prob outside [0, 1], a non-finite snr_db, seconds <= 0, more than four entries."""
+    a missing parameter, prob outside [0, 1], a non-finite snr_db, seconds <= 0, more than four entries; for
+    {"kind": "reverberation", "rt60": 0.3 | [0.1, 0.5], "drr_db": -3.0}: a missing rt60, rt60 not 0 < lo <= hi (finite), a
+    non-finite drr_db, a second reverberation."""
     if not chain:
         return []
     if isinstance(chain, dict) or not isinstance(chain, (list, tuple)):
@@ -53,6 +65,22 @@ def parse_chain(chain) -> list[dict]:
             if "snr_db" not in a or not math.isfinite(float(a["snr_db"])):
                 raise ValueError(f"loop_attacks[{j}] (gaussian_noise): a finite snr_db is required")
             e["snr_db"] = float(a["snr_db"])
+        elif kind == "reverberation":
+            if any(o["kind"] == "reverberation" for o in out):
+                raise ValueError(f"loop_attacks[{j}] (reverberation): at most one reverberation per chain")
+            if "rt60" not in a:
+                raise ValueError(f"loop_attacks[{j}] (reverberation): rt60 is required")
+            rt = a["rt60"]
+            try:
+                lo, hi = (float(rt[0]), float(rt[1])) if isinstance(rt, (list, tuple)) and len(rt) == 2 else (float(rt), float(rt))
+            except (TypeError, ValueError):
+                raise ValueError(f"loop_attacks[{j}] (reverberation): rt60 = {rt!r} is neither a number nor [lo, hi]") from None
+            if not (math.isfinite(lo) and math.isfinite(hi) and 0.0 < lo <= hi):
+                raise ValueError(f"loop_attacks[{j}] (reverberation): rt60 needs 0 < lo <= hi, both finite; got {rt!r}")
+            drr = float(a.get("drr_db", -3.0))
+            if not math.isfinite(drr):
+                raise ValueError(f"loop_attacks[{j}] (reverberation): a finite drr_db is required")
+            e["rt60"], e["drr_db"] = [lo, hi], drr
         else:
             if "seconds" not in a or not math.isfinite(float(a["seconds"])) or float(a["seconds"]) <= 0.0:
                 raise ValueError(f"loop_attacks[{j}] (sample_suppression): seconds > 0 is required")
@@ -66,9 +94,21 @@ def suppression_samples(entry: dict, sample_rate: int) -> int:
     return int(entry["seconds"] * sample_rate)
 
 
+def reverb_taps(entry: dict, sample_rate: int) -> tuple[int, int]:
+    """(n_lo, n_hi) = (int(lo * sample_rate), int(hi * sample_rate)) of a parsed reverberation entry."""
+    return int(entry["rt60"][0] * sample_rate), int(entry["rt60"][1] * sample_rate)
+
+
 def check_lengths(chain: list[dict], sample_rate: int, out_lengths) -> None:
-    """ValueError naming the first clip that a suppression would not fit into (0 < k < Ny_b is required)."""
+    """ValueError naming the first clip that a suppression would not fit into (0 < k < Ny_b is required), or a reverberation
+    whose impulse response would have fewer than 2 or more than MAX_IR taps at this sample rate."""
     for j, a in enumerate(chain):
+        if a["kind"] == "reverberation":
+            n_lo, n_hi = reverb_taps(a, sample_rate)
+            if n_lo < 2 or n_hi > MAX_IR:
+                raise ValueError(f"loop_attacks[{j}] (reverberation): rt60 = {a['rt60']} s is {n_lo}..{n_hi} taps at "
+                                 f"{sample_rate} Hz, outside 2..{MAX_IR}")
+            continue
         if a["kind"] != "sample_suppression":
             continue
         k = suppression_samples(a, sample_rate)
@@ -109,19 +149,44 @@ def suppression_start(r1: int, ny: int, k: int) -> int:
     return (int(r1) * (int(ny) - int(k))) >> 32
 
 
-def normal_draws(n: int, seed: int, step: int, j: int) -> np.ndarray:
-    """n standard normal draws (float64) of noise entry j at this step: counter (i // 4, step, 0, j), key (seed, 0x5EED),
-    u = (r + 0.5) / 2^32, z0 = sqrt(-2 ln u0) cos(2 pi u1), z1 = sqrt(-2 ln u0) sin(2 pi u1), z2 / z3 from lanes 2 and 3."""
+def normal_draws(n: int, seed: int, step: int, j: int, word: int = 0) -> np.ndarray:
+    """n standard normal draws (float64) of noise entry j at this step: counter (i // 4, step, word, j), key (seed, 0x5EED),
+    u = (r + 0.5) / 2^32, z0 = sqrt(-2 ln u0) cos(2 pi u1), z1 = sqrt(-2 ln u0) sin(2 pi u1), z2 / z3 from lanes 2 and 3.
+    word 0 is the noise entries' stream; the impulse responses draw from word 8."""
     nblk = (n + 3) // 4
     ctr = np.zeros((nblk, 4), dtype=np.uint64)
     ctr[:, 0] = np.arange(nblk, dtype=np.uint64)
     ctr[:, 1] = step
+    ctr[:, 2] = word
     ctr[:, 3] = j
     u = (philox4x32(ctr, (seed, _KEY1)).astype(np.float64) + 0.5) / 4294967296.0
     r0, r1 = np.sqrt(-2.0 * np.log(u[:, 0])), np.sqrt(-2.0 * np.log(u[:, 2]))
     z = np.stack([r0 * np.cos(2 * np.pi * u[:, 1]), r0 * np.sin(2 * np.pi * u[:, 1]),
                   r1 * np.cos(2 * np.pi * u[:, 3]), r1 * np.sin(2 * np.pi * u[:, 3])], axis=1)
     return z.reshape(-1)[:n]
+
+
+def reverb_length(r2: int, n_lo: int, n_hi: int) -> int:
+    """n_h = n_lo + ((r2 * (n_hi - n_lo + 1)) >> 32): uniform on [n_lo, n_hi], in integers as the device computes it."""
+    return int(n_lo) + ((int(r2) * (int(n_hi) - int(n_lo) + 1)) >> 32)
+
+
+def reverb_ir(seed: int, step: int, j: int, n_h: int, drr_db: float) -> np.ndarray:
+    """The n_h taps (float64) of entry j's impulse response at this step: an exponentially decaying Gaussian tail that is
+    60 dB down at n_h, and a direct path h_0 whose energy is drr_db above the tail's."""
+    i = np.arange(n_h, dtype=np.float64)
+    h = normal_draws(n_h, int(seed) & 0xFFFFFFFF, step, j, _IR_WORD) * np.exp(-math.log(1000.0) * i / n_h)
+    h[0] = 0.0
+    h[0] = 10.0 ** (drr_db / 20.0) * math.sqrt(float(np.sum(h * h)))
+    return h
+
+
+def _convolve(xb: torch.Tensor, h: np.ndarray) -> torch.Tensor:
+    """(h * xb)[0 : len(xb)] in xb's dtype through an FFT at least len(xb) + len(h) - 1 long; differentiable in xb."""
+    ny, nh = xb.shape[-1], len(h)
+    n = 1 << int(math.ceil(math.log2(ny + nh - 1)))
+    ht = torch.as_tensor(h).to(dtype=xb.dtype, device=xb.device)
+    return torch.fft.irfft(torch.fft.rfft(xb, n) * torch.fft.rfft(ht, n), n)[..., :ny]
 
 
 def apply_chain(x, chain, seeds, step: int, sample_rate: int = 16000):
@@ -147,6 +212,10 @@ def apply_chain(x, chain, seeds, step: int, sample_rate: int = 16000):
                     mask = torch.ones(ny, dtype=xb.dtype, device=xb.device)
                     mask[start:start + k] = 0
                     xb = xb * mask
+            elif a["kind"] == "reverberation":
+                n_h = reverb_length(r[2], *reverb_taps(a, sample_rate))
+                if on:
+                    xb = _convolve(xb, reverb_ir(seed, step, j, n_h, a["drr_db"]))
             elif on:
                 power = float(np.mean(xb.detach().double().cpu().numpy() ** 2))
                 sigma = math.sqrt(power / (10.0 ** (a["snr_db"] / 10.0)))
@@ -156,7 +225,22 @@ def apply_chain(x, chain, seeds, step: int, sample_rate: int = 16000):
     return torch.stack(out) if torch.is_tensor(x) else out
 
 
+def device_entries_ex(chain: list[dict], sample_rate: int):
+    """(kind, prob, [param0..3]) of the C ABI's aware_loop_attack_ex: kinds 0 and 1 as device_entries in param[0]; a
+    reverberation has param = [n_lo, n_hi, drr_db, 0]."""
+    out = []
+    for a in chain:
+        if a["kind"] == "reverberation":
+            n_lo, n_hi = reverb_taps(a, sample_rate)
+            out.append((KINDS[a["kind"]], a["prob"], [float(n_lo), float(n_hi), a["drr_db"], 0.0]))
+        else:
+            k, p, pr = device_entries([a], sample_rate)[0]
+            out.append((k, pr, [p, 0.0, 0.0, 0.0]))
+    return out
+
+
 def device_entries(chain: list[dict], sample_rate: int):
-    """(kind, param, prob) triples of the C ABI (aware_loop_attack): param = snr_db or the suppression length in samples."""
+    """(kind, param, prob) triples of the C ABI (aware_loop_attack): param = snr_db or the suppression length in samples.
+    Chains of these two kinds only; a reverberation goes through device_entries_ex."""
     return [(KINDS[a["kind"]], a["snr_db"] if a["kind"] == "gaussian_noise" else float(suppression_samples(a, sample_rate)),
              a["prob"]) for a in chain]

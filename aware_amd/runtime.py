@@ -568,12 +568,20 @@ class EmbedSession:
         if len(seeds) != self.batch.B:
             raise ValueError(f"set_loop_attacks: {self.batch.B} clips but {len(seeds)} seeds")
         la.check_lengths(chain, sample_rate, self.batch.out_lengths)      # ValueError naming the clip, before any launch
-        ent = la.device_entries(chain, sample_rate)
-        arr = (_lib.LoopAttack * len(ent))(*[_lib.LoopAttack(k, p, pr) for k, p, pr in ent])
         sd = (C.c_uint32 * self.batch.B)(*[int(s) & 0xFFFFFFFF for s in seeds])
-        nbytes = self.lib.aware_embed_loop_attack_workspace_bytes(self.batch.h, len(ent))
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=_dev())
-        rc = self.lib.aware_embed_set_loop_attacks(self.h, arr, len(ent), sd, _ptr(ws), nbytes, _stream())
+        if any(a["kind"] == "reverberation" for a in chain):
+            # the entry points with four parameters per entry; chains of the two older kinds keep the older call
+            ent = la.device_entries_ex(chain, sample_rate)
+            arr = (_lib.LoopAttackEx * len(ent))(*[_lib.LoopAttackEx(k, pr, (C.c_float * 4)(*p)) for k, pr, p in ent])
+            nbytes = self.lib.aware_embed_loop_attack_workspace_bytes_ex(self.batch.h, arr, len(ent))
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=_dev())
+            rc = self.lib.aware_embed_set_loop_attacks_ex(self.h, arr, len(ent), sd, _ptr(ws), nbytes, _stream())
+        else:
+            ent = la.device_entries(chain, sample_rate)
+            arr = (_lib.LoopAttack * len(ent))(*[_lib.LoopAttack(k, p, pr) for k, p, pr in ent])
+            nbytes = self.lib.aware_embed_loop_attack_workspace_bytes(self.batch.h, len(ent))
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=_dev())
+            rc = self.lib.aware_embed_set_loop_attacks(self.h, arr, len(ent), sd, _ptr(ws), nbytes, _stream())
         if rc == -1:
             raise ValueError("set_loop_attacks: refused (it has to precede the first iterate(); see aware_hip.h)")
         check(rc, "aware_embed_set_loop_attacks")
@@ -587,6 +595,16 @@ class EmbedSession:
             return None
         off = p - self._la_ws.data_ptr()
         return self._la_ws[off: off + 4 * self.batch.total_out].view(torch.float32)
+
+    @property
+    def impulse_responses(self):
+        """The reverberation's impulse responses of the last forward pass, [B, 8192] (zero beyond the drawn length, the unit
+        impulse where the entry did not fire); None unless the chain has a reverberation."""
+        p = self.lib.aware_embed_buffer(self.h, 13)
+        if not p:
+            return None
+        off = p - self._la_ws.data_ptr()
+        return self._la_ws[off: off + 4 * 8192 * self.batch.B].view(torch.float32).view(self.batch.B, 8192)
 
     def begin(self, audio: torch.Tensor, target: torch.Tensor):
         self._audio, self._target = audio, target.contiguous().float()
@@ -858,6 +876,41 @@ def gaussian_noise(x: Ragged, snr_db: float, seeds: Sequence[int]) -> Ragged:
     scr = torch.empty(x.B * 8 + 64, dtype=torch.uint8, device=dev)
     check(lib.aware_gaussian_noise(_ptr(x.data), _ptr(out.data), _ptr(x.d_off), _ptr(x.d_len), x.B, x.max_len, _ptr(sd),
                                    float(snr_db), _ptr(scr), _stream()), "aware_gaussian_noise")
+    return out
+
+
+def reverb_ir(seeds: Sequence[int], step: int, entry: int, n_lo: int, n_hi: int, drr_db: float, stride: int = 8192):
+    """The impulse responses embedding.loop_attacks.reverb_ir specifies, drawn on the device (aware_reverb_ir): (h [B, stride]
+    float32, zero beyond the drawn length, and the lengths [B] int32) for the clips' seeds at optimiser step `step`, chain
+    entry `entry`, lengths uniform on [n_lo, n_hi]."""
+    lib = load_library()
+    dev = _dev()
+    sd = torch.from_numpy(np.array([int(s) & 0xFFFFFFFF for s in seeds], dtype=np.uint32).view(np.int32)).to(dev)
+    h = torch.empty((len(seeds), int(stride)), dtype=torch.float32, device=dev)
+    nh = torch.empty(len(seeds), dtype=torch.int32, device=dev)
+    rc = lib.aware_reverb_ir(_ptr(sd), len(seeds), int(step), int(entry), int(n_lo), int(n_hi), float(drr_db), _ptr(h),
+                             int(stride), _ptr(nh), _stream())
+    if rc == -1:
+        raise ValueError(f"reverb_ir: 2 <= n_lo <= n_hi <= min(8192, stride) and a finite drr_db are required; got "
+                         f"{n_lo}, {n_hi}, stride {stride}, {drr_db}")
+    check(rc, "aware_reverb_ir")
+    return h, nh
+
+
+def convolve(x: Ragged, h: torch.Tensor, nh: torch.Tensor, adjoint: bool = False) -> Ragged:
+    """Per clip (h_b * x_b)[0 : n_b], causal and truncated, or with adjoint its transpose out[i] = sum_k h_b[k] x_b[i + k]
+    (aware_convolve: partitioned FFT convolution).  h: device float32 [B, stride <= 8192], nh: device int32 [B] taps."""
+    lib = load_library()
+    if h.dim() != 2 or h.shape[0] != x.B or nh.numel() != x.B or not 1 <= h.shape[1] <= 8192:
+        raise ValueError(f"convolve: h [B, <= 8192] and nh [B] are required for B = {x.B}; got {tuple(h.shape)}, {tuple(nh.shape)}")
+    h = h.contiguous().float()
+    nh = nh.contiguous().to(torch.int32)
+    xin = x.data if x.data.dtype == torch.float32 else x.data.float()
+    out = Ragged(torch.empty_like(xin), x.lengths)
+    nbytes = lib.aware_convolve_workspace_bytes(x.B, x.max_len, sum(x.lengths), h.shape[1])
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=xin.device)
+    check(lib.aware_convolve(_ptr(xin), _ptr(x.d_off), _ptr(x.d_len), x.B, x.max_len, _ptr(h), h.shape[1], _ptr(nh),
+                             int(bool(adjoint)), _ptr(out.data), _ptr(ws), nbytes, _stream()), "aware_convolve")
     return out
 
 

@@ -391,7 +391,8 @@ int aware_embed_finish(aware_embed* e, const float* rescale, float* out, void* s
 /* device pointers to internal state for inspection: 0 loss[B], 1 best_loss[B], 2 pred[B][n_bits],
  * 3 coef [frames][band stride], 4 best coef, 5 lo, 6 hi, 7 phasor (complex64), 8 step counter (int32), 9 un-normalised synthesis,
  * 10 band magnitudes of the last analysis, 11 per-clip learning rates (f64 [B]; NULL unless aware_embed_set_optimizer ran),
- * 12 the attacked signal z of the last forward pass (layout of 9; NULL unless aware_embed_set_loop_attacks set a chain) */
+ * 12 the attacked signal z of the last forward pass (layout of 9; NULL unless aware_embed_set_loop_attacks set a chain)
+ * 13 the impulse responses of the last forward pass (NULL unless the chain has a reverberation; see below) */
 void* aware_embed_buffer(aware_embed* e, int which);
 
 /* ---- attacks (scripts/attacks.py) ------------------------------------------------------------------
@@ -516,6 +517,43 @@ typedef struct aware_loop_attack { int kind; float param; float prob; } aware_lo
 size_t aware_embed_loop_attack_workspace_bytes(const aware_batch* batch, int n_attacks);
 int aware_embed_set_loop_attacks(aware_embed* e, const aware_loop_attack* attacks, int n_attacks, const uint32_t* seeds,
                                  void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- reverberation inside the loop and as an attack (EXTENSION, parity unpinned: the reference has neither) ---------------
+ * The two entry points above keep their behaviour (kind 2 stays AWARE_E_BADARG there).  The _ex pair takes entries with four
+ * parameters and, besides kinds 0 and 1 (param[0] as above; the same launches and results as through the old call), accepts
+ *   AWARE_LOOP_REVERBERATION, param = { n_lo, n_hi, drr_db }: with r the entry's draw as above and
+ *     n_h = n_lo + ((r[2] * (n_hi - n_lo + 1)) >> 32) taps,
+ *     t_i = eps_i * exp(-ln(1000) * i / n_h) for 1 <= i < n_h, eps_i the standard normals of philox4x32_10 counter
+ *       (i / 4, s, 8, j), key (seed_b, 0x5EED), paired through Box-Muller as the noise pairs them,
+ *     h_0 = 10^(drr_db / 20) * sqrt(sum t_i^2),  h_i = t_i,
+ *   on: x = (h * x)[0 : Ny_b], causal and truncated; h is a CONSTANT in the backward pass, which is the correlation
+ *   gx[i] = sum_k h_k gy[i + k].  A noise entry behind it takes its sigma from the convolved signal.  At most one per chain.
+ * The convolution is overlap-save on 4096-point transforms (blocks of 2048 output samples, the response in up to four
+ * partitions of 2048 taps); a clip whose entry does not fire is copied, and a clip on which no entry of such a chain fires
+ * at a step leaves the bits of the loop without a chain (its maxima are taken as 1, so the normalisers of z are the identity).  aware_embed_buffer 13: the responses of the last
+ * forward pass, dev f32 [B][8192], zero beyond n_h (the unit impulse where the entry did not fire).
+ * AWARE_E_BADARG of the _ex setter, besides those above: two reverberations, n_lo < 2, n_hi > 8192, n_lo > n_hi, a length
+ * that is not an integer, a non-finite drr_db.  Added without a version step: callers detect the feature by symbol. */
+#define AWARE_LOOP_REVERBERATION 2       /* param = n_lo, n_hi (taps; the host converts rt60 * sample_rate), drr_db */
+typedef struct aware_loop_attack_ex { int kind; float prob; float param[4]; } aware_loop_attack_ex;
+size_t aware_embed_loop_attack_workspace_bytes_ex(const aware_batch* batch, const aware_loop_attack_ex* attacks, int n_attacks);
+int aware_embed_set_loop_attacks_ex(aware_embed* e, const aware_loop_attack_ex* attacks, int n_attacks, const uint32_t* seeds,
+                                    void* workspace, size_t workspace_bytes, void* stream);
+/* The same convolution alone, on a ragged batch: clip b is len[b] floats at float offset off[b] of in and out (dev int [B],
+ * len[b] <= max_len), its response h[b * h_stride ...] with nh[b] taps (dev int [B]; at most h_stride <= 8192 are used;
+ * nh[b] <= 0 copies the clip).  adjoint 0: out = (h * in)[0 : len];  1: out[i] = sum_k h[k] in[i + k].  out may be in.
+ * workspace: device, 256-byte aligned, >= aware_convolve_workspace_bytes with nh_max >= h_stride (0: an argument out of
+ * range; total_len is the sum of the lengths and only checked against [max_len, B * max_len]).  Three launches and one
+ * 25 KB upload of twiddles on `stream`.  AWARE_E_BADARG: a null argument, B < 1 or > 65535, h_stride outside 1..8192;
+ * AWARE_E_WORKSPACE: workspace too small. */
+size_t aware_convolve_workspace_bytes(int B, int max_len, long long total_len, int nh_max);
+int aware_convolve(const float* in, const int* off, const int* len, int B, int max_len, const float* h, int h_stride,
+                   const int* nh, int adjoint, float* out, void* workspace, size_t workspace_bytes, void* stream);
+/* The response the loop draws for seeds[b] (dev uint32 [B]) at optimiser step `step`, chain entry `entry`, with prob 1:
+ * h dev f32 [B][h_stride] (h_stride >= n_hi, zero beyond n_h), nh dev int [B].  AWARE_E_BADARG: a null argument,
+ * n_lo < 2, n_hi > 8192, n_lo > n_hi, h_stride < n_hi, entry outside 0..3, a non-finite drr_db. */
+int aware_reverb_ir(const uint32_t* seeds, int B, int step, int entry, int n_lo, int n_hi, float drr_db, float* h,
+                    int h_stride, int* nh, void* stream);
 
 /* ---- bare GEMM (tests / roofline): C[M][N] = A[M][K] * Bt[N][K]^T + bias ------------------------------ */
 int aware_gemm_nt(const float* A, int lda, const float* Bt, int ldb, const float* bias, float* C, int ldc,

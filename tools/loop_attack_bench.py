@@ -1,10 +1,12 @@
-"""Attack-aware embedding: what a chain of loop attacks costs per iteration, and what it buys.
+"""Attack-aware embedding (DESIGN.md sections 15 and 16): what a chain of loop attacks costs per iteration, and what it buys.
 
-  (a) config-3 batch (256 x 3 s): per-iteration time of the graph-replayed loop with no chain, noise only, suppression only and
-      both, from device events over --steps steps (>= 200) after a warm-up, the variants alternating in one process
+  (a) config-3 batch (256 x 3 s): per-iteration time of the graph-replayed loop with no chain, noise only, suppression only,
+      both, reverberation only and reverberation followed by noise, from device events over --steps steps (>= 200) after a warm-up, the variants alternating in one process
       (--rounds rounds; the median over rounds is reported);
   (b) the BER table at that size: 400-step embeddings without a chain, with noise at 10 dB and with 0.5 s suppression
-      (prob 0.75) in the loop, then clean / Gaussian noise at 10 and 5 dB / 0.5 s and 0.3 s zeroed (--no-ber skips it).
+      (prob 0.75), with the reverberation and with the reverberation followed by noise in the loop, then clean / Gaussian
+      noise at 10 and 5 dB / 0.5 s and 0.3 s zeroed / reverberation of rt60 0.1 and 0.3 s / an echo of 100 ms x 0.7
+      (--no-ber skips it).
 `--only-loop` runs a few steps of every variant and nothing else, for a per-kernel trace
 (rocprofv3 --kernel-trace --stats -- python tools/loop_attack_bench.py --only-loop)."""
 import argparse
@@ -25,6 +27,9 @@ VARIANTS = {
     "noise": [{"kind": "gaussian_noise", "snr_db": 10.0}],
     "suppression": [{"kind": "sample_suppression", "seconds": 0.5, "prob": 0.75}],
     "both": [{"kind": "sample_suppression", "seconds": 0.3}, {"kind": "gaussian_noise", "snr_db": 10.0}],
+    "reverb": [{"kind": "reverberation", "rt60": [0.1, 0.5], "drr_db": -3.0, "prob": 0.75}],
+    "reverb_noise": [{"kind": "reverberation", "rt60": [0.1, 0.5], "drr_db": -3.0, "prob": 0.75},
+                     {"kind": "gaussian_noise", "snr_db": 10.0}],
 }
 
 
@@ -68,7 +73,7 @@ def main():
         result[f"us_per_iteration/{name}"] = round(float(np.median(times[name])), 2)
         print(f"{name:12s} {np.median(times[name]):8.1f} us per iteration (rounds: {', '.join(f'{t:.1f}' for t in times[name])})")
     base = result["us_per_iteration/none"]
-    for name in ("noise", "suppression", "both"):
+    for name in ("noise", "suppression", "both", "reverb", "reverb_noise"):
         result[f"extra_us/{name}"] = round(result[f"us_per_iteration/{name}"] - base, 2)
     del sessions
 
@@ -80,7 +85,10 @@ def main():
             return 100.0 * float(((vals > 0).astype(np.int64) != bits_h).mean())
 
         table = {}
-        for name in ("none", "noise", "suppression"):
+        echo_h = torch.zeros((B, 1601), device="cuda")
+        echo_h[:, 0], echo_h[:, 1600] = 1.0, 0.7
+        echo_n = torch.full((B,), 1601, dtype=torch.int32, device="cuda")
+        for name in ("none", "noise", "suppression", "reverb", "reverb_noise"):
             emb.loop_attacks = VARIANTS[name] or []
             out, _ = emb.embed_device(audio, batch, 16000, target)
             y = rt.Ragged(torch.cat(batch.unpack_out(out)), batch.out_lengths)
@@ -92,6 +100,10 @@ def main():
                 ny = batch.out_lengths[0]
                 starts = [0, (ny - int(sec * 16000)) // 2, ny - int(sec * 16000) - 1]
                 row[f"zeroed_{sec}s"] = float(np.mean([ber(A.SampleSupression(sec).apply_batch(y, 16000, starts=[st] * B)) for st in starts]))
+            for rt60 in (0.1, 0.3):
+                row[f"reverb_{rt60}s"] = float(np.mean([ber(A.Reverberation(rt60, seed=100000 * s + 7).apply_batch(y, 16000))
+                                                        for s in range(2)]))
+            row["echo_100ms_0.7"] = ber(rt.convolve(y, echo_h, echo_n))
             table[name] = {k: round(v, 3) for k, v in row.items()}
             print(f"BER % embedded with {name:12s}: " + ", ".join(f"{k} {v:.2f}" for k, v in row.items()))
         result["ber_percent"] = table
