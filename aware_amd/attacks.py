@@ -238,6 +238,24 @@ class Reverberation(Attack):
 
 
 @register
+class SpeedChange(Attack):
+    """EXTENSION (not in the reference, parity unpinned): the clip played fast or slow by `cents` (pitch and duration change
+    together, as under a sample-rate mismatch): Catmull-Rom resampling at the fixed ratio R / 65536,
+    R = 65536 + round(65536 (2^(cents / 1200) - 1)), as embedding.loop_attacks.speed_change specifies it.  A true speed
+    change: a clip of n samples comes out ((n - 1) << 16) // R + 1 long.  Inside the embed loop the same operator keeps the
+    clip's length ({"kind": "speed_change", "cents": ...})."""
+
+    def __init__(self, cents=50.0):
+        self.cents = float(cents)
+        self.m = int(round(65536.0 * (2.0 ** (self.cents / 1200.0) - 1.0)))
+        self.name = f"speed_{cents}"
+
+    def apply_batch(self, x, sr):
+        from .embedding.loop_attacks import speed_length
+        return rt.speed_change(x, [self.m] * x.B, out_lengths=[speed_length(n, self.m) for n in x.lengths])
+
+
+@register
 class MP3Surrogate(Attack):
     """EXTENSION (not in the reference; BASELINE.json north_star): MP3-like quantisation surrogate
     -- STFT -> per-frame log-magnitude quantisation (`step_db` grid, bins more than `-floor_db` below

@@ -1719,6 +1719,8 @@ struct aware_embed {
         cf* tables = nullptr;                     // W_2048 half table, W_4096 table
         cf* hspec = nullptr;                      // [B][4][2056]
         cf* xspec = nullptr;                      // [B][kmax][2056]
+        // speed change (kind 3): entry sp of the chain, -1 without one; it shares u with the reverberation, which it excludes
+        int sp = -1, m_lo = 0, m_hi = 0;
         bool locked = false;                      // an optimiser step has run: the chain stays what it is
     } la;
 };
@@ -1948,11 +1950,13 @@ static const std::vector<cf>& reverb_tables() {
     }();
     return t;
 }
-static bool has_reverb(const aware_loop_attack_ex* attacks, int n) {
+static bool has_kind(const aware_loop_attack_ex* attacks, int n, int kind) {
     for (int j = 0; attacks && j < n; ++j)
-        if (attacks[j].kind == AWARE_LOOP_REVERBERATION) return true;
+        if (attacks[j].kind == kind) return true;
     return false;
 }
+// the speed change's part: the one signal u it reads
+template <typename LA> static void carve_loop_speed(Carver& c, const aware_batch* b, LA& la) { la.u = c.take<float>(b->NS); }
 extern "C" size_t aware_embed_loop_attack_workspace_bytes(const aware_batch* b, int n_attacks) {
     if (!b || b->general || n_attacks < 1 || n_attacks > kMaxLoopAttacks) return 0;
     Carver c(nullptr, 0);
@@ -1966,20 +1970,21 @@ extern "C" size_t aware_embed_loop_attack_workspace_bytes_ex(const aware_batch* 
     Carver c(nullptr, 0);
     aware_embed e;
     carve_loop_attacks(c, b, e.la);
-    if (has_reverb(attacks, n_attacks)) carve_loop_reverb(c, b, e.la);
+    if (has_kind(attacks, n_attacks, AWARE_LOOP_REVERBERATION)) carve_loop_reverb(c, b, e.la);
+    else if (has_kind(attacks, n_attacks, AWARE_LOOP_SPEED_CHANGE)) carve_loop_speed(c, b, e.la);
     return c.off;
 }
-static int set_loop_attacks(aware_embed* e, const aware_loop_attack_ex* attacks, int n_attacks, bool allow_reverb,
+static int set_loop_attacks(aware_embed* e, const aware_loop_attack_ex* attacks, int n_attacks, bool ex,
                             const uint32_t* seeds, void* workspace, size_t workspace_bytes, void* stream) {
     static_assert(AWARE_LOOP_GAUSSIAN_NOISE == kLoopGaussianNoise && AWARE_LOOP_SAMPLE_SUPPRESSION == kLoopSampleSuppression &&
-                  AWARE_LOOP_REVERBERATION == kLoopReverberation, "");
+                  AWARE_LOOP_REVERBERATION == kLoopReverberation && AWARE_LOOP_SPEED_CHANGE == kLoopSpeedChange, "");
     if (!e || n_attacks < 0 || n_attacks > kMaxLoopAttacks) return AWARE_E_BADARG;
     if (e->gexec || e->la.locked) return AWARE_E_BADARG;          // before the first aware_embed_iterate, as aware_embed_set_optimizer
-    if (n_attacks == 0) { e->la.n = 0; e->la.z = nullptr; e->la.rv = -1; e->la.h = nullptr; return AWARE_OK; }
+    if (n_attacks == 0) { e->la.n = 0; e->la.z = nullptr; e->la.rv = -1; e->la.sp = -1; e->la.h = nullptr; return AWARE_OK; }
     if (!attacks || !seeds || !workspace || ((uintptr_t)workspace & 255)) return AWARE_E_BADARG;
     const aware_batch* b = e->b;
     auto la = e->la;
-    la.rv = -1; la.h = nullptr;
+    la.rv = -1; la.sp = -1; la.h = nullptr;
     for (int j = 0; j < n_attacks; ++j) {
         const aware_loop_attack_ex& a = attacks[j];
         if (!(a.prob >= 0.f && a.prob <= 1.f)) return AWARE_E_BADARG;
@@ -1990,13 +1995,19 @@ static int set_loop_attacks(aware_embed* e, const aware_loop_attack_ex* attacks,
         } else if (a.kind == AWARE_LOOP_SAMPLE_SUPPRESSION) {
             if (!(a.param[0] >= 1.f) || a.param[0] > 2147483520.f || a.param[0] != floorf(a.param[0])) return AWARE_E_BADARG;
             la.k[j] = (int)a.param[0];
-        } else if (a.kind == AWARE_LOOP_REVERBERATION && allow_reverb) {
+        } else if (a.kind == AWARE_LOOP_REVERBERATION && ex) {
             const float lo = a.param[0], hi = a.param[1], drr = a.param[2];
-            if (la.rv >= 0) return AWARE_E_BADARG;                   // one reverberation per chain
+            if (la.rv >= 0 || la.sp >= 0) return AWARE_E_BADARG;     // one reverberation per chain, and no speed change beside it
             if (!(lo >= 2.f) || !(hi <= (float)kReverbMaxIr) || !(lo <= hi) || lo != floorf(lo) || hi != floorf(hi) ||
                 !std::isfinite(drr))
                 return AWARE_E_BADARG;
             la.rv = j; la.n_lo = (int)lo; la.n_hi = (int)hi; la.gain = pow(10.0, (double)drr / 20.0);
+        } else if (a.kind == AWARE_LOOP_SPEED_CHANGE && ex) {
+            const float lo = a.param[0], hi = a.param[1];
+            if (la.rv >= 0 || la.sp >= 0) return AWARE_E_BADARG;     // one speed change per chain, and no reverberation beside it
+            if (!(lo >= (float)kSpeedMin) || !(hi <= (float)kSpeedMax) || !(lo <= hi) || lo != floorf(lo) || hi != floorf(hi))
+                return AWARE_E_BADARG;
+            la.sp = j; la.m_lo = (int)lo; la.m_hi = (int)hi;
         } else {
             return AWARE_E_BADARG;
         }
@@ -2007,6 +2018,7 @@ static int set_loop_attacks(aware_embed* e, const aware_loop_attack_ex* attacks,
     Carver c(workspace, workspace_bytes);
     carve_loop_attacks(c, b, la);
     if (la.rv >= 0) carve_loop_reverb(c, b, la);
+    else if (la.sp >= 0) carve_loop_speed(c, b, la);
     if (!c.ok) return AWARE_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     HIPCHK(hipMemsetAsync(la.gpad0, 0, (size_t)b->B * 1024 * sizeof(float), st));
@@ -2082,6 +2094,19 @@ extern "C" int aware_reverb_ir(const uint32_t* seeds, int B, int step, int entry
     return AWARE_OK;
 }
 
+// ---- the speed change alone (EXTENSION; attacks.SpeedChange, tests) -------------------------------------------------------
+extern "C" int aware_speed_change(const float* in, const int* in_off, const int* in_len, float* out, const int* out_off,
+                                  const int* out_len, int B, int max_len, const int* m, int adjoint, void* stream) {
+    if (!in || !in_off || !in_len || !out || !out_off || !out_len || !m || in == out) return AWARE_E_BADARG;
+    if (B < 1 || B > 65535 || max_len < 1 || max_len > (1 << 30) || adjoint < 0 || adjoint > 1) return AWARE_E_BADARG;
+    SpeedLaunch L;
+    L.in = in; L.out = out; L.B = B; L.adjoint = adjoint; L.max_len = max_len; L.m = m;
+    L.x_off = in_off; L.x_len = in_len; L.z_off = out_off; L.z_len = out_len;
+    launch_speed_change(L, (hipStream_t)stream);
+    LAUNCHCHK();
+    return AWARE_OK;
+}
+
 extern "C" void aware_embed_destroy(aware_embed* e) {
     if (!e) return;
 
@@ -2152,6 +2177,15 @@ extern "C" int aware_embed_begin(aware_embed* e, const float* audio, const float
     return AWARE_OK;
 }
 
+static SpeedLaunch speed_launch(const aware_embed* e, const float* in, float* out, int adjoint, int step_back) {
+    const auto& la = e->la;
+    SpeedLaunch S;
+    S.in = in; S.out = out; S.B = e->b->B; S.adjoint = adjoint; S.frame_off = e->b->d_frame_off; S.pstride = e->b->pstride;
+    S.run_blocks = e->b->synth_run; S.step = e->step; S.step_back = step_back; S.seeds = la.seeds; S.entry = la.sp;
+    S.m_lo = la.m_lo; S.m_hi = la.m_hi; S.prob = la.prob[la.sp];
+    return S;
+}
+
 static ConvolveLaunch reverb_launch(const aware_embed* e, const float* in, float* out, int adjoint) {
     const auto& la = e->la;
     ConvolveLaunch C;
@@ -2191,8 +2225,13 @@ static int embed_iteration(aware_embed* e, hipStream_t st, int do_step, float* g
         A.step = e->step; A.seeds = la.seeds; A.n = la.n;
         for (int j = 0; j < la.n; ++j) { A.kind[j] = la.kind[j]; A.k[j] = la.k[j]; A.inv_snr[j] = la.inv_snr[j]; A.prob[j] = la.prob[j]; }
         A.yraw = e->yraw; A.pmaxY = e->pmaxY; A.psq = la.psq; A.z = la.z; A.pmaxZ = la.pmaxZ;
-        if (la.rv >= 0) { A.idle_plain = 1; A.gpad_out = la.gpad0; }
-        if (la.rv < 0) {
+        if (la.rv >= 0 || la.sp >= 0) { A.idle_plain = 1; A.gpad_out = la.gpad0; }
+        if (la.sp >= 0) {
+            // the entries in front of the speed change on N(N(yraw)), the resampling, the entries behind it
+            launch_loop_attack_stage(A, 0, la.sp, e->yraw, 1, la.u, nullptr, st);
+            launch_speed_change(speed_launch(e, la.u, la.z, 0, 0), st);
+            launch_loop_attack_stage(A, la.sp + 1, la.n, la.z, 0, la.z, la.pmaxZ, st);
+        } else if (la.rv < 0) {
             launch_loop_attack_forward(A, st);
         } else {
             // the entries in front of the reverberation on N(N(yraw)), the convolution, the entries behind it
@@ -2243,7 +2282,15 @@ static int embed_iteration(aware_embed* e, hipStream_t st, int do_step, float* g
         const bool streamed = dsp == 0 && stream_supported(e->plan->dev);
         A.step_back = do_step ? 1 : 0;                  // the read-out kernel has advanced the counter
         A.gy = e->gy; A.gpad = streamed ? e->gpad : nullptr; A.pdot_in = e->pdot; A.pdot_out = e->la.pdot;
-        if (e->la.rv < 0) {
+        if (e->la.sp >= 0) {
+            // the mirror: normalisers at z and the masks behind the speed change into u (the forward pass is done with
+            // it), the gather-form adjoint back into gy, the masks in front of it and the partial sums against x
+            A.gy_out = e->la.u;
+            launch_loop_attack_stage_bwd(A, e->la.sp + 1, e->la.n, 1, 0, st);
+            A.gy_out = nullptr;
+            launch_speed_change(speed_launch(e, e->la.u, e->gy, 1, A.step_back), st);
+            launch_loop_attack_stage_bwd(A, 0, e->la.sp, 0, 1, st);
+        } else if (e->la.rv < 0) {
             launch_loop_attack_backward(A, st);
         } else {
             // the mirror: normalisers at z and the masks behind the reverberation, the correlation with the same

@@ -356,7 +356,7 @@ void launch_stoi(const StoiLaunch& L, hipStream_t st);
 // ---- loop_attack_kernels.hip: attack-aware embedding (EXTENSION): a chain of attacks between the embed loop's synthesis and
 // its analysis, drawn afresh at every optimiser step (aware_embed_set_loop_attacks) --------------------------------------
 constexpr int kMaxLoopAttacks = 4;
-constexpr int kLoopGaussianNoise = 0, kLoopSampleSuppression = 1, kLoopReverberation = 2;      // AWARE_LOOP_* of aware_hip.h
+constexpr int kLoopGaussianNoise = 0, kLoopSampleSuppression = 1, kLoopReverberation = 2, kLoopSpeedChange = 3;      // AWARE_LOOP_* of aware_hip.h
 struct LoopAttackLaunch {
     const int* frame_off = nullptr;
     const int* pcount = nullptr;          // [B] synthesis runs per clip: the partials' layout
@@ -375,10 +375,11 @@ struct LoopAttackLaunch {
     float* z = nullptr;                   // the attacked signal (layout of yraw) and its partial maxima
     unsigned long long* pmaxZ = nullptr;
     float* gy = nullptr;                  // backward: gradient in / out
+    float* gy_out = nullptr;              // backward: where a stage writes instead of gy (null: in place)
     const float* gpad = nullptr;          // reflect-pad parts of the streaming synthesis adjoint (null: already folded)
     const double* pdot_in = nullptr;
     double* pdot_out = nullptr;
-    // chains with a reverberation: a clip on which no entry fires at a step leaves the plain loop's bits (its maxima are
+    // chains with a reverberation or a speed change: a clip on which no entry fires at a step leaves the plain loop's bits (its maxima are
     // recorded as 1, the backward stages pass gradient, partial sums and reflect pads through); gpad_out: [B][2][512], the
     // pads the analysis adjoint then reads (zeros for every other clip)
     int idle_plain = 0;
@@ -388,11 +389,11 @@ struct LoopAttackLaunch {
 void launch_loop_attack_forward(const LoopAttackLaunch& L, hipStream_t st);
 // gy: dL/d N(N(z)) -> dL/dx in place, pdot_out: partial sums of dL/dx * x
 void launch_loop_attack_backward(const LoopAttackLaunch& L, hipStream_t st);
-// the same in stages, for a chain that a reverberation splits: entries [j0, j1) on src (norm 1: src is the raw synthesis and
+// the same in stages, for a chain that a reverberation or a speed change splits: entries [j0, j1) on src (norm 1: src is the raw synthesis and
 // x = N(N(src)); 0: src is x itself) -> dst (may be src) and, unless null, the partial maxima of |dst|
 void launch_loop_attack_stage(const LoopAttackLaunch& L, int j0, int j1, const float* src, int norm, float* dst,
                               unsigned long long* pmax, hipStream_t st);
-// backward of entries [j0, j1) on gy in place; at_z: the normalisers' backward at z and the reflect pads come first;
+// backward of entries [j0, j1) on gy in place (into gy_out when set; an idle clip is then copied); at_z: the normalisers' backward at z and the reflect pads come first;
 // dot: the partial sums of the result against x go to pdot_out
 void launch_loop_attack_stage_bwd(const LoopAttackLaunch& L, int j0, int j1, int at_z, int dot, hipStream_t st);
 
@@ -429,5 +430,26 @@ struct ConvolveLaunch {
     cf* xspec = nullptr;                  // [B][kmax][kReverbBins]
 };
 void launch_convolve(const ConvolveLaunch& L, hipStream_t st);
+
+// ---- loop_speed_kernels.hip: speed change (EXTENSION): Catmull-Rom resampling at a drawn ratio R / 65536, inside the embed
+// loop (chain kind 3) and stand-alone (aware_speed_change), and its adjoint in gather form ------------------------------
+constexpr int kSpeedMin = -13520, kSpeedMax = 17034;      // ceil / floor of 65536 (2^(-+400 / 1200) - 1)
+struct SpeedLaunch {
+    const float* in = nullptr; float* out = nullptr;      // never the same buffer
+    int B = 0, adjoint = 0;               // 0: out = z from in = x; 1: out = gx from in = gy
+    // the embed loop's layout: x and z both Ny_b long at sig_offset, one workgroup per synthesis run, m drawn in the kernel
+    const int* frame_off = nullptr;
+    int pstride = 0, run_blocks = 0;
+    const int* step = nullptr; int step_back = 0;
+    const unsigned* seeds = nullptr;      // [B]
+    int entry = 0, m_lo = 0, m_hi = 0;
+    float prob = 0.f;
+    // or a ragged batch (frame_off null): x is x_len[b] floats at x_off[b], z is z_len[b] floats at z_off[b], m[b] given
+    const int* x_off = nullptr; const int* x_len = nullptr;
+    const int* z_off = nullptr; const int* z_len = nullptr;
+    int max_len = 0;                      // >= every length written
+    const int* m = nullptr;               // [B]
+};
+void launch_speed_change(const SpeedLaunch& L, hipStream_t st);
 
 }  // namespace aware

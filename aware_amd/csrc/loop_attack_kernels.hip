@@ -32,7 +32,7 @@ struct ChainArgs {
     int step_back;                        // 1 when the read-out kernel has advanced the counter since the forward pass
     const unsigned* seeds;                // [B]
     int n;                                // chain entries
-    int j0;                               // first entry of this stage (0 unless a reverberation splits the chain)
+    int j0;                               // first entry of this stage (0 unless a reverberation or a speed change splits the chain)
     int upto;                             // entries [j0, upto) are applied (sums of squares: those in front of noise entry `upto`)
     const float* src;                     // the stage's input, layout of yraw
     int norm;                             // 1: src is the raw synthesis, x = N(N(src)); 0: src is x itself
@@ -52,6 +52,7 @@ struct ChainArgs {
     unsigned long long* pmaxZ;            // [B][pstride]
     // backward
     float* gy;                            // in: dL/d N(N(z)) (reflect pads folded, or in gpad); out: dL/dx
+    float* gdst;                          // where the stage writes dL/dx: gy, or the buffer the speed change's adjoint reads
     const float* gpad;                    // [B][2][512] reflect-pad parts of the streaming synthesis adjoint (null: folded)
     const double* pdot_in;                // [B][pstride] partial sums of gy * N(N(z))
     double* pdot_out;                     // [B][pstride] partial sums of dL/dx * x
@@ -81,7 +82,7 @@ __device__ __forceinline__ ChainState chain_state(const ChainArgs& a, int b, int
 #pragma unroll
     for (int j = 0; j < kMaxLoopAttacks; ++j) {
         cs.on[j] = false; cs.start[j] = 0; cs.sigma[j] = 0.f;
-        if (j >= j0 && j < upto && a.kind[j] != kLoopReverberation) {
+        if (j >= j0 && j < upto && a.kind[j] != kLoopReverberation && a.kind[j] != kLoopSpeedChange) {
             unsigned r[4];
             philox4x32_10(0u, step, 1u + (unsigned)j, 1u, seed, 0x5EEDu, r);
             cs.on[j] = ((double)r[0] + 0.5) * 2.3283064365386963e-10 < (double)a.prob[j];
@@ -96,7 +97,7 @@ __device__ __forceinline__ ChainState chain_state(const ChainArgs& a, int b, int
     return cs;
 }
 
-// With idle_plain (the chains with a reverberation): true when no entry of the whole chain fires for this clip at this step.
+// With idle_plain (the chains with a reverberation or a speed change): true when no entry of the whole chain fires for this clip at this step.
 // Such a clip is to leave the plain loop's bits.  Forward: z = N(N(y)) as always, but its maxima are recorded as 1 -- what
 // max|N(N(y))| is to within an ulp -- so the analysis' two normalisers of z are exactly the identity and it sees the bits the
 // plain loop's analysis computes from y.  Backward: the stages hand the synthesis adjoint's gradient, its partial sums
@@ -206,7 +207,7 @@ __global__ __launch_bounds__(kLaThreads) void chain_bwd_kernel(ChainArgs a) {
         const float zk = a.z[so + min(cz.k, (unsigned)(Ny - 1))];
         corr = adot * ((zk > 0.f) ? 1.f : ((zk < 0.f) ? -1.f : 0.f));
     } else {
-        cz.k = 0xFFFFFFFFu;                  // a stage in front of a reverberation: masks and the dot product only
+        cz.k = 0xFFFFFFFFu;                  // a stage in front of the splitting entry: masks and the dot product only
         inv_mm2 = 1.0f;
     }
     const unsigned step = (unsigned)(*a.step - a.step_back), seed = a.seeds[b];
@@ -218,6 +219,11 @@ __global__ __launch_bounds__(kLaThreads) void chain_bwd_kernel(ChainArgs a) {
         for (int i = threadIdx.x; i < 1024; i += kLaThreads) po[i] = pi ? pi[i] : 0.f;
     }
     if (idle) {
+        if (a.gdst != a.gy) {
+            const float4* s4 = reinterpret_cast<const float4*>(a.gy + so);
+            float4* d4 = reinterpret_cast<float4*>(a.gdst + so);
+            for (int q = jb0 * (kHop / 4) + threadIdx.x; q < jb1 * (kHop / 4); q += kLaThreads) d4[q] = s4[q];
+        }
         if (a.dot && threadIdx.x == 0) {
             const size_t i = (size_t)b * a.pstride + blockIdx.x;
             a.pdot_out[i] = a.pdot_in[i];
@@ -227,7 +233,8 @@ __global__ __launch_bounds__(kLaThreads) void chain_bwd_kernel(ChainArgs a) {
     const ChainState cs = chain_state<false>(a, b, a.j0, a.upto, Ny, step, seed, dred);
 
     const float4* y4 = reinterpret_cast<const float4*>(a.yraw + so);
-    float4* g4 = reinterpret_cast<float4*>(a.gy + so);
+    const float4* g4 = reinterpret_cast<const float4*>(a.gy + so);
+    float4* gd4 = reinterpret_cast<float4*>(a.gdst + so);
     const float* gpL = (a.gpad && a.at_z) ? a.gpad + (size_t)b * 1024 : nullptr;
     const float* gpR = gpL ? gpL + 512 : nullptr;
     double dot = 0.0;
@@ -260,7 +267,7 @@ __global__ __launch_bounds__(kLaThreads) void chain_bwd_kernel(ChainArgs a) {
                     if ((unsigned)(i0 + e - cs.start[j]) < (unsigned)a.k[j]) g[e] = 0.f;
             }
         }
-        g4[q] = make_float4(g[0], g[1], g[2], g[3]);
+        gd4[q] = make_float4(g[0], g[1], g[2], g[3]);
 #pragma unroll
         for (int e = 0; e < 4; ++e) dot += (double)g[e] * (double)x[e];
     }
@@ -284,7 +291,7 @@ ChainArgs chain_args(const LoopAttackLaunch& L) {
         a.prob[j] = j < L.n ? L.prob[j] : 0.f;
     }
     a.yraw = L.yraw; a.pmaxY = L.pmaxY; a.psq = L.psq; a.z = L.z; a.pmaxZ = L.pmaxZ;
-    a.gy = L.gy; a.gpad = L.gpad; a.pdot_in = L.pdot_in; a.pdot_out = L.pdot_out;
+    a.gy = L.gy; a.gdst = L.gy_out ? L.gy_out : L.gy; a.gpad = L.gpad; a.pdot_in = L.pdot_in; a.pdot_out = L.pdot_out;
     return a;
 }
 

@@ -1,0 +1,135 @@
+// Speed change (EXTENSION, parity unpinned: the reference has neither the attack nor a chain inside its loop): the clip
+// played at the ratio R / 65536, R = 65536 + m, through Catmull-Rom interpolation.  DESIGN.md section 17; the torch
+// restatement is aware_amd/embedding/loop_attacks.py::speed_change / apply_chain.
+//
+//   r = philox4x32_10((0, s, 1 + j, 1), (seed_b, 0x5EED)),  on = (r0 + 0.5) / 2^32 < prob,
+//   m = m_lo + ((r3 * (m_hi - m_lo + 1)) >> 32),  R = 65536 + m          (m = 0 where the entry does not fire)
+//   p_i = i R (64-bit, 16.16 fixed point),  i0 = p_i >> 16,  f = (p_i & 0xFFFF) / 65536   (exact in f32)
+//   forward   z[i] = w_-1(f) x[i0 - 1] + w_0(f) x[i0] + w_1(f) x[i0 + 1] + w_2(f) x[i0 + 2],  x zero outside [0, n),
+//             z[i] = 0 where p_i > (n - 1) << 16
+//   adjoint   gx[j] = sum over ascending i of w_{j - i0(i)}(f_i) gy[i],  i from ceil(((j - 2) << 16) / R) while i0(i) <= j + 1
+//
+// One kernel for both directions and both layouts; every thread owns four consecutive outputs.  The forward gathers its four
+// taps per output, the adjoint walks the at most ten inputs that can reach its four outputs, in ascending order: no atomics,
+// one fixed order.  m = 0 copies the clip: the identity is exact.  Inside the loop one workgroup works through one synthesis
+// run of a clip (the partition chain_kernel uses) with float4 stores, which the 256-float clip alignment allows; the
+// stand-alone entry takes any offset and length and stores scalars.
+#include "common.hpp"
+#include "kernels.h"
+#include "loop_rng.hpp"
+
+namespace aware {
+
+namespace {
+
+constexpr int kSpThreads = 256;
+
+struct SpeedWeights { float wm1, w0, w1, w2; };
+
+// explicit fused multiply-adds, so that every instantiation rounds the same way
+__device__ __forceinline__ SpeedWeights speed_weights(float f) {
+    SpeedWeights w;
+    w.wm1 = (fmaf(2.f - f, f, -1.f) * f) * 0.5f;              // ((-f + 2) f - 1) f / 2
+    w.w0 = fmaf(fmaf(3.f, f, -5.f), f * f, 2.f) * 0.5f;       // ((3 f - 5) f^2 + 2) / 2
+    w.w1 = (fmaf(fmaf(-3.f, f, 4.f), f, 1.f) * f) * 0.5f;     // ((-3 f + 4) f + 1) f / 2
+    w.w2 = ((f - 1.f) * (f * f)) * 0.5f;                      // (f - 1) f^2 / 2
+    return w;
+}
+
+__device__ __forceinline__ float speed_tap(const float* __restrict__ x, int n, long long R, int i) {
+    const long long p = (long long)i * R;
+    if (p > ((long long)(n - 1) << 16)) return 0.f;
+    const int i0 = (int)(p >> 16);                            // 0 <= i0 <= n - 1
+    const SpeedWeights w = speed_weights((float)(unsigned)(p & 0xFFFF) * (1.0f / 65536.0f));
+    const float a = i0 >= 1 ? x[i0 - 1] : 0.f;
+    const float b = x[i0];
+    const float c = i0 + 1 < n ? x[i0 + 1] : 0.f;
+    const float d = i0 + 2 < n ? x[i0 + 2] : 0.f;
+    return fmaf(w.w2, d, fmaf(w.w1, c, fmaf(w.w0, b, w.wm1 * a)));
+}
+
+// gx[j0 .. j0 + 3] from gy[0 .. n_out): x has n samples
+__device__ __forceinline__ void speed_adjoint4(const float* __restrict__ gy, int n_out, int n, long long R, int j0, float g[4]) {
+    g[0] = g[1] = g[2] = g[3] = 0.f;
+    const long long lo = ((long long)j0 - 2) << 16, plim = (long long)(n - 1) << 16;
+    int i = lo <= 0 ? 0 : (int)(((unsigned long long)lo + (unsigned long long)R - 1ull) / (unsigned long long)R);
+    for (; i < n_out; ++i) {
+        const long long p = (long long)i * R;
+        const int i0 = (int)(p >> 16);
+        if (p > plim || i0 > j0 + 4) break;
+        const SpeedWeights w = speed_weights((float)(unsigned)(p & 0xFFFF) * (1.0f / 65536.0f));
+        const float v = gy[i];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int t = j0 + e - i0;
+            const float wt = t == -1 ? w.wm1 : (t == 0 ? w.w0 : (t == 1 ? w.w1 : w.w2));
+            if (t >= -1 && t <= 2) g[e] = fmaf(wt, v, g[e]);
+        }
+    }
+}
+
+template <bool LOOP>
+__global__ __launch_bounds__(kSpThreads) void speed_kernel(SpeedLaunch a) {
+    const int b = blockIdx.y;
+    const float* x;
+    float* y;
+    int nx, nz, q0, q1, m;          // lengths of the x side and the z side; this workgroup's groups of four outputs [q0, q1)
+    if (LOOP) {
+        const int nblk = a.frame_off[b + 1] - a.frame_off[b] - 1;
+        int nseg, jb0, jb1;
+        synth_segment(nblk, blockIdx.x, a.run_blocks, nseg, jb0, jb1);
+        if ((int)blockIdx.x >= nseg) return;
+        const int so = sig_offset(a.frame_off, b);
+        x = a.in + so; y = a.out + so;
+        nx = nz = kHop * nblk;
+        q0 = jb0 * (kHop / 4); q1 = jb1 * (kHop / 4);
+        const unsigned step = (unsigned)(*a.step - a.step_back);
+        unsigned r[4];
+        philox4x32_10(0u, step, 1u + (unsigned)a.entry, 1u, a.seeds[b], 0x5EEDu, r);
+        const bool on = ((double)r[0] + 0.5) * 2.3283064365386963e-10 < (double)a.prob;
+        m = on ? a.m_lo + (int)(((unsigned long long)r[3] * (unsigned long long)(unsigned)(a.m_hi - a.m_lo + 1)) >> 32) : 0;
+    } else {
+        nx = a.x_len[b]; nz = a.z_len[b];
+        x = a.in + (a.adjoint ? a.z_off[b] : a.x_off[b]);
+        y = a.out + (a.adjoint ? a.x_off[b] : a.z_off[b]);
+        q0 = blockIdx.x * kSpThreads; q1 = q0 + kSpThreads;
+        m = a.m[b];
+    }
+    const int n_in = a.adjoint ? nz : nx, n_w = a.adjoint ? nx : nz;       // samples read / written
+    q1 = min(q1, (n_w + 3) / 4);
+    const long long R = 65536 + (long long)m;
+    for (int q = q0 + threadIdx.x; q < q1; q += kSpThreads) {
+        const int i = 4 * q;
+        float v[4];
+        if (m == 0) {
+            // the identity, exactly (the two sides differ in length only in the stand-alone entry)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = i + e < n_in ? x[i + e] : 0.f;
+        } else if (a.adjoint) {
+            speed_adjoint4(x, nz, nx, R, i, v);
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = speed_tap(x, nx, R, i + e);
+        }
+        if (LOOP) {
+            reinterpret_cast<float4*>(y)[q] = make_float4(v[0], v[1], v[2], v[3]);
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (i + e < n_w) y[i + e] = v[e];
+        }
+    }
+}
+
+}  // namespace
+
+void launch_speed_change(const SpeedLaunch& L, hipStream_t st) {
+    if (L.frame_off) {
+        hipLaunchKernelGGL(speed_kernel<true>, dim3((unsigned)L.pstride, (unsigned)L.B, 1), dim3(kSpThreads), 0, st, L);
+    } else {
+        const unsigned gx = (unsigned)((L.max_len + 4 * kSpThreads - 1) / (4 * kSpThreads));
+        hipLaunchKernelGGL(speed_kernel<false>, dim3(gx, (unsigned)L.B, 1), dim3(kSpThreads), 0, st, L);
+    }
+}
+
+}  // namespace aware

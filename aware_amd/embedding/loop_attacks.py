@@ -18,6 +18,17 @@ the loop's new stage.  For clip b (length Ny) at optimiser step s with seed_b:
         h).  At most one per chain; a noise entry behind it takes its sigma from the convolved signal.  At s = 0, j = 0 and a
         scalar rt60 this is the post-hoc attacks.Reverberation of the same seed.
 
+      speed_change(cents = c or [lo, hi], -400 <= lo <= hi <= 400; a scalar c > 0 means [-c, c]),
+        m_lo = ceil(65536 (2^(lo / 1200) - 1)), m_hi = floor(65536 (2^(hi / 1200) - 1)) in float64:
+        m = m_lo + ((r[3] * (m_hi - m_lo + 1)) >> 32), R = 65536 + m: the clip played at R / 65536 of its speed.  The draw is
+        uniform in that ratio, not in cents.  p_i = i R as a 64-bit integer in 16.16 fixed point, i0 = p_i >> 16,
+        f = (p_i & 0xFFFF) / 65536 (exact in float32, so host and device agree on every index and fraction);
+        on: x[i] = w_-1(f) x[i0 - 1] + w_0(f) x[i0] + w_1(f) x[i0 + 1] + w_2(f) x[i0 + 2], samples outside [0, Ny) read as
+        zero, 0 where p_i > (Ny - 1) << 16; Catmull-Rom weights w_-1 = ((-f + 2) f - 1) f / 2, w_0 = ((3 f - 5) f^2 + 2) / 2,
+        w_1 = ((-3 f + 4) f + 1) f / 2, w_2 = (f - 1) f^2 / 2.  The clip keeps its length (a faster one ends in zeros, a slower
+        one is truncated); m = 0 is the identity; R is detached.  At most one per chain, and not beside a reverberation; a
+        noise entry behind it takes its sigma from the resampled signal.
+
 In the loop x = N(N(y)) of the raw synthesis y, N(v) = v / (max|v| + 1e-8), and the analysis (N, N, STFT, band magnitudes)
 runs on the chain's output."""
 from __future__ import annotations
@@ -28,12 +39,13 @@ import numpy as np
 import torch
 
 MAX_ATTACKS = 4
-KINDS = {"gaussian_noise": 0, "sample_suppression": 1, "reverberation": 2}          # AWARE_LOOP_* of include/aware_hip.h
+KINDS = {"gaussian_noise": 0, "sample_suppression": 1, "reverberation": 2, "speed_change": 3}          # AWARE_LOOP_* of include/aware_hip.h
 _KEYS = {"gaussian_noise": {"kind", "snr_db", "prob"}, "sample_suppression": {"kind", "seconds", "prob"},
-         "reverberation": {"kind", "rt60", "drr_db", "prob"}}
+         "reverberation": {"kind", "rt60", "drr_db", "prob"}, "speed_change": {"kind", "cents", "prob"}}
 _KEY1 = 0x5EED
 MAX_IR = 8192                   # taps of the longest impulse response
 _IR_WORD = 8                    # third Philox counter word of the impulse responses (0: noise, 1..4: entry draws)
+MAX_CENTS = 400.0               # widest speed change either way
 
 
 def parse_chain(chain) -> list[dict]:
@@ -41,7 +53,9 @@ def parse_chain(chain) -> list[dict]:
     {"kind": "sample_suppression", "seconds": 0.3, "prob": 0.75}] (None / empty: no chain).  ValueError: unknown kind or key,
     a missing parameter, prob outside [0, 1], a non-finite snr_db, seconds <= 0, more than four entries; for
     {"kind": "reverberation", "rt60": 0.3 | [0.1, 0.5], "drr_db": -3.0}: a missing rt60, rt60 not 0 < lo <= hi (finite), a
-    non-finite drr_db, a second reverberation."""
+    non-finite drr_db, a second reverberation; for {"kind": "speed_change", "cents": 200.0 | [-50.0, 120.0]}: a missing
+    cents, a scalar <= 0, cents not -400 <= lo <= hi <= 400 (finite), a range that holds no speed offset (m_lo > m_hi), a
+    second speed change, a speed change in a chain with a reverberation."""
     if not chain:
         return []
     if isinstance(chain, dict) or not isinstance(chain, (list, tuple)):
@@ -68,6 +82,8 @@ def parse_chain(chain) -> list[dict]:
         elif kind == "reverberation":
             if any(o["kind"] == "reverberation" for o in out):
                 raise ValueError(f"loop_attacks[{j}] (reverberation): at most one reverberation per chain")
+            if any(o["kind"] == "speed_change" for o in out):
+                raise ValueError(f"loop_attacks[{j}] (reverberation): a chain holds a speed change or a reverberation, not both")
             if "rt60" not in a:
                 raise ValueError(f"loop_attacks[{j}] (reverberation): rt60 is required")
             rt = a["rt60"]
@@ -81,6 +97,33 @@ def parse_chain(chain) -> list[dict]:
             if not math.isfinite(drr):
                 raise ValueError(f"loop_attacks[{j}] (reverberation): a finite drr_db is required")
             e["rt60"], e["drr_db"] = [lo, hi], drr
+        elif kind == "speed_change":
+            if any(o["kind"] == "speed_change" for o in out):
+                raise ValueError(f"loop_attacks[{j}] (speed_change): at most one speed change per chain")
+            if any(o["kind"] == "reverberation" for o in out):
+                raise ValueError(f"loop_attacks[{j}] (speed_change): a chain holds a speed change or a reverberation, not both")
+            if "cents" not in a:
+                raise ValueError(f"loop_attacks[{j}] (speed_change): cents is required")
+            ct = a["cents"]
+            try:
+                if isinstance(ct, (list, tuple)):
+                    if len(ct) != 2:
+                        raise TypeError
+                    lo, hi = float(ct[0]), float(ct[1])
+                else:
+                    lo, hi = -float(ct), float(ct)
+                    if not hi > 0.0:
+                        raise ValueError(f"loop_attacks[{j}] (speed_change): a scalar cents has to be > 0; got {ct!r}")
+            except TypeError:
+                raise ValueError(f"loop_attacks[{j}] (speed_change): cents = {ct!r} is neither a number nor [lo, hi]") from None
+            if not (math.isfinite(lo) and math.isfinite(hi) and -MAX_CENTS <= lo <= hi <= MAX_CENTS):
+                raise ValueError(f"loop_attacks[{j}] (speed_change): cents needs -{MAX_CENTS:g} <= lo <= hi <= {MAX_CENTS:g}, "
+                                 f"both finite; got {ct!r}")
+            e["cents"] = [lo, hi]
+            m_lo, m_hi = speed_range(e)
+            if m_lo > m_hi:
+                raise ValueError(f"loop_attacks[{j}] (speed_change): cents = {ct!r} holds no speed offset "
+                                 f"(m_lo = {m_lo} > m_hi = {m_hi}, in units of 1 / 65536)")
         else:
             if "seconds" not in a or not math.isfinite(float(a["seconds"])) or float(a["seconds"]) <= 0.0:
                 raise ValueError(f"loop_attacks[{j}] (sample_suppression): seconds > 0 is required")
@@ -97,6 +140,13 @@ def suppression_samples(entry: dict, sample_rate: int) -> int:
 def reverb_taps(entry: dict, sample_rate: int) -> tuple[int, int]:
     """(n_lo, n_hi) = (int(lo * sample_rate), int(hi * sample_rate)) of a parsed reverberation entry."""
     return int(entry["rt60"][0] * sample_rate), int(entry["rt60"][1] * sample_rate)
+
+
+def speed_range(entry: dict) -> tuple[int, int]:
+    """(m_lo, m_hi) = (ceil(65536 (2^(lo / 1200) - 1)), floor(65536 (2^(hi / 1200) - 1))) of a parsed speed_change entry, in
+    float64: the speed offsets, in units of 1 / 65536, that lie inside the range of cents."""
+    lo, hi = entry["cents"]
+    return (int(math.ceil(65536.0 * (2.0 ** (lo / 1200.0) - 1.0))), int(math.floor(65536.0 * (2.0 ** (hi / 1200.0) - 1.0))))
 
 
 def check_lengths(chain: list[dict], sample_rate: int, out_lengths) -> None:
@@ -181,6 +231,39 @@ def reverb_ir(seed: int, step: int, j: int, n_h: int, drr_db: float) -> np.ndarr
     return h
 
 
+def speed_offset(r3: int, m_lo: int, m_hi: int) -> int:
+    """m = m_lo + ((r3 * (m_hi - m_lo + 1)) >> 32): uniform on [m_lo, m_hi], in integers as the device computes it."""
+    return int(m_lo) + ((int(r3) * (int(m_hi) - int(m_lo) + 1)) >> 32)
+
+
+def speed_length(n: int, m: int) -> int:
+    """Samples of a clip of n played at (65536 + m) / 65536 of its speed: ((n - 1) << 16) // R + 1."""
+    return ((int(n) - 1) << 16) // (65536 + int(m)) + 1
+
+
+def speed_change(x: torch.Tensor, m: int, n_out: int | None = None) -> torch.Tensor:
+    """x [..., n] played at R / 65536 of its speed, R = 65536 + m, by Catmull-Rom interpolation at the positions i R in 16.16
+    fixed point; n_out samples (default n: the clip keeps its geometry).  Differentiable in x; m = 0 returns x."""
+    n = x.shape[-1]
+    n_out = n if n_out is None else int(n_out)
+    m = int(m)
+    if m == 0 and n_out == n:
+        return x
+    p = np.arange(n_out, dtype=np.int64) * np.int64(65536 + m)
+    i0 = p >> 16
+    live = p <= (np.int64(n - 1) << 16)
+    f = torch.as_tensor((p & 0xFFFF).astype(np.float64) / 65536.0).to(dtype=x.dtype, device=x.device)
+    w = (((-f + 2) * f - 1) * f / 2, ((3 * f - 5) * f * f + 2) / 2, ((-3 * f + 4) * f + 1) * f / 2, (f - 1) * f * f / 2)
+    z = None
+    for t, wt in zip((-1, 0, 1, 2), w):
+        idx = i0 + t
+        ok = live & (idx >= 0) & (idx < n)
+        tap = x[..., torch.as_tensor(np.where(ok, idx, 0), device=x.device)]
+        term = wt * tap * torch.as_tensor(ok).to(dtype=x.dtype, device=x.device)
+        z = term if z is None else z + term
+    return z
+
+
 def _convolve(xb: torch.Tensor, h: np.ndarray) -> torch.Tensor:
     """(h * xb)[0 : len(xb)] in xb's dtype through an FFT at least len(xb) + len(h) - 1 long; differentiable in xb."""
     ny, nh = xb.shape[-1], len(h)
@@ -216,6 +299,9 @@ def apply_chain(x, chain, seeds, step: int, sample_rate: int = 16000):
                 n_h = reverb_length(r[2], *reverb_taps(a, sample_rate))
                 if on:
                     xb = _convolve(xb, reverb_ir(seed, step, j, n_h, a["drr_db"]))
+            elif a["kind"] == "speed_change":
+                if on:
+                    xb = speed_change(xb, speed_offset(r[3], *speed_range(a)))
             elif on:
                 power = float(np.mean(xb.detach().double().cpu().numpy() ** 2))
                 sigma = math.sqrt(power / (10.0 ** (a["snr_db"] / 10.0)))
@@ -227,12 +313,15 @@ def apply_chain(x, chain, seeds, step: int, sample_rate: int = 16000):
 
 def device_entries_ex(chain: list[dict], sample_rate: int):
     """(kind, prob, [param0..3]) of the C ABI's aware_loop_attack_ex: kinds 0 and 1 as device_entries in param[0]; a
-    reverberation has param = [n_lo, n_hi, drr_db, 0]."""
+    reverberation has param = [n_lo, n_hi, drr_db, 0], a speed change [m_lo, m_hi, 0, 0]."""
     out = []
     for a in chain:
         if a["kind"] == "reverberation":
             n_lo, n_hi = reverb_taps(a, sample_rate)
             out.append((KINDS[a["kind"]], a["prob"], [float(n_lo), float(n_hi), a["drr_db"], 0.0]))
+        elif a["kind"] == "speed_change":
+            m_lo, m_hi = speed_range(a)
+            out.append((KINDS[a["kind"]], a["prob"], [float(m_lo), float(m_hi), 0.0, 0.0]))
         else:
             k, p, pr = device_entries([a], sample_rate)[0]
             out.append((k, pr, [p, 0.0, 0.0, 0.0]))
@@ -241,6 +330,6 @@ def device_entries_ex(chain: list[dict], sample_rate: int):
 
 def device_entries(chain: list[dict], sample_rate: int):
     """(kind, param, prob) triples of the C ABI (aware_loop_attack): param = snr_db or the suppression length in samples.
-    Chains of these two kinds only; a reverberation goes through device_entries_ex."""
+    Chains of these two kinds only; a reverberation or a speed change goes through device_entries_ex."""
     return [(KINDS[a["kind"]], a["snr_db"] if a["kind"] == "gaussian_noise" else float(suppression_samples(a, sample_rate)),
              a["prob"]) for a in chain]

@@ -555,6 +555,32 @@ int aware_convolve(const float* in, const int* off, const int* len, int B, int m
 int aware_reverb_ir(const uint32_t* seeds, int B, int step, int entry, int n_lo, int n_hi, float drr_db, float* h,
                     int h_stride, int* nh, void* stream);
 
+/* ---- speed change inside the loop and as an attack (EXTENSION, parity unpinned: the reference has neither) ----------------
+ * The _ex pair also accepts (the older entry point keeps refusing every kind above 1)
+ *   AWARE_LOOP_SPEED_CHANGE, param = { m_lo, m_hi }: with r the entry's draw as above,
+ *     m = m_lo + ((r[3] * (m_hi - m_lo + 1)) >> 32),  R = 65536 + m: the clip is played at R / 65536 of its speed (uniform in
+ *     that ratio, not in cents; the host converts cents: m_lo = ceil(65536 (2^(lo / 1200) - 1)), m_hi = floor(...));
+ *     p_i = i * R as a 64-bit integer in 16.16 fixed point, i0 = p_i >> 16, f = (p_i & 0xFFFF) / 65536,
+ *   on: z[i] = w_-1(f) x[i0 - 1] + w_0(f) x[i0] + w_1(f) x[i0 + 1] + w_2(f) x[i0 + 2] for i < Ny_b, x read as zero outside
+ *   [0, Ny_b), z[i] = 0 where p_i > (Ny_b - 1) << 16, with the Catmull-Rom weights w_-1 = ((-f + 2) f - 1) f / 2,
+ *   w_0 = ((3 f - 5) f^2 + 2) / 2, w_1 = ((-3 f + 4) f + 1) f / 2, w_2 = (f - 1) f^2 / 2.  The clip keeps its length: a faster
+ *   one ends in zeros, a slower one is truncated.  m = 0 is the identity.  R is a CONSTANT in the backward pass, which is
+ *   gx[j] = sum over ascending i of w_{j - i0(i)}(f_i) gy[i] (no atomics).  A noise entry behind it takes its sigma from the
+ *   resampled signal; a clip on which no entry of such a chain fires at a step leaves the bits of the loop without a chain.
+ * AWARE_E_BADARG of the _ex setter, besides those above: a value that is not an integer, m_lo > m_hi, m_lo < -13520 or
+ * m_hi > 17034 (what -+400 cents give), a second speed change, a speed change together with a reverberation.
+ * aware_embed_loop_attack_workspace_bytes_ex grows by one signal for such a chain.  Added without a version step. */
+#define AWARE_LOOP_SPEED_CHANGE 3        /* param = m_lo, m_hi (the host converts cents) */
+/* The same operator alone, on a ragged batch: clip b of the x side is in_len[b] floats at float offset in_off[b], of the z
+ * side out_len[b] floats at out_off[b] (dev int [B], any offsets, every length <= max_len <= 2^30), m dev int [B].
+ * adjoint 0: `in` holds x and `out` receives z[0 : out_len[b]] (out_len = in_len keeps the geometry as the loop does;
+ * ((in_len - 1) << 16) / R + 1 is the whole clip at its new speed).  adjoint 1: `in` holds gy with the lengths and offsets of
+ * the z side (out_off, out_len) and `out` receives gx with those of the x side (in_off, in_len).  in and out are distinct
+ * buffers.  One launch on `stream`.  AWARE_E_BADARG: a null argument, in == out, B < 1 or > 65535, max_len < 1 or > 2^30,
+ * adjoint outside 0..1 (checked before anything is launched); the m[b] are taken as they are. */
+int aware_speed_change(const float* in, const int* in_off, const int* in_len, float* out, const int* out_off,
+                       const int* out_len, int B, int max_len, const int* m, int adjoint, void* stream);
+
 /* ---- bare GEMM (tests / roofline): C[M][N] = A[M][K] * Bt[N][K]^T + bias ------------------------------ */
 int aware_gemm_nt(const float* A, int lda, const float* Bt, int ldb, const float* bias, float* C, int ldc,
                   int M, int N, int K, void* stream);

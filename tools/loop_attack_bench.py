@@ -1,12 +1,12 @@
-"""Attack-aware embedding (DESIGN.md sections 15 and 16): what a chain of loop attacks costs per iteration, and what it buys.
+"""Attack-aware embedding (DESIGN.md sections 15 to 17): what a chain of loop attacks costs per iteration, and what it buys.
 
   (a) config-3 batch (256 x 3 s): per-iteration time of the graph-replayed loop with no chain, noise only, suppression only,
-      both, reverberation only and reverberation followed by noise, from device events over --steps steps (>= 200) after a warm-up, the variants alternating in one process
+      both, reverberation only, reverberation followed by noise, speed change only and speed change followed by noise, from device events over --steps steps (>= 200) after a warm-up, the variants alternating in one process
       (--rounds rounds; the median over rounds is reported);
   (b) the BER table at that size: 400-step embeddings without a chain, with noise at 10 dB and with 0.5 s suppression
-      (prob 0.75), with the reverberation and with the reverberation followed by noise in the loop, then clean / Gaussian
-      noise at 10 and 5 dB / 0.5 s and 0.3 s zeroed / reverberation of rt60 0.1 and 0.3 s / an echo of 100 ms x 0.7
-      (--no-ber skips it).
+      (prob 0.75), with the reverberation, the reverberation followed by noise and the speed change in the loop, then clean /
+      Gaussian noise at 10 and 5 dB / 0.5 s and 0.3 s zeroed / reverberation of rt60 0.1 and 0.3 s / an echo of 100 ms x 0.7 /
+      polyphase resampling at 101/100, 21/20, 20/21, 11/10 and 10/11 (--no-ber skips it).
 `--only-loop` runs a few steps of every variant and nothing else, for a per-kernel trace
 (rocprofv3 --kernel-trace --stats -- python tools/loop_attack_bench.py --only-loop)."""
 import argparse
@@ -30,6 +30,8 @@ VARIANTS = {
     "reverb": [{"kind": "reverberation", "rt60": [0.1, 0.5], "drr_db": -3.0, "prob": 0.75}],
     "reverb_noise": [{"kind": "reverberation", "rt60": [0.1, 0.5], "drr_db": -3.0, "prob": 0.75},
                      {"kind": "gaussian_noise", "snr_db": 10.0}],
+    "speed": [{"kind": "speed_change", "cents": 200.0, "prob": 0.75}],
+    "speed_noise": [{"kind": "speed_change", "cents": 200.0, "prob": 0.75}, {"kind": "gaussian_noise", "snr_db": 10.0}],
 }
 
 
@@ -73,7 +75,7 @@ def main():
         result[f"us_per_iteration/{name}"] = round(float(np.median(times[name])), 2)
         print(f"{name:12s} {np.median(times[name]):8.1f} us per iteration (rounds: {', '.join(f'{t:.1f}' for t in times[name])})")
     base = result["us_per_iteration/none"]
-    for name in ("noise", "suppression", "both", "reverb", "reverb_noise"):
+    for name in ("noise", "suppression", "both", "reverb", "reverb_noise", "speed", "speed_noise"):
         result[f"extra_us/{name}"] = round(result[f"us_per_iteration/{name}"] - base, 2)
     del sessions
 
@@ -88,7 +90,7 @@ def main():
         echo_h = torch.zeros((B, 1601), device="cuda")
         echo_h[:, 0], echo_h[:, 1600] = 1.0, 0.7
         echo_n = torch.full((B,), 1601, dtype=torch.int32, device="cuda")
-        for name in ("none", "noise", "suppression", "reverb", "reverb_noise"):
+        for name in ("none", "noise", "suppression", "reverb", "reverb_noise", "speed"):
             emb.loop_attacks = VARIANTS[name] or []
             out, _ = emb.embed_device(audio, batch, 16000, target)
             y = rt.Ragged(torch.cat(batch.unpack_out(out)), batch.out_lengths)
@@ -104,6 +106,8 @@ def main():
                 row[f"reverb_{rt60}s"] = float(np.mean([ber(A.Reverberation(rt60, seed=100000 * s + 7).apply_batch(y, 16000))
                                                         for s in range(2)]))
             row["echo_100ms_0.7"] = ber(rt.convolve(y, echo_h, echo_n))
+            for up, down in ((101, 100), (21, 20), (20, 21), (11, 10), (10, 11)):
+                row[f"polyphase_{up}/{down}"] = ber(A.resample_poly_batch(y, up, down))
             table[name] = {k: round(v, 3) for k, v in row.items()}
             print(f"BER % embedded with {name:12s}: " + ", ".join(f"{k} {v:.2f}" for k, v in row.items()))
         result["ber_percent"] = table
