@@ -880,6 +880,14 @@ __global__ __launch_bounds__(256) void in_lrelu_bwd_reg_kernel(float* __restrict
     }
 }
 
+// a * b rounded to float before any use, never fused into a following add or subtract.  The from-memory backward kernels
+// compute dL/du in both of their sweeps; fused into `du - m1` the second sweep would see the unrounded product, and a clip of
+// one pooled frame (m1 == du, gradient exactly 0) would get the rounding residue of the product instead of 0.
+__device__ __forceinline__ float mul_rounded(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+
 __global__ __launch_bounds__(256) void in_lrelu_bwd_kernel(float* __restrict__ dA, const float* __restrict__ A,
                                                             const int* __restrict__ frame_off, const int* __restrict__ pool_off, const float* __restrict__ rstd,
                                                             int C) {
@@ -895,7 +903,7 @@ __global__ __launch_bounds__(256) void in_lrelu_bwd_kernel(float* __restrict__ d
     if (ok) for (int t = g; t < Tp; t += 4) {
         float av = a[(size_t)t * C];
         float u = av > 0.f ? av : av * 5.0f;            // invert LeakyReLU(0.2)
-        float du = d[(size_t)t * C] * (av > 0.f ? 1.f : 0.2f);
+        float du = mul_rounded(d[(size_t)t * C], av > 0.f ? 1.f : 0.2f);
         p1 += du; p2 += du * u;
     }
     s1[g][cl] = p1; s2[g][cl] = p2;
@@ -906,7 +914,7 @@ __global__ __launch_bounds__(256) void in_lrelu_bwd_kernel(float* __restrict__ d
     if (ok) for (int t = g; t < Tp; t += 4) {
         float av = a[(size_t)t * C];
         float u = av > 0.f ? av : av * 5.0f;
-        float du = d[(size_t)t * C] * (av > 0.f ? 1.f : 0.2f);
+        float du = mul_rounded(d[(size_t)t * C], av > 0.f ? 1.f : 0.2f);
         d[(size_t)t * C] = rs * (du - m1 - u * m2);
     }
 }
@@ -1026,7 +1034,9 @@ __global__ __launch_bounds__(256) void norm_act_bwd_kernel(float* __restrict__ d
     auto load = [&](int t, float& u, float& du) {
         const float av = su ? 0.f : a[(size_t)t * C];
         u = su ? su[(size_t)t * C] : (ACT == kActLRelu ? (av > 0.f ? av : av * 5.0f) : av);
-        du = d[(size_t)t * C] * act_grad<ACT>(u, av);
+        // (the from-memory InstanceNorm form runs this in both sweeps: see mul_rounded)
+        du = (NORM == kNormInstance && R == 0) ? mul_rounded(d[(size_t)t * C], act_grad<ACT>(u, av))
+                                                : d[(size_t)t * C] * act_grad<ACT>(u, av);
     };
     if (NORM != kNormInstance) {
         if (!ok) return;
