@@ -256,6 +256,24 @@ class SpeedChange(Attack):
 
 
 @register
+class OverlapAddStretch(Attack):
+    """EXTENSION (not in the reference, parity unpinned): the clip stretched in time at `rate` (above 1: faster and shorter, the
+    pitch kept) by plain overlap-add of Hann-windowed segments at the fixed rate Q / 65536, Q = 65536 + round(65536 (rate - 1)),
+    as embedding.loop_attacks.time_stretch specifies it.  A true stretch: a clip of n samples comes out
+    ((n - 1) << 16) // Q + 1 long.  Inside the embed loop the same operator keeps the clip's length
+    ({"kind": "time_stretch", "rate": ...}).  TimeStretch is the phase vocoder, built differently."""
+
+    def __init__(self, rate=1.05):
+        self.rate = float(rate)
+        self.m = int(round(65536.0 * (self.rate - 1.0)))
+        self.name = f"ola_{rate}"
+
+    def apply_batch(self, x, sr):
+        from .embedding.loop_attacks import stretch_length
+        return rt.stretch_ola(x, [self.m] * x.B, out_lengths=[stretch_length(n, self.m) for n in x.lengths])
+
+
+@register
 class MP3Surrogate(Attack):
     """EXTENSION (not in the reference; BASELINE.json north_star): MP3-like quantisation surrogate
     -- STFT -> per-frame log-magnitude quantisation (`step_db` grid, bins more than `-floor_db` below

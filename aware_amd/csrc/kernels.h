@@ -356,7 +356,7 @@ void launch_stoi(const StoiLaunch& L, hipStream_t st);
 // ---- loop_attack_kernels.hip: attack-aware embedding (EXTENSION): a chain of attacks between the embed loop's synthesis and
 // its analysis, drawn afresh at every optimiser step (aware_embed_set_loop_attacks) --------------------------------------
 constexpr int kMaxLoopAttacks = 4;
-constexpr int kLoopGaussianNoise = 0, kLoopSampleSuppression = 1, kLoopReverberation = 2, kLoopSpeedChange = 3;      // AWARE_LOOP_* of aware_hip.h
+constexpr int kLoopGaussianNoise = 0, kLoopSampleSuppression = 1, kLoopReverberation = 2, kLoopSpeedChange = 3, kLoopTimeStretch = 4;      // AWARE_LOOP_* of aware_hip.h
 struct LoopAttackLaunch {
     const int* frame_off = nullptr;
     const int* pcount = nullptr;          // [B] synthesis runs per clip: the partials' layout
@@ -379,7 +379,7 @@ struct LoopAttackLaunch {
     const float* gpad = nullptr;          // reflect-pad parts of the streaming synthesis adjoint (null: already folded)
     const double* pdot_in = nullptr;
     double* pdot_out = nullptr;
-    // chains with a reverberation or a speed change: a clip on which no entry fires at a step leaves the plain loop's bits (its maxima are
+    // chains with a reverberation, a speed change or a time stretch: a clip on which no entry fires at a step leaves the plain loop's bits (its maxima are
     // recorded as 1, the backward stages pass gradient, partial sums and reflect pads through); gpad_out: [B][2][512], the
     // pads the analysis adjoint then reads (zeros for every other clip)
     int idle_plain = 0;
@@ -451,5 +451,30 @@ struct SpeedLaunch {
     const int* m = nullptr;               // [B]
 };
 void launch_speed_change(const SpeedLaunch& L, hipStream_t st);
+
+// ---- loop_stretch_kernels.hip: time stretch (EXTENSION): overlap-add of Hann-windowed segments taken at a drawn rate
+// Q / 65536, inside the embed loop (chain kind 4) and stand-alone (aware_stretch_ola), and its adjoint in gather form ------
+constexpr int kStretchMin = -16384, kStretchMax = 21845;      // ceil / floor of 65536 (0.75 - 1) and 65536 (4 / 3 - 1)
+struct StretchLaunch {
+    const float* in = nullptr; float* out = nullptr;      // never the same buffer
+    const float* window = nullptr;        // stretch_window()
+    int B = 0, adjoint = 0;               // 0: out = z from in = x; 1: out = gx from in = gz
+    // the embed loop's layout: x and z both Ny_b long at sig_offset, one workgroup per synthesis run, m drawn in the kernel
+    const int* frame_off = nullptr;
+    int pstride = 0, run_blocks = 0;
+    const int* step = nullptr; int step_back = 0;
+    const unsigned* seeds = nullptr;      // [B]
+    int entry = 0, m_lo = 0, m_hi = 0;
+    float prob = 0.f;
+    // or a ragged batch (frame_off null): x is x_len[b] floats at x_off[b], z is z_len[b] floats at z_off[b], m[b] given
+    const int* x_off = nullptr; const int* x_len = nullptr;
+    const int* z_off = nullptr; const int* z_len = nullptr;
+    int max_len = 0;                      // >= every length written
+    const int* m = nullptr;               // [B]
+};
+// the periodic Hann window of 1024 points in f32 on the current device (uploaded once, outside any stream capture); null
+// when the device refuses
+const float* stretch_window();
+void launch_time_stretch(const StretchLaunch& L, hipStream_t st);
 
 }  // namespace aware

@@ -82,7 +82,8 @@ __device__ __forceinline__ ChainState chain_state(const ChainArgs& a, int b, int
 #pragma unroll
     for (int j = 0; j < kMaxLoopAttacks; ++j) {
         cs.on[j] = false; cs.start[j] = 0; cs.sigma[j] = 0.f;
-        if (j >= j0 && j < upto && a.kind[j] != kLoopReverberation && a.kind[j] != kLoopSpeedChange) {
+        if (j >= j0 && j < upto && a.kind[j] != kLoopReverberation && a.kind[j] != kLoopSpeedChange &&
+            a.kind[j] != kLoopTimeStretch) {
             unsigned r[4];
             philox4x32_10(0u, step, 1u + (unsigned)j, 1u, seed, 0x5EEDu, r);
             cs.on[j] = ((double)r[0] + 0.5) * 2.3283064365386963e-10 < (double)a.prob[j];

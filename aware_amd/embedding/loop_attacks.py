@@ -29,6 +29,17 @@ the loop's new stage.  For clip b (length Ny) at optimiser step s with seed_b:
         one is truncated); m = 0 is the identity; R is detached.  At most one per chain, and not beside a reverberation; a
         noise entry behind it takes its sigma from the resampled signal.
 
+      time_stretch(rate = r or [lo, hi], 0.75 <= lo <= hi <= 4/3; a scalar r > 1 means [1 / r, r]; above 1 is faster and shorter),
+        m_lo = ceil(65536 (lo - 1)), m_hi = floor(65536 (hi - 1)) in float64:
+        m = m_lo + ((r[3] * (m_hi - m_lo + 1)) >> 32), Q = 65536 + m: the clip's duration divided by Q / 65536 at its own pitch,
+        by plain overlap-add.  H = 256, N = 1024, w the periodic Hann window of N points in float32 (the loop's STFT window);
+        a_t = (t H Q) >> 16 in 64-bit signed integers (arithmetic shift) for every integer t >= -2;
+        on: x[n] = 1/2 sum_t w[n - t H + 512] x[n - t H + a_t] over the at most four t with 0 <= n - t H + 512 < N, samples
+        outside [0, Ny) read as zero.  Every index is an integer, so host and device agree on every tap.  The clip keeps its
+        length (a faster one ends in zeros, a slower one is truncated); m = 0 is the identity; Q is detached.  At most one per
+        chain and not beside a reverberation; a speed_change may follow it directly (tempo and pitch then move independently,
+        a pitch shift being the diagonal), and in no other place of such a chain.
+
 In the loop x = N(N(y)) of the raw synthesis y, N(v) = v / (max|v| + 1e-8), and the analysis (N, N, STFT, band magnitudes)
 runs on the chain's output."""
 from __future__ import annotations
@@ -39,13 +50,15 @@ import numpy as np
 import torch
 
 MAX_ATTACKS = 4
-KINDS = {"gaussian_noise": 0, "sample_suppression": 1, "reverberation": 2, "speed_change": 3}          # AWARE_LOOP_* of include/aware_hip.h
+KINDS = {"gaussian_noise": 0, "sample_suppression": 1, "reverberation": 2, "speed_change": 3, "time_stretch": 4}          # AWARE_LOOP_* of include/aware_hip.h
 _KEYS = {"gaussian_noise": {"kind", "snr_db", "prob"}, "sample_suppression": {"kind", "seconds", "prob"},
-         "reverberation": {"kind", "rt60", "drr_db", "prob"}, "speed_change": {"kind", "cents", "prob"}}
+         "reverberation": {"kind", "rt60", "drr_db", "prob"}, "speed_change": {"kind", "cents", "prob"}, "time_stretch": {"kind", "rate", "prob"}}
 _KEY1 = 0x5EED
 MAX_IR = 8192                   # taps of the longest impulse response
 _IR_WORD = 8                    # third Philox counter word of the impulse responses (0: noise, 1..4: entry draws)
 MAX_CENTS = 400.0               # widest speed change either way
+MIN_RATE, MAX_RATE = 0.75, 4.0 / 3.0            # slowest and fastest time stretch
+STRETCH_HOP, STRETCH_WIN = 256, 1024            # the overlap-add's hop and window: the loop's STFT geometry
 
 
 def parse_chain(chain) -> list[dict]:
@@ -55,7 +68,9 @@ def parse_chain(chain) -> list[dict]:
     {"kind": "reverberation", "rt60": 0.3 | [0.1, 0.5], "drr_db": -3.0}: a missing rt60, rt60 not 0 < lo <= hi (finite), a
     non-finite drr_db, a second reverberation; for {"kind": "speed_change", "cents": 200.0 | [-50.0, 120.0]}: a missing
     cents, a scalar <= 0, cents not -400 <= lo <= hi <= 400 (finite), a range that holds no speed offset (m_lo > m_hi), a
-    second speed change, a speed change in a chain with a reverberation."""
+    second speed change, a speed change in a chain with a reverberation; for {"kind": "time_stretch", "rate": 1.1 |
+    [0.9, 1.1]}: a missing rate, a scalar <= 1, rate not 0.75 <= lo <= hi <= 4/3 (finite), a range that holds no offset, a
+    second stretch, a stretch in a chain with a reverberation, a speed change anywhere but directly behind the stretch."""
     if not chain:
         return []
     if isinstance(chain, dict) or not isinstance(chain, (list, tuple)):
@@ -84,6 +99,8 @@ def parse_chain(chain) -> list[dict]:
                 raise ValueError(f"loop_attacks[{j}] (reverberation): at most one reverberation per chain")
             if any(o["kind"] == "speed_change" for o in out):
                 raise ValueError(f"loop_attacks[{j}] (reverberation): a chain holds a speed change or a reverberation, not both")
+            if any(o["kind"] == "time_stretch" for o in out):
+                raise ValueError(f"loop_attacks[{j}] (reverberation): a chain holds a time stretch or a reverberation, not both")
             if "rt60" not in a:
                 raise ValueError(f"loop_attacks[{j}] (reverberation): rt60 is required")
             rt = a["rt60"]
@@ -102,6 +119,8 @@ def parse_chain(chain) -> list[dict]:
                 raise ValueError(f"loop_attacks[{j}] (speed_change): at most one speed change per chain")
             if any(o["kind"] == "reverberation" for o in out):
                 raise ValueError(f"loop_attacks[{j}] (speed_change): a chain holds a speed change or a reverberation, not both")
+            if any(o["kind"] == "time_stretch" for o in out) and out[-1]["kind"] != "time_stretch":
+                raise ValueError(f"loop_attacks[{j}] (speed_change): beside a time stretch, the speed change follows it directly")
             if "cents" not in a:
                 raise ValueError(f"loop_attacks[{j}] (speed_change): cents is required")
             ct = a["cents"]
@@ -123,6 +142,36 @@ def parse_chain(chain) -> list[dict]:
             m_lo, m_hi = speed_range(e)
             if m_lo > m_hi:
                 raise ValueError(f"loop_attacks[{j}] (speed_change): cents = {ct!r} holds no speed offset "
+                                 f"(m_lo = {m_lo} > m_hi = {m_hi}, in units of 1 / 65536)")
+        elif kind == "time_stretch":
+            if any(o["kind"] == "time_stretch" for o in out):
+                raise ValueError(f"loop_attacks[{j}] (time_stretch): at most one time stretch per chain")
+            if any(o["kind"] == "reverberation" for o in out):
+                raise ValueError(f"loop_attacks[{j}] (time_stretch): a chain holds a time stretch or a reverberation, not both")
+            if any(o["kind"] == "speed_change" for o in out):
+                raise ValueError(f"loop_attacks[{j}] (time_stretch): a speed change in the same chain follows the stretch directly")
+            if "rate" not in a:
+                raise ValueError(f"loop_attacks[{j}] (time_stretch): rate is required")
+            rr = a["rate"]
+            try:
+                if isinstance(rr, (list, tuple)):
+                    if len(rr) != 2:
+                        raise TypeError
+                    lo, hi = float(rr[0]), float(rr[1])
+                else:
+                    hi = float(rr)
+                    if not hi > 1.0:
+                        raise ValueError(f"loop_attacks[{j}] (time_stretch): a scalar rate has to be > 1; got {rr!r}")
+                    lo = 1.0 / hi
+            except TypeError:
+                raise ValueError(f"loop_attacks[{j}] (time_stretch): rate = {rr!r} is neither a number nor [lo, hi]") from None
+            if not (math.isfinite(lo) and math.isfinite(hi) and MIN_RATE <= lo <= hi <= MAX_RATE):
+                raise ValueError(f"loop_attacks[{j}] (time_stretch): rate needs {MIN_RATE:g} <= lo <= hi <= 4/3, both finite; "
+                                 f"got {rr!r}")
+            e["rate"] = [lo, hi]
+            m_lo, m_hi = stretch_range(e)
+            if m_lo > m_hi:
+                raise ValueError(f"loop_attacks[{j}] (time_stretch): rate = {rr!r} holds no offset "
                                  f"(m_lo = {m_lo} > m_hi = {m_hi}, in units of 1 / 65536)")
         else:
             if "seconds" not in a or not math.isfinite(float(a["seconds"])) or float(a["seconds"]) <= 0.0:
@@ -147,6 +196,13 @@ def speed_range(entry: dict) -> tuple[int, int]:
     float64: the speed offsets, in units of 1 / 65536, that lie inside the range of cents."""
     lo, hi = entry["cents"]
     return (int(math.ceil(65536.0 * (2.0 ** (lo / 1200.0) - 1.0))), int(math.floor(65536.0 * (2.0 ** (hi / 1200.0) - 1.0))))
+
+
+def stretch_range(entry: dict) -> tuple[int, int]:
+    """(m_lo, m_hi) = (ceil(65536 (lo - 1)), floor(65536 (hi - 1))) of a parsed time_stretch entry, in float64: the offsets of
+    the rate from 1, in units of 1 / 65536, that lie inside the range."""
+    lo, hi = entry["rate"]
+    return int(math.ceil(65536.0 * (lo - 1.0))), int(math.floor(65536.0 * (hi - 1.0)))
 
 
 def check_lengths(chain: list[dict], sample_rate: int, out_lengths) -> None:
@@ -264,6 +320,47 @@ def speed_change(x: torch.Tensor, m: int, n_out: int | None = None) -> torch.Ten
     return z
 
 
+def stretch_offset(r3: int, m_lo: int, m_hi: int) -> int:
+    """m = m_lo + ((r3 * (m_hi - m_lo + 1)) >> 32): uniform on [m_lo, m_hi], in integers as the device computes it."""
+    return int(m_lo) + ((int(r3) * (int(m_hi) - int(m_lo) + 1)) >> 32)
+
+
+def stretch_length(n: int, m: int) -> int:
+    """Samples of a clip of n stretched at the rate (65536 + m) / 65536: ((n - 1) << 16) // Q + 1."""
+    return ((int(n) - 1) << 16) // (65536 + int(m)) + 1
+
+
+def stretch_window() -> np.ndarray:
+    """The periodic Hann window of 1024 points in float32, as the loop's STFT holds it."""
+    return (0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(STRETCH_WIN, dtype=np.float64) / STRETCH_WIN)).astype(np.float32)
+
+
+def time_stretch(x: torch.Tensor, m: int, n_out: int | None = None) -> torch.Tensor:
+    """x [..., n] stretched in time at the rate Q / 65536, Q = 65536 + m (above 1: faster and shorter, at the same pitch), by
+    plain overlap-add: z[i] = 1/2 sum_t w[i - t H + 512] x[i - t H + a_t], a_t = (t H Q) >> 16, over the four t (ascending)
+    whose window holds i; n_out samples (default n: the clip keeps its geometry).  Linear in x and differentiable; m = 0
+    returns x."""
+    n = x.shape[-1]
+    n_out = n if n_out is None else int(n_out)
+    m = int(m)
+    if m == 0 and n_out == n:
+        return x
+    H, N = STRETCH_HOP, STRETCH_WIN
+    i = np.arange(n_out, dtype=np.int64)
+    w = torch.as_tensor(stretch_window().astype(np.float64)).to(dtype=x.dtype, device=x.device)
+    z = None
+    for k in (3, 2, 1, 0):                                        # ascending t
+        t = (i + N // 2) // H - k                                 # >= -1
+        a = (t * np.int64(H) * np.int64(65536 + m)) >> 16         # arithmetic shift
+        src = i - t * H + a
+        ok = (src >= 0) & (src < n)
+        tap = x[..., torch.as_tensor(np.where(ok, src, 0), device=x.device)]
+        wk = w[torch.as_tensor(i - t * H + N // 2, device=x.device)] * torch.as_tensor(ok).to(dtype=x.dtype, device=x.device)
+        term = wk * tap
+        z = term if z is None else z + term
+    return 0.5 * z
+
+
 def _convolve(xb: torch.Tensor, h: np.ndarray) -> torch.Tensor:
     """(h * xb)[0 : len(xb)] in xb's dtype through an FFT at least len(xb) + len(h) - 1 long; differentiable in xb."""
     ny, nh = xb.shape[-1], len(h)
@@ -302,6 +399,9 @@ def apply_chain(x, chain, seeds, step: int, sample_rate: int = 16000):
             elif a["kind"] == "speed_change":
                 if on:
                     xb = speed_change(xb, speed_offset(r[3], *speed_range(a)))
+            elif a["kind"] == "time_stretch":
+                if on:
+                    xb = time_stretch(xb, stretch_offset(r[3], *stretch_range(a)))
             elif on:
                 power = float(np.mean(xb.detach().double().cpu().numpy() ** 2))
                 sigma = math.sqrt(power / (10.0 ** (a["snr_db"] / 10.0)))
@@ -313,7 +413,7 @@ def apply_chain(x, chain, seeds, step: int, sample_rate: int = 16000):
 
 def device_entries_ex(chain: list[dict], sample_rate: int):
     """(kind, prob, [param0..3]) of the C ABI's aware_loop_attack_ex: kinds 0 and 1 as device_entries in param[0]; a
-    reverberation has param = [n_lo, n_hi, drr_db, 0], a speed change [m_lo, m_hi, 0, 0]."""
+    reverberation has param = [n_lo, n_hi, drr_db, 0], a speed change or a time stretch [m_lo, m_hi, 0, 0]."""
     out = []
     for a in chain:
         if a["kind"] == "reverberation":
@@ -321,6 +421,9 @@ def device_entries_ex(chain: list[dict], sample_rate: int):
             out.append((KINDS[a["kind"]], a["prob"], [float(n_lo), float(n_hi), a["drr_db"], 0.0]))
         elif a["kind"] == "speed_change":
             m_lo, m_hi = speed_range(a)
+            out.append((KINDS[a["kind"]], a["prob"], [float(m_lo), float(m_hi), 0.0, 0.0]))
+        elif a["kind"] == "time_stretch":
+            m_lo, m_hi = stretch_range(a)
             out.append((KINDS[a["kind"]], a["prob"], [float(m_lo), float(m_hi), 0.0, 0.0]))
         else:
             k, p, pr = device_entries([a], sample_rate)[0]
@@ -330,6 +433,6 @@ def device_entries_ex(chain: list[dict], sample_rate: int):
 
 def device_entries(chain: list[dict], sample_rate: int):
     """(kind, param, prob) triples of the C ABI (aware_loop_attack): param = snr_db or the suppression length in samples.
-    Chains of these two kinds only; a reverberation or a speed change goes through device_entries_ex."""
+    Chains of these two kinds only; a reverberation, a speed change or a time stretch goes through device_entries_ex."""
     return [(KINDS[a["kind"]], a["snr_db"] if a["kind"] == "gaussian_noise" else float(suppression_samples(a, sample_rate)),
              a["prob"]) for a in chain]

@@ -581,6 +581,39 @@ int aware_reverb_ir(const uint32_t* seeds, int B, int step, int entry, int n_lo,
 int aware_speed_change(const float* in, const int* in_off, const int* in_len, float* out, const int* out_off,
                        const int* out_len, int B, int max_len, const int* m, int adjoint, void* stream);
 
+/* ---- time stretch inside the loop and as an attack (EXTENSION, parity unpinned: the reference's is rubberband) ------------
+ * The _ex pair also accepts (the older entry point keeps refusing every kind above 1)
+ *   AWARE_LOOP_TIME_STRETCH, param = { m_lo, m_hi }: with r the entry's draw as above,
+ *     m = m_lo + ((r[3] * (m_hi - m_lo + 1)) >> 32),  Q = 65536 + m: the clip's duration is divided by Q / 65536 at its own
+ *     pitch (above 1: faster and shorter; the host converts rates: m_lo = ceil(65536 (lo - 1)), m_hi = floor(65536 (hi - 1)));
+ *     H = 256, N = 1024, w the periodic Hann window of N points in f32, a_t = (t H Q) >> 16 as a 64-bit signed integer with
+ *     an arithmetic shift, for every integer t >= -2,
+ *   on: z[n] = 1/2 sum_t w[n - t H + 512] x[n - t H + a_t] for n < Ny_b, over the at most four t with
+ *   0 <= n - t H + 512 < N in ascending order, x read as zero outside [0, Ny_b).  The clip keeps its length: a faster one ends
+ *   in zeros, a slower one is truncated.  m = 0 is the identity.  Q is a CONSTANT in the backward pass, which is
+ *   gx[j] = 1/2 sum over ascending t of w[j - a_t + 512] gz[j - a_t + t H], 0 <= j - a_t + 512 < N (no atomics).  A noise
+ *   entry behind it takes its sigma from the stretched signal; a clip on which no entry of such a chain fires at a step
+ *   leaves the bits of the loop without a chain.
+ *   An AWARE_LOOP_SPEED_CHANGE entry may follow the stretch DIRECTLY: the two then form one stage (stretch, then resampling;
+ *   each with its own draw, so tempo and pitch move independently and a pitch shift is the diagonal).
+ * AWARE_E_BADARG of the _ex setter, besides those above: a value that is not an integer, m_lo > m_hi, m_lo < -16384 or
+ * m_hi > 21845 (what the rates 0.75 and 4/3 give), a second time stretch, a time stretch together with a reverberation, a
+ * speed change in the same chain anywhere but directly behind the stretch.
+ * aware_embed_loop_attack_workspace_bytes_ex grows by one signal for such a chain, by two for the pair; chains without the
+ * kind need what they needed.  Added without a version step. */
+#define AWARE_LOOP_TIME_STRETCH 4        /* param = m_lo, m_hi (the host converts rates) */
+/* The same operator alone, on a ragged batch, with the argument list of aware_speed_change: clip b of the x side is in_len[b]
+ * floats at float offset in_off[b], of the z side out_len[b] floats at out_off[b] (dev int [B], any offsets, every length
+ * <= max_len <= 2^30), m dev int [B].  adjoint 0: `in` holds x and `out` receives z[0 : out_len[b]] (out_len = in_len keeps
+ * the geometry as the loop does; ((in_len - 1) << 16) / Q + 1 is the whole clip at its new duration).  adjoint 1: `in` holds
+ * gz with the lengths and offsets of the z side (out_off, out_len) and `out` receives gx with those of the x side (in_off,
+ * in_len).  in and out are distinct buffers.  One launch on `stream`; the first call on a device uploads the window table
+ * (4 KiB, synchronously: not inside a stream capture).  AWARE_E_BADARG: a null argument, in == out, B < 1 or > 65535,
+ * max_len < 1 or > 2^30, adjoint outside 0..1 (checked before anything is launched); a clip whose m[b] lies outside
+ * -16384..21845 is copied as with m = 0. */
+int aware_stretch_ola(const float* in, const int* in_off, const int* in_len, float* out, const int* out_off,
+                      const int* out_len, int B, int max_len, const int* m, int adjoint, void* stream);
+
 /* ---- bare GEMM (tests / roofline): C[M][N] = A[M][K] * Bt[N][K]^T + bias ------------------------------ */
 int aware_gemm_nt(const float* A, int lda, const float* Bt, int ldb, const float* bias, float* C, int ldc,
                   int M, int N, int K, void* stream);

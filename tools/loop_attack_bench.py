@@ -1,7 +1,7 @@
-"""Attack-aware embedding (DESIGN.md sections 15 to 17): what a chain of loop attacks costs per iteration, and what it buys.
+"""Attack-aware embedding (DESIGN.md sections 15 to 18): what a chain of loop attacks costs per iteration, and what it buys.
 
   (a) config-3 batch (256 x 3 s): per-iteration time of the graph-replayed loop with no chain, noise only, suppression only,
-      both, reverberation only, reverberation followed by noise, speed change only and speed change followed by noise, from device events over --steps steps (>= 200) after a warm-up, the variants alternating in one process
+      both, reverberation only, reverberation followed by noise, speed change only, speed change followed by noise, time stretch only and time stretch followed by a speed change, from device events over --steps steps (>= 200) after a warm-up, the variants alternating in one process
       (--rounds rounds; the median over rounds is reported);
   (b) the BER table at that size: 400-step embeddings without a chain, with noise at 10 dB and with 0.5 s suppression
       (prob 0.75), with the reverberation, the reverberation followed by noise and the speed change in the loop, then clean /
@@ -32,6 +32,9 @@ VARIANTS = {
                      {"kind": "gaussian_noise", "snr_db": 10.0}],
     "speed": [{"kind": "speed_change", "cents": 200.0, "prob": 0.75}],
     "speed_noise": [{"kind": "speed_change", "cents": 200.0, "prob": 0.75}, {"kind": "gaussian_noise", "snr_db": 10.0}],
+    "stretch": [{"kind": "time_stretch", "rate": [0.85, 1.15], "prob": 0.75}],
+    "stretch_speed": [{"kind": "time_stretch", "rate": [0.85, 1.15], "prob": 0.75},
+                      {"kind": "speed_change", "cents": 100.0, "prob": 0.75}],
 }
 
 
@@ -73,9 +76,9 @@ def main():
             times[name].append(1e3 * a.elapsed_time(b) / steps)
     for name in VARIANTS:
         result[f"us_per_iteration/{name}"] = round(float(np.median(times[name])), 2)
-        print(f"{name:12s} {np.median(times[name]):8.1f} us per iteration (rounds: {', '.join(f'{t:.1f}' for t in times[name])})")
+        print(f"{name:13s} {np.median(times[name]):8.1f} us per iteration (rounds: {', '.join(f'{t:.1f}' for t in times[name])})")
     base = result["us_per_iteration/none"]
-    for name in ("noise", "suppression", "both", "reverb", "reverb_noise", "speed", "speed_noise"):
+    for name in ("noise", "suppression", "both", "reverb", "reverb_noise", "speed", "speed_noise", "stretch", "stretch_speed"):
         result[f"extra_us/{name}"] = round(result[f"us_per_iteration/{name}"] - base, 2)
     del sessions
 
