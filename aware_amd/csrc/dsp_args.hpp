@@ -36,7 +36,7 @@ __device__ __forceinline__ void nadam_clamp_update(float& p, float& mo, float& v
 // c: per-step scalars computed on the host (learning-rate schedule included), h: hyper-parameters:
 //   kind 1 adam / 2 adamw  c.x = -lr/bc1, c.z = sqrt(bc2), c.w = 1 - lr*wd (adamw);  h0 = 1-beta1, h1 = beta2, h2 = 1-beta2, h3 = eps
 //   kind 3 sgd             c.x = -lr, c.y = 1 on the first step (buf = grad);  h0 = momentum, h5 = nesterov, h6 = 1-dampening
-//   kind 4 rmsprop         c.x = -lr;  h1 = alpha, h2 = 1-alpha, h3 = eps
+//   kind 4 rmsprop         c.x = -lr;  h0 = momentum (0 = none; mo holds the momentum buffer), h1 = alpha, h2 = 1-alpha, h3 = eps
 //   kind 5 adagrad         c.x = -lr/(1+(t-1)*lr_decay);  h3 = eps
 //   kind 6 adamax          c.x = -lr/bc1;  h0 = 1-beta1, h1 = beta2, h3 = eps
 //   kind 7 adadelta        c.x = -lr;  h1 = rho, h2 = 1-rho, h3 = eps     (mo holds acc_delta, ve square_avg)
@@ -71,7 +71,10 @@ __device__ __forceinline__ void opt_clamp_update(int kind, float& p, float& mo, 
     } else if (kind == OPT_RMSPROP) {
         ve = ve * h[1] + (h[2] * g) * g;
         const float avg = sqrtf(ve) + h[3];
-        p = p + (c.x * g) / avg;
+        if (h[0] != 0.f) {
+            mo = mo * h[0] + g / avg;              // buf.mul_(momentum).addcdiv_(grad, avg)
+            p = p + c.x * mo;
+        } else p = p + (c.x * g) / avg;
     } else if (kind == OPT_ADAGRAD) {
         ve = ve + g * g;
         const float sd = sqrtf(ve) + h[3];

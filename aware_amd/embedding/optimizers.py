@@ -43,15 +43,14 @@ def get_optimizer(name: str, params=None, **kwargs) -> dict:
     for key, allowed in unsupported.items():
         if key in g and bool(g[key]) != allowed:
             raise NotImplementedError(f"optimizer '{name}': {key}={g[key]} is not on the HIP path")
-    if name == "rmsprop" and g["momentum"] != 0:
-        raise NotImplementedError("rmsprop with momentum is not on the HIP path")
     if name == "adagrad" and g.get("initial_accumulator_value", 0) != 0:
         raise NotImplementedError("adagrad with an initial accumulator value is not on the HIP path")
     return {"name": name, "kind": KINDS[name], "torch": opt, "group": g}
 
 
 def hyper_parameters(opt: dict) -> tuple[list, float]:
-    """(hyp[8] of opt_clamp_update, decoupled weight decay)."""
+    """(hyp[8] of opt_clamp_update, decoupled weight decay).  h[0] (1 - beta1, or the momentum of sgd / rmsprop) is the
+    param_group's value now; step_table carries the value of every step, which replaces it on the device."""
     g, name = opt["group"], opt["name"]
     h = [0.0] * 8
     wd_decoupled = 0.0
@@ -61,7 +60,7 @@ def hyper_parameters(opt: dict) -> tuple[list, float]:
     elif name == "sgd":
         h[0], h[5], h[6] = g["momentum"], float(bool(g["nesterov"])), 1.0 - g["dampening"]
     elif name == "rmsprop":
-        h[1], h[2], h[3] = g["alpha"], 1.0 - g["alpha"], g["eps"]
+        h[0], h[1], h[2], h[3] = g["momentum"], g["alpha"], 1.0 - g["alpha"], g["eps"]
     elif name == "adagrad":
         h[3] = g["eps"]
     elif name == "adadelta":
@@ -105,7 +104,9 @@ def step_table(opt: dict, num_iterations: int, scheduler=None) -> np.ndarray:
             ux, uy, h0 = -1.0, 1.0 if t == 1 else 0.0, float(g["momentum"])
         elif name == "adagrad":
             ux = -1.0 / (1.0 + (t - 1) * g["lr_decay"])
-        else:                                                       # rmsprop, adadelta
+        elif name == "rmsprop":
+            ux, h0 = -1.0, float(g["momentum"])
+        else:                                                       # adadelta
             ux = -1.0
         tab[t - 1] = (ux, uy, z, lr, h0)
         if scheduler is not None:
@@ -114,11 +115,13 @@ def step_table(opt: dict, num_iterations: int, scheduler=None) -> np.ndarray:
     return tab
 
 
-def step_scalars(opt: dict, tab: np.ndarray, t: int, lr: float | None = None):
-    """(coef4, hyp8) of step t (1-based) as float32 arrays for aware_opt_clamp_step."""
+def step_scalars(opt: dict, tab: np.ndarray, t: int, lr: float | None = None, hyp=None):
+    """(coef4, hyp8) of step t (1-based) as float32 arrays for aware_opt_clamp_step.  `hyp`: hyper_parameters(opt) taken
+    BEFORE step_table consumed a scheduler (CyclicLR rewrites the param_group's momentum / beta1 while it steps; the table
+    carries the per-step value in h0); None takes them now."""
     ux, uy, z, lr_t, h0 = tab[t - 1]
     lr = lr_t if lr is None else lr
-    h, wd = hyper_parameters(opt)
+    h, wd = hyper_parameters(opt) if hyp is None else (list(hyp[0]), hyp[1])
     if h0 >= 0:
         h[0] = h0
     cy = uy if opt["name"] == "sgd" else lr * uy

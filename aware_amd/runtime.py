@@ -303,7 +303,7 @@ class OptClamp:
 
     def __init__(self, param: torch.Tensor, name: str, num_steps: int, scheduler_name: str | None = None, scheduler_params=None,
                  **params):
-        from .embedding.optimizers import get_optimizer, step_table
+        from .embedding.optimizers import get_optimizer, hyper_parameters, step_table
         from .embedding.schedulers import get_scheduler
         self.lib = load_library()
         self.param = param
@@ -311,6 +311,7 @@ class OptClamp:
         sched = get_scheduler(scheduler_name, self.opt, num_steps, **(scheduler_params or {})) if scheduler_name else None
         if sched is not None and sched["plateau"] is not None:
             raise NotImplementedError("OptClamp: a firing ReduceLROnPlateau needs the per-clip state of an embed session")
+        self.hyp = hyper_parameters(self.opt)          # before the table consumes the scheduler (CyclicLR cycles momentum / beta1)
         self.table = step_table(self.opt, num_steps, sched["torch"] if sched else None)
         self.s1 = torch.zeros_like(param)
         self.s2 = torch.zeros_like(param)
@@ -319,7 +320,7 @@ class OptClamp:
     def step(self, grad: torch.Tensor, lo: torch.Tensor | None = None, hi: torch.Tensor | None = None):
         from .embedding.optimizers import step_scalars
         self.t += 1
-        c4, h8 = step_scalars(self.opt, self.table, self.t)
+        c4, h8 = step_scalars(self.opt, self.table, self.t, hyp=self.hyp)
         check(self.lib.aware_opt_clamp_step(self.opt["kind"], _ptr(self.param), _ptr(grad), _ptr(self.s1), _ptr(self.s2), _ptr(lo),
                                             _ptr(hi), self.param.numel(), c4.ctypes.data_as(C.POINTER(C.c_float)),
                                             h8.ctypes.data_as(C.POINTER(C.c_float)), _stream()), "aware_opt_clamp_step")
@@ -539,8 +540,8 @@ class EmbedSession:
         """Any optimiser / scheduler of the reference's registries (embedding.optimizers.get_optimizer /
         embedding.schedulers.get_scheduler dicts) instead of the model card's fused NAdam (aware_embed_set_optimizer)."""
         from .embedding.optimizers import hyper_parameters, step_table
+        hyp, wd = hyper_parameters(opt)                # before the table consumes the scheduler (CyclicLR cycles momentum / beta1)
         tab = np.ascontiguousarray(step_table(opt, self.cfg.num_iterations, sched["torch"]), dtype=np.float64)
-        hyp, wd = hyper_parameters(opt)
         oc = _lib.OptimizerConfig()
         oc.kind = opt["kind"]
         oc.hyp = (C.c_float * 8)(*hyp)

@@ -335,8 +335,9 @@ typedef struct aware_embed_config {
  * Any other registered optimiser / schedule: the HOST computes the per-step scalars of torch's single-tensor update under
  * the chosen learning-rate schedule, the device applies them in one element-wise launch per iteration (+ clamp, + best
  * snapshot).  kind: AWARE_OPT_*.  table: HOST [num_iterations][5] doubles per step t = 1..: (ux, uy, z, lr_t, h0_t) with
- * c.x = lr*ux, c.y = lr*uy (sgd: uy = 1 on the first step), c.z = z, h0_t >= 0 overrides hyp[0] (CyclicLR cycles beta1 /
- * momentum); hyp: see csrc/dsp_args.hpp::opt_clamp_update.  plateau != 0: torch's ReduceLROnPlateau (mode min, rel
+ * c.x = lr*ux, c.y = lr*uy (sgd: uy = 1 on the first step), c.z = z, h0_t >= 0 overrides hyp[0] (1 - beta1, or the momentum
+ * of sgd / rmsprop: CyclicLR cycles it); hyp: see csrc/dsp_args.hpp::opt_clamp_update (rmsprop: hyp[0] = momentum, 0 = none;
+ * with it state1 is torch's momentum buffer).  plateau != 0: torch's ReduceLROnPlateau (mode min, rel
  * threshold, cooldown 0) with one state PER CLIP, stepped with the clip's loss after each optimiser step; lr0 = initial rate.
  * Call after aware_embed_create and before the first aware_embed_iterate. */
 #define AWARE_OPT_NADAM 0
