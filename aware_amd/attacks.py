@@ -274,6 +274,23 @@ class OverlapAddStretch(Attack):
 
 
 @register
+class OverlapAddPitchShift(Attack):
+    """EXTENSION (not in the reference, parity unpinned): the clip's pitch moved by `cents` at its own duration, as the
+    resampling at R / 65536, R = 65536 + round(65536 (2^(cents / 1200) - 1)), of the plain overlap-add stretch at the coupled
+    rate round(2^32 / R) / 65536, in one launch, as embedding.loop_attacks.pitch_shift specifies it.  The output is as long as
+    the input.  Inside the embed loop it is the chain entry {"kind": "pitch_shift", "cents": ...}.  PitchShift is the phase
+    vocoder, built differently."""
+
+    def __init__(self, cents=50.0):
+        self.cents = float(cents)
+        self.m = int(round(65536.0 * (2.0 ** (self.cents / 1200.0) - 1.0)))
+        self.name = f"ola_ps_{cents}"
+
+    def apply_batch(self, x, sr):
+        return rt.pitch_shift_ola(x, [self.m] * x.B)
+
+
+@register
 class MP3Surrogate(Attack):
     """EXTENSION (not in the reference; BASELINE.json north_star): MP3-like quantisation surrogate
     -- STFT -> per-frame log-magnitude quantisation (`step_db` grid, bins more than `-floor_db` below

@@ -1725,6 +1725,9 @@ struct aware_embed {
         // directly behind it (sp == ts + 1) forms one stage u -> v -> z with it
         int ts = -1, q_lo = 0, q_hi = 0;
         float* v = nullptr;                       // [NS] between the stretch and the speed change of such a pair
+        // pitch shift (kind 5): entry ps of the chain, -1 without one; it excludes the three kinds above, reads u as the
+        // speed change does and draws from the speed offsets [p_lo, p_hi]
+        int ps = -1, p_lo = 0, p_hi = 0;
         const float* hann = nullptr;              // stretch_window()
         bool locked = false;                      // an optimiser step has run: the chain stays what it is
     } la;
@@ -1983,21 +1986,22 @@ extern "C" size_t aware_embed_loop_attack_workspace_bytes_ex(const aware_batch* 
     if (has_kind(attacks, n_attacks, AWARE_LOOP_REVERBERATION)) carve_loop_reverb(c, b, e.la);
     else if (has_kind(attacks, n_attacks, AWARE_LOOP_TIME_STRETCH))
         carve_loop_stretch(c, b, e.la, has_kind(attacks, n_attacks, AWARE_LOOP_SPEED_CHANGE));
-    else if (has_kind(attacks, n_attacks, AWARE_LOOP_SPEED_CHANGE)) carve_loop_speed(c, b, e.la);
+    else if (has_kind(attacks, n_attacks, AWARE_LOOP_SPEED_CHANGE) || has_kind(attacks, n_attacks, AWARE_LOOP_PITCH_SHIFT))
+        carve_loop_speed(c, b, e.la);
     return c.off;
 }
 static int set_loop_attacks(aware_embed* e, const aware_loop_attack_ex* attacks, int n_attacks, bool ex,
                             const uint32_t* seeds, void* workspace, size_t workspace_bytes, void* stream) {
     static_assert(AWARE_LOOP_GAUSSIAN_NOISE == kLoopGaussianNoise && AWARE_LOOP_SAMPLE_SUPPRESSION == kLoopSampleSuppression &&
                   AWARE_LOOP_REVERBERATION == kLoopReverberation && AWARE_LOOP_SPEED_CHANGE == kLoopSpeedChange &&
-                  AWARE_LOOP_TIME_STRETCH == kLoopTimeStretch, "");
+                  AWARE_LOOP_TIME_STRETCH == kLoopTimeStretch && AWARE_LOOP_PITCH_SHIFT == kLoopPitchShift, "");
     if (!e || n_attacks < 0 || n_attacks > kMaxLoopAttacks) return AWARE_E_BADARG;
     if (e->gexec || e->la.locked) return AWARE_E_BADARG;          // before the first aware_embed_iterate, as aware_embed_set_optimizer
-    if (n_attacks == 0) { e->la.n = 0; e->la.z = nullptr; e->la.rv = -1; e->la.sp = -1; e->la.ts = -1; e->la.h = nullptr; return AWARE_OK; }
+    if (n_attacks == 0) { e->la.n = 0; e->la.z = nullptr; e->la.rv = -1; e->la.sp = -1; e->la.ts = -1; e->la.ps = -1; e->la.h = nullptr; return AWARE_OK; }
     if (!attacks || !seeds || !workspace || ((uintptr_t)workspace & 255)) return AWARE_E_BADARG;
     const aware_batch* b = e->b;
     auto la = e->la;
-    la.rv = -1; la.sp = -1; la.ts = -1; la.h = nullptr; la.v = nullptr;
+    la.rv = -1; la.sp = -1; la.ts = -1; la.ps = -1; la.h = nullptr; la.v = nullptr;
     for (int j = 0; j < n_attacks; ++j) {
         const aware_loop_attack_ex& a = attacks[j];
         if (!(a.prob >= 0.f && a.prob <= 1.f)) return AWARE_E_BADARG;
@@ -2010,25 +2014,32 @@ static int set_loop_attacks(aware_embed* e, const aware_loop_attack_ex* attacks,
             la.k[j] = (int)a.param[0];
         } else if (a.kind == AWARE_LOOP_REVERBERATION && ex) {
             const float lo = a.param[0], hi = a.param[1], drr = a.param[2];
-            if (la.rv >= 0 || la.sp >= 0 || la.ts >= 0) return AWARE_E_BADARG;     // one reverberation per chain, and no speed change or time stretch beside it
+            if (la.rv >= 0 || la.sp >= 0 || la.ts >= 0 || la.ps >= 0) return AWARE_E_BADARG;     // one reverberation per chain, and no speed change, time stretch or pitch shift beside it
             if (!(lo >= 2.f) || !(hi <= (float)kReverbMaxIr) || !(lo <= hi) || lo != floorf(lo) || hi != floorf(hi) ||
                 !std::isfinite(drr))
                 return AWARE_E_BADARG;
             la.rv = j; la.n_lo = (int)lo; la.n_hi = (int)hi; la.gain = pow(10.0, (double)drr / 20.0);
         } else if (a.kind == AWARE_LOOP_SPEED_CHANGE && ex) {
             const float lo = a.param[0], hi = a.param[1];
-            if (la.rv >= 0 || la.sp >= 0) return AWARE_E_BADARG;     // one speed change per chain, and no reverberation beside it
+            if (la.rv >= 0 || la.sp >= 0 || la.ps >= 0) return AWARE_E_BADARG;     // one speed change per chain, and no reverberation or pitch shift beside it
             if (la.ts >= 0 && la.ts != j - 1) return AWARE_E_BADARG; // beside a time stretch: directly behind it
             if (!(lo >= (float)kSpeedMin) || !(hi <= (float)kSpeedMax) || !(lo <= hi) || lo != floorf(lo) || hi != floorf(hi))
                 return AWARE_E_BADARG;
             la.sp = j; la.m_lo = (int)lo; la.m_hi = (int)hi;
         } else if (a.kind == AWARE_LOOP_TIME_STRETCH && ex) {
             const float lo = a.param[0], hi = a.param[1];
-            // one time stretch per chain, no reverberation beside it, and no speed change in front of it
-            if (la.rv >= 0 || la.sp >= 0 || la.ts >= 0) return AWARE_E_BADARG;
+            // one time stretch per chain, no reverberation or pitch shift beside it, and no speed change in front of it
+            if (la.rv >= 0 || la.sp >= 0 || la.ts >= 0 || la.ps >= 0) return AWARE_E_BADARG;
             if (!(lo >= (float)kStretchMin) || !(hi <= (float)kStretchMax) || !(lo <= hi) || lo != floorf(lo) || hi != floorf(hi))
                 return AWARE_E_BADARG;
             la.ts = j; la.q_lo = (int)lo; la.q_hi = (int)hi;
+        } else if (a.kind == AWARE_LOOP_PITCH_SHIFT && ex) {
+            const float lo = a.param[0], hi = a.param[1];
+            // one pitch shift per chain, and none of the three other kinds that split a chain beside it
+            if (la.rv >= 0 || la.sp >= 0 || la.ts >= 0 || la.ps >= 0) return AWARE_E_BADARG;
+            if (!(lo >= (float)kSpeedMin) || !(hi <= (float)kSpeedMax) || !(lo <= hi) || lo != floorf(lo) || hi != floorf(hi))
+                return AWARE_E_BADARG;
+            la.ps = j; la.p_lo = (int)lo; la.p_hi = (int)hi;
         } else {
             return AWARE_E_BADARG;
         }
@@ -2040,9 +2051,9 @@ static int set_loop_attacks(aware_embed* e, const aware_loop_attack_ex* attacks,
     carve_loop_attacks(c, b, la);
     if (la.rv >= 0) carve_loop_reverb(c, b, la);
     else if (la.ts >= 0) carve_loop_stretch(c, b, la, la.sp >= 0);
-    else if (la.sp >= 0) carve_loop_speed(c, b, la);
+    else if (la.sp >= 0 || la.ps >= 0) carve_loop_speed(c, b, la);
     if (!c.ok) return AWARE_E_WORKSPACE;
-    if (la.ts >= 0 && !(la.hann = stretch_window())) return AWARE_E_HIP;
+    if ((la.ts >= 0 || la.ps >= 0) && !(la.hann = stretch_window())) return AWARE_E_HIP;
     hipStream_t st = (hipStream_t)stream;
     HIPCHK(hipMemsetAsync(la.gpad0, 0, (size_t)b->B * 1024 * sizeof(float), st));
     HIPCHK(hipMemcpyAsync(la.seeds, seeds, (size_t)b->B * sizeof(unsigned), hipMemcpyHostToDevice, st));
@@ -2144,6 +2155,20 @@ extern "C" int aware_stretch_ola(const float* in, const int* in_off, const int* 
     return AWARE_OK;
 }
 
+// ---- the pitch shift alone (EXTENSION; attacks.OverlapAddPitchShift, tests) ------------------------------------------------
+extern "C" int aware_pitch_shift_ola(const float* in, const int* in_off, const int* in_len, float* out, const int* out_off,
+                                     const int* out_len, int B, int max_len, const int* m, int adjoint, void* stream) {
+    if (!in || !in_off || !in_len || !out || !out_off || !out_len || !m || in == out) return AWARE_E_BADARG;
+    if (B < 1 || B > 65535 || max_len < 1 || max_len > (1 << 30) || adjoint < 0 || adjoint > 1) return AWARE_E_BADARG;
+    PitchLaunch L;
+    if (!(L.window = stretch_window())) return AWARE_E_HIP;
+    L.in = in; L.out = out; L.B = B; L.adjoint = adjoint; L.max_len = max_len; L.m = m;
+    L.x_off = in_off; L.x_len = in_len; L.z_off = out_off; L.z_len = out_len;
+    launch_pitch_shift(L, (hipStream_t)stream);
+    LAUNCHCHK();
+    return AWARE_OK;
+}
+
 extern "C" void aware_embed_destroy(aware_embed* e) {
     if (!e) return;
 
@@ -2232,6 +2257,15 @@ static StretchLaunch stretch_launch(const aware_embed* e, const float* in, float
     return S;
 }
 
+static PitchLaunch pitch_launch(const aware_embed* e, const float* in, float* out, int adjoint, int step_back) {
+    const auto& la = e->la;
+    PitchLaunch S;
+    S.in = in; S.out = out; S.window = la.hann; S.B = e->b->B; S.adjoint = adjoint; S.frame_off = e->b->d_frame_off;
+    S.pstride = e->b->pstride; S.run_blocks = e->b->synth_run; S.step = e->step; S.step_back = step_back; S.seeds = la.seeds;
+    S.entry = la.ps; S.m_lo = la.p_lo; S.m_hi = la.p_hi; S.prob = la.prob[la.ps];
+    return S;
+}
+
 static ConvolveLaunch reverb_launch(const aware_embed* e, const float* in, float* out, int adjoint) {
     const auto& la = e->la;
     ConvolveLaunch C;
@@ -2271,7 +2305,7 @@ static int embed_iteration(aware_embed* e, hipStream_t st, int do_step, float* g
         A.step = e->step; A.seeds = la.seeds; A.n = la.n;
         for (int j = 0; j < la.n; ++j) { A.kind[j] = la.kind[j]; A.k[j] = la.k[j]; A.inv_snr[j] = la.inv_snr[j]; A.prob[j] = la.prob[j]; }
         A.yraw = e->yraw; A.pmaxY = e->pmaxY; A.psq = la.psq; A.z = la.z; A.pmaxZ = la.pmaxZ;
-        if (la.rv >= 0 || la.sp >= 0 || la.ts >= 0) { A.idle_plain = 1; A.gpad_out = la.gpad0; }
+        if (la.rv >= 0 || la.sp >= 0 || la.ts >= 0 || la.ps >= 0) { A.idle_plain = 1; A.gpad_out = la.gpad0; }
         if (la.ts >= 0) {
             // the entries in front of the stretch on N(N(yraw)), the overlap-add (and the resampling of a speed change
             // directly behind it), the entries behind
@@ -2285,6 +2319,12 @@ static int embed_iteration(aware_embed* e, hipStream_t st, int do_step, float* g
             launch_loop_attack_stage(A, 0, la.sp, e->yraw, 1, la.u, nullptr, st);
             launch_speed_change(speed_launch(e, la.u, la.z, 0, 0), st);
             launch_loop_attack_stage(A, la.sp + 1, la.n, la.z, 0, la.z, la.pmaxZ, st);
+        } else if (la.ps >= 0) {
+            // the same shape: the entries in front of the pitch shift on N(N(yraw)), the fused stretch and resampling, the
+            // entries behind it
+            launch_loop_attack_stage(A, 0, la.ps, e->yraw, 1, la.u, nullptr, st);
+            launch_pitch_shift(pitch_launch(e, la.u, la.z, 0, 0), st);
+            launch_loop_attack_stage(A, la.ps + 1, la.n, la.z, 0, la.z, la.pmaxZ, st);
         } else if (la.rv < 0) {
             launch_loop_attack_forward(A, st);
         } else {
@@ -2354,6 +2394,13 @@ static int embed_iteration(aware_embed* e, hipStream_t st, int do_step, float* g
             A.gy_out = nullptr;
             launch_speed_change(speed_launch(e, e->la.u, e->gy, 1, A.step_back), st);
             launch_loop_attack_stage_bwd(A, 0, e->la.sp, 0, 1, st);
+        } else if (e->la.ps >= 0) {
+            // the mirror, as for the speed change: into u, the fused gather-form adjoint back into gy, the stage in front
+            A.gy_out = e->la.u;
+            launch_loop_attack_stage_bwd(A, e->la.ps + 1, e->la.n, 1, 0, st);
+            A.gy_out = nullptr;
+            launch_pitch_shift(pitch_launch(e, e->la.u, e->gy, 1, A.step_back), st);
+            launch_loop_attack_stage_bwd(A, 0, e->la.ps, 0, 1, st);
         } else if (e->la.rv < 0) {
             launch_loop_attack_backward(A, st);
         } else {

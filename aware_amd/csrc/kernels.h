@@ -356,7 +356,8 @@ void launch_stoi(const StoiLaunch& L, hipStream_t st);
 // ---- loop_attack_kernels.hip: attack-aware embedding (EXTENSION): a chain of attacks between the embed loop's synthesis and
 // its analysis, drawn afresh at every optimiser step (aware_embed_set_loop_attacks) --------------------------------------
 constexpr int kMaxLoopAttacks = 4;
-constexpr int kLoopGaussianNoise = 0, kLoopSampleSuppression = 1, kLoopReverberation = 2, kLoopSpeedChange = 3, kLoopTimeStretch = 4;      // AWARE_LOOP_* of aware_hip.h
+constexpr int kLoopGaussianNoise = 0, kLoopSampleSuppression = 1, kLoopReverberation = 2, kLoopSpeedChange = 3, kLoopTimeStretch = 4,
+              kLoopPitchShift = 5;      // AWARE_LOOP_* of aware_hip.h
 struct LoopAttackLaunch {
     const int* frame_off = nullptr;
     const int* pcount = nullptr;          // [B] synthesis runs per clip: the partials' layout
@@ -476,5 +477,27 @@ struct StretchLaunch {
 // when the device refuses
 const float* stretch_window();
 void launch_time_stretch(const StretchLaunch& L, hipStream_t st);
+
+// ---- loop_pitch_kernels.hip: pitch shift (EXTENSION): the speed change at a drawn ratio R / 65536 of the overlap-add stretch
+// at the coupled rate Q = round(2^32 / R), fused (the stretched signal lives in LDS only), inside the embed loop (chain kind 5)
+// and stand-alone (aware_pitch_shift_ola), and its adjoint in gather form --------------------------------------------------
+struct PitchLaunch {
+    const float* in = nullptr; float* out = nullptr;      // never the same buffer
+    const float* window = nullptr;        // stretch_window()
+    int B = 0, adjoint = 0;               // 0: out = z from in = x; 1: out = gx from in = gz
+    // the embed loop's layout: x and z both Ny_b long at sig_offset, one workgroup per synthesis run, m drawn in the kernel
+    const int* frame_off = nullptr;
+    int pstride = 0, run_blocks = 0;
+    const int* step = nullptr; int step_back = 0;
+    const unsigned* seeds = nullptr;      // [B]
+    int entry = 0, m_lo = 0, m_hi = 0;    // speed offsets, inside kSpeedMin .. kSpeedMax
+    float prob = 0.f;
+    // or a ragged batch (frame_off null): x is x_len[b] floats at x_off[b], z is z_len[b] floats at z_off[b], m[b] given
+    const int* x_off = nullptr; const int* x_len = nullptr;
+    const int* z_off = nullptr; const int* z_len = nullptr;
+    int max_len = 0;                      // >= every length written
+    const int* m = nullptr;               // [B]
+};
+void launch_pitch_shift(const PitchLaunch& L, hipStream_t st);
 
 }  // namespace aware

@@ -40,6 +40,14 @@ the loop's new stage.  For clip b (length Ny) at optimiser step s with seed_b:
         chain and not beside a reverberation; a speed_change may follow it directly (tempo and pitch then move independently,
         a pitch shift being the diagonal), and in no other place of such a chain.
 
+      pitch_shift(cents = c or [lo, hi], parsed and drawn as speed_change's: m from r[3] on [m_lo, m_hi], R = 65536 + m),
+        the coupled rate Q = ((1 << 32) + R // 2) // R in 64-bit integers (Q R is within R / 2 of 2^32), mq = Q - 65536,
+        L_u = stretch_length(Ny, mq): on: x = speed_change(time_stretch(x, mq, L_u), m, Ny): the overlap-add stretches the clip
+        to its true length L_u (about R / 65536 of Ny; zero outside [0, L_u)), and the resampling plays that at R / 65536 of its
+        speed, so the pitch moves by the drawn interval and the duration stays: the one diagonal of the tempo-pitch plane that
+        the pair above leaves most steps.  Linear in x; m = 0 is the identity; m is detached.  At most one per chain, and not in
+        a chain with a reverberation, a speed change or a time stretch.
+
 In the loop x = N(N(y)) of the raw synthesis y, N(v) = v / (max|v| + 1e-8), and the analysis (N, N, STFT, band magnitudes)
 runs on the chain's output."""
 from __future__ import annotations
@@ -50,15 +58,49 @@ import numpy as np
 import torch
 
 MAX_ATTACKS = 4
-KINDS = {"gaussian_noise": 0, "sample_suppression": 1, "reverberation": 2, "speed_change": 3, "time_stretch": 4}          # AWARE_LOOP_* of include/aware_hip.h
+KINDS = {"gaussian_noise": 0, "sample_suppression": 1, "reverberation": 2, "speed_change": 3, "time_stretch": 4,
+         "pitch_shift": 5}      # AWARE_LOOP_* of include/aware_hip.h
 _KEYS = {"gaussian_noise": {"kind", "snr_db", "prob"}, "sample_suppression": {"kind", "seconds", "prob"},
-         "reverberation": {"kind", "rt60", "drr_db", "prob"}, "speed_change": {"kind", "cents", "prob"}, "time_stretch": {"kind", "rate", "prob"}}
+         "reverberation": {"kind", "rt60", "drr_db", "prob"}, "speed_change": {"kind", "cents", "prob"}, "time_stretch": {"kind", "rate", "prob"},
+         "pitch_shift": {"kind", "cents", "prob"}}
 _KEY1 = 0x5EED
 MAX_IR = 8192                   # taps of the longest impulse response
 _IR_WORD = 8                    # third Philox counter word of the impulse responses (0: noise, 1..4: entry draws)
-MAX_CENTS = 400.0               # widest speed change either way
+MAX_CENTS = 400.0               # widest speed change or pitch shift either way
 MIN_RATE, MAX_RATE = 0.75, 4.0 / 3.0            # slowest and fastest time stretch
 STRETCH_HOP, STRETCH_WIN = 256, 1024            # the overlap-add's hop and window: the loop's STFT geometry
+
+
+def _no_pitch_shift(j: int, kind: str, out: list[dict]) -> None:
+    if any(o["kind"] == "pitch_shift" for o in out):
+        raise ValueError(f"loop_attacks[{j}] ({kind}): a chain holds a pitch shift or a {kind.replace('_', ' ')}, not both")
+
+
+def _parse_cents(j: int, kind: str, a: dict) -> list[float]:
+    """[lo, hi] of a speed_change or pitch_shift entry's cents: a scalar c > 0 means [-c, c]; -400 <= lo <= hi <= 400, and at
+    least one speed offset inside."""
+    if "cents" not in a:
+        raise ValueError(f"loop_attacks[{j}] ({kind}): cents is required")
+    ct = a["cents"]
+    try:
+        if isinstance(ct, (list, tuple)):
+            if len(ct) != 2:
+                raise TypeError
+            lo, hi = float(ct[0]), float(ct[1])
+        else:
+            lo, hi = -float(ct), float(ct)
+            if not hi > 0.0:
+                raise ValueError(f"loop_attacks[{j}] ({kind}): a scalar cents has to be > 0; got {ct!r}")
+    except TypeError:
+        raise ValueError(f"loop_attacks[{j}] ({kind}): cents = {ct!r} is neither a number nor [lo, hi]") from None
+    if not (math.isfinite(lo) and math.isfinite(hi) and -MAX_CENTS <= lo <= hi <= MAX_CENTS):
+        raise ValueError(f"loop_attacks[{j}] ({kind}): cents needs -{MAX_CENTS:g} <= lo <= hi <= {MAX_CENTS:g}, "
+                         f"both finite; got {ct!r}")
+    m_lo, m_hi = speed_range({"cents": [lo, hi]})
+    if m_lo > m_hi:
+        raise ValueError(f"loop_attacks[{j}] ({kind}): cents = {ct!r} holds no speed offset "
+                         f"(m_lo = {m_lo} > m_hi = {m_hi}, in units of 1 / 65536)")
+    return [lo, hi]
 
 
 def parse_chain(chain) -> list[dict]:
@@ -70,7 +112,9 @@ def parse_chain(chain) -> list[dict]:
     cents, a scalar <= 0, cents not -400 <= lo <= hi <= 400 (finite), a range that holds no speed offset (m_lo > m_hi), a
     second speed change, a speed change in a chain with a reverberation; for {"kind": "time_stretch", "rate": 1.1 |
     [0.9, 1.1]}: a missing rate, a scalar <= 1, rate not 0.75 <= lo <= hi <= 4/3 (finite), a range that holds no offset, a
-    second stretch, a stretch in a chain with a reverberation, a speed change anywhere but directly behind the stretch."""
+    second stretch, a stretch in a chain with a reverberation, a speed change anywhere but directly behind the stretch; for {"kind": "pitch_shift",
+    "cents": 100.0 | [-50.0, 120.0]}: what a speed change's cents are refused for, a second pitch shift, a pitch shift in a
+    chain with a reverberation, a speed change or a time stretch."""
     if not chain:
         return []
     if isinstance(chain, dict) or not isinstance(chain, (list, tuple)):
@@ -97,6 +141,7 @@ def parse_chain(chain) -> list[dict]:
         elif kind == "reverberation":
             if any(o["kind"] == "reverberation" for o in out):
                 raise ValueError(f"loop_attacks[{j}] (reverberation): at most one reverberation per chain")
+            _no_pitch_shift(j, kind, out)
             if any(o["kind"] == "speed_change" for o in out):
                 raise ValueError(f"loop_attacks[{j}] (reverberation): a chain holds a speed change or a reverberation, not both")
             if any(o["kind"] == "time_stretch" for o in out):
@@ -117,35 +162,16 @@ def parse_chain(chain) -> list[dict]:
         elif kind == "speed_change":
             if any(o["kind"] == "speed_change" for o in out):
                 raise ValueError(f"loop_attacks[{j}] (speed_change): at most one speed change per chain")
+            _no_pitch_shift(j, kind, out)
             if any(o["kind"] == "reverberation" for o in out):
                 raise ValueError(f"loop_attacks[{j}] (speed_change): a chain holds a speed change or a reverberation, not both")
             if any(o["kind"] == "time_stretch" for o in out) and out[-1]["kind"] != "time_stretch":
                 raise ValueError(f"loop_attacks[{j}] (speed_change): beside a time stretch, the speed change follows it directly")
-            if "cents" not in a:
-                raise ValueError(f"loop_attacks[{j}] (speed_change): cents is required")
-            ct = a["cents"]
-            try:
-                if isinstance(ct, (list, tuple)):
-                    if len(ct) != 2:
-                        raise TypeError
-                    lo, hi = float(ct[0]), float(ct[1])
-                else:
-                    lo, hi = -float(ct), float(ct)
-                    if not hi > 0.0:
-                        raise ValueError(f"loop_attacks[{j}] (speed_change): a scalar cents has to be > 0; got {ct!r}")
-            except TypeError:
-                raise ValueError(f"loop_attacks[{j}] (speed_change): cents = {ct!r} is neither a number nor [lo, hi]") from None
-            if not (math.isfinite(lo) and math.isfinite(hi) and -MAX_CENTS <= lo <= hi <= MAX_CENTS):
-                raise ValueError(f"loop_attacks[{j}] (speed_change): cents needs -{MAX_CENTS:g} <= lo <= hi <= {MAX_CENTS:g}, "
-                                 f"both finite; got {ct!r}")
-            e["cents"] = [lo, hi]
-            m_lo, m_hi = speed_range(e)
-            if m_lo > m_hi:
-                raise ValueError(f"loop_attacks[{j}] (speed_change): cents = {ct!r} holds no speed offset "
-                                 f"(m_lo = {m_lo} > m_hi = {m_hi}, in units of 1 / 65536)")
+            e["cents"] = _parse_cents(j, kind, a)
         elif kind == "time_stretch":
             if any(o["kind"] == "time_stretch" for o in out):
                 raise ValueError(f"loop_attacks[{j}] (time_stretch): at most one time stretch per chain")
+            _no_pitch_shift(j, kind, out)
             if any(o["kind"] == "reverberation" for o in out):
                 raise ValueError(f"loop_attacks[{j}] (time_stretch): a chain holds a time stretch or a reverberation, not both")
             if any(o["kind"] == "speed_change" for o in out):
@@ -173,6 +199,13 @@ def parse_chain(chain) -> list[dict]:
             if m_lo > m_hi:
                 raise ValueError(f"loop_attacks[{j}] (time_stretch): rate = {rr!r} holds no offset "
                                  f"(m_lo = {m_lo} > m_hi = {m_hi}, in units of 1 / 65536)")
+        elif kind == "pitch_shift":
+            if any(o["kind"] == "pitch_shift" for o in out):
+                raise ValueError(f"loop_attacks[{j}] (pitch_shift): at most one pitch shift per chain")
+            for other in ("reverberation", "speed_change", "time_stretch"):
+                if any(o["kind"] == other for o in out):
+                    raise ValueError(f"loop_attacks[{j}] (pitch_shift): a chain holds a pitch shift or a {other.replace('_', ' ')}, not both")
+            e["cents"] = _parse_cents(j, kind, a)
         else:
             if "seconds" not in a or not math.isfinite(float(a["seconds"])) or float(a["seconds"]) <= 0.0:
                 raise ValueError(f"loop_attacks[{j}] (sample_suppression): seconds > 0 is required")
@@ -192,7 +225,7 @@ def reverb_taps(entry: dict, sample_rate: int) -> tuple[int, int]:
 
 
 def speed_range(entry: dict) -> tuple[int, int]:
-    """(m_lo, m_hi) = (ceil(65536 (2^(lo / 1200) - 1)), floor(65536 (2^(hi / 1200) - 1))) of a parsed speed_change entry, in
+    """(m_lo, m_hi) = (ceil(65536 (2^(lo / 1200) - 1)), floor(65536 (2^(hi / 1200) - 1))) of a parsed speed_change or pitch_shift entry, in
     float64: the speed offsets, in units of 1 / 65536, that lie inside the range of cents."""
     lo, hi = entry["cents"]
     return (int(math.ceil(65536.0 * (2.0 ** (lo / 1200.0) - 1.0))), int(math.floor(65536.0 * (2.0 ** (hi / 1200.0) - 1.0))))
@@ -361,6 +394,28 @@ def time_stretch(x: torch.Tensor, m: int, n_out: int | None = None) -> torch.Ten
     return 0.5 * z
 
 
+def pitch_offsets(m: int) -> tuple[int, int]:
+    """(R, Q) of a pitch shift at the speed offset m: R = 65536 + m, the ratio the pitch moves by in units of 1 / 65536, and
+    the coupled stretch rate Q = ((1 << 32) + R // 2) // R, the nearest integer to 2^32 / R, so that Q R / 2^32 is 1 to within
+    2^-17: the stretch lengthens the clip by what the resampling shortens it."""
+    R = 65536 + int(m)
+    return R, ((1 << 32) + R // 2) // R
+
+
+def pitch_shift(x: torch.Tensor, m: int, n_out: int | None = None) -> torch.Tensor:
+    """x [..., n] with its pitch moved by the ratio R / 65536, R = 65536 + m, at its own duration:
+    speed_change(time_stretch(x, mq, L_u), m, n_out) with (R, Q) = pitch_offsets(m), mq = Q - 65536 and the intermediate at its
+    true stretched length L_u = stretch_length(n, mq), zero outside; n_out samples (default n).  Linear in x and differentiable;
+    m = 0 returns x."""
+    n = x.shape[-1]
+    n_out = n if n_out is None else int(n_out)
+    m = int(m)
+    if m == 0 and n_out == n:
+        return x
+    mq = pitch_offsets(m)[1] - 65536
+    return speed_change(time_stretch(x, mq, stretch_length(n, mq)), m, n_out)
+
+
 def _convolve(xb: torch.Tensor, h: np.ndarray) -> torch.Tensor:
     """(h * xb)[0 : len(xb)] in xb's dtype through an FFT at least len(xb) + len(h) - 1 long; differentiable in xb."""
     ny, nh = xb.shape[-1], len(h)
@@ -402,6 +457,9 @@ def apply_chain(x, chain, seeds, step: int, sample_rate: int = 16000):
             elif a["kind"] == "time_stretch":
                 if on:
                     xb = time_stretch(xb, stretch_offset(r[3], *stretch_range(a)))
+            elif a["kind"] == "pitch_shift":
+                if on:
+                    xb = pitch_shift(xb, speed_offset(r[3], *speed_range(a)))
             elif on:
                 power = float(np.mean(xb.detach().double().cpu().numpy() ** 2))
                 sigma = math.sqrt(power / (10.0 ** (a["snr_db"] / 10.0)))
@@ -413,13 +471,13 @@ def apply_chain(x, chain, seeds, step: int, sample_rate: int = 16000):
 
 def device_entries_ex(chain: list[dict], sample_rate: int):
     """(kind, prob, [param0..3]) of the C ABI's aware_loop_attack_ex: kinds 0 and 1 as device_entries in param[0]; a
-    reverberation has param = [n_lo, n_hi, drr_db, 0], a speed change or a time stretch [m_lo, m_hi, 0, 0]."""
+    reverberation has param = [n_lo, n_hi, drr_db, 0], a speed change, a time stretch or a pitch shift [m_lo, m_hi, 0, 0]."""
     out = []
     for a in chain:
         if a["kind"] == "reverberation":
             n_lo, n_hi = reverb_taps(a, sample_rate)
             out.append((KINDS[a["kind"]], a["prob"], [float(n_lo), float(n_hi), a["drr_db"], 0.0]))
-        elif a["kind"] == "speed_change":
+        elif a["kind"] in ("speed_change", "pitch_shift"):
             m_lo, m_hi = speed_range(a)
             out.append((KINDS[a["kind"]], a["prob"], [float(m_lo), float(m_hi), 0.0, 0.0]))
         elif a["kind"] == "time_stretch":
@@ -433,6 +491,6 @@ def device_entries_ex(chain: list[dict], sample_rate: int):
 
 def device_entries(chain: list[dict], sample_rate: int):
     """(kind, param, prob) triples of the C ABI (aware_loop_attack): param = snr_db or the suppression length in samples.
-    Chains of these two kinds only; a reverberation, a speed change or a time stretch goes through device_entries_ex."""
+    Chains of these two kinds only; every other kind goes through device_entries_ex."""
     return [(KINDS[a["kind"]], a["snr_db"] if a["kind"] == "gaussian_noise" else float(suppression_samples(a, sample_rate)),
              a["prob"]) for a in chain]

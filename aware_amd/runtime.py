@@ -570,7 +570,7 @@ class EmbedSession:
             raise ValueError(f"set_loop_attacks: {self.batch.B} clips but {len(seeds)} seeds")
         la.check_lengths(chain, sample_rate, self.batch.out_lengths)      # ValueError naming the clip, before any launch
         sd = (C.c_uint32 * self.batch.B)(*[int(s) & 0xFFFFFFFF for s in seeds])
-        if any(a["kind"] in ("reverberation", "speed_change", "time_stretch") for a in chain):
+        if any(a["kind"] in ("reverberation", "speed_change", "time_stretch", "pitch_shift") for a in chain):
             # the entry points with four parameters per entry; chains of the two older kinds keep the older call
             ent = la.device_entries_ex(chain, sample_rate)
             arr = (_lib.LoopAttackEx * len(ent))(*[_lib.LoopAttackEx(k, pr, (C.c_float * 4)(*p)) for k, pr, p in ent])
@@ -956,6 +956,29 @@ def stretch_ola(x: Ragged, m, adjoint: bool = False, out_lengths=None) -> Ragged
     src, dst = (out, x) if adjoint else (x, out)
     check(lib.aware_stretch_ola(_ptr(xin), _ptr(src.d_off), _ptr(src.d_len), _ptr(out.data), _ptr(dst.d_off), _ptr(dst.d_len),
                                 x.B, max(x.max_len, out.max_len), _ptr(md), int(bool(adjoint)), _stream()), "aware_stretch_ola")
+    return out
+
+
+def pitch_shift_ola(x: Ragged, m, adjoint: bool = False, out_lengths=None) -> Ragged:
+    """Per clip embedding.loop_attacks.pitch_shift at the speed offsets m (B integers, or one for all): clip b with its pitch
+    moved by the ratio (65536 + m[b]) / 65536 at its own duration, the overlap-add stretch at the coupled rate and the
+    resampling in one launch (aware_pitch_shift_ola), out_lengths[b] samples long (default: the clip's own length).  With
+    adjoint, x holds the gradient with respect to that output and the result, out_lengths long, is the gradient with respect to
+    the input (out_lengths is then the forward pass's input lengths)."""
+    lib = load_library()
+    ms = [int(m)] * x.B if np.isscalar(m) else [int(v) for v in m]
+    if len(ms) != x.B or any(v < -13520 or v > 17034 for v in ms):
+        raise ValueError(f"pitch_shift_ola: {x.B} speed offsets within -13520..17034 (-+400 cents) are required; got {ms}")
+    out_len = x.lengths if out_lengths is None else [int(n) for n in out_lengths]
+    if len(out_len) != x.B or min(out_len) < 1:
+        raise ValueError(f"pitch_shift_ola: {x.B} output lengths >= 1 are required; got {out_len}")
+    xin = x.data if x.data.dtype == torch.float32 else x.data.float()
+    out = Ragged(torch.empty(sum(out_len), dtype=torch.float32, device=xin.device), out_len)
+    md = torch.tensor(ms, dtype=torch.int32, device=xin.device)
+    # the C entry names the two sides of the forward operator: with adjoint, `out` is on the input side
+    src, dst = (out, x) if adjoint else (x, out)
+    check(lib.aware_pitch_shift_ola(_ptr(xin), _ptr(src.d_off), _ptr(src.d_len), _ptr(out.data), _ptr(dst.d_off), _ptr(dst.d_len),
+                                    x.B, max(x.max_len, out.max_len), _ptr(md), int(bool(adjoint)), _stream()), "aware_pitch_shift_ola")
     return out
 
 

@@ -602,7 +602,8 @@ int aware_speed_change(const float* in, const int* in_off, const int* in_len, fl
  * speed change in the same chain anywhere but directly behind the stretch.
  * aware_embed_loop_attack_workspace_bytes_ex grows by one signal for such a chain, by two for the pair; chains without the
  * kind need what they needed.  Added without a version step. */
-#define AWARE_LOOP_TIME_STRETCH 4        /* param = m_lo, m_hi (the host converts rates) */
+#define AWARE_LOOP_TIME_STRETCH 4        /* param = m_lo, m_hi (the host converts rates); a pitch shift, the diagonal of
+                                          * the stretch-speed pair with one draw for both, is AWARE_LOOP_PITCH_SHIFT below */
 /* The same operator alone, on a ragged batch, with the argument list of aware_speed_change: clip b of the x side is in_len[b]
  * floats at float offset in_off[b], of the z side out_len[b] floats at out_off[b] (dev int [B], any offsets, every length
  * <= max_len <= 2^30), m dev int [B].  adjoint 0: `in` holds x and `out` receives z[0 : out_len[b]] (out_len = in_len keeps
@@ -614,6 +615,29 @@ int aware_speed_change(const float* in, const int* in_off, const int* in_len, fl
  * -16384..21845 is copied as with m = 0. */
 int aware_stretch_ola(const float* in, const int* in_off, const int* in_len, float* out, const int* out_off,
                       const int* out_len, int B, int max_len, const int* m, int adjoint, void* stream);
+
+/* ---- pitch shift inside the loop and as an attack (EXTENSION, parity unpinned: the reference's is a library call) ------------
+ * The _ex pair also accepts (the older entry point keeps refusing every kind above 1)
+ *   AWARE_LOOP_PITCH_SHIFT, param = { m_lo, m_hi }, the speed offsets of AWARE_LOOP_SPEED_CHANGE: with r the entry's draw,
+ *     m = m_lo + ((r[3] * (m_hi - m_lo + 1)) >> 32),  R = 65536 + m: the pitch moves by the ratio R / 65536 (the host converts
+ *     cents as for the speed change) and the duration stays.  The coupled rate Q = ((1 << 32) + R / 2) / R and
+ *     L_u = ((Ny_b - 1) << 16) / Q + 1 in 64-bit integers;
+ *   on: u = the AWARE_LOOP_TIME_STRETCH operator at Q on x, L_u samples long (its true stretched length) and zero outside;
+ *   z = the AWARE_LOOP_SPEED_CHANGE operator at R on u, Ny_b samples long.  One fused launch: u is never in memory.  m = 0 is
+ *   the identity.  R and Q are CONSTANTS in the backward pass, which is the exact transpose in gather form (the resampling's
+ *   into gu over ascending i, then the stretch's over ascending t; no atomics).  Entries in front of it and behind it behave as
+ *   around a lone speed change, and a clip on which no entry fires at a step leaves the bits of the loop without a chain.
+ * AWARE_E_BADARG of the _ex setter, besides those above: a value that is not an integer, m_lo > m_hi, m_lo < -13520 or
+ * m_hi > 17034, a second pitch shift, a pitch shift together with a reverberation, a speed change or a time stretch.
+ * aware_embed_loop_attack_workspace_bytes_ex for a chain with the kind is that of the same chain with a speed change in its
+ * place; chains without the kind need what they needed.  Added without a version step. */
+#define AWARE_LOOP_PITCH_SHIFT 5         /* param = m_lo, m_hi (the host converts cents) */
+/* The same operator alone, on a ragged batch, with the argument list and the conventions of aware_speed_change and
+ * aware_stretch_ola (x side: in_off / in_len, z side: out_off / out_len; adjoint 1 reads gz on the z side and writes gx on the
+ * x side; the window table is uploaded on the first call on a device).  AWARE_E_BADARG as aware_stretch_ola; a clip whose m[b]
+ * lies outside -13520..17034 is copied as with m = 0. */
+int aware_pitch_shift_ola(const float* in, const int* in_off, const int* in_len, float* out, const int* out_off,
+                          const int* out_len, int B, int max_len, const int* m, int adjoint, void* stream);
 
 /* ---- bare GEMM (tests / roofline): C[M][N] = A[M][K] * Bt[N][K]^T + bias ------------------------------ */
 int aware_gemm_nt(const float* A, int lda, const float* Bt, int ldb, const float* bias, float* C, int ldc,
