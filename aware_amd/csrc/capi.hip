@@ -1728,6 +1728,11 @@ struct aware_embed {
         // pitch shift (kind 5): entry ps of the chain, -1 without one; it excludes the three kinds above, reads u as the
         // speed change does and draws from the speed offsets [p_lo, p_hi]
         int ps = -1, p_lo = 0, p_hi = 0;
+        // phase vocoder (kind 6): entry pv of the chain, -1 without one; it excludes the four kinds above and reads u as the
+        // speed change does.  Stretch offsets [pq_lo, pq_hi] and speed offsets [pm_lo, pm_hi], lo > hi where the mode is absent
+        int pv = -1, pq_lo = 0, pq_hi = -1, pm_lo = 0, pm_hi = -1;
+        cf* pvS = nullptr;                        // [NF][520] the spectrum of u; the backward pass turns it into its gradient
+        cf* pvY = nullptr;                        // [NF][520] the vocoded spectrum; the backward pass holds dL/dY in it
         const float* hann = nullptr;              // stretch_window()
         bool locked = false;                      // an optimiser step has run: the chain stays what it is
     } la;
@@ -1970,6 +1975,12 @@ template <typename LA> static void carve_loop_stretch(Carver& c, const aware_bat
     la.u = c.take<float>(b->NS);
     if (pair) la.v = c.take<float>(b->NS);
 }
+// the phase vocoder's part: the same one signal, and the two spectra between the staged STFT and iSTFT
+template <typename LA> static void carve_loop_pv(Carver& c, const aware_batch* b, LA& la) {
+    la.u = c.take<float>(b->NS);
+    la.pvS = c.take<cf>((size_t)b->NF * 520);
+    la.pvY = c.take<cf>((size_t)b->NF * 520);
+}
 extern "C" size_t aware_embed_loop_attack_workspace_bytes(const aware_batch* b, int n_attacks) {
     if (!b || b->general || n_attacks < 1 || n_attacks > kMaxLoopAttacks) return 0;
     Carver c(nullptr, 0);
@@ -1984,6 +1995,7 @@ extern "C" size_t aware_embed_loop_attack_workspace_bytes_ex(const aware_batch* 
     aware_embed e;
     carve_loop_attacks(c, b, e.la);
     if (has_kind(attacks, n_attacks, AWARE_LOOP_REVERBERATION)) carve_loop_reverb(c, b, e.la);
+    else if (has_kind(attacks, n_attacks, AWARE_LOOP_PHASE_VOCODER)) carve_loop_pv(c, b, e.la);
     else if (has_kind(attacks, n_attacks, AWARE_LOOP_TIME_STRETCH))
         carve_loop_stretch(c, b, e.la, has_kind(attacks, n_attacks, AWARE_LOOP_SPEED_CHANGE));
     else if (has_kind(attacks, n_attacks, AWARE_LOOP_SPEED_CHANGE) || has_kind(attacks, n_attacks, AWARE_LOOP_PITCH_SHIFT))
@@ -1994,14 +2006,15 @@ static int set_loop_attacks(aware_embed* e, const aware_loop_attack_ex* attacks,
                             const uint32_t* seeds, void* workspace, size_t workspace_bytes, void* stream) {
     static_assert(AWARE_LOOP_GAUSSIAN_NOISE == kLoopGaussianNoise && AWARE_LOOP_SAMPLE_SUPPRESSION == kLoopSampleSuppression &&
                   AWARE_LOOP_REVERBERATION == kLoopReverberation && AWARE_LOOP_SPEED_CHANGE == kLoopSpeedChange &&
-                  AWARE_LOOP_TIME_STRETCH == kLoopTimeStretch && AWARE_LOOP_PITCH_SHIFT == kLoopPitchShift, "");
+                  AWARE_LOOP_TIME_STRETCH == kLoopTimeStretch && AWARE_LOOP_PITCH_SHIFT == kLoopPitchShift &&
+                  AWARE_LOOP_PHASE_VOCODER == kLoopPhaseVocoder, "");
     if (!e || n_attacks < 0 || n_attacks > kMaxLoopAttacks) return AWARE_E_BADARG;
     if (e->gexec || e->la.locked) return AWARE_E_BADARG;          // before the first aware_embed_iterate, as aware_embed_set_optimizer
-    if (n_attacks == 0) { e->la.n = 0; e->la.z = nullptr; e->la.rv = -1; e->la.sp = -1; e->la.ts = -1; e->la.ps = -1; e->la.h = nullptr; return AWARE_OK; }
+    if (n_attacks == 0) { e->la.n = 0; e->la.z = nullptr; e->la.rv = -1; e->la.sp = -1; e->la.ts = -1; e->la.ps = -1; e->la.pv = -1; e->la.h = nullptr; return AWARE_OK; }
     if (!attacks || !seeds || !workspace || ((uintptr_t)workspace & 255)) return AWARE_E_BADARG;
     const aware_batch* b = e->b;
     auto la = e->la;
-    la.rv = -1; la.sp = -1; la.ts = -1; la.ps = -1; la.h = nullptr; la.v = nullptr;
+    la.rv = -1; la.sp = -1; la.ts = -1; la.ps = -1; la.pv = -1; la.h = nullptr; la.v = nullptr;
     for (int j = 0; j < n_attacks; ++j) {
         const aware_loop_attack_ex& a = attacks[j];
         if (!(a.prob >= 0.f && a.prob <= 1.f)) return AWARE_E_BADARG;
@@ -2014,32 +2027,43 @@ static int set_loop_attacks(aware_embed* e, const aware_loop_attack_ex* attacks,
             la.k[j] = (int)a.param[0];
         } else if (a.kind == AWARE_LOOP_REVERBERATION && ex) {
             const float lo = a.param[0], hi = a.param[1], drr = a.param[2];
-            if (la.rv >= 0 || la.sp >= 0 || la.ts >= 0 || la.ps >= 0) return AWARE_E_BADARG;     // one reverberation per chain, and no speed change, time stretch or pitch shift beside it
+            if (la.rv >= 0 || la.sp >= 0 || la.ts >= 0 || la.ps >= 0 || la.pv >= 0) return AWARE_E_BADARG;     // one reverberation per chain, and no other kind that splits a chain beside it
             if (!(lo >= 2.f) || !(hi <= (float)kReverbMaxIr) || !(lo <= hi) || lo != floorf(lo) || hi != floorf(hi) ||
                 !std::isfinite(drr))
                 return AWARE_E_BADARG;
             la.rv = j; la.n_lo = (int)lo; la.n_hi = (int)hi; la.gain = pow(10.0, (double)drr / 20.0);
         } else if (a.kind == AWARE_LOOP_SPEED_CHANGE && ex) {
             const float lo = a.param[0], hi = a.param[1];
-            if (la.rv >= 0 || la.sp >= 0 || la.ps >= 0) return AWARE_E_BADARG;     // one speed change per chain, and no reverberation or pitch shift beside it
+            if (la.rv >= 0 || la.sp >= 0 || la.ps >= 0 || la.pv >= 0) return AWARE_E_BADARG;     // one speed change per chain, and no reverberation, pitch shift or phase vocoder beside it
             if (la.ts >= 0 && la.ts != j - 1) return AWARE_E_BADARG; // beside a time stretch: directly behind it
             if (!(lo >= (float)kSpeedMin) || !(hi <= (float)kSpeedMax) || !(lo <= hi) || lo != floorf(lo) || hi != floorf(hi))
                 return AWARE_E_BADARG;
             la.sp = j; la.m_lo = (int)lo; la.m_hi = (int)hi;
         } else if (a.kind == AWARE_LOOP_TIME_STRETCH && ex) {
             const float lo = a.param[0], hi = a.param[1];
-            // one time stretch per chain, no reverberation or pitch shift beside it, and no speed change in front of it
-            if (la.rv >= 0 || la.sp >= 0 || la.ts >= 0 || la.ps >= 0) return AWARE_E_BADARG;
+            // one time stretch per chain, no reverberation, pitch shift or phase vocoder beside it, and no speed change in front of it
+            if (la.rv >= 0 || la.sp >= 0 || la.ts >= 0 || la.ps >= 0 || la.pv >= 0) return AWARE_E_BADARG;
             if (!(lo >= (float)kStretchMin) || !(hi <= (float)kStretchMax) || !(lo <= hi) || lo != floorf(lo) || hi != floorf(hi))
                 return AWARE_E_BADARG;
             la.ts = j; la.q_lo = (int)lo; la.q_hi = (int)hi;
         } else if (a.kind == AWARE_LOOP_PITCH_SHIFT && ex) {
             const float lo = a.param[0], hi = a.param[1];
-            // one pitch shift per chain, and none of the three other kinds that split a chain beside it
-            if (la.rv >= 0 || la.sp >= 0 || la.ts >= 0 || la.ps >= 0) return AWARE_E_BADARG;
+            // one pitch shift per chain, and none of the other kinds that split a chain beside it
+            if (la.rv >= 0 || la.sp >= 0 || la.ts >= 0 || la.ps >= 0 || la.pv >= 0) return AWARE_E_BADARG;
             if (!(lo >= (float)kSpeedMin) || !(hi <= (float)kSpeedMax) || !(lo <= hi) || lo != floorf(lo) || hi != floorf(hi))
                 return AWARE_E_BADARG;
             la.ps = j; la.p_lo = (int)lo; la.p_hi = (int)hi;
+        } else if (a.kind == AWARE_LOOP_PHASE_VOCODER && ex) {
+            // one phase vocoder per chain, and none of the other kinds that split a chain beside it; param = {mq_lo, mq_hi,
+            // m_lo, m_hi}, a mode with lo > hi is absent, and one of the two is there
+            if (la.rv >= 0 || la.sp >= 0 || la.ts >= 0 || la.ps >= 0 || la.pv >= 0) return AWARE_E_BADARG;
+            for (int i = 0; i < 4; ++i)
+                if (!(fabsf(a.param[i]) <= 65536.f) || a.param[i] != floorf(a.param[i])) return AWARE_E_BADARG;
+            const int ql = (int)a.param[0], qh = (int)a.param[1], ml = (int)a.param[2], mh = (int)a.param[3];
+            if (ql > qh && ml > mh) return AWARE_E_BADARG;
+            if (ql <= qh && (ql < kStretchMin || qh > kStretchMax)) return AWARE_E_BADARG;
+            if (ml <= mh && (ml < kSpeedMin || mh > kSpeedMax)) return AWARE_E_BADARG;
+            la.pv = j; la.pq_lo = ql; la.pq_hi = qh; la.pm_lo = ml; la.pm_hi = mh;
         } else {
             return AWARE_E_BADARG;
         }
@@ -2050,6 +2074,7 @@ static int set_loop_attacks(aware_embed* e, const aware_loop_attack_ex* attacks,
     Carver c(workspace, workspace_bytes);
     carve_loop_attacks(c, b, la);
     if (la.rv >= 0) carve_loop_reverb(c, b, la);
+    else if (la.pv >= 0) carve_loop_pv(c, b, la);
     else if (la.ts >= 0) carve_loop_stretch(c, b, la, la.sp >= 0);
     else if (la.sp >= 0 || la.ps >= 0) carve_loop_speed(c, b, la);
     if (!c.ok) return AWARE_E_WORKSPACE;
@@ -2169,6 +2194,25 @@ extern "C" int aware_pitch_shift_ola(const float* in, const int* in_off, const i
     return AWARE_OK;
 }
 
+// ---- the phase vocoder's two kernels alone on a ragged spectrum (EXTENSION; runtime.pv_frames, runtime.pv_stretch, tests) -----
+extern "C" int aware_pv_frames(const void* spec, const int* frame_off, int B, const int* mq, void* out, void* stream) {
+    if (!spec || !frame_off || !mq || !out || spec == out || B < 1 || B > 65535) return AWARE_E_BADARG;
+    PvLaunch L;
+    L.spec = spec; L.out = out; L.frame_off = frame_off; L.B = B; L.mq = mq;
+    launch_pv_frames(L, 0, (hipStream_t)stream);
+    LAUNCHCHK();
+    return AWARE_OK;
+}
+extern "C" int aware_pv_frames_bwd(const void* spec, const void* grad_out, const int* frame_off, int B, const int* mq,
+                                   void* grad_spec, void* stream) {
+    if (!spec || !grad_out || !frame_off || !mq || !grad_spec || grad_out == grad_spec || B < 1 || B > 65535) return AWARE_E_BADARG;
+    PvLaunch L;
+    L.spec = spec; L.grad = grad_out; L.out = grad_spec; L.frame_off = frame_off; L.B = B; L.mq = mq;
+    launch_pv_frames(L, 1, (hipStream_t)stream);
+    LAUNCHCHK();
+    return AWARE_OK;
+}
+
 extern "C" void aware_embed_destroy(aware_embed* e) {
     if (!e) return;
 
@@ -2266,6 +2310,67 @@ static PitchLaunch pitch_launch(const aware_embed* e, const float* in, float* ou
     return S;
 }
 
+// the phase vocoder's stage (kind 6).  Forward: STFT of u, the frames, iSTFT into `tmp`, u itself for the clips the entry leaves
+// alone, the resampling of tmp into z.  The transforms are what aware_stft / aware_istft launch, on the loop's signal layout.
+static PvLaunch pv_launch(const aware_embed* e, int step_back) {
+    const auto& la = e->la;
+    PvLaunch P;
+    P.frame_off = e->b->d_frame_off; P.B = e->b->B; P.pstride = e->b->pstride; P.run_blocks = e->b->synth_run;
+    P.step = e->step; P.step_back = step_back; P.seeds = la.seeds; P.entry = la.pv; P.prob = la.prob[la.pv];
+    P.q_lo = la.pq_lo; P.q_hi = la.pq_hi; P.m_lo = la.pm_lo; P.m_hi = la.pm_hi;
+    return P;
+}
+static SpeedLaunch pv_speed_launch(const aware_embed* e, const float* in, float* out, int adjoint, int step_back) {
+    const auto& la = e->la;
+    SpeedLaunch S;
+    S.in = in; S.out = out; S.B = e->b->B; S.adjoint = adjoint; S.frame_off = e->b->d_frame_off; S.pstride = e->b->pstride;
+    S.run_blocks = e->b->synth_run; S.step = e->step; S.step_back = step_back; S.seeds = la.seeds; S.entry = la.pv;
+    S.prob = la.prob[la.pv];
+    const bool has_m = la.pm_lo <= la.pm_hi;
+    S.m_lo = has_m ? la.pm_lo : 0; S.m_hi = has_m ? la.pm_hi : 0;      // stretch mode alone: m = 0, the identity
+    S.coin = has_m && la.pq_lo <= la.pq_hi;
+    return S;
+}
+static void pv_stage_forward(const aware_embed* e, float* tmp, hipStream_t st) {
+    const aware_batch* b = e->b;
+    const auto& la = e->la;
+    AnalysisLaunch L;
+    L.plan = e->plan->dev; L.frame_off = b->d_frame_off; L.B = b->B; L.max_frames = b->max_frames; L.run_frames = b->an_run; L.wg_tab = b->d_an_wg; L.n_wg = b->n_an_wg;
+    L.sig = la.u; L.sig_off = b->d_out_off; L.sig_len = b->d_out_len; L.pcount = b->d_pc_syn; L.pstride = b->pstride;
+    L.full = la.pvS;
+    launch_analysis(L, st);
+    PvLaunch P = pv_launch(e, 0);
+    P.spec = la.pvS; P.out = la.pvY;
+    launch_pv_frames(P, 0, st);
+    SynthLaunch S;
+    S.plan = e->plan->dev; S.frame_off = b->d_frame_off; S.B = b->B; S.max_frames = b->max_frames; S.run_blocks = b->synth_run; S.wg_tab = b->d_syn_wg; S.n_wg = b->n_syn_wg;
+    S.full = la.pvY; S.out = tmp; S.pstride = b->pstride;
+    launch_synth(S, st);
+    launch_pv_idle(P, la.u, tmp, st);
+    launch_speed_change(pv_speed_launch(e, tmp, la.z, 0, 0), st);
+}
+// The mirror: gz in u -> the resampling's adjoint into gy, the iSTFT's adjoint into the Y buffer, the frames' backward into the
+// S buffer, the STFT's adjoint into gy, and gz itself for the clips the entry left alone
+static void pv_stage_backward(const aware_embed* e, int step_back, hipStream_t st) {
+    const aware_batch* b = e->b;
+    const auto& la = e->la;
+    launch_speed_change(pv_speed_launch(e, la.u, e->gy, 1, step_back), st);
+    AnalysisLaunch L;
+    L.plan = e->plan->dev; L.frame_off = b->d_frame_off; L.B = b->B; L.max_frames = b->max_frames; L.run_frames = b->an_run; L.wg_tab = b->d_an_wg; L.n_wg = b->n_an_wg;
+    L.sig = e->gy; L.sig_off = b->d_out_off; L.sig_len = b->d_out_len; L.pcount = b->d_pc_syn; L.pstride = b->pstride;
+    L.full = la.pvY; L.adjoint = 1;
+    launch_analysis(L, st);
+    PvLaunch P = pv_launch(e, step_back);
+    P.spec = la.pvS; P.grad = la.pvY; P.out = la.pvS;
+    launch_pv_frames(P, 1, st);
+    SynthLaunch S;
+    S.plan = e->plan->dev; S.frame_off = b->d_frame_off; S.B = b->B; S.max_frames = b->max_frames; S.run_blocks = b->synth_run; S.wg_tab = b->d_syn_wg; S.n_wg = b->n_syn_wg;
+    S.full = la.pvS; S.out = e->gy; S.adjoint = 1; S.pstride = b->pstride;
+    S.sig_off = b->d_out_off; S.sig_len = b->d_out_len;
+    launch_synth(S, st);
+    launch_pv_idle(P, la.u, e->gy, st);
+}
+
 static ConvolveLaunch reverb_launch(const aware_embed* e, const float* in, float* out, int adjoint) {
     const auto& la = e->la;
     ConvolveLaunch C;
@@ -2305,7 +2410,7 @@ static int embed_iteration(aware_embed* e, hipStream_t st, int do_step, float* g
         A.step = e->step; A.seeds = la.seeds; A.n = la.n;
         for (int j = 0; j < la.n; ++j) { A.kind[j] = la.kind[j]; A.k[j] = la.k[j]; A.inv_snr[j] = la.inv_snr[j]; A.prob[j] = la.prob[j]; }
         A.yraw = e->yraw; A.pmaxY = e->pmaxY; A.psq = la.psq; A.z = la.z; A.pmaxZ = la.pmaxZ;
-        if (la.rv >= 0 || la.sp >= 0 || la.ts >= 0 || la.ps >= 0) { A.idle_plain = 1; A.gpad_out = la.gpad0; }
+        if (la.rv >= 0 || la.sp >= 0 || la.ts >= 0 || la.ps >= 0 || la.pv >= 0) { A.idle_plain = 1; A.gpad_out = la.gpad0; }
         if (la.ts >= 0) {
             // the entries in front of the stretch on N(N(yraw)), the overlap-add (and the resampling of a speed change
             // directly behind it), the entries behind
@@ -2325,6 +2430,12 @@ static int embed_iteration(aware_embed* e, hipStream_t st, int do_step, float* g
             launch_loop_attack_stage(A, 0, la.ps, e->yraw, 1, la.u, nullptr, st);
             launch_pitch_shift(pitch_launch(e, la.u, la.z, 0, 0), st);
             launch_loop_attack_stage(A, la.ps + 1, la.n, la.z, 0, la.z, la.pmaxZ, st);
+        } else if (la.pv >= 0) {
+            // the same shape again: the entries in front of the phase vocoder on N(N(yraw)), its stage (gy is free until the
+            // synthesis adjoint writes it, and carries the vocoded signal to the resampling), the entries behind it
+            launch_loop_attack_stage(A, 0, la.pv, e->yraw, 1, la.u, nullptr, st);
+            pv_stage_forward(e, e->gy, st);
+            launch_loop_attack_stage(A, la.pv + 1, la.n, la.z, 0, la.z, la.pmaxZ, st);
         } else if (la.rv < 0) {
             launch_loop_attack_forward(A, st);
         } else {
@@ -2401,6 +2512,13 @@ static int embed_iteration(aware_embed* e, hipStream_t st, int do_step, float* g
             A.gy_out = nullptr;
             launch_pitch_shift(pitch_launch(e, e->la.u, e->gy, 1, A.step_back), st);
             launch_loop_attack_stage_bwd(A, 0, e->la.ps, 0, 1, st);
+        } else if (e->la.pv >= 0) {
+            // the mirror: into u, the stage's backward into gy, the stage in front
+            A.gy_out = e->la.u;
+            launch_loop_attack_stage_bwd(A, e->la.pv + 1, e->la.n, 1, 0, st);
+            A.gy_out = nullptr;
+            pv_stage_backward(e, A.step_back, st);
+            launch_loop_attack_stage_bwd(A, 0, e->la.pv, 0, 1, st);
         } else if (e->la.rv < 0) {
             launch_loop_attack_backward(A, st);
         } else {

@@ -357,7 +357,7 @@ void launch_stoi(const StoiLaunch& L, hipStream_t st);
 // its analysis, drawn afresh at every optimiser step (aware_embed_set_loop_attacks) --------------------------------------
 constexpr int kMaxLoopAttacks = 4;
 constexpr int kLoopGaussianNoise = 0, kLoopSampleSuppression = 1, kLoopReverberation = 2, kLoopSpeedChange = 3, kLoopTimeStretch = 4,
-              kLoopPitchShift = 5;      // AWARE_LOOP_* of aware_hip.h
+              kLoopPitchShift = 5, kLoopPhaseVocoder = 6;      // AWARE_LOOP_* of aware_hip.h
 struct LoopAttackLaunch {
     const int* frame_off = nullptr;
     const int* pcount = nullptr;          // [B] synthesis runs per clip: the partials' layout
@@ -445,6 +445,7 @@ struct SpeedLaunch {
     const unsigned* seeds = nullptr;      // [B]
     int entry = 0, m_lo = 0, m_hi = 0;
     float prob = 0.f;
+    int coin = 0;                         // 1: behind a phase vocoder with both modes, m = 0 where the draw's r[2] < 2^31 (stretch mode)
     // or a ragged batch (frame_off null): x is x_len[b] floats at x_off[b], z is z_len[b] floats at z_off[b], m[b] given
     const int* x_off = nullptr; const int* x_len = nullptr;
     const int* z_off = nullptr; const int* z_len = nullptr;
@@ -499,5 +500,29 @@ struct PitchLaunch {
     const int* m = nullptr;               // [B]
 };
 void launch_pitch_shift(const PitchLaunch& L, hipStream_t st);
+
+// ---- loop_pv_kernels.hip: phase vocoder on the frames of a spectrum (EXTENSION): magnitudes interpolated at the rate
+// Q / 65536, phases accumulated as a product of unit phasors, inside the embed loop (chain kind 6, between the staged STFT and
+// iSTFT) and stand-alone (aware_pv_frames, aware_pv_frames_bwd) -------------------------------------------------------------
+struct PvLaunch {
+    const void* spec = nullptr;           // S [NF][520] complex
+    const void* grad = nullptr;           // backward: G = dL/dY [NF][520]; never `out`
+    void* out = nullptr;                  // forward: Y; backward: gS (may be `spec`)
+    const int* frame_off = nullptr;       // [B + 1]
+    int B = 0;
+    // the embed loop (seeds non-null): the mode and the offset drawn in the kernel; a clip that the entry leaves alone is skipped
+    int pstride = 0, run_blocks = 0;
+    const int* step = nullptr; int step_back = 0;
+    const unsigned* seeds = nullptr;      // [B]
+    int entry = 0;
+    int q_lo = 0, q_hi = -1;              // stretch offsets, inside kStretchMin .. kStretchMax; lo > hi: no stretch mode
+    int m_lo = 0, m_hi = -1;              // speed offsets, inside kSpeedMin .. kSpeedMax; lo > hi: no pitch mode
+    float prob = 0.f;
+    // or stand-alone (seeds null): mq[b] given, outside kStretchMin .. kStretchMax read as 0 (the identity)
+    const int* mq = nullptr;              // [B]
+};
+void launch_pv_frames(const PvLaunch& L, int backward, hipStream_t st);
+// the loop's clips that the entry leaves alone at this step: dst = src (the embed loop's signal layout)
+void launch_pv_idle(const PvLaunch& L, const float* src, float* dst, hipStream_t st);
 
 }  // namespace aware

@@ -3,7 +3,8 @@
 // restatement is aware_amd/embedding/loop_attacks.py::speed_change / apply_chain.
 //
 //   r = philox4x32_10((0, s, 1 + j, 1), (seed_b, 0x5EED)),  on = (r0 + 0.5) / 2^32 < prob,
-//   m = m_lo + ((r3 * (m_hi - m_lo + 1)) >> 32),  R = 65536 + m          (m = 0 where the entry does not fire)
+//   m = m_lo + ((r3 * (m_hi - m_lo + 1)) >> 32),  R = 65536 + m          (m = 0 where the entry does not fire, and behind a
+//   phase vocoder that drew its stretch mode: `coin`)
 //   p_i = i R (64-bit, 16.16 fixed point),  i0 = p_i >> 16,  f = (p_i & 0xFFFF) / 65536   (exact in f32)
 //   forward   z[i] = w_-1(f) x[i0 - 1] + w_0(f) x[i0] + w_1(f) x[i0 + 1] + w_2(f) x[i0 + 2],  x zero outside [0, n),
 //             z[i] = 0 where p_i > (n - 1) << 16
@@ -88,6 +89,7 @@ __global__ __launch_bounds__(kSpThreads) void speed_kernel(SpeedLaunch a) {
         philox4x32_10(0u, step, 1u + (unsigned)a.entry, 1u, a.seeds[b], 0x5EEDu, r);
         const bool on = ((double)r[0] + 0.5) * 2.3283064365386963e-10 < (double)a.prob;
         m = on ? a.m_lo + (int)(((unsigned long long)r[3] * (unsigned long long)(unsigned)(a.m_hi - a.m_lo + 1)) >> 32) : 0;
+        if (a.coin && r[2] < 0x80000000u) m = 0;          // behind a phase vocoder in stretch mode: the identity
     } else {
         nx = a.x_len[b]; nz = a.z_len[b];
         x = a.in + (a.adjoint ? a.z_off[b] : a.x_off[b]);

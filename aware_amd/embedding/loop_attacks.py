@@ -48,6 +48,25 @@ the loop's new stage.  For clip b (length Ny) at optimiser step s with seed_b:
         the pair above leaves most steps.  Linear in x; m = 0 is the identity; m is detached.  At most one per chain, and not in
         a chain with a reverberation, a speed change or a time stretch.
 
+      phase_vocoder(rate = r or [lo, hi], cents = c or [lo, hi]; at least one of the two; rate parsed and refused exactly as
+        time_stretch's, cents exactly as speed_change's): with both keys the mode is stretch where r[2] < 2^31, else pitch; with
+        one key it is that key's mode.  Stretch mode: mq = stretch_offset(r[3], *stretch_range), m = 0.  Pitch mode:
+        m = speed_offset(r[3], *speed_range), mq = pitch_offsets(m)[1] - 65536 (the coupled rate of pitch_shift, inside the
+        stretch's range for +-400 cents).  Q = 65536 + mq.  on: x = speed_change(pv_stretch(x, mq), m), both Ny long.
+        pv_stretch(x, mq): S = STFT(x) on the loop's geometry (reflect-centred, periodic Hann 1024, hop 256, T = Ny / 256 + 1
+        frames); for t = 0 .. T - 1: p = t Q in int64, i = p >> 16, al = (p & 0xFFFF) / 65536 (exact in float32, so host and
+        device agree on every index and weight); Y[t] = 0 where i >= T, otherwise Y[t] = ((1 - al) |S[i]| + al |S[i + 1]|) P[t]
+        with S[T] := 0; P[0] = u(S[0]), P[t + 1] = P[t] u(S[i + 1]) conj(u(S[i])); u(c) = c / |c|, and u(c) = 1 for a zero cell:
+        one whose real and imaginary parts both compare equal to 0; x' = iSTFT(Y), the loop's iSTFT: T frames give Ny samples.
+        mq = 0 and m = 0 returns x; a faster clip ends in zeros, a slower one is truncated.  P is the textbook accumulator in
+        product form: acc += adv + princarg(dtheta - adv) is acc += dtheta modulo 2 pi when the two hops are equal, so it is the
+        phase of oracle.phase_vocoder without an atan2 and without sensitivity to where the wrap falls.  P, Q and m are
+        detached (no phase gradients) and d|c|/dc is torch's, 0 at 0, so the backward pass of pv_stretch is: the iSTFT adjoint,
+        gm[t] = Re(conj(P[t]) G[t]), the transpose of the two-tap interpolation onto the input frames over ascending t,
+        gS[i] = gmag[i] u(S[i]) (0 at a zero cell), the STFT adjoint.  At most one per chain, and not in a chain with a
+        reverberation, a speed change, a time stretch or a pitch shift, in either order; element-wise entries may stand in front
+        of it and behind it, and a noise entry behind it takes its sigma from the vocoded signal.
+
 In the loop x = N(N(y)) of the raw synthesis y, N(v) = v / (max|v| + 1e-8), and the analysis (N, N, STFT, band magnitudes)
 runs on the chain's output."""
 from __future__ import annotations
@@ -59,10 +78,10 @@ import torch
 
 MAX_ATTACKS = 4
 KINDS = {"gaussian_noise": 0, "sample_suppression": 1, "reverberation": 2, "speed_change": 3, "time_stretch": 4,
-         "pitch_shift": 5}      # AWARE_LOOP_* of include/aware_hip.h
+         "pitch_shift": 5, "phase_vocoder": 6}      # AWARE_LOOP_* of include/aware_hip.h
 _KEYS = {"gaussian_noise": {"kind", "snr_db", "prob"}, "sample_suppression": {"kind", "seconds", "prob"},
          "reverberation": {"kind", "rt60", "drr_db", "prob"}, "speed_change": {"kind", "cents", "prob"}, "time_stretch": {"kind", "rate", "prob"},
-         "pitch_shift": {"kind", "cents", "prob"}}
+         "pitch_shift": {"kind", "cents", "prob"}, "phase_vocoder": {"kind", "rate", "cents", "prob"}}
 _KEY1 = 0x5EED
 MAX_IR = 8192                   # taps of the longest impulse response
 _IR_WORD = 8                    # third Philox counter word of the impulse responses (0: noise, 1..4: entry draws)
@@ -74,6 +93,39 @@ STRETCH_HOP, STRETCH_WIN = 256, 1024            # the overlap-add's hop and wind
 def _no_pitch_shift(j: int, kind: str, out: list[dict]) -> None:
     if any(o["kind"] == "pitch_shift" for o in out):
         raise ValueError(f"loop_attacks[{j}] ({kind}): a chain holds a pitch shift or a {kind.replace('_', ' ')}, not both")
+
+
+def _no_phase_vocoder(j: int, kind: str, out: list[dict]) -> None:
+    if any(o["kind"] == "phase_vocoder" for o in out):
+        raise ValueError(f"loop_attacks[{j}] ({kind}): a chain holds a phase vocoder or a {kind.replace('_', ' ')}, not both")
+
+
+def _parse_rate(j: int, kind: str, a: dict) -> list[float]:
+    """[lo, hi] of a time_stretch or phase_vocoder entry's rate: a scalar r > 1 means [1 / r, r]; 0.75 <= lo <= hi <= 4/3, and
+    at least one offset inside."""
+    if "rate" not in a:
+        raise ValueError(f"loop_attacks[{j}] ({kind}): rate is required")
+    rr = a["rate"]
+    try:
+        if isinstance(rr, (list, tuple)):
+            if len(rr) != 2:
+                raise TypeError
+            lo, hi = float(rr[0]), float(rr[1])
+        else:
+            hi = float(rr)
+            if not hi > 1.0:
+                raise ValueError(f"loop_attacks[{j}] ({kind}): a scalar rate has to be > 1; got {rr!r}")
+            lo = 1.0 / hi
+    except TypeError:
+        raise ValueError(f"loop_attacks[{j}] ({kind}): rate = {rr!r} is neither a number nor [lo, hi]") from None
+    if not (math.isfinite(lo) and math.isfinite(hi) and MIN_RATE <= lo <= hi <= MAX_RATE):
+        raise ValueError(f"loop_attacks[{j}] ({kind}): rate needs {MIN_RATE:g} <= lo <= hi <= 4/3, both finite; "
+                         f"got {rr!r}")
+    m_lo, m_hi = stretch_range({"rate": [lo, hi]})
+    if m_lo > m_hi:
+        raise ValueError(f"loop_attacks[{j}] ({kind}): rate = {rr!r} holds no offset "
+                         f"(m_lo = {m_lo} > m_hi = {m_hi}, in units of 1 / 65536)")
+    return [lo, hi]
 
 
 def _parse_cents(j: int, kind: str, a: dict) -> list[float]:
@@ -114,7 +166,9 @@ def parse_chain(chain) -> list[dict]:
     [0.9, 1.1]}: a missing rate, a scalar <= 1, rate not 0.75 <= lo <= hi <= 4/3 (finite), a range that holds no offset, a
     second stretch, a stretch in a chain with a reverberation, a speed change anywhere but directly behind the stretch; for {"kind": "pitch_shift",
     "cents": 100.0 | [-50.0, 120.0]}: what a speed change's cents are refused for, a second pitch shift, a pitch shift in a
-    chain with a reverberation, a speed change or a time stretch."""
+    chain with a reverberation, a speed change or a time stretch; for {"kind": "phase_vocoder", "rate": 1.15 | [0.85, 1.15],
+    "cents": 150.0 | [-50.0, 120.0]}: neither key, what a time stretch's rate or a speed change's cents are refused for, a second
+    phase vocoder, a phase vocoder in a chain with a reverberation, a speed change, a time stretch or a pitch shift."""
     if not chain:
         return []
     if isinstance(chain, dict) or not isinstance(chain, (list, tuple)):
@@ -142,6 +196,7 @@ def parse_chain(chain) -> list[dict]:
             if any(o["kind"] == "reverberation" for o in out):
                 raise ValueError(f"loop_attacks[{j}] (reverberation): at most one reverberation per chain")
             _no_pitch_shift(j, kind, out)
+            _no_phase_vocoder(j, kind, out)
             if any(o["kind"] == "speed_change" for o in out):
                 raise ValueError(f"loop_attacks[{j}] (reverberation): a chain holds a speed change or a reverberation, not both")
             if any(o["kind"] == "time_stretch" for o in out):
@@ -163,6 +218,7 @@ def parse_chain(chain) -> list[dict]:
             if any(o["kind"] == "speed_change" for o in out):
                 raise ValueError(f"loop_attacks[{j}] (speed_change): at most one speed change per chain")
             _no_pitch_shift(j, kind, out)
+            _no_phase_vocoder(j, kind, out)
             if any(o["kind"] == "reverberation" for o in out):
                 raise ValueError(f"loop_attacks[{j}] (speed_change): a chain holds a speed change or a reverberation, not both")
             if any(o["kind"] == "time_stretch" for o in out) and out[-1]["kind"] != "time_stretch":
@@ -172,40 +228,32 @@ def parse_chain(chain) -> list[dict]:
             if any(o["kind"] == "time_stretch" for o in out):
                 raise ValueError(f"loop_attacks[{j}] (time_stretch): at most one time stretch per chain")
             _no_pitch_shift(j, kind, out)
+            _no_phase_vocoder(j, kind, out)
             if any(o["kind"] == "reverberation" for o in out):
                 raise ValueError(f"loop_attacks[{j}] (time_stretch): a chain holds a time stretch or a reverberation, not both")
             if any(o["kind"] == "speed_change" for o in out):
                 raise ValueError(f"loop_attacks[{j}] (time_stretch): a speed change in the same chain follows the stretch directly")
-            if "rate" not in a:
-                raise ValueError(f"loop_attacks[{j}] (time_stretch): rate is required")
-            rr = a["rate"]
-            try:
-                if isinstance(rr, (list, tuple)):
-                    if len(rr) != 2:
-                        raise TypeError
-                    lo, hi = float(rr[0]), float(rr[1])
-                else:
-                    hi = float(rr)
-                    if not hi > 1.0:
-                        raise ValueError(f"loop_attacks[{j}] (time_stretch): a scalar rate has to be > 1; got {rr!r}")
-                    lo = 1.0 / hi
-            except TypeError:
-                raise ValueError(f"loop_attacks[{j}] (time_stretch): rate = {rr!r} is neither a number nor [lo, hi]") from None
-            if not (math.isfinite(lo) and math.isfinite(hi) and MIN_RATE <= lo <= hi <= MAX_RATE):
-                raise ValueError(f"loop_attacks[{j}] (time_stretch): rate needs {MIN_RATE:g} <= lo <= hi <= 4/3, both finite; "
-                                 f"got {rr!r}")
-            e["rate"] = [lo, hi]
-            m_lo, m_hi = stretch_range(e)
-            if m_lo > m_hi:
-                raise ValueError(f"loop_attacks[{j}] (time_stretch): rate = {rr!r} holds no offset "
-                                 f"(m_lo = {m_lo} > m_hi = {m_hi}, in units of 1 / 65536)")
+            e["rate"] = _parse_rate(j, kind, a)
         elif kind == "pitch_shift":
             if any(o["kind"] == "pitch_shift" for o in out):
                 raise ValueError(f"loop_attacks[{j}] (pitch_shift): at most one pitch shift per chain")
             for other in ("reverberation", "speed_change", "time_stretch"):
                 if any(o["kind"] == other for o in out):
                     raise ValueError(f"loop_attacks[{j}] (pitch_shift): a chain holds a pitch shift or a {other.replace('_', ' ')}, not both")
+            _no_phase_vocoder(j, kind, out)
             e["cents"] = _parse_cents(j, kind, a)
+        elif kind == "phase_vocoder":
+            if any(o["kind"] == "phase_vocoder" for o in out):
+                raise ValueError(f"loop_attacks[{j}] (phase_vocoder): at most one phase vocoder per chain")
+            for other in ("reverberation", "speed_change", "time_stretch", "pitch_shift"):
+                if any(o["kind"] == other for o in out):
+                    raise ValueError(f"loop_attacks[{j}] (phase_vocoder): a chain holds a phase vocoder or a {other.replace('_', ' ')}, not both")
+            if "rate" not in a and "cents" not in a:
+                raise ValueError(f"loop_attacks[{j}] (phase_vocoder): at least one of rate and cents is required")
+            if "rate" in a:
+                e["rate"] = _parse_rate(j, kind, a)
+            if "cents" in a:
+                e["cents"] = _parse_cents(j, kind, a)
         else:
             if "seconds" not in a or not math.isfinite(float(a["seconds"])) or float(a["seconds"]) <= 0.0:
                 raise ValueError(f"loop_attacks[{j}] (sample_suppression): seconds > 0 is required")
@@ -416,6 +464,83 @@ def pitch_shift(x: torch.Tensor, m: int, n_out: int | None = None) -> torch.Tens
     return speed_change(time_stretch(x, mq, stretch_length(n, mq)), m, n_out)
 
 
+def pv_draw(entry: dict, r) -> tuple[int, int]:
+    """(mq, m) of a parsed phase_vocoder entry from its draw r = entry_draw(seed, step, j): stretch mode (m = 0) with rate alone,
+    or with both keys where r[2] < 2^31; pitch mode otherwise, with the coupled stretch offset mq = pitch_offsets(m)[1] - 65536."""
+    if "rate" in entry and ("cents" not in entry or int(r[2]) < (1 << 31)):
+        return stretch_offset(r[3], *stretch_range(entry)), 0
+    m = speed_offset(r[3], *speed_range(entry))
+    return pitch_offsets(m)[1] - 65536, m
+
+
+def pv_positions(T: int, mq: int):
+    """(i, al, live) of the T output frames at Q = 65536 + mq: p = t Q in int64, i = p >> 16, al = (p & 0xFFFF) / 65536 in
+    float64 (exact in float32 too), live = i < T."""
+    p = np.arange(int(T), dtype=np.int64) * np.int64(65536 + int(mq))
+    i = p >> 16
+    return i, (p & 0xFFFF).astype(np.float64) / 65536.0, i < int(T)
+
+
+def _pv_unit(S: torch.Tensor) -> torch.Tensor:
+    """u(c) = c / |c|, and 1 for a zero cell: both parts compare equal to 0.  Detached."""
+    S = S.detach()
+    zero = (S.real == 0) & (S.imag == 0)
+    return torch.where(zero, torch.ones_like(S), S / torch.where(zero, torch.ones_like(S.real), S.abs()))
+
+
+def pv_frames(S: torch.Tensor, mq: int) -> torch.Tensor:
+    """The phase vocoder on the frames of a spectrum S [T, F] complex (frame-major, as the device holds it) at the rate
+    Q / 65536, Q = 65536 + mq: Y[t] = ((1 - al) |S[i]| + al |S[i + 1]|) P[t], S[T] := 0, Y[t] = 0 where i >= T;
+    P[0] = u(S[0]), P[t + 1] = P[t] u(S[i + 1]) conj(u(S[i])).  Differentiable through the magnitudes only (P is detached);
+    mq = 0 returns S."""
+    mq = int(mq)
+    if mq == 0:
+        return S
+    T = S.shape[0]
+    i, al, live = pv_positions(T, mq)
+    Sp = torch.cat([S, torch.zeros((2,) + tuple(S.shape[1:]), dtype=S.dtype, device=S.device)])
+    U = _pv_unit(Sp)
+    ic = np.where(live, i, T)                                         # a dead frame reads the zero rows: magnitude 0, step 1
+    i0, i1 = torch.as_tensor(ic, device=S.device), torch.as_tensor(ic + 1, device=S.device)
+    step = U[i1] * U[i0].conj()                                       # [T, F]
+    P = torch.cat([U[:1], step[:-1]]).cumprod(0)                      # P[t] = u(S[0]) prod_{s < t} step[s]
+    a = torch.as_tensor(al, device=S.device).to(S.real.dtype).reshape((-1,) + (1,) * (S.dim() - 1))
+    mag = Sp.abs()
+    out = ((1 - a) * mag[i0] + a * mag[i1]) * P
+    return out * torch.as_tensor(live, device=S.device).to(S.real.dtype).reshape(a.shape)
+
+
+def _loop_stft(x: torch.Tensor) -> torch.Tensor:
+    """The loop's STFT of x [n]: reflect-centred, periodic Hann 1024, hop 256; [n // 256 + 1, 513] complex, frame-major."""
+    w = torch.hann_window(STRETCH_WIN, dtype=x.dtype, device=x.device)
+    xp = torch.nn.functional.pad(x.reshape(1, 1, -1), (STRETCH_WIN // 2, STRETCH_WIN // 2), mode="reflect").reshape(-1)
+    return torch.fft.rfft(xp.unfold(-1, STRETCH_WIN, STRETCH_HOP) * w, dim=-1)
+
+
+def _loop_istft(Y: torch.Tensor) -> torch.Tensor:
+    """The loop's iSTFT of Y [T, 513]: irfft, window, overlap-add, / the squared windows' overlap-add, trimmed to 256 (T - 1)."""
+    T = Y.shape[0]
+    w = torch.hann_window(STRETCH_WIN, dtype=Y.real.dtype, device=Y.device)
+    frames = torch.fft.irfft(Y, n=STRETCH_WIN, dim=-1) * w
+    L = STRETCH_WIN + STRETCH_HOP * (T - 1)
+    fold = lambda f: torch.nn.functional.fold(f.transpose(0, 1).unsqueeze(0), output_size=(1, L), kernel_size=(1, STRETCH_WIN),
+                                              stride=(1, STRETCH_HOP)).reshape(L)
+    lo, hi = STRETCH_WIN // 2, STRETCH_WIN // 2 + STRETCH_HOP * (T - 1)
+    return fold(frames)[lo:hi] / fold((w * w).expand(T, -1))[lo:hi]
+
+
+def pv_stretch(x: torch.Tensor, mq: int) -> torch.Tensor:
+    """x [n] (n > 512) stretched in time at the rate Q / 65536, Q = 65536 + mq, at its own pitch by the phase vocoder:
+    iSTFT(pv_frames(STFT(x), mq)) on the loop's geometry, n samples long (the iSTFT gives 256 (n // 256) of them, zeros follow;
+    inside the loop n is a multiple of 256).  Differentiable through the magnitudes; mq = 0 returns x."""
+    mq = int(mq)
+    if mq == 0:
+        return x
+    n = x.shape[-1]
+    y = _loop_istft(pv_frames(_loop_stft(x), mq))
+    return y if y.shape[-1] == n else torch.cat([y, torch.zeros(n - y.shape[-1], dtype=y.dtype, device=y.device)])
+
+
 def _convolve(xb: torch.Tensor, h: np.ndarray) -> torch.Tensor:
     """(h * xb)[0 : len(xb)] in xb's dtype through an FFT at least len(xb) + len(h) - 1 long; differentiable in xb."""
     ny, nh = xb.shape[-1], len(h)
@@ -460,6 +585,10 @@ def apply_chain(x, chain, seeds, step: int, sample_rate: int = 16000):
             elif a["kind"] == "pitch_shift":
                 if on:
                     xb = pitch_shift(xb, speed_offset(r[3], *speed_range(a)))
+            elif a["kind"] == "phase_vocoder":
+                mq, m = pv_draw(a, r)
+                if on:
+                    xb = speed_change(pv_stretch(xb, mq), m)
             elif on:
                 power = float(np.mean(xb.detach().double().cpu().numpy() ** 2))
                 sigma = math.sqrt(power / (10.0 ** (a["snr_db"] / 10.0)))
@@ -471,7 +600,8 @@ def apply_chain(x, chain, seeds, step: int, sample_rate: int = 16000):
 
 def device_entries_ex(chain: list[dict], sample_rate: int):
     """(kind, prob, [param0..3]) of the C ABI's aware_loop_attack_ex: kinds 0 and 1 as device_entries in param[0]; a
-    reverberation has param = [n_lo, n_hi, drr_db, 0], a speed change, a time stretch or a pitch shift [m_lo, m_hi, 0, 0]."""
+    reverberation has param = [n_lo, n_hi, drr_db, 0], a speed change, a time stretch or a pitch shift [m_lo, m_hi, 0, 0], a
+    phase vocoder [mq_lo, mq_hi, m_lo, m_hi] with [0, -1] (lo > hi) for an absent mode."""
     out = []
     for a in chain:
         if a["kind"] == "reverberation":
@@ -480,6 +610,10 @@ def device_entries_ex(chain: list[dict], sample_rate: int):
         elif a["kind"] in ("speed_change", "pitch_shift"):
             m_lo, m_hi = speed_range(a)
             out.append((KINDS[a["kind"]], a["prob"], [float(m_lo), float(m_hi), 0.0, 0.0]))
+        elif a["kind"] == "phase_vocoder":
+            q_lo, q_hi = stretch_range(a) if "rate" in a else (0, -1)
+            m_lo, m_hi = speed_range(a) if "cents" in a else (0, -1)
+            out.append((KINDS[a["kind"]], a["prob"], [float(q_lo), float(q_hi), float(m_lo), float(m_hi)]))
         elif a["kind"] == "time_stretch":
             m_lo, m_hi = stretch_range(a)
             out.append((KINDS[a["kind"]], a["prob"], [float(m_lo), float(m_hi), 0.0, 0.0]))

@@ -570,7 +570,7 @@ class EmbedSession:
             raise ValueError(f"set_loop_attacks: {self.batch.B} clips but {len(seeds)} seeds")
         la.check_lengths(chain, sample_rate, self.batch.out_lengths)      # ValueError naming the clip, before any launch
         sd = (C.c_uint32 * self.batch.B)(*[int(s) & 0xFFFFFFFF for s in seeds])
-        if any(a["kind"] in ("reverberation", "speed_change", "time_stretch", "pitch_shift") for a in chain):
+        if any(a["kind"] in ("reverberation", "speed_change", "time_stretch", "pitch_shift", "phase_vocoder") for a in chain):
             # the entry points with four parameters per entry; chains of the two older kinds keep the older call
             ent = la.device_entries_ex(chain, sample_rate)
             arr = (_lib.LoopAttackEx * len(ent))(*[_lib.LoopAttackEx(k, pr, (C.c_float * 4)(*p)) for k, pr, p in ent])
@@ -979,6 +979,63 @@ def pitch_shift_ola(x: Ragged, m, adjoint: bool = False, out_lengths=None) -> Ra
     src, dst = (out, x) if adjoint else (x, out)
     check(lib.aware_pitch_shift_ola(_ptr(xin), _ptr(src.d_off), _ptr(src.d_len), _ptr(out.data), _ptr(dst.d_off), _ptr(dst.d_len),
                                     x.B, max(x.max_len, out.max_len), _ptr(md), int(bool(adjoint)), _stream()), "aware_pitch_shift_ola")
+    return out
+
+
+PV_MQ_MIN, PV_MQ_MAX = -16384, 21845       # the stretch's range: ceil / floor of 65536 (0.75 - 1) and 65536 (4 / 3 - 1)
+
+
+def _pv_args(B: int, frame_offsets, mq, dev, who: str):
+    mqs = [int(mq)] * B if np.isscalar(mq) else [int(v) for v in mq]
+    if len(mqs) != B or any(v < PV_MQ_MIN or v > PV_MQ_MAX for v in mqs):
+        raise ValueError(f"{who}: {B} stretch offsets within {PV_MQ_MIN}..{PV_MQ_MAX} (rates 0.75 to 4/3) are required; got {mqs}")
+    fo = [int(v) for v in frame_offsets]
+    if len(fo) != B + 1 or fo[0] < 0 or any(b <= a for a, b in zip(fo, fo[1:])):
+        raise ValueError(f"{who}: {B + 1} ascending frame offsets are required; got {fo}")
+    return torch.tensor(fo, dtype=torch.int32, device=dev), torch.tensor(mqs, dtype=torch.int32, device=dev), fo
+
+
+def pv_frames(spec: torch.Tensor, frame_offsets, mq) -> torch.Tensor:
+    """embedding.loop_attacks.pv_frames per clip on a ragged spectrum (aware_pv_frames): spec [rows, 520] complex64 as `stft`
+    writes it, clip b's frames at rows frame_offsets[b] .. frame_offsets[b + 1] (B + 1 values; rows outside them are left
+    alone), mq B stretch offsets or one for all.  mq[b] = 0 copies the clip's rows."""
+    B = len(frame_offsets) - 1
+    fo, md, host = _pv_args(B, frame_offsets, mq, spec.device, "pv_frames")
+    if spec.dtype != torch.complex64 or spec.dim() != 2 or spec.shape[1] != FULL_STRIDE or spec.shape[0] < host[-1] or not spec.is_contiguous():
+        raise ValueError(f"pv_frames: a contiguous complex64 spectrum [>= {host[-1]}, {FULL_STRIDE}] is required")
+    out = torch.zeros_like(spec)
+    check(load_library().aware_pv_frames(_ptr(spec), _ptr(fo), B, _ptr(md), _ptr(out), _stream()), "aware_pv_frames")
+    return out
+
+
+def pv_frames_bwd(spec: torch.Tensor, grad_out: torch.Tensor, frame_offsets, mq) -> torch.Tensor:
+    """Backward of `pv_frames` through the magnitudes (aware_pv_frames_bwd; the phases are constants): the gradient with respect
+    to spec from grad_out, the gradient with respect to pv_frames' result; both laid out as spec."""
+    B = len(frame_offsets) - 1
+    fo, md, host = _pv_args(B, frame_offsets, mq, spec.device, "pv_frames_bwd")
+    for t in (spec, grad_out):
+        if t.dtype != torch.complex64 or t.dim() != 2 or t.shape[1] != FULL_STRIDE or t.shape[0] < host[-1] or not t.is_contiguous():
+            raise ValueError(f"pv_frames_bwd: contiguous complex64 spectra [>= {host[-1]}, {FULL_STRIDE}] are required")
+    out = torch.zeros_like(spec)
+    check(load_library().aware_pv_frames_bwd(_ptr(spec), _ptr(grad_out), _ptr(fo), B, _ptr(md), _ptr(out), _stream()),
+          "aware_pv_frames_bwd")
+    return out
+
+
+def pv_stretch(plan: "Plan", x: Ragged, mq) -> Ragged:
+    """Per clip embedding.loop_attacks.pv_stretch at the stretch offsets mq (B integers, or one for all): STFT -> pv_frames ->
+    iSTFT on the card geometry, every clip as long as it was (the iSTFT gives 256 (n // 256) samples, zeros follow; a clip with
+    mq[b] = 0 is returned as it is).  ValueError for an mq outside the stretch's range."""
+    mqs = [int(mq)] * x.B if np.isscalar(mq) else [int(v) for v in mq]
+    if len(mqs) != x.B or any(v < PV_MQ_MIN or v > PV_MQ_MAX for v in mqs):          # before any launch
+        raise ValueError(f"pv_stretch: {x.B} stretch offsets within {PV_MQ_MIN}..{PV_MQ_MAX} (rates 0.75 to 4/3) are required; got {mqs}")
+    bt = Batch(x.lengths)
+    xin = x.data if x.data.dtype == torch.float32 else x.data.float()
+    y = istft(plan, bt, pv_frames(stft(plan, bt, xin, normalize=False), bt.frame_offsets, mqs), normalize=False)
+    out = Ragged(torch.zeros_like(xin), x.lengths)
+    for b in range(x.B):
+        o, n = out.offsets[b], (x.lengths[b] if mqs[b] == 0 else bt.out_lengths[b])
+        out.data[o:o + n] = xin[o:o + n] if mqs[b] == 0 else y[bt.out_offsets[b]: bt.out_offsets[b] + n]
     return out
 
 

@@ -639,6 +639,37 @@ int aware_stretch_ola(const float* in, const int* in_off, const int* in_len, flo
 int aware_pitch_shift_ola(const float* in, const int* in_off, const int* in_len, float* out, const int* out_off,
                           const int* out_len, int B, int max_len, const int* m, int adjoint, void* stream);
 
+/* ---- phase vocoder inside the loop (EXTENSION, parity unpinned: the reference's TimeStretch / PitchShift are library calls) ---
+ * The _ex pair also accepts (the older entry point keeps refusing every kind above 1)
+ *   AWARE_LOOP_PHASE_VOCODER, param = { mq_lo, mq_hi, m_lo, m_hi }: the stretch offsets of AWARE_LOOP_TIME_STRETCH and the
+ *     speed offsets of AWARE_LOOP_SPEED_CHANGE (the host converts rates and cents).  A mode is ABSENT where its lo > hi (the
+ *     host passes 0, -1); at least one is present.  With r the entry's draw: stretch mode where only the stretch range is
+ *     present, or both are and r[2] < 2^31; pitch mode otherwise.
+ *     stretch mode: mq = mq_lo + ((r[3] * (mq_hi - mq_lo + 1)) >> 32), m = 0;
+ *     pitch mode:   m = m_lo + ((r[3] * (m_hi - m_lo + 1)) >> 32), R = 65536 + m, mq = ((1 << 32) + R / 2) / R - 65536.
+ *   Q = 65536 + mq.  on: S = STFT(x) (the loop's geometry, T_b frames); for t < T_b: p = t Q (64-bit), i = p >> 16,
+ *   al = (p & 0xFFFF) / 65536; Y[t] = ((1 - al) |S[i]| + al |S[i + 1]|) P[t] with S[T_b] := 0 and Y[t] = 0 where i >= T_b;
+ *   P[0] = u(S[0]), P[t + 1] = P[t] u(S[i + 1]) conj(u(S[i])), u(c) = c / |c| and u(c) = 1 where both parts of c are zero;
+ *   z = the AWARE_LOOP_SPEED_CHANGE operator at m on iSTFT(Y), Ny_b samples long.  mq = 0 is the identity.  P, Q and m are
+ *   CONSTANTS in the backward pass (no phase gradients); d|c|/dc is 0 at a zero cell.  Entries in front of it and behind it
+ *   behave as around a lone speed change; a clip on which the entry does not fire keeps its bits through the stage, and one
+ *   on which no entry fires leaves the bits of the loop without a chain.
+ * AWARE_E_BADARG of the _ex setter, besides those above: a value that is not an integer, both modes absent, a present
+ * stretch range outside -16384..21845, a present speed range outside -13520..17034, a second phase vocoder, a phase vocoder
+ * together with a reverberation, a speed change, a time stretch or a pitch shift (in either order).
+ * aware_embed_loop_attack_workspace_bytes_ex for a chain with the kind is that of the same chain with a speed change in its
+ * place plus two spectra of [total frames][520] complex values (each rounded up to 256 bytes); chains without the kind need
+ * what they needed.  Added without a version step. */
+#define AWARE_LOOP_PHASE_VOCODER 6       /* param = mq_lo, mq_hi, m_lo, m_hi; lo > hi: the mode is absent */
+/* The frames' two kernels alone.  spec, out, grad_out, grad_spec: [frame_off[B]][520] complex float rows as aware_stft writes
+ * them, clip b's T_b = frame_off[b + 1] - frame_off[b] rows at row frame_off[b] (dev int [B + 1]); mq dev int [B], a value
+ * outside -16384..21845 is read as 0, which copies the clip's rows.  aware_pv_frames: out = Y from spec = S (never the same
+ * buffer).  aware_pv_frames_bwd: grad_spec = gS from spec = S and grad_out = dL/dY; grad_spec may be spec, never grad_out.
+ * AWARE_E_BADARG: a null pointer, B outside 1..65535, buffers that may not coincide. */
+int aware_pv_frames(const void* spec, const int* frame_off, int B, const int* mq, void* out, void* stream);
+int aware_pv_frames_bwd(const void* spec, const void* grad_out, const int* frame_off, int B, const int* mq, void* grad_spec,
+                        void* stream);
+
 /* ---- bare GEMM (tests / roofline): C[M][N] = A[M][K] * Bt[N][K]^T + bias ------------------------------ */
 int aware_gemm_nt(const float* A, int lda, const float* Bt, int ldb, const float* bias, float* C, int ldc,
                   int M, int N, int K, void* stream);

@@ -1,7 +1,7 @@
-"""Attack-aware embedding (DESIGN.md sections 15 to 19): what a chain of loop attacks costs per iteration, and what it buys.
+"""Attack-aware embedding (DESIGN.md sections 15 to 20): what a chain of loop attacks costs per iteration, and what it buys.
 
   (a) config-3 batch (256 x 3 s): per-iteration time of the graph-replayed loop with no chain, noise only, suppression only,
-      both, reverberation only, reverberation followed by noise, speed change only, speed change followed by noise, time stretch only, time stretch followed by a speed change and pitch shift only, from device events over --steps steps (>= 200) after a warm-up, the variants alternating in one process
+      both, reverberation only, reverberation followed by noise, speed change only, speed change followed by noise, time stretch only, time stretch followed by a speed change, pitch shift only and the phase vocoder with both modes, from device events over --steps steps (>= 200) after a warm-up, the variants alternating in one process
       (--rounds rounds; the median over rounds is reported);
   (b) the BER table at that size: 400-step embeddings without a chain, with noise at 10 dB and with 0.5 s suppression
       (prob 0.75), with the reverberation, the reverberation followed by noise and the speed change in the loop, then clean /
@@ -36,6 +36,7 @@ VARIANTS = {
     "stretch_speed": [{"kind": "time_stretch", "rate": [0.85, 1.15], "prob": 0.75},
                       {"kind": "speed_change", "cents": 100.0, "prob": 0.75}],
     "pitch": [{"kind": "pitch_shift", "cents": 100.0, "prob": 0.75}],
+    "phase_vocoder": [{"kind": "phase_vocoder", "rate": [0.85, 1.15], "cents": 150.0, "prob": 0.9}],
 }
 
 
@@ -79,7 +80,7 @@ def main():
         result[f"us_per_iteration/{name}"] = round(float(np.median(times[name])), 2)
         print(f"{name:13s} {np.median(times[name]):8.1f} us per iteration (rounds: {', '.join(f'{t:.1f}' for t in times[name])})")
     base = result["us_per_iteration/none"]
-    for name in ("noise", "suppression", "both", "reverb", "reverb_noise", "speed", "speed_noise", "stretch", "stretch_speed", "pitch"):
+    for name in ("noise", "suppression", "both", "reverb", "reverb_noise", "speed", "speed_noise", "stretch", "stretch_speed", "pitch", "phase_vocoder"):
         result[f"extra_us/{name}"] = round(result[f"us_per_iteration/{name}"] - base, 2)
     del sessions
 
