@@ -1733,6 +1733,9 @@ struct aware_embed {
         int pv = -1, pq_lo = 0, pq_hi = -1, pm_lo = 0, pm_hi = -1;
         cf* pvS = nullptr;                        // [NF][520] the spectrum of u; the backward pass turns it into its gradient
         cf* pvY = nullptr;                        // [NF][520] the vocoded spectrum; the backward pass holds dL/dY in it
+        // sample deletion (kind 7): entry ds of the chain, -1 without one; it excludes the five kinds above and reads u as the
+        // speed change does.  k drawn from [d_lo, d_hi], d_at 0: the cut starts at sample 0, 1: anywhere
+        int ds = -1, d_lo = 0, d_hi = 0, d_at = 0;
         const float* hann = nullptr;              // stretch_window()
         bool locked = false;                      // an optimiser step has run: the chain stays what it is
     } la;
@@ -1998,7 +2001,8 @@ extern "C" size_t aware_embed_loop_attack_workspace_bytes_ex(const aware_batch* 
     else if (has_kind(attacks, n_attacks, AWARE_LOOP_PHASE_VOCODER)) carve_loop_pv(c, b, e.la);
     else if (has_kind(attacks, n_attacks, AWARE_LOOP_TIME_STRETCH))
         carve_loop_stretch(c, b, e.la, has_kind(attacks, n_attacks, AWARE_LOOP_SPEED_CHANGE));
-    else if (has_kind(attacks, n_attacks, AWARE_LOOP_SPEED_CHANGE) || has_kind(attacks, n_attacks, AWARE_LOOP_PITCH_SHIFT))
+    else if (has_kind(attacks, n_attacks, AWARE_LOOP_SPEED_CHANGE) || has_kind(attacks, n_attacks, AWARE_LOOP_PITCH_SHIFT) ||
+             has_kind(attacks, n_attacks, AWARE_LOOP_DELETE_SAMPLES))
         carve_loop_speed(c, b, e.la);
     return c.off;
 }
@@ -2007,14 +2011,14 @@ static int set_loop_attacks(aware_embed* e, const aware_loop_attack_ex* attacks,
     static_assert(AWARE_LOOP_GAUSSIAN_NOISE == kLoopGaussianNoise && AWARE_LOOP_SAMPLE_SUPPRESSION == kLoopSampleSuppression &&
                   AWARE_LOOP_REVERBERATION == kLoopReverberation && AWARE_LOOP_SPEED_CHANGE == kLoopSpeedChange &&
                   AWARE_LOOP_TIME_STRETCH == kLoopTimeStretch && AWARE_LOOP_PITCH_SHIFT == kLoopPitchShift &&
-                  AWARE_LOOP_PHASE_VOCODER == kLoopPhaseVocoder, "");
+                  AWARE_LOOP_PHASE_VOCODER == kLoopPhaseVocoder && AWARE_LOOP_DELETE_SAMPLES == kLoopDeleteSamples, "");
     if (!e || n_attacks < 0 || n_attacks > kMaxLoopAttacks) return AWARE_E_BADARG;
     if (e->gexec || e->la.locked) return AWARE_E_BADARG;          // before the first aware_embed_iterate, as aware_embed_set_optimizer
-    if (n_attacks == 0) { e->la.n = 0; e->la.z = nullptr; e->la.rv = -1; e->la.sp = -1; e->la.ts = -1; e->la.ps = -1; e->la.pv = -1; e->la.h = nullptr; return AWARE_OK; }
+    if (n_attacks == 0) { e->la.n = 0; e->la.z = nullptr; e->la.rv = -1; e->la.sp = -1; e->la.ts = -1; e->la.ps = -1; e->la.pv = -1; e->la.ds = -1; e->la.h = nullptr; return AWARE_OK; }
     if (!attacks || !seeds || !workspace || ((uintptr_t)workspace & 255)) return AWARE_E_BADARG;
     const aware_batch* b = e->b;
     auto la = e->la;
-    la.rv = -1; la.sp = -1; la.ts = -1; la.ps = -1; la.pv = -1; la.h = nullptr; la.v = nullptr;
+    la.rv = -1; la.sp = -1; la.ts = -1; la.ps = -1; la.pv = -1; la.ds = -1; la.h = nullptr; la.v = nullptr;
     for (int j = 0; j < n_attacks; ++j) {
         const aware_loop_attack_ex& a = attacks[j];
         if (!(a.prob >= 0.f && a.prob <= 1.f)) return AWARE_E_BADARG;
@@ -2027,14 +2031,14 @@ static int set_loop_attacks(aware_embed* e, const aware_loop_attack_ex* attacks,
             la.k[j] = (int)a.param[0];
         } else if (a.kind == AWARE_LOOP_REVERBERATION && ex) {
             const float lo = a.param[0], hi = a.param[1], drr = a.param[2];
-            if (la.rv >= 0 || la.sp >= 0 || la.ts >= 0 || la.ps >= 0 || la.pv >= 0) return AWARE_E_BADARG;     // one reverberation per chain, and no other kind that splits a chain beside it
+            if (la.rv >= 0 || la.sp >= 0 || la.ts >= 0 || la.ps >= 0 || la.pv >= 0 || la.ds >= 0) return AWARE_E_BADARG;     // one reverberation per chain, and no other kind that splits a chain beside it
             if (!(lo >= 2.f) || !(hi <= (float)kReverbMaxIr) || !(lo <= hi) || lo != floorf(lo) || hi != floorf(hi) ||
                 !std::isfinite(drr))
                 return AWARE_E_BADARG;
             la.rv = j; la.n_lo = (int)lo; la.n_hi = (int)hi; la.gain = pow(10.0, (double)drr / 20.0);
         } else if (a.kind == AWARE_LOOP_SPEED_CHANGE && ex) {
             const float lo = a.param[0], hi = a.param[1];
-            if (la.rv >= 0 || la.sp >= 0 || la.ps >= 0 || la.pv >= 0) return AWARE_E_BADARG;     // one speed change per chain, and no reverberation, pitch shift or phase vocoder beside it
+            if (la.rv >= 0 || la.sp >= 0 || la.ps >= 0 || la.pv >= 0 || la.ds >= 0) return AWARE_E_BADARG;     // one speed change per chain, and no reverberation, pitch shift or phase vocoder beside it
             if (la.ts >= 0 && la.ts != j - 1) return AWARE_E_BADARG; // beside a time stretch: directly behind it
             if (!(lo >= (float)kSpeedMin) || !(hi <= (float)kSpeedMax) || !(lo <= hi) || lo != floorf(lo) || hi != floorf(hi))
                 return AWARE_E_BADARG;
@@ -2042,21 +2046,21 @@ static int set_loop_attacks(aware_embed* e, const aware_loop_attack_ex* attacks,
         } else if (a.kind == AWARE_LOOP_TIME_STRETCH && ex) {
             const float lo = a.param[0], hi = a.param[1];
             // one time stretch per chain, no reverberation, pitch shift or phase vocoder beside it, and no speed change in front of it
-            if (la.rv >= 0 || la.sp >= 0 || la.ts >= 0 || la.ps >= 0 || la.pv >= 0) return AWARE_E_BADARG;
+            if (la.rv >= 0 || la.sp >= 0 || la.ts >= 0 || la.ps >= 0 || la.pv >= 0 || la.ds >= 0) return AWARE_E_BADARG;
             if (!(lo >= (float)kStretchMin) || !(hi <= (float)kStretchMax) || !(lo <= hi) || lo != floorf(lo) || hi != floorf(hi))
                 return AWARE_E_BADARG;
             la.ts = j; la.q_lo = (int)lo; la.q_hi = (int)hi;
         } else if (a.kind == AWARE_LOOP_PITCH_SHIFT && ex) {
             const float lo = a.param[0], hi = a.param[1];
             // one pitch shift per chain, and none of the other kinds that split a chain beside it
-            if (la.rv >= 0 || la.sp >= 0 || la.ts >= 0 || la.ps >= 0 || la.pv >= 0) return AWARE_E_BADARG;
+            if (la.rv >= 0 || la.sp >= 0 || la.ts >= 0 || la.ps >= 0 || la.pv >= 0 || la.ds >= 0) return AWARE_E_BADARG;
             if (!(lo >= (float)kSpeedMin) || !(hi <= (float)kSpeedMax) || !(lo <= hi) || lo != floorf(lo) || hi != floorf(hi))
                 return AWARE_E_BADARG;
             la.ps = j; la.p_lo = (int)lo; la.p_hi = (int)hi;
         } else if (a.kind == AWARE_LOOP_PHASE_VOCODER && ex) {
             // one phase vocoder per chain, and none of the other kinds that split a chain beside it; param = {mq_lo, mq_hi,
             // m_lo, m_hi}, a mode with lo > hi is absent, and one of the two is there
-            if (la.rv >= 0 || la.sp >= 0 || la.ts >= 0 || la.ps >= 0 || la.pv >= 0) return AWARE_E_BADARG;
+            if (la.rv >= 0 || la.sp >= 0 || la.ts >= 0 || la.ps >= 0 || la.pv >= 0 || la.ds >= 0) return AWARE_E_BADARG;
             for (int i = 0; i < 4; ++i)
                 if (!(fabsf(a.param[i]) <= 65536.f) || a.param[i] != floorf(a.param[i])) return AWARE_E_BADARG;
             const int ql = (int)a.param[0], qh = (int)a.param[1], ml = (int)a.param[2], mh = (int)a.param[3];
@@ -2064,19 +2068,29 @@ static int set_loop_attacks(aware_embed* e, const aware_loop_attack_ex* attacks,
             if (ql <= qh && (ql < kStretchMin || qh > kStretchMax)) return AWARE_E_BADARG;
             if (ml <= mh && (ml < kSpeedMin || mh > kSpeedMax)) return AWARE_E_BADARG;
             la.pv = j; la.pq_lo = ql; la.pq_hi = qh; la.pm_lo = ml; la.pm_hi = mh;
+        } else if (a.kind == AWARE_LOOP_DELETE_SAMPLES && ex) {
+            // one sample deletion per chain, and none of the other kinds that split a chain beside it; param = {k_lo, k_hi, at, 0}
+            const float lo = a.param[0], hi = a.param[1], at = a.param[2];
+            if (la.rv >= 0 || la.sp >= 0 || la.ts >= 0 || la.ps >= 0 || la.pv >= 0 || la.ds >= 0) return AWARE_E_BADARG;
+            if (!(lo >= 1.f) || !(hi <= 2147483520.f) || !(lo <= hi) || lo != floorf(lo) || hi != floorf(hi) ||
+                !(at == 0.f || at == 1.f))
+                return AWARE_E_BADARG;
+            la.ds = j; la.d_lo = (int)lo; la.d_hi = (int)hi; la.d_at = (int)at;
         } else {
             return AWARE_E_BADARG;
         }
     }
     for (int j = 0; j < n_attacks; ++j)
         for (int i = 0; i < b->B; ++i)
-            if (la.kind[j] == AWARE_LOOP_SAMPLE_SUPPRESSION && la.k[j] >= b->out_len[i]) return AWARE_E_UNSUPPORTED;
+            if ((la.kind[j] == AWARE_LOOP_SAMPLE_SUPPRESSION && la.k[j] >= b->out_len[i]) ||
+                (la.kind[j] == AWARE_LOOP_DELETE_SAMPLES && la.d_hi >= b->out_len[i]))
+                return AWARE_E_UNSUPPORTED;
     Carver c(workspace, workspace_bytes);
     carve_loop_attacks(c, b, la);
     if (la.rv >= 0) carve_loop_reverb(c, b, la);
     else if (la.pv >= 0) carve_loop_pv(c, b, la);
     else if (la.ts >= 0) carve_loop_stretch(c, b, la, la.sp >= 0);
-    else if (la.sp >= 0 || la.ps >= 0) carve_loop_speed(c, b, la);
+    else if (la.sp >= 0 || la.ps >= 0 || la.ds >= 0) carve_loop_speed(c, b, la);
     if (!c.ok) return AWARE_E_WORKSPACE;
     if ((la.ts >= 0 || la.ps >= 0) && !(la.hann = stretch_window())) return AWARE_E_HIP;
     hipStream_t st = (hipStream_t)stream;
@@ -2162,6 +2176,28 @@ extern "C" int aware_speed_change(const float* in, const int* in_off, const int*
     L.in = in; L.out = out; L.B = B; L.adjoint = adjoint; L.max_len = max_len; L.m = m;
     L.x_off = in_off; L.x_len = in_len; L.z_off = out_off; L.z_len = out_len;
     launch_speed_change(L, (hipStream_t)stream);
+    LAUNCHCHK();
+    return AWARE_OK;
+}
+
+// ---- the sample deletion alone (EXTENSION; runtime.delete_samples, tests) --------------------------------------------------
+extern "C" int aware_delete_samples(const float* in, const int* off, const int* len, int B, int max_len, const int* start,
+                                    const int* k, float* out, int adjoint, void* stream) {
+    if (!in || !off || !len || !start || !k || !out || in == out) return AWARE_E_BADARG;
+    if (B < 1 || B > 65535 || max_len < 1 || max_len > (1 << 30) || adjoint < 0 || adjoint > 1) return AWARE_E_BADARG;
+    DeleteLaunch L;
+    L.in = in; L.out = out; L.B = B; L.adjoint = adjoint; L.off = off; L.len = len; L.max_len = max_len; L.start = start; L.k = k;
+    launch_delete_samples(L, (hipStream_t)stream);
+    LAUNCHCHK();
+    return AWARE_OK;
+}
+
+// ---- the offset search's selection (EXTENSION; AWAREDetector.detect_batch(sync_search=n), tests) ---------------------------
+extern "C" int aware_sync_select(const float* values, int B, int n, int L, float centre, float* out_values, int* out_index,
+                                 float* out_conf, void* stream) {
+    if (!values || !out_values || !out_index || !out_conf || values == out_values) return AWARE_E_BADARG;
+    if (B < 1 || B > 65535 || n < 1 || n > 64 || L < 1 || L > 65536 || !std::isfinite(centre)) return AWARE_E_BADARG;
+    launch_sync_select(values, B, n, L, centre, out_values, out_index, out_conf, (hipStream_t)stream);
     LAUNCHCHK();
     return AWARE_OK;
 }
@@ -2292,6 +2328,15 @@ static SpeedLaunch speed_launch(const aware_embed* e, const float* in, float* ou
     return S;
 }
 
+static DeleteLaunch delete_launch(const aware_embed* e, const float* in, float* out, int adjoint, int step_back) {
+    const auto& la = e->la;
+    DeleteLaunch S;
+    S.in = in; S.out = out; S.B = e->b->B; S.adjoint = adjoint; S.frame_off = e->b->d_frame_off; S.pstride = e->b->pstride;
+    S.run_blocks = e->b->synth_run; S.step = e->step; S.step_back = step_back; S.seeds = la.seeds; S.entry = la.ds;
+    S.k_lo = la.d_lo; S.k_hi = la.d_hi; S.at = la.d_at; S.prob = la.prob[la.ds];
+    return S;
+}
+
 static StretchLaunch stretch_launch(const aware_embed* e, const float* in, float* out, int adjoint, int step_back) {
     const auto& la = e->la;
     StretchLaunch S;
@@ -2410,7 +2455,7 @@ static int embed_iteration(aware_embed* e, hipStream_t st, int do_step, float* g
         A.step = e->step; A.seeds = la.seeds; A.n = la.n;
         for (int j = 0; j < la.n; ++j) { A.kind[j] = la.kind[j]; A.k[j] = la.k[j]; A.inv_snr[j] = la.inv_snr[j]; A.prob[j] = la.prob[j]; }
         A.yraw = e->yraw; A.pmaxY = e->pmaxY; A.psq = la.psq; A.z = la.z; A.pmaxZ = la.pmaxZ;
-        if (la.rv >= 0 || la.sp >= 0 || la.ts >= 0 || la.ps >= 0 || la.pv >= 0) { A.idle_plain = 1; A.gpad_out = la.gpad0; }
+        if (la.rv >= 0 || la.sp >= 0 || la.ts >= 0 || la.ps >= 0 || la.pv >= 0 || la.ds >= 0) { A.idle_plain = 1; A.gpad_out = la.gpad0; }
         if (la.ts >= 0) {
             // the entries in front of the stretch on N(N(yraw)), the overlap-add (and the resampling of a speed change
             // directly behind it), the entries behind
@@ -2436,6 +2481,11 @@ static int embed_iteration(aware_embed* e, hipStream_t st, int do_step, float* g
             launch_loop_attack_stage(A, 0, la.pv, e->yraw, 1, la.u, nullptr, st);
             pv_stage_forward(e, e->gy, st);
             launch_loop_attack_stage(A, la.pv + 1, la.n, la.z, 0, la.z, la.pmaxZ, st);
+        } else if (la.ds >= 0) {
+            // the same shape: the entries in front of the deletion on N(N(yraw)), the gather, the entries behind it
+            launch_loop_attack_stage(A, 0, la.ds, e->yraw, 1, la.u, nullptr, st);
+            launch_delete_samples(delete_launch(e, la.u, la.z, 0, 0), st);
+            launch_loop_attack_stage(A, la.ds + 1, la.n, la.z, 0, la.z, la.pmaxZ, st);
         } else if (la.rv < 0) {
             launch_loop_attack_forward(A, st);
         } else {
@@ -2519,6 +2569,13 @@ static int embed_iteration(aware_embed* e, hipStream_t st, int do_step, float* g
             A.gy_out = nullptr;
             pv_stage_backward(e, A.step_back, st);
             launch_loop_attack_stage_bwd(A, 0, e->la.pv, 0, 1, st);
+        } else if (e->la.ds >= 0) {
+            // the mirror, as for the speed change: into u, the gather-form adjoint back into gy, the stage in front
+            A.gy_out = e->la.u;
+            launch_loop_attack_stage_bwd(A, e->la.ds + 1, e->la.n, 1, 0, st);
+            A.gy_out = nullptr;
+            launch_delete_samples(delete_launch(e, e->la.u, e->gy, 1, A.step_back), st);
+            launch_loop_attack_stage_bwd(A, 0, e->la.ds, 0, 1, st);
         } else if (e->la.rv < 0) {
             launch_loop_attack_backward(A, st);
         } else {

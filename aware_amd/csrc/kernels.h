@@ -357,7 +357,7 @@ void launch_stoi(const StoiLaunch& L, hipStream_t st);
 // its analysis, drawn afresh at every optimiser step (aware_embed_set_loop_attacks) --------------------------------------
 constexpr int kMaxLoopAttacks = 4;
 constexpr int kLoopGaussianNoise = 0, kLoopSampleSuppression = 1, kLoopReverberation = 2, kLoopSpeedChange = 3, kLoopTimeStretch = 4,
-              kLoopPitchShift = 5, kLoopPhaseVocoder = 6;      // AWARE_LOOP_* of aware_hip.h
+              kLoopPitchShift = 5, kLoopPhaseVocoder = 6, kLoopDeleteSamples = 7;      // AWARE_LOOP_* of aware_hip.h
 struct LoopAttackLaunch {
     const int* frame_off = nullptr;
     const int* pcount = nullptr;          // [B] synthesis runs per clip: the partials' layout
@@ -524,5 +524,31 @@ struct PvLaunch {
 void launch_pv_frames(const PvLaunch& L, int backward, hipStream_t st);
 // the loop's clips that the entry leaves alone at this step: dst = src (the embed loop's signal layout)
 void launch_pv_idle(const PvLaunch& L, const float* src, float* dst, hipStream_t st);
+
+// ---- loop_delete_kernels.hip: sample deletion (EXTENSION): k samples cut out at `start`, the remainder moved up, zeros at the
+// end, inside the embed loop (chain kind 7) and stand-alone (aware_delete_samples), and its adjoint in gather form ---------
+struct DeleteLaunch {
+    const float* in = nullptr; float* out = nullptr;      // never the same buffer
+    int B = 0, adjoint = 0;               // 0: out = z from in = x; 1: out = gx from in = gz
+    // the embed loop's layout: x and z both Ny_b long at sig_offset, one workgroup per synthesis run, start and k drawn in the kernel
+    const int* frame_off = nullptr;
+    int pstride = 0, run_blocks = 0;
+    const int* step = nullptr; int step_back = 0;
+    const unsigned* seeds = nullptr;      // [B]
+    int entry = 0, k_lo = 0, k_hi = 0;    // 1 <= k_lo <= k_hi < every Ny_b
+    int at = 0;                           // 0: the cut starts at sample 0; 1: anywhere
+    float prob = 0.f;
+    // or a ragged batch (frame_off null): both sides are len[b] floats at off[b]; start[b] and k[b] given, clamped to the clip
+    const int* off = nullptr; const int* len = nullptr;
+    int max_len = 0;                      // >= every length
+    const int* start = nullptr;           // [B]
+    const int* k = nullptr;               // [B]
+};
+void launch_delete_samples(const DeleteLaunch& L, hipStream_t st);
+
+// ---- sync_kernels.hip: offset search in detection (EXTENSION): values [B][n][L] -> the row of the largest mean |v - centre|
+// per clip (the smallest j on a tie), its index and that mean; one wave per clip ------------------------------------------
+void launch_sync_select(const float* values, int B, int n, int L, float centre, float* out_values, int* out_index,
+                        float* out_conf, hipStream_t st);
 
 }  // namespace aware

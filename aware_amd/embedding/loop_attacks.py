@@ -67,6 +67,18 @@ the loop's new stage.  For clip b (length Ny) at optimiser step s with seed_b:
         reverberation, a speed change, a time stretch or a pitch shift, in either order; element-wise entries may stand in front
         of it and behind it, and a noise entry behind it takes its sigma from the vocoded signal.
 
+      delete_samples(seconds = v or [lo, hi], at = "start" or "anywhere"): a scalar v means k_lo = 1, k_hi = int(v * sample_rate);
+        a pair k_lo = int(lo * sample_rate), k_hi = int(hi * sample_rate); 1 <= k_lo <= k_hi < Ny.
+        k = k_lo + ((r[2] * (k_hi - k_lo + 1)) >> 32);  start = 0 for at: start (the reference's Cropout), otherwise
+        suppression_start(r[1], Ny, k) = (r[1] * (Ny - k)) >> 32 (its DeleteSamples);
+        on: z[i] = x[i] for i < start, x[i + k] for start <= i < Ny - k, 0 for i >= Ny - k: k samples are cut out, the remainder
+        moves up and the clip keeps its length, as under the speed and stretch kinds.  Every index is an integer and every
+        value a copy, so host and device agree bit for bit.  The backward pass is the exact adjoint in gather form:
+        gx[i] = gz[i] for i < start, 0 for start <= i < start + k, gz[i - k] for i >= start + k.  At most one per chain, and not
+        in a chain with a reverberation, a speed change, a time stretch, a pitch shift or a phase vocoder, in either order;
+        element-wise entries may stand in front of it and behind it, and a noise entry behind it takes its sigma from the
+        shortened signal.
+
 In the loop x = N(N(y)) of the raw synthesis y, N(v) = v / (max|v| + 1e-8), and the analysis (N, N, STFT, band magnitudes)
 runs on the chain's output."""
 from __future__ import annotations
@@ -78,16 +90,18 @@ import torch
 
 MAX_ATTACKS = 4
 KINDS = {"gaussian_noise": 0, "sample_suppression": 1, "reverberation": 2, "speed_change": 3, "time_stretch": 4,
-         "pitch_shift": 5, "phase_vocoder": 6}      # AWARE_LOOP_* of include/aware_hip.h
+         "pitch_shift": 5, "phase_vocoder": 6, "delete_samples": 7}      # AWARE_LOOP_* of include/aware_hip.h
 _KEYS = {"gaussian_noise": {"kind", "snr_db", "prob"}, "sample_suppression": {"kind", "seconds", "prob"},
          "reverberation": {"kind", "rt60", "drr_db", "prob"}, "speed_change": {"kind", "cents", "prob"}, "time_stretch": {"kind", "rate", "prob"},
-         "pitch_shift": {"kind", "cents", "prob"}, "phase_vocoder": {"kind", "rate", "cents", "prob"}}
+         "pitch_shift": {"kind", "cents", "prob"}, "phase_vocoder": {"kind", "rate", "cents", "prob"},
+         "delete_samples": {"kind", "seconds", "at", "prob"}}
 _KEY1 = 0x5EED
 MAX_IR = 8192                   # taps of the longest impulse response
 _IR_WORD = 8                    # third Philox counter word of the impulse responses (0: noise, 1..4: entry draws)
 MAX_CENTS = 400.0               # widest speed change or pitch shift either way
 MIN_RATE, MAX_RATE = 0.75, 4.0 / 3.0            # slowest and fastest time stretch
 STRETCH_HOP, STRETCH_WIN = 256, 1024            # the overlap-add's hop and window: the loop's STFT geometry
+DELETE_AT = {"start": 0, "anywhere": 1}         # where a sample deletion cuts: param[2] of the C ABI's entry
 
 
 def _no_pitch_shift(j: int, kind: str, out: list[dict]) -> None:
@@ -98,6 +112,11 @@ def _no_pitch_shift(j: int, kind: str, out: list[dict]) -> None:
 def _no_phase_vocoder(j: int, kind: str, out: list[dict]) -> None:
     if any(o["kind"] == "phase_vocoder" for o in out):
         raise ValueError(f"loop_attacks[{j}] ({kind}): a chain holds a phase vocoder or a {kind.replace('_', ' ')}, not both")
+
+
+def _no_delete_samples(j: int, kind: str, out: list[dict]) -> None:
+    if any(o["kind"] == "delete_samples" for o in out):
+        raise ValueError(f"loop_attacks[{j}] ({kind}): a chain holds a sample deletion or a {kind.replace('_', ' ')}, not both")
 
 
 def _parse_rate(j: int, kind: str, a: dict) -> list[float]:
@@ -168,7 +187,10 @@ def parse_chain(chain) -> list[dict]:
     "cents": 100.0 | [-50.0, 120.0]}: what a speed change's cents are refused for, a second pitch shift, a pitch shift in a
     chain with a reverberation, a speed change or a time stretch; for {"kind": "phase_vocoder", "rate": 1.15 | [0.85, 1.15],
     "cents": 150.0 | [-50.0, 120.0]}: neither key, what a time stretch's rate or a speed change's cents are refused for, a second
-    phase vocoder, a phase vocoder in a chain with a reverberation, a speed change, a time stretch or a pitch shift."""
+    phase vocoder, a phase vocoder in a chain with a reverberation, a speed change, a time stretch or a pitch shift; for
+    {"kind": "delete_samples", "seconds": 0.032 | [0.01, 0.2], "at": "start" | "anywhere"}: a missing seconds, seconds not
+    0 < lo <= hi (finite), more or fewer than two values in a list, an unknown at, a second sample deletion, a sample deletion in
+    a chain with any of those five kinds (in either order)."""
     if not chain:
         return []
     if isinstance(chain, dict) or not isinstance(chain, (list, tuple)):
@@ -197,6 +219,7 @@ def parse_chain(chain) -> list[dict]:
                 raise ValueError(f"loop_attacks[{j}] (reverberation): at most one reverberation per chain")
             _no_pitch_shift(j, kind, out)
             _no_phase_vocoder(j, kind, out)
+            _no_delete_samples(j, kind, out)
             if any(o["kind"] == "speed_change" for o in out):
                 raise ValueError(f"loop_attacks[{j}] (reverberation): a chain holds a speed change or a reverberation, not both")
             if any(o["kind"] == "time_stretch" for o in out):
@@ -219,6 +242,7 @@ def parse_chain(chain) -> list[dict]:
                 raise ValueError(f"loop_attacks[{j}] (speed_change): at most one speed change per chain")
             _no_pitch_shift(j, kind, out)
             _no_phase_vocoder(j, kind, out)
+            _no_delete_samples(j, kind, out)
             if any(o["kind"] == "reverberation" for o in out):
                 raise ValueError(f"loop_attacks[{j}] (speed_change): a chain holds a speed change or a reverberation, not both")
             if any(o["kind"] == "time_stretch" for o in out) and out[-1]["kind"] != "time_stretch":
@@ -229,6 +253,7 @@ def parse_chain(chain) -> list[dict]:
                 raise ValueError(f"loop_attacks[{j}] (time_stretch): at most one time stretch per chain")
             _no_pitch_shift(j, kind, out)
             _no_phase_vocoder(j, kind, out)
+            _no_delete_samples(j, kind, out)
             if any(o["kind"] == "reverberation" for o in out):
                 raise ValueError(f"loop_attacks[{j}] (time_stretch): a chain holds a time stretch or a reverberation, not both")
             if any(o["kind"] == "speed_change" for o in out):
@@ -241,6 +266,7 @@ def parse_chain(chain) -> list[dict]:
                 if any(o["kind"] == other for o in out):
                     raise ValueError(f"loop_attacks[{j}] (pitch_shift): a chain holds a pitch shift or a {other.replace('_', ' ')}, not both")
             _no_phase_vocoder(j, kind, out)
+            _no_delete_samples(j, kind, out)
             e["cents"] = _parse_cents(j, kind, a)
         elif kind == "phase_vocoder":
             if any(o["kind"] == "phase_vocoder" for o in out):
@@ -248,12 +274,39 @@ def parse_chain(chain) -> list[dict]:
             for other in ("reverberation", "speed_change", "time_stretch", "pitch_shift"):
                 if any(o["kind"] == other for o in out):
                     raise ValueError(f"loop_attacks[{j}] (phase_vocoder): a chain holds a phase vocoder or a {other.replace('_', ' ')}, not both")
+            _no_delete_samples(j, kind, out)
             if "rate" not in a and "cents" not in a:
                 raise ValueError(f"loop_attacks[{j}] (phase_vocoder): at least one of rate and cents is required")
             if "rate" in a:
                 e["rate"] = _parse_rate(j, kind, a)
             if "cents" in a:
                 e["cents"] = _parse_cents(j, kind, a)
+        elif kind == "delete_samples":
+            if any(o["kind"] == "delete_samples" for o in out):
+                raise ValueError(f"loop_attacks[{j}] (delete_samples): at most one sample deletion per chain")
+            for other in ("reverberation", "speed_change", "time_stretch", "pitch_shift", "phase_vocoder"):
+                if any(o["kind"] == other for o in out):
+                    raise ValueError(f"loop_attacks[{j}] (delete_samples): a chain holds a sample deletion or a {other.replace('_', ' ')}, not both")
+            if "seconds" not in a:
+                raise ValueError(f"loop_attacks[{j}] (delete_samples): seconds is required")
+            sec = a["seconds"]
+            try:
+                if isinstance(sec, (list, tuple)):
+                    if len(sec) != 2:
+                        raise TypeError
+                    lo, hi = float(sec[0]), float(sec[1])
+                    e["seconds"] = [lo, hi]
+                else:
+                    lo = hi = float(sec)
+                    e["seconds"] = hi
+            except (TypeError, ValueError):
+                raise ValueError(f"loop_attacks[{j}] (delete_samples): seconds = {sec!r} is neither a number nor [lo, hi]") from None
+            if not (math.isfinite(lo) and math.isfinite(hi) and 0.0 < lo <= hi):
+                raise ValueError(f"loop_attacks[{j}] (delete_samples): seconds needs 0 < lo <= hi, both finite; got {sec!r}")
+            at = a.get("at", "start")
+            if not isinstance(at, str) or at not in DELETE_AT:
+                raise ValueError(f"loop_attacks[{j}] (delete_samples): at = {at!r}; available: {list(DELETE_AT)}")
+            e["at"] = at
         else:
             if "seconds" not in a or not math.isfinite(float(a["seconds"])) or float(a["seconds"]) <= 0.0:
                 raise ValueError(f"loop_attacks[{j}] (sample_suppression): seconds > 0 is required")
@@ -286,10 +339,30 @@ def stretch_range(entry: dict) -> tuple[int, int]:
     return int(math.ceil(65536.0 * (lo - 1.0))), int(math.floor(65536.0 * (hi - 1.0)))
 
 
+def delete_range(entry: dict, sample_rate: int) -> tuple[int, int]:
+    """(k_lo, k_hi) of a parsed delete_samples entry: (1, int(v * sample_rate)) for a scalar v, (int(lo * sample_rate),
+    int(hi * sample_rate)) for a pair."""
+    sec = entry["seconds"]
+    if isinstance(sec, (list, tuple)):
+        return int(sec[0] * sample_rate), int(sec[1] * sample_rate)
+    return 1, int(sec * sample_rate)
+
+
 def check_lengths(chain: list[dict], sample_rate: int, out_lengths) -> None:
-    """ValueError naming the first clip that a suppression would not fit into (0 < k < Ny_b is required), or a reverberation
-    whose impulse response would have fewer than 2 or more than MAX_IR taps at this sample rate."""
+    """ValueError naming the first clip that a suppression would not fit into (0 < k < Ny_b is required), a reverberation
+    whose impulse response would have fewer than 2 or more than MAX_IR taps at this sample rate, or a sample deletion without
+    1 <= k_lo <= k_hi < Ny_b."""
     for j, a in enumerate(chain):
+        if a["kind"] == "delete_samples":
+            k_lo, k_hi = delete_range(a, sample_rate)
+            if not 1 <= k_lo <= k_hi:
+                raise ValueError(f"loop_attacks[{j}] (delete_samples): seconds = {a['seconds']} is {k_lo}..{k_hi} samples at "
+                                 f"{sample_rate} Hz; 1 <= k_lo <= k_hi is required")
+            for b, ny in enumerate(out_lengths):
+                if k_hi >= int(ny):
+                    raise ValueError(f"loop_attacks[{j}] (delete_samples): clip {b} has {int(ny)} output samples, "
+                                     f"not more than the {k_hi} that may be deleted")
+            continue
         if a["kind"] == "reverberation":
             n_lo, n_hi = reverb_taps(a, sample_rate)
             if n_lo < 2 or n_hi > MAX_IR:
@@ -541,6 +614,37 @@ def pv_stretch(x: torch.Tensor, mq: int) -> torch.Tensor:
     return y if y.shape[-1] == n else torch.cat([y, torch.zeros(n - y.shape[-1], dtype=y.dtype, device=y.device)])
 
 
+def delete_count(r2: int, k_lo: int, k_hi: int) -> int:
+    """k = k_lo + ((r2 * (k_hi - k_lo + 1)) >> 32): uniform on [k_lo, k_hi], in integers as the device computes it."""
+    return int(k_lo) + ((int(r2) * (int(k_hi) - int(k_lo) + 1)) >> 32)
+
+
+def delete_draw(entry: dict, r, ny: int, sample_rate: int) -> tuple[int, int]:
+    """(start, k) of a parsed delete_samples entry from its draw r = entry_draw(seed, step, j) on a clip of ny samples."""
+    k = delete_count(r[2], *delete_range(entry, sample_rate))
+    return (suppression_start(r[1], ny, k) if entry["at"] == "anywhere" else 0), k
+
+
+def delete_samples(x: torch.Tensor, start: int, k: int) -> torch.Tensor:
+    """x [..., n] without its samples [start, start + k): z[i] = x[i] for i < start, x[i + k] for start <= i < n - k, 0 behind;
+    n samples long.  Differentiable in x (a gather: every value is a copy); k = 0 returns x."""
+    n, start, k = x.shape[-1], int(start), int(k)
+    if k == 0:
+        return x
+    if not (0 <= start and 0 < k and start + k <= n):
+        raise ValueError(f"delete_samples: the cut [{start}, {start + k}) does not lie inside the {n} samples")
+    return torch.cat([x[..., :start], x[..., start + k:], torch.zeros(x.shape[:-1] + (k,), dtype=x.dtype, device=x.device)], dim=-1)
+
+
+def delete_samples_adjoint(gz: torch.Tensor, start: int, k: int) -> torch.Tensor:
+    """The adjoint of delete_samples in gather form: gx[i] = gz[i] for i < start, 0 for start <= i < start + k, gz[i - k] for
+    i >= start + k."""
+    n, start, k = gz.shape[-1], int(start), int(k)
+    if k == 0:
+        return gz
+    return torch.cat([gz[..., :start], torch.zeros(gz.shape[:-1] + (k,), dtype=gz.dtype, device=gz.device), gz[..., start:n - k]], dim=-1)
+
+
 def _convolve(xb: torch.Tensor, h: np.ndarray) -> torch.Tensor:
     """(h * xb)[0 : len(xb)] in xb's dtype through an FFT at least len(xb) + len(h) - 1 long; differentiable in xb."""
     ny, nh = xb.shape[-1], len(h)
@@ -589,6 +693,10 @@ def apply_chain(x, chain, seeds, step: int, sample_rate: int = 16000):
                 mq, m = pv_draw(a, r)
                 if on:
                     xb = speed_change(pv_stretch(xb, mq), m)
+            elif a["kind"] == "delete_samples":
+                start, k = delete_draw(a, r, ny, sample_rate)
+                if on:
+                    xb = delete_samples(xb, start, k)
             elif on:
                 power = float(np.mean(xb.detach().double().cpu().numpy() ** 2))
                 sigma = math.sqrt(power / (10.0 ** (a["snr_db"] / 10.0)))
@@ -601,7 +709,8 @@ def apply_chain(x, chain, seeds, step: int, sample_rate: int = 16000):
 def device_entries_ex(chain: list[dict], sample_rate: int):
     """(kind, prob, [param0..3]) of the C ABI's aware_loop_attack_ex: kinds 0 and 1 as device_entries in param[0]; a
     reverberation has param = [n_lo, n_hi, drr_db, 0], a speed change, a time stretch or a pitch shift [m_lo, m_hi, 0, 0], a
-    phase vocoder [mq_lo, mq_hi, m_lo, m_hi] with [0, -1] (lo > hi) for an absent mode."""
+    phase vocoder [mq_lo, mq_hi, m_lo, m_hi] with [0, -1] (lo > hi) for an absent mode, a sample deletion
+    [k_lo, k_hi, at (0 start / 1 anywhere), 0]."""
     out = []
     for a in chain:
         if a["kind"] == "reverberation":
@@ -617,6 +726,9 @@ def device_entries_ex(chain: list[dict], sample_rate: int):
         elif a["kind"] == "time_stretch":
             m_lo, m_hi = stretch_range(a)
             out.append((KINDS[a["kind"]], a["prob"], [float(m_lo), float(m_hi), 0.0, 0.0]))
+        elif a["kind"] == "delete_samples":
+            k_lo, k_hi = delete_range(a, sample_rate)
+            out.append((KINDS[a["kind"]], a["prob"], [float(k_lo), float(k_hi), float(DELETE_AT[a["at"]]), 0.0]))
         else:
             k, p, pr = device_entries([a], sample_rate)[0]
             out.append((k, pr, [p, 0.0, 0.0, 0.0]))

@@ -570,7 +570,7 @@ class EmbedSession:
             raise ValueError(f"set_loop_attacks: {self.batch.B} clips but {len(seeds)} seeds")
         la.check_lengths(chain, sample_rate, self.batch.out_lengths)      # ValueError naming the clip, before any launch
         sd = (C.c_uint32 * self.batch.B)(*[int(s) & 0xFFFFFFFF for s in seeds])
-        if any(a["kind"] in ("reverberation", "speed_change", "time_stretch", "pitch_shift", "phase_vocoder") for a in chain):
+        if any(a["kind"] in ("reverberation", "speed_change", "time_stretch", "pitch_shift", "phase_vocoder", "delete_samples") for a in chain):
             # the entry points with four parameters per entry; chains of the two older kinds keep the older call
             ent = la.device_entries_ex(chain, sample_rate)
             arr = (_lib.LoopAttackEx * len(ent))(*[_lib.LoopAttackEx(k, pr, (C.c_float * 4)(*p)) for k, pr, p in ent])
@@ -935,6 +935,43 @@ def speed_change(x: Ragged, m, adjoint: bool = False, out_lengths=None) -> Ragge
     check(lib.aware_speed_change(_ptr(xin), _ptr(src.d_off), _ptr(src.d_len), _ptr(out.data), _ptr(dst.d_off), _ptr(dst.d_len),
                                  x.B, max(x.max_len, out.max_len), _ptr(md), int(bool(adjoint)), _stream()), "aware_speed_change")
     return out
+
+
+def delete_samples(x: Ragged, start, k, adjoint: bool = False) -> Ragged:
+    """Per clip embedding.loop_attacks.delete_samples (aware_delete_samples): the k[b] samples from start[b] on are cut out of
+    clip b, the remainder moves up and zeros follow, so every clip keeps its length (B integers each, or one for all; k = 0
+    is the identity).  With adjoint, x holds the gradient with respect to that output and the result is the gradient with
+    respect to the input (zeros where the cut was)."""
+    lib = load_library()
+    st = [int(start)] * x.B if np.isscalar(start) else [int(v) for v in start]
+    ks = [int(k)] * x.B if np.isscalar(k) else [int(v) for v in k]
+    if len(st) != x.B or len(ks) != x.B or any(s < 0 or c < 0 or s + c > n for s, c, n in zip(st, ks, x.lengths)):
+        raise ValueError(f"delete_samples: {x.B} cuts [start, start + k) inside the clips are required; got start = {st}, "
+                         f"k = {ks} for lengths {list(x.lengths)}")
+    xin = x.data if x.data.dtype == torch.float32 else x.data.float()
+    out = Ragged(torch.empty(sum(x.lengths), dtype=torch.float32, device=xin.device), x.lengths)
+    sd = torch.tensor(st, dtype=torch.int32, device=xin.device)
+    kd = torch.tensor(ks, dtype=torch.int32, device=xin.device)
+    check(lib.aware_delete_samples(_ptr(xin), _ptr(x.d_off), _ptr(x.d_len), x.B, x.max_len, _ptr(sd), _ptr(kd), _ptr(out.data),
+                                   int(bool(adjoint)), _stream()), "aware_delete_samples")
+    return out
+
+
+def sync_select(values: torch.Tensor, n: int, centre: float = 0.0):
+    """detection.sync.sync_select on the device (aware_sync_select): values [B * n, L] float32, clip-major, the n candidate
+    views of each of the B clips -> (values [B, L] of the view with the largest mean |v - centre| per clip, the smallest j on
+    a tie; its index [B] int32; that mean [B] float32)."""
+    n = int(n)
+    if values.dim() != 2 or n < 1 or values.shape[0] % n or values.shape[0] == 0:
+        raise ValueError(f"sync_select: values [B * n, L] with n = {n} are required; got {tuple(values.shape)}")
+    v = values.contiguous().float()
+    B, L = v.shape[0] // n, v.shape[1]
+    out = torch.empty((B, L), dtype=torch.float32, device=v.device)
+    idx = torch.empty(B, dtype=torch.int32, device=v.device)
+    conf = torch.empty(B, dtype=torch.float32, device=v.device)
+    check(load_library().aware_sync_select(_ptr(v), B, n, L, float(centre), _ptr(out), _ptr(idx), _ptr(conf), _stream()),
+          "aware_sync_select")
+    return out, idx, conf
 
 
 def stretch_ola(x: Ragged, m, adjoint: bool = False, out_lengths=None) -> Ragged:

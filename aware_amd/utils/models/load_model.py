@@ -20,7 +20,9 @@ _EMBEDDER = {"pattern_mode": ("pattern_mode", "bits2bipolar"), "tolerance_db": (
              "loss": ("loss", "push_extremes"), "verbose": ("verbose", True),
              # EXTENSION (embedding/loop_attacks.py): attacks inside the optimisation loop; absent = none
              "loop_attacks": ("loop_attacks", None), "loop_attack_seed": ("loop_attack_seed", 0)}
-_DETECTOR = {"threshold": ("threshold", 0.0), "pattern_mode": ("pattern_mode", "bipolar")}
+_DETECTOR = {"threshold": ("threshold", 0.0), "pattern_mode": ("pattern_mode", "bipolar"),
+             # EXTENSION (detection/sync.py): offset search in detection; absent = off
+             "sync_search": ("sync_search", 0)}
 
 
 def _pick(card: dict, table: dict) -> dict:

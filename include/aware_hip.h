@@ -670,6 +670,43 @@ int aware_pv_frames(const void* spec, const int* frame_off, int B, const int* mq
 int aware_pv_frames_bwd(const void* spec, const void* grad_out, const int* frame_off, int B, const int* mq, void* grad_spec,
                         void* stream);
 
+/* ---- sample deletion inside the loop (EXTENSION, parity unpinned: the reference's Cropout / DeleteSamples are post-hoc) --------
+ * The _ex pair also accepts (the older entry point keeps refusing every kind above 1)
+ *   AWARE_LOOP_DELETE_SAMPLES, param = { k_lo, k_hi, at, 0 }: with r the entry's draw as above,
+ *     k = k_lo + ((r[2] * (k_hi - k_lo + 1)) >> 32) samples are cut out,
+ *     start = 0 for at = 0 (the reference's Cropout), (r[1] * (Ny_b - k)) >> 32 for at = 1 (its DeleteSamples);
+ *   on: z[i] = x[i] for i < start, x[i + k] for start <= i < Ny_b - k, 0 for i >= Ny_b - k.  The clip keeps its length: the
+ *   remainder moves up and zeros follow.  The backward pass is the exact adjoint in gather form: gx[i] = gz[i] for i < start,
+ *   0 for start <= i < start + k, gz[i - k] for i >= start + k.  Every value is a copy.  A noise entry behind it takes its
+ *   sigma from the shortened signal; a clip on which no entry of such a chain fires at a step leaves the bits of the loop
+ *   without a chain.
+ * AWARE_E_BADARG of the _ex setter, besides those above: a value that is not an integer, k_lo < 1, k_lo > k_hi, at other than
+ * 0 or 1, a second sample deletion, a sample deletion together with a reverberation, a speed change, a time stretch, a pitch
+ * shift or a phase vocoder (in either order).  AWARE_E_UNSUPPORTED: k_hi >= Ny_b for some clip, as for a sample suppression
+ * that is too long.  aware_embed_loop_attack_workspace_bytes_ex for a chain with the kind is that of the same chain with a
+ * speed change in its place; chains without the kind need what they needed.  aware_embed_buffer gains no index.  Added
+ * without a version step: callers detect the addition by symbol. */
+#define AWARE_LOOP_DELETE_SAMPLES 7      /* param = k_lo, k_hi, at (0: start, 1: anywhere), 0 */
+/* The same operator alone, on a ragged batch: clip b is len[b] floats at float offset off[b] of `in` and of `out` (dev int
+ * [B], any offsets, every length <= max_len <= 2^30); start and k dev int [B], read as k = min(max(k, 0), len) and
+ * start = min(max(start, 0), len - k); k = 0 is the identity.  adjoint 0: `in` holds x and `out` receives z.  adjoint 1: `in`
+ * holds gz and `out` receives gx.  in and out are distinct buffers.  One launch on `stream`.  AWARE_E_BADARG: a null
+ * argument, in == out, B < 1 or > 65535, max_len < 1 or > 2^30, adjoint outside 0..1 (checked before anything is launched). */
+int aware_delete_samples(const float* in, const int* off, const int* len, int B, int max_len, const int* start, const int* k,
+                         float* out, int adjoint, void* stream);
+
+/* ---- offset search in detection (EXTENSION, parity unpinned: the reference detects at the clip's own start only) -----------
+ * The detector pools pairs of frames of hop 256, so its read-out has a period of 512 samples in where the clip starts, and a
+ * clip whose first d samples are gone reads worse the nearer d mod 512 is to 256.  The host detects n views of each clip, view
+ * j with a further j * (512 / n) samples dropped (one aware_detect on a batch of B * n rows with overlapping in_offsets), and
+ * this entry keeps the best view per clip:
+ *   values [B][n][L] f32 (clip-major), c_j = mean_l |values[b][j][l] - centre| accumulated in f32 in one fixed order,
+ *   j* = the smallest j with the largest c_j;  out_values[b][0 : L] = values[b][j*], out_index[b] = j*, out_conf[b] = c_j*.
+ * centre is 0.5 for a sigmoid read-out and 0 otherwise.  One wave per clip, one launch on `stream`.  AWARE_E_BADARG: a null
+ * pointer, values == out_values, B outside 1..65535, n outside 1..64, L outside 1..65536, a non-finite centre. */
+int aware_sync_select(const float* values, int B, int n, int L, float centre, float* out_values, int* out_index,
+                      float* out_conf, void* stream);
+
 /* ---- bare GEMM (tests / roofline): C[M][N] = A[M][K] * Bt[N][K]^T + bias ------------------------------ */
 int aware_gemm_nt(const float* A, int lda, const float* Bt, int ldb, const float* bias, float* C, int ldc,
                   int M, int N, int K, void* stream);

@@ -1,8 +1,10 @@
-"""Attack-aware embedding (DESIGN.md sections 15 to 20): what a chain of loop attacks costs per iteration, and what it buys.
+"""Attack-aware embedding (DESIGN.md sections 15 to 21): what a chain of loop attacks costs per iteration, and what it buys.
 
   (a) config-3 batch (256 x 3 s): per-iteration time of the graph-replayed loop with no chain, noise only, suppression only,
-      both, reverberation only, reverberation followed by noise, speed change only, speed change followed by noise, time stretch only, time stretch followed by a speed change, pitch shift only and the phase vocoder with both modes, from device events over --steps steps (>= 200) after a warm-up, the variants alternating in one process
-      (--rounds rounds; the median over rounds is reported);
+      both, reverberation only, reverberation followed by noise, speed change only, speed change followed by noise, time stretch only, time stretch followed by a speed change, pitch shift only, the phase vocoder with both modes, sample deletion only and sample deletion between a suppression and noise, from device events over --steps steps (>= 200) after a warm-up, the variants alternating in one process
+      (--rounds rounds; the median over rounds is reported; --variants a,b,c measures those and `none` only);
+  (a') --sync n: the time of AWAREDetector.detect_batch's device work on that batch, trimmed by 256 samples, plain and with
+      sync_search = n (median of 10 calls after a warm-up);
   (b) the BER table at that size: 400-step embeddings without a chain, with noise at 10 dB and with 0.5 s suppression
       (prob 0.75), with the reverberation, the reverberation followed by noise and the speed change in the loop, then clean /
       Gaussian noise at 10 and 5 dB / 0.5 s and 0.3 s zeroed / reverberation of rt60 0.1 and 0.3 s / an echo of 100 ms x 0.7 /
@@ -37,7 +39,45 @@ VARIANTS = {
                       {"kind": "speed_change", "cents": 100.0, "prob": 0.75}],
     "pitch": [{"kind": "pitch_shift", "cents": 100.0, "prob": 0.75}],
     "phase_vocoder": [{"kind": "phase_vocoder", "rate": [0.85, 1.15], "cents": 150.0, "prob": 0.9}],
+    "delete": [{"kind": "delete_samples", "seconds": 0.032, "prob": 0.75}],
+    "suppression_delete_noise": [{"kind": "sample_suppression", "seconds": 0.3}, {"kind": "delete_samples", "seconds": [0.01, 0.2], "at": "anywhere", "prob": 0.75},
+                                 {"kind": "gaussian_noise", "snr_db": 10.0}],
 }
+
+
+def sync_timing(det, audio, B, n, views):
+    """us per call of the plain detection and of the offset search over `views` views, on the batch trimmed by 256 samples."""
+    from aware_amd.detection import sync
+    m = n - 256
+    flat = audio.view(B, n)[:, 256:].contiguous().view(-1)
+    plan = det._plan(16000)
+    dw = det.detection_net.device_weights(plan)
+    plain_batch = rt.Batch([m] * B)
+    per = max(1, sync.SYNC_MAX_ROWS // views)
+    vlen, voff = sync.sync_views([m] * B, views)
+    chunks = [rt.Batch(vlen[b0 * views:min(B, b0 + per) * views], [b * m + voff[b * views + j] for b in range(b0, min(B, b0 + per)) for j in range(views)])
+              for b0 in range(0, B, per)]
+
+    def plain():
+        return rt.detect(plan, dw, plain_batch, flat)
+
+    def search():
+        return [rt.sync_select(rt.detect(plan, dw, c, flat), views, det._centre()) for c in chunks]
+
+    out = {}
+    for name, fn in (("plain", plain), ("search", search)):
+        for _ in range(3):
+            fn()
+        ts = []
+        for _ in range(10):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            ts.append(1e3 * a.elapsed_time(b))
+        out[name] = round(float(np.median(ts)), 1)
+    return out
 
 
 def main():
@@ -49,6 +89,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--no-ber", action="store_true")
     ap.add_argument("--only-loop", action="store_true")
+    ap.add_argument("--variants", default="")
+    ap.add_argument("--sync", type=int, default=0)
     args = ap.parse_args()
     B, n = args.clips, int(args.seconds * 16000)
     emb, det = load()
@@ -60,12 +102,18 @@ def main():
     batch = rt.Batch([n] * B)
     result = {"clips": B, "seconds": args.seconds, "steps": args.steps}
 
+    if args.sync:
+        t = sync_timing(det, audio, B, n, args.sync)
+        result[f"us_per_detect/plain"], result[f"us_per_detect/sync_search_{args.sync}"] = t["plain"], t["search"]
+        print(f"detect: plain {t['plain']:.1f} us, sync_search = {args.sync}: {t['search']:.1f} us ({t['search'] / t['plain']:.2f} x)")
+    chosen = {"none"} | {v for v in args.variants.split(",") if v}
+    variants = {k: v for k, v in VARIANTS.items() if not args.variants or k in chosen}
     sessions = {}
-    for name, chain in VARIANTS.items():
+    for name, chain in variants.items():
         emb.loop_attacks = chain or []
         sessions[name] = emb.start_session(batch, 16000)
     steps = 16 if args.only_loop else args.steps
-    times = {name: [] for name in VARIANTS}
+    times = {name: [] for name in variants}
     for _ in range(1 if args.only_loop else args.rounds):
         for name, sess in sessions.items():
             sess.begin(audio, target)
@@ -76,11 +124,11 @@ def main():
             b.record()
             b.synchronize()
             times[name].append(1e3 * a.elapsed_time(b) / steps)
-    for name in VARIANTS:
+    for name in variants:
         result[f"us_per_iteration/{name}"] = round(float(np.median(times[name])), 2)
         print(f"{name:13s} {np.median(times[name]):8.1f} us per iteration (rounds: {', '.join(f'{t:.1f}' for t in times[name])})")
     base = result["us_per_iteration/none"]
-    for name in ("noise", "suppression", "both", "reverb", "reverb_noise", "speed", "speed_noise", "stretch", "stretch_speed", "pitch", "phase_vocoder"):
+    for name in [v for v in variants if v != "none"]:
         result[f"extra_us/{name}"] = round(result[f"us_per_iteration/{name}"] - base, 2)
     del sessions
 
