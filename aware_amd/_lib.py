@@ -14,7 +14,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AWARE_HIP_LIB") or os.path.join(_HERE, "libaware_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["capi.hip", "dsp_kernels.hip", "dsp_stream.hip", "seam_kernels.hip", "detector_kernels.hip", "gemm_x3.hip", "gemm_h2.hip", "attack_kernels.hip", "stft_any.hip", "stoi_kernels.hip", "loop_attack_kernels.hip", "loop_reverb_kernels.hip", "loop_speed_kernels.hip", "loop_stretch_kernels.hip", "loop_pitch_kernels.hip", "loop_pv_kernels.hip", "loop_delete_kernels.hip", "sync_kernels.hip"]
+SOURCES = ["capi.hip", "dsp_kernels.hip", "dsp_stream.hip", "seam_kernels.hip", "detector_kernels.hip", "gemm_x3.hip", "gemm_h2.hip", "attack_kernels.hip", "stft_any.hip", "stoi_kernels.hip", "loop_attack_kernels.hip", "loop_reverb_kernels.hip", "loop_speed_kernels.hip", "loop_stretch_kernels.hip", "loop_pitch_kernels.hip", "loop_pv_kernels.hip", "loop_delete_kernels.hip", "sync_kernels.hip", "loop_mix_kernels.hip"]
 
 AWARE_OK = 0
 ERRORS = {-1: "bad argument", -2: "unsupported configuration", -3: "HIP runtime error", -4: "workspace too small"}
@@ -78,6 +78,10 @@ class LoopAttack(C.Structure):
 
 class LoopAttackEx(C.Structure):
     _fields_ = [("kind", C.c_int), ("prob", C.c_float), ("param", C.c_float * 4)]
+
+
+class LoopChain(C.Structure):
+    _fields_ = [("attacks", C.POINTER(LoopAttackEx)), ("n_attacks", C.c_int), ("weight", C.c_float)]
 
 
 class OptimizerConfig(C.Structure):
@@ -145,6 +149,9 @@ SIGNATURES = {
     "aware_embed_set_loop_attacks": (_i, [_vp, C.POINTER(LoopAttack), _i, C.POINTER(C.c_uint32), _vp, _sz, _vp]),
     "aware_embed_loop_attack_workspace_bytes_ex": (_sz, [_vp, C.POINTER(LoopAttackEx), _i]),
     "aware_embed_set_loop_attacks_ex": (_i, [_vp, C.POINTER(LoopAttackEx), _i, C.POINTER(C.c_uint32), _vp, _sz, _vp]),
+    "aware_embed_loop_mixture_workspace_bytes": (_sz, [_vp, C.POINTER(LoopChain), _i]),
+    "aware_embed_set_loop_mixture": (_i, [_vp, C.POINTER(LoopChain), _i, C.POINTER(C.c_uint32), _vp, _sz, _vp]),
+    "aware_loop_mixture_draw": (_i, [_vp, _i, _i, C.POINTER(C.c_float), _i, _vp, _vp]),
     "aware_convolve_workspace_bytes": (_sz, [_i, _i, C.c_longlong, _i]),
     "aware_convolve": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _sz, _vp]),
     "aware_reverb_ir": (_i, [_vp, _i, _i, _i, _i, _i, _f, _vp, _i, _vp, _vp]),

@@ -1699,7 +1699,7 @@ struct aware_embed {
     } opt;
     // attack-aware embedding (aware_embed_set_loop_attacks; EXTENSION): the chain and its buffers in the caller's second
     // workspace.  n == 0: the loop issues exactly the launches of the plain loop
-    struct {
+    struct LoopChainState {
         int n = 0;
         int kind[kMaxLoopAttacks] = {0}, k[kMaxLoopAttacks] = {0};
         double inv_snr[kMaxLoopAttacks] = {0};
@@ -1738,8 +1738,18 @@ struct aware_embed {
         int ds = -1, d_lo = 0, d_hi = 0, d_at = 0;
         const float* hann = nullptr;              // stretch_window()
         bool locked = false;                      // an optimiser step has run: the chain stays what it is
+        LoopGate gate;                            // a chain of a mixture: the clips that drew it (null: every clip)
     } la;
+    // attack mixtures (aware_embed_set_loop_mixture; EXTENSION): mix_n chains, one drawn per clip and step into mix_choice.
+    // Every clip belongs to one chain at a step, so the chains share z, pmaxZ, psq, pdot, gpad0, seeds and u -- those of `la`,
+    // whose n stays 0 -- and keep only what a backward pass needs from its forward pass (mix[c].h .. xspec, pvS, pvY, v)
+    int mix_n = 0;
+    LoopChainState mix[kMaxLoopChains];
+    unsigned long long mix_thr[kMaxLoopChains] = {0};
+    int* mix_choice = nullptr;                    // [B]
+    int mix_rv = -1;                              // the chain with the reverberation (aware_embed_buffer 13), -1 without one
 };
+using LoopChainState = aware_embed::LoopChainState;
 
 // the embed loop's workspace: the detector's buffers, then the loop state; iters: num_iterations, l1: the L1 term's buffers
 static void carve_embed(Carver& c, const aware_batch* b, const aware_detector* det, int iters, bool l1, aware_embed* e) {
@@ -2006,18 +2016,13 @@ extern "C" size_t aware_embed_loop_attack_workspace_bytes_ex(const aware_batch* 
         carve_loop_speed(c, b, e.la);
     return c.off;
 }
-static int set_loop_attacks(aware_embed* e, const aware_loop_attack_ex* attacks, int n_attacks, bool ex,
-                            const uint32_t* seeds, void* workspace, size_t workspace_bytes, void* stream) {
+// one chain's entries into its state: every AWARE_E_BADARG / AWARE_E_UNSUPPORTED of the setters, no buffer touched
+static int parse_loop_chain(const aware_batch* b, const aware_loop_attack_ex* attacks, int n_attacks, bool ex, LoopChainState& la) {
     static_assert(AWARE_LOOP_GAUSSIAN_NOISE == kLoopGaussianNoise && AWARE_LOOP_SAMPLE_SUPPRESSION == kLoopSampleSuppression &&
                   AWARE_LOOP_REVERBERATION == kLoopReverberation && AWARE_LOOP_SPEED_CHANGE == kLoopSpeedChange &&
                   AWARE_LOOP_TIME_STRETCH == kLoopTimeStretch && AWARE_LOOP_PITCH_SHIFT == kLoopPitchShift &&
                   AWARE_LOOP_PHASE_VOCODER == kLoopPhaseVocoder && AWARE_LOOP_DELETE_SAMPLES == kLoopDeleteSamples, "");
-    if (!e || n_attacks < 0 || n_attacks > kMaxLoopAttacks) return AWARE_E_BADARG;
-    if (e->gexec || e->la.locked) return AWARE_E_BADARG;          // before the first aware_embed_iterate, as aware_embed_set_optimizer
-    if (n_attacks == 0) { e->la.n = 0; e->la.z = nullptr; e->la.rv = -1; e->la.sp = -1; e->la.ts = -1; e->la.ps = -1; e->la.pv = -1; e->la.ds = -1; e->la.h = nullptr; return AWARE_OK; }
-    if (!attacks || !seeds || !workspace || ((uintptr_t)workspace & 255)) return AWARE_E_BADARG;
-    const aware_batch* b = e->b;
-    auto la = e->la;
+    if (!attacks || n_attacks < 1 || n_attacks > kMaxLoopAttacks) return AWARE_E_BADARG;
     la.rv = -1; la.sp = -1; la.ts = -1; la.ps = -1; la.pv = -1; la.ds = -1; la.h = nullptr; la.v = nullptr;
     for (int j = 0; j < n_attacks; ++j) {
         const aware_loop_attack_ex& a = attacks[j];
@@ -2085,6 +2090,23 @@ static int set_loop_attacks(aware_embed* e, const aware_loop_attack_ex* attacks,
             if ((la.kind[j] == AWARE_LOOP_SAMPLE_SUPPRESSION && la.k[j] >= b->out_len[i]) ||
                 (la.kind[j] == AWARE_LOOP_DELETE_SAMPLES && la.d_hi >= b->out_len[i]))
                 return AWARE_E_UNSUPPORTED;
+    la.n = n_attacks;
+    return AWARE_OK;
+}
+static void clear_loop_chain(aware_embed* e) {
+    e->la.n = 0; e->la.z = nullptr; e->la.rv = -1; e->la.sp = -1; e->la.ts = -1; e->la.ps = -1; e->la.pv = -1; e->la.ds = -1; e->la.h = nullptr;
+    e->mix_n = 0; e->mix_choice = nullptr; e->mix_rv = -1;
+}
+static int set_loop_attacks(aware_embed* e, const aware_loop_attack_ex* attacks, int n_attacks, bool ex,
+                            const uint32_t* seeds, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!e || n_attacks < 0 || n_attacks > kMaxLoopAttacks) return AWARE_E_BADARG;
+    if (e->gexec || e->la.locked) return AWARE_E_BADARG;          // before the first aware_embed_iterate, as aware_embed_set_optimizer
+    if (n_attacks == 0) { clear_loop_chain(e); return AWARE_OK; }
+    if (!attacks || !seeds || !workspace || ((uintptr_t)workspace & 255)) return AWARE_E_BADARG;
+    const aware_batch* b = e->b;
+    auto la = e->la;
+    la.gate = LoopGate();
+    if (int rc = parse_loop_chain(b, attacks, n_attacks, ex, la)) return rc;
     Carver c(workspace, workspace_bytes);
     carve_loop_attacks(c, b, la);
     if (la.rv >= 0) carve_loop_reverb(c, b, la);
@@ -2105,6 +2127,7 @@ static int set_loop_attacks(aware_embed* e, const aware_loop_attack_ex* attacks,
     HIPCHK(hipStreamSynchronize(st));
     la.n = n_attacks;
     e->la = la;
+    e->mix_n = 0; e->mix_choice = nullptr; e->mix_rv = -1;          // a plain chain replaces a mixture
     return AWARE_OK;
 }
 extern "C" int aware_embed_set_loop_attacks(aware_embed* e, const aware_loop_attack* attacks, int n_attacks,
@@ -2118,6 +2141,132 @@ extern "C" int aware_embed_set_loop_attacks(aware_embed* e, const aware_loop_att
 extern "C" int aware_embed_set_loop_attacks_ex(aware_embed* e, const aware_loop_attack_ex* attacks, int n_attacks,
                                                const uint32_t* seeds, void* workspace, size_t workspace_bytes, void* stream) {
     return set_loop_attacks(e, attacks, n_attacks, true, seeds, workspace, workspace_bytes, stream);
+}
+
+// ---- attack mixtures (EXTENSION): one of several chains drawn per clip and step (loop_mix_kernels.hip)
+static bool chain_splits(const LoopChainState& la) {
+    return la.rv >= 0 || la.sp >= 0 || la.ts >= 0 || la.ps >= 0 || la.pv >= 0 || la.ds >= 0;
+}
+// The mixture's workspace: what the chains share (the buffers of a chain of kinds 0/1, and the one signal u if a chain has a
+// kind that splits it), then per chain what its backward pass needs from its forward pass, then the choices.  For one chain
+// this is the layout of aware_embed_set_loop_attacks_ex followed by int [B] at the next 256-byte boundary.
+static void carve_loop_mixture(Carver& c, const aware_batch* b, LoopChainState& shared, LoopChainState* mix, int n, int*& choice) {
+    carve_loop_attacks(c, b, shared);
+    bool any_u = false;
+    for (int i = 0; i < n; ++i) any_u = any_u || chain_splits(mix[i]);
+    shared.u = any_u ? c.take<float>(b->NS) : nullptr;
+    for (int i = 0; i < n; ++i) {
+        LoopChainState& la = mix[i];
+        la.z = shared.z; la.pmaxZ = shared.pmaxZ; la.psq = shared.psq; la.pdot = shared.pdot; la.gpad0 = shared.gpad0;
+        la.seeds = shared.seeds; la.u = shared.u;
+        if (la.rv >= 0) {
+            la.kmax = reverb_kmax(b);
+            la.h = c.take<float>((size_t)b->B * kReverbMaxIr);
+            la.nh = c.take<int>(b->B);
+            la.tables = c.take<cf>(kReverbTwHalf + kReverbBins);
+            la.hspec = c.take<cf>((size_t)b->B * kReverbParts * kReverbBins);
+            la.xspec = c.take<cf>((size_t)b->B * la.kmax * kReverbBins);
+        } else if (la.pv >= 0) {
+            la.pvS = c.take<cf>((size_t)b->NF * 520);
+            la.pvY = c.take<cf>((size_t)b->NF * 520);
+        } else if (la.ts >= 0 && la.sp >= 0) {
+            la.v = c.take<float>(b->NS);
+        }
+    }
+    choice = c.take<int>(b->B);
+}
+// the chains and weights into states and thresholds; rc as the setter's
+static int parse_loop_mixture(const aware_batch* b, const aware_loop_chain* chains, int n_chains, LoopChainState* mix,
+                              unsigned long long* thr, int& mix_rv) {
+    if (!b || b->general || !chains || n_chains < 1 || n_chains > kMaxLoopChains) return AWARE_E_BADARG;
+    float w[kMaxLoopChains] = {0};
+    double sum = 0.0;
+    mix_rv = -1;
+    for (int i = 0; i < n_chains; ++i) {
+        if (!std::isfinite(chains[i].weight) || chains[i].weight < 0.f) return AWARE_E_BADARG;
+        w[i] = chains[i].weight; sum += (double)w[i];
+        mix[i] = LoopChainState();
+        if (int rc = parse_loop_chain(b, chains[i].attacks, chains[i].n_attacks, true, mix[i])) return rc;
+        if (mix[i].rv >= 0) {
+            if (mix_rv >= 0) return AWARE_E_BADARG;            // one reverberation chain per mixture: aware_embed_buffer 13 is its responses
+            mix_rv = i;
+        }
+    }
+    if (sum > 1.0 + 1e-6) return AWARE_E_BADARG;
+    loop_mix_thresholds(w, n_chains, thr);
+    return AWARE_OK;
+}
+extern "C" size_t aware_embed_loop_mixture_workspace_bytes(const aware_batch* b, const aware_loop_chain* chains, int n_chains) {
+    LoopChainState shared, mix[kMaxLoopChains];
+    unsigned long long thr[kMaxLoopChains];
+    int rv = -1, *choice = nullptr;
+    int rc = parse_loop_mixture(b, chains, n_chains, mix, thr, rv);
+    if (rc != AWARE_OK && rc != AWARE_E_UNSUPPORTED) return 0;
+    Carver c(nullptr, 0);
+    carve_loop_mixture(c, b, shared, mix, n_chains, choice);
+    return c.off;
+}
+extern "C" int aware_embed_set_loop_mixture(aware_embed* e, const aware_loop_chain* chains, int n_chains, const uint32_t* seeds,
+                                            void* workspace, size_t workspace_bytes, void* stream) {
+    if (!e || n_chains < 0 || n_chains > kMaxLoopChains) return AWARE_E_BADARG;
+    if (e->gexec || e->la.locked) return AWARE_E_BADARG;          // before the first aware_embed_iterate, as the chain's setter
+    if (n_chains == 0) { clear_loop_chain(e); return AWARE_OK; }
+    if (!chains || !seeds || !workspace || ((uintptr_t)workspace & 255)) return AWARE_E_BADARG;
+    const aware_batch* b = e->b;
+    LoopChainState shared, mix[kMaxLoopChains];
+    unsigned long long thr[kMaxLoopChains];
+    int rv = -1, *choice = nullptr;
+    if (int rc = parse_loop_mixture(b, chains, n_chains, mix, thr, rv)) return rc;
+    Carver c(workspace, workspace_bytes);
+    carve_loop_mixture(c, b, shared, mix, n_chains, choice);
+    if (!c.ok) return AWARE_E_WORKSPACE;
+    const float* hann = nullptr;
+    for (int i = 0; i < n_chains; ++i)
+        if ((mix[i].ts >= 0 || mix[i].ps >= 0) && !hann && !(hann = stretch_window())) return AWARE_E_HIP;
+    hipStream_t st = (hipStream_t)stream;
+    HIPCHK(hipMemsetAsync(shared.gpad0, 0, (size_t)b->B * 1024 * sizeof(float), st));
+    HIPCHK(hipMemcpyAsync(shared.seeds, seeds, (size_t)b->B * sizeof(unsigned), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)choice, -1, b->B, st));
+    // a clip reaches a chain's stage only at the steps it draws the chain: the signals in between start as zeros, so that
+    // a kernel that is not gated per clip (none today) would read numbers, and the responses of a clip that never drew
+    // the reverberation chain read as zeros
+    HIPCHK(hipMemsetAsync(shared.z, 0, (size_t)b->NS * sizeof(float), st));
+    if (shared.u) HIPCHK(hipMemsetAsync(shared.u, 0, (size_t)b->NS * sizeof(float), st));
+    for (int i = 0; i < n_chains; ++i) {
+        LoopChainState& la = mix[i];
+        la.hann = hann;
+        la.gate.choice = choice; la.gate.chain = i;
+        if (la.rv >= 0) {
+            const std::vector<cf>& t = reverb_tables();
+            HIPCHK(hipMemcpyAsync(la.tables, t.data(), t.size() * sizeof(cf), hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemsetAsync(la.h, 0, (size_t)b->B * kReverbMaxIr * sizeof(float), st));
+            HIPCHK(hipMemsetAsync(la.nh, 0, (size_t)b->B * sizeof(int), st));
+        }
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    clear_loop_chain(e);                                           // a mixture replaces a plain chain
+    const bool locked = e->la.locked;
+    e->la = shared; e->la.n = 0; e->la.locked = locked;
+    for (int i = 0; i < n_chains; ++i) { e->mix[i] = mix[i]; e->mix_thr[i] = thr[i]; }
+    e->mix_n = n_chains; e->mix_choice = choice; e->mix_rv = rv;
+    return AWARE_OK;
+}
+// the draw alone: choice[b] for B clips at `step`, weights on the host
+extern "C" int aware_loop_mixture_draw(const uint32_t* seeds, int B, int step, const float* weights, int n_chains, int* choice,
+                                       void* stream) {
+    if (!seeds || !weights || !choice || B < 1 || n_chains < 1 || n_chains > kMaxLoopChains) return AWARE_E_BADARG;
+    double sum = 0.0;
+    for (int i = 0; i < n_chains; ++i) {
+        if (!std::isfinite(weights[i]) || weights[i] < 0.f) return AWARE_E_BADARG;
+        sum += (double)weights[i];
+    }
+    if (sum > 1.0 + 1e-6) return AWARE_E_BADARG;
+    LoopMixDrawLaunch D;
+    D.seeds = seeds; D.step_imm = step; D.B = B; D.n = n_chains; D.choice = choice;
+    loop_mix_thresholds(weights, n_chains, D.thr);
+    launch_loop_mix_draw(D, (hipStream_t)stream);
+    LAUNCHCHK();
+    return AWARE_OK;
 }
 
 // ---- the convolution and the impulse-response draw alone (EXTENSION; attacks.Reverberation, tests) ------------------------
@@ -2275,8 +2424,11 @@ extern "C" void* aware_embed_buffer(aware_embed* e, int which) {
         case 9: return e->yraw;
         case 10: return e->mag;
         case 11: return e->opt.active ? e->opt.d_lr : nullptr;      // per-clip learning rate (double; ReduceLROnPlateau state)
-        case 12: return e->la.n ? e->la.z : nullptr;                // the attacked signal of the last forward pass
-        case 13: return (e->la.n && e->la.rv >= 0) ? e->la.h : nullptr;      // its impulse responses, f32 [B][8192]
+        case 12: return (e->la.n || e->mix_n) ? e->la.z : nullptr;  // the attacked signal of the last forward pass
+        case 13:                                                    // its impulse responses, f32 [B][8192]
+            if (e->mix_n) return e->mix_rv >= 0 ? e->mix[e->mix_rv].h : nullptr;
+            return (e->la.n && e->la.rv >= 0) ? e->la.h : nullptr;
+        case 14: return e->mix_n ? e->mix_choice : nullptr;         // a mixture's choices of the last forward pass, int [B]
         default: return nullptr;
     }
 }
@@ -2319,54 +2471,53 @@ extern "C" int aware_embed_begin(aware_embed* e, const float* audio, const float
     return AWARE_OK;
 }
 
-static SpeedLaunch speed_launch(const aware_embed* e, const float* in, float* out, int adjoint, int step_back) {
-    const auto& la = e->la;
+static SpeedLaunch speed_launch(const aware_embed* e, const LoopChainState& la, const float* in, float* out, int adjoint, int step_back) {
     SpeedLaunch S;
     S.in = in; S.out = out; S.B = e->b->B; S.adjoint = adjoint; S.frame_off = e->b->d_frame_off; S.pstride = e->b->pstride;
     S.run_blocks = e->b->synth_run; S.step = e->step; S.step_back = step_back; S.seeds = la.seeds; S.entry = la.sp;
     S.m_lo = la.m_lo; S.m_hi = la.m_hi; S.prob = la.prob[la.sp];
+    S.gate = la.gate;
     return S;
 }
 
-static DeleteLaunch delete_launch(const aware_embed* e, const float* in, float* out, int adjoint, int step_back) {
-    const auto& la = e->la;
+static DeleteLaunch delete_launch(const aware_embed* e, const LoopChainState& la, const float* in, float* out, int adjoint, int step_back) {
     DeleteLaunch S;
     S.in = in; S.out = out; S.B = e->b->B; S.adjoint = adjoint; S.frame_off = e->b->d_frame_off; S.pstride = e->b->pstride;
     S.run_blocks = e->b->synth_run; S.step = e->step; S.step_back = step_back; S.seeds = la.seeds; S.entry = la.ds;
     S.k_lo = la.d_lo; S.k_hi = la.d_hi; S.at = la.d_at; S.prob = la.prob[la.ds];
+    S.gate = la.gate;
     return S;
 }
 
-static StretchLaunch stretch_launch(const aware_embed* e, const float* in, float* out, int adjoint, int step_back) {
-    const auto& la = e->la;
+static StretchLaunch stretch_launch(const aware_embed* e, const LoopChainState& la, const float* in, float* out, int adjoint, int step_back) {
     StretchLaunch S;
     S.in = in; S.out = out; S.window = la.hann; S.B = e->b->B; S.adjoint = adjoint; S.frame_off = e->b->d_frame_off;
     S.pstride = e->b->pstride; S.run_blocks = e->b->synth_run; S.step = e->step; S.step_back = step_back; S.seeds = la.seeds;
     S.entry = la.ts; S.m_lo = la.q_lo; S.m_hi = la.q_hi; S.prob = la.prob[la.ts];
+    S.gate = la.gate;
     return S;
 }
 
-static PitchLaunch pitch_launch(const aware_embed* e, const float* in, float* out, int adjoint, int step_back) {
-    const auto& la = e->la;
+static PitchLaunch pitch_launch(const aware_embed* e, const LoopChainState& la, const float* in, float* out, int adjoint, int step_back) {
     PitchLaunch S;
     S.in = in; S.out = out; S.window = la.hann; S.B = e->b->B; S.adjoint = adjoint; S.frame_off = e->b->d_frame_off;
     S.pstride = e->b->pstride; S.run_blocks = e->b->synth_run; S.step = e->step; S.step_back = step_back; S.seeds = la.seeds;
     S.entry = la.ps; S.m_lo = la.p_lo; S.m_hi = la.p_hi; S.prob = la.prob[la.ps];
+    S.gate = la.gate;
     return S;
 }
 
 // the phase vocoder's stage (kind 6).  Forward: STFT of u, the frames, iSTFT into `tmp`, u itself for the clips the entry leaves
 // alone, the resampling of tmp into z.  The transforms are what aware_stft / aware_istft launch, on the loop's signal layout.
-static PvLaunch pv_launch(const aware_embed* e, int step_back) {
-    const auto& la = e->la;
+static PvLaunch pv_launch(const aware_embed* e, const LoopChainState& la, int step_back) {
     PvLaunch P;
     P.frame_off = e->b->d_frame_off; P.B = e->b->B; P.pstride = e->b->pstride; P.run_blocks = e->b->synth_run;
     P.step = e->step; P.step_back = step_back; P.seeds = la.seeds; P.entry = la.pv; P.prob = la.prob[la.pv];
     P.q_lo = la.pq_lo; P.q_hi = la.pq_hi; P.m_lo = la.pm_lo; P.m_hi = la.pm_hi;
+    P.gate = la.gate;
     return P;
 }
-static SpeedLaunch pv_speed_launch(const aware_embed* e, const float* in, float* out, int adjoint, int step_back) {
-    const auto& la = e->la;
+static SpeedLaunch pv_speed_launch(const aware_embed* e, const LoopChainState& la, const float* in, float* out, int adjoint, int step_back) {
     SpeedLaunch S;
     S.in = in; S.out = out; S.B = e->b->B; S.adjoint = adjoint; S.frame_off = e->b->d_frame_off; S.pstride = e->b->pstride;
     S.run_blocks = e->b->synth_run; S.step = e->step; S.step_back = step_back; S.seeds = la.seeds; S.entry = la.pv;
@@ -2374,55 +2525,167 @@ static SpeedLaunch pv_speed_launch(const aware_embed* e, const float* in, float*
     const bool has_m = la.pm_lo <= la.pm_hi;
     S.m_lo = has_m ? la.pm_lo : 0; S.m_hi = has_m ? la.pm_hi : 0;      // stretch mode alone: m = 0, the identity
     S.coin = has_m && la.pq_lo <= la.pq_hi;
+    S.gate = la.gate;
     return S;
 }
-static void pv_stage_forward(const aware_embed* e, float* tmp, hipStream_t st) {
+static void pv_stage_forward(const aware_embed* e, const LoopChainState& la, float* tmp, hipStream_t st) {
     const aware_batch* b = e->b;
-    const auto& la = e->la;
     AnalysisLaunch L;
     L.plan = e->plan->dev; L.frame_off = b->d_frame_off; L.B = b->B; L.max_frames = b->max_frames; L.run_frames = b->an_run; L.wg_tab = b->d_an_wg; L.n_wg = b->n_an_wg;
     L.sig = la.u; L.sig_off = b->d_out_off; L.sig_len = b->d_out_len; L.pcount = b->d_pc_syn; L.pstride = b->pstride;
-    L.full = la.pvS;
+    L.full = la.pvS; L.gate = la.gate;
     launch_analysis(L, st);
-    PvLaunch P = pv_launch(e, 0);
+    PvLaunch P = pv_launch(e, la, 0);
     P.spec = la.pvS; P.out = la.pvY;
     launch_pv_frames(P, 0, st);
     SynthLaunch S;
     S.plan = e->plan->dev; S.frame_off = b->d_frame_off; S.B = b->B; S.max_frames = b->max_frames; S.run_blocks = b->synth_run; S.wg_tab = b->d_syn_wg; S.n_wg = b->n_syn_wg;
-    S.full = la.pvY; S.out = tmp; S.pstride = b->pstride;
+    S.full = la.pvY; S.out = tmp; S.pstride = b->pstride; S.gate = la.gate;
     launch_synth(S, st);
     launch_pv_idle(P, la.u, tmp, st);
-    launch_speed_change(pv_speed_launch(e, tmp, la.z, 0, 0), st);
+    launch_speed_change(pv_speed_launch(e, la, tmp, la.z, 0, 0), st);
 }
 // The mirror: gz in u -> the resampling's adjoint into gy, the iSTFT's adjoint into the Y buffer, the frames' backward into the
 // S buffer, the STFT's adjoint into gy, and gz itself for the clips the entry left alone
-static void pv_stage_backward(const aware_embed* e, int step_back, hipStream_t st) {
+static void pv_stage_backward(const aware_embed* e, const LoopChainState& la, int step_back, hipStream_t st) {
     const aware_batch* b = e->b;
-    const auto& la = e->la;
-    launch_speed_change(pv_speed_launch(e, la.u, e->gy, 1, step_back), st);
+    launch_speed_change(pv_speed_launch(e, la, la.u, e->gy, 1, step_back), st);
     AnalysisLaunch L;
     L.plan = e->plan->dev; L.frame_off = b->d_frame_off; L.B = b->B; L.max_frames = b->max_frames; L.run_frames = b->an_run; L.wg_tab = b->d_an_wg; L.n_wg = b->n_an_wg;
     L.sig = e->gy; L.sig_off = b->d_out_off; L.sig_len = b->d_out_len; L.pcount = b->d_pc_syn; L.pstride = b->pstride;
-    L.full = la.pvY; L.adjoint = 1;
+    L.full = la.pvY; L.adjoint = 1; L.gate = la.gate;
     launch_analysis(L, st);
-    PvLaunch P = pv_launch(e, step_back);
+    PvLaunch P = pv_launch(e, la, step_back);
     P.spec = la.pvS; P.grad = la.pvY; P.out = la.pvS;
     launch_pv_frames(P, 1, st);
     SynthLaunch S;
     S.plan = e->plan->dev; S.frame_off = b->d_frame_off; S.B = b->B; S.max_frames = b->max_frames; S.run_blocks = b->synth_run; S.wg_tab = b->d_syn_wg; S.n_wg = b->n_syn_wg;
-    S.full = la.pvS; S.out = e->gy; S.adjoint = 1; S.pstride = b->pstride;
+    S.full = la.pvS; S.out = e->gy; S.adjoint = 1; S.pstride = b->pstride; S.gate = la.gate;
     S.sig_off = b->d_out_off; S.sig_len = b->d_out_len;
     launch_synth(S, st);
     launch_pv_idle(P, la.u, e->gy, st);
 }
 
-static ConvolveLaunch reverb_launch(const aware_embed* e, const float* in, float* out, int adjoint) {
-    const auto& la = e->la;
+static ConvolveLaunch reverb_launch(const aware_embed* e, const LoopChainState& la, const float* in, float* out, int adjoint) {
     ConvolveLaunch C;
     C.tables = la.tables; C.in = in; C.out = out; C.frame_off = e->b->d_frame_off; C.B = e->b->B; C.kmax = la.kmax;
     C.h = la.h; C.h_stride = kReverbMaxIr; C.nh = la.nh; C.parts = kReverbParts; C.adjoint = adjoint; C.skip_h = adjoint;
     C.hspec = la.hspec; C.xspec = la.xspec;
+    C.gate = la.gate;
     return C;
+}
+
+// the launch struct of one chain's stage kernels: the chain of a plain handle, or chain c of a mixture behind its gate
+static LoopAttackLaunch chain_stage_launch(const aware_embed* e, const LoopChainState& la) {
+    const aware_batch* b = e->b;
+    LoopAttackLaunch A;
+    A.frame_off = b->d_frame_off; A.pcount = b->d_pc_syn; A.B = b->B; A.pstride = b->pstride; A.run_blocks = b->synth_run;
+    A.step = e->step; A.seeds = la.seeds; A.n = la.n;
+    for (int j = 0; j < la.n; ++j) { A.kind[j] = la.kind[j]; A.k[j] = la.k[j]; A.inv_snr[j] = la.inv_snr[j]; A.prob[j] = la.prob[j]; }
+    A.yraw = e->yraw; A.pmaxY = e->pmaxY; A.psq = la.psq; A.z = la.z; A.pmaxZ = la.pmaxZ;
+    if (la.rv >= 0 || la.sp >= 0 || la.ts >= 0 || la.ps >= 0 || la.pv >= 0 || la.ds >= 0) { A.idle_plain = 1; A.gpad_out = la.gpad0; }
+    // inside a mixture the pads are shared between the chains: a chain of kinds 0/1 has no idle rule, and writes the zeros
+    // its clips' pads hold on a plain handle
+    if (la.gate.choice) A.gpad_out = la.gpad0;
+    A.gate = la.gate;
+    return A;
+}
+// one chain's forward half: x = N(N(yraw)) -> z and its partial maxima
+static void chain_forward(const aware_embed* e, const LoopChainState& la, const LoopAttackLaunch& A, hipStream_t st) {
+    const aware_batch* b = e->b;
+    if (la.ts >= 0) {
+        // the entries in front of the stretch on N(N(yraw)), the overlap-add (and the resampling of a speed change
+        // directly behind it), the entries behind
+        const bool pair = la.sp >= 0;
+        launch_loop_attack_stage(A, 0, la.ts, e->yraw, 1, la.u, nullptr, st);
+        launch_time_stretch(stretch_launch(e, la, la.u, pair ? la.v : la.z, 0, 0), st);
+        if (pair) launch_speed_change(speed_launch(e, la, la.v, la.z, 0, 0), st);
+        launch_loop_attack_stage(A, (pair ? la.sp : la.ts) + 1, la.n, la.z, 0, la.z, la.pmaxZ, st);
+    } else if (la.sp >= 0) {
+        // the entries in front of the speed change on N(N(yraw)), the resampling, the entries behind it
+        launch_loop_attack_stage(A, 0, la.sp, e->yraw, 1, la.u, nullptr, st);
+        launch_speed_change(speed_launch(e, la, la.u, la.z, 0, 0), st);
+        launch_loop_attack_stage(A, la.sp + 1, la.n, la.z, 0, la.z, la.pmaxZ, st);
+    } else if (la.ps >= 0) {
+        // the same shape: the entries in front of the pitch shift on N(N(yraw)), the fused stretch and resampling, the
+        // entries behind it
+        launch_loop_attack_stage(A, 0, la.ps, e->yraw, 1, la.u, nullptr, st);
+        launch_pitch_shift(pitch_launch(e, la, la.u, la.z, 0, 0), st);
+        launch_loop_attack_stage(A, la.ps + 1, la.n, la.z, 0, la.z, la.pmaxZ, st);
+    } else if (la.pv >= 0) {
+        // the same shape again: the entries in front of the phase vocoder on N(N(yraw)), its stage (gy is free until the
+        // synthesis adjoint writes it, and carries the vocoded signal to the resampling), the entries behind it
+        launch_loop_attack_stage(A, 0, la.pv, e->yraw, 1, la.u, nullptr, st);
+        pv_stage_forward(e, la, e->gy, st);
+        launch_loop_attack_stage(A, la.pv + 1, la.n, la.z, 0, la.z, la.pmaxZ, st);
+    } else if (la.ds >= 0) {
+        // the same shape: the entries in front of the deletion on N(N(yraw)), the gather, the entries behind it
+        launch_loop_attack_stage(A, 0, la.ds, e->yraw, 1, la.u, nullptr, st);
+        launch_delete_samples(delete_launch(e, la, la.u, la.z, 0, 0), st);
+        launch_loop_attack_stage(A, la.ds + 1, la.n, la.z, 0, la.z, la.pmaxZ, st);
+    } else if (la.rv < 0) {
+        launch_loop_attack_forward(A, st);
+    } else {
+        // the entries in front of the reverberation on N(N(yraw)), the convolution, the entries behind it
+        launch_loop_attack_stage(A, 0, la.rv, e->yraw, 1, la.u, nullptr, st);
+        ReverbIrLaunch R;
+        R.seeds = la.seeds; R.step = e->step; R.entry = la.rv; R.B = b->B; R.n_lo = la.n_lo; R.n_hi = la.n_hi;
+        R.gain = la.gain; R.prob = la.prob[la.rv]; R.h = la.h; R.h_stride = kReverbMaxIr; R.nh = la.nh; R.gate = la.gate;
+        launch_reverb_ir(R, st);
+        launch_convolve(reverb_launch(e, la, la.u, la.z, 0), st);
+        launch_loop_attack_stage(A, la.rv + 1, la.n, la.z, 0, la.z, la.pmaxZ, st);
+    }
+}
+// its mirror: gy, dL/d N(N(z)) -> dL/dx, the partial sums against x and the reflect pads for the analysis adjoint
+static void chain_backward(const aware_embed* e, const LoopChainState& la, LoopAttackLaunch& A, hipStream_t st) {
+    if (la.ts >= 0) {
+        // the mirror: normalisers at z and the masks behind the stage into u, the gather-form adjoints (of the speed
+        // change into v, of the stretch into gy), the masks in front and the partial sums against x
+        const bool pair = la.sp >= 0;
+        A.gy_out = la.u;
+        launch_loop_attack_stage_bwd(A, (pair ? la.sp : la.ts) + 1, la.n, 1, 0, st);
+        A.gy_out = nullptr;
+        if (pair) launch_speed_change(speed_launch(e, la, la.u, la.v, 1, A.step_back), st);
+        launch_time_stretch(stretch_launch(e, la, pair ? la.v : la.u, e->gy, 1, A.step_back), st);
+        launch_loop_attack_stage_bwd(A, 0, la.ts, 0, 1, st);
+    } else if (la.sp >= 0) {
+        // the mirror: normalisers at z and the masks behind the speed change into u (the forward pass is done with
+        // it), the gather-form adjoint back into gy, the masks in front of it and the partial sums against x
+        A.gy_out = la.u;
+        launch_loop_attack_stage_bwd(A, la.sp + 1, la.n, 1, 0, st);
+        A.gy_out = nullptr;
+        launch_speed_change(speed_launch(e, la, la.u, e->gy, 1, A.step_back), st);
+        launch_loop_attack_stage_bwd(A, 0, la.sp, 0, 1, st);
+    } else if (la.ps >= 0) {
+        // the mirror, as for the speed change: into u, the fused gather-form adjoint back into gy, the stage in front
+        A.gy_out = la.u;
+        launch_loop_attack_stage_bwd(A, la.ps + 1, la.n, 1, 0, st);
+        A.gy_out = nullptr;
+        launch_pitch_shift(pitch_launch(e, la, la.u, e->gy, 1, A.step_back), st);
+        launch_loop_attack_stage_bwd(A, 0, la.ps, 0, 1, st);
+    } else if (la.pv >= 0) {
+        // the mirror: into u, the stage's backward into gy, the stage in front
+        A.gy_out = la.u;
+        launch_loop_attack_stage_bwd(A, la.pv + 1, la.n, 1, 0, st);
+        A.gy_out = nullptr;
+        pv_stage_backward(e, la, A.step_back, st);
+        launch_loop_attack_stage_bwd(A, 0, la.pv, 0, 1, st);
+    } else if (la.ds >= 0) {
+        // the mirror, as for the speed change: into u, the gather-form adjoint back into gy, the stage in front
+        A.gy_out = la.u;
+        launch_loop_attack_stage_bwd(A, la.ds + 1, la.n, 1, 0, st);
+        A.gy_out = nullptr;
+        launch_delete_samples(delete_launch(e, la, la.u, e->gy, 1, A.step_back), st);
+        launch_loop_attack_stage_bwd(A, 0, la.ds, 0, 1, st);
+    } else if (la.rv < 0) {
+        launch_loop_attack_backward(A, st);
+    } else {
+        // the mirror: normalisers at z and the masks behind the reverberation, the correlation with the same
+        // responses (their spectra are still there), the masks in front of it and the partial sums against x
+        launch_loop_attack_stage_bwd(A, la.rv + 1, la.n, 1, 0, st);
+        launch_convolve(reverb_launch(e, la, e->gy, e->gy, 1), st);
+        launch_loop_attack_stage_bwd(A, 0, la.rv, 0, 1, st);
+    }
 }
 
 // one loop body of AWAREEmbedder._optimize (multibit_embedder.py:95-122)
@@ -2447,56 +2710,31 @@ static int embed_iteration(aware_embed* e, hipStream_t st, int do_step, float* g
     L.sig = e->yraw; L.sig_off = b->d_out_off; L.sig_len = b->d_out_len;
     L.pmax = e->pmaxY; L.pcount = b->d_pc_syn; L.pstride = b->pstride; L.double_norm = 1;
     // attack-aware embedding (EXTENSION): the chain turns the normalised synthesis into z; the analysis reads z
-    const bool attacked = e->la.n > 0;
-    LoopAttackLaunch A;
+    const bool attacked = e->la.n > 0 || e->mix_n > 0;
+    LoopAttackLaunch A, MA[kMaxLoopChains], AC;
     if (attacked) {
         const auto& la = e->la;
-        A.frame_off = b->d_frame_off; A.pcount = b->d_pc_syn; A.B = b->B; A.pstride = b->pstride; A.run_blocks = b->synth_run;
-        A.step = e->step; A.seeds = la.seeds; A.n = la.n;
-        for (int j = 0; j < la.n; ++j) { A.kind[j] = la.kind[j]; A.k[j] = la.k[j]; A.inv_snr[j] = la.inv_snr[j]; A.prob[j] = la.prob[j]; }
-        A.yraw = e->yraw; A.pmaxY = e->pmaxY; A.psq = la.psq; A.z = la.z; A.pmaxZ = la.pmaxZ;
-        if (la.rv >= 0 || la.sp >= 0 || la.ts >= 0 || la.ps >= 0 || la.pv >= 0 || la.ds >= 0) { A.idle_plain = 1; A.gpad_out = la.gpad0; }
-        if (la.ts >= 0) {
-            // the entries in front of the stretch on N(N(yraw)), the overlap-add (and the resampling of a speed change
-            // directly behind it), the entries behind
-            const bool pair = la.sp >= 0;
-            launch_loop_attack_stage(A, 0, la.ts, e->yraw, 1, la.u, nullptr, st);
-            launch_time_stretch(stretch_launch(e, la.u, pair ? la.v : la.z, 0, 0), st);
-            if (pair) launch_speed_change(speed_launch(e, la.v, la.z, 0, 0), st);
-            launch_loop_attack_stage(A, (pair ? la.sp : la.ts) + 1, la.n, la.z, 0, la.z, la.pmaxZ, st);
-        } else if (la.sp >= 0) {
-            // the entries in front of the speed change on N(N(yraw)), the resampling, the entries behind it
-            launch_loop_attack_stage(A, 0, la.sp, e->yraw, 1, la.u, nullptr, st);
-            launch_speed_change(speed_launch(e, la.u, la.z, 0, 0), st);
-            launch_loop_attack_stage(A, la.sp + 1, la.n, la.z, 0, la.z, la.pmaxZ, st);
-        } else if (la.ps >= 0) {
-            // the same shape: the entries in front of the pitch shift on N(N(yraw)), the fused stretch and resampling, the
-            // entries behind it
-            launch_loop_attack_stage(A, 0, la.ps, e->yraw, 1, la.u, nullptr, st);
-            launch_pitch_shift(pitch_launch(e, la.u, la.z, 0, 0), st);
-            launch_loop_attack_stage(A, la.ps + 1, la.n, la.z, 0, la.z, la.pmaxZ, st);
-        } else if (la.pv >= 0) {
-            // the same shape again: the entries in front of the phase vocoder on N(N(yraw)), its stage (gy is free until the
-            // synthesis adjoint writes it, and carries the vocoded signal to the resampling), the entries behind it
-            launch_loop_attack_stage(A, 0, la.pv, e->yraw, 1, la.u, nullptr, st);
-            pv_stage_forward(e, e->gy, st);
-            launch_loop_attack_stage(A, la.pv + 1, la.n, la.z, 0, la.z, la.pmaxZ, st);
-        } else if (la.ds >= 0) {
-            // the same shape: the entries in front of the deletion on N(N(yraw)), the gather, the entries behind it
-            launch_loop_attack_stage(A, 0, la.ds, e->yraw, 1, la.u, nullptr, st);
-            launch_delete_samples(delete_launch(e, la.u, la.z, 0, 0), st);
-            launch_loop_attack_stage(A, la.ds + 1, la.n, la.z, 0, la.z, la.pmaxZ, st);
-        } else if (la.rv < 0) {
-            launch_loop_attack_forward(A, st);
+        if (e->mix_n) {
+            // a mixture: the draw, every chain on the clips that drew it, the clips that drew none on the idle route of a
+            // chain that splits (z = N(N(y)), maxima recorded as 1)
+            LoopMixDrawLaunch D;
+            D.seeds = la.seeds; D.step = e->step; D.B = b->B; D.n = e->mix_n; D.choice = e->mix_choice;
+            for (int c = 0; c < e->mix_n; ++c) D.thr[c] = e->mix_thr[c];
+            launch_loop_mix_draw(D, st);
+            for (int c = 0; c < e->mix_n; ++c) {
+                MA[c] = chain_stage_launch(e, e->mix[c]);
+                chain_forward(e, e->mix[c], MA[c], st);
+            }
+            if (e->mix_thr[e->mix_n - 1] < 4294967296ull) {
+                LoopChainState clean = la;
+                clean.n = 0; clean.gate.choice = e->mix_choice; clean.gate.chain = -1;
+                AC = chain_stage_launch(e, clean);
+                AC.idle_plain = 1;
+                launch_loop_attack_forward(AC, st);
+            }
         } else {
-            // the entries in front of the reverberation on N(N(yraw)), the convolution, the entries behind it
-            launch_loop_attack_stage(A, 0, la.rv, e->yraw, 1, la.u, nullptr, st);
-            ReverbIrLaunch R;
-            R.seeds = la.seeds; R.step = e->step; R.entry = la.rv; R.B = b->B; R.n_lo = la.n_lo; R.n_hi = la.n_hi;
-            R.gain = la.gain; R.prob = la.prob[la.rv]; R.h = la.h; R.h_stride = kReverbMaxIr; R.nh = la.nh;
-            launch_reverb_ir(R, st);
-            launch_convolve(reverb_launch(e, la.u, la.z, 0), st);
-            launch_loop_attack_stage(A, la.rv + 1, la.n, la.z, 0, la.z, la.pmaxZ, st);
+            A = chain_stage_launch(e, la);
+            chain_forward(e, la, A, st);
         }
         LAUNCHCHK(); PROF(K_MISC);
         L.sig = la.z; L.pmax = la.pmaxZ;
@@ -2535,55 +2773,16 @@ static int embed_iteration(aware_embed* e, hipStream_t st, int do_step, float* g
         // gy: dL/d N(N(z)) -> dL/dx (normalisers at z, mask of the suppressions); the reflect-pad parts of the streaming
         // adjoint are folded in here, so the analysis adjoint below gets a block of zeros for them
         const bool streamed = dsp == 0 && stream_supported(e->plan->dev);
-        A.step_back = do_step ? 1 : 0;                  // the read-out kernel has advanced the counter
-        A.gy = e->gy; A.gpad = streamed ? e->gpad : nullptr; A.pdot_in = e->pdot; A.pdot_out = e->la.pdot;
-        if (e->la.ts >= 0) {
-            // the mirror: normalisers at z and the masks behind the stage into u, the gather-form adjoints (of the speed
-            // change into v, of the stretch into gy), the masks in front and the partial sums against x
-            const bool pair = e->la.sp >= 0;
-            A.gy_out = e->la.u;
-            launch_loop_attack_stage_bwd(A, (pair ? e->la.sp : e->la.ts) + 1, e->la.n, 1, 0, st);
-            A.gy_out = nullptr;
-            if (pair) launch_speed_change(speed_launch(e, e->la.u, e->la.v, 1, A.step_back), st);
-            launch_time_stretch(stretch_launch(e, pair ? e->la.v : e->la.u, e->gy, 1, A.step_back), st);
-            launch_loop_attack_stage_bwd(A, 0, e->la.ts, 0, 1, st);
-        } else if (e->la.sp >= 0) {
-            // the mirror: normalisers at z and the masks behind the speed change into u (the forward pass is done with
-            // it), the gather-form adjoint back into gy, the masks in front of it and the partial sums against x
-            A.gy_out = e->la.u;
-            launch_loop_attack_stage_bwd(A, e->la.sp + 1, e->la.n, 1, 0, st);
-            A.gy_out = nullptr;
-            launch_speed_change(speed_launch(e, e->la.u, e->gy, 1, A.step_back), st);
-            launch_loop_attack_stage_bwd(A, 0, e->la.sp, 0, 1, st);
-        } else if (e->la.ps >= 0) {
-            // the mirror, as for the speed change: into u, the fused gather-form adjoint back into gy, the stage in front
-            A.gy_out = e->la.u;
-            launch_loop_attack_stage_bwd(A, e->la.ps + 1, e->la.n, 1, 0, st);
-            A.gy_out = nullptr;
-            launch_pitch_shift(pitch_launch(e, e->la.u, e->gy, 1, A.step_back), st);
-            launch_loop_attack_stage_bwd(A, 0, e->la.ps, 0, 1, st);
-        } else if (e->la.pv >= 0) {
-            // the mirror: into u, the stage's backward into gy, the stage in front
-            A.gy_out = e->la.u;
-            launch_loop_attack_stage_bwd(A, e->la.pv + 1, e->la.n, 1, 0, st);
-            A.gy_out = nullptr;
-            pv_stage_backward(e, A.step_back, st);
-            launch_loop_attack_stage_bwd(A, 0, e->la.pv, 0, 1, st);
-        } else if (e->la.ds >= 0) {
-            // the mirror, as for the speed change: into u, the gather-form adjoint back into gy, the stage in front
-            A.gy_out = e->la.u;
-            launch_loop_attack_stage_bwd(A, e->la.ds + 1, e->la.n, 1, 0, st);
-            A.gy_out = nullptr;
-            launch_delete_samples(delete_launch(e, e->la.u, e->gy, 1, A.step_back), st);
-            launch_loop_attack_stage_bwd(A, 0, e->la.ds, 0, 1, st);
-        } else if (e->la.rv < 0) {
-            launch_loop_attack_backward(A, st);
+        auto arm = [&](LoopAttackLaunch& X) {
+            X.step_back = do_step ? 1 : 0;              // the read-out kernel has advanced the counter
+            X.gy = e->gy; X.gpad = streamed ? e->gpad : nullptr; X.pdot_in = e->pdot; X.pdot_out = e->la.pdot;
+        };
+        if (e->mix_n) {
+            for (int c = 0; c < e->mix_n; ++c) { arm(MA[c]); chain_backward(e, e->mix[c], MA[c], st); }
+            if (e->mix_thr[e->mix_n - 1] < 4294967296ull) { arm(AC); launch_loop_attack_backward(AC, st); }
         } else {
-            // the mirror: normalisers at z and the masks behind the reverberation, the correlation with the same
-            // responses (their spectra are still there), the masks in front of it and the partial sums against x
-            launch_loop_attack_stage_bwd(A, e->la.rv + 1, e->la.n, 1, 0, st);
-            launch_convolve(reverb_launch(e, e->gy, e->gy, 1), st);
-            launch_loop_attack_stage_bwd(A, 0, e->la.rv, 0, 1, st);
+            arm(A);
+            chain_backward(e, e->la, A, st);
         }
         LAUNCHCHK(); PROF(K_MISC);
     }

@@ -44,6 +44,15 @@ struct PlanDev {
 // 256*(frame_off[b] - b) of any per-clip signal array (frame_off: B+1 prefix sums of T_b).
 __device__ __forceinline__ int sig_offset(const int* frame_off, int b) { return kHop * (frame_off[b] - b); }
 
+// Attack mixtures (EXTENSION, loop_mix_kernels.hip): the gate every kernel of the loop family carries.  With `choice` set, a
+// workgroup whose clip did not draw chain `chain` at this step returns at once (skipped, not copied); with `choice` null the
+// kernel computes what it computes without a gate.
+struct LoopGate {
+    const int* choice = nullptr;          // [B] the chain clip b drew at this step, -1: none
+    int chain = 0;
+};
+__device__ __forceinline__ bool loop_gate_skips(const LoopGate& g, int b) { return g.choice && g.choice[b] != g.chain; }
+
 // per-clip maximum of |y| with the first index attaining it, packed so that an
 // unsigned max gives (largest value, smallest index)
 __device__ __forceinline__ unsigned long long pack_max(float a, unsigned idx) {

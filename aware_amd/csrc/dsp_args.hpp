@@ -148,6 +148,7 @@ struct AnalysisArgs {
     float* mel_out;                   // [NF][128]
     const float* melf_w;              // [128][kMelTapsB], zero beyond the filter's support
     const unsigned char* melf_s;      // [128] first band column of the support (<= kFS - kMelTapsB)
+    LoopGate gate;                    // staged kernels on a full spectrum: the clips of one chain of a mixture (kernels.h)
 };
 
 
@@ -182,6 +183,7 @@ struct SynthArgs {
     const float* dmel;
     const float2* melw;               // [kFS]
     const unsigned char* melm;        // [kFS], <= 126
+    LoopGate gate;                    // staged kernels on a full spectrum: the clips of one chain of a mixture (kernels.h)
 };
 
 

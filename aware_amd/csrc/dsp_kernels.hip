@@ -56,6 +56,7 @@ __global__ __launch_bounds__(kThreads) void analysis_kernel(AnalysisArgs a) {
     __shared__ double dred[4];
 
     const int b = blockIdx.y;
+    if (FULLOUT && loop_gate_skips(a.gate, b)) return;
     const int f0 = a.frame_off[b];
     const int T = a.frame_off[b + 1] - f0;
     const int t0 = blockIdx.x * kFramesPerWG;
@@ -274,6 +275,7 @@ __global__ __launch_bounds__(kThreads) void synth_kernel(SynthArgs a) {
     __shared__ double dred[4];
 
     const int b = blockIdx.y;
+    if (INP == 0 && loop_gate_skips(a.gate, b)) return;
     const int f0 = a.frame_off[b];
     const int T = a.frame_off[b + 1] - f0;
     const int nblk = T - 1;                     // output hop blocks
@@ -552,7 +554,7 @@ void launch_analysis(const AnalysisLaunch& L, hipStream_t st) {
     a.sig = L.sig; a.sig_off = L.sig_off; a.sig_len = L.sig_len;
     a.pmax = L.pmax; a.pcount = L.pcount; a.pstride = L.pstride;
     a.double_norm = L.double_norm; a.unit_default = L.unit_default;
-    a.mag = L.mag; a.unit = (cf*)L.unit; a.full = (cf*)L.full;
+    a.mag = L.mag; a.unit = (cf*)L.unit; a.full = (cf*)L.full; a.gate = L.gate;
     a.yraw = L.yraw; a.pdot = L.pdot; a.phasor = (const cf*)L.phasor;
     a.coef = L.coef; a.mom = L.mom; a.vel = L.vel; a.lo = L.lo; a.hi = L.hi; a.best = L.best;
     a.improved = L.improved; a.sched = (const float4*)L.sched; a.sched_len = L.sched_len > 0 ? L.sched_len : 1; a.step = L.step;
@@ -573,7 +575,7 @@ void launch_synth(const SynthLaunch& L, hipStream_t st) {
     SynthArgs a{};
     a.plan = L.plan;
     a.frame_off = L.frame_off;
-    a.amp = L.amp; a.ph = (const cf*)L.ph; a.full = (const cf*)L.full;
+    a.amp = L.amp; a.ph = (const cf*)L.ph; a.full = (const cf*)L.full; a.gate = L.gate;
     a.out = L.out; a.add = L.add; a.pmax = L.pmax; a.pstride = L.pstride;
     a.yraw = L.yraw; a.pmax_in = L.pmax_in; a.pcount = L.pcount; a.pdot = L.pdot;
     a.sig_off = L.sig_off; a.sig_len = L.sig_len;

@@ -7,6 +7,22 @@
 
 namespace aware {
 
+// ---- loop_mix_kernels.hip: attack mixtures (EXTENSION): one of several loop chains drawn per clip and step.  The gate every
+// kernel of the loop family carries: with `choice` set, a workgroup whose clip did not draw chain `chain` returns at once
+// (skipped, not copied); with `choice` null the kernel computes what it computes without a gate -------------------------
+// (LoopGate itself is in common.hpp, beside the layout helpers every kernel file shares)
+constexpr int kMaxLoopChains = 8;
+struct LoopMixDrawLaunch {
+    const unsigned* seeds = nullptr;      // [B]
+    const int* step = nullptr;            // device step counter, or null: step_imm
+    int step_imm = 0, B = 0, n = 0;
+    unsigned long long thr[kMaxLoopChains] = {0};     // T_c = min(floor((w_0 + .. + w_c) 2^32), 2^32)
+    int* choice = nullptr;                // [B]
+};
+// T_c from the float32 weights, summed in double
+void loop_mix_thresholds(const float* weights, int n, unsigned long long* thr);
+void launch_loop_mix_draw(const LoopMixDrawLaunch& L, hipStream_t st);
+
 // ---- dsp_kernels.hip ------------------------------------------------------------------
 constexpr int kStreamWaves = 4;        // waves (= runs) per workgroup of the streaming DSP kernels
 
@@ -53,6 +69,7 @@ struct AnalysisLaunch {
     float* mel_out = nullptr;         // stream, forward: the mel tile [NF][128] instead of mag (AnalysisArgs)
     const float* melf_w = nullptr;
     const unsigned char* melf_s = nullptr;
+    LoopGate gate;                    // staged kernels on a full spectrum (the phase vocoder's stage inside a mixture)
 };
 struct SynthLaunch {
     PlanDev plan;
@@ -82,6 +99,7 @@ struct SynthLaunch {
     const float* dmel = nullptr;      // stream + adjoint: amplitudes from dL/d(mel) [NF][128] through the two-tap table (SynthArgs)
     const void* melw = nullptr;
     const unsigned char* melm = nullptr;
+    LoopGate gate;                    // staged kernels on a full spectrum (the phase vocoder's stage inside a mixture)
 };
 void launch_absmax_partials(const float* sig, const int* sig_off, const int* sig_len, unsigned long long* pmax,
                             int pstride, int B, int max_len, hipStream_t st);
@@ -385,6 +403,7 @@ struct LoopAttackLaunch {
     // pads the analysis adjoint then reads (zeros for every other clip)
     int idle_plain = 0;
     float* gpad_out = nullptr;
+    LoopGate gate;                        // inside a mixture: the clips that drew this chain
 };
 // x = N(N(yraw)), the chain, z and the partial maxima of |z|: one reduction launch per noise entry, then one pass
 void launch_loop_attack_forward(const LoopAttackLaunch& L, hipStream_t st);
@@ -415,6 +434,7 @@ struct ReverbIrLaunch {
     float prob = 1.f;
     float* h = nullptr; int h_stride = 0; // [B][h_stride], zero beyond the drawn length
     int* nh = nullptr;                    // [B] the drawn length; 0: the entry does not fire (h is then the unit impulse)
+    LoopGate gate;
 };
 void launch_reverb_ir(const ReverbIrLaunch& L, hipStream_t st);
 struct ConvolveLaunch {
@@ -429,6 +449,7 @@ struct ConvolveLaunch {
     int skip_h = 0;                       // hspec is that of an earlier launch with the same h
     cf* hspec = nullptr;                  // [B][parts][kReverbBins]
     cf* xspec = nullptr;                  // [B][kmax][kReverbBins]
+    LoopGate gate;
 };
 void launch_convolve(const ConvolveLaunch& L, hipStream_t st);
 
@@ -451,6 +472,7 @@ struct SpeedLaunch {
     const int* z_off = nullptr; const int* z_len = nullptr;
     int max_len = 0;                      // >= every length written
     const int* m = nullptr;               // [B]
+    LoopGate gate;                        // the embed loop inside a mixture: the clips that drew this chain
 };
 void launch_speed_change(const SpeedLaunch& L, hipStream_t st);
 
@@ -473,6 +495,7 @@ struct StretchLaunch {
     const int* z_off = nullptr; const int* z_len = nullptr;
     int max_len = 0;                      // >= every length written
     const int* m = nullptr;               // [B]
+    LoopGate gate;                        // the embed loop inside a mixture: the clips that drew this chain
 };
 // the periodic Hann window of 1024 points in f32 on the current device (uploaded once, outside any stream capture); null
 // when the device refuses
@@ -498,6 +521,7 @@ struct PitchLaunch {
     const int* z_off = nullptr; const int* z_len = nullptr;
     int max_len = 0;                      // >= every length written
     const int* m = nullptr;               // [B]
+    LoopGate gate;                        // the embed loop inside a mixture: the clips that drew this chain
 };
 void launch_pitch_shift(const PitchLaunch& L, hipStream_t st);
 
@@ -520,6 +544,7 @@ struct PvLaunch {
     float prob = 0.f;
     // or stand-alone (seeds null): mq[b] given, outside kStretchMin .. kStretchMax read as 0 (the identity)
     const int* mq = nullptr;              // [B]
+    LoopGate gate;                        // the embed loop inside a mixture: the clips that drew this chain
 };
 void launch_pv_frames(const PvLaunch& L, int backward, hipStream_t st);
 // the loop's clips that the entry leaves alone at this step: dst = src (the embed loop's signal layout)
@@ -543,6 +568,7 @@ struct DeleteLaunch {
     int max_len = 0;                      // >= every length
     const int* start = nullptr;           // [B]
     const int* k = nullptr;               // [B]
+    LoopGate gate;                        // the embed loop inside a mixture: the clips that drew this chain
 };
 void launch_delete_samples(const DeleteLaunch& L, hipStream_t st);
 

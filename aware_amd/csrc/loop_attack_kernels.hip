@@ -56,6 +56,7 @@ struct ChainArgs {
     const float* gpad;                    // [B][2][512] reflect-pad parts of the streaming synthesis adjoint (null: folded)
     const double* pdot_in;                // [B][pstride] partial sums of gy * N(N(z))
     double* pdot_out;                     // [B][pstride] partial sums of dL/dx * x
+    LoopGate gate;                        // inside a mixture: the clips that drew this chain
 };
 
 // sum of a clip's f64 partials in a fixed order; all threads of the block call this
@@ -123,6 +124,7 @@ __global__ __launch_bounds__(kLaThreads) void chain_kernel(ChainArgs a) {
     __shared__ unsigned long long red[4];
     __shared__ double dred[4];
     const int b = blockIdx.y;
+    if (loop_gate_skips(a.gate, b)) return;
     const int nblk = a.frame_off[b + 1] - a.frame_off[b] - 1;
     int nseg, jb0, jb1;
     synth_segment(nblk, blockIdx.x, a.run_blocks, nseg, jb0, jb1);
@@ -192,6 +194,7 @@ __global__ __launch_bounds__(kLaThreads) void chain_bwd_kernel(ChainArgs a) {
     __shared__ unsigned long long red[4];
     __shared__ double dred[4];
     const int b = blockIdx.y;
+    if (loop_gate_skips(a.gate, b)) return;
     const int nblk = a.frame_off[b + 1] - a.frame_off[b] - 1;
     int nseg, jb0, jb1;
     synth_segment(nblk, blockIdx.x, a.run_blocks, nseg, jb0, jb1);
@@ -292,6 +295,7 @@ ChainArgs chain_args(const LoopAttackLaunch& L) {
         a.prob[j] = j < L.n ? L.prob[j] : 0.f;
     }
     a.yraw = L.yraw; a.pmaxY = L.pmaxY; a.psq = L.psq; a.z = L.z; a.pmaxZ = L.pmaxZ;
+    a.gate = L.gate;
     a.gy = L.gy; a.gdst = L.gy_out ? L.gy_out : L.gy; a.gpad = L.gpad; a.pdot_in = L.pdot_in; a.pdot_out = L.pdot_out;
     return a;
 }

@@ -31,6 +31,7 @@ __global__ __launch_bounds__(kDsThreads) void delete_kernel(DeleteLaunch a) {
     float* __restrict__ y;
     int n, i0, i1, start, k;        // the clip's length, this workgroup's samples [i0, i1), the cut [start, start + k)
     if (LOOP) {
+        if (loop_gate_skips(a.gate, b)) return;
         const int nblk = a.frame_off[b + 1] - a.frame_off[b] - 1;
         int nseg, jb0, jb1;
         synth_segment(nblk, blockIdx.x, a.run_blocks, nseg, jb0, jb1);

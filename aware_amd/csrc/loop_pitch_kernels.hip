@@ -126,6 +126,7 @@ __global__ __launch_bounds__(kPsThreads) void pitch_kernel(PitchLaunch a) {
     float* y;
     int nx, nz, q0, q1, m;          // lengths of the x side and the z side; this workgroup's groups of four outputs [q0, q1)
     if (LOOP) {
+        if (loop_gate_skips(a.gate, b)) return;
         const int nblk = a.frame_off[b + 1] - a.frame_off[b] - 1;
         int nseg, jb0, jb1;
         synth_segment(nblk, blockIdx.x, a.run_blocks, nseg, jb0, jb1);

@@ -89,6 +89,7 @@ __global__ __launch_bounds__(kPvThreads) void pv_frames_kernel(PvLaunch a) {
     if (k >= kPvRow) return;
     const int f0 = a.frame_off[b], T = a.frame_off[b + 1] - f0;
     if (T < 1) return;
+    if (LOOP && loop_gate_skips(a.gate, b)) return;
     int mq;
     const bool on = pv_draw<LOOP>(a, b, mq);
     if (LOOP && !on) return;                       // the clip does not go through the spectra at all (pv_idle_kernel)
@@ -149,6 +150,7 @@ __global__ __launch_bounds__(kPvThreads) void pv_frames_kernel(PvLaunch a) {
 // run, as speed_kernel)
 __global__ __launch_bounds__(256) void pv_idle_kernel(PvLaunch a, const float* __restrict__ src, float* __restrict__ dst) {
     const int b = blockIdx.y;
+    if (loop_gate_skips(a.gate, b)) return;
     const int nblk = a.frame_off[b + 1] - a.frame_off[b] - 1;
     int nseg, jb0, jb1;
     synth_segment(nblk, blockIdx.x, a.run_blocks, nseg, jb0, jb1);

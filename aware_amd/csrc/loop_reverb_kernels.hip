@@ -34,6 +34,7 @@ static_assert(kRvS == kReverbBins && kReverbTwHalf == kRvM / 2 && kReverbParts *
 __global__ __launch_bounds__(256) void reverb_ir_kernel(ReverbIrLaunch a) {
     __shared__ double dred[4];
     const int b = blockIdx.x;
+    if (loop_gate_skips(a.gate, b)) return;
     const unsigned step = (unsigned)(a.step ? *a.step : a.step_imm), seed = a.seeds[b], j = (unsigned)a.entry;
     unsigned r[4];
     philox4x32_10(0u, step, 1u + j, 1u, seed, 0x5EEDu, r);
@@ -88,6 +89,7 @@ template <bool IS_H>
 __global__ __launch_bounds__(256) void spectra_kernel(ConvolveLaunch a) {
     __shared__ cf sbuf[kRvWaves][kRvS];
     __shared__ cf th[kRvM / 2];
+    if (loop_gate_skips(a.gate, blockIdx.y)) return;        // the whole workgroup: in front of the barrier
     load_tables(th, a.tables);
     const cf* twN = a.tables + kReverbTwHalf;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -181,6 +183,7 @@ __device__ __forceinline__ void accumulate(int lane, int adjoint, int k, int K, 
 __global__ __launch_bounds__(256) void apply_kernel(ConvolveLaunch a) {
     __shared__ cf sbuf[kRvWaves][kRvS];
     __shared__ cf th[kRvM / 2];
+    if (loop_gate_skips(a.gate, blockIdx.y)) return;        // the whole workgroup: in front of the barrier
     load_tables(th, a.tables);
     const cf* twN = a.tables + kReverbTwHalf;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;

@@ -740,3 +740,119 @@ def device_entries(chain: list[dict], sample_rate: int):
     Chains of these two kinds only; every other kind goes through device_entries_ex."""
     return [(KINDS[a["kind"]], a["snr_db"] if a["kind"] == "gaussian_noise" else float(suppression_samples(a, sample_rate)),
              a["prob"]) for a in chain]
+
+
+# ---- attack mixtures (EXTENSION; DESIGN.md section 22): one of several chains drawn per clip and step ---------------------
+#
+# A chain holds at most one of the kinds that split it, so one chain buys robustness against one family.  A mixture is a list
+# of 1..8 chains with weights; at optimiser step s clip b draws r = philox4x32_10((0, s, 12, 1), (seed_b, 0x5EED)) and goes
+# through the first chain c with r[0] < T_c, T_c = min(floor((w_0 + .. + w_c) 2^32), 2^32) (the float32 weights summed in
+# float64), exactly as under a handle that holds chain c alone; what the weights leave of 1 is the share of clean steps
+# (choice -1: the identity).
+MAX_CHAINS = 8
+_MIX_WORD = 12                  # third Philox counter word of the mixture's draw (0: noise, 1..4: entry draws, 8: responses)
+
+
+def parse_mixture(mixture) -> list[dict]:
+    """Validated copy of a mixture such as [{"weight": 0.5, "chain": [{"kind": "gaussian_noise", "snr_db": 10.0}]}, ...]
+    (None / empty: no mixture): a list of {"weight": w, "chain": [...]} with every chain through parse_chain; weight defaults
+    to 1 / len(mixture).  ValueError, with the index of the offender: more than eight chains, an entry that is no dict, an
+    unknown key, an empty chain, a chain parse_chain refuses, a weight that is negative or not finite, a second chain with a
+    reverberation (the handle keeps one set of impulse responses, aware_embed_buffer 13), a weight sum above 1 + 1e-6."""
+    if not mixture:
+        return []
+    if isinstance(mixture, dict) or not isinstance(mixture, (list, tuple)):
+        raise ValueError("loop_attack_mixture: a list of {weight: ..., chain: [...]} entries is expected")
+    if len(mixture) > MAX_CHAINS:
+        raise ValueError(f"loop_attack_mixture: at most {MAX_CHAINS} chains, got {len(mixture)}")
+    out, reverb = [], None
+    for c, m in enumerate(mixture):
+        if not isinstance(m, dict):
+            raise ValueError(f"loop_attack_mixture[{c}]: a {{weight: ..., chain: [...]}} entry is expected, got {m!r}")
+        extra = set(m) - {"weight", "chain"}
+        if extra:
+            raise ValueError(f"loop_attack_mixture[{c}]: unknown key(s) {sorted(extra)}")
+        try:
+            chain = parse_chain(m.get("chain"))
+        except ValueError as err:
+            raise ValueError(f"loop_attack_mixture[{c}]: {err}") from None
+        if not chain:
+            raise ValueError(f"loop_attack_mixture[{c}]: the chain is empty")
+        try:
+            w = float(m.get("weight", 1.0 / len(mixture)))
+        except (TypeError, ValueError):
+            raise ValueError(f"loop_attack_mixture[{c}]: weight = {m.get('weight')!r} is not a number") from None
+        if not (math.isfinite(w) and w >= 0.0):
+            raise ValueError(f"loop_attack_mixture[{c}]: weight = {w} has to be finite and >= 0")
+        if any(a["kind"] == "reverberation" for a in chain):
+            if reverb is not None:
+                raise ValueError(f"loop_attack_mixture[{c}]: a second chain with a reverberation (the first is chain {reverb})")
+            reverb = c
+        out.append({"weight": w, "chain": chain})
+    total = float(np.sum(np.asarray([m["weight"] for m in out], dtype=np.float32).astype(np.float64)))
+    if total > 1.0 + 1e-6:
+        raise ValueError(f"loop_attack_mixture: the weights sum to {total}, above 1")
+    return out
+
+
+def mixture_thresholds(weights) -> list[int]:
+    """T_c = min(floor((w_0 + .. + w_c) 2^32), 2^32): the weights at float32, summed in float64 in order."""
+    acc, out = 0.0, []
+    for w in np.asarray(weights, dtype=np.float32):
+        acc += float(w)
+        out.append(min(int(math.floor(acc * 4294967296.0)), 1 << 32))
+    return out
+
+
+def mixture_choice(seed: int, step: int, weights) -> int:
+    """The chain clip `seed` draws at `step`: the first c with r[0] < T_c, -1 if there is none.  The host twin of
+    csrc/loop_mix_kernels.hip."""
+    r0 = int(philox4x32(np.array([[0, step, _MIX_WORD, 1]], dtype=np.uint64), (int(seed) & 0xFFFFFFFF, _KEY1))[0][0])
+    for c, t in enumerate(mixture_thresholds(weights)):
+        if r0 < t:
+            return c
+    return -1
+
+
+def mixture_choices(seeds, step: int, weights) -> np.ndarray:
+    """mixture_choice for many seeds at once, int32 [len(seeds)]."""
+    thr = mixture_thresholds(weights)
+    out = np.full(len(seeds), -1, dtype=np.int32)
+    for b, seed in enumerate(seeds):            # the key differs per clip, so Philox runs once per seed; the thresholds are shared
+        r0 = int(philox4x32(np.array([[0, step, _MIX_WORD, 1]], dtype=np.uint64), (int(seed) & 0xFFFFFFFF, _KEY1))[0][0])
+        out[b] = next((c for c, t in enumerate(thr) if r0 < t), -1)
+    return out
+
+
+def mixture_weights(mixture: list[dict]) -> list[float]:
+    return [m["weight"] for m in mixture]
+
+
+def check_mixture_lengths(mixture: list[dict], sample_rate: int, out_lengths) -> None:
+    """check_lengths per chain, the offender's index in front."""
+    for c, m in enumerate(mixture):
+        try:
+            check_lengths(m["chain"], sample_rate, out_lengths)
+        except ValueError as err:
+            raise ValueError(f"loop_attack_mixture[{c}]: {err}") from None
+
+
+def apply_mixture(x, mixture, seeds, step: int, sample_rate: int = 16000):
+    """The mixture on x (container types as apply_chain): per clip, apply_chain of the chain it draws at `step` on that clip
+    alone, and the clip itself for choice -1.  Differentiable as apply_chain is."""
+    mixture = parse_mixture(mixture)
+    clips = list(x) if not torch.is_tensor(x) else [x[b] for b in range(x.shape[0])]
+    if len(seeds) != len(clips):
+        raise ValueError(f"apply_mixture: {len(clips)} clips but {len(seeds)} seeds")
+    check_mixture_lengths(mixture, sample_rate, [c.shape[-1] for c in clips])
+    weights = mixture_weights(mixture)
+    out = []
+    for xb, seed in zip(clips, seeds):
+        c = mixture_choice(seed, step, weights)
+        out.append(xb if c < 0 else apply_chain([xb], mixture[c]["chain"], [seed], step, sample_rate)[0])
+    return torch.stack(out) if torch.is_tensor(x) else out
+
+
+def device_mixture(mixture: list[dict], sample_rate: int):
+    """[(weight, device_entries_ex(chain))] of the C ABI's aware_loop_chain."""
+    return [(m["weight"], device_entries_ex(m["chain"], sample_rate)) for m in mixture]

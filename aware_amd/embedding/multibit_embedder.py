@@ -17,7 +17,7 @@ from ..interfaces import BaseEmbedder
 from ..utils.audio import ISTFT, STFT, STFTAssembler, STFTDecomposer, WaveformNormalizer, band_bins, get_plan
 from ..utils.logger import logger
 from .. import runtime as rt
-from .loop_attacks import parse_chain
+from .loop_attacks import parse_chain, parse_mixture
 from .losses import get_loss_fn
 from .optimizers import get_optimizer, is_card_default
 from .schedulers import get_scheduler
@@ -28,10 +28,13 @@ class AWAREEmbedder(BaseEmbedder):
                  pattern_mode: str = "bits2bipolar", embedding_bands=(500, 4000), tolerance_db: float = 6.0,
                  num_iterations: int = 400, detection_net_cfg: dict = None, optimizer_cfg: dict = None,
                  scheduler_cfg: dict = None, loss: str = "push", verbose: bool = True, use_graph: bool = True,
-                 loop_attacks=None, loop_attack_seed: int = 0):
+                 loop_attacks=None, loop_attack_seed: int = 0, loop_attack_mixture=None):
         """loop_attacks (EXTENSION, see embedding/loop_attacks.py): a chain of attacks applied inside the optimisation loop,
         e.g. [{"kind": "gaussian_noise", "snr_db": 10.0}, {"kind": "sample_suppression", "seconds": 0.3, "prob": 0.75}];
-        clip i of a batch draws with seed loop_attack_seed + i.  None: the reference's loop (clean synthesis only)."""
+        clip i of a batch draws with seed loop_attack_seed + i.  None: the reference's loop (clean synthesis only).
+        loop_attack_mixture (EXTENSION): a list of {"weight": w, "chain": [...]}; every clip draws one of the chains (or, with
+        what the weights leave of 1, none) afresh at every step, so one watermark meets several attack families.  Giving
+        both loop_attacks and loop_attack_mixture is a ValueError."""
         rt.require_card_geometry("AWAREEmbedder", frame_length, hop_length, win_length)
         self.frame_length, self.hop_length, self.window, self.win_length = frame_length, hop_length, window, win_length
         self.device = torch.device("cuda")
@@ -51,6 +54,9 @@ class AWAREEmbedder(BaseEmbedder):
         self.verbose = verbose
         self.use_graph = use_graph
         self.loop_attacks = parse_chain(loop_attacks)     # ValueError on an unknown kind / key, prob outside [0, 1], > 4 entries
+        self.loop_attack_mixture = parse_mixture(loop_attack_mixture)      # ValueError with the index of the offending chain
+        if self.loop_attacks and self.loop_attack_mixture:
+            raise ValueError("AWAREEmbedder: loop_attacks or loop_attack_mixture, not both")
         self.loop_attack_seed = int(loop_attack_seed)
         self.conv_pipe = "f16x2"                       # runtime.CONV_PIPES: arithmetic of the detector's conv-block GEMMs
         self.audio_preprocess_pipeline = [WaveformNormalizer(), STFT(frame_length, hop_length, window, win_length), STFTDecomposer()]
@@ -74,6 +80,9 @@ class AWAREEmbedder(BaseEmbedder):
         if self.loop_attacks:
             seeds = attack_seeds if attack_seeds is not None else [self.loop_attack_seed + i for i in range(batch.B)]
             sess.set_loop_attacks(self.loop_attacks, seeds, sample_rate)
+        elif self.loop_attack_mixture:
+            seeds = attack_seeds if attack_seeds is not None else [self.loop_attack_seed + i for i in range(batch.B)]
+            sess.set_loop_mixture(self.loop_attack_mixture, seeds, sample_rate)
         return sess
 
     def _start_session(self, batch: "rt.Batch", sample_rate: int) -> "rt.EmbedSession":

@@ -500,6 +500,30 @@ def detector_forward(plan: Plan, det: DetectorWeights, batch: Batch, mag: torch.
     return out
 
 
+def mixture_struct(dev_mixture):
+    """The C ABI's aware_loop_chain array of embedding.loop_attacks.device_mixture, and the entry arrays it points into
+    (keep them alive as long as the array is used)."""
+    keep = [(_lib.LoopAttackEx * len(ent))(*[_lib.LoopAttackEx(k, pr, (C.c_float * 4)(*p)) for k, pr, p in ent])
+            for _, ent in dev_mixture]
+    arr = (_lib.LoopChain * len(dev_mixture))(*[_lib.LoopChain(C.cast(a, C.POINTER(_lib.LoopAttackEx)), len(a), float(w))
+                                                 for a, (w, _) in zip(keep, dev_mixture)])
+    return arr, keep
+
+
+def loop_mixture_draw(seeds, step: int, weights) -> torch.Tensor:
+    """embedding.loop_attacks.mixture_choice on the device (aware_loop_mixture_draw): the chain each of the B seeds draws
+    at `step` under `weights` (-1: none), int32 [B]."""
+    lib = load_library()
+    sd = torch.from_numpy(np.asarray([int(s) & 0xFFFFFFFF for s in seeds], dtype=np.uint32).view(np.int32)).to(_dev())
+    out = torch.empty(len(seeds), dtype=torch.int32, device=_dev())
+    w = (C.c_float * len(weights))(*[float(x) for x in weights])
+    rc = lib.aware_loop_mixture_draw(_ptr(sd), len(seeds), int(step), w, len(weights), _ptr(out), _stream())
+    if rc == -1:
+        raise ValueError("loop_mixture_draw: refused (1..8 finite weights >= 0 with a sum <= 1, at least one seed)")
+    check(rc, "aware_loop_mixture_draw")
+    return out
+
+
 class EmbedSession:
     """One batched run of AWAREEmbedder._optimize (aware_embed)."""
 
@@ -587,6 +611,42 @@ class EmbedSession:
             raise ValueError("set_loop_attacks: refused (it has to precede the first iterate(); see aware_hip.h)")
         check(rc, "aware_embed_set_loop_attacks")
         self.loop_attacks, self._la_ws = chain, ws
+
+    def set_loop_mixture(self, mixture, seeds, sample_rate: int = 16000):
+        """Attack mixtures (EXTENSION; aware_embed_set_loop_mixture): a list of {"weight": w, "chain": [...]} of
+        embedding.loop_attacks.parse_mixture; at every step each clip draws one chain (or none) from its seed and goes
+        through it as under set_loop_attacks with that chain alone.  Before the first iterate(); an empty mixture clears
+        it; a mixture and a chain replace each other.  The choices of the last forward pass are `choices`."""
+        from .embedding import loop_attacks as la
+        mixture = la.parse_mixture(mixture)
+        if not mixture:
+            rc = self.lib.aware_embed_set_loop_mixture(self.h, None, 0, None, None, 0, _stream())
+            if rc == -1:
+                raise ValueError("set_loop_mixture: refused (it has to precede the first iterate(); see aware_hip.h)")
+            check(rc, "aware_embed_set_loop_mixture")
+            self.loop_attacks, self.loop_mixture, self._la_ws = [], [], None
+            return
+        if len(seeds) != self.batch.B:
+            raise ValueError(f"set_loop_mixture: {self.batch.B} clips but {len(seeds)} seeds")
+        la.check_mixture_lengths(mixture, sample_rate, self.batch.out_lengths)     # ValueError naming chain and clip
+        sd = (C.c_uint32 * self.batch.B)(*[int(s) & 0xFFFFFFFF for s in seeds])
+        arr, keep = mixture_struct(la.device_mixture(mixture, sample_rate))
+        nbytes = self.lib.aware_embed_loop_mixture_workspace_bytes(self.batch.h, arr, len(arr))
+        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=_dev())
+        rc = self.lib.aware_embed_set_loop_mixture(self.h, arr, len(arr), sd, _ptr(ws), nbytes, _stream())
+        if rc == -1:
+            raise ValueError("set_loop_mixture: refused (it has to precede the first iterate(); see aware_hip.h)")
+        check(rc, "aware_embed_set_loop_mixture")
+        self.loop_attacks, self.loop_mixture, self._la_ws = [], mixture, ws
+
+    @property
+    def choices(self):
+        """The chain every clip drew in the last forward pass, int32 [B] (-1: none); None without a mixture."""
+        p = self.lib.aware_embed_buffer(self.h, 14)
+        if not p:
+            return None
+        off = p - self._la_ws.data_ptr()
+        return self._la_ws[off: off + 4 * self.batch.B].view(torch.int32)
 
     @property
     def attacked(self):

@@ -19,7 +19,9 @@ _EMBEDDER = {"pattern_mode": ("pattern_mode", "bits2bipolar"), "tolerance_db": (
              "scheduler_cfg": ("scheduler_cfg", {"name": "reduce_lr_on_plateau", "params": {"factor": 0.9, "patience": 500}}),
              "loss": ("loss", "push_extremes"), "verbose": ("verbose", True),
              # EXTENSION (embedding/loop_attacks.py): attacks inside the optimisation loop; absent = none
-             "loop_attacks": ("loop_attacks", None), "loop_attack_seed": ("loop_attack_seed", 0)}
+             "loop_attacks": ("loop_attacks", None), "loop_attack_seed": ("loop_attack_seed", 0),
+             # EXTENSION: one of several chains drawn per clip and step; absent = none, and not beside loop_attacks
+             "loop_attack_mixture": ("loop_attack_mixture", None)}
 _DETECTOR = {"threshold": ("threshold", 0.0), "pattern_mode": ("pattern_mode", "bipolar"),
              # EXTENSION (detection/sync.py): offset search in detection; absent = off
              "sync_search": ("sync_search", 0)}

@@ -393,7 +393,8 @@ int aware_embed_finish(aware_embed* e, const float* rescale, float* out, void* s
  * 3 coef [frames][band stride], 4 best coef, 5 lo, 6 hi, 7 phasor (complex64), 8 step counter (int32), 9 un-normalised synthesis,
  * 10 band magnitudes of the last analysis, 11 per-clip learning rates (f64 [B]; NULL unless aware_embed_set_optimizer ran),
  * 12 the attacked signal z of the last forward pass (layout of 9; NULL unless aware_embed_set_loop_attacks set a chain)
- * 13 the impulse responses of the last forward pass (NULL unless the chain has a reverberation; see below) */
+ * 13 the impulse responses of the last forward pass (NULL unless the chain has a reverberation; see below)
+ * 14 the choices of the last forward pass, int32 [B] (NULL unless aware_embed_set_loop_mixture set a mixture; see below) */
 void* aware_embed_buffer(aware_embed* e, int which);
 
 /* ---- attacks (scripts/attacks.py) ------------------------------------------------------------------
@@ -694,6 +695,35 @@ int aware_pv_frames_bwd(const void* spec, const void* grad_out, const int* frame
  * argument, in == out, B < 1 or > 65535, max_len < 1 or > 2^30, adjoint outside 0..1 (checked before anything is launched). */
 int aware_delete_samples(const float* in, const int* off, const int* len, int B, int max_len, const int* start, const int* k,
                          float* out, int adjoint, void* stream);
+
+/* ---- attack mixtures (EXTENSION, parity unpinned: the reference has no attacks in its loop) -------------------------------
+ * A handle holds one chain, and the kinds that split a chain refuse each other.  A mixture is a list of 1..8 chains, each a
+ * valid chain of aware_embed_set_loop_attacks_ex with a weight; at optimiser step s clip b draws
+ *     r = philox4x32_10((0, s, 12, 1), (seed_b, 0x5EED)),   T_c = min(floor((w_0 + .. + w_c) * 2^32), 2^32)
+ * (the float weights summed in double), and goes through the first chain c with r[0] < T_c exactly as on a handle that holds
+ * chain c alone: the same entry indices, draws, noise streams, prob gating and idle rule, forward and backward.  What the
+ * weights leave of 1 is the share of steps without a chain: such a clip (choice -1) leaves the bits of the loop without a
+ * chain, as an idle clip of a chain that splits does.  A mixture of one chain of weight 1 is that chain, bit for bit.
+ * Calling rules as aware_embed_set_loop_attacks_ex (before the first aware_embed_iterate, else AWARE_E_BADARG); n_chains = 0
+ * clears the mixture; a mixture and a plain chain replace each other.  Per chain every AWARE_E_BADARG / AWARE_E_UNSUPPORTED
+ * of the _ex setter applies; besides: n_chains outside 0..8, an empty chain, a weight that is negative or not finite, a
+ * weight sum above 1 + 1e-6, a SECOND chain with a reverberation (AWARE_E_BADARG), a workspace that is too small
+ * (AWARE_E_WORKSPACE).  workspace: device memory, 256-byte aligned, alive as long as the handle: the buffers of a chain of
+ * kinds 0/1 and one signal (if a chain has a kind that splits it) shared by all chains -- every clip belongs to one chain
+ * at a step, and the kernels skip the clips of the others -- then per chain what its backward pass needs from its forward
+ * pass (responses and spectra of the reverberation, the two spectra of the phase vocoder, the signal between a stretch and a
+ * speed change), then int [B] choices at the next 256-byte boundary.  For one chain that is
+ * aware_embed_loop_attack_workspace_bytes_ex rounded up to 256, plus 4 * B.
+ * aware_embed_buffer 14: int [B], the choices of the last forward pass (NULL without a mixture); 12 as before; 13 the
+ * responses of the mixture's reverberation chain (a row is refreshed at the steps its clip draws that chain; zeros before).
+ * aware_loop_mixture_draw: the draw alone, for B seeds (dev) at `step`, weights on the host, choice dev int [B]; one launch.
+ * Added without a version step: callers detect the addition by symbol. */
+typedef struct aware_loop_chain { const aware_loop_attack_ex* attacks; int n_attacks; float weight; } aware_loop_chain;
+size_t aware_embed_loop_mixture_workspace_bytes(const aware_batch* batch, const aware_loop_chain* chains, int n_chains);
+int aware_embed_set_loop_mixture(aware_embed* e, const aware_loop_chain* chains, int n_chains, const uint32_t* seeds,
+                                 void* workspace, size_t workspace_bytes, void* stream);
+int aware_loop_mixture_draw(const uint32_t* seeds, int B, int step, const float* weights, int n_chains, int* choice,
+                            void* stream);
 
 /* ---- offset search in detection (EXTENSION, parity unpinned: the reference detects at the clip's own start only) -----------
  * The detector pools pairs of frames of hop 256, so its read-out has a period of 512 samples in where the clip starts, and a

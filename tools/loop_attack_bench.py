@@ -9,6 +9,10 @@
       (prob 0.75), with the reverberation, the reverberation followed by noise and the speed change in the loop, then clean /
       Gaussian noise at 10 and 5 dB / 0.5 s and 0.3 s zeroed / reverberation of rt60 0.1 and 0.3 s / an echo of 100 ms x 0.7 /
       polyphase resampling at 101/100, 21/20, 20/21, 11/10 and 10/11 (--no-ber skips it).
+`--mixture a,b` adds the named attack mixtures of MIXTURES and each of their chains alone to (a), so that
+a mixture's iteration reads against the weighted mean and the sum of its chains.  `--dump FILE` does none of the above: it runs
+20 iterations of a kind-0/1 chain and of a pitch-shift chain on ten 1 s clips and writes the sha256 of the coefficients, the best
+coefficients, the losses and the finished waveform, the record a change to the loop is compared against.
 `--only-loop` runs a few steps of every variant and nothing else, for a per-kernel trace
 (rocprofv3 --kernel-trace --stats -- python tools/loop_attack_bench.py --only-loop)."""
 import argparse
@@ -43,6 +47,45 @@ VARIANTS = {
     "suppression_delete_noise": [{"kind": "sample_suppression", "seconds": 0.3}, {"kind": "delete_samples", "seconds": [0.01, 0.2], "at": "anywhere", "prob": 0.75},
                                  {"kind": "gaussian_noise", "snr_db": 10.0}],
 }
+
+
+MIXTURES = {
+    "four_families": [
+        {"weight": 0.2, "chain": [{"kind": "sample_suppression", "seconds": 0.3, "prob": 0.75}, {"kind": "gaussian_noise", "snr_db": 10.0}]},
+        {"weight": 0.2, "chain": [{"kind": "reverberation", "rt60": [0.1, 0.5], "drr_db": -3.0, "prob": 0.75},
+                                  {"kind": "gaussian_noise", "snr_db": 20.0}]},
+        {"weight": 0.2, "chain": [{"kind": "phase_vocoder", "rate": [0.85, 1.15], "cents": 150.0, "prob": 0.9}]},
+        {"weight": 0.2, "chain": [{"kind": "delete_samples", "seconds": [0.01, 0.2], "at": "anywhere", "prob": 0.75},
+                                  {"kind": "gaussian_noise", "snr_db": 10.0}]},
+    ],
+    "tempo_pitch": [
+        {"weight": 0.4, "chain": [{"kind": "time_stretch", "rate": [0.85, 1.15]}, {"kind": "speed_change", "cents": 200.0}]},
+        {"weight": 0.3, "chain": [{"kind": "pitch_shift", "cents": 150.0}]},
+        {"weight": 0.3, "chain": [{"kind": "speed_change", "cents": 200.0}, {"kind": "gaussian_noise", "snr_db": 10.0}]},
+    ],
+}
+
+
+def dump(emb, path):
+    """sha256 of what 20 iterations of a single-chain handle leave, per chain; written to `path` unless it is empty."""
+    import hashlib
+    B, n = 10, 16000
+    g = torch.Generator(device="cuda").manual_seed(11)
+    audio = 0.1 * torch.randn(B * n, generator=g, device="cuda")
+    target = torch.randint(0, 2, (B, 20), generator=g, device="cuda").float() * 2 - 1
+    batch = rt.Batch([n] * B)
+    out = {}
+    for name in ("both", "pitch"):
+        emb.loop_attacks, emb.loop_attack_mixture = VARIANTS[name], []
+        sess = emb.start_session(batch, 16000)
+        sess.begin(audio, target)
+        sess.iterate(20)
+        parts = {"coef": sess.coef, "best": sess.best_coef, "loss": sess.loss, "best_loss": sess.best_loss, "out": sess.finish(None)}
+        out[name] = {k: hashlib.sha256(v.detach().cpu().numpy().tobytes()).hexdigest() for k, v in parts.items()}
+    if path:
+        with open(path, "w") as f:
+            json.dump(out, f, indent=1, sort_keys=True)
+    return out
 
 
 def sync_timing(det, audio, B, n, views):
@@ -91,10 +134,15 @@ def main():
     ap.add_argument("--only-loop", action="store_true")
     ap.add_argument("--variants", default="")
     ap.add_argument("--sync", type=int, default=0)
+    ap.add_argument("--mixture", default="")
+    ap.add_argument("--dump", default="")
     args = ap.parse_args()
     B, n = args.clips, int(args.seconds * 16000)
     emb, det = load()
     emb.verbose = False
+    if args.dump:
+        print(json.dumps(dump(emb, args.dump)))
+        return
     g = torch.Generator(device="cuda").manual_seed(3)
     audio = 0.1 * torch.randn(B * n, generator=g, device="cuda")
     bits = torch.randint(0, 2, (B, 20), generator=g, device="cuda")
@@ -108,10 +156,20 @@ def main():
         print(f"detect: plain {t['plain']:.1f} us, sync_search = {args.sync}: {t['search']:.1f} us ({t['search'] / t['plain']:.2f} x)")
     chosen = {"none"} | {v for v in args.variants.split(",") if v}
     variants = {k: v for k, v in VARIANTS.items() if not args.variants or k in chosen}
+    mixtures = {}
+    for m in [v for v in args.mixture.split(",") if v]:
+        mixtures[f"mixture:{m}"] = MIXTURES[m]
+        for c, entry in enumerate(MIXTURES[m]):
+            variants[f"{m}/{c}"] = entry["chain"]
     sessions = {}
     for name, chain in variants.items():
-        emb.loop_attacks = chain or []
+        emb.loop_attacks, emb.loop_attack_mixture = chain or [], []
         sessions[name] = emb.start_session(batch, 16000)
+    for name, mix in mixtures.items():
+        emb.loop_attacks, emb.loop_attack_mixture = [], mix
+        sessions[name] = emb.start_session(batch, 16000)
+    emb.loop_attack_mixture = []
+    variants = {**variants, **mixtures}
     steps = 16 if args.only_loop else args.steps
     times = {name: [] for name in variants}
     for _ in range(1 if args.only_loop else args.rounds):
