@@ -14,6 +14,8 @@
 #include "../../include/aware_hip.h"
 #include "common.hpp"
 #include "kernels.h"
+#define AWARE_LOOP_CF cf
+#include "loop_chain.hpp"
 
 using namespace aware;
 
@@ -590,20 +592,7 @@ static void run_synth(SynthLaunch& S, int dsp_path, hipStream_t st) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// workspace carving
-struct Carver {
-    char* base;       // null: only count (off is then the workspace size)
-    size_t off = 0, cap;
-    bool ok = true;
-    Carver(void* p, size_t c) : base((char*)p), cap(c) {}
-    template <typename Tp> Tp* take(size_t count) {
-        off = (off + 255) & ~(size_t)255;
-        Tp* r = base ? (Tp*)(base + off) : nullptr;
-        off += count * sizeof(Tp);
-        if (off > cap) ok = false;
-        return r;
-    }
-};
+// workspace carving: Carver is in loop_chain.hpp
 
 // ---------------------------------------------------------------------------------------------
 extern "C" int aware_stft(const aware_plan* plan, const aware_batch* b, const float* audio, int normalize, void* spec,
@@ -1699,57 +1688,16 @@ struct aware_embed {
     } opt;
     // attack-aware embedding (aware_embed_set_loop_attacks; EXTENSION): the chain and its buffers in the caller's second
     // workspace.  n == 0: the loop issues exactly the launches of the plain loop
-    struct LoopChainState {
-        int n = 0;
-        int kind[kMaxLoopAttacks] = {0}, k[kMaxLoopAttacks] = {0};
-        double inv_snr[kMaxLoopAttacks] = {0};
-        float prob[kMaxLoopAttacks] = {0};
-        float* z = nullptr;                       // [NS] the attacked signal
-        unsigned long long* pmaxZ = nullptr;      // [B][pstride]
-        double* psq = nullptr;                    // [kMaxLoopAttacks][B][pstride] partial sums of squares per noise entry
-        double* pdot = nullptr;                   // [B][pstride] partial sums of dL/dx * x for the analysis adjoint
-        float* gpad0 = nullptr;                   // [B][2][512] zeros: the pads are folded before the analysis adjoint
-        unsigned* seeds = nullptr;                // [B]
-        // reverberation (aware_embed_set_loop_attacks_ex): entry rv of the chain, -1 without one
-        int rv = -1, n_lo = 0, n_hi = 0, kmax = 0;
-        double gain = 0;                          // 10^(drr_db / 20)
-        float* u = nullptr;                       // [NS] the convolution's input: the entries in front of it on N(N(yraw))
-        float* h = nullptr;                       // [B][8192] the impulse responses of the last forward pass
-        int* nh = nullptr;                        // [B] their lengths, 0 where the entry did not fire
-        cf* tables = nullptr;                     // W_2048 half table, W_4096 table
-        cf* hspec = nullptr;                      // [B][4][2056]
-        cf* xspec = nullptr;                      // [B][kmax][2056]
-        // speed change (kind 3): entry sp of the chain, -1 without one; it shares u with the reverberation, which it excludes
-        int sp = -1, m_lo = 0, m_hi = 0;
-        // time stretch (kind 4): entry ts of the chain, -1 without one; it reads u as the speed change does.  A speed change
-        // directly behind it (sp == ts + 1) forms one stage u -> v -> z with it
-        int ts = -1, q_lo = 0, q_hi = 0;
-        float* v = nullptr;                       // [NS] between the stretch and the speed change of such a pair
-        // pitch shift (kind 5): entry ps of the chain, -1 without one; it excludes the three kinds above, reads u as the
-        // speed change does and draws from the speed offsets [p_lo, p_hi]
-        int ps = -1, p_lo = 0, p_hi = 0;
-        // phase vocoder (kind 6): entry pv of the chain, -1 without one; it excludes the four kinds above and reads u as the
-        // speed change does.  Stretch offsets [pq_lo, pq_hi] and speed offsets [pm_lo, pm_hi], lo > hi where the mode is absent
-        int pv = -1, pq_lo = 0, pq_hi = -1, pm_lo = 0, pm_hi = -1;
-        cf* pvS = nullptr;                        // [NF][520] the spectrum of u; the backward pass turns it into its gradient
-        cf* pvY = nullptr;                        // [NF][520] the vocoded spectrum; the backward pass holds dL/dY in it
-        // sample deletion (kind 7): entry ds of the chain, -1 without one; it excludes the five kinds above and reads u as the
-        // speed change does.  k drawn from [d_lo, d_hi], d_at 0: the cut starts at sample 0, 1: anywhere
-        int ds = -1, d_lo = 0, d_hi = 0, d_at = 0;
-        const float* hann = nullptr;              // stretch_window()
-        bool locked = false;                      // an optimiser step has run: the chain stays what it is
-        LoopGate gate;                            // a chain of a mixture: the clips that drew it (null: every clip)
-    } la;
+    LoopChainState la;
     // attack mixtures (aware_embed_set_loop_mixture; EXTENSION): mix_n chains, one drawn per clip and step into mix_choice.
     // Every clip belongs to one chain at a step, so the chains share z, pmaxZ, psq, pdot, gpad0, seeds and u -- those of `la`,
-    // whose n stays 0 -- and keep only what a backward pass needs from its forward pass (mix[c].h .. xspec, pvS, pvY, v)
+    // whose n stays 0 -- and keep only what a backward pass needs from its forward pass (carve_chain_private)
     int mix_n = 0;
     LoopChainState mix[kMaxLoopChains];
     unsigned long long mix_thr[kMaxLoopChains] = {0};
     int* mix_choice = nullptr;                    // [B]
     int mix_rv = -1;                              // the chain with the reverberation (aware_embed_buffer 13), -1 without one
 };
-using LoopChainState = aware_embed::LoopChainState;
 
 // the embed loop's workspace: the detector's buffers, then the loop state; iters: num_iterations, l1: the L1 term's buffers
 static void carve_embed(Carver& c, const aware_batch* b, const aware_detector* det, int iters, bool l1, aware_embed* e) {
@@ -1938,31 +1886,11 @@ extern "C" int aware_embed_set_optimizer(aware_embed* e, const aware_optimizer_c
     return AWARE_OK;
 }
 
-// Attack-aware embedding (EXTENSION): the chain's buffers live in a workspace of their own, so that
-// aware_embed_workspace_bytes and the layout of the loop's workspace stay what they were
-template <typename LA> static void carve_loop_attacks(Carver& c, const aware_batch* b, LA& la) {
-    const size_t np = (size_t)b->B * b->pstride;
-    la.z = c.take<float>(b->NS);
-    la.pmaxZ = c.take<unsigned long long>(np);
-    la.psq = c.take<double>(np * kMaxLoopAttacks);
-    la.pdot = c.take<double>(np);
-    la.gpad0 = c.take<float>((size_t)b->B * 1024);
-    la.seeds = c.take<unsigned>(b->B);
-}
-// the reverberation's part of that workspace, behind the chain's
-static int reverb_kmax(const aware_batch* b) {
-    int m = 0;
-    for (int i = 0; i < b->B; ++i) m = std::max(m, b->out_len[i]);
-    return reverb_blocks(m);
-}
-template <typename LA> static void carve_loop_reverb(Carver& c, const aware_batch* b, LA& la) {
-    la.kmax = reverb_kmax(b);
-    la.u = c.take<float>(b->NS);
-    la.h = c.take<float>((size_t)b->B * kReverbMaxIr);
-    la.nh = c.take<int>(b->B);
-    la.tables = c.take<cf>(kReverbTwHalf + kReverbBins);
-    la.hspec = c.take<cf>((size_t)b->B * kReverbParts * kReverbBins);
-    la.xspec = c.take<cf>((size_t)b->B * la.kmax * kReverbBins);
+// Attack-aware embedding (EXTENSION): the chains' parser and the carving of their workspace are loop_chain.hpp's
+static LoopDims loop_dims(const aware_batch* b) {
+    LoopDims d;
+    d.B = b->B; d.NS = b->NS; d.NF = b->NF; d.pstride = b->pstride; d.out_len = b->out_len.data();
+    return d;
 }
 // W_2048^j, j < 1024, then W_4096^k, k <= 2048 (padded to 2056), from float64
 static const std::vector<cf>& reverb_tables() {
@@ -1976,126 +1904,36 @@ static const std::vector<cf>& reverb_tables() {
     }();
     return t;
 }
-static bool has_kind(const aware_loop_attack_ex* attacks, int n, int kind) {
-    for (int j = 0; attacks && j < n; ++j)
-        if (attacks[j].kind == kind) return true;
-    return false;
-}
-// the speed change's part: the one signal u it reads
-template <typename LA> static void carve_loop_speed(Carver& c, const aware_batch* b, LA& la) { la.u = c.take<float>(b->NS); }
-// the time stretch's part: the same one signal, and a second one between it and a speed change behind it
-template <typename LA> static void carve_loop_stretch(Carver& c, const aware_batch* b, LA& la, bool pair) {
-    la.u = c.take<float>(b->NS);
-    if (pair) la.v = c.take<float>(b->NS);
-}
-// the phase vocoder's part: the same one signal, and the two spectra between the staged STFT and iSTFT
-template <typename LA> static void carve_loop_pv(Carver& c, const aware_batch* b, LA& la) {
-    la.u = c.take<float>(b->NS);
-    la.pvS = c.take<cf>((size_t)b->NF * 520);
-    la.pvY = c.take<cf>((size_t)b->NF * 520);
-}
 extern "C" size_t aware_embed_loop_attack_workspace_bytes(const aware_batch* b, int n_attacks) {
     if (!b || b->general || n_attacks < 1 || n_attacks > kMaxLoopAttacks) return 0;
     Carver c(nullptr, 0);
-    aware_embed e;
-    carve_loop_attacks(c, b, e.la);
+    LoopChainState la;
+    carve_chain_shared(c, loop_dims(b), la);
     return c.off;
 }
 extern "C" size_t aware_embed_loop_attack_workspace_bytes_ex(const aware_batch* b, const aware_loop_attack_ex* attacks,
                                                              int n_attacks) {
-    if (!b || b->general || !attacks || n_attacks < 1 || n_attacks > kMaxLoopAttacks) return 0;
-    Carver c(nullptr, 0);
-    aware_embed e;
-    carve_loop_attacks(c, b, e.la);
-    if (has_kind(attacks, n_attacks, AWARE_LOOP_REVERBERATION)) carve_loop_reverb(c, b, e.la);
-    else if (has_kind(attacks, n_attacks, AWARE_LOOP_PHASE_VOCODER)) carve_loop_pv(c, b, e.la);
-    else if (has_kind(attacks, n_attacks, AWARE_LOOP_TIME_STRETCH))
-        carve_loop_stretch(c, b, e.la, has_kind(attacks, n_attacks, AWARE_LOOP_SPEED_CHANGE));
-    else if (has_kind(attacks, n_attacks, AWARE_LOOP_SPEED_CHANGE) || has_kind(attacks, n_attacks, AWARE_LOOP_PITCH_SHIFT) ||
-             has_kind(attacks, n_attacks, AWARE_LOOP_DELETE_SAMPLES))
-        carve_loop_speed(c, b, e.la);
-    return c.off;
-}
-// one chain's entries into its state: every AWARE_E_BADARG / AWARE_E_UNSUPPORTED of the setters, no buffer touched
-static int parse_loop_chain(const aware_batch* b, const aware_loop_attack_ex* attacks, int n_attacks, bool ex, LoopChainState& la) {
-    static_assert(AWARE_LOOP_GAUSSIAN_NOISE == kLoopGaussianNoise && AWARE_LOOP_SAMPLE_SUPPRESSION == kLoopSampleSuppression &&
-                  AWARE_LOOP_REVERBERATION == kLoopReverberation && AWARE_LOOP_SPEED_CHANGE == kLoopSpeedChange &&
-                  AWARE_LOOP_TIME_STRETCH == kLoopTimeStretch && AWARE_LOOP_PITCH_SHIFT == kLoopPitchShift &&
-                  AWARE_LOOP_PHASE_VOCODER == kLoopPhaseVocoder && AWARE_LOOP_DELETE_SAMPLES == kLoopDeleteSamples, "");
-    if (!attacks || n_attacks < 1 || n_attacks > kMaxLoopAttacks) return AWARE_E_BADARG;
-    la.rv = -1; la.sp = -1; la.ts = -1; la.ps = -1; la.pv = -1; la.ds = -1; la.h = nullptr; la.v = nullptr;
-    for (int j = 0; j < n_attacks; ++j) {
-        const aware_loop_attack_ex& a = attacks[j];
-        if (!(a.prob >= 0.f && a.prob <= 1.f)) return AWARE_E_BADARG;
-        la.kind[j] = a.kind; la.prob[j] = a.prob; la.k[j] = 0; la.inv_snr[j] = 0.0;
-        if (a.kind == AWARE_LOOP_GAUSSIAN_NOISE) {
-            if (!std::isfinite(a.param[0])) return AWARE_E_BADARG;
-            la.inv_snr[j] = pow(10.0, -(double)a.param[0] / 10.0);
-        } else if (a.kind == AWARE_LOOP_SAMPLE_SUPPRESSION) {
-            if (!(a.param[0] >= 1.f) || a.param[0] > 2147483520.f || a.param[0] != floorf(a.param[0])) return AWARE_E_BADARG;
-            la.k[j] = (int)a.param[0];
-        } else if (a.kind == AWARE_LOOP_REVERBERATION && ex) {
-            const float lo = a.param[0], hi = a.param[1], drr = a.param[2];
-            if (la.rv >= 0 || la.sp >= 0 || la.ts >= 0 || la.ps >= 0 || la.pv >= 0 || la.ds >= 0) return AWARE_E_BADARG;     // one reverberation per chain, and no other kind that splits a chain beside it
-            if (!(lo >= 2.f) || !(hi <= (float)kReverbMaxIr) || !(lo <= hi) || lo != floorf(lo) || hi != floorf(hi) ||
-                !std::isfinite(drr))
-                return AWARE_E_BADARG;
-            la.rv = j; la.n_lo = (int)lo; la.n_hi = (int)hi; la.gain = pow(10.0, (double)drr / 20.0);
-        } else if (a.kind == AWARE_LOOP_SPEED_CHANGE && ex) {
-            const float lo = a.param[0], hi = a.param[1];
-            if (la.rv >= 0 || la.sp >= 0 || la.ps >= 0 || la.pv >= 0 || la.ds >= 0) return AWARE_E_BADARG;     // one speed change per chain, and no reverberation, pitch shift or phase vocoder beside it
-            if (la.ts >= 0 && la.ts != j - 1) return AWARE_E_BADARG; // beside a time stretch: directly behind it
-            if (!(lo >= (float)kSpeedMin) || !(hi <= (float)kSpeedMax) || !(lo <= hi) || lo != floorf(lo) || hi != floorf(hi))
-                return AWARE_E_BADARG;
-            la.sp = j; la.m_lo = (int)lo; la.m_hi = (int)hi;
-        } else if (a.kind == AWARE_LOOP_TIME_STRETCH && ex) {
-            const float lo = a.param[0], hi = a.param[1];
-            // one time stretch per chain, no reverberation, pitch shift or phase vocoder beside it, and no speed change in front of it
-            if (la.rv >= 0 || la.sp >= 0 || la.ts >= 0 || la.ps >= 0 || la.pv >= 0 || la.ds >= 0) return AWARE_E_BADARG;
-            if (!(lo >= (float)kStretchMin) || !(hi <= (float)kStretchMax) || !(lo <= hi) || lo != floorf(lo) || hi != floorf(hi))
-                return AWARE_E_BADARG;
-            la.ts = j; la.q_lo = (int)lo; la.q_hi = (int)hi;
-        } else if (a.kind == AWARE_LOOP_PITCH_SHIFT && ex) {
-            const float lo = a.param[0], hi = a.param[1];
-            // one pitch shift per chain, and none of the other kinds that split a chain beside it
-            if (la.rv >= 0 || la.sp >= 0 || la.ts >= 0 || la.ps >= 0 || la.pv >= 0 || la.ds >= 0) return AWARE_E_BADARG;
-            if (!(lo >= (float)kSpeedMin) || !(hi <= (float)kSpeedMax) || !(lo <= hi) || lo != floorf(lo) || hi != floorf(hi))
-                return AWARE_E_BADARG;
-            la.ps = j; la.p_lo = (int)lo; la.p_hi = (int)hi;
-        } else if (a.kind == AWARE_LOOP_PHASE_VOCODER && ex) {
-            // one phase vocoder per chain, and none of the other kinds that split a chain beside it; param = {mq_lo, mq_hi,
-            // m_lo, m_hi}, a mode with lo > hi is absent, and one of the two is there
-            if (la.rv >= 0 || la.sp >= 0 || la.ts >= 0 || la.ps >= 0 || la.pv >= 0 || la.ds >= 0) return AWARE_E_BADARG;
-            for (int i = 0; i < 4; ++i)
-                if (!(fabsf(a.param[i]) <= 65536.f) || a.param[i] != floorf(a.param[i])) return AWARE_E_BADARG;
-            const int ql = (int)a.param[0], qh = (int)a.param[1], ml = (int)a.param[2], mh = (int)a.param[3];
-            if (ql > qh && ml > mh) return AWARE_E_BADARG;
-            if (ql <= qh && (ql < kStretchMin || qh > kStretchMax)) return AWARE_E_BADARG;
-            if (ml <= mh && (ml < kSpeedMin || mh > kSpeedMax)) return AWARE_E_BADARG;
-            la.pv = j; la.pq_lo = ql; la.pq_hi = qh; la.pm_lo = ml; la.pm_hi = mh;
-        } else if (a.kind == AWARE_LOOP_DELETE_SAMPLES && ex) {
-            // one sample deletion per chain, and none of the other kinds that split a chain beside it; param = {k_lo, k_hi, at, 0}
-            const float lo = a.param[0], hi = a.param[1], at = a.param[2];
-            if (la.rv >= 0 || la.sp >= 0 || la.ts >= 0 || la.ps >= 0 || la.pv >= 0 || la.ds >= 0) return AWARE_E_BADARG;
-            if (!(lo >= 1.f) || !(hi <= 2147483520.f) || !(lo <= hi) || lo != floorf(lo) || hi != floorf(hi) ||
-                !(at == 0.f || at == 1.f))
-                return AWARE_E_BADARG;
-            la.ds = j; la.d_lo = (int)lo; la.d_hi = (int)hi; la.d_at = (int)at;
-        } else {
-            return AWARE_E_BADARG;
-        }
-    }
-    for (int j = 0; j < n_attacks; ++j)
-        for (int i = 0; i < b->B; ++i)
-            if ((la.kind[j] == AWARE_LOOP_SAMPLE_SUPPRESSION && la.k[j] >= b->out_len[i]) ||
-                (la.kind[j] == AWARE_LOOP_DELETE_SAMPLES && la.d_hi >= b->out_len[i]))
-                return AWARE_E_UNSUPPORTED;
-    la.n = n_attacks;
-    return AWARE_OK;
+    return (b && !b->general) ? loop_chain_workspace_bytes(loop_dims(b), attacks, n_attacks) : 0;
 }
 static void clear_loop_chain(aware_embed* e) {
-    e->la.n = 0; e->la.z = nullptr; e->la.rv = -1; e->la.sp = -1; e->la.ts = -1; e->la.ps = -1; e->la.pv = -1; e->la.ds = -1; e->la.h = nullptr;
+    e->la.n = 0; e->la.z = nullptr; e->la.split = -1; e->la.pair_speed = -1; e->la.h = nullptr;
     e->mix_n = 0; e->mix_choice = nullptr; e->mix_rv = -1;
+}
+// what both setters do to a chain's buffers before the first step: the window of the overlap-add kinds (`hann`: the one a
+// mixture's earlier chain fetched), and the reverberation's twiddles and zeroed responses (those of a clip that never draws
+// the chain read as zeros)
+static int init_chain_buffers(LoopChainState& la, const aware_batch* b, const float*& hann, hipStream_t st) {
+    if (chain_has(la, AWARE_LOOP_TIME_STRETCH) || chain_has(la, AWARE_LOOP_PITCH_SHIFT)) {
+        if (!hann && !(hann = stretch_window())) return AWARE_E_HIP;
+    }
+    la.hann = hann;
+    if (chain_has(la, AWARE_LOOP_REVERBERATION)) {
+        const std::vector<cf>& t = reverb_tables();
+        HIPCHK(hipMemcpyAsync(la.tables, t.data(), t.size() * sizeof(cf), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemsetAsync(la.h, 0, (size_t)b->B * kReverbMaxIr * sizeof(float), st));
+        HIPCHK(hipMemsetAsync(la.nh, 0, (size_t)b->B * sizeof(int), st));
+    }
+    return AWARE_OK;
 }
 static int set_loop_attacks(aware_embed* e, const aware_loop_attack_ex* attacks, int n_attacks, bool ex,
                             const uint32_t* seeds, void* workspace, size_t workspace_bytes, void* stream) {
@@ -2106,24 +1944,15 @@ static int set_loop_attacks(aware_embed* e, const aware_loop_attack_ex* attacks,
     const aware_batch* b = e->b;
     auto la = e->la;
     la.gate = LoopGate();
-    if (int rc = parse_loop_chain(b, attacks, n_attacks, ex, la)) return rc;
+    if (int rc = parse_loop_chain(loop_dims(b), attacks, n_attacks, ex, la)) return rc;
     Carver c(workspace, workspace_bytes);
-    carve_loop_attacks(c, b, la);
-    if (la.rv >= 0) carve_loop_reverb(c, b, la);
-    else if (la.pv >= 0) carve_loop_pv(c, b, la);
-    else if (la.ts >= 0) carve_loop_stretch(c, b, la, la.sp >= 0);
-    else if (la.sp >= 0 || la.ps >= 0 || la.ds >= 0) carve_loop_speed(c, b, la);
+    carve_loop_chain(c, loop_dims(b), la);
     if (!c.ok) return AWARE_E_WORKSPACE;
-    if ((la.ts >= 0 || la.ps >= 0) && !(la.hann = stretch_window())) return AWARE_E_HIP;
     hipStream_t st = (hipStream_t)stream;
+    const float* hann = nullptr;
+    if (int rc = init_chain_buffers(la, b, hann, st)) return rc;
     HIPCHK(hipMemsetAsync(la.gpad0, 0, (size_t)b->B * 1024 * sizeof(float), st));
     HIPCHK(hipMemcpyAsync(la.seeds, seeds, (size_t)b->B * sizeof(unsigned), hipMemcpyHostToDevice, st));
-    if (la.rv >= 0) {
-        const std::vector<cf>& t = reverb_tables();
-        HIPCHK(hipMemcpyAsync(la.tables, t.data(), t.size() * sizeof(cf), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemsetAsync(la.h, 0, (size_t)b->B * kReverbMaxIr * sizeof(float), st));
-        HIPCHK(hipMemsetAsync(la.nh, 0, (size_t)b->B * sizeof(int), st));
-    }
     HIPCHK(hipStreamSynchronize(st));
     la.n = n_attacks;
     e->la = la;
@@ -2144,67 +1973,8 @@ extern "C" int aware_embed_set_loop_attacks_ex(aware_embed* e, const aware_loop_
 }
 
 // ---- attack mixtures (EXTENSION): one of several chains drawn per clip and step (loop_mix_kernels.hip)
-static bool chain_splits(const LoopChainState& la) {
-    return la.rv >= 0 || la.sp >= 0 || la.ts >= 0 || la.ps >= 0 || la.pv >= 0 || la.ds >= 0;
-}
-// The mixture's workspace: what the chains share (the buffers of a chain of kinds 0/1, and the one signal u if a chain has a
-// kind that splits it), then per chain what its backward pass needs from its forward pass, then the choices.  For one chain
-// this is the layout of aware_embed_set_loop_attacks_ex followed by int [B] at the next 256-byte boundary.
-static void carve_loop_mixture(Carver& c, const aware_batch* b, LoopChainState& shared, LoopChainState* mix, int n, int*& choice) {
-    carve_loop_attacks(c, b, shared);
-    bool any_u = false;
-    for (int i = 0; i < n; ++i) any_u = any_u || chain_splits(mix[i]);
-    shared.u = any_u ? c.take<float>(b->NS) : nullptr;
-    for (int i = 0; i < n; ++i) {
-        LoopChainState& la = mix[i];
-        la.z = shared.z; la.pmaxZ = shared.pmaxZ; la.psq = shared.psq; la.pdot = shared.pdot; la.gpad0 = shared.gpad0;
-        la.seeds = shared.seeds; la.u = shared.u;
-        if (la.rv >= 0) {
-            la.kmax = reverb_kmax(b);
-            la.h = c.take<float>((size_t)b->B * kReverbMaxIr);
-            la.nh = c.take<int>(b->B);
-            la.tables = c.take<cf>(kReverbTwHalf + kReverbBins);
-            la.hspec = c.take<cf>((size_t)b->B * kReverbParts * kReverbBins);
-            la.xspec = c.take<cf>((size_t)b->B * la.kmax * kReverbBins);
-        } else if (la.pv >= 0) {
-            la.pvS = c.take<cf>((size_t)b->NF * 520);
-            la.pvY = c.take<cf>((size_t)b->NF * 520);
-        } else if (la.ts >= 0 && la.sp >= 0) {
-            la.v = c.take<float>(b->NS);
-        }
-    }
-    choice = c.take<int>(b->B);
-}
-// the chains and weights into states and thresholds; rc as the setter's
-static int parse_loop_mixture(const aware_batch* b, const aware_loop_chain* chains, int n_chains, LoopChainState* mix,
-                              unsigned long long* thr, int& mix_rv) {
-    if (!b || b->general || !chains || n_chains < 1 || n_chains > kMaxLoopChains) return AWARE_E_BADARG;
-    float w[kMaxLoopChains] = {0};
-    double sum = 0.0;
-    mix_rv = -1;
-    for (int i = 0; i < n_chains; ++i) {
-        if (!std::isfinite(chains[i].weight) || chains[i].weight < 0.f) return AWARE_E_BADARG;
-        w[i] = chains[i].weight; sum += (double)w[i];
-        mix[i] = LoopChainState();
-        if (int rc = parse_loop_chain(b, chains[i].attacks, chains[i].n_attacks, true, mix[i])) return rc;
-        if (mix[i].rv >= 0) {
-            if (mix_rv >= 0) return AWARE_E_BADARG;            // one reverberation chain per mixture: aware_embed_buffer 13 is its responses
-            mix_rv = i;
-        }
-    }
-    if (sum > 1.0 + 1e-6) return AWARE_E_BADARG;
-    loop_mix_thresholds(w, n_chains, thr);
-    return AWARE_OK;
-}
 extern "C" size_t aware_embed_loop_mixture_workspace_bytes(const aware_batch* b, const aware_loop_chain* chains, int n_chains) {
-    LoopChainState shared, mix[kMaxLoopChains];
-    unsigned long long thr[kMaxLoopChains];
-    int rv = -1, *choice = nullptr;
-    int rc = parse_loop_mixture(b, chains, n_chains, mix, thr, rv);
-    if (rc != AWARE_OK && rc != AWARE_E_UNSUPPORTED) return 0;
-    Carver c(nullptr, 0);
-    carve_loop_mixture(c, b, shared, mix, n_chains, choice);
-    return c.off;
+    return (b && !b->general) ? loop_mixture_workspace_bytes(loop_dims(b), chains, n_chains) : 0;
 }
 extern "C" int aware_embed_set_loop_mixture(aware_embed* e, const aware_loop_chain* chains, int n_chains, const uint32_t* seeds,
                                             void* workspace, size_t workspace_bytes, void* stream) {
@@ -2213,36 +1983,27 @@ extern "C" int aware_embed_set_loop_mixture(aware_embed* e, const aware_loop_cha
     if (n_chains == 0) { clear_loop_chain(e); return AWARE_OK; }
     if (!chains || !seeds || !workspace || ((uintptr_t)workspace & 255)) return AWARE_E_BADARG;
     const aware_batch* b = e->b;
+    if (b->general) return AWARE_E_BADARG;
     LoopChainState shared, mix[kMaxLoopChains];
     unsigned long long thr[kMaxLoopChains];
     int rv = -1, *choice = nullptr;
-    if (int rc = parse_loop_mixture(b, chains, n_chains, mix, thr, rv)) return rc;
+    if (int rc = parse_loop_mixture(loop_dims(b), chains, n_chains, mix, thr, rv)) return rc;
     Carver c(workspace, workspace_bytes);
-    carve_loop_mixture(c, b, shared, mix, n_chains, choice);
+    carve_loop_mixture(c, loop_dims(b), shared, mix, n_chains, choice);
     if (!c.ok) return AWARE_E_WORKSPACE;
-    const float* hann = nullptr;
-    for (int i = 0; i < n_chains; ++i)
-        if ((mix[i].ts >= 0 || mix[i].ps >= 0) && !hann && !(hann = stretch_window())) return AWARE_E_HIP;
     hipStream_t st = (hipStream_t)stream;
+    const float* hann = nullptr;
+    for (int i = 0; i < n_chains; ++i) {
+        mix[i].gate.choice = choice; mix[i].gate.chain = i;
+        if (int rc = init_chain_buffers(mix[i], b, hann, st)) return rc;
+    }
     HIPCHK(hipMemsetAsync(shared.gpad0, 0, (size_t)b->B * 1024 * sizeof(float), st));
     HIPCHK(hipMemcpyAsync(shared.seeds, seeds, (size_t)b->B * sizeof(unsigned), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetD32Async((hipDeviceptr_t)choice, -1, b->B, st));
-    // a clip reaches a chain's stage only at the steps it draws the chain: the signals in between start as zeros, so that
-    // a kernel that is not gated per clip (none today) would read numbers, and the responses of a clip that never drew
-    // the reverberation chain read as zeros
+    // a clip reaches a chain's stage only at the steps it draws the chain.  Every stage kernel is gated per clip, so the
+    // signals in between are never read where they were not written; they start as zeros all the same
     HIPCHK(hipMemsetAsync(shared.z, 0, (size_t)b->NS * sizeof(float), st));
     if (shared.u) HIPCHK(hipMemsetAsync(shared.u, 0, (size_t)b->NS * sizeof(float), st));
-    for (int i = 0; i < n_chains; ++i) {
-        LoopChainState& la = mix[i];
-        la.hann = hann;
-        la.gate.choice = choice; la.gate.chain = i;
-        if (la.rv >= 0) {
-            const std::vector<cf>& t = reverb_tables();
-            HIPCHK(hipMemcpyAsync(la.tables, t.data(), t.size() * sizeof(cf), hipMemcpyHostToDevice, st));
-            HIPCHK(hipMemsetAsync(la.h, 0, (size_t)b->B * kReverbMaxIr * sizeof(float), st));
-            HIPCHK(hipMemsetAsync(la.nh, 0, (size_t)b->B * sizeof(int), st));
-        }
-    }
     HIPCHK(hipStreamSynchronize(st));
     clear_loop_chain(e);                                           // a mixture replaces a plain chain
     const bool locked = e->la.locked;
@@ -2383,7 +2144,7 @@ extern "C" int aware_pitch_shift_ola(const float* in, const int* in_off, const i
 extern "C" int aware_pv_frames(const void* spec, const int* frame_off, int B, const int* mq, void* out, void* stream) {
     if (!spec || !frame_off || !mq || !out || spec == out || B < 1 || B > 65535) return AWARE_E_BADARG;
     PvLaunch L;
-    L.spec = spec; L.out = out; L.frame_off = frame_off; L.B = B; L.mq = mq;
+    L.spec = spec; L.out = out; L.draw.frame_off = frame_off; L.B = B; L.mq = mq;
     launch_pv_frames(L, 0, (hipStream_t)stream);
     LAUNCHCHK();
     return AWARE_OK;
@@ -2392,7 +2153,7 @@ extern "C" int aware_pv_frames_bwd(const void* spec, const void* grad_out, const
                                    void* grad_spec, void* stream) {
     if (!spec || !grad_out || !frame_off || !mq || !grad_spec || grad_out == grad_spec || B < 1 || B > 65535) return AWARE_E_BADARG;
     PvLaunch L;
-    L.spec = spec; L.grad = grad_out; L.out = grad_spec; L.frame_off = frame_off; L.B = B; L.mq = mq;
+    L.spec = spec; L.grad = grad_out; L.out = grad_spec; L.draw.frame_off = frame_off; L.B = B; L.mq = mq;
     launch_pv_frames(L, 1, (hipStream_t)stream);
     LAUNCHCHK();
     return AWARE_OK;
@@ -2427,7 +2188,7 @@ extern "C" void* aware_embed_buffer(aware_embed* e, int which) {
         case 12: return (e->la.n || e->mix_n) ? e->la.z : nullptr;  // the attacked signal of the last forward pass
         case 13:                                                    // its impulse responses, f32 [B][8192]
             if (e->mix_n) return e->mix_rv >= 0 ? e->mix[e->mix_rv].h : nullptr;
-            return (e->la.n && e->la.rv >= 0) ? e->la.h : nullptr;
+            return (e->la.n && chain_has(e->la, AWARE_LOOP_REVERBERATION)) ? e->la.h : nullptr;
         case 14: return e->mix_n ? e->mix_choice : nullptr;         // a mixture's choices of the last forward pass, int [B]
         default: return nullptr;
     }
@@ -2471,39 +2232,40 @@ extern "C" int aware_embed_begin(aware_embed* e, const float* audio, const float
     return AWARE_OK;
 }
 
+// the loop side of a stage launch that serves entry `entry` of the chain
+static LoopDraw loop_draw(const aware_embed* e, const LoopChainState& la, int step_back, int entry) {
+    LoopDraw D;
+    D.frame_off = e->b->d_frame_off; D.pstride = e->b->pstride; D.run_blocks = e->b->synth_run;
+    D.step = e->step; D.step_back = step_back; D.seeds = la.seeds; D.entry = entry; D.prob = la.prob[entry];
+    D.gate = la.gate;
+    return D;
+}
+// a launch struct of the in -> out family (speed change, time stretch, pitch shift, sample deletion) for the splitting entry,
+// or for the speed change of a stretch-then-speed pair
+template <typename Launch>
+static Launch stage_launch(const aware_embed* e, const LoopChainState& la, const float* in, float* out, int adjoint, int step_back,
+                           bool of_pair = false) {
+    Launch S;
+    S.in = in; S.out = out; S.B = e->b->B; S.adjoint = adjoint;
+    S.draw = loop_draw(e, la, step_back, of_pair ? la.pair_speed : la.split);
+    return S;
+}
 static SpeedLaunch speed_launch(const aware_embed* e, const LoopChainState& la, const float* in, float* out, int adjoint, int step_back) {
-    SpeedLaunch S;
-    S.in = in; S.out = out; S.B = e->b->B; S.adjoint = adjoint; S.frame_off = e->b->d_frame_off; S.pstride = e->b->pstride;
-    S.run_blocks = e->b->synth_run; S.step = e->step; S.step_back = step_back; S.seeds = la.seeds; S.entry = la.sp;
-    S.m_lo = la.m_lo; S.m_hi = la.m_hi; S.prob = la.prob[la.sp];
-    S.gate = la.gate;
+    const bool of_pair = la.pair_speed >= 0;
+    SpeedLaunch S = stage_launch<SpeedLaunch>(e, la, in, out, adjoint, step_back, of_pair);
+    S.m_lo = of_pair ? la.lo2 : la.lo; S.m_hi = of_pair ? la.hi2 : la.hi;
     return S;
 }
-
 static DeleteLaunch delete_launch(const aware_embed* e, const LoopChainState& la, const float* in, float* out, int adjoint, int step_back) {
-    DeleteLaunch S;
-    S.in = in; S.out = out; S.B = e->b->B; S.adjoint = adjoint; S.frame_off = e->b->d_frame_off; S.pstride = e->b->pstride;
-    S.run_blocks = e->b->synth_run; S.step = e->step; S.step_back = step_back; S.seeds = la.seeds; S.entry = la.ds;
-    S.k_lo = la.d_lo; S.k_hi = la.d_hi; S.at = la.d_at; S.prob = la.prob[la.ds];
-    S.gate = la.gate;
+    DeleteLaunch S = stage_launch<DeleteLaunch>(e, la, in, out, adjoint, step_back);
+    S.k_lo = la.lo; S.k_hi = la.hi; S.at = la.at;
     return S;
 }
-
-static StretchLaunch stretch_launch(const aware_embed* e, const LoopChainState& la, const float* in, float* out, int adjoint, int step_back) {
-    StretchLaunch S;
-    S.in = in; S.out = out; S.window = la.hann; S.B = e->b->B; S.adjoint = adjoint; S.frame_off = e->b->d_frame_off;
-    S.pstride = e->b->pstride; S.run_blocks = e->b->synth_run; S.step = e->step; S.step_back = step_back; S.seeds = la.seeds;
-    S.entry = la.ts; S.m_lo = la.q_lo; S.m_hi = la.q_hi; S.prob = la.prob[la.ts];
-    S.gate = la.gate;
-    return S;
-}
-
-static PitchLaunch pitch_launch(const aware_embed* e, const LoopChainState& la, const float* in, float* out, int adjoint, int step_back) {
-    PitchLaunch S;
-    S.in = in; S.out = out; S.window = la.hann; S.B = e->b->B; S.adjoint = adjoint; S.frame_off = e->b->d_frame_off;
-    S.pstride = e->b->pstride; S.run_blocks = e->b->synth_run; S.step = e->step; S.step_back = step_back; S.seeds = la.seeds;
-    S.entry = la.ps; S.m_lo = la.p_lo; S.m_hi = la.p_hi; S.prob = la.prob[la.ps];
-    S.gate = la.gate;
+// the time stretch and the pitch shift: the window and one range of offsets
+template <typename Launch>
+static Launch ola_launch(const aware_embed* e, const LoopChainState& la, const float* in, float* out, int adjoint, int step_back) {
+    Launch S = stage_launch<Launch>(e, la, in, out, adjoint, step_back);
+    S.window = la.hann; S.m_lo = la.lo; S.m_hi = la.hi;
     return S;
 }
 
@@ -2511,21 +2273,15 @@ static PitchLaunch pitch_launch(const aware_embed* e, const LoopChainState& la, 
 // alone, the resampling of tmp into z.  The transforms are what aware_stft / aware_istft launch, on the loop's signal layout.
 static PvLaunch pv_launch(const aware_embed* e, const LoopChainState& la, int step_back) {
     PvLaunch P;
-    P.frame_off = e->b->d_frame_off; P.B = e->b->B; P.pstride = e->b->pstride; P.run_blocks = e->b->synth_run;
-    P.step = e->step; P.step_back = step_back; P.seeds = la.seeds; P.entry = la.pv; P.prob = la.prob[la.pv];
-    P.q_lo = la.pq_lo; P.q_hi = la.pq_hi; P.m_lo = la.pm_lo; P.m_hi = la.pm_hi;
-    P.gate = la.gate;
+    P.B = e->b->B; P.draw = loop_draw(e, la, step_back, la.split);
+    P.q_lo = la.lo; P.q_hi = la.hi; P.m_lo = la.lo2; P.m_hi = la.hi2;
     return P;
 }
 static SpeedLaunch pv_speed_launch(const aware_embed* e, const LoopChainState& la, const float* in, float* out, int adjoint, int step_back) {
-    SpeedLaunch S;
-    S.in = in; S.out = out; S.B = e->b->B; S.adjoint = adjoint; S.frame_off = e->b->d_frame_off; S.pstride = e->b->pstride;
-    S.run_blocks = e->b->synth_run; S.step = e->step; S.step_back = step_back; S.seeds = la.seeds; S.entry = la.pv;
-    S.prob = la.prob[la.pv];
-    const bool has_m = la.pm_lo <= la.pm_hi;
-    S.m_lo = has_m ? la.pm_lo : 0; S.m_hi = has_m ? la.pm_hi : 0;      // stretch mode alone: m = 0, the identity
-    S.coin = has_m && la.pq_lo <= la.pq_hi;
-    S.gate = la.gate;
+    SpeedLaunch S = stage_launch<SpeedLaunch>(e, la, in, out, adjoint, step_back);
+    const bool has_m = la.lo2 <= la.hi2;
+    S.m_lo = has_m ? la.lo2 : 0; S.m_hi = has_m ? la.hi2 : 0;      // stretch mode alone: m = 0, the identity
+    S.coin = has_m && la.lo <= la.hi;
     return S;
 }
 static void pv_stage_forward(const aware_embed* e, const LoopChainState& la, float* tmp, hipStream_t st) {
@@ -2583,109 +2339,76 @@ static LoopAttackLaunch chain_stage_launch(const aware_embed* e, const LoopChain
     A.step = e->step; A.seeds = la.seeds; A.n = la.n;
     for (int j = 0; j < la.n; ++j) { A.kind[j] = la.kind[j]; A.k[j] = la.k[j]; A.inv_snr[j] = la.inv_snr[j]; A.prob[j] = la.prob[j]; }
     A.yraw = e->yraw; A.pmaxY = e->pmaxY; A.psq = la.psq; A.z = la.z; A.pmaxZ = la.pmaxZ;
-    if (la.rv >= 0 || la.sp >= 0 || la.ts >= 0 || la.ps >= 0 || la.pv >= 0 || la.ds >= 0) { A.idle_plain = 1; A.gpad_out = la.gpad0; }
+    if (chain_splits(la)) { A.idle_plain = 1; A.gpad_out = la.gpad0; }
     // inside a mixture the pads are shared between the chains: a chain of kinds 0/1 has no idle rule, and writes the zeros
     // its clips' pads hold on a plain handle
     if (la.gate.choice) A.gpad_out = la.gpad0;
     A.gate = la.gate;
     return A;
 }
+// the first entry behind the splitting stage
+static int split_end(const LoopChainState& la) { return std::max(la.split, la.pair_speed) + 1; }
+// the splitting stage, u -> z
+static void split_forward(const aware_embed* e, const LoopChainState& la, hipStream_t st) {
+    switch (la.split_kind) {
+        case AWARE_LOOP_REVERBERATION: {
+            ReverbIrLaunch R;
+            R.seeds = la.seeds; R.step = e->step; R.entry = la.split; R.B = e->b->B; R.n_lo = la.lo; R.n_hi = la.hi;
+            R.gain = la.gain; R.prob = la.prob[la.split]; R.h = la.h; R.h_stride = kReverbMaxIr; R.nh = la.nh; R.gate = la.gate;
+            launch_reverb_ir(R, st);
+            launch_convolve(reverb_launch(e, la, la.u, la.z, 0), st);
+            break;
+        }
+        case AWARE_LOOP_SPEED_CHANGE: launch_speed_change(speed_launch(e, la, la.u, la.z, 0, 0), st); break;
+        case AWARE_LOOP_TIME_STRETCH: {
+            // the overlap-add, and the resampling of a speed change directly behind it through v
+            const bool pair = la.pair_speed >= 0;
+            launch_time_stretch(ola_launch<StretchLaunch>(e, la, la.u, pair ? la.v : la.z, 0, 0), st);
+            if (pair) launch_speed_change(speed_launch(e, la, la.v, la.z, 0, 0), st);
+            break;
+        }
+        case AWARE_LOOP_PITCH_SHIFT: launch_pitch_shift(ola_launch<PitchLaunch>(e, la, la.u, la.z, 0, 0), st); break;
+        // gy is free until the synthesis adjoint writes it, and carries the vocoded signal to the resampling
+        case AWARE_LOOP_PHASE_VOCODER: pv_stage_forward(e, la, e->gy, st); break;
+        default: launch_delete_samples(delete_launch(e, la, la.u, la.z, 0, 0), st); break;      // AWARE_LOOP_DELETE_SAMPLES
+    }
+}
+// its mirror: the gradient behind the stage -> e->gy.  Every kind but the reverberation takes it from u (the forward pass is
+// done with u) through its gather-form adjoint; the reverberation correlates gy in place with the same responses (their
+// spectra are still there)
+static void split_backward(const aware_embed* e, const LoopChainState& la, int step_back, hipStream_t st) {
+    switch (la.split_kind) {
+        case AWARE_LOOP_REVERBERATION: launch_convolve(reverb_launch(e, la, e->gy, e->gy, 1), st); break;
+        case AWARE_LOOP_SPEED_CHANGE: launch_speed_change(speed_launch(e, la, la.u, e->gy, 1, step_back), st); break;
+        case AWARE_LOOP_TIME_STRETCH: {
+            const bool pair = la.pair_speed >= 0;
+            if (pair) launch_speed_change(speed_launch(e, la, la.u, la.v, 1, step_back), st);
+            launch_time_stretch(ola_launch<StretchLaunch>(e, la, pair ? la.v : la.u, e->gy, 1, step_back), st);
+            break;
+        }
+        case AWARE_LOOP_PITCH_SHIFT: launch_pitch_shift(ola_launch<PitchLaunch>(e, la, la.u, e->gy, 1, step_back), st); break;
+        case AWARE_LOOP_PHASE_VOCODER: pv_stage_backward(e, la, step_back, st); break;
+        default: launch_delete_samples(delete_launch(e, la, la.u, e->gy, 1, step_back), st); break;
+    }
+}
 // one chain's forward half: x = N(N(yraw)) -> z and its partial maxima
 static void chain_forward(const aware_embed* e, const LoopChainState& la, const LoopAttackLaunch& A, hipStream_t st) {
-    const aware_batch* b = e->b;
-    if (la.ts >= 0) {
-        // the entries in front of the stretch on N(N(yraw)), the overlap-add (and the resampling of a speed change
-        // directly behind it), the entries behind
-        const bool pair = la.sp >= 0;
-        launch_loop_attack_stage(A, 0, la.ts, e->yraw, 1, la.u, nullptr, st);
-        launch_time_stretch(stretch_launch(e, la, la.u, pair ? la.v : la.z, 0, 0), st);
-        if (pair) launch_speed_change(speed_launch(e, la, la.v, la.z, 0, 0), st);
-        launch_loop_attack_stage(A, (pair ? la.sp : la.ts) + 1, la.n, la.z, 0, la.z, la.pmaxZ, st);
-    } else if (la.sp >= 0) {
-        // the entries in front of the speed change on N(N(yraw)), the resampling, the entries behind it
-        launch_loop_attack_stage(A, 0, la.sp, e->yraw, 1, la.u, nullptr, st);
-        launch_speed_change(speed_launch(e, la, la.u, la.z, 0, 0), st);
-        launch_loop_attack_stage(A, la.sp + 1, la.n, la.z, 0, la.z, la.pmaxZ, st);
-    } else if (la.ps >= 0) {
-        // the same shape: the entries in front of the pitch shift on N(N(yraw)), the fused stretch and resampling, the
-        // entries behind it
-        launch_loop_attack_stage(A, 0, la.ps, e->yraw, 1, la.u, nullptr, st);
-        launch_pitch_shift(pitch_launch(e, la, la.u, la.z, 0, 0), st);
-        launch_loop_attack_stage(A, la.ps + 1, la.n, la.z, 0, la.z, la.pmaxZ, st);
-    } else if (la.pv >= 0) {
-        // the same shape again: the entries in front of the phase vocoder on N(N(yraw)), its stage (gy is free until the
-        // synthesis adjoint writes it, and carries the vocoded signal to the resampling), the entries behind it
-        launch_loop_attack_stage(A, 0, la.pv, e->yraw, 1, la.u, nullptr, st);
-        pv_stage_forward(e, la, e->gy, st);
-        launch_loop_attack_stage(A, la.pv + 1, la.n, la.z, 0, la.z, la.pmaxZ, st);
-    } else if (la.ds >= 0) {
-        // the same shape: the entries in front of the deletion on N(N(yraw)), the gather, the entries behind it
-        launch_loop_attack_stage(A, 0, la.ds, e->yraw, 1, la.u, nullptr, st);
-        launch_delete_samples(delete_launch(e, la, la.u, la.z, 0, 0), st);
-        launch_loop_attack_stage(A, la.ds + 1, la.n, la.z, 0, la.z, la.pmaxZ, st);
-    } else if (la.rv < 0) {
-        launch_loop_attack_forward(A, st);
-    } else {
-        // the entries in front of the reverberation on N(N(yraw)), the convolution, the entries behind it
-        launch_loop_attack_stage(A, 0, la.rv, e->yraw, 1, la.u, nullptr, st);
-        ReverbIrLaunch R;
-        R.seeds = la.seeds; R.step = e->step; R.entry = la.rv; R.B = b->B; R.n_lo = la.n_lo; R.n_hi = la.n_hi;
-        R.gain = la.gain; R.prob = la.prob[la.rv]; R.h = la.h; R.h_stride = kReverbMaxIr; R.nh = la.nh; R.gate = la.gate;
-        launch_reverb_ir(R, st);
-        launch_convolve(reverb_launch(e, la, la.u, la.z, 0), st);
-        launch_loop_attack_stage(A, la.rv + 1, la.n, la.z, 0, la.z, la.pmaxZ, st);
-    }
+    if (!chain_splits(la)) { launch_loop_attack_forward(A, st); return; }
+    // the entries in front of the splitting entry on N(N(yraw)), its stage, the entries behind it
+    launch_loop_attack_stage(A, 0, la.split, e->yraw, 1, la.u, nullptr, st);
+    split_forward(e, la, st);
+    launch_loop_attack_stage(A, split_end(la), la.n, la.z, 0, la.z, la.pmaxZ, st);
 }
 // its mirror: gy, dL/d N(N(z)) -> dL/dx, the partial sums against x and the reflect pads for the analysis adjoint
 static void chain_backward(const aware_embed* e, const LoopChainState& la, LoopAttackLaunch& A, hipStream_t st) {
-    if (la.ts >= 0) {
-        // the mirror: normalisers at z and the masks behind the stage into u, the gather-form adjoints (of the speed
-        // change into v, of the stretch into gy), the masks in front and the partial sums against x
-        const bool pair = la.sp >= 0;
-        A.gy_out = la.u;
-        launch_loop_attack_stage_bwd(A, (pair ? la.sp : la.ts) + 1, la.n, 1, 0, st);
-        A.gy_out = nullptr;
-        if (pair) launch_speed_change(speed_launch(e, la, la.u, la.v, 1, A.step_back), st);
-        launch_time_stretch(stretch_launch(e, la, pair ? la.v : la.u, e->gy, 1, A.step_back), st);
-        launch_loop_attack_stage_bwd(A, 0, la.ts, 0, 1, st);
-    } else if (la.sp >= 0) {
-        // the mirror: normalisers at z and the masks behind the speed change into u (the forward pass is done with
-        // it), the gather-form adjoint back into gy, the masks in front of it and the partial sums against x
-        A.gy_out = la.u;
-        launch_loop_attack_stage_bwd(A, la.sp + 1, la.n, 1, 0, st);
-        A.gy_out = nullptr;
-        launch_speed_change(speed_launch(e, la, la.u, e->gy, 1, A.step_back), st);
-        launch_loop_attack_stage_bwd(A, 0, la.sp, 0, 1, st);
-    } else if (la.ps >= 0) {
-        // the mirror, as for the speed change: into u, the fused gather-form adjoint back into gy, the stage in front
-        A.gy_out = la.u;
-        launch_loop_attack_stage_bwd(A, la.ps + 1, la.n, 1, 0, st);
-        A.gy_out = nullptr;
-        launch_pitch_shift(pitch_launch(e, la, la.u, e->gy, 1, A.step_back), st);
-        launch_loop_attack_stage_bwd(A, 0, la.ps, 0, 1, st);
-    } else if (la.pv >= 0) {
-        // the mirror: into u, the stage's backward into gy, the stage in front
-        A.gy_out = la.u;
-        launch_loop_attack_stage_bwd(A, la.pv + 1, la.n, 1, 0, st);
-        A.gy_out = nullptr;
-        pv_stage_backward(e, la, A.step_back, st);
-        launch_loop_attack_stage_bwd(A, 0, la.pv, 0, 1, st);
-    } else if (la.ds >= 0) {
-        // the mirror, as for the speed change: into u, the gather-form adjoint back into gy, the stage in front
-        A.gy_out = la.u;
-        launch_loop_attack_stage_bwd(A, la.ds + 1, la.n, 1, 0, st);
-        A.gy_out = nullptr;
-        launch_delete_samples(delete_launch(e, la, la.u, e->gy, 1, A.step_back), st);
-        launch_loop_attack_stage_bwd(A, 0, la.ds, 0, 1, st);
-    } else if (la.rv < 0) {
-        launch_loop_attack_backward(A, st);
-    } else {
-        // the mirror: normalisers at z and the masks behind the reverberation, the correlation with the same
-        // responses (their spectra are still there), the masks in front of it and the partial sums against x
-        launch_loop_attack_stage_bwd(A, la.rv + 1, la.n, 1, 0, st);
-        launch_convolve(reverb_launch(e, la, e->gy, e->gy, 1), st);
-        launch_loop_attack_stage_bwd(A, 0, la.rv, 0, 1, st);
-    }
+    if (!chain_splits(la)) { launch_loop_attack_backward(A, st); return; }
+    // normalisers at z and the masks behind the stage (into u, unless the stage works on gy in place), the stage's adjoint
+    // into gy, the masks in front of it and the partial sums against x
+    A.gy_out = chain_has(la, AWARE_LOOP_REVERBERATION) ? nullptr : la.u;
+    launch_loop_attack_stage_bwd(A, split_end(la), la.n, 1, 0, st);
+    A.gy_out = nullptr;
+    split_backward(e, la, A.step_back, st);
+    launch_loop_attack_stage_bwd(A, 0, la.split, 0, 1, st);
 }
 
 // one loop body of AWAREEmbedder._optimize (multibit_embedder.py:95-122)

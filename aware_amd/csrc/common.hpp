@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "fft512.hpp"
+#include "loop_limits.hpp"
 
 namespace aware {
 
@@ -46,11 +47,7 @@ __device__ __forceinline__ int sig_offset(const int* frame_off, int b) { return 
 
 // Attack mixtures (EXTENSION, loop_mix_kernels.hip): the gate every kernel of the loop family carries.  With `choice` set, a
 // workgroup whose clip did not draw chain `chain` at this step returns at once (skipped, not copied); with `choice` null the
-// kernel computes what it computes without a gate.
-struct LoopGate {
-    const int* choice = nullptr;          // [B] the chain clip b drew at this step, -1: none
-    int chain = 0;
-};
+// kernel computes what it computes without a gate.  LoopGate itself is in loop_limits.hpp, which the host-only chain logic shares.
 __device__ __forceinline__ bool loop_gate_skips(const LoopGate& g, int b) { return g.choice && g.choice[b] != g.chain; }
 
 // per-clip maximum of |y| with the first index attaining it, packed so that an

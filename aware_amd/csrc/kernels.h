@@ -4,14 +4,14 @@
 #include <stddef.h>
 #include <stdint.h>
 #include "common.hpp"
+#include "loop_limits.hpp"
 
 namespace aware {
 
 // ---- loop_mix_kernels.hip: attack mixtures (EXTENSION): one of several loop chains drawn per clip and step.  The gate every
 // kernel of the loop family carries: with `choice` set, a workgroup whose clip did not draw chain `chain` returns at once
 // (skipped, not copied); with `choice` null the kernel computes what it computes without a gate -------------------------
-// (LoopGate itself is in common.hpp, beside the layout helpers every kernel file shares)
-constexpr int kMaxLoopChains = 8;
+// (LoopGate, kMaxLoopChains and the other limits of the loop family are in loop_limits.hpp, which the host-only chain logic shares)
 struct LoopMixDrawLaunch {
     const unsigned* seeds = nullptr;      // [B]
     const int* step = nullptr;            // device step counter, or null: step_imm
@@ -19,8 +19,6 @@ struct LoopMixDrawLaunch {
     unsigned long long thr[kMaxLoopChains] = {0};     // T_c = min(floor((w_0 + .. + w_c) 2^32), 2^32)
     int* choice = nullptr;                // [B]
 };
-// T_c from the float32 weights, summed in double
-void loop_mix_thresholds(const float* weights, int n, unsigned long long* thr);
 void launch_loop_mix_draw(const LoopMixDrawLaunch& L, hipStream_t st);
 
 // ---- dsp_kernels.hip ------------------------------------------------------------------
@@ -373,9 +371,6 @@ void launch_stoi(const StoiLaunch& L, hipStream_t st);
 
 // ---- loop_attack_kernels.hip: attack-aware embedding (EXTENSION): a chain of attacks between the embed loop's synthesis and
 // its analysis, drawn afresh at every optimiser step (aware_embed_set_loop_attacks) --------------------------------------
-constexpr int kMaxLoopAttacks = 4;
-constexpr int kLoopGaussianNoise = 0, kLoopSampleSuppression = 1, kLoopReverberation = 2, kLoopSpeedChange = 3, kLoopTimeStretch = 4,
-              kLoopPitchShift = 5, kLoopPhaseVocoder = 6, kLoopDeleteSamples = 7;      // AWARE_LOOP_* of aware_hip.h
 struct LoopAttackLaunch {
     const int* frame_off = nullptr;
     const int* pcount = nullptr;          // [B] synthesis runs per clip: the partials' layout
@@ -398,9 +393,9 @@ struct LoopAttackLaunch {
     const float* gpad = nullptr;          // reflect-pad parts of the streaming synthesis adjoint (null: already folded)
     const double* pdot_in = nullptr;
     double* pdot_out = nullptr;
-    // chains with a reverberation, a speed change or a time stretch: a clip on which no entry fires at a step leaves the plain loop's bits (its maxima are
-    // recorded as 1, the backward stages pass gradient, partial sums and reflect pads through); gpad_out: [B][2][512], the
-    // pads the analysis adjoint then reads (zeros for every other clip)
+    // chains with a splitting entry (loop_chain.hpp: kinds 2 to 7): a clip on which no entry fires at a step leaves the plain loop's
+    // bits (its maxima are recorded as 1, the backward stages pass gradient, partial sums and reflect pads through);
+    // gpad_out: [B][2][512], the pads the analysis adjoint then reads (zeros for every other clip)
     int idle_plain = 0;
     float* gpad_out = nullptr;
     LoopGate gate;                        // inside a mixture: the clips that drew this chain
@@ -417,14 +412,20 @@ void launch_loop_attack_stage(const LoopAttackLaunch& L, int j0, int j1, const f
 // dot: the partial sums of the result against x go to pdot_out
 void launch_loop_attack_stage_bwd(const LoopAttackLaunch& L, int j0, int j1, int at_z, int dot, hipStream_t st);
 
+// The loop side of a stage kernel that serves one splitting entry of a chain (kinds 3 to 7): the embed loop's layout (x and z
+// both Ny_b long at sig_offset, one workgroup per synthesis run) and the entry's draw (loop_rng.hpp loop_entry_draw)
+struct LoopDraw {
+    const int* frame_off = nullptr;       // [B + 1]
+    int pstride = 0, run_blocks = 0;
+    const int* step = nullptr; int step_back = 0;      // device step counter; step_back = 1 once the read-out kernel has advanced it
+    const unsigned* seeds = nullptr;      // [B]
+    int entry = 0;
+    float prob = 0.f;
+    LoopGate gate;                        // inside a mixture: the clips that drew this chain
+};
+
 // ---- loop_reverb_kernels.hip: reverberation (EXTENSION): a drawn impulse response per clip and the partitioned FFT
 // convolution that applies it, inside the embed loop (chain kind 2) and stand-alone (aware_convolve, aware_reverb_ir) ----
-constexpr int kReverbMaxIr = 8192;        // taps
-constexpr int kReverbBlock = 2048;        // output samples per block; the transform has 4096 points
-constexpr int kReverbBins = 2056;         // complex values per spectrum row: bins 0..2048 and padding
-constexpr int kReverbParts = 4;           // partitions of 2048 taps
-constexpr int kReverbTwHalf = 1024;       // W_2048^j, j < 1024; then W_4096^k, k <= 2048, padded to kReverbBins
-inline int reverb_blocks(int n) { return (n + kReverbBlock - 1) / kReverbBlock; }
 struct ReverbIrLaunch {
     const unsigned* seeds = nullptr;      // [B]
     const int* step = nullptr;            // device step counter, or null: step_imm
@@ -455,47 +456,35 @@ void launch_convolve(const ConvolveLaunch& L, hipStream_t st);
 
 // ---- loop_speed_kernels.hip: speed change (EXTENSION): Catmull-Rom resampling at a drawn ratio R / 65536, inside the embed
 // loop (chain kind 3) and stand-alone (aware_speed_change), and its adjoint in gather form ------------------------------
-constexpr int kSpeedMin = -13520, kSpeedMax = 17034;      // ceil / floor of 65536 (2^(-+400 / 1200) - 1)
 struct SpeedLaunch {
     const float* in = nullptr; float* out = nullptr;      // never the same buffer
     int B = 0, adjoint = 0;               // 0: out = z from in = x; 1: out = gx from in = gy
-    // the embed loop's layout: x and z both Ny_b long at sig_offset, one workgroup per synthesis run, m drawn in the kernel
-    const int* frame_off = nullptr;
-    int pstride = 0, run_blocks = 0;
-    const int* step = nullptr; int step_back = 0;
-    const unsigned* seeds = nullptr;      // [B]
-    int entry = 0, m_lo = 0, m_hi = 0;
-    float prob = 0.f;
+    // the embed loop (draw.frame_off set): m drawn in the kernel
+    LoopDraw draw;
+    int m_lo = 0, m_hi = 0;
     int coin = 0;                         // 1: behind a phase vocoder with both modes, m = 0 where the draw's r[2] < 2^31 (stretch mode)
-    // or a ragged batch (frame_off null): x is x_len[b] floats at x_off[b], z is z_len[b] floats at z_off[b], m[b] given
+    // or a ragged batch (draw.frame_off null): x is x_len[b] floats at x_off[b], z is z_len[b] floats at z_off[b], m[b] given
     const int* x_off = nullptr; const int* x_len = nullptr;
     const int* z_off = nullptr; const int* z_len = nullptr;
     int max_len = 0;                      // >= every length written
     const int* m = nullptr;               // [B]
-    LoopGate gate;                        // the embed loop inside a mixture: the clips that drew this chain
 };
 void launch_speed_change(const SpeedLaunch& L, hipStream_t st);
 
 // ---- loop_stretch_kernels.hip: time stretch (EXTENSION): overlap-add of Hann-windowed segments taken at a drawn rate
 // Q / 65536, inside the embed loop (chain kind 4) and stand-alone (aware_stretch_ola), and its adjoint in gather form ------
-constexpr int kStretchMin = -16384, kStretchMax = 21845;      // ceil / floor of 65536 (0.75 - 1) and 65536 (4 / 3 - 1)
 struct StretchLaunch {
     const float* in = nullptr; float* out = nullptr;      // never the same buffer
     const float* window = nullptr;        // stretch_window()
     int B = 0, adjoint = 0;               // 0: out = z from in = x; 1: out = gx from in = gz
-    // the embed loop's layout: x and z both Ny_b long at sig_offset, one workgroup per synthesis run, m drawn in the kernel
-    const int* frame_off = nullptr;
-    int pstride = 0, run_blocks = 0;
-    const int* step = nullptr; int step_back = 0;
-    const unsigned* seeds = nullptr;      // [B]
-    int entry = 0, m_lo = 0, m_hi = 0;
-    float prob = 0.f;
-    // or a ragged batch (frame_off null): x is x_len[b] floats at x_off[b], z is z_len[b] floats at z_off[b], m[b] given
+    // the embed loop (draw.frame_off set): m drawn in the kernel
+    LoopDraw draw;
+    int m_lo = 0, m_hi = 0;
+    // or a ragged batch (draw.frame_off null): x is x_len[b] floats at x_off[b], z is z_len[b] floats at z_off[b], m[b] given
     const int* x_off = nullptr; const int* x_len = nullptr;
     const int* z_off = nullptr; const int* z_len = nullptr;
     int max_len = 0;                      // >= every length written
     const int* m = nullptr;               // [B]
-    LoopGate gate;                        // the embed loop inside a mixture: the clips that drew this chain
 };
 // the periodic Hann window of 1024 points in f32 on the current device (uploaded once, outside any stream capture); null
 // when the device refuses
@@ -509,19 +498,14 @@ struct PitchLaunch {
     const float* in = nullptr; float* out = nullptr;      // never the same buffer
     const float* window = nullptr;        // stretch_window()
     int B = 0, adjoint = 0;               // 0: out = z from in = x; 1: out = gx from in = gz
-    // the embed loop's layout: x and z both Ny_b long at sig_offset, one workgroup per synthesis run, m drawn in the kernel
-    const int* frame_off = nullptr;
-    int pstride = 0, run_blocks = 0;
-    const int* step = nullptr; int step_back = 0;
-    const unsigned* seeds = nullptr;      // [B]
-    int entry = 0, m_lo = 0, m_hi = 0;    // speed offsets, inside kSpeedMin .. kSpeedMax
-    float prob = 0.f;
-    // or a ragged batch (frame_off null): x is x_len[b] floats at x_off[b], z is z_len[b] floats at z_off[b], m[b] given
+    // the embed loop (draw.frame_off set): m drawn in the kernel
+    LoopDraw draw;
+    int m_lo = 0, m_hi = 0;    // speed offsets, inside kSpeedMin .. kSpeedMax
+    // or a ragged batch (draw.frame_off null): x is x_len[b] floats at x_off[b], z is z_len[b] floats at z_off[b], m[b] given
     const int* x_off = nullptr; const int* x_len = nullptr;
     const int* z_off = nullptr; const int* z_len = nullptr;
     int max_len = 0;                      // >= every length written
     const int* m = nullptr;               // [B]
-    LoopGate gate;                        // the embed loop inside a mixture: the clips that drew this chain
 };
 void launch_pitch_shift(const PitchLaunch& L, hipStream_t st);
 
@@ -532,19 +516,14 @@ struct PvLaunch {
     const void* spec = nullptr;           // S [NF][520] complex
     const void* grad = nullptr;           // backward: G = dL/dY [NF][520]; never `out`
     void* out = nullptr;                  // forward: Y; backward: gS (may be `spec`)
-    const int* frame_off = nullptr;       // [B + 1]
     int B = 0;
-    // the embed loop (seeds non-null): the mode and the offset drawn in the kernel; a clip that the entry leaves alone is skipped
-    int pstride = 0, run_blocks = 0;
-    const int* step = nullptr; int step_back = 0;
-    const unsigned* seeds = nullptr;      // [B]
-    int entry = 0;
+    // draw.frame_off [B + 1] always; the embed loop (draw.seeds non-null): the mode and the offset drawn in the kernel; a clip
+    // that the entry leaves alone is skipped
+    LoopDraw draw;
     int q_lo = 0, q_hi = -1;              // stretch offsets, inside kStretchMin .. kStretchMax; lo > hi: no stretch mode
     int m_lo = 0, m_hi = -1;              // speed offsets, inside kSpeedMin .. kSpeedMax; lo > hi: no pitch mode
-    float prob = 0.f;
-    // or stand-alone (seeds null): mq[b] given, outside kStretchMin .. kStretchMax read as 0 (the identity)
+    // or stand-alone (draw.seeds null): mq[b] given, outside kStretchMin .. kStretchMax read as 0 (the identity)
     const int* mq = nullptr;              // [B]
-    LoopGate gate;                        // the embed loop inside a mixture: the clips that drew this chain
 };
 void launch_pv_frames(const PvLaunch& L, int backward, hipStream_t st);
 // the loop's clips that the entry leaves alone at this step: dst = src (the embed loop's signal layout)
@@ -555,20 +534,15 @@ void launch_pv_idle(const PvLaunch& L, const float* src, float* dst, hipStream_t
 struct DeleteLaunch {
     const float* in = nullptr; float* out = nullptr;      // never the same buffer
     int B = 0, adjoint = 0;               // 0: out = z from in = x; 1: out = gx from in = gz
-    // the embed loop's layout: x and z both Ny_b long at sig_offset, one workgroup per synthesis run, start and k drawn in the kernel
-    const int* frame_off = nullptr;
-    int pstride = 0, run_blocks = 0;
-    const int* step = nullptr; int step_back = 0;
-    const unsigned* seeds = nullptr;      // [B]
-    int entry = 0, k_lo = 0, k_hi = 0;    // 1 <= k_lo <= k_hi < every Ny_b
+    // the embed loop (draw.frame_off set): start and k drawn in the kernel
+    LoopDraw draw;
+    int k_lo = 0, k_hi = 0;    // 1 <= k_lo <= k_hi < every Ny_b
     int at = 0;                           // 0: the cut starts at sample 0; 1: anywhere
-    float prob = 0.f;
-    // or a ragged batch (frame_off null): both sides are len[b] floats at off[b]; start[b] and k[b] given, clamped to the clip
+    // or a ragged batch (draw.frame_off null): both sides are len[b] floats at off[b]; start[b] and k[b] given, clamped to the clip
     const int* off = nullptr; const int* len = nullptr;
     int max_len = 0;                      // >= every length
     const int* start = nullptr;           // [B]
     const int* k = nullptr;               // [B]
-    LoopGate gate;                        // the embed loop inside a mixture: the clips that drew this chain
 };
 void launch_delete_samples(const DeleteLaunch& L, hipStream_t st);
 

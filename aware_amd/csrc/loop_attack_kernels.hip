@@ -87,7 +87,7 @@ __device__ __forceinline__ ChainState chain_state(const ChainArgs& a, int b, int
             a.kind[j] != kLoopTimeStretch) {
             unsigned r[4];
             philox4x32_10(0u, step, 1u + (unsigned)j, 1u, seed, 0x5EEDu, r);
-            cs.on[j] = ((double)r[0] + 0.5) * 2.3283064365386963e-10 < (double)a.prob[j];
+            cs.on[j] = loop_entry_fires(r[0], a.prob[j]);
             if (a.kind[j] == kLoopSampleSuppression) {
                 cs.start[j] = (int)(((unsigned long long)r[1] * (unsigned long long)(unsigned)(Ny - a.k[j])) >> 32);
             } else if (SIGMA) {
@@ -112,7 +112,7 @@ __device__ __forceinline__ bool chain_idle(const ChainArgs& a, unsigned step, un
         if (j < a.n) {
             unsigned r[4];
             philox4x32_10(0u, step, 1u + (unsigned)j, 1u, seed, 0x5EEDu, r);
-            any = any || ((double)r[0] + 0.5) * 2.3283064365386963e-10 < (double)a.prob[j];
+            any = any || loop_entry_fires(r[0], a.prob[j]);
         }
     }
     return !any;

@@ -31,19 +31,17 @@ __global__ __launch_bounds__(kDsThreads) void delete_kernel(DeleteLaunch a) {
     float* __restrict__ y;
     int n, i0, i1, start, k;        // the clip's length, this workgroup's samples [i0, i1), the cut [start, start + k)
     if (LOOP) {
-        if (loop_gate_skips(a.gate, b)) return;
-        const int nblk = a.frame_off[b + 1] - a.frame_off[b] - 1;
+        if (loop_gate_skips(a.draw.gate, b)) return;
+        const int nblk = a.draw.frame_off[b + 1] - a.draw.frame_off[b] - 1;
         int nseg, jb0, jb1;
-        synth_segment(nblk, blockIdx.x, a.run_blocks, nseg, jb0, jb1);
+        synth_segment(nblk, blockIdx.x, a.draw.run_blocks, nseg, jb0, jb1);
         if ((int)blockIdx.x >= nseg) return;
-        const int so = sig_offset(a.frame_off, b);
+        const int so = sig_offset(a.draw.frame_off, b);
         x = a.in + so; y = a.out + so;
         n = kHop * nblk;
         i0 = jb0 * kHop; i1 = jb1 * kHop;
-        const unsigned step = (unsigned)(*a.step - a.step_back);
         unsigned r[4];
-        philox4x32_10(0u, step, 1u + (unsigned)a.entry, 1u, a.seeds[b], 0x5EEDu, r);
-        const bool on = ((double)r[0] + 0.5) * 2.3283064365386963e-10 < (double)a.prob;
+        const bool on = loop_entry_draw(a.draw, b, r);
         k = on ? a.k_lo + (int)(((unsigned long long)r[2] * (unsigned long long)(unsigned)(a.k_hi - a.k_lo + 1)) >> 32) : 0;
         k = min(k, n);              // k_hi < Ny is checked where the chain is set
         start = (on && a.at) ? (int)(((unsigned long long)r[1] * (unsigned long long)(unsigned)(n - k)) >> 32) : 0;
@@ -67,8 +65,8 @@ __global__ __launch_bounds__(kDsThreads) void delete_kernel(DeleteLaunch a) {
 }  // namespace
 
 void launch_delete_samples(const DeleteLaunch& L, hipStream_t st) {
-    if (L.frame_off) {
-        hipLaunchKernelGGL(delete_kernel<true>, dim3((unsigned)L.pstride, (unsigned)L.B, 1), dim3(kDsThreads), 0, st, L);
+    if (L.draw.frame_off) {
+        hipLaunchKernelGGL(delete_kernel<true>, dim3((unsigned)L.draw.pstride, (unsigned)L.B, 1), dim3(kDsThreads), 0, st, L);
     } else {
         const unsigned gx = (unsigned)((L.max_len + kDsChunk - 1) / kDsChunk);
         hipLaunchKernelGGL(delete_kernel<false>, dim3(gx, (unsigned)L.B, 1), dim3(kDsThreads), 0, st, L);

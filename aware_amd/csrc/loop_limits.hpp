@@ -1,0 +1,29 @@
+// Limits and kind numbers of the embed loop's attack chains and the mixture's gate: what the kernels (kernels.h, common.hpp) and
+// the host-only chain logic (loop_chain.hpp) share.  Plain C++: no HIP header, no HIP call.
+#pragma once
+
+namespace aware {
+
+constexpr int kMaxLoopChains = 8;
+constexpr int kMaxLoopAttacks = 4;
+constexpr int kLoopGaussianNoise = 0, kLoopSampleSuppression = 1, kLoopReverberation = 2, kLoopSpeedChange = 3, kLoopTimeStretch = 4,
+              kLoopPitchShift = 5, kLoopPhaseVocoder = 6, kLoopDeleteSamples = 7;      // AWARE_LOOP_* of aware_hip.h
+
+// reverberation (loop_reverb_kernels.hip)
+constexpr int kReverbMaxIr = 8192;        // taps
+constexpr int kReverbBlock = 2048;        // output samples per block; the transform has 4096 points
+constexpr int kReverbBins = 2056;         // complex values per spectrum row: bins 0..2048 and padding
+constexpr int kReverbParts = 4;           // partitions of 2048 taps
+constexpr int kReverbTwHalf = 1024;       // W_2048^j, j < 1024; then W_4096^k, k <= 2048, padded to kReverbBins
+inline int reverb_blocks(int n) { return (n + kReverbBlock - 1) / kReverbBlock; }
+
+constexpr int kSpeedMin = -13520, kSpeedMax = 17034;      // speed offsets: ceil / floor of 65536 (2^(-+400 / 1200) - 1)
+constexpr int kStretchMin = -16384, kStretchMax = 21845;  // stretch offsets: ceil / floor of 65536 (0.75 - 1) and 65536 (4 / 3 - 1)
+
+// Attack mixtures: with `choice` set, a workgroup whose clip did not draw chain `chain` at this step returns at once
+struct LoopGate {
+    const int* choice = nullptr;          // [B] the chain clip b drew at this step, -1: none
+    int chain = 0;
+};
+
+}  // namespace aware

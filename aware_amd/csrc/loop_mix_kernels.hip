@@ -34,15 +34,6 @@ __global__ __launch_bounds__(64) void loop_mix_draw_kernel(LoopMixDrawLaunch a) 
 
 }  // namespace
 
-void loop_mix_thresholds(const float* weights, int n, unsigned long long* thr) {
-    double acc = 0.0;
-    for (int c = 0; c < kMaxLoopChains; ++c) {
-        if (c < n) acc += (double)weights[c];
-        const double t = std::floor(acc * 4294967296.0);
-        thr[c] = c < n ? (t >= 4294967296.0 ? 4294967296ull : (t > 0.0 ? (unsigned long long)t : 0ull)) : 0ull;
-    }
-}
-
 void launch_loop_mix_draw(const LoopMixDrawLaunch& L, hipStream_t st) {
     hipLaunchKernelGGL(loop_mix_draw_kernel, dim3((unsigned)((L.B + 63) / 64)), dim3(64), 0, st, L);
 }

@@ -126,19 +126,17 @@ __global__ __launch_bounds__(kPsThreads) void pitch_kernel(PitchLaunch a) {
     float* y;
     int nx, nz, q0, q1, m;          // lengths of the x side and the z side; this workgroup's groups of four outputs [q0, q1)
     if (LOOP) {
-        if (loop_gate_skips(a.gate, b)) return;
-        const int nblk = a.frame_off[b + 1] - a.frame_off[b] - 1;
+        if (loop_gate_skips(a.draw.gate, b)) return;
+        const int nblk = a.draw.frame_off[b + 1] - a.draw.frame_off[b] - 1;
         int nseg, jb0, jb1;
-        synth_segment(nblk, blockIdx.x, a.run_blocks, nseg, jb0, jb1);
+        synth_segment(nblk, blockIdx.x, a.draw.run_blocks, nseg, jb0, jb1);
         if ((int)blockIdx.x >= nseg) return;
-        const int so = sig_offset(a.frame_off, b);
+        const int so = sig_offset(a.draw.frame_off, b);
         x = a.in + so; y = a.out + so;
         nx = nz = kHop * nblk;
         q0 = jb0 * (kHop / 4); q1 = jb1 * (kHop / 4);
-        const unsigned step = (unsigned)(*a.step - a.step_back);
         unsigned r[4];
-        philox4x32_10(0u, step, 1u + (unsigned)a.entry, 1u, a.seeds[b], 0x5EEDu, r);
-        const bool on = ((double)r[0] + 0.5) * 2.3283064365386963e-10 < (double)a.prob;
+        const bool on = loop_entry_draw(a.draw, b, r);
         m = on ? a.m_lo + (int)(((unsigned long long)r[3] * (unsigned long long)(unsigned)(a.m_hi - a.m_lo + 1)) >> 32) : 0;
     } else {
         nx = a.x_len[b]; nz = a.z_len[b];
@@ -241,8 +239,8 @@ __global__ __launch_bounds__(kPsThreads) void pitch_kernel(PitchLaunch a) {
 }  // namespace
 
 void launch_pitch_shift(const PitchLaunch& L, hipStream_t st) {
-    if (L.frame_off) {
-        hipLaunchKernelGGL(pitch_kernel<true>, dim3((unsigned)L.pstride, (unsigned)L.B, 1), dim3(kPsThreads), 0, st, L);
+    if (L.draw.frame_off) {
+        hipLaunchKernelGGL(pitch_kernel<true>, dim3((unsigned)L.draw.pstride, (unsigned)L.B, 1), dim3(kPsThreads), 0, st, L);
     } else {
         const unsigned gx = (unsigned)((L.max_len + kPsTile - 1) / kPsTile);
         hipLaunchKernelGGL(pitch_kernel<false>, dim3(gx, (unsigned)L.B, 1), dim3(kPsThreads), 0, st, L);

@@ -67,10 +67,8 @@ __device__ __forceinline__ bool pv_draw(const PvLaunch& a, int b, int& mq) {
         if (mq < kStretchMin || mq > kStretchMax) mq = 0;
         return true;
     }
-    const unsigned step = (unsigned)(*a.step - a.step_back);
     unsigned r[4];
-    philox4x32_10(0u, step, 1u + (unsigned)a.entry, 1u, a.seeds[b], 0x5EEDu, r);
-    const bool on = ((double)r[0] + 0.5) * 2.3283064365386963e-10 < (double)a.prob;
+    const bool on = loop_entry_draw(a.draw, b, r);
     const bool has_q = a.q_lo <= a.q_hi, has_m = a.m_lo <= a.m_hi;
     if (has_q && (!has_m || r[2] < 0x80000000u)) {
         mq = a.q_lo + (int)(((unsigned long long)r[3] * (unsigned long long)(unsigned)(a.q_hi - a.q_lo + 1)) >> 32);
@@ -87,9 +85,9 @@ template <bool LOOP, bool BWD>
 __global__ __launch_bounds__(kPvThreads) void pv_frames_kernel(PvLaunch a) {
     const int b = blockIdx.y, k = blockIdx.x * kPvThreads + threadIdx.x;
     if (k >= kPvRow) return;
-    const int f0 = a.frame_off[b], T = a.frame_off[b + 1] - f0;
+    const int f0 = a.draw.frame_off[b], T = a.draw.frame_off[b + 1] - f0;
     if (T < 1) return;
-    if (LOOP && loop_gate_skips(a.gate, b)) return;
+    if (LOOP && loop_gate_skips(a.draw.gate, b)) return;
     int mq;
     const bool on = pv_draw<LOOP>(a, b, mq);
     if (LOOP && !on) return;                       // the clip does not go through the spectra at all (pv_idle_kernel)
@@ -150,14 +148,14 @@ __global__ __launch_bounds__(kPvThreads) void pv_frames_kernel(PvLaunch a) {
 // run, as speed_kernel)
 __global__ __launch_bounds__(256) void pv_idle_kernel(PvLaunch a, const float* __restrict__ src, float* __restrict__ dst) {
     const int b = blockIdx.y;
-    if (loop_gate_skips(a.gate, b)) return;
-    const int nblk = a.frame_off[b + 1] - a.frame_off[b] - 1;
+    if (loop_gate_skips(a.draw.gate, b)) return;
+    const int nblk = a.draw.frame_off[b + 1] - a.draw.frame_off[b] - 1;
     int nseg, jb0, jb1;
-    synth_segment(nblk, blockIdx.x, a.run_blocks, nseg, jb0, jb1);
+    synth_segment(nblk, blockIdx.x, a.draw.run_blocks, nseg, jb0, jb1);
     if ((int)blockIdx.x >= nseg) return;
     int mq;
     if (pv_draw<true>(a, b, mq)) return;
-    const int so = sig_offset(a.frame_off, b);
+    const int so = sig_offset(a.draw.frame_off, b);
     const float4* s4 = reinterpret_cast<const float4*>(src + so);
     float4* d4 = reinterpret_cast<float4*>(dst + so);
     for (int q = jb0 * (kHop / 4) + threadIdx.x; q < jb1 * (kHop / 4); q += 256) d4[q] = s4[q];
@@ -167,7 +165,7 @@ __global__ __launch_bounds__(256) void pv_idle_kernel(PvLaunch a, const float* _
 
 void launch_pv_frames(const PvLaunch& L, int backward, hipStream_t st) {
     const dim3 grid((kPvRow + kPvThreads - 1) / kPvThreads, (unsigned)L.B, 1);
-    if (L.seeds) {
+    if (L.draw.seeds) {
         if (backward) hipLaunchKernelGGL((pv_frames_kernel<true, true>), grid, dim3(kPvThreads), 0, st, L);
         else hipLaunchKernelGGL((pv_frames_kernel<true, false>), grid, dim3(kPvThreads), 0, st, L);
     } else {
@@ -177,7 +175,7 @@ void launch_pv_frames(const PvLaunch& L, int backward, hipStream_t st) {
 }
 
 void launch_pv_idle(const PvLaunch& L, const float* src, float* dst, hipStream_t st) {
-    hipLaunchKernelGGL(pv_idle_kernel, dim3((unsigned)L.pstride, (unsigned)L.B, 1), dim3(256), 0, st, L, src, dst);
+    hipLaunchKernelGGL(pv_idle_kernel, dim3((unsigned)L.draw.pstride, (unsigned)L.B, 1), dim3(256), 0, st, L, src, dst);
 }
 
 }  // namespace aware

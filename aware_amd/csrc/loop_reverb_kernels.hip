@@ -38,7 +38,7 @@ __global__ __launch_bounds__(256) void reverb_ir_kernel(ReverbIrLaunch a) {
     const unsigned step = (unsigned)(a.step ? *a.step : a.step_imm), seed = a.seeds[b], j = (unsigned)a.entry;
     unsigned r[4];
     philox4x32_10(0u, step, 1u + j, 1u, seed, 0x5EEDu, r);
-    const bool on = ((double)r[0] + 0.5) * 2.3283064365386963e-10 < (double)a.prob;
+    const bool on = loop_entry_fires(r[0], a.prob);
     const int n_h = a.n_lo + (int)(((unsigned long long)r[2] * (unsigned long long)(unsigned)(a.n_hi - a.n_lo + 1)) >> 32);
     float* h = a.h + (size_t)b * a.h_stride;
     const double rate = -6.907755278982137 / (double)n_h;       // -ln(1000) / n_h

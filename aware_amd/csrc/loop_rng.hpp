@@ -2,8 +2,11 @@
 // loop_reverb_kernels.hip); the host twin is aware_amd/embedding/loop_attacks.py::philox4x32 / normal_draws.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "kernels.h"
 
 namespace aware {
+
+constexpr double kTwoToMinus32 = 2.3283064365386963e-10;
 
 __device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
                                               unsigned (&r)[4]) {
@@ -18,12 +21,21 @@ __device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned
     r[0] = c0; r[1] = c1; r[2] = c2; r[3] = c3;
 }
 
+// whether an entry fires: (r0 + 0.5) / 2^32 < prob, in double as the host twin's fires()
+__device__ __forceinline__ bool loop_entry_fires(unsigned r0, float prob) { return ((double)r0 + 0.5) * kTwoToMinus32 < (double)prob; }
+// the draw of the entry a stage kernel serves, for clip b at the step the forward pass ran at:
+// r = philox4x32_10((0, s, 1 + entry, 1), (seed_b, 0x5EED)); returns on
+__device__ __forceinline__ bool loop_entry_draw(const LoopDraw& d, int b, unsigned (&r)[4]) {
+    philox4x32_10(0u, (unsigned)(*d.step - d.step_back), 1u + (unsigned)d.entry, 1u, d.seeds[b], 0x5EEDu, r);
+    return loop_entry_fires(r[0], d.prob);
+}
+
 // Box-Muller in f32 from the 32-bit lanes, arguments reduced in integers so that no bit of the draw is lost where it counts:
 // radius sqrt(-2 ln u), u = (r + 0.5) / 2^32: the upper half of the range goes through log1p of the exact complement
 __device__ __forceinline__ float bm_radius(unsigned r) {
     float w;
-    if (r & 0x80000000u) w = -log1pf(-(((float)(0u - r) - 0.5f) * 2.3283064365386963e-10f));
-    else w = -logf(((float)r + 0.5f) * 2.3283064365386963e-10f);
+    if (r & 0x80000000u) w = -log1pf(-(((float)(0u - r) - 0.5f) * (float)kTwoToMinus32));
+    else w = -logf(((float)r + 0.5f) * (float)kTwoToMinus32);
     return sqrtf(2.f * w);
 }
 // (cos, sin) of 2 pi (r + 0.5) / 2^32: the quadrant from the two top bits, the rest as a fraction of a quarter turn

@@ -104,19 +104,27 @@ STRETCH_HOP, STRETCH_WIN = 256, 1024            # the overlap-add's hop and wind
 DELETE_AT = {"start": 0, "anywhere": 1}         # where a sample deletion cuts: param[2] of the C ABI's entry
 
 
-def _no_pitch_shift(j: int, kind: str, out: list[dict]) -> None:
-    if any(o["kind"] == "pitch_shift" for o in out):
-        raise ValueError(f"loop_attacks[{j}] ({kind}): a chain holds a pitch shift or a {kind.replace('_', ' ')}, not both")
+# The one-split rule (csrc/loop_chain.hpp holds the device's statement of it): these kinds need launches of their own between
+# two stages of element-wise entries, and a chain holds at most one entry of them.  The one exception is the pair: a speed
+# change directly behind a time stretch.
+SPLITTING = ("reverberation", "speed_change", "time_stretch", "pitch_shift", "phase_vocoder", "delete_samples")
+_NAME = dict({k: k.replace("_", " ") for k in SPLITTING}, delete_samples="sample deletion")
 
 
-def _no_phase_vocoder(j: int, kind: str, out: list[dict]) -> None:
-    if any(o["kind"] == "phase_vocoder" for o in out):
-        raise ValueError(f"loop_attacks[{j}] ({kind}): a chain holds a phase vocoder or a {kind.replace('_', ' ')}, not both")
-
-
-def _no_delete_samples(j: int, kind: str, out: list[dict]) -> None:
-    if any(o["kind"] == "delete_samples" for o in out):
-        raise ValueError(f"loop_attacks[{j}] ({kind}): a chain holds a sample deletion or a {kind.replace('_', ' ')}, not both")
+def _one_split(j: int, kind: str, out: list[dict]) -> None:
+    """ValueError if entry j of a splitting kind may not join the entries `out` in front of it.  The message names the kind
+    itself if the chain holds it already, otherwise the last splitting entry, the later of the two in SPLITTING first."""
+    held = [o["kind"] for o in out if o["kind"] in SPLITTING]
+    if not held or (kind == "speed_change" and held == ["time_stretch"] and out[-1]["kind"] == "time_stretch"):
+        return
+    head = f"loop_attacks[{j}] ({kind}): "
+    if kind in held:
+        raise ValueError(head + f"at most one {_NAME[kind]} per chain")
+    if {kind, held[-1]} == {"speed_change", "time_stretch"}:
+        raise ValueError(head + ("beside a time stretch, the speed change follows it directly" if kind == "speed_change"
+                                 else "a speed change in the same chain follows the stretch directly"))
+    first, second = sorted((kind, held[-1]), key=SPLITTING.index, reverse=True)
+    raise ValueError(head + f"a chain holds a {_NAME[first]} or a {_NAME[second]}, not both")
 
 
 def _parse_rate(j: int, kind: str, a: dict) -> list[float]:
@@ -177,20 +185,16 @@ def _parse_cents(j: int, kind: str, a: dict) -> list[float]:
 def parse_chain(chain) -> list[dict]:
     """Validated copy of a chain such as [{"kind": "gaussian_noise", "snr_db": 10.0, "prob": 1.0},
     {"kind": "sample_suppression", "seconds": 0.3, "prob": 0.75}] (None / empty: no chain).  ValueError: unknown kind or key,
-    a missing parameter, prob outside [0, 1], a non-finite snr_db, seconds <= 0, more than four entries; for
+    a missing parameter, prob outside [0, 1], a non-finite snr_db, seconds <= 0, more than four entries, a second entry of the
+    SPLITTING kinds other than a speed change directly behind a time stretch (_one_split); and per kind, for
     {"kind": "reverberation", "rt60": 0.3 | [0.1, 0.5], "drr_db": -3.0}: a missing rt60, rt60 not 0 < lo <= hi (finite), a
-    non-finite drr_db, a second reverberation; for {"kind": "speed_change", "cents": 200.0 | [-50.0, 120.0]}: a missing
-    cents, a scalar <= 0, cents not -400 <= lo <= hi <= 400 (finite), a range that holds no speed offset (m_lo > m_hi), a
-    second speed change, a speed change in a chain with a reverberation; for {"kind": "time_stretch", "rate": 1.1 |
-    [0.9, 1.1]}: a missing rate, a scalar <= 1, rate not 0.75 <= lo <= hi <= 4/3 (finite), a range that holds no offset, a
-    second stretch, a stretch in a chain with a reverberation, a speed change anywhere but directly behind the stretch; for {"kind": "pitch_shift",
-    "cents": 100.0 | [-50.0, 120.0]}: what a speed change's cents are refused for, a second pitch shift, a pitch shift in a
-    chain with a reverberation, a speed change or a time stretch; for {"kind": "phase_vocoder", "rate": 1.15 | [0.85, 1.15],
-    "cents": 150.0 | [-50.0, 120.0]}: neither key, what a time stretch's rate or a speed change's cents are refused for, a second
-    phase vocoder, a phase vocoder in a chain with a reverberation, a speed change, a time stretch or a pitch shift; for
+    non-finite drr_db; for {"kind": "speed_change", "cents": 200.0 | [-50.0, 120.0]} and {"kind": "pitch_shift", "cents": ...}:
+    a missing cents, a scalar <= 0, cents not -400 <= lo <= hi <= 400 (finite), a range that holds no speed offset
+    (m_lo > m_hi); for {"kind": "time_stretch", "rate": 1.1 | [0.9, 1.1]}: a missing rate, a scalar <= 1, rate not
+    0.75 <= lo <= hi <= 4/3 (finite), a range that holds no offset; for {"kind": "phase_vocoder", "rate": 1.15 | [0.85, 1.15],
+    "cents": 150.0 | [-50.0, 120.0]}: neither key, what a time stretch's rate or a speed change's cents are refused for; for
     {"kind": "delete_samples", "seconds": 0.032 | [0.01, 0.2], "at": "start" | "anywhere"}: a missing seconds, seconds not
-    0 < lo <= hi (finite), more or fewer than two values in a list, an unknown at, a second sample deletion, a sample deletion in
-    a chain with any of those five kinds (in either order)."""
+    0 < lo <= hi (finite), more or fewer than two values in a list, an unknown at."""
     if not chain:
         return []
     if isinstance(chain, dict) or not isinstance(chain, (list, tuple)):
@@ -210,20 +214,13 @@ def parse_chain(chain) -> list[dict]:
         if not 0.0 <= prob <= 1.0:
             raise ValueError(f"loop_attacks[{j}] ({kind}): prob = {prob} outside [0, 1]")
         e = {"kind": kind, "prob": prob}
+        if kind in SPLITTING:
+            _one_split(j, kind, out)
         if kind == "gaussian_noise":
             if "snr_db" not in a or not math.isfinite(float(a["snr_db"])):
                 raise ValueError(f"loop_attacks[{j}] (gaussian_noise): a finite snr_db is required")
             e["snr_db"] = float(a["snr_db"])
         elif kind == "reverberation":
-            if any(o["kind"] == "reverberation" for o in out):
-                raise ValueError(f"loop_attacks[{j}] (reverberation): at most one reverberation per chain")
-            _no_pitch_shift(j, kind, out)
-            _no_phase_vocoder(j, kind, out)
-            _no_delete_samples(j, kind, out)
-            if any(o["kind"] == "speed_change" for o in out):
-                raise ValueError(f"loop_attacks[{j}] (reverberation): a chain holds a speed change or a reverberation, not both")
-            if any(o["kind"] == "time_stretch" for o in out):
-                raise ValueError(f"loop_attacks[{j}] (reverberation): a chain holds a time stretch or a reverberation, not both")
             if "rt60" not in a:
                 raise ValueError(f"loop_attacks[{j}] (reverberation): rt60 is required")
             rt = a["rt60"]
@@ -238,43 +235,12 @@ def parse_chain(chain) -> list[dict]:
                 raise ValueError(f"loop_attacks[{j}] (reverberation): a finite drr_db is required")
             e["rt60"], e["drr_db"] = [lo, hi], drr
         elif kind == "speed_change":
-            if any(o["kind"] == "speed_change" for o in out):
-                raise ValueError(f"loop_attacks[{j}] (speed_change): at most one speed change per chain")
-            _no_pitch_shift(j, kind, out)
-            _no_phase_vocoder(j, kind, out)
-            _no_delete_samples(j, kind, out)
-            if any(o["kind"] == "reverberation" for o in out):
-                raise ValueError(f"loop_attacks[{j}] (speed_change): a chain holds a speed change or a reverberation, not both")
-            if any(o["kind"] == "time_stretch" for o in out) and out[-1]["kind"] != "time_stretch":
-                raise ValueError(f"loop_attacks[{j}] (speed_change): beside a time stretch, the speed change follows it directly")
             e["cents"] = _parse_cents(j, kind, a)
         elif kind == "time_stretch":
-            if any(o["kind"] == "time_stretch" for o in out):
-                raise ValueError(f"loop_attacks[{j}] (time_stretch): at most one time stretch per chain")
-            _no_pitch_shift(j, kind, out)
-            _no_phase_vocoder(j, kind, out)
-            _no_delete_samples(j, kind, out)
-            if any(o["kind"] == "reverberation" for o in out):
-                raise ValueError(f"loop_attacks[{j}] (time_stretch): a chain holds a time stretch or a reverberation, not both")
-            if any(o["kind"] == "speed_change" for o in out):
-                raise ValueError(f"loop_attacks[{j}] (time_stretch): a speed change in the same chain follows the stretch directly")
             e["rate"] = _parse_rate(j, kind, a)
         elif kind == "pitch_shift":
-            if any(o["kind"] == "pitch_shift" for o in out):
-                raise ValueError(f"loop_attacks[{j}] (pitch_shift): at most one pitch shift per chain")
-            for other in ("reverberation", "speed_change", "time_stretch"):
-                if any(o["kind"] == other for o in out):
-                    raise ValueError(f"loop_attacks[{j}] (pitch_shift): a chain holds a pitch shift or a {other.replace('_', ' ')}, not both")
-            _no_phase_vocoder(j, kind, out)
-            _no_delete_samples(j, kind, out)
             e["cents"] = _parse_cents(j, kind, a)
         elif kind == "phase_vocoder":
-            if any(o["kind"] == "phase_vocoder" for o in out):
-                raise ValueError(f"loop_attacks[{j}] (phase_vocoder): at most one phase vocoder per chain")
-            for other in ("reverberation", "speed_change", "time_stretch", "pitch_shift"):
-                if any(o["kind"] == other for o in out):
-                    raise ValueError(f"loop_attacks[{j}] (phase_vocoder): a chain holds a phase vocoder or a {other.replace('_', ' ')}, not both")
-            _no_delete_samples(j, kind, out)
             if "rate" not in a and "cents" not in a:
                 raise ValueError(f"loop_attacks[{j}] (phase_vocoder): at least one of rate and cents is required")
             if "rate" in a:
@@ -282,11 +248,6 @@ def parse_chain(chain) -> list[dict]:
             if "cents" in a:
                 e["cents"] = _parse_cents(j, kind, a)
         elif kind == "delete_samples":
-            if any(o["kind"] == "delete_samples" for o in out):
-                raise ValueError(f"loop_attacks[{j}] (delete_samples): at most one sample deletion per chain")
-            for other in ("reverberation", "speed_change", "time_stretch", "pitch_shift", "phase_vocoder"):
-                if any(o["kind"] == other for o in out):
-                    raise ValueError(f"loop_attacks[{j}] (delete_samples): a chain holds a sample deletion or a {other.replace('_', ' ')}, not both")
             if "seconds" not in a:
                 raise ValueError(f"loop_attacks[{j}] (delete_samples): seconds is required")
             sec = a["seconds"]
@@ -716,16 +677,13 @@ def device_entries_ex(chain: list[dict], sample_rate: int):
         if a["kind"] == "reverberation":
             n_lo, n_hi = reverb_taps(a, sample_rate)
             out.append((KINDS[a["kind"]], a["prob"], [float(n_lo), float(n_hi), a["drr_db"], 0.0]))
-        elif a["kind"] in ("speed_change", "pitch_shift"):
-            m_lo, m_hi = speed_range(a)
+        elif a["kind"] in ("speed_change", "pitch_shift", "time_stretch"):
+            m_lo, m_hi = stretch_range(a) if a["kind"] == "time_stretch" else speed_range(a)
             out.append((KINDS[a["kind"]], a["prob"], [float(m_lo), float(m_hi), 0.0, 0.0]))
         elif a["kind"] == "phase_vocoder":
             q_lo, q_hi = stretch_range(a) if "rate" in a else (0, -1)
             m_lo, m_hi = speed_range(a) if "cents" in a else (0, -1)
             out.append((KINDS[a["kind"]], a["prob"], [float(q_lo), float(q_hi), float(m_lo), float(m_hi)]))
-        elif a["kind"] == "time_stretch":
-            m_lo, m_hi = stretch_range(a)
-            out.append((KINDS[a["kind"]], a["prob"], [float(m_lo), float(m_hi), 0.0, 0.0]))
         elif a["kind"] == "delete_samples":
             k_lo, k_hi = delete_range(a, sample_rate)
             out.append((KINDS[a["kind"]], a["prob"], [float(k_lo), float(k_hi), float(DELETE_AT[a["at"]]), 0.0]))

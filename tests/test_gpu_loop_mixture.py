@@ -241,6 +241,41 @@ def test_single_chain_handles_keep_their_bits(rt, O):
     assert got == want
 
 
+def test_every_chain_keeps_its_bits(rt, O, LA):
+    """tests/golden/loop_chains_sha256.json, recorded with the same tool on the commit before the chains' host logic moved into
+    csrc/loop_chain.hpp: every chain of VARIANTS and both MIXTURES, 8 iterations on three ragged clips (24 draws per entry, so
+    every entry of prob 0.75 fires and idles), sha256 of the coefficients, the best coefficients, the losses and the finished
+    waveform; and the two workspace byte counts of the C ABI for the same chains on that batch and on [16000, 8000]."""
+    import importlib.util
+    from aware_amd._lib import LoopAttackEx
+    spec = importlib.util.spec_from_file_location("loop_attack_bench", os.path.join(ROOT, "tools", "loop_attack_bench.py"))
+    tool = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(tool)
+    from aware_amd.utils.models import load
+    with open(os.path.join(ROOT, "tests", "golden", "loop_chains_sha256.json")) as f:
+        want = json.load(f)
+    names = [k for k in tool.VARIANTS if k != "none"] + list(tool.MIXTURES)
+    assert want["names"] == names and len(names) == 15 and want["lengths"] == [16000, 12000, 9000] and want["iters"] == 8
+    emb, _ = load()
+    emb.verbose = False
+    got = tool.dump(emb, None, names=names, lengths=want["lengths"], iters=want["iters"])
+    for name in names:
+        assert got[name] == want["sha256"][name], name
+    for ws in want["workspace"]:
+        batch = rt.Batch(ws["lengths"])
+        assert (batch.B, batch.total_out, batch.total_frames, batch.out_lengths) == \
+            (ws["dims"]["B"], ws["dims"]["NS"], ws["dims"]["NF"], ws["dims"]["out_len"])
+        assert len(ws["bytes"]) == (15 if ws["lengths"] == want["lengths"] else 14)
+        for name, nbytes in ws["bytes"].items():
+            if name in tool.VARIANTS:
+                ent = LA.device_entries_ex(LA.parse_chain(tool.VARIANTS[name]), 16000)
+                arr = (LoopAttackEx * len(ent))(*[LoopAttackEx(k, pr, (C.c_float * 4)(*p)) for k, pr, p in ent])
+                assert batch.lib.aware_embed_loop_attack_workspace_bytes_ex(batch.h, arr, len(ent)) == nbytes, (ws["lengths"], name)
+            else:
+                arr, keep = chains_struct(rt, LA, tool.MIXTURES[name])
+                assert batch.lib.aware_embed_loop_mixture_workspace_bytes(batch.h, arr, len(arr)) == nbytes, (ws["lengths"], name)
+
+
 # ---- 7. workspace and errors ------------------------------------------------------------------------------------------------------
 def chains_struct(rt, LA, mixture, sample_rate=16000):
     return rt.mixture_struct([(m["weight"], LA.device_entries_ex(LA.parse_chain(m["chain"]), sample_rate)) for m in mixture])

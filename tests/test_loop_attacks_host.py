@@ -243,3 +243,115 @@ def test_suppression_in_the_loop_survives_half_the_clip(value_setup):
     assert clean0 == 0.0 and clean2 == 0.0
     assert s0 >= 10.0
     assert s2 <= 0.5 * s0
+
+
+# ---- the one-split rule: the messages of parse_chain, and the C parser and carver on the CPU --------------------------------
+def _golden(name):
+    import json
+    with open(os.path.join(ROOT, "tests", "golden", name)) as f:
+        return json.load(f)
+
+
+def test_parse_chain_messages_are_the_recorded_ones():
+    """tests/golden/loop_chain_messages.json, recorded from parse_chain before the exclusion rule was stated once: every ordered
+    pair of the eight kinds with valid parameters and the chains that exercise the stretch-then-speed pair, "ok" or the message."""
+    table = _golden("loop_chain_messages.json")
+    assert list(table["entries"]) == list(LA.KINDS) and len(table["cases"]) == 64 + 6
+    for case in table["cases"]:
+        chain = [table["entries"][k] for k in case["chain"]]
+        try:
+            LA.parse_chain(chain)
+            got = "ok"
+        except ValueError as err:
+            got = str(err)
+        assert got == case["result"], case["chain"]
+
+
+def _entry_lines(entries):
+    return "".join(f"{k} {pr!r} " + " ".join(repr(float(x)) for x in (list(p) + [0.0] * 4)[:4]) + "\n" for k, pr, p in entries)
+
+
+def _chain_case(entries, ex=1):
+    return f"chain {len(entries)} {ex}\n" + _entry_lines(entries)
+
+
+def _mixture_case(chains):
+    return f"mixture {len(chains)}\n" + "".join(f"{w!r} {len(e)}\n" + _entry_lines(e) for e, w in chains)
+
+
+def _dims_case(d):
+    return f"dims {d['B']} {d['NS']} {d['NF']} {d['pstride']} " + " ".join(str(n) for n in d["out_len"]) + "\n"
+
+
+def test_c_parser_and_carver_on_the_cpu():
+    """csrc/loop_chain.hpp through tests/host_sim/loop_chain_check.cpp, built without HIP: the return code is 0 exactly where
+    parse_chain accepts the chain (the message table's chains through device_entries_ex); the byte counts of the bench tool's
+    variants and mixtures are those recorded on the device before the parser and the carver moved
+    (tests/golden/loop_chains_sha256.json, with the batches' dimensions); the -1 / -2 cases of test_workspace_and_error_codes."""
+    import importlib.util
+    import shutil
+    import subprocess
+    exe = os.path.join(ROOT, "tests", "host_sim", "loop_chain_check")
+    src = os.path.join(ROOT, "tests", "host_sim", "loop_chain_check.cpp")
+    hdrs = [os.path.join(ROOT, "aware_amd", "csrc", h) for h in ("loop_chain.hpp", "loop_limits.hpp")]
+    if not os.path.exists(exe) or os.path.getmtime(exe) < max(os.path.getmtime(f) for f in [src] + hdrs):
+        cxx = ["g++", "-O2", "-std=c++17"] if shutil.which("g++") else ["hipcc", "-O2", "-std=c++17", "-x", "hip", "--offload-host-only"]
+        subprocess.run(cxx + ["-o", exe, src], check=True)
+
+    def run(text):
+        out = subprocess.run([exe], input=text, check=True, capture_output=True, text=True).stdout.split()
+        return list(zip(map(int, out[0::2]), map(int, out[1::2])))
+
+    spec = importlib.util.spec_from_file_location("loop_attack_bench", os.path.join(ROOT, "tools", "loop_attack_bench.py"))
+    tool = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(tool)
+    fixture = _golden("loop_chains_sha256.json")
+    ragged, short = fixture["workspace"]
+    assert ragged["lengths"] == [16000, 12000, 9000] and short["lengths"] == [16000, 8000]
+
+    # 1. the message table: every entry alone through device_entries_ex, so that a chain parse_chain refuses reaches the C parser too
+    table = _golden("loop_chain_messages.json")
+    one = {k: LA.device_entries_ex(LA.parse_chain([a]), 16000)[0] for k, a in table["entries"].items()}
+    got = run(_dims_case(ragged["dims"]) + "".join(_chain_case([one[k] for k in case["chain"]]) for case in table["cases"]))
+    for case, (rc, nbytes) in zip(table["cases"], got):
+        assert (rc == 0) == (case["result"] == "ok") and rc in (0, -1), (case["chain"], rc)
+        assert nbytes > 0
+    # ... and the older entry points refuse kinds 2 to 7
+    got = run(_dims_case(ragged["dims"]) + "".join(_chain_case([one[k]], ex=0) for k in LA.KINDS))
+    assert [rc for rc, _ in got] == [0, 0] + [-1] * 6
+
+    # 2. the recorded byte counts
+    for ws in (ragged, short):
+        names = list(ws["bytes"])
+        assert len(names) == (15 if ws is ragged else 14)
+        text = _dims_case(ws["dims"])
+        for name in names:
+            if name in tool.VARIANTS:
+                text += _chain_case(LA.device_entries_ex(LA.parse_chain(tool.VARIANTS[name]), 16000))
+            else:
+                text += _mixture_case([(e, w) for w, e in LA.device_mixture(LA.parse_mixture(tool.MIXTURES[name]), 16000)])
+        for name, (rc, nbytes) in zip(names, run(text)):
+            assert rc == 0 and nbytes == ws["bytes"][name], (ws["lengths"], name, rc, nbytes)
+
+    # 3. test_workspace_and_error_codes on the batch [16000, 8000]: one chain of weight 1 is the chain's own workspace, rounded
+    # up to 256, then int [B]; the refused mixtures
+    B = short["dims"]["B"]
+    chains = [LA.device_entries_ex(LA.parse_chain(c), 16000) for c in
+              (tool.MIXTURES["four_families"][0]["chain"], tool.MIXTURES["four_families"][1]["chain"],
+               tool.MIXTURES["four_families"][2]["chain"], tool.MIXTURES["tempo_pitch"][0]["chain"], tool.VARIANTS["pitch"])]
+    got = run(_dims_case(short["dims"]) + "".join(_chain_case(e) + _mixture_case([(e, 1.0)]) for e in chains))
+    for (rc1, ex), (rc2, mixed) in zip(got[0::2], got[1::2]):
+        assert rc1 == 0 and rc2 == 0 and mixed == ((ex + 255) & ~255) + 4 * B
+    NO, SU, RV = (0, 1.0, [10.0]), (1, 1.0, [4800.0]), (2, 1.0, [1600.0, 8000.0, -3.0])
+    DS, SP = (7, 1.0, [1.0, 512.0, 1.0]), (3, 1.0, [-3678.0, 3896.0])
+    bad = [([([NO], -0.1)], -1), ([([NO], float("nan"))], -1), ([([NO], float("inf"))], -1),
+           ([([NO], 0.6), ([SU], 0.5)], -1),                            # a sum above 1
+           ([([NO], 0.5), ([(9, 1.0, [0.0])], 0.5)], -1),               # what the _ex setter refuses, per chain
+           ([([NO], 0.5), ([DS, SP], 0.5)], -1),                        # two kinds that split one chain
+           ([([NO] * 5, 0.5)], -1),
+           ([([RV], 0.5), ([RV, NO], 0.5)], -1),                        # a second reverberation chain
+           ([([NO], 0.5), ([(1, 1.0, [7936.0])], 0.5)], -2)]            # k >= Ny of the 8000-sample clip
+    got = run(_dims_case(short["dims"]) + "".join(_mixture_case(m) for m, _ in bad) + _mixture_case([([NO], 0.5), ([SU], 0.5 + 5e-7)]))
+    for (m, want), (rc, nbytes) in zip(bad, got):
+        assert rc == want and (nbytes == 0 or rc == -2), (m, rc, nbytes)
+    assert got[-1][0] == 0                                               # a sum within 1 + 1e-6

@@ -66,20 +66,22 @@ MIXTURES = {
 }
 
 
-def dump(emb, path):
-    """sha256 of what 20 iterations of a single-chain handle leave, per chain; written to `path` unless it is empty."""
+def dump(emb, path, names=("both", "pitch"), lengths=None, iters=20):
+    """sha256 of what `iters` iterations of a handle leave, per entry of `names` (a chain of VARIANTS, or a mixture of MIXTURES,
+    which is set through emb.loop_attack_mixture), on ten 1 s clips or a ragged batch of `lengths`; written to `path` unless it
+    is empty."""
     import hashlib
-    B, n = 10, 16000
+    lengths = [16000] * 10 if lengths is None else [int(n) for n in lengths]
     g = torch.Generator(device="cuda").manual_seed(11)
-    audio = 0.1 * torch.randn(B * n, generator=g, device="cuda")
-    target = torch.randint(0, 2, (B, 20), generator=g, device="cuda").float() * 2 - 1
-    batch = rt.Batch([n] * B)
+    audio = 0.1 * torch.randn(sum(lengths), generator=g, device="cuda")
+    target = torch.randint(0, 2, (len(lengths), 20), generator=g, device="cuda").float() * 2 - 1
+    batch = rt.Batch(lengths)
     out = {}
-    for name in ("both", "pitch"):
-        emb.loop_attacks, emb.loop_attack_mixture = VARIANTS[name], []
+    for name in names:
+        emb.loop_attacks, emb.loop_attack_mixture = (VARIANTS[name], []) if name in VARIANTS else ([], MIXTURES[name])
         sess = emb.start_session(batch, 16000)
         sess.begin(audio, target)
-        sess.iterate(20)
+        sess.iterate(iters)
         parts = {"coef": sess.coef, "best": sess.best_coef, "loss": sess.loss, "best_loss": sess.best_loss, "out": sess.finish(None)}
         out[name] = {k: hashlib.sha256(v.detach().cpu().numpy().tobytes()).hexdigest() for k, v in parts.items()}
     if path:
