@@ -238,6 +238,84 @@ class Reverberation(Attack):
 
 
 @register
+class GainEnvelope(Attack):
+    """EXTENSION (not in the reference, parity unpinned): a gain that moves over time, piecewise linear between random
+    breakpoints int(period * sr) samples apart, each breakpoint's gain uniform in [floor, 1].  Clip i draws the envelope of
+    seed + i that embedding.loop_attacks.gain_envelope specifies at step 0, entry 0: what a {"kind": "gain_envelope",
+    "period": period, "floor": floor} entry of the embed loop applies at its first step."""
+
+    def __init__(self, period=0.25, floor=0.0, seed=0):
+        self.period, self.floor, self.seed = float(period), float(floor), int(seed)
+        self.name = f"gain_envelope_{period}"
+
+    def apply_batch(self, x, sr, seeds=None):
+        if seeds is None:
+            seeds = [self.seed + i for i in range(x.B)]
+        return rt.gain_envelope(x, seeds, 0, 0, int(self.period * sr), self.floor)
+
+
+def _scale(x: "rt.Ragged", gains) -> "rt.Ragged":
+    """x times one gain curve per clip (torch tensors on x's device), float32."""
+    data = x.data.float()
+    return rt.Ragged(torch.cat([data[o:o + n] * g.to(data.dtype) for o, n, g in zip(x.offsets, x.lengths, gains)]), x.lengths)
+
+
+@register
+class Fade(Attack):
+    """EXTENSION (not in the reference, parity unpinned): a linear fade-in over the first seconds_in and / or a linear fade-out
+    over the last seconds_out of the clip.  A side that is not given is not faded; None means the whole clip for that side:
+    Fade(seconds_in=None) rises over the whole clip, Fade(seconds_out=0.5) falls over the last half second.  At least one side
+    is given.  Plain torch on the ragged buffer, on purpose: what the loop's gain_envelope entry buys is measured with an
+    operator its model does not contain."""
+    _ABSENT = object()
+
+    def __init__(self, seconds_in=_ABSENT, seconds_out=_ABSENT):
+        if seconds_in is Fade._ABSENT and seconds_out is Fade._ABSENT:
+            raise ValueError("Fade: at least one of seconds_in and seconds_out is required (None: the whole clip)")
+        for v in (seconds_in, seconds_out):
+            if v is not None and v is not Fade._ABSENT and not (np.isfinite(v) and v > 0.0):
+                raise ValueError(f"Fade: seconds have to be finite and > 0, or None; got {v!r}")
+        self.seconds_in, self.seconds_out = seconds_in, seconds_out
+        side = lambda v: "none" if v is Fade._ABSENT else ("all" if v is None else v)
+        self.name = f"fade_in_{side(seconds_in)}_out_{side(seconds_out)}"
+
+    def _samples(self, v, n, sr):
+        return 0 if v is Fade._ABSENT else (n if v is None else max(1, min(n, int(v * sr))))
+
+    def gain(self, n, sr, device):
+        t = torch.arange(n, dtype=torch.float64, device=device)
+        g = torch.ones(n, dtype=torch.float64, device=device)
+        k_in, k_out = self._samples(self.seconds_in, n, sr), self._samples(self.seconds_out, n, sr)
+        if k_in > 0:
+            g = g * torch.clamp(t / k_in, max=1.0)
+        if k_out > 0:
+            g = g * torch.clamp((n - 1 - t) / k_out, max=1.0)
+        return g.float()
+
+    def apply_batch(self, x, sr):
+        return _scale(x, [self.gain(n, sr, x.data.device) for n in x.lengths])
+
+
+@register
+class Tremolo(Attack):
+    """EXTENSION (not in the reference, parity unpinned): amplitude modulation 1 - depth / 2 * (1 + sin(2 pi rate_hz t)), t in
+    seconds from the clip's start: the gain swings between 1 and 1 - depth.  Plain torch, as Fade and for its reason."""
+
+    def __init__(self, rate_hz, depth):
+        self.rate_hz, self.depth = float(rate_hz), float(depth)
+        if not (np.isfinite(self.rate_hz) and self.rate_hz > 0.0 and 0.0 <= self.depth <= 1.0):
+            raise ValueError(f"Tremolo: rate_hz > 0 and 0 <= depth <= 1 are required; got {rate_hz!r}, {depth!r}")
+        self.name = f"tremolo_{rate_hz}Hz_{depth}"
+
+    def gain(self, n, sr, device):
+        t = torch.arange(n, dtype=torch.float64, device=device) / sr
+        return (1.0 - self.depth / 2.0 * (1.0 + torch.sin(2.0 * np.pi * self.rate_hz * t))).float()
+
+    def apply_batch(self, x, sr):
+        return _scale(x, [self.gain(n, sr, x.data.device) for n in x.lengths])
+
+
+@register
 class SpeedChange(Attack):
     """EXTENSION (not in the reference, parity unpinned): the clip played fast or slow by `cents` (pitch and duration change
     together, as under a sample-rate mismatch): Catmull-Rom resampling at the fixed ratio R / 65536,

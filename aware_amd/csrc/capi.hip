@@ -2102,6 +2102,20 @@ extern "C" int aware_delete_samples(const float* in, const int* off, const int* 
     return AWARE_OK;
 }
 
+// ---- the gain envelope alone (EXTENSION; attacks.GainEnvelope, runtime.gain_envelope, tests) ----------------------------------
+extern "C" int aware_gain_envelope(const float* in, const int* off, const int* len, int B, int max_len, const uint32_t* seeds,
+                                   int step, int entry, int p_lo, int p_hi, float floor, float* out, float* gains, void* stream) {
+    if (!in || !off || !len || !seeds || !out) return AWARE_E_BADARG;
+    if (B < 1 || B > 65535 || max_len < 1 || max_len > (1 << 30) || step < 0 || entry < 0 || entry >= kMaxLoopAttacks) return AWARE_E_BADARG;
+    if (p_lo < kEnvelopeMinPeriod || p_lo > p_hi || p_hi > kEnvelopeMaxPeriod || !(floor >= 0.f && floor < 1.f)) return AWARE_E_BADARG;
+    GainLaunch L;
+    L.in = in; L.out = out; L.gains = gains; L.off = off; L.len = len; L.B = B; L.max_len = max_len; L.seeds = seeds;
+    L.step = step; L.entry = entry; L.p_lo = p_lo; L.p_hi = p_hi; L.floor = floor;
+    launch_gain_envelope(L, (hipStream_t)stream);
+    LAUNCHCHK();
+    return AWARE_OK;
+}
+
 // ---- the offset search's selection (EXTENSION; AWAREDetector.detect_batch(sync_search=n), tests) ---------------------------
 extern "C" int aware_sync_select(const float* values, int B, int n, int L, float centre, float* out_values, int* out_index,
                                  float* out_conf, void* stream) {
@@ -2338,6 +2352,7 @@ static LoopAttackLaunch chain_stage_launch(const aware_embed* e, const LoopChain
     A.frame_off = b->d_frame_off; A.pcount = b->d_pc_syn; A.B = b->B; A.pstride = b->pstride; A.run_blocks = b->synth_run;
     A.step = e->step; A.seeds = la.seeds; A.n = la.n;
     for (int j = 0; j < la.n; ++j) { A.kind[j] = la.kind[j]; A.k[j] = la.k[j]; A.inv_snr[j] = la.inv_snr[j]; A.prob[j] = la.prob[j]; }
+    for (int j = 0; j < la.n; ++j) { A.p_lo[j] = la.p_lo[j]; A.p_hi[j] = la.p_hi[j]; A.floor[j] = la.floor[j]; }
     A.yraw = e->yraw; A.pmaxY = e->pmaxY; A.psq = la.psq; A.z = la.z; A.pmaxZ = la.pmaxZ;
     if (chain_splits(la)) { A.idle_plain = 1; A.gpad_out = la.gpad0; }
     // inside a mixture the pads are shared between the chains: a chain of kinds 0/1 has no idle rule, and writes the zeros

@@ -383,6 +383,8 @@ struct LoopAttackLaunch {
     int k[kMaxLoopAttacks] = {0};         // suppression: samples
     double inv_snr[kMaxLoopAttacks] = {0};   // noise: 10^(-snr_db / 10)
     float prob[kMaxLoopAttacks] = {0};
+    int p_lo[kMaxLoopAttacks] = {0}, p_hi[kMaxLoopAttacks] = {0};      // gain envelope: samples between breakpoints
+    float floor[kMaxLoopAttacks] = {0};   // gain envelope: the lowest gain
     const float* yraw = nullptr;          // the raw synthesis and its partial maxima
     const unsigned long long* pmaxY = nullptr;
     double* psq = nullptr;                // [kMaxLoopAttacks][B][pstride]
@@ -545,6 +547,20 @@ struct DeleteLaunch {
     const int* k = nullptr;               // [B]
 };
 void launch_delete_samples(const DeleteLaunch& L, hipStream_t st);
+
+// ---- loop_gain_kernels.hip: gain envelope (EXTENSION): the element-wise chain kind 8 alone (aware_gain_envelope); inside the
+// embed loop it runs in the stage kernels of loop_attack_kernels.hip (loop_gain.hpp holds what the two share) ---------------
+struct GainLaunch {
+    const float* in = nullptr; float* out = nullptr;      // may be the same buffer
+    float* gains = nullptr;               // null, or the layout of out: g itself
+    const int* off = nullptr; const int* len = nullptr;   // [B] float offset and length of clip b
+    int B = 0, max_len = 0;               // max_len >= every length
+    const unsigned* seeds = nullptr;      // [B]
+    int step = 0, entry = 0;
+    int p_lo = 0, p_hi = 0;               // kEnvelopeMinPeriod <= p_lo <= p_hi <= kEnvelopeMaxPeriod
+    float floor = 0.f;
+};
+void launch_gain_envelope(const GainLaunch& L, hipStream_t st);
 
 // ---- sync_kernels.hip: offset search in detection (EXTENSION): values [B][n][L] -> the row of the largest mean |v - centre|
 // per clip (the smallest j on a tie), its index and that mean; one wave per clip ------------------------------------------

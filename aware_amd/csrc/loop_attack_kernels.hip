@@ -7,6 +7,8 @@
 //     sample suppression (k samples):  start = (r1 * (Ny - k)) >> 32;  on: x[start : start + k] = 0
 //     Gaussian noise (snr_db):         sigma = sqrt(mean(x^2) / 10^(snr_db / 10)) (a constant in the backward pass);
 //                                      on: x += sigma * eps, eps_i from philox((i / 4, s, 0, j), (seed_b, 0x5EED)), Box-Muller
+//     gain envelope (P_lo, P_hi, floor): g(i) piecewise linear between drawn breakpoints P samples apart (loop_gain.hpp);
+//                                      on: x[i] *= g(i) (g a constant in the backward pass, which multiplies by it too)
 //   z = x; the loop's analysis then runs on z instead of y
 //
 // s is the optimiser step read from device memory, so a recorded graph replays with fresh draws.  Three kernels, all on the
@@ -14,8 +16,11 @@
 //   chain_kernel<false>  per noise entry: f64 partial sums of x^2 in front of it (fixed order, no atomics)
 //   chain_kernel<true>   z and the partial maxima of |z|
 //   chain_bwd_kernel     the synthesis adjoint's gradient with respect to N(N(z)) -> the gradient with respect to x
+// Each has a second instantiation (ENV) for the stages that hold a gain envelope; every other stage launches the first, which
+// holds no code and no LDS of the envelope.
 #include "common.hpp"
 #include "kernels.h"
+#include "loop_gain.hpp"
 #include "loop_rng.hpp"
 
 namespace aware {
@@ -44,6 +49,8 @@ struct ChainArgs {
     int k[kMaxLoopAttacks];               // suppression: samples
     double inv_snr[kMaxLoopAttacks];      // noise: 10^(-snr_db / 10)
     float prob[kMaxLoopAttacks];
+    int p_lo[kMaxLoopAttacks], p_hi[kMaxLoopAttacks];      // gain envelope: samples between breakpoints, drawn in [p_lo, p_hi]
+    float floor[kMaxLoopAttacks];         // gain envelope: the lowest gain
     int B;
     const float* yraw;                    // raw synthesis, clip b at 256 * (frame_off[b] - b)
     const unsigned long long* pmaxY;      // [B][pstride]
@@ -75,14 +82,17 @@ struct ChainState {
     bool on[kMaxLoopAttacks];
     int start[kMaxLoopAttacks];
     float sigma[kMaxLoopAttacks];
+    EnvBlock env[kMaxLoopAttacks];        // gain envelope: its geometry on this workgroup's run (ENV instantiations only)
 };
-template <bool SIGMA>
+// i_first: the first sample of the workgroup's run; gtab: [kMaxLoopAttacks][kEnvTab] in LDS, complete behind a barrier
+template <bool SIGMA, bool ENV>
 __device__ __forceinline__ ChainState chain_state(const ChainArgs& a, int b, int j0, int upto, int Ny, unsigned step,
-                                                  unsigned seed, double* dred) {
+                                                  unsigned seed, double* dred, int i_first = 0, float* gtab = nullptr) {
     ChainState cs;
 #pragma unroll
     for (int j = 0; j < kMaxLoopAttacks; ++j) {
         cs.on[j] = false; cs.start[j] = 0; cs.sigma[j] = 0.f;
+        if (ENV) cs.env[j] = EnvBlock{kEnvelopeMinPeriod, 0.f, 0, 0};
         if (j >= j0 && j < upto && a.kind[j] != kLoopReverberation && a.kind[j] != kLoopSpeedChange &&
             a.kind[j] != kLoopTimeStretch) {
             unsigned r[4];
@@ -90,12 +100,19 @@ __device__ __forceinline__ ChainState chain_state(const ChainArgs& a, int b, int
             cs.on[j] = loop_entry_fires(r[0], a.prob[j]);
             if (a.kind[j] == kLoopSampleSuppression) {
                 cs.start[j] = (int)(((unsigned long long)r[1] * (unsigned long long)(unsigned)(Ny - a.k[j])) >> 32);
+            } else if (ENV && a.kind[j] == kLoopGainEnvelope) {
+                if (cs.on[j]) {
+                    int P, ph;
+                    envelope_draw(r, a.p_lo[j], a.p_hi[j], P, ph);
+                    cs.env[j] = envelope_block(gtab + j * kEnvTab, i_first, P, ph, a.floor[j], step, (unsigned)j, seed);
+                }
             } else if (SIGMA) {
                 const double ss = block_sum_d(a.psq + ((size_t)j * a.B + b) * a.pstride, a.pcount[b], dred);
                 cs.sigma[j] = (float)sqrt(ss / (double)Ny * a.inv_snr[j]);
             }
         }
     }
+    if (ENV) __syncthreads();             // the tables are complete
     return cs;
 }
 
@@ -119,10 +136,11 @@ __device__ __forceinline__ bool chain_idle(const ChainArgs& a, unsigned step, un
 }
 
 // WRITE = false: partial sums of x^2 with the entries in front of `upto` applied; true: the whole chain, z and max|z|
-template <bool WRITE>
+template <bool WRITE, bool ENV>
 __global__ __launch_bounds__(kLaThreads) void chain_kernel(ChainArgs a) {
     __shared__ unsigned long long red[4];
     __shared__ double dred[4];
+    __shared__ float gtab[ENV ? kMaxLoopAttacks * kEnvTab : 1];
     const int b = blockIdx.y;
     if (loop_gate_skips(a.gate, b)) return;
     const int nblk = a.frame_off[b + 1] - a.frame_off[b] - 1;
@@ -134,7 +152,7 @@ __global__ __launch_bounds__(kLaThreads) void chain_kernel(ChainArgs a) {
     const ClipNorm cn = clip_norm_from_partials(a.pmaxY + (size_t)b * a.pstride, a.pcount[b], red);
     const float inv_m = a.norm ? 1.0f / cn.m : 1.0f, inv_m2 = a.norm ? 1.0f / cn.m2 : 1.0f;
     const unsigned step = (unsigned)(*a.step - a.step_back), seed = a.seeds[b];
-    const ChainState cs = chain_state<true>(a, b, a.j0, a.upto, Ny, step, seed, dred);
+    const ChainState cs = chain_state<true, ENV>(a, b, a.j0, a.upto, Ny, step, seed, dred, jb0 * kHop, gtab);
 
     const float4* y4 = reinterpret_cast<const float4*>(a.src + so);
     float4* z4 = reinterpret_cast<float4*>(a.z + so);
@@ -151,6 +169,11 @@ __global__ __launch_bounds__(kLaThreads) void chain_kernel(ChainArgs a) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e)
                         if ((unsigned)(i0 + e - cs.start[j]) < (unsigned)a.k[j]) v[e] = 0.f;
+                } else if (ENV && a.kind[j] == kLoopGainEnvelope) {
+                    float g[4];
+                    envelope_gain4(cs.env[j], gtab + j * kEnvTab, i0 - jb0 * kHop, g);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = v[e] * g[e];
                 } else {
                     float eps[4];
                     normal4((unsigned)q, step, (unsigned)j, seed, eps);
@@ -188,11 +211,13 @@ __global__ __launch_bounds__(kLaThreads) void chain_kernel(ChainArgs a) {
 
 // gy holds G = dL/d N(N(z)) (the synthesis adjoint run on z), pdot_in the partial sums of G * N(N(z)).  Backward of the two
 // normalisers at z (scale 1 / (m m2), the arg-max sample also carries -sum * sign(z[k])), identity through the noise (sigma is
-// a constant), the 0/1 mask through the suppressions.  The result replaces G; its partial sums against x = N(N(y)) go to
+// a constant), the 0/1 mask through the suppressions, the gains through the envelopes (all diagonal: their order is free).  The result replaces G; its partial sums against x = N(N(y)) go to
 // pdot_out, which is what the analysis adjoint needs for the normalisers in front of the chain.
+template <bool ENV>
 __global__ __launch_bounds__(kLaThreads) void chain_bwd_kernel(ChainArgs a) {
     __shared__ unsigned long long red[4];
     __shared__ double dred[4];
+    __shared__ float gtab[ENV ? kMaxLoopAttacks * kEnvTab : 1];
     const int b = blockIdx.y;
     if (loop_gate_skips(a.gate, b)) return;
     const int nblk = a.frame_off[b + 1] - a.frame_off[b] - 1;
@@ -234,7 +259,7 @@ __global__ __launch_bounds__(kLaThreads) void chain_bwd_kernel(ChainArgs a) {
         }
         return;
     }
-    const ChainState cs = chain_state<false>(a, b, a.j0, a.upto, Ny, step, seed, dred);
+    const ChainState cs = chain_state<false, ENV>(a, b, a.j0, a.upto, Ny, step, seed, dred, jb0 * kHop, gtab);
 
     const float4* y4 = reinterpret_cast<const float4*>(a.yraw + so);
     const float4* g4 = reinterpret_cast<const float4*>(a.gy + so);
@@ -270,6 +295,12 @@ __global__ __launch_bounds__(kLaThreads) void chain_bwd_kernel(ChainArgs a) {
                 for (int e = 0; e < 4; ++e)
                     if ((unsigned)(i0 + e - cs.start[j]) < (unsigned)a.k[j]) g[e] = 0.f;
             }
+            if (ENV && j >= a.j0 && j < a.upto && cs.on[j] && a.kind[j] == kLoopGainEnvelope) {
+                float ge[4];
+                envelope_gain4(cs.env[j], gtab + j * kEnvTab, i0 - jb0 * kHop, ge);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) g[e] = g[e] * ge[e];
+            }
         }
         gd4[q] = make_float4(g[0], g[1], g[2], g[3]);
 #pragma unroll
@@ -293,11 +324,19 @@ ChainArgs chain_args(const LoopAttackLaunch& L) {
         a.k[j] = j < L.n ? L.k[j] : 0;
         a.inv_snr[j] = j < L.n ? L.inv_snr[j] : 0.0;
         a.prob[j] = j < L.n ? L.prob[j] : 0.f;
+        a.p_lo[j] = j < L.n ? L.p_lo[j] : 0; a.p_hi[j] = j < L.n ? L.p_hi[j] : 0; a.floor[j] = j < L.n ? L.floor[j] : 0.f;
     }
     a.yraw = L.yraw; a.pmaxY = L.pmaxY; a.psq = L.psq; a.z = L.z; a.pmaxZ = L.pmaxZ;
     a.gate = L.gate;
     a.gy = L.gy; a.gdst = L.gy_out ? L.gy_out : L.gy; a.gpad = L.gpad; a.pdot_in = L.pdot_in; a.pdot_out = L.pdot_out;
     return a;
+}
+
+// whether entries [j0, j1) hold a gain envelope: the stage then launches the ENV instantiations
+bool stage_has_envelope(const LoopAttackLaunch& L, int j0, int j1) {
+    for (int j = j0; j < j1; ++j)
+        if (L.kind[j] == kLoopGainEnvelope) return true;
+    return false;
 }
 
 }  // namespace
@@ -311,16 +350,20 @@ void launch_loop_attack_stage(const LoopAttackLaunch& L, int j0, int j1, const f
     for (int j = j0; j < j1; ++j) {
         if (L.kind[j] != kLoopGaussianNoise) continue;
         a.upto = j;
-        hipLaunchKernelGGL(chain_kernel<false>, grid, dim3(kLaThreads), 0, st, a);
+        if (stage_has_envelope(L, j0, j)) hipLaunchKernelGGL((chain_kernel<false, true>), grid, dim3(kLaThreads), 0, st, a);
+        else hipLaunchKernelGGL((chain_kernel<false, false>), grid, dim3(kLaThreads), 0, st, a);
     }
     a.upto = j1;
-    hipLaunchKernelGGL(chain_kernel<true>, grid, dim3(kLaThreads), 0, st, a);
+    if (stage_has_envelope(L, j0, j1)) hipLaunchKernelGGL((chain_kernel<true, true>), grid, dim3(kLaThreads), 0, st, a);
+    else hipLaunchKernelGGL((chain_kernel<true, false>), grid, dim3(kLaThreads), 0, st, a);
 }
 
 void launch_loop_attack_stage_bwd(const LoopAttackLaunch& L, int j0, int j1, int at_z, int dot, hipStream_t st) {
     ChainArgs a = chain_args(L);
     a.j0 = j0; a.upto = j1; a.at_z = at_z; a.dot = dot;
-    hipLaunchKernelGGL(chain_bwd_kernel, dim3((unsigned)L.pstride, (unsigned)L.B, 1), dim3(kLaThreads), 0, st, a);
+    const dim3 grid((unsigned)L.pstride, (unsigned)L.B, 1);
+    if (stage_has_envelope(L, j0, j1)) hipLaunchKernelGGL(chain_bwd_kernel<true>, grid, dim3(kLaThreads), 0, st, a);
+    else hipLaunchKernelGGL(chain_bwd_kernel<false>, grid, dim3(kLaThreads), 0, st, a);
 }
 
 void launch_loop_attack_forward(const LoopAttackLaunch& L, hipStream_t st) {

@@ -2,7 +2,7 @@
 // chain's state, the parser with every AWARE_E_BADARG / AWARE_E_UNSUPPORTED of the setters, and the carving of the chains'
 // workspace.  Plain C++: no HIP header and no HIP call, so tests/host_sim/loop_chain_check.cpp runs it on the CPU.
 //
-// THE ONE-SPLIT RULE.  Kinds 0 and 1 (noise, suppression) are element-wise and run inside the stage kernels of
+// THE ONE-SPLIT RULE.  Kinds 0, 1 and 8 (noise, suppression, gain envelope) are element-wise and run inside the stage kernels of
 // loop_attack_kernels.hip.  Kinds 2 to 7 (reverberation, speed change, time stretch, pitch shift, phase vocoder, sample
 // deletion) each need launches of their own between two such stages: they SPLIT the chain.  A chain holds at most one
 // splitting entry.  The one exception: a speed change directly behind a time stretch (j == split + 1) forms one stage
@@ -55,6 +55,8 @@ struct LoopChainState {
     int kind[kMaxLoopAttacks] = {0}, k[kMaxLoopAttacks] = {0};
     double inv_snr[kMaxLoopAttacks] = {0};
     float prob[kMaxLoopAttacks] = {0};
+    int p_lo[kMaxLoopAttacks] = {0}, p_hi[kMaxLoopAttacks] = {0};      // gain envelope: samples between breakpoints, drawn in [p_lo, p_hi]
+    float floor[kMaxLoopAttacks] = {0};       // gain envelope: the lowest gain
     float* z = nullptr;                       // [NS] the attacked signal
     unsigned long long* pmaxZ = nullptr;      // [B][pstride]
     double* psq = nullptr;                    // [kMaxLoopAttacks][B][pstride] partial sums of squares per noise entry
@@ -100,7 +102,8 @@ inline int parse_loop_chain(const LoopDims& d, const aware_loop_attack_ex* attac
     static_assert(AWARE_LOOP_GAUSSIAN_NOISE == kLoopGaussianNoise && AWARE_LOOP_SAMPLE_SUPPRESSION == kLoopSampleSuppression &&
                   AWARE_LOOP_REVERBERATION == kLoopReverberation && AWARE_LOOP_SPEED_CHANGE == kLoopSpeedChange &&
                   AWARE_LOOP_TIME_STRETCH == kLoopTimeStretch && AWARE_LOOP_PITCH_SHIFT == kLoopPitchShift &&
-                  AWARE_LOOP_PHASE_VOCODER == kLoopPhaseVocoder && AWARE_LOOP_DELETE_SAMPLES == kLoopDeleteSamples, "");
+                  AWARE_LOOP_PHASE_VOCODER == kLoopPhaseVocoder && AWARE_LOOP_DELETE_SAMPLES == kLoopDeleteSamples &&
+                  AWARE_LOOP_GAIN_ENVELOPE == kLoopGainEnvelope, "");
     if (!attacks || n_attacks < 1 || n_attacks > kMaxLoopAttacks) return AWARE_E_BADARG;
     la.split = -1; la.pair_speed = -1; la.h = nullptr; la.v = nullptr;
     for (int j = 0; j < n_attacks; ++j) {
@@ -108,6 +111,7 @@ inline int parse_loop_chain(const LoopDims& d, const aware_loop_attack_ex* attac
         const float* p = a.param;
         if (!(a.prob >= 0.f && a.prob <= 1.f)) return AWARE_E_BADARG;
         la.kind[j] = a.kind; la.prob[j] = a.prob; la.k[j] = 0; la.inv_snr[j] = 0.0;
+        la.p_lo[j] = 0; la.p_hi[j] = 0; la.floor[j] = 0.f;
         if (a.kind == AWARE_LOOP_GAUSSIAN_NOISE) {
             if (!std::isfinite(p[0])) return AWARE_E_BADARG;
             la.inv_snr[j] = pow(10.0, -(double)p[0] / 10.0);
@@ -116,6 +120,12 @@ inline int parse_loop_chain(const LoopDims& d, const aware_loop_attack_ex* attac
         if (a.kind == AWARE_LOOP_SAMPLE_SUPPRESSION) {
             if (!(p[0] >= 1.f) || p[0] > 2147483520.f || p[0] != floorf(p[0])) return AWARE_E_BADARG;
             la.k[j] = (int)p[0];
+            continue;
+        }
+        if (ex && a.kind == AWARE_LOOP_GAIN_ENVELOPE) {      // element-wise: param = {P_lo, P_hi, floor, 0}, never a split
+            if (!int_range(p[0], p[1], (float)kEnvelopeMinPeriod, (float)kEnvelopeMaxPeriod) || !(p[2] >= 0.f && p[2] < 1.f))
+                return AWARE_E_BADARG;
+            la.p_lo[j] = (int)p[0]; la.p_hi[j] = (int)p[1]; la.floor[j] = p[2];
             continue;
         }
         if (!ex || a.kind < AWARE_LOOP_REVERBERATION || a.kind > AWARE_LOOP_DELETE_SAMPLES) return AWARE_E_BADARG;

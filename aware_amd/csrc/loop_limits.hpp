@@ -7,7 +7,7 @@ namespace aware {
 constexpr int kMaxLoopChains = 8;
 constexpr int kMaxLoopAttacks = 4;
 constexpr int kLoopGaussianNoise = 0, kLoopSampleSuppression = 1, kLoopReverberation = 2, kLoopSpeedChange = 3, kLoopTimeStretch = 4,
-              kLoopPitchShift = 5, kLoopPhaseVocoder = 6, kLoopDeleteSamples = 7;      // AWARE_LOOP_* of aware_hip.h
+              kLoopPitchShift = 5, kLoopPhaseVocoder = 6, kLoopDeleteSamples = 7, kLoopGainEnvelope = 8;      // AWARE_LOOP_* of aware_hip.h
 
 // reverberation (loop_reverb_kernels.hip)
 constexpr int kReverbMaxIr = 8192;        // taps
@@ -19,6 +19,9 @@ inline int reverb_blocks(int n) { return (n + kReverbBlock - 1) / kReverbBlock; 
 
 constexpr int kSpeedMin = -13520, kSpeedMax = 17034;      // speed offsets: ceil / floor of 65536 (2^(-+400 / 1200) - 1)
 constexpr int kStretchMin = -16384, kStretchMax = 21845;  // stretch offsets: ceil / floor of 65536 (0.75 - 1) and 65536 (4 / 3 - 1)
+
+// gain envelope (loop_attack_kernels.hip, loop_gain_kernels.hip): samples between two breakpoints
+constexpr int kEnvelopeMinPeriod = 64, kEnvelopeMaxPeriod = 1 << 20;
 
 // Attack mixtures: with `choice` set, a workgroup whose clip did not draw chain `chain` at this step returns at once
 struct LoopGate {

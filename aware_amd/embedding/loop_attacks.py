@@ -79,6 +79,18 @@ the loop's new stage.  For clip b (length Ny) at optimiser step s with seed_b:
         element-wise entries may stand in front of it and behind it, and a noise entry behind it takes its sigma from the
         shortened signal.
 
+      gain_envelope(period = v or [lo, hi] seconds, floor = 0.0), P_lo = int(lo * sample_rate), P_hi = int(hi * sample_rate),
+        64 <= P_lo <= P_hi <= 2^20, 0 <= floor < 1: a gain that moves over time (a fade, ducking, tremolo, an AGC riding the level):
+        P = P_lo + ((r[2] * (P_hi - P_lo + 1)) >> 32) samples between breakpoints, ph = (r[1] * P) >> 32 the phase of the first;
+        breakpoint k >= 0: w_k = philox4x32_10((k // 4, s, 16 + j, 0), (seed_b, 0x5EED))[k % 4] (the third counter words 16..19
+        are the envelopes': 0 is noise, 1..4 the entry draws, 8 the responses, 12 the mixture), u_k = (w_k >> 8) 2^-24 (exact in
+        float32), g_k = floor + (1 - floor) u_k in float32, so floor <= g_k <= 1;  at sample i: pos = i + ph, k = pos // P,
+        f = float32(pos - k P) / float32(P), g(i) = g_k + f (g_{k+1} - g_k): piecewise linear, continuous;  on: x[i] *= g(i).
+        A period longer than the clip is valid: the clip then sees one ramp.  g is detached: the backward pass is gx[i] = g(i) gz[i],
+        the same operator.  Element-wise as noise and suppression are: it does not split a chain, any number of entries may
+        stand in front of or behind a splitting entry and in every chain of a mixture, and a noise entry behind it takes its
+        sigma from the enveloped signal.  Host and device agree on g to 1e-6 (the division and the fused multiply-add).
+
 In the loop x = N(N(y)) of the raw synthesis y, N(v) = v / (max|v| + 1e-8), and the analysis (N, N, STFT, band magnitudes)
 runs on the chain's output."""
 from __future__ import annotations
@@ -91,10 +103,14 @@ import torch
 MAX_ATTACKS = 4
 KINDS = {"gaussian_noise": 0, "sample_suppression": 1, "reverberation": 2, "speed_change": 3, "time_stretch": 4,
          "pitch_shift": 5, "phase_vocoder": 6, "delete_samples": 7}      # AWARE_LOOP_* of include/aware_hip.h
+# The element-wise kinds added after the message table of tests/golden/loop_chain_messages.json was recorded.  That table and the
+# tests that iterate over KINDS pin KINDS to the eight kinds above, in their order, so later kinds have a table of their own;
+# kind_id() is the one lookup over both, for the parser and the device-entry builders.
+ELEMENTWISE_EX = {"gain_envelope": 8}
 _KEYS = {"gaussian_noise": {"kind", "snr_db", "prob"}, "sample_suppression": {"kind", "seconds", "prob"},
          "reverberation": {"kind", "rt60", "drr_db", "prob"}, "speed_change": {"kind", "cents", "prob"}, "time_stretch": {"kind", "rate", "prob"},
          "pitch_shift": {"kind", "cents", "prob"}, "phase_vocoder": {"kind", "rate", "cents", "prob"},
-         "delete_samples": {"kind", "seconds", "at", "prob"}}
+         "delete_samples": {"kind", "seconds", "at", "prob"}, "gain_envelope": {"kind", "period", "floor", "prob"}}
 _KEY1 = 0x5EED
 MAX_IR = 8192                   # taps of the longest impulse response
 _IR_WORD = 8                    # third Philox counter word of the impulse responses (0: noise, 1..4: entry draws)
@@ -102,6 +118,15 @@ MAX_CENTS = 400.0               # widest speed change or pitch shift either way
 MIN_RATE, MAX_RATE = 0.75, 4.0 / 3.0            # slowest and fastest time stretch
 STRETCH_HOP, STRETCH_WIN = 256, 1024            # the overlap-add's hop and window: the loop's STFT geometry
 DELETE_AT = {"start": 0, "anywhere": 1}         # where a sample deletion cuts: param[2] of the C ABI's entry
+MIN_PERIOD, MAX_PERIOD = 64, 1 << 20            # samples between two breakpoints of a gain envelope
+_ENV_WORD = 16                  # third Philox counter word of entry j's breakpoints is 16 + j
+
+
+def kind_id(kind) -> int | None:
+    """The C ABI's number of a chain kind (AWARE_LOOP_* of include/aware_hip.h), None for an unknown one."""
+    if not isinstance(kind, str):
+        return None
+    return KINDS.get(kind, ELEMENTWISE_EX.get(kind))
 
 
 # The one-split rule (csrc/loop_chain.hpp holds the device's statement of it): these kinds need launches of their own between
@@ -182,7 +207,7 @@ def _parse_cents(j: int, kind: str, a: dict) -> list[float]:
     return [lo, hi]
 
 
-def parse_chain(chain) -> list[dict]:
+def parse_chain(chain, sample_rate: int = 16000) -> list[dict]:
     """Validated copy of a chain such as [{"kind": "gaussian_noise", "snr_db": 10.0, "prob": 1.0},
     {"kind": "sample_suppression", "seconds": 0.3, "prob": 0.75}] (None / empty: no chain).  ValueError: unknown kind or key,
     a missing parameter, prob outside [0, 1], a non-finite snr_db, seconds <= 0, more than four entries, a second entry of the
@@ -194,7 +219,9 @@ def parse_chain(chain) -> list[dict]:
     0.75 <= lo <= hi <= 4/3 (finite), a range that holds no offset; for {"kind": "phase_vocoder", "rate": 1.15 | [0.85, 1.15],
     "cents": 150.0 | [-50.0, 120.0]}: neither key, what a time stretch's rate or a speed change's cents are refused for; for
     {"kind": "delete_samples", "seconds": 0.032 | [0.01, 0.2], "at": "start" | "anywhere"}: a missing seconds, seconds not
-    0 < lo <= hi (finite), more or fewer than two values in a list, an unknown at."""
+    0 < lo <= hi (finite), more or fewer than two values in a list, an unknown at; for {"kind": "gain_envelope",
+    "period": 0.25 | [0.05, 0.5], "floor": 0.0}: a missing period, period not 0 < lo <= hi (finite), a period that is not
+    64 <= P_lo <= P_hi <= 2^20 samples at `sample_rate` (the one rule that reads it), floor not 0 <= floor < 1 (finite)."""
     if not chain:
         return []
     if isinstance(chain, dict) or not isinstance(chain, (list, tuple)):
@@ -203,9 +230,9 @@ def parse_chain(chain) -> list[dict]:
         raise ValueError(f"loop_attacks: at most {MAX_ATTACKS} entries, got {len(chain)}")
     out = []
     for j, a in enumerate(chain):
-        if not isinstance(a, dict) or a.get("kind") not in KINDS:
+        if not isinstance(a, dict) or kind_id(a.get("kind")) is None:
             raise ValueError(f"loop_attacks[{j}]: unknown kind {a.get('kind') if isinstance(a, dict) else a!r}; "
-                             f"available: {list(KINDS)}")
+                             f"available: {list(KINDS) + list(ELEMENTWISE_EX)}")
         kind = a["kind"]
         extra = set(a) - _KEYS[kind]
         if extra:
@@ -268,6 +295,32 @@ def parse_chain(chain) -> list[dict]:
             if not isinstance(at, str) or at not in DELETE_AT:
                 raise ValueError(f"loop_attacks[{j}] (delete_samples): at = {at!r}; available: {list(DELETE_AT)}")
             e["at"] = at
+        elif kind == "gain_envelope":
+            if "period" not in a:
+                raise ValueError(f"loop_attacks[{j}] (gain_envelope): period is required")
+            pd = a["period"]
+            try:
+                if isinstance(pd, (list, tuple)):
+                    if len(pd) != 2:
+                        raise TypeError
+                    lo, hi = float(pd[0]), float(pd[1])
+                else:
+                    lo = hi = float(pd)
+            except (TypeError, ValueError):
+                raise ValueError(f"loop_attacks[{j}] (gain_envelope): period = {pd!r} is neither a number nor [lo, hi]") from None
+            if not (math.isfinite(lo) and math.isfinite(hi) and 0.0 < lo <= hi):
+                raise ValueError(f"loop_attacks[{j}] (gain_envelope): period needs 0 < lo <= hi, both finite; got {pd!r}")
+            try:
+                fl = float(a.get("floor", 0.0))
+            except (TypeError, ValueError):
+                raise ValueError(f"loop_attacks[{j}] (gain_envelope): floor = {a.get('floor')!r} is not a number") from None
+            if not (math.isfinite(fl) and 0.0 <= fl < 1.0):
+                raise ValueError(f"loop_attacks[{j}] (gain_envelope): floor needs 0 <= floor < 1, finite; got {a.get('floor')!r}")
+            e["period"], e["floor"] = [lo, hi], fl
+            try:
+                envelope_range(e, sample_rate)
+            except ValueError as err:
+                raise ValueError(f"loop_attacks[{j}] (gain_envelope): {err}") from None
         else:
             if "seconds" not in a or not math.isfinite(float(a["seconds"])) or float(a["seconds"]) <= 0.0:
                 raise ValueError(f"loop_attacks[{j}] (sample_suppression): seconds > 0 is required")
@@ -307,6 +360,16 @@ def delete_range(entry: dict, sample_rate: int) -> tuple[int, int]:
     if isinstance(sec, (list, tuple)):
         return int(sec[0] * sample_rate), int(sec[1] * sample_rate)
     return 1, int(sec * sample_rate)
+
+
+def envelope_range(entry: dict, sample_rate: int) -> tuple[int, int]:
+    """(P_lo, P_hi) = (int(lo * sample_rate), int(hi * sample_rate)) of a parsed gain_envelope entry: samples between two
+    breakpoints.  ValueError unless 64 <= P_lo <= P_hi <= 2^20."""
+    p_lo, p_hi = int(entry["period"][0] * sample_rate), int(entry["period"][1] * sample_rate)
+    if not MIN_PERIOD <= p_lo <= p_hi <= MAX_PERIOD:
+        raise ValueError(f"period = {entry['period']} s is {p_lo}..{p_hi} samples at {sample_rate} Hz, outside "
+                         f"{MIN_PERIOD}..{MAX_PERIOD}")
+    return p_lo, p_hi
 
 
 def check_lengths(chain: list[dict], sample_rate: int, out_lengths) -> None:
@@ -606,6 +669,46 @@ def delete_samples_adjoint(gz: torch.Tensor, start: int, k: int) -> torch.Tensor
     return torch.cat([gz[..., :start], torch.zeros(gz.shape[:-1] + (k,), dtype=gz.dtype, device=gz.device), gz[..., start:n - k]], dim=-1)
 
 
+def envelope_draw(entry: dict, r, sample_rate: int) -> tuple[int, int]:
+    """(P, ph) of a parsed gain_envelope entry from its draw r = entry_draw(seed, step, j): P = P_lo + ((r[2] * (P_hi - P_lo + 1))
+    >> 32) samples between breakpoints, ph = (r[1] * P) >> 32 < P the phase of the first."""
+    p_lo, p_hi = envelope_range(entry, sample_rate)
+    P = p_lo + ((int(r[2]) * (p_hi - p_lo + 1)) >> 32)
+    return P, (int(r[1]) * P) >> 32
+
+
+def envelope_gains(seed: int, step: int, j: int, n_k: int, floor: float) -> np.ndarray:
+    """The first n_k breakpoint gains (float32) of envelope entry j at this step: w_k = philox4x32_10((k // 4, step, 16 + j, 0),
+    (seed, 0x5EED))[k % 4], u_k = (w_k >> 8) 2^-24, g_k = floor + (1 - floor) u_k in float32."""
+    nblk = (int(n_k) + 3) // 4
+    ctr = np.zeros((nblk, 4), dtype=np.uint64)
+    ctr[:, 0] = np.arange(nblk, dtype=np.uint64)
+    ctr[:, 1] = step
+    ctr[:, 2] = _ENV_WORD + int(j)
+    w = philox4x32(ctr, (int(seed) & 0xFFFFFFFF, _KEY1)).reshape(-1)[:int(n_k)]
+    u = (w >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24)
+    fl = np.float32(floor)
+    return (fl + (np.float32(1.0) - fl) * u).astype(np.float32)
+
+
+def envelope_curve(n: int, seed: int, step: int, j: int, P: int, ph: int, floor: float) -> np.ndarray:
+    """g(i), i < n, in float32: pos = i + ph, k = pos // P, f = float32(pos - k P) / float32(P), g = g_k + f (g_{k+1} - g_k)."""
+    pos = np.arange(int(n), dtype=np.int64) + int(ph)
+    k = pos // int(P)
+    g = envelope_gains(seed, step, j, (int(k[-1]) + 2) if n else 0, floor)
+    f = (pos - k * int(P)).astype(np.float32) / np.float32(P)
+    return (g[k] + f * (g[k + 1] - g[k])).astype(np.float32)
+
+
+def gain_envelope(x, seed, step: int, j: int, P: int, ph: int, floor: float):
+    """x * g with g = envelope_curve(...) detached, in x's dtype: x a tensor [n] with one seed, or a list of 1-D tensors (ragged)
+    with a seed each.  Differentiable in x; float32 or float64.  Forward and adjoint are the same operator."""
+    if not torch.is_tensor(x):
+        return [gain_envelope(xb, sd, step, j, P, ph, floor) for xb, sd in zip(x, seed)]
+    g = envelope_curve(x.shape[-1], int(seed) & 0xFFFFFFFF, step, j, P, ph, floor)
+    return x * torch.as_tensor(g).to(dtype=x.dtype, device=x.device)
+
+
 def _convolve(xb: torch.Tensor, h: np.ndarray) -> torch.Tensor:
     """(h * xb)[0 : len(xb)] in xb's dtype through an FFT at least len(xb) + len(h) - 1 long; differentiable in xb."""
     ny, nh = xb.shape[-1], len(h)
@@ -616,9 +719,9 @@ def _convolve(xb: torch.Tensor, h: np.ndarray) -> torch.Tensor:
 
 def apply_chain(x, chain, seeds, step: int, sample_rate: int = 16000):
     """The chain on x: a tensor [B, Ny] or a list of B 1-D tensors (ragged), float32 or float64; differentiable (the noise
-    amplitude is detached, a suppression multiplies by a 0/1 mask).  seeds: B integers; step: the optimiser step.  Returns the
+    amplitude is detached, a suppression multiplies by a 0/1 mask, a gain envelope by its detached gains).  seeds: B integers; step: the optimiser step.  Returns the
     same container type."""
-    chain = parse_chain(chain)
+    chain = parse_chain(chain, sample_rate)
     clips = list(x) if not torch.is_tensor(x) else [x[b] for b in range(x.shape[0])]
     if len(seeds) != len(clips):
         raise ValueError(f"apply_chain: {len(clips)} clips but {len(seeds)} seeds")
@@ -658,6 +761,10 @@ def apply_chain(x, chain, seeds, step: int, sample_rate: int = 16000):
                 start, k = delete_draw(a, r, ny, sample_rate)
                 if on:
                     xb = delete_samples(xb, start, k)
+            elif a["kind"] == "gain_envelope":
+                P, ph = envelope_draw(a, r, sample_rate)
+                if on:
+                    xb = gain_envelope(xb, seed, step, j, P, ph, a["floor"])
             elif on:
                 power = float(np.mean(xb.detach().double().cpu().numpy() ** 2))
                 sigma = math.sqrt(power / (10.0 ** (a["snr_db"] / 10.0)))
@@ -671,22 +778,25 @@ def device_entries_ex(chain: list[dict], sample_rate: int):
     """(kind, prob, [param0..3]) of the C ABI's aware_loop_attack_ex: kinds 0 and 1 as device_entries in param[0]; a
     reverberation has param = [n_lo, n_hi, drr_db, 0], a speed change, a time stretch or a pitch shift [m_lo, m_hi, 0, 0], a
     phase vocoder [mq_lo, mq_hi, m_lo, m_hi] with [0, -1] (lo > hi) for an absent mode, a sample deletion
-    [k_lo, k_hi, at (0 start / 1 anywhere), 0]."""
+    [k_lo, k_hi, at (0 start / 1 anywhere), 0], a gain envelope [P_lo, P_hi, floor, 0]."""
     out = []
     for a in chain:
-        if a["kind"] == "reverberation":
+        if a["kind"] == "gain_envelope":
+            p_lo, p_hi = envelope_range(a, sample_rate)
+            out.append((kind_id(a["kind"]), a["prob"], [float(p_lo), float(p_hi), a["floor"], 0.0]))
+        elif a["kind"] == "reverberation":
             n_lo, n_hi = reverb_taps(a, sample_rate)
-            out.append((KINDS[a["kind"]], a["prob"], [float(n_lo), float(n_hi), a["drr_db"], 0.0]))
+            out.append((kind_id(a["kind"]), a["prob"], [float(n_lo), float(n_hi), a["drr_db"], 0.0]))
         elif a["kind"] in ("speed_change", "pitch_shift", "time_stretch"):
             m_lo, m_hi = stretch_range(a) if a["kind"] == "time_stretch" else speed_range(a)
-            out.append((KINDS[a["kind"]], a["prob"], [float(m_lo), float(m_hi), 0.0, 0.0]))
+            out.append((kind_id(a["kind"]), a["prob"], [float(m_lo), float(m_hi), 0.0, 0.0]))
         elif a["kind"] == "phase_vocoder":
             q_lo, q_hi = stretch_range(a) if "rate" in a else (0, -1)
             m_lo, m_hi = speed_range(a) if "cents" in a else (0, -1)
-            out.append((KINDS[a["kind"]], a["prob"], [float(q_lo), float(q_hi), float(m_lo), float(m_hi)]))
+            out.append((kind_id(a["kind"]), a["prob"], [float(q_lo), float(q_hi), float(m_lo), float(m_hi)]))
         elif a["kind"] == "delete_samples":
             k_lo, k_hi = delete_range(a, sample_rate)
-            out.append((KINDS[a["kind"]], a["prob"], [float(k_lo), float(k_hi), float(DELETE_AT[a["at"]]), 0.0]))
+            out.append((kind_id(a["kind"]), a["prob"], [float(k_lo), float(k_hi), float(DELETE_AT[a["at"]]), 0.0]))
         else:
             k, p, pr = device_entries([a], sample_rate)[0]
             out.append((k, pr, [p, 0.0, 0.0, 0.0]))
@@ -696,7 +806,7 @@ def device_entries_ex(chain: list[dict], sample_rate: int):
 def device_entries(chain: list[dict], sample_rate: int):
     """(kind, param, prob) triples of the C ABI (aware_loop_attack): param = snr_db or the suppression length in samples.
     Chains of these two kinds only; every other kind goes through device_entries_ex."""
-    return [(KINDS[a["kind"]], a["snr_db"] if a["kind"] == "gaussian_noise" else float(suppression_samples(a, sample_rate)),
+    return [(kind_id(a["kind"]), a["snr_db"] if a["kind"] == "gaussian_noise" else float(suppression_samples(a, sample_rate)),
              a["prob"]) for a in chain]
 
 

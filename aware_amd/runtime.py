@@ -594,7 +594,7 @@ class EmbedSession:
             raise ValueError(f"set_loop_attacks: {self.batch.B} clips but {len(seeds)} seeds")
         la.check_lengths(chain, sample_rate, self.batch.out_lengths)      # ValueError naming the clip, before any launch
         sd = (C.c_uint32 * self.batch.B)(*[int(s) & 0xFFFFFFFF for s in seeds])
-        if any(a["kind"] in ("reverberation", "speed_change", "time_stretch", "pitch_shift", "phase_vocoder", "delete_samples") for a in chain):
+        if any(a["kind"] not in ("gaussian_noise", "sample_suppression") for a in chain):
             # the entry points with four parameters per entry; chains of the two older kinds keep the older call
             ent = la.device_entries_ex(chain, sample_rate)
             arr = (_lib.LoopAttackEx * len(ent))(*[_lib.LoopAttackEx(k, pr, (C.c_float * 4)(*p)) for k, pr, p in ent])
@@ -1015,6 +1015,32 @@ def delete_samples(x: Ragged, start, k, adjoint: bool = False) -> Ragged:
     check(lib.aware_delete_samples(_ptr(xin), _ptr(x.d_off), _ptr(x.d_len), x.B, x.max_len, _ptr(sd), _ptr(kd), _ptr(out.data),
                                    int(bool(adjoint)), _stream()), "aware_delete_samples")
     return out
+
+
+def gain_envelope(x: Ragged, seeds: Sequence[int], step: int, entry: int, period_samples, floor: float = 0.0,
+                  return_gains: bool = False, out: Ragged | None = None):
+    """Per clip embedding.loop_attacks.gain_envelope with the draw of chain entry `entry` at optimiser step `step`, always on
+    (aware_gain_envelope): clip b times a gain that is piecewise linear between breakpoints P samples apart, P drawn from the
+    clip's seed in period_samples = P or (P_lo, P_hi), every breakpoint's gain in [floor, 1].  The operator is its own adjoint.
+    out: a Ragged of x's lengths to write into (x itself: in place).  With return_gains the result is (out, gains)."""
+    lib = load_library()
+    p_lo, p_hi = (int(period_samples),) * 2 if np.isscalar(period_samples) else (int(period_samples[0]), int(period_samples[1]))
+    if len(seeds) != x.B:
+        raise ValueError(f"gain_envelope: {x.B} clips but {len(seeds)} seeds")
+    xin = x.data if x.data.dtype == torch.float32 else x.data.float()
+    if out is None:
+        out = Ragged(torch.empty(sum(x.lengths), dtype=torch.float32, device=xin.device), x.lengths)
+    elif list(out.lengths) != list(x.lengths) or out.data.dtype != torch.float32:
+        raise ValueError("gain_envelope: out needs x's lengths in float32")
+    gains = Ragged(torch.empty(sum(x.lengths), dtype=torch.float32, device=xin.device), x.lengths) if return_gains else None
+    sd = torch.from_numpy(np.array([int(s) & 0xFFFFFFFF for s in seeds], dtype=np.uint32).view(np.int32)).to(xin.device)
+    rc = lib.aware_gain_envelope(_ptr(xin), _ptr(x.d_off), _ptr(x.d_len), x.B, x.max_len, _ptr(sd), int(step), int(entry), p_lo, p_hi,
+                                 float(floor), _ptr(out.data), _ptr(gains.data) if return_gains else None, _stream())
+    if rc == -1:
+        raise ValueError(f"gain_envelope: 64 <= P_lo <= P_hi <= 2^20, 0 <= floor < 1, step >= 0 and entry in 0..3 are required; got "
+                         f"{p_lo}, {p_hi}, {floor}, step {step}, entry {entry}")
+    check(rc, "aware_gain_envelope")
+    return (out, gains) if return_gains else out
 
 
 def sync_select(values: torch.Tensor, n: int, centre: float = 0.0):

@@ -696,6 +696,33 @@ int aware_pv_frames_bwd(const void* spec, const void* grad_out, const int* frame
 int aware_delete_samples(const float* in, const int* off, const int* len, int B, int max_len, const int* start, const int* k,
                          float* out, int adjoint, void* stream);
 
+/* ---- gain envelope inside the loop and alone (EXTENSION, parity unpinned: the reference has neither) -----------------------
+ * The _ex pair and the mixture's setter also accept (the older entry point keeps refusing every kind above 1)
+ *   AWARE_LOOP_GAIN_ENVELOPE, param = { P_lo, P_hi, floor, 0 }: a gain that moves over time, piecewise linear between random
+ *     breakpoints (a fade, ducking, tremolo, an AGC riding the level).  With r the entry's draw as above,
+ *     P = P_lo + ((r[2] * (P_hi - P_lo + 1)) >> 32) samples between breakpoints (the host converts seconds),
+ *     ph = (r[1] * P) >> 32;  breakpoint k >= 0: w_k = philox4x32_10((k / 4, s, 16 + j, 0), (seed_b, 0x5EED))[k % 4],
+ *     u_k = (w_k >> 8) * 2^-24, g_k = floor + (1 - floor) * u_k in f32;  at sample i: pos = i + ph, k = pos / P,
+ *     f = (float)(pos - k * P) / (float)P, g(i) = g_k + f * (g_{k+1} - g_k);
+ *   on: z[i] = g(i) * x[i].  P may exceed Ny_b: the clip then sees one ramp.  g is a CONSTANT in the backward pass, which is
+ *   the same operator: gx[i] = g(i) * gz[i].  The kind is ELEMENT-WISE, as kinds 0 and 1 are: it runs inside the stage kernels,
+ *   never splits a chain, may stand any number of times (up to the chain's four entries) in front of and behind a splitting
+ *   entry and in every chain of a mixture, and a noise entry behind it takes its sigma from the enveloped signal.  The device
+ *   evaluates f with a reciprocal and a fused multiply-add: g is within 1e-6 of the formula above.
+ * AWARE_E_BADARG of the _ex setter, besides those above: a period that is not an integer, P_lo < 64, P_lo > P_hi,
+ * P_hi > 1048576, floor outside [0, 1) or not finite.  aware_embed_loop_attack_workspace_bytes_ex for a chain with the kind is
+ * that of the same chain with a Gaussian noise in its place: no new workspace.  Added without a version step: callers detect
+ * the addition by symbol. */
+#define AWARE_LOOP_GAIN_ENVELOPE 8       /* param = P_lo, P_hi (samples; the host converts seconds), floor, 0 */
+/* The same operator alone, on a ragged batch, always on: clip b is len[b] floats at float offset off[b] of `in` and of `out`
+ * (dev int [B], any offsets, every length <= max_len <= 2^30); seeds dev uint32 [B]; the draw is that of chain entry `entry`
+ * (0..3) at optimiser step `step` (>= 0).  out[i] = g(i) * in[i]; out may be in.  gains: NULL, or dev float with the layout of
+ * `out`, receives g itself.  The operator is its own adjoint.  One launch on `stream`.  AWARE_E_BADARG: a null argument (gains
+ * apart), B < 1 or > 65535, max_len < 1 or > 2^30, step < 0, entry outside 0..3, the periods or the floor as above (checked
+ * before anything is launched). */
+int aware_gain_envelope(const float* in, const int* off, const int* len, int B, int max_len, const uint32_t* seeds, int step,
+                        int entry, int p_lo, int p_hi, float floor, float* out, float* gains, void* stream);
+
 /* ---- attack mixtures (EXTENSION, parity unpinned: the reference has no attacks in its loop) -------------------------------
  * A handle holds one chain, and the kinds that split a chain refuse each other.  A mixture is a list of 1..8 chains, each a
  * valid chain of aware_embed_set_loop_attacks_ex with a weight; at optimiser step s clip b draws

@@ -13,6 +13,8 @@
 a mixture's iteration reads against the weighted mean and the sum of its chains.  `--dump FILE` does none of the above: it runs
 20 iterations of a kind-0/1 chain and of a pitch-shift chain on ten 1 s clips and writes the sha256 of the coefficients, the best
 coefficients, the losses and the finished waveform, the record a change to the loop is compared against.
+`--envelope` adds the chains of ENVELOPE_VARIANTS, which hold the gain envelope, to (a); `--variants` may
+name them too.
 `--only-loop` runs a few steps of every variant and nothing else, for a per-kernel trace
 (rocprofv3 --kernel-trace --stats -- python tools/loop_attack_bench.py --only-loop)."""
 import argparse
@@ -46,6 +48,17 @@ VARIANTS = {
     "delete": [{"kind": "delete_samples", "seconds": 0.032, "prob": 0.75}],
     "suppression_delete_noise": [{"kind": "sample_suppression", "seconds": 0.3}, {"kind": "delete_samples", "seconds": [0.01, 0.2], "at": "anywhere", "prob": 0.75},
                                  {"kind": "gaussian_noise", "snr_db": 10.0}],
+}
+
+# The chains with a gain envelope (chain kind 8) live in a table of their own: the recorded fixtures of the loop's chains
+# (tests/golden/loop_chains_sha256.json) key on VARIANTS, names and count.
+ENVELOPE_VARIANTS = {
+    "envelope": [{"kind": "gain_envelope", "period": [0.05, 0.5], "prob": 0.75}],
+    "envelope_noise": [{"kind": "gain_envelope", "period": [0.05, 0.5], "prob": 0.75}, {"kind": "gaussian_noise", "snr_db": 10.0}],
+    "envelope_64": [{"kind": "gain_envelope", "period": 0.004}],
+    "envelope_reverb_envelope": [{"kind": "gain_envelope", "period": [0.05, 0.5], "prob": 0.75},
+                                 {"kind": "reverberation", "rt60": [0.1, 0.5], "drr_db": -3.0, "prob": 0.75},
+                                 {"kind": "gain_envelope", "period": 0.25, "floor": 0.25}],
 }
 
 
@@ -138,6 +151,7 @@ def main():
     ap.add_argument("--sync", type=int, default=0)
     ap.add_argument("--mixture", default="")
     ap.add_argument("--dump", default="")
+    ap.add_argument("--envelope", action="store_true")
     args = ap.parse_args()
     B, n = args.clips, int(args.seconds * 16000)
     emb, det = load()
@@ -158,6 +172,7 @@ def main():
         print(f"detect: plain {t['plain']:.1f} us, sync_search = {args.sync}: {t['search']:.1f} us ({t['search'] / t['plain']:.2f} x)")
     chosen = {"none"} | {v for v in args.variants.split(",") if v}
     variants = {k: v for k, v in VARIANTS.items() if not args.variants or k in chosen}
+    variants.update({k: v for k, v in ENVELOPE_VARIANTS.items() if k in chosen or (args.envelope and not args.variants)})
     mixtures = {}
     for m in [v for v in args.mixture.split(",") if v]:
         mixtures[f"mixture:{m}"] = MIXTURES[m]
