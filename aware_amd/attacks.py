@@ -254,6 +254,33 @@ class GainEnvelope(Attack):
         return rt.gain_envelope(x, seeds, 0, 0, int(self.period * sr), self.floor)
 
 
+@register
+class BandFilter(Attack):
+    """EXTENSION (not in the reference, parity unpinned): the embed loop's band_filter operator at fixed edges, applied after
+    embedding: a zero-phase windowed-sinc FIR of 255 taps (embedding.loop_attacks.filter_taps), response "lowpass" or "highpass"
+    at freq Hz, "bandpass" or "bandstop" between freq and freq_hi Hz.  The Butterworth classes above are what the loop's kind
+    is measured against; this one is its own model."""
+
+    def __init__(self, response, freq, freq_hi=None):
+        from .embedding.loop_attacks import RESPONSES
+        if response not in RESPONSES:
+            raise ValueError(f"BandFilter: response = {response!r}; available: {list(RESPONSES)}")
+        band = RESPONSES[response] >= 4
+        if band != (freq_hi is not None):
+            raise ValueError(f"BandFilter: {response} takes freq{' and freq_hi' if band else ' alone'}")
+        self.response, self.freq, self.freq_hi = response, float(freq), float(freq if freq_hi is None else freq_hi)
+        if not (np.isfinite(self.freq) and np.isfinite(self.freq_hi) and 0.0 < self.freq <= self.freq_hi):
+            raise ValueError(f"BandFilter: 0 < freq <= freq_hi, both finite, are required; got {freq!r}, {freq_hi!r}")
+        self.name = f"band_filter_{response}_{freq}" + (f"_{freq_hi}" if band else "")
+
+    def apply_batch(self, x, sr):
+        from .embedding.loop_attacks import MAX_EDGE, RESPONSES, filter_edge
+        c1, c2 = filter_edge(self.freq, sr), filter_edge(self.freq_hi, sr)
+        if not 1 <= c1 <= c2 <= MAX_EDGE:
+            raise ValueError(f"BandFilter: {self.freq} .. {self.freq_hi} Hz does not lie inside (0, Nyquist) at {sr} Hz")
+        return rt.band_filter(x, RESPONSES[self.response], c1, c2)
+
+
 def _scale(x: "rt.Ragged", gains) -> "rt.Ragged":
     """x times one gain curve per clip (torch tensors on x's device), float32."""
     data = x.data.float()

@@ -2102,6 +2102,19 @@ extern "C" int aware_delete_samples(const float* in, const int* off, const int* 
     return AWARE_OK;
 }
 
+// ---- the band filter alone (EXTENSION; attacks.BandFilter, runtime.band_filter, tests) -------------------------------------
+extern "C" int aware_band_filter(const float* in, const int* off, const int* len, int B, int max_len, const int* response,
+                                 const int* c1, const int* c2, float* out, float* taps, void* stream) {
+    if (!in || !off || !len || !response || !c1 || !c2 || !out || in == out) return AWARE_E_BADARG;
+    if (B < 1 || B > 65535 || max_len < 1 || max_len > (1 << 30)) return AWARE_E_BADARG;
+    FilterLaunch L;
+    L.in = in; L.out = out; L.B = B; L.off = off; L.len = len; L.max_len = max_len; L.response = response; L.c1 = c1; L.c2 = c2;
+    L.taps = taps;
+    launch_band_filter(L, (hipStream_t)stream);
+    LAUNCHCHK();
+    return AWARE_OK;
+}
+
 // ---- the gain envelope alone (EXTENSION; attacks.GainEnvelope, runtime.gain_envelope, tests) ----------------------------------
 extern "C" int aware_gain_envelope(const float* in, const int* off, const int* len, int B, int max_len, const uint32_t* seeds,
                                    int step, int entry, int p_lo, int p_hi, float floor, float* out, float* gains, void* stream) {
@@ -2275,6 +2288,11 @@ static DeleteLaunch delete_launch(const aware_embed* e, const LoopChainState& la
     S.k_lo = la.lo; S.k_hi = la.hi; S.at = la.at;
     return S;
 }
+static FilterLaunch filter_launch(const aware_embed* e, const LoopChainState& la, const float* in, float* out, int step_back) {
+    FilterLaunch S = stage_launch<FilterLaunch>(e, la, in, out, 0, step_back);
+    S.mask = la.mask; S.c_lo = la.lo; S.c_hi = la.hi; S.w_min = la.w_min;
+    return S;
+}
 // the time stretch and the pitch shift: the window and one range of offsets
 template <typename Launch>
 static Launch ola_launch(const aware_embed* e, const LoopChainState& la, const float* in, float* out, int adjoint, int step_back) {
@@ -2385,6 +2403,7 @@ static void split_forward(const aware_embed* e, const LoopChainState& la, hipStr
         case AWARE_LOOP_PITCH_SHIFT: launch_pitch_shift(ola_launch<PitchLaunch>(e, la, la.u, la.z, 0, 0), st); break;
         // gy is free until the synthesis adjoint writes it, and carries the vocoded signal to the resampling
         case AWARE_LOOP_PHASE_VOCODER: pv_stage_forward(e, la, e->gy, st); break;
+        case AWARE_LOOP_BAND_FILTER: launch_band_filter(filter_launch(e, la, la.u, la.z, 0), st); break;
         default: launch_delete_samples(delete_launch(e, la, la.u, la.z, 0, 0), st); break;      // AWARE_LOOP_DELETE_SAMPLES
     }
 }
@@ -2403,6 +2422,7 @@ static void split_backward(const aware_embed* e, const LoopChainState& la, int s
         }
         case AWARE_LOOP_PITCH_SHIFT: launch_pitch_shift(ola_launch<PitchLaunch>(e, la, la.u, e->gy, 1, step_back), st); break;
         case AWARE_LOOP_PHASE_VOCODER: pv_stage_backward(e, la, step_back, st); break;
+        case AWARE_LOOP_BAND_FILTER: launch_band_filter(filter_launch(e, la, la.u, e->gy, step_back), st); break;      // its own adjoint
         default: launch_delete_samples(delete_launch(e, la, la.u, e->gy, 1, step_back), st); break;
     }
 }

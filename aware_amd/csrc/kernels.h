@@ -562,6 +562,26 @@ struct GainLaunch {
 };
 void launch_gain_envelope(const GainLaunch& L, hipStream_t st);
 
+// ---- loop_filter_kernels.hip: band filter (EXTENSION): a zero-phase windowed-sinc FIR of 2 kFilterHalf + 1 taps, low-pass,
+// high-pass, band-pass or band-stop at edges in units of 1 / 65536 cycle per sample, inside the embed loop (chain kind 9) and
+// stand-alone (aware_band_filter).  Its own adjoint: the backward pass is the same launch on the gradient -------------------
+struct FilterLaunch {
+    const float* in = nullptr; float* out = nullptr;      // never the same buffer
+    int B = 0, adjoint = 0;               // adjoint is not read: h is symmetric and the extension is by zeros
+    // the embed loop (draw.frame_off set): the response and the edges drawn in the kernel
+    LoopDraw draw;
+    int mask = 0;                         // bits 1 lowpass, 2 highpass, 4 bandpass, 8 bandstop: the responses drawn from
+    int c_lo = 0, c_hi = 0, w_min = 0;    // 1 <= c_lo <= c_hi, 1 <= w_min, c_hi + w_min <= kFilterMaxEdge
+    // or a ragged batch (draw.frame_off null): both sides are len[b] floats at off[b]; response[b] (one bit), c1[b], c2[b] given
+    const int* off = nullptr; const int* len = nullptr;
+    int max_len = 0;                      // >= every length
+    const int* response = nullptr;        // [B]
+    const int* c1 = nullptr;              // [B]
+    const int* c2 = nullptr;              // [B] read by the band responses
+    float* taps = nullptr;                // null, or [B][256]: tap k at index k + kFilterHalf, zero at 255
+};
+void launch_band_filter(const FilterLaunch& L, hipStream_t st);
+
 // ---- sync_kernels.hip: offset search in detection (EXTENSION): values [B][n][L] -> the row of the largest mean |v - centre|
 // per clip (the smallest j on a tie), its index and that mean; one wave per clip ------------------------------------------
 void launch_sync_select(const float* values, int B, int n, int L, float centre, float* out_values, int* out_index,

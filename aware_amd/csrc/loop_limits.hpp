@@ -7,7 +7,8 @@ namespace aware {
 constexpr int kMaxLoopChains = 8;
 constexpr int kMaxLoopAttacks = 4;
 constexpr int kLoopGaussianNoise = 0, kLoopSampleSuppression = 1, kLoopReverberation = 2, kLoopSpeedChange = 3, kLoopTimeStretch = 4,
-              kLoopPitchShift = 5, kLoopPhaseVocoder = 6, kLoopDeleteSamples = 7, kLoopGainEnvelope = 8;      // AWARE_LOOP_* of aware_hip.h
+              kLoopPitchShift = 5, kLoopPhaseVocoder = 6, kLoopDeleteSamples = 7, kLoopGainEnvelope = 8,
+              kLoopBandFilter = 9;      // AWARE_LOOP_* of aware_hip.h
 
 // reverberation (loop_reverb_kernels.hip)
 constexpr int kReverbMaxIr = 8192;        // taps
@@ -22,6 +23,9 @@ constexpr int kStretchMin = -16384, kStretchMax = 21845;  // stretch offsets: ce
 
 // gain envelope (loop_attack_kernels.hip, loop_gain_kernels.hip): samples between two breakpoints
 constexpr int kEnvelopeMinPeriod = 64, kEnvelopeMaxPeriod = 1 << 20;
+
+// band filter (loop_filter_kernels.hip): taps on either side of the centre; edges in units of 1 / 65536 cycle per sample
+constexpr int kFilterHalf = 127, kFilterMaxEdge = 32767;
 
 // Attack mixtures: with `choice` set, a workgroup whose clip did not draw chain `chain` at this step returns at once
 struct LoopGate {

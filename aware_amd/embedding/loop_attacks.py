@@ -91,6 +91,21 @@ the loop's new stage.  For clip b (length Ny) at optimiser step s with seed_b:
         stand in front of or behind a splitting entry and in every chain of a mixture, and a noise entry behind it takes its
         sigma from the enveloped signal.  Host and device agree on g to 1e-6 (the division and the fused multiply-add).
 
+      band_filter(response = "lowpass" | "highpass" | "bandpass" | "bandstop" or a list of them, freq = f or [lo, hi] in Hz,
+        min_width = 400.0 Hz): a frequency-selective channel (a telephone line, a small speaker, a notch), a zero-phase
+        windowed-sinc FIR of 255 taps.  Frequencies travel as integers c = round(65536 f / sample_rate), in units of 1 / 65536
+        cycle per sample (Nyquist is 32768): c_lo, c_hi, w_min (filter_range).  mask = the sum of the responses' bits
+        (lowpass 1, highpass 2, bandpass 4, bandstop 8);  e1 = c_lo + ((r[1] * (c_hi - c_lo + 1)) >> 32), e2 the same from r[2];
+        response = the ((r[3] * popcount(mask)) >> 32)-th set bit of mask, counted from the lowest;  lowpass and highpass:
+        c1 = e1;  band responses: c1 = min(e1, e2), c2 = max(e1, e2), and c2 = c1 + w_min if c2 - c1 < w_min (filter_draw).
+        Taps, k = -127..127 (filter_taps): w[k] = 0.54 + 0.46 cos(pi k / 127), lp_c[0] = c / 32768,
+        lp_c[k] = w[k] sin(2 pi ((c |k|) mod 65536) / 65536) / (pi |k|) (the phase reduced in integers), delta the unit impulse;
+        h = lp_c1, delta - lp_c1, lp_c2 - lp_c1, delta - (lp_c2 - lp_c1).  on: z[i] = sum_k h[k] x[i - k], x zero outside the
+        clip (band_filter): the clip keeps its length and there is no delay.  h is symmetric and the extension is by zeros, so
+        the operator is its own adjoint.  At most one per chain, and not in a chain with any other splitting kind, in either
+        order; element-wise entries may stand in front of it (noise there is coloured noise) and behind it (noise there takes
+        its sigma from the filtered signal).  Host and device agree on h to 1e-6.
+
 In the loop x = N(N(y)) of the raw synthesis y, N(v) = v / (max|v| + 1e-8), and the analysis (N, N, STFT, band magnitudes)
 runs on the chain's output."""
 from __future__ import annotations
@@ -107,10 +122,13 @@ KINDS = {"gaussian_noise": 0, "sample_suppression": 1, "reverberation": 2, "spee
 # tests that iterate over KINDS pin KINDS to the eight kinds above, in their order, so later kinds have a table of their own;
 # kind_id() is the one lookup over both, for the parser and the device-entry builders.
 ELEMENTWISE_EX = {"gain_envelope": 8}
+# The splitting kinds added after that table was recorded, for the same reason in a table of their own.
+SPLITTING_EX = {"band_filter": 9}
 _KEYS = {"gaussian_noise": {"kind", "snr_db", "prob"}, "sample_suppression": {"kind", "seconds", "prob"},
          "reverberation": {"kind", "rt60", "drr_db", "prob"}, "speed_change": {"kind", "cents", "prob"}, "time_stretch": {"kind", "rate", "prob"},
          "pitch_shift": {"kind", "cents", "prob"}, "phase_vocoder": {"kind", "rate", "cents", "prob"},
-         "delete_samples": {"kind", "seconds", "at", "prob"}, "gain_envelope": {"kind", "period", "floor", "prob"}}
+         "delete_samples": {"kind", "seconds", "at", "prob"}, "gain_envelope": {"kind", "period", "floor", "prob"},
+         "band_filter": {"kind", "response", "freq", "min_width", "prob"}}
 _KEY1 = 0x5EED
 MAX_IR = 8192                   # taps of the longest impulse response
 _IR_WORD = 8                    # third Philox counter word of the impulse responses (0: noise, 1..4: entry draws)
@@ -120,26 +138,30 @@ STRETCH_HOP, STRETCH_WIN = 256, 1024            # the overlap-add's hop and wind
 DELETE_AT = {"start": 0, "anywhere": 1}         # where a sample deletion cuts: param[2] of the C ABI's entry
 MIN_PERIOD, MAX_PERIOD = 64, 1 << 20            # samples between two breakpoints of a gain envelope
 _ENV_WORD = 16                  # third Philox counter word of entry j's breakpoints is 16 + j
+RESPONSES = {"lowpass": 1, "highpass": 2, "bandpass": 4, "bandstop": 8}      # the bits of a band filter's mask: param[0]
+FILTER_HALF = 127               # taps on either side of a band filter's centre
+MAX_EDGE = 32767                # the highest edge, in units of 1 / 65536 cycle per sample: one below Nyquist
 
 
 def kind_id(kind) -> int | None:
     """The C ABI's number of a chain kind (AWARE_LOOP_* of include/aware_hip.h), None for an unknown one."""
     if not isinstance(kind, str):
         return None
-    return KINDS.get(kind, ELEMENTWISE_EX.get(kind))
+    return KINDS.get(kind, ELEMENTWISE_EX.get(kind, SPLITTING_EX.get(kind)))
 
 
 # The one-split rule (csrc/loop_chain.hpp holds the device's statement of it): these kinds need launches of their own between
 # two stages of element-wise entries, and a chain holds at most one entry of them.  The one exception is the pair: a speed
 # change directly behind a time stretch.
 SPLITTING = ("reverberation", "speed_change", "time_stretch", "pitch_shift", "phase_vocoder", "delete_samples")
-_NAME = dict({k: k.replace("_", " ") for k in SPLITTING}, delete_samples="sample deletion")
+_NAME = dict({k: k.replace("_", " ") for k in SPLITTING + tuple(SPLITTING_EX)}, delete_samples="sample deletion")
+_SPLIT_ORDER = SPLITTING + tuple(SPLITTING_EX)
 
 
 def _one_split(j: int, kind: str, out: list[dict]) -> None:
     """ValueError if entry j of a splitting kind may not join the entries `out` in front of it.  The message names the kind
     itself if the chain holds it already, otherwise the last splitting entry, the later of the two in SPLITTING first."""
-    held = [o["kind"] for o in out if o["kind"] in SPLITTING]
+    held = [o["kind"] for o in out if o["kind"] in _SPLIT_ORDER]
     if not held or (kind == "speed_change" and held == ["time_stretch"] and out[-1]["kind"] == "time_stretch"):
         return
     head = f"loop_attacks[{j}] ({kind}): "
@@ -148,7 +170,7 @@ def _one_split(j: int, kind: str, out: list[dict]) -> None:
     if {kind, held[-1]} == {"speed_change", "time_stretch"}:
         raise ValueError(head + ("beside a time stretch, the speed change follows it directly" if kind == "speed_change"
                                  else "a speed change in the same chain follows the stretch directly"))
-    first, second = sorted((kind, held[-1]), key=SPLITTING.index, reverse=True)
+    first, second = sorted((kind, held[-1]), key=_SPLIT_ORDER.index, reverse=True)
     raise ValueError(head + f"a chain holds a {_NAME[first]} or a {_NAME[second]}, not both")
 
 
@@ -207,6 +229,43 @@ def _parse_cents(j: int, kind: str, a: dict) -> list[float]:
     return [lo, hi]
 
 
+def _parse_filter(j: int, a: dict, sample_rate: int) -> dict:
+    """response (a list of names, in the order of their bits), freq [lo, hi] and min_width of a band_filter entry."""
+    head = f"loop_attacks[{j}] (band_filter): "
+    if "response" not in a:
+        raise ValueError(head + "response is required")
+    if "freq" not in a:
+        raise ValueError(head + "freq is required")
+    rs = a["response"]
+    names = [rs] if isinstance(rs, str) else list(rs) if isinstance(rs, (list, tuple)) else None
+    if not names or any(not isinstance(r, str) or r not in RESPONSES for r in names):
+        raise ValueError(head + f"response = {rs!r}; available: {list(RESPONSES)}, one or a list of them")
+    fq = a["freq"]
+    try:
+        if isinstance(fq, (list, tuple)):
+            if len(fq) != 2:
+                raise TypeError
+            lo, hi = float(fq[0]), float(fq[1])
+        else:
+            lo = hi = float(fq)
+        mw = float(a.get("min_width", 400.0))
+    except (TypeError, ValueError):
+        raise ValueError(head + f"freq = {fq!r} is neither a number nor [lo, hi], or min_width = {a.get('min_width')!r} is "
+                         f"not a number") from None
+    if not (math.isfinite(lo) and math.isfinite(hi) and math.isfinite(mw)):
+        raise ValueError(head + f"freq and min_width have to be finite; got {fq!r}, {a.get('min_width', 400.0)!r}")
+    if not mw > 0.0:
+        raise ValueError(head + f"min_width = {mw} has to be > 0")
+    if lo > hi:
+        raise ValueError(head + f"freq needs lo <= hi; got {fq!r}")
+    e = {"response": [r for r in RESPONSES if r in names], "freq": [lo, hi], "min_width": mw}
+    c_lo, c_hi, w_min = filter_range(e, sample_rate)
+    if not (lo > 0.0 and hi < 0.5 * sample_rate - mw and 1 <= c_lo <= c_hi and w_min >= 1 and c_hi + w_min <= MAX_EDGE):
+        raise ValueError(head + f"freq = {fq!r} Hz has an edge outside (0, Nyquist - min_width) = (0, "
+                         f"{0.5 * sample_rate - mw:g}) at {sample_rate} Hz")
+    return e
+
+
 def parse_chain(chain, sample_rate: int = 16000) -> list[dict]:
     """Validated copy of a chain such as [{"kind": "gaussian_noise", "snr_db": 10.0, "prob": 1.0},
     {"kind": "sample_suppression", "seconds": 0.3, "prob": 0.75}] (None / empty: no chain).  ValueError: unknown kind or key,
@@ -221,7 +280,10 @@ def parse_chain(chain, sample_rate: int = 16000) -> list[dict]:
     {"kind": "delete_samples", "seconds": 0.032 | [0.01, 0.2], "at": "start" | "anywhere"}: a missing seconds, seconds not
     0 < lo <= hi (finite), more or fewer than two values in a list, an unknown at; for {"kind": "gain_envelope",
     "period": 0.25 | [0.05, 0.5], "floor": 0.0}: a missing period, period not 0 < lo <= hi (finite), a period that is not
-    64 <= P_lo <= P_hi <= 2^20 samples at `sample_rate` (the one rule that reads it), floor not 0 <= floor < 1 (finite)."""
+    64 <= P_lo <= P_hi <= 2^20 samples at `sample_rate`, floor not 0 <= floor < 1 (finite); for {"kind": "band_filter",
+    "response": "lowpass" | ["lowpass", "bandstop"], "freq": 1000.0 | [600.0, 3800.0], "min_width": 400.0}: a missing freq or
+    response, an unknown response, a non-finite value, lo > hi, an edge outside (0, Nyquist - min_width) at `sample_rate`,
+    min_width <= 0 (the period and these edges are the rules that read `sample_rate`)."""
     if not chain:
         return []
     if isinstance(chain, dict) or not isinstance(chain, (list, tuple)):
@@ -232,7 +294,7 @@ def parse_chain(chain, sample_rate: int = 16000) -> list[dict]:
     for j, a in enumerate(chain):
         if not isinstance(a, dict) or kind_id(a.get("kind")) is None:
             raise ValueError(f"loop_attacks[{j}]: unknown kind {a.get('kind') if isinstance(a, dict) else a!r}; "
-                             f"available: {list(KINDS) + list(ELEMENTWISE_EX)}")
+                             f"available: {list(KINDS) + list(ELEMENTWISE_EX) + list(SPLITTING_EX)}")
         kind = a["kind"]
         extra = set(a) - _KEYS[kind]
         if extra:
@@ -241,7 +303,7 @@ def parse_chain(chain, sample_rate: int = 16000) -> list[dict]:
         if not 0.0 <= prob <= 1.0:
             raise ValueError(f"loop_attacks[{j}] ({kind}): prob = {prob} outside [0, 1]")
         e = {"kind": kind, "prob": prob}
-        if kind in SPLITTING:
+        if kind in _SPLIT_ORDER:
             _one_split(j, kind, out)
         if kind == "gaussian_noise":
             if "snr_db" not in a or not math.isfinite(float(a["snr_db"])):
@@ -295,6 +357,8 @@ def parse_chain(chain, sample_rate: int = 16000) -> list[dict]:
             if not isinstance(at, str) or at not in DELETE_AT:
                 raise ValueError(f"loop_attacks[{j}] (delete_samples): at = {at!r}; available: {list(DELETE_AT)}")
             e["at"] = at
+        elif kind == "band_filter":
+            e.update(_parse_filter(j, a, sample_rate))
         elif kind == "gain_envelope":
             if "period" not in a:
                 raise ValueError(f"loop_attacks[{j}] (gain_envelope): period is required")
@@ -370,6 +434,22 @@ def envelope_range(entry: dict, sample_rate: int) -> tuple[int, int]:
         raise ValueError(f"period = {entry['period']} s is {p_lo}..{p_hi} samples at {sample_rate} Hz, outside "
                          f"{MIN_PERIOD}..{MAX_PERIOD}")
     return p_lo, p_hi
+
+
+def filter_edge(f: float, sample_rate: int) -> int:
+    """c = round(65536 f / sample_rate): a frequency in units of 1 / 65536 cycle per sample."""
+    return int(round(65536.0 * float(f) / sample_rate))
+
+
+def filter_range(entry: dict, sample_rate: int) -> tuple[int, int, int]:
+    """(c_lo, c_hi, w_min) of a parsed band_filter entry: its edges' range and a band's least width, through filter_edge."""
+    return (filter_edge(entry["freq"][0], sample_rate), filter_edge(entry["freq"][1], sample_rate),
+            filter_edge(entry["min_width"], sample_rate))
+
+
+def filter_mask(entry: dict) -> int:
+    """The sum of the bits of a parsed band_filter entry's responses."""
+    return sum(RESPONSES[r] for r in entry["response"])
 
 
 def check_lengths(chain: list[dict], sample_rate: int, out_lengths) -> None:
@@ -709,6 +789,68 @@ def gain_envelope(x, seed, step: int, j: int, P: int, ph: int, floor: float):
     return x * torch.as_tensor(g).to(dtype=x.dtype, device=x.device)
 
 
+def filter_draw(entry: dict, r, sample_rate: int) -> tuple[int, int, int]:
+    """(response bit, c1, c2) of a parsed band_filter entry from its draw r = entry_draw(seed, step, j): the edges from r[1] and
+    r[2], the response from r[3]; c2 = c1 for lowpass and highpass."""
+    c_lo, c_hi, w_min = filter_range(entry, sample_rate)
+    e1 = c_lo + ((int(r[1]) * (c_hi - c_lo + 1)) >> 32)
+    e2 = c_lo + ((int(r[2]) * (c_hi - c_lo + 1)) >> 32)
+    bits = [RESPONSES[n] for n in entry["response"]]
+    response = bits[(int(r[3]) * len(bits)) >> 32]
+    if response < 4:
+        return response, e1, e1
+    c1, c2 = min(e1, e2), max(e1, e2)
+    return response, c1, max(c2, c1 + w_min)
+
+
+def _filter_lowpass(c: int, dtype) -> np.ndarray:
+    k = np.arange(-FILTER_HALF, FILTER_HALF + 1)
+    ak = np.abs(k)
+    if dtype == np.float32:
+        # the device's arithmetic: the window, the sine of the exact argument, one division
+        w = (np.float32(0.54) + np.float32(0.46) * np.cos(np.pi * (ak.astype(np.float32) * np.float32(1.0 / 127.0)).astype(np.float64)).astype(np.float32))
+        sn = np.sin(np.pi * ((c * ak) % 65536).astype(np.float64) / 32768.0).astype(np.float32)
+        den = (np.float32(np.pi) * np.maximum(ak, 1).astype(np.float32)).astype(np.float32)
+        lp = ((w * sn).astype(np.float32) / den).astype(np.float32)
+        lp[FILTER_HALF] = np.float32(c) / np.float32(32768.0)
+        return lp
+    w = 0.54 + 0.46 * np.cos(np.pi * k / FILTER_HALF)
+    lp = w * np.sin(2.0 * np.pi * ((c * ak) % 65536) / 65536.0) / (np.pi * np.maximum(ak, 1))
+    lp[FILTER_HALF] = c / 32768.0
+    return lp
+
+
+def filter_taps(response: int, c1: int, c2: int, dtype=np.float64) -> np.ndarray:
+    """The 255 taps h[k], k = -127..127 at index k + 127, of the response bit (1 lowpass, 2 highpass, 4 bandpass, 8 bandstop) at
+    the edges c1 (and c2 for the band responses), in float64 or float32."""
+    dtype = np.dtype(dtype).type
+    response, c1, c2 = int(response), int(c1), int(c2)
+    if response not in RESPONSES.values() or not (0 <= c1 <= MAX_EDGE and 0 <= c2 <= MAX_EDGE):
+        raise ValueError(f"filter_taps: response = {response} is not one of 1, 2, 4, 8, or an edge of ({c1}, {c2}) lies outside "
+                         f"0..{MAX_EDGE}")
+    delta = np.zeros(2 * FILTER_HALF + 1, dtype=dtype)
+    delta[FILTER_HALF] = 1
+    l1 = _filter_lowpass(c1, dtype)
+    if response == 1:
+        return l1
+    if response == 2:
+        return (delta - l1).astype(dtype)
+    band = (_filter_lowpass(c2, dtype) - l1).astype(dtype)
+    return band if response == 4 else (delta - band).astype(dtype)
+
+
+def band_filter(x, response, c1, c2):
+    """z[i] = sum_k h[k] x[i - k] with h = filter_taps(response, c1, c2) in float64, cast to x's dtype, and x zero outside
+    [0, n): x a tensor [..., n], or a list of 1-D tensors (ragged) with a response and edges each.  The clip keeps its length.
+    Differentiable in x; the operator is its own adjoint."""
+    if not torch.is_tensor(x):
+        return [band_filter(xb, rs, a, b) for xb, rs, a, b in zip(x, response, c1, c2)]
+    h = torch.as_tensor(filter_taps(response, c1, c2)).to(dtype=x.dtype, device=x.device)
+    n = x.shape[-1]
+    z = torch.nn.functional.conv1d(x.reshape(-1, 1, n), h.reshape(1, 1, -1), padding=FILTER_HALF)      # h is symmetric: correlation is convolution
+    return z.reshape(x.shape)
+
+
 def _convolve(xb: torch.Tensor, h: np.ndarray) -> torch.Tensor:
     """(h * xb)[0 : len(xb)] in xb's dtype through an FFT at least len(xb) + len(h) - 1 long; differentiable in xb."""
     ny, nh = xb.shape[-1], len(h)
@@ -761,6 +903,9 @@ def apply_chain(x, chain, seeds, step: int, sample_rate: int = 16000):
                 start, k = delete_draw(a, r, ny, sample_rate)
                 if on:
                     xb = delete_samples(xb, start, k)
+            elif a["kind"] == "band_filter":
+                if on:
+                    xb = band_filter(xb, *filter_draw(a, r, sample_rate))
             elif a["kind"] == "gain_envelope":
                 P, ph = envelope_draw(a, r, sample_rate)
                 if on:
@@ -778,12 +923,15 @@ def device_entries_ex(chain: list[dict], sample_rate: int):
     """(kind, prob, [param0..3]) of the C ABI's aware_loop_attack_ex: kinds 0 and 1 as device_entries in param[0]; a
     reverberation has param = [n_lo, n_hi, drr_db, 0], a speed change, a time stretch or a pitch shift [m_lo, m_hi, 0, 0], a
     phase vocoder [mq_lo, mq_hi, m_lo, m_hi] with [0, -1] (lo > hi) for an absent mode, a sample deletion
-    [k_lo, k_hi, at (0 start / 1 anywhere), 0], a gain envelope [P_lo, P_hi, floor, 0]."""
+    [k_lo, k_hi, at (0 start / 1 anywhere), 0], a gain envelope [P_lo, P_hi, floor, 0], a band filter [mask, c_lo, c_hi, w_min]."""
     out = []
     for a in chain:
         if a["kind"] == "gain_envelope":
             p_lo, p_hi = envelope_range(a, sample_rate)
             out.append((kind_id(a["kind"]), a["prob"], [float(p_lo), float(p_hi), a["floor"], 0.0]))
+        elif a["kind"] == "band_filter":
+            c_lo, c_hi, w_min = filter_range(a, sample_rate)
+            out.append((kind_id(a["kind"]), a["prob"], [float(filter_mask(a)), float(c_lo), float(c_hi), float(w_min)]))
         elif a["kind"] == "reverberation":
             n_lo, n_hi = reverb_taps(a, sample_rate)
             out.append((kind_id(a["kind"]), a["prob"], [float(n_lo), float(n_hi), a["drr_db"], 0.0]))

@@ -1043,6 +1043,31 @@ def gain_envelope(x: Ragged, seeds: Sequence[int], step: int, entry: int, period
     return (out, gains) if return_gains else out
 
 
+def band_filter(x: Ragged, response, c1, c2, return_taps: bool = False, out: Ragged | None = None):
+    """Per clip embedding.loop_attacks.band_filter (aware_band_filter): clip b through the zero-phase windowed-sinc FIR of 255
+    taps with the response bit response[b] (1 lowpass, 2 highpass, 4 bandpass, 8 bandstop) at the edges c1[b] and, for the band
+    responses, c2[b], in units of 1 / 65536 cycle per sample (B integers each, or one for all).  Every clip keeps its length,
+    zeros are read outside it, and the operator is its own adjoint.  out: a Ragged of x's lengths in float32 to write into, never
+    x itself.  With return_taps the result is (out, taps [B, 256] float32: tap k at index k + 127, zero at 255)."""
+    lib = load_library()
+    rs, a1, a2 = ([int(v)] * x.B if np.isscalar(v) else [int(u) for u in v] for v in (response, c1, c2))
+    if (len(rs) != x.B or len(a1) != x.B or len(a2) != x.B or any(r not in (1, 2, 4, 8) for r in rs)
+            or any(not 0 <= a <= 32767 for a in a1 + a2) or any(r >= 4 and a > b for r, a, b in zip(rs, a1, a2))):
+        raise ValueError(f"band_filter: {x.B} responses of 1, 2, 4, 8 with edges in 0..32767 (c1 <= c2 for a band) are required; "
+                         f"got response = {rs}, c1 = {a1}, c2 = {a2}")
+    xin = x.data if x.data.dtype == torch.float32 else x.data.float()
+    if out is None:
+        out = Ragged(torch.empty(sum(x.lengths), dtype=torch.float32, device=xin.device), x.lengths)
+    elif list(out.lengths) != list(x.lengths) or out.data.dtype != torch.float32 or out.data.data_ptr() == xin.data_ptr():
+        raise ValueError("band_filter: out needs x's lengths in float32 and a buffer of its own")
+    taps = torch.zeros((x.B, 256), dtype=torch.float32, device=xin.device) if return_taps else None
+    dev = lambda v: torch.tensor(v, dtype=torch.int32, device=xin.device)
+    rd, d1, d2 = dev(rs), dev(a1), dev(a2)
+    check(lib.aware_band_filter(_ptr(xin), _ptr(x.d_off), _ptr(x.d_len), x.B, x.max_len, _ptr(rd), _ptr(d1), _ptr(d2),
+                                _ptr(out.data), _ptr(taps) if return_taps else None, _stream()), "aware_band_filter")
+    return (out, taps) if return_taps else out
+
+
 def sync_select(values: torch.Tensor, n: int, centre: float = 0.0):
     """detection.sync.sync_select on the device (aware_sync_select): values [B * n, L] float32, clip-major, the n candidate
     views of each of the B clips -> (values [B, L] of the view with the largest mean |v - centre| per clip, the smallest j on

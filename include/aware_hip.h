@@ -723,6 +723,40 @@ int aware_delete_samples(const float* in, const int* off, const int* len, int B,
 int aware_gain_envelope(const float* in, const int* off, const int* len, int B, int max_len, const uint32_t* seeds, int step,
                         int entry, int p_lo, int p_hi, float floor, float* out, float* gains, void* stream);
 
+/* ---- band filter inside the loop and alone (EXTENSION, parity unpinned: the reference's LowPassFilter, HighPassFilter and
+ * RandomBandstop are post-hoc IIR attacks) ------------------------------------------------------------------------------------
+ * The _ex pair and the mixture's setter also accept (the older entry point keeps refusing every kind above 1)
+ *   AWARE_LOOP_BAND_FILTER, param = { mask, c_lo, c_hi, w_min }: a frequency-selective channel, a zero-phase windowed-sinc FIR
+ *     of 255 taps.  Frequencies are integers c = round(65536 * f / sample_rate), in units of 1 / 65536 cycle per sample
+ *     (Nyquist is 32768; the host converts Hz).  mask: bit 1 lowpass, 2 highpass, 4 bandpass, 8 bandstop, the responses drawn
+ *     from.  With r the entry's draw as above,
+ *     e1 = c_lo + ((r[1] * (c_hi - c_lo + 1)) >> 32), e2 the same from r[2],
+ *     response = the ((r[3] * popcount(mask)) >> 32)-th set bit of mask, counted from the lowest;
+ *     lowpass and highpass: c1 = e1;  band responses: c1 = min(e1, e2), c2 = max(e1, e2), and c2 = c1 + w_min if c2 - c1 < w_min;
+ *     w[k] = 0.54 + 0.46 * cos(pi * k / 127), lp_c[0] = c / 32768,
+ *     lp_c[k] = w[k] * sin(2 * pi * ((c * |k|) mod 65536) / 65536) / (pi * |k|), k = -127..127, delta the unit impulse at 0;
+ *     h = lp_c1 (lowpass), delta - lp_c1 (highpass), lp_c2 - lp_c1 (bandpass), delta - (lp_c2 - lp_c1) (bandstop);
+ *   on: z[i] = sum_k h[k] * x[i - k], 0 <= i < Ny_b, x zero outside the clip.  The clip keeps its length and there is no delay.
+ *   h is symmetric and the extension is by zeros, so the backward pass is the same operator on the gradient with the same
+ *   draw.  The kind SPLITS a chain as kinds 2 to 7 do: at most one per chain, none of them beside it, element-wise entries on
+ *   either side (noise in front of it is coloured noise; noise behind it takes its sigma from the filtered signal); a clip on
+ *   which no entry of such a chain fires at a step leaves the bits of the loop without a chain.  The device builds the taps in
+ *   f32 with the sine's argument inside one turn: they are within 1e-6 of the formula above.
+ * AWARE_E_BADARG of the _ex setter, besides those above: a value that is not an integer, mask outside 1..15, c_lo < 1,
+ * c_lo > c_hi, w_min < 1, c_hi + w_min > 32767, a second band filter, a band filter together with any of kinds 2 to 7 (in
+ * either order).  aware_embed_loop_attack_workspace_bytes_ex for a chain with the kind is that of the same chain with a sample
+ * deletion in its place: no private workspace.  aware_embed_buffer gains no index.  Added without a version step: callers
+ * detect the addition by symbol. */
+#define AWARE_LOOP_BAND_FILTER 9         /* param = mask, c_lo, c_hi, w_min (1 / 65536 cycle per sample; the host converts Hz) */
+/* The same operator alone, on a ragged batch, always on: clip b is len[b] floats at float offset off[b] of `in` and of `out`
+ * (dev int [B], any offsets, every length <= max_len <= 2^30); response dev int [B], each one of 1, 2, 4, 8 (the lowest set bit
+ * of the low four is read; none: a copy); c1, c2 dev int [B], read clamped to 0..32767, c2 by the band responses only.  in and
+ * out are distinct buffers.  taps: NULL, or dev float [B][256]: receives clip b's taps, tap k at index k + 127, zero at 255.
+ * The operator is its own adjoint.  One launch on `stream`.  AWARE_E_BADARG: a null argument (taps apart), in == out, B < 1 or
+ * > 65535, max_len < 1 or > 2^30 (checked before anything is launched). */
+int aware_band_filter(const float* in, const int* off, const int* len, int B, int max_len, const int* response, const int* c1,
+                      const int* c2, float* out, float* taps, void* stream);
+
 /* ---- attack mixtures (EXTENSION, parity unpinned: the reference has no attacks in its loop) -------------------------------
  * A handle holds one chain, and the kinds that split a chain refuse each other.  A mixture is a list of 1..8 chains, each a
  * valid chain of aware_embed_set_loop_attacks_ex with a weight; at optimiser step s clip b draws

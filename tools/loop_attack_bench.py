@@ -15,6 +15,9 @@ a mixture's iteration reads against the weighted mean and the sum of its chains.
 coefficients, the losses and the finished waveform, the record a change to the loop is compared against.
 `--envelope` adds the chains of ENVELOPE_VARIANTS, which hold the gain envelope, to (a); `--variants` may
 name them too.
+`--filter` adds the chains of FILTER_VARIANTS, which hold the band filter, in the same way.  `--fir` does
+none of the above: it times the FIR kernel alone (aware_band_filter) on the batch against aware_convolve fed the same 255 taps,
+from device events, 20 calls each after a warm-up (under rocprofv3 --kernel-trace --stats the two show per kernel).
 `--only-loop` runs a few steps of every variant and nothing else, for a per-kernel trace
 (rocprofv3 --kernel-trace --stats -- python tools/loop_attack_bench.py --only-loop)."""
 import argparse
@@ -59,6 +62,15 @@ ENVELOPE_VARIANTS = {
     "envelope_reverb_envelope": [{"kind": "gain_envelope", "period": [0.05, 0.5], "prob": 0.75},
                                  {"kind": "reverberation", "rt60": [0.1, 0.5], "drr_db": -3.0, "prob": 0.75},
                                  {"kind": "gain_envelope", "period": 0.25, "floor": 0.25}],
+}
+
+# The chains with a band filter (chain kind 9), in a table of their own for the same reason.
+FILTER_VARIANTS = {
+    "filter": [{"kind": "band_filter", "response": ["lowpass", "highpass", "bandpass", "bandstop"], "freq": [600.0, 3800.0], "prob": 0.75}],
+    "filter_noise": [{"kind": "band_filter", "response": ["lowpass", "highpass", "bandpass", "bandstop"], "freq": [600.0, 3800.0], "prob": 0.75},
+                     {"kind": "gaussian_noise", "snr_db": 10.0}],
+    "noise_filter": [{"kind": "gaussian_noise", "snr_db": 10.0},
+                     {"kind": "band_filter", "response": ["lowpass", "highpass", "bandpass", "bandstop"], "freq": [600.0, 3800.0], "prob": 0.75}],
 }
 
 
@@ -138,6 +150,28 @@ def sync_timing(det, audio, B, n, views):
     return out
 
 
+def fir_timing(audio, B, n):
+    """us per call of aware_band_filter (a band-pass of 1000 to 3000 Hz on every clip) and of aware_convolve fed its 255 taps."""
+    x = rt.Ragged(audio, [n] * B)
+    _, taps = rt.band_filter(x, 4, 4096, 12288, return_taps=True)
+    h = taps[:, :255].contiguous()
+    nh = torch.full((B,), 255, dtype=torch.int32, device="cuda")
+    out = {}
+    for name, fn in (("band_filter", lambda: rt.band_filter(x, 4, 4096, 12288)), ("convolve_255", lambda: rt.convolve(x, h, nh))):
+        for _ in range(3):
+            fn()
+        ts = []
+        for _ in range(20):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            ts.append(1e3 * a.elapsed_time(b))
+        out[name] = round(float(np.median(ts)), 1)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--clips", type=int, default=256)
@@ -152,6 +186,8 @@ def main():
     ap.add_argument("--mixture", default="")
     ap.add_argument("--dump", default="")
     ap.add_argument("--envelope", action="store_true")
+    ap.add_argument("--filter", action="store_true")
+    ap.add_argument("--fir", action="store_true")
     args = ap.parse_args()
     B, n = args.clips, int(args.seconds * 16000)
     emb, det = load()
@@ -163,6 +199,12 @@ def main():
     audio = 0.1 * torch.randn(B * n, generator=g, device="cuda")
     bits = torch.randint(0, 2, (B, 20), generator=g, device="cuda")
     target = bits.float() * 2 - 1
+    if args.fir:
+        t = fir_timing(audio, B, n)
+        print(f"FIR of 255 taps on {B} x {n} samples: aware_band_filter {t['band_filter']:.1f} us, aware_convolve {t['convolve_255']:.1f} us "
+              f"(host calls included)")
+        print(json.dumps({"clips": B, "seconds": args.seconds, "us_per_call": t}))
+        return
     batch = rt.Batch([n] * B)
     result = {"clips": B, "seconds": args.seconds, "steps": args.steps}
 
@@ -173,6 +215,7 @@ def main():
     chosen = {"none"} | {v for v in args.variants.split(",") if v}
     variants = {k: v for k, v in VARIANTS.items() if not args.variants or k in chosen}
     variants.update({k: v for k, v in ENVELOPE_VARIANTS.items() if k in chosen or (args.envelope and not args.variants)})
+    variants.update({k: v for k, v in FILTER_VARIANTS.items() if k in chosen or (args.filter and not args.variants)})
     mixtures = {}
     for m in [v for v in args.mixture.split(",") if v]:
         mixtures[f"mixture:{m}"] = MIXTURES[m]
