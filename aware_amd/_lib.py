@@ -112,6 +112,8 @@ SIGNATURES = {
     "aware_batch_out_offset": (_i, [_vp, _i]),
     "aware_batch_out_length": (_i, [_vp, _i]),
     "aware_batch_frames": (_i, [_vp, _i]),
+    "aware_batch_synth_run": (_i, [_vp]),
+    "aware_batch_analysis_run": (_i, [_vp]),
     "aware_batch_create_for_plan": (_i, [C.POINTER(_vp), _vp, _i, _pi, _pi]),
     "aware_batch_scratch_bytes": (_sz, [_vp]),
     "aware_stft": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp]),

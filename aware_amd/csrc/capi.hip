@@ -519,6 +519,8 @@ extern "C" void aware_batch_destroy(aware_batch* b) {
 extern "C" int aware_batch_total_frames(const aware_batch* b) { return b ? b->NF : AWARE_E_BADARG; }
 extern "C" int aware_batch_total_pooled(const aware_batch* b) { return b ? b->NP : AWARE_E_BADARG; }
 extern "C" int aware_batch_total_out(const aware_batch* b) { return b ? b->NS : AWARE_E_BADARG; }
+extern "C" int aware_batch_synth_run(const aware_batch* b) { return b ? b->synth_run : AWARE_E_BADARG; }
+extern "C" int aware_batch_analysis_run(const aware_batch* b) { return b ? b->an_run : AWARE_E_BADARG; }
 extern "C" int aware_batch_out_offset(const aware_batch* b, int i) {
     return (b && i >= 0 && i < b->B) ? b->out_off[i] : AWARE_E_BADARG;
 }
@@ -2372,7 +2374,11 @@ static LoopAttackLaunch chain_stage_launch(const aware_embed* e, const LoopChain
     for (int j = 0; j < la.n; ++j) { A.kind[j] = la.kind[j]; A.k[j] = la.k[j]; A.inv_snr[j] = la.inv_snr[j]; A.prob[j] = la.prob[j]; }
     for (int j = 0; j < la.n; ++j) { A.p_lo[j] = la.p_lo[j]; A.p_hi[j] = la.p_hi[j]; A.floor[j] = la.floor[j]; }
     A.yraw = e->yraw; A.pmaxY = e->pmaxY; A.psq = la.psq; A.z = la.z; A.pmaxZ = la.pmaxZ;
-    if (chain_splits(la)) { A.idle_plain = 1; A.gpad_out = la.gpad0; }
+    // the idle rule (chain_idle): every chain with a splitting entry, and every chain that holds a gain envelope.  Chains of
+    // noise and suppression alone keep the arithmetic of the loop before the rule existed, which recorded hashes pin.
+    bool envelope = false;
+    for (int j = 0; j < la.n; ++j) envelope = envelope || la.kind[j] == AWARE_LOOP_GAIN_ENVELOPE;
+    if (chain_splits(la) || envelope) { A.idle_plain = 1; A.gpad_out = la.gpad0; }
     // inside a mixture the pads are shared between the chains: a chain of kinds 0/1 has no idle rule, and writes the zeros
     // its clips' pads hold on a plain handle
     if (la.gate.choice) A.gpad_out = la.gpad0;

@@ -395,7 +395,7 @@ struct LoopAttackLaunch {
     const float* gpad = nullptr;          // reflect-pad parts of the streaming synthesis adjoint (null: already folded)
     const double* pdot_in = nullptr;
     double* pdot_out = nullptr;
-    // chains with a splitting entry (loop_chain.hpp: kinds 2 to 7): a clip on which no entry fires at a step leaves the plain loop's
+    // chains with a splitting entry (loop_chain.hpp) or a gain envelope: a clip on which no entry fires at a step leaves the plain loop's
     // bits (its maxima are recorded as 1, the backward stages pass gradient, partial sums and reflect pads through);
     // gpad_out: [B][2][512], the pads the analysis adjoint then reads (zeros for every other clip)
     int idle_plain = 0;

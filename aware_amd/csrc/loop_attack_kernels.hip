@@ -116,7 +116,7 @@ __device__ __forceinline__ ChainState chain_state(const ChainArgs& a, int b, int
     return cs;
 }
 
-// With idle_plain (the chains with a reverberation or a speed change): true when no entry of the whole chain fires for this clip at this step.
+// With idle_plain (the chains with a splitting entry or a gain envelope): true when no entry of the whole chain fires for this clip at this step.
 // Such a clip is to leave the plain loop's bits.  Forward: z = N(N(y)) as always, but its maxima are recorded as 1 -- what
 // max|N(N(y))| is to within an ulp -- so the analysis' two normalisers of z are exactly the identity and it sees the bits the
 // plain loop's analysis computes from y.  Backward: the stages hand the synthesis adjoint's gradient, its partial sums

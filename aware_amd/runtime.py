@@ -177,6 +177,10 @@ class Batch:
         self.frame_offsets = np.concatenate([[0], np.cumsum(self.frames)]).tolist()
         self.total_in = self.in_offsets[-1] + self.lengths[-1]
         self.scratch_bytes = self.lib.aware_batch_scratch_bytes(h)
+        # the run lengths the library chose for this batch (read-only): hop blocks per synthesis / loop-attack segment, frames
+        # per analysis run
+        self.synth_run = self.lib.aware_batch_synth_run(h)
+        self.analysis_run = self.lib.aware_batch_analysis_run(h)
         self.uniform = len(set(self.lengths)) == 1 and in_offsets is None
 
     def __del__(self):

@@ -122,6 +122,11 @@ int aware_batch_total_out(const aware_batch* batch);      /* sum 256*(T_b-1)  */
 int aware_batch_out_offset(const aware_batch* batch, int b); /* float offset of clip b's output */
 int aware_batch_out_length(const aware_batch* batch, int b);
 int aware_batch_frames(const aware_batch* batch, int b);
+/* read-only: the run lengths aware_batch_create chose for this batch -- hop blocks per workgroup segment of the synthesis
+ * side (and of every embed-loop attack kernel), 16 / 12 / 8 / 6 / 4, and frames per analysis run, 4..12 (a general batch,
+ * which has no streaming kernels, reports 16 and 0).  For tests and logs; nothing can set them. */
+int aware_batch_synth_run(const aware_batch* batch);
+int aware_batch_analysis_run(const aware_batch* batch);
 /* a batch for a plan: frames T_b = 1 + n_b/hop by the plan's hop, istft outputs hop*(T_b - 1) samples, clips need more than
  * n_fft/2 samples (AWARE_E_BADARG otherwise).  For the card plan the same as aware_batch_create.  A general batch also holds
  * the overlap-add frame buffer of the synthesis direction ([total frames][n_fft] floats, allocated here), so one general batch

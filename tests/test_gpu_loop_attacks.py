@@ -84,12 +84,17 @@ def attacked(sess, batch):
     return [z[o:o + n] for o, n in zip(batch.out_offsets, batch.out_lengths)]
 
 
-# ---- 4. forward ---------------------------------------------------------------------------------------------------------------
-def check_forward(LA, sess, batch, chain, seeds, step, tag):
-    torch.cuda.synchronize()
+def sampled(sess, batch, sample=None):
+    """(b, buffer 9, buffer 12) of every clip, or of the clips `sample` names only (a batch whose other clips are filler)."""
     ys, zs = synthesis(sess, batch), attacked(sess, batch)
+    return [(b, ys[b], zs[b]) for b in (range(batch.B) if sample is None else sample)]
+
+
+# ---- 4. forward ---------------------------------------------------------------------------------------------------------------
+def check_forward(LA, sess, batch, chain, seeds, step, tag, sample=None):
+    torch.cuda.synchronize()
     worst = 0.0
-    for b, (y, z) in enumerate(zip(ys, zs)):
+    for b, y, z in sampled(sess, batch, sample):
         ref = LA.apply_chain(norm2(y.double())[None], chain, [seeds[b]], step)[0]
         np.testing.assert_array_equal((z == 0).numpy(), (ref == 0).numpy())       # suppressed samples: exact zeros, same places
         worst = max(worst, float((z.double() - ref).abs().max()))

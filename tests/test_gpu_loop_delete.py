@@ -16,7 +16,7 @@ import torch
 import yaml
 
 from conftest import ROOT, make_clip
-from test_gpu_loop_attacks import attacked, norm2, session, synthesis
+from test_gpu_loop_attacks import attacked, norm2, sampled, session, synthesis
 from test_gpu_loop_reverb import CHAIN_BOUND
 from test_gpu_loop_stretch import PARENT_WORKSPACE, ex_entries
 from test_gpu_loop_pv import KINK, oracle_gradient
@@ -124,11 +124,11 @@ def test_delete_samples_is_numpy_bit_for_bit(rt):
 
 
 # ---- 2. forward inside the loop -----------------------------------------------------------------------------------------------
-def check_forward(LA, sess, batch, chain, seeds, step, tag):
+def check_forward(LA, sess, batch, chain, seeds, step, tag, sample=None):
     torch.cuda.synchronize()
     exact = chain[-1]["kind"] != "gaussian_noise"
     worst = 0.0
-    for b, (y, z) in enumerate(zip(synthesis(sess, batch), attacked(sess, batch))):
+    for b, y, z in sampled(sess, batch, sample):
         on, start, k = drawn(LA, chain, seeds[b], step, len(y))
         assert on and 1 <= k < len(y)
         if exact:

@@ -21,7 +21,7 @@ import torch
 import yaml
 
 from conftest import ROOT, make_clip
-from test_gpu_loop_attacks import attacked, norm2, session, synthesis
+from test_gpu_loop_attacks import attacked, norm2, sampled, session, synthesis
 from test_gpu_loop_reverb import CHAIN_BOUND
 from test_gpu_loop_stretch import PARENT_WORKSPACE, ex_entries
 from test_gpu_loop_pv import KINK, oracle_gradient
@@ -171,7 +171,7 @@ def test_nothing_is_written_past_the_clip(rt, n):
 
 
 # ---- 2. forward inside the loop -----------------------------------------------------------------------------------------------
-def check_forward(rt, LA, sess, batch, chain, seeds, step, tag):
+def check_forward(rt, LA, sess, batch, chain, seeds, step, tag, sample=None):
     """Filter alone or behind a suppression: against the restatement with the device's taps on x = N(N(buffer 9)) in the device's
     rounding, to the stand-alone bound 2^-16 sum|h| max|x|.  With a noise entry the device's noise is f32 and within the project's
     CHAIN_BOUND of the peak of the float64 one: in front of the filter that passes through it, at most sum|h| times as large;
@@ -179,7 +179,7 @@ def check_forward(rt, LA, sess, batch, chain, seeds, step, tag):
     torch.cuda.synchronize()
     noisy = any(a["kind"] == "gaussian_noise" for a in chain)
     worst = 0.0
-    for b, (y, z) in enumerate(zip(synthesis(sess, batch), attacked(sess, batch))):
+    for b, y, z in sampled(sess, batch, sample):
         on, rs, c1, c2 = drawn(LA, chain, seeds[b], step)
         assert on
         h = device_taps(rt, rs, c1, c2)

@@ -16,7 +16,7 @@ import torch
 import yaml
 
 from conftest import ROOT, make_clip
-from test_gpu_loop_attacks import attacked, attacked_oracle, norm2, session, synthesis
+from test_gpu_loop_attacks import attacked, attacked_oracle, norm2, sampled, session, synthesis
 from test_gpu_loop_reverb import CHAIN_BOUND
 from test_gpu_loop_stretch import PARENT_WORKSPACE, ex_entries
 
@@ -164,10 +164,10 @@ def test_pitch_shift_ola_per_clip_offsets_and_errors(rt, LA, alone):
 
 
 # ---- 2. forward inside the loop -----------------------------------------------------------------------------------------------
-def check_forward(LA, sess, batch, chain, seeds, step, tag):
+def check_forward(LA, sess, batch, chain, seeds, step, tag, sample=None):
     torch.cuda.synchronize()
     worst = 0.0
-    for b, (y, z) in enumerate(zip(synthesis(sess, batch), attacked(sess, batch))):
+    for b, y, z in sampled(sess, batch, sample):
         ref = LA.apply_chain(norm2(y.double())[None], chain, [seeds[b]], step)[0]
         worst = max(worst, float((z.double() - ref).abs().max() / ref.abs().max()))
     print(f"{tag}, step {step}: max |z - restatement| / peak = {worst:.2e}")

@@ -22,7 +22,7 @@ import torch
 import yaml
 
 from conftest import ROOT, make_clip
-from test_gpu_loop_attacks import attacked, norm2, session, synthesis
+from test_gpu_loop_attacks import attacked, norm2, sampled, session, synthesis
 from test_gpu_loop_reverb import CHAIN_BOUND
 from test_gpu_loop_stretch import PARENT_WORKSPACE, ex_entries
 
@@ -198,13 +198,13 @@ def test_pv_stretch_against_the_restatement(rt, LA, plan):
 
 
 # ---- 3. forward inside the loop -----------------------------------------------------------------------------------------------
-def check_forward(LA, sess, batch, chain, seeds, step, tag):
+def check_forward(LA, sess, batch, chain, seeds, step, tag, sample=None):
     """Per clip: the device within four times the float32 restatement's distance from the float64 one, and never asked for
     more than the project's bound for the loop's attacked signal (the two normalisers' rounding alone reaches it)."""
     torch.cuda.synchronize()
     worst = worst_floor = 0.0
     by_floor = by_chain_bound = 0
-    for b, (y, z) in enumerate(zip(synthesis(sess, batch), attacked(sess, batch))):
+    for b, y, z in sampled(sess, batch, sample):
         ref = LA.apply_chain(norm2(y.double())[None], chain, [seeds[b]], step)[0]
         r32 = LA.apply_chain(norm2(y.double()).float()[None], chain, [seeds[b]], step)[0]
         peak = float(ref.abs().max())

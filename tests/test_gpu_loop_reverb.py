@@ -15,7 +15,7 @@ import torch
 import yaml
 
 from conftest import ROOT, make_clip
-from test_gpu_loop_attacks import attacked, check_first_gradient, norm2, session, synthesis
+from test_gpu_loop_attacks import attacked, check_first_gradient, norm2, sampled, session, synthesis
 
 pytestmark = pytest.mark.gpu
 
@@ -165,14 +165,13 @@ def test_reverb_ir_against_the_restatement(rt, LA, n_lo, n_hi):
 
 
 # ---- 3. forward inside the loop -----------------------------------------------------------------------------------------------
-def check_forward(rt, LA, sess, batch, chain, seeds, step, tag):
+def check_forward(rt, LA, sess, batch, chain, seeds, step, tag, sample=None):
     torch.cuda.synchronize()
-    ys, zs = synthesis(sess, batch), attacked(sess, batch)
     j = [a["kind"] for a in chain].index("reverberation")
     entry = LA.parse_chain(chain)[j]
     hs = sess.impulse_responses.cpu().numpy()
     worst, worst_h = 0.0, [0.0, 0.0]
-    for b, (y, z) in enumerate(zip(ys, zs)):
+    for b, y, z in sampled(sess, batch, sample):
         r = LA.entry_draw(seeds[b], step, j)
         n_h = LA.reverb_length(r[2], *LA.reverb_taps(entry, 16000))
         if LA.fires(r[0], entry["prob"]):
