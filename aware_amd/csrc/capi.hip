@@ -2141,6 +2141,16 @@ extern "C" int aware_sync_select(const float* values, int B, int n, int L, float
     return AWARE_OK;
 }
 
+// ---- the speed search's views (EXTENSION; AWAREDetector.detect_batch(speed_search=...), runtime.speed_views, tests) ---------
+extern "C" int aware_speed_views(const float* in, const int* in_off, const int* in_len, int B, const int* m, int n_views,
+                                 float* out, const int* out_off, int max_len, void* stream) {
+    if (!in || !in_off || !in_len || !m || !out || !out_off || in == out) return AWARE_E_BADARG;
+    if (B < 1 || B > 65535 || n_views < 1 || n_views > 63 || max_len < 1 || max_len > (1 << 30)) return AWARE_E_BADARG;
+    launch_speed_views(in, in_off, in_len, B, m, n_views, out, out_off, max_len, (hipStream_t)stream);
+    LAUNCHCHK();
+    return AWARE_OK;
+}
+
 // ---- the time stretch alone (EXTENSION; attacks.OverlapAddStretch, tests) -----------------------------------------------------
 extern "C" int aware_stretch_ola(const float* in, const int* in_off, const int* in_len, float* out, const int* out_off,
                                  const int* out_len, int B, int max_len, const int* m, int adjoint, void* stream) {

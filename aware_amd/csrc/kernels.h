@@ -587,4 +587,10 @@ void launch_band_filter(const FilterLaunch& L, hipStream_t st);
 void launch_sync_select(const float* values, int B, int n, int L, float centre, float* out_values, int* out_index,
                         float* out_conf, hipStream_t st);
 
+// ---- speed_search_kernels.hip: speed search in detection (EXTENSION): every clip of a ragged batch resampled at n_views
+// speed offsets m[j] in one launch; view (b, j) is ((in_len[b] - 1) << 16) / (65536 + m[j]) + 1 floats at
+// out_off[b * n_views + j], bit for bit what launch_speed_change gives at that m and length ---------------------------------
+void launch_speed_views(const float* in, const int* in_off, const int* in_len, int B, const int* m, int n_views, float* out,
+                        const int* out_off, int max_len, hipStream_t st);
+
 }  // namespace aware

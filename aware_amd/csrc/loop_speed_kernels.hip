@@ -14,40 +14,18 @@
 // taps per output, the adjoint walks the at most ten inputs that can reach its four outputs, in ascending order: no atomics,
 // one fixed order.  m = 0 copies the clip: the identity is exact.  Inside the loop one workgroup works through one synthesis
 // run of a clip (the partition chain_kernel uses) with float4 stores, which the 256-float clip alignment allows; the
-// stand-alone entry takes any offset and length and stores scalars.
+// stand-alone entry takes any offset and length and stores scalars.  The weights and the tap are speed_interp.hpp's, shared
+// with the speed search's views (speed_search_kernels.hip).
 #include "common.hpp"
 #include "kernels.h"
 #include "loop_rng.hpp"
+#include "speed_interp.hpp"
 
 namespace aware {
 
 namespace {
 
 constexpr int kSpThreads = 256;
-
-struct SpeedWeights { float wm1, w0, w1, w2; };
-
-// explicit fused multiply-adds, so that every instantiation rounds the same way
-__device__ __forceinline__ SpeedWeights speed_weights(float f) {
-    SpeedWeights w;
-    w.wm1 = (fmaf(2.f - f, f, -1.f) * f) * 0.5f;              // ((-f + 2) f - 1) f / 2
-    w.w0 = fmaf(fmaf(3.f, f, -5.f), f * f, 2.f) * 0.5f;       // ((3 f - 5) f^2 + 2) / 2
-    w.w1 = (fmaf(fmaf(-3.f, f, 4.f), f, 1.f) * f) * 0.5f;     // ((-3 f + 4) f + 1) f / 2
-    w.w2 = ((f - 1.f) * (f * f)) * 0.5f;                      // (f - 1) f^2 / 2
-    return w;
-}
-
-__device__ __forceinline__ float speed_tap(const float* __restrict__ x, int n, long long R, int i) {
-    const long long p = (long long)i * R;
-    if (p > ((long long)(n - 1) << 16)) return 0.f;
-    const int i0 = (int)(p >> 16);                            // 0 <= i0 <= n - 1
-    const SpeedWeights w = speed_weights((float)(unsigned)(p & 0xFFFF) * (1.0f / 65536.0f));
-    const float a = i0 >= 1 ? x[i0 - 1] : 0.f;
-    const float b = x[i0];
-    const float c = i0 + 1 < n ? x[i0 + 1] : 0.f;
-    const float d = i0 + 2 < n ? x[i0 + 2] : 0.f;
-    return fmaf(w.w2, d, fmaf(w.w1, c, fmaf(w.w0, b, w.wm1 * a)));
-}
 
 // gx[j0 .. j0 + 3] from gy[0 .. n_out): x has n samples
 __device__ __forceinline__ void speed_adjoint4(const float* __restrict__ gy, int n_out, int n, long long R, int j0, float g[4]) {

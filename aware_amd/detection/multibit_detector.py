@@ -2,7 +2,8 @@
 
 Reference: src/AWARE/detection/multibit_detector.py:9-42 -- normalise, STFT, magnitude, zero the
 bins outside the embedding band, network forward.  Batched entry point: detect_batch.  EXTENSION: sync_search = n reads n views of every clip, 512 / n samples
-apart, and keeps the most confident one (detection/sync.py); off by default."""
+apart, and keeps the most confident one (detection/sync.py); off by default.  EXTENSION: speed_search reads every clip at
+candidate playback speeds as well (same module); off by default."""
 from __future__ import annotations
 
 import numpy as np
@@ -17,9 +18,10 @@ from . import sync
 class AWAREDetector(BaseDetector):
     def __init__(self, model, threshold: float = 0.0, frame_length: int = 1024, hop_length: int = 256,
                  window: str = "hann", win_length: int = 1024, pattern_mode: str = "bits2bipolar",
-                 embedding_bands=(500, 4000), sync_search: int = 0):
+                 embedding_bands=(500, 4000), sync_search: int = 0, speed_search=None):
         rt.require_card_geometry("AWAREDetector", frame_length, hop_length, win_length)
         self.sync_search = sync.check_sync_search(sync_search)
+        self.speed_search = sync.check_speed_search(speed_search)
         self.threshold = threshold
         self.device = torch.device("cuda")
         self.pattern_mode = pattern_mode
@@ -41,11 +43,27 @@ class AWAREDetector(BaseDetector):
         """What an undecided read-out value is: 0.5 behind a sigmoid, 0 otherwise."""
         return 0.5 if getattr(self.detection_net, "final_activation", "tanh") == "sigmoid" else 0.0
 
-    def detect_batch(self, clips, sample_rate: int, sync_search=None, return_sync: bool = False):
+    def detect_batch(self, clips, sample_rate: int, sync_search=None, return_sync: bool = False, speed_search=None,
+                     return_speed: bool = False):
         """list of 1-D float arrays (any lengths) -> device tensor [B, n_bits] of raw values.  sync_search (default: the
         detector's own, 0 = off): the number of views per clip of the offset search.  return_sync: (values, the chosen views'
-        offsets in samples [B] int32, their confidence mean |value - centre| [B] float32) instead."""
+        offsets in samples [B] int32, their confidence mean |value - centre| [B] float32) instead.  speed_search (default: the
+        detector's own, None = off): max_percent or {"max_percent", "step_percent"} of the speed search.  return_speed:
+        (values, offsets [B] int32, the chosen views' speed offsets m [B] int32 -- the clip was played at sync.speed_of(m) --
+        confidence [B] float32) instead."""
         n = self.sync_search if sync_search is None else sync.check_sync_search(sync_search)
+        speed = self.speed_search if speed_search is None else sync.check_speed_search(speed_search)
+        if speed is None:
+            out = self._detect_sync(clips, sample_rate, n, return_sync or return_speed)
+            if return_speed:
+                return out[0], out[1], torch.zeros(len(clips), dtype=torch.int32, device=out[0].device), out[2]
+            return out
+        vals, offsets, m, conf = self._detect_speed(clips, sample_rate, n, speed)
+        if return_speed:
+            return vals, offsets, m, conf
+        return (vals, offsets, conf) if return_sync else vals
+
+    def _detect_sync(self, clips, sample_rate: int, n: int, return_sync: bool):
         plan = self._plan(sample_rate)
         det = self.detection_net.device_weights(plan)
         if n == 0:
@@ -73,10 +91,52 @@ class AWAREDetector(BaseDetector):
         step = sync.SYNC_PERIOD // n
         return vals, torch.cat([o[1] for o in outs]) * step, torch.cat([o[2] for o in outs])
 
+    def _detect_speed(self, clips, sample_rate: int, n: int, speed: dict):
+        """(values, offsets, m, confidence) of the speed search `speed`, times the offset search where n > 0: every clip at
+        every speed offset in one aware_speed_views launch per chunk, one aware_detect over all the views (with n > 0 over the
+        n overlapping windows into each), then aware_sync_select over the sync views and once more over the speed views."""
+        ms = sync.speed_offsets(speed)
+        ns, nw = len(ms), max(n, 1)
+        lengths = [len(c) for c in clips]
+        vlen = sync.speed_views(lengths, speed, n)                # ValueError for a clip too short or too long, before any launch
+        if ns * nw > sync.SYNC_MAX_ROWS:
+            raise ValueError(f"speed_search with sync_search = {n}: {ns} x {nw} views per clip; at most {sync.SYNC_MAX_ROWS}")
+        plan = self._plan(sample_rate)
+        det = self.detection_net.device_weights(plan)
+        x = rt.Ragged.from_list([np.asarray(c, dtype=np.float32) for c in clips])
+        offs = sync.sync_offsets(n)
+        centre = self._centre()
+        md = torch.tensor(ms, dtype=torch.int32, device=x.data.device)
+        # chunks of whole clips: at most SYNC_MAX_ROWS rows per aware_detect call and 2^30 view samples per buffer
+        padded = [sum((v + 3) // 4 * 4 for v in vlen[b * ns:(b + 1) * ns]) for b in range(len(clips))]
+        chunks, b0, size = [], 0, 0
+        for b in range(len(clips)):
+            if b > b0 and ((b - b0 + 1) * ns * nw > sync.SYNC_MAX_ROWS or size + padded[b] > sync.SPEED_MAX_SAMPLES):
+                chunks.append((b0, b))
+                b0, size = b, 0
+            size += padded[b]
+        chunks.append((b0, len(clips)))
+        outs = []
+        for b0, b1 in chunks:
+            sub = x if (b0, b1) == (0, x.B) else rt.Ragged(x.data[x.offsets[b0]:x.offsets[b1 - 1] + x.lengths[b1 - 1]], x.lengths[b0:b1])
+            flat, sl, so = rt.speed_views(sub, ms)
+            rows = rt.Batch([v - e for v in sl for e in offs], [o + e for o in so for e in offs])
+            vals = rt.detect(plan, det, rows, flat)               # [(b1 - b0) * ns * nw, n_bits]
+            if n:
+                vals, isync, _ = rt.sync_select(vals, n, centre)  # round one: the sync views of every (clip, speed view)
+            best, ispeed, conf = rt.sync_select(vals, ns, centre)             # round two: the speed views of every clip
+            if n:
+                chosen = isync.view(b1 - b0, ns).gather(1, ispeed.long()[:, None])[:, 0] * (sync.SYNC_PERIOD // n)
+            else:
+                chosen = torch.zeros(b1 - b0, dtype=torch.int32, device=best.device)
+            outs.append((best, chosen.to(torch.int32), md[ispeed.long()], conf))
+        return tuple(torch.cat([o[i] for o in outs]) for i in range(4))
+
     def detect_device(self, audio: torch.Tensor, batch: "rt.Batch", sample_rate: int) -> torch.Tensor:
         plan = self._plan(sample_rate)
         return rt.detect(plan, self.detection_net.device_weights(plan), batch, audio)
 
-    def detect(self, audio: np.ndarray, sample_rate: int, sync_search=None) -> np.ndarray:
-        vals = self.detect_batch([np.asarray(audio, dtype=np.float32)], sample_rate, sync_search=sync_search)
+    def detect(self, audio: np.ndarray, sample_rate: int, sync_search=None, speed_search=None) -> np.ndarray:
+        vals = self.detect_batch([np.asarray(audio, dtype=np.float32)], sample_rate, sync_search=sync_search,
+                                 speed_search=speed_search)
         return vals[0].detach().cpu().numpy()

@@ -8,14 +8,31 @@ device kernel (csrc/sync_kernels.hip, aware_sync_select) is tested against:
 
     c_j = mean_l |v[b][j][l] - centre| in float32,  j* = the smallest j with the largest c_j,  out[b] = v[b][j*]
 
-centre is 0.5 for a sigmoid read-out and 0 otherwise."""
+centre is 0.5 for a sigmoid read-out and 0 otherwise.
+
+Speed search (EXTENSION as well).  A clip that was played at another speed (resampled: pitch and tempo
+move together) loses its bits, and reads them again once it is played back at the inverse speed.  With speed_search on, the
+detector reads every clip at 2 K + 1 candidate speeds and keeps the most confident view, by the same rule:
+
+    delta = floor(65536 step_percent / 100 + 0.5),  K = floor(max_percent / step_percent + 1e-9),
+    m_0 = 0,  m_{2i-1} = -i delta,  m_{2i} = +i delta,  i = 1 .. K          (ordered by |m|: a tie prefers the plain read)
+    view j of a clip of n samples = loop_attacks.speed_change(x, m_j, speed_length(n, m_j))
+
+the existing operator (Catmull-Rom at the 16.16 positions i (65536 + m_j)) at the length that keeps every position inside the
+clip.  The device writes all views in one launch (csrc/speed_search_kernels.hip, aware_speed_views).  With the offset search on
+as well, every speed view is read at the n sync offsets, and `speed_select` states the selection over all of them."""
 from __future__ import annotations
+
+import math
 
 import numpy as np
 
 SYNC_PERIOD = 512                       # hop 256 times the (2, 2) initial pool
 SYNC_CHOICES = (2, 4, 8, 16, 32, 64)
 SYNC_MAX_ROWS = 4096                    # views per aware_detect call: larger searches are chunked on the host
+SPEED_MAX_VIEWS = 63                    # speed views per clip: the second round of aware_sync_select takes n <= 64
+SPEED_MAX_SAMPLES = 1 << 30             # samples of the views of one aware_speed_views call
+SPEED_STEP_DEFAULT = 0.5                # percent: the confidence peak is about +-0.35 % wide at half height
 
 
 def check_sync_search(n) -> int:
@@ -70,3 +87,79 @@ def sync_select(values, n: int, centre: float = 0.0):
         dev = values.device
         return torch.as_tensor(out, device=dev), torch.as_tensor(idx, device=dev), torch.as_tensor(best, device=dev)
     return out, idx, best
+
+
+# ---- speed search -------------------------------------------------------------------------------------------------------------------
+def check_speed_search(search):
+    """None for off (None, 0, False or {}), {"max_percent", "step_percent"} in floats otherwise.  A number is max_percent with
+    step_percent = 0.5.  ValueError for anything else: values that are not finite numbers, 0.05 <= step_percent <= 2 and
+    step_percent <= max_percent <= 20 violated, an unknown key, more than 63 views."""
+    def number(v, what):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(float(v)):
+            raise ValueError(f"speed_search: {what} = {v!r}: a finite number is expected")
+        return float(v)
+
+    if search is None or search is False:
+        return None
+    if isinstance(search, dict):
+        if not search:
+            return None
+        unknown = sorted(set(search) - {"max_percent", "step_percent"})
+        if unknown or "max_percent" not in search:
+            raise ValueError(f"speed_search = {search!r}: the keys are max_percent and, optionally, step_percent")
+        mx = number(search["max_percent"], "max_percent")
+        step = number(search.get("step_percent", SPEED_STEP_DEFAULT), "step_percent")
+    else:
+        mx, step = number(search, "max_percent"), SPEED_STEP_DEFAULT
+        if mx == 0.0:
+            return None
+    if not 0.05 <= step <= 2.0:
+        raise ValueError(f"speed_search: step_percent = {step}: 0.05 <= step_percent <= 2 is expected")
+    if not step <= mx <= 20.0:
+        raise ValueError(f"speed_search: max_percent = {mx}: step_percent = {step} <= max_percent <= 20 is expected")
+    views = 2 * int(math.floor(mx / step + 1e-9)) + 1
+    if views > SPEED_MAX_VIEWS:
+        raise ValueError(f"speed_search: max_percent = {mx} at step_percent = {step} is {views} views; at most {SPEED_MAX_VIEWS}")
+    return {"max_percent": mx, "step_percent": step}
+
+
+def speed_offsets(search) -> list[int]:
+    """The speed offsets m_j of the views, ordered by |m|: [0, -delta, +delta, -2 delta, ...]; [0] where the search is off."""
+    s = check_speed_search(search)
+    if s is None:
+        return [0]
+    delta = int(math.floor(65536.0 * s["step_percent"] / 100.0 + 0.5))
+    k = int(math.floor(s["max_percent"] / s["step_percent"] + 1e-9))
+    return [0] + [sign * i * delta for i in range(1, k + 1) for sign in (-1, 1)]
+
+
+def speed_of(m: int) -> float:
+    """The speed a received clip was played at, if the view at the offset m restores it: 65536 / (65536 + m)."""
+    return 65536.0 / (65536.0 + int(m))
+
+
+def speed_views(lengths, search, sync_n: int = 0) -> list[int]:
+    """The view lengths speed_length(n_b, m_j), clip-major, of clips `lengths` long.  ValueError, naming the clip, where a
+    clip's shortest view, less the largest offset of the offset search sync_n, would have 512 samples or fewer (the STFT's
+    reflect padding needs more), or where the views of one clip, each padded to a multiple of four samples, exceed 2^30."""
+    from ..embedding.loop_attacks import speed_length
+    ms = speed_offsets(search)
+    drop = sync_offsets(sync_n)[-1]
+    out = []
+    for b, nb in enumerate(lengths):
+        v = [speed_length(int(nb), m) for m in ms] if int(nb) >= 1 else [0] * len(ms)
+        if min(v) - drop <= SYNC_PERIOD:
+            raise ValueError(f"speed_search: clip {b} has {int(nb)} samples; its shortest view ({min(v)}"
+                             + (f", less {drop} for sync_search = {sync_n}" if drop else "") + f") needs more than {SYNC_PERIOD}")
+        if sum((n + 3) // 4 * 4 for n in v) > SPEED_MAX_SAMPLES:
+            raise ValueError(f"speed_search: the {len(ms)} views of clip {b} ({int(nb)} samples) exceed 2^30 samples")
+        out += v
+    return out
+
+
+def speed_select(values, n_speed: int, n_sync: int = 0, centre: float = 0.0):
+    """values [B * n_speed * max(n_sync, 1), L], clip-major, then the speed view, then the sync view -> (out [B, L] float32:
+    per clip the row with the largest mean_l |v - centre| in float32, the smallest flat index on a tie; that flat index
+    idx_speed * n_sync + idx_sync [B] int32; that mean [B] float32).  It equals two rounds of sync_select, over the sync views
+    of every (clip, speed view) and then over the speed views, which is how the device selects."""
+    return sync_select(values, int(n_speed) * max(int(n_sync), 1), centre)

@@ -1089,6 +1089,37 @@ def sync_select(values: torch.Tensor, n: int, centre: float = 0.0):
     return out, idx, conf
 
 
+def speed_views(x: Ragged, ms, out: torch.Tensor | None = None):
+    """The views of detection.sync's speed search (aware_speed_views): every clip of x at every speed offset of ms, in one
+    launch -> (flat float32 device tensor, view lengths, view offsets into it), both clip-major lists of x.B * len(ms); view
+    (b, j) is loop_attacks.speed_length(x.lengths[b], ms[j]) samples, bit for bit speed_change(x, ms[j]) at that length.  The
+    offsets are multiples of four floats; the up to three floats between two rows are not written.  out: a float32 device
+    tensor of at least the views' size to write into."""
+    from .embedding.loop_attacks import speed_length
+    lib = load_library()
+    ms = [int(v) for v in ms]
+    if not 1 <= len(ms) <= 63 or any(v < -13520 or v > 17034 for v in ms):
+        raise ValueError(f"speed_views: 1 to 63 speed offsets within -13520..17034 (-+400 cents) are required; got {ms}")
+    if min(x.lengths) < 1:
+        raise ValueError(f"speed_views: every clip needs a sample; got {x.lengths}")
+    vlen = [speed_length(n, m) for n in x.lengths for m in ms]
+    voff = np.concatenate([[0], np.cumsum([(n + 3) // 4 * 4 for n in vlen])]).astype(np.int64)
+    if int(voff[-1]) > 1 << 30:
+        raise ValueError(f"speed_views: the views hold {int(voff[-1])} samples; at most 2^30 per call")
+    xin = x.data if x.data.dtype == torch.float32 else x.data.float()
+    if out is None:
+        flat = torch.empty(int(voff[-1]), dtype=torch.float32, device=xin.device)
+    elif out.dtype != torch.float32 or out.dim() != 1 or out.numel() < int(voff[-1]) or not out.is_contiguous() or out.device != xin.device:
+        raise ValueError(f"speed_views: out needs {int(voff[-1])} contiguous float32 values on x's device")
+    else:
+        flat = out
+    md = torch.tensor(ms, dtype=torch.int32, device=xin.device)
+    od = torch.tensor(voff[:-1], dtype=torch.int32, device=xin.device)
+    check(lib.aware_speed_views(_ptr(xin), _ptr(x.d_off), _ptr(x.d_len), x.B, _ptr(md), len(ms), _ptr(flat), _ptr(od),
+                                max(vlen), _stream()), "aware_speed_views")
+    return flat, vlen, voff[:-1].tolist()
+
+
 def stretch_ola(x: Ragged, m, adjoint: bool = False, out_lengths=None) -> Ragged:
     """Per clip embedding.loop_attacks.time_stretch at the offsets m (B integers, or one for all): clip b stretched in time at
     the rate (65536 + m[b]) / 65536 by plain overlap-add (aware_stretch_ola), out_lengths[b] samples long (default: the clip's

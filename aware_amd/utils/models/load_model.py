@@ -24,7 +24,9 @@ _EMBEDDER = {"pattern_mode": ("pattern_mode", "bits2bipolar"), "tolerance_db": (
              "loop_attack_mixture": ("loop_attack_mixture", None)}
 _DETECTOR = {"threshold": ("threshold", 0.0), "pattern_mode": ("pattern_mode", "bipolar"),
              # EXTENSION (detection/sync.py): offset search in detection; absent = off
-             "sync_search": ("sync_search", 0)}
+             "sync_search": ("sync_search", 0),
+             # EXTENSION (detection/sync.py): speed search in detection; absent = off
+             "speed_search": ("speed_search", None)}
 
 
 def _pick(card: dict, table: dict) -> dict:

@@ -803,6 +803,21 @@ int aware_loop_mixture_draw(const uint32_t* seeds, int B, int step, const float*
 int aware_sync_select(const float* values, int B, int n, int L, float centre, float* out_values, int* out_index,
                       float* out_conf, void* stream);
 
+/* ---- speed search in detection (EXTENSION, parity unpinned: the reference detects a clip as it is) -------------------------
+ * A clip that was played at another speed (resampled: pitch and tempo move together) reads its bits again once it is played
+ * back at the inverse speed.  The host detects n_views resampled views of each clip, m[0] = 0 first (one aware_detect on a
+ * batch of B * n_views rows, times the views of the offset search where that is on), and keeps the best view per clip with
+ * aware_sync_select.  This entry writes the views, all in one launch on `stream`:
+ *   clip b is in_len[b] floats at float offset in_off[b] of `in` (dev int [B], any offsets); m dev int [n_views];
+ *   view (b, j): R = 65536 + m[j], n_out = ((in_len[b] - 1) << 16) / R + 1 floats at out + out_off[b * n_views + j]
+ *   (dev int [B * n_views], from the host: rows that start at multiples of 4 floats are stored 16 bytes at a time), equal
+ *   bit for bit to aware_speed_change at m[j] with out_len = n_out; m[j] = 0 copies the clip.  max_len >= every n_out.
+ *   Floats of `out` outside the rows are not written.  A view whose m[j] lies outside -13520..17034 is not written.
+ * AWARE_E_BADARG, before anything is launched: a null pointer, in == out, B outside 1..65535, n_views outside 1..63,
+ * max_len outside 1..2^30.  Added without a version step: callers detect the addition by symbol. */
+int aware_speed_views(const float* in, const int* in_off, const int* in_len, int B, const int* m, int n_views, float* out,
+                      const int* out_off, int max_len, void* stream);
+
 /* ---- bare GEMM (tests / roofline): C[M][N] = A[M][K] * Bt[N][K]^T + bias ------------------------------ */
 int aware_gemm_nt(const float* A, int lda, const float* Bt, int ldb, const float* bias, float* C, int ldc,
                   int M, int N, int K, void* stream);
