@@ -64,7 +64,7 @@ class EmbedConfig(C.Structure):
     _fields_ = [("num_iterations", C.c_int), ("tolerance_db", C.c_float), ("loss", C.c_int),
                 ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
                 ("momentum_decay", C.c_float), ("use_graph", C.c_int), ("conv_pipe", C.c_int), ("readout", C.c_int),
-                ("dsp_path", C.c_int), ("l1_weight", C.c_float), ("mel", C.c_int)]
+                ("dsp_path", C.c_int), ("l1_weight", C.c_float), ("mel", C.c_int), ("conv_tile", C.c_int)]
 
 
 class DetectorArch(C.Structure):
@@ -146,6 +146,7 @@ SIGNATURES = {
     "aware_embed_workspace_bytes": (_sz, [_vp, _vp]),
     "aware_embed_create": (_i, [C.POINTER(_vp), _vp, _vp, _vp, C.POINTER(EmbedConfig), _vp, _sz, _vp]),
     "aware_embed_destroy": (None, [_vp]),
+    "aware_embed_conv_tile": (_i, [_vp, _i, _i]),
     "aware_embed_set_optimizer": (_i, [_vp, C.POINTER(OptimizerConfig), _vp]),
     "aware_embed_loop_attack_workspace_bytes": (_sz, [_vp, _i]),
     "aware_embed_set_loop_attacks": (_i, [_vp, C.POINTER(LoopAttack), _i, C.POINTER(C.c_uint32), _vp, _sz, _vp]),
@@ -198,6 +199,8 @@ SIGNATURES = {
     "aware_gemm_clip_last": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp]),
     "aware_gemm_clip_h2_workspace_bytes": (_sz, [_i, _i, _i]),
     "aware_gemm_clip_h2": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
+    "aware_gemm_clip_h2_tile": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _sz, _i,
+                                     _vp]),
     "aware_gemm_nt": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp]),
 }
 

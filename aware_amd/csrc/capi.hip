@@ -1106,6 +1106,20 @@ static int clip_tile_groups(const aware_batch* b) {
 constexpr int kMelFrontMinClips = 192;
 // fewer workgroups than this: the latency variant of the bf16x3 kernel serves the conv block (gemm_x3.hip, kSmallGrid)
 constexpr int kH2MinGrid = 128;
+// The wide form of the f16 two-term kernel (gemm_h2.hip, tile 2: 256-column slabs, 256 threads, two waves per SIMD) needs a
+// grid of at least this many workgroups: the chip holds 512 of them at a time (256 CUs x 2), and below one full round the
+// 128-column form's twice as many, half as heavy workgroups spread better.  Measured inside the embed loop on 3 s clips (ms per
+// iteration, 128-column form / wide form everywhere / this rule): 256 clips (512 and 1024 workgroups) 0.987 / 0.954 / 0.955;
+// 128 clips (256 and 512) 0.559 / 0.545 / 0.541 -- the 256-workgroup launches are better left narrow; 64 clips (128 and 256)
+// 0.340 / 0.366 / 0.340.  The crossover lies between 256 and 512 workgroups.  DESIGN.md section 4.
+constexpr int kH2WideMinGrid = 512;
+// conv_tile: aware_embed_config::conv_tile (0 automatic, 1 the 128-column form, 2 the wide form wherever it can run).
+// Returns the `tile` of launch_gemm_clip_h2 for a [B clips of nwm row groups] x N x K launch.
+static int h2_conv_tile(int conv_tile, int B, int nwm, int N, int K) {
+    if (conv_tile == 1 || !gemm_clip_h2_wide_supported(nwm, N, K, K)) return 1;
+    if (conv_tile == 2) return 2;
+    return (N / kH2WideTile) * B >= kH2WideMinGrid ? 2 : 1;
+}
 
 // The kernels of one detector call, chosen once by det_plan and launched by det_forward / det_forward_backward.
 enum class MelFwd : unsigned char {
@@ -1143,6 +1157,8 @@ struct DetPlan {
     Readout readout = Readout::Head;
     bool tail_k64 = false;    // the tail writes dL/dZ of the last block with a row pitch of 64, for Conv::ReadoutGrad
     Conv fwd[kMaxLayers] = {}, bwd[kMaxLayers] = {};
+    // Conv::ClipH2 launches: the form of the kernel (h2_conv_tile: 1 = 128-column slabs, 2 = wide), else 0
+    unsigned char fwd_tile[kMaxLayers] = {}, bwd_tile[kMaxLayers] = {};
     // x_max[l]: the kernel that writes block l's input also leaves its per-clip maxima in amax[l], for an f16 two-term block
     // l (otherwise that block launches the maxima kernel first); g_max[l]: the same for dL/dZ_l in gmax[l & 1]
     bool x_max[kMaxLayers + 1] = {}, g_max[kMaxLayers] = {};
@@ -1155,7 +1171,7 @@ static bool is_h2(Conv k) { return k == Conv::ClipH2 || k == Conv::RaggedH2; }
 // readout: aware_embed_config::readout (1: never the fused read-out); training: the parameter gradients are wanted too;
 // mel_folded: the analysis kernel writes the raw mel tile (xm); mel_grad_only: the backward stops at dL/d(mel)
 static DetPlan det_plan(const aware_detector* d, const aware_batch* b, int pipe, int readout, bool training, bool mel_folded,
-                        bool mel_grad_only) {
+                        bool mel_grad_only, int conv_tile = 0) {
     DetPlan p;
     const int nl = d->n_layers;
     const std::vector<int>& ch = d->ch;
@@ -1197,6 +1213,7 @@ static DetPlan det_plan(const aware_detector* d, const aware_batch* b, int pipe,
             k = Conv::RaggedX3;
         }
         p.fwd[l] = k;
+        p.fwd_tile[l] = k == Conv::ClipH2 ? (unsigned char)h2_conv_tile(conv_tile, b->B, nwm, co, ci) : 0;
     }
     // the clip form of the mel norm kernel leaves the maxima of x0 when handed amax[0]; the chunked form does not
     const bool mel_writes_max = p.mel == MelFwd::Front || (p.mel_amax && b->max_frames <= kMelClipFrames);
@@ -1233,6 +1250,7 @@ static DetPlan det_plan(const aware_detector* d, const aware_batch* b, int pipe,
             k = Conv::MelBack;
         }
         p.bwd[l] = k;
+        p.bwd_tile[l] = k == Conv::ClipH2 ? (unsigned char)h2_conv_tile(conv_tile, b->B, nwm, ci, co) : 0;
         // the fused and wide read-outs, the f16 two-term kernels and the ragged read-out gradient leave the maxima of the
         // gradient they write for an f16 two-term consumer
         const bool writes_max = l == p.top ? p.readout == Readout::X3 || p.readout == Readout::Wide
@@ -1276,7 +1294,8 @@ static int det_forward(const aware_detector* d, const aware_batch* b, const DetP
         case Conv::ClipH2:
             if (!p.x_max[l]) { launch_clip_amax(x, ci, ci, 32 * p.nwm, b->B, o.amax[l], st); LAUNCHCHK(); PROF(K_MISC); }
             launch_gemm_clip_h2(x, ci, d->wh2[l], o.amax[l], amax_out, d->bias[l], o.act[l], co, b->B, p.nwm, b->uniform_tp, co, ci,
-                                1, o.rstd[l], nullptr, st, emit ? d->lastpk : nullptr, emit ? o.zpart : nullptr, d->ch[nl]);
+                                1, o.rstd[l], nullptr, st, emit ? d->lastpk : nullptr, emit ? o.zpart : nullptr, d->ch[nl],
+                                p.fwd_tile[l]);
             LAUNCHCHK(); PROF(K_GEMM_X3_FWD);
             break;
         case Conv::ClipX3:
@@ -1482,7 +1501,7 @@ static int det_forward_backward(const aware_detector* d, const aware_batch* b, c
         case Conv::ClipH2:
             if (!p.g_max[l]) { launch_clip_amax(dA, co, co, 32 * p.nwm, b->B, db.gmax[l & 1], st); LAUNCHCHK(); PROF(K_MISC); }
             launch_gemm_clip_h2(dA, co, d->wTh2[l], db.gmax[l & 1], g_out, nullptr, dB, ci, b->B, p.nwm, b->uniform_tp, ci, co, 2,
-                                db.rstd[l - 1], db.act[l - 1], st);
+                                db.rstd[l - 1], db.act[l - 1], st, nullptr, nullptr, 0, p.bwd_tile[l]);
             LAUNCHCHK(); PROF(K_GEMM_X3_BWD);
             break;
         case Conv::ClipX3:
@@ -1813,12 +1832,19 @@ extern "C" int aware_embed_create(aware_embed** out, const aware_plan* plan, con
     if (cfg->num_iterations < 1 || cfg->num_iterations > 4096 || cfg->loss < 0 || cfg->loss > AWARE_LOSS_PUSH_L1) return AWARE_E_BADARG;
     if (cfg->conv_pipe < 0 || cfg->conv_pipe > 2 || cfg->readout < 0 || cfg->readout > 1 || cfg->mel < 0 || cfg->mel > 1)
         return AWARE_E_BADARG;
-    if (cfg->dsp_path < 0 || cfg->dsp_path > 1) return AWARE_E_BADARG;
+    if (cfg->dsp_path < 0 || cfg->dsp_path > 1 || cfg->conv_tile < 0 || cfg->conv_tile > 2) return AWARE_E_BADARG;
     // the detector's mel operands have the layout of the plan it was created for
     if (det->band_lo != plan->dev.band_lo || det->nband != plan->dev.nband || det->stride != plan->dev.stride) return AWARE_E_BADARG;
     // the L1 term lives in the streaming DSP kernels only
     const bool l1 = cfg->loss == AWARE_LOSS_PUSH_L1;
     if (l1 && (cfg->dsp_path != 0 || !stream_supported(plan->dev))) return AWARE_E_UNSUPPORTED;
+    if (cfg->conv_tile == 2) {
+        // the wide form was asked for: some conv launch of this session has to be able to take it
+        const DetPlan p = det_plan(det, b, cfg->conv_pipe, cfg->readout, false, false, false, 2);
+        bool any = false;
+        for (int l = 0; l < det->n_layers; ++l) any = any || p.fwd_tile[l] == 2 || p.bwd_tile[l] == 2;
+        if (!any) return AWARE_E_UNSUPPORTED;
+    }
     hipStream_t st = (hipStream_t)stream;
     aware_embed* e = new aware_embed();
     e->plan = plan; e->det = det; e->b = b; e->cfg = *cfg;
@@ -2209,6 +2235,14 @@ extern "C" void aware_embed_destroy(aware_embed* e) {
     delete e;
 }
 
+extern "C" int aware_embed_conv_tile(const aware_embed* e, int backward, int layer) {
+    if (!e || layer < 0 || layer >= e->det->n_layers) return AWARE_E_BADARG;
+    // the conv kinds and tiles of a plan do not depend on its mel flags
+    const DetPlan p = det_plan(e->det, e->b, e->cfg.conv_pipe, e->cfg.readout, false, false, false, e->cfg.conv_tile);
+    if (backward) return layer <= p.top ? p.bwd_tile[layer] : 0;
+    return layer < p.n_fwd ? p.fwd_tile[layer] : 0;
+}
+
 extern "C" void* aware_embed_buffer(aware_embed* e, int which) {
     if (!e) return nullptr;
     switch (which) {
@@ -2531,7 +2565,7 @@ static int embed_iteration(aware_embed* e, hipStream_t st, int do_step, float* g
     // inside the optimiser loop (multibit_embedder.py:120-122)
     G.best_loss = do_step ? e->best_loss : nullptr;
     G.improved = do_step ? e->improved : nullptr;
-    const DetPlan p = det_plan(d, b, e->cfg.conv_pipe, e->cfg.readout, false, mel_fold, mel_taps);
+    const DetPlan p = det_plan(d, b, e->cfg.conv_pipe, e->cfg.readout, false, mel_fold, mel_taps, e->cfg.conv_tile);
     int rc = det_forward_backward(d, b, p, e->mag, e->db, G, st);
     if (rc) return rc;
     // backward through |.|, STFT, reflect padding
@@ -3014,11 +3048,22 @@ extern "C" size_t aware_gemm_clip_h2_workspace_bytes(int B, int N, int K) {
 extern "C" int aware_gemm_clip_h2(const float* A, int lda, const float* Bt, int ldb, const float* bias, float* C, int ldc, int B,
                                   int Tp, int N, int K, int epi, float* rstd_io, const float* act, const void* lastpk, float* zpart,
                                   int CL, float* amax_out, void* workspace, size_t workspace_bytes, void* stream) {
+    return aware_gemm_clip_h2_tile(A, lda, Bt, ldb, bias, C, ldc, B, Tp, N, K, epi, rstd_io, act, lastpk, zpart, CL, amax_out,
+                                   workspace, workspace_bytes, 0, stream);
+}
+// tile 0: the 128-column form (what the entry above runs; the automatic choice belongs to a session's plan), 1: the same,
+// 2: the wide form (AWARE_E_UNSUPPORTED where it cannot run: more than 96 rows per clip, N no multiple of 256)
+extern "C" int aware_gemm_clip_h2_tile(const float* A, int lda, const float* Bt, int ldb, const float* bias, float* C, int ldc,
+                                       int B, int Tp, int N, int K, int epi, float* rstd_io, const float* act, const void* lastpk,
+                                       float* zpart, int CL, float* amax_out, void* workspace, size_t workspace_bytes, int tile,
+                                       void* stream) {
+    if (tile < 0 || tile > 2) return AWARE_E_BADARG;
     if (!A || !Bt || !C || !workspace || B < 1 || Tp < 1 || Tp > 128 || epi < 0 || epi > 2 || (ldb & 3)) return AWARE_E_BADARG;
     if (epi != 0 && !rstd_io) return AWARE_E_BADARG;
     if (epi == 2 && !act) return AWARE_E_BADARG;
     const int nwm = (Tp + 31) / 32;
     if (!gemm_clip_h2_supported(nwm, N, K, lda) || N % 16) return AWARE_E_BADARG;
+    if (tile == 2 && !gemm_clip_h2_wide_supported(nwm, N, K, lda)) return AWARE_E_UNSUPPORTED;
     if (workspace_bytes < aware_gemm_clip_h2_workspace_bytes(B, N, K)) return AWARE_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     Carver c(workspace, workspace_bytes);
@@ -3027,7 +3072,7 @@ extern "C" int aware_gemm_clip_h2(const float* A, int lda, const float* Bt, int 
     launch_h2_pack(Bt, ldb, N, K, pk, st);
     launch_clip_amax(A, lda, K, 32 * nwm, B, amax, st);
     launch_gemm_clip_h2(A, lda, pk, amax, amax_out, bias, C, ldc, B, nwm, Tp, N, K, epi, rstd_io, act, st,
-                        (epi == 1 && lastpk && zpart) ? lastpk : nullptr, zpart, CL);
+                        (epi == 1 && lastpk && zpart) ? lastpk : nullptr, zpart, CL, tile == 2 ? 2 : 1);
     LAUNCHCHK();
     return AWARE_OK;
 }

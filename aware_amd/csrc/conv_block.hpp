@@ -11,8 +11,10 @@
 //   kWeightBytes   packed bytes per weight (the slab-group size of the uniform walk);
 //   kTerms         A terms staged in LDS (the staging buffer of one K tile is 2 kTerms MT KiB);
 //   tile_gemm<RG>  the K loop: acc[m][0] = A[bm + 16 m ..][0..K) * B^T for the wave's 16 columns (scaled by ascale when kScaled);
+//   tile_gemm<RG, NT, NW>  (formats with a wide form) the same for NT column tiles per wave in a workgroup of NW waves;
 //   scale_for / pow2_inverse (kScaled only).
-// Every workgroup is 8 waves x 128 columns; a wave owns every row of its 16 columns.
+// A workgroup is 8 waves x 128 columns, a wave owning every row of its 16 columns -- or, in the wide form of the uniform f16x2
+// kernel, 4 waves x 256 columns, a wave owning every row of 64.
 // Reference semantics of the epilogues: detection/modules/conv1d.py:38-42 (conv -> InstanceNorm1d -> LeakyReLU) and its autograd.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -22,8 +24,8 @@ namespace aware {
 
 constexpr int kConvFrag = 1024;        // one 16-row x 32-k 16-bit fragment image, bytes
 
-// staging memory of the uniform kernel: two K tiles; FWD_LAST re-lays the output tile as f32 [32 RG][132] in the same memory,
-// then parks 8 x RG x 3 partial tiles of 1 KiB there
+// staging memory of the uniform kernel: two K tiles; FWD_LAST re-lays one 128-column slab of the output tile as f32
+// [32 RG][132] in the same memory, then parks 8 x RG x 3 partial tiles of 1 KiB there
 template <class P, int RG, int EPI>
 constexpr int conv_block_lds_bytes() {
     constexpr int stage = 2 * 2 * P::kTerms * 2 * RG * kConvFrag;
@@ -31,12 +33,27 @@ constexpr int conv_block_lds_bytes() {
     return (EPI == X3_FWD_LAST && last > stage) ? last : stage;
 }
 
+// columns of a workgroup's tile: NW waves x NT column tiles of 16
+constexpr int conv_tile_width(int NT, int NW) { return 16 * NT * NW; }
+
+// Slab-group size of the uniform walk: the largest divisor of tiles_n whose packed weights (sg * width * K * weight_bytes)
+// fit 3.2 MB of an XCD's 4 MB L2 (host and device; tests/test_conv_tile_rule_host.py restates it)
+__host__ __device__ inline int conv_slab_group(int tiles_n, int width, int K, int weight_bytes) {
+    int sg = (int)(3355443u / (unsigned)(width * K * weight_bytes));
+    sg = sg < 1 ? 1 : (sg > tiles_n ? tiles_n : sg);
+    while (tiles_n % sg) --sg;
+    return sg;
+}
+
 // ---------------------------------------------------------------------------------------------------
-// uniform batches: one workgroup = all 32 RG rows of one clip x one 128-column slab
+// uniform batches: one workgroup = all 32 RG rows of one clip x one slab of 16 NT NW columns
 // ---------------------------------------------------------------------------------------------------
 // binv / amax_in / amax_out: kScaled only.  Mrows (x3, PLAIN only): rows of A and C that exist; the last row block may be
-// partial (reads clamped, stores masked).
-template <class P, int RG, int EPI>
+// partial (reads clamped, stores masked).  tiles_n = N / (16 NT NW).
+// NT column tiles per wave, NW waves: 1 x 8 (128-column slabs) everywhere, and 4 x 4 (256-column slabs, the wide form of the
+// f16 two-term kernel).  The epilogue walks a wave's column tiles one after the other with the arithmetic of the 1 x 8 form on
+// each, so every output, statistic and partial maximum has the same bits at any NT.
+template <class P, int RG, int EPI, int NT = 1, int NW = 8>
 __device__ __forceinline__ void conv_block_uniform(const float* __restrict__ A, int lda, const u32x4* __restrict__ Bpk,
                                                    const float* __restrict__ binv, const float* __restrict__ amax_in,
                                                    float* __restrict__ amax_out, const float* __restrict__ bias,
@@ -46,10 +63,13 @@ __device__ __forceinline__ void conv_block_uniform(const float* __restrict__ A, 
     constexpr int MT = 2 * RG;            // 16-row tiles per clip
     constexpr int MH = RG;
     constexpr int FRAG = kConvFrag;
+    constexpr int W = conv_tile_width(NT, NW);
+    static_assert(NT == 1 || P::kScaled, "the row-major PLAIN epilogue of the unscaled format is written for one column tile");
+    static_assert(W % 128 == 0 && (NW == 8 || NW == 4), "FWD_LAST works on whole 128-column slabs with 4 or 8 waves");
     __shared__ __attribute__((aligned(16))) unsigned char lds[conv_block_lds_bytes<P, RG, EPI>()];
 
     // Blocks b and b + 8 share an XCD (observed round-robin placement; speed only).  An XCD takes a contiguous range of clips and
-    // walks it slab-group-major: `sg` column slabs at a time whose packed weights (sg * 128 * K * kWeightBytes) fit its 4 MB L2
+    // walks it slab-group-major: `sg` column slabs at a time whose packed weights (sg * W * K * kWeightBytes) fit its 4 MB L2
     // together with the activation rows in flight, all clips of the range for that group, then the next group.  Clip-major
     // order streamed all 6.3 MB of a 1024 x 1024 bf16x3 layer through the L2 for every clip (PMC: 565 MB fetched per launch for
     // 206 MB of operands); this order fetches the weights once per XCD and the activation rows once per group.
@@ -59,9 +79,7 @@ __device__ __forceinline__ void conv_block_uniform(const float* __restrict__ A, 
         const int x = id & 7, j = id >> 3, R = ntiles >> 3;          // XCD, index inside its range, workgroups per XCD
         const int nclip = R / tiles_n;                                // clips per XCD (ntiles = clips * tiles_n, clips % 8 == 0 here
         if (nclip * tiles_n == R && nclip > 0) {                     //  whenever the batch size is a multiple of 8)
-            int sg = (int)(3355443u / (unsigned)(128 * K * P::kWeightBytes));      // slabs whose weights fit 3.2 MB
-            sg = sg < 1 ? 1 : (sg > tiles_n ? tiles_n : sg);
-            while (tiles_n % sg) --sg;
+            const int sg = conv_slab_group(tiles_n, W, K, P::kWeightBytes);
             const int per_group = nclip * sg;
             const int grp = j / per_group, r = j % per_group;
             clip = x * nclip + r / sg;
@@ -76,12 +94,12 @@ __device__ __forceinline__ void conv_block_uniform(const float* __restrict__ A, 
         slab = id % tiles_n;
     }
     const int bm = clip * 32 * RG;
-    const int bn = slab * 128;
+    const int bn = slab * W;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r16 = lane & 15, kg = lane >> 4;
-    const int col = bn + wave * 16 + r16;
+    const int col0 = bn + wave * (16 * NT) + r16;      // this lane's column of the wave's first column tile
 
-    float ascale = 1.f, ainv = 1.f, bcol = 1.f;
+    float ascale = 1.f, ainv = 1.f;
     if constexpr (P::kScaled) {
         // the clip's scale from the producer's partial maxima (K/16 of them: one per wave of each of its workgroups)
         float am = lane < (K >> 4) ? amax_in[(size_t)clip * 64 + lane] : 0.f;
@@ -90,21 +108,21 @@ __device__ __forceinline__ void conv_block_uniform(const float* __restrict__ A, 
         ascale = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(P::scale_for(am))));
     }
 
-    f32x4 acc[MT][1];
-    P::template tile_gemm<RG>(A, lda, Bpk, K, bm, bn, lds, acc,
-                              (!P::kScaled && EPI == X3_PLAIN) ? min(32 * RG, Mrows - bm) : 32 * RG, ascale);
+    f32x4 acc[MT][NT];
+    const int row_limit = (!P::kScaled && EPI == X3_PLAIN) ? min(32 * RG, Mrows - bm) : 32 * RG;
+    if constexpr (NT == 1 && NW == 8) P::template tile_gemm<RG>(A, lda, Bpk, K, bm, bn, lds, acc, row_limit, ascale);
+    else P::template tile_gemm<RG, NT, NW>(A, lda, Bpk, K, bm, bn, lds, acc, row_limit, ascale);
 
-    // ---- epilogue: lane holds rows m*16 + 4*kg + e (e = 0..3) of column col ----
-    if constexpr (P::kScaled) { ainv = P::pow2_inverse(ascale); bcol = binv[col]; }
+    // ---- epilogue: lane holds rows m*16 + 4*kg + e (e = 0..3) of columns col0 + 16 n ----
+    if constexpr (P::kScaled) ainv = P::pow2_inverse(ascale);
     const float invT = 1.0f / (float)Tp;
-    float omax = 0.f;                                   // max |output| of this wave's 16 columns, for the next GEMM's scale
     if constexpr (!P::kScaled && EPI == X3_PLAIN) {
         if ((ldc & 3) == 0) {
             // The tile leaves in ROW-MAJOR order (16 bytes per lane, half a wave = one 512-byte row segment), not in the
             // accumulator's layout (4 rows x 64 bytes per wave instruction, which streams at about half the rate: measured on
             // the read-out kernel, 3.0 vs 6 TB/s).  The staging LDS is free now; pitch 132 floats keeps both sides conflict-free.
             float (*T)[132] = reinterpret_cast<float (*)[132]>(lds);
-            const float bv = bias ? bias[col] : 0.f;
+            const float bv = bias ? bias[col0] : 0.f;
             __syncthreads();                                // every wave has left the K loop
 #pragma unroll
             for (int m = 0; m < MT; ++m)
@@ -124,6 +142,12 @@ __device__ __forceinline__ void conv_block_uniform(const float* __restrict__ A, 
     }
     // (the forward / backward epilogues keep the accumulator-layout stores: behind the K loop of a second resident workgroup
     //  they are hidden -- the row-major form measured the same time on the three conv blocks)
+#pragma unroll
+    for (int n = 0; n < NT; ++n) {
+    const int col = col0 + 16 * n;
+    float bcol = 1.f;
+    if constexpr (P::kScaled) bcol = binv[col];
+    float omax = 0.f;                                   // max |output| of this column tile, for the next GEMM's scale
     if (EPI == X3_PLAIN) {
         const float bv = bias ? bias[col] : 0.f;
 #pragma unroll
@@ -131,7 +155,7 @@ __device__ __forceinline__ void conv_block_uniform(const float* __restrict__ A, 
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const int row = m * 16 + 4 * kg + e;
-                const float o = row < Tp ? fmaf(acc[m][0][e] * ainv, bcol, bv) : 0.f;
+                const float o = row < Tp ? fmaf(acc[m][n][e] * ainv, bcol, bv) : 0.f;
                 omax = fmaxf(omax, fabsf(o));
                 if (P::kScaled || bm + row < Mrows) C[(size_t)(bm + row) * ldc + col] = o;
             }
@@ -143,8 +167,8 @@ __device__ __forceinline__ void conv_block_uniform(const float* __restrict__ A, 
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const int row = m * 16 + 4 * kg + e;
-                acc[m][0][e] = fmaf(acc[m][0][e] * ainv, bcol, bv);
-                if (row < Tp) s += acc[m][0][e];
+                acc[m][n][e] = fmaf(acc[m][n][e] * ainv, bcol, bv);
+                if (row < Tp) s += acc[m][n][e];
             }
         s += __shfl_xor(s, 16);
         s += __shfl_xor(s, 32);
@@ -163,7 +187,7 @@ __device__ __forceinline__ void conv_block_uniform(const float* __restrict__ A, 
             for (int e = 0; e < 4; ++e) {
                 const int row = m * 16 + 4 * kg + e;
                 if (row < Tp) {
-                    const float d = centre(acc[m][0][e]);
+                    const float d = centre(acc[m][n][e]);
                     if constexpr (P::kScaled) qq = fmaf(d, d, qq);
                     else qq += d * d;
                 }
@@ -177,9 +201,9 @@ __device__ __forceinline__ void conv_block_uniform(const float* __restrict__ A, 
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const int row = m * 16 + 4 * kg + e;
-                const float u = centre(acc[m][0][e]) * rs;
+                const float u = centre(acc[m][n][e]) * rs;
                 const float o = row < Tp ? (u > 0.f ? u : 0.2f * u) : 0.f;
-                acc[m][0][e] = o;
+                acc[m][n][e] = o;
                 omax = fmaxf(omax, fabsf(o));
                 C[(size_t)(bm + row) * ldc + col] = o;
             }
@@ -198,8 +222,8 @@ __device__ __forceinline__ void conv_block_uniform(const float* __restrict__ A, 
                 const float av = act[(size_t)(bm + row) * ldc + col];
                 const bool valid = row < Tp;
                 const float uv = valid ? (av > 0.f ? av : av * 5.0f) : 0.f;                 // invert LeakyReLU(0.2)
-                const float du = valid ? acc[m][0][e] * ainv * bcol * (av > 0.f ? 1.f : 0.2f) : 0.f;
-                acc[m][0][e] = du;
+                const float du = valid ? acc[m][n][e] * ainv * bcol * (av > 0.f ? 1.f : 0.2f) : 0.f;
+                acc[m][n][e] = du;
                 u[m][e] = uv;
                 s1 += du;
                 s2 += du * uv;
@@ -214,7 +238,7 @@ __device__ __forceinline__ void conv_block_uniform(const float* __restrict__ A, 
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const int row = m * 16 + 4 * kg + e;
-                const float o = row < Tp ? rs * (acc[m][0][e] - m1 - u[m][e] * m2) : 0.f;
+                const float o = row < Tp ? rs * (acc[m][n][e] - m1 - u[m][e] * m2) : 0.f;
                 omax = fmaxf(omax, fabsf(o));
                 C[(size_t)(bm + row) * ldc + col] = o;
             }
@@ -226,39 +250,51 @@ __device__ __forceinline__ void conv_block_uniform(const float* __restrict__ A, 
             if (lane == 0) amax_out[(size_t)clip * 64 + (col >> 4)] = omax;
         }
     }
+    }
     if (EPI == X3_FWD_LAST) {
-        // acc[m][0][e] holds this block's output (zero in padding rows).  The next conv block is the skinny last one
-        // (CL <= 48 channels): its K = this N is split over the column slabs, so this workgroup contributes the partial
-        // z_part[slab] = out[:, slab] * Wlast[:, slab]^T, on the bf16 pipe with the exact three-way split whatever the format
-        // of the K loop (Lpk: gemm_x3.hip's pack).  The output tile is re-laid as A fragments (k = column) in LDS.
-        // Work split: wave w takes K32 step t = w>>1 of the slab's 128 columns and half mh = w&1 of the row tiles (all
-        // column tiles of the last conv); the four t-partials are then summed through LDS.
+        // acc[m][n][e] holds this block's output (zero in padding rows).  The next conv block is the skinny last one
+        // (CL <= 48 channels): its K = this N is split over the 128-column slabs, so this workgroup contributes, per slab of its
+        // tile, the partial z_part[slab] = out[:, slab] * Wlast[:, slab]^T, on the bf16 pipe with the exact three-way split
+        // whatever the format of the K loop (Lpk: gemm_x3.hip's pack).  A slab of the output tile is re-laid as A fragments
+        // (k = column) in LDS.  Work units of a slab: (K32 step t = 0..3 of its 128 columns) x (half mh of the row tiles), all
+        // column tiles of the last conv each; eight waves take one unit each (t = w>>1, mh = w&1), four waves take both halves
+        // of step t = w.  The four t-partials are then summed through LDS in the order t = 0..3 at any wave count.
         const int KS2L = N >> 5, ncl = (CL + 15) >> 4;
-        const int tq = wave >> 1, mh = wave & 1;
+        constexpr int UH = 8 / NW;                        // row halves per wave
+        constexpr int WS = 8 / NT;                        // waves whose columns make one 128-column slab
+        const int tq = NW == 8 ? wave >> 1 : wave, mh0 = NW == 8 ? wave & 1 : 0;
+        float* const T = reinterpret_cast<float*>(lds);
+        constexpr int TP = 132;
+#pragma unroll
+        for (int sl = 0; sl < W / 128; ++sl) {
+        const int slab128 = (bn >> 7) + sl;
         bf16x8 bl[3][3];
 #pragma unroll
         for (int n = 0; n < 3; ++n)
             if (n < ncl) {
 #pragma unroll
                 for (int p = 0; p < 3; ++p)
-                    bl[n][p] = __builtin_bit_cast(bf16x8, Lpk[(((size_t)n * KS2L + 4 * slab + tq) * 3 + p) * 64 + lane]);
+                    bl[n][p] = __builtin_bit_cast(bf16x8, Lpk[(((size_t)n * KS2L + 4 * slab128 + tq) * 3 + p) * 64 + lane]);
             }
-        __syncthreads();                                  // every wave is done with the staging buffers
-        // the output tile goes through LDS as f32 [row][column], row pitch 132 floats (conflict-free 4-byte stores from
+        __syncthreads();                                  // every wave is done with the staging buffers / the slab before
+        // the slab goes through LDS as f32 [row][column], row pitch 132 floats (conflict-free 4-byte stores from
         // the accumulator layout); each wave reads its A fragments back as 8 consecutive columns per lane and splits them
-        float* const T = reinterpret_cast<float*>(lds);
-        constexpr int TP = 132;
+        if (wave / WS == sl) {
 #pragma unroll
-        for (int m = 0; m < MT; ++m)
+            for (int n = 0; n < NT; ++n)
 #pragma unroll
-            for (int e = 0; e < 4; ++e) T[(16 * m + 4 * kg + e) * TP + 16 * wave + r16] = acc[m][0][e];
+                for (int m = 0; m < MT; ++m)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        T[(16 * m + 4 * kg + e) * TP + 16 * ((wave % WS) * NT + n) + r16] = acc[m][n][e];
+        }
         __syncthreads();
-        f32x4 zt[MH][3];
+        f32x4 zt[UH * MH][3];
 #pragma unroll
-        for (int mm = 0; mm < MH; ++mm) {
+        for (int mm = 0; mm < UH * MH; ++mm) {
 #pragma unroll
             for (int n = 0; n < 3; ++n) zt[mm][n] = f32x4{0.f, 0.f, 0.f, 0.f};
-            const float* src = T + (16 * (mh * MH + mm) + r16) * TP + 32 * tq + 8 * kg;
+            const float* src = T + (16 * (mh0 * MH + mm) + r16) * TP + 32 * tq + 8 * kg;
             const float4 x0 = *reinterpret_cast<const float4*>(src), x1 = *reinterpret_cast<const float4*>(src + 4);
             uint4 q0, q1, q2;
             split_pair(x0.x, x0.y, q0.x, q1.x, q2.x);
@@ -277,27 +313,28 @@ __device__ __forceinline__ void conv_block_uniform(const float* __restrict__ A, 
             }
         }
         __syncthreads();                                  // all fragment reads done: the buffer becomes the partial store
+        // partial of (step tq, row tile rt) at slot tq * MT + rt (with eight waves: (wave * MH + mm), as rt = mh0 * MH + mm)
 #pragma unroll
-        for (int mm = 0; mm < MH; ++mm)
+        for (int mm = 0; mm < UH * MH; ++mm)
 #pragma unroll
             for (int n = 0; n < 3; ++n)
-                *reinterpret_cast<f32x4*>(lds + (size_t)((wave * MH + mm) * 3 + n) * FRAG + lane * 16) = zt[mm][n];
+                *reinterpret_cast<f32x4*>(lds + (size_t)((tq * MT + mh0 * MH + mm) * 3 + n) * FRAG + lane * 16) = zt[mm][n];
         __syncthreads();
-        if (wave < MT) {
-            const int smh = wave / MH, smm = wave % MH;   // this wave finishes row tile `wave`
-            float* zp = zpart + (size_t)slab * ((size_t)(ntiles / tiles_n) * 32 * RG * CL) + (size_t)(bm + 16 * wave + 4 * kg) * CL;
+        for (int rt = wave; rt < MT; rt += NW) {          // this wave finishes row tile rt
+            float* zp = zpart + (size_t)slab128 * ((size_t)(ntiles / tiles_n) * 32 * RG * CL) + (size_t)(bm + 16 * rt + 4 * kg) * CL;
 #pragma unroll
             for (int n = 0; n < 3; ++n)
                 if (n < ncl) {
                     f32x4 t = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                     for (int q = 0; q < 4; ++q)
-                        t += *reinterpret_cast<const f32x4*>(lds + (size_t)(((2 * q + smh) * MH + smm) * 3 + n) * FRAG + lane * 16);
+                        t += *reinterpret_cast<const f32x4*>(lds + (size_t)((q * MT + rt) * 3 + n) * FRAG + lane * 16);
                     if (16 * n + r16 < CL) {
 #pragma unroll
                         for (int e = 0; e < 4; ++e) zp[(size_t)e * CL + 16 * n + r16] = t[e];
                     }
                 }
+        }
         }
     }
 }

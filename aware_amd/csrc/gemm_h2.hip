@@ -133,21 +133,26 @@ __device__ __forceinline__ void h2_split_pair(float x, float y, float s, unsigne
     l = __builtin_bit_cast(unsigned, ll);
 }
 
-// acc[m][0] += (A[bm + 16 m .. +16)[0..K) * 2^sa) * (B 2^sb)^T for the wave's 16 columns bn + 16 wave ..; the caller unscales.
-// `lds`: 2 * 2 * 2 * 2RG KiB of staging memory (two K tiles of 64, two K32 steps, two planes); every wave of the 8-wave
-// workgroup calls this with the same arguments; the caller provides a barrier between two calls that reuse `lds`.
-template <int RG>
+// acc[m][n] += (A[bm + 16 m .. +16)[0..K) * 2^sa) * (B 2^sb)^T for the wave's NT column tiles bn + 16 (NT wave + n) ..; the
+// caller unscales.  `lds`: 2 * 2 * 2 * 2RG KiB of staging memory (two K tiles of 64, two K32 steps, two planes); every wave of
+// the NW-wave workgroup calls this with the same arguments; the caller provides a barrier between two calls that reuse `lds`.
+// NT = 1, NW = 8: a wave owns 16 columns, three MFMAs per A fragment read.  NT = 4, NW = 4 (the wide form): a wave owns 64
+// columns, twelve MFMAs per A fragment read, and a workgroup of half the threads stages the rows for twice the columns.  Every
+// accumulator sees the same products in the same order at any NT (l_a h_b, h_a l_b, h_a h_b per K32 step, ascending K): the
+// forms are bit-identical.
+template <int RG, int NT = 1, int NW = 8>
 __device__ __forceinline__ void h2_tile_gemm(const float* __restrict__ A, int lda, const u32x4* __restrict__ Bpk, int K, int bm,
-                                             int bn, unsigned char* lds, f32x4 (&acc)[2 * RG][1], int row_limit, float ascale) {
+                                             int bn, unsigned char* lds, f32x4 (&acc)[2 * RG][NT], int row_limit, float ascale) {
     constexpr int MT = 2 * RG;            // 16-row tiles per clip
     constexpr int MH = RG;                // ... per half (the unit of the A-fragment schedule)
     constexpr int FRAG = 1024;            // one 16-row x 32-k f16 fragment image, bytes
     constexpr int PLANE = MT * FRAG;
     constexpr int KSS = 2 * PLANE;        // one K32 step
     constexpr int BUF = 2 * KSS;          // one K tile (BK = 64)
-    // A staging: pass i covers rows 32 i .. 32 i + 31 of the K tile; thread -> (row tid >> 4, 4 floats at k = 4 (tid & 15)):
+    // A staging: pass i covers rows RP i .. RP i + RP - 1 of the K tile; thread -> (row tid >> 4, 4 floats at k = 4 (tid & 15)):
     // one fully coalesced 16-byte load per lane (16 lanes = one 256-byte row segment) and one 8-byte LDS store per plane
-    constexpr int NPASS = RG;
+    constexpr int RP = 4 * NW;            // rows per pass: 32 (8 waves) or 16 (4 waves)
+    constexpr int NPASS = 32 * RG / RP;
 
     bm = __builtin_amdgcn_readfirstlane(bm);
     bn = __builtin_amdgcn_readfirstlane(bn);
@@ -160,17 +165,19 @@ __device__ __forceinline__ void h2_tile_gemm(const float* __restrict__ A, int ld
 
     const int KS2 = K >> 5;
     const int nkt = K >> 6;
-    const u32x4* bp = Bpk + ((size_t)((bn >> 4) + wave) * KS2) * 128;               // uniform; + lane per thread
+    const u32x4* bp = Bpk + ((size_t)((bn >> 4) + wave * NT) * KS2) * 128;          // uniform; + lane per thread
     const float* ap = A + (size_t)bm * lda;                                          // uniform
     unsigned roff[NPASS];
 #pragma unroll
-    for (int i = 0; i < NPASS; ++i) roff[i] = (unsigned)(min(srow + 32 * i, row_limit - 1) * lda + k4 * 4);
-    // LDS slot of this thread's 4 k-values of row srow (+ 32 i: two fragment images further): the XOR of the row slot with
+    for (int i = 0; i < NPASS; ++i) roff[i] = (unsigned)(min(srow + RP * i, row_limit - 1) * lda + k4 * 4);
+    // LDS slot of this thread's 4 k-values of row srow (+ RP i: RP / 16 fragment images further): the XOR of the row slot with
     // the k chunk keeps the 16 lanes of a row on 16 distinct 8-byte slots of a 128-byte bank row
     const unsigned woff = (unsigned)((sc >> 2) * KSS + (srow >> 4) * FRAG + (sc & 3) * 256 + (((srow & 15) ^ sc) * 16) + (k4 & 1) * 8);
 
 #pragma unroll
-    for (int m = 0; m < MT; ++m) acc[m][0] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int m = 0; m < MT; ++m)
+#pragma unroll
+        for (int n = 0; n < NT; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     float4 ra[NPASS];
     auto gload_c = [&](int i, int kt) { ra[i] = *reinterpret_cast<const float4*>(ap + kt * 64 + roff[i]); };
@@ -178,16 +185,18 @@ __device__ __forceinline__ void h2_tile_gemm(const float* __restrict__ A, int ld
         uint2 qh, ql;
         h2_split_pair(ra[i].x, ra[i].y, ascale, qh.x, ql.x);
         h2_split_pair(ra[i].z, ra[i].w, ascale, qh.y, ql.y);
-        unsigned char* d = lds + boff + woff + i * 2 * FRAG;
+        unsigned char* d = lds + boff + woff + i * (RP / 16) * FRAG;
         *reinterpret_cast<uint2*>(d) = qh;
         *reinterpret_cast<uint2*>(d + PLANE) = ql;
     };
     // B fragments one K32 step ahead (two steps ahead measured no different)
-    u32x4 bq[2][2];
+    u32x4 bq[2][2][NT];
     auto loadB = [&](int set, int ks2) {
         ks2 = ks2 < KS2 ? ks2 : KS2 - 1;
 #pragma unroll
-        for (int p = 0; p < 2; ++p) bq[set][p] = (bp + ((size_t)ks2 * 2 + p) * 64)[(unsigned)lane];
+        for (int n = 0; n < NT; ++n)
+#pragma unroll
+            for (int p = 0; p < 2; ++p) bq[set][p][n] = (bp + (((size_t)n * KS2 + ks2) * 2 + p) * 64)[(unsigned)lane];
     };
     auto lds_barrier = [&]() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
     // A fragments: the h plane is double-buffered (the next quarter's h fragments are requested a whole quarter -- 3 MH MFMAs
@@ -201,10 +210,12 @@ __device__ __forceinline__ void h2_tile_gemm(const float* __restrict__ A, int ld
 #pragma unroll
         for (int m = 0; m < MH; ++m) al[m] = *reinterpret_cast<const f16x8*>(lds + off + PLANE + m * FRAG);
     };
+    // (column tile outermost: consecutive MFMAs never share an accumulator)
 #define H2_MFMA(a_, b_, hf_)                                                                                                   \
+    _Pragma("unroll") for (int n = 0; n < NT; ++n)                                                                             \
     _Pragma("unroll") for (int m = 0; m < MH; ++m)                                                                             \
-        acc[(hf_) * MH + m][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16((a_)[m], __builtin_bit_cast(f16x8, (b_)),              \
-                                                                        acc[(hf_) * MH + m][0], 0, 0, 0)
+        acc[(hf_) * MH + m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16((a_)[m], __builtin_bit_cast(f16x8, (b_)[n]),           \
+                                                                        acc[(hf_) * MH + m][n], 0, 0, 0)
 #define H2_PIN(mask, n) __builtin_amdgcn_sched_group_barrier(mask, n, 0)
 
 #pragma unroll
@@ -224,14 +235,15 @@ __device__ __forceinline__ void h2_tile_gemm(const float* __restrict__ A, int ld
         for (int q = 0; q < 4; ++q) {                 // quarter = (K32 step q>>1, row half q&1)
             const int t = q >> 1, hf = q & 1;
             if (hf == 0) loadB((t + 1) & 1, kt * 2 + t + 1);
-            if (q < NPASS) {
-                split_store_c(q, nxt);
-                gload_c(q, ktn);
+#pragma unroll
+            for (int i = q; i < NPASS; i += 4) {
+                split_store_c(i, nxt);
+                gload_c(i, ktn);
             }
             const unsigned noff = q < 3 ? cur + rb[(q + 1) >> 1] + ((q + 1) & 1) * MH * FRAG : nxt + rb[0];
             if (q < 3) { read_h((q + 1) & 1, noff); H2_PIN(0x100, MH); }
             H2_MFMA(al, bq[t][0], hf);                // l_a * h_b
-            H2_PIN(0x008, MH);
+            H2_PIN(0x008, MH * NT);
             if (q == 3) {                             // tile kt+1 is complete; every wave has finished its reads of tile kt
                 lds_barrier();
                 read_h(0, noff);
@@ -244,7 +256,7 @@ __device__ __forceinline__ void h2_tile_gemm(const float* __restrict__ A, int ld
             __builtin_amdgcn_s_setprio(1);
             H2_MFMA(ah[q & 1], bq[t][1], hf);         // h_a * l_b
             H2_MFMA(ah[q & 1], bq[t][0], hf);         // h_a * h_b
-            H2_PIN(0x008, 2 * MH);
+            H2_PIN(0x008, 2 * MH * NT);
             __builtin_amdgcn_s_setprio(0);
         }
     }
@@ -257,25 +269,27 @@ struct H2Ops {
     static constexpr bool kScaled = true;
     static constexpr int kWeightBytes = 4;        // two f16 terms
     static constexpr int kTerms = 2;
-    template <int RG>
+    template <int RG, int NT = 1, int NW = 8>
     __device__ static __forceinline__ void tile_gemm(const float* __restrict__ A, int lda, const u32x4* __restrict__ Bpk, int K,
-                                                     int bm, int bn, unsigned char* lds, f32x4 (&acc)[2 * RG][1], int row_limit,
+                                                     int bm, int bn, unsigned char* lds, f32x4 (&acc)[2 * RG][NT], int row_limit,
                                                      float ascale) {
-        h2_tile_gemm<RG>(A, lda, Bpk, K, bm, bn, lds, acc, row_limit, ascale);
+        h2_tile_gemm<RG, NT, NW>(A, lda, Bpk, K, bm, bn, lds, acc, row_limit, ascale);
     }
     __device__ static __forceinline__ float scale_for(float amax) { return h2_scale_for(amax); }
     __device__ static __forceinline__ float pow2_inverse(float s) { return h2_pow2_inverse(s); }
 };
 
-// the conv block / data-gradient kernel for uniform batches (epilogues as gemm_clip_x3_kernel, plus the per-clip scales)
-template <int RG, int EPI>
-__global__ __launch_bounds__(512, RG <= 3 ? 4 : 2) void gemm_clip_h2_kernel(
+// the conv block / data-gradient kernel for uniform batches (epilogues as gemm_clip_x3_kernel, plus the per-clip scales).
+// NT x NW = 1 x 8: 128-column slabs, 512 threads, <= 128 VGPRs for RG <= 3 (two workgroups per CU).  4 x 4 (the wide form,
+// RG <= 3): 256-column slabs, 256 threads at two waves per SIMD (again two workgroups per CU).
+template <int RG, int EPI, int NT = 1, int NW = 8>
+__global__ __launch_bounds__(64 * NW, NT > 1 ? 2 : RG <= 3 ? 4 : 2) void gemm_clip_h2_kernel(
     const float* __restrict__ A, int lda, const u32x4* __restrict__ Bpk, const float* __restrict__ binv,
     const float* __restrict__ amax_in, float* __restrict__ amax_out, const float* __restrict__ bias, float* __restrict__ C, int ldc,
     int Tp, int N, int K, int tiles_n, int ntiles, float* __restrict__ rstd_io, const float* __restrict__ act,
     const u32x4* __restrict__ Lpk, float* __restrict__ zpart, int CL) {
-    conv_block_uniform<H2Ops, RG, EPI>(A, lda, Bpk, binv, amax_in, amax_out, bias, C, ldc, Tp, N, K, tiles_n, ntiles, rstd_io, act,
-                                       Lpk, zpart, CL, 0);
+    conv_block_uniform<H2Ops, RG, EPI, NT, NW>(A, lda, Bpk, binv, amax_in, amax_out, bias, C, ldc, Tp, N, K, tiles_n, ntiles, rstd_io,
+                                               act, Lpk, zpart, CL, 0);
 }
 
 // Ragged batches (as gemm_ragged_x3_kernel): the clip's scale comes from amax_in as in the uniform kernel; the partial maxima
@@ -334,29 +348,46 @@ void launch_ragged_amax(const float* A, int lda, int K, const int* frame_off, co
 bool gemm_clip_h2_supported(int nwm, int N, int K, int lda) {
     return nwm >= 1 && nwm <= 4 && N % 128 == 0 && K % 64 == 0 && K <= 1024 && lda % 4 == 0;
 }
+// the wide form (tile 2 of launch_gemm_clip_h2): clips of at most three 32-row groups (four do not fit the register file: 256
+// VGPRs and 46 spilled in the K loop alone), whole 256-column slabs
+bool gemm_clip_h2_wide_supported(int nwm, int N, int K, int lda) {
+    return gemm_clip_h2_supported(nwm, N, K, lda) && nwm <= 3 && N % kH2WideTile == 0;
+}
 
-// Wave arrangement: 8 waves x 1 tile (128-column slabs, two workgroups per CU).  Measured alternatives on the five launches of
-// an iteration at B = 256 (kernel trace of the launches alone, us): 8 x 1 543; 16 x 1 (256-column slabs, one 1024-thread
+// Wave arrangement.  Two forms, bit-identical (tests/test_gpu_conv_wide_tile.py), chosen once per plan (capi.hip, det_plan):
+//   tile 1   8 waves x 1 column tile (128-column slabs, <= 128 VGPRs, two workgroups per CU).  Per wave and K tile at RG = 3:
+//            36 MFMA, 24 ds_read_b128, 3 LDS stores, 7 global loads, 51 VALU; the A rows of a clip are loaded, split and
+//            staged by N / 128 workgroups.
+//   tile 2   4 waves x 4 column tiles (256-column slabs, the register file spent on 24 accumulators per wave, two waves per
+//            SIMD, two workgroups per CU; RG <= 3).  Per wave and K tile: 144 MFMA, the same 24 ds_read_b128 (twelve MFMAs per
+//            fragment instead of three), 12 LDS stores, 22 global loads; the A work of a clip is done by N / 256
+//            workgroups.
+// Measured alternatives to tile 1 that kept 16 columns per wave or three to four waves per SIMD, on the five launches of an
+// iteration at B = 256 (kernel trace of the launches alone, us): 8 x 1 543; 16 x 1 (256-column slabs, one 1024-thread
 // workgroup per CU: half the A staging per MFMA) 510 -- but no difference inside the embed loop (1.025 vs 1.026 ms per iteration,
 // alternating runs on one box); 8 x 2 (two tiles per wave, 150 VGPRs) 548; the same GEMM on v_mfma_f32_32x32x16_f16 (a wave =
 // all rows x 32 columns: half the MFMA issues, LDS fragment reads and staging per multiply-add, at the 128-VGPR limit) 565;
 // B fragments two K32 steps ahead instead of one: no change; the split arithmetic of a quarter spread behind its MFMAs (two
 // vector instructions per MFMA, sched_group_barrier) instead of ahead of them: +3 % (the scheduler then exposes the fragment
-// reads).  DESIGN.md section 4 has the counters behind this.
+// reads).  DESIGN.md section 4 has the counters behind this and the measurements of tile 2.
 
 // Bpk: launch_h2_pack image of Wt [N][K]; amax_in: [B][64] partial maxima of A's clips (K/16 valid per clip); amax_out: the
 // same for C ([B][64], N/16 written per clip) or null; lastpk / zpart / CL as launch_gemm_clip_x3 (gemm_x3.hip's pack, N / 128
-// partial slabs)
+// partial slabs at either tile).  tile: 1 or 2 (2 only where gemm_clip_h2_wide_supported).
 void launch_gemm_clip_h2(const float* A, int lda, const void* Bpk, const float* amax_in, float* amax_out, const float* bias,
                          float* C, int ldc, int B, int nwm, int Tp, int N, int K, int epi, float* rstd_io, const float* act,
-                         hipStream_t st, const void* lastpk, float* zpart, int CL) {
+                         hipStream_t st, const void* lastpk, float* zpart, int CL, int tile) {
     const float* binv = h2_inv_scale(Bpk, N, K);
     if (epi == X3_FWD && lastpk && zpart) epi = X3_FWD_LAST;
-    const int tn = N / 128;
-#define HK(M_, E_) hipLaunchKernelGGL((gemm_clip_h2_kernel<M_, E_>), dim3(tn * B), dim3(512), 0, st, A, lda, (const u32x4*)Bpk,   \
-                                      binv, amax_in, amax_out, bias, C, ldc, Tp, N, K, tn, tn * B, rstd_io, act,                 \
-                                      (const u32x4*)lastpk, zpart, CL)
-#define HM(E_) switch (nwm) { case 1: HK(1, E_); break; case 2: HK(2, E_); break; case 3: HK(3, E_); break; default: HK(4, E_); break; }
+    const bool wide = tile == 2 && nwm <= 3;
+    const int tn = N / (wide ? kH2WideTile : 128);
+#define HK(M_, E_, NT_, NW_) hipLaunchKernelGGL((gemm_clip_h2_kernel<M_, E_, NT_, NW_>), dim3(tn * B), dim3(64 * NW_), 0, st, A, lda, \
+                                                (const u32x4*)Bpk, binv, amax_in, amax_out, bias, C, ldc, Tp, N, K, tn, tn * B,        \
+                                                rstd_io, act, (const u32x4*)lastpk, zpart, CL)
+#define HM(E_)                                                                                                                 \
+    if (wide) switch (nwm) { case 1: HK(1, E_, 4, 4); break; case 2: HK(2, E_, 4, 4); break; default: HK(3, E_, 4, 4); break; }  \
+    else switch (nwm) { case 1: HK(1, E_, 1, 8); break; case 2: HK(2, E_, 1, 8); break; case 3: HK(3, E_, 1, 8); break;          \
+                        default: HK(4, E_, 1, 8); break; }
     if (epi == X3_FWD) { HM(X3_FWD) } else if (epi == X3_BWD) { HM(X3_BWD) } else if (epi == X3_FWD_LAST) { HM(X3_FWD_LAST) }
     else { HM(X3_PLAIN) }
 #undef HM

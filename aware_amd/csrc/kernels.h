@@ -156,10 +156,13 @@ size_t h2_packed_bytes(int N, int K);
 void launch_h2_pack(const float* Wt_dev, int ldw, int N, int K, void* out, hipStream_t st);   // device -> device
 void launch_clip_amax(const float* A, int lda, int K, int rows_per_clip, int B, float* amax, hipStream_t st);
 bool gemm_clip_h2_supported(int nwm, int N, int K, int lda);
+// the wide form: 4 waves x 64 columns per workgroup (tile = 2 below) instead of 8 waves x 16 (tile = 1); same bits
+constexpr int kH2WideTile = 256;
+bool gemm_clip_h2_wide_supported(int nwm, int N, int K, int lda);
 // amax_in: [B][64] partial maxima of |A| per clip (K/16 valid); amax_out: [B][64] the same of C (N/16 written) or null
 void launch_gemm_clip_h2(const float* A, int lda, const void* Bpk, const float* amax_in, float* amax_out, const float* bias,
                          float* C, int ldc, int B, int nwm, int Tp, int N, int K, int epi, float* rstd_io, const float* act,
-                         hipStream_t st, const void* lastpk = nullptr, float* zpart = nullptr, int CL = 0);
+                         hipStream_t st, const void* lastpk = nullptr, float* zpart = nullptr, int CL = 0, int tile = 1);
 void launch_gemm_ragged_h2(const float* A, int lda, const void* Bpk, const float* amax_in, float* amax_out, const float* bias,
                            float* C, int ldc, int B, const int* frame_off, const int* pool_off, const int* order, int N, int K,
                            int epi, float* rstd_io, const float* act, hipStream_t st);

@@ -18,6 +18,7 @@ SPEC_STRIDE = 256         # floats per band row, narrow layout (a plan's own val
 SPEC_STRIDE_WIDE = 576    # ... wide layout: a band outside bins 1..511 or wider than 256 bins
 FULL_STRIDE = 520
 CONV_PIPES = {"f16x2": 0, "f32": 1, "bf16x3": 2}
+CONV_TILES = {"auto": 0, "narrow": 1, "wide": 2}       # aware_embed_config::conv_tile
 LOSS_KINDS = {"push_extremes": 0, "mse": 1, "hinge": 2, "sign": 3, "push_sigmoid": 4, "ber": 5, "push_extremes_l1": 6}
 
 
@@ -533,22 +534,28 @@ class EmbedSession:
 
     def __init__(self, plan: Plan, det: DetectorWeights, batch: Batch, num_iterations=400, tolerance_db=6.0,
                  loss="push_extremes", lr=0.1, beta1=0.9, beta2=0.999, eps=1e-8, momentum_decay=4e-3,
-                 use_graph=True, conv_pipe="f16x2", fused_readout=True, dsp_path="stream", l1_weight=0.0, mel="taps"):
+                 use_graph=True, conv_pipe="f16x2", fused_readout=True, dsp_path="stream", l1_weight=0.0, mel="taps",
+                 conv_tile="auto"):
         """conv_pipe: "f16x2" (default: conv blocks of chip-filling uniform batches on the f16 matrix pipe, two-term operand
         split, three products -- gemm_h2.hip; everything else as "bf16x3"), "bf16x3" (bf16 matrix pipe, exact three-way operand
         split, six products -- gemm_x3.hip) or "f32" (f32-input MFMA);
         fused_readout=False selects the three-kernel read-out that ragged batches use; dsp_path: "stream" (default:
-        streaming wave kernels) or "staged" (workgroup-staged kernels) for the STFT / iSTFT stages (aware_embed_config)."""
+        streaming wave kernels) or "staged" (workgroup-staged kernels) for the STFT / iSTFT stages (aware_embed_config);
+        conv_tile: the form of the f16 two-term conv kernel -- "auto" (default: chosen per launch by the session's plan), "narrow"
+        (8 waves x 16 columns, 128-column slabs) or "wide" (4 waves x 64 columns, 256-column slabs, wherever it can run; the
+        library refuses a session in which no launch can take it).  The forms give the same bits; conv_tiles() reports them."""
         self.lib = load_library()
         self.plan, self.det, self.batch = plan, det, batch
         if loss not in LOSS_KINDS:
             raise ValueError(f"Unknown loss type: {loss}. Available on the HIP path: {list(LOSS_KINDS)}")
         if conv_pipe not in CONV_PIPES:
             raise ValueError(f"Unknown conv_pipe: {conv_pipe}")
+        if conv_tile not in CONV_TILES:
+            raise ValueError(f"Unknown conv_tile: {conv_tile}")
         self.cfg = EmbedConfig(int(num_iterations), float(tolerance_db), LOSS_KINDS[loss], lr, beta1, beta2, eps,
                                momentum_decay, int(bool(use_graph)), CONV_PIPES[conv_pipe],
                                0 if fused_readout else 1, {"stream": 0, "staged": 1}[dsp_path], float(l1_weight),
-                               {"taps": 0, "dense": 1}[mel])
+                               {"taps": 0, "dense": 1}[mel], CONV_TILES[conv_tile])
         self.nbytes = self.lib.aware_embed_workspace_bytes(batch.h, det.h)
         self.ws = torch.empty(self.nbytes, dtype=torch.uint8, device=_dev())
         h = C.c_void_p()
@@ -563,6 +570,13 @@ class EmbedSession:
                 self.h = None
         except Exception:
             pass
+
+    def conv_tiles(self):
+        """The form of each conv launch of this session (aware_embed_conv_tile): (forward, backward), one entry per conv block:
+        2 = the wide form of the f16 two-term kernel, 1 = its 128-column form, 0 = another kernel / no such launch."""
+        n = len(self.det.channels) - 1
+        return ([int(self.lib.aware_embed_conv_tile(self.h, 0, l)) for l in range(n)],
+                [int(self.lib.aware_embed_conv_tile(self.h, 1, l)) for l in range(n)])
 
     def set_optimizer(self, opt: dict, sched: dict):
         """Any optimiser / scheduler of the reference's registries (embedding.optimizers.get_optimizer /
@@ -775,8 +789,10 @@ def gemm_clip(a: torch.Tensor, bt: torch.Tensor, bias, B: int, Tp: int, epi: int
     return c, rstd
 
 
-def gemm_clip_h2(a: torch.Tensor, bt: torch.Tensor, bias, B: int, Tp: int, epi: int = 0, rstd=None, act=None, w_last=None):
-    """One clip-aligned conv block on the f16 two-term kernel (aware_gemm_clip_h2; the embed loop's default conv pipe).
+def gemm_clip_h2(a: torch.Tensor, bt: torch.Tensor, bias, B: int, Tp: int, epi: int = 0, rstd=None, act=None, w_last=None,
+                 tile: int = 0):
+    """One clip-aligned conv block on the f16 two-term kernel (aware_gemm_clip_h2_tile; the embed loop's default conv pipe).
+    tile: 0 or 1 = the 128-column form, 2 = the wide form (AwareHipError "unsupported" where it cannot run).
     Returns (C, rstd, amax_out[B, 64]) and, with w_last [CL, N] (epi 1), also zpart [N/128, M, CL]."""
     lib = load_library()
     M, K = a.shape
@@ -796,8 +812,9 @@ def gemm_clip_h2(a: torch.Tensor, bt: torch.Tensor, bias, B: int, Tp: int, epi: 
         wl[:CL] = w_last.detach().cpu().float()
         pkl = x3_pack(wl)
         zpart = torch.zeros((N // 128, M, CL), dtype=torch.float32, device=dev)
-    check(lib.aware_gemm_clip_h2(_ptr(a), a.stride(0), _ptr(btd), btd.stride(0), _ptr(bias), _ptr(c), N, B, Tp, N, K, epi, _ptr(rstd),
-                                 _ptr(act), _ptr(pkl), _ptr(zpart), CL, _ptr(amax), _ptr(ws), nbytes, _stream()), "aware_gemm_clip_h2")
+    check(lib.aware_gemm_clip_h2_tile(_ptr(a), a.stride(0), _ptr(btd), btd.stride(0), _ptr(bias), _ptr(c), N, B, Tp, N, K, epi,
+                                      _ptr(rstd), _ptr(act), _ptr(pkl), _ptr(zpart), CL, _ptr(amax), _ptr(ws), nbytes, int(tile),
+                                      _stream()), "aware_gemm_clip_h2_tile")
     torch.cuda.current_stream().synchronize()
     return (c, rstd, amax) if w_last is None else (c, rstd, amax, zpart)
 

@@ -333,6 +333,13 @@ typedef struct aware_embed_config {
      *   [NF][128] x [128][stride] GEMM (the only form of a band with the wide layout)
      *   (what the fused form is tested against). */
     int mel;
+    /* conv_tile (conv_pipe 0, uniform batches): the form of the f16 two-term conv kernel.  0: chosen per launch when the
+     *   session plans its kernels -- the wide form (4 waves x 64 columns per workgroup, 256-column slabs, csrc/gemm_h2.hip) where
+     *   it can run (at most 96 pooled rows per clip, N % 256 == 0) and its grid still fills the chip, else the 128-column form;
+     *   1: the 128-column form everywhere; 2: the wide form wherever it can run (AWARE_E_UNSUPPORTED from aware_embed_create
+     *   when no conv launch of the session can take it).  The forms give the same bits.  (Added at the end of the struct
+     *   without a version step: a caller finds it by the symbol aware_embed_conv_tile.) */
+    int conv_tile;
 } aware_embed_config;
 
 /* ---- optimiser / scheduler registries (the reference's third seam: embedding/optimizers.py:3-20, schedulers.py:3-16) ------
@@ -373,6 +380,10 @@ int aware_embed_create(aware_embed** out, const aware_plan* plan, const aware_de
                        const aware_batch* batch, const aware_embed_config* cfg, void* workspace,
                        size_t workspace_bytes, void* stream);
 void aware_embed_destroy(aware_embed* e);
+/* read-only, for tests and logs: the form the session's plan gives the conv launch of block `layer` (backward 0: the block's
+ * forward, 1: its data-gradient GEMM): 2 = the wide form of the f16 two-term kernel, 1 = its 128-column form, 0 = the launch
+ * runs on another kernel (or does not exist); AWARE_E_BADARG for a layer outside 0 .. n_layers - 1. */
+int aware_embed_conv_tile(const aware_embed* e, int backward, int layer);
 /* analysis, bounds, optimiser reset.  audio: dev ragged f32 (un-normalised); target: dev f32
  * [B][n_bits] bipolar (+-1), PatternEncoder output (utils/watermark/encoder.py:35-45). */
 int aware_embed_begin(aware_embed* e, const float* audio, const float* target, void* stream);
@@ -856,6 +867,13 @@ size_t aware_gemm_clip_h2_workspace_bytes(int B, int N, int K);
 int aware_gemm_clip_h2(const float* A, int lda, const float* Bt, int ldb, const float* bias, float* C, int ldc, int B, int Tp,
                        int N, int K, int epi, float* rstd_io, const float* act, const void* lastpk, float* zpart, int CL,
                        float* amax_out, void* workspace, size_t workspace_bytes, void* stream);
+/* The same with the form of the kernel chosen by the caller, so that a test can hold the two forms against each other on one
+ * set of operands: tile 0 or 1 = 8 waves x 16 columns per workgroup (128-column slabs; what aware_gemm_clip_h2 runs), 2 = the
+ * wide form, 4 waves x 64 columns (256-column slabs).  The two forms give the same bits in C, rstd, amax_out and zpart.
+ * tile 2 needs Tp <= 96 and N % 256 == 0, else AWARE_E_UNSUPPORTED. */
+int aware_gemm_clip_h2_tile(const float* A, int lda, const float* Bt, int ldb, const float* bias, float* C, int ldc, int B,
+                            int Tp, int N, int K, int epi, float* rstd_io, const float* act, const void* lastpk, float* zpart,
+                            int CL, float* amax_out, void* workspace, size_t workspace_bytes, int tile, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,6 @@
 """Clip-aligned conv block: f32-MFMA (mode 0), bf16 three-term / six-product (mode 1), f16 two-term / three-product (h2).
-usage: python tools/clip_h2_bench.py [B] [Tp]  -- column-relative error vs fp64 and microseconds per launch, detector shapes."""
+usage: python tools/clip_h2_bench.py [B] [Tp] [tile]  -- column-relative error vs fp64 and microseconds per launch, detector
+shapes; tile: form of the f16 two-term kernel, 1 = 128-column slabs (default), 2 = wide (256-column slabs; Tp <= 96)."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import ctypes as C
@@ -9,6 +10,7 @@ from aware_amd.runtime import _ptr, _stream, check, load_library
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 256
 Tp = int(sys.argv[2]) if len(sys.argv) > 2 else 94
+tile = int(sys.argv[3]) if len(sys.argv) > 3 else 1
 RP = 32 * ((Tp + 31) // 32)
 g = torch.Generator().manual_seed(1)
 lib = load_library()
@@ -53,13 +55,13 @@ for (N, K, epi) in [(512, 128, 1), (1024, 512, 1), (1024, 1024, 1), (1024, 1024,
         ref = rstd.double()[:, None, :] * (du - du.mean(1, keepdim=True) - u * (du * u).mean(1, keepdim=True))
     scale = ref.abs().amax(dim=(0, 1), keepdim=True).clamp_min(1e-30)
     outs = [rt.gemm_clip(ad, wd, bd, B, Tp, epi, rd.clone(), actd, m, pk)[0] for m in (0, 1)]
-    outs.append(rt.gemm_clip_h2(ad, wd, bd, B, Tp, epi, rd.clone(), actd)[0])
+    outs.append(rt.gemm_clip_h2(ad, wd, bd, B, Tp, epi, rd.clone(), actd, tile=tile)[0])
     errs = [((o.cpu().view(B, RP, N)[:, :Tp].double() - ref).abs() / scale).max().item() for o in outs]
     rms = [(((o.cpu().view(B, RP, N)[:, :Tp].double() - ref) / scale) ** 2).mean().sqrt().item() for o in outs]
     # timing: h2 with the weights packed once and the maxima computed once, as in the embed loop
     nbytes = int(lib.aware_gemm_clip_h2_workspace_bytes(B, N, K))
     t = [bench(lambda: rt.gemm_clip(ad, wd, bd, B, Tp, epi, rd, actd, m, pk)) for m in (0, 1)]
-    t.append(bench(lambda: rt.gemm_clip_h2(ad, wd, bd, B, Tp, epi, rd, actd)))
+    t.append(bench(lambda: rt.gemm_clip_h2(ad, wd, bd, B, Tp, epi, rd, actd, tile=tile)))
     fl = 2.0 * B * Tp * N * K
     print(f"N={N:5d} K={K:5d} epi={epi}  max err f32 {errs[0]:.2e} x3 {errs[1]:.2e} h2 {errs[2]:.2e} | rms {rms[0]:.2e} {rms[1]:.2e} {rms[2]:.2e}"
           f" | us (TF f32-eq): f32 {t[0]:6.1f} ({fl / t[0] / 1e6:5.1f})  x3 {t[1]:6.1f} ({fl / t[1] / 1e6:5.1f})  "

@@ -1,5 +1,6 @@
 """Timing only: the five conv-block launches of one embed iteration on the f16 two-term kernel (B clips of Tp pooled frames).
-usage: AWARE_HIP_LIB=variants/lib_X.so python tools/h2_time.py [B] [Tp] [rounds]"""
+usage: AWARE_HIP_LIB=variants/lib_X.so python tools/h2_time.py [B] [Tp] [rounds] [tile]
+tile: 1 = the 128-column form (default), 2 = the wide form (256-column slabs; Tp <= 96)"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -8,6 +9,7 @@ from aware_amd.runtime import _ptr, _stream, check, load_library
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 256
 Tp = int(sys.argv[2]) if len(sys.argv) > 2 else 94
 rounds = int(sys.argv[3]) if len(sys.argv) > 3 else 5
+tile = int(sys.argv[4]) if len(sys.argv) > 4 else 1
 RP = 32 * ((Tp + 31) // 32)
 lib = load_library()
 g = torch.Generator().manual_seed(1)
@@ -27,8 +29,8 @@ for (N, K, epi) in shapes:
 
 def run(case):
     a, w, bias, act, rstd, c, ws, nb, N, K, epi = case
-    check(lib.aware_gemm_clip_h2(_ptr(a), K, _ptr(w), K, _ptr(bias), _ptr(c), N, B, Tp, N, K, epi, _ptr(rstd), _ptr(act), None, None, 0,
-                                 None, _ptr(ws), nb, _stream()), "h2")
+    check(lib.aware_gemm_clip_h2_tile(_ptr(a), K, _ptr(w), K, _ptr(bias), _ptr(c), N, B, Tp, N, K, epi, _ptr(rstd), _ptr(act), None, None,
+                                      0, None, _ptr(ws), nb, tile, _stream()), "h2")
 
 
 # per-launch kernel time comes from the profiler; here: wall per call incl. the pack + amax pre-pass (constant across variants)
