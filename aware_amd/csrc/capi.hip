@@ -2177,6 +2177,46 @@ extern "C" int aware_speed_views(const float* in, const int* in_off, const int* 
     return AWARE_OK;
 }
 
+// ---- scanning long recordings (EXTENSION; AWAREDetector.scan, runtime.scan_select, runtime.scan_segments, tests) ------------
+// win_off is read on the host: B + 1 window offsets from 0, never falling, at least one window in all
+static bool scan_offsets_ok(const int* win_off, int B) {
+    if (win_off[0] != 0) return false;
+    for (int b = 0; b < B; ++b)
+        if (win_off[b + 1] < win_off[b]) return false;
+    return win_off[B] >= 1;
+}
+
+extern "C" int aware_scan_select(const float* values, const int* win_off, int B, int n_sync, int L, float centre,
+                                 float* win_conf, int* win_view, float* win_values, uint32_t* win_bits, void* stream) {
+    if (!values || !win_off || !win_conf || !win_view || !win_values || !win_bits || values == win_values) return AWARE_E_BADARG;
+    if (B < 1 || n_sync < 1 || n_sync > 64 || L < 1 || L > kScanMaxBits || !std::isfinite(centre)) return AWARE_E_BADARG;
+    if (!scan_offsets_ok(win_off, B)) return AWARE_E_BADARG;
+    launch_scan_select(values, win_off[B], n_sync, L, centre, win_conf, win_view, win_values, win_bits, (hipStream_t)stream);
+    LAUNCHCHK();
+    return AWARE_OK;
+}
+
+extern "C" int aware_scan_segments(const float* win_conf, const int* win_view, const float* win_values, const uint32_t* win_bits,
+                                   const int* win_off, const int* win_off_dev, int B, int L, float centre, float min_confidence,
+                                   int max_flip, int max_segments, int* n_seg, int* seg_first, int* seg_last, int* seg_peak,
+                                   int* seg_view, float* seg_conf, float* seg_values, void* stream) {
+    if (!win_conf || !win_view || !win_values || !win_bits || !win_off || !win_off_dev || !n_seg || !seg_first || !seg_last ||
+        !seg_peak || !seg_view || !seg_conf || !seg_values)
+        return AWARE_E_BADARG;
+    if (B < 1 || L < 1 || L > kScanMaxBits || !std::isfinite(centre) || !std::isfinite(min_confidence) || max_flip < 0 ||
+        max_segments < 1)
+        return AWARE_E_BADARG;
+    if (!scan_offsets_ok(win_off, B)) return AWARE_E_BADARG;
+    ScanSegments S;
+    S.win_conf = win_conf; S.win_view = win_view; S.win_values = win_values; S.win_bits = win_bits; S.win_off = win_off_dev;
+    S.B = B; S.L = L; S.max_flip = max_flip; S.max_segments = max_segments; S.centre = centre; S.min_conf = min_confidence;
+    S.n_seg = n_seg; S.seg_first = seg_first; S.seg_last = seg_last; S.seg_peak = seg_peak; S.seg_view = seg_view;
+    S.seg_conf = seg_conf; S.seg_values = seg_values;
+    launch_scan_segments(S, (hipStream_t)stream);
+    LAUNCHCHK();
+    return AWARE_OK;
+}
+
 // ---- the time stretch alone (EXTENSION; attacks.OverlapAddStretch, tests) -----------------------------------------------------
 extern "C" int aware_stretch_ola(const float* in, const int* in_off, const int* in_len, float* out, const int* out_off,
                                  const int* out_len, int B, int max_len, const int* m, int adjoint, void* stream) {

@@ -596,4 +596,21 @@ void launch_sync_select(const float* values, int B, int n, int L, float centre, 
 void launch_speed_views(const float* in, const int* in_off, const int* in_len, int B, const int* m, int n_views, float* out,
                         const int* out_off, int max_len, hipStream_t st);
 
+// ---- scan_kernels.hip: scanning long recordings (EXTENSION).  launch_scan_select: values [W][n][L] -> per window the
+// confidence, index, row and packed decision bits ([W][ceil(L / 32)]) of the most confident view; one wave per window.
+// launch_scan_segments: per file b (windows win_off[b] .. win_off[b + 1], dev int [B + 1]) the runs of marked windows that
+// agree on their bits; one workgroup per file; the seg_* arrays are [B][max_segments], slots beyond a file's runs untouched
+constexpr int kScanMaxBits = 512;      // L of both kernels: a lane of scan_segments_kernel keeps 512 / 64 sums in registers
+void launch_scan_select(const float* values, int W, int n, int L, float centre, float* win_conf, int* win_view,
+                        float* win_values, unsigned* win_bits, hipStream_t st);
+struct ScanSegments {
+    const float* win_conf = nullptr; const int* win_view = nullptr; const float* win_values = nullptr;
+    const unsigned* win_bits = nullptr; const int* win_off = nullptr;
+    int B = 0, L = 0, max_flip = 0, max_segments = 0;
+    float centre = 0.f, min_conf = 0.f;
+    int* n_seg = nullptr; int* seg_first = nullptr; int* seg_last = nullptr; int* seg_peak = nullptr; int* seg_view = nullptr;
+    float* seg_conf = nullptr; float* seg_values = nullptr;
+};
+void launch_scan_segments(const ScanSegments& S, hipStream_t st);
+
 }  // namespace aware

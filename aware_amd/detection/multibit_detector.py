@@ -3,7 +3,8 @@
 Reference: src/AWARE/detection/multibit_detector.py:9-42 -- normalise, STFT, magnitude, zero the
 bins outside the embedding band, network forward.  Batched entry point: detect_batch.  EXTENSION: sync_search = n reads n views of every clip, 512 / n samples
 apart, and keeps the most confident one (detection/sync.py); off by default.  EXTENSION: speed_search reads every clip at
-candidate playback speeds as well (same module); off by default."""
+candidate playback speeds as well (same module); off by default.  EXTENSION: scan reads a long file in windows and returns the
+marked spans with one payload each (same module); off unless called."""
 from __future__ import annotations
 
 import numpy as np
@@ -18,10 +19,12 @@ from . import sync
 class AWAREDetector(BaseDetector):
     def __init__(self, model, threshold: float = 0.0, frame_length: int = 1024, hop_length: int = 256,
                  window: str = "hann", win_length: int = 1024, pattern_mode: str = "bits2bipolar",
-                 embedding_bands=(500, 4000), sync_search: int = 0, speed_search=None):
+                 embedding_bands=(500, 4000), sync_search: int = 0, speed_search=None, scan=None):
         rt.require_card_geometry("AWAREDetector", frame_length, hop_length, win_length)
         self.sync_search = sync.check_sync_search(sync_search)
         self.speed_search = sync.check_speed_search(speed_search)
+        self.scan_defaults = sync.check_scan_card(scan)           # what scan() uses where its arguments are None
+        self.scan_rows_per_call = sync.SYNC_MAX_ROWS              # rows per aware_detect call of scan()
         self.threshold = threshold
         self.device = torch.device("cuda")
         self.pattern_mode = pattern_mode
@@ -131,6 +134,70 @@ class AWAREDetector(BaseDetector):
                 chosen = torch.zeros(b1 - b0, dtype=torch.int32, device=best.device)
             outs.append((best, chosen.to(torch.int32), md[ispeed.long()], conf))
         return tuple(torch.cat([o[i] for o in outs]) for i in range(4))
+
+    def scan(self, clips, sample_rate: int, window_seconds=None, hop_samples=None, sync_search=None, min_confidence=None,
+             max_flip=None, max_segments=None, return_profile: bool = False):
+        """list of 1-D float arrays (files of any lengths) -> per file the list of its marked spans, in order.  Every file is
+        read in windows of window_seconds (default 1.0) every hop_samples (4096), each at the sync_search views of the offset
+        search (None: the detector's own, or 8 where that is off; an explicit 0 or 1: one view per window, no offsets); a
+        window is marked where the confidence mean |value - centre| of its best view reaches min_confidence (0.06; at 0 or
+        below, windows of confidence 0 are marked and a span of such windows alone has values 0 / 0), and marked neighbours
+        whose bits differ in at most max_flip (n_bits // 4) places form one span; the first max_segments (16) spans of a file are returned.  The four
+        defaults are the detector's scan_defaults (the card key `scan`).  A span is a dict of `start` and `end` (samples: the
+        first window's start, the last window's start plus the window length), `peak` (samples: the most confident window's
+        start plus its view's offset), `confidence` (that window's), `values` [n_bits] float32 (the confidence-weighted mean of
+        the span's windows: decode these) and `windows` (first, last: indices into the profile).  return_profile: (spans,
+        profiles) instead, a profile per file being a dict of `starts` (the window starts), `length` (samples per window),
+        `win_conf`, `win_view` and `win_values` (numpy, per window: the best view's confidence, index and row) and `n_segments` (the true span count, which max_segments may have cut).
+        ValueError, before any launch: a parameter check_scan refuses, a file too short (by its index), speed_search on."""
+        if self.speed_search is not None:
+            raise ValueError("scan: speed_search is on for this detector; scanning at candidate speeds is not supported")
+        d = self.scan_defaults
+        par = sync.check_scan(d["window_seconds"] if window_seconds is None else window_seconds,
+                              d["hop_samples"] if hop_samples is None else hop_samples,
+                              d["min_confidence"] if min_confidence is None else min_confidence,
+                              d["max_segments"] if max_segments is None else max_segments, max_flip, sample_rate)
+        n = (self.sync_search or sync.SCAN_SYNC) if sync_search is None else (sync.check_sync_search(sync_search) or 1)
+        offs = sync.sync_offsets(n)
+        lengths = [len(c) for c in clips]
+        if not lengths:
+            return ([], []) if return_profile else []
+        geometry = [sync.scan_windows(m, par["window"], par["hop_samples"], n, index=b) for b, m in enumerate(lengths)]
+        plan = self._plan(sample_rate)
+        det = self.detection_net.device_weights(plan)
+        if det.n_bits > sync.SCAN_MAX_BITS:
+            raise ValueError(f"scan: payloads of {det.n_bits} bits; at most {sync.SCAN_MAX_BITS}")
+        flip = det.n_bits // 4 if par["max_flip"] is None else par["max_flip"]
+        base = np.concatenate([[0], np.cumsum(lengths)[:-1]]).astype(np.int64)
+        flat = torch.zeros(int(sum(lengths)), dtype=torch.float32, device=self.device)
+        for c, o, m in zip(clips, base, lengths):
+            flat[int(o):int(o) + m] = torch.as_tensor(c, dtype=torch.float32)
+        # the views of all windows share the files' samples: batches with overlapping in_offsets, no copies
+        row_off = [int(o) + s + e for o, (starts, _) in zip(base, geometry) for s in starts for e in offs]
+        row_len = [length for starts, length in geometry for _ in starts for _ in offs]
+        win_off = np.concatenate([[0], np.cumsum([len(starts) for starts, _ in geometry])]).astype(np.int64).tolist()
+        per = max(1, int(self.scan_rows_per_call))
+        vals = torch.cat([rt.detect(plan, det, rt.Batch(row_len[r:r + per], row_off[r:r + per]), flat)
+                          for r in range(0, len(row_off), per)])
+        centre = self._centre()
+        win_values, win_view, win_conf, win_bits = rt.scan_select(vals, win_off, n, centre)
+        seg = rt.scan_segments(win_conf, win_view, win_values, win_bits, win_off, centre, par["min_confidence"], flip,
+                               par["max_segments"])
+        host = {k: v.cpu().numpy() for k, v in seg.items()}
+        conf_h, view_h, rows_h = win_conf.cpu().numpy(), win_view.cpu().numpy(), win_values.cpu().numpy()
+        spans, profiles = [], []
+        for b, (starts, length) in enumerate(geometry):
+            found = []
+            for r in range(min(int(host["n_seg"][b]), par["max_segments"])):
+                first, last, peak = (int(host[k][b, r]) for k in ("first", "last", "peak"))
+                found.append({"start": starts[first], "end": starts[last] + length,
+                              "peak": starts[peak] + offs[int(host["view"][b, r])], "confidence": float(host["confidence"][b, r]),
+                              "values": host["values"][b, r].copy(), "windows": (first, last)})
+            spans.append(found)
+            profiles.append({"starts": list(starts), "length": length, "win_conf": conf_h[win_off[b]:win_off[b + 1]].copy(),
+                             "win_view": view_h[win_off[b]:win_off[b + 1]].copy(),
+                             "win_values": rows_h[win_off[b]:win_off[b + 1]].copy(), "n_segments": int(host["n_seg"][b])})
+        return (spans, profiles) if return_profile else spans
 
     def detect_device(self, audio: torch.Tensor, batch: "rt.Batch", sample_rate: int) -> torch.Tensor:
         plan = self._plan(sample_rate)

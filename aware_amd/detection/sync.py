@@ -163,3 +163,157 @@ def speed_select(values, n_speed: int, n_sync: int = 0, centre: float = 0.0):
     idx_speed * n_sync + idx_sync [B] int32; that mean [B] float32).  It equals two rounds of sync_select, over the sync views
     of every (clip, speed view) and then over the speed views, which is how the device selects."""
     return sync_select(values, int(n_speed) * max(int(n_sync), 1), centre)
+
+
+# ---- scanning long recordings -------------------------------------------------------------------------------------------------------
+# (EXTENSION, DESIGN.md section 28.)  A long file in which only a part is marked reads nothing as a whole.  The scan reads it in
+# windows, every window at the n sync offsets, keeps the most confident view per window (scan_select) and joins marked windows
+# that agree on their bits into runs (scan_segments): one payload per run.  These functions are the specification the device
+# kernels (csrc/scan_kernels.hip, aware_scan_select and aware_scan_segments) are tested against.
+SCAN_WINDOW_SECONDS = 1.0
+SCAN_HOP = 4096
+SCAN_SYNC = 8
+SCAN_MAX_SEGMENTS = 16
+SCAN_MIN_CONFIDENCE = 0.06              # 2.2 x the largest of 76 unmarked windows (0.0270); where a half-overlapping window reads
+SCAN_MAX_BITS = 512                     # L of aware_scan_select / aware_scan_segments
+SCAN_KEYS = ("window_seconds", "hop_samples", "min_confidence", "max_segments")
+
+
+def check_scan(window_seconds=SCAN_WINDOW_SECONDS, hop_samples=SCAN_HOP, min_confidence=SCAN_MIN_CONFIDENCE,
+               max_segments=SCAN_MAX_SEGMENTS, max_flip=None, sample_rate: int = 16000) -> dict:
+    """The scan's parameters, checked: {"window_seconds", "hop_samples", "min_confidence", "max_segments", "max_flip",
+    "window"} with `window` in samples at sample_rate.  ValueError, naming the key, for: a window_seconds that is not a
+    finite number or gives a window of 512 samples or fewer (or of 2^30 or more), a hop_samples that is not a positive
+    multiple of 512, a min_confidence that is not a finite number, a max_segments that is not an integer >= 1, a max_flip
+    that is neither None (n_bits // 4 is then used) nor an integer >= 0."""
+    def number(v, key):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(float(v)):
+            raise ValueError(f"scan: {key} = {v!r}: a finite number is expected")
+        return float(v)
+
+    def integer(v, key, lo):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < lo:
+            raise ValueError(f"scan: {key} = {v!r}: an integer >= {lo} is expected")
+        return int(v)
+
+    ws = number(window_seconds, "window_seconds")
+    window = int(round(ws * int(sample_rate))) if 0.0 < ws * int(sample_rate) < float(1 << 30) else 0
+    if window <= SYNC_PERIOD:
+        raise ValueError(f"scan: window_seconds = {window_seconds!r}: a window of more than {SYNC_PERIOD} and fewer than 2^30 "
+                         f"samples at {int(sample_rate)} Hz is expected")
+    hop = integer(hop_samples, "hop_samples", 1)
+    if hop % SYNC_PERIOD:
+        raise ValueError(f"scan: hop_samples = {hop}: a positive multiple of {SYNC_PERIOD} is expected")
+    return {"window_seconds": ws, "hop_samples": hop, "min_confidence": number(min_confidence, "min_confidence"),
+            "max_segments": integer(max_segments, "max_segments", 1),
+            "max_flip": None if max_flip is None else integer(max_flip, "max_flip", 0), "window": window}
+
+
+def check_scan_card(scan) -> dict:
+    """The card key `scan`: None or {} for the defaults, or a dict with some of SCAN_KEYS -> all four, checked by check_scan.
+    ValueError for anything else, naming the key."""
+    if scan is None:
+        scan = {}
+    if not isinstance(scan, dict):
+        raise ValueError(f"scan = {scan!r}: a mapping with some of the keys {SCAN_KEYS} is expected")
+    unknown = sorted(set(scan) - set(SCAN_KEYS), key=str)
+    if unknown:
+        raise ValueError(f"scan: unknown key {unknown[0]!r}: the keys are {SCAN_KEYS}")
+    checked = check_scan(**scan)
+    return {k: checked[k] for k in SCAN_KEYS}
+
+
+def scan_windows(n_samples: int, window: int, hop: int, n_sync: int, index: int = 0):
+    """(starts, length): the windows of a file of n_samples.  With e_max the largest of sync_offsets(n_sync), windows of
+    `window` samples start at 0, hop, 2 hop, ... while start + e_max + window <= n_samples, and one more at
+    n_samples - window - e_max where that start is not on the grid: view j of a window reads `length` samples from
+    start + e_j.  A file shorter than window + e_max is one window of n_samples - e_max samples.  ValueError for a hop that is
+    no positive multiple of 512, a window of 512 samples or fewer, and, naming the file by `index`, a file with
+    n_samples - e_max <= 512 (the STFT's reflect padding needs more)."""
+    n_samples, window, hop = int(n_samples), int(window), int(hop)
+    e_max = sync_offsets(n_sync)[-1]
+    if hop < 1 or hop % SYNC_PERIOD:
+        raise ValueError(f"scan: hop_samples = {hop}: a positive multiple of {SYNC_PERIOD} is expected")
+    if window <= SYNC_PERIOD:
+        raise ValueError(f"scan: a window of {window} samples: more than {SYNC_PERIOD} are expected")
+    if n_samples - e_max <= SYNC_PERIOD:
+        raise ValueError(f"scan with sync_search = {n_sync}: file {index} has {n_samples} samples; its shortest view "
+                         f"({n_samples - e_max}) needs more than {SYNC_PERIOD}")
+    if n_samples < window + e_max:
+        return [0], n_samples - e_max
+    tail = n_samples - window - e_max
+    starts = list(range(0, tail + 1, hop))
+    if tail % hop:
+        starts.append(tail)
+    return starts, window
+
+
+def pack_bits(bits) -> np.ndarray:
+    """bits [W, L] bool -> [W, ceil(L / 32)] uint32, bit l of a row at bit l % 32 of word l // 32: aware_scan_select's words."""
+    bits = np.asarray(bits, dtype=bool)
+    W, L = bits.shape
+    padded = np.zeros((W, (L + 31) // 32 * 32), dtype=np.uint64)
+    padded[:, :L] = bits
+    return (padded.reshape(W, -1, 32) << np.arange(32, dtype=np.uint64)).sum(axis=2).astype(np.uint32)
+
+
+def scan_select(values, win_off, n_sync: int, centre: float = 0.0):
+    """values [W * n_sync, L] (numpy), window-major, the n_sync views of each of the W = win_off[-1] windows of all files ->
+    (win_values [W, L] float32, win_view [W] int32, win_conf [W] float32, bits [W, L] bool).  Per window,
+    c_j = mean_l |v_jl - centre| as in sync_select, j* the smallest j with the largest c_j, win_conf = c_j*,
+    win_values = v_j*, bits = win_values > centre.  A c_j that is NaN never wins; a window whose c_j are all NaN keeps view 0
+    with win_conf = -1, as aware_sync_select does."""
+    v = np.ascontiguousarray(np.asarray(values), dtype=np.float32)
+    n, W = int(n_sync), int(np.asarray(win_off)[-1])
+    if v.ndim != 2 or n < 1 or W < 1 or v.shape[0] != W * n:
+        raise ValueError(f"scan_select: values [W * n_sync, L] with W = {W} and n_sync = {n} are required; got {v.shape}")
+    L = v.shape[1]
+    v = v.reshape(W, n, L)
+    conf = np.abs(v - np.float32(centre)).mean(axis=-1, dtype=np.float32)           # [W, n]
+    conf = np.where(np.isnan(conf), np.float32(-1.0), conf).astype(np.float32)
+    view = np.argmax(conf, axis=1).astype(np.int32)                                 # the first of equal maxima
+    out = v[np.arange(W), view]
+    return out, view, conf[np.arange(W), view], out > np.float32(centre)
+
+
+def scan_segments(C, V, win_off, centre: float, min_confidence: float, max_flip: int, max_segments: int, view=None,
+                  dtype=np.float32):
+    """Per file b, over its windows win_off[b] .. win_off[b + 1] of C [W] (win_conf) and V [W, L] (win_values): window w is
+    marked where C_w >= min_confidence (a NaN is never marked); it continues the run of w - 1 where both are marked and
+    bits_w = V_w > centre and bits_{w-1} differ in at most max_flip places, and a marked window opens a new run otherwise.
+    -> a list over the files of (the true run count, the first max_segments runs), every run a dict of `first`, `last` and
+    `peak` (window indices inside the file; the peak is the smallest w with the largest C_w), `view` (view[peak] where `view`
+    is given, else 0), `confidence` (C_peak) and `values` [L]:
+
+        values[l] = centre + (sum_w C_w (V_w[l] - centre)) / (sum_w C_w),  both sums in `dtype` over ascending w from zero.
+
+    dtype = np.float64 is the yardstick the float32 sums are held against."""
+    C = np.asarray(C, dtype=np.float32)
+    V = np.asarray(V, dtype=np.float32)
+    off = [int(o) for o in win_off]
+    bits = V > np.float32(centre)
+    ctr = dtype(centre)
+    out = []
+    for b in range(len(off) - 1):
+        runs, count, prev = [], 0, False
+        for w in range(off[b], off[b + 1]):
+            marked = bool(C[w] >= np.float32(min_confidence))
+            if marked and not (prev and int(np.count_nonzero(bits[w] != bits[w - 1])) <= int(max_flip)):
+                count += 1
+                if count <= int(max_segments):
+                    runs.append([w, w])
+            elif marked and count <= int(max_segments):
+                runs[-1][1] = w
+            prev = marked
+        segs = []
+        for first, last in runs:
+            num, den = np.zeros(V.shape[1], dtype=dtype), dtype(0)
+            for w in range(first, last + 1):
+                num = num + dtype(C[w]) * (V[w].astype(dtype) - ctr)
+                den = den + dtype(C[w])
+            peak = first + int(np.argmax(C[first:last + 1]))
+            segs.append({"first": first - off[b], "last": last - off[b], "peak": peak - off[b],
+                         "view": int(view[peak]) if view is not None else 0, "confidence": float(C[peak]),
+                         "values": (ctr + num / den).astype(dtype)})
+        out.append((count, segs))
+    return out

@@ -6,6 +6,7 @@ call into libaware_hip.so on `torch.cuda.current_stream()`.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Sequence
 
 import numpy as np
@@ -1104,6 +1105,73 @@ def sync_select(values: torch.Tensor, n: int, centre: float = 0.0):
     check(load_library().aware_sync_select(_ptr(v), B, n, L, float(centre), _ptr(out), _ptr(idx), _ptr(conf), _stream()),
           "aware_sync_select")
     return out, idx, conf
+
+
+def _scan_offsets(win_off, what: str):
+    """win_off as the C ABI takes it: (host int array [B + 1], B, W); ValueError unless it starts at 0, never falls and
+    holds a window."""
+    off = [int(o) for o in win_off]
+    if len(off) < 2 or off[0] != 0 or off[-1] < 1 or any(b < a for a, b in zip(off, off[1:])):
+        raise ValueError(f"{what}: win_off needs B + 1 window offsets from 0 that never fall, with a window in all; got {off}")
+    return (C.c_int * len(off))(*off), len(off) - 1, off[-1]
+
+
+def scan_select(values: torch.Tensor, win_off, n_sync: int, centre: float = 0.0):
+    """detection.sync.scan_select on the device (aware_scan_select): values [W * n_sync, L] float32, window-major, the
+    n_sync views of each of the W = win_off[-1] windows (win_off: B + 1 host integers, the windows of file b are
+    win_off[b] .. win_off[b + 1]) -> (win_values [W, L] float32, win_view [W] int32, win_conf [W] float32, win_bits
+    [W, ceil(L / 32)] int32: bit l % 32 of word l // 32 is win_values[w][l] > centre)."""
+    n = int(n_sync)
+    arr, B, W = _scan_offsets(win_off, "scan_select")
+    if values.dim() != 2 or not 1 <= n <= 64 or values.shape[0] != W * n or not 1 <= values.shape[1] <= 512:
+        raise ValueError(f"scan_select: values [W * n_sync, L] with W = {W}, n_sync = {n} in 1..64 and L in 1..512 are "
+                         f"required; got {tuple(values.shape)}")
+    v = values.contiguous().float()
+    L = v.shape[1]
+    out = torch.empty((W, L), dtype=torch.float32, device=v.device)
+    view = torch.empty(W, dtype=torch.int32, device=v.device)
+    conf = torch.empty(W, dtype=torch.float32, device=v.device)
+    bits = torch.empty((W, (L + 31) // 32), dtype=torch.int32, device=v.device)
+    check(load_library().aware_scan_select(_ptr(v), arr, B, n, L, float(centre), _ptr(conf), _ptr(view), _ptr(out), _ptr(bits),
+                                           _stream()), "aware_scan_select")
+    return out, view, conf, bits
+
+
+def scan_segments(win_conf: torch.Tensor, win_view: torch.Tensor, win_values: torch.Tensor, win_bits: torch.Tensor, win_off,
+                  centre: float, min_confidence: float, max_flip: int, max_segments: int, out=None):
+    """detection.sync.scan_segments on the device (aware_scan_segments), on scan_select's four results: per file the runs of
+    marked windows that agree on their bits -> {"n_seg" [B] int32: the true run counts; "first", "last", "peak", "view"
+    [B, max_segments] int32 (windows counted from the file's first; the peak window's view); "confidence"
+    [B, max_segments] float32; "values" [B, max_segments, L] float32}.  Slots beyond a file's runs are not written: they
+    hold what `out` (a dict of the same tensors) held, or nothing in particular."""
+    arr, B, W = _scan_offsets(win_off, "scan_segments")
+    S, L = int(max_segments), int(win_values.shape[-1])
+    if (win_values.dim() != 2 or win_values.shape[0] != W or not 1 <= L <= 512 or win_conf.shape != (W,) or win_view.shape != (W,)
+            or win_bits.shape != (W, (L + 31) // 32) or S < 1 or int(max_flip) < 0 or not math.isfinite(float(min_confidence))):
+        raise ValueError(f"scan_segments: scan_select's results for {W} windows, max_segments >= 1, max_flip >= 0 and a finite "
+                         f"min_confidence are required; got values {tuple(win_values.shape)}, max_segments {max_segments}, "
+                         f"max_flip {max_flip}, min_confidence {min_confidence}")
+    dev = win_values.device
+    if out is None:
+        out = {k: torch.empty((B, S), dtype=torch.int32, device=dev) for k in ("first", "last", "peak", "view")}
+        out.update(n_seg=torch.empty(B, dtype=torch.int32, device=dev),
+                   confidence=torch.empty((B, S), dtype=torch.float32, device=dev),
+                   values=torch.empty((B, S, L), dtype=torch.float32, device=dev))
+    shapes = {"n_seg": (B,), "first": (B, S), "last": (B, S), "peak": (B, S), "view": (B, S), "confidence": (B, S),
+              "values": (B, S, L)}
+    for k, shp in shapes.items():
+        t = out[k]
+        if tuple(t.shape) != shp or not t.is_contiguous() or t.device != dev or t.dtype != (
+                torch.float32 if k in ("confidence", "values") else torch.int32):
+            raise ValueError(f"scan_segments: out[{k!r}] needs the shape {shp}, contiguous, on the values' device")
+    tensors = [win_conf.contiguous().float(), win_view.contiguous().int(), win_values.contiguous().float(),
+               win_bits.contiguous().int()]
+    off_dev = torch.tensor(list(arr), dtype=torch.int32, device=dev)
+    check(load_library().aware_scan_segments(*[_ptr(t) for t in tensors], arr, _ptr(off_dev), B, L, float(centre),
+                                             float(min_confidence), int(max_flip), S, _ptr(out["n_seg"]), _ptr(out["first"]),
+                                             _ptr(out["last"]), _ptr(out["peak"]), _ptr(out["view"]), _ptr(out["confidence"]),
+                                             _ptr(out["values"]), _stream()), "aware_scan_segments")
+    return out
 
 
 def speed_views(x: Ragged, ms, out: torch.Tensor | None = None):

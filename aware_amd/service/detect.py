@@ -1,7 +1,8 @@
 """detect_watermark (reference: src/AWARE/service/detect.py:7-55): 16 kHz only, mono 1-D or
 stereo [N,2] (per bit, the channel with the larger |value| wins, :23-37), then PatternDecoder.
 EXTENSION: sync_search = n runs the detector's offset search (detection/sync.py); None keeps the detector's own setting.
-EXTENSION: speed_search runs its speed search (same module), likewise."""
+EXTENSION: speed_search runs its speed search (same module), likewise.
+EXTENSION: scan_watermark reads a long recording in windows and returns its marked spans, one payload each (same module)."""
 import numpy as np
 
 from ..utils.logger import logger
@@ -55,3 +56,64 @@ def detect_watermark_batch(clips, sample_rate: int, detector, sync_search=None, 
     decode = PatternDecoder(encoder_mode=detector.pattern_mode, threshold=detector.threshold)
     vals = _detect(detector, [np.asarray(c, dtype=np.float32) for c in clips], sample_rate, sync_search, speed_search).cpu().numpy()
     return [decode(v) for v in vals]
+
+
+def _scan(detector, files, sample_rate, options):
+    if sample_rate != 16000:
+        logger.error(f"Invalid sample rate. Expected 16000Hz, got {sample_rate}Hz.")
+        raise ValueError("Invalid sample rate. Expected 16000Hz.")
+    decode = PatternDecoder(encoder_mode=detector.pattern_mode, threshold=detector.threshold)
+    found = detector.scan([np.asarray(f, dtype=np.float32) for f in files], sample_rate, **options)
+    return [[{"start": s["start"], "end": s["end"], "peak": s["peak"], "confidence": s["confidence"],
+              "payload": decode(s["values"]), "values": s["values"]} for s in spans] for spans in found]
+
+
+def _scan_stereo(left, right, max_flip: int, centre: float = 0.0):
+    """detect_watermark's rule for the spans of two channels.  A span's counterpart is the span of the other channel that it
+    overlaps by the most samples (the earlier one on a tie).  Two spans that are each other's counterpart and whose bits
+    (values > centre) differ in at most max_flip places, the rule that joins windows into a span, are one span heard twice,
+    and the more confident of the two is kept (the left one on a tie).  Every other span stays, also where it overlaps a span
+    of the other channel: a span is only ever replaced by a counterpart that reads the same payload, so no payload that one
+    channel alone would report is dropped, and the result may hold overlapping spans, as a mono scan of two adjacent clips
+    does.  In order of their starts."""
+    def counterpart(s, others):
+        shared = [min(s["end"], o["end"]) - max(s["start"], o["start"]) for o in others]
+        return int(np.argmax(shared)) if shared and max(shared) > 0 else None
+
+    def same_payload(a, b):
+        return int(np.count_nonzero((np.asarray(a["values"]) > centre) != (np.asarray(b["values"]) > centre))) <= max_flip
+
+    kept, lost = [], set()
+    for j, r in enumerate(right):
+        i = counterpart(r, left)
+        if i is not None and counterpart(left[i], right) == j and same_payload(left[i], r):
+            if r["confidence"] > left[i]["confidence"]:
+                lost.add(i)
+                kept.append(r)
+        else:
+            kept.append(r)
+    kept += [l for i, l in enumerate(left) if i not in lost]
+    return sorted(kept, key=lambda k: (k["start"], k["end"]))
+
+
+def scan_watermark(audio: np.ndarray, sample_rate: int, detector, **options):
+    """The marked spans of a long recording (AWAREDetector.scan; options: its keywords window_seconds, hop_samples,
+    sync_search, min_confidence, max_flip, max_segments): a list of dicts, in order, of `start`, `end` and `peak` (samples),
+    `confidence`, `payload` (the span's values through PatternDecoder) and `values`.  16 kHz only; mono 1-D, or stereo
+    [N, 2]: both channels are scanned, and of two spans, one per channel, that are each other's largest overlap and read
+    the same payload to within max_flip bits the more confident one is kept (_scan_stereo)."""
+    audio = np.asarray(audio)
+    if audio.ndim == 2 and audio.shape[1] == 2:
+        left, right = _scan(detector, [audio[:, 0], audio[:, 1]], sample_rate, options)
+        n_bits = len((left + right)[0]["values"]) if left or right else 0
+        flip = options.get("max_flip")
+        return _scan_stereo(left, right, n_bits // 4 if flip is None else int(flip), detector._centre())
+    if audio.ndim == 1:
+        return _scan(detector, [audio], sample_rate, options)[0]
+    logger.error("Invalid audio shape. Expected 1D or 2D numpy array.")
+    raise ValueError("Invalid audio shape. Expected 1D or 2D numpy array.")
+
+
+def scan_watermark_batch(files, sample_rate: int, detector, **options):
+    """scan_watermark for a list of mono recordings of any lengths, in one scan: a list of span lists."""
+    return _scan(detector, files, sample_rate, options)

@@ -26,7 +26,10 @@ _DETECTOR = {"threshold": ("threshold", 0.0), "pattern_mode": ("pattern_mode", "
              # EXTENSION (detection/sync.py): offset search in detection; absent = off
              "sync_search": ("sync_search", 0),
              # EXTENSION (detection/sync.py): speed search in detection; absent = off
-             "speed_search": ("speed_search", None)}
+             "speed_search": ("speed_search", None),
+             # EXTENSION (detection/sync.py): the defaults of AWAREDetector.scan; absent = window_seconds 1.0,
+             # hop_samples 4096, min_confidence 0.06, max_segments 16
+             "scan": ("scan", None)}
 
 
 def _pick(card: dict, table: dict) -> dict:

@@ -829,6 +829,35 @@ int aware_sync_select(const float* values, int B, int n, int L, float centre, fl
 int aware_speed_views(const float* in, const int* in_off, const int* in_len, int B, const int* m, int n_views, float* out,
                       const int* out_off, int max_len, void* stream);
 
+/* ---- scanning long recordings (EXTENSION, parity unpinned: the reference reads one payload per clip) ----------------------
+ * A file in which only a part is marked reads nothing as a whole.  The host detects every file in windows, window w at the
+ * n_sync views of the offset search (aware_detect on rows with overlapping in_offsets, window-major, file after file), and
+ * these two entries, one launch each on `stream`, read one payload per marked span.  win_off is a HOST int [B + 1]: file b owns
+ * the windows win_off[b] .. win_off[b + 1] - 1 of W = win_off[B]; it starts at 0 and never falls.
+ * aware_scan_select, one wave per window:
+ *   values [W][n_sync][L] f32;  c_j = mean_l |values[w][j][l] - centre| in aware_sync_select's order,
+ *   j* = the smallest j with the largest c_j (a NaN c_j never wins; all NaN: j* = 0 and c = -1);
+ *   win_conf[w] = c_j*, win_view[w] = j*, win_values[w][0 : L] = values[w][j*],
+ *   bit l % 32 of win_bits[w][l / 32] = values[w][j*][l] > centre  (uint32 [W][ceil(L / 32)], the unused bits zero).
+ * aware_scan_segments, one workgroup per file; win_off_dev is the same B + 1 offsets on the device:
+ *   window w is marked where win_conf[w] >= min_confidence (a NaN is never marked); a marked w continues the run of w - 1
+ *   where that is marked too and their bits differ in at most max_flip places, and opens a new run otherwise.
+ *   n_seg[b] = the runs of file b.  For its first max_segments runs r, at [b][r] of the seg_* arrays ([B][max_segments]):
+ *   seg_first, seg_last = the run's first and last window, counted from the file's first; seg_peak = the smallest w of the
+ *   run with the largest win_conf, counted likewise; seg_view = win_view[peak]; seg_conf = win_conf[peak];
+ *   seg_values[b][r][l] = centre + (sum_w win_conf[w] (win_values[w][l] - centre)) / (sum_w win_conf[w]), both sums in f32
+ *   over the run's windows in ascending order, every operation rounded on its own.  Slots beyond a file's runs are not
+ *   written.
+ * AWARE_E_BADARG, before anything is launched: a null pointer, values == win_values, B < 1, n_sync outside 1..64, L outside
+ * 1..512, a centre or min_confidence that is not finite, max_flip < 0, max_segments < 1, a win_off that does not start at 0,
+ * falls, or holds no window.  Added without a version step: callers detect the addition by symbol. */
+int aware_scan_select(const float* values, const int* win_off, int B, int n_sync, int L, float centre, float* win_conf,
+                      int* win_view, float* win_values, uint32_t* win_bits, void* stream);
+int aware_scan_segments(const float* win_conf, const int* win_view, const float* win_values, const uint32_t* win_bits,
+                        const int* win_off, const int* win_off_dev, int B, int L, float centre, float min_confidence,
+                        int max_flip, int max_segments, int* n_seg, int* seg_first, int* seg_last, int* seg_peak,
+                        int* seg_view, float* seg_conf, float* seg_values, void* stream);
+
 /* ---- bare GEMM (tests / roofline): C[M][N] = A[M][K] * Bt[N][K]^T + bias ------------------------------ */
 int aware_gemm_nt(const float* A, int lda, const float* Bt, int ldb, const float* bias, float* C, int ldc,
                   int M, int N, int K, void* stream);
