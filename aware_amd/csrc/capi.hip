@@ -2105,17 +2105,34 @@ extern "C" int aware_reverb_ir(const uint32_t* seeds, int B, int step, int entry
     return AWARE_OK;
 }
 
-// ---- the speed change alone (EXTENSION; attacks.SpeedChange, tests) -------------------------------------------------------
-extern "C" int aware_speed_change(const float* in, const int* in_off, const int* in_len, float* out, const int* out_off,
-                                  const int* out_len, int B, int max_len, const int* m, int adjoint, void* stream) {
+// ---- the in -> out resamplers alone: one argument list, one set of checks; `windowed`: the launch reads stretch_window() ------
+static int resample_alone(void (*launch)(const ResampleLaunch&, hipStream_t), bool windowed, const float* in, const int* in_off,
+                          const int* in_len, float* out, const int* out_off, const int* out_len, int B, int max_len, const int* m,
+                          int adjoint, void* stream) {
     if (!in || !in_off || !in_len || !out || !out_off || !out_len || !m || in == out) return AWARE_E_BADARG;
     if (B < 1 || B > 65535 || max_len < 1 || max_len > (1 << 30) || adjoint < 0 || adjoint > 1) return AWARE_E_BADARG;
-    SpeedLaunch L;
+    ResampleLaunch L;
+    if (windowed && !(L.window = stretch_window())) return AWARE_E_HIP;
     L.in = in; L.out = out; L.B = B; L.adjoint = adjoint; L.max_len = max_len; L.m = m;
     L.x_off = in_off; L.x_len = in_len; L.z_off = out_off; L.z_len = out_len;
-    launch_speed_change(L, (hipStream_t)stream);
+    launch(L, (hipStream_t)stream);
     LAUNCHCHK();
     return AWARE_OK;
+}
+// the speed change (EXTENSION; attacks.SpeedChange, tests)
+extern "C" int aware_speed_change(const float* in, const int* in_off, const int* in_len, float* out, const int* out_off,
+                                  const int* out_len, int B, int max_len, const int* m, int adjoint, void* stream) {
+    return resample_alone(launch_speed_change, false, in, in_off, in_len, out, out_off, out_len, B, max_len, m, adjoint, stream);
+}
+// the time stretch (EXTENSION; attacks.OverlapAddStretch, tests)
+extern "C" int aware_stretch_ola(const float* in, const int* in_off, const int* in_len, float* out, const int* out_off,
+                                 const int* out_len, int B, int max_len, const int* m, int adjoint, void* stream) {
+    return resample_alone(launch_time_stretch, true, in, in_off, in_len, out, out_off, out_len, B, max_len, m, adjoint, stream);
+}
+// the pitch shift (EXTENSION; attacks.OverlapAddPitchShift, tests)
+extern "C" int aware_pitch_shift_ola(const float* in, const int* in_off, const int* in_len, float* out, const int* out_off,
+                                     const int* out_len, int B, int max_len, const int* m, int adjoint, void* stream) {
+    return resample_alone(launch_pitch_shift, true, in, in_off, in_len, out, out_off, out_len, B, max_len, m, adjoint, stream);
 }
 
 // ---- the sample deletion alone (EXTENSION; runtime.delete_samples, tests) --------------------------------------------------
@@ -2213,34 +2230,6 @@ extern "C" int aware_scan_segments(const float* win_conf, const int* win_view, c
     S.n_seg = n_seg; S.seg_first = seg_first; S.seg_last = seg_last; S.seg_peak = seg_peak; S.seg_view = seg_view;
     S.seg_conf = seg_conf; S.seg_values = seg_values;
     launch_scan_segments(S, (hipStream_t)stream);
-    LAUNCHCHK();
-    return AWARE_OK;
-}
-
-// ---- the time stretch alone (EXTENSION; attacks.OverlapAddStretch, tests) -----------------------------------------------------
-extern "C" int aware_stretch_ola(const float* in, const int* in_off, const int* in_len, float* out, const int* out_off,
-                                 const int* out_len, int B, int max_len, const int* m, int adjoint, void* stream) {
-    if (!in || !in_off || !in_len || !out || !out_off || !out_len || !m || in == out) return AWARE_E_BADARG;
-    if (B < 1 || B > 65535 || max_len < 1 || max_len > (1 << 30) || adjoint < 0 || adjoint > 1) return AWARE_E_BADARG;
-    StretchLaunch L;
-    if (!(L.window = stretch_window())) return AWARE_E_HIP;
-    L.in = in; L.out = out; L.B = B; L.adjoint = adjoint; L.max_len = max_len; L.m = m;
-    L.x_off = in_off; L.x_len = in_len; L.z_off = out_off; L.z_len = out_len;
-    launch_time_stretch(L, (hipStream_t)stream);
-    LAUNCHCHK();
-    return AWARE_OK;
-}
-
-// ---- the pitch shift alone (EXTENSION; attacks.OverlapAddPitchShift, tests) ------------------------------------------------
-extern "C" int aware_pitch_shift_ola(const float* in, const int* in_off, const int* in_len, float* out, const int* out_off,
-                                     const int* out_len, int B, int max_len, const int* m, int adjoint, void* stream) {
-    if (!in || !in_off || !in_len || !out || !out_off || !out_len || !m || in == out) return AWARE_E_BADARG;
-    if (B < 1 || B > 65535 || max_len < 1 || max_len > (1 << 30) || adjoint < 0 || adjoint > 1) return AWARE_E_BADARG;
-    PitchLaunch L;
-    if (!(L.window = stretch_window())) return AWARE_E_HIP;
-    L.in = in; L.out = out; L.B = B; L.adjoint = adjoint; L.max_len = max_len; L.m = m;
-    L.x_off = in_off; L.x_len = in_len; L.z_off = out_off; L.z_len = out_len;
-    launch_pitch_shift(L, (hipStream_t)stream);
     LAUNCHCHK();
     return AWARE_OK;
 }
@@ -2363,9 +2352,9 @@ static Launch stage_launch(const aware_embed* e, const LoopChainState& la, const
     S.draw = loop_draw(e, la, step_back, of_pair ? la.pair_speed : la.split);
     return S;
 }
-static SpeedLaunch speed_launch(const aware_embed* e, const LoopChainState& la, const float* in, float* out, int adjoint, int step_back) {
+static ResampleLaunch speed_launch(const aware_embed* e, const LoopChainState& la, const float* in, float* out, int adjoint, int step_back) {
     const bool of_pair = la.pair_speed >= 0;
-    SpeedLaunch S = stage_launch<SpeedLaunch>(e, la, in, out, adjoint, step_back, of_pair);
+    ResampleLaunch S = stage_launch<ResampleLaunch>(e, la, in, out, adjoint, step_back, of_pair);
     S.m_lo = of_pair ? la.lo2 : la.lo; S.m_hi = of_pair ? la.hi2 : la.hi;
     return S;
 }
@@ -2380,9 +2369,8 @@ static FilterLaunch filter_launch(const aware_embed* e, const LoopChainState& la
     return S;
 }
 // the time stretch and the pitch shift: the window and one range of offsets
-template <typename Launch>
-static Launch ola_launch(const aware_embed* e, const LoopChainState& la, const float* in, float* out, int adjoint, int step_back) {
-    Launch S = stage_launch<Launch>(e, la, in, out, adjoint, step_back);
+static ResampleLaunch ola_launch(const aware_embed* e, const LoopChainState& la, const float* in, float* out, int adjoint, int step_back) {
+    ResampleLaunch S = stage_launch<ResampleLaunch>(e, la, in, out, adjoint, step_back);
     S.window = la.hann; S.m_lo = la.lo; S.m_hi = la.hi;
     return S;
 }
@@ -2395,8 +2383,8 @@ static PvLaunch pv_launch(const aware_embed* e, const LoopChainState& la, int st
     P.q_lo = la.lo; P.q_hi = la.hi; P.m_lo = la.lo2; P.m_hi = la.hi2;
     return P;
 }
-static SpeedLaunch pv_speed_launch(const aware_embed* e, const LoopChainState& la, const float* in, float* out, int adjoint, int step_back) {
-    SpeedLaunch S = stage_launch<SpeedLaunch>(e, la, in, out, adjoint, step_back);
+static ResampleLaunch pv_speed_launch(const aware_embed* e, const LoopChainState& la, const float* in, float* out, int adjoint, int step_back) {
+    ResampleLaunch S = stage_launch<ResampleLaunch>(e, la, in, out, adjoint, step_back);
     const bool has_m = la.lo2 <= la.hi2;
     S.m_lo = has_m ? la.lo2 : 0; S.m_hi = has_m ? la.hi2 : 0;      // stretch mode alone: m = 0, the identity
     S.coin = has_m && la.lo <= la.hi;
@@ -2486,11 +2474,11 @@ static void split_forward(const aware_embed* e, const LoopChainState& la, hipStr
         case AWARE_LOOP_TIME_STRETCH: {
             // the overlap-add, and the resampling of a speed change directly behind it through v
             const bool pair = la.pair_speed >= 0;
-            launch_time_stretch(ola_launch<StretchLaunch>(e, la, la.u, pair ? la.v : la.z, 0, 0), st);
+            launch_time_stretch(ola_launch(e, la, la.u, pair ? la.v : la.z, 0, 0), st);
             if (pair) launch_speed_change(speed_launch(e, la, la.v, la.z, 0, 0), st);
             break;
         }
-        case AWARE_LOOP_PITCH_SHIFT: launch_pitch_shift(ola_launch<PitchLaunch>(e, la, la.u, la.z, 0, 0), st); break;
+        case AWARE_LOOP_PITCH_SHIFT: launch_pitch_shift(ola_launch(e, la, la.u, la.z, 0, 0), st); break;
         // gy is free until the synthesis adjoint writes it, and carries the vocoded signal to the resampling
         case AWARE_LOOP_PHASE_VOCODER: pv_stage_forward(e, la, e->gy, st); break;
         case AWARE_LOOP_BAND_FILTER: launch_band_filter(filter_launch(e, la, la.u, la.z, 0), st); break;
@@ -2507,10 +2495,10 @@ static void split_backward(const aware_embed* e, const LoopChainState& la, int s
         case AWARE_LOOP_TIME_STRETCH: {
             const bool pair = la.pair_speed >= 0;
             if (pair) launch_speed_change(speed_launch(e, la, la.u, la.v, 1, step_back), st);
-            launch_time_stretch(ola_launch<StretchLaunch>(e, la, pair ? la.v : la.u, e->gy, 1, step_back), st);
+            launch_time_stretch(ola_launch(e, la, pair ? la.v : la.u, e->gy, 1, step_back), st);
             break;
         }
-        case AWARE_LOOP_PITCH_SHIFT: launch_pitch_shift(ola_launch<PitchLaunch>(e, la, la.u, e->gy, 1, step_back), st); break;
+        case AWARE_LOOP_PITCH_SHIFT: launch_pitch_shift(ola_launch(e, la, la.u, e->gy, 1, step_back), st); break;
         case AWARE_LOOP_PHASE_VOCODER: pv_stage_backward(e, la, step_back, st); break;
         case AWARE_LOOP_BAND_FILTER: launch_band_filter(filter_launch(e, la, la.u, e->gy, step_back), st); break;      // its own adjoint
         default: launch_delete_samples(delete_launch(e, la, la.u, e->gy, 1, step_back), st); break;

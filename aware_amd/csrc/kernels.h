@@ -428,6 +428,11 @@ struct LoopDraw {
     float prob = 0.f;
     LoopGate gate;                        // inside a mixture: the clips that drew this chain
 };
+// the grid of a stage kernel: in the loop one workgroup per synthesis run and clip, stand-alone one per `per_wg` samples of the
+// longest clip (max_len) and clip
+inline dim3 stage_grid(const LoopDraw& d, int B, int max_len, int per_wg) {
+    return dim3(d.frame_off ? (unsigned)d.pstride : (unsigned)((max_len + per_wg - 1) / per_wg), (unsigned)B, 1);
+}
 
 // ---- loop_reverb_kernels.hip: reverberation (EXTENSION): a drawn impulse response per clip and the partitioned FFT
 // convolution that applies it, inside the embed loop (chain kind 2) and stand-alone (aware_convolve, aware_reverb_ir) ----
@@ -459,32 +464,20 @@ struct ConvolveLaunch {
 };
 void launch_convolve(const ConvolveLaunch& L, hipStream_t st);
 
-// ---- loop_speed_kernels.hip: speed change (EXTENSION): Catmull-Rom resampling at a drawn ratio R / 65536, inside the embed
-// loop (chain kind 3) and stand-alone (aware_speed_change), and its adjoint in gather form ------------------------------
-struct SpeedLaunch {
+// ---- loop_speed_kernels.hip, loop_stretch_kernels.hip, loop_pitch_kernels.hip: the in -> out resamplers (EXTENSION), inside
+// the embed loop and stand-alone, each with its adjoint in gather form.  Speed change (chain kind 3, aware_speed_change):
+// Catmull-Rom resampling at a drawn ratio R / 65536.  Time stretch (kind 4, aware_stretch_ola): overlap-add of Hann-windowed
+// segments taken at a drawn rate Q / 65536.  Pitch shift (kind 5, aware_pitch_shift_ola): the speed change at R / 65536 of the
+// stretch at the coupled rate Q = round(2^32 / R), fused (the stretched signal lives in LDS only) ------------------------------
+constexpr int kResampleThreads = 256;     // every thread owns four consecutive outputs
+struct ResampleLaunch {
     const float* in = nullptr; float* out = nullptr;      // never the same buffer
-    int B = 0, adjoint = 0;               // 0: out = z from in = x; 1: out = gx from in = gy
-    // the embed loop (draw.frame_off set): m drawn in the kernel
-    LoopDraw draw;
-    int m_lo = 0, m_hi = 0;
-    int coin = 0;                         // 1: behind a phase vocoder with both modes, m = 0 where the draw's r[2] < 2^31 (stretch mode)
-    // or a ragged batch (draw.frame_off null): x is x_len[b] floats at x_off[b], z is z_len[b] floats at z_off[b], m[b] given
-    const int* x_off = nullptr; const int* x_len = nullptr;
-    const int* z_off = nullptr; const int* z_len = nullptr;
-    int max_len = 0;                      // >= every length written
-    const int* m = nullptr;               // [B]
-};
-void launch_speed_change(const SpeedLaunch& L, hipStream_t st);
-
-// ---- loop_stretch_kernels.hip: time stretch (EXTENSION): overlap-add of Hann-windowed segments taken at a drawn rate
-// Q / 65536, inside the embed loop (chain kind 4) and stand-alone (aware_stretch_ola), and its adjoint in gather form ------
-struct StretchLaunch {
-    const float* in = nullptr; float* out = nullptr;      // never the same buffer
-    const float* window = nullptr;        // stretch_window()
+    const float* window = nullptr;        // stretch_window(); not read by the speed change
     int B = 0, adjoint = 0;               // 0: out = z from in = x; 1: out = gx from in = gz
     // the embed loop (draw.frame_off set): m drawn in the kernel
     LoopDraw draw;
-    int m_lo = 0, m_hi = 0;
+    int m_lo = 0, m_hi = 0;               // the pitch shift's are speed offsets, inside kSpeedMin .. kSpeedMax
+    int coin = 0;                         // read by the speed change only.  1: behind a phase vocoder with both modes, m = 0 where the draw's r[2] < 2^31 (stretch mode)
     // or a ragged batch (draw.frame_off null): x is x_len[b] floats at x_off[b], z is z_len[b] floats at z_off[b], m[b] given
     const int* x_off = nullptr; const int* x_len = nullptr;
     const int* z_off = nullptr; const int* z_len = nullptr;
@@ -494,25 +487,9 @@ struct StretchLaunch {
 // the periodic Hann window of 1024 points in f32 on the current device (uploaded once, outside any stream capture); null
 // when the device refuses
 const float* stretch_window();
-void launch_time_stretch(const StretchLaunch& L, hipStream_t st);
-
-// ---- loop_pitch_kernels.hip: pitch shift (EXTENSION): the speed change at a drawn ratio R / 65536 of the overlap-add stretch
-// at the coupled rate Q = round(2^32 / R), fused (the stretched signal lives in LDS only), inside the embed loop (chain kind 5)
-// and stand-alone (aware_pitch_shift_ola), and its adjoint in gather form --------------------------------------------------
-struct PitchLaunch {
-    const float* in = nullptr; float* out = nullptr;      // never the same buffer
-    const float* window = nullptr;        // stretch_window()
-    int B = 0, adjoint = 0;               // 0: out = z from in = x; 1: out = gx from in = gz
-    // the embed loop (draw.frame_off set): m drawn in the kernel
-    LoopDraw draw;
-    int m_lo = 0, m_hi = 0;    // speed offsets, inside kSpeedMin .. kSpeedMax
-    // or a ragged batch (draw.frame_off null): x is x_len[b] floats at x_off[b], z is z_len[b] floats at z_off[b], m[b] given
-    const int* x_off = nullptr; const int* x_len = nullptr;
-    const int* z_off = nullptr; const int* z_len = nullptr;
-    int max_len = 0;                      // >= every length written
-    const int* m = nullptr;               // [B]
-};
-void launch_pitch_shift(const PitchLaunch& L, hipStream_t st);
+void launch_speed_change(const ResampleLaunch& L, hipStream_t st);
+void launch_time_stretch(const ResampleLaunch& L, hipStream_t st);
+void launch_pitch_shift(const ResampleLaunch& L, hipStream_t st);
 
 // ---- loop_pv_kernels.hip: phase vocoder on the frames of a spectrum (EXTENSION): magnitudes interpolated at the rate
 // Q / 65536, phases accumulated as a product of unit phasors, inside the embed loop (chain kind 6, between the staged STFT and

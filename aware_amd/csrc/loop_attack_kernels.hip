@@ -21,7 +21,7 @@
 #include "common.hpp"
 #include "kernels.h"
 #include "loop_gain.hpp"
-#include "loop_rng.hpp"
+#include "loop_stage.hpp"
 
 namespace aware {
 
@@ -99,7 +99,7 @@ __device__ __forceinline__ ChainState chain_state(const ChainArgs& a, int b, int
             philox4x32_10(0u, step, 1u + (unsigned)j, 1u, seed, 0x5EEDu, r);
             cs.on[j] = loop_entry_fires(r[0], a.prob[j]);
             if (a.kind[j] == kLoopSampleSuppression) {
-                cs.start[j] = (int)(((unsigned long long)r[1] * (unsigned long long)(unsigned)(Ny - a.k[j])) >> 32);
+                cs.start[j] = loop_below(r[1], Ny - a.k[j]);
             } else if (ENV && a.kind[j] == kLoopGainEnvelope) {
                 if (cs.on[j]) {
                     int P, ph;

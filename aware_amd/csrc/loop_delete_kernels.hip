@@ -13,9 +13,7 @@
 // reads 256 consecutive bytes and writes 256 consecutive bytes, whatever k is.  Inside the loop one workgroup works through
 // one synthesis run of a clip (the partition chain_kernel uses); the stand-alone entry runs on a grid over (chunk, clip) at
 // any offset and length.
-#include "common.hpp"
-#include "kernels.h"
-#include "loop_rng.hpp"
+#include "loop_stage.hpp"
 
 namespace aware {
 
@@ -31,20 +29,14 @@ __global__ __launch_bounds__(kDsThreads) void delete_kernel(DeleteLaunch a) {
     float* __restrict__ y;
     int n, i0, i1, start, k;        // the clip's length, this workgroup's samples [i0, i1), the cut [start, start + k)
     if (LOOP) {
-        if (loop_gate_skips(a.draw.gate, b)) return;
-        const int nblk = a.draw.frame_off[b + 1] - a.draw.frame_off[b] - 1;
-        int nseg, jb0, jb1;
-        synth_segment(nblk, blockIdx.x, a.draw.run_blocks, nseg, jb0, jb1);
-        if ((int)blockIdx.x >= nseg) return;
-        const int so = sig_offset(a.draw.frame_off, b);
-        x = a.in + so; y = a.out + so;
-        n = kHop * nblk;
-        i0 = jb0 * kHop; i1 = jb1 * kHop;
-        unsigned r[4];
-        const bool on = loop_entry_draw(a.draw, b, r);
-        k = on ? a.k_lo + (int)(((unsigned long long)r[2] * (unsigned long long)(unsigned)(a.k_hi - a.k_lo + 1)) >> 32) : 0;
+        LoopStage s;
+        if (!loop_stage_enter(a.draw, b, s)) return;
+        x = a.in + s.so; y = a.out + s.so;
+        n = s.n;
+        i0 = s.jb0 * kHop; i1 = s.jb1 * kHop;
+        k = s.on ? loop_uniform(s.r[2], a.k_lo, a.k_hi) : 0;
         k = min(k, n);              // k_hi < Ny is checked where the chain is set
-        start = (on && a.at) ? (int)(((unsigned long long)r[1] * (unsigned long long)(unsigned)(n - k)) >> 32) : 0;
+        start = (s.on && a.at) ? loop_below(s.r[1], n - k) : 0;
     } else {
         n = a.len[b];
         x = a.in + a.off[b]; y = a.out + a.off[b];
@@ -65,12 +57,8 @@ __global__ __launch_bounds__(kDsThreads) void delete_kernel(DeleteLaunch a) {
 }  // namespace
 
 void launch_delete_samples(const DeleteLaunch& L, hipStream_t st) {
-    if (L.draw.frame_off) {
-        hipLaunchKernelGGL(delete_kernel<true>, dim3((unsigned)L.draw.pstride, (unsigned)L.B, 1), dim3(kDsThreads), 0, st, L);
-    } else {
-        const unsigned gx = (unsigned)((L.max_len + kDsChunk - 1) / kDsChunk);
-        hipLaunchKernelGGL(delete_kernel<false>, dim3(gx, (unsigned)L.B, 1), dim3(kDsThreads), 0, st, L);
-    }
+    hipLaunchKernelGGL(L.draw.frame_off ? delete_kernel<true> : delete_kernel<false>, stage_grid(L.draw, L.B, L.max_len, kDsChunk),
+                       dim3(kDsThreads), 0, st, L);
 }
 
 }  // namespace aware

@@ -17,9 +17,7 @@
 // same place in the upper half.  The two share their taps, so each tap is one packed FMA on both: 16 FMAs per three LDS reads
 // (one sample of each half and the broadcast tap).  The window of 8 samples slides through registers.  LDS index q lives at
 // q + (q >> 3): thread t reads 8 t + const, which would put a wave on 8 banks; with the padding its stride is 9.
-#include "common.hpp"
-#include "kernels.h"
-#include "loop_rng.hpp"
+#include "loop_stage.hpp"
 
 namespace aware {
 
@@ -62,25 +60,17 @@ __global__ __launch_bounds__(kFbThreads) void band_filter_kernel(FilterLaunch a)
     float* __restrict__ y;
     int n, i0, i1, response, c1, c2;            // the clip's length, this workgroup's outputs [i0, i1), the filter (response 0: a copy)
     if (LOOP) {
-        if (loop_gate_skips(a.draw.gate, b)) return;
-        const int nblk = a.draw.frame_off[b + 1] - a.draw.frame_off[b] - 1;
-        int nseg, jb0, jb1;
-        synth_segment(nblk, blockIdx.x, a.draw.run_blocks, nseg, jb0, jb1);
-        if ((int)blockIdx.x >= nseg) return;
-        const int so = sig_offset(a.draw.frame_off, b);
-        x = a.in + so; y = a.out + so;
-        n = kHop * nblk;
-        i0 = jb0 * kHop; i1 = jb1 * kHop;
-        unsigned r[4];
-        const bool on = loop_entry_draw(a.draw, b, r);
-        const unsigned span = (unsigned)(a.c_hi - a.c_lo + 1);
-        const int e1 = a.c_lo + (int)(((unsigned long long)r[1] * span) >> 32);
-        const int e2 = a.c_lo + (int)(((unsigned long long)r[2] * span) >> 32);
-        int pick = (int)(((unsigned long long)r[3] * (unsigned)__popc((unsigned)a.mask)) >> 32);
+        LoopStage s;
+        if (!loop_stage_enter(a.draw, b, s)) return;
+        x = a.in + s.so; y = a.out + s.so;
+        n = s.n;
+        i0 = s.jb0 * kHop; i1 = s.jb1 * kHop;
+        const int e1 = loop_uniform(s.r[1], a.c_lo, a.c_hi), e2 = loop_uniform(s.r[2], a.c_lo, a.c_hi);
+        int pick = loop_below(s.r[3], __popc((unsigned)a.mask));
         response = 0;
         for (int bit = 1; bit <= 8; bit <<= 1)
             if (a.mask & bit) { if (pick == 0) response = bit; --pick; }
-        if (!on) response = 0;
+        if (!s.on) response = 0;
         if (response >= 4) { c1 = min(e1, e2); c2 = max(max(e1, e2), c1 + a.w_min); }
         else { c1 = e1; c2 = e1; }
     } else {
@@ -162,12 +152,8 @@ __global__ __launch_bounds__(kFbThreads) void band_filter_kernel(FilterLaunch a)
 }  // namespace
 
 void launch_band_filter(const FilterLaunch& L, hipStream_t st) {
-    if (L.draw.frame_off) {
-        hipLaunchKernelGGL(band_filter_kernel<true>, dim3((unsigned)L.draw.pstride, (unsigned)L.B, 1), dim3(kFbThreads), 0, st, L);
-    } else {
-        const unsigned gx = (unsigned)((L.max_len + kFbTile - 1) / kFbTile);
-        hipLaunchKernelGGL(band_filter_kernel<false>, dim3(gx, (unsigned)L.B, 1), dim3(kFbThreads), 0, st, L);
-    }
+    hipLaunchKernelGGL(L.draw.frame_off ? band_filter_kernel<true> : band_filter_kernel<false>, stage_grid(L.draw, L.B, L.max_len, kFbTile),
+                       dim3(kFbThreads), 0, st, L);
 }
 
 }  // namespace aware

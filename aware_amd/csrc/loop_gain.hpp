@@ -12,7 +12,7 @@
 // correction step give the exact quotient, with no integer division per sample.
 #pragma once
 #include "common.hpp"
-#include "loop_rng.hpp"
+#include "loop_stage.hpp"
 
 namespace aware {
 
@@ -32,8 +32,8 @@ struct EnvBlock {
 
 // P and ph of the entry from its draw r
 __device__ __forceinline__ void envelope_draw(const unsigned (&r)[4], int p_lo, int p_hi, int& P, int& ph) {
-    P = p_lo + (int)(((unsigned long long)r[2] * (unsigned long long)(unsigned)(p_hi - p_lo + 1)) >> 32);
-    ph = (int)(((unsigned long long)r[1] * (unsigned long long)(unsigned)P) >> 32);
+    P = loop_uniform(r[2], p_lo, p_hi);
+    ph = loop_below(r[1], P);
 }
 
 // The table of the workgroup whose first sample is i_first (< 2^31): the threads below kEnvQuads draw four breakpoints each.

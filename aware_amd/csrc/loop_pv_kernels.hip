@@ -21,7 +21,7 @@
 // written after it has been read); it is never G.  P is pulled back to the unit circle by one Newton step per frame.
 #include "common.hpp"
 #include "kernels.h"
-#include "loop_rng.hpp"
+#include "loop_stage.hpp"
 
 namespace aware {
 
@@ -71,9 +71,9 @@ __device__ __forceinline__ bool pv_draw(const PvLaunch& a, int b, int& mq) {
     const bool on = loop_entry_draw(a.draw, b, r);
     const bool has_q = a.q_lo <= a.q_hi, has_m = a.m_lo <= a.m_hi;
     if (has_q && (!has_m || r[2] < 0x80000000u)) {
-        mq = a.q_lo + (int)(((unsigned long long)r[3] * (unsigned long long)(unsigned)(a.q_hi - a.q_lo + 1)) >> 32);
+        mq = loop_uniform(r[3], a.q_lo, a.q_hi);
     } else {
-        const int m = a.m_lo + (int)(((unsigned long long)r[3] * (unsigned long long)(unsigned)(a.m_hi - a.m_lo + 1)) >> 32);
+        const int m = loop_uniform(r[3], a.m_lo, a.m_hi);
         const long long R = 65536 + (long long)m;
         mq = (int)(((1ll << 32) + R / 2) / R) - 65536;
     }

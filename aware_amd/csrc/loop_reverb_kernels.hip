@@ -20,7 +20,7 @@
 #include "common.hpp"
 #include "fft_any.hpp"
 #include "kernels.h"
-#include "loop_rng.hpp"
+#include "loop_stage.hpp"
 
 namespace aware {
 
@@ -39,7 +39,7 @@ __global__ __launch_bounds__(256) void reverb_ir_kernel(ReverbIrLaunch a) {
     unsigned r[4];
     philox4x32_10(0u, step, 1u + j, 1u, seed, 0x5EEDu, r);
     const bool on = loop_entry_fires(r[0], a.prob);
-    const int n_h = a.n_lo + (int)(((unsigned long long)r[2] * (unsigned long long)(unsigned)(a.n_hi - a.n_lo + 1)) >> 32);
+    const int n_h = loop_uniform(r[2], a.n_lo, a.n_hi);
     float* h = a.h + (size_t)b * a.h_stride;
     const double rate = -6.907755278982137 / (double)n_h;       // -ln(1000) / n_h
     double acc = 0.0;

@@ -1,6 +1,6 @@
 // Catmull-Rom interpolation at a 16.16 fixed-point position: the weights and the order of the fused multiply-adds that the
-// speed change (loop_speed_kernels.hip) and the speed search's views (speed_search_kernels.hip) share, so that the two give
-// the same bits.  DESIGN.md sections 17 and 27.
+// speed change (loop_speed_kernels.hip), the pitch shift (loop_pitch_kernels.hip) and the speed search's views
+// (speed_search_kernels.hip) share, so that they give the same bits.  DESIGN.md sections 17, 19 and 27.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -40,6 +40,27 @@ __device__ __forceinline__ float speed_tap(const float* __restrict__ x, int n, l
     const float c = i0 + 1 < n ? x[i0 + 1] : 0.f;
     const float d = i0 + 2 < n ? x[i0 + 2] : 0.f;
     return speed_mix(w, a, b, c, d);
+}
+
+// The transposed resampling in gather form: g[0 .. 3] = gu[j0 .. j0 + 3] from gy[0 .. n_out), u being n samples long; the at
+// most ten inputs that can reach the four, in ascending order
+__device__ __forceinline__ void speed_adjoint4(const float* __restrict__ gy, int n_out, int n, long long R, int j0, float g[4]) {
+    g[0] = g[1] = g[2] = g[3] = 0.f;
+    const long long lo = ((long long)j0 - 2) << 16, plim = (long long)(n - 1) << 16;
+    int i = lo <= 0 ? 0 : (int)(((unsigned long long)lo + (unsigned long long)R - 1ull) / (unsigned long long)R);
+    for (; i < n_out; ++i) {
+        const long long p = (long long)i * R;
+        const int i0 = (int)(p >> 16);
+        if (p > plim || i0 > j0 + 4) break;
+        const SpeedWeights w = speed_weights_at(p);
+        const float v = gy[i];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int t = j0 + e - i0;
+            const float wt = t == -1 ? w.wm1 : (t == 0 ? w.w0 : (t == 1 ? w.w1 : w.w2));
+            if (t >= -1 && t <= 2) g[e] = fmaf(wt, v, g[e]);
+        }
+    }
 }
 
 }  // namespace aware

@@ -997,26 +997,32 @@ def convolve(x: Ragged, h: torch.Tensor, nh: torch.Tensor, adjoint: bool = False
     return out
 
 
-def speed_change(x: Ragged, m, adjoint: bool = False, out_lengths=None) -> Ragged:
-    """Per clip embedding.loop_attacks.speed_change at the speed offsets m (B integers, or one for all): clip b played at
-    (65536 + m[b]) / 65536 of its speed (aware_speed_change), out_lengths[b] samples long (default: the clip's own length).
-    With adjoint, x holds the gradient with respect to that output and the result, out_lengths long, is the gradient with
-    respect to the input (out_lengths is then the forward pass's input lengths)."""
+def _resample_alone(who: str, entry: str, m_lo: int, m_hi: int, what: str, x: Ragged, m, adjoint: bool, out_lengths) -> Ragged:
+    """What speed_change, stretch_ola and pitch_shift_ola share: the checks, the output and the call of the C entry `entry`."""
     lib = load_library()
     ms = [int(m)] * x.B if np.isscalar(m) else [int(v) for v in m]
-    if len(ms) != x.B or any(v < -13520 or v > 17034 for v in ms):
-        raise ValueError(f"speed_change: {x.B} speed offsets within -13520..17034 (-+400 cents) are required; got {ms}")
+    if len(ms) != x.B or any(v < m_lo or v > m_hi for v in ms):
+        raise ValueError(f"{who}: {x.B} {what} are required; got {ms}")
     out_len = x.lengths if out_lengths is None else [int(n) for n in out_lengths]
     if len(out_len) != x.B or min(out_len) < 1:
-        raise ValueError(f"speed_change: {x.B} output lengths >= 1 are required; got {out_len}")
+        raise ValueError(f"{who}: {x.B} output lengths >= 1 are required; got {out_len}")
     xin = x.data if x.data.dtype == torch.float32 else x.data.float()
     out = Ragged(torch.empty(sum(out_len), dtype=torch.float32, device=xin.device), out_len)
     md = torch.tensor(ms, dtype=torch.int32, device=xin.device)
     # the C entry names the two sides of the forward operator: with adjoint, `out` is on the input side
     src, dst = (out, x) if adjoint else (x, out)
-    check(lib.aware_speed_change(_ptr(xin), _ptr(src.d_off), _ptr(src.d_len), _ptr(out.data), _ptr(dst.d_off), _ptr(dst.d_len),
-                                 x.B, max(x.max_len, out.max_len), _ptr(md), int(bool(adjoint)), _stream()), "aware_speed_change")
+    check(getattr(lib, entry)(_ptr(xin), _ptr(src.d_off), _ptr(src.d_len), _ptr(out.data), _ptr(dst.d_off), _ptr(dst.d_len),
+                              x.B, max(x.max_len, out.max_len), _ptr(md), int(bool(adjoint)), _stream()), entry)
     return out
+
+
+def speed_change(x: Ragged, m, adjoint: bool = False, out_lengths=None) -> Ragged:
+    """Per clip embedding.loop_attacks.speed_change at the speed offsets m (B integers, or one for all): clip b played at
+    (65536 + m[b]) / 65536 of its speed (aware_speed_change), out_lengths[b] samples long (default: the clip's own length).
+    With adjoint, x holds the gradient with respect to that output and the result, out_lengths long, is the gradient with
+    respect to the input (out_lengths is then the forward pass's input lengths)."""
+    return _resample_alone("speed_change", "aware_speed_change", -13520, 17034, "speed offsets within -13520..17034 (-+400 cents)",
+                           x, m, adjoint, out_lengths)
 
 
 def delete_samples(x: Ragged, start, k, adjoint: bool = False) -> Ragged:
@@ -1210,21 +1216,8 @@ def stretch_ola(x: Ragged, m, adjoint: bool = False, out_lengths=None) -> Ragged
     the rate (65536 + m[b]) / 65536 by plain overlap-add (aware_stretch_ola), out_lengths[b] samples long (default: the clip's
     own length).  With adjoint, x holds the gradient with respect to that output and the result, out_lengths long, is the
     gradient with respect to the input (out_lengths is then the forward pass's input lengths)."""
-    lib = load_library()
-    ms = [int(m)] * x.B if np.isscalar(m) else [int(v) for v in m]
-    if len(ms) != x.B or any(v < -16384 or v > 21845 for v in ms):
-        raise ValueError(f"stretch_ola: {x.B} offsets within -16384..21845 (rates 0.75 to 4/3) are required; got {ms}")
-    out_len = x.lengths if out_lengths is None else [int(n) for n in out_lengths]
-    if len(out_len) != x.B or min(out_len) < 1:
-        raise ValueError(f"stretch_ola: {x.B} output lengths >= 1 are required; got {out_len}")
-    xin = x.data if x.data.dtype == torch.float32 else x.data.float()
-    out = Ragged(torch.empty(sum(out_len), dtype=torch.float32, device=xin.device), out_len)
-    md = torch.tensor(ms, dtype=torch.int32, device=xin.device)
-    # the C entry names the two sides of the forward operator: with adjoint, `out` is on the input side
-    src, dst = (out, x) if adjoint else (x, out)
-    check(lib.aware_stretch_ola(_ptr(xin), _ptr(src.d_off), _ptr(src.d_len), _ptr(out.data), _ptr(dst.d_off), _ptr(dst.d_len),
-                                x.B, max(x.max_len, out.max_len), _ptr(md), int(bool(adjoint)), _stream()), "aware_stretch_ola")
-    return out
+    return _resample_alone("stretch_ola", "aware_stretch_ola", -16384, 21845, "offsets within -16384..21845 (rates 0.75 to 4/3)",
+                           x, m, adjoint, out_lengths)
 
 
 def pitch_shift_ola(x: Ragged, m, adjoint: bool = False, out_lengths=None) -> Ragged:
@@ -1233,21 +1226,8 @@ def pitch_shift_ola(x: Ragged, m, adjoint: bool = False, out_lengths=None) -> Ra
     resampling in one launch (aware_pitch_shift_ola), out_lengths[b] samples long (default: the clip's own length).  With
     adjoint, x holds the gradient with respect to that output and the result, out_lengths long, is the gradient with respect to
     the input (out_lengths is then the forward pass's input lengths)."""
-    lib = load_library()
-    ms = [int(m)] * x.B if np.isscalar(m) else [int(v) for v in m]
-    if len(ms) != x.B or any(v < -13520 or v > 17034 for v in ms):
-        raise ValueError(f"pitch_shift_ola: {x.B} speed offsets within -13520..17034 (-+400 cents) are required; got {ms}")
-    out_len = x.lengths if out_lengths is None else [int(n) for n in out_lengths]
-    if len(out_len) != x.B or min(out_len) < 1:
-        raise ValueError(f"pitch_shift_ola: {x.B} output lengths >= 1 are required; got {out_len}")
-    xin = x.data if x.data.dtype == torch.float32 else x.data.float()
-    out = Ragged(torch.empty(sum(out_len), dtype=torch.float32, device=xin.device), out_len)
-    md = torch.tensor(ms, dtype=torch.int32, device=xin.device)
-    # the C entry names the two sides of the forward operator: with adjoint, `out` is on the input side
-    src, dst = (out, x) if adjoint else (x, out)
-    check(lib.aware_pitch_shift_ola(_ptr(xin), _ptr(src.d_off), _ptr(src.d_len), _ptr(out.data), _ptr(dst.d_off), _ptr(dst.d_len),
-                                    x.B, max(x.max_len, out.max_len), _ptr(md), int(bool(adjoint)), _stream()), "aware_pitch_shift_ola")
-    return out
+    return _resample_alone("pitch_shift_ola", "aware_pitch_shift_ola", -13520, 17034, "speed offsets within -13520..17034 (-+400 cents)",
+                           x, m, adjoint, out_lengths)
 
 
 PV_MQ_MIN, PV_MQ_MAX = -16384, 21845       # the stretch's range: ceil / floor of 65536 (0.75 - 1) and 65536 (4 / 3 - 1)

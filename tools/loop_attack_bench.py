@@ -92,7 +92,7 @@ MIXTURES = {
 
 
 def dump(emb, path, names=("both", "pitch"), lengths=None, iters=20):
-    """sha256 of what `iters` iterations of a handle leave, per entry of `names` (a chain of VARIANTS, or a mixture of MIXTURES,
+    """sha256 of what `iters` iterations of a handle leave, per entry of `names` (a chain of VARIANTS or FILTER_VARIANTS, or a mixture of MIXTURES,
     which is set through emb.loop_attack_mixture), on ten 1 s clips or a ragged batch of `lengths`; written to `path` unless it
     is empty."""
     import hashlib
@@ -102,13 +102,46 @@ def dump(emb, path, names=("both", "pitch"), lengths=None, iters=20):
     target = torch.randint(0, 2, (len(lengths), 20), generator=g, device="cuda").float() * 2 - 1
     batch = rt.Batch(lengths)
     out = {}
+    chains = {**VARIANTS, **FILTER_VARIANTS}
     for name in names:
-        emb.loop_attacks, emb.loop_attack_mixture = (VARIANTS[name], []) if name in VARIANTS else ([], MIXTURES[name])
+        emb.loop_attacks, emb.loop_attack_mixture = (chains[name], []) if name in chains else ([], MIXTURES[name])
         sess = emb.start_session(batch, 16000)
         sess.begin(audio, target)
         sess.iterate(iters)
         parts = {"coef": sess.coef, "best": sess.best_coef, "loss": sess.loss, "best_loss": sess.best_loss, "out": sess.finish(None)}
         out[name] = {k: hashlib.sha256(v.detach().cpu().numpy().tobytes()).hexdigest() for k, v in parts.items()}
+    if path:
+        with open(path, "w") as f:
+            json.dump(out, f, indent=1, sort_keys=True)
+    return out
+
+
+def dump_alone(path=""):
+    """sha256 of what the stand-alone entries of the loop's stage kernels write, by case name, on two clips of 4099 and 7937
+    samples packed back to back (an odd second offset, several workgroups per clip), inputs from numpy with fixed seeds: the
+    three resamplers forward and adjoint at same-length and true-length outputs, the sample deletion in both directions, and
+    the band filter's four responses with their taps; written to `path` unless it is empty."""
+    import hashlib
+    from aware_amd.embedding.loop_attacks import speed_length
+    lengths = [4099, 7937]
+    rng = np.random.default_rng(17)
+    x = rt.Ragged.from_list([rng.standard_normal(n).astype(np.float32) for n in lengths])
+    sha = lambda t: hashlib.sha256(t.detach().cpu().numpy().tobytes()).hexdigest()
+    out = {}
+    for name, fn, ms in (("speed_change", rt.speed_change, (-13520, 17034, -1, 0, 1, 3000)),
+                         ("pitch_shift_ola", rt.pitch_shift_ola, (-13520, 17034, -1, 0, 1, 3000)),
+                         ("stretch_ola", rt.stretch_ola, (-16384, 21845, -1, 0, 1, 3000))):
+        for m in ms:
+            for which, z_len in (("same", lengths), ("true", [speed_length(n, m) for n in lengths])):
+                g = rt.Ragged.from_list([np.random.default_rng(m % 1000 + b).standard_normal(n).astype(np.float32) for b, n in enumerate(z_len)])
+                out[f"{name}/m={m}/{which}/forward"] = sha(fn(x, m, out_lengths=z_len).data)
+                out[f"{name}/m={m}/{which}/adjoint"] = sha(fn(g, m, adjoint=True, out_lengths=lengths).data)
+    for start, k in (([0, 0], 0), ([0, 0], 512), ([1000, 1000], 333), ([n - 7 for n in lengths], 7)):
+        for adjoint in (False, True):
+            out[f"delete_samples/start={start[0]}/k={k}/{'adjoint' if adjoint else 'forward'}"] = sha(rt.delete_samples(x, start, k, adjoint=adjoint).data)
+    for response in (1, 2, 4, 8):
+        z, taps = rt.band_filter(x, response, 2458, 15565, return_taps=True)
+        out[f"band_filter/response={response}/out"], out[f"band_filter/response={response}/taps"] = sha(z.data), sha(taps)
     if path:
         with open(path, "w") as f:
             json.dump(out, f, indent=1, sort_keys=True)
