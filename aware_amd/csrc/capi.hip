@@ -1125,7 +1125,7 @@ static int h2_conv_tile(int conv_tile, int B, int nwm, int N, int K) {
 enum class MelFwd : unsigned char {
     Folded,   // the analysis kernel left the raw mel tile in xm: the norms and pooling only
     Front,    // mel GEMM, norms and pooling in one launch (launch_mel_front_x3)
-    Gemm,     // mel GEMM, then the norms and pooling (the 128-band kernels or the any-bank form)
+    Gemm,     // mel GEMM, then the norms and pooling (launch_mel_norm_fwd)
 };
 // a conv block's forward (GEMM + norm + activation), or its data-gradient GEMM with the previous block's norm and activation
 // backward fused in where the kind is not Plain
@@ -1150,7 +1150,6 @@ struct DetPlan {
     int pipe = 0, nwm = 0;    // conv pipe (aware_embed_config::conv_pipe); clip_tile_groups
     MelFwd mel = MelFwd::Gemm;
     bool mel_amax = false;    // the mel kernel is handed amax[0]
-    bool mel_any = false;     // not 128 bands: the any-bank norm kernels
     bool mag_grad = true;     // the backward ends with the GEMM to dL/d|S| (else the caller expands dL/d(mel) itself)
     int n_fwd = 0;            // blocks the forward runs (the fused read-out computes the last one itself)
     int top = 0;              // first block the backward loop differentiates
@@ -1186,7 +1185,6 @@ static DetPlan det_plan(const aware_detector* d, const aware_batch* b, int pipe,
                            mel_front_x3_supported(b->T[0], d->stride, d->stride);
     p.mel = mel_folded ? MelFwd::Folded : mel_front ? MelFwd::Front : MelFwd::Gemm;
     p.mel_amax = p.mel == MelFwd::Front || (p.mel == MelFwd::Folded && pipe == 0 && nwm);
-    p.mel_any = d->n_mels != 128;
     p.mag_grad = !mel_grad_only;
     // one kernel for the last conv block, the BRH head, the loss, their backward and the data gradient of the last conv
     // (uniform batches, bf16x3 configuration); otherwise split-K GEMM + tail kernel + data-gradient GEMM
@@ -1264,21 +1262,16 @@ static DetPlan det_plan(const aware_detector* d, const aware_batch* b, int pipe,
 static int det_forward(const aware_detector* d, const aware_batch* b, const DetPlan& p, const float* mag, DetBufs& o,
                        hipStream_t st) {
     const int nl = d->n_layers, Mp = d->ch[0];
-    if (p.mel == MelFwd::Folded) {
-        launch_mel_norm_fwd(o.xm, b->d_frame_off, b->d_pool_off, o.x0, o.mstats, o.gstat, o.mpart, o.mstride, b->B, b->max_frames,
-                            st, p.mel_amax ? o.amax[0] : nullptr);
-    } else if (p.mel == MelFwd::Front) {
+    if (p.mel == MelFwd::Front) {
         launch_mel_front_x3(mag, d->stride, d->melTpk, b->d_frame_off, b->d_pool_off, o.xm, o.x0, o.mstats, o.gstat, b->B, b->T[0],
                             d->stride, st, o.amax[0]);
     } else {
-        gemm_plain(p.pipe, mag, d->stride, d->melT, d->stride, d->melTpk, nullptr, o.xm, Mp, b->NF, Mp, d->stride, st);
-        LAUNCHCHK(); PROF(K_GEMM);
-        if (p.mel_any)
-            launch_mel_norm_fwd_any(o.xm, b->d_frame_off, b->d_pool_off, o.x0, o.mstats, o.gstat, o.mpart, o.mstride, b->B,
-                                    b->max_frames, d->n_mels, Mp, st);
-        else
-            launch_mel_norm_fwd(o.xm, b->d_frame_off, b->d_pool_off, o.x0, o.mstats, o.gstat, o.mpart, o.mstride, b->B,
-                                b->max_frames, st);
+        if (p.mel == MelFwd::Gemm) {
+            gemm_plain(p.pipe, mag, d->stride, d->melT, d->stride, d->melTpk, nullptr, o.xm, Mp, b->NF, Mp, d->stride, st);
+            LAUNCHCHK(); PROF(K_GEMM);
+        }
+        launch_mel_norm_fwd(o.xm, b->d_frame_off, b->d_pool_off, o.x0, o.mstats, o.gstat, o.mpart, o.mstride, b->B, b->max_frames,
+                            d->n_mels, Mp, st, p.mel_amax ? o.amax[0] : nullptr);
     }
     LAUNCHCHK(); PROF(K_MELNORM);
     const float* x = o.x0;
@@ -1545,12 +1538,8 @@ static int det_forward_backward(const aware_detector* d, const aware_batch* b, c
     }
     const int Mp = d->ch[0];
     if (p.bwd[0] != Conv::MelBack) {
-        if (p.mel_any)
-            launch_mel_norm_bwd_any(dA, db.xm, b->d_frame_off, b->d_pool_off, db.mstats, db.gstat, db.mpart, db.mstride, b->B,
-                                    b->max_frames, d->n_mels, Mp, st);
-        else
-            launch_mel_norm_bwd(dA, db.xm, b->d_frame_off, b->d_pool_off, db.mstats, db.gstat, db.mpart, db.mstride, b->B,
-                                b->max_frames, st);
+        launch_mel_norm_bwd(dA, db.xm, b->d_frame_off, b->d_pool_off, db.mstats, db.gstat, db.mpart, db.mstride, b->B,
+                            b->max_frames, d->n_mels, Mp, st);
         LAUNCHCHK(); PROF(K_MELNORM);
     }
     if (p.mag_grad) {

@@ -18,6 +18,7 @@
 
 #include "common.hpp"
 #include "kernels.h"
+#include "mel_norm.hpp"
 
 namespace aware {
 
@@ -540,223 +541,272 @@ void launch_gemm_nt(const float* A, int lda, const float* Bt, int ldb, const flo
 }
 
 // ---------------------------------------------------------------------------------
-// block reductions (256 threads)
+// block reductions
 // ---------------------------------------------------------------------------------
-__device__ __forceinline__ float block_sum(float v, float* red) {
+// every wave's sum of v into red[wave]
+__device__ __forceinline__ void wave_partials(float v, float* red) {
     v = wave_sum(v);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();
+}
+// 256 threads (the four partials in sequence: the pairwise order of mel_sum8 would change the bits of every caller)
+__device__ __forceinline__ float block_sum(float v, float* red) {
+    wave_partials(v, red);
     return red[0] + red[1] + red[2] + red[3];
+}
+// 512 threads
+__device__ __forceinline__ float mel_block_sum(float v, float* red8) {
+    wave_partials(v, red8);
+    return mel_sum8(red8);
 }
 
 // ---------------------------------------------------------------------------------
-// mel block: InstanceNorm1d(128) over time -> GlobalStandardize (per clip, unbiased
-// std) -> AvgPool1d(2,2), and its backward.  Time is cut into 32-frame chunks so that
-// B * ceil(T/32) workgroups share the work; per-channel statistics are produced as
-// per-chunk (count, mean, M2) partials and merged with Chan's formula by every consumer
-// workgroup in fixed order (deterministic, no atomics).
+// mel block (the maths: mel_norm.hpp), chunked form, for clips longer than kMelClipFrames.  Time is cut into 32-frame chunks
+// so that B * ceil(T/32) workgroups share the work; per-channel statistics are produced as per-chunk (count, mean, M2)
+// partials and merged with Chan's formula by every consumer workgroup in fixed order (deterministic, no atomics).
+// Partials [B][pstride][2 Mp] = {mean | D1, M2 | D2} per chunk.
 //
-// With u = (x - mu_c) * rs_c the per-channel sums are  sum_t u = 0  and
-// sum_t u^2 = rs_c^2 * M2_c  exactly, so the clip-wide mean of u is taken as 0 (the
-// reference evaluates a rounding residue of order 1e-9 there, globalStandardize.py:17)
-// and its unbiased std follows from the per-channel M2.
-// stats[b][c] = {mu, rs, M2, -};  gstat[b] = {1/(s+1e-8), s, n, T}
+// One family for every bank of n_mels <= 512 bands in rows of Mp >= n_mels floats (Mp a multiple of 4; stored_channels in
+// capi.hip): channels are taken in groups of 128 (thread c of a group: channel 128 j + c, row group g: every second row), and
+// the clip-wide GlobalStandardize sum runs over the n_mels real channels only.  Padding channels n_mels .. Mp-1 get zero
+// statistics, zero x0 columns and zero dL/dxm.  MelBank128 makes the card's 128 bands, pitch and single group compile-time
+// constants; MelBankAny takes them at run time.  Row loops have a fixed trip count, loads first (clamped indices), stores
+// masked: no per-iteration load/wait chain.
 // ---------------------------------------------------------------------------------
-constexpr int kMelChunk = 32;
+struct MelBank128 {
+    static constexpr int kGroups = 1;
+    static constexpr int n_mels = 128, Mp = 128, ng = 1;
+    __device__ MelBank128(int, int) {}
+};
+struct MelBankAny {
+    static constexpr int kGroups = 4;               // 128-channel groups: Mp <= 512
+    int n_mels, Mp, ng;
+    __device__ MelBankAny(int n_mels_, int Mp_) : n_mels(n_mels_), Mp(Mp_), ng((Mp_ + 127) / 128) {}
+};
 
+// per-chunk (mean, M2) of every channel
+template <class Bank>
 __global__ __launch_bounds__(256) void mel_partial_stats_kernel(const float* __restrict__ xm, const int* __restrict__ frame_off,
-                                                                 float* __restrict__ part, int pstride) {
+                                                                 float* __restrict__ part, int pstride, int n_mels, int Mp) {
     __shared__ float s1[2][128];
+    const Bank bk(n_mels, Mp);
     const int b = blockIdx.y;
     const int f0 = frame_off[b], T = frame_off[b + 1] - f0;
     const int t0 = blockIdx.x * kMelChunk;
     if (t0 >= T) return;
     const int nt = min(kMelChunk, T - t0);
     const int c = threadIdx.x & 127, g = threadIdx.x >> 7;
-    const float* x = xm + (size_t)(f0 + t0) * 128 + c;
-    float v[kMelChunk / 2];
-    float a = 0.f;
+    float* o = part + ((size_t)b * pstride + blockIdx.x) * 2 * bk.Mp;
+    for (int j = 0; j < bk.ng; ++j) {
+        const int ch = 128 * j + c;
+        const bool on = ch < bk.n_mels;
+        const float* x = xm + (size_t)(f0 + t0) * bk.Mp + min(ch, bk.n_mels - 1);
+        float v[kMelChunk / 2];
+        float a = 0.f;
 #pragma unroll
-    for (int i = 0; i < kMelChunk / 2; ++i) {
-        const int t = 2 * i + g;
-        v[i] = (t < nt) ? x[(size_t)t * 128] : 0.f;
-        a += v[i];
-    }
-    s1[g][c] = a;
-    __syncthreads();
-    const float mean = (s1[0][c] + s1[1][c]) / (float)nt;
-    __syncthreads();
-    float q = 0.f;
+        for (int i = 0; i < kMelChunk / 2; ++i) {
+            const int t = 2 * i + g;
+            v[i] = (t < nt) ? x[(size_t)t * bk.Mp] : 0.f;
+            a += v[i];
+        }
+        s1[g][c] = a;
+        __syncthreads();
+        const float mean = (s1[0][c] + s1[1][c]) / (float)nt;
+        __syncthreads();
+        float q = 0.f;
 #pragma unroll
-    for (int i = 0; i < kMelChunk / 2; ++i) {
-        const int t = 2 * i + g;
-        if (t < nt) { float d = v[i] - mean; q += d * d; }
-    }
-    s1[g][c] = q;
-    __syncthreads();
-    if (g == 0) {
-        float* o = part + ((size_t)b * pstride + blockIdx.x) * 256;
-        o[c] = mean;
-        o[128 + c] = s1[0][c] + s1[1][c];
+        for (int i = 0; i < kMelChunk / 2; ++i) {
+            const int t = 2 * i + g;
+            if (t < nt) { float d = v[i] - mean; q += d * d; }
+        }
+        s1[g][c] = q;
+        __syncthreads();
+        if (g == 0 && ch < bk.Mp) {
+            o[ch] = on ? mean : 0.f;
+            o[bk.Mp + ch] = on ? s1[0][c] + s1[1][c] : 0.f;
+        }
+        if (Bank::kGroups > 1) __syncthreads();
     }
 }
 
-// merge the chunk partials of channel c (all threads with the same c get the same result)
-__device__ __forceinline__ void mel_merge(const float* __restrict__ part, int nchunk, int T, int c, float& mean, float& M2) {
-    float n = 0.f;
-    mean = 0.f; M2 = 0.f;
-    for (int k = 0; k < nchunk; ++k) {
-        const float nk = (float)min(kMelChunk, T - k * kMelChunk);
-        const float mk = part[(size_t)k * 256 + c], qk = part[(size_t)k * 256 + 128 + c];
-        const float d = mk - mean, nn = n + nk;
-        mean += d * (nk / nn);
-        M2 += qk + d * d * (n * nk / nn);
-        n = nn;
-    }
-}
-
+template <class Bank>
 __global__ __launch_bounds__(256) void mel_apply_pool_kernel(const float* __restrict__ xm, const int* __restrict__ frame_off,
                                                               const int* __restrict__ pool_off, const float* __restrict__ part,
                                                               int pstride, float* __restrict__ x0, float* __restrict__ stats,
-                                                              float* __restrict__ gstat) {
+                                                              float* __restrict__ gstat, int n_mels, int Mp) {
     __shared__ float red[4];
+    const Bank bk(n_mels, Mp);
     const int b = blockIdx.y;
     const int f0 = frame_off[b], T = frame_off[b + 1] - f0;
     const int t0 = blockIdx.x * kMelChunk;
     if (t0 >= T) return;
     const int nchunk = (T + kMelChunk - 1) / kMelChunk;
     const int c = threadIdx.x & 127, g = threadIdx.x >> 7;
-    float mu, M2;
-    mel_merge(part + (size_t)b * pstride * 256, nchunk, T, c, mu, M2);
-    const float rs = 1.0f / sqrtf(M2 / (float)T + 1e-5f);            // biased var, eps 1e-5
-    float suu = (g == 0) ? rs * rs * M2 : 0.f;
-    suu = block_sum(suu, red);
-    const float n = (float)T * 128.f;
-    const float gs = sqrtf(suu / (n - 1.f));                          // unbiased std of u (mean 0)
-    const float ginv = 1.0f / (gs + 1e-8f);
-    if (blockIdx.x == 0) {
-        if (g == 0) { float* st = stats + ((size_t)b * 128 + c) * 4; st[0] = mu; st[1] = rs; st[2] = M2; st[3] = 0.f; }
-        if (threadIdx.x == 0) { gstat[b * 4 + 0] = ginv; gstat[b * 4 + 1] = gs; gstat[b * 4 + 2] = n; gstat[b * 4 + 3] = (float)T; }
+    const float* pp = part + (size_t)b * pstride * 2 * bk.Mp;
+    float mus[Bank::kGroups], rss[Bank::kGroups], M2s[Bank::kGroups];   // zero for padding channels
+    float suu = 0.f;
+#pragma unroll
+    for (int j = 0; j < Bank::kGroups; ++j) {
+        mus[j] = 0.f; rss[j] = 0.f; M2s[j] = 0.f;
+        const int ch = 128 * j + c;
+        if (j >= bk.ng || ch >= bk.n_mels) continue;
+        float mu, M2;
+        mel_merge(pp, nchunk, T, ch, bk.Mp, mu, M2);
+        const float rs = mel_rs(M2, (float)T);
+        mus[j] = mu; rss[j] = rs; M2s[j] = M2;
+        if (g == 0) suu += mel_suu(rs, M2);
     }
+    suu = block_sum(suu, red);
+    const MelClip k = mel_clip(suu, (float)T, bk.n_mels);
+    if (blockIdx.x == 0 && threadIdx.x == 0) mel_write_gstat(gstat, b, k, (float)T);
     // pooled frames tp = t0/2 .. ; chunk is even-sized so pairs never straddle chunks
     const int Tp = T / 2;
-    const float* x = xm + (size_t)f0 * 128 + c;
-    float* o = x0 + (size_t)pool_off[b] * 128 + c;
     const int tp0 = t0 / 2, tp1 = min(Tp, tp0 + kMelChunk / 2);
-    if (Tp > 0) {
-        // fixed trip count, loads first (clamped indices), stores masked: no per-iteration load/wait chain
-        constexpr int NI = kMelChunk / 4;
-        float xa[NI], xb[NI];
+    const bool last = (int)blockIdx.x == nchunk - 1;
 #pragma unroll
-        for (int i = 0; i < NI; ++i) {
-            const int tc = min(tp0 + g + 2 * i, Tp - 1);
-            xa[i] = x[(size_t)(2 * tc) * 128];
-            xb[i] = x[(size_t)(2 * tc + 1) * 128];
-        }
+    for (int j = 0; j < Bank::kGroups; ++j) {
+        const int ch = 128 * j + c;
+        if (j >= bk.ng || ch >= bk.Mp) continue;
+        const bool on = ch < bk.n_mels;
+        if (blockIdx.x == 0 && g == 0) mel_write_stats(stats, (size_t)b * bk.Mp + ch, mus[j], rss[j], M2s[j]);
+        const float* x = xm + (size_t)f0 * bk.Mp + ch;
+        float* o = x0 + (size_t)pool_off[b] * bk.Mp + ch;
+        const float mu = mus[j], rs = rss[j];
+        if (Tp > 0) {
+            constexpr int NI = kMelChunk / 4;
+            float xa[NI], xb[NI];
 #pragma unroll
-        for (int i = 0; i < NI; ++i) {
-            const int tp = tp0 + g + 2 * i;
-            if (tp < tp1) {
-                const float u0 = (xa[i] - mu) * rs, u1 = (xb[i] - mu) * rs;
-                o[(size_t)tp * 128] = 0.5f * (u0 * ginv + u1 * ginv);
+            for (int i = 0; i < NI; ++i) {
+                const int tc = min(tp0 + g + 2 * i, Tp - 1);
+                xa[i] = x[(size_t)(2 * tc) * bk.Mp];
+                xb[i] = x[(size_t)(2 * tc + 1) * bk.Mp];
+            }
+#pragma unroll
+            for (int i = 0; i < NI; ++i) {
+                const int tp = tp0 + g + 2 * i;
+                if (tp < tp1)                                         // padding channels stay zero
+                    o[(size_t)tp * bk.Mp] = on ? mel_pooled(mel_u(xa[i], mu, rs), mel_u(xb[i], mu, rs), k.ginv) : 0.f;
             }
         }
+        // pooled rows are 32-aligned per clip: keep the pad rows finite (they flow through the GEMMs)
+        if (last)
+            for (int tp = Tp + g; tp < ((Tp + 31) & ~31); tp += 2) o[(size_t)tp * bk.Mp] = 0.f;
     }
-    // pooled rows are 32-aligned per clip: keep the pad rows finite (they flow through the GEMMs)
-    if ((int)blockIdx.x == nchunk - 1)
-        for (int tp = Tp + g; tp < ((Tp + 31) & ~31); tp += 2) o[(size_t)tp * 128] = 0.f;
 }
 
 // backward partials: D1_c = sum_t dv, D2_c = sum_t dv*u over the chunk (dv = dx0/2 on pooled frames)
+template <class Bank>
 __global__ __launch_bounds__(256) void mel_bwd_partial_kernel(const float* __restrict__ dx0, const float* __restrict__ xm,
                                                                const int* __restrict__ frame_off, const int* __restrict__ pool_off,
                                                                const float* __restrict__ stats, float* __restrict__ part,
-                                                               int pstride) {
+                                                               int pstride, int n_mels, int Mp) {
     __shared__ float s1[2][128], s2[2][128];
+    const Bank bk(n_mels, Mp);
     const int b = blockIdx.y;
     const int f0 = frame_off[b], T = frame_off[b + 1] - f0, Tp = T / 2;
     const int t0 = blockIdx.x * kMelChunk;
     if (t0 >= T) return;
     const int c = threadIdx.x & 127, g = threadIdx.x >> 7;
-    const float* st = stats + ((size_t)b * 128 + c) * 4;
-    const float mu = st[0], rs = st[1];
-    const float* x = xm + (size_t)f0 * 128 + c;
-    const float* d0 = dx0 + (size_t)pool_off[b] * 128 + c;
     const int tp0 = t0 / 2, tp1 = min(Tp, tp0 + kMelChunk / 2);
-    float a1 = 0.f, a2 = 0.f;
-    if (Tp > 0) {
-        constexpr int NI = kMelChunk / 4;
-        float dd[NI], xa[NI], xb[NI];
+    float* o = part + ((size_t)b * pstride + blockIdx.x) * 2 * bk.Mp;
+    for (int j = 0; j < bk.ng; ++j) {
+        const int ch = 128 * j + c;
+        const bool on = ch < bk.n_mels;
+        const int cc = min(ch, bk.n_mels - 1);
+        const MelChan s = mel_read_stats(stats, (size_t)b * bk.Mp + cc);
+        const float* x = xm + (size_t)f0 * bk.Mp + cc;
+        const float* d0 = dx0 + (size_t)pool_off[b] * bk.Mp + cc;
+        float a1 = 0.f, a2 = 0.f;
+        if (Tp > 0) {
+            constexpr int NI = kMelChunk / 4;
+            float dd[NI], xa[NI], xb[NI];
 #pragma unroll
-        for (int i = 0; i < NI; ++i) {
-            const int tc = min(tp0 + g + 2 * i, Tp - 1);
-            dd[i] = d0[(size_t)tc * 128];
-            xa[i] = x[(size_t)(2 * tc) * 128];
-            xb[i] = x[(size_t)(2 * tc + 1) * 128];
-        }
-#pragma unroll
-        for (int i = 0; i < NI; ++i)
-            if (tp0 + g + 2 * i < tp1) {
-                const float dv = 0.5f * dd[i];
-                const float u0 = (xa[i] - mu) * rs, u1 = (xb[i] - mu) * rs;
-                a1 += 2.f * dv;
-                a2 += dv * u0 + dv * u1;
+            for (int i = 0; i < NI; ++i) {
+                const int tc = min(tp0 + g + 2 * i, Tp - 1);
+                dd[i] = d0[(size_t)tc * bk.Mp];
+                xa[i] = x[(size_t)(2 * tc) * bk.Mp];
+                xb[i] = x[(size_t)(2 * tc + 1) * bk.Mp];
             }
-    }
-    s1[g][c] = a1; s2[g][c] = a2;
-    __syncthreads();
-    if (g == 0) {
-        float* o = part + ((size_t)b * pstride + blockIdx.x) * 256;
-        o[c] = s1[0][c] + s1[1][c];
-        o[128 + c] = s2[0][c] + s2[1][c];
+#pragma unroll
+            for (int i = 0; i < NI; ++i)
+                if (tp0 + g + 2 * i < tp1) {
+                    const float dv = 0.5f * dd[i];
+                    const float u0 = mel_u(xa[i], s.mu, s.rs), u1 = mel_u(xb[i], s.mu, s.rs);
+                    a1 += 2.f * dv;
+                    a2 += mel_dv_u(dv, u0, u1);
+                }
+        }
+        s1[g][c] = a1; s2[g][c] = a2;
+        __syncthreads();
+        if (g == 0 && ch < bk.Mp) {
+            o[ch] = on ? s1[0][c] + s1[1][c] : 0.f;
+            o[bk.Mp + ch] = on ? s2[0][c] + s2[1][c] : 0.f;
+        }
+        if (Bank::kGroups > 1) __syncthreads();
     }
 }
 
-// backward apply, in place on xm (xm <- dL/dxm)
+// backward apply, in place on xm (xm <- dL/dxm; zero in the padding channels)
+template <class Bank>
 __global__ __launch_bounds__(256) void mel_bwd_apply_kernel(const float* __restrict__ dx0, float* __restrict__ xm,
                                                              const int* __restrict__ frame_off, const int* __restrict__ pool_off,
                                                              const float* __restrict__ stats, const float* __restrict__ gstat,
-                                                             const float* __restrict__ part, int pstride) {
+                                                             const float* __restrict__ part, int pstride, int n_mels, int Mp) {
     __shared__ float red[4];
+    const Bank bk(n_mels, Mp);
     const int b = blockIdx.y;
     const int f0 = frame_off[b], T = frame_off[b + 1] - f0, Tp = T / 2;
     const int t0 = blockIdx.x * kMelChunk;
     if (t0 >= T) return;
     const int nchunk = (T + kMelChunk - 1) / kMelChunk;
     const int c = threadIdx.x & 127, g = threadIdx.x >> 7;
-    const float* st = stats + ((size_t)b * 128 + c) * 4;
-    const float mu = st[0], rs = st[1], M2 = st[2];
-    const float ginv = gstat[b * 4 + 0], gs = gstat[b * 4 + 1], n = gstat[b * 4 + 2];
-    float D1 = 0.f, D2 = 0.f;
-    const float* pp = part + (size_t)b * pstride * 256;
-    for (int k = 0; k < nchunk; ++k) { D1 += pp[(size_t)k * 256 + c]; D2 += pp[(size_t)k * 256 + 128 + c]; }
-    const float sa = block_sum(g == 0 ? D1 : 0.f, red);
-    const float sb = block_sum(g == 0 ? D2 : 0.f, red);
-    const float mdv = sa / n;
-    const float Q = (gs > 0.f) ? sb * ginv * ginv / ((n - 1.f) * gs) : 0.f;
-    const float m1 = ginv * (D1 / (float)T - mdv);
-    const float m2 = (ginv * D2 - Q * rs * rs * M2) / (float)T;
-    float* x = xm + (size_t)f0 * 128 + c;
-    const float* d0 = dx0 + (size_t)pool_off[b] * 128 + c;
+    const MelClip k = mel_read_gstat(gstat, b);
+    const float* pp = part + (size_t)b * pstride * 2 * bk.Mp;
+    float d1s[Bank::kGroups], d2s[Bank::kGroups];
+    MelChan ss[Bank::kGroups];                      // read ahead of the sums, whose barriers would expose the loads
+    float sa = 0.f, sb = 0.f;
+#pragma unroll
+    for (int j = 0; j < Bank::kGroups; ++j) {
+        d1s[j] = 0.f; d2s[j] = 0.f; ss[j] = MelChan{0.f, 0.f, 0.f};
+        const int ch = 128 * j + c;
+        if (j >= bk.ng || ch >= bk.n_mels) continue;
+        ss[j] = mel_read_stats(stats, (size_t)b * bk.Mp + ch);
+        float D1 = 0.f, D2 = 0.f;
+        for (int i = 0; i < nchunk; ++i) { D1 += pp[(size_t)i * 2 * bk.Mp + ch]; D2 += pp[(size_t)i * 2 * bk.Mp + bk.Mp + ch]; }
+        d1s[j] = D1; d2s[j] = D2;
+        if (g == 0) { sa += D1; sb += D2; }
+    }
+    sa = block_sum(sa, red);
+    sb = block_sum(sb, red);
+    const MelClipGrad q = mel_clip_grad(sa, sb, k);
     const int t1 = min(T, t0 + kMelChunk);
-    {
+#pragma unroll
+    for (int j = 0; j < Bank::kGroups; ++j) {
+        const int ch = 128 * j + c;
+        if (j >= bk.ng || ch >= bk.Mp) continue;
+        float* x = xm + (size_t)f0 * bk.Mp + ch;
+        if (ch >= bk.n_mels) {
+            for (int t = t0 + g; t < t1; t += 2) x[(size_t)t * bk.Mp] = 0.f;
+            continue;
+        }
+        const MelChan s = ss[j];
+        const MelChanGrad m = mel_chan_grad(d1s[j], d2s[j], (float)T, s.rs, s.M2, k, q);
+        const float* d0 = dx0 + (size_t)pool_off[b] * bk.Mp + ch;
         constexpr int NI = kMelChunk / 2;
         float dd[NI], xv[NI];
 #pragma unroll
         for (int i = 0; i < NI; ++i) {
             const int tc = min(t0 + g + 2 * i, T - 1);
-            dd[i] = d0[(size_t)min(tc >> 1, max(Tp - 1, 0)) * 128];
-            xv[i] = x[(size_t)tc * 128];
+            dd[i] = d0[(size_t)min(tc >> 1, max(Tp - 1, 0)) * bk.Mp];
+            xv[i] = x[(size_t)tc * bk.Mp];
         }
 #pragma unroll
         for (int i = 0; i < NI; ++i) {
             const int t = t0 + g + 2 * i;
             if (t < t1) {
                 const float dv = (t < 2 * Tp) ? 0.5f * dd[i] : 0.f;
-                const float u = (xv[i] - mu) * rs;
-                const float du = (dv - mdv) * ginv - u * Q;
-                x[(size_t)t * 128] = rs * (du - m1 - u * m2);
+                x[(size_t)t * bk.Mp] = mel_bwd_value(dv, mel_u(xv[i], s.mu, s.rs), s.rs, k.ginv, q, m);
             }
         }
     }
@@ -1499,14 +1549,6 @@ __device__ __forceinline__ float mel_chan_sum(float v, float (*red)[128], int c,
     __syncthreads();
     return (red[0][c] + red[1][c]) + (red[2][c] + red[3][c]);
 }
-// sum over the whole workgroup (8 waves)
-__device__ __forceinline__ float mel_block_sum(float v, float* red8) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red8[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((red8[0] + red8[1]) + (red8[2] + red8[3])) + ((red8[4] + red8[5]) + (red8[6] + red8[7]));
-}
 
 // amax_out: [B][64] partial maxima of |x0| per clip (entries 0..7 written: the maximum, then zeros) for gemm_h2.hip, or null
 __global__ __launch_bounds__(512) void mel_norm_clip_fwd_kernel(const float* __restrict__ xm, const int* __restrict__ frame_off,
@@ -1542,22 +1584,20 @@ __global__ __launch_bounds__(512) void mel_norm_clip_fwd_kernel(const float* __r
         if (t + 1 < T) { const float d = xb[i] - mu; q += d * d; }
     }
     const float M2 = mel_chan_sum(q, red, c, g);
-    const float rs = 1.0f / sqrtf(M2 / (float)T + 1e-5f);            // biased var, eps 1e-5 (InstanceNorm1d)
-    const float suu = mel_block_sum(g == 0 ? rs * rs * M2 : 0.f, red8);
-    const float n = (float)T * 128.f;
-    const float gs = sqrtf(suu / (n - 1.f));                          // unbiased std of u (mean 0): GlobalStandardize
-    const float ginv = 1.0f / (gs + 1e-8f);
-    if (g == 0) { float* st = stats + ((size_t)b * 128 + c) * 4; st[0] = mu; st[1] = rs; st[2] = M2; st[3] = 0.f; }
-    if (threadIdx.x == 0) { gstat[b * 4 + 0] = ginv; gstat[b * 4 + 1] = gs; gstat[b * 4 + 2] = n; gstat[b * 4 + 3] = (float)T; }
+    const float rs = mel_rs(M2, (float)T);
+    const float suu = mel_block_sum(g == 0 ? mel_suu(rs, M2) : 0.f, red8);
+    const MelClip k = mel_clip(suu, (float)T, 128);
+    if (g == 0) mel_write_stats(stats, (size_t)b * 128 + c, mu, rs, M2);
+    if (threadIdx.x == 0) mel_write_gstat(gstat, b, k, (float)T);
     float* o = x0 + (size_t)pool_off[b] * 128 + c;
     const int Tpad = (Tp + 31) & ~31;
     float omax = 0.f;
 #pragma unroll
     for (int i = 0; i < kMelClipR; ++i) {
         const int tp = g + 4 * i;
-        const float u0 = (xa[i] - mu) * rs, u1 = (xb[i] - mu) * rs;
+        const float u0 = mel_u(xa[i], mu, rs), u1 = mel_u(xb[i], mu, rs);
         if (tp < Tp) {
-            const float v = 0.5f * (u0 * ginv + u1 * ginv);                       // AvgPool1d(2, 2)
+            const float v = mel_pooled(u0, u1, k.ginv);
             o[(size_t)tp * 128] = v;
             omax = fmaxf(omax, fabsf(v));
         } else if (tp < Tpad) o[(size_t)tp * 128] = 0.f;                          // pad rows stay finite
@@ -1585,9 +1625,8 @@ __global__ __launch_bounds__(512) void mel_norm_clip_bwd_kernel(const float* __r
     const int b = blockIdx.x;
     const int f0 = frame_off[b], T = frame_off[b + 1] - f0, Tp = T / 2;
     const int c = threadIdx.x & 127, g = threadIdx.x >> 7;
-    const float* st = stats + ((size_t)b * 128 + c) * 4;
-    const float mu = st[0], rs = st[1], M2 = st[2];
-    const float ginv = gstat[b * 4 + 0], gs = gstat[b * 4 + 1], n = gstat[b * 4 + 2];
+    const MelChan s = mel_read_stats(stats, (size_t)b * 128 + c);
+    const MelClip k = mel_read_gstat(gstat, b);
     float* x = xm + (size_t)f0 * 128 + c;
     const float* d0 = dx0 + (size_t)pool_off[b] * 128 + c;
     float xa[kMelClipR], xb[kMelClipR], dd[kMelClipR];
@@ -1604,65 +1643,36 @@ __global__ __launch_bounds__(512) void mel_norm_clip_bwd_kernel(const float* __r
         const bool pair = g + 4 * i < Tp;
         const float dv = pair ? 0.5f * dd[i] : 0.f;                   // d(avg pool): half the pooled gradient to each frame
         dd[i] = dv;
-        xa[i] = (xa[i] - mu) * rs;                                    // u
-        xb[i] = (xb[i] - mu) * rs;
-        if (pair) { a1 += 2.f * dv; a2 += dv * xa[i] + dv * xb[i]; }
+        xa[i] = mel_u(xa[i], s.mu, s.rs);
+        xb[i] = mel_u(xb[i], s.mu, s.rs);
+        if (pair) { a1 += 2.f * dv; a2 += mel_dv_u(dv, xa[i], xb[i]); }
     }
     const float D1 = mel_chan_sum(a1, red, c, g), D2 = mel_chan_sum(a2, red, c, g);
     const float sa = mel_block_sum(g == 0 ? D1 : 0.f, red8);
     const float sb = mel_block_sum(g == 0 ? D2 : 0.f, red8);
-    const float mdv = sa / n;
-    const float Q = (gs > 0.f) ? sb * ginv * ginv / ((n - 1.f) * gs) : 0.f;
-    const float m1 = ginv * (D1 / (float)T - mdv);
-    const float m2 = (ginv * D2 - Q * rs * rs * M2) / (float)T;
+    const MelClipGrad q = mel_clip_grad(sa, sb, k);
+    const MelChanGrad m = mel_chan_grad(D1, D2, (float)T, s.rs, s.M2, k, q);
 #pragma unroll
     for (int i = 0; i < kMelClipR; ++i) {
         const int t = 2 * (g + 4 * i);
-        if (t < T) { const float u = xa[i]; x[(size_t)t * 128] = rs * (((dd[i] - mdv) * ginv - u * Q) - m1 - u * m2); }
-        if (t + 1 < T) { const float u = xb[i]; x[(size_t)(t + 1) * 128] = rs * (((dd[i] - mdv) * ginv - u * Q) - m1 - u * m2); }
+        if (t < T) x[(size_t)t * 128] = mel_bwd_value(dd[i], xa[i], s.rs, k.ginv, q, m);
+        if (t + 1 < T) x[(size_t)(t + 1) * 128] = mel_bwd_value(dd[i], xb[i], s.rs, k.ginv, q, m);
     }
 }
 
-void launch_mel_norm_fwd(const float* xm, const int* frame_off, const int* pool_off, float* x0, float* stats,
-                         float* gstat, float* part, int pstride, int B, int max_frames, hipStream_t st, float* amax_out) {
-    if (max_frames <= kMelClipFrames) {
-        hipLaunchKernelGGL(mel_norm_clip_fwd_kernel, dim3(B), dim3(512), 0, st, xm, frame_off, pool_off, x0, stats, gstat, amax_out);
-        return;
-    }
-    const int nx = (max_frames + kMelChunk - 1) / kMelChunk;
-    hipLaunchKernelGGL(mel_partial_stats_kernel, dim3(nx, B), dim3(256), 0, st, xm, frame_off, part, pstride);
-    hipLaunchKernelGGL(mel_apply_pool_kernel, dim3(nx, B), dim3(256), 0, st, xm, frame_off, pool_off, part, pstride, x0, stats,
-                       gstat);
-}
-void launch_mel_norm_bwd(const float* dx0, float* xm, const int* frame_off, const int* pool_off, const float* stats,
-                         const float* gstat, float* part, int pstride, int B, int max_frames, hipStream_t st) {
-    if (max_frames <= kMelClipFrames) {
-        hipLaunchKernelGGL(mel_norm_clip_bwd_kernel, dim3(B), dim3(512), 0, st, dx0, xm, frame_off, pool_off, stats, gstat);
-        return;
-    }
-    const int nx = (max_frames + kMelChunk - 1) / kMelChunk;
-    hipLaunchKernelGGL(mel_bwd_partial_kernel, dim3(nx, B), dim3(256), 0, st, dx0, xm, frame_off, pool_off, stats, part, pstride);
-    hipLaunchKernelGGL(mel_bwd_apply_kernel, dim3(nx, B), dim3(256), 0, st, dx0, xm, frame_off, pool_off, stats, gstat, part,
-                       pstride);
-}
 // ---------------------------------------------------------------------------------
-// The mel block for any bank of n_mels <= 512 bands, rows of Mp >= n_mels floats (Mp a multiple of 4; stored_channels in
-// capi.hip).  Same maths as the 128-band kernels above: channels are taken in groups of 128 (thread c of a group: channel
-// 128 j + c), each group's statistics are complete before the next starts, and the clip-wide GlobalStandardize sum runs over
-// the n_mels real channels only.  Padding channels n_mels .. Mp-1 get zero statistics, zero x0 columns and zero dL/dxm.
-// Short clips (<= kMelClipFrames): one 512-thread workgroup per clip (4 row groups; the passes over the clip's rows -- mean,
-// M2, output -- re-read it from L2).  Longer clips: the chunked two-launch form, partials
-// [B][pstride][2 Mp] = {mean | D1, M2 | D2} per 32-frame chunk.
+// The clip form for any bank (MelBankAny's layout above): one 512-thread workgroup per clip, 4 row groups; each 128-channel
+// group's statistics are complete before the next starts, and the passes over the clip's rows -- mean, M2, output -- re-read
+// it from L2 (frames g, g + 4, ...), where the 128-band kernels above sum frame pairs held in registers: another order of the
+// same sums, so the two stay apart.
 // ---------------------------------------------------------------------------------
-constexpr int kMelGroups = 4;                       // 128-channel groups: Mp <= 512
-
 __global__ __launch_bounds__(512) void mel_any_clip_fwd_kernel(const float* __restrict__ xm, const int* __restrict__ frame_off,
                                                                 const int* __restrict__ pool_off, float* __restrict__ x0,
                                                                 float* __restrict__ stats, float* __restrict__ gstat, int n_mels,
                                                                 int Mp) {
     __shared__ float red[4][128];
     __shared__ float red8[8];
-    __shared__ float smu[kMelGroups][128], srs[kMelGroups][128];   // the statistics of the output pass
+    __shared__ float smu[MelBankAny::kGroups][128], srs[MelBankAny::kGroups][128];   // the statistics of the output pass
     const int b = blockIdx.x;
     const int f0 = frame_off[b], T = frame_off[b + 1] - f0, Tp = T / 2;
     const int c = threadIdx.x & 127, g = threadIdx.x >> 7;
@@ -1680,19 +1690,14 @@ __global__ __launch_bounds__(512) void mel_any_clip_fwd_kernel(const float* __re
         float q = 0.f;
         for (int t = g; t < T; t += 4) { const float d = x[(size_t)t * Mp] - mu; q += d * d; }
         const float M2 = mel_chan_sum(q, red, c, g);
-        const float rs = 1.0f / sqrtf(M2 / (float)T + 1e-5f);        // biased var, eps 1e-5 (InstanceNorm1d)
-        if (g == 0 && ch < Mp) {
-            float* so = stats + ((size_t)b * Mp + ch) * 4;
-            so[0] = on ? mu : 0.f; so[1] = on ? rs : 0.f; so[2] = on ? M2 : 0.f; so[3] = 0.f;
-        }
-        if (on && g == 0) suu += rs * rs * M2;
+        const float rs = mel_rs(M2, (float)T);
+        if (g == 0 && ch < Mp) mel_write_stats(stats, (size_t)b * Mp + ch, on ? mu : 0.f, on ? rs : 0.f, on ? M2 : 0.f);
+        if (on && g == 0) suu += mel_suu(rs, M2);
         if (g == 0) { smu[j][c] = on ? mu : 0.f; srs[j][c] = on ? rs : 0.f; }
     }
     suu = mel_block_sum(suu, red8);
-    const float n = (float)T * (float)n_mels;
-    const float gs = sqrtf(suu / (n - 1.f));                          // unbiased std of u (mean 0): GlobalStandardize
-    const float ginv = 1.0f / (gs + 1e-8f);
-    if (threadIdx.x == 0) { gstat[b * 4 + 0] = ginv; gstat[b * 4 + 1] = gs; gstat[b * 4 + 2] = n; gstat[b * 4 + 3] = (float)T; }
+    const MelClip k = mel_clip(suu, (float)T, n_mels);
+    if (threadIdx.x == 0) mel_write_gstat(gstat, b, k, (float)T);
     const int Tpad = (Tp + 31) & ~31;
 #pragma unroll 1
     for (int j = 0; j < ng; ++j) {
@@ -1703,10 +1708,8 @@ __global__ __launch_bounds__(512) void mel_any_clip_fwd_kernel(const float* __re
         const float mu = smu[j][c], rs = srs[j][c];
         for (int tp = g; tp < Tpad; tp += 4) {
             float v = 0.f;                                            // pad rows and padding channels stay zero
-            if (tp < Tp && ch < n_mels) {
-                const float u0 = (x[(size_t)(2 * tp) * Mp] - mu) * rs, u1 = (x[(size_t)(2 * tp + 1) * Mp] - mu) * rs;
-                v = 0.5f * (u0 * ginv + u1 * ginv);                   // AvgPool1d(2, 2)
-            }
+            if (tp < Tp && ch < n_mels)
+                v = mel_pooled(mel_u(x[(size_t)(2 * tp) * Mp], mu, rs), mel_u(x[(size_t)(2 * tp + 1) * Mp], mu, rs), k.ginv);
             o[(size_t)tp * Mp] = v;
         }
     }
@@ -1716,24 +1719,24 @@ __global__ __launch_bounds__(512) void mel_any_clip_bwd_kernel(const float* __re
                                                                 const int* __restrict__ frame_off, const int* __restrict__ pool_off,
                                                                 const float* __restrict__ stats, const float* __restrict__ gstat,
                                                                 int n_mels, int Mp) {
+    constexpr int kGroups = MelBankAny::kGroups;
     __shared__ float red[4][128];
     __shared__ float red8[8];
     const int b = blockIdx.x;
     const int f0 = frame_off[b], T = frame_off[b + 1] - f0, Tp = T / 2;
     const int c = threadIdx.x & 127, g = threadIdx.x >> 7;
     const int ng = (Mp + 127) / 128;
-    const float ginv = gstat[b * 4 + 0], gs = gstat[b * 4 + 1], n = gstat[b * 4 + 2];
-    float d1s[kMelGroups], d2s[kMelGroups];
+    const MelClip k = mel_read_gstat(gstat, b);
+    float d1s[kGroups], d2s[kGroups];
     float sa = 0.f, sb = 0.f;
 #pragma unroll
-    for (int j = 0; j < kMelGroups; ++j) {
+    for (int j = 0; j < kGroups; ++j) {
         d1s[j] = 0.f; d2s[j] = 0.f;
         if (j >= ng) continue;                                         // uniform across the workgroup
         const int ch = 128 * j + c;
         const bool on = ch < n_mels;
         const int cc = min(ch, n_mels - 1);
-        const float* so = stats + ((size_t)b * Mp + cc) * 4;
-        const float mu = so[0], rs = so[1];
+        const MelChan s = mel_read_stats(stats, (size_t)b * Mp + cc);
         const float* x = xm + (size_t)f0 * Mp + cc;
         const float* d0 = dx0 + (size_t)pool_off[b] * Mp + cc;
         float a1 = 0.f, a2 = 0.f;
@@ -1742,9 +1745,9 @@ __global__ __launch_bounds__(512) void mel_any_clip_bwd_kernel(const float* __re
             const int tp = g + 4 * i, t = 2 * tp;
             if (tp < Tp) {
                 const float dv = 0.5f * d0[(size_t)tp * Mp];           // d(avg pool): half the pooled gradient to each frame
-                const float u0 = (x[(size_t)t * Mp] - mu) * rs, u1 = (x[(size_t)(t + 1) * Mp] - mu) * rs;
+                const float u0 = mel_u(x[(size_t)t * Mp], s.mu, s.rs), u1 = mel_u(x[(size_t)(t + 1) * Mp], s.mu, s.rs);
                 a1 += 2.f * dv;
-                a2 += dv * u0 + dv * u1;
+                a2 += mel_dv_u(dv, u0, u1);
             }
         }
         const float D1 = mel_chan_sum(a1, red, c, g), D2 = mel_chan_sum(a2, red, c, g);
@@ -1753,11 +1756,10 @@ __global__ __launch_bounds__(512) void mel_any_clip_bwd_kernel(const float* __re
     }
     sa = mel_block_sum(sa, red8);
     sb = mel_block_sum(sb, red8);
-    const float mdv = sa / n;
-    const float Q = (gs > 0.f) ? sb * ginv * ginv / ((n - 1.f) * gs) : 0.f;
+    const MelClipGrad q = mel_clip_grad(sa, sb, k);
     // every read of the clip's xm above is complete (the block sums hold barriers): the in-place writes start here
 #pragma unroll
-    for (int j = 0; j < kMelGroups; ++j) {
+    for (int j = 0; j < kGroups; ++j) {
         const int ch = 128 * j + c;
         if (j >= ng || ch >= Mp) continue;
         float* x = xm + (size_t)f0 * Mp + ch;
@@ -1765,254 +1767,68 @@ __global__ __launch_bounds__(512) void mel_any_clip_bwd_kernel(const float* __re
             for (int t = g; t < T; t += 4) x[(size_t)t * Mp] = 0.f;
             continue;
         }
-        const float* so = stats + ((size_t)b * Mp + ch) * 4;
-        const float mu = so[0], rs = so[1], M2 = so[2];
+        const MelChan s = mel_read_stats(stats, (size_t)b * Mp + ch);
         const float* d0 = dx0 + (size_t)pool_off[b] * Mp + ch;
-        const float m1 = ginv * (d1s[j] / (float)T - mdv);
-        const float m2 = (ginv * d2s[j] - Q * rs * rs * M2) / (float)T;
+        const MelChanGrad m = mel_chan_grad(d1s[j], d2s[j], (float)T, s.rs, s.M2, k, q);
         for (int t = g; t < T; t += 4) {
             const float dv = (t < 2 * Tp) ? 0.5f * d0[(size_t)(t >> 1) * Mp] : 0.f;
-            const float u = (x[(size_t)t * Mp] - mu) * rs;
-            x[(size_t)t * Mp] = rs * (((dv - mdv) * ginv - u * Q) - m1 - u * m2);
+            x[(size_t)t * Mp] = mel_bwd_value(dv, mel_u(x[(size_t)t * Mp], s.mu, s.rs), s.rs, k.ginv, q, m);
         }
     }
 }
 
-// chunked form: per-chunk (mean, M2) of every channel
-__global__ __launch_bounds__(256) void mel_any_partial_stats_kernel(const float* __restrict__ xm, const int* __restrict__ frame_off,
-                                                                     float* __restrict__ part, int pstride, int n_mels, int Mp) {
-    __shared__ float s1[2][128];
-    const int b = blockIdx.y;
-    const int f0 = frame_off[b], T = frame_off[b + 1] - f0;
-    const int t0 = blockIdx.x * kMelChunk;
-    if (t0 >= T) return;
-    const int nt = min(kMelChunk, T - t0);
-    const int c = threadIdx.x & 127, g = threadIdx.x >> 7;
-    const int ng = (Mp + 127) / 128;
-    float* o = part + ((size_t)b * pstride + blockIdx.x) * 2 * Mp;
-    for (int j = 0; j < ng; ++j) {
-        const int ch = 128 * j + c;
-        const bool on = ch < n_mels;
-        const float* x = xm + (size_t)(f0 + t0) * Mp + min(ch, n_mels - 1);
-        float v[kMelChunk / 2];
-        float a = 0.f;
-#pragma unroll
-        for (int i = 0; i < kMelChunk / 2; ++i) {
-            const int t = 2 * i + g;
-            v[i] = (t < nt) ? x[(size_t)t * Mp] : 0.f;
-            a += v[i];
-        }
-        s1[g][c] = a;
-        __syncthreads();
-        const float mean = (s1[0][c] + s1[1][c]) / (float)nt;
-        __syncthreads();
-        float q = 0.f;
-#pragma unroll
-        for (int i = 0; i < kMelChunk / 2; ++i) {
-            const int t = 2 * i + g;
-            if (t < nt) { float d = v[i] - mean; q += d * d; }
-        }
-        s1[g][c] = q;
-        __syncthreads();
-        if (g == 0 && ch < Mp) {
-            o[ch] = on ? mean : 0.f;
-            o[Mp + ch] = on ? s1[0][c] + s1[1][c] : 0.f;
-        }
-        __syncthreads();
-    }
-}
-
-// merge the chunk partials of channel ch (row pitch 2 Mp)
-__device__ __forceinline__ void mel_any_merge(const float* __restrict__ part, int nchunk, int T, int ch, int Mp, float& mean,
-                                              float& M2) {
-    float n = 0.f;
-    mean = 0.f; M2 = 0.f;
-    for (int k = 0; k < nchunk; ++k) {
-        const float nk = (float)min(kMelChunk, T - k * kMelChunk);
-        const float mk = part[(size_t)k * 2 * Mp + ch], qk = part[(size_t)k * 2 * Mp + Mp + ch];
-        const float d = mk - mean, nn = n + nk;
-        mean += d * (nk / nn);
-        M2 += qk + d * d * (n * nk / nn);
-        n = nn;
-    }
-}
-
-__global__ __launch_bounds__(256) void mel_any_apply_pool_kernel(const float* __restrict__ xm, const int* __restrict__ frame_off,
-                                                                  const int* __restrict__ pool_off, const float* __restrict__ part,
-                                                                  int pstride, float* __restrict__ x0, float* __restrict__ stats,
-                                                                  float* __restrict__ gstat, int n_mels, int Mp) {
-    __shared__ float red[4];
-    const int b = blockIdx.y;
-    const int f0 = frame_off[b], T = frame_off[b + 1] - f0;
-    const int t0 = blockIdx.x * kMelChunk;
-    if (t0 >= T) return;
-    const int nchunk = (T + kMelChunk - 1) / kMelChunk;
-    const int c = threadIdx.x & 127, g = threadIdx.x >> 7;
-    const int ng = (Mp + 127) / 128;
-    const float* pp = part + (size_t)b * pstride * 2 * Mp;
-    float mus[kMelGroups], rss[kMelGroups];
-    float suu = 0.f;
-#pragma unroll
-    for (int j = 0; j < kMelGroups; ++j) {
-        mus[j] = 0.f; rss[j] = 0.f;
-        const int ch = 128 * j + c;
-        if (j >= ng || ch >= n_mels) continue;
-        float mu, M2;
-        mel_any_merge(pp, nchunk, T, ch, Mp, mu, M2);
-        const float rs = 1.0f / sqrtf(M2 / (float)T + 1e-5f);        // biased var, eps 1e-5
-        mus[j] = mu; rss[j] = rs;
-        if (g == 0) suu += rs * rs * M2;
-        if (blockIdx.x == 0 && g == 0) { float* so = stats + ((size_t)b * Mp + ch) * 4; so[0] = mu; so[1] = rs; so[2] = M2; so[3] = 0.f; }
-    }
-    suu = block_sum(suu, red);
-    const float n = (float)T * (float)n_mels;
-    const float gs = sqrtf(suu / (n - 1.f));                          // unbiased std of u (mean 0)
-    const float ginv = 1.0f / (gs + 1e-8f);
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        gstat[b * 4 + 0] = ginv; gstat[b * 4 + 1] = gs; gstat[b * 4 + 2] = n; gstat[b * 4 + 3] = (float)T;
-    }
-    const int Tp = T / 2;
-    const int tp0 = t0 / 2, tp1 = min(Tp, tp0 + kMelChunk / 2);
-    const bool last = (int)blockIdx.x == nchunk - 1;
-#pragma unroll
-    for (int j = 0; j < kMelGroups; ++j) {
-        const int ch = 128 * j + c;
-        if (j >= ng || ch >= Mp) continue;
-        if (blockIdx.x == 0 && g == 0 && ch >= n_mels) {
-            float* so = stats + ((size_t)b * Mp + ch) * 4; so[0] = 0.f; so[1] = 0.f; so[2] = 0.f; so[3] = 0.f;
-        }
-        const float* x = xm + (size_t)f0 * Mp + ch;
-        float* o = x0 + (size_t)pool_off[b] * Mp + ch;
-        const float mu = mus[j], rs = rss[j];
-        for (int tp = tp0 + g; tp < tp1; tp += 2) {
-            float v = 0.f;                                            // padding channels stay zero
-            if (ch < n_mels) {
-                const float u0 = (x[(size_t)(2 * tp) * Mp] - mu) * rs, u1 = (x[(size_t)(2 * tp + 1) * Mp] - mu) * rs;
-                v = 0.5f * (u0 * ginv + u1 * ginv);
-            }
-            o[(size_t)tp * Mp] = v;
-        }
-        // pooled rows are 32-aligned per clip: keep the pad rows finite (they flow through the GEMMs)
-        if (last)
-            for (int tp = Tp + g; tp < ((Tp + 31) & ~31); tp += 2) o[(size_t)tp * Mp] = 0.f;
-    }
-}
-
-// backward partials: D1_c = sum_t dv, D2_c = sum_t dv*u over the chunk (dv = dx0/2 on pooled frames)
-__global__ __launch_bounds__(256) void mel_any_bwd_partial_kernel(const float* __restrict__ dx0, const float* __restrict__ xm,
-                                                                   const int* __restrict__ frame_off, const int* __restrict__ pool_off,
-                                                                   const float* __restrict__ stats, float* __restrict__ part,
-                                                                   int pstride, int n_mels, int Mp) {
-    __shared__ float s1[2][128], s2[2][128];
-    const int b = blockIdx.y;
-    const int f0 = frame_off[b], T = frame_off[b + 1] - f0, Tp = T / 2;
-    const int t0 = blockIdx.x * kMelChunk;
-    if (t0 >= T) return;
-    const int c = threadIdx.x & 127, g = threadIdx.x >> 7;
-    const int ng = (Mp + 127) / 128;
-    const int tp0 = t0 / 2, tp1 = min(Tp, tp0 + kMelChunk / 2);
-    float* o = part + ((size_t)b * pstride + blockIdx.x) * 2 * Mp;
-    for (int j = 0; j < ng; ++j) {
-        const int ch = 128 * j + c;
-        const int cc = min(ch, n_mels - 1);
-        const float* so = stats + ((size_t)b * Mp + cc) * 4;
-        const float mu = so[0], rs = so[1];
-        const float* x = xm + (size_t)f0 * Mp + cc;
-        const float* d0 = dx0 + (size_t)pool_off[b] * Mp + cc;
-        float a1 = 0.f, a2 = 0.f;
-        for (int tp = tp0 + g; tp < tp1; tp += 2) {
-            const float dv = 0.5f * d0[(size_t)tp * Mp];
-            const float u0 = (x[(size_t)(2 * tp) * Mp] - mu) * rs, u1 = (x[(size_t)(2 * tp + 1) * Mp] - mu) * rs;
-            a1 += 2.f * dv;
-            a2 += dv * u0 + dv * u1;
-        }
-        s1[g][c] = a1; s2[g][c] = a2;
-        __syncthreads();
-        if (g == 0 && ch < Mp) {
-            const bool on = ch < n_mels;
-            o[ch] = on ? s1[0][c] + s1[1][c] : 0.f;
-            o[Mp + ch] = on ? s2[0][c] + s2[1][c] : 0.f;
-        }
-        __syncthreads();
-    }
-}
-
-// backward apply, in place on xm (xm <- dL/dxm; zero in the padding channels)
-__global__ __launch_bounds__(256) void mel_any_bwd_apply_kernel(const float* __restrict__ dx0, float* __restrict__ xm,
-                                                                 const int* __restrict__ frame_off, const int* __restrict__ pool_off,
-                                                                 const float* __restrict__ stats, const float* __restrict__ gstat,
-                                                                 const float* __restrict__ part, int pstride, int n_mels, int Mp) {
-    __shared__ float red[4];
-    const int b = blockIdx.y;
-    const int f0 = frame_off[b], T = frame_off[b + 1] - f0, Tp = T / 2;
-    const int t0 = blockIdx.x * kMelChunk;
-    if (t0 >= T) return;
-    const int nchunk = (T + kMelChunk - 1) / kMelChunk;
-    const int c = threadIdx.x & 127, g = threadIdx.x >> 7;
-    const int ng = (Mp + 127) / 128;
-    const float ginv = gstat[b * 4 + 0], gs = gstat[b * 4 + 1], n = gstat[b * 4 + 2];
-    const float* pp = part + (size_t)b * pstride * 2 * Mp;
-    float d1s[kMelGroups], d2s[kMelGroups];
-    float sa = 0.f, sb = 0.f;
-#pragma unroll
-    for (int j = 0; j < kMelGroups; ++j) {
-        d1s[j] = 0.f; d2s[j] = 0.f;
-        const int ch = 128 * j + c;
-        if (j >= ng || ch >= n_mels) continue;
-        float D1 = 0.f, D2 = 0.f;
-        for (int k = 0; k < nchunk; ++k) { D1 += pp[(size_t)k * 2 * Mp + ch]; D2 += pp[(size_t)k * 2 * Mp + Mp + ch]; }
-        d1s[j] = D1; d2s[j] = D2;
-        if (g == 0) { sa += D1; sb += D2; }
-    }
-    sa = block_sum(sa, red);
-    sb = block_sum(sb, red);
-    const float mdv = sa / n;
-    const float Q = (gs > 0.f) ? sb * ginv * ginv / ((n - 1.f) * gs) : 0.f;
-    const int t1 = min(T, t0 + kMelChunk);
-#pragma unroll
-    for (int j = 0; j < kMelGroups; ++j) {
-        const int ch = 128 * j + c;
-        if (j >= ng || ch >= Mp) continue;
-        float* x = xm + (size_t)f0 * Mp + ch;
-        if (ch >= n_mels) {
-            for (int t = t0 + g; t < t1; t += 2) x[(size_t)t * Mp] = 0.f;
-            continue;
-        }
-        const float* so = stats + ((size_t)b * Mp + ch) * 4;
-        const float mu = so[0], rs = so[1], M2 = so[2];
-        const float m1 = ginv * (d1s[j] / (float)T - mdv);
-        const float m2 = (ginv * d2s[j] - Q * rs * rs * M2) / (float)T;
-        const float* d0 = dx0 + (size_t)pool_off[b] * Mp + ch;
-        for (int t = t0 + g; t < t1; t += 2) {
-            const float dv = (t < 2 * Tp) ? 0.5f * d0[(size_t)(t >> 1) * Mp] : 0.f;
-            const float u = (x[(size_t)t * Mp] - mu) * rs;
-            x[(size_t)t * Mp] = rs * (((dv - mdv) * ginv - u * Q) - m1 - u * m2);
-        }
-    }
-}
-
-void launch_mel_norm_fwd_any(const float* xm, const int* frame_off, const int* pool_off, float* x0, float* stats, float* gstat,
-                             float* part, int pstride, int B, int max_frames, int n_mels, int Mp, hipStream_t st) {
-    if (max_frames <= kMelClipFrames) {
-        hipLaunchKernelGGL(mel_any_clip_fwd_kernel, dim3(B), dim3(512), 0, st, xm, frame_off, pool_off, x0, stats, gstat, n_mels, Mp);
-        return;
-    }
-    const int nx = (max_frames + kMelChunk - 1) / kMelChunk;
-    hipLaunchKernelGGL(mel_any_partial_stats_kernel, dim3(nx, B), dim3(256), 0, st, xm, frame_off, part, pstride, n_mels, Mp);
-    hipLaunchKernelGGL(mel_any_apply_pool_kernel, dim3(nx, B), dim3(256), 0, st, xm, frame_off, pool_off, part, pstride, x0, stats,
+// The chunked form's two launches per direction, for one bank: a block per 32-frame chunk and clip.
+template <class Bank>
+static void mel_chunked_fwd(const float* xm, const int* frame_off, const int* pool_off, float* x0, float* stats, float* gstat,
+                            float* part, int pstride, int B, int max_frames, int n_mels, int Mp, hipStream_t st) {
+    const dim3 grid((max_frames + kMelChunk - 1) / kMelChunk, B);
+    hipLaunchKernelGGL(mel_partial_stats_kernel<Bank>, grid, dim3(256), 0, st, xm, frame_off, part, pstride, n_mels, Mp);
+    hipLaunchKernelGGL(mel_apply_pool_kernel<Bank>, grid, dim3(256), 0, st, xm, frame_off, pool_off, part, pstride, x0, stats,
                        gstat, n_mels, Mp);
 }
-void launch_mel_norm_bwd_any(const float* dx0, float* xm, const int* frame_off, const int* pool_off, const float* stats,
-                             const float* gstat, float* part, int pstride, int B, int max_frames, int n_mels, int Mp, hipStream_t st) {
+template <class Bank>
+static void mel_chunked_bwd(const float* dx0, float* xm, const int* frame_off, const int* pool_off, const float* stats,
+                            const float* gstat, float* part, int pstride, int B, int max_frames, int n_mels, int Mp,
+                            hipStream_t st) {
+    const dim3 grid((max_frames + kMelChunk - 1) / kMelChunk, B);
+    hipLaunchKernelGGL(mel_bwd_partial_kernel<Bank>, grid, dim3(256), 0, st, dx0, xm, frame_off, pool_off, stats, part, pstride,
+                       n_mels, Mp);
+    hipLaunchKernelGGL(mel_bwd_apply_kernel<Bank>, grid, dim3(256), 0, st, dx0, xm, frame_off, pool_off, stats, gstat, part,
+                       pstride, n_mels, Mp);
+}
+
+// One launcher per direction: the clip form up to kMelClipFrames frames, else the chunked two-launch form; the 128-band
+// instantiations for the card's bank, else the any-bank ones.  n_mels <= 512 bands in rows of Mp >= n_mels floats
+// (Mp % 4 == 0); stats [B][Mp][4], part [B][pstride][2 Mp].
+void launch_mel_norm_fwd(const float* xm, const int* frame_off, const int* pool_off, float* x0, float* stats, float* gstat,
+                         float* part, int pstride, int B, int max_frames, int n_mels, int Mp, hipStream_t st, float* amax_out) {
+    const bool card = n_mels == 128;
     if (max_frames <= kMelClipFrames) {
-        hipLaunchKernelGGL(mel_any_clip_bwd_kernel, dim3(B), dim3(512), 0, st, dx0, xm, frame_off, pool_off, stats, gstat, n_mels, Mp);
+        if (card)
+            hipLaunchKernelGGL(mel_norm_clip_fwd_kernel, dim3(B), dim3(512), 0, st, xm, frame_off, pool_off, x0, stats, gstat, amax_out);
+        else
+            hipLaunchKernelGGL(mel_any_clip_fwd_kernel, dim3(B), dim3(512), 0, st, xm, frame_off, pool_off, x0, stats, gstat, n_mels, Mp);
         return;
     }
-    const int nx = (max_frames + kMelChunk - 1) / kMelChunk;
-    hipLaunchKernelGGL(mel_any_bwd_partial_kernel, dim3(nx, B), dim3(256), 0, st, dx0, xm, frame_off, pool_off, stats, part, pstride,
-                       n_mels, Mp);
-    hipLaunchKernelGGL(mel_any_bwd_apply_kernel, dim3(nx, B), dim3(256), 0, st, dx0, xm, frame_off, pool_off, stats, gstat, part,
-                       pstride, n_mels, Mp);
+    if (card)
+        mel_chunked_fwd<MelBank128>(xm, frame_off, pool_off, x0, stats, gstat, part, pstride, B, max_frames, n_mels, Mp, st);
+    else
+        mel_chunked_fwd<MelBankAny>(xm, frame_off, pool_off, x0, stats, gstat, part, pstride, B, max_frames, n_mels, Mp, st);
+}
+void launch_mel_norm_bwd(const float* dx0, float* xm, const int* frame_off, const int* pool_off, const float* stats,
+                         const float* gstat, float* part, int pstride, int B, int max_frames, int n_mels, int Mp, hipStream_t st) {
+    const bool card = n_mels == 128;
+    if (max_frames <= kMelClipFrames) {
+        if (card)
+            hipLaunchKernelGGL(mel_norm_clip_bwd_kernel, dim3(B), dim3(512), 0, st, dx0, xm, frame_off, pool_off, stats, gstat);
+        else
+            hipLaunchKernelGGL(mel_any_clip_bwd_kernel, dim3(B), dim3(512), 0, st, dx0, xm, frame_off, pool_off, stats, gstat, n_mels, Mp);
+        return;
+    }
+    if (card)
+        mel_chunked_bwd<MelBank128>(dx0, xm, frame_off, pool_off, stats, gstat, part, pstride, B, max_frames, n_mels, Mp, st);
+    else
+        mel_chunked_bwd<MelBankAny>(dx0, xm, frame_off, pool_off, stats, gstat, part, pstride, B, max_frames, n_mels, Mp, st);
 }
 void launch_in_lrelu_fwd(float* z, const int* frame_off, const int* pool_off, float* rstd, int C, int B, int max_pooled, hipStream_t st) {
     if (max_pooled <= 128)

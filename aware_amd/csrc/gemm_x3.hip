@@ -31,6 +31,7 @@
 #include "common.hpp"
 #include "split_bf16.hpp"
 #include "conv_block.hpp"
+#include "mel_norm.hpp"
 
 namespace aware {
 
@@ -509,9 +510,9 @@ __global__ __launch_bounds__(512, 2) void mel_front_x3_kernel(const float* __res
     q += __shfl_xor(q, 16);
     q += __shfl_xor(q, 32);
     const float M2 = q;
-    const float rs = 1.0f / sqrtf(M2 / fT + 1e-5f);                    // biased var, eps 1e-5 (InstanceNorm1d)
+    const float rs = mel_rs(M2, fT);
     // GlobalStandardize: unbiased std of the normalised tile (its mean is 0): sum over channels of rs^2 M2
-    float su = (kg == 0) ? rs * rs * M2 : 0.f;
+    float su = (kg == 0) ? mel_suu(rs, M2) : 0.f;
     su = wave_sum(su);
     __syncthreads();                                                   // every wave has left the K loop (LDS is reused below)
     if (lane == 0) red8[wave] = su;
@@ -522,12 +523,9 @@ __global__ __launch_bounds__(512, 2) void mel_front_x3_kernel(const float* __res
 #pragma unroll
         for (int e = 0; e < 4; ++e) Tm[16 * m + 4 * kg + e][c] = acc[m][0][e];
     __syncthreads();
-    const float suu = ((red8[0] + red8[1]) + (red8[2] + red8[3])) + ((red8[4] + red8[5]) + (red8[6] + red8[7]));
-    const float n = fT * 128.f;
-    const float gs = sqrtf(suu / (n - 1.f));
-    const float ginv = 1.0f / (gs + 1e-8f);
-    if (kg == 0) { float* stp = stats + ((size_t)b * 128 + c) * 4; stp[0] = mu; stp[1] = rs; stp[2] = M2; stp[3] = 0.f; }
-    if (tid == 0) { gstat[b * 4 + 0] = ginv; gstat[b * 4 + 1] = gs; gstat[b * 4 + 2] = n; gstat[b * 4 + 3] = fT; }
+    const MelClip k = mel_clip(mel_sum8(red8), fT, 128);
+    if (kg == 0) mel_write_stats(stats, (size_t)b * 128 + c, mu, rs, M2);
+    if (tid == 0) mel_write_gstat(gstat, b, k, fT);
     const int c4 = (lane & 31) * 4, rr = 2 * wave + (lane >> 5);
 #pragma unroll
     for (int j = 0; j < MT; ++j) {
@@ -542,8 +540,9 @@ __global__ __launch_bounds__(512, 2) void mel_front_x3_kernel(const float* __res
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const int tp = (m * 16 + 4 * kg) / 2 + h;
-            const float u0 = (acc[m][0][2 * h] - mu) * rs, u1 = (acc[m][0][2 * h + 1] - mu) * rs;
-            const float pv = tp < Tp ? 0.5f * (u0 * ginv + u1 * ginv) : 0.f;           // AvgPool1d(2, 2)
+            // (u inside the conditional: outside it the pair is no longer packed and the sum contracts, other bits)
+            const float pv = tp < Tp ? mel_pooled(mel_u(acc[m][0][2 * h], mu, rs), mel_u(acc[m][0][2 * h + 1], mu, rs), k.ginv)
+                                     : 0.f;
             Tm[tp][c] = pv;
             pmax = fmaxf(pmax, fabsf(pv));
         }
@@ -598,9 +597,8 @@ __global__ __launch_bounds__(512, 2) void mel_back_x3_kernel(const float* __rest
     // (an odd T has one more frame than pooled pairs: the tile may be taller than the clip's pooled rows; reads are clamped)
     x3_tile_gemm<RG, 8>(dZ, lda, Bpk, K, pool_off[b], 0, lds, acc, Tpad);
     const int c = wave * 16 + r16;
-    const float* stp = stats + ((size_t)b * 128 + c) * 4;
-    const float mu = stp[0], rs = stp[1], M2 = stp[2];
-    const float ginv = gstat[b * 4 + 0], gs = gstat[b * 4 + 1], n = gstat[b * 4 + 2];
+    const MelChan s = mel_read_stats(stats, (size_t)b * 128 + c);
+    const MelClip k = mel_read_gstat(gstat, b);
     float* x = xm + (size_t)f0 * 128 + c;
     float ua[MT][4], ub[MT][4];
 #pragma unroll
@@ -619,9 +617,9 @@ __global__ __launch_bounds__(512, 2) void mel_back_x3_kernel(const float* __rest
             const bool pair = m * 16 + 4 * kg + e < Tp;
             const float dv = pair ? 0.5f * acc[m][0][e] : 0.f;        // d(avg pool): half the pooled gradient to each frame
             acc[m][0][e] = dv;
-            ua[m][e] = (ua[m][e] - mu) * rs;                          // u
-            ub[m][e] = (ub[m][e] - mu) * rs;
-            if (pair) { a1 += 2.f * dv; a2 += dv * ua[m][e] + dv * ub[m][e]; }
+            ua[m][e] = mel_u(ua[m][e], s.mu, s.rs);
+            ub[m][e] = mel_u(ub[m][e], s.mu, s.rs);
+            if (pair) { a1 += 2.f * dv; a2 += mel_dv_u(dv, ua[m][e], ub[m][e]); }
         }
     a1 += __shfl_xor(a1, 16); a1 += __shfl_xor(a1, 32);
     a2 += __shfl_xor(a2, 16); a2 += __shfl_xor(a2, 32);
@@ -629,21 +627,16 @@ __global__ __launch_bounds__(512, 2) void mel_back_x3_kernel(const float* __rest
     const float w1 = wave_sum(kg == 0 ? D1 : 0.f), w2 = wave_sum(kg == 0 ? D2 : 0.f);
     if (lane == 0) { red8[0][wave] = w1; red8[1][wave] = w2; }
     __syncthreads();
-    const float sa = ((red8[0][0] + red8[0][1]) + (red8[0][2] + red8[0][3])) + ((red8[0][4] + red8[0][5]) + (red8[0][6] + red8[0][7]));
-    const float sb = ((red8[1][0] + red8[1][1]) + (red8[1][2] + red8[1][3])) + ((red8[1][4] + red8[1][5]) + (red8[1][6] + red8[1][7]));
-    const float fT = (float)T;
-    const float mdv = sa / n;
-    const float Q = (gs > 0.f) ? sb * ginv * ginv / ((n - 1.f) * gs) : 0.f;
-    const float m1 = ginv * (D1 / fT - mdv);
-    const float m2 = (ginv * D2 - Q * rs * rs * M2) / fT;
+    const MelClipGrad q = mel_clip_grad(mel_sum8(red8[0]), mel_sum8(red8[1]), k);
+    const MelChanGrad mg = mel_chan_grad(D1, D2, (float)T, s.rs, s.M2, k, q);
 #pragma unroll
     for (int m = 0; m < MT; ++m)
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const int t = 2 * (m * 16 + 4 * kg + e);
             const float dv = acc[m][0][e];
-            if (t < T) { const float u = ua[m][e]; x[(size_t)t * 128] = rs * (((dv - mdv) * ginv - u * Q) - m1 - u * m2); }
-            if (t + 1 < T) { const float u = ub[m][e]; x[(size_t)(t + 1) * 128] = rs * (((dv - mdv) * ginv - u * Q) - m1 - u * m2); }
+            if (t < T) x[(size_t)t * 128] = mel_bwd_value(dv, ua[m][e], s.rs, k.ginv, q, mg);
+            if (t + 1 < T) x[(size_t)(t + 1) * 128] = mel_bwd_value(dv, ub[m][e], s.rs, k.ginv, q, mg);
         }
 }
 

@@ -137,7 +137,7 @@ void launch_x3_pack_dev(const float* Wt_dev, int ldw, int Nvalid, int Kvalid, in
 bool gemm_clip_x3_supported(int nwm, int N, int K, int lda);
 // mel projection + InstanceNorm + GlobalStandardize + AvgPool of a UNIFORM batch of clips of T <= 192 frames in one launch
 // (one workgroup per clip): xm [NF][128] raw mel tile (kept for the backward), x0 pooled tile, stats / gstat as
-// launch_mel_norm_fwd leaves them
+// mel_norm.hpp lays them out
 bool mel_front_x3_supported(int T, int K, int lda);
 void launch_mel_front_x3(const float* mag, int lda, const void* melTpk, const int* frame_off, const int* pool_off, float* xm,
                          float* x0, float* stats, float* gstat, int B, int T, int K, hipStream_t st, float* amax_out = nullptr);
@@ -187,20 +187,17 @@ size_t readout_x3_image_bytes(int B, int nwm);      // scratch `img` of launch_r
 void launch_readout_grad_ragged_x3(const float* hin, int ci, const float* dZl, const void* WTpk, const float* rstd_prev, float* dZ,
                                    const int* frame_off, const int* pool_off, const int* order, int B, hipStream_t st,
                                    float* amax_out = nullptr);
-// mel block: InstanceNorm over time, per-clip GlobalStandardize, AvgPool(2,2).  Clips of up to kMelClipFrames frames take one
-// workgroup per clip, which also writes amax_out (as launch_mel_front_x3) when given; longer clips a chunked form, which does not
+// mel block (mel_norm.hpp): InstanceNorm over time, per-clip GlobalStandardize, AvgPool(2,2), for a bank of n_mels <= 512 bands
+// in rows of Mp >= n_mels floats (Mp % 4 == 0); stats [B][Mp][4], gstat [B][4], part [B][pstride][2 Mp] with pstride >=
+// ceil(max_frames / 32).  Padding channels get zero statistics, zero x0 columns and zero dL/dxm.  Clips of up to kMelClipFrames
+// frames take one workgroup per clip and leave part alone; longer clips a chunked form of two launches.  amax_out ([B][64], as
+// launch_mel_front_x3) is written by the 128-band clip form only: det_plan hands it over where that form runs
 constexpr int kMelClipFrames = 192;
-void launch_mel_norm_fwd(const float* xm, const int* frame_off, const int* pool_off, float* x0, float* stats,
-                         float* gstat, float* part, int pstride, int B, int max_frames, hipStream_t st,
+void launch_mel_norm_fwd(const float* xm, const int* frame_off, const int* pool_off, float* x0, float* stats, float* gstat,
+                         float* part, int pstride, int B, int max_frames, int n_mels, int Mp, hipStream_t st,
                          float* amax_out = nullptr);
 void launch_mel_norm_bwd(const float* dx0, float* xm_inout, const int* frame_off, const int* pool_off, const float* stats,
-                         const float* gstat, float* part, int pstride, int B, int max_frames, hipStream_t st);
-// the same for any bank: n_mels <= 512 bands in rows of Mp >= n_mels floats (Mp % 4 == 0); stats [B][Mp][4], part
-// [B][pstride][2 Mp].  Padding channels get zero statistics, zero x0 columns and zero dL/dxm
-void launch_mel_norm_fwd_any(const float* xm, const int* frame_off, const int* pool_off, float* x0, float* stats, float* gstat,
-                             float* part, int pstride, int B, int max_frames, int n_mels, int Mp, hipStream_t st);
-void launch_mel_norm_bwd_any(const float* dx0, float* xm_inout, const int* frame_off, const int* pool_off, const float* stats,
-                             const float* gstat, float* part, int pstride, int B, int max_frames, int n_mels, int Mp, hipStream_t st);
+                         const float* gstat, float* part, int pstride, int B, int max_frames, int n_mels, int Mp, hipStream_t st);
 // conv block tail: InstanceNorm over time + LeakyReLU(0.2), in place; saves rstd
 void launch_in_lrelu_fwd(float* z, const int* frame_off, const int* pool_off, float* rstd, int C, int B, int max_pooled,
                          hipStream_t st);

@@ -219,7 +219,7 @@ def test_detector_entry_points_long(rt, name):
     """aware_detector_forward / _backward on band magnitudes of 642, 63 and 1251 frames against the float64 restatement:
     values to 5e-5, the push_extremes magnitude gradient per clip to 1e-4 relative L2, every clip clear of a kink (by KINK,
     or by KINK_FLOOR where no seed reaches that).  The smooth networks cover norm_act_*_kernel<Instance / Affine, ., 0>,
-    relu_none the element-wise norm, m13_odd the any-bank chunked mel norm and odd widths, card64 readout_wide_kernel over
+    relu_none the element-wise norm, m13_odd the chunked mel norm on MelBankAny (mel_*_kernel<MelBankAny>) and odd widths, card64 readout_wide_kernel over
     625 pooled frames."""
     from aware_amd.utils.audio import default_plan
     plan = default_plan()
