@@ -2223,6 +2223,18 @@ extern "C" int aware_scan_segments(const float* win_conf, const int* win_view, c
     return AWARE_OK;
 }
 
+// ---- coded payloads: the Viterbi decoder (EXTENSION; service.detect_message, AWAREDetector.scan, runtime.viterbi_decode, tests) --
+extern "C" int aware_viterbi_decode(const float* values, int R, int L, float centre, int rate_n, int crc_bits, uint32_t* bits,
+                                    float* metric, int* valid, int* corrected, void* stream) {
+    if (!values || !bits || !metric || !valid || !corrected) return AWARE_E_BADARG;
+    if (R < 1 || R > kViterbiMaxRows || L < 1 || L > kViterbiMaxBits || (rate_n != 2 && rate_n != 3)) return AWARE_E_BADARG;
+    if ((crc_bits != 0 && crc_bits != 8 && crc_bits != 16) || !std::isfinite(centre)) return AWARE_E_BADARG;
+    if (L / rate_n - 6 - crc_bits < 1) return AWARE_E_BADARG;
+    launch_viterbi(values, R, L, centre, rate_n, crc_bits, bits, metric, valid, corrected, (hipStream_t)stream);
+    LAUNCHCHK();
+    return AWARE_OK;
+}
+
 // ---- the phase vocoder's two kernels alone on a ragged spectrum (EXTENSION; runtime.pv_frames, runtime.pv_stretch, tests) -----
 extern "C" int aware_pv_frames(const void* spec, const int* frame_off, int B, const int* mq, void* out, void* stream) {
     if (!spec || !frame_off || !mq || !out || spec == out || B < 1 || B > 65535) return AWARE_E_BADARG;

@@ -587,4 +587,12 @@ struct ScanSegments {
 };
 void launch_scan_segments(const ScanSegments& S, hipStream_t st);
 
+// ---- viterbi_kernels.hip: coded payloads (EXTENSION).  values [R][L] -> per row the T = L / n decoded input bits packed
+// into ceil(T / 32) words, the final path metric, the CRC's verdict and the count of corrected positions; one wave per row
+constexpr int kViterbiMaxBits = 512;   // L: T <= 256 steps, four survivor registers per lane
+constexpr int kViterbiMaxRows = 1 << 20;
+constexpr int kViterbiRows = 4;        // rows (waves) per workgroup
+void launch_viterbi(const float* values, int R, int L, float centre, int n, int c, unsigned* bits, float* metric, int* valid,
+                    int* corrected, hipStream_t st);
+
 }  // namespace aware

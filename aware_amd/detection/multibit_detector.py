@@ -4,7 +4,9 @@ Reference: src/AWARE/detection/multibit_detector.py:9-42 -- normalise, STFT, mag
 bins outside the embedding band, network forward.  Batched entry point: detect_batch.  EXTENSION: sync_search = n reads n views of every clip, 512 / n samples
 apart, and keeps the most confident one (detection/sync.py); off by default.  EXTENSION: speed_search reads every clip at
 candidate playback speeds as well (same module); off by default.  EXTENSION: scan reads a long file in windows and returns the
-marked spans with one payload each (same module); off unless called."""
+marked spans with one payload each (same module); off unless called.  EXTENSION: payload_code names the
+channel code of the payload (utils/watermark/fec.py): decode_messages runs the Viterbi decoder over rows
+of values, and scan() adds the decoded message to every span; absent = no code."""
 from __future__ import annotations
 
 import numpy as np
@@ -12,6 +14,7 @@ import torch
 
 from ..interfaces import BaseDetector
 from ..utils.audio import STFT, STFTDecomposer, WaveformNormalizer, band_bins, get_plan
+from ..utils.watermark import fec
 from .. import runtime as rt
 from . import sync
 
@@ -19,12 +22,15 @@ from . import sync
 class AWAREDetector(BaseDetector):
     def __init__(self, model, threshold: float = 0.0, frame_length: int = 1024, hop_length: int = 256,
                  window: str = "hann", win_length: int = 1024, pattern_mode: str = "bits2bipolar",
-                 embedding_bands=(500, 4000), sync_search: int = 0, speed_search=None, scan=None):
+                 embedding_bands=(500, 4000), sync_search: int = 0, speed_search=None, scan=None, payload_code=None):
         rt.require_card_geometry("AWAREDetector", frame_length, hop_length, win_length)
         self.sync_search = sync.check_sync_search(sync_search)
         self.speed_search = sync.check_speed_search(speed_search)
         self.scan_defaults = sync.check_scan_card(scan)           # what scan() uses where its arguments are None
         self.scan_rows_per_call = sync.SYNC_MAX_ROWS              # rows per aware_detect call of scan()
+        self.payload_code = fec.check_payload_code(payload_code)  # the channel code of service.detect_message and scan()
+        if self.payload_code:
+            fec.capacity(model.output_length, **self.payload_code)            # ValueError where no message bit is left
         self.threshold = threshold
         self.device = torch.device("cuda")
         self.pattern_mode = pattern_mode
@@ -45,6 +51,19 @@ class AWAREDetector(BaseDetector):
     def _centre(self) -> float:
         """What an undecided read-out value is: 0.5 behind a sigmoid, 0 otherwise."""
         return 0.5 if getattr(self.detection_net, "final_activation", "tanh") == "sigmoid" else 0.0
+
+    def decode_messages(self, values) -> list:
+        """values [R, L] (device tensor or numpy) of coded frames -> per row {"message" int32 [k], "bytes" (the first k // 8
+        bytes), "valid", "corrected", "metric"}: one aware_viterbi_decode over all rows.  ValueError without a payload_code."""
+        code = self.payload_code
+        if not code:
+            raise ValueError("decode_messages: this detector has no payload_code")
+        v = torch.as_tensor(values, dtype=torch.float32).to(self.device)
+        k = fec.capacity(v.shape[-1], **code)
+        out = {name: t.cpu().numpy() for name, t in rt.viterbi_decode(v, self._centre(), code["rate"], code["crc"]).items()}
+        bits = fec.unpack_bits(out["bits"], k)
+        return [{"message": bits[r], "bytes": fec.message_bytes(bits[r]), "valid": bool(out["valid"][r]),
+                 "corrected": int(out["corrected"][r]), "metric": float(out["metric"][r])} for r in range(len(bits))]
 
     def detect_batch(self, clips, sample_rate: int, sync_search=None, return_sync: bool = False, speed_search=None,
                      return_speed: bool = False):
@@ -146,7 +165,8 @@ class AWAREDetector(BaseDetector):
         defaults are the detector's scan_defaults (the card key `scan`).  A span is a dict of `start` and `end` (samples: the
         first window's start, the last window's start plus the window length), `peak` (samples: the most confident window's
         start plus its view's offset), `confidence` (that window's), `values` [n_bits] float32 (the confidence-weighted mean of
-        the span's windows: decode these) and `windows` (first, last: indices into the profile).  return_profile: (spans,
+        the span's windows: decode these) and `windows` (first, last: indices into the profile); with a payload_code on the
+        detector also `message`, `valid` and `corrected` of decode_messages (valid informs; it does not filter).  return_profile: (spans,
         profiles) instead, a profile per file being a dict of `starts` (the window starts), `length` (samples per window),
         `win_conf`, `win_view` and `win_values` (numpy, per window: the best view's confidence, index and row) and `n_segments` (the true span count, which max_segments may have cut).
         ValueError, before any launch: a parameter check_scan refuses, a file too short (by its index), speed_search on."""
@@ -197,6 +217,10 @@ class AWAREDetector(BaseDetector):
             profiles.append({"starts": list(starts), "length": length, "win_conf": conf_h[win_off[b]:win_off[b + 1]].copy(),
                              "win_view": view_h[win_off[b]:win_off[b + 1]].copy(),
                              "win_values": rows_h[win_off[b]:win_off[b + 1]].copy(), "n_segments": int(host["n_seg"][b])})
+        every = [s for found in spans for s in found]
+        if self.payload_code and every:                           # one decode over all spans of all files
+            for s, m in zip(every, self.decode_messages(np.stack([s["values"] for s in every]))):
+                s.update(message=m["message"], valid=m["valid"], corrected=m["corrected"])
         return (spans, profiles) if return_profile else spans
 
     def detect_device(self, audio: torch.Tensor, batch: "rt.Batch", sample_rate: int) -> torch.Tensor:

@@ -17,6 +17,7 @@ from ..interfaces import BaseEmbedder
 from ..utils.audio import ISTFT, STFT, STFTAssembler, STFTDecomposer, WaveformNormalizer, band_bins, get_plan
 from ..utils.logger import logger
 from .. import runtime as rt
+from ..utils.watermark import fec
 from .loop_attacks import parse_chain, parse_mixture
 from .losses import get_loss_fn
 from .optimizers import get_optimizer, is_card_default
@@ -28,13 +29,15 @@ class AWAREEmbedder(BaseEmbedder):
                  pattern_mode: str = "bits2bipolar", embedding_bands=(500, 4000), tolerance_db: float = 6.0,
                  num_iterations: int = 400, detection_net_cfg: dict = None, optimizer_cfg: dict = None,
                  scheduler_cfg: dict = None, loss: str = "push", verbose: bool = True, use_graph: bool = True,
-                 loop_attacks=None, loop_attack_seed: int = 0, loop_attack_mixture=None):
+                 loop_attacks=None, loop_attack_seed: int = 0, loop_attack_mixture=None, payload_code=None):
         """loop_attacks (EXTENSION, see embedding/loop_attacks.py): a chain of attacks applied inside the optimisation loop,
         e.g. [{"kind": "gaussian_noise", "snr_db": 10.0}, {"kind": "sample_suppression", "seconds": 0.3, "prob": 0.75}];
         clip i of a batch draws with seed loop_attack_seed + i.  None: the reference's loop (clean synthesis only).
         loop_attack_mixture (EXTENSION): a list of {"weight": w, "chain": [...]}; every clip draws one of the chains (or, with
         what the weights leave of 1, none) afresh at every step, so one watermark meets several attack families.  Giving
-        both loop_attacks and loop_attack_mixture is a ValueError."""
+        both loop_attacks and loop_attack_mixture is a ValueError.
+        payload_code (EXTENSION, utils/watermark/fec.py): {"rate": "1/2" or "1/3", "crc": 0, 8 or 16}, the channel code of
+        service.embed_message; None: no code.  embed() itself is not changed by it."""
         rt.require_card_geometry("AWAREEmbedder", frame_length, hop_length, win_length)
         self.frame_length, self.hop_length, self.window, self.win_length = frame_length, hop_length, window, win_length
         self.device = torch.device("cuda")
@@ -44,6 +47,9 @@ class AWAREEmbedder(BaseEmbedder):
         self.pattern_mode = pattern_mode
         self.detection_net = AWAREDetectorNet(**(detection_net_cfg or {}))
         self.detection_net.embedding_bands = self.embedding_bands
+        self.payload_code = fec.check_payload_code(payload_code)      # ValueError naming the key
+        if self.payload_code:
+            fec.capacity(self.detection_net.output_length, **self.payload_code)   # ValueError where no message bit is left
         optimizer_cfg = optimizer_cfg or {"name": "nadam", "params": {"lr": 0.1}}
         scheduler_cfg = scheduler_cfg or {"name": "reduce_lr_on_plateau", "params": {"factor": 0.9, "patience": 500}}
         self.optimizer_name, self.optimizer_params = optimizer_cfg["name"], optimizer_cfg.get("params", {}) or {}

@@ -1180,6 +1180,29 @@ def scan_segments(win_conf: torch.Tensor, win_view: torch.Tensor, win_values: to
     return out
 
 
+def viterbi_decode(values: torch.Tensor, centre: float, rate: str, crc: int) -> dict:
+    """utils.watermark.fec.viterbi_decode on the device (aware_viterbi_decode): values [R, L] float32, one coded frame per
+    row -> {"bits" [R, ceil(T / 32)] int32: the T = L // n decoded input bits, bit t at bit t % 32 of word t // 32
+    (fec.unpack_bits); "metric" [R] float32; "valid" [R] bool; "corrected" [R] int32}.  One launch over all rows."""
+    from .utils.watermark import fec
+    n, c = len(fec.RATES[fec.check_rate(rate)]), fec.check_crc(crc)
+    if values.dim() != 2 or not 1 <= values.shape[0] <= fec.MAX_ROWS or not 1 <= values.shape[1] <= fec.MAX_BITS:
+        raise ValueError(f"viterbi_decode: values [R, L] with R in 1..{fec.MAX_ROWS} and L in 1..{fec.MAX_BITS} are required; "
+                         f"got {tuple(values.shape)}")
+    if not math.isfinite(float(centre)):
+        raise ValueError(f"viterbi_decode: centre = {centre} is not finite")
+    R, L = values.shape
+    fec.capacity(L, rate, c)                                      # ValueError where the frame holds no message bit
+    v = values.contiguous().float()
+    bits = torch.empty((R, (L // n + 31) // 32), dtype=torch.int32, device=v.device)
+    metric = torch.empty(R, dtype=torch.float32, device=v.device)
+    valid = torch.empty(R, dtype=torch.int32, device=v.device)
+    corrected = torch.empty(R, dtype=torch.int32, device=v.device)
+    check(load_library().aware_viterbi_decode(_ptr(v), R, L, float(centre), n, c, _ptr(bits), _ptr(metric), _ptr(valid),
+                                              _ptr(corrected), _stream()), "aware_viterbi_decode")
+    return {"bits": bits, "metric": metric, "valid": valid != 0, "corrected": corrected}
+
+
 def speed_views(x: Ragged, ms, out: torch.Tensor | None = None):
     """The views of detection.sync's speed search (aware_speed_views): every clip of x at every speed offset of ms, in one
     launch -> (flat float32 device tensor, view lengths, view offsets into it), both clip-major lists of x.B * len(ms); view

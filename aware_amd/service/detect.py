@@ -2,7 +2,9 @@
 stereo [N,2] (per bit, the channel with the larger |value| wins, :23-37), then PatternDecoder.
 EXTENSION: sync_search = n runs the detector's offset search (detection/sync.py); None keeps the detector's own setting.
 EXTENSION: speed_search runs its speed search (same module), likewise.
-EXTENSION: scan_watermark reads a long recording in windows and returns its marked spans, one payload each (same module)."""
+EXTENSION: scan_watermark reads a long recording in windows and returns its marked spans, one payload each (same module).
+EXTENSION: detect_message reads the message of a coded payload (utils/watermark/fec.py), and with a
+payload_code on the detector every span of a scan carries its decoded message."""
 import numpy as np
 
 from ..utils.logger import logger
@@ -64,8 +66,10 @@ def _scan(detector, files, sample_rate, options):
         raise ValueError("Invalid sample rate. Expected 16000Hz.")
     decode = PatternDecoder(encoder_mode=detector.pattern_mode, threshold=detector.threshold)
     found = detector.scan([np.asarray(f, dtype=np.float32) for f in files], sample_rate, **options)
-    return [[{"start": s["start"], "end": s["end"], "peak": s["peak"], "confidence": s["confidence"],
-              "payload": decode(s["values"]), "values": s["values"]} for s in spans] for spans in found]
+    coded = ("message", "valid", "corrected")                   # what a detector with a payload_code adds to a span
+    return [[dict({"start": s["start"], "end": s["end"], "peak": s["peak"], "confidence": s["confidence"],
+                   "payload": decode(s["values"]), "values": s["values"]}, **{k: s[k] for k in coded if k in s})
+             for s in spans] for spans in found]
 
 
 def _scan_stereo(left, right, max_flip: int, centre: float = 0.0):
@@ -99,7 +103,8 @@ def _scan_stereo(left, right, max_flip: int, centre: float = 0.0):
 def scan_watermark(audio: np.ndarray, sample_rate: int, detector, **options):
     """The marked spans of a long recording (AWAREDetector.scan; options: its keywords window_seconds, hop_samples,
     sync_search, min_confidence, max_flip, max_segments): a list of dicts, in order, of `start`, `end` and `peak` (samples),
-    `confidence`, `payload` (the span's values through PatternDecoder) and `values`.  16 kHz only; mono 1-D, or stereo
+    `confidence`, `payload` (the span's values through PatternDecoder) and `values`, and with a payload_code on the detector
+    `message`, `valid` and `corrected` of the span's decoded frame (valid informs; it does not filter).  16 kHz only; mono 1-D, or stereo
     [N, 2]: both channels are scanned, and of two spans, one per channel, that are each other's largest overlap and read
     the same payload to within max_flip bits the more confident one is kept (_scan_stereo)."""
     audio = np.asarray(audio)
@@ -117,3 +122,46 @@ def scan_watermark(audio: np.ndarray, sample_rate: int, detector, **options):
 def scan_watermark_batch(files, sample_rate: int, detector, **options):
     """scan_watermark for a list of mono recordings of any lengths, in one scan: a list of span lists."""
     return _scan(detector, files, sample_rate, options)
+
+
+def _coded(detector):
+    if not getattr(detector, "payload_code", None):
+        raise ValueError("detect_message: the detector has no payload_code (model card key `payload_code`)")
+
+
+def _messages(detector, values):
+    """decode_messages on rows of values, each result with its `values` row."""
+    rows = values.detach().cpu().numpy()
+    return [dict(m, values=rows[r]) for r, m in enumerate(detector.decode_messages(values))]
+
+
+def detect_message(audio: np.ndarray, sample_rate: int, detector, sync_search=None, speed_search=None):
+    """EXTENSION: the message of a clip that embed_message marked (the detector's payload_code; utils/watermark/fec.py): the
+    existing detection, searches included, then the Viterbi decoder (one aware_viterbi_decode) -> {"message": the k decoded
+    bits, "bytes": their first k // 8 bytes, "valid": the CRC's verdict (with a CRC of 0 bits: a finite metric), "corrected":
+    the positions the decoder changed, "metric", "values"}.  16 kHz only; mono 1-D, or stereo [N, 2]: both channels are
+    decoded and the valid one is kept, of two valid ones (or none) the one with the larger metric, the left one on a tie."""
+    if sample_rate != 16000:
+        logger.error(f"Invalid sample rate. Expected 16000Hz, got {sample_rate}Hz.")
+        raise ValueError("Invalid sample rate. Expected 16000Hz.")
+    _coded(detector)
+    audio = np.asarray(audio)
+    if audio.ndim == 2 and audio.shape[1] == 2:
+        l, r = _messages(detector, _detect(detector, [audio[:, 0].astype(np.float32), audio[:, 1].astype(np.float32)],
+                                           sample_rate, sync_search, speed_search))
+        if l["valid"] != r["valid"]:
+            return l if l["valid"] else r
+        return r if r["metric"] > l["metric"] else l
+    if audio.ndim == 1:
+        return _messages(detector, _detect(detector, [audio.astype(np.float32)], sample_rate, sync_search, speed_search))[0]
+    logger.error("Invalid audio shape. Expected 1D or 2D numpy array.")
+    raise ValueError("Invalid audio shape. Expected 1D or 2D numpy array.")
+
+
+def detect_message_batch(clips, sample_rate: int, detector, sync_search=None, speed_search=None):
+    """detect_message for a list of mono clips of any lengths: one detection, one decode over all clips; a list of dicts."""
+    if sample_rate != 16000:
+        raise ValueError("Invalid sample rate. Expected 16000Hz.")
+    _coded(detector)
+    return _messages(detector, _detect(detector, [np.asarray(c, dtype=np.float32) for c in clips], sample_rate, sync_search,
+                                       speed_search))

@@ -3,12 +3,13 @@
 Same checks and the same ValueErrors in the same order: 16 kHz only (:24-26), watermark length
 == detector output_length (:32-34), mono [N] / [N,1] or stereo [N,2] (:37, :61, :75-77), silence
 gate (:47-49, :65-67), rescale by the SIGNED maximum of the input (:69, :73).  Stereo is two
-independent mono problems (:52-53) -- here they run as one batch of two clips."""
+independent mono problems (:52-53) -- here they run as one batch of two clips.
+EXTENSION: embed_message / embed_message_batch embed a message as a coded frame (utils/watermark/fec.py)."""
 import numpy as np
 
 from ..utils.audio import SilenceChecker
 from ..utils.logger import logger
-from ..utils.watermark import PatternEncoder
+from ..utils.watermark import PatternEncoder, fec
 
 _SILENT_MSG = "Signal you provided doesn't contain any speach. Please provide signal that contains speach."
 
@@ -60,3 +61,29 @@ def embed_watermark_batch(clips, sample_rate: int, watermark_bits, model):
     mx = np.array([np.max(c) for c in clips], dtype=np.float32)
     outs = model.embed_batch([np.asarray(c, dtype=np.float32) for c in clips], sample_rate, wms, rescale=mx)
     return [o.cpu().numpy() for o in outs]
+
+
+def _frame(message, model):
+    """The frame of a message (utils/watermark/fec.py) for the embedder's payload_code, as bits for its PatternEncoder."""
+    code = getattr(model, "payload_code", None)
+    if not code:
+        raise ValueError("embed_message: the embedder has no payload_code (model card key `payload_code`)")
+    if model.pattern_mode != "bits2bipolar":
+        raise ValueError(f"embed_message: pattern_mode {model.pattern_mode!r}; a coded frame is embedded as bits2bipolar")
+    return fec.encode_frame(message, model.detection_net.output_length, code["rate"], code["crc"])
+
+
+def embed_message(audio: np.ndarray, sample_rate: int, message, embedder) -> np.ndarray:
+    """EXTENSION: embed_watermark with the payload a coded frame of `message`: a bit array of exactly
+    fec.capacity(output_length, rate, crc) bits, or bytes that fit (padded with zero bits).  Same checks, stereo as there."""
+    if sample_rate != 16000:
+        logger.error(f"Invalid sample rate. Expected 16000Hz, got {sample_rate}Hz.")
+        raise ValueError("Invalid sample rate. Expected 16000Hz.")
+    return embed_watermark(audio, sample_rate, _frame(message, embedder), embedder)
+
+
+def embed_message_batch(clips, sample_rate: int, messages, embedder):
+    """EXTENSION: embed_watermark_batch with one message per clip, each as embed_message takes it."""
+    if sample_rate != 16000:
+        raise ValueError("Invalid sample rate. Expected 16000Hz.")
+    return embed_watermark_batch(clips, sample_rate, [_frame(m, embedder) for m in messages], embedder)

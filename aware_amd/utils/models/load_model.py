@@ -21,7 +21,9 @@ _EMBEDDER = {"pattern_mode": ("pattern_mode", "bits2bipolar"), "tolerance_db": (
              # EXTENSION (embedding/loop_attacks.py): attacks inside the optimisation loop; absent = none
              "loop_attacks": ("loop_attacks", None), "loop_attack_seed": ("loop_attack_seed", 0),
              # EXTENSION: one of several chains drawn per clip and step; absent = none, and not beside loop_attacks
-             "loop_attack_mixture": ("loop_attack_mixture", None)}
+             "loop_attack_mixture": ("loop_attack_mixture", None),
+             # EXTENSION (utils/watermark/fec.py): the channel code of service.embed_message / detect_message; absent = none
+             "payload_code": ("payload_code", None)}
 _DETECTOR = {"threshold": ("threshold", 0.0), "pattern_mode": ("pattern_mode", "bipolar"),
              # EXTENSION (detection/sync.py): offset search in detection; absent = off
              "sync_search": ("sync_search", 0),
@@ -29,7 +31,9 @@ _DETECTOR = {"threshold": ("threshold", 0.0), "pattern_mode": ("pattern_mode", "
              "speed_search": ("speed_search", None),
              # EXTENSION (detection/sync.py): the defaults of AWAREDetector.scan; absent = window_seconds 1.0,
              # hop_samples 4096, min_confidence 0.06, max_segments 16
-             "scan": ("scan", None)}
+             "scan": ("scan", None),
+             # EXTENSION (utils/watermark/fec.py): as the embedder's
+             "payload_code": ("payload_code", None)}
 
 
 def _pick(card: dict, table: dict) -> dict:

@@ -858,6 +858,25 @@ int aware_scan_segments(const float* win_conf, const int* win_view, const float*
                         int max_flip, int max_segments, int* n_seg, int* seg_first, int* seg_last, int* seg_peak,
                         int* seg_view, float* seg_conf, float* seg_values, void* stream);
 
+/* ---- coded payloads: the Viterbi decoder (EXTENSION, no counterpart in the reference) -------------------------------------
+ * A payload may be a frame of a zero-terminated convolutional code of constraint length 7 with a CRC (the definition is
+ * aware_amd/utils/watermark/fec.py): rate_n = 2 has the generators (0171, 0133), rate_n = 3 has
+ * (0133, 0171, 0165).  This entry decodes R rows of detector outputs in one launch on `stream`, one wave per row:
+ *   values [R][L] f32;  y_i = values[r][i] - centre, 0 where that is not finite;  T = L / rate_n steps, the last
+ *   L - rate_n T values ignored;  k = T - 6 - crc_bits message bits.  Path metrics in f32 from 0 for state 0 and -inf
+ *   elsewhere; the metric of the branch from s_x = ((d & 31) << 1) | x into d is ((pm[s_x] + o_0 y_nt) + o_1 y_nt+1) + o_2 y_nt+2
+ *   with o_g = +-1 the branch's output bit, every addition rounded on its own; x = 1 exactly where m_1 > m_0.
+ *   bits [R][ceil(T / 32)] u32: bit t % 32 of word t / 32 is the decoded input bit of step t (message, CRC MSB first, 6 tail
+ *   bits), traced back from state 0, the unused bits zero;  metric[r] = pm[0] after the last step;
+ *   valid[r] = 1 where the metric is finite and (crc_bits > 0) the decoded CRC equals the CRC of the decoded message (bitwise,
+ *   MSB first, register all ones at the start, no final xor; polynomial 0x07 or 0x1021), else 0;
+ *   corrected[r] = the positions i < rate_n T where (y_i > 0) differs from the re-encoded decoded sequence.
+ * AWARE_E_BADARG, before anything is launched: a null pointer, R outside 1..2^20, L outside 1..512, rate_n not 2 or 3,
+ * crc_bits not 0, 8 or 16, a centre that is not finite, L / rate_n - 6 - crc_bits < 1.  Added without a version step:
+ * callers detect the addition by symbol. */
+int aware_viterbi_decode(const float* values, int R, int L, float centre, int rate_n, int crc_bits, uint32_t* bits,
+                         float* metric, int* valid, int* corrected, void* stream);
+
 /* ---- bare GEMM (tests / roofline): C[M][N] = A[M][K] * Bt[N][K]^T + bias ------------------------------ */
 int aware_gemm_nt(const float* A, int lda, const float* Bt, int ldb, const float* bias, float* C, int ldc,
                   int M, int N, int K, void* stream);
