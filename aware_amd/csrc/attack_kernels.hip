@@ -62,12 +62,14 @@ __global__ __launch_bounds__(256) void upfirdn_kernel(const float* __restrict__ 
     for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < n_out; j += gridDim.x * blockDim.x) {
         const long pos = (long)j * down + half_len;
         int i_hi = (int)(pos / up);
-        long tap = pos - (long)i_hi * up;               // tap index for i = i_hi
-        int i_lo = i_hi - (int)((nh - 1 - tap) / up);
-        if (i_lo < 0) i_lo = 0;
-        if (i_hi > n_in - 1) i_hi = n_in - 1;
+        const long tap = pos - (long)i_hi * up;         // tap index for i = i_hi
         float acc = 0.f;
-        for (int i = i_lo; i <= i_hi; ++i) acc += x[i] * h[pos - (long)i * up];
+        if (tap < nh) {                                 // nh < up: a phase past the filter's end has no tap and reads nothing
+            int i_lo = i_hi - (int)((nh - 1 - tap) / up);
+            if (i_lo < 0) i_lo = 0;
+            if (i_hi > n_in - 1) i_hi = n_in - 1;
+            for (int i = i_lo; i <= i_hi; ++i) acc += x[i] * h[pos - (long)i * up];
+        }
         y[j] = acc;
     }
 }
@@ -141,6 +143,7 @@ __global__ __launch_bounds__(kIirChunks + 64) void iir_kernel(const float* __res
 #pragma unroll
     for (int k = 0; k < NC; ++k) { bb[k] = bc[(size_t)b * NC + k]; aa[k] = ac[(size_t)b * NC + k]; }
     const int n = len[b];
+    if (n < 1) return;                           // the whole workgroup: an empty clip has no chunk length (L = 0 below)
     const float* x = in + off[b];
     double* od = reinterpret_cast<double*>(outv) + off[b];
     float* of = reinterpret_cast<float*>(outv) + off[b];

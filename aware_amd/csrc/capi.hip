@@ -2796,7 +2796,7 @@ extern "C" int aware_waveform_normalize(const float* in, float* out, const int* 
 extern "C" int aware_upfirdn(const float* in, const int* in_off, const int* in_len, float* out, const int* out_off,
                              const int* out_len, int B, int max_out, const float* h, int nh, int up, int down,
                              int half_len, void* stream) {
-    if (!in || !out || !h || B < 1 || up < 1 || down < 1) return AWARE_E_BADARG;
+    if (!in || !out || !h || B < 1 || nh < 1 || up < 1 || down < 1 || half_len < 0) return AWARE_E_BADARG;
     launch_upfirdn(in, in_off, in_len, out, out_off, out_len, h, nh, up, down, half_len, B, max_out,
                    (hipStream_t)stream);
     LAUNCHCHK();

@@ -915,6 +915,8 @@ def upfirdn(x: Ragged, h: torch.Tensor, up: int, down: int, half_len: int) -> Ra
 
 def iir(x: Ragged, b: np.ndarray, a: np.ndarray, zi: np.ndarray | None = None, filtfilt=False, out_f64=False) -> Ragged:
     """b, a: [B, ncoef] float64 (a[:,0] == 1) per clip; zi [B, ncoef-1] for filtfilt."""
+    if min(x.lengths) < 1:                                  # aware_iir cannot see the device lengths: its precondition
+        raise ValueError("iir: every clip needs at least one sample")
     lib = load_library()
     dev = x.data.device
     bd = torch.as_tensor(np.ascontiguousarray(b, dtype=np.float64), device=dev)

@@ -423,7 +423,8 @@ int aware_pcm_quantize(const float* in, float* out, const int* off, const int* l
 int aware_waveform_normalize(const float* in, float* out, const int* off, const int* len, int B, int max_len,
                              void* scratch, void* stream);
 /* scipy.signal.resample_poly's polyphase core (Resample.apply :290-293, scripts/test.py:60-63):
- * out[j] = sum_i in[i] * h[j*down - i*up + half_len], fp32.  h: dev f32 [nh] (already scaled by up). */
+ * out[j] = sum_i in[i] * h[j*down - i*up + half_len], fp32.  h: dev f32 [nh] (already scaled by up), nh >= 1 and
+ * half_len >= 0.  Any nh is served: with nh < up some output phases meet no tap, and those outputs are 0. */
 int aware_upfirdn(const float* in, const int* in_off, const int* in_len, float* out, const int* out_off,
                   const int* out_len, int B, int max_out, const float* h, int nh, int up, int down,
                   int half_len, void* stream);
@@ -437,8 +438,10 @@ int aware_decimate_interp(const float* in, const int* off, const int* len, int B
  * out is f64 when out_f64 != 0 (the reference returns float64 from lfilter), else f32.
  * scratch (filtfilt): dev f64 [B][max_len + 6*ncoef].  2 <= ncoef <= 12.  A filtfilt clip must be longer than the
  * padding of 3*ncoef samples (scipy raises for such a clip; the host binding does the same, the kernel only stays inside
- * its buffers).  One workgroup per clip, parallel in time (128 chunks chained with a double-double state transition):
- * results agree with scipy's sequential recurrence to the rounding of that recurrence itself. */
+ * its buffers).  PRECONDITION: every len[b] >= 1.  The lengths live on the device, so this call cannot check them: the
+ * host binding refuses a batch with an empty clip, and a direct caller must do the same (the kernel leaves an empty
+ * clip's workgroup at once and writes nothing for it).  One workgroup per clip, parallel in time (128 chunks chained
+ * with a double-double state transition): results agree with scipy's sequential recurrence to the rounding of that recurrence itself. */
 int aware_iir(const float* in, const int* off, const int* len, int B, int max_len, void* out, int out_f64,
               const double* b, const double* a, const double* zi, int ncoef, int filtfilt,
               void* scratch, void* stream);
