@@ -60,8 +60,12 @@ struct aware_plan {
     PlanDev dev;
     void* mem = nullptr;
     // general-geometry plans (stft_any.hip): every geometry other than the card's, or any geometry created with
-    // AWARE_PLAN_GENERAL.  Only the four transform entry points accept them.
-    int general = 0;
+    // AWARE_PLAN_GENERAL.  The transforms run on stft_any.hip, the embed / detect loop on the general route (loop_any.hip).
+    // loop: created with AWARE_PLAN_GENERAL, which also opens the embed / detect loop on it; a plan that is general only
+    // because its geometry is not the card's serves the transforms alone, and the loop's entry points refuse it with
+    // AWARE_E_UNSUPPORTED before they read another argument.  band_ok: the band lies inside bins 0..n_fft/2 (a plan made for
+    // the transforms may carry any band; the loop refuses it)
+    int general = 0, loop = 0, band_ok = 1;
     int n_fft = kNfft, hop = kHop, win_length = kNfft, window = 0;
     GenPlanDev gdev;
     std::vector<float> w2h, envh;       // host copies of the squared window and the envelope tables (NOLA check)
@@ -96,6 +100,8 @@ struct aware_detector {
     int n_mels = 0, n_layers = 0, nbits = 0;
     int band_lo = 0, nband = 0;
     int stride = kFS;        // floats per band row of the plan the detector was created for
+    int n_fft = kNfft;       // ... and its transform size: the mel basis handed over is [n_mels][n_fft/2 + 1]
+    bool general = false;    // created for a general plan: dense mel operands only (the tap forms belong to the card kernels)
     // channel counts as the caller gave them (uch) and as stored (ch, stored_channels): ch[0] = Mp >= n_mels is the row
     // stride of the mel stage; padding channels have zero weights, bias and melT rows and get a zero gradient
     std::vector<int> uch, ch;
@@ -193,7 +199,7 @@ static int gen_validate(int n_fft, int hop, int win_length, int window) {
 }
 
 static int gen_plan_create(aware_plan** out, int n_fft, int hop, int win_length, int window, int band_lo_bin,
-                           int band_hi_bin) {
+                           int band_hi_bin, int flags) {
     const int rc = gen_validate(n_fft, hop, win_length, window);
     if (rc != AWARE_OK) return rc;
     const int N = n_fft, M = N / 2;
@@ -232,6 +238,7 @@ static int gen_plan_create(aware_plan** out, int n_fft, int hop, int win_length,
     }
     const float* d = (const float*)p->mem;
     p->general = 1;
+    p->loop = (flags & AWARE_PLAN_GENERAL) ? 1 : 0;
     p->n_fft = N; p->hop = hop; p->win_length = win_length; p->window = window;
     p->gdev.n_fft = N; p->gdev.hop = hop; p->gdev.stride = gen_stride(N);
     p->gdev.th = (const cf*)(d + o_th);
@@ -239,9 +246,12 @@ static int gen_plan_create(aware_plan** out, int n_fft, int hop, int win_length,
     p->gdev.window = d + o_w;
     p->gdev.window2 = d + o_w2;
     p->gdev.env = d + o_env;
-    p->dev.band_lo = band_lo_bin;                 // (not used by the general kernels)
+    // band rows of the loop: nband columns rounded up to whole 64-column chunks (K % 64 == 0 for the mel GEMMs, one wave
+    // per chunk in loop_any.hip); 2112 floats for all 2049 bins of n_fft 4096
+    p->dev.band_lo = band_lo_bin;
     p->dev.nband = band_hi_bin - band_lo_bin + 1;
-    p->dev.stride = kFS;
+    p->band_ok = band_lo_bin >= 0 && band_hi_bin <= N / 2 && p->dev.nband >= 1;
+    p->dev.stride = p->band_ok ? (p->dev.nband + 63) & ~63 : kFS;
     p->w2h = w2;
     p->envh = env;
     *out = p;
@@ -257,7 +267,7 @@ extern "C" int aware_plan_create_ex(aware_plan** out, int n_fft, int hop, int wi
                                     int band_hi_bin, int flags) {
     if (!out || (flags & ~AWARE_PLAN_GENERAL)) return AWARE_E_BADARG;
     if (n_fft != kNfft || hop != kHop || win_length != kNfft || (flags & AWARE_PLAN_GENERAL))
-        return gen_plan_create(out, n_fft, hop, win_length, window, band_lo_bin, band_hi_bin);
+        return gen_plan_create(out, n_fft, hop, win_length, window, band_lo_bin, band_hi_bin, flags);
     if (window != 0 && window != 1) return AWARE_E_BADARG;
     const int nband = band_hi_bin - band_lo_bin + 1;
     // any band of the one-sided spectrum: narrow layout (kFS columns) inside bins 1..511 up to 256 bins wide, else wide
@@ -462,6 +472,7 @@ static int gen_batch_create(aware_batch** out, const aware_plan* plan, int B, co
         acc += n;
         b->T[i] = T;
         b->frame_off[i + 1] = b->frame_off[i] + T;
+        b->pool_off[i + 1] = b->pool_off[i] + ((T / 2 + 31) & ~31);   // floor(T / 2) pooled rows, 32-aligned per clip
         b->out_off[i] = hop * (b->frame_off[i] - i);
         b->out_len[i] = hop * (T - 1);
         b->pc_in[i] = (n + 4095) / 4096;
@@ -472,9 +483,16 @@ static int gen_batch_create(aware_batch** out, const aware_plan* plan, int B, co
         b->nola_ok = b->nola_ok && gen_nola_ok(plan->envh.data(), plan->w2h.data(), N, hop, T);
     }
     b->NF = b->frame_off[B];
+    b->NP = b->pool_off[B];
+    b->uniform_tp = b->T[0] / 2;
+    for (int i = 1; i < B; ++i)
+        if (b->T[i] / 2 != b->uniform_tp) b->uniform_tp = 0;
     b->NS = hop * (b->NF - B);
     b->pstride = max_pc;
-    const size_t ints = (size_t)(B + 1) + (size_t)B * 6;
+    b->order.resize(B);
+    for (int i = 0; i < B; ++i) b->order[i] = i;
+    std::stable_sort(b->order.begin(), b->order.end(), [&](int x, int y) { return b->T[x] > b->T[y]; });
+    const size_t ints = (size_t)(B + 1) * 2 + (size_t)B * 7;
     if (hipMalloc((void**)&b->d_mem, ints * sizeof(int)) != hipSuccess ||
         hipMalloc((void**)&b->d_frames, (size_t)b->NF * N * sizeof(float)) != hipSuccess) {
         g_last_err = "aware_batch_create_for_plan: device memory";
@@ -494,6 +512,8 @@ static int gen_batch_create(aware_batch** out, const aware_plan* plan, int B, co
     if (e == hipSuccess) e = up(b->d_out_len, b->out_len);
     if (e == hipSuccess) e = up(b->d_pc_in, b->pc_in);
     if (e == hipSuccess) e = up(b->d_pc_out, pc_out);
+    if (e == hipSuccess) e = up(b->d_pool_off, b->pool_off);
+    if (e == hipSuccess) e = up(b->d_order, b->order);
     if (e != hipSuccess) {
         g_last_err = std::string("aware_batch_create_for_plan: ") + hipGetErrorString(e);
         aware_batch_destroy(b);
@@ -749,7 +769,7 @@ static int detector_upload(aware_detector* d, const float* mel_basis, const floa
     for (int i = 0; i < n_layers; ++i) total += (size_t)channels[i] * channels[i + 1] * 2 + channels[i + 1];
     std::vector<float> h(total, 0.f);
     size_t o = 0;
-    const int nbins = kNfft / 2 + 1;
+    const int nbins = d->n_fft / 2 + 1;
     const int lo = d->band_lo, nb = d->nband;
     size_t o_melT = o; o += (size_t)Mp * S;
     size_t o_melB = o; o += (size_t)S * Mp;
@@ -765,7 +785,7 @@ static int detector_upload(aware_detector* d, const float* mel_basis, const floa
         // two-tap form of the band's columns, if the basis has it (any triangular filter bank does)
         std::vector<float2> tw(kFS, make_float2(0.f, 0.f));
         std::vector<unsigned char> tm(kFS, 0);
-        bool sparse = n_mels == 128 && S == kFS;
+        bool sparse = n_mels == 128 && S == kFS && !d->general;
         for (int f = 0; f < nb && sparse; ++f) {
             int first = -1, count = 0, lastnz = -1;
             for (int j = 0; j < n_mels; ++j)
@@ -909,7 +929,8 @@ static int detector_create(aware_detector** out, const aware_plan* plan, const f
                            const int* channels, const float* const* weights, const float* const* biases,
                            const aware_detector_arch* arch) {
     if (!out || !plan || !mel_basis || !channels || !weights) return AWARE_E_BADARG;
-    if (plan->general) return AWARE_E_UNSUPPORTED;       // the detector runs on the card geometry only
+    // a general plan made for the transforms alone (no AWARE_PLAN_GENERAL), or a band outside bins 0..n_fft/2
+    if (plan->general && (!plan->loop || !plan->band_ok)) return AWARE_E_UNSUPPORTED;
     if (n_mels < 1 || n_mels > kMaxMels || n_layers < 1 || n_layers > kMaxLayers || channels[0] != n_mels) return AWARE_E_UNSUPPORTED;
     const int cl = channels[n_layers];
     if (cl % 2 || cl < 2 || cl > kMaxOutChannels) return AWARE_E_UNSUPPORTED;
@@ -918,6 +939,7 @@ static int detector_create(aware_detector** out, const aware_plan* plan, const f
     aware_detector* d = new aware_detector();
     d->n_mels = n_mels; d->n_layers = n_layers; d->nbits = cl / 2;
     d->band_lo = plan->dev.band_lo; d->nband = plan->dev.nband; d->stride = plan->dev.stride;
+    d->n_fft = plan->n_fft; d->general = plan->general != 0;
     d->uch.assign(channels, channels + n_layers + 1);
     d->ch.resize(n_layers + 1);
     for (int i = 0; i <= n_layers; ++i) {
@@ -1348,12 +1370,27 @@ static void readout_forward(const aware_detector* d, const aware_batch* b, const
                     d->nbits, b->B, st, nullptr, d->final_act, C);
 }
 
-// aware_detect: the detector's buffers, the band magnitudes and the analysis's partial maxima
+// the general route's band kernels (loop_any.hip) for a plan and its batch
+static BandLaunch band_launch(const aware_plan* plan, const aware_batch* b) {
+    BandLaunch L;
+    L.NF = b->NF; L.B = b->B; L.frame_off = b->d_frame_off; L.sstride = plan->gdev.stride;
+    L.band_lo = plan->dev.band_lo; L.nband = plan->dev.nband; L.bstride = plan->dev.stride;
+    return L;
+}
+// a general plan, its batch and a detector created for it: one geometry, one band layout
+static bool gen_loop_matches(const aware_plan* plan, const aware_batch* b, const aware_detector* d) {
+    return plan->band_ok && gen_batch_matches(plan, b) && d->general && d->n_fft == plan->n_fft &&
+           d->band_lo == plan->dev.band_lo && d->nband == plan->dev.nband && d->stride == plan->dev.stride;
+}
+
+// aware_detect: the detector's buffers, the band magnitudes and the analysis's partial maxima; a general batch also the
+// spectrum the band magnitudes are taken from
 static void carve_detect(Carver& c, const aware_batch* b, const aware_detector* d, DetBufs& o, float*& mag,
-                         unsigned long long*& pmax) {
+                         unsigned long long*& pmax, cf*& spec) {
     carve_det(c, b, d, o);
     mag = c.take<float>((size_t)b->NF * d->stride);
     pmax = c.take<unsigned long long>((size_t)b->B * b->pstride);
+    spec = b->general ? c.take<cf>((size_t)b->NF * gen_stride(b->g_nfft)) : nullptr;
 }
 extern "C" size_t aware_detect_workspace_bytes(const aware_batch* b, const aware_detector* d) {
     if (!b || !d) return 0;
@@ -1361,7 +1398,8 @@ extern "C" size_t aware_detect_workspace_bytes(const aware_batch* b, const aware
     DetBufs o;
     float* mag;
     unsigned long long* pmax;
-    carve_detect(c, b, d, o, mag, pmax);
+    cf* spec;
+    carve_detect(c, b, d, o, mag, pmax, spec);
     return c.off;
 }
 
@@ -1385,8 +1423,8 @@ extern "C" int aware_detector_forward(const aware_detector* d, const aware_batch
 extern "C" int aware_detect(const aware_plan* plan, const aware_detector* d, const aware_batch* b, const float* audio,
                             float* values, void* workspace, size_t workspace_bytes, void* stream) {
     if (!plan || !d || !b || !audio || !values || !workspace) return AWARE_E_BADARG;
-    if (plan->general) return AWARE_E_UNSUPPORTED;
-    if (b->general) return AWARE_E_BADARG;
+    if (plan->general && !plan->loop) return AWARE_E_UNSUPPORTED;          // a plan for the transforms alone
+    if (plan->general ? !gen_loop_matches(plan, b, d) : (b->general || d->general)) return AWARE_E_BADARG;
     // the magnitude rows are carved at the detector's stride and written at the plan's: one band layout
     if (d->band_lo != plan->dev.band_lo || d->nband != plan->dev.nband || d->stride != plan->dev.stride) return AWARE_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
@@ -1394,10 +1432,17 @@ extern "C" int aware_detect(const aware_plan* plan, const aware_detector* d, con
     DetBufs o;
     float* mag;
     unsigned long long* pmax;
-    carve_detect(c, b, d, o, mag, pmax);
+    cf* spec;
+    carve_detect(c, b, d, o, mag, pmax, spec);
     if (!c.ok) return AWARE_E_WORKSPACE;
     for (int l = 0; l < d->n_layers; ++l) o.stash[l] = nullptr;
-    int rc = aware_stft_band(plan, b, audio, 1, mag, nullptr, pmax, stream);
+    int rc;
+    if (plan->general) {
+        // the general route: normalised spectrum (stft_any.hip), then its band magnitudes in the detector's layout
+        rc = gen_stft(plan, b, audio, 1, spec, pmax, st);
+        if (rc == AWARE_OK) { launch_band_mag(band_launch(plan, b), spec, mag, nullptr, st); LAUNCHCHK(); }
+    } else
+        rc = aware_stft_band(plan, b, audio, 1, mag, nullptr, pmax, stream);
     if (rc) return rc;
     const DetPlan p = det_plan(d, b, 0, 1, false, false, false);
     rc = det_forward(d, b, p, mag, o, st);
@@ -1707,12 +1752,45 @@ struct aware_embed {
     unsigned long long mix_thr[kMaxLoopChains] = {0};
     int* mix_choice = nullptr;                    // [B]
     int mix_rv = -1;                              // the chain with the reverberation (aware_embed_buffer 13), -1 without one
+    // the general route (a general plan; gen_embed_iteration): full spectra [NF][spectrum stride] -- S0 the normalised
+    // original, whose band columns every step overwrites with coef * U; S2 the analysis of the normalised synthesis, then
+    // the gradient of the synthesis' input; GS the gradient of S2, zero outside the band -- and the two normalised
+    // signals with the gradient of the first [NS]
+    cf *S0 = nullptr, *S2 = nullptr, *GS = nullptr;
+    float *y1 = nullptr, *y2 = nullptr, *gy1 = nullptr;
 };
 
 // the embed loop's workspace: the detector's buffers, then the loop state; iters: num_iterations, l1: the L1 term's buffers
 static void carve_embed(Carver& c, const aware_batch* b, const aware_detector* det, int iters, bool l1, aware_embed* e) {
     carve_det(c, b, det, e->db);
     const size_t nsp = (size_t)b->NF * det->stride;
+    if (b->general) {
+        // the general route: band rows, three full spectra, five signals; no out-of-band residual, no reflect-pad parts and
+        // no L1 term (they belong to the card kernels).  The step tables are carved at the longest loop aware_embed_create
+        // accepts whatever `iters` is, so aware_embed_workspace_bytes is exact: one byte less is AWARE_E_WORKSPACE
+        iters = 4096;
+        const size_t nfull = (size_t)b->NF * gen_stride(b->g_nfft);
+        e->coef = c.take<float>(nsp); e->lo = c.take<float>(nsp); e->hi = c.take<float>(nsp);
+        e->mom = c.take<float>(nsp); e->vel = c.take<float>(nsp); e->best = c.take<float>(nsp);
+        e->mag = c.take<float>(nsp); e->gmag = c.take<float>(nsp); e->c0 = c.take<float>(nsp);
+        e->U = c.take<cf>(nsp); e->P = e->U;
+        e->S0 = c.take<cf>(nfull); e->S2 = c.take<cf>(nfull); e->GS = c.take<cf>(nfull);
+        e->yraw = c.take<float>(b->NS); e->y1 = c.take<float>(b->NS); e->y2 = c.take<float>(b->NS);
+        e->gy = c.take<float>(b->NS); e->gy1 = c.take<float>(b->NS);
+        e->oob = nullptr; e->gpad = nullptr;
+        e->d1 = c.take<float>((size_t)b->NP * det->maxc); e->d2 = c.take<float>((size_t)b->NP * det->maxc);
+        e->loss = c.take<float>(b->B); e->best_loss = c.take<float>(b->B);
+        e->target = c.take<float>((size_t)b->B * det->nbits);
+        e->improved = c.take<int>(b->B); e->step = c.take<int>(4);
+        e->sched = c.take<float4>(iters + 1);
+        e->pmaxA = c.take<unsigned long long>((size_t)b->B * b->pstride);
+        e->pmaxY = c.take<unsigned long long>((size_t)b->B * b->pstride);
+        e->pdot = nullptr;
+        e->opt.d_tab = c.take<double>((size_t)iters * 5);
+        e->opt.d_lr = c.take<double>(b->B);
+        e->opt.d_state = c.take<double>((size_t)b->B * 3);
+        return;
+    }
     e->coef = c.take<float>(nsp); e->lo = c.take<float>(nsp); e->hi = c.take<float>(nsp);
     e->mom = c.take<float>(nsp); e->vel = c.take<float>(nsp); e->best = c.take<float>(nsp);
     e->mag = c.take<float>(nsp); e->gmag = c.take<float>(nsp);
@@ -1816,8 +1894,14 @@ extern "C" int aware_embed_create(aware_embed** out, const aware_plan* plan, con
                                   const aware_batch* b, const aware_embed_config* cfg, void* workspace,
                                   size_t workspace_bytes, void* stream) {
     if (!out || !plan || !det || !b || !cfg || !workspace) return AWARE_E_BADARG;
-    if (plan->general) return AWARE_E_UNSUPPORTED;       // the embed loop runs on the card geometry only
-    if (b->general) return AWARE_E_BADARG;
+    if (plan->general && !plan->loop) return AWARE_E_UNSUPPORTED;          // a plan for the transforms alone
+    if (plan->general ? !gen_loop_matches(plan, b, det) : (b->general || det->general)) return AWARE_E_BADARG;
+    if (plan->general) {
+        // torch.istft's NOLA condition for every clip, and at least one hop of output to analyse again
+        if (!b->nola_ok) return AWARE_E_BADARG;
+        for (int i = 0; i < b->B; ++i)
+            if (b->out_len[i] < 1) return AWARE_E_BADARG;
+    }
     if (cfg->num_iterations < 1 || cfg->num_iterations > 4096 || cfg->loss < 0 || cfg->loss > AWARE_LOSS_PUSH_L1) return AWARE_E_BADARG;
     if (cfg->conv_pipe < 0 || cfg->conv_pipe > 2 || cfg->readout < 0 || cfg->readout > 1 || cfg->mel < 0 || cfg->mel > 1)
         return AWARE_E_BADARG;
@@ -1826,7 +1910,7 @@ extern "C" int aware_embed_create(aware_embed** out, const aware_plan* plan, con
     if (det->band_lo != plan->dev.band_lo || det->nband != plan->dev.nband || det->stride != plan->dev.stride) return AWARE_E_BADARG;
     // the L1 term lives in the streaming DSP kernels only
     const bool l1 = cfg->loss == AWARE_LOSS_PUSH_L1;
-    if (l1 && (cfg->dsp_path != 0 || !stream_supported(plan->dev))) return AWARE_E_UNSUPPORTED;
+    if (l1 && (plan->general || cfg->dsp_path != 0 || !stream_supported(plan->dev))) return AWARE_E_UNSUPPORTED;
     if (cfg->conv_tile == 2) {
         // the wide form was asked for: some conv launch of this session has to be able to take it
         const DetPlan p = det_plan(det, b, cfg->conv_pipe, cfg->readout, false, false, false, 2);
@@ -1844,7 +1928,9 @@ extern "C" int aware_embed_create(aware_embed** out, const aware_plan* plan, con
     // columns nband..stride-1 of every spectral row are padding: zeroed once here, never written by the loop kernels
     HIPCHK(hipMemsetAsync(e->mag, 0, nsp * sizeof(float), st));
     HIPCHK(hipMemsetAsync(e->U, 0, nsp * sizeof(cf), st));
-    HIPCHK(hipMemsetAsync(e->gpad, 0, (size_t)b->B * 1024 * sizeof(float), st));
+    if (e->gpad) HIPCHK(hipMemsetAsync(e->gpad, 0, (size_t)b->B * 1024 * sizeof(float), st));
+    // general route: the gradient spectrum is zero outside the band, and only its band columns are ever written
+    if (e->GS) HIPCHK(hipMemsetAsync(e->GS, 0, (size_t)b->NF * plan->gdev.stride * sizeof(cf), st));
     std::vector<float4> sc(cfg->num_iterations + 1);
     float mu_product = 1.0f;
     const double b1 = cfg->beta1, b2 = cfg->beta2;
@@ -1957,8 +2043,9 @@ static int set_loop_attacks(aware_embed* e, const aware_loop_attack_ex* attacks,
     if (!e || n_attacks < 0 || n_attacks > kMaxLoopAttacks) return AWARE_E_BADARG;
     if (e->gexec || e->la.locked) return AWARE_E_BADARG;          // before the first aware_embed_iterate, as aware_embed_set_optimizer
     if (n_attacks == 0) { clear_loop_chain(e); return AWARE_OK; }
-    if (!attacks || !seeds || !workspace || ((uintptr_t)workspace & 255)) return AWARE_E_BADARG;
     const aware_batch* b = e->b;
+    if (b->general) return AWARE_E_UNSUPPORTED;                   // the stage kernels run on the card geometry only
+    if (!attacks || !seeds || !workspace || ((uintptr_t)workspace & 255)) return AWARE_E_BADARG;
     auto la = e->la;
     la.gate = LoopGate();
     if (int rc = parse_loop_chain(loop_dims(b), attacks, n_attacks, ex, la)) return rc;
@@ -1998,9 +2085,9 @@ extern "C" int aware_embed_set_loop_mixture(aware_embed* e, const aware_loop_cha
     if (!e || n_chains < 0 || n_chains > kMaxLoopChains) return AWARE_E_BADARG;
     if (e->gexec || e->la.locked) return AWARE_E_BADARG;          // before the first aware_embed_iterate, as the chain's setter
     if (n_chains == 0) { clear_loop_chain(e); return AWARE_OK; }
-    if (!chains || !seeds || !workspace || ((uintptr_t)workspace & 255)) return AWARE_E_BADARG;
     const aware_batch* b = e->b;
-    if (b->general) return AWARE_E_BADARG;
+    if (b->general) return AWARE_E_UNSUPPORTED;                   // as the chain's setter
+    if (!chains || !seeds || !workspace || ((uintptr_t)workspace & 255)) return AWARE_E_BADARG;
     LoopChainState shared, mix[kMaxLoopChains];
     unsigned long long thr[kMaxLoopChains];
     int rv = -1, *choice = nullptr;
@@ -2297,10 +2384,105 @@ extern "C" void* aware_embed_buffer(aware_embed* e, int which) {
     }
 }
 
+// ---- the general route (a general plan): the loop on the transforms of stft_any.hip and the band kernels of loop_any.hip ----
+// the transforms on the synthesis' signal layout: clip b at out_off[b], hop (T_b - 1) samples, on both sides
+static GenLaunch gen_loop_launch(const aware_embed* e) {
+    GenLaunch L = gen_launch(e->plan, e->b);
+    L.sig_off = e->b->d_out_off; L.sig_len = e->b->d_out_len;
+    return L;
+}
+// [WaveformNormalizer, STFT, STFTDecomposer] on the whole spectrum: S0, then the band's magnitudes, unit phasors, box and
+// optimiser state in one launch
+static int gen_embed_begin(aware_embed* e, const float* audio, hipStream_t st) {
+    const aware_batch* b = e->b;
+    int rc = gen_stft(e->plan, b, audio, 1, e->S0, e->pmaxA, st);
+    if (rc) return rc;
+    BandBegin G;
+    G.unit = e->U; G.coef = e->coef; G.lo = e->lo; G.hi = e->hi; G.mom = e->mom; G.vel = e->vel; G.best = e->best; G.c0 = e->c0;
+    G.ratio = (float)pow(10.0, -(double)e->cfg.tolerance_db / 20.0);
+    launch_band_mag(band_launch(e->plan, b), e->S0, e->mag, &G, st);
+    LAUNCHCHK();
+    return AWARE_OK;
+}
+// Assembler + ISTFT of `coef` into yraw, and the partial maxima of yraw
+static int gen_synthesise(aware_embed* e, const float* coef, hipStream_t st) {
+    const aware_batch* b = e->b;
+    launch_band_assemble(band_launch(e->plan, b), coef, e->U, e->S0, st);
+    LAUNCHCHK(); PROF(K_MISC);
+    launch_gen_synthesis(gen_loop_launch(e), e->S0, e->yraw, 0, st);
+    LAUNCHCHK(); PROF(K_SYNTH);
+    launch_absmax_partials(e->yraw, b->d_out_off, b->d_out_len, e->pmaxY, b->pstride, b->B, b->max_len, st);
+    LAUNCHCHK(); PROF(K_MISC);
+    return AWARE_OK;
+}
+// one loop body of AWAREEmbedder._optimize (multibit_embedder.py:95-122), every stage its own launch, one chain
+static int gen_embed_iteration(aware_embed* e, hipStream_t st, int do_step, float* grad_out) {
+    const aware_batch* b = e->b;
+    const aware_detector* d = e->det;
+    const BandLaunch BL = band_launch(e->plan, b);
+    const GenLaunch L = gen_loop_launch(e);
+    // :99-103 scatter + Assembler + ISTFT, then the two normalisers (the post-process list ends with one, the pre-process
+    // list starts with one), STFT and |.| on the band (:104 zeroes the rest)
+    int rc = gen_synthesise(e, e->coef, st);
+    if (rc) return rc;
+    launch_normalize(e->yraw, e->y1, b->d_out_off, b->d_out_len, e->pmaxY, b->d_pc_out, b->pstride, b->B, b->max_len, st);
+    launch_absmax_partials(e->y1, b->d_out_off, b->d_out_len, e->pmaxY, b->pstride, b->B, b->max_len, st);
+    launch_normalize(e->y1, e->y2, b->d_out_off, b->d_out_len, e->pmaxY, b->d_pc_out, b->pstride, b->B, b->max_len, st);
+    LAUNCHCHK(); PROF(K_MISC);
+    launch_gen_analysis(L, e->y2, e->S2, 0, st);
+    LAUNCHCHK(); PROF(K_ANALYSIS);
+    launch_band_mag(BL, e->S2, e->mag, nullptr, st);
+    LAUNCHCHK(); PROF(K_MISC);
+    // :107 detector forward, :109 loss, :120-122 best tracking, :111 backward through the detector
+    DetGradCtx G;
+    G.target = e->target; G.loss_kind = e->cfg.loss;
+    G.loss = e->loss; G.d1 = e->d1; G.d2 = e->d2; G.gmag = e->gmag;
+    G.step = do_step ? e->step : nullptr;
+    G.best_loss = do_step ? e->best_loss : nullptr;
+    G.improved = do_step ? e->improved : nullptr;
+    const DetPlan p = det_plan(d, b, e->cfg.conv_pipe, e->cfg.readout, false, false, false, e->cfg.conv_tile);
+    rc = det_forward_backward(d, b, p, e->mag, e->db, G, st);
+    if (rc) return rc;
+    // backward through |.|, the STFT and its reflect padding, the two normalisers, the ISTFT and the assembler
+    launch_band_mag_bwd(BL, e->S2, e->gmag, e->GS, st);
+    LAUNCHCHK(); PROF(K_MISC);
+    launch_gen_synthesis(L, e->GS, e->gy, 1, st);
+    LAUNCHCHK(); PROF(K_SYNTH_ADJ);
+    launch_normalize_bwd(e->y1, e->gy, e->gy1, b->d_out_off, b->d_out_len, b->B, st);
+    launch_normalize_bwd(e->yraw, e->gy1, e->gy, b->d_out_off, b->d_out_len, b->B, st);
+    LAUNCHCHK(); PROF(K_MISC);
+    launch_gen_analysis(L, e->gy, e->S2, 1, st);
+    LAUNCHCHK(); PROF(K_ANALYSIS_ADJ);
+    // :112-117 the step and the clamp: the card's NAdam inside the gradient kernel, any other optimiser / schedule in its
+    // own launch on the gradient (left in gmag, which the backward above has consumed)
+    const bool own_step = do_step && e->opt.active;
+    BandStep S;
+    S.coef = e->coef; S.mom = e->mom; S.vel = e->vel; S.best = e->best; S.lo = e->lo; S.hi = e->hi;
+    S.improved = e->improved; S.sched = e->sched; S.sched_len = e->cfg.num_iterations + 1; S.step = e->step;
+    memcpy(S.hyp, e->hyp, sizeof(S.hyp));
+    launch_band_coef_grad(BL, e->S2, e->U, own_step ? e->gmag : grad_out, (do_step && !own_step) ? &S : nullptr, st);
+    LAUNCHCHK(); PROF(K_MISC);
+    if (own_step) {
+        const auto& o = e->opt;
+        launch_opt_rows(o.kind, e->coef, e->gmag, e->mom, e->vel, e->c0, (float)pow(10.0, -(double)e->cfg.tolerance_db / 20.0),
+                        e->best, e->improved, b->d_frame_off, b->B, b->NF, o.d_tab, e->cfg.num_iterations, e->step,
+                        o.plateau ? o.d_lr : nullptr, o.wd, o.hyp, e->plan->dev.nband, e->plan->dev.stride, st);
+        if (o.plateau)
+            launch_plateau(e->loss, o.d_state, o.d_lr, b->B, o.factor, o.patience, o.threshold, o.min_lr, o.eps, st);
+        LAUNCHCHK(); PROF(K_MISC);
+    }
+    return AWARE_OK;
+}
+
+static int embed_begin_state(aware_embed* e, const float* target, hipStream_t st);
 extern "C" int aware_embed_begin(aware_embed* e, const float* audio, const float* target, void* stream) {
     if (!e || !audio || !target) return AWARE_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
     const aware_batch* b = e->b;
+    if (e->plan->general) {
+        if (int rc = gen_embed_begin(e, audio, st)) return rc;
+        return embed_begin_state(e, target, st);
+    }
     // [WaveformNormalizer, STFT, STFTDecomposer] (multibit_embedder.py:143-147), band only
     launch_absmax_partials(audio, b->d_in_off, b->d_in_len, e->pmaxA, b->pstride, b->B, b->max_len, st);
     LAUNCHCHK();
@@ -2323,6 +2505,11 @@ extern "C" int aware_embed_begin(aware_embed* e, const float* audio, const float
     const float ratio = (float)pow(10.0, -(double)e->cfg.tolerance_db / 20.0);
     launch_embed_prepare(e->mag, e->coef, e->lo, e->hi, e->mom, e->vel, e->best, e->c0, ratio, (size_t)b->NF * e->plan->dev.stride, st);
     LAUNCHCHK();
+    return embed_begin_state(e, target, st);
+}
+// the payload, the step counter, the best losses and a registry optimiser's per-clip state at the start of a run
+static int embed_begin_state(aware_embed* e, const float* target, hipStream_t st) {
+    const aware_batch* b = e->b;
     HIPCHK(hipMemcpyAsync(e->target, target, (size_t)b->B * e->det->nbits * sizeof(float), hipMemcpyDeviceToDevice, st));
     HIPCHK(hipMemsetAsync(e->step, 0, 4 * sizeof(int), st));
     // best_loss = +inf (0x7F800000)
@@ -2527,6 +2714,7 @@ static void chain_backward(const aware_embed* e, const LoopChainState& la, LoopA
 
 // one loop body of AWAREEmbedder._optimize (multibit_embedder.py:95-122)
 static int embed_iteration(aware_embed* e, hipStream_t st, int do_step, float* grad_out) {
+    if (e->plan->general) return gen_embed_iteration(e, st, do_step, grad_out);
     const aware_batch* b = e->b;
     const aware_detector* d = e->det;
     // :99-103  scatter + Assembler + ISTFT  (out-of-band part is the constant `oob`)
@@ -2735,6 +2923,14 @@ extern "C" int aware_embed_finish(aware_embed* e, const float* rescale, float* o
     if (!e || !out) return AWARE_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
     const aware_batch* b = e->b;
+    if (e->plan->general) {
+        // the best coefficients through the assembler and the ISTFT, one normaliser, the caller's rescale
+        if (int rc = gen_synthesise(e, e->best, st)) return rc;
+        launch_rescale_normalize(e->yraw, out, b->d_out_off, b->d_out_len, e->pmaxY, b->d_pc_out, b->pstride, rescale, b->B,
+                                 b->max_len, st);
+        LAUNCHCHK();
+        return AWARE_OK;
+    }
     SynthLaunch S;
     S.plan = e->plan->dev; S.frame_off = b->d_frame_off; S.B = b->B; S.max_frames = b->max_frames; S.run_blocks = b->synth_run; S.wg_tab = b->d_syn_wg; S.n_wg = b->n_syn_wg;
     S.amp = e->best; S.ph = e->P; S.out = e->yraw; S.add = e->oob; S.pmax = e->pmaxY; S.pstride = b->pstride;

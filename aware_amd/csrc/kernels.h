@@ -336,6 +336,49 @@ void launch_gen_synthesis(const GenLaunch& L, const void* spec, float* out, int 
 // out /= max|out| + 1e-8 per clip over the istft-length signals (L.pmax: partials of `out`)
 void launch_gen_normalize(const GenLaunch& L, float* out, hipStream_t st);
 
+// ---- loop_any.hip: the band kernels of the embed / detect loop on a general plan -------------------------------------
+// Rows of the general spectrum (`sstride` complex values, bins 0..n_fft/2) on one side, band rows in the detector's layout
+// (`bstride` floats, column f = bin band_lo + f, columns nband..bstride-1 padding) on the other; NF rows, ragged over
+// frame_off.  Threads exist for the band columns only.
+struct BandLaunch {
+    int NF = 0, B = 0;
+    const int* frame_off = nullptr;       // [B+1]
+    int sstride = 0;                      // GenPlanDev::stride
+    int band_lo = 0, nband = 0, bstride = 0;
+};
+// what band_mag also writes at aware_embed_begin: the unit phasors of the original spectrum, the coefficients, their box
+// (box_bounds, the card route's formula) and the optimiser state
+struct BandBegin {
+    void* unit = nullptr;                 // cf [NF][bstride], (1, 0) where |S| == 0, (0, 0) in the padding
+    float *coef = nullptr, *lo = nullptr, *hi = nullptr, *mom = nullptr, *vel = nullptr, *best = nullptr, *c0 = nullptr;
+    float ratio = 0.f;                    // 10^(-tolerance_db / 20)
+};
+// mag[row][f] = |spec[row][band_lo + f]|, padding columns zero; begin != null: the arrays of BandBegin too
+void launch_band_mag(const BandLaunch& L, const void* spec, float* mag, const BandBegin* begin, hipStream_t st);
+// spec[row][band_lo + f] = coef[row][f] * unit[row][f]; every other bin of spec is left as it is
+void launch_band_assemble(const BandLaunch& L, const float* coef, const void* unit, void* spec, hipStream_t st);
+// gspec[row][band_lo + f] = gmag[row][f] * spec / |spec| (0 where |spec| == 0); every other bin of gspec is left as it is
+// (the caller zeroed it once)
+void launch_band_mag_bwd(const BandLaunch& L, const void* spec, const float* gmag, void* gspec, hipStream_t st);
+// g[row][f] = Re(conj(unit[row][f]) * gspec[row][band_lo + f]) -> grad_out (may be null); do_step: the model card's NAdam
+// step, the clamp to the box and the best snapshot of the clips in `improved`, as the card route's analysis adjoint does
+// them (nadam_clamp_update with sched[*step - 1])
+struct BandStep {
+    float *coef = nullptr, *mom = nullptr, *vel = nullptr, *best = nullptr;
+    const float *lo = nullptr, *hi = nullptr;
+    const int* improved = nullptr;        // [B]
+    const void* sched = nullptr;          // float4 per step {c_grad, c_mom, bias_correction2, 0}
+    int sched_len = 0;
+    const int* step = nullptr;            // device step counter (already advanced by the read-out)
+    float hyp[4] = {0.f, 0.f, 0.f, 0.f};  // {1 - beta1, beta2, 1 - beta2, eps}
+};
+// out[off[b] + i] = rescale[b] * (in[off[b] + i] / (max|in_b| + 1e-8)) (rescale null: 1): the last normaliser of an embed run and
+// the caller's rescale, on ragged signals (pmax: partial maxima of `in`)
+void launch_rescale_normalize(const float* in, float* out, const int* off, const int* len, const unsigned long long* pmax,
+                              const int* pcount, int pstride, const float* rescale, int B, int max_len, hipStream_t st);
+void launch_band_coef_grad(const BandLaunch& L, const void* gspec, const void* unit, float* grad_out, const BandStep* step,
+                           hipStream_t st);
+
 // ---- stoi_kernels.hip: batched short-time objective intelligibility (metrics/audio.py::stoi) at 10 kHz -------------
 constexpr int kStoiFrame = 256, kStoiHop = 128, kStoiBands = 15, kStoiRow = 16, kStoiN = 30;
 constexpr int kStoiSegChunk = 64;         // segments per partial sum of the last stage

@@ -71,6 +71,9 @@ __global__ __launch_bounds__(256) void gen_analysis_kernel(GenLaunch L, const fl
                 int idx = base + o;
                 idx = idx < 0 ? -idx : idx;
                 idx = idx >= n ? 2 * (n - 1) - idx : idx;
+                // n > n_fft/2 (every clip aware_stft takes): in range already.  The embed loop's second analysis reads the
+                // synthesis, hop (T - 1) samples, which may be n_fft/2 or fewer; torch.stft refuses to pad such a signal
+                idx = min(max(idx, 0), n - 1);
                 r[e] = wo != 0.f ? (x[idx] * inv) * wo : 0.f;
             }
             s[2 * q] = mk(r[0], r[1]);

@@ -22,10 +22,22 @@ from . import sync
 class AWAREDetector(BaseDetector):
     def __init__(self, model, threshold: float = 0.0, frame_length: int = 1024, hop_length: int = 256,
                  window: str = "hann", win_length: int = 1024, pattern_mode: str = "bits2bipolar",
-                 embedding_bands=(500, 4000), sync_search: int = 0, speed_search=None, scan=None, payload_code=None):
-        rt.require_card_geometry("AWAREDetector", frame_length, hop_length, win_length)
+                 embedding_bands=(500, 4000), sync_search: int = 0, speed_search=None, scan=None, payload_code=None,
+                 general_geometry: bool = False):
+        """general_geometry (EXTENSION): detect at any frame_length in runtime.GENERAL_NFFT, any
+        hop_length and win_length in 1..frame_length, on the general route; off: the card geometry only.  With it sync_search,
+        speed_search and scan raise NotImplementedError (their offsets assume the card's 512-sample pooling period)."""
+        self.general_geometry = bool(general_geometry)
+        rt.require_card_geometry("AWAREDetector", frame_length, hop_length, win_length, self.general_geometry, window)
         self.sync_search = sync.check_sync_search(sync_search)
         self.speed_search = sync.check_speed_search(speed_search)
+        if self.general_geometry and self.sync_search:
+            rt.refuse_general_geometry("sync_search")
+        if self.general_geometry and self.speed_search is not None:
+            rt.refuse_general_geometry("speed_search")
+        if self.general_geometry and model is not None and getattr(model, "n_fft", frame_length) != frame_length:
+            raise ValueError(f"AWAREDetector: the detection net's n_fft = {model.n_fft} but frame_length = {frame_length}; "
+                             f"with general_geometry the detector's mel bank follows the STFT")
         self.scan_defaults = sync.check_scan_card(scan)           # what scan() uses where its arguments are None
         self.scan_rows_per_call = sync.SYNC_MAX_ROWS              # rows per aware_detect call of scan()
         self.payload_code = fec.check_payload_code(payload_code)  # the channel code of service.detect_message and scan()
@@ -44,9 +56,20 @@ class AWAREDetector(BaseDetector):
                                           STFTDecomposer()]
 
     def _plan(self, sample_rate):
-        rt.require_card_geometry("AWAREDetector", self.frame_length, self.hop_length, self.win_length)
+        rt.require_card_geometry("AWAREDetector", self.frame_length, self.hop_length, self.win_length, self.general_geometry,
+                                 self.window)
         return get_plan(self.frame_length, self.hop_length, self.window,
-                        band_bins(sample_rate, self.frame_length, self.embedding_bands), win_length=self.win_length)
+                        band_bins(sample_rate, self.frame_length, self.embedding_bands), win_length=self.win_length,
+                        general=self.general_geometry)
+
+    def make_batch(self, lengths, sample_rate: int) -> "rt.Batch":
+        """The batch geometry of this detector's plan for clips of `lengths` samples (with general_geometry: ValueError
+        naming a clip of n_fft/2 samples or fewer)."""
+        if not self.general_geometry:
+            return rt.Batch(list(lengths))
+        rt.check_general_clips("AWAREDetector", self.frame_length, self.hop_length, self.win_length, self.window, lengths,
+                               embed=False)
+        return rt.Batch(list(lengths), plan=self._plan(sample_rate))
 
     def _centre(self) -> float:
         """What an undecided read-out value is: 0.5 behind a sigmoid, 0 otherwise."""
@@ -75,6 +98,13 @@ class AWAREDetector(BaseDetector):
         confidence [B] float32) instead."""
         n = self.sync_search if sync_search is None else sync.check_sync_search(sync_search)
         speed = self.speed_search if speed_search is None else sync.check_speed_search(speed_search)
+        if self.general_geometry and n:
+            rt.refuse_general_geometry("sync_search")
+        if self.general_geometry and speed is not None:
+            rt.refuse_general_geometry("speed_search")
+        if self.general_geometry:                                 # ValueError naming the clip, before any plan or launch
+            rt.check_general_clips("AWAREDetector", self.frame_length, self.hop_length, self.win_length, self.window,
+                                   [len(c) for c in clips], embed=False)
         if speed is None:
             out = self._detect_sync(clips, sample_rate, n, return_sync or return_speed)
             if return_speed:
@@ -89,7 +119,7 @@ class AWAREDetector(BaseDetector):
         plan = self._plan(sample_rate)
         det = self.detection_net.device_weights(plan)
         if n == 0:
-            batch = rt.Batch([len(c) for c in clips])
+            batch = self.make_batch([len(c) for c in clips], sample_rate)
             vals = rt.detect(plan, det, batch, batch.pack(clips))
             if not return_sync:
                 return vals
@@ -170,6 +200,8 @@ class AWAREDetector(BaseDetector):
         profiles) instead, a profile per file being a dict of `starts` (the window starts), `length` (samples per window),
         `win_conf`, `win_view` and `win_values` (numpy, per window: the best view's confidence, index and row) and `n_segments` (the true span count, which max_segments may have cut).
         ValueError, before any launch: a parameter check_scan refuses, a file too short (by its index), speed_search on."""
+        if self.general_geometry:
+            rt.refuse_general_geometry("scan")
         if self.speed_search is not None:
             raise ValueError("scan: speed_search is on for this detector; scanning at candidate speeds is not supported")
         d = self.scan_defaults

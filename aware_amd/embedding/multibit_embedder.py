@@ -29,7 +29,8 @@ class AWAREEmbedder(BaseEmbedder):
                  pattern_mode: str = "bits2bipolar", embedding_bands=(500, 4000), tolerance_db: float = 6.0,
                  num_iterations: int = 400, detection_net_cfg: dict = None, optimizer_cfg: dict = None,
                  scheduler_cfg: dict = None, loss: str = "push", verbose: bool = True, use_graph: bool = True,
-                 loop_attacks=None, loop_attack_seed: int = 0, loop_attack_mixture=None, payload_code=None):
+                 loop_attacks=None, loop_attack_seed: int = 0, loop_attack_mixture=None, payload_code=None,
+                 general_geometry: bool = False):
         """loop_attacks (EXTENSION, see embedding/loop_attacks.py): a chain of attacks applied inside the optimisation loop,
         e.g. [{"kind": "gaussian_noise", "snr_db": 10.0}, {"kind": "sample_suppression", "seconds": 0.3, "prob": 0.75}];
         clip i of a batch draws with seed loop_attack_seed + i.  None: the reference's loop (clean synthesis only).
@@ -37,8 +38,13 @@ class AWAREEmbedder(BaseEmbedder):
         what the weights leave of 1, none) afresh at every step, so one watermark meets several attack families.  Giving
         both loop_attacks and loop_attack_mixture is a ValueError.
         payload_code (EXTENSION, utils/watermark/fec.py): {"rate": "1/2" or "1/3", "crc": 0, 8 or 16}, the channel code of
-        service.embed_message; None: no code.  embed() itself is not changed by it."""
-        rt.require_card_geometry("AWAREEmbedder", frame_length, hop_length, win_length)
+        service.embed_message; None: no code.  embed() itself is not changed by it.
+        general_geometry (EXTENSION): embed at any frame_length in runtime.GENERAL_NFFT, any
+        hop_length and win_length in 1..frame_length, on the general route (the card geometry included); off: the card
+        geometry only, on the card kernels.  With it, loop_attacks, loop_attack_mixture and the loss push_extremes_l1 raise
+        NotImplementedError, and detection_net_cfg.n_fft has to equal frame_length."""
+        self.general_geometry = bool(general_geometry)
+        rt.require_card_geometry("AWAREEmbedder", frame_length, hop_length, win_length, self.general_geometry, window)
         self.frame_length, self.hop_length, self.window, self.win_length = frame_length, hop_length, window, win_length
         self.device = torch.device("cuda")
         self.embedding_bands = tuple(embedding_bands)
@@ -47,6 +53,10 @@ class AWAREEmbedder(BaseEmbedder):
         self.pattern_mode = pattern_mode
         self.detection_net = AWAREDetectorNet(**(detection_net_cfg or {}))
         self.detection_net.embedding_bands = self.embedding_bands
+        if self.general_geometry and self.detection_net.n_fft != frame_length:
+            # the mel bank is [n_mels, n_fft/2 + 1] and multiplies spectra of frame_length/2 + 1 bins
+            raise ValueError(f"AWAREEmbedder: detection_net_cfg.n_fft = {self.detection_net.n_fft} but frame_length = "
+                             f"{frame_length}; with general_geometry the detector's mel bank follows the STFT")
         self.payload_code = fec.check_payload_code(payload_code)      # ValueError naming the key
         if self.payload_code:
             fec.capacity(self.detection_net.output_length, **self.payload_code)   # ValueError where no message bit is left
@@ -55,6 +65,8 @@ class AWAREEmbedder(BaseEmbedder):
         self.optimizer_name, self.optimizer_params = optimizer_cfg["name"], optimizer_cfg.get("params", {}) or {}
         self.scheduler_name, self.scheduler_params = scheduler_cfg["name"], scheduler_cfg.get("params", {}) or {}
         self.loss = get_loss_fn(loss)                     # ValueError on an unknown name, as the reference
+        if self.general_geometry and getattr(self.loss, "l1_weight", 0.0):
+            rt.refuse_general_geometry("the loss push_extremes_l1 (its L1 term lives in the streaming kernels)")
         self._opt = get_optimizer(self.optimizer_name, None, **self.optimizer_params)
         self._sched = get_scheduler(self.scheduler_name, self._opt, num_iterations, **self.scheduler_params)
         self.verbose = verbose
@@ -63,6 +75,10 @@ class AWAREEmbedder(BaseEmbedder):
         self.loop_attack_mixture = parse_mixture(loop_attack_mixture)      # ValueError with the index of the offending chain
         if self.loop_attacks and self.loop_attack_mixture:
             raise ValueError("AWAREEmbedder: loop_attacks or loop_attack_mixture, not both")
+        if self.general_geometry and self.loop_attacks:
+            rt.refuse_general_geometry("loop_attacks")
+        if self.general_geometry and self.loop_attack_mixture:
+            rt.refuse_general_geometry("loop_attack_mixture")
         self.loop_attack_seed = int(loop_attack_seed)
         self.conv_pipe = "f16x2"                       # runtime.CONV_PIPES: arithmetic of the detector's conv-block GEMMs
         self.conv_tile = "auto"                        # runtime.CONV_TILES: form of the f16 two-term conv kernel (same bits)
@@ -77,9 +93,22 @@ class AWAREEmbedder(BaseEmbedder):
         return allb[mask], allb[~mask]
 
     def _plan(self, sample_rate):
-        rt.require_card_geometry("AWAREEmbedder", self.frame_length, self.hop_length, self.win_length)
+        rt.require_card_geometry("AWAREEmbedder", self.frame_length, self.hop_length, self.win_length, self.general_geometry,
+                                 self.window)
         return get_plan(self.frame_length, self.hop_length, self.window,
-                        band_bins(sample_rate, self.frame_length, self.embedding_bands), win_length=self.win_length)
+                        band_bins(sample_rate, self.frame_length, self.embedding_bands), win_length=self.win_length,
+                        general=self.general_geometry)
+
+    def check_clips(self, lengths):
+        """With general_geometry: ValueError naming the first clip the geometry cannot embed (runtime.check_general_clips: too
+        short, NOLA); needs no GPU.  Without the key the card batch checks its clips itself."""
+        if self.general_geometry:
+            rt.check_general_clips("AWAREEmbedder", self.frame_length, self.hop_length, self.win_length, self.window, lengths)
+
+    def make_batch(self, lengths, sample_rate: int) -> "rt.Batch":
+        """The batch geometry of this embedder's plan for clips of `lengths` samples."""
+        self.check_clips(lengths)
+        return rt.Batch(list(lengths), plan=self._plan(sample_rate) if self.general_geometry else None)
 
     # ---- batched hot path ----------------------------------------------------------------------
     def start_session(self, batch: "rt.Batch", sample_rate: int, attack_seeds=None) -> "rt.EmbedSession":
@@ -123,9 +152,9 @@ class AWAREEmbedder(BaseEmbedder):
 
     def embed_batch(self, clips, sample_rate: int, watermarks, rescale=None):
         """clips: list of 1-D float arrays; watermarks: [B, n_bits] bipolar.  Returns a list of
-        device tensors (one per clip, length 256*(T_b-1))."""
+        device tensors (one per clip, length hop_length*(T_b-1) with T_b = 1 + n_b // hop_length)."""
         t0 = time.time()
-        batch = rt.Batch([len(c) for c in clips])
+        batch = self.make_batch([len(c) for c in clips], sample_rate)
         wm = torch.as_tensor(np.asarray(watermarks), dtype=torch.float32, device="cuda")
         rs = None if rescale is None else torch.as_tensor(np.asarray(rescale), dtype=torch.float32, device="cuda")
         out, sess = self.embed_device(batch.pack(clips), batch, sample_rate, wm, rs)

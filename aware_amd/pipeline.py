@@ -44,13 +44,13 @@ class WatermarkPipeline:
         workspace, measured GEMM tile choice, hipGraph capture, resampler design.  Not part of a step."""
         key = tuple(int(n) for n in lengths_16k)
         if key not in self._sessions:
-            b = rt.Batch(list(key))
+            b = self.embedder.make_batch(list(key), self.sample_rate)
             self._sessions[key] = (b, self.embedder.start_session(b, self.sample_rate))
         batch, sess = self._sessions[key]
         sess.iterate(0)                                    # records the graphs without running them
         dkey = ("det",) + tuple(batch.out_lengths)
         if dkey not in self._sessions:
-            self._sessions[dkey] = rt.Batch(batch.out_lengths)
+            self._sessions[dkey] = self.detector.make_batch(batch.out_lengths, self.sample_rate)
         if input_rate and input_rate != self.sample_rate:
             from .attacks import _resample_filter
             g = int(np.gcd(self.sample_rate, input_rate))
@@ -68,7 +68,7 @@ class WatermarkPipeline:
         data = x.data if x.data.dtype == torch.float32 else x.data.float()
         key = ("det",) + tuple(x.lengths)
         if key not in self._sessions:
-            self._sessions[key] = rt.Batch(x.lengths)
+            self._sessions[key] = self.detector.make_batch(x.lengths, self.sample_rate)
         vals = self.detector.detect_device(data, self._sessions[key], self.sample_rate)
         return (vals > self.detector.threshold).to(torch.int32), vals
 
@@ -129,7 +129,7 @@ class WatermarkPipeline:
         self._host16k = x
         key = tuple(x.lengths)
         if key not in self._sessions:          # geometry tables + workspace are reused across steps
-            b = rt.Batch(x.lengths)
+            b = self.embedder.make_batch(x.lengths, self.sample_rate)
             self._sessions[key] = (b, self.embedder.start_session(b, self.sample_rate))
         batch, sess = self._sessions[key]
         target = (2 * bits - 1).to(torch.float32)                                  # PatternEncoder bits2bipolar

@@ -29,6 +29,12 @@ def band_stride(band_lo: int, band_hi: int) -> int:
     return SPEC_STRIDE if band_lo >= 1 and band_hi <= 511 and band_hi - band_lo + 1 <= SPEC_STRIDE else SPEC_STRIDE_WIDE
 
 
+def general_band_stride(nband: int) -> int:
+    """Row layout of a general plan's band-limited arrays (gen_plan_create, csrc/capi.hip): the band's bins rounded up to a
+    multiple of 64 -- 2112 floats for all 2049 bins of n_fft 4096."""
+    return (int(nband) + 63) // 64 * 64
+
+
 def stored_channels(channels: Sequence[int]) -> list[int]:
     """Channel counts a detector stores for the caller's `channels` = [n_mels, hidden widths..., 2 * payload bits]
     (stored_channels, csrc/capi.hip): the mel bank and every hidden width as is when a multiple of 4, else rounded up to a
@@ -70,7 +76,7 @@ def _dev():
 
 
 GENERAL_NFFT = (256, 512, 1024, 2048, 4096)
-PLAN_GENERAL = 1          # aware_plan_create_ex flag: the general kernels even for the card geometry
+PLAN_GENERAL = 1          # aware_plan_create_ex flag: the general kernels even for the card geometry, and the loop on them
 WINDOWS = {"hann": 0, "hamming": 1}
 
 
@@ -100,18 +106,54 @@ def nola_ok(n_fft: int, hop: int, win_length: int, window: str, n_samples: int) 
 CARD_GEOMETRY = (1024, 256, 1024)
 
 
-def require_card_geometry(who: str, n_fft: int, hop: int, win_length: int):
-    """The embed / detect loop runs on the model card's STFT geometry only (the general path serves the transforms)."""
+def require_card_geometry(who: str, n_fft: int, hop: int, win_length: int, general_geometry: bool = False,
+                          window: str = "hann"):
+    """Without the key `general_geometry` the embed / detect loop runs on the model card's STFT geometry only.  With it the
+    loop takes the general route at every geometry check_geometry accepts, the card's included."""
+    if general_geometry:
+        check_geometry(n_fft, hop, win_length, window)
+        return
     if (int(n_fft), int(hop), int(win_length)) != CARD_GEOMETRY:
         raise NotImplementedError(f"{who}: frame_length / hop_length / win_length {n_fft} / {hop} / {win_length} is not "
                                   f"supported; the embed and detect kernels run on the model card's geometry "
-                                  f"{CARD_GEOMETRY[0]} / {CARD_GEOMETRY[1]} / {CARD_GEOMETRY[2]} only")
+                                  f"{CARD_GEOMETRY[0]} / {CARD_GEOMETRY[1]} / {CARD_GEOMETRY[2]} only unless the key "
+                                  f"general_geometry is set (general_geometry=True, or `general_geometry: true` in the card)")
+
+
+def refuse_general_geometry(feature: str):
+    """What the general route does not serve: its kernels or its offsets are built on the card geometry (hop 256, a
+    512-sample pooling period).  NotImplementedError naming the feature and the key."""
+    raise NotImplementedError(f"{feature} is not supported with general_geometry=True: it runs on the model card's STFT "
+                              f"geometry {CARD_GEOMETRY[0]} / {CARD_GEOMETRY[1]} / {CARD_GEOMETRY[2]} only (key general_geometry off)")
+
+
+def check_general_clips(who: str, n_fft: int, hop: int, win_length: int, window: str, lengths, embed: bool = True):
+    """The clips a general plan takes, checked on the host before any launch; ValueError naming the clip.  Every clip needs
+    more than n_fft/2 samples (torch.stft's reflect padding).  For embedding it also has to pass torch.istft's NOLA
+    condition (nola_ok) and leave a synthesis (hop * (T - 1) samples, T = 1 + n // hop frames) that the loop's second STFT
+    can pad: more than n_fft/2 samples, or so few frames (T < 4, one pooled frame) that every block's InstanceNorm reads 0
+    whatever the spectrum holds."""
+    for i, n in enumerate(int(x) for x in lengths):
+        if n <= n_fft // 2:
+            raise ValueError(f"{who}: clip {i} has {n} samples; every clip needs more than n_fft/2 = {n_fft // 2}")
+        if not embed:
+            continue
+        if not nola_ok(n_fft, hop, win_length, window, n):
+            raise ValueError(f"{who}: clip {i} ({n} samples) fails the NOLA condition of torch.istft for n_fft {n_fft}, hop "
+                             f"{hop}, win_length {win_length}, {window} window (the window's overlap-add envelope drops below "
+                             f"1e-11 inside the output)")
+        frames = 1 + n // hop
+        if frames < 2 or (hop * (frames - 1) <= n_fft // 2 and frames >= 4):
+            raise ValueError(f"{who}: clip {i} ({n} samples) synthesises to {hop * (frames - 1)} samples at hop {hop}; the loop's "
+                             f"second STFT needs more than n_fft/2 = {n_fft // 2}")
 
 
 class Plan:
-    """FFT tables + window + embedding band (aware_plan).  The card geometry (1024 / 256 / 1024) gives the plan of the
-    embed / detect loop; any other supported geometry (or general=True) a general plan, which serves stft / istft /
-    stft_bwd / istft_bwd only (spectra of `spectrum_stride` complex values per row)."""
+    """FFT tables + window + embedding band (aware_plan).  The card geometry (1024 / 256 / 1024) gives the card plan of the
+    embed / detect loop; any other supported geometry (or general=True) a general plan: stft / istft / stft_bwd / istft_bwd
+    on spectra of `spectrum_stride` complex values per row, and with general=True (the flag PLAN_GENERAL, what the key
+    general_geometry passes) also the loop's general route, on band rows of `band_stride` floats (the band's bins rounded up
+    to a multiple of 64), when the band lies inside bins 0..n_fft/2."""
 
     def __init__(self, n_fft=1024, hop=256, win_length=1024, window="hann", band_bins=(32, 256), general=False):
         require_gpu()

@@ -34,6 +34,8 @@ class DetectorTrainer:
         from .embedding.optimizers import get_optimizer, step_table
         self.detector = detector
         self.net = detector.detection_net
+        if getattr(detector, "general_geometry", False):
+            rt.refuse_general_geometry("DetectorTrainer")
         if not getattr(self.net, "is_card_arch", True):
             raise NotImplementedError("DetectorTrainer supports the model card's detector architecture only "
                                       "(instance norm, leaky_relu blocks, tanh read-out)")

@@ -26,13 +26,14 @@ def band_bins(sample_rate: int, n_fft: int, bands) -> tuple:
     return int(idx[0]), int(idx[-1])
 
 
-def get_plan(n_fft=1024, hop=256, window="hann", bins=(32, 256), win_length=None) -> "rt.Plan":
-    """Cached plan per geometry (win_length None = n_fft): the card plan for 1024 / 256 / 1024, a general plan (transforms
-    only) for any other geometry rt.check_geometry accepts."""
+def get_plan(n_fft=1024, hop=256, window="hann", bins=(32, 256), win_length=None, general=False) -> "rt.Plan":
+    """Cached plan per geometry (win_length None = n_fft): the card plan for 1024 / 256 / 1024, a general plan for any other
+    geometry rt.check_geometry accepts, and for the card geometry too with general=True (the key general_geometry)."""
     win_length = n_fft if win_length is None else win_length
-    key = (n_fft, hop, win_length, window, tuple(bins), torch.cuda.current_device() if torch.cuda.is_available() else -1)
+    key = (n_fft, hop, win_length, window, tuple(bins), bool(general),
+           torch.cuda.current_device() if torch.cuda.is_available() else -1)
     if key not in _PLANS:
-        _PLANS[key] = rt.Plan(n_fft, hop, win_length, window, bins)
+        _PLANS[key] = rt.Plan(n_fft, hop, win_length, window, bins, general=general)
     return _PLANS[key]
 
 

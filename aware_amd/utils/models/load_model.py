@@ -12,7 +12,9 @@ _CARD = Path(__file__).resolve().parents[2] / "cards" / "config.yaml"
 
 # constructor argument -> (card key, default); tuples for the band edges like the reference
 _SHARED = {"frame_length": ("frame_length", 1024), "hop_length": ("hop_length", 256),
-           "window": ("window", "hann"), "win_length": ("win_length", 1024)}
+           "window": ("window", "hann"), "win_length": ("win_length", 1024),
+           # EXTENSION: the embed / detect loop at any STFT geometry; absent = the card geometry only
+           "general_geometry": ("general_geometry", False)}
 _EMBEDDER = {"pattern_mode": ("pattern_mode", "bits2bipolar"), "tolerance_db": ("tolerance_db", 6.0),
              "num_iterations": ("num_iterations", 400), "detection_net_cfg": ("detection_net_cfg", {}),
              "optimizer_cfg": ("optimizer_cfg", {"name": "nadam", "params": {"lr": 0.1}}),

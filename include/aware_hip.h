@@ -38,7 +38,7 @@ extern "C" {
 
 #define AWARE_OK 0
 #define AWARE_E_BADARG (-1)
-#define AWARE_E_UNSUPPORTED (-2)   /* e.g. n_fft outside {256, ..., 4096}, a general plan where only the card's geometry runs */
+#define AWARE_E_UNSUPPORTED (-2)   /* e.g. n_fft outside {256, ..., 4096}, a general plan where only the card's geometry runs (loop attacks, the L1 loss) */
 #define AWARE_E_HIP (-3)           /* a HIP runtime call failed; see aware_last_hip_error() */
 #define AWARE_E_WORKSPACE (-4)     /* caller's workspace too small */
 
@@ -70,7 +70,9 @@ typedef struct aware_stoi_plan aware_stoi_plan;
  * aware_detector_create accepts any even channels[n_layers] from 2 to 1024; 350: detector sizes -- n_mels 1..512, hidden
  * widths 1..4096, n_layers 1..33).  The STOI entry points (aware_stoi_create, aware_stoi_destroy, aware_stoi_workspace_bytes,
  * aware_stoi, aware_stoi_band_edges, aware_stoi_frames) were added without a version step -- tests/test_detector_sizes_host.py
- * pins the literal 350 -- so a caller detects them by symbol. */
+ * pins the literal 350 -- so a caller detects them by symbol.  The embed / detect loop on general plans (the general route)
+ * came without a version step for the same reason and adds no symbol: a caller detects it by aware_detector_create
+ * returning AWARE_OK for a plan created with AWARE_PLAN_GENERAL (before: AWARE_E_UNSUPPORTED). */
 int aware_version(void);
 /* text of the last failed HIP runtime call on the calling thread (thread-local) */
 const char* aware_last_hip_error(void);
@@ -90,11 +92,20 @@ void aware_plan_destroy(aware_plan* plan);
 /* Geometries.  The model card's (n_fft 1024, hop 256, win_length 1024) gives a card plan: the kernels of the embed / detect
  * loop.  Every other geometry with n_fft in {256, 512, 1024, 2048, 4096} (else AWARE_E_UNSUPPORTED), 1 <= hop <= n_fft and
  * 1 <= win_length <= n_fft (else AWARE_E_BADARG) gives a GENERAL plan (csrc/stft_any.hip): the window of win_length samples
- * is zero-padded to n_fft and centred as torch.stft does.  A general plan serves only aware_stft, aware_istft,
- * aware_stft_bwd and aware_istft_bwd, on batches made by aware_batch_create_for_plan; the band arguments are not used, and
- * every other entry point that takes a plan returns AWARE_E_UNSUPPORTED for it.
+ * is zero-padded to n_fft and centred as torch.stft does.  A general plan serves aware_stft, aware_istft, aware_stft_bwd
+ * and aware_istft_bwd on batches made by aware_batch_create_for_plan, with any band arguments.  Created with the flag
+ * AWARE_PLAN_GENERAL (below) and a band inside bins 0..n_fft/2 it also serves the loop on the GENERAL ROUTE (csrc/loop_any.hip): aware_detector_create[_ex],
+ * aware_detect, aware_embed_create / _begin / _iterate / _gradient / _profile / _finish / _buffer and
+ * aware_embed_set_optimizer, with a batch made for that plan and a detector created for it (anything else: AWARE_E_BADARG;
+ * a band outside the spectrum: AWARE_E_UNSUPPORTED from aware_detector_create).  A general plan created without the flag
+ * is a plan for the transforms alone: aware_detector_create, aware_detect and aware_embed_create return
+ * AWARE_E_UNSUPPORTED for it before they read another argument, as they always did.  The mel basis handed to
+ * aware_detector_create is then [n_mels][n_fft/2 + 1].  Not on a general plan: aware_stft_band, the loop attacks and
+ * mixtures and the loss AWARE_LOSS_PUSH_L1 (AWARE_E_UNSUPPORTED), aware_detector_forward / _backward and the training entry
+ * points (AWARE_E_BADARG for a general batch).  aware_embed_create also refuses (AWARE_E_BADARG) a batch with a clip that
+ * fails aware_nola_check or is shorter than one hop.
  * aware_plan_create_ex: flags AWARE_PLAN_GENERAL builds a general plan even for the card geometry (tests hold the two
- * paths against each other).  aware_plan_create(...) == aware_plan_create_ex(..., 0). */
+ * paths against each other) and opens the loop on the plan, whatever its geometry.  aware_plan_create(...) == aware_plan_create_ex(..., 0). */
 #define AWARE_PLAN_GENERAL 1
 int aware_plan_create_ex(aware_plan** out, int n_fft, int hop, int win_length, int window, int band_lo_bin,
                          int band_hi_bin, int flags);
@@ -103,8 +114,9 @@ int aware_plan_create_ex(aware_plan** out, int n_fft, int hop, int win_length, i
 int aware_plan_spectrum_stride(const aware_plan* plan);
 /* 1 for a general plan, 0 for the card plan */
 int aware_plan_is_general(const aware_plan* plan);
-/* floats per row of the plan's band-limited arrays: AWARE_SPEC_STRIDE or AWARE_SPEC_STRIDE_WIDE (card plans; a general plan,
- * which has no band kernels, reports AWARE_SPEC_STRIDE).  The *_workspace_bytes functions count rows of this stride. */
+/* floats per row of the plan's band-limited arrays: AWARE_SPEC_STRIDE or AWARE_SPEC_STRIDE_WIDE for a card plan; for a
+ * general plan the band's bins rounded up to a multiple of 64 (2112 for all 2049 bins of n_fft 4096; AWARE_SPEC_STRIDE when
+ * its band lies outside the spectrum).  The *_workspace_bytes functions count rows of this stride. */
 int aware_plan_band_stride(const aware_plan* plan);
 /* torch.istft's NOLA condition (host only, no device): AWARE_OK when the overlap-add envelope of this geometry stays
  * >= 1e-11 over the trimmed output of a clip of n_samples samples (T = 1 + n_samples/hop frames), AWARE_E_BADARG when
@@ -130,7 +142,9 @@ int aware_batch_analysis_run(const aware_batch* batch);
 /* a batch for a plan: frames T_b = 1 + n_b/hop by the plan's hop, istft outputs hop*(T_b - 1) samples, clips need more than
  * n_fft/2 samples (AWARE_E_BADARG otherwise).  For the card plan the same as aware_batch_create.  A general batch also holds
  * the overlap-add frame buffer of the synthesis direction ([total frames][n_fft] floats, allocated here), so one general batch
- * must not be used on two streams at the same time; total_pooled is 0 and the detector / embed entry points refuse it. */
+ * must not be used on two streams at the same time.  It has T_b/2 pooled frames per clip like a card batch
+ * (aware_batch_total_pooled), and aware_detect_workspace_bytes / aware_embed_workspace_bytes are exact for it: one byte
+ * less is AWARE_E_WORKSPACE. */
 int aware_batch_create_for_plan(aware_batch** out, const aware_plan* plan, int B, const int* n_samples,
                                 const int* in_offsets);
 
