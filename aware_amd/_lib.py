@@ -204,6 +204,7 @@ SIGNATURES = {
     "aware_gemm_clip_h2": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
     "aware_gemm_clip_h2_tile": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _sz, _i,
                                      _vp]),
+    "aware_gemm_clip_h2_form": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i]),
     "aware_gemm_nt": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp]),
 }
 

@@ -1133,7 +1133,8 @@ constexpr int kH2MinGrid = 128;
 // 128-column form's twice as many, half as heavy workgroups spread better.  Measured inside the embed loop on 3 s clips (ms per
 // iteration, 128-column form / wide form everywhere / this rule): 256 clips (512 and 1024 workgroups) 0.987 / 0.954 / 0.955;
 // 128 clips (256 and 512) 0.559 / 0.545 / 0.541 -- the 256-workgroup launches are better left narrow; 64 clips (128 and 256)
-// 0.340 / 0.366 / 0.340.  The crossover lies between 256 and 512 workgroups.  DESIGN.md section 4.
+// 0.340 / 0.366 / 0.340.  The crossover lies between 256 and 512 workgroups.  DESIGN.md section 4.  (With the wide form's
+// row-major epilogue: 0.976 / 0.922 / 0.921, 0.552 / 0.531 / 0.525, 0.339 / 0.366 / 0.338 -- the crossover has not moved.)
 constexpr int kH2WideMinGrid = 512;
 // conv_tile: aware_embed_config::conv_tile (0 automatic, 1 the 128-column form, 2 the wide form wherever it can run).
 // Returns the `tile` of launch_gemm_clip_h2 for a [B clips of nwm row groups] x N x K launch.
@@ -3300,6 +3301,16 @@ extern "C" int aware_gemm_clip_h2_tile(const float* A, int lda, const float* Bt,
                         (epi == 1 && lastpk && zpart) ? lastpk : nullptr, zpart, CL, tile == 2 ? 2 : 1);
     LAUNCHCHK();
     return AWARE_OK;
+}
+// the form aware_gemm_clip_h2_tile runs for these arguments (the launcher's own decision): 1 = 128-column, 2 = wide with the
+// accumulator-layout epilogue, 3 = wide with the row-major epilogue; AWARE_E_* as the entry above would return
+extern "C" int aware_gemm_clip_h2_form(const float* C, int ldc, const float* act, int Tp, int N, int K, int lda, int epi, int last,
+                                       int tile) {
+    if (tile < 0 || tile > 2 || !C || Tp < 1 || Tp > 128 || epi < 0 || epi > 2) return AWARE_E_BADARG;
+    const int nwm = (Tp + 31) / 32;
+    if (!gemm_clip_h2_supported(nwm, N, K, lda) || N % 16) return AWARE_E_BADARG;
+    if (tile == 2 && !gemm_clip_h2_wide_supported(nwm, N, K, lda)) return AWARE_E_UNSUPPORTED;
+    return gemm_clip_h2_form(tile == 2 ? 2 : 1, nwm, epi, last != 0, C, ldc, act);
 }
 
 extern "C" int aware_gemm_nt(const float* A, int lda, const float* Bt, int ldb, const float* bias, float* C, int ldc,

@@ -19,6 +19,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "split_bf16.hpp"
+#include "conv_epilogue_rows.hpp"
 
 namespace aware {
 
@@ -53,7 +54,11 @@ __host__ __device__ inline int conv_slab_group(int tiles_n, int width, int K, in
 // NT column tiles per wave, NW waves: 1 x 8 (128-column slabs) everywhere, and 4 x 4 (256-column slabs, the wide form of the
 // f16 two-term kernel).  The epilogue walks a wave's column tiles one after the other with the arithmetic of the 1 x 8 form on
 // each, so every output, statistic and partial maximum has the same bits at any NT.
-template <class P, int RG, int EPI, int NT = 1, int NW = 8>
+// ROWS (wide form only; needs ldc % 4 == 0 and 16-byte aligned C and act, which the launcher checks): C leaves, and the data
+// gradient's `act` arrives, in ROW-MAJOR order -- 16 bytes per lane, every wave instruction eight whole 128-byte row pieces --
+// turned through a wave-private quarter of the staging memory (conv_epilogue_rows.hpp), instead of in the accumulator's
+// layout (four 64-byte row pieces per instruction).  Only the path between register and memory differs: same bits.
+template <class P, int RG, int EPI, int NT = 1, int NW = 8, bool ROWS = false>
 __device__ __forceinline__ void conv_block_uniform(const float* __restrict__ A, int lda, const u32x4* __restrict__ Bpk,
                                                    const float* __restrict__ binv, const float* __restrict__ amax_in,
                                                    float* __restrict__ amax_out, const float* __restrict__ bias,
@@ -66,6 +71,7 @@ __device__ __forceinline__ void conv_block_uniform(const float* __restrict__ A, 
     constexpr int W = conv_tile_width(NT, NW);
     static_assert(NT == 1 || P::kScaled, "the row-major PLAIN epilogue of the unscaled format is written for one column tile");
     static_assert(W % 128 == 0 && (NW == 8 || NW == 4), "FWD_LAST works on whole 128-column slabs with 4 or 8 waves");
+    static_assert(!ROWS || (NT == 4 && NW == 4 && P::kScaled), "the row-major epilogue is written for the wide form");
     __shared__ __attribute__((aligned(16))) unsigned char lds[conv_block_lds_bytes<P, RG, EPI>()];
 
     // Blocks b and b + 8 share an XCD (observed round-robin placement; speed only).  An XCD takes a contiguous range of clips and
@@ -140,10 +146,47 @@ __device__ __forceinline__ void conv_block_uniform(const float* __restrict__ A, 
             return;
         }
     }
-    // (the forward / backward epilogues keep the accumulator-layout stores: behind the K loop of a second resident workgroup
-    //  they are hidden -- the row-major form measured the same time on the three conv blocks)
+    // (the 128-column form keeps the accumulator-layout stores: at four waves per SIMD, behind the K loop of a second resident
+    //  workgroup, they are hidden -- the row-major form measured the same time on the three conv blocks.  The wide form has two
+    //  waves per SIMD to hide them behind and takes the row-major path, ROWS.)
+    // ROWS: the wave's region [32 RG][32] f32 of the staging memory, one half (two column tiles) of its tile at a time
+    namespace er = epi_rows;
+    constexpr int RJ = ROWS ? er::row_passes(RG) : 1;
+    constexpr bool kTurn = ROWS && EPI != X3_FWD_LAST;          // (FWD_LAST stores from the slab it lays out below)
+    float* const reg = reinterpret_cast<float*>(lds) + wave * er::region_floats(RG);
+    // what orders a wave's own LDS traffic: its DS instructions execute in order, the compiler must not move them
+    auto wave_sync = [&]() {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    };
+    // half h of the wave's tile in global memory, row-major: pass j = rows 8 j .. 8 j + 7, eight lanes per 128-byte piece
+    auto half_offset = [&](int h, int j) {
+        return (size_t)(bm + er::rm_row(lane, j)) * ldc + (bn + wave * (16 * NT) + 32 * h + er::rm_col(lane));
+    };
+    // the data gradient's `act`: the fragment registers of the K loop are dead, so both halves are requested at once, ahead of
+    // the barrier (no spill at RG = 3 beside the 96 accumulators: 251 VGPRs)
+    f32x4 ar[2][RJ];
+    auto load_act = [&](int h) {
+#pragma unroll
+        for (int j = 0; j < RJ; ++j) ar[h][j] = *reinterpret_cast<const f32x4*>(act + half_offset(h, j));
+    };
+    if constexpr (kTurn) {
+        if constexpr (EPI == X3_BWD) {
+            load_act(0);
+            load_act(1);
+        }
+        __syncthreads();                                    // every wave has left the K loop: the staging memory is free
+    }
 #pragma unroll
     for (int n = 0; n < NT; ++n) {
+    if constexpr (kTurn && EPI == X3_BWD) {
+        if ((n & 1) == 0) {
+#pragma unroll
+            for (int j = 0; j < RJ; ++j) *reinterpret_cast<f32x4*>(reg + er::act_write(lane, j)) = ar[n >> 1][j];
+            wave_sync();
+        }
+    }
     const int col = col0 + 16 * n;
     float bcol = 1.f;
     if constexpr (P::kScaled) bcol = binv[col];
@@ -157,7 +200,8 @@ __device__ __forceinline__ void conv_block_uniform(const float* __restrict__ A, 
                 const int row = m * 16 + 4 * kg + e;
                 const float o = row < Tp ? fmaf(acc[m][n][e] * ainv, bcol, bv) : 0.f;
                 omax = fmaxf(omax, fabsf(o));
-                if (P::kScaled || bm + row < Mrows) C[(size_t)(bm + row) * ldc + col] = o;
+                if constexpr (ROWS) acc[m][n][e] = o;
+                else if (P::kScaled || bm + row < Mrows) C[(size_t)(bm + row) * ldc + col] = o;
             }
     } else if (EPI == X3_FWD || EPI == X3_FWD_LAST) {
         const float bv = bias ? bias[col] : 0.f;
@@ -205,7 +249,7 @@ __device__ __forceinline__ void conv_block_uniform(const float* __restrict__ A, 
                 const float o = row < Tp ? (u > 0.f ? u : 0.2f * u) : 0.f;
                 acc[m][n][e] = o;
                 omax = fmaxf(omax, fabsf(o));
-                C[(size_t)(bm + row) * ldc + col] = o;
+                if constexpr (!ROWS) C[(size_t)(bm + row) * ldc + col] = o;
             }
     } else {
         // X3_BWD: acc = dL/dA of the previous block's output (read from `act`, post-activation);
@@ -219,7 +263,9 @@ __device__ __forceinline__ void conv_block_uniform(const float* __restrict__ A, 
             for (int e = 0; e < 4; ++e) {
                 const int row = m * 16 + 4 * kg + e;
                 // unconditional load (padding rows exist and hold zeros): a branch here would serialise the loads
-                const float av = act[(size_t)(bm + row) * ldc + col];
+                float av;
+                if constexpr (ROWS) av = reg[er::act_read(lane, m, n & 1, e)];
+                else av = act[(size_t)(bm + row) * ldc + col];
                 const bool valid = row < Tp;
                 const float uv = valid ? (av > 0.f ? av : av * 5.0f) : 0.f;                 // invert LeakyReLU(0.2)
                 const float du = valid ? acc[m][n][e] * ainv * bcol * (av > 0.f ? 1.f : 0.2f) : 0.f;
@@ -240,8 +286,24 @@ __device__ __forceinline__ void conv_block_uniform(const float* __restrict__ A, 
                 const int row = m * 16 + 4 * kg + e;
                 const float o = row < Tp ? rs * (acc[m][n][e] - m1 - u[m][e] * m2) : 0.f;
                 omax = fmaxf(omax, fabsf(o));
-                C[(size_t)(bm + row) * ldc + col] = o;
+                if constexpr (ROWS) acc[m][n][e] = o;
+                else C[(size_t)(bm + row) * ldc + col] = o;
             }
+    }
+    if constexpr (kTurn) {
+        // the finished column tile (zeros in its padding rows) goes to the region -- in the data gradient onto the slots its
+        // `act` values were just read from; after the second tile of a half the half leaves in whole rows
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) reg[er::c_write(lane, m, n & 1, e)] = acc[m][n][e];
+        if (n & 1) {
+            wave_sync();
+#pragma unroll
+            for (int j = 0; j < RJ; ++j)
+                *reinterpret_cast<float4*>(C + half_offset(n >> 1, j)) = *reinterpret_cast<const float4*>(reg + er::c_read(lane, j));
+            wave_sync();
+        }
     }
     if constexpr (P::kScaled) {
         if (amax_out) {
@@ -289,6 +351,16 @@ __device__ __forceinline__ void conv_block_uniform(const float* __restrict__ A, 
                         T[(16 * m + 4 * kg + e) * TP + 16 * ((wave % WS) * NT + n) + r16] = acc[m][n][e];
         }
         __syncthreads();
+        if constexpr (ROWS) {
+            // C leaves from the slab: half a wave = one 512-byte row segment, eight rows per pass of the four waves
+            const int c4 = (lane & 31) * 4, rr = 2 * wave + (lane >> 5);
+#pragma unroll
+            for (int j = 0; j < 4 * RG; ++j) {
+                const int row = rr + 8 * j;
+                *reinterpret_cast<float4*>(C + (size_t)(bm + row) * ldc + bn + 128 * sl + c4) =
+                    *reinterpret_cast<const float4*>(T + row * TP + c4);
+            }
+        }
         f32x4 zt[UH * MH][3];
 #pragma unroll
         for (int mm = 0; mm < UH * MH; ++mm) {

@@ -282,14 +282,15 @@ struct H2Ops {
 // the conv block / data-gradient kernel for uniform batches (epilogues as gemm_clip_x3_kernel, plus the per-clip scales).
 // NT x NW = 1 x 8: 128-column slabs, 512 threads, <= 128 VGPRs for RG <= 3 (two workgroups per CU).  4 x 4 (the wide form,
 // RG <= 3): 256-column slabs, 256 threads at two waves per SIMD (again two workgroups per CU).
-template <int RG, int EPI, int NT = 1, int NW = 8>
+// ROWS (wide form only): the row-major epilogue of conv_block_uniform, chosen by the launcher.
+template <int RG, int EPI, int NT = 1, int NW = 8, bool ROWS = false>
 __global__ __launch_bounds__(64 * NW, NT > 1 ? 2 : RG <= 3 ? 4 : 2) void gemm_clip_h2_kernel(
     const float* __restrict__ A, int lda, const u32x4* __restrict__ Bpk, const float* __restrict__ binv,
     const float* __restrict__ amax_in, float* __restrict__ amax_out, const float* __restrict__ bias, float* __restrict__ C, int ldc,
     int Tp, int N, int K, int tiles_n, int ntiles, float* __restrict__ rstd_io, const float* __restrict__ act,
     const u32x4* __restrict__ Lpk, float* __restrict__ zpart, int CL) {
-    conv_block_uniform<H2Ops, RG, EPI, NT, NW>(A, lda, Bpk, binv, amax_in, amax_out, bias, C, ldc, Tp, N, K, tiles_n, ntiles, rstd_io,
-                                               act, Lpk, zpart, CL, 0);
+    conv_block_uniform<H2Ops, RG, EPI, NT, NW, ROWS>(A, lda, Bpk, binv, amax_in, amax_out, bias, C, ldc, Tp, N, K, tiles_n, ntiles,
+                                                     rstd_io, act, Lpk, zpart, CL, 0);
 }
 
 // Ragged batches (as gemm_ragged_x3_kernel): the clip's scale comes from amax_in as in the uniform kernel; the partial maxima
@@ -374,23 +375,42 @@ bool gemm_clip_h2_wide_supported(int nwm, int N, int K, int lda) {
 // Bpk: launch_h2_pack image of Wt [N][K]; amax_in: [B][64] partial maxima of A's clips (K/16 valid per clip); amax_out: the
 // same for C ([B][64], N/16 written per clip) or null; lastpk / zpart / CL as launch_gemm_clip_x3 (gemm_x3.hip's pack, N / 128
 // partial slabs at either tile).  tile: 1 or 2 (2 only where gemm_clip_h2_wide_supported).
+// The epilogues of the wide form that take the row-major path where the buffers allow it (bit X3_*; conv_block.hpp, ROWS).
+// A build may narrow the set to hold single epilogues against their accumulator-layout form.
+#ifndef AWARE_H2_ROW_EPILOGUES
+#define AWARE_H2_ROW_EPILOGUES ((1 << X3_PLAIN) | (1 << X3_FWD) | (1 << X3_BWD) | (1 << X3_FWD_LAST))
+#endif
+constexpr int kH2RowEpilogues = AWARE_H2_ROW_EPILOGUES;
+
+// The form a launch takes: 1 = 128-column slabs, 2 = wide with the accumulator-layout epilogue, 3 = wide with the row-major
+// epilogue, whose 16-byte accesses need ldc % 4 == 0 and 16-byte aligned C and act (last: the forward epilogue with lastpk / zpart).
+int gemm_clip_h2_form(int tile, int nwm, int epi, bool last, const float* C, int ldc, const float* act) {
+    if (tile != 2 || nwm > 3) return 1;
+    if (epi == X3_FWD && last) epi = X3_FWD_LAST;
+    const bool aligned = (ldc & 3) == 0 && ((uintptr_t)C & 15) == 0 && (epi != X3_BWD || ((uintptr_t)act & 15) == 0);
+    return aligned && ((kH2RowEpilogues >> epi) & 1) ? 3 : 2;
+}
+
 void launch_gemm_clip_h2(const float* A, int lda, const void* Bpk, const float* amax_in, float* amax_out, const float* bias,
                          float* C, int ldc, int B, int nwm, int Tp, int N, int K, int epi, float* rstd_io, const float* act,
                          hipStream_t st, const void* lastpk, float* zpart, int CL, int tile) {
     const float* binv = h2_inv_scale(Bpk, N, K);
+    const int form = gemm_clip_h2_form(tile, nwm, epi, lastpk && zpart, C, ldc, act);
     if (epi == X3_FWD && lastpk && zpart) epi = X3_FWD_LAST;
-    const bool wide = tile == 2 && nwm <= 3;
+    const bool wide = form >= 2, rows = form == 3;
     const int tn = N / (wide ? kH2WideTile : 128);
-#define HK(M_, E_, NT_, NW_) hipLaunchKernelGGL((gemm_clip_h2_kernel<M_, E_, NT_, NW_>), dim3(tn * B), dim3(64 * NW_), 0, st, A, lda, \
-                                                (const u32x4*)Bpk, binv, amax_in, amax_out, bias, C, ldc, Tp, N, K, tn, tn * B,        \
-                                                rstd_io, act, (const u32x4*)lastpk, zpart, CL)
+#define HK(M_, E_, NT_, NW_, R_) hipLaunchKernelGGL((gemm_clip_h2_kernel<M_, E_, NT_, NW_, R_>), dim3(tn * B), dim3(64 * NW_), 0, st, \
+                                                    A, lda, (const u32x4*)Bpk, binv, amax_in, amax_out, bias, C, ldc, Tp, N, K, tn,    \
+                                                    tn * B, rstd_io, act, (const u32x4*)lastpk, zpart, CL)
+#define HW(M_, E_) if (rows) HK(M_, E_, 4, 4, true); else HK(M_, E_, 4, 4, false)
 #define HM(E_)                                                                                                                 \
-    if (wide) switch (nwm) { case 1: HK(1, E_, 4, 4); break; case 2: HK(2, E_, 4, 4); break; default: HK(3, E_, 4, 4); break; }  \
-    else switch (nwm) { case 1: HK(1, E_, 1, 8); break; case 2: HK(2, E_, 1, 8); break; case 3: HK(3, E_, 1, 8); break;          \
-                        default: HK(4, E_, 1, 8); break; }
+    if (wide) switch (nwm) { case 1: HW(1, E_); break; case 2: HW(2, E_); break; default: HW(3, E_); break; }                    \
+    else switch (nwm) { case 1: HK(1, E_, 1, 8, false); break; case 2: HK(2, E_, 1, 8, false); break;                            \
+                        case 3: HK(3, E_, 1, 8, false); break; default: HK(4, E_, 1, 8, false); break; }
     if (epi == X3_FWD) { HM(X3_FWD) } else if (epi == X3_BWD) { HM(X3_BWD) } else if (epi == X3_FWD_LAST) { HM(X3_FWD_LAST) }
     else { HM(X3_PLAIN) }
 #undef HM
+#undef HW
 #undef HK
 }
 

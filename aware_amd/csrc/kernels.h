@@ -159,6 +159,9 @@ bool gemm_clip_h2_supported(int nwm, int N, int K, int lda);
 // the wide form: 4 waves x 64 columns per workgroup (tile = 2 below) instead of 8 waves x 16 (tile = 1); same bits
 constexpr int kH2WideTile = 256;
 bool gemm_clip_h2_wide_supported(int nwm, int N, int K, int lda);
+// the form launch_gemm_clip_h2 takes for these arguments: 1 = 128-column, 2 = wide with the accumulator-layout epilogue,
+// 3 = wide with the row-major epilogue (ldc % 4 == 0, C and act 16-byte aligned); epi 0..2, last: epi 1 with lastpk / zpart
+int gemm_clip_h2_form(int tile, int nwm, int epi, bool last, const float* C, int ldc, const float* act);
 // amax_in: [B][64] partial maxima of |A| per clip (K/16 valid); amax_out: [B][64] the same of C (N/16 written) or null
 void launch_gemm_clip_h2(const float* A, int lda, const void* Bpk, const float* amax_in, float* amax_out, const float* bias,
                          float* C, int ldc, int B, int nwm, int Tp, int N, int K, int epi, float* rstd_io, const float* act,

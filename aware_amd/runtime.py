@@ -833,16 +833,25 @@ def gemm_clip(a: torch.Tensor, bt: torch.Tensor, bias, B: int, Tp: int, epi: int
 
 
 def gemm_clip_h2(a: torch.Tensor, bt: torch.Tensor, bias, B: int, Tp: int, epi: int = 0, rstd=None, act=None, w_last=None,
-                 tile: int = 0):
+                 tile: int = 0, out=None):
     """One clip-aligned conv block on the f16 two-term kernel (aware_gemm_clip_h2_tile; the embed loop's default conv pipe).
     tile: 0 or 1 = the 128-column form, 2 = the wide form (AwareHipError "unsupported" where it cannot run).
+    out: the caller's C, an [M, N] view of any row pitch ldc = out.stride(0) >= N (act, where given, has the same pitch).
     Returns (C, rstd, amax_out[B, 64]) and, with w_last [CL, N] (epi 1), also zpart [N/128, M, CL]."""
     lib = load_library()
     M, K = a.shape
     N = bt.shape[0]
     dev = a.device
     btd = bt.to(dev).contiguous()
-    c = torch.empty((M, N), dtype=torch.float32, device=dev)
+    if out is None:
+        c = torch.empty((M, N), dtype=torch.float32, device=dev)
+    else:
+        c = out
+        if tuple(c.shape) != (M, N) or c.stride(1) != 1 or c.stride(0) < N or c.dtype != torch.float32 or c.device != dev:
+            raise ValueError("out: an [M, N] f32 view on a's device with unit column stride and a row pitch of at least N")
+    ldc = c.stride(0)
+    if act is not None and (act.stride(0) != ldc or act.stride(1) != 1):
+        raise ValueError("act: the row pitch of C")
     if rstd is None:
         rstd = torch.zeros((B, N), dtype=torch.float32, device=dev)
     amax = torch.zeros((B, 64), dtype=torch.float32, device=dev)
@@ -855,11 +864,21 @@ def gemm_clip_h2(a: torch.Tensor, bt: torch.Tensor, bias, B: int, Tp: int, epi: 
         wl[:CL] = w_last.detach().cpu().float()
         pkl = x3_pack(wl)
         zpart = torch.zeros((N // 128, M, CL), dtype=torch.float32, device=dev)
-    check(lib.aware_gemm_clip_h2_tile(_ptr(a), a.stride(0), _ptr(btd), btd.stride(0), _ptr(bias), _ptr(c), N, B, Tp, N, K, epi,
+    check(lib.aware_gemm_clip_h2_tile(_ptr(a), a.stride(0), _ptr(btd), btd.stride(0), _ptr(bias), _ptr(c), ldc, B, Tp, N, K, epi,
                                       _ptr(rstd), _ptr(act), _ptr(pkl), _ptr(zpart), CL, _ptr(amax), _ptr(ws), nbytes, int(tile),
                                       _stream()), "aware_gemm_clip_h2_tile")
     torch.cuda.current_stream().synchronize()
     return (c, rstd, amax) if w_last is None else (c, rstd, amax, zpart)
+
+
+def gemm_clip_h2_form(c: torch.Tensor, act, Tp: int, K: int, epi: int = 0, last: bool = False, tile: int = 0) -> int:
+    """The form gemm_clip_h2 runs for this C (an [M, N] view, row pitch c.stride(0)) and act (aware_gemm_clip_h2_form):
+    1 = 128-column, 2 = wide with the accumulator-layout epilogue, 3 = wide with the row-major epilogue."""
+    lib = load_library()
+    rc = int(lib.aware_gemm_clip_h2_form(_ptr(c), c.stride(0), _ptr(act), Tp, c.shape[1], K, K, epi, int(last), int(tile)))
+    if rc < 0:
+        check(rc, "aware_gemm_clip_h2_form")
+    return rc
 
 
 def gemm_clip_last(a: torch.Tensor, bt: torch.Tensor, bias, w_last: torch.Tensor, B: int, Tp: int):

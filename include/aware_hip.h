@@ -939,6 +939,10 @@ int aware_gemm_clip_h2(const float* A, int lda, const float* Bt, int ldb, const 
 int aware_gemm_clip_h2_tile(const float* A, int lda, const float* Bt, int ldb, const float* bias, float* C, int ldc, int B,
                             int Tp, int N, int K, int epi, float* rstd_io, const float* act, const void* lastpk, float* zpart,
                             int CL, float* amax_out, void* workspace, size_t workspace_bytes, int tile, void* stream);
+/* Which form aware_gemm_clip_h2_tile runs for these arguments (no launch): 1 = 128-column slabs, 2 = the wide form with the
+ * accumulator-layout epilogue, 3 = the wide form with the row-major epilogue (16-byte loads and stores: ldc % 4 == 0, C and --
+ * epi 2 -- act 16-byte aligned).  last != 0: epi 1 with lastpk / zpart.  Same bits in every form.  AWARE_E_* as that entry. */
+int aware_gemm_clip_h2_form(const float* C, int ldc, const float* act, int Tp, int N, int K, int lda, int epi, int last, int tile);
 
 #ifdef __cplusplus
 }
