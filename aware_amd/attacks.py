@@ -281,6 +281,49 @@ class BandFilter(Attack):
         return rt.band_filter(x, RESPONSES[self.response], c1, c2)
 
 
+def _excerpt_bounds(name, seconds, start_seconds, x, sr):
+    """(starts, lengths) in samples of the excerpt of every clip of x: int(start_seconds * sr) and int(seconds * sr), inside it."""
+    s, L = int(start_seconds * sr), int(seconds * sr)
+    if L < 1 or any(s + L > n for n in x.lengths):
+        raise ValueError(f"{name}: the excerpt [{s}, {s + L}) at {sr} Hz does not lie inside clips of {list(x.lengths)} samples")
+    return [s] * x.B, [L] * x.B
+
+
+@register
+class Excerpt(Attack):
+    """EXTENSION (not in the reference, parity unpinned; its Cropout above drops the head only): the true excerpt, a shorter
+    clip: the int(seconds * sr) samples from int(start_seconds * sr) on, and nothing else.  What the embed loop's excerpt kind
+    is measured against; a detector needs more than 512 samples."""
+
+    def __init__(self, seconds, start_seconds=0.0):
+        self.seconds, self.start_seconds = float(seconds), float(start_seconds)
+        if not (np.isfinite(self.seconds) and np.isfinite(self.start_seconds) and self.seconds > 0.0 and self.start_seconds >= 0.0):
+            raise ValueError(f"Excerpt: seconds > 0 and start_seconds >= 0, both finite, are required; got {seconds!r}, {start_seconds!r}")
+        self.name = f"excerpt_{seconds}_at_{start_seconds}"
+
+    def apply_batch(self, x, sr):
+        starts, lengths = _excerpt_bounds("Excerpt", self.seconds, self.start_seconds, x, sr)
+        head = rt.segment_cut(x, [0] * x.B, starts, zero_fill=False)                        # x[start:]
+        return rt.segment_cut(head, lengths, [n - L for n, L in zip(head.lengths, lengths)], zero_fill=False)
+
+
+@register
+class ExcerptTile(Attack):
+    """EXTENSION (not in the reference, parity unpinned): the embed loop's excerpt operator at fixed values, applied after
+    embedding: the int(seconds * sr) samples from int(start_seconds * sr) on, repeated periodically until they fill the clip,
+    which keeps its length (embedding.loop_attacks.excerpt_tile).  Excerpt above is what the loop's kind is measured against;
+    this one is its own model."""
+
+    def __init__(self, seconds, start_seconds=0.0):
+        self.seconds, self.start_seconds = float(seconds), float(start_seconds)
+        if not (np.isfinite(self.seconds) and np.isfinite(self.start_seconds) and self.seconds > 0.0 and self.start_seconds >= 0.0):
+            raise ValueError(f"ExcerptTile: seconds > 0 and start_seconds >= 0, both finite, are required; got {seconds!r}, {start_seconds!r}")
+        self.name = f"excerpt_tile_{seconds}_at_{start_seconds}"
+
+    def apply_batch(self, x, sr):
+        return rt.excerpt_tile(x, *_excerpt_bounds("ExcerptTile", self.seconds, self.start_seconds, x, sr))
+
+
 def _scale(x: "rt.Ragged", gains) -> "rt.Ragged":
     """x times one gain curve per clip (torch tensors on x's device), float32."""
     data = x.data.float()

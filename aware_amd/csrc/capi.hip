@@ -2224,6 +2224,18 @@ extern "C" int aware_delete_samples(const float* in, const int* off, const int* 
     return AWARE_OK;
 }
 
+// ---- the tiled excerpt alone (EXTENSION; attacks.ExcerptTile, runtime.excerpt_tile, tests) ----------------------------------
+extern "C" int aware_excerpt_tile(const float* in, const int* off, const int* len, int B, int max_len, const int* start,
+                                  const int* length, float* out, int adjoint, void* stream) {
+    if (!in || !off || !len || !start || !length || !out || in == out) return AWARE_E_BADARG;
+    if (B < 1 || B > 65535 || max_len < 1 || max_len > (1 << 30) || adjoint < 0 || adjoint > 1) return AWARE_E_BADARG;
+    ExcerptLaunch L;
+    L.in = in; L.out = out; L.B = B; L.adjoint = adjoint; L.off = off; L.len = len; L.max_len = max_len; L.start = start; L.length = length;
+    launch_excerpt_tile(L, (hipStream_t)stream);
+    LAUNCHCHK();
+    return AWARE_OK;
+}
+
 // ---- the band filter alone (EXTENSION; attacks.BandFilter, runtime.band_filter, tests) -------------------------------------
 extern "C" int aware_band_filter(const float* in, const int* off, const int* len, int B, int max_len, const int* response,
                                  const int* c1, const int* c2, float* out, float* taps, void* stream) {
@@ -2552,6 +2564,11 @@ static DeleteLaunch delete_launch(const aware_embed* e, const LoopChainState& la
     S.k_lo = la.lo; S.k_hi = la.hi; S.at = la.at;
     return S;
 }
+static ExcerptLaunch excerpt_launch(const aware_embed* e, const LoopChainState& la, const float* in, float* out, int adjoint, int step_back) {
+    ExcerptLaunch S = stage_launch<ExcerptLaunch>(e, la, in, out, adjoint, step_back);
+    S.l_lo = la.lo; S.l_hi = la.hi;
+    return S;
+}
 static FilterLaunch filter_launch(const aware_embed* e, const LoopChainState& la, const float* in, float* out, int step_back) {
     FilterLaunch S = stage_launch<FilterLaunch>(e, la, in, out, 0, step_back);
     S.mask = la.mask; S.c_lo = la.lo; S.c_hi = la.hi; S.w_min = la.w_min;
@@ -2671,6 +2688,7 @@ static void split_forward(const aware_embed* e, const LoopChainState& la, hipStr
         // gy is free until the synthesis adjoint writes it, and carries the vocoded signal to the resampling
         case AWARE_LOOP_PHASE_VOCODER: pv_stage_forward(e, la, e->gy, st); break;
         case AWARE_LOOP_BAND_FILTER: launch_band_filter(filter_launch(e, la, la.u, la.z, 0), st); break;
+        case AWARE_LOOP_EXCERPT: launch_excerpt_tile(excerpt_launch(e, la, la.u, la.z, 0, 0), st); break;
         default: launch_delete_samples(delete_launch(e, la, la.u, la.z, 0, 0), st); break;      // AWARE_LOOP_DELETE_SAMPLES
     }
 }
@@ -2690,6 +2708,7 @@ static void split_backward(const aware_embed* e, const LoopChainState& la, int s
         case AWARE_LOOP_PITCH_SHIFT: launch_pitch_shift(ola_launch(e, la, la.u, e->gy, 1, step_back), st); break;
         case AWARE_LOOP_PHASE_VOCODER: pv_stage_backward(e, la, step_back, st); break;
         case AWARE_LOOP_BAND_FILTER: launch_band_filter(filter_launch(e, la, la.u, e->gy, step_back), st); break;      // its own adjoint
+        case AWARE_LOOP_EXCERPT: launch_excerpt_tile(excerpt_launch(e, la, la.u, e->gy, 1, step_back), st); break;
         default: launch_delete_samples(delete_launch(e, la, la.u, e->gy, 1, step_back), st); break;
     }
 }

@@ -605,6 +605,23 @@ struct FilterLaunch {
 };
 void launch_band_filter(const FilterLaunch& L, hipStream_t st);
 
+// ---- loop_excerpt_kernels.hip: tiled excerpt (EXTENSION): the excerpt [start, start + L) of the clip repeated periodically
+// until it fills the clip, inside the embed loop (chain kind 10) and stand-alone (aware_excerpt_tile), and its adjoint in
+// gather form: the sum over the periods in f32, m ascending ------------------------------------------------------------------
+struct ExcerptLaunch {
+    const float* in = nullptr; float* out = nullptr;      // never the same buffer
+    int B = 0, adjoint = 0;               // 0: out = z from in = x; 1: out = gx from in = gz
+    // the embed loop (draw.frame_off set): start and L drawn in the kernel
+    LoopDraw draw;
+    int l_lo = 0, l_hi = 0;               // kExcerptMinLen <= l_lo <= l_hi; a draw above Ny_b is read as Ny_b
+    // or a ragged batch (draw.frame_off null): both sides are len[b] floats at off[b]; start[b] and length[b] given, clamped to the clip
+    const int* off = nullptr; const int* len = nullptr;
+    int max_len = 0;                      // >= every length
+    const int* start = nullptr;           // [B]
+    const int* length = nullptr;          // [B]
+};
+void launch_excerpt_tile(const ExcerptLaunch& L, hipStream_t st);
+
 // ---- sync_kernels.hip: offset search in detection (EXTENSION): values [B][n][L] -> the row of the largest mean |v - centre|
 // per clip (the smallest j on a tie), its index and that mean; one wave per clip ------------------------------------------
 void launch_sync_select(const float* values, int B, int n, int L, float centre, float* out_values, int* out_index,

@@ -3,10 +3,10 @@
 // workspace.  Plain C++: no HIP header and no HIP call, so tests/host_sim/loop_chain_check.cpp runs it on the CPU.
 //
 // THE ONE-SPLIT RULE.  Kinds 0, 1 and 8 (noise, suppression, gain envelope) are element-wise and run inside the stage kernels of
-// loop_attack_kernels.hip.  Kinds 2 to 7 and 9 (reverberation, speed change, time stretch, pitch shift, phase vocoder, sample
-// deletion, band filter) each need launches of their own between two such stages: they SPLIT the chain.  A chain holds at most one
-// splitting entry.  The one exception: a speed change directly behind a time stretch (j == split + 1) forms one stage
-// u -> v -> z with it.  The host twin is embedding/loop_attacks.py::parse_chain (SPLITTING, SPLITTING_EX).
+// loop_attack_kernels.hip.  Kinds 2 to 7, 9 and 10 (reverberation, speed change, time stretch, pitch shift, phase vocoder, sample
+// deletion, band filter, tiled excerpt) each need launches of their own between two such stages: they SPLIT the chain.  A chain
+// holds at most one splitting entry.  The one exception: a speed change directly behind a time stretch (j == split + 1) forms one
+// stage u -> v -> z with it.  The host twin is embedding/loop_attacks.py::parse_chain (SPLITTING, SPLITTING_EX, SPLITTING_EX2).
 #pragma once
 #include <math.h>
 #include <stddef.h>
@@ -72,6 +72,7 @@ struct LoopChainState {
     //   phase vocoder   lo..hi: stretch offsets, lo2..hi2: speed offsets; lo > hi where the mode is absent
     //   sample deletion lo..hi: samples cut out; at 0: the cut starts at sample 0, 1: anywhere
     //   band filter     lo..hi: edges in 1 / 65536 cycle per sample; mask: the responses drawn from; w_min: a band's least width
+    //   tiled excerpt   lo..hi: samples of the excerpt
     int split = -1, split_kind = 0, pair_speed = -1;
     int lo = 0, hi = 0, lo2 = 0, hi2 = -1, at = 0, kmax = 0, mask = 0, w_min = 0;
     double gain = 0;
@@ -104,7 +105,8 @@ inline int parse_loop_chain(const LoopDims& d, const aware_loop_attack_ex* attac
                   AWARE_LOOP_REVERBERATION == kLoopReverberation && AWARE_LOOP_SPEED_CHANGE == kLoopSpeedChange &&
                   AWARE_LOOP_TIME_STRETCH == kLoopTimeStretch && AWARE_LOOP_PITCH_SHIFT == kLoopPitchShift &&
                   AWARE_LOOP_PHASE_VOCODER == kLoopPhaseVocoder && AWARE_LOOP_DELETE_SAMPLES == kLoopDeleteSamples &&
-                  AWARE_LOOP_GAIN_ENVELOPE == kLoopGainEnvelope && AWARE_LOOP_BAND_FILTER == kLoopBandFilter, "");
+                  AWARE_LOOP_GAIN_ENVELOPE == kLoopGainEnvelope && AWARE_LOOP_BAND_FILTER == kLoopBandFilter &&
+                  AWARE_LOOP_EXCERPT == kLoopExcerpt, "");
     if (!attacks || n_attacks < 1 || n_attacks > kMaxLoopAttacks) return AWARE_E_BADARG;
     la.split = -1; la.pair_speed = -1; la.h = nullptr; la.v = nullptr;
     for (int j = 0; j < n_attacks; ++j) {
@@ -129,7 +131,8 @@ inline int parse_loop_chain(const LoopDims& d, const aware_loop_attack_ex* attac
             la.p_lo[j] = (int)p[0]; la.p_hi[j] = (int)p[1]; la.floor[j] = p[2];
             continue;
         }
-        if (!ex || a.kind < AWARE_LOOP_REVERBERATION || (a.kind > AWARE_LOOP_DELETE_SAMPLES && a.kind != AWARE_LOOP_BAND_FILTER))
+        if (!ex || a.kind < AWARE_LOOP_REVERBERATION ||
+            (a.kind > AWARE_LOOP_DELETE_SAMPLES && a.kind != AWARE_LOOP_BAND_FILTER && a.kind != AWARE_LOOP_EXCERPT))
             return AWARE_E_BADARG;
         // the one-split rule
         const bool pair = chain_has(la, AWARE_LOOP_TIME_STRETCH) && a.kind == AWARE_LOOP_SPEED_CHANGE && j == la.split + 1;
@@ -163,6 +166,9 @@ inline int parse_loop_chain(const LoopDims& d, const aware_loop_attack_ex* attac
                     return AWARE_E_BADARG;
                 la.mask = (int)p[0]; la.w_min = (int)p[3];
                 break;
+            case AWARE_LOOP_EXCERPT:          // param = {L_lo, L_hi, 0, 0}; a clip shorter than L_lo is left alone, not refused
+                if (!int_range(p[0], p[1], (float)kExcerptMinLen, 2147483520.f) || p[2] != 0.f || p[3] != 0.f) return AWARE_E_BADARG;
+                break;
             default:    // AWARE_LOOP_DELETE_SAMPLES, param = {k_lo, k_hi, at, 0}
                 if (!int_range(p[0], p[1], 1.f, 2147483520.f) || !(p[2] == 0.f || p[2] == 1.f)) return AWARE_E_BADARG;
                 la.at = (int)p[2];
@@ -189,9 +195,9 @@ inline int parse_loop_chain(const LoopDims& d, const aware_loop_attack_ex* attac
 inline void size_refused_chain(const aware_loop_attack_ex* attacks, int n_attacks, LoopChainState& la) {
     static const int order[] = {AWARE_LOOP_REVERBERATION, AWARE_LOOP_PHASE_VOCODER, AWARE_LOOP_TIME_STRETCH,
                                 AWARE_LOOP_SPEED_CHANGE,  AWARE_LOOP_PITCH_SHIFT,   AWARE_LOOP_DELETE_SAMPLES,
-                                AWARE_LOOP_BAND_FILTER};
+                                AWARE_LOOP_BAND_FILTER,   AWARE_LOOP_EXCERPT};
     la.split = -1; la.pair_speed = -1;
-    for (int o = 0; o < 7 && !chain_splits(la); ++o)
+    for (int o = 0; o < 8 && !chain_splits(la); ++o)
         for (int j = 0; j < n_attacks && !chain_splits(la); ++j)
             if (attacks[j].kind == order[o]) { la.split = j; la.split_kind = order[o]; }
     for (int j = 0; j < n_attacks && chain_has(la, AWARE_LOOP_TIME_STRETCH); ++j)

@@ -8,7 +8,7 @@ constexpr int kMaxLoopChains = 8;
 constexpr int kMaxLoopAttacks = 4;
 constexpr int kLoopGaussianNoise = 0, kLoopSampleSuppression = 1, kLoopReverberation = 2, kLoopSpeedChange = 3, kLoopTimeStretch = 4,
               kLoopPitchShift = 5, kLoopPhaseVocoder = 6, kLoopDeleteSamples = 7, kLoopGainEnvelope = 8,
-              kLoopBandFilter = 9;      // AWARE_LOOP_* of aware_hip.h
+              kLoopBandFilter = 9, kLoopExcerpt = 10;      // AWARE_LOOP_* of aware_hip.h
 
 // reverberation (loop_reverb_kernels.hip)
 constexpr int kReverbMaxIr = 8192;        // taps
@@ -26,6 +26,9 @@ constexpr int kEnvelopeMinPeriod = 64, kEnvelopeMaxPeriod = 1 << 20;
 
 // band filter (loop_filter_kernels.hip): taps on either side of the centre; edges in units of 1 / 65536 cycle per sample
 constexpr int kFilterHalf = 127, kFilterMaxEdge = 32767;
+
+// tiled excerpt (loop_excerpt_kernels.hip): the shortest excerpt a chain may draw, in samples
+constexpr int kExcerptMinLen = 1024;
 
 // Attack mixtures: with `choice` set, a workgroup whose clip did not draw chain `chain` at this step returns at once
 struct LoopGate {

@@ -106,6 +106,21 @@ the loop's new stage.  For clip b (length Ny) at optimiser step s with seed_b:
         order; element-wise entries may stand in front of it (noise there is coloured noise) and behind it (noise there takes
         its sigma from the filtered signal).  Host and device agree on h to 1e-6.
 
+      excerpt(seconds = v or [lo, hi]), L_lo = int(lo * sample_rate), L_hi = int(hi * sample_rate), 1024 <= L_lo <= L_hi (a
+        scalar is a fixed length): what a detector sees of an excerpt of the clip.
+        L = min(L_lo + ((r[2] * (L_hi - L_lo + 1)) >> 32), Ny), and L = Ny where the entry does not fire;
+        start = (r[1] * (Ny - L + 1)) >> 32, so 0 <= start <= Ny - L (excerpt_draw);
+        z[i] = x[start + (i mod L)] (excerpt_tile): the excerpt repeated periodically until it fills the clip, which keeps its
+        length.  The detector's convolutions are 1 x 1, so time couples only through the norms' statistics and the read-out's
+        mean, and the periodic repetition has both as the excerpt alone has them, up to the frames at the seams; zeros
+        outside the excerpt would enter those statistics.  Every value is a copy, so host and device agree bit for bit.  The
+        backward pass is the exact adjoint in gather form (excerpt_tile_adjoint): gx[i] = sum_m gz[(i - start) + m L] for
+        start <= i < start + L over m = 0, 1, .. while the index is below Ny, 0 outside; in float32 the sum runs over
+        ascending m, the first term copied and every further one a single rounded addition, so host and device agree bit for
+        bit there too.  L = Ny is the identity in both directions: a clip shorter than L_lo is left alone, not refused.  At
+        most one per chain, and not in a chain with any other splitting kind, in either order; element-wise entries may stand
+        in front of it and behind it, and a noise entry behind it takes its sigma from the tiled signal.
+
 In the loop x = N(N(y)) of the raw synthesis y, N(v) = v / (max|v| + 1e-8), and the analysis (N, N, STFT, band magnitudes)
 runs on the chain's output."""
 from __future__ import annotations
@@ -124,11 +139,13 @@ KINDS = {"gaussian_noise": 0, "sample_suppression": 1, "reverberation": 2, "spee
 ELEMENTWISE_EX = {"gain_envelope": 8}
 # The splitting kinds added after that table was recorded, for the same reason in a table of their own.
 SPLITTING_EX = {"band_filter": 9}
+# ... and the splitting kinds added after the tests of kind 9 pinned SPLITTING_EX: a third table.
+SPLITTING_EX2 = {"excerpt": 10}
 _KEYS = {"gaussian_noise": {"kind", "snr_db", "prob"}, "sample_suppression": {"kind", "seconds", "prob"},
          "reverberation": {"kind", "rt60", "drr_db", "prob"}, "speed_change": {"kind", "cents", "prob"}, "time_stretch": {"kind", "rate", "prob"},
          "pitch_shift": {"kind", "cents", "prob"}, "phase_vocoder": {"kind", "rate", "cents", "prob"},
          "delete_samples": {"kind", "seconds", "at", "prob"}, "gain_envelope": {"kind", "period", "floor", "prob"},
-         "band_filter": {"kind", "response", "freq", "min_width", "prob"}}
+         "band_filter": {"kind", "response", "freq", "min_width", "prob"}, "excerpt": {"kind", "seconds", "prob"}}
 _KEY1 = 0x5EED
 MAX_IR = 8192                   # taps of the longest impulse response
 _IR_WORD = 8                    # third Philox counter word of the impulse responses (0: noise, 1..4: entry draws)
@@ -141,21 +158,22 @@ _ENV_WORD = 16                  # third Philox counter word of entry j's breakpo
 RESPONSES = {"lowpass": 1, "highpass": 2, "bandpass": 4, "bandstop": 8}      # the bits of a band filter's mask: param[0]
 FILTER_HALF = 127               # taps on either side of a band filter's centre
 MAX_EDGE = 32767                # the highest edge, in units of 1 / 65536 cycle per sample: one below Nyquist
+MIN_EXCERPT = 1024              # samples of the shortest excerpt a chain may draw
 
 
 def kind_id(kind) -> int | None:
     """The C ABI's number of a chain kind (AWARE_LOOP_* of include/aware_hip.h), None for an unknown one."""
     if not isinstance(kind, str):
         return None
-    return KINDS.get(kind, ELEMENTWISE_EX.get(kind, SPLITTING_EX.get(kind)))
+    return KINDS.get(kind, ELEMENTWISE_EX.get(kind, SPLITTING_EX.get(kind, SPLITTING_EX2.get(kind))))
 
 
 # The one-split rule (csrc/loop_chain.hpp holds the device's statement of it): these kinds need launches of their own between
 # two stages of element-wise entries, and a chain holds at most one entry of them.  The one exception is the pair: a speed
 # change directly behind a time stretch.
 SPLITTING = ("reverberation", "speed_change", "time_stretch", "pitch_shift", "phase_vocoder", "delete_samples")
-_NAME = dict({k: k.replace("_", " ") for k in SPLITTING + tuple(SPLITTING_EX)}, delete_samples="sample deletion")
-_SPLIT_ORDER = SPLITTING + tuple(SPLITTING_EX)
+_SPLIT_ORDER = SPLITTING + tuple(SPLITTING_EX) + tuple(SPLITTING_EX2)
+_NAME = dict({k: k.replace("_", " ") for k in _SPLIT_ORDER}, delete_samples="sample deletion", excerpt="tiled excerpt")
 
 
 def _one_split(j: int, kind: str, out: list[dict]) -> None:
@@ -283,7 +301,9 @@ def parse_chain(chain, sample_rate: int = 16000) -> list[dict]:
     64 <= P_lo <= P_hi <= 2^20 samples at `sample_rate`, floor not 0 <= floor < 1 (finite); for {"kind": "band_filter",
     "response": "lowpass" | ["lowpass", "bandstop"], "freq": 1000.0 | [600.0, 3800.0], "min_width": 400.0}: a missing freq or
     response, an unknown response, a non-finite value, lo > hi, an edge outside (0, Nyquist - min_width) at `sample_rate`,
-    min_width <= 0 (the period and these edges are the rules that read `sample_rate`)."""
+    min_width <= 0; for {"kind": "excerpt", "seconds": 0.5 | [0.1875, 0.625]}: a missing seconds, seconds not 0 < lo <= hi
+    (finite), more or fewer than two values in a list, fewer than 1024 samples at `sample_rate` (the period, these edges and
+    the excerpt's least length are the rules that read `sample_rate`)."""
     if not chain:
         return []
     if isinstance(chain, dict) or not isinstance(chain, (list, tuple)):
@@ -294,7 +314,7 @@ def parse_chain(chain, sample_rate: int = 16000) -> list[dict]:
     for j, a in enumerate(chain):
         if not isinstance(a, dict) or kind_id(a.get("kind")) is None:
             raise ValueError(f"loop_attacks[{j}]: unknown kind {a.get('kind') if isinstance(a, dict) else a!r}; "
-                             f"available: {list(KINDS) + list(ELEMENTWISE_EX) + list(SPLITTING_EX)}")
+                             f"available: {list(KINDS) + list(ELEMENTWISE_EX) + list(SPLITTING_EX) + list(SPLITTING_EX2)}")
         kind = a["kind"]
         extra = set(a) - _KEYS[kind]
         if extra:
@@ -359,6 +379,26 @@ def parse_chain(chain, sample_rate: int = 16000) -> list[dict]:
             e["at"] = at
         elif kind == "band_filter":
             e.update(_parse_filter(j, a, sample_rate))
+        elif kind == "excerpt":
+            if "seconds" not in a:
+                raise ValueError(f"loop_attacks[{j}] (excerpt): seconds is required")
+            sec = a["seconds"]
+            try:
+                if isinstance(sec, (list, tuple)):
+                    if len(sec) != 2:
+                        raise TypeError
+                    lo, hi = float(sec[0]), float(sec[1])
+                else:
+                    lo = hi = float(sec)
+            except (TypeError, ValueError):
+                raise ValueError(f"loop_attacks[{j}] (excerpt): seconds = {sec!r} is neither a number nor [lo, hi]") from None
+            if not (math.isfinite(lo) and math.isfinite(hi) and 0.0 < lo <= hi):
+                raise ValueError(f"loop_attacks[{j}] (excerpt): seconds needs 0 < lo <= hi, both finite; got {sec!r}")
+            e["seconds"] = [lo, hi]
+            try:
+                excerpt_range(e, sample_rate)
+            except ValueError as err:
+                raise ValueError(f"loop_attacks[{j}] (excerpt): {err}") from None
         elif kind == "gain_envelope":
             if "period" not in a:
                 raise ValueError(f"loop_attacks[{j}] (gain_envelope): period is required")
@@ -434,6 +474,16 @@ def envelope_range(entry: dict, sample_rate: int) -> tuple[int, int]:
         raise ValueError(f"period = {entry['period']} s is {p_lo}..{p_hi} samples at {sample_rate} Hz, outside "
                          f"{MIN_PERIOD}..{MAX_PERIOD}")
     return p_lo, p_hi
+
+
+def excerpt_range(entry: dict, sample_rate: int) -> tuple[int, int]:
+    """(L_lo, L_hi) = (int(lo * sample_rate), int(hi * sample_rate)) of a parsed excerpt entry: samples of the excerpt.
+    ValueError unless 1024 <= L_lo <= L_hi <= 2147483520."""
+    l_lo, l_hi = int(entry["seconds"][0] * sample_rate), int(entry["seconds"][1] * sample_rate)
+    if not MIN_EXCERPT <= l_lo <= l_hi <= 2147483520:
+        raise ValueError(f"seconds = {entry['seconds']} is {l_lo}..{l_hi} samples at {sample_rate} Hz; at least {MIN_EXCERPT} "
+                         f"are required")
+    return l_lo, l_hi
 
 
 def filter_edge(f: float, sample_rate: int) -> int:
@@ -749,6 +799,53 @@ def delete_samples_adjoint(gz: torch.Tensor, start: int, k: int) -> torch.Tensor
     return torch.cat([gz[..., :start], torch.zeros(gz.shape[:-1] + (k,), dtype=gz.dtype, device=gz.device), gz[..., start:n - k]], dim=-1)
 
 
+def excerpt_draw(entry: dict, r, ny: int, sample_rate: int, on: bool = True) -> tuple[int, int]:
+    """(start, L) of a parsed excerpt entry from its draw r = entry_draw(seed, step, j) on a clip of ny samples:
+    L = min(L_lo + ((r[2] * (L_hi - L_lo + 1)) >> 32), ny), L = ny where the entry does not fire (on false);
+    start = (r[1] * (ny - L + 1)) >> 32."""
+    l_lo, l_hi = excerpt_range(entry, sample_rate)
+    L = min(l_lo + ((int(r[2]) * (l_hi - l_lo + 1)) >> 32), int(ny)) if on else int(ny)
+    return (int(r[1]) * (int(ny) - L + 1)) >> 32, L
+
+
+def _excerpt_check(n: int, start: int, L: int) -> None:
+    if not (0 <= start and 1 <= L and start + L <= n):
+        raise ValueError(f"excerpt_tile: the excerpt [{start}, {start + L}) does not lie inside the {n} samples")
+
+
+def excerpt_tile(x, start, L):
+    """z[i] = x[start + (i mod L)], 0 <= i < n: the excerpt [start, start + L) of x repeated periodically until it fills the
+    clip.  x a tensor [..., n], or a list of 1-D tensors (ragged) with a start and a length each.  Differentiable in x (a
+    gather: every value is a copy); L = n returns x."""
+    if not torch.is_tensor(x):
+        return [excerpt_tile(xb, s, l) for xb, s, l in zip(x, start, L)]
+    n, start, L = x.shape[-1], int(start), int(L)
+    _excerpt_check(n, start, L)
+    if L == n:
+        return x
+    return x[..., torch.as_tensor(start + np.arange(n, dtype=np.int64) % L, device=x.device)]
+
+
+def excerpt_tile_adjoint(gz, start, L):
+    """The adjoint of excerpt_tile in gather form: gx[i] = sum_m gz[(i - start) + m L] for start <= i < start + L over
+    m = 0, 1, .. while the index is below n, 0 outside.  The sum runs over ascending m in gz's dtype, the first term copied and
+    every further one a single rounded addition: in float32 it is the device's, bit for bit.  gz a tensor [..., n] or a
+    list of 1-D tensors (ragged) with a start and a length each; L = n returns gz."""
+    if not torch.is_tensor(gz):
+        return [excerpt_tile_adjoint(gb, s, l) for gb, s, l in zip(gz, start, L)]
+    n, start, L = gz.shape[-1], int(start), int(L)
+    _excerpt_check(n, start, L)
+    if L == n:
+        return gz
+    acc = gz[..., :L].clone()
+    for lo in range(L, n, L):                                         # ascending m: period m covers gz[m L : min((m + 1) L, n)]
+        w = min(L, n - lo)
+        acc[..., :w] = acc[..., :w] + gz[..., lo:lo + w]
+    gx = torch.zeros_like(gz)
+    gx[..., start:start + L] = acc
+    return gx
+
+
 def envelope_draw(entry: dict, r, sample_rate: int) -> tuple[int, int]:
     """(P, ph) of a parsed gain_envelope entry from its draw r = entry_draw(seed, step, j): P = P_lo + ((r[2] * (P_hi - P_lo + 1))
     >> 32) samples between breakpoints, ph = (r[1] * P) >> 32 < P the phase of the first."""
@@ -906,6 +1003,9 @@ def apply_chain(x, chain, seeds, step: int, sample_rate: int = 16000):
             elif a["kind"] == "band_filter":
                 if on:
                     xb = band_filter(xb, *filter_draw(a, r, sample_rate))
+            elif a["kind"] == "excerpt":
+                if on:
+                    xb = excerpt_tile(xb, *excerpt_draw(a, r, ny, sample_rate))
             elif a["kind"] == "gain_envelope":
                 P, ph = envelope_draw(a, r, sample_rate)
                 if on:
@@ -923,7 +1023,8 @@ def device_entries_ex(chain: list[dict], sample_rate: int):
     """(kind, prob, [param0..3]) of the C ABI's aware_loop_attack_ex: kinds 0 and 1 as device_entries in param[0]; a
     reverberation has param = [n_lo, n_hi, drr_db, 0], a speed change, a time stretch or a pitch shift [m_lo, m_hi, 0, 0], a
     phase vocoder [mq_lo, mq_hi, m_lo, m_hi] with [0, -1] (lo > hi) for an absent mode, a sample deletion
-    [k_lo, k_hi, at (0 start / 1 anywhere), 0], a gain envelope [P_lo, P_hi, floor, 0], a band filter [mask, c_lo, c_hi, w_min]."""
+    [k_lo, k_hi, at (0 start / 1 anywhere), 0], a gain envelope [P_lo, P_hi, floor, 0], a band filter [mask, c_lo, c_hi, w_min],
+    a tiled excerpt [L_lo, L_hi, 0, 0]."""
     out = []
     for a in chain:
         if a["kind"] == "gain_envelope":
@@ -932,6 +1033,9 @@ def device_entries_ex(chain: list[dict], sample_rate: int):
         elif a["kind"] == "band_filter":
             c_lo, c_hi, w_min = filter_range(a, sample_rate)
             out.append((kind_id(a["kind"]), a["prob"], [float(filter_mask(a)), float(c_lo), float(c_hi), float(w_min)]))
+        elif a["kind"] == "excerpt":
+            l_lo, l_hi = excerpt_range(a, sample_rate)
+            out.append((kind_id(a["kind"]), a["prob"], [float(l_lo), float(l_hi), 0.0, 0.0]))
         elif a["kind"] == "reverberation":
             n_lo, n_hi = reverb_taps(a, sample_rate)
             out.append((kind_id(a["kind"]), a["prob"], [float(n_lo), float(n_hi), a["drr_db"], 0.0]))

@@ -1108,6 +1108,26 @@ def delete_samples(x: Ragged, start, k, adjoint: bool = False) -> Ragged:
     return out
 
 
+def excerpt_tile(x: Ragged, start, length, adjoint: bool = False) -> Ragged:
+    """Per clip embedding.loop_attacks.excerpt_tile (aware_excerpt_tile): the length[b] samples of clip b from start[b] on,
+    repeated periodically until they fill the clip, so every clip keeps its length (B integers each, or one for all; a length
+    equal to the clip's is the identity).  With adjoint, x holds the gradient with respect to that output and the result is the
+    gradient with respect to the input: the sum over the periods in float32, zeros outside the excerpt."""
+    lib = load_library()
+    st = [int(start)] * x.B if np.isscalar(start) else [int(v) for v in start]
+    ls = [int(length)] * x.B if np.isscalar(length) else [int(v) for v in length]
+    if len(st) != x.B or len(ls) != x.B or any(s < 0 or c < 1 or s + c > n for s, c, n in zip(st, ls, x.lengths)):
+        raise ValueError(f"excerpt_tile: {x.B} excerpts [start, start + length) inside the clips are required; got start = {st}, "
+                         f"length = {ls} for lengths {list(x.lengths)}")
+    xin = x.data if x.data.dtype == torch.float32 else x.data.float()
+    out = Ragged(torch.empty(sum(x.lengths), dtype=torch.float32, device=xin.device), x.lengths)
+    sd = torch.tensor(st, dtype=torch.int32, device=xin.device)
+    ld = torch.tensor(ls, dtype=torch.int32, device=xin.device)
+    check(lib.aware_excerpt_tile(_ptr(xin), _ptr(x.d_off), _ptr(x.d_len), x.B, x.max_len, _ptr(sd), _ptr(ld), _ptr(out.data),
+                                 int(bool(adjoint)), _stream()), "aware_excerpt_tile")
+    return out
+
+
 def gain_envelope(x: Ragged, seeds: Sequence[int], step: int, entry: int, period_samples, floor: float = 0.0,
                   return_gains: bool = False, out: Ragged | None = None):
     """Per clip embedding.loop_attacks.gain_envelope with the draw of chain entry `entry` at optimiser step `step`, always on

@@ -790,6 +790,33 @@ int aware_gain_envelope(const float* in, const int* off, const int* len, int B, 
 int aware_band_filter(const float* in, const int* off, const int* len, int B, int max_len, const int* response, const int* c1,
                       const int* c2, float* out, float* taps, void* stream);
 
+/* ---- tiled excerpt inside the loop and alone (EXTENSION, parity unpinned: the reference's Cropout is a post-hoc attack) ------
+ * The _ex pair and the mixture's setter also accept (the older entry point keeps refusing every kind above 1)
+ *   AWARE_LOOP_EXCERPT, param = { L_lo, L_hi, 0, 0 }: what a detector sees of an excerpt of the clip.  The excerpt
+ *     [start, start + L) is repeated periodically until it fills the clip, so the clip keeps its length and every norm and mean
+ *     along time sees the excerpt's own statistics.  With r the entry's draw as above,
+ *     L = min(L_lo + ((r[2] * (L_hi - L_lo + 1)) >> 32), Ny), and L = Ny where the entry does not fire;
+ *     start = (r[1] * (Ny - L + 1)) >> 32, so 0 <= start <= Ny - L;
+ *     forward  z[i] = x[start + (i mod L)], 0 <= i < Ny: every value is a copy;
+ *     adjoint  gx[i] = sum_m gz[(i - start) + m * L] for start <= i < start + L, over m = 0, 1, .. while the index is below Ny,
+ *     in f32 with m ascending (the first term is copied, every further one is one rounded addition), and +0.0 outside.
+ *   An excerpt as long as the clip is the identity in both directions, bit for bit; a clip shorter than L_lo is therefore left
+ *   alone and not refused.
+ * AWARE_E_BADARG of the _ex setter, besides those above: a value that is not an integer, L_lo < 1024, L_lo > L_hi,
+ * L_hi > 2147483520, param[2] or param[3] not 0, a second excerpt, an excerpt together with any of kinds 2 to 7 and 9 (in
+ * either order).  aware_embed_loop_attack_workspace_bytes_ex for a chain with the kind is that of the same chain with a sample
+ * deletion in its place: no private workspace.  aware_embed_buffer gains no index.  Added without a version step: callers
+ * detect the addition by symbol. */
+#define AWARE_LOOP_EXCERPT 10            /* param = L_lo, L_hi, 0, 0 (samples) */
+/* The same operator alone, on a ragged batch: clip b is len[b] floats at float offset off[b] of `in` and of `out` (dev int
+ * [B], any offsets, every length <= max_len <= 2^30); start and length dev int [B], read as length = min(max(length, 1), len)
+ * and start = min(max(start, 0), len - length); length = len is the identity.  adjoint 0: `in` holds x and `out` receives z.
+ * adjoint 1: `in` holds gz and `out` receives gx.  in and out are distinct buffers.  One launch on `stream`.  AWARE_E_BADARG:
+ * a null argument, in == out, B < 1 or > 65535, max_len < 1 or > 2^30, adjoint outside 0..1 (checked before anything is
+ * launched). */
+int aware_excerpt_tile(const float* in, const int* off, const int* len, int B, int max_len, const int* start, const int* length,
+                       float* out, int adjoint, void* stream);
+
 /* ---- attack mixtures (EXTENSION, parity unpinned: the reference has no attacks in its loop) -------------------------------
  * A handle holds one chain, and the kinds that split a chain refuse each other.  A mixture is a list of 1..8 chains, each a
  * valid chain of aware_embed_set_loop_attacks_ex with a weight; at optimiser step s clip b draws

@@ -18,6 +18,7 @@ name them too.
 `--filter` adds the chains of FILTER_VARIANTS, which hold the band filter, in the same way.  `--fir` does
 none of the above: it times the FIR kernel alone (aware_band_filter) on the batch against aware_convolve fed the same 255 taps,
 from device events, 20 calls each after a warm-up (under rocprofv3 --kernel-trace --stats the two show per kernel).
+`--excerpt` adds the chains of EXCERPT_VARIANTS, which hold the tiled excerpt, in the same way.
 `--only-loop` runs a few steps of every variant and nothing else, for a per-kernel trace
 (rocprofv3 --kernel-trace --stats -- python tools/loop_attack_bench.py --only-loop)."""
 import argparse
@@ -71,6 +72,12 @@ FILTER_VARIANTS = {
                      {"kind": "gaussian_noise", "snr_db": 10.0}],
     "noise_filter": [{"kind": "gaussian_noise", "snr_db": 10.0},
                      {"kind": "band_filter", "response": ["lowpass", "highpass", "bandpass", "bandstop"], "freq": [600.0, 3800.0], "prob": 0.75}],
+}
+
+# The chains with a tiled excerpt (chain kind 10), in a table of their own for the same reason.
+EXCERPT_VARIANTS = {
+    "excerpt": [{"kind": "excerpt", "seconds": [0.1875, 0.625], "prob": 0.75}],
+    "excerpt_noise": [{"kind": "excerpt", "seconds": [0.1875, 0.625], "prob": 0.75}, {"kind": "gaussian_noise", "snr_db": 10.0}],
 }
 
 
@@ -221,6 +228,7 @@ def main():
     ap.add_argument("--envelope", action="store_true")
     ap.add_argument("--filter", action="store_true")
     ap.add_argument("--fir", action="store_true")
+    ap.add_argument("--excerpt", action="store_true")
     args = ap.parse_args()
     B, n = args.clips, int(args.seconds * 16000)
     emb, det = load()
@@ -249,6 +257,7 @@ def main():
     variants = {k: v for k, v in VARIANTS.items() if not args.variants or k in chosen}
     variants.update({k: v for k, v in ENVELOPE_VARIANTS.items() if k in chosen or (args.envelope and not args.variants)})
     variants.update({k: v for k, v in FILTER_VARIANTS.items() if k in chosen or (args.filter and not args.variants)})
+    variants.update({k: v for k, v in EXCERPT_VARIANTS.items() if k in chosen or (args.excerpt and not args.variants)})
     mixtures = {}
     for m in [v for v in args.mixture.split(",") if v]:
         mixtures[f"mixture:{m}"] = MIXTURES[m]
