@@ -70,6 +70,12 @@ __global__ __launch_bounds__(256) void band_mag_bwd_kernel(BandLaunch L, const c
     gspec[k] = mk(X.x * s, X.y * s);
 }
 
+// dL/dcoef of one bin: the gradient spectrum projected on the bin's unit phasor.  One fused form for both instantiations of
+// the kernel below: left to the compiler, the stepping one contracted the sum into an FMA and the reporting one did not, so
+// aware_embed_gradient reported a gradient whose last bit was not the one the step had consumed (the two terms cancel where
+// the gradient is small, and NAdam's first steps turn 1e-11 there into 1e-3 of a coefficient).
+__device__ __forceinline__ float coef_grad(cf G, cf u) { return __builtin_fmaf(G.x, u.x, G.y * u.y); }
+
 template <bool STEP>
 __global__ __launch_bounds__(256) void band_coef_grad_kernel(BandLaunch L, const cf* __restrict__ gspec,
                                                              const cf* __restrict__ unit, float* __restrict__ grad_out,
@@ -79,7 +85,7 @@ __global__ __launch_bounds__(256) void band_coef_grad_kernel(BandLaunch L, const
     const size_t idx = (size_t)row * L.bstride + f;
     const cf G = gspec[(size_t)row * L.sstride + L.band_lo + f];
     const cf u = unit[idx];
-    const float g = G.x * u.x + G.y * u.y;
+    const float g = coef_grad(G, u);
     if (grad_out) grad_out[idx] = g;
     if (STEP) {
         // the clip of this row (the same for the whole wave): frame_off[clip] <= row < frame_off[clip + 1]
