@@ -1515,25 +1515,27 @@ static int det_forward_backward(const aware_detector* d, const aware_batch* b, c
                                     d->nscale[l], co, b->B, b->max_frames / 2, st);
             LAUNCHCHK(); PROF(K_INLRELU);
         }
-        if (G.wgrad && G.wgrad[l]) {
-            // dA = dL/dZ_l [NP][co] (zero in padding rows), X = input of the block [NP][ci]:  dW = dZ^T X as an NT GEMM over
-            // the transposed operands (K = NP contiguous); db = column sums of dZ (zero up to rounding: the InstanceNorm
-            // behind the convolution removes any per-channel constant)
-            // (the last block's padding channels: only the caller's 2 * nbits rows of dW and db are written)
+        // dA = dL/dZ_l [NP][co] (zero in padding rows), X = input of the block [NP][ci]:  dW = dZ^T X as an NT GEMM over
+        // the transposed operands (K = NP contiguous); db = column sums of dZ (zero up to rounding: the InstanceNorm
+        // behind the convolution removes any per-channel constant)
+        // (the last block's padding channels: only the caller's 2 * nbits rows of dW and db are written)
+        // Each of the two is written where the caller asks for it, whether or not it asks for the other.
+        const bool want_w = G.wgrad && G.wgrad[l], want_b = G.bgrad && G.bgrad[l];
+        const int rows = l == nl - 1 ? 2 * d->nbits : co;
+        if (want_w) {
             const float* X = l > 0 ? db.act[l - 1] : db.x0;
-            const int rows = l == nl - 1 ? 2 * d->nbits : co;
             launch_transpose(dA, G.tr1, b->NP, co, st);
             launch_transpose(X, G.tr2, b->NP, ci, st);
             launch_gemm_nt(G.tr1, b->NP, G.tr2, b->NP, nullptr, G.wgrad[l], ci, rows, ci, b->NP, st);
-            if (G.bgrad && G.bgrad[l]) {
-                if (rows == co) launch_colsum(dA, G.bgrad[l], b->NP, co, st);
-                else {
-                    launch_colsum(dA, G.tr2, b->NP, co, st);      // tr2 is free once the GEMM above has read it
-                    HIPCHK(hipMemcpyAsync(G.bgrad[l], G.tr2, (size_t)rows * sizeof(float), hipMemcpyDeviceToDevice, st));
-                }
-            }
-            LAUNCHCHK(); PROF(K_MISC);
         }
+        if (want_b) {
+            if (rows == co) launch_colsum(dA, G.bgrad[l], b->NP, co, st);
+            else {
+                launch_colsum(dA, G.tr2, b->NP, co, st);      // tr2 is free once the GEMM above has read it
+                HIPCHK(hipMemcpyAsync(G.bgrad[l], G.tr2, (size_t)rows * sizeof(float), hipMemcpyDeviceToDevice, st));
+            }
+        }
+        if (want_w || want_b) { LAUNCHCHK(); PROF(K_MISC); }
         // the data gradient of block l; every kind but Plain also runs the backward of block l-1's norm and activation
         float* g_out = l > 0 ? gmax(l - 1, p.g_max[l - 1]) : nullptr;
         switch (p.bwd[l]) {

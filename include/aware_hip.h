@@ -285,8 +285,9 @@ int aware_detector_backward(const aware_detector* det, const aware_batch* batch,
  * gradients"; the reference freezes the detector, multibit_embedder.py:76-77, and trains nothing: parity unpinned, specified
  * by torch autograd on the oracle's Detector).  aware_detector_weight_gradients = aware_detector_backward plus
  * dL/dW_l [Cout][Cin] and dL/db_l [Cout] of every conv block (grad_weights / grad_biases: host arrays of n_layers device
- * pointers, entries may be NULL); the caller all-reduces them over its ranks, applies its optimiser and writes the new
- * parameters back with aware_detector_update (host arrays as for aware_detector_create, same shapes, synchronous).
+ * pointers, entries may be NULL, each on its own); the caller all-reduces them over its ranks, applies its optimiser and
+ * writes the new parameters back with aware_detector_update (host arrays as for aware_detector_create, same shapes,
+ * synchronous).
  * The gradient entry points serve detectors of a narrow-layout band only: AWARE_E_UNSUPPORTED for the wide layout. */
 size_t aware_detector_train_workspace_bytes(const aware_batch* batch, const aware_detector* det);
 int aware_detector_weight_gradients(const aware_detector* det, const aware_batch* batch, const float* mag,

@@ -256,14 +256,20 @@ def test_detector_weight_gradients_extension(env):
     od.ws, od.bs = ws, bs
     oe = O.Embedder()
     total = 0.0
+    mags = []
     for i, c in enumerate(clips):
         a = torch.from_numpy(c)[None]
         m = torch.abs(O.stft(a / torch.amax(torch.abs(a) + 1e-8))).clone()
         m[:, oe.nonband] = 0.0
+        mags.append(m.requires_grad_(True))
         out = od.forward(m)
         np.testing.assert_allclose(vals[i].cpu().numpy(), out[0].detach().numpy(), atol=5e-5)
         total = total + (out[0] * cot[i]).sum()
     total.backward()
+    gref = torch.cat([m.grad[0, oe.band].T for m in mags])              # [total frames, 225], the layout of grad_mag
+    rel = float((gmag.cpu()[:, :225] - gref).norm() / gref.norm())
+    print(f"dL/dmag rel L2 vs autograd {rel:.2e}")
+    assert rel < 1e-4, rel
     for l in range(4):
         ref = ws[l].grad
         rel = float((gw[l].cpu() - ref).norm() / ref.norm())
