@@ -324,6 +324,56 @@ class ExcerptTile(Attack):
         return rt.excerpt_tile(x, *_excerpt_bounds("ExcerptTile", self.seconds, self.start_seconds, x, sr))
 
 
+@register
+class TimeWarp(Attack):
+    """EXTENSION (not in the reference, parity unpinned): the clip played at a speed that wanders inside it, piecewise linear
+    between random breakpoints, each rate uniform in 1 +- depth.  Clip i draws the warp of seed + i that
+    embedding.loop_attacks.apply_chain specifies at step 0, entry 0: what a {"kind": "time_warp", "depth": depth, "period": period}
+    entry of the embed loop applies at its first step.  The clip keeps its length."""
+
+    def __init__(self, depth=0.04, period=(0.032, 0.512), seed=0):
+        from .embedding.loop_attacks import parse_chain
+        self.entry = parse_chain([{"kind": "time_warp", "depth": depth, "period": period}])[0]      # its refusals are this one's
+        self.seed = int(seed)
+        self.name = f"time_warp_{depth}"
+
+    def apply_batch(self, x, sr, seeds=None):
+        from .embedding import loop_attacks as la
+        if seeds is None:
+            seeds = [self.seed + i for i in range(x.B)]
+        D = la.warp_range(self.entry, sr)[2]
+        es, phs, rates = [], [], []
+        for sd, n in zip(seeds, x.lengths):
+            e, ph = la.warp_draw(self.entry, la.entry_draw(int(sd) & 0xFFFFFFFF, 0, 0), sr)
+            es.append(e)
+            phs.append(ph)
+            rates.append(la.warp_rates(sd, 0, 0, la.warp_breakpoints(n, e), D))
+        return rt.time_warp(x, es, phs, rates)
+
+
+@register
+class Flutter(Attack):
+    """EXTENSION (not in the reference, parity unpinned): wow (a few tenths of a hertz to a few hertz) and flutter (above):
+    the clip played at the speed 1 + depth sin(2 pi hz t + phase), through the embed loop's time_warp operator at the finest
+    breakpoints it has, 256 samples apart: m_k = round(65536 depth sin(2 pi hz 256 k / sr + phase)).  The clip keeps its
+    length."""
+
+    def __init__(self, depth, hz, phase=0.0):
+        self.depth, self.hz, self.phase = float(depth), float(hz), float(phase)
+        if not (np.isfinite(self.depth) and np.isfinite(self.hz) and np.isfinite(self.phase) and 0.0 < self.depth < 0.1 and self.hz > 0.0):
+            raise ValueError(f"Flutter: 0 < depth < 0.1 and hz > 0, all finite, are required; got {depth!r}, {hz!r}, {phase!r}")
+        self.name = f"flutter_{depth}_{hz}"
+
+    def rates(self, n, sr):
+        """The rate offsets m_k of a clip of n samples at sr Hz."""
+        from .embedding.loop_attacks import warp_breakpoints
+        k = np.arange(warp_breakpoints(n, 8), dtype=np.float64)
+        return np.round(65536.0 * self.depth * np.sin(2.0 * np.pi * self.hz * 256.0 * k / sr + self.phase)).astype(np.int64)
+
+    def apply_batch(self, x, sr):
+        return rt.time_warp(x, 8, 0, [self.rates(n, sr) for n in x.lengths])
+
+
 def _scale(x: "rt.Ragged", gains) -> "rt.Ragged":
     """x times one gain curve per clip (torch tensors on x's device), float32."""
     data = x.data.float()

@@ -2039,6 +2039,10 @@ static int init_chain_buffers(LoopChainState& la, const aware_batch* b, const fl
         HIPCHK(hipMemsetAsync(la.h, 0, (size_t)b->B * kReverbMaxIr * sizeof(float), st));
         HIPCHK(hipMemsetAsync(la.nh, 0, (size_t)b->B * sizeof(int), st));
     }
+    if (chain_has(la, AWARE_LOOP_TIME_WARP)) {           // read only where the forward pass of the same step wrote them
+        HIPCHK(hipMemsetAsync(la.warpR, 0, (size_t)b->B * la.kmax * sizeof(int), st));
+        HIPCHK(hipMemsetAsync(la.warpA, 0, (size_t)b->B * la.kmax * sizeof(long long), st));
+    }
     return AWARE_OK;
 }
 static int set_loop_attacks(aware_embed* e, const aware_loop_attack_ex* attacks, int n_attacks, bool ex,
@@ -2234,6 +2238,19 @@ extern "C" int aware_excerpt_tile(const float* in, const int* off, const int* le
     ExcerptLaunch L;
     L.in = in; L.out = out; L.B = B; L.adjoint = adjoint; L.off = off; L.len = len; L.max_len = max_len; L.start = start; L.length = length;
     launch_excerpt_tile(L, (hipStream_t)stream);
+    LAUNCHCHK();
+    return AWARE_OK;
+}
+
+// ---- the time warp alone (EXTENSION; attacks.TimeWarp, attacks.Flutter, runtime.time_warp, tests) --------------------------
+extern "C" int aware_time_warp(const float* in, const int* off, const int* len, int B, int max_len, const int* e, const int* ph,
+                               const int* rates, int stride, int* table_r, long long* table_a, float* out, int adjoint, void* stream) {
+    if (!in || !off || !len || !e || !ph || !rates || !table_r || !table_a || !out || in == out) return AWARE_E_BADARG;
+    if (B < 1 || B > 65535 || max_len < 1 || max_len > (1 << 30) || stride < 3 || adjoint < 0 || adjoint > 1) return AWARE_E_BADARG;
+    WarpLaunch L;
+    L.in = in; L.out = out; L.B = B; L.adjoint = adjoint; L.table_r = table_r; L.table_a = table_a; L.stride = stride;
+    L.off = off; L.len = len; L.max_len = max_len; L.e = e; L.ph = ph; L.rates = rates;
+    launch_time_warp(L, (hipStream_t)stream);
     LAUNCHCHK();
     return AWARE_OK;
 }
@@ -2571,6 +2588,12 @@ static ExcerptLaunch excerpt_launch(const aware_embed* e, const LoopChainState& 
     S.l_lo = la.lo; S.l_hi = la.hi;
     return S;
 }
+static WarpLaunch warp_launch(const aware_embed* e, const LoopChainState& la, const float* in, float* out, int adjoint, int step_back) {
+    WarpLaunch S = stage_launch<WarpLaunch>(e, la, in, out, adjoint, step_back);
+    S.e_lo = la.lo; S.e_hi = la.hi; S.depth = la.depth;
+    S.table_r = la.warpR; S.table_a = la.warpA; S.stride = la.kmax;
+    return S;
+}
 static FilterLaunch filter_launch(const aware_embed* e, const LoopChainState& la, const float* in, float* out, int step_back) {
     FilterLaunch S = stage_launch<FilterLaunch>(e, la, in, out, 0, step_back);
     S.mask = la.mask; S.c_lo = la.lo; S.c_hi = la.hi; S.w_min = la.w_min;
@@ -2691,6 +2714,8 @@ static void split_forward(const aware_embed* e, const LoopChainState& la, hipStr
         case AWARE_LOOP_PHASE_VOCODER: pv_stage_forward(e, la, e->gy, st); break;
         case AWARE_LOOP_BAND_FILTER: launch_band_filter(filter_launch(e, la, la.u, la.z, 0), st); break;
         case AWARE_LOOP_EXCERPT: launch_excerpt_tile(excerpt_launch(e, la, la.u, la.z, 0, 0), st); break;
+        // the table of the drawn rates first, then the resampling; the backward pass reads that table
+        case AWARE_LOOP_TIME_WARP: launch_time_warp(warp_launch(e, la, la.u, la.z, 0, 0), st); break;
         default: launch_delete_samples(delete_launch(e, la, la.u, la.z, 0, 0), st); break;      // AWARE_LOOP_DELETE_SAMPLES
     }
 }
@@ -2711,6 +2736,7 @@ static void split_backward(const aware_embed* e, const LoopChainState& la, int s
         case AWARE_LOOP_PHASE_VOCODER: pv_stage_backward(e, la, step_back, st); break;
         case AWARE_LOOP_BAND_FILTER: launch_band_filter(filter_launch(e, la, la.u, e->gy, step_back), st); break;      // its own adjoint
         case AWARE_LOOP_EXCERPT: launch_excerpt_tile(excerpt_launch(e, la, la.u, e->gy, 1, step_back), st); break;
+        case AWARE_LOOP_TIME_WARP: launch_time_warp(warp_launch(e, la, la.u, e->gy, 1, step_back), st); break;
         default: launch_delete_samples(delete_launch(e, la, la.u, e->gy, 1, step_back), st); break;
     }
 }

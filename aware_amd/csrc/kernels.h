@@ -622,6 +622,28 @@ struct ExcerptLaunch {
 };
 void launch_excerpt_tile(const ExcerptLaunch& L, hipStream_t st);
 
+// ---- loop_warp_kernels.hip: time warp (EXTENSION): the clip resampled through the speed change's Catmull-Rom taps at a rate
+// that is piecewise linear in time between breakpoints 2^e samples apart, every position exact in 64-bit integers, inside the
+// embed loop (chain kind 11) and stand-alone (aware_time_warp), and its adjoint in gather form.  The forward launch fills the
+// table (R_k, A(k)) first; the adjoint launch reads it ------------------------------------------------------------------------
+struct WarpLaunch {
+    const float* in = nullptr; float* out = nullptr;      // never the same buffer
+    int B = 0, adjoint = 0;               // 0: out = z from in = x; 1: out = gx from in = gz
+    int* table_r = nullptr;               // [B][stride] R_k = 65536 + m_k
+    long long* table_a = nullptr;         // [B][stride] A(k)
+    int stride = 0;                       // >= warp_breakpoints(Ny_b, e) of every clip; an index from `stride` on reads the last entry
+    // the embed loop (draw.frame_off set): e, ph and the m_k drawn in the kernels
+    LoopDraw draw;
+    int e_lo = 0, e_hi = 0, depth = 0;    // kWarpMinExp <= e_lo <= e_hi <= kWarpMaxExp, 1 <= depth <= kWarpMaxDepth
+    // or a ragged batch (draw.frame_off null): both sides are len[b] floats at off[b]; e[b], ph[b] and the m_k given, clamped
+    const int* off = nullptr; const int* len = nullptr;
+    int max_len = 0;                      // >= every length
+    const int* e = nullptr;               // [B]
+    const int* ph = nullptr;              // [B]
+    const int* rates = nullptr;           // [B][stride] m_k
+};
+void launch_time_warp(const WarpLaunch& L, hipStream_t st);
+
 // ---- sync_kernels.hip: offset search in detection (EXTENSION): values [B][n][L] -> the row of the largest mean |v - centre|
 // per clip (the smallest j on a tie), its index and that mean; one wave per clip ------------------------------------------
 void launch_sync_select(const float* values, int B, int n, int L, float centre, float* out_values, int* out_index,

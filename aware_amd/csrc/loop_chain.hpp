@@ -3,10 +3,11 @@
 // workspace.  Plain C++: no HIP header and no HIP call, so tests/host_sim/loop_chain_check.cpp runs it on the CPU.
 //
 // THE ONE-SPLIT RULE.  Kinds 0, 1 and 8 (noise, suppression, gain envelope) are element-wise and run inside the stage kernels of
-// loop_attack_kernels.hip.  Kinds 2 to 7, 9 and 10 (reverberation, speed change, time stretch, pitch shift, phase vocoder, sample
-// deletion, band filter, tiled excerpt) each need launches of their own between two such stages: they SPLIT the chain.  A chain
-// holds at most one splitting entry.  The one exception: a speed change directly behind a time stretch (j == split + 1) forms one
-// stage u -> v -> z with it.  The host twin is embedding/loop_attacks.py::parse_chain (SPLITTING, SPLITTING_EX, SPLITTING_EX2).
+// loop_attack_kernels.hip.  Kinds 2 to 7 and 9 to 11 (reverberation, speed change, time stretch, pitch shift, phase vocoder, sample
+// deletion, band filter, tiled excerpt, time warp) each need launches of their own between two such stages: they SPLIT the chain.
+// A chain holds at most one splitting entry.  The one exception: a speed change directly behind a time stretch (j == split + 1)
+// forms one stage u -> v -> z with it.  The host twin is embedding/loop_attacks.py::parse_chain (SPLITTING, SPLITTING_EX,
+// SPLITTING_EX2, SPLITTING_EX3).
 #pragma once
 #include <math.h>
 #include <stddef.h>
@@ -73,8 +74,10 @@ struct LoopChainState {
     //   sample deletion lo..hi: samples cut out; at 0: the cut starts at sample 0, 1: anywhere
     //   band filter     lo..hi: edges in 1 / 65536 cycle per sample; mask: the responses drawn from; w_min: a band's least width
     //   tiled excerpt   lo..hi: samples of the excerpt
+    //   time warp       lo..hi: exponents e of the 2^e samples between breakpoints; depth: the widest rate offset D; kmax:
+    //                   breakpoints of the longest clip at 2^lo
     int split = -1, split_kind = 0, pair_speed = -1;
-    int lo = 0, hi = 0, lo2 = 0, hi2 = -1, at = 0, kmax = 0, mask = 0, w_min = 0;
+    int lo = 0, hi = 0, lo2 = 0, hi2 = -1, at = 0, kmax = 0, mask = 0, w_min = 0, depth = 0;
     double gain = 0;
     float* u = nullptr;                       // [NS] the splitting stage's input: the entries in front of it on N(N(yraw))
     float* h = nullptr;                       // [B][8192] the impulse responses of the last forward pass
@@ -85,6 +88,8 @@ struct LoopChainState {
     float* v = nullptr;                       // [NS] between the stretch and the speed change of a pair
     cf* pvS = nullptr;                        // [NF][520] the spectrum of u; the backward pass turns it into its gradient
     cf* pvY = nullptr;                        // [NF][520] the vocoded spectrum; the backward pass holds dL/dY in it
+    int* warpR = nullptr;                     // [B][kmax] the rates R_k = 65536 + m_k of the last forward pass's time warp
+    long long* warpA = nullptr;               // [B][kmax] the positions A(k) at its breakpoints, 16.16 fixed point
     const float* hann = nullptr;              // stretch_window()
     bool locked = false;                      // an optimiser step has run: the chain stays what it is
     LoopGate gate;                            // a chain of a mixture: the clips that drew it (null: every clip)
@@ -106,7 +111,7 @@ inline int parse_loop_chain(const LoopDims& d, const aware_loop_attack_ex* attac
                   AWARE_LOOP_TIME_STRETCH == kLoopTimeStretch && AWARE_LOOP_PITCH_SHIFT == kLoopPitchShift &&
                   AWARE_LOOP_PHASE_VOCODER == kLoopPhaseVocoder && AWARE_LOOP_DELETE_SAMPLES == kLoopDeleteSamples &&
                   AWARE_LOOP_GAIN_ENVELOPE == kLoopGainEnvelope && AWARE_LOOP_BAND_FILTER == kLoopBandFilter &&
-                  AWARE_LOOP_EXCERPT == kLoopExcerpt, "");
+                  AWARE_LOOP_EXCERPT == kLoopExcerpt && AWARE_LOOP_TIME_WARP == kLoopTimeWarp, "");
     if (!attacks || n_attacks < 1 || n_attacks > kMaxLoopAttacks) return AWARE_E_BADARG;
     la.split = -1; la.pair_speed = -1; la.h = nullptr; la.v = nullptr;
     for (int j = 0; j < n_attacks; ++j) {
@@ -132,7 +137,8 @@ inline int parse_loop_chain(const LoopDims& d, const aware_loop_attack_ex* attac
             continue;
         }
         if (!ex || a.kind < AWARE_LOOP_REVERBERATION ||
-            (a.kind > AWARE_LOOP_DELETE_SAMPLES && a.kind != AWARE_LOOP_BAND_FILTER && a.kind != AWARE_LOOP_EXCERPT))
+            (a.kind > AWARE_LOOP_DELETE_SAMPLES && a.kind != AWARE_LOOP_BAND_FILTER && a.kind != AWARE_LOOP_EXCERPT &&
+             a.kind != AWARE_LOOP_TIME_WARP))
             return AWARE_E_BADARG;
         // the one-split rule
         const bool pair = chain_has(la, AWARE_LOOP_TIME_STRETCH) && a.kind == AWARE_LOOP_SPEED_CHANGE && j == la.split + 1;
@@ -169,6 +175,12 @@ inline int parse_loop_chain(const LoopDims& d, const aware_loop_attack_ex* attac
             case AWARE_LOOP_EXCERPT:          // param = {L_lo, L_hi, 0, 0}; a clip shorter than L_lo is left alone, not refused
                 if (!int_range(p[0], p[1], (float)kExcerptMinLen, 2147483520.f) || p[2] != 0.f || p[3] != 0.f) return AWARE_E_BADARG;
                 break;
+            case AWARE_LOOP_TIME_WARP:        // param = {e_lo, e_hi, D, 0}; D >= 1: a warp of depth 0 is no entry
+                if (!int_range(p[0], p[1], (float)kWarpMinExp, (float)kWarpMaxExp) || !int_range(p[2], p[2], 1.f, (float)kWarpMaxDepth) ||
+                    p[3] != 0.f)
+                    return AWARE_E_BADARG;
+                la.depth = (int)p[2];
+                break;
             default:    // AWARE_LOOP_DELETE_SAMPLES, param = {k_lo, k_hi, at, 0}
                 if (!int_range(p[0], p[1], 1.f, 2147483520.f) || !(p[2] == 0.f || p[2] == 1.f)) return AWARE_E_BADARG;
                 la.at = (int)p[2];
@@ -195,9 +207,9 @@ inline int parse_loop_chain(const LoopDims& d, const aware_loop_attack_ex* attac
 inline void size_refused_chain(const aware_loop_attack_ex* attacks, int n_attacks, LoopChainState& la) {
     static const int order[] = {AWARE_LOOP_REVERBERATION, AWARE_LOOP_PHASE_VOCODER, AWARE_LOOP_TIME_STRETCH,
                                 AWARE_LOOP_SPEED_CHANGE,  AWARE_LOOP_PITCH_SHIFT,   AWARE_LOOP_DELETE_SAMPLES,
-                                AWARE_LOOP_BAND_FILTER,   AWARE_LOOP_EXCERPT};
+                                AWARE_LOOP_BAND_FILTER,   AWARE_LOOP_EXCERPT,       AWARE_LOOP_TIME_WARP};
     la.split = -1; la.pair_speed = -1;
-    for (int o = 0; o < 8 && !chain_splits(la); ++o)
+    for (int o = 0; o < 9 && !chain_splits(la); ++o)
         for (int j = 0; j < n_attacks && !chain_splits(la); ++j)
             if (attacks[j].kind == order[o]) { la.split = j; la.split_kind = order[o]; }
     for (int j = 0; j < n_attacks && chain_has(la, AWARE_LOOP_TIME_STRETCH); ++j)
@@ -228,6 +240,12 @@ inline void carve_chain_private(Carver& c, const LoopDims& d, LoopChainState& la
     } else if (chain_has(la, AWARE_LOOP_PHASE_VOCODER)) {
         la.pvS = c.take<cf>((size_t)d.NF * 520);
         la.pvY = c.take<cf>((size_t)d.NF * 520);
+    } else if (chain_has(la, AWARE_LOOP_TIME_WARP)) {
+        // a refused chain is sized too (size_refused_chain): its exponent may be unset
+        const int e_lo = std::min(std::max(la.lo, kWarpMinExp), kWarpMaxExp);
+        la.kmax = warp_breakpoints(*std::max_element(d.out_len, d.out_len + d.B), e_lo);
+        la.warpR = c.take<int>((size_t)d.B * la.kmax);
+        la.warpA = c.take<long long>((size_t)d.B * la.kmax);
     } else if (la.pair_speed >= 0) {
         la.v = c.take<float>(d.NS);
     }

@@ -8,7 +8,7 @@ constexpr int kMaxLoopChains = 8;
 constexpr int kMaxLoopAttacks = 4;
 constexpr int kLoopGaussianNoise = 0, kLoopSampleSuppression = 1, kLoopReverberation = 2, kLoopSpeedChange = 3, kLoopTimeStretch = 4,
               kLoopPitchShift = 5, kLoopPhaseVocoder = 6, kLoopDeleteSamples = 7, kLoopGainEnvelope = 8,
-              kLoopBandFilter = 9, kLoopExcerpt = 10;      // AWARE_LOOP_* of aware_hip.h
+              kLoopBandFilter = 9, kLoopExcerpt = 10, kLoopTimeWarp = 11;      // AWARE_LOOP_* of aware_hip.h
 
 // reverberation (loop_reverb_kernels.hip)
 constexpr int kReverbMaxIr = 8192;        // taps
@@ -29,6 +29,13 @@ constexpr int kFilterHalf = 127, kFilterMaxEdge = 32767;
 
 // tiled excerpt (loop_excerpt_kernels.hip): the shortest excerpt a chain may draw, in samples
 constexpr int kExcerptMinLen = 1024;
+
+// time warp (loop_warp_kernels.hip): samples between two breakpoints of the rate are 2^e, kWarpMinExp <= e <= kWarpMaxExp; a
+// rate is (65536 + m) / 65536 with |m| <= D <= kWarpMaxDepth (a tenth either way)
+constexpr int kWarpMinExp = 8, kWarpMaxExp = 20, kWarpMaxDepth = 6553;
+// breakpoints of a clip of n samples at 2^e between them: the last position read is n - 1 + 2^e - 1, and the segment it lies
+// in needs the breakpoint behind it
+constexpr int warp_breakpoints(int n, int e) { return (int)(((long long)n + (1ll << e) - 1) >> e) + 2; }
 
 // Attack mixtures: with `choice` set, a workgroup whose clip did not draw chain `chain` at this step returns at once
 struct LoopGate {

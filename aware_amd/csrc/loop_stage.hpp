@@ -1,7 +1,7 @@
 // What the stage kernels of the embed loop's splitting entries share (loop_speed_kernels.hip, loop_stretch_kernels.hip,
-// loop_pitch_kernels.hip, loop_delete_kernels.hip, loop_filter_kernels.hip, loop_excerpt_kernels.hip): the uniform integer draw,
-// the workgroup's way into the loop's layout, the entry of the in -> out resamplers for both layouts, and the four-sample load
-// and store.  Device helpers only.  DESIGN.md sections 17 to 21, 25 and 32.
+// loop_pitch_kernels.hip, loop_delete_kernels.hip, loop_filter_kernels.hip, loop_excerpt_kernels.hip, loop_warp_kernels.hip): the
+// uniform integer draw, the workgroup's way into the loop's layout, the entry of the in -> out resamplers for both layouts, and
+// the four-sample load and store.  Device helpers only.  DESIGN.md sections 17 to 21, 25, 32 and 35.
 #pragma once
 #include "common.hpp"
 #include "kernels.h"

@@ -1,6 +1,7 @@
 // Catmull-Rom interpolation at a 16.16 fixed-point position: the weights and the order of the fused multiply-adds that the
-// speed change (loop_speed_kernels.hip), the pitch shift (loop_pitch_kernels.hip) and the speed search's views
-// (speed_search_kernels.hip) share, so that they give the same bits.  DESIGN.md sections 17, 19 and 27.
+// speed change (loop_speed_kernels.hip), the pitch shift (loop_pitch_kernels.hip), the speed search's views
+// (speed_search_kernels.hip) and the time warp (loop_warp_kernels.hip) share, so that they give the same bits.  DESIGN.md
+// sections 17, 19, 27 and 35.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -29,9 +30,8 @@ __device__ __forceinline__ float speed_mix(const SpeedWeights& w, float a, float
     return fmaf(w.w2, d, fmaf(w.w1, c, fmaf(w.w0, b, w.wm1 * a)));
 }
 
-// output i of a clip x of n samples played at R / 65536 of its speed; zero past the clip's last sample
-__device__ __forceinline__ float speed_tap(const float* __restrict__ x, int n, long long R, int i) {
-    const long long p = (long long)i * R;
+// the clip x of n samples read at the position p >= 0 in 16.16 fixed point; zero past the clip's last sample
+__device__ __forceinline__ float speed_tap_at(const float* __restrict__ x, int n, long long p) {
     if (p > ((long long)(n - 1) << 16)) return 0.f;
     const int i0 = (int)(p >> 16);                            // 0 <= i0 <= n - 1
     const SpeedWeights w = speed_weights_at(p);
@@ -40,6 +40,10 @@ __device__ __forceinline__ float speed_tap(const float* __restrict__ x, int n, l
     const float c = i0 + 1 < n ? x[i0 + 1] : 0.f;
     const float d = i0 + 2 < n ? x[i0 + 2] : 0.f;
     return speed_mix(w, a, b, c, d);
+}
+// output i of a clip x of n samples played at R / 65536 of its speed
+__device__ __forceinline__ float speed_tap(const float* __restrict__ x, int n, long long R, int i) {
+    return speed_tap_at(x, n, (long long)i * R);
 }
 
 // The transposed resampling in gather form: g[0 .. 3] = gu[j0 .. j0 + 3] from gy[0 .. n_out), u being n samples long; the at

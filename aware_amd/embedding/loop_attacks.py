@@ -121,6 +121,25 @@ the loop's new stage.  For clip b (length Ny) at optimiser step s with seed_b:
         most one per chain, and not in a chain with any other splitting kind, in either order; element-wise entries may stand
         in front of it and behind it, and a noise entry behind it takes its sigma from the tiled signal.
 
+      time_warp(depth = d, period = v or [lo, hi]), 0 < d <= 0.1, D = floor(65536 d) in float64, so 1 <= D <= 6553; period in
+        seconds, default [0.032, 0.512]: the clip resampled at a rate that is piecewise linear in time between drawn
+        breakpoints: wow and flutter, a drifting sample clock, a deliberate desynchronisation.  The breakpoints are a power of two
+        apart, so that nothing divides: e_lo = ceil(log2(int(lo * sample_rate))), e_hi = floor(log2(int(hi * sample_rate))),
+        8 <= e_lo <= e_hi <= 20; a scalar v means e_lo = e_hi = round(log2(int(v * sample_rate))) (warp_range).
+        e = e_lo + ((r[2] * (e_hi - e_lo + 1)) >> 32), P = 2^e, ph = (r[1] * P) >> 32 (warp_draw).  For breakpoint k >= 0:
+        w_k = philox4x32_10((k // 4, s, 20 + j, 0), (seed_b, 0x5EED))[k % 4] (the third counter words 20..23 are this kind's; 0,
+        1..4, 8, 12 and 16..19 are taken), m_k = -D + ((w_k * (2 D + 1)) >> 32), R_k = 65536 + m_k (warp_rates).
+        In signed 64-bit integers, >> arithmetic (warp_positions): A(0) = 0, A(k + 1) = A(k) + P R_k + (((R_{k+1} - R_k) P) >> 1);
+        for u >= 0 with k = u >> e and t = u & (P - 1), Pos(u) = A(k) + t R_k + (((R_{k+1} - R_k) t t) >> (e + 1)): continuous at
+        the breakpoints by construction, strictly increasing because every rate is at least 0.9; p_i = Pos(i + ph) - Pos(ph).
+        i0 = p_i >> 16, f = (p_i & 0xFFFF) / 65536, and z[i] is the speed change's Catmull-Rom tap at (i0, f), samples outside
+        [0, Ny) read as zero, z[i] = 0 where p_i > (Ny - 1) << 16 (time_warp): the clip keeps its length.  An entry that does not
+        fire copies the clip.  The rates are detached.  The backward pass is the exact adjoint in gather form
+        (time_warp_adjoint): gx[j] = sum over ascending i of w_{j - i0(i)}(f_i) gz[i].  At most one per chain, and not in a chain
+        with any other splitting kind, in either order; element-wise entries may stand in front of it and behind it, and a noise
+        entry behind it takes its sigma from the warped signal.  At a depth of 0.01 or less the plain watermark already reads
+        0 %: the kind buys robustness against strong warps.
+
 In the loop x = N(N(y)) of the raw synthesis y, N(v) = v / (max|v| + 1e-8), and the analysis (N, N, STFT, band magnitudes)
 runs on the chain's output."""
 from __future__ import annotations
@@ -141,11 +160,14 @@ ELEMENTWISE_EX = {"gain_envelope": 8}
 SPLITTING_EX = {"band_filter": 9}
 # ... and the splitting kinds added after the tests of kind 9 pinned SPLITTING_EX: a third table.
 SPLITTING_EX2 = {"excerpt": 10}
+# ... and those added after the tests of kind 10 pinned SPLITTING_EX2: a fourth.
+SPLITTING_EX3 = {"time_warp": 11}
 _KEYS = {"gaussian_noise": {"kind", "snr_db", "prob"}, "sample_suppression": {"kind", "seconds", "prob"},
          "reverberation": {"kind", "rt60", "drr_db", "prob"}, "speed_change": {"kind", "cents", "prob"}, "time_stretch": {"kind", "rate", "prob"},
          "pitch_shift": {"kind", "cents", "prob"}, "phase_vocoder": {"kind", "rate", "cents", "prob"},
          "delete_samples": {"kind", "seconds", "at", "prob"}, "gain_envelope": {"kind", "period", "floor", "prob"},
-         "band_filter": {"kind", "response", "freq", "min_width", "prob"}, "excerpt": {"kind", "seconds", "prob"}}
+         "band_filter": {"kind", "response", "freq", "min_width", "prob"}, "excerpt": {"kind", "seconds", "prob"},
+         "time_warp": {"kind", "depth", "period", "prob"}}
 _KEY1 = 0x5EED
 MAX_IR = 8192                   # taps of the longest impulse response
 _IR_WORD = 8                    # third Philox counter word of the impulse responses (0: noise, 1..4: entry draws)
@@ -159,20 +181,24 @@ RESPONSES = {"lowpass": 1, "highpass": 2, "bandpass": 4, "bandstop": 8}      # t
 FILTER_HALF = 127               # taps on either side of a band filter's centre
 MAX_EDGE = 32767                # the highest edge, in units of 1 / 65536 cycle per sample: one below Nyquist
 MIN_EXCERPT = 1024              # samples of the shortest excerpt a chain may draw
+MIN_WARP_EXP, MAX_WARP_EXP = 8, 20              # a time warp's breakpoints are 2^e samples apart
+MAX_WARP_DEPTH = 6553           # the widest rate offset D of a time warp: a tenth either way, floor(65536 * 0.1)
+WARP_PERIOD = [0.032, 0.512]    # a time warp's default period in seconds
+_WARP_WORD = 20                 # third Philox counter word of entry j's rates is 20 + j
 
 
 def kind_id(kind) -> int | None:
     """The C ABI's number of a chain kind (AWARE_LOOP_* of include/aware_hip.h), None for an unknown one."""
     if not isinstance(kind, str):
         return None
-    return KINDS.get(kind, ELEMENTWISE_EX.get(kind, SPLITTING_EX.get(kind, SPLITTING_EX2.get(kind))))
+    return KINDS.get(kind, ELEMENTWISE_EX.get(kind, SPLITTING_EX.get(kind, SPLITTING_EX2.get(kind, SPLITTING_EX3.get(kind)))))
 
 
 # The one-split rule (csrc/loop_chain.hpp holds the device's statement of it): these kinds need launches of their own between
 # two stages of element-wise entries, and a chain holds at most one entry of them.  The one exception is the pair: a speed
 # change directly behind a time stretch.
 SPLITTING = ("reverberation", "speed_change", "time_stretch", "pitch_shift", "phase_vocoder", "delete_samples")
-_SPLIT_ORDER = SPLITTING + tuple(SPLITTING_EX) + tuple(SPLITTING_EX2)
+_SPLIT_ORDER = SPLITTING + tuple(SPLITTING_EX) + tuple(SPLITTING_EX2) + tuple(SPLITTING_EX3)
 _NAME = dict({k: k.replace("_", " ") for k in _SPLIT_ORDER}, delete_samples="sample deletion", excerpt="tiled excerpt")
 
 
@@ -302,8 +328,11 @@ def parse_chain(chain, sample_rate: int = 16000) -> list[dict]:
     "response": "lowpass" | ["lowpass", "bandstop"], "freq": 1000.0 | [600.0, 3800.0], "min_width": 400.0}: a missing freq or
     response, an unknown response, a non-finite value, lo > hi, an edge outside (0, Nyquist - min_width) at `sample_rate`,
     min_width <= 0; for {"kind": "excerpt", "seconds": 0.5 | [0.1875, 0.625]}: a missing seconds, seconds not 0 < lo <= hi
-    (finite), more or fewer than two values in a list, fewer than 1024 samples at `sample_rate` (the period, these edges and
-    the excerpt's least length are the rules that read `sample_rate`)."""
+    (finite), more or fewer than two values in a list, fewer than 1024 samples at `sample_rate`; for
+    {"kind": "time_warp", "depth": 0.04, "period": 0.128 | [0.032, 0.512]}: a missing depth, depth not 0 < depth <= 0.1 (finite)
+    or below 1 / 65536, period not 0 < lo <= hi (finite), more or fewer than two values in a list, a period that holds no power
+    of two from 2^8 to 2^20 samples at `sample_rate` (the periods, these edges and the excerpt's least length are the rules
+    that read `sample_rate`)."""
     if not chain:
         return []
     if isinstance(chain, dict) or not isinstance(chain, (list, tuple)):
@@ -314,7 +343,7 @@ def parse_chain(chain, sample_rate: int = 16000) -> list[dict]:
     for j, a in enumerate(chain):
         if not isinstance(a, dict) or kind_id(a.get("kind")) is None:
             raise ValueError(f"loop_attacks[{j}]: unknown kind {a.get('kind') if isinstance(a, dict) else a!r}; "
-                             f"available: {list(KINDS) + list(ELEMENTWISE_EX) + list(SPLITTING_EX) + list(SPLITTING_EX2)}")
+                             f"available: {list(KINDS) + list(ELEMENTWISE_EX) + list(SPLITTING_EX) + list(SPLITTING_EX2) + list(SPLITTING_EX3)}")
         kind = a["kind"]
         extra = set(a) - _KEYS[kind]
         if extra:
@@ -399,6 +428,34 @@ def parse_chain(chain, sample_rate: int = 16000) -> list[dict]:
                 excerpt_range(e, sample_rate)
             except ValueError as err:
                 raise ValueError(f"loop_attacks[{j}] (excerpt): {err}") from None
+        elif kind == "time_warp":
+            if "depth" not in a:
+                raise ValueError(f"loop_attacks[{j}] (time_warp): depth is required")
+            try:
+                depth = float(a["depth"])
+            except (TypeError, ValueError):
+                raise ValueError(f"loop_attacks[{j}] (time_warp): depth = {a['depth']!r} is not a number") from None
+            if not (math.isfinite(depth) and 0.0 < depth <= 0.1):
+                raise ValueError(f"loop_attacks[{j}] (time_warp): depth needs 0 < depth <= 0.1, finite; got {a['depth']!r}")
+            pd = a.get("period", WARP_PERIOD)
+            try:
+                if isinstance(pd, (list, tuple)):
+                    if len(pd) != 2:
+                        raise TypeError
+                    lo, hi = float(pd[0]), float(pd[1])
+                    e["period"] = [lo, hi]
+                else:
+                    lo = hi = float(pd)
+                    e["period"] = hi
+            except (TypeError, ValueError):
+                raise ValueError(f"loop_attacks[{j}] (time_warp): period = {pd!r} is neither a number nor [lo, hi]") from None
+            if not (math.isfinite(lo) and math.isfinite(hi) and 0.0 < lo <= hi):
+                raise ValueError(f"loop_attacks[{j}] (time_warp): period needs 0 < lo <= hi, both finite; got {pd!r}")
+            e["depth"] = depth
+            try:
+                warp_range(e, sample_rate)
+            except ValueError as err:
+                raise ValueError(f"loop_attacks[{j}] (time_warp): {err}") from None
         elif kind == "gain_envelope":
             if "period" not in a:
                 raise ValueError(f"loop_attacks[{j}] (gain_envelope): period is required")
@@ -484,6 +541,28 @@ def excerpt_range(entry: dict, sample_rate: int) -> tuple[int, int]:
         raise ValueError(f"seconds = {entry['seconds']} is {l_lo}..{l_hi} samples at {sample_rate} Hz; at least {MIN_EXCERPT} "
                          f"are required")
     return l_lo, l_hi
+
+
+def warp_range(entry: dict, sample_rate: int) -> tuple[int, int, int]:
+    """(e_lo, e_hi, D) of a parsed time_warp entry: the breakpoints are 2^e samples apart with e_lo <= e <= e_hi, and a rate is
+    (65536 + m) / 65536 with |m| <= D = floor(65536 depth).  A period [lo, hi] in seconds holds the powers of two from
+    e_lo = ceil(log2(int(lo * sample_rate))) to e_hi = floor(log2(int(hi * sample_rate))); a scalar v means
+    e_lo = e_hi = round(log2(int(v * sample_rate))).  ValueError unless 8 <= e_lo <= e_hi <= 20 and 1 <= D <= 6553."""
+    D = int(math.floor(65536.0 * float(entry["depth"])))
+    if not 1 <= D <= MAX_WARP_DEPTH:
+        raise ValueError(f"depth = {entry['depth']} is a rate offset of {D} / 65536; 1 to {MAX_WARP_DEPTH} are required")
+    pd = entry["period"]
+    if isinstance(pd, (list, tuple)):
+        n_lo, n_hi = int(pd[0] * sample_rate), int(pd[1] * sample_rate)
+        e_lo = (n_lo - 1).bit_length() if n_lo >= 1 else -1           # ceil(log2(n_lo)), in integers
+        e_hi = n_hi.bit_length() - 1                                   # floor(log2(n_hi)); -1 for no sample at all
+    else:
+        n_lo = n_hi = int(pd * sample_rate)
+        e_lo = e_hi = int(round(math.log2(n_lo))) if n_lo >= 1 else -1
+    if not MIN_WARP_EXP <= e_lo <= e_hi <= MAX_WARP_EXP:
+        raise ValueError(f"period = {pd} is {n_lo}..{n_hi} samples at {sample_rate} Hz, which holds no power of two from "
+                         f"2^{MIN_WARP_EXP} to 2^{MAX_WARP_EXP} (2^{e_lo}..2^{e_hi})")
+    return e_lo, e_hi, D
 
 
 def filter_edge(f: float, sample_rate: int) -> int:
@@ -846,6 +925,108 @@ def excerpt_tile_adjoint(gz, start, L):
     return gx
 
 
+def warp_draw(entry: dict, r, sample_rate: int) -> tuple[int, int]:
+    """(e, ph) of a parsed time_warp entry from its draw r = entry_draw(seed, step, j): e = e_lo + ((r[2] * (e_hi - e_lo + 1)) >> 32),
+    so P = 2^e samples between breakpoints, and ph = (r[1] * P) >> 32 < P the phase of the first."""
+    e_lo, e_hi, _ = warp_range(entry, sample_rate)
+    e = e_lo + ((int(r[2]) * (e_hi - e_lo + 1)) >> 32)
+    return e, (int(r[1]) << e) >> 32
+
+
+def warp_breakpoints(n: int, e: int) -> int:
+    """K = ((n + 2^e - 1) >> e) + 2: the breakpoints a clip of n samples reads at any phase."""
+    return ((int(n) + (1 << int(e)) - 1) >> int(e)) + 2
+
+
+def warp_rates(seed: int, step: int, j: int, n_k: int, D: int) -> np.ndarray:
+    """The first n_k rate offsets m_k (int64) of time_warp entry j at this step: w_k = philox4x32_10((k // 4, step, 20 + j, 0),
+    (seed, 0x5EED))[k % 4], m_k = -D + ((w_k * (2 D + 1)) >> 32): uniform on [-D, D].  The rate itself is R_k = 65536 + m_k."""
+    nblk = (int(n_k) + 3) // 4
+    ctr = np.zeros((nblk, 4), dtype=np.uint64)
+    ctr[:, 0] = np.arange(nblk, dtype=np.uint64)
+    ctr[:, 1] = step
+    ctr[:, 2] = _WARP_WORD + int(j)
+    w = philox4x32(ctr, (int(seed) & 0xFFFFFFFF, _KEY1)).reshape(-1)[:int(n_k)].astype(np.int64)
+    return -int(D) + ((w * np.int64(2 * int(D) + 1)) >> np.int64(32))
+
+
+def warp_table(rates, e: int) -> tuple[np.ndarray, np.ndarray]:
+    """(R, A) of the rate offsets m_k: R_k = 65536 + m_k and A(0) = 0, A(k + 1) = A(k) + P R_k + (((R_{k+1} - R_k) P) >> 1) with
+    P = 2^e, both int64 and as long as `rates`: the table the device keeps from the forward pass to the backward pass."""
+    R = 65536 + np.asarray(rates, dtype=np.int64)
+    P = np.int64(1) << np.int64(e)
+    A = np.zeros(len(R), dtype=np.int64)
+    if len(R) > 1:
+        A[1:] = np.cumsum(P * R[:-1] + (((R[1:] - R[:-1]) * P) >> np.int64(1)))
+    return R, A
+
+
+def warp_positions(n: int, e: int, ph: int, rates) -> np.ndarray:
+    """p_i = Pos(i + ph) - Pos(ph), i < n, in int64 (16.16 fixed point) from the rate offsets m_k, at least
+    warp_breakpoints(n, e) of them: Pos(u) = A(k) + t R_k + (((R_{k+1} - R_k) t t) >> (e + 1)) with k = u >> e, t = u & (2^e - 1)."""
+    n, e, ph = int(n), int(e), int(ph)
+    if not (MIN_WARP_EXP <= e <= MAX_WARP_EXP and 0 <= ph < (1 << e)):
+        raise ValueError(f"warp_positions: e = {e} outside {MIN_WARP_EXP}..{MAX_WARP_EXP} or ph = {ph} outside [0, 2^e)")
+    rates = np.asarray(rates, dtype=np.int64)
+    if len(rates) < warp_breakpoints(n, e) or np.any(np.abs(rates) > MAX_WARP_DEPTH):
+        raise ValueError(f"warp_positions: {warp_breakpoints(n, e)} rate offsets within +-{MAX_WARP_DEPTH} are required for {n} "
+                         f"samples at e = {e}; got {len(rates)}")
+    R, A = warp_table(rates, e)
+    u = np.concatenate([[0], np.arange(n, dtype=np.int64)]) + np.int64(ph)                 # Pos(ph) first
+    k, t = u >> np.int64(e), u & np.int64((1 << e) - 1)
+    pos = A[k] + t * R[k] + (((R[k + 1] - R[k]) * t * t) >> np.int64(e + 1))
+    return pos[1:] - pos[0]
+
+
+def _warp_taps(n: int, p: np.ndarray, dtype, device):
+    """The four (index, weight) pairs of the Catmull-Rom tap at the positions p on a clip of n samples: index [n_out] int64 with
+    the dead taps at 0, weight [n_out] in `dtype`, zero where the tap is dead (outside the clip, or p past its last sample)."""
+    i0 = p >> 16
+    live = p <= (np.int64(n - 1) << 16)
+    f = torch.as_tensor((p & 0xFFFF).astype(np.float64) / 65536.0).to(dtype=dtype, device=device)
+    w = (((-f + 2) * f - 1) * f / 2, ((3 * f - 5) * f * f + 2) / 2, ((-3 * f + 4) * f + 1) * f / 2, (f - 1) * f * f / 2)
+    out = []
+    for t, wt in zip((-1, 0, 1, 2), w):
+        idx = i0 + t
+        ok = live & (idx >= 0) & (idx < n)
+        out.append((torch.as_tensor(np.where(ok, idx, 0), device=device), wt * torch.as_tensor(ok).to(dtype=dtype, device=device)))
+    return out
+
+
+def time_warp(x, e, ph, rates):
+    """x played at the moving rate of warp_positions(n, e, ph, rates): z[i] = the speed change's Catmull-Rom tap at p_i, samples
+    outside the clip read as zero, zero where p_i lies past the last sample; the clip keeps its length.  x a tensor [..., n],
+    or a list of 1-D tensors (ragged) with e, ph and rates each.  Differentiable in x (the rates are numbers, not tensors);
+    float32 or float64; rate offsets that are all zero return x."""
+    if not torch.is_tensor(x):
+        return [time_warp(xb, eb, pb, rb) for xb, eb, pb, rb in zip(x, e, ph, rates)]
+    n = x.shape[-1]
+    p = warp_positions(n, e, ph, rates)
+    if not np.any(np.asarray(rates)[:warp_breakpoints(n, e)]):
+        return x
+    z = None
+    for idx, wt in _warp_taps(n, p, x.dtype, x.device):
+        term = wt * x[..., idx]
+        z = term if z is None else z + term
+    return z
+
+
+def time_warp_adjoint(gz, e, ph, rates):
+    """The adjoint of time_warp: gx[j] = sum over ascending i of w_{j - i0(i)}(f_i) gz[i], in gz's dtype (every tap's
+    contributions are added in ascending i, the taps in the order -1, 0, 1, 2).  gz a tensor [..., n] or a list of 1-D tensors
+    (ragged) with e, ph and rates each; rate offsets that are all zero return gz."""
+    if not torch.is_tensor(gz):
+        return [time_warp_adjoint(gb, eb, pb, rb) for gb, eb, pb, rb in zip(gz, e, ph, rates)]
+    n = gz.shape[-1]
+    p = warp_positions(n, e, ph, rates)
+    if not np.any(np.asarray(rates)[:warp_breakpoints(n, e)]):
+        return gz
+    gx = torch.zeros_like(gz)
+    for idx, wt in _warp_taps(n, p, gz.dtype, gz.device):
+        gx.index_add_(-1, idx, wt * gz)
+    return gx
+
+
 def envelope_draw(entry: dict, r, sample_rate: int) -> tuple[int, int]:
     """(P, ph) of a parsed gain_envelope entry from its draw r = entry_draw(seed, step, j): P = P_lo + ((r[2] * (P_hi - P_lo + 1))
     >> 32) samples between breakpoints, ph = (r[1] * P) >> 32 < P the phase of the first."""
@@ -1006,6 +1187,10 @@ def apply_chain(x, chain, seeds, step: int, sample_rate: int = 16000):
             elif a["kind"] == "excerpt":
                 if on:
                     xb = excerpt_tile(xb, *excerpt_draw(a, r, ny, sample_rate))
+            elif a["kind"] == "time_warp":
+                if on:
+                    e, ph = warp_draw(a, r, sample_rate)
+                    xb = time_warp(xb, e, ph, warp_rates(seed, step, j, warp_breakpoints(ny, e), warp_range(a, sample_rate)[2]))
             elif a["kind"] == "gain_envelope":
                 P, ph = envelope_draw(a, r, sample_rate)
                 if on:
@@ -1024,7 +1209,7 @@ def device_entries_ex(chain: list[dict], sample_rate: int):
     reverberation has param = [n_lo, n_hi, drr_db, 0], a speed change, a time stretch or a pitch shift [m_lo, m_hi, 0, 0], a
     phase vocoder [mq_lo, mq_hi, m_lo, m_hi] with [0, -1] (lo > hi) for an absent mode, a sample deletion
     [k_lo, k_hi, at (0 start / 1 anywhere), 0], a gain envelope [P_lo, P_hi, floor, 0], a band filter [mask, c_lo, c_hi, w_min],
-    a tiled excerpt [L_lo, L_hi, 0, 0]."""
+    a tiled excerpt [L_lo, L_hi, 0, 0], a time warp [e_lo, e_hi, D, 0]."""
     out = []
     for a in chain:
         if a["kind"] == "gain_envelope":
@@ -1036,6 +1221,9 @@ def device_entries_ex(chain: list[dict], sample_rate: int):
         elif a["kind"] == "excerpt":
             l_lo, l_hi = excerpt_range(a, sample_rate)
             out.append((kind_id(a["kind"]), a["prob"], [float(l_lo), float(l_hi), 0.0, 0.0]))
+        elif a["kind"] == "time_warp":
+            e_lo, e_hi, D = warp_range(a, sample_rate)
+            out.append((kind_id(a["kind"]), a["prob"], [float(e_lo), float(e_hi), float(D), 0.0]))
         elif a["kind"] == "reverberation":
             n_lo, n_hi = reverb_taps(a, sample_rate)
             out.append((kind_id(a["kind"]), a["prob"], [float(n_lo), float(n_hi), a["drr_db"], 0.0]))

@@ -1128,6 +1128,52 @@ def excerpt_tile(x: Ragged, start, length, adjoint: bool = False) -> Ragged:
     return out
 
 
+def time_warp(x: Ragged, e, ph, rates, adjoint: bool = False, return_table: bool = False, table=None):
+    """Per clip embedding.loop_attacks.time_warp (aware_time_warp): clip b played at a rate that is piecewise linear between
+    breakpoints 2^e[b] samples apart, the first one ph[b] samples before the clip's start, with the rate offsets rates[b]
+    (integers m_k within -6553..6553, at least warp_breakpoints(len[b], e[b]) of them; the rate is (65536 + m_k) / 65536).  e
+    and ph: B integers each, or one for all.  Every clip keeps its length; offsets that are all zero give the identity.  With
+    adjoint, x holds the gradient with respect to that output and the result is the gradient with respect to the input.
+    return_table: also the table the device built, (R [B, stride] int32, A [B, stride] int64); table: such a pair for the
+    adjoint to read, which otherwise reads the one loop_attacks.warp_table gives."""
+    from .embedding.loop_attacks import MAX_WARP_DEPTH, MAX_WARP_EXP, MIN_WARP_EXP, warp_breakpoints, warp_table
+    lib = load_library()
+    es = [int(e)] * x.B if np.isscalar(e) else [int(v) for v in e]
+    phs = [int(ph)] * x.B if np.isscalar(ph) else [int(v) for v in ph]
+    rs = [np.asarray(r, dtype=np.int64).reshape(-1) for r in rates]
+    if len(es) != x.B or len(phs) != x.B or len(rs) != x.B or any(
+            not (MIN_WARP_EXP <= eb <= MAX_WARP_EXP and 0 <= pb < (1 << eb) and len(rb) >= warp_breakpoints(n, eb)
+                 and np.all(np.abs(rb) <= MAX_WARP_DEPTH)) for eb, pb, rb, n in zip(es, phs, rs, x.lengths)):
+        raise ValueError(f"time_warp: per clip {MIN_WARP_EXP} <= e <= {MAX_WARP_EXP}, 0 <= ph < 2^e and ((len + 2^e - 1) >> e) + 2 rate "
+                         f"offsets within +-{MAX_WARP_DEPTH} are required; got e = {es}, ph = {phs}, {[len(r) for r in rs]} offsets for "
+                         f"lengths {list(x.lengths)}")
+    counts = [warp_breakpoints(n, eb) for n, eb in zip(x.lengths, es)]
+    stride = max(counts)
+    host = np.zeros((x.B, stride), dtype=np.int32)
+    for b, (rb, c) in enumerate(zip(rs, counts)):
+        host[b, :c] = rb[:c]
+    xin = x.data if x.data.dtype == torch.float32 else x.data.float()
+    dev = xin.device
+    out = Ragged(torch.empty(sum(x.lengths), dtype=torch.float32, device=dev), x.lengths)
+    ed = torch.tensor(es, dtype=torch.int32, device=dev)
+    pd = torch.tensor(phs, dtype=torch.int32, device=dev)
+    rd = torch.from_numpy(host).to(dev)
+    if adjoint and table is None:
+        tabs = [warp_table(host[b], es[b]) for b in range(x.B)]
+        table = (torch.from_numpy(np.stack([t[0] for t in tabs]).astype(np.int32)).to(dev), torch.from_numpy(np.stack([t[1] for t in tabs])).to(dev))
+    if adjoint:
+        tr, ta = table
+        if tr.dtype != torch.int32 or ta.dtype != torch.int64 or tuple(tr.shape) != (x.B, stride) or tuple(ta.shape) != (x.B, stride):
+            raise ValueError(f"time_warp: the table is int32 and int64 [{x.B}, {stride}]")
+        tr, ta = tr.contiguous(), ta.contiguous()
+    else:
+        tr = torch.zeros((x.B, stride), dtype=torch.int32, device=dev)
+        ta = torch.zeros((x.B, stride), dtype=torch.int64, device=dev)
+    check(lib.aware_time_warp(_ptr(xin), _ptr(x.d_off), _ptr(x.d_len), x.B, x.max_len, _ptr(ed), _ptr(pd), _ptr(rd), stride, _ptr(tr),
+                              _ptr(ta), _ptr(out.data), int(bool(adjoint)), _stream()), "aware_time_warp")
+    return (out, tr, ta) if return_table else out
+
+
 def gain_envelope(x: Ragged, seeds: Sequence[int], step: int, entry: int, period_samples, floor: float = 0.0,
                   return_gains: bool = False, out: Ragged | None = None):
     """Per clip embedding.loop_attacks.gain_envelope with the draw of chain entry `entry` at optimiser step `step`, always on

@@ -818,6 +818,38 @@ int aware_band_filter(const float* in, const int* off, const int* len, int B, in
 int aware_excerpt_tile(const float* in, const int* off, const int* len, int B, int max_len, const int* start, const int* length,
                        float* out, int adjoint, void* stream);
 
+/* ---- time warp inside the loop and alone (EXTENSION, parity unpinned: the reference has neither) -----------------------------
+ * The _ex pair and the mixture's setter also accept (the older entry point keeps refusing every kind above 1)
+ *   AWARE_LOOP_TIME_WARP, param = { e_lo, e_hi, D, 0 }: the clip resampled at a rate that is piecewise linear in time between
+ *     drawn breakpoints 2^e samples apart: wow and flutter, a drifting sample clock.  With r the entry's draw as above,
+ *     e = e_lo + ((r[2] * (e_hi - e_lo + 1)) >> 32), P = 2^e, ph = (r[1] * P) >> 32;
+ *     w_k = philox4x32_10((k / 4, s, 20 + j, 0), (seed_b, 0x5EED))[k % 4], m_k = -D + ((w_k * (2 D + 1)) >> 32),
+ *     R_k = 65536 + m_k, for breakpoint k >= 0;
+ *     in signed 64-bit integers with arithmetic shifts: A(0) = 0, A(k + 1) = A(k) + P R_k + (((R_{k+1} - R_k) P) >> 1);
+ *     Pos(u) = A(k) + t R_k + (((R_{k+1} - R_k) t t) >> (e + 1)) with k = u >> e, t = u & (P - 1);
+ *     p_i = Pos(i + ph) - Pos(ph), i0 = p_i >> 16, f = (p_i & 0xFFFF) / 65536;
+ *     forward  z[i] = the Catmull-Rom tap of the speed change at (i0, f), x zero outside [0, Ny); 0 where p_i > (Ny - 1) << 16;
+ *     adjoint  gx[j] = sum over ascending i of w_{j - i0(i)}(f_i) gz[i], gathered in one fixed order.
+ *   The clip keeps its length.  An entry that does not fire copies the clip; the rates are not differentiated.
+ * AWARE_E_BADARG of the _ex setter, besides those above: a value that is not an integer, e_lo < 8, e_lo > e_hi, e_hi > 20,
+ * D < 1, D > 6553, param[3] not 0, a second time warp, a time warp together with any of kinds 2 to 7, 9 and 10 (in either
+ * order).  aware_embed_loop_attack_workspace_bytes_ex for a chain with the kind is that of the same chain with a sample
+ * deletion in its place, and behind it, each at the next 256-byte boundary, int [B][K] and long long [B][K] with
+ * K = ((Ny_max + 2^e_lo - 1) >> e_lo) + 2: R_k and A(k) of the last forward pass, which the backward pass reads.
+ * aware_embed_buffer gains no index.  Added without a version step: callers detect the addition by symbol. */
+#define AWARE_LOOP_TIME_WARP 11          /* param = e_lo, e_hi, D, 0 */
+/* The same operator alone, on a ragged batch: clip b is len[b] floats at float offset off[b] of `in` and of `out` (dev int
+ * [B], any offsets, every length <= max_len <= 2^30); e and ph dev int [B], read as e = min(max(e, 8), 20) and
+ * ph = min(max(ph, 0), 2^e - 1); rates dev int [B][stride], m_k of clip b at rates[b * stride + k], each read as
+ * min(max(m, -6553), 6553), and an index from `stride` on reads the last one (the caller provides
+ * stride >= ((len[b] + 2^e[b] - 1) >> e[b]) + 2 for every clip); table_r dev int [B][stride] and table_a dev long long
+ * [B][stride] receive R_k and A(k) (adjoint 0) and are read (adjoint 1: the tables of the forward call).  adjoint 0: `in`
+ * holds x and `out` receives z.  adjoint 1: `in` holds gz and `out` receives gx.  in and out are distinct buffers.  At most two
+ * launches on `stream`.  AWARE_E_BADARG: a null argument, in == out, B < 1 or > 65535, max_len < 1 or > 2^30, stride < 3,
+ * adjoint outside 0..1 (checked before anything is launched). */
+int aware_time_warp(const float* in, const int* off, const int* len, int B, int max_len, const int* e, const int* ph,
+                    const int* rates, int stride, int* table_r, long long* table_a, float* out, int adjoint, void* stream);
+
 /* ---- attack mixtures (EXTENSION, parity unpinned: the reference has no attacks in its loop) -------------------------------
  * A handle holds one chain, and the kinds that split a chain refuse each other.  A mixture is a list of 1..8 chains, each a
  * valid chain of aware_embed_set_loop_attacks_ex with a weight; at optimiser step s clip b draws

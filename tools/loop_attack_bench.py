@@ -19,6 +19,7 @@ name them too.
 none of the above: it times the FIR kernel alone (aware_band_filter) on the batch against aware_convolve fed the same 255 taps,
 from device events, 20 calls each after a warm-up (under rocprofv3 --kernel-trace --stats the two show per kernel).
 `--excerpt` adds the chains of EXCERPT_VARIANTS, which hold the tiled excerpt, in the same way.
+`--warp` adds the chains of WARP_VARIANTS, which hold the time warp, in the same way.
 `--only-loop` runs a few steps of every variant and nothing else, for a per-kernel trace
 (rocprofv3 --kernel-trace --stats -- python tools/loop_attack_bench.py --only-loop)."""
 import argparse
@@ -78,6 +79,12 @@ FILTER_VARIANTS = {
 EXCERPT_VARIANTS = {
     "excerpt": [{"kind": "excerpt", "seconds": [0.1875, 0.625], "prob": 0.75}],
     "excerpt_noise": [{"kind": "excerpt", "seconds": [0.1875, 0.625], "prob": 0.75}, {"kind": "gaussian_noise", "snr_db": 10.0}],
+}
+
+# The chains with a time warp (chain kind 11), in a table of their own for the same reason.
+WARP_VARIANTS = {
+    "warp": [{"kind": "time_warp", "depth": 0.04, "period": [0.032, 0.512], "prob": 0.75}],
+    "warp_noise": [{"kind": "time_warp", "depth": 0.04, "period": [0.032, 0.512], "prob": 0.75}, {"kind": "gaussian_noise", "snr_db": 10.0}],
 }
 
 
@@ -229,6 +236,7 @@ def main():
     ap.add_argument("--filter", action="store_true")
     ap.add_argument("--fir", action="store_true")
     ap.add_argument("--excerpt", action="store_true")
+    ap.add_argument("--warp", action="store_true")
     args = ap.parse_args()
     B, n = args.clips, int(args.seconds * 16000)
     emb, det = load()
@@ -258,6 +266,7 @@ def main():
     variants.update({k: v for k, v in ENVELOPE_VARIANTS.items() if k in chosen or (args.envelope and not args.variants)})
     variants.update({k: v for k, v in FILTER_VARIANTS.items() if k in chosen or (args.filter and not args.variants)})
     variants.update({k: v for k, v in EXCERPT_VARIANTS.items() if k in chosen or (args.excerpt and not args.variants)})
+    variants.update({k: v for k, v in WARP_VARIANTS.items() if k in chosen or (args.warp and not args.variants)})
     mixtures = {}
     for m in [v for v in args.mixture.split(",") if v]:
         mixtures[f"mixture:{m}"] = MIXTURES[m]
