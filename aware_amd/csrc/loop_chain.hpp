@@ -2,12 +2,10 @@
 // chain's state, the parser with every AWARE_E_BADARG / AWARE_E_UNSUPPORTED of the setters, and the carving of the chains'
 // workspace.  Plain C++: no HIP header and no HIP call, so tests/host_sim/loop_chain_check.cpp runs it on the CPU.
 //
-// THE ONE-SPLIT RULE.  Kinds 0, 1 and 8 (noise, suppression, gain envelope) are element-wise and run inside the stage kernels of
-// loop_attack_kernels.hip.  Kinds 2 to 7 and 9 to 11 (reverberation, speed change, time stretch, pitch shift, phase vocoder, sample
-// deletion, band filter, tiled excerpt, time warp) each need launches of their own between two such stages: they SPLIT the chain.
-// A chain holds at most one splitting entry.  The one exception: a speed change directly behind a time stretch (j == split + 1)
-// forms one stage u -> v -> z with it.  The host twin is embedding/loop_attacks.py::parse_chain (SPLITTING, SPLITTING_EX,
-// SPLITTING_EX2, SPLITTING_EX3).
+// THE ONE-SPLIT RULE.  kLoopKindTable (loop_limits.hpp) says of every kind whether it is element-wise and runs inside the stage
+// kernels of loop_attack_kernels.hip, or needs launches of its own between two such stages: it SPLITS the chain.  A chain holds at
+// most one splitting entry.  The one exception: a speed change directly behind a time stretch (j == split + 1) forms one stage
+// u -> v -> z with it.  The host twin is embedding/loop_attacks.py::parse_chain (TABLE, SPLITTING).
 #pragma once
 #include <math.h>
 #include <stddef.h>
@@ -120,30 +118,25 @@ inline int parse_loop_chain(const LoopDims& d, const aware_loop_attack_ex* attac
         if (!(a.prob >= 0.f && a.prob <= 1.f)) return AWARE_E_BADARG;
         la.kind[j] = a.kind; la.prob[j] = a.prob; la.k[j] = 0; la.inv_snr[j] = 0.0;
         la.p_lo[j] = 0; la.p_hi[j] = 0; la.floor[j] = 0.f;
-        if (a.kind == AWARE_LOOP_GAUSSIAN_NOISE) {
-            if (!std::isfinite(p[0])) return AWARE_E_BADARG;
-            la.inv_snr[j] = pow(10.0, -(double)p[0] / 10.0);
-            continue;
-        }
-        if (a.kind == AWARE_LOOP_SAMPLE_SUPPRESSION) {
-            if (!(p[0] >= 1.f) || p[0] > 2147483520.f || p[0] != floorf(p[0])) return AWARE_E_BADARG;
-            la.k[j] = (int)p[0];
-            continue;
-        }
-        if (ex && a.kind == AWARE_LOOP_GAIN_ENVELOPE) {      // element-wise: param = {P_lo, P_hi, floor, 0}, never a split
-            if (!int_range(p[0], p[1], (float)kEnvelopeMinPeriod, (float)kEnvelopeMaxPeriod) || !(p[2] >= 0.f && p[2] < 1.f))
-                return AWARE_E_BADARG;
-            la.p_lo[j] = (int)p[0]; la.p_hi[j] = (int)p[1]; la.floor[j] = p[2];
-            continue;
-        }
-        if (!ex || a.kind < AWARE_LOOP_REVERBERATION ||
-            (a.kind > AWARE_LOOP_DELETE_SAMPLES && a.kind != AWARE_LOOP_BAND_FILTER && a.kind != AWARE_LOOP_EXCERPT &&
-             a.kind != AWARE_LOOP_TIME_WARP))
-            return AWARE_E_BADARG;
+        if (a.kind < 0 || a.kind >= kLoopKinds || (kLoopKindTable[a.kind].ex_only && !ex)) return AWARE_E_BADARG;
+        const bool splits = kLoopKindTable[a.kind].splits;
         // the one-split rule
         const bool pair = chain_has(la, AWARE_LOOP_TIME_STRETCH) && a.kind == AWARE_LOOP_SPEED_CHANGE && j == la.split + 1;
-        if (chain_splits(la) && !pair) return AWARE_E_BADARG;
-        switch (a.kind) {            // the parameters' validation; p[0] and p[1] are integers in range behind it
+        if (splits && chain_splits(la) && !pair) return AWARE_E_BADARG;
+        switch (a.kind) {            // the parameters' validation; a splitting kind's range is integers in range behind it
+            case AWARE_LOOP_GAUSSIAN_NOISE:
+                if (!std::isfinite(p[0])) return AWARE_E_BADARG;
+                la.inv_snr[j] = pow(10.0, -(double)p[0] / 10.0);
+                break;
+            case AWARE_LOOP_SAMPLE_SUPPRESSION:
+                if (!(p[0] >= 1.f) || p[0] > 2147483520.f || p[0] != floorf(p[0])) return AWARE_E_BADARG;
+                la.k[j] = (int)p[0];
+                break;
+            case AWARE_LOOP_GAIN_ENVELOPE:      // param = {P_lo, P_hi, floor, 0}
+                if (!int_range(p[0], p[1], (float)kEnvelopeMinPeriod, (float)kEnvelopeMaxPeriod) || !(p[2] >= 0.f && p[2] < 1.f))
+                    return AWARE_E_BADARG;
+                la.p_lo[j] = (int)p[0]; la.p_hi[j] = (int)p[1]; la.floor[j] = p[2];
+                break;
             case AWARE_LOOP_REVERBERATION:
                 if (!int_range(p[0], p[1], 2.f, (float)kReverbMaxIr) || !std::isfinite(p[2])) return AWARE_E_BADARG;
                 la.gain = pow(10.0, (double)p[2] / 20.0);
@@ -186,6 +179,7 @@ inline int parse_loop_chain(const LoopDims& d, const aware_loop_attack_ex* attac
                 la.at = (int)p[2];
                 break;
         }
+        if (!splits) continue;
         if (pair) { la.pair_speed = j; la.lo2 = (int)p[0]; la.hi2 = (int)p[1]; }
         else {
             const int first = a.kind == AWARE_LOOP_BAND_FILTER ? 1 : 0;      // the band filter's range follows its mask
@@ -202,16 +196,17 @@ inline int parse_loop_chain(const LoopDims& d, const aware_loop_attack_ex* attac
 }
 
 // A chain that the parser refuses with AWARE_E_BADARG still has the byte count aware_embed_loop_attack_workspace_bytes_ex
-// has always answered for it: that of the first of these kinds its entries hold, with a pair's v if a time stretch decides
-// and a speed change stands anywhere
+// has always answered for it: that of the first of its splitting entries of the lowest refused_rank (kLoopKindTable), with a
+// pair's v if a time stretch decides and a speed change stands anywhere
 inline void size_refused_chain(const aware_loop_attack_ex* attacks, int n_attacks, LoopChainState& la) {
-    static const int order[] = {AWARE_LOOP_REVERBERATION, AWARE_LOOP_PHASE_VOCODER, AWARE_LOOP_TIME_STRETCH,
-                                AWARE_LOOP_SPEED_CHANGE,  AWARE_LOOP_PITCH_SHIFT,   AWARE_LOOP_DELETE_SAMPLES,
-                                AWARE_LOOP_BAND_FILTER,   AWARE_LOOP_EXCERPT,       AWARE_LOOP_TIME_WARP};
     la.split = -1; la.pair_speed = -1;
-    for (int o = 0; o < 9 && !chain_splits(la); ++o)
-        for (int j = 0; j < n_attacks && !chain_splits(la); ++j)
-            if (attacks[j].kind == order[o]) { la.split = j; la.split_kind = order[o]; }
+    for (int j = 0; j < n_attacks; ++j) {
+        const int kind = attacks[j].kind;
+        if (kind < 0 || kind >= kLoopKinds || !kLoopKindTable[kind].splits) continue;
+        if (!chain_splits(la) || kLoopKindTable[kind].refused_rank < kLoopKindTable[la.split_kind].refused_rank) {
+            la.split = j; la.split_kind = kind;
+        }
+    }
     for (int j = 0; j < n_attacks && chain_has(la, AWARE_LOOP_TIME_STRETCH); ++j)
         if (attacks[j].kind == AWARE_LOOP_SPEED_CHANGE) la.pair_speed = j;
 }

@@ -10,6 +10,28 @@ constexpr int kLoopGaussianNoise = 0, kLoopSampleSuppression = 1, kLoopReverbera
               kLoopPitchShift = 5, kLoopPhaseVocoder = 6, kLoopDeleteSamples = 7, kLoopGainEnvelope = 8,
               kLoopBandFilter = 9, kLoopExcerpt = 10, kLoopTimeWarp = 11;      // AWARE_LOOP_* of aware_hip.h
 
+// THE KINDS, one row each, indexed by the kind's number.  splits: the kind needs launches of its own between two stages of
+// element-wise entries (the one-split rule, loop_chain.hpp); the others run inside the stage kernels.  ex_only: only the _ex
+// entry points and the mixture's setter accept it.  refused_rank: a refused chain is sized by the splitting entry of the lowest
+// rank (size_refused_chain); -1 where the kind never decides.  The host twin is embedding/loop_attacks.py::TABLE.
+struct LoopKindRow { bool splits, ex_only; int refused_rank; };
+constexpr LoopKindRow kLoopKindTable[] = {
+    {false, false, -1},      //  0 gaussian noise
+    {false, false, -1},      //  1 sample suppression
+    {true, true, 0},         //  2 reverberation
+    {true, true, 3},         //  3 speed change
+    {true, true, 2},         //  4 time stretch
+    {true, true, 4},         //  5 pitch shift
+    {true, true, 1},         //  6 phase vocoder
+    {true, true, 5},         //  7 sample deletion
+    {false, true, -1},       //  8 gain envelope
+    {true, true, 6},         //  9 band filter
+    {true, true, 7},         // 10 tiled excerpt
+    {true, true, 8},         // 11 time warp
+};
+constexpr int kLoopKinds = sizeof(kLoopKindTable) / sizeof(kLoopKindTable[0]);
+static_assert(kLoopKinds == kLoopTimeWarp + 1, "one row per kind");
+
 // reverberation (loop_reverb_kernels.hip)
 constexpr int kReverbMaxIr = 8192;        // taps
 constexpr int kReverbBlock = 2048;        // output samples per block; the transform has 4096 points

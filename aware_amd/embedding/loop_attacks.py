@@ -145,29 +145,12 @@ runs on the chain's output."""
 from __future__ import annotations
 
 import math
+from collections import namedtuple
 
 import numpy as np
 import torch
 
 MAX_ATTACKS = 4
-KINDS = {"gaussian_noise": 0, "sample_suppression": 1, "reverberation": 2, "speed_change": 3, "time_stretch": 4,
-         "pitch_shift": 5, "phase_vocoder": 6, "delete_samples": 7}      # AWARE_LOOP_* of include/aware_hip.h
-# The element-wise kinds added after the message table of tests/golden/loop_chain_messages.json was recorded.  That table and the
-# tests that iterate over KINDS pin KINDS to the eight kinds above, in their order, so later kinds have a table of their own;
-# kind_id() is the one lookup over both, for the parser and the device-entry builders.
-ELEMENTWISE_EX = {"gain_envelope": 8}
-# The splitting kinds added after that table was recorded, for the same reason in a table of their own.
-SPLITTING_EX = {"band_filter": 9}
-# ... and the splitting kinds added after the tests of kind 9 pinned SPLITTING_EX: a third table.
-SPLITTING_EX2 = {"excerpt": 10}
-# ... and those added after the tests of kind 10 pinned SPLITTING_EX2: a fourth.
-SPLITTING_EX3 = {"time_warp": 11}
-_KEYS = {"gaussian_noise": {"kind", "snr_db", "prob"}, "sample_suppression": {"kind", "seconds", "prob"},
-         "reverberation": {"kind", "rt60", "drr_db", "prob"}, "speed_change": {"kind", "cents", "prob"}, "time_stretch": {"kind", "rate", "prob"},
-         "pitch_shift": {"kind", "cents", "prob"}, "phase_vocoder": {"kind", "rate", "cents", "prob"},
-         "delete_samples": {"kind", "seconds", "at", "prob"}, "gain_envelope": {"kind", "period", "floor", "prob"},
-         "band_filter": {"kind", "response", "freq", "min_width", "prob"}, "excerpt": {"kind", "seconds", "prob"},
-         "time_warp": {"kind", "depth", "period", "prob"}}
 _KEY1 = 0x5EED
 MAX_IR = 8192                   # taps of the longest impulse response
 _IR_WORD = 8                    # third Philox counter word of the impulse responses (0: noise, 1..4: entry draws)
@@ -189,93 +172,79 @@ _WARP_WORD = 20                 # third Philox counter word of entry j's rates i
 
 def kind_id(kind) -> int | None:
     """The C ABI's number of a chain kind (AWARE_LOOP_* of include/aware_hip.h), None for an unknown one."""
-    if not isinstance(kind, str):
-        return None
-    return KINDS.get(kind, ELEMENTWISE_EX.get(kind, SPLITTING_EX.get(kind, SPLITTING_EX2.get(kind, SPLITTING_EX3.get(kind)))))
+    return KINDS.get(kind) if isinstance(kind, str) else None
 
 
-# The one-split rule (csrc/loop_chain.hpp holds the device's statement of it): these kinds need launches of their own between
-# two stages of element-wise entries, and a chain holds at most one entry of them.  The one exception is the pair: a speed
-# change directly behind a time stretch.
-SPLITTING = ("reverberation", "speed_change", "time_stretch", "pitch_shift", "phase_vocoder", "delete_samples")
-_SPLIT_ORDER = SPLITTING + tuple(SPLITTING_EX) + tuple(SPLITTING_EX2) + tuple(SPLITTING_EX3)
-_NAME = dict({k: k.replace("_", " ") for k in _SPLIT_ORDER}, delete_samples="sample deletion", excerpt="tiled excerpt")
-
-
+# The one-split rule (csrc/loop_chain.hpp holds the device's statement of it): the kinds of SPLITTING need launches of their own
+# between two stages of element-wise entries, and a chain holds at most one entry of them.  The one exception is the pair: a
+# speed change directly behind a time stretch.
 def _one_split(j: int, kind: str, out: list[dict]) -> None:
     """ValueError if entry j of a splitting kind may not join the entries `out` in front of it.  The message names the kind
     itself if the chain holds it already, otherwise the last splitting entry, the later of the two in SPLITTING first."""
-    held = [o["kind"] for o in out if o["kind"] in _SPLIT_ORDER]
+    held = [o["kind"] for o in out if o["kind"] in SPLITTING]
     if not held or (kind == "speed_change" and held == ["time_stretch"] and out[-1]["kind"] == "time_stretch"):
         return
     head = f"loop_attacks[{j}] ({kind}): "
     if kind in held:
-        raise ValueError(head + f"at most one {_NAME[kind]} per chain")
+        raise ValueError(head + f"at most one {_KIND[kind].display} per chain")
     if {kind, held[-1]} == {"speed_change", "time_stretch"}:
         raise ValueError(head + ("beside a time stretch, the speed change follows it directly" if kind == "speed_change"
                                  else "a speed change in the same chain follows the stretch directly"))
-    first, second = sorted((kind, held[-1]), key=_SPLIT_ORDER.index, reverse=True)
-    raise ValueError(head + f"a chain holds a {_NAME[first]} or a {_NAME[second]}, not both")
+    first, second = sorted((kind, held[-1]), key=SPLITTING.index, reverse=True)
+    raise ValueError(head + f"a chain holds a {_KIND[first].display} or a {_KIND[second].display}, not both")
 
 
-def _parse_rate(j: int, kind: str, a: dict) -> list[float]:
+def _number_or_pair(head: str, a: dict, key: str, scalar: str = "same", ok=lambda lo, hi: 0.0 < lo <= hi, needs: str = "0 < lo <= hi",
+                    catch=(TypeError, ValueError), default=None):
+    """The parameter a[key], a number or [lo, hi], as it goes into the parsed entry: [lo, hi] in floats.  `scalar` says what a
+    number v means: "same" [v, v]; "keep" the same range, and the number itself is returned; "neg" [-v, v], for v > 0 only;
+    "inv" [1 / v, v], for v > 1 only.  ValueError with `head` in front: a missing key without a `default`, what is neither a
+    number nor a list of two (the exceptions of `catch`; a ValueError of float() passes where it is not among them), a scalar
+    outside its rule, values that are not finite or not ok(lo, hi), which the message states as `needs`."""
+    if key not in a and default is None:
+        raise ValueError(head + f"{key} is required")
+    v = a.get(key, default)
+    pair = isinstance(v, (list, tuple))
+    try:
+        if pair and len(v) != 2:
+            raise TypeError
+        lo, hi = (float(v[0]), float(v[1])) if pair else (float(v), float(v))
+    except catch:
+        raise ValueError(head + f"{key} = {v!r} is neither a number nor [lo, hi]") from None
+    if not pair and scalar in ("neg", "inv"):
+        least = 0.0 if scalar == "neg" else 1.0
+        if not hi > least:
+            raise ValueError(head + f"a scalar {key} has to be > {least:g}; got {v!r}")
+        lo = -hi if scalar == "neg" else 1.0 / hi
+    if not (math.isfinite(lo) and math.isfinite(hi) and ok(lo, hi)):
+        raise ValueError(head + f"{key} needs {needs}, both finite; got {v!r}")
+    return hi if scalar == "keep" and not pair else [lo, hi]
+
+
+def _parse_rate(head: str, a: dict) -> list[float]:
     """[lo, hi] of a time_stretch or phase_vocoder entry's rate: a scalar r > 1 means [1 / r, r]; 0.75 <= lo <= hi <= 4/3, and
     at least one offset inside."""
-    if "rate" not in a:
-        raise ValueError(f"loop_attacks[{j}] ({kind}): rate is required")
-    rr = a["rate"]
-    try:
-        if isinstance(rr, (list, tuple)):
-            if len(rr) != 2:
-                raise TypeError
-            lo, hi = float(rr[0]), float(rr[1])
-        else:
-            hi = float(rr)
-            if not hi > 1.0:
-                raise ValueError(f"loop_attacks[{j}] ({kind}): a scalar rate has to be > 1; got {rr!r}")
-            lo = 1.0 / hi
-    except TypeError:
-        raise ValueError(f"loop_attacks[{j}] ({kind}): rate = {rr!r} is neither a number nor [lo, hi]") from None
-    if not (math.isfinite(lo) and math.isfinite(hi) and MIN_RATE <= lo <= hi <= MAX_RATE):
-        raise ValueError(f"loop_attacks[{j}] ({kind}): rate needs {MIN_RATE:g} <= lo <= hi <= 4/3, both finite; "
-                         f"got {rr!r}")
-    m_lo, m_hi = stretch_range({"rate": [lo, hi]})
+    rate = _number_or_pair(head, a, "rate", "inv", lambda lo, hi: MIN_RATE <= lo <= hi <= MAX_RATE, f"{MIN_RATE:g} <= lo <= hi <= 4/3",
+                           catch=(TypeError,))
+    m_lo, m_hi = stretch_range({"rate": rate})
     if m_lo > m_hi:
-        raise ValueError(f"loop_attacks[{j}] ({kind}): rate = {rr!r} holds no offset "
-                         f"(m_lo = {m_lo} > m_hi = {m_hi}, in units of 1 / 65536)")
-    return [lo, hi]
+        raise ValueError(head + f"rate = {a['rate']!r} holds no offset (m_lo = {m_lo} > m_hi = {m_hi}, in units of 1 / 65536)")
+    return rate
 
 
-def _parse_cents(j: int, kind: str, a: dict) -> list[float]:
-    """[lo, hi] of a speed_change or pitch_shift entry's cents: a scalar c > 0 means [-c, c]; -400 <= lo <= hi <= 400, and at
-    least one speed offset inside."""
-    if "cents" not in a:
-        raise ValueError(f"loop_attacks[{j}] ({kind}): cents is required")
-    ct = a["cents"]
-    try:
-        if isinstance(ct, (list, tuple)):
-            if len(ct) != 2:
-                raise TypeError
-            lo, hi = float(ct[0]), float(ct[1])
-        else:
-            lo, hi = -float(ct), float(ct)
-            if not hi > 0.0:
-                raise ValueError(f"loop_attacks[{j}] ({kind}): a scalar cents has to be > 0; got {ct!r}")
-    except TypeError:
-        raise ValueError(f"loop_attacks[{j}] ({kind}): cents = {ct!r} is neither a number nor [lo, hi]") from None
-    if not (math.isfinite(lo) and math.isfinite(hi) and -MAX_CENTS <= lo <= hi <= MAX_CENTS):
-        raise ValueError(f"loop_attacks[{j}] ({kind}): cents needs -{MAX_CENTS:g} <= lo <= hi <= {MAX_CENTS:g}, "
-                         f"both finite; got {ct!r}")
-    m_lo, m_hi = speed_range({"cents": [lo, hi]})
+def _parse_cents(head: str, a: dict) -> list[float]:
+    """[lo, hi] of a speed_change, pitch_shift or phase_vocoder entry's cents: a scalar c > 0 means [-c, c];
+    -400 <= lo <= hi <= 400, and at least one speed offset inside."""
+    cents = _number_or_pair(head, a, "cents", "neg", lambda lo, hi: -MAX_CENTS <= lo <= hi <= MAX_CENTS,
+                            f"-{MAX_CENTS:g} <= lo <= hi <= {MAX_CENTS:g}", catch=(TypeError,))
+    m_lo, m_hi = speed_range({"cents": cents})
     if m_lo > m_hi:
-        raise ValueError(f"loop_attacks[{j}] ({kind}): cents = {ct!r} holds no speed offset "
-                         f"(m_lo = {m_lo} > m_hi = {m_hi}, in units of 1 / 65536)")
-    return [lo, hi]
+        raise ValueError(head + f"cents = {a['cents']!r} holds no speed offset (m_lo = {m_lo} > m_hi = {m_hi}, in units of 1 / 65536)")
+    return cents
 
 
-def _parse_filter(j: int, a: dict, sample_rate: int) -> dict:
+def _parse_filter(head: str, a: dict, sample_rate: int) -> dict:
     """response (a list of names, in the order of their bits), freq [lo, hi] and min_width of a band_filter entry."""
-    head = f"loop_attacks[{j}] (band_filter): "
     if "response" not in a:
         raise ValueError(head + "response is required")
     if "freq" not in a:
@@ -310,6 +279,73 @@ def _parse_filter(j: int, a: dict, sample_rate: int) -> dict:
     return e
 
 
+def _number(head: str, a: dict, key: str, ok, needs: str, default=None) -> float:
+    """The parameter a[key] as a float.  ValueError with `head` in front: a missing key without a `default`, what is no number,
+    a value that is not finite or not ok(v), which the message states as `needs`."""
+    if key not in a and default is None:
+        raise ValueError(head + f"{key} is required")
+    try:
+        v = float(a.get(key, default))
+    except (TypeError, ValueError):
+        raise ValueError(head + f"{key} = {a.get(key)!r} is not a number") from None
+    if not (math.isfinite(v) and ok(v)):
+        raise ValueError(head + f"{key} needs {needs}, finite; got {a.get(key)!r}")
+    return v
+
+
+def _in_range(head: str, range_of, e: dict, sample_rate: int) -> dict:
+    """The parameters e if range_of(e, sample_rate), one of the *_range helpers, takes them; its ValueError behind `head` if not."""
+    try:
+        range_of(e, sample_rate)
+    except ValueError as err:
+        raise ValueError(head + f"{err}") from None
+    return e
+
+
+# One parser per kind, parse(head, a, sample_rate): the parameters of the entry a as the parsed entry holds them, behind kind and prob.
+def _parse_noise(head, a, sample_rate):
+    if "snr_db" not in a or not math.isfinite(float(a["snr_db"])):
+        raise ValueError(head + "a finite snr_db is required")
+    return {"snr_db": float(a["snr_db"])}
+
+
+def _parse_suppression(head, a, sample_rate):
+    if "seconds" not in a or not math.isfinite(float(a["seconds"])) or float(a["seconds"]) <= 0.0:
+        raise ValueError(head + "seconds > 0 is required")
+    return {"seconds": float(a["seconds"])}
+
+
+def _parse_reverberation(head, a, sample_rate):
+    e = {"rt60": _number_or_pair(head, a, "rt60"), "drr_db": float(a.get("drr_db", -3.0))}
+    if not math.isfinite(e["drr_db"]):
+        raise ValueError(head + "a finite drr_db is required")
+    return e
+
+
+def _parse_vocoder(head, a, sample_rate):
+    if "rate" not in a and "cents" not in a:
+        raise ValueError(head + "at least one of rate and cents is required")
+    return {key: parse(head, a) for key, parse in (("rate", _parse_rate), ("cents", _parse_cents)) if key in a}
+
+
+def _parse_delete(head, a, sample_rate):
+    e = {"seconds": _number_or_pair(head, a, "seconds", "keep"), "at": a.get("at", "start")}
+    if not isinstance(e["at"], str) or e["at"] not in DELETE_AT:
+        raise ValueError(head + f"at = {e['at']!r}; available: {list(DELETE_AT)}")
+    return e
+
+
+def _parse_envelope(head, a, sample_rate):
+    e = {"period": _number_or_pair(head, a, "period"),
+         "floor": _number(head, a, "floor", lambda v: 0.0 <= v < 1.0, "0 <= floor < 1", default=0.0)}
+    return _in_range(head, envelope_range, e, sample_rate)
+
+
+def _parse_warp(head, a, sample_rate):
+    depth = _number(head, a, "depth", lambda v: 0.0 < v <= 0.1, "0 < depth <= 0.1")
+    return _in_range(head, warp_range, {"period": _number_or_pair(head, a, "period", "keep", default=WARP_PERIOD), "depth": depth}, sample_rate)
+
+
 def parse_chain(chain, sample_rate: int = 16000) -> list[dict]:
     """Validated copy of a chain such as [{"kind": "gaussian_noise", "snr_db": 10.0, "prob": 1.0},
     {"kind": "sample_suppression", "seconds": 0.3, "prob": 0.75}] (None / empty: no chain).  ValueError: unknown kind or key,
@@ -342,151 +378,17 @@ def parse_chain(chain, sample_rate: int = 16000) -> list[dict]:
     out = []
     for j, a in enumerate(chain):
         if not isinstance(a, dict) or kind_id(a.get("kind")) is None:
-            raise ValueError(f"loop_attacks[{j}]: unknown kind {a.get('kind') if isinstance(a, dict) else a!r}; "
-                             f"available: {list(KINDS) + list(ELEMENTWISE_EX) + list(SPLITTING_EX) + list(SPLITTING_EX2) + list(SPLITTING_EX3)}")
-        kind = a["kind"]
-        extra = set(a) - _KEYS[kind]
-        if extra:
-            raise ValueError(f"loop_attacks[{j}] ({kind}): unknown key(s) {sorted(extra)}")
-        prob = float(a.get("prob", 1.0))
-        if not 0.0 <= prob <= 1.0:
-            raise ValueError(f"loop_attacks[{j}] ({kind}): prob = {prob} outside [0, 1]")
-        e = {"kind": kind, "prob": prob}
-        if kind in _SPLIT_ORDER:
-            _one_split(j, kind, out)
-        if kind == "gaussian_noise":
-            if "snr_db" not in a or not math.isfinite(float(a["snr_db"])):
-                raise ValueError(f"loop_attacks[{j}] (gaussian_noise): a finite snr_db is required")
-            e["snr_db"] = float(a["snr_db"])
-        elif kind == "reverberation":
-            if "rt60" not in a:
-                raise ValueError(f"loop_attacks[{j}] (reverberation): rt60 is required")
-            rt = a["rt60"]
-            try:
-                lo, hi = (float(rt[0]), float(rt[1])) if isinstance(rt, (list, tuple)) and len(rt) == 2 else (float(rt), float(rt))
-            except (TypeError, ValueError):
-                raise ValueError(f"loop_attacks[{j}] (reverberation): rt60 = {rt!r} is neither a number nor [lo, hi]") from None
-            if not (math.isfinite(lo) and math.isfinite(hi) and 0.0 < lo <= hi):
-                raise ValueError(f"loop_attacks[{j}] (reverberation): rt60 needs 0 < lo <= hi, both finite; got {rt!r}")
-            drr = float(a.get("drr_db", -3.0))
-            if not math.isfinite(drr):
-                raise ValueError(f"loop_attacks[{j}] (reverberation): a finite drr_db is required")
-            e["rt60"], e["drr_db"] = [lo, hi], drr
-        elif kind == "speed_change":
-            e["cents"] = _parse_cents(j, kind, a)
-        elif kind == "time_stretch":
-            e["rate"] = _parse_rate(j, kind, a)
-        elif kind == "pitch_shift":
-            e["cents"] = _parse_cents(j, kind, a)
-        elif kind == "phase_vocoder":
-            if "rate" not in a and "cents" not in a:
-                raise ValueError(f"loop_attacks[{j}] (phase_vocoder): at least one of rate and cents is required")
-            if "rate" in a:
-                e["rate"] = _parse_rate(j, kind, a)
-            if "cents" in a:
-                e["cents"] = _parse_cents(j, kind, a)
-        elif kind == "delete_samples":
-            if "seconds" not in a:
-                raise ValueError(f"loop_attacks[{j}] (delete_samples): seconds is required")
-            sec = a["seconds"]
-            try:
-                if isinstance(sec, (list, tuple)):
-                    if len(sec) != 2:
-                        raise TypeError
-                    lo, hi = float(sec[0]), float(sec[1])
-                    e["seconds"] = [lo, hi]
-                else:
-                    lo = hi = float(sec)
-                    e["seconds"] = hi
-            except (TypeError, ValueError):
-                raise ValueError(f"loop_attacks[{j}] (delete_samples): seconds = {sec!r} is neither a number nor [lo, hi]") from None
-            if not (math.isfinite(lo) and math.isfinite(hi) and 0.0 < lo <= hi):
-                raise ValueError(f"loop_attacks[{j}] (delete_samples): seconds needs 0 < lo <= hi, both finite; got {sec!r}")
-            at = a.get("at", "start")
-            if not isinstance(at, str) or at not in DELETE_AT:
-                raise ValueError(f"loop_attacks[{j}] (delete_samples): at = {at!r}; available: {list(DELETE_AT)}")
-            e["at"] = at
-        elif kind == "band_filter":
-            e.update(_parse_filter(j, a, sample_rate))
-        elif kind == "excerpt":
-            if "seconds" not in a:
-                raise ValueError(f"loop_attacks[{j}] (excerpt): seconds is required")
-            sec = a["seconds"]
-            try:
-                if isinstance(sec, (list, tuple)):
-                    if len(sec) != 2:
-                        raise TypeError
-                    lo, hi = float(sec[0]), float(sec[1])
-                else:
-                    lo = hi = float(sec)
-            except (TypeError, ValueError):
-                raise ValueError(f"loop_attacks[{j}] (excerpt): seconds = {sec!r} is neither a number nor [lo, hi]") from None
-            if not (math.isfinite(lo) and math.isfinite(hi) and 0.0 < lo <= hi):
-                raise ValueError(f"loop_attacks[{j}] (excerpt): seconds needs 0 < lo <= hi, both finite; got {sec!r}")
-            e["seconds"] = [lo, hi]
-            try:
-                excerpt_range(e, sample_rate)
-            except ValueError as err:
-                raise ValueError(f"loop_attacks[{j}] (excerpt): {err}") from None
-        elif kind == "time_warp":
-            if "depth" not in a:
-                raise ValueError(f"loop_attacks[{j}] (time_warp): depth is required")
-            try:
-                depth = float(a["depth"])
-            except (TypeError, ValueError):
-                raise ValueError(f"loop_attacks[{j}] (time_warp): depth = {a['depth']!r} is not a number") from None
-            if not (math.isfinite(depth) and 0.0 < depth <= 0.1):
-                raise ValueError(f"loop_attacks[{j}] (time_warp): depth needs 0 < depth <= 0.1, finite; got {a['depth']!r}")
-            pd = a.get("period", WARP_PERIOD)
-            try:
-                if isinstance(pd, (list, tuple)):
-                    if len(pd) != 2:
-                        raise TypeError
-                    lo, hi = float(pd[0]), float(pd[1])
-                    e["period"] = [lo, hi]
-                else:
-                    lo = hi = float(pd)
-                    e["period"] = hi
-            except (TypeError, ValueError):
-                raise ValueError(f"loop_attacks[{j}] (time_warp): period = {pd!r} is neither a number nor [lo, hi]") from None
-            if not (math.isfinite(lo) and math.isfinite(hi) and 0.0 < lo <= hi):
-                raise ValueError(f"loop_attacks[{j}] (time_warp): period needs 0 < lo <= hi, both finite; got {pd!r}")
-            e["depth"] = depth
-            try:
-                warp_range(e, sample_rate)
-            except ValueError as err:
-                raise ValueError(f"loop_attacks[{j}] (time_warp): {err}") from None
-        elif kind == "gain_envelope":
-            if "period" not in a:
-                raise ValueError(f"loop_attacks[{j}] (gain_envelope): period is required")
-            pd = a["period"]
-            try:
-                if isinstance(pd, (list, tuple)):
-                    if len(pd) != 2:
-                        raise TypeError
-                    lo, hi = float(pd[0]), float(pd[1])
-                else:
-                    lo = hi = float(pd)
-            except (TypeError, ValueError):
-                raise ValueError(f"loop_attacks[{j}] (gain_envelope): period = {pd!r} is neither a number nor [lo, hi]") from None
-            if not (math.isfinite(lo) and math.isfinite(hi) and 0.0 < lo <= hi):
-                raise ValueError(f"loop_attacks[{j}] (gain_envelope): period needs 0 < lo <= hi, both finite; got {pd!r}")
-            try:
-                fl = float(a.get("floor", 0.0))
-            except (TypeError, ValueError):
-                raise ValueError(f"loop_attacks[{j}] (gain_envelope): floor = {a.get('floor')!r} is not a number") from None
-            if not (math.isfinite(fl) and 0.0 <= fl < 1.0):
-                raise ValueError(f"loop_attacks[{j}] (gain_envelope): floor needs 0 <= floor < 1, finite; got {a.get('floor')!r}")
-            e["period"], e["floor"] = [lo, hi], fl
-            try:
-                envelope_range(e, sample_rate)
-            except ValueError as err:
-                raise ValueError(f"loop_attacks[{j}] (gain_envelope): {err}") from None
-        else:
-            if "seconds" not in a or not math.isfinite(float(a["seconds"])) or float(a["seconds"]) <= 0.0:
-                raise ValueError(f"loop_attacks[{j}] (sample_suppression): seconds > 0 is required")
-            e["seconds"] = float(a["seconds"])
-        out.append(e)
+            raise ValueError(f"loop_attacks[{j}]: unknown kind {a.get('kind') if isinstance(a, dict) else a!r}; available: {list(KINDS)}")
+        k = _KIND[a["kind"]]
+        head = f"loop_attacks[{j}] ({k.name}): "
+        if set(a) - k.keys:
+            raise ValueError(head + f"unknown key(s) {sorted(set(a) - k.keys)}")
+        e = {"kind": k.name, "prob": float(a.get("prob", 1.0))}
+        if not 0.0 <= e["prob"] <= 1.0:
+            raise ValueError(head + f"prob = {e['prob']} outside [0, 1]")
+        if k.splits:
+            _one_split(j, k.name, out)
+        out.append({**e, **k.parse(head, a, sample_rate)})
     return out
 
 
@@ -581,36 +483,39 @@ def filter_mask(entry: dict) -> int:
     return sum(RESPONSES[r] for r in entry["response"])
 
 
+def _clips_longer(head, out_lengths, k, what):
+    for b, ny in enumerate(out_lengths):
+        if k >= int(ny):
+            raise ValueError(head + f"clip {b} has {int(ny)} output samples, not more than the {k} {what}")
+
+
+def _check_suppression(head, a, sample_rate, out_lengths):
+    k = suppression_samples(a, sample_rate)
+    if k < 1:
+        raise ValueError(head + f"{a['seconds']} s is less than one sample at {sample_rate} Hz")
+    _clips_longer(head, out_lengths, k, "to be suppressed")
+
+
+def _check_reverberation(head, a, sample_rate, out_lengths):
+    n_lo, n_hi = reverb_taps(a, sample_rate)
+    if n_lo < 2 or n_hi > MAX_IR:
+        raise ValueError(head + f"rt60 = {a['rt60']} s is {n_lo}..{n_hi} taps at {sample_rate} Hz, outside 2..{MAX_IR}")
+
+
+def _check_delete(head, a, sample_rate, out_lengths):
+    k_lo, k_hi = delete_range(a, sample_rate)
+    if not 1 <= k_lo <= k_hi:
+        raise ValueError(head + f"seconds = {a['seconds']} is {k_lo}..{k_hi} samples at {sample_rate} Hz; 1 <= k_lo <= k_hi is required")
+    _clips_longer(head, out_lengths, k_hi, "that may be deleted")
+
+
 def check_lengths(chain: list[dict], sample_rate: int, out_lengths) -> None:
     """ValueError naming the first clip that a suppression would not fit into (0 < k < Ny_b is required), a reverberation
     whose impulse response would have fewer than 2 or more than MAX_IR taps at this sample rate, or a sample deletion without
     1 <= k_lo <= k_hi < Ny_b."""
     for j, a in enumerate(chain):
-        if a["kind"] == "delete_samples":
-            k_lo, k_hi = delete_range(a, sample_rate)
-            if not 1 <= k_lo <= k_hi:
-                raise ValueError(f"loop_attacks[{j}] (delete_samples): seconds = {a['seconds']} is {k_lo}..{k_hi} samples at "
-                                 f"{sample_rate} Hz; 1 <= k_lo <= k_hi is required")
-            for b, ny in enumerate(out_lengths):
-                if k_hi >= int(ny):
-                    raise ValueError(f"loop_attacks[{j}] (delete_samples): clip {b} has {int(ny)} output samples, "
-                                     f"not more than the {k_hi} that may be deleted")
-            continue
-        if a["kind"] == "reverberation":
-            n_lo, n_hi = reverb_taps(a, sample_rate)
-            if n_lo < 2 or n_hi > MAX_IR:
-                raise ValueError(f"loop_attacks[{j}] (reverberation): rt60 = {a['rt60']} s is {n_lo}..{n_hi} taps at "
-                                 f"{sample_rate} Hz, outside 2..{MAX_IR}")
-            continue
-        if a["kind"] != "sample_suppression":
-            continue
-        k = suppression_samples(a, sample_rate)
-        if k < 1:
-            raise ValueError(f"loop_attacks[{j}] (sample_suppression): {a['seconds']} s is less than one sample at {sample_rate} Hz")
-        for b, ny in enumerate(out_lengths):
-            if k >= int(ny):
-                raise ValueError(f"loop_attacks[{j}] (sample_suppression): clip {b} has {int(ny)} output samples, "
-                                 f"not more than the {k} to be suppressed")
+        if _KIND[a["kind"]].check is not None:
+            _KIND[a["kind"]].check(f"loop_attacks[{j}] ({a['kind']}): ", a, sample_rate, out_lengths)
 
 
 def philox4x32(counter: np.ndarray, key, rounds: int = 10) -> np.ndarray:
@@ -1137,6 +1042,78 @@ def _convolve(xb: torch.Tensor, h: np.ndarray) -> torch.Tensor:
     return torch.fft.irfft(torch.fft.rfft(xb, n) * torch.fft.rfft(ht, n), n)[..., :ny]
 
 
+# One operator per kind, apply(xb, a, r, seed, step, j, sample_rate): the parsed entry a at place j of its chain on the clip xb
+# with the entry's draw r, at a step where it fires.  The short ones stand in the table itself.
+def _apply_noise(xb, a, r, seed, step, j, sample_rate):
+    power = float(np.mean(xb.detach().double().cpu().numpy() ** 2))
+    sigma = math.sqrt(power / (10.0 ** (a["snr_db"] / 10.0)))
+    return xb + torch.as_tensor(sigma * normal_draws(xb.shape[-1], seed, step, j)).to(dtype=xb.dtype, device=xb.device)
+
+
+def _apply_suppression(xb, a, r, seed, step, j, sample_rate):
+    k = suppression_samples(a, sample_rate)
+    start = suppression_start(r[1], xb.shape[-1], k)
+    mask = torch.ones(xb.shape[-1], dtype=xb.dtype, device=xb.device)
+    mask[start:start + k] = 0
+    return xb * mask
+
+
+def _apply_warp(xb, a, r, seed, step, j, sample_rate):
+    e, ph = warp_draw(a, r, sample_rate)
+    return time_warp(xb, e, ph, warp_rates(seed, step, j, warp_breakpoints(xb.shape[-1], e), warp_range(a, sample_rate)[2]))
+
+
+# One chain kind: its name and number (AWARE_LOOP_* of include/aware_hip.h), whether it splits the chain, what the one-split
+# messages call it, the keys an entry may hold, and its four functions: parse and apply as above, device(a, sample_rate) the
+# param[0..3] of the C ABI's aware_loop_attack_ex, check(head, a, sample_rate, out_lengths) the rule of check_lengths, None
+# where no rule reads the clips' lengths.
+Kind = namedtuple("Kind", "name id splits display keys parse device check apply")
+
+
+def _kind(name, id, splits, keys, parse, device, check, apply, display=None):
+    return Kind(name, id, splits, display or name.replace("_", " "), frozenset(("kind", "prob") + keys), parse, device, check, apply)
+
+
+# THE TABLE: every kind stated once, in the order of its number.  csrc/loop_limits.hpp holds the device's (kLoopKindTable);
+# INTEGRATION.md, "Adding a loop attack kind", lists what else a new kind touches.
+TABLE = (
+    _kind("gaussian_noise", 0, False, ("snr_db",), _parse_noise, lambda a, sr: [a["snr_db"], 0.0, 0.0, 0.0], None, _apply_noise),
+    _kind("sample_suppression", 1, False, ("seconds",), _parse_suppression,
+          lambda a, sr: [float(suppression_samples(a, sr)), 0.0, 0.0, 0.0], _check_suppression, _apply_suppression),
+    _kind("reverberation", 2, True, ("rt60", "drr_db"), _parse_reverberation,
+          lambda a, sr: [*map(float, reverb_taps(a, sr)), a["drr_db"], 0.0], _check_reverberation,
+          lambda xb, a, r, seed, step, j, sr: _convolve(xb, reverb_ir(seed, step, j, reverb_length(r[2], *reverb_taps(a, sr)), a["drr_db"]))),
+    _kind("speed_change", 3, True, ("cents",), lambda head, a, sr: {"cents": _parse_cents(head, a)},
+          lambda a, sr: [*map(float, speed_range(a)), 0.0, 0.0], None,
+          lambda xb, a, r, seed, step, j, sr: speed_change(xb, speed_offset(r[3], *speed_range(a)))),
+    _kind("time_stretch", 4, True, ("rate",), lambda head, a, sr: {"rate": _parse_rate(head, a)},
+          lambda a, sr: [*map(float, stretch_range(a)), 0.0, 0.0], None,
+          lambda xb, a, r, seed, step, j, sr: time_stretch(xb, stretch_offset(r[3], *stretch_range(a)))),
+    _kind("pitch_shift", 5, True, ("cents",), lambda head, a, sr: {"cents": _parse_cents(head, a)},
+          lambda a, sr: [*map(float, speed_range(a)), 0.0, 0.0], None,
+          lambda xb, a, r, seed, step, j, sr: pitch_shift(xb, speed_offset(r[3], *speed_range(a)))),
+    _kind("phase_vocoder", 6, True, ("rate", "cents"), _parse_vocoder,
+          lambda a, sr: [*map(float, stretch_range(a) if "rate" in a else (0, -1)), *map(float, speed_range(a) if "cents" in a else (0, -1))], None,
+          lambda xb, a, r, seed, step, j, sr: speed_change(pv_stretch(xb, pv_draw(a, r)[0]), pv_draw(a, r)[1])),
+    _kind("delete_samples", 7, True, ("seconds", "at"), _parse_delete,
+          lambda a, sr: [*map(float, delete_range(a, sr)), float(DELETE_AT[a["at"]]), 0.0], _check_delete,
+          lambda xb, a, r, seed, step, j, sr: delete_samples(xb, *delete_draw(a, r, xb.shape[-1], sr)), display="sample deletion"),
+    _kind("gain_envelope", 8, False, ("period", "floor"), _parse_envelope,
+          lambda a, sr: [*map(float, envelope_range(a, sr)), a["floor"], 0.0], None,
+          lambda xb, a, r, seed, step, j, sr: gain_envelope(xb, seed, step, j, *envelope_draw(a, r, sr), a["floor"])),
+    _kind("band_filter", 9, True, ("response", "freq", "min_width"), _parse_filter,
+          lambda a, sr: [float(filter_mask(a)), *map(float, filter_range(a, sr))], None,
+          lambda xb, a, r, seed, step, j, sr: band_filter(xb, *filter_draw(a, r, sr))),
+    _kind("excerpt", 10, True, ("seconds",), lambda head, a, sr: _in_range(head, excerpt_range, {"seconds": _number_or_pair(head, a, "seconds")}, sr),
+          lambda a, sr: [*map(float, excerpt_range(a, sr)), 0.0, 0.0], None,
+          lambda xb, a, r, seed, step, j, sr: excerpt_tile(xb, *excerpt_draw(a, r, xb.shape[-1], sr)), display="tiled excerpt"),
+    _kind("time_warp", 11, True, ("depth", "period"), _parse_warp, lambda a, sr: [*map(float, warp_range(a, sr)), 0.0], None, _apply_warp),
+)
+_KIND = {k.name: k for k in TABLE}
+KINDS = {k.name: k.id for k in TABLE}                          # AWARE_LOOP_* of include/aware_hip.h
+SPLITTING = tuple(k.name for k in TABLE if k.splits)           # the kinds of the one-split rule, in the order of their numbers
+
+
 def apply_chain(x, chain, seeds, step: int, sample_rate: int = 16000):
     """The chain on x: a tensor [B, Ny] or a list of B 1-D tensors (ragged), float32 or float64; differentiable (the noise
     amplitude is detached, a suppression multiplies by a 0/1 mask, a gain envelope by its detached gains).  seeds: B integers; step: the optimiser step.  Returns the
@@ -1148,58 +1125,11 @@ def apply_chain(x, chain, seeds, step: int, sample_rate: int = 16000):
     check_lengths(chain, sample_rate, [c.shape[-1] for c in clips])
     out = []
     for xb, seed in zip(clips, seeds):
-        ny = xb.shape[-1]
         seed = int(seed) & 0xFFFFFFFF
         for j, a in enumerate(chain):
             r = entry_draw(seed, step, j)
-            on = fires(r[0], a["prob"])
-            if a["kind"] == "sample_suppression":
-                k = suppression_samples(a, sample_rate)
-                start = suppression_start(r[1], ny, k)
-                if on:
-                    mask = torch.ones(ny, dtype=xb.dtype, device=xb.device)
-                    mask[start:start + k] = 0
-                    xb = xb * mask
-            elif a["kind"] == "reverberation":
-                n_h = reverb_length(r[2], *reverb_taps(a, sample_rate))
-                if on:
-                    xb = _convolve(xb, reverb_ir(seed, step, j, n_h, a["drr_db"]))
-            elif a["kind"] == "speed_change":
-                if on:
-                    xb = speed_change(xb, speed_offset(r[3], *speed_range(a)))
-            elif a["kind"] == "time_stretch":
-                if on:
-                    xb = time_stretch(xb, stretch_offset(r[3], *stretch_range(a)))
-            elif a["kind"] == "pitch_shift":
-                if on:
-                    xb = pitch_shift(xb, speed_offset(r[3], *speed_range(a)))
-            elif a["kind"] == "phase_vocoder":
-                mq, m = pv_draw(a, r)
-                if on:
-                    xb = speed_change(pv_stretch(xb, mq), m)
-            elif a["kind"] == "delete_samples":
-                start, k = delete_draw(a, r, ny, sample_rate)
-                if on:
-                    xb = delete_samples(xb, start, k)
-            elif a["kind"] == "band_filter":
-                if on:
-                    xb = band_filter(xb, *filter_draw(a, r, sample_rate))
-            elif a["kind"] == "excerpt":
-                if on:
-                    xb = excerpt_tile(xb, *excerpt_draw(a, r, ny, sample_rate))
-            elif a["kind"] == "time_warp":
-                if on:
-                    e, ph = warp_draw(a, r, sample_rate)
-                    xb = time_warp(xb, e, ph, warp_rates(seed, step, j, warp_breakpoints(ny, e), warp_range(a, sample_rate)[2]))
-            elif a["kind"] == "gain_envelope":
-                P, ph = envelope_draw(a, r, sample_rate)
-                if on:
-                    xb = gain_envelope(xb, seed, step, j, P, ph, a["floor"])
-            elif on:
-                power = float(np.mean(xb.detach().double().cpu().numpy() ** 2))
-                sigma = math.sqrt(power / (10.0 ** (a["snr_db"] / 10.0)))
-                noise = torch.as_tensor(sigma * normal_draws(ny, seed, step, j)).to(dtype=xb.dtype, device=xb.device)
-                xb = xb + noise
+            if fires(r[0], a["prob"]):
+                xb = _KIND[a["kind"]].apply(xb, a, r, seed, step, j, sample_rate)
         out.append(xb)
     return torch.stack(out) if torch.is_tensor(x) else out
 
@@ -1210,37 +1140,7 @@ def device_entries_ex(chain: list[dict], sample_rate: int):
     phase vocoder [mq_lo, mq_hi, m_lo, m_hi] with [0, -1] (lo > hi) for an absent mode, a sample deletion
     [k_lo, k_hi, at (0 start / 1 anywhere), 0], a gain envelope [P_lo, P_hi, floor, 0], a band filter [mask, c_lo, c_hi, w_min],
     a tiled excerpt [L_lo, L_hi, 0, 0], a time warp [e_lo, e_hi, D, 0]."""
-    out = []
-    for a in chain:
-        if a["kind"] == "gain_envelope":
-            p_lo, p_hi = envelope_range(a, sample_rate)
-            out.append((kind_id(a["kind"]), a["prob"], [float(p_lo), float(p_hi), a["floor"], 0.0]))
-        elif a["kind"] == "band_filter":
-            c_lo, c_hi, w_min = filter_range(a, sample_rate)
-            out.append((kind_id(a["kind"]), a["prob"], [float(filter_mask(a)), float(c_lo), float(c_hi), float(w_min)]))
-        elif a["kind"] == "excerpt":
-            l_lo, l_hi = excerpt_range(a, sample_rate)
-            out.append((kind_id(a["kind"]), a["prob"], [float(l_lo), float(l_hi), 0.0, 0.0]))
-        elif a["kind"] == "time_warp":
-            e_lo, e_hi, D = warp_range(a, sample_rate)
-            out.append((kind_id(a["kind"]), a["prob"], [float(e_lo), float(e_hi), float(D), 0.0]))
-        elif a["kind"] == "reverberation":
-            n_lo, n_hi = reverb_taps(a, sample_rate)
-            out.append((kind_id(a["kind"]), a["prob"], [float(n_lo), float(n_hi), a["drr_db"], 0.0]))
-        elif a["kind"] in ("speed_change", "pitch_shift", "time_stretch"):
-            m_lo, m_hi = stretch_range(a) if a["kind"] == "time_stretch" else speed_range(a)
-            out.append((kind_id(a["kind"]), a["prob"], [float(m_lo), float(m_hi), 0.0, 0.0]))
-        elif a["kind"] == "phase_vocoder":
-            q_lo, q_hi = stretch_range(a) if "rate" in a else (0, -1)
-            m_lo, m_hi = speed_range(a) if "cents" in a else (0, -1)
-            out.append((kind_id(a["kind"]), a["prob"], [float(q_lo), float(q_hi), float(m_lo), float(m_hi)]))
-        elif a["kind"] == "delete_samples":
-            k_lo, k_hi = delete_range(a, sample_rate)
-            out.append((kind_id(a["kind"]), a["prob"], [float(k_lo), float(k_hi), float(DELETE_AT[a["at"]]), 0.0]))
-        else:
-            k, p, pr = device_entries([a], sample_rate)[0]
-            out.append((k, pr, [p, 0.0, 0.0, 0.0]))
-    return out
+    return [(KINDS[a["kind"]], a["prob"], _KIND[a["kind"]].device(a, sample_rate)) for a in chain]
 
 
 def device_entries(chain: list[dict], sample_rate: int):

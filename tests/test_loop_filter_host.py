@@ -230,9 +230,9 @@ def test_parse_chain_refuses(entry, msg):
 
 
 def test_parse_chain_accepts_and_keeps_the_tables():
-    assert LA.SPLITTING_EX == {"band_filter": 9} and LA.kind_id("band_filter") == 9
-    assert list(LA.KINDS) == list(_golden("loop_chain_messages.json")["entries"]) and LA.ELEMENTWISE_EX == {"gain_envelope": 8}
-    assert LA.SPLITTING == ("reverberation", "speed_change", "time_stretch", "pitch_shift", "phase_vocoder", "delete_samples")
+    assert LA.KINDS["band_filter"] == 9 and LA.SPLITTING[6] == "band_filter" and LA.kind_id("band_filter") == 9
+    assert list(LA.KINDS)[:8] == list(_golden("loop_chain_messages.json")["entries"]) and LA.KINDS["gain_envelope"] == 8 and "gain_envelope" not in LA.SPLITTING
+    assert LA.SPLITTING[:6] == ("reverberation", "speed_change", "time_stretch", "pitch_shift", "phase_vocoder", "delete_samples")
     p = LA.parse_chain([{"kind": "band_filter", "response": "bandstop", "freq": [500.0, 1500.0]}])
     assert p == [{"kind": "band_filter", "prob": 1.0, "response": ["bandstop"], "freq": [500.0, 1500.0], "min_width": 400.0}]
     assert LA.parse_chain(p) == p
@@ -244,7 +244,7 @@ def test_parse_chain_accepts_and_keeps_the_tables():
     # the one-split rule against every splitting kind, in either order, and against itself
     table = _golden("loop_chain_messages.json")
     env = {"kind": "gain_envelope", "period": 0.05}
-    for kind in LA.SPLITTING:
+    for kind in LA.SPLITTING[:6]:
         s = table["entries"][kind]
         for chain in ([FIL, s], [s, FIL], [FIL, NOISE, s], [s, env, FIL]):
             with pytest.raises(ValueError, match="not both") as err:
@@ -308,7 +308,7 @@ def test_c_parser_on_the_cpu():
         assert [rc for rc, _ in run(dims + _chain_case([BF], ex=0) + _chain_case([NO, BF], ex=0))] == [-1, -1]
         # beside every other splitting kind, in either order and with an element-wise entry between them, and beside itself:
         # refused, and sized as the chain was sized before the kind existed (the other kind decides)
-        for k in LA.SPLITTING:
+        for k in LA.SPLITTING[:6]:
             got = run(dims + "".join(_chain_case(c) for c in ([BF, one[k]], [one[k], BF], [one[k], EV, BF], [one[k]])))
             assert [rc for rc, _ in got[:3]] == [-1, -1, -1], k
             assert got[0][1] == got[1][1] == got[3][1] > 0, k
