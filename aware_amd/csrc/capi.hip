@@ -9,6 +9,7 @@
 #include <string.h>
 #include <string>
 #include <algorithm>
+#include <memory>
 #include <vector>
 
 #include "../../include/aware_hip.h"
@@ -16,6 +17,7 @@
 #include "kernels.h"
 #define AWARE_LOOP_CF cf
 #include "loop_chain.hpp"
+#include "batch_layout.hpp"
 
 using namespace aware;
 
@@ -30,6 +32,11 @@ static thread_local std::string g_last_err;
         }                                                                             \
     } while (0)
 #define LAUNCHCHK() HIPCHK(hipGetLastError())
+
+// A handle under construction: every return between `new` and `*out = h.release()` destroys it with the object's own
+// aware_*_destroy (each of which takes a half-built object: it frees what is not null)
+template <auto Destroy> struct HandleDeleter { template <typename H> void operator()(H* h) const { Destroy(h); } };
+template <typename H, auto Destroy> using Building = std::unique_ptr<H, HandleDeleter<Destroy>>;
 
 // Optional per-launch timing of one optimiser iteration (aware_embed_profile): an event is
 // recorded on the launch stream after every kernel; consecutive events bracket one kernel.
@@ -71,23 +78,16 @@ struct aware_plan {
     std::vector<float> w2h, envh;       // host copies of the squared window and the envelope tables (NOLA check)
 };
 
-struct aware_batch {
+// host tables and scalars: batch_layout.hpp's BatchLayout on both routes, CardRuns (runs, workgroup tables) on the card route
+struct aware_batch : BatchLayout, CardRuns {
     int B = 0;
-    std::vector<int> n, in_off, T, frame_off, pool_off, out_off, out_len, pc_in, pc_syn;
-    int NF = 0, NP = 0, NS = 0, max_frames = 0, max_len = 0, pstride = 0;
-    int uniform_tp = 0;   // pooled frames per clip when all clips agree (else 0)
-    int synth_run = kSynthBlocks;   // hop blocks per synthesis run: 16, or 8 / 4 when 16 would leave the chip short of waves
+    std::vector<int> n;
     // device tables (one allocation)
     int* d_mem = nullptr;
     int *d_frame_off = nullptr, *d_pool_off = nullptr, *d_in_off = nullptr, *d_in_len = nullptr, *d_out_off = nullptr,
         *d_out_len = nullptr, *d_pc_in = nullptr, *d_pc_syn = nullptr;
-    // streaming DSP kernels: one workgroup = kStreamWaves runs of one clip; flat tables (clip << 12 | workgroup within the
-    // clip) so that a ragged batch launches exactly the workgroups that have work
-    int an_run = 0, n_an_wg = 0, n_syn_wg = 0;
     int *d_an_wg = nullptr, *d_syn_wg = nullptr;
-    std::vector<int> an_wg, syn_wg;
-    int* d_order = nullptr;            // clips longest first (dispatch order of the ragged GEMM: short clips fill the tail)
-    std::vector<int> order;
+    int* d_order = nullptr;
     // batch built by aware_batch_create_for_plan for a general plan: its geometry, whether every clip passes the NOLA
     // condition, and the frame buffer of the synthesis direction [NF][n_fft] floats
     int general = 0;
@@ -228,12 +228,10 @@ static int gen_plan_create(aware_plan** out, int n_fft, int hop, int win_length,
     twN[2 * M] = -1.f; twN[2 * M + 1] = 0.f;
     const size_t o_th = put(th.data(), th.size()), o_tw = put(twN.data(), twN.size());
     const size_t o_w = put(w.data(), w.size()), o_w2 = put(w2.data(), w2.size()), o_env = put(env.data(), env.size());
-    aware_plan* p = new aware_plan();
+    Building<aware_plan, aware_plan_destroy> p(new aware_plan());
     if (hipMalloc(&p->mem, h.size() * sizeof(float)) != hipSuccess ||
         hipMemcpy(p->mem, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
         g_last_err = "aware_plan_create: device tables";
-        if (p->mem) (void)hipFree(p->mem);
-        delete p;
         return AWARE_E_HIP;
     }
     const float* d = (const float*)p->mem;
@@ -254,7 +252,7 @@ static int gen_plan_create(aware_plan** out, int n_fft, int hop, int win_length,
     p->dev.stride = p->band_ok ? (p->dev.nband + 63) & ~63 : kFS;
     p->w2h = w2;
     p->envh = env;
-    *out = p;
+    *out = p.release();
     return AWARE_OK;
 }
 
@@ -303,7 +301,7 @@ extern "C" int aware_plan_create_ex(aware_plan** out, int n_fft, int hop, int wi
         for (int off = (q & 255) + 768; off >= q + 256; off -= 256) et += win2[off];
         env[1536 + q] = et;                                       // tail: p = 256*T + q
     }
-    aware_plan* p = new aware_plan();
+    Building<aware_plan, aware_plan_destroy> p(new aware_plan());
     HIPCHK(hipMalloc(&p->mem, h.size() * sizeof(float)));
     HIPCHK(hipMemcpy(p->mem, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
     float* d = (float*)p->mem;
@@ -315,7 +313,7 @@ extern "C" int aware_plan_create_ex(aware_plan** out, int n_fft, int hop, int wi
     p->dev.band_lo = band_lo_bin;
     p->dev.nband = nband;
     p->dev.stride = band_stride_for(band_lo_bin, band_hi_bin);
-    *out = p;
+    *out = p.release();
     return AWARE_OK;
 }
 extern "C" void aware_plan_destroy(aware_plan* p) {
@@ -339,187 +337,58 @@ extern "C" int aware_nola_check(int n_fft, int hop, int win_length, int window, 
 }
 
 // ---------------------------------------------------------------------------------------------
+// The host tables of a batch into its one device allocation d_mem, one behind the other: those of both routes, then the
+// route's own.  An empty table is not copied and keeps a null pointer.  Returns the first error.
+static hipError_t upload_tables(aware_batch* b, std::initializer_list<std::pair<int**, const std::vector<int>*>> own) {
+    int* d = b->d_mem;
+    hipError_t e = hipSuccess;
+    auto up = [&](int*& dst, const std::vector<int>& v) {
+        if (e != hipSuccess || v.empty()) return;
+        dst = d; d += v.size();
+        e = hipMemcpy(dst, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice);
+    };
+    up(b->d_frame_off, b->frame_off); up(b->d_pool_off, b->pool_off); up(b->d_in_off, b->in_off); up(b->d_in_len, b->n);
+    up(b->d_out_off, b->out_off); up(b->d_out_len, b->out_len); up(b->d_pc_in, b->pc_in); up(b->d_order, b->order);
+    for (const auto& t : own) up(*t.first, *t.second);
+    return e;
+}
 extern "C" int aware_batch_create(aware_batch** out, int B, const int* n_samples, const int* in_offsets) {
     if (!out || B < 1 || !n_samples) return AWARE_E_BADARG;
-    aware_batch* b = new aware_batch();
+    Building<aware_batch, aware_batch_destroy> b(new aware_batch());
     b->B = B;
     b->n.assign(n_samples, n_samples + B);
-    b->in_off.resize(B);
-    b->T.resize(B);
-    b->frame_off.resize(B + 1);
-    b->pool_off.resize(B + 1);
-    b->out_off.resize(B);
-    b->out_len.resize(B);
-    b->pc_in.resize(B);
-    b->pc_syn.resize(B);
-    int acc = 0, max_pc = 1;
-    // run length of the synthesis kernels (one wave of the streaming kernels per run): the longest of 16 / 12 / 8 / 6 / 4
-    // hop blocks that still gives ~16 waves per CU; a run of r blocks transforms r + 3 frames, so short runs cost more
-    // arithmetic and are only worth it while the chip would otherwise idle
-    // (measured, 3 s clips, us synthesis / adjoint: B = 256: 16 66/66, 12 65/64, 8 77/75; B = 128: 12 43/47, 8 40/42, 6 39/42,
-    // 4 51/52; B = 64: 8 31/30, 6 28/28, 4 28/28)
-    for (int rb : {12, 8, 6, 4}) {          // (16 never measured better than 12)
-        long runs = 0;
-        for (int i = 0; i < B; ++i) runs += (n_samples[i] / kHop + rb - 1) / rb;
-        // the staged adjoint folds the reflect pads inside the first / last segment: keep those at >= 3 blocks
-        bool ok = true;
-        for (int i = 0; i < B && ok; ++i) {
-            const int nb = n_samples[i] / kHop, ns = (nb + rb - 1) / rb;
-            if (ns > 1 && nb / ns < 3) ok = false;
-        }
-        if (!ok) continue;
-        b->synth_run = rb;
-        if (runs >= 4096) break;
-    }
-    b->frame_off[0] = 0;
-    b->pool_off[0] = 0;
-    for (int i = 0; i < B; ++i) {
-        const int n = n_samples[i];
-        // torch.stft's reflect padding needs n > n_fft/2
-        if (n <= kHalf) { delete b; return AWARE_E_BADARG; }
-        b->in_off[i] = in_offsets ? in_offsets[i] : acc;
-        acc += n;
-        const int T = 1 + n / kHop;
-        b->T[i] = T;
-        b->frame_off[i + 1] = b->frame_off[i] + T;
-        b->pool_off[i + 1] = b->pool_off[i] + ((T / 2 + 31) & ~31);   // pooled rows are 32-aligned per clip
-        b->out_off[i] = kHop * (b->frame_off[i] - i);
-        b->out_len[i] = kHop * (T - 1);
-        b->pc_in[i] = (n + 4095) / 4096;
-        int nseg = (T - 1 + b->synth_run - 1) / b->synth_run;
-        if (nseg < 1) nseg = 1;
-        b->pc_syn[i] = nseg;
-        if (T > b->max_frames) b->max_frames = T;
-        if (n > b->max_len) b->max_len = n;
-        if (b->pc_in[i] > max_pc) max_pc = b->pc_in[i];
-        if (nseg > max_pc) max_pc = nseg;
-    }
-    b->NF = b->frame_off[B];
-    b->NP = b->pool_off[B];
-    b->uniform_tp = b->T[0] / 2;
-    for (int i = 1; i < B; ++i)
-        if (b->T[i] / 2 != b->uniform_tp) b->uniform_tp = 0;
-    b->NS = kHop * (b->NF - B);
-    b->pstride = max_pc;
-    {
-        // (runs longer than 12 frames measured slower even when the chip has waves to spare: B = 256 x 3 s, analysis / adjoint
-        //  67 / 118 us at R = 12 against 69 / 136 at R = 16)
-        constexpr int kAnalysisMaxRun = 12;
-        // frames per analysis run: the longest R in [4, 12] that still gives 4096 waves; for a uniform batch then the nearest
-        // shorter R whose run count per clip is a multiple of the waves of a workgroup (measurements: dsp_stream.hip)
-        auto total_runs = [&](int r) { long t = 0; for (int i = 0; i < B; ++i) t += (b->T[i] + r - 1) / r; return t; };
-        int R = 4;
-        for (int cand = kAnalysisMaxRun; cand >= 4; --cand)
-            if (total_runs(cand) >= 4096) { R = cand; break; }
-        bool same = true;
-        for (int i = 1; i < B; ++i) same = same && b->T[i] == b->T[0];
-        if (same)
-            for (int cand = R; cand >= 4 && cand >= R - 3; --cand)
-                if (((b->T[0] + cand - 1) / cand) % kStreamWaves == 0) { R = cand; break; }
-        b->an_run = R;
-        if (B < (1 << 19) && b->max_frames / 4 < 4096 * kStreamWaves) {
-            for (int i = 0; i < B; ++i) {
-                const int ra = (b->T[i] + R - 1) / R, rs = std::max(1, (b->T[i] - 1 + b->synth_run - 1) / b->synth_run);
-                for (int w = 0; w < (ra + kStreamWaves - 1) / kStreamWaves; ++w) b->an_wg.push_back((i << 12) | w);
-                for (int w = 0; w < (rs + kStreamWaves - 1) / kStreamWaves; ++w) b->syn_wg.push_back((i << 12) | w);
-            }
-        }
-        b->n_an_wg = (int)b->an_wg.size();
-        b->n_syn_wg = (int)b->syn_wg.size();
-    }
-    b->order.resize(B);
-    for (int i = 0; i < B; ++i) b->order[i] = i;
-    std::stable_sort(b->order.begin(), b->order.end(), [&](int x, int y) { return b->T[x] > b->T[y]; });
+    // torch.stft's reflect padding needs n > n_fft/2
+    if (!batch_layout(n_samples, in_offsets, B, kHop, kHalf, *b)) return AWARE_E_BADARG;
+    card_runs(n_samples, kHop, kStreamWaves, kSynthBlocks, *b, *b);
     const size_t ints = (size_t)(B + 1) * 2 + (size_t)B * 7 + b->an_wg.size() + b->syn_wg.size();
     HIPCHK(hipMalloc((void**)&b->d_mem, ints * sizeof(int)));
-    int* d = b->d_mem;
-    auto up = [&](int*& dst, const std::vector<int>& v) -> hipError_t {
-        dst = d;
-        d += v.size();
-        return hipMemcpy(dst, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice);
-    };
-    HIPCHK(up(b->d_frame_off, b->frame_off));
-    HIPCHK(up(b->d_pool_off, b->pool_off));
-    HIPCHK(up(b->d_in_off, b->in_off));
-    HIPCHK(up(b->d_in_len, b->n));
-    HIPCHK(up(b->d_out_off, b->out_off));
-    HIPCHK(up(b->d_out_len, b->out_len));
-    HIPCHK(up(b->d_pc_in, b->pc_in));
-    HIPCHK(up(b->d_pc_syn, b->pc_syn));
-    HIPCHK(up(b->d_order, b->order));
-    if (b->n_an_wg) HIPCHK(up(b->d_an_wg, b->an_wg));
-    if (b->n_syn_wg) HIPCHK(up(b->d_syn_wg, b->syn_wg));
-    *out = b;
+    HIPCHK(upload_tables(b.get(), {{&b->d_pc_syn, &b->pc_syn}, {&b->d_an_wg, &b->an_wg}, {&b->d_syn_wg, &b->syn_wg}}));
+    *out = b.release();
     return AWARE_OK;
 }
 static int gen_batch_create(aware_batch** out, const aware_plan* plan, int B, const int* n_samples, const int* in_offsets) {
     const int N = plan->n_fft, hop = plan->hop;
-    for (int i = 0; i < B; ++i)
-        if (n_samples[i] <= N / 2) return AWARE_E_BADARG;      // torch.stft's reflect padding needs n > n_fft/2
-    aware_batch* b = new aware_batch();
+    Building<aware_batch, aware_batch_destroy> b(new aware_batch());
     b->general = 1;
     b->g_nfft = N; b->g_hop = hop; b->g_win = plan->win_length; b->g_window = plan->window;
     b->B = B;
     b->n.assign(n_samples, n_samples + B);
-    b->in_off.resize(B); b->T.resize(B); b->frame_off.assign(B + 1, 0); b->pool_off.assign(B + 1, 0);
-    b->out_off.resize(B); b->out_len.resize(B); b->pc_in.resize(B); b->pc_syn.resize(B);
-    std::vector<int> pc_out(B);
-    long acc = 0;
-    int max_pc = 1;
-    for (int i = 0; i < B; ++i) {
-        const int n = n_samples[i], T = 1 + n / hop;
-        b->in_off[i] = in_offsets ? in_offsets[i] : (int)acc;
-        acc += n;
-        b->T[i] = T;
-        b->frame_off[i + 1] = b->frame_off[i] + T;
-        b->pool_off[i + 1] = b->pool_off[i] + ((T / 2 + 31) & ~31);   // floor(T / 2) pooled rows, 32-aligned per clip
-        b->out_off[i] = hop * (b->frame_off[i] - i);
-        b->out_len[i] = hop * (T - 1);
-        b->pc_in[i] = (n + 4095) / 4096;
-        pc_out[i] = (b->out_len[i] + 4095) / 4096;
-        b->max_frames = std::max(b->max_frames, T);
-        b->max_len = std::max(b->max_len, n);
-        max_pc = std::max(max_pc, b->pc_in[i]);
-        b->nola_ok = b->nola_ok && gen_nola_ok(plan->envh.data(), plan->w2h.data(), N, hop, T);
-    }
-    b->NF = b->frame_off[B];
-    b->NP = b->pool_off[B];
-    b->uniform_tp = b->T[0] / 2;
-    for (int i = 1; i < B; ++i)
-        if (b->T[i] / 2 != b->uniform_tp) b->uniform_tp = 0;
-    b->NS = hop * (b->NF - B);
-    b->pstride = max_pc;
-    b->order.resize(B);
-    for (int i = 0; i < B; ++i) b->order[i] = i;
-    std::stable_sort(b->order.begin(), b->order.end(), [&](int x, int y) { return b->T[x] > b->T[y]; });
+    if (!batch_layout(n_samples, in_offsets, B, hop, N / 2, *b)) return AWARE_E_BADARG;      // n > n_fft/2, as on the card route
+    b->synth_run = kSynthBlocks;      // no runs on this route: aware_batch_synth_run reports the staged kernels' block count
+    const std::vector<int> pc_out = pc_out_for(b->out_len);
+    for (int i = 0; i < B; ++i) b->nola_ok = b->nola_ok && gen_nola_ok(plan->envh.data(), plan->w2h.data(), N, hop, b->T[i]);
     const size_t ints = (size_t)(B + 1) * 2 + (size_t)B * 7;
     if (hipMalloc((void**)&b->d_mem, ints * sizeof(int)) != hipSuccess ||
         hipMalloc((void**)&b->d_frames, (size_t)b->NF * N * sizeof(float)) != hipSuccess) {
         g_last_err = "aware_batch_create_for_plan: device memory";
-        aware_batch_destroy(b);
         return AWARE_E_HIP;
     }
-    int* d = b->d_mem;
-    auto up = [&](int*& dst, const std::vector<int>& v) -> hipError_t {
-        dst = d;
-        d += v.size();
-        return hipMemcpy(dst, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice);
-    };
-    hipError_t e = up(b->d_frame_off, b->frame_off);
-    if (e == hipSuccess) e = up(b->d_in_off, b->in_off);
-    if (e == hipSuccess) e = up(b->d_in_len, b->n);
-    if (e == hipSuccess) e = up(b->d_out_off, b->out_off);
-    if (e == hipSuccess) e = up(b->d_out_len, b->out_len);
-    if (e == hipSuccess) e = up(b->d_pc_in, b->pc_in);
-    if (e == hipSuccess) e = up(b->d_pc_out, pc_out);
-    if (e == hipSuccess) e = up(b->d_pool_off, b->pool_off);
-    if (e == hipSuccess) e = up(b->d_order, b->order);
+    const hipError_t e = upload_tables(b.get(), {{&b->d_pc_out, &pc_out}});
     if (e != hipSuccess) {
         g_last_err = std::string("aware_batch_create_for_plan: ") + hipGetErrorString(e);
-        aware_batch_destroy(b);
         return AWARE_E_HIP;
     }
-    *out = b;
+    *out = b.release();
     return AWARE_OK;
 }
 
@@ -569,6 +438,23 @@ static GenLaunch gen_launch(const aware_plan* plan, const aware_batch* b) {
     L.pstride = b->pstride;
     L.frames = b->d_frames;
     return L;
+}
+// ---- card dispatch (dsp_kernels.hip, dsp_stream.hip): what every launch of a transform takes from its plan and its batch;
+// everything else is set where the launch is made.  The analysis reads `sig` on the caller's layout (clip i at in_off[i], n_i
+// samples, one partial maximum per 4096 of them), or on the loop's (at out_off[i], hop (T_i - 1) samples, one per synthesis run)
+static AnalysisLaunch analysis_launch(const aware_plan* plan, const aware_batch* b, const float* sig, bool loop_layout) {
+    AnalysisLaunch L;
+    L.plan = plan->dev; L.frame_off = b->d_frame_off; L.B = b->B; L.max_frames = b->max_frames;
+    L.run_frames = b->an_run; L.wg_tab = b->d_an_wg; L.n_wg = (int)b->an_wg.size();
+    L.sig = sig; L.sig_off = loop_layout ? b->d_out_off : b->d_in_off; L.sig_len = loop_layout ? b->d_out_len : b->d_in_len;
+    L.pcount = loop_layout ? b->d_pc_syn : b->d_pc_in; L.pstride = b->pstride;
+    return L;
+}
+static SynthLaunch synth_launch(const aware_plan* plan, const aware_batch* b) {
+    SynthLaunch S;
+    S.plan = plan->dev; S.frame_off = b->d_frame_off; S.B = b->B; S.max_frames = b->max_frames;
+    S.run_blocks = b->synth_run; S.wg_tab = b->d_syn_wg; S.n_wg = (int)b->syn_wg.size();
+    return S;
 }
 static int gen_stft(const aware_plan* plan, const aware_batch* b, const float* audio, int normalize, void* spec,
                     void* scratch, hipStream_t st) {
@@ -628,10 +514,8 @@ extern "C" int aware_stft(const aware_plan* plan, const aware_batch* b, const fl
         launch_absmax_partials(audio, b->d_in_off, b->d_in_len, pmax, b->pstride, b->B, b->max_len, st);
         LAUNCHCHK();
     }
-    AnalysisLaunch L;
-    L.plan = plan->dev; L.frame_off = b->d_frame_off; L.B = b->B; L.max_frames = b->max_frames; L.run_frames = b->an_run; L.wg_tab = b->d_an_wg; L.n_wg = b->n_an_wg;
-    L.sig = audio; L.sig_off = b->d_in_off; L.sig_len = b->d_in_len;
-    L.pmax = normalize ? pmax : nullptr; L.pcount = b->d_pc_in; L.pstride = b->pstride;
+    AnalysisLaunch L = analysis_launch(plan, b, audio, false);
+    L.pmax = normalize ? pmax : nullptr;
     L.full = spec;
     launch_analysis(L, st);
     LAUNCHCHK();
@@ -649,10 +533,8 @@ extern "C" int aware_stft_band(const aware_plan* plan, const aware_batch* b, con
         launch_absmax_partials(audio, b->d_in_off, b->d_in_len, pmax, b->pstride, b->B, b->max_len, st);
         LAUNCHCHK();
     }
-    AnalysisLaunch L;
-    L.plan = plan->dev; L.frame_off = b->d_frame_off; L.B = b->B; L.max_frames = b->max_frames; L.run_frames = b->an_run; L.wg_tab = b->d_an_wg; L.n_wg = b->n_an_wg;
-    L.sig = audio; L.sig_off = b->d_in_off; L.sig_len = b->d_in_len;
-    L.pmax = normalize ? pmax : nullptr; L.pcount = b->d_pc_in; L.pstride = b->pstride;
+    AnalysisLaunch L = analysis_launch(plan, b, audio, false);
+    L.pmax = normalize ? pmax : nullptr;
     L.mag = mag; L.unit = phasor; L.unit_default = 1.f;
     run_analysis(L, 0, st);
     LAUNCHCHK();
@@ -666,8 +548,7 @@ extern "C" int aware_istft(const aware_plan* plan, const aware_batch* b, const v
     if (plan->general) return gen_istft(plan, b, spec, normalize, out, scratch, st);
     if (b->general) return AWARE_E_BADARG;
     unsigned long long* pmax = (unsigned long long*)scratch;
-    SynthLaunch S;
-    S.plan = plan->dev; S.frame_off = b->d_frame_off; S.B = b->B; S.max_frames = b->max_frames; S.run_blocks = b->synth_run; S.wg_tab = b->d_syn_wg; S.n_wg = b->n_syn_wg;
+    SynthLaunch S = synth_launch(plan, b);
     S.full = spec; S.out = out; S.pmax = normalize ? pmax : nullptr; S.pstride = b->pstride;
     launch_synth(S, st);
     LAUNCHCHK();
@@ -692,13 +573,9 @@ extern "C" int aware_stft_bwd(const aware_plan* plan, const aware_batch* b, cons
     if (b->general) return AWARE_E_BADARG;
     // the staged synthesis kernel in adjoint mode: overlap-add of the windowed rfft adjoints, then the fold of the two reflect
     // pads for a clip of any length n > 512 at the clip's offset in the caller's ragged array
-    if (b->synth_run > 0)
-        for (int i = 0; i < b->B; ++i) {
-            const int nb = b->T[i] - 1, ns = (nb + b->synth_run - 1) / b->synth_run;
-            if (ns > 1 && nb / ns < 3) return AWARE_E_UNSUPPORTED;          // (aware_batch_create never builds such a batch)
-        }
-    SynthLaunch S;
-    S.plan = plan->dev; S.frame_off = b->d_frame_off; S.B = b->B; S.max_frames = b->max_frames; S.run_blocks = b->synth_run; S.wg_tab = b->d_syn_wg; S.n_wg = b->n_syn_wg;
+    for (int i = 0; i < b->B; ++i)
+        if (run_cuts_short_segments(b->T[i] - 1, b->synth_run)) return AWARE_E_UNSUPPORTED;      // (synth_run_for never picks such a run)
+    SynthLaunch S = synth_launch(plan, b);
     S.full = grad_spec; S.out = grad_audio; S.adjoint = 1; S.pstride = b->pstride;
     S.sig_off = b->d_in_off; S.sig_len = b->d_in_len;
     launch_synth(S, (hipStream_t)stream);
@@ -716,10 +593,7 @@ extern "C" int aware_istft_bwd(const aware_plan* plan, const aware_batch* b, con
         return AWARE_OK;
     }
     if (b->general) return AWARE_E_BADARG;
-    AnalysisLaunch L;
-    L.plan = plan->dev; L.frame_off = b->d_frame_off; L.B = b->B; L.max_frames = b->max_frames; L.run_frames = b->an_run; L.wg_tab = b->d_an_wg; L.n_wg = b->n_an_wg;
-    L.sig = grad_audio; L.sig_off = b->d_out_off; L.sig_len = b->d_out_len;
-    L.pcount = b->d_pc_syn; L.pstride = b->pstride;
+    AnalysisLaunch L = analysis_launch(plan, b, grad_audio, true);
     L.full = grad_spec; L.adjoint = 1;
     launch_analysis(L, (hipStream_t)stream);
     LAUNCHCHK();
@@ -936,7 +810,7 @@ static int detector_create(aware_detector** out, const aware_plan* plan, const f
     if (cl % 2 || cl < 2 || cl > kMaxOutChannels) return AWARE_E_UNSUPPORTED;
     for (int i = 1; i < n_layers; ++i)
         if (channels[i] < 1 || channels[i] > kMaxHidden) return AWARE_E_UNSUPPORTED;
-    aware_detector* d = new aware_detector();
+    Building<aware_detector, aware_detector_destroy> d(new aware_detector());
     d->n_mels = n_mels; d->n_layers = n_layers; d->nbits = cl / 2;
     d->band_lo = plan->dev.band_lo; d->nband = plan->dev.nband; d->stride = plan->dev.stride;
     d->n_fft = plan->n_fft; d->general = plan->general != 0;
@@ -954,7 +828,7 @@ static int detector_create(aware_detector** out, const aware_plan* plan, const f
         d->act = arch->activation; d->norm = arch->norm; d->final_act = arch->final_activation;
         d->card_arch = d->act == kActLRelu && d->norm == kNormInstance && d->final_act == kActTanh;
     }
-    int rc = detector_upload(d, mel_basis, weights, biases, true);
+    int rc = detector_upload(d.get(), mel_basis, weights, biases, true);
     if (rc == AWARE_OK && d->norm == kNormAffine) {
         // padding channels (stored_channels) get scale 0 and shift 0: their pre-activation is 0 and their output act(0) = 0
         // for every block activation.  They are never read out and their gradient is zero.
@@ -980,8 +854,8 @@ static int detector_create(aware_detector** out, const aware_plan* plan, const f
             }
         }
     }
-    if (rc) { aware_detector_destroy(d); return rc; }
-    *out = d;
+    if (rc) return rc;
+    *out = d.release();
     return AWARE_OK;
 }
 extern "C" int aware_detector_create(aware_detector** out, const aware_plan* plan, const float* mel_basis, int n_mels,
@@ -1922,11 +1796,11 @@ extern "C" int aware_embed_create(aware_embed** out, const aware_plan* plan, con
         if (!any) return AWARE_E_UNSUPPORTED;
     }
     hipStream_t st = (hipStream_t)stream;
-    aware_embed* e = new aware_embed();
+    Building<aware_embed, aware_embed_destroy> e(new aware_embed());
     e->plan = plan; e->det = det; e->b = b; e->cfg = *cfg;
     Carver c(workspace, workspace_bytes);
-    carve_embed(c, b, det, cfg->num_iterations, l1, e);
-    if (!c.ok) { delete e; return AWARE_E_WORKSPACE; }
+    carve_embed(c, b, det, cfg->num_iterations, l1, e.get());
+    if (!c.ok) return AWARE_E_WORKSPACE;
     const size_t nsp = (size_t)b->NF * plan->dev.stride;
     // columns nband..stride-1 of every spectral row are padding: zeroed once here, never written by the loop kernels
     HIPCHK(hipMemsetAsync(e->mag, 0, nsp * sizeof(float), st));
@@ -1966,7 +1840,7 @@ extern "C" int aware_embed_create(aware_embed** out, const aware_plan* plan, con
         }
         HIPCHK(hipStreamSynchronize(st));
     }
-    *out = e;
+    *out = e.release();
     return AWARE_OK;
 }
 // The third seam of the reference: optimiser / scheduler registries selected by YAML strings (embedding/optimizers.py:3-20,
@@ -2188,12 +2062,15 @@ extern "C" int aware_reverb_ir(const uint32_t* seeds, int B, int step, int entry
     return AWARE_OK;
 }
 
+// the ragged signal array of a stand-alone attack entry point: 1 to 65535 clips, the longest of 1 to 2^30 samples
+static bool ragged_args_ok(int B, int max_len) { return B >= 1 && B <= 65535 && max_len >= 1 && max_len <= (1 << 30); }
+
 // ---- the in -> out resamplers alone: one argument list, one set of checks; `windowed`: the launch reads stretch_window() ------
 static int resample_alone(void (*launch)(const ResampleLaunch&, hipStream_t), bool windowed, const float* in, const int* in_off,
                           const int* in_len, float* out, const int* out_off, const int* out_len, int B, int max_len, const int* m,
                           int adjoint, void* stream) {
     if (!in || !in_off || !in_len || !out || !out_off || !out_len || !m || in == out) return AWARE_E_BADARG;
-    if (B < 1 || B > 65535 || max_len < 1 || max_len > (1 << 30) || adjoint < 0 || adjoint > 1) return AWARE_E_BADARG;
+    if (!ragged_args_ok(B, max_len) || adjoint < 0 || adjoint > 1) return AWARE_E_BADARG;
     ResampleLaunch L;
     if (windowed && !(L.window = stretch_window())) return AWARE_E_HIP;
     L.in = in; L.out = out; L.B = B; L.adjoint = adjoint; L.max_len = max_len; L.m = m;
@@ -2222,7 +2099,7 @@ extern "C" int aware_pitch_shift_ola(const float* in, const int* in_off, const i
 extern "C" int aware_delete_samples(const float* in, const int* off, const int* len, int B, int max_len, const int* start,
                                     const int* k, float* out, int adjoint, void* stream) {
     if (!in || !off || !len || !start || !k || !out || in == out) return AWARE_E_BADARG;
-    if (B < 1 || B > 65535 || max_len < 1 || max_len > (1 << 30) || adjoint < 0 || adjoint > 1) return AWARE_E_BADARG;
+    if (!ragged_args_ok(B, max_len) || adjoint < 0 || adjoint > 1) return AWARE_E_BADARG;
     DeleteLaunch L;
     L.in = in; L.out = out; L.B = B; L.adjoint = adjoint; L.off = off; L.len = len; L.max_len = max_len; L.start = start; L.k = k;
     launch_delete_samples(L, (hipStream_t)stream);
@@ -2234,7 +2111,7 @@ extern "C" int aware_delete_samples(const float* in, const int* off, const int* 
 extern "C" int aware_excerpt_tile(const float* in, const int* off, const int* len, int B, int max_len, const int* start,
                                   const int* length, float* out, int adjoint, void* stream) {
     if (!in || !off || !len || !start || !length || !out || in == out) return AWARE_E_BADARG;
-    if (B < 1 || B > 65535 || max_len < 1 || max_len > (1 << 30) || adjoint < 0 || adjoint > 1) return AWARE_E_BADARG;
+    if (!ragged_args_ok(B, max_len) || adjoint < 0 || adjoint > 1) return AWARE_E_BADARG;
     ExcerptLaunch L;
     L.in = in; L.out = out; L.B = B; L.adjoint = adjoint; L.off = off; L.len = len; L.max_len = max_len; L.start = start; L.length = length;
     launch_excerpt_tile(L, (hipStream_t)stream);
@@ -2246,7 +2123,7 @@ extern "C" int aware_excerpt_tile(const float* in, const int* off, const int* le
 extern "C" int aware_time_warp(const float* in, const int* off, const int* len, int B, int max_len, const int* e, const int* ph,
                                const int* rates, int stride, int* table_r, long long* table_a, float* out, int adjoint, void* stream) {
     if (!in || !off || !len || !e || !ph || !rates || !table_r || !table_a || !out || in == out) return AWARE_E_BADARG;
-    if (B < 1 || B > 65535 || max_len < 1 || max_len > (1 << 30) || stride < 3 || adjoint < 0 || adjoint > 1) return AWARE_E_BADARG;
+    if (!ragged_args_ok(B, max_len) || stride < 3 || adjoint < 0 || adjoint > 1) return AWARE_E_BADARG;
     WarpLaunch L;
     L.in = in; L.out = out; L.B = B; L.adjoint = adjoint; L.table_r = table_r; L.table_a = table_a; L.stride = stride;
     L.off = off; L.len = len; L.max_len = max_len; L.e = e; L.ph = ph; L.rates = rates;
@@ -2259,7 +2136,7 @@ extern "C" int aware_time_warp(const float* in, const int* off, const int* len, 
 extern "C" int aware_band_filter(const float* in, const int* off, const int* len, int B, int max_len, const int* response,
                                  const int* c1, const int* c2, float* out, float* taps, void* stream) {
     if (!in || !off || !len || !response || !c1 || !c2 || !out || in == out) return AWARE_E_BADARG;
-    if (B < 1 || B > 65535 || max_len < 1 || max_len > (1 << 30)) return AWARE_E_BADARG;
+    if (!ragged_args_ok(B, max_len)) return AWARE_E_BADARG;
     FilterLaunch L;
     L.in = in; L.out = out; L.B = B; L.off = off; L.len = len; L.max_len = max_len; L.response = response; L.c1 = c1; L.c2 = c2;
     L.taps = taps;
@@ -2272,7 +2149,7 @@ extern "C" int aware_band_filter(const float* in, const int* off, const int* len
 extern "C" int aware_gain_envelope(const float* in, const int* off, const int* len, int B, int max_len, const uint32_t* seeds,
                                    int step, int entry, int p_lo, int p_hi, float floor, float* out, float* gains, void* stream) {
     if (!in || !off || !len || !seeds || !out) return AWARE_E_BADARG;
-    if (B < 1 || B > 65535 || max_len < 1 || max_len > (1 << 30) || step < 0 || entry < 0 || entry >= kMaxLoopAttacks) return AWARE_E_BADARG;
+    if (!ragged_args_ok(B, max_len) || step < 0 || entry < 0 || entry >= kMaxLoopAttacks) return AWARE_E_BADARG;
     if (p_lo < kEnvelopeMinPeriod || p_lo > p_hi || p_hi > kEnvelopeMaxPeriod || !(floor >= 0.f && floor < 1.f)) return AWARE_E_BADARG;
     GainLaunch L;
     L.in = in; L.out = out; L.gains = gains; L.off = off; L.len = len; L.B = B; L.max_len = max_len; L.seeds = seeds;
@@ -2296,7 +2173,7 @@ extern "C" int aware_sync_select(const float* values, int B, int n, int L, float
 extern "C" int aware_speed_views(const float* in, const int* in_off, const int* in_len, int B, const int* m, int n_views,
                                  float* out, const int* out_off, int max_len, void* stream) {
     if (!in || !in_off || !in_len || !m || !out || !out_off || in == out) return AWARE_E_BADARG;
-    if (B < 1 || B > 65535 || n_views < 1 || n_views > 63 || max_len < 1 || max_len > (1 << 30)) return AWARE_E_BADARG;
+    if (!ragged_args_ok(B, max_len) || n_views < 1 || n_views > 63) return AWARE_E_BADARG;
     launch_speed_views(in, in_off, in_len, B, m, n_views, out, out_off, max_len, (hipStream_t)stream);
     LAUNCHCHK();
     return AWARE_OK;
@@ -2416,6 +2293,31 @@ extern "C" void* aware_embed_buffer(aware_embed* e, int which) {
     }
 }
 
+// ---- what one loop body needs on both routes ----
+// the box of the coefficients: |c - c0| <= c0 * ratio, tolerance_db below the original magnitude
+static float box_ratio(const aware_embed_config& cfg) { return (float)pow(10.0, -(double)cfg.tolerance_db / 20.0); }
+// what det_forward_backward takes from the handle (the card route adds loss_add)
+static DetGradCtx loop_grad_ctx(const aware_embed* e, int do_step) {
+    DetGradCtx G;
+    G.target = e->target; G.loss_kind = e->cfg.loss;
+    G.loss = e->loss; G.d1 = e->d1; G.d2 = e->d2; G.gmag = e->gmag;
+    G.step = do_step ? e->step : nullptr;               // the read-out kernel advances the step counter
+    // aware_embed_gradient (do_step == 0) leaves the best-loss bookkeeping alone: the reference snapshots only
+    // inside the optimiser loop (multibit_embedder.py:120-122)
+    G.best_loss = do_step ? e->best_loss : nullptr;
+    G.improved = do_step ? e->improved : nullptr;
+    return G;
+}
+// the step of an optimiser / schedule set by aware_embed_set_optimizer, on the gradient the loop body left in gmag
+static void own_optimizer_step(const aware_embed* e, hipStream_t st) {
+    const aware_batch* b = e->b;
+    const auto& o = e->opt;
+    launch_opt_rows(o.kind, e->coef, e->gmag, e->mom, e->vel, e->c0, box_ratio(e->cfg), e->best, e->improved, b->d_frame_off, b->B,
+                    b->NF, o.d_tab, e->cfg.num_iterations, e->step, o.plateau ? o.d_lr : nullptr, o.wd, o.hyp,
+                    e->plan->dev.nband, e->plan->dev.stride, st);
+    if (o.plateau) launch_plateau(e->loss, o.d_state, o.d_lr, b->B, o.factor, o.patience, o.threshold, o.min_lr, o.eps, st);
+}
+
 // ---- the general route (a general plan): the loop on the transforms of stft_any.hip and the band kernels of loop_any.hip ----
 // the transforms on the synthesis' signal layout: clip b at out_off[b], hop (T_b - 1) samples, on both sides
 static GenLaunch gen_loop_launch(const aware_embed* e) {
@@ -2431,7 +2333,7 @@ static int gen_embed_begin(aware_embed* e, const float* audio, hipStream_t st) {
     if (rc) return rc;
     BandBegin G;
     G.unit = e->U; G.coef = e->coef; G.lo = e->lo; G.hi = e->hi; G.mom = e->mom; G.vel = e->vel; G.best = e->best; G.c0 = e->c0;
-    G.ratio = (float)pow(10.0, -(double)e->cfg.tolerance_db / 20.0);
+    G.ratio = box_ratio(e->cfg);
     launch_band_mag(band_launch(e->plan, b), e->S0, e->mag, &G, st);
     LAUNCHCHK();
     return AWARE_OK;
@@ -2466,14 +2368,8 @@ static int gen_embed_iteration(aware_embed* e, hipStream_t st, int do_step, floa
     launch_band_mag(BL, e->S2, e->mag, nullptr, st);
     LAUNCHCHK(); PROF(K_MISC);
     // :107 detector forward, :109 loss, :120-122 best tracking, :111 backward through the detector
-    DetGradCtx G;
-    G.target = e->target; G.loss_kind = e->cfg.loss;
-    G.loss = e->loss; G.d1 = e->d1; G.d2 = e->d2; G.gmag = e->gmag;
-    G.step = do_step ? e->step : nullptr;
-    G.best_loss = do_step ? e->best_loss : nullptr;
-    G.improved = do_step ? e->improved : nullptr;
     const DetPlan p = det_plan(d, b, e->cfg.conv_pipe, e->cfg.readout, false, false, false, e->cfg.conv_tile);
-    rc = det_forward_backward(d, b, p, e->mag, e->db, G, st);
+    rc = det_forward_backward(d, b, p, e->mag, e->db, loop_grad_ctx(e, do_step), st);
     if (rc) return rc;
     // backward through |.|, the STFT and its reflect padding, the two normalisers, the ISTFT and the assembler
     launch_band_mag_bwd(BL, e->S2, e->gmag, e->GS, st);
@@ -2495,12 +2391,7 @@ static int gen_embed_iteration(aware_embed* e, hipStream_t st, int do_step, floa
     launch_band_coef_grad(BL, e->S2, e->U, own_step ? e->gmag : grad_out, (do_step && !own_step) ? &S : nullptr, st);
     LAUNCHCHK(); PROF(K_MISC);
     if (own_step) {
-        const auto& o = e->opt;
-        launch_opt_rows(o.kind, e->coef, e->gmag, e->mom, e->vel, e->c0, (float)pow(10.0, -(double)e->cfg.tolerance_db / 20.0),
-                        e->best, e->improved, b->d_frame_off, b->B, b->NF, o.d_tab, e->cfg.num_iterations, e->step,
-                        o.plateau ? o.d_lr : nullptr, o.wd, o.hyp, e->plan->dev.nband, e->plan->dev.stride, st);
-        if (o.plateau)
-            launch_plateau(e->loss, o.d_state, o.d_lr, b->B, o.factor, o.patience, o.threshold, o.min_lr, o.eps, st);
+        own_optimizer_step(e, st);
         LAUNCHCHK(); PROF(K_MISC);
     }
     return AWARE_OK;
@@ -2518,24 +2409,21 @@ extern "C" int aware_embed_begin(aware_embed* e, const float* audio, const float
     // [WaveformNormalizer, STFT, STFTDecomposer] (multibit_embedder.py:143-147), band only
     launch_absmax_partials(audio, b->d_in_off, b->d_in_len, e->pmaxA, b->pstride, b->B, b->max_len, st);
     LAUNCHCHK();
-    AnalysisLaunch L;
-    L.plan = e->plan->dev; L.frame_off = b->d_frame_off; L.B = b->B; L.max_frames = b->max_frames; L.run_frames = b->an_run; L.wg_tab = b->d_an_wg; L.n_wg = b->n_an_wg;
-    L.sig = audio; L.sig_off = b->d_in_off; L.sig_len = b->d_in_len;
-    L.pmax = e->pmaxA; L.pcount = b->d_pc_in; L.pstride = b->pstride;
+    AnalysisLaunch L = analysis_launch(e->plan, b, audio, false);
+    L.pmax = e->pmaxA;
     L.mag = e->mag; L.unit = e->P; L.unit_default = 1.f;
     run_analysis(L, e->cfg.dsp_path, st);
     LAUNCHCHK();
     // constant out-of-band part of every synthesis: x/m - istft(band of the original)
-    SynthLaunch S;
-    S.plan = e->plan->dev; S.frame_off = b->d_frame_off; S.B = b->B; S.max_frames = b->max_frames; S.run_blocks = b->synth_run; S.wg_tab = b->d_syn_wg; S.n_wg = b->n_syn_wg;
+    SynthLaunch S = synth_launch(e->plan, b);
     S.amp = e->mag; S.ph = e->P; S.out = e->gy; S.pstride = b->pstride;
     run_synth(S, e->cfg.dsp_path, st);
     LAUNCHCHK();
     launch_oob_residual(audio, b->d_in_off, e->pmaxA, b->d_pc_in, b->pstride, e->gy, b->d_frame_off, e->oob, b->B,
                         b->max_frames, st);
     LAUNCHCHK();
-    const float ratio = (float)pow(10.0, -(double)e->cfg.tolerance_db / 20.0);
-    launch_embed_prepare(e->mag, e->coef, e->lo, e->hi, e->mom, e->vel, e->best, e->c0, ratio, (size_t)b->NF * e->plan->dev.stride, st);
+    launch_embed_prepare(e->mag, e->coef, e->lo, e->hi, e->mom, e->vel, e->best, e->c0, box_ratio(e->cfg),
+                         (size_t)b->NF * e->plan->dev.stride, st);
     LAUNCHCHK();
     return embed_begin_state(e, target, st);
 }
@@ -2623,16 +2511,13 @@ static ResampleLaunch pv_speed_launch(const aware_embed* e, const LoopChainState
 }
 static void pv_stage_forward(const aware_embed* e, const LoopChainState& la, float* tmp, hipStream_t st) {
     const aware_batch* b = e->b;
-    AnalysisLaunch L;
-    L.plan = e->plan->dev; L.frame_off = b->d_frame_off; L.B = b->B; L.max_frames = b->max_frames; L.run_frames = b->an_run; L.wg_tab = b->d_an_wg; L.n_wg = b->n_an_wg;
-    L.sig = la.u; L.sig_off = b->d_out_off; L.sig_len = b->d_out_len; L.pcount = b->d_pc_syn; L.pstride = b->pstride;
+    AnalysisLaunch L = analysis_launch(e->plan, b, la.u, true);
     L.full = la.pvS; L.gate = la.gate;
     launch_analysis(L, st);
     PvLaunch P = pv_launch(e, la, 0);
     P.spec = la.pvS; P.out = la.pvY;
     launch_pv_frames(P, 0, st);
-    SynthLaunch S;
-    S.plan = e->plan->dev; S.frame_off = b->d_frame_off; S.B = b->B; S.max_frames = b->max_frames; S.run_blocks = b->synth_run; S.wg_tab = b->d_syn_wg; S.n_wg = b->n_syn_wg;
+    SynthLaunch S = synth_launch(e->plan, b);
     S.full = la.pvY; S.out = tmp; S.pstride = b->pstride; S.gate = la.gate;
     launch_synth(S, st);
     launch_pv_idle(P, la.u, tmp, st);
@@ -2643,16 +2528,13 @@ static void pv_stage_forward(const aware_embed* e, const LoopChainState& la, flo
 static void pv_stage_backward(const aware_embed* e, const LoopChainState& la, int step_back, hipStream_t st) {
     const aware_batch* b = e->b;
     launch_speed_change(pv_speed_launch(e, la, la.u, e->gy, 1, step_back), st);
-    AnalysisLaunch L;
-    L.plan = e->plan->dev; L.frame_off = b->d_frame_off; L.B = b->B; L.max_frames = b->max_frames; L.run_frames = b->an_run; L.wg_tab = b->d_an_wg; L.n_wg = b->n_an_wg;
-    L.sig = e->gy; L.sig_off = b->d_out_off; L.sig_len = b->d_out_len; L.pcount = b->d_pc_syn; L.pstride = b->pstride;
+    AnalysisLaunch L = analysis_launch(e->plan, b, e->gy, true);
     L.full = la.pvY; L.adjoint = 1; L.gate = la.gate;
     launch_analysis(L, st);
     PvLaunch P = pv_launch(e, la, step_back);
     P.spec = la.pvS; P.grad = la.pvY; P.out = la.pvS;
     launch_pv_frames(P, 1, st);
-    SynthLaunch S;
-    S.plan = e->plan->dev; S.frame_off = b->d_frame_off; S.B = b->B; S.max_frames = b->max_frames; S.run_blocks = b->synth_run; S.wg_tab = b->d_syn_wg; S.n_wg = b->n_syn_wg;
+    SynthLaunch S = synth_launch(e->plan, b);
     S.full = la.pvS; S.out = e->gy; S.adjoint = 1; S.pstride = b->pstride; S.gate = la.gate;
     S.sig_off = b->d_out_off; S.sig_len = b->d_out_len;
     launch_synth(S, st);
@@ -2766,8 +2648,7 @@ static int embed_iteration(aware_embed* e, hipStream_t st, int do_step, float* g
     const aware_batch* b = e->b;
     const aware_detector* d = e->det;
     // :99-103  scatter + Assembler + ISTFT  (out-of-band part is the constant `oob`)
-    SynthLaunch S;
-    S.plan = e->plan->dev; S.frame_off = b->d_frame_off; S.B = b->B; S.max_frames = b->max_frames; S.run_blocks = b->synth_run; S.wg_tab = b->d_syn_wg; S.n_wg = b->n_syn_wg;
+    SynthLaunch S = synth_launch(e->plan, b);
     S.amp = e->coef; S.ph = e->P; S.out = e->yraw; S.add = e->oob; S.pmax = e->pmaxY; S.pstride = b->pstride;
     S.c0 = e->pl1 ? e->c0 : nullptr; S.pl1 = e->pl1;
     const int dsp = e->cfg.dsp_path;
@@ -2778,10 +2659,8 @@ static int embed_iteration(aware_embed* e, hipStream_t st, int do_step, float* g
         LAUNCHCHK(); PROF(K_MISC);
     }
     // normalise x2 + STFT + |.| on the band (:104 zeroes the rest, so it is never computed)
-    AnalysisLaunch L;
-    L.plan = e->plan->dev; L.frame_off = b->d_frame_off; L.B = b->B; L.max_frames = b->max_frames; L.run_frames = b->an_run; L.wg_tab = b->d_an_wg; L.n_wg = b->n_an_wg;
-    L.sig = e->yraw; L.sig_off = b->d_out_off; L.sig_len = b->d_out_len;
-    L.pmax = e->pmaxY; L.pcount = b->d_pc_syn; L.pstride = b->pstride; L.double_norm = 1;
+    AnalysisLaunch L = analysis_launch(e->plan, b, e->yraw, true);
+    L.pmax = e->pmaxY; L.double_norm = 1;
     // attack-aware embedding (EXTENSION): the chain turns the normalised synthesis into z; the analysis reads z
     const bool attacked = e->la.n > 0 || e->mix_n > 0;
     LoopAttackLaunch A, MA[kMaxLoopChains], AC;
@@ -2822,20 +2701,13 @@ static int embed_iteration(aware_embed* e, hipStream_t st, int do_step, float* g
     run_analysis(L, dsp, st);
     LAUNCHCHK(); PROF(K_ANALYSIS);
     // :107 detector forward, :109 loss, :120-122 best tracking, :111 backward through the detector
-    DetGradCtx G;
-    G.target = e->target; G.loss_kind = e->cfg.loss;
-    G.loss = e->loss; G.d1 = e->d1; G.d2 = e->d2; G.gmag = e->gmag; G.loss_add = e->l1term;
-    G.step = do_step ? e->step : nullptr;               // the read-out kernel advances the step counter
-    // aware_embed_gradient (do_step == 0) leaves the best-loss bookkeeping alone: the reference snapshots only
-    // inside the optimiser loop (multibit_embedder.py:120-122)
-    G.best_loss = do_step ? e->best_loss : nullptr;
-    G.improved = do_step ? e->improved : nullptr;
+    DetGradCtx G = loop_grad_ctx(e, do_step);
+    G.loss_add = e->l1term;
     const DetPlan p = det_plan(d, b, e->cfg.conv_pipe, e->cfg.readout, false, mel_fold, mel_taps, e->cfg.conv_tile);
     int rc = det_forward_backward(d, b, p, e->mag, e->db, G, st);
     if (rc) return rc;
     // backward through |.|, STFT, reflect padding
-    SynthLaunch SA;
-    SA.plan = e->plan->dev; SA.frame_off = b->d_frame_off; SA.B = b->B; SA.max_frames = b->max_frames; SA.run_blocks = b->synth_run; SA.wg_tab = b->d_syn_wg; SA.n_wg = b->n_syn_wg;
+    SynthLaunch SA = synth_launch(e->plan, b);
     SA.amp = e->gmag; SA.ph = e->U; SA.out = e->gy; SA.adjoint = 1; SA.yraw = e->yraw; SA.pmax_in = e->pmaxY;
     SA.pcount = b->d_pc_syn; SA.pdot = e->pdot; SA.pstride = b->pstride; SA.gpad = e->gpad;
     if (mel_taps) { SA.dmel = e->db.xm; SA.melw = d->melw; SA.melm = d->melm; }
@@ -2860,11 +2732,8 @@ static int embed_iteration(aware_embed* e, hipStream_t st, int do_step, float* g
         LAUNCHCHK(); PROF(K_MISC);
     }
     // backward through the normalisers, ISTFT and the assembler; :112-117 NAdam + clamp
-    AnalysisLaunch LA;
-    LA.plan = e->plan->dev; LA.frame_off = b->d_frame_off; LA.B = b->B; LA.max_frames = b->max_frames; LA.run_frames = b->an_run; LA.wg_tab = b->d_an_wg; LA.n_wg = b->n_an_wg;
-    LA.sig = e->gy; LA.sig_off = b->d_out_off; LA.sig_len = b->d_out_len;
-    LA.pmax = e->pmaxY; LA.pcount = b->d_pc_syn; LA.pstride = b->pstride;
-    LA.adjoint = 1; LA.yraw = e->yraw; LA.pdot = e->pdot; LA.phasor = e->P;
+    AnalysisLaunch LA = analysis_launch(e->plan, b, e->gy, true);
+    LA.pmax = e->pmaxY; LA.adjoint = 1; LA.yraw = e->yraw; LA.pdot = e->pdot; LA.phasor = e->P;
     LA.coef = e->coef; LA.mom = e->mom; LA.vel = e->vel; LA.lo = e->lo; LA.hi = e->hi; LA.best = e->best;
     LA.improved = e->improved; LA.sched = e->sched; LA.sched_len = e->cfg.num_iterations + 1; LA.step = e->step;
     // (an optimiser / schedule set by aware_embed_set_optimizer steps in its own launch below: the adjoint then only
@@ -2872,18 +2741,13 @@ static int embed_iteration(aware_embed* e, hipStream_t st, int do_step, float* g
     const bool own_step = do_step && e->opt.active;
     LA.grad_out = own_step ? e->gmag : grad_out; LA.do_step = own_step ? 0 : do_step;
     memcpy(LA.hyp, e->hyp, sizeof(LA.hyp));
-    LA.gpad = e->gpad; LA.c0 = e->c0; LA.box_ratio = (float)pow(10.0, -(double)e->cfg.tolerance_db / 20.0);
+    LA.gpad = e->gpad; LA.c0 = e->c0; LA.box_ratio = box_ratio(e->cfg);
     LA.l1_weight = e->pl1 ? e->cfg.l1_weight : 0.f;
     if (attacked) { LA.pdot = e->la.pdot; LA.gpad = e->la.gpad0; }
     run_analysis(LA, dsp, st);
     LAUNCHCHK(); PROF(K_ANALYSIS_ADJ);
     if (own_step) {
-        const auto& o = e->opt;
-        launch_opt_rows(o.kind, e->coef, e->gmag, e->mom, e->vel, e->c0, LA.box_ratio, e->best, e->improved, b->d_frame_off, b->B,
-                        b->NF, o.d_tab, e->cfg.num_iterations, e->step, o.plateau ? o.d_lr : nullptr, o.wd, o.hyp,
-                        e->plan->dev.nband, e->plan->dev.stride, st);
-        if (o.plateau)
-            launch_plateau(e->loss, o.d_state, o.d_lr, b->B, o.factor, o.patience, o.threshold, o.min_lr, o.eps, st);
+        own_optimizer_step(e, st);
         LAUNCHCHK(); PROF(K_MISC);
     }
     return AWARE_OK;
@@ -2979,8 +2843,7 @@ extern "C" int aware_embed_finish(aware_embed* e, const float* rescale, float* o
         LAUNCHCHK();
         return AWARE_OK;
     }
-    SynthLaunch S;
-    S.plan = e->plan->dev; S.frame_off = b->d_frame_off; S.B = b->B; S.max_frames = b->max_frames; S.run_blocks = b->synth_run; S.wg_tab = b->d_syn_wg; S.n_wg = b->n_syn_wg;
+    SynthLaunch S = synth_launch(e->plan, b);
     S.amp = e->best; S.ph = e->P; S.out = e->yraw; S.add = e->oob; S.pmax = e->pmaxY; S.pstride = b->pstride;
     run_synth(S, e->cfg.dsp_path, st);
     LAUNCHCHK();
@@ -3124,7 +2987,7 @@ extern "C" int aware_stoi_create(aware_stoi_plan** out) {
     if (!out) return AWARE_E_BADARG;
     const double PI = 3.14159265358979323846;
     const int M = kStoiFrame, N = 2 * M;
-    aware_stoi_plan* p = new aware_stoi_plan();
+    Building<aware_stoi_plan, aware_stoi_destroy> p(new aware_stoi_plan());
     stoi_band_edges(p->band_lo, p->band_hi);
     // device image: th [M/2] cf, twN [M + 1 -> M + 2] cf, window [256] f32, bands [32] int
     std::vector<float> h(M + 2 * (M + 2) + kStoiFrame + 2 * kStoiRow, 0.f);
@@ -3149,8 +3012,6 @@ extern "C" int aware_stoi_create(aware_stoi_plan** out) {
     if (hipMalloc(&p->mem, h.size() * sizeof(float)) != hipSuccess ||
         hipMemcpy(p->mem, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
         g_last_err = "aware_stoi_create: device tables";
-        if (p->mem) (void)hipFree(p->mem);
-        delete p;
         return AWARE_E_HIP;
     }
     float* d = (float*)p->mem;
@@ -3158,7 +3019,7 @@ extern "C" int aware_stoi_create(aware_stoi_plan** out) {
     p->tab.twN = (const cf*)(d + M);
     p->tab.window = d + M + 2 * (M + 2);
     p->tab.bands = (const int*)(d + M + 2 * (M + 2) + kStoiFrame);
-    *out = p;
+    *out = p.release();
     return AWARE_OK;
 }
 

@@ -1,6 +1,7 @@
-"""Which synthesis run length a batch selects (no device): the rule of aware_batch_create (csrc/capi.hip) restated, the batches of
-tests/test_gpu_loop_run_lengths.py that select 12, 8 and 6, and the record that every batch of the other loop-chain device
-tests selects 4."""
+"""Which synthesis run length a batch selects (no device): the rule of aware_batch_create (synth_run_for and
+run_cuts_short_segments, csrc/batch_layout.hpp) restated, the batches of tests/test_gpu_loop_run_lengths.py that select 12, 8
+and 6, and the record that every batch of the other loop-chain device tests selects 4.
+tests/test_batch_layout_host.py holds the restatement against the C rule itself."""
 import importlib
 
 import pytest
