@@ -3,91 +3,20 @@ against the torch restatement aware_amd/embedding/loop_attacks.py::apply_chain c
 
 Run on the MI355X box:  python -m pytest tests/test_gpu_loop_attacks.py -m gpu -q -s"""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 import torch
-import yaml
 
-from conftest import ROOT, make_clip
+from conftest import make_clip
+from loop_support import LA, NOISE10, O, SUP, attacked, check_first_gradient, graph_replay_bits, norm2, rt, sampled, session
+from loop_support import synthesis, value_claim_setup
 
 pytestmark = pytest.mark.gpu
 
-NOISE10 = {"kind": "gaussian_noise", "snr_db": 10.0}
 NOISE5 = {"kind": "gaussian_noise", "snr_db": 5.0}
-SUP = {"kind": "sample_suppression", "seconds": 0.3}
 CHAINS = {"noise10": [NOISE10], "noise5": [NOISE5], "suppression": [SUP], "suppression_noise": [SUP, NOISE10],
           "noise_suppression": [NOISE5, SUP]}
-
-
-@pytest.fixture(scope="module")
-def rt():
-    from aware_amd import runtime
-    from aware_amd._lib import require_gpu
-    require_gpu()
-    return runtime
-
-
-@pytest.fixture(scope="module")
-def O():
-    from oracle import aware_oracle
-    return aware_oracle
-
-
-@pytest.fixture(scope="module")
-def LA():
-    from aware_amd.embedding import loop_attacks
-    return loop_attacks
-
-
-_PLANS, _DETS = {}, {}
-
-
-def plan_for(rt, band=(32, 256)):
-    if band not in _PLANS:
-        _PLANS[band] = rt.Plan(band_bins=band)
-    return _PLANS[band]
-
-
-def det_for(rt, O, band=(32, 256)):
-    if band not in _DETS:
-        ws, bs = O.detector_weights()
-        _DETS[band] = rt.DetectorWeights(plan_for(rt, band), O.mel_filter_bank(), [w.numpy() for w in ws], [b.numpy() for b in bs])
-    return _DETS[band]
-
-
-def session(rt, O, lengths, seeds, chain=None, attack_seeds=None, band=(32, 256), **kw):
-    pairs = [make_clip(s, n) for s, n in zip(seeds, lengths)]
-    wm = np.stack([O.bits_to_bipolar(p[1]) for p in pairs]).astype(np.float32)
-    batch = rt.Batch(lengths)
-    sess = rt.EmbedSession(plan_for(rt, band), det_for(rt, O, band), batch, **kw)
-    if chain is not None:
-        sess.set_loop_attacks(chain, attack_seeds if attack_seeds is not None else list(range(len(lengths))))
-    sess.begin(batch.pack([p[0] for p in pairs]), torch.from_numpy(wm).cuda())
-    return sess, batch, pairs, wm
-
-
-def norm2(y):
-    """N(N(y)) as the kernels apply it in front of the chain."""
-    y = y / (y.abs().max() + 1e-8)
-    return y / (y.abs().max() + 1e-8)
-
-
-def synthesis(sess, batch):
-    y = sess._view(9, (batch.total_out,)).cpu()
-    return [y[o:o + n] for o, n in zip(batch.out_offsets, batch.out_lengths)]
-
-
-def attacked(sess, batch):
-    z = sess.attacked.cpu()
-    return [z[o:o + n] for o, n in zip(batch.out_offsets, batch.out_lengths)]
-
-
-def sampled(sess, batch, sample=None):
-    """(b, buffer 9, buffer 12) of every clip, or of the clips `sample` names only (a batch whose other clips are filler)."""
-    ys, zs = synthesis(sess, batch), attacked(sess, batch)
-    return [(b, ys[b], zs[b]) for b in (range(batch.B) if sample is None else sample)]
 
 
 # ---- 4. forward ---------------------------------------------------------------------------------------------------------------
@@ -153,49 +82,6 @@ def test_step_0_matches_the_device_attacks(rt, O, LA, lengths):
 
 
 # ---- 5. first gradient ----------------------------------------------------------------------------------------------------------
-def attacked_oracle(O, LA, chain, seed, step=0, band=None):
-    class Attacked(O.Embedder):
-        def recompute_magnitude(self, mag_full, phase):
-            y = O.istft(mag_full * torch.exp(1j * phase))
-            y = y / torch.amax(torch.abs(y) + 1e-8, dim=-1, keepdim=True)
-            y = y / torch.amax(torch.abs(y) + 1e-8, dim=-1, keepdim=True)
-            y = LA.apply_chain(y, chain, [seed], step)
-            y = y / torch.amax(torch.abs(y) + 1e-8, dim=-1, keepdim=True)
-            y = y / torch.amax(torch.abs(y) + 1e-8, dim=-1, keepdim=True)
-            return torch.abs(O.stft(y)), y
-    emb = Attacked()
-    if band is not None:
-        emb.band, emb.nonband = O.band_indices(bands=(band[0] * 15.625, band[1] * 15.625))
-    return emb
-
-
-def check_first_gradient(rt, O, LA, chain, lengths, band=(32, 256), **kw):
-    from test_gpu_kernels import _min_kink_distance
-    clip_seeds = list(range(40, 40 + len(lengths)))
-    seeds = [5 + 2 * i for i in range(len(lengths))]
-    sess, batch, pairs, wm = session(rt, O, lengths, clip_seeds, chain, seeds, band=band, use_graph=False, **kw)
-    g = sess.gradient()
-    torch.cuda.synchronize()
-    g = g.cpu()
-    loss, pred = sess.loss.cpu().numpy(), sess.pred.cpu().numpy()
-    nb = band[1] - band[0] + 1
-    for i, (clip, _) in enumerate(pairs):
-        emb = attacked_oracle(O, LA, chain, seeds[i], 0, None if band == (32, 256) else band)
-        mag0, phase = emb.analyse(torch.from_numpy(clip)[None])
-        c0 = mag0[:, emb.band].clone().requires_grad_(True)
-        l, p = emb.forward_loss(c0, mag0, phase, torch.from_numpy(wm[i])[None])
-        l.sum().backward()
-        ref = c0.grad[0]
-        mine = g[batch.frame_offsets[i]: batch.frame_offsets[i + 1], :nb].T
-        rel = (mine - ref).norm().item() / ref.norm().item()
-        kink = _min_kink_distance(emb, mag0, phase)
-        lerr, perr = abs(loss[i] - float(l.detach())), float(np.abs(pred[i] - p[0].detach().numpy()).max())
-        print(f"{kw} band {band} clip {i} (n = {lengths[i]}): loss err {lerr:.1e}, pred err {perr:.1e}, "
-              f"gradient rel L2 {rel:.2e}, nearest LeakyReLU kink {kink:.1e}")
-        assert lerr < 1e-5 and perr < 1e-5, (i, lerr, perr)
-        assert rel < (2e-5 if kink > 2e-6 else 2e-2), (i, rel, kink)
-
-
 @pytest.mark.parametrize("name", ["noise10", "suppression", "suppression_noise", "noise_suppression"])
 @pytest.mark.parametrize("dsp_path", ["stream", "staged"])
 def test_first_gradient(rt, O, LA, name, dsp_path):
@@ -224,21 +110,8 @@ def test_first_gradient_wide_band(rt, O, LA, dsp_path):
 @pytest.mark.parametrize("lengths", [[16000] * 4, [16000, 40000]])
 def test_graph_replay_is_bit_identical_and_redraws(rt, O, lengths):
     chain = [{"kind": "sample_suppression", "seconds": 0.3, "prob": 0.75}, NOISE10]
-    out = []
-    for use_graph in (True, False):
-        sess, batch, _, _ = session(rt, O, lengths, list(range(50, 50 + len(lengths))), chain, num_iterations=40, use_graph=use_graph)
-        zs, losses = [], []
-        sess.iterate(32)
-        for _ in range(8):
-            sess.iterate(1)
-            zs.append(sess.attacked.clone())
-            losses.append(sess.loss.clone())
-        torch.cuda.synchronize()
-        out.append((sess.coef.cpu(), sess.best_coef.cpu(), sess.best_loss.cpu(), torch.stack(losses).cpu(), torch.stack(zs).cpu()))
-        assert int(sess.step.cpu()[0]) == 40
-    for a, b in zip(*out):
-        assert torch.equal(a, b)
-    zs = out[0][4]
+    out, _ = graph_replay_bits(rt, O, chain, lengths)
+    zs = out[4]
     for i in range(7):
         assert float((zs[i + 1] - zs[i]).abs().max()) > 1e-2        # the draw is keyed by the device step counter
 
@@ -323,26 +196,7 @@ def test_value_claim_on_the_device(rt, O, tmp_path):
     (8 seeds per clip) of the noise-aware embedding at most half the plain one's, which is at least 10 %; the same for
     0.5 s zeroed at six starts with sample_suppression(0.5 s, prob 0.75) in the loop."""
     from aware_amd import attacks as A
-    from aware_amd.utils.models import load
-    with open(os.path.join(ROOT, "aware_amd", "cards", "config.yaml")) as f:
-        card = yaml.safe_load(f)
-    pairs = [make_clip(s, 16000) for s in range(4)]
-    clips, bits = [p[0] for p in pairs], np.stack([p[1] for p in pairs])
-    wm = np.stack([O.bits_to_bipolar(b) for b in bits]).astype(np.float32)
-
-    def embed(chain):
-        c = dict(card)
-        if chain:
-            c["loop_attacks"] = chain
-        p = tmp_path / "card.yaml"
-        p.write_text(yaml.safe_dump(c))
-        emb, det = load(str(p))
-        assert emb.loop_attacks == __import__("aware_amd.embedding.loop_attacks", fromlist=["x"]).parse_chain(chain)
-        return [o.cpu().numpy() for o in emb.embed_batch(clips, 16000, wm)], det
-
-    def ber(det, ragged):
-        vals = det.detect_batch(ragged.to_list() if hasattr(ragged, "to_list") else ragged, 16000).cpu().numpy()
-        return 100.0 * float((O.decode_bits(vals) != bits).mean())
+    clips, bits, embed, ber = value_claim_setup(O, tmp_path)
 
     def noise5(det, ys):
         x = rt.Ragged.from_list(ys)

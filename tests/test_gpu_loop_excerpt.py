@@ -9,48 +9,22 @@ clips of 4099, 1025 and 2048 samples, packed back to back so that the second sta
 
 Run on the MI355X box:  python -m pytest tests/test_gpu_loop_excerpt.py -m gpu -q -s"""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 import torch
-import yaml
 
-from conftest import ROOT, make_clip
-from test_gpu_loop_attacks import attacked, norm2, sampled, session, synthesis
-from test_gpu_loop_reverb import CHAIN_BOUND
-from test_gpu_loop_stretch import PARENT_WORKSPACE, ex_entries
-from test_gpu_loop_pv import KINK, oracle_gradient
-from test_gpu_loop_delete import bits_equal, device_x, plus_zero
+from loop_support import CHAIN_BOUND, DS, EV, FB, KINK, LA, LONG, NO, NOISE10, O, PS, PV, RAGGED, RV, SHORT, SP, ST, SU, SUP, XC
+from loop_support import attacked, bits_equal, check_gradient, device_x, does_not_fire_keeps_its_bits, ex_entries
+from loop_support import forward_at_run_length, forward_at_steps_0_2_17, graph_replay_bits, mixture_is_its_chains, norm2
+from loop_support import older_chains_workspace, plus_zero, prob_0_is_the_plain_loop, rt, sampled, session, stereo_round_trip
+from loop_support import synthesis, value_claim_setup
 
 pytestmark = pytest.mark.gpu
 
-SHORT, LONG, RAGGED = [8000] * 2, [16000] * 2, [16000, 8000]
 EX = {"kind": "excerpt", "seconds": [0.1875, 0.625]}
-NOISE10 = {"kind": "gaussian_noise", "snr_db": 10.0}
-SUP = {"kind": "sample_suppression", "seconds": 0.3}
 CHAINS = {"excerpt": [EX], "suppression_excerpt": [SUP, EX], "excerpt_noise": [EX, NOISE10]}
 assert CHAIN_BOUND == 1.13e-6                              # the project's bound for the loop's attacked signal (DESIGN 16)
-
-
-@pytest.fixture(scope="module")
-def rt():
-    from aware_amd import runtime
-    from aware_amd._lib import require_gpu
-    require_gpu()
-    return runtime
-
-
-@pytest.fixture(scope="module")
-def O():
-    from oracle import aware_oracle
-    return aware_oracle
-
-
-@pytest.fixture(scope="module")
-def LA():
-    from aware_amd.embedding import loop_attacks
-    return loop_attacks
 
 
 def tile(x, start, L):
@@ -169,16 +143,7 @@ def test_forward_matches_the_restatement(rt, O, LA, lengths, name):
     x = N(N(buffer 9)) in the device's rounding.  With noise behind it: within CHAIN_BOUND = 1.13e-6 of the peak of the float64
     restatement (all chains are held to that as well).  The draws differ from step to step."""
     chain = LA.parse_chain(CHAINS[name])
-    seeds = [11 + 3 * i for i in range(len(lengths))]
-    sess, batch, _, _ = session(rt, O, lengths, list(range(20, 20 + len(lengths))), chain, seeds, num_iterations=20)
-    assert sorted(batch.out_lengths)[0] in (7936, 15872)
-    sess.gradient()
-    check_forward(LA, sess, batch, chain, seeds, 0, name)
-    sess.iterate(3)
-    check_forward(LA, sess, batch, chain, seeds, 2, name)
-    sess.iterate(15)
-    assert int(sess.step.cpu()[0]) == 18
-    check_forward(LA, sess, batch, chain, seeds, 17, name)
+    batch, seeds = forward_at_steps_0_2_17(rt, O, LA, chain, lengths, name, check_forward)
     if batch.out_lengths[0] == 15872:                                                       # every excerpt is shorter than this clip
         assert len({drawn(LA, chain, seeds[0], s, 15872)[1:] for s in (0, 2, 17)}) == 3
         assert all(drawn(LA, chain, seeds[0], s, 15872)[2] < 15872 for s in (0, 2, 17))
@@ -215,106 +180,44 @@ def test_a_clip_shorter_than_the_excerpt_is_left_alone(rt, O, LA):
 # 82 as the second at 4.0e-6).  The draws at step 0: alone (start, L) = (1368, 3691) and (2588, 3516); between, entry 1,
 # (5547, 9022) and (2841, 6314): every position of the long clips' adjoint has two to five terms.
 SEED0, SEED0_BETWEEN = 81, 80
-
-
-def check_gradient(rt, O, LA, chain, lengths, clip_seed0, **kw):
-    """aware_embed_gradient against autograd over the float64 restatement composed with the oracle's loop body, with the rule
-    and the bounds of test_gpu_loop_pv.py: relative L2 per clip within four times the float32 composition's own distance from
-    the float64 one and at least 2e-5; loss and prediction the same way, at least 1e-6; no clip closer than KINK to a LeakyReLU
-    kink in either precision."""
-    clip_seeds = list(range(clip_seed0, clip_seed0 + len(lengths)))
-    seeds = [5 + 2 * i for i in range(len(lengths))]
-    sess, batch, pairs, wm = session(rt, O, lengths, clip_seeds, chain, seeds, use_graph=False, **kw)
-    g = sess.gradient()
-    torch.cuda.synchronize()
-    g = g.cpu()
-    loss, pred = sess.loss.cpu().numpy(), sess.pred.cpu().numpy()
-    for i, (clip, _) in enumerate(pairs):
-        ref, l, p, kink = oracle_gradient(O, LA, chain, seeds[i], clip, wm[i], torch.float64)
-        r32, l32, p32, kink32 = oracle_gradient(O, LA, chain, seeds[i], clip, wm[i], torch.float32)
-        floor = float((r32 - ref).norm() / ref.norm())
-        lfloor, pfloor = abs(l32 - l), float(np.abs(p32 - p).max())
-        mine = g[batch.frame_offsets[i]: batch.frame_offsets[i + 1], :225].T.double()
-        rel = float((mine - ref).norm() / ref.norm())
-        lerr, perr = abs(loss[i] - l), float(np.abs(pred[i] - p).max())
-        on, start, L = drawn(LA, chain, seeds[i], 0, batch.out_lengths[i])
-        print(f"{kw} clip {i} (n = {lengths[i]}, start = {start}, L = {L}): loss err {lerr:.1e} (float32 restatement {lfloor:.1e}), pred err "
-              f"{perr:.1e} ({pfloor:.1e}), gradient rel L2 {rel:.2e} ({floor:.2e}), nearest LeakyReLU kink {kink:.1e} / {kink32:.1e}")
-        assert on and L < batch.out_lengths[i], "the case is to exercise the operator"
-        assert min(kink, kink32) >= KINK, (i, kink, kink32)
-        assert lerr <= max(4 * lfloor, 1e-6) and perr <= max(4 * pfloor, 1e-6), (i, lerr, lfloor, perr, pfloor)
-        assert rel <= max(4 * floor, 2e-5), (i, rel, floor)
+assert KINK == 8e-6
+# the module's pieces of loop_support.check_gradient, which states the rule and its bounds
+GRADIENT = dict(drawn=drawn, describe=lambda d: f"start = {d[1]}, L = {d[2]}", exercised=lambda d, i, ny: d[0] and d[2] < ny)
 
 
 @pytest.mark.parametrize("dsp_path", ["stream", "staged"])
 def test_first_gradient(rt, O, LA, dsp_path):
-    check_gradient(rt, O, LA, [EX], RAGGED, SEED0, dsp_path=dsp_path)
+    check_gradient(rt, O, LA, [EX], RAGGED, SEED0, **GRADIENT, dsp_path=dsp_path)
 
 
 def test_first_gradient_f32_dense(rt, O, LA):
-    check_gradient(rt, O, LA, [EX], RAGGED, SEED0, conv_pipe="f32", mel="dense")
+    check_gradient(rt, O, LA, [EX], RAGGED, SEED0, **GRADIENT, conv_pipe="f32", mel="dense")
 
 
 @pytest.mark.parametrize("dsp_path", ["stream", "staged"])
 def test_first_gradient_between_other_entries(rt, O, LA, dsp_path):
     """A suppression in front and noise behind: the stages on both sides."""
-    check_gradient(rt, O, LA, [SUP, EX, NOISE10], LONG, SEED0_BETWEEN, dsp_path=dsp_path)
+    check_gradient(rt, O, LA, [SUP, EX, NOISE10], LONG, SEED0_BETWEEN, **GRADIENT, dsp_path=dsp_path)
 
 
 # ---- 4. per-clip and replay behaviour ---------------------------------------------------------------------------------------------
 def test_a_clip_that_does_not_fire_keeps_its_bits(rt, O, LA):
     """prob 0.5 on three clips, 8 steps: where the entry does not fire, buffer 12 is N(N(buffer 9)) in the device's rounding,
     bit for bit; where it fires it is the tiling of that.  Both occur."""
-    lengths, seeds = [16000, 8000, 24000], [1, 2, 3]
-    chain = LA.parse_chain([dict(EX, prob=0.5)])
-    sess, batch, _, _ = session(rt, O, lengths, [70, 71, 72], chain, seeds, num_iterations=20)
-    seen = set()
-    for step in range(8):
-        sess.iterate(1)
-        torch.cuda.synchronize()
-        for b, (y, z) in enumerate(zip(synthesis(sess, batch), attacked(sess, batch))):
-            on, start, L = drawn(LA, chain, seeds[b], step, len(y))
-            x = device_x(y.numpy())
-            assert bits_equal(z.numpy(), tile(x, start, L) if on else x), (step, b, on)
-            seen.add(on and L < len(y))
-    assert seen == {False, True}
+    does_not_fire_keeps_its_bits(rt, O, LA, EX, drawn, apply=lambda x, z, d: bits_equal(z, tile(x, d[1], d[2])),
+                                 fired=lambda d, ny: d[0] and d[2] < ny)
 
 
 def test_prob_0_is_the_plain_loop(rt, O):
     """An excerpt that never fires against the loop without a chain: coefficients, best coefficients and losses after 20 steps
     and the gradient of step 20, bit for bit, alone and between two older entries that never fire either, on both dsp_paths."""
-    lengths = [8000, 16000, 24000]
-    for dsp_path in ("stream", "staged"):
-        plain, _, _, _ = session(rt, O, lengths, [62, 63, 64], None, num_iterations=21, dsp_path=dsp_path)
-        plain.iterate(20)
-        gp = plain.gradient()
-        for chain in ([dict(EX, prob=0.0)], [dict(SUP, prob=0.0), dict(EX, prob=0.0), dict(NOISE10, prob=0.0)]):
-            att, batch, _, _ = session(rt, O, lengths, [62, 63, 64], chain, num_iterations=21, dsp_path=dsp_path)
-            att.iterate(20)
-            ga = att.gradient()
-            torch.cuda.synchronize()
-            assert torch.equal(plain.coef, att.coef) and torch.equal(plain.best_coef, att.best_coef)
-            assert torch.equal(plain.loss, att.loss) and torch.equal(plain.best_loss, att.best_loss)
-            assert torch.equal(gp, ga)
+    prob_0_is_the_plain_loop(rt, O, ([dict(EX, prob=0.0)], [dict(SUP, prob=0.0), dict(EX, prob=0.0), dict(NOISE10, prob=0.0)]))
 
 
 @pytest.mark.parametrize("lengths", [LONG, RAGGED], ids=["long", "ragged"])
 def test_graph_replay_is_bit_identical_and_redraws(rt, O, LA, lengths):
     chain = LA.parse_chain([dict(EX, prob=0.75), NOISE10])
-    out = []
-    for use_graph in (True, False):
-        sess, batch, _, _ = session(rt, O, lengths, list(range(50, 50 + len(lengths))), chain, num_iterations=40, use_graph=use_graph)
-        zs, losses = [], []
-        sess.iterate(32)
-        for _ in range(8):
-            sess.iterate(1)
-            zs.append(sess.attacked.clone())
-            losses.append(sess.loss.clone())
-        torch.cuda.synchronize()
-        out.append((sess.coef.cpu(), sess.best_coef.cpu(), sess.best_loss.cpu(), torch.stack(losses).cpu(), torch.stack(zs).cpu()))
-        assert int(sess.step.cpu()[0]) == 40
-    for a, b in zip(*out):
-        assert torch.equal(a, b)
+    _, batch = graph_replay_bits(rt, O, chain, lengths)
     # the draws are keyed by the device step counter: both start and L of clip 0 (seed 0) move from step to step
     n0 = batch.out_lengths[0]
     draws = [drawn(LA, chain, 0, s, n0) for s in range(32, 40)]
@@ -339,33 +242,7 @@ def test_a_mixture_is_its_chains(rt, O, LA):
     """A mixture of {excerpt, noise} and {reverberation} at step 0: buffer 14 holds the host's choices, and every clip's buffer 12
     (with buffer 9, loss, prediction and its rows of the coefficient gradient) is bit for bit that of a session that holds only the
     chain the clip drew; the clips of the excerpt chain are within CHAIN_BOUND of the float64 restatement."""
-    from test_gpu_loop_mixture import rows, session as mix_session, span
-    lengths = [16000, 8000, 16000, 8000]
-    mixture = LA.parse_mixture([{"weight": 0.5, "chain": [EX, NOISE10]}, {"weight": 0.5, "chain": [{"kind": "reverberation", "rt60": [0.1, 0.3]}]}])
-    s0 = 0
-    while set(LA.mixture_choices(list(range(s0, s0 + 4)), 0, [0.5, 0.5]).tolist()) != {0, 1}:
-        s0 += 1
-    seeds = list(range(s0, s0 + 4))
-    choice = LA.mixture_choices(seeds, 0, [0.5, 0.5])
-    kw = dict(num_iterations=4)
-    mix, batch = mix_session(rt, O, lengths, seeds, mixture=mixture, **kw)
-    g = mix.gradient()
-    torch.cuda.synchronize()
-    np.testing.assert_array_equal(mix.choices.cpu().numpy(), choice)
-    z, y, loss, pred = mix.attacked.clone(), mix._view(9, (batch.total_out,)).clone(), mix.loss.clone(), mix.pred.clone()
-    for c in (0, 1):
-        one, _ = mix_session(rt, O, lengths, seeds, chain=mixture[c]["chain"], **kw)
-        g1 = one.gradient()
-        torch.cuda.synchronize()
-        y1 = one._view(9, (batch.total_out,))
-        for b in np.flatnonzero(choice == c):
-            assert torch.equal(y[span(batch, b)], y1[span(batch, b)]) and torch.equal(z[span(batch, b)], one.attacked[span(batch, b)]), (b, c)
-            assert torch.equal(loss[b], one.loss[b]) and torch.equal(pred[b], one.pred[b]), (b, c)
-            assert torch.equal(g[rows(batch, b)], g1[rows(batch, b)]) and float(g[rows(batch, b)].abs().max()) > 0.0, (b, c)
-    for b in np.flatnonzero(choice == 0):
-        yb, zb = y[span(batch, b)].cpu(), z[span(batch, b)].cpu()
-        ref = LA.apply_chain(norm2(yb.double())[None], mixture[0]["chain"], [seeds[b]], 0)[0]
-        assert float((zb.double() - ref).abs().max() / ref.abs().max()) < CHAIN_BOUND, b
+    mixture_is_its_chains(rt, O, LA, [EX, NOISE10], [{"kind": "reverberation", "rt60": [0.1, 0.3]}], bound=CHAIN_BOUND)
 
 
 @pytest.mark.parametrize("bname", ["R12", "R8", "R6"])
@@ -374,42 +251,14 @@ def test_forward_at_every_synthesis_run_length(rt, O, LA, bname):
     head clips (18432, 16000, 8000, 24000 and 513 samples) at steps 0 and 2, bit for bit the restatement on N(N(buffer 9)) in the
     device's rounding.  A workgroup's share of a clip then spans up to 3072 samples, which holds a whole period of the shortest
     excerpt and a wrap."""
-    from test_gpu_loop_run_lengths import COMPARED, big_session
-    chain = LA.parse_chain([EX])
-    sess, batch, seeds = big_session(rt, O, bname, "excerpt", chain=chain, num_iterations=4)
-    sess.gradient()
-    check_forward(LA, sess, batch, chain, seeds, 0, f"{bname} excerpt", sample=COMPARED[bname])
-    sess.iterate(3)
-    assert int(sess.step.cpu()[0]) == 3
-    check_forward(LA, sess, batch, chain, seeds, 2, f"{bname} excerpt", sample=COMPARED[bname])
-    z = sess.attacked
-    assert bool(torch.isfinite(z).all()) and float(z.abs().max()) > 0.0
+    forward_at_run_length(rt, O, LA, bname, "excerpt", LA.parse_chain([EX]), check_forward)
 
 
 # ---- 5. workspace and error codes -------------------------------------------------------------------------------------------------
-XC = (10, 0.75, [3000.0, 10000.0, 0.0, 0.0])
-FB = (9, 0.75, [15.0, 2458.0, 15565.0, 1638.0])
-DS = (7, 0.75, [1.0, 512.0, 0.0])
-PV = (6, 0.9, [-9830.0, 9830.0, -5435.0, 5930.0])
-PS = (5, 0.75, [-3678.0, 3896.0])
-ST = (4, 0.75, [-9830.0, 9830.0])
-SP = (3, 0.75, [-3678.0, 3896.0])
-RV = (2, 1.0, [1600.0, 8000.0, -3.0])
-NO = (0, 1.0, [10.0])
-SU = (1, 1.0, [4800.0])
-EV = (8, 0.75, [800.0, 8000.0, 0.25])
-
-
 def test_workspace_bytes(rt, O):
     """The seven older chains need what they needed; a chain with the kind needs what the same chain with a deletion in its place
     needs; a refused chain is sized by the older kind, as before."""
-    sess, batch, _, _ = session(rt, O, RAGGED, [64, 65], None, num_iterations=20, use_graph=False)
-    lib = sess.lib
-    size = lambda ent: lib.aware_embed_loop_attack_workspace_bytes_ex(batch.h, ex_entries(ent), len(ent))
-    nb = {name: size(ent)
-          for name, ent in (("noise", [NO]), ("noise_suppression", [NO, SU]), ("reverb", [RV]), ("suppression_reverb_noise", [SU, RV, NO]),
-                            ("speed", [SP]), ("noise_speed", [NO, SP]), ("four", [NO, SU, SP, NO]))}
-    assert nb == PARENT_WORKSPACE
+    size, nb, _ = older_chains_workspace(rt, O)
     for with_xc, with_ds in (([XC], [DS]), ([NO, XC], [NO, DS]), ([NO, SU, XC, NO], [NO, SU, DS, NO]), ([EV, XC, EV], [EV, DS, EV])):
         assert size(with_xc) == size(with_ds) > nb["noise"]
     for other in (RV, SP, ST, PS, PV, DS, FB):
@@ -476,23 +325,7 @@ def test_entry_point_error_codes(rt, O):
 def test_stereo_service_round_trip_with_the_card_key(rt, tmp_path):
     """load() of a card with the excerpt in loop_attacks, then embed_watermark / detect_watermark on a stereo clip: every
     channel carries the payload."""
-    from aware_amd.embedding.loop_attacks import parse_chain
-    from aware_amd.service import detect_watermark, embed_watermark
-    from aware_amd.utils.models import load
-    with open(os.path.join(ROOT, "aware_amd", "cards", "config.yaml")) as f:
-        card = yaml.safe_load(f)
-    card["loop_attacks"] = yaml.safe_load("[{kind: excerpt, seconds: [0.1875, 0.625], prob: 0.75}]")
-    p = tmp_path / "card.yaml"
-    p.write_text(yaml.safe_dump(card))
-    emb, det = load(str(p))
-    assert emb.loop_attacks == parse_chain([dict(EX, prob=0.75)])
-    bits = np.random.default_rng(29).integers(0, 2, 20).astype(np.int32)
-    stereo = np.column_stack([make_clip(51, 16000)[0], make_clip(52, 16000)[0]])
-    out = embed_watermark(stereo, 16000, bits, emb)
-    assert out.shape[1] == 2 and np.isfinite(out).all()
-    got = detect_watermark(out, 16000, det)
-    for ch in (got if isinstance(got, (list, tuple)) else [got]):
-        np.testing.assert_array_equal(np.asarray(ch).reshape(-1)[:20].astype(np.int32), bits)
+    stereo_round_trip(tmp_path, "[{kind: excerpt, seconds: [0.1875, 0.625], prob: 0.75}]", dict(EX, prob=0.75))
 
 
 # ---- 7. the value claim on the device ---------------------------------------------------------------------------------------------
@@ -500,30 +333,10 @@ def test_value_claim_on_the_device(rt, O, tmp_path):
     """The host test's two embeddings (four 1 s clips, seeds 0..3, 400 steps) through AWAREEmbedder(loop_attacks=...) from an
     edited card, sliced on the host at the host test's points with its bounds: clean 0 % both, the plain mean over the slices of
     8000 and 6000 samples at least 10 %, the aware mean at most half of it.  Figures: DESIGN.md section 32."""
-    from aware_amd.utils.models import load
-    from aware_amd.embedding.loop_attacks import parse_chain
     from aware_amd.attacks import Excerpt
     from test_loop_excerpt_host import AWARE_CHAIN, STARTS
     from test_loop_gain_host import snr_db
-    with open(os.path.join(ROOT, "aware_amd", "cards", "config.yaml")) as f:
-        card = yaml.safe_load(f)
-    pairs = [make_clip(s, 16000) for s in range(4)]
-    clips, bits = [p[0] for p in pairs], np.stack([p[1] for p in pairs])
-    wm = np.stack([O.bits_to_bipolar(b) for b in bits]).astype(np.float32)
-
-    def embed(chain):
-        c = dict(card)
-        if chain:
-            c["loop_attacks"] = chain
-        p = tmp_path / "card.yaml"
-        p.write_text(yaml.safe_dump(c))
-        emb, det = load(str(p))
-        assert emb.loop_attacks == parse_chain(chain)
-        return np.stack([o.cpu().numpy() for o in emb.embed_batch(clips, 16000, wm)]), det
-
-    def ber(det, ys):
-        vals = det.detect_batch(list(ys), 16000).cpu().numpy()
-        return 100.0 * float((O.decode_bits(vals) != bits).mean())
+    clips, bits, embed, ber = value_claim_setup(O, tmp_path)
 
     def table(det, y):
         n = y.shape[-1]
@@ -531,6 +344,7 @@ def test_value_claim_on_the_device(rt, O, tmp_path):
 
     y0, det = embed(None)
     y1, _ = embed(AWARE_CHAIN)
+    y0, y1 = np.stack(y0), np.stack(y1)
     clean0, clean1 = ber(det, y0), ber(det, y1)
     t0, t1 = table(det, y0), table(det, y1)
     for L in t0:

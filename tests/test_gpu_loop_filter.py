@@ -13,51 +13,26 @@ one synthesis run per clip) and [16000, 8000, 513] (the shortest clip the loop t
 Run on the MI355X box:  python -m pytest tests/test_gpu_loop_filter.py -m gpu -q -s"""
 import contextlib
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 import torch
-import yaml
 
-from conftest import ROOT, make_clip
-from test_gpu_loop_attacks import attacked, norm2, sampled, session, synthesis
-from test_gpu_loop_reverb import CHAIN_BOUND
-from test_gpu_loop_stretch import PARENT_WORKSPACE, ex_entries
-from test_gpu_loop_pv import KINK, oracle_gradient
-from test_gpu_loop_delete import bits_equal, device_x
+from loop_support import CHAIN_BOUND, DS, EV, FB, KINK, LA, LONG, NO, NOISE10, O, PS, PV, RAGGED, RV, SHORT, SP, ST, SU
+from loop_support import bits_equal, check_gradient, device_x, does_not_fire_keeps_its_bits, ex_entries, forward_at_steps_0_2_17
+from loop_support import graph_replay_bits, mixture_is_its_chains, norm2, older_chains_workspace, prob_0_is_the_plain_loop, rt
+from loop_support import sampled, session, stereo_round_trip, value_claim_setup
 
 pytestmark = pytest.mark.gpu
 
-SHORT, LONG, RAGGED, TINY = [8000] * 2, [16000] * 2, [16000, 8000], [16000, 8000, 513]
+TINY = [16000, 8000, 513]
 ALL4 = ["lowpass", "highpass", "bandpass", "bandstop"]
 BF = {"kind": "band_filter", "response": ALL4, "freq": [600.0, 3800.0], "min_width": 400.0}
-NOISE10 = {"kind": "gaussian_noise", "snr_db": 10.0}
-SUP = {"kind": "sample_suppression", "seconds": 0.02}
+SUP = {"kind": "sample_suppression", "seconds": 0.02}      # this module's own: short enough for the 513-sample clip of TINY
 CHAINS = {"filter": [BF], "suppression_filter": [SUP, BF], "noise_filter": [NOISE10, BF], "filter_noise": [BF, NOISE10]}
 W = 1638
 TILE = 4096                                                 # outputs per workgroup of the stand-alone grid (kFbTile)
 assert CHAIN_BOUND == 1.13e-6
-
-
-@pytest.fixture(scope="module")
-def rt():
-    from aware_amd import runtime
-    from aware_amd._lib import require_gpu
-    require_gpu()
-    return runtime
-
-
-@pytest.fixture(scope="module")
-def O():
-    from oracle import aware_oracle
-    return aware_oracle
-
-
-@pytest.fixture(scope="module")
-def LA():
-    from aware_amd.embedding import loop_attacks
-    return loop_attacks
 
 
 _TAPS = {}
@@ -201,16 +176,7 @@ def check_forward(rt, LA, sess, batch, chain, seeds, step, tag, sample=None):
 @pytest.mark.parametrize("lengths", [SHORT, LONG, TINY], ids=["short", "long", "tiny"])
 def test_forward_matches_the_restatement(rt, O, LA, lengths, name):
     chain = LA.parse_chain(CHAINS[name])
-    seeds = [11 + 3 * i for i in range(len(lengths))]
-    sess, batch, _, _ = session(rt, O, lengths, list(range(20, 20 + len(lengths))), chain, seeds, num_iterations=20)
-    assert sorted(batch.out_lengths)[0] in (512, 7936, 15872)
-    sess.gradient()
-    check_forward(rt, LA, sess, batch, chain, seeds, 0, name)
-    sess.iterate(3)
-    check_forward(rt, LA, sess, batch, chain, seeds, 2, name)
-    sess.iterate(15)
-    assert int(sess.step.cpu()[0]) == 18
-    check_forward(rt, LA, sess, batch, chain, seeds, 17, name)
+    batch, seeds = forward_at_steps_0_2_17(rt, O, LA, chain, lengths, name, lambda *a: check_forward(rt, *a), shortest=(512, 7936, 15872))
     assert len({drawn(LA, chain, seeds[0], s)[1:] for s in (0, 2, 17)}) == 3
 
 
@@ -220,109 +186,47 @@ def test_forward_matches_the_restatement(rt, O, LA, lengths, name):
 # (80 as the long clip was at 1.2e-6, 82 at 4.1e-6).  Two long clips between a suppression and noise: seeds 89 and 90, 3.1e-5 /
 # 5.6e-5 (87 as the first was at 2.2e-6, 85 as the second at 1.3e-7).
 SEED0, SEED0_BETWEEN = 86, 89
-
-
-def check_gradient(rt, O, LA, chain, lengths, clip_seed0, **kw):
-    """aware_embed_gradient against autograd over the float64 restatement composed with the oracle's loop body, with the rule and
-    the bounds of test_gpu_loop_pv.py: relative L2 per clip within four times the float32 composition's own distance from the
-    float64 one and at least 2e-5; loss and prediction the same way, at least 1e-6; no clip closer than KINK to a LeakyReLU kink
-    in either precision."""
-    clip_seeds = list(range(clip_seed0, clip_seed0 + len(lengths)))
-    seeds = [5 + 2 * i for i in range(len(lengths))]
-    sess, batch, pairs, wm = session(rt, O, lengths, clip_seeds, chain, seeds, use_graph=False, **kw)
-    g = sess.gradient()
-    torch.cuda.synchronize()
-    g = g.cpu()
-    loss, pred = sess.loss.cpu().numpy(), sess.pred.cpu().numpy()
-    for i, (clip, _) in enumerate(pairs):
-        ref, l, p, kink = oracle_gradient(O, LA, chain, seeds[i], clip, wm[i], torch.float64)
-        r32, l32, p32, kink32 = oracle_gradient(O, LA, chain, seeds[i], clip, wm[i], torch.float32)
-        floor = float((r32 - ref).norm() / ref.norm())
-        lfloor, pfloor = abs(l32 - l), float(np.abs(p32 - p).max())
-        mine = g[batch.frame_offsets[i]: batch.frame_offsets[i + 1], :225].T.double()
-        rel = float((mine - ref).norm() / ref.norm())
-        lerr, perr = abs(loss[i] - l), float(np.abs(pred[i] - p).max())
-        on, rs, c1, c2 = drawn(LA, chain, seeds[i], 0)
-        print(f"{kw} clip {i} (n = {lengths[i]}, response {rs}, c1 = {c1}, c2 = {c2}): loss err {lerr:.1e} (float32 restatement {lfloor:.1e}), "
-              f"pred err {perr:.1e} ({pfloor:.1e}), gradient rel L2 {rel:.2e} ({floor:.2e}), nearest LeakyReLU kink {kink:.1e} / {kink32:.1e}")
-        assert on, "the case is to exercise the operator"
-        assert min(kink, kink32) >= KINK, (i, kink, kink32)
-        assert lerr <= max(4 * lfloor, 1e-6) and perr <= max(4 * pfloor, 1e-6), (i, lerr, lfloor, perr, pfloor)
-        assert rel <= max(4 * floor, 2e-5), (i, rel, floor)
+assert KINK == 8e-6
+# the module's pieces of loop_support.check_gradient, which states the rule and its bounds
+GRADIENT = dict(drawn=lambda LA, chain, seed, step, ny: drawn(LA, chain, seed, step), exercised=lambda d, i, ny: d[0],
+                describe=lambda d: f"response {d[1]}, c1 = {d[2]}, c2 = {d[3]}")
 
 
 @pytest.mark.parametrize("dsp_path", ["stream", "staged"])
 def test_first_gradient(rt, O, LA, dsp_path):
-    check_gradient(rt, O, LA, [BF], RAGGED, SEED0, dsp_path=dsp_path)
+    check_gradient(rt, O, LA, [BF], RAGGED, SEED0, **GRADIENT, dsp_path=dsp_path)
 
 
 @pytest.mark.parametrize("dsp_path", ["stream", "staged"])
 def test_first_gradient_between_other_entries(rt, O, LA, dsp_path):
     """A suppression in front and noise behind: the stages on both sides."""
-    check_gradient(rt, O, LA, [SUP, BF, NOISE10], LONG, SEED0_BETWEEN, dsp_path=dsp_path)
+    check_gradient(rt, O, LA, [SUP, BF, NOISE10], LONG, SEED0_BETWEEN, **GRADIENT, dsp_path=dsp_path)
 
 
 # ---- 4. per-clip and replay behaviour ---------------------------------------------------------------------------------------------
 def test_a_clip_that_does_not_fire_keeps_its_bits(rt, O, LA):
     """prob 0.5 on three clips, 8 steps: where the entry does not fire, buffer 12 is N(N(buffer 9)) in the device's rounding, bit
     for bit; where it fires it is the drawn filter of that, to the stand-alone bound.  Both occur."""
-    lengths, seeds = [16000, 8000, 24000], [1, 2, 3]
-    chain = LA.parse_chain([dict(BF, prob=0.5)])
-    sess, batch, _, _ = session(rt, O, lengths, [70, 71, 72], chain, seeds, num_iterations=20)
-    seen = set()
-    for step in range(8):
-        sess.iterate(1)
-        torch.cuda.synchronize()
-        for b, (y, z) in enumerate(zip(synthesis(sess, batch), attacked(sess, batch))):
-            on, rs, c1, c2 = drawn(LA, chain, seeds[b], step)
-            x = device_x(y.numpy())
-            if not on:
-                assert bits_equal(z.numpy(), x), (step, b)
-            else:
-                h = device_taps(rt, rs, c1, c2)
-                ref = np.convolve(x.astype(np.float64), h)[127:127 + len(x)]
-                assert float(np.abs(z.numpy() - ref).max()) <= 2.0 ** -16 * np.abs(h).sum() * float(np.abs(x).max()), (step, b)
-            seen.add(on)
-    assert seen == {False, True}
+    def filtered(x, z, d):
+        h = device_taps(rt, *d[1:])
+        ref = np.convolve(x.astype(np.float64), h)[127:127 + len(x)]
+        return float(np.abs(z - ref).max()) <= 2.0 ** -16 * np.abs(h).sum() * float(np.abs(x).max())
+
+    does_not_fire_keeps_its_bits(rt, O, LA, BF, GRADIENT["drawn"], apply=filtered, fired=lambda d, ny: d[0])
 
 
 def test_prob_0_is_the_plain_loop(rt, O):
     """A filter that never fires against the loop without a chain: coefficients, best coefficients and losses after 20 steps and
     the gradient of step 20, bit for bit, alone and between two older entries that never fire either, on both dsp_paths."""
-    lengths = [8000, 16000, 24000]
-    for dsp_path in ("stream", "staged"):
-        plain, _, _, _ = session(rt, O, lengths, [62, 63, 64], None, num_iterations=21, dsp_path=dsp_path)
-        plain.iterate(20)
-        gp = plain.gradient()
-        for chain in ([dict(BF, prob=0.0)], [dict(SUP, prob=0.0), dict(BF, prob=0.0), dict(NOISE10, prob=0.0)]):
-            att, batch, _, _ = session(rt, O, lengths, [62, 63, 64], chain, num_iterations=21, dsp_path=dsp_path)
-            att.iterate(20)
-            ga = att.gradient()
-            torch.cuda.synchronize()
-            assert torch.equal(plain.coef, att.coef) and torch.equal(plain.best_coef, att.best_coef)
-            assert torch.equal(plain.loss, att.loss) and torch.equal(plain.best_loss, att.best_loss)
-            assert torch.equal(gp, ga)
+    prob_0_is_the_plain_loop(rt, O, ([dict(BF, prob=0.0)], [dict(SUP, prob=0.0), dict(BF, prob=0.0), dict(NOISE10, prob=0.0)]))
 
 
 @pytest.mark.parametrize("lengths", [LONG, RAGGED], ids=["long", "ragged"])
 def test_graph_replay_is_bit_identical_and_redraws(rt, O, LA, lengths):
     chain = LA.parse_chain([dict(BF, prob=0.75), NOISE10])
-    out = []
-    for use_graph in (True, False):
-        sess, batch, _, _ = session(rt, O, lengths, list(range(50, 50 + len(lengths))), chain, num_iterations=40, use_graph=use_graph)
-        zs, losses = [], []
-        sess.iterate(32)
-        for _ in range(8):
-            sess.iterate(1)
-            zs.append(sess.attacked.clone())
-            losses.append(sess.loss.clone())
-        torch.cuda.synchronize()
-        out.append((sess.coef.cpu(), sess.best_coef.cpu(), sess.best_loss.cpu(), torch.stack(losses).cpu(), torch.stack(zs).cpu()))
-        assert int(sess.step.cpu()[0]) == 40
-    for a, b in zip(*out):
-        assert torch.equal(a, b)
+    out, _ = graph_replay_bits(rt, O, chain, lengths)
     # the draws are keyed by the device step counter: the replayed graph's buffer 12 moves with them
-    zs = out[0][4]
+    zs = out[4]
     assert len({zs[i].numpy().tobytes() for i in range(8)}) == 8
     draws = [drawn(LA, chain, 0, s) for s in range(32, 40)]
     assert len({d[1:] for d in draws if d[0]}) >= 4, draws
@@ -331,54 +235,14 @@ def test_graph_replay_is_bit_identical_and_redraws(rt, O, LA, lengths):
 def test_a_mixture_is_its_chains(rt, O, LA):
     """A mixture of a filter chain and a noise chain at step 0 against, per clip, a session that holds only the chain the clip
     drew: buffers 12 and 9, loss, prediction and the rows of the coefficient gradient, bit for bit."""
-    from test_gpu_loop_mixture import rows, session as mix_session, span
-    lengths = [16000, 8000, 16000, 8000]
-    mixture = LA.parse_mixture([{"weight": 0.5, "chain": [BF, NOISE10]}, {"weight": 0.5, "chain": [NOISE10]}])
-    s0 = 0
-    while set(LA.mixture_choices(list(range(s0, s0 + 4)), 0, [0.5, 0.5]).tolist()) != {0, 1}:
-        s0 += 1
-    seeds = list(range(s0, s0 + 4))
-    choice = LA.mixture_choices(seeds, 0, [0.5, 0.5])
-    kw = dict(num_iterations=4)
-    mix, batch = mix_session(rt, O, lengths, seeds, mixture=mixture, **kw)
-    g = mix.gradient()
-    torch.cuda.synchronize()
-    np.testing.assert_array_equal(mix.choices.cpu().numpy(), choice)
-    z, y, loss, pred = mix.attacked.clone(), mix._view(9, (batch.total_out,)).clone(), mix.loss.clone(), mix.pred.clone()
-    for c in (0, 1):
-        one, _ = mix_session(rt, O, lengths, seeds, chain=mixture[c]["chain"], **kw)
-        g1 = one.gradient()
-        torch.cuda.synchronize()
-        y1 = one._view(9, (batch.total_out,))
-        for b in np.flatnonzero(choice == c):
-            assert torch.equal(y[span(batch, b)], y1[span(batch, b)]) and torch.equal(z[span(batch, b)], one.attacked[span(batch, b)]), (b, c)
-            assert torch.equal(loss[b], one.loss[b]) and torch.equal(pred[b], one.pred[b]), (b, c)
-            assert torch.equal(g[rows(batch, b)], g1[rows(batch, b)]) and float(g[rows(batch, b)].abs().max()) > 0.0, (b, c)
+    mixture_is_its_chains(rt, O, LA, [BF, NOISE10], [NOISE10])
 
 
 # ---- 5. workspace and error codes -------------------------------------------------------------------------------------------------
-FB = (9, 0.75, [15.0, 2458.0, 15565.0, 1638.0])
-DS = (7, 0.75, [1.0, 512.0, 0.0])
-PV = (6, 0.9, [-9830.0, 9830.0, -5435.0, 5930.0])
-PS = (5, 0.75, [-3678.0, 3896.0])
-ST = (4, 0.75, [-9830.0, 9830.0])
-SP = (3, 0.75, [-3678.0, 3896.0])
-RV = (2, 1.0, [1600.0, 8000.0, -3.0])
-NO = (0, 1.0, [10.0])
-SU = (1, 1.0, [4800.0])
-EV = (8, 0.75, [800.0, 8000.0, 0.25])
-
-
 def test_workspace_bytes(rt, O):
     """The seven older chains need what they needed; a chain with the kind needs what the same chain with a deletion in its place
     needs."""
-    sess, batch, _, _ = session(rt, O, RAGGED, [64, 65], None, num_iterations=20, use_graph=False)
-    lib = sess.lib
-    size = lambda ent: lib.aware_embed_loop_attack_workspace_bytes_ex(batch.h, ex_entries(ent), len(ent))
-    nb = {name: size(ent)
-          for name, ent in (("noise", [NO]), ("noise_suppression", [NO, SU]), ("reverb", [RV]), ("suppression_reverb_noise", [SU, RV, NO]),
-                            ("speed", [SP]), ("noise_speed", [NO, SP]), ("four", [NO, SU, SP, NO]))}
-    assert nb == PARENT_WORKSPACE
+    size, nb, _ = older_chains_workspace(rt, O)
     for with_fb, with_ds in (([FB], [DS]), ([NO, FB], [NO, DS]), ([NO, SU, FB, NO], [NO, SU, DS, NO]), ([EV, FB, EV], [EV, DS, EV])):
         assert size(with_fb) == size(with_ds) > nb["noise"]
     for other in (RV, SP, ST, PS, PV, DS):                  # a refused chain is sized by the older kind, as before
@@ -431,24 +295,8 @@ def test_entry_point_error_codes(rt, O):
 def test_stereo_service_round_trip_with_the_card_key(rt, tmp_path):
     """load() of a card with the filter in loop_attacks, then embed_watermark / detect_watermark on a stereo clip: every channel
     carries the payload."""
-    from aware_amd.embedding.loop_attacks import parse_chain
-    from aware_amd.service import detect_watermark, embed_watermark
-    from aware_amd.utils.models import load
-    with open(os.path.join(ROOT, "aware_amd", "cards", "config.yaml")) as f:
-        card = yaml.safe_load(f)
-    card["loop_attacks"] = yaml.safe_load("[{kind: band_filter, response: [lowpass, highpass, bandpass, bandstop], freq: [600.0, 3800.0], "
-                                          "min_width: 400.0, prob: 0.75}]")
-    p = tmp_path / "card.yaml"
-    p.write_text(yaml.safe_dump(card))
-    emb, det = load(str(p))
-    assert emb.loop_attacks == parse_chain([dict(BF, prob=0.75)])
-    bits = np.random.default_rng(29).integers(0, 2, 20).astype(np.int32)
-    stereo = np.column_stack([make_clip(51, 16000)[0], make_clip(52, 16000)[0]])
-    out = embed_watermark(stereo, 16000, bits, emb)
-    assert out.shape[1] == 2 and np.isfinite(out).all()
-    got = detect_watermark(out, 16000, det)
-    for ch in (got if isinstance(got, (list, tuple)) else [got]):
-        np.testing.assert_array_equal(np.asarray(ch).reshape(-1)[:20].astype(np.int32), bits)
+    stereo_round_trip(tmp_path, "[{kind: band_filter, response: [lowpass, highpass, bandpass, bandstop], freq: [600.0, 3800.0], "
+                                "min_width: 400.0, prob: 0.75}]", dict(BF, prob=0.75))
 
 
 # ---- 7. the value claim on the device ---------------------------------------------------------------------------------------------
@@ -456,32 +304,13 @@ def test_value_claim_on_the_device(rt, O, tmp_path):
     """The host test's two embeddings (four 1 s clips, seeds 0..3, 400 steps) through AWAREEmbedder(loop_attacks=...) from an
     edited card, under the host test's six Butterworth channels with its bounds: clean 0 % both, the plain mean over the six at
     least 10 %, the aware mean at most half of it.  Figures: DESIGN.md section 25."""
-    from aware_amd.utils.models import load
-    from aware_amd.embedding.loop_attacks import parse_chain
     from test_loop_filter_host import AWARE_CHAIN, butterworth_attacks
     from test_loop_gain_host import snr_db
-    with open(os.path.join(ROOT, "aware_amd", "cards", "config.yaml")) as f:
-        card = yaml.safe_load(f)
-    pairs = [make_clip(s, 16000) for s in range(4)]
-    clips, bits = [p[0] for p in pairs], np.stack([p[1] for p in pairs])
-    wm = np.stack([O.bits_to_bipolar(b) for b in bits]).astype(np.float32)
-
-    def embed(chain):
-        c = dict(card)
-        if chain:
-            c["loop_attacks"] = chain
-        p = tmp_path / "card.yaml"
-        p.write_text(yaml.safe_dump(c))
-        emb, det = load(str(p))
-        assert emb.loop_attacks == parse_chain(chain)
-        return np.stack([o.cpu().numpy() for o in emb.embed_batch(clips, 16000, wm)]), det
-
-    def ber(det, ys):
-        vals = det.detect_batch(list(ys), 16000).cpu().numpy()
-        return 100.0 * float((O.decode_bits(vals) != bits).mean())
+    clips, bits, embed, ber = value_claim_setup(O, tmp_path)
 
     y0, det = embed(None)
     y1, _ = embed(AWARE_CHAIN)
+    y0, y1 = np.stack(y0), np.stack(y1)
     clean0, clean1 = ber(det, y0), ber(det, y1)
     a0, a1 = butterworth_attacks(y0), butterworth_attacks(y1)
     b0 = {k: ber(det, v) for k, v in a0.items()}

@@ -5,50 +5,26 @@ and the value claim under fades, tremolo and ducking.
 
 Run on the MI355X box:  python -m pytest tests/test_gpu_loop_gain.py -m gpu -q -s"""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 import torch
-import yaml
 
-from conftest import ROOT, make_clip
-from test_gpu_loop_attacks import attacked, check_first_gradient, norm2, session, synthesis
+from loop_support import LA, NOISE10, O, SUP, attacked, check_first_gradient, ex_entries, graph_replay_bits, mixture_session
+from loop_support import norm2, rt, session, synthesis, value_claim_setup, weights
+# the forward checks of the kinds an envelope's chains hold beside it, each from the module that owns it
 from test_gpu_loop_attacks import check_forward as check_forward_01
 from test_gpu_loop_reverb import check_forward as check_forward_reverb
 from test_gpu_loop_mixture import check_forward as check_forward_mixture
-from test_gpu_loop_mixture import session as mixture_session, weights
 
 pytestmark = pytest.mark.gpu
 
 ENV = {"kind": "gain_envelope", "period": [0.05, 0.5], "prob": 0.75}
 ENV_SHORT = {"kind": "gain_envelope", "period": 0.004, "floor": 0.25}          # 64 samples: the shortest period
-NOISE10 = {"kind": "gaussian_noise", "snr_db": 10.0}
-SUP = {"kind": "sample_suppression", "seconds": 0.3}
 REVERB = {"kind": "reverberation", "rt60": 0.3, "drr_db": -3.0}
 CHAINS = {"envelope": [ENV], "envelope_noise": [ENV, NOISE10], "suppression_envelope": [SUP, ENV_SHORT],
           "envelope_reverb_envelope": [ENV, REVERB, ENV_SHORT], "envelope_prob_0": [dict(ENV, prob=0.0)]}
 RAGGED, UNIFORM = [16000, 12000, 9000], [16000] * 32
-
-
-@pytest.fixture(scope="module")
-def rt():
-    from aware_amd import runtime
-    from aware_amd._lib import require_gpu
-    require_gpu()
-    return runtime
-
-
-@pytest.fixture(scope="module")
-def O():
-    from oracle import aware_oracle
-    return aware_oracle
-
-
-@pytest.fixture(scope="module")
-def LA():
-    from aware_amd.embedding import loop_attacks
-    return loop_attacks
 
 
 # ---- 1. the operator alone ----------------------------------------------------------------------------------------------------
@@ -185,7 +161,7 @@ def test_forward_matches_the_restatement(rt, O, LA, lengths, name):
 @pytest.mark.parametrize("lengths", [RAGGED, UNIFORM], ids=["ragged", "uniform32"])
 def test_first_gradient(rt, O, LA, lengths, name):
     """aware_embed_gradient with the chain against torch autograd over the restatement composed with the oracle's loop body, by
-    test_gpu_loop_attacks.check_first_gradient: 2e-5 relative L2 per clip (2e-2 within 2e-6 of a LeakyReLU kink), loss and
+    loop_support.check_first_gradient: 2e-5 relative L2 per clip (2e-2 within 2e-6 of a LeakyReLU kink), loss and
     prediction 1e-5."""
     check_first_gradient(rt, O, LA, CHAINS[name], lengths)
 
@@ -201,21 +177,8 @@ def test_first_gradient_on_every_conv_pipe(rt, O, LA, kw):
 # ---- 3. graph replay ----------------------------------------------------------------------------------------------------------
 def test_graph_replay_is_bit_identical_and_redraws(rt, O):
     chain = [dict(ENV_SHORT, floor=0.0), NOISE10, dict(ENV, prob=1.0)]
-    out = []
-    for use_graph in (True, False):
-        sess, batch, _, _ = session(rt, O, RAGGED, [50, 51, 52], chain, num_iterations=32, use_graph=use_graph)
-        zs, losses = [], []
-        sess.iterate(24)
-        for _ in range(8):
-            sess.iterate(1)
-            zs.append(sess.attacked.clone())
-            losses.append(sess.loss.clone())
-        torch.cuda.synchronize()
-        out.append((sess.coef.cpu(), sess.best_coef.cpu(), sess.best_loss.cpu(), torch.stack(losses).cpu(), torch.stack(zs).cpu()))
-        assert int(sess.step.cpu()[0]) == 32
-    for a, b in zip(*out):
-        assert torch.equal(a, b)
-    zs = out[0][4]
+    out, _ = graph_replay_bits(rt, O, chain, RAGGED, first=24)
+    zs = out[4]
     for i in range(7):
         assert float((zs[i + 1] - zs[i]).abs().max()) > 1e-2        # the draw is keyed by the device step counter
 
@@ -275,15 +238,11 @@ def test_a_mixture_with_an_envelope_chain(rt, O, LA, w):
 
 # ---- 5. error codes -----------------------------------------------------------------------------------------------------------
 def test_entry_point_error_codes(rt, O, LA):
-    from aware_amd._lib import LoopAttack, LoopAttackEx
+    from aware_amd._lib import LoopAttack
     lengths = [16000, 8000]
     sess, batch, _, _ = session(rt, O, lengths, [64, 65], None, num_iterations=4, use_graph=False)
     lib = sess.lib
-
-    def ex(entries):
-        return (LoopAttackEx * max(1, len(entries)))(*[LoopAttackEx(k, pr, (C.c_float * 4)(*(list(p) + [0.0] * (4 - len(p)))))
-                                                       for k, pr, p in entries])
-
+    ex = ex_entries
     ev = (8, 0.75, [800.0, 8000.0, 0.0])
     nb_noise = lib.aware_embed_loop_attack_workspace_bytes_ex(batch.h, ex([(0, 1.0, [10.0])]), 1)
     assert lib.aware_embed_loop_attack_workspace_bytes_ex(batch.h, ex([ev]), 1) == nb_noise        # no new workspace
@@ -326,28 +285,8 @@ def test_value_claim_on_the_device(rt, O, tmp_path):
     embeddings, the plain mean over the six at least 10 %, the aware mean at most half of it.  Measured: plain 32.5 / 35 / 36.25 /
     36.25 / 30 / 40 %, mean 35.00 %; aware 0 / 0 / 2.5 / 5 / 13.75 / 6.25 %, mean 4.58 %; clean 0 %; SNR 15.8 against 14.2 dB."""
     from aware_amd import attacks as A
-    from aware_amd.utils.models import load
-    from aware_amd.embedding.loop_attacks import parse_chain
     from test_loop_gain_host import AWARE_CHAIN, snr_db
-    with open(os.path.join(ROOT, "aware_amd", "cards", "config.yaml")) as f:
-        card = yaml.safe_load(f)
-    pairs = [make_clip(s, 16000) for s in range(4)]
-    clips, bits = [p[0] for p in pairs], np.stack([p[1] for p in pairs])
-    wm = np.stack([O.bits_to_bipolar(b) for b in bits]).astype(np.float32)
-
-    def embed(chain):
-        c = dict(card)
-        if chain:
-            c["loop_attacks"] = chain
-        p = tmp_path / "card.yaml"
-        p.write_text(yaml.safe_dump(c))
-        emb, det = load(str(p))
-        assert emb.loop_attacks == parse_chain(chain)
-        return [o.cpu().numpy() for o in emb.embed_batch(clips, 16000, wm)], det
-
-    def ber(det, ys):
-        vals = det.detect_batch(ys.to_list() if hasattr(ys, "to_list") else ys, 16000).cpu().numpy()
-        return 100.0 * float((O.decode_bits(vals) != bits).mean())
+    clips, bits, embed, ber = value_claim_setup(O, tmp_path)
 
     def duck(x):
         data = x.data.clone()

@@ -11,8 +11,7 @@ import torch
 import yaml
 
 from conftest import ROOT, make_clip
-from test_gpu_loop_attacks import attacked, det_for, norm2, plan_for, synthesis
-from test_gpu_loop_reverb import CHAIN_BOUND
+from loop_support import CHAIN_BOUND, LA, NO, O, RV, SU, attacked, mixture_session as session, norm2, rows, rt, span, synthesis, weights
 from test_loop_mixture_host import CENTS, CROPS, FAMILIES, HALF_OF_PLAIN, MIX, MIX2, RATES
 
 pytestmark = pytest.mark.gpu
@@ -27,30 +26,6 @@ PITCH = [{"kind": "pitch_shift", "cents": 100.0, "prob": 0.75}]
 HALF_OF_PLAIN_DEVICE = tuple(k for k in HALF_OF_PLAIN if k != "rooms of rt60 0.3 s")
 
 
-@pytest.fixture(scope="module")
-def rt():
-    from aware_amd import runtime
-    from aware_amd._lib import require_gpu
-    require_gpu()
-    return runtime
-
-
-@pytest.fixture(scope="module")
-def O():
-    from oracle import aware_oracle
-    return aware_oracle
-
-
-@pytest.fixture(scope="module")
-def LA():
-    from aware_amd.embedding import loop_attacks
-    return loop_attacks
-
-
-def weights(mixture):
-    return [m["weight"] for m in mixture]
-
-
 def covering_seeds(LA, mixture, n=10):
     """The first run of n seeds >= 100 in which every option of the mixture, -1 included if it has a clean share, occurs at step 0."""
     w = weights(mixture)
@@ -61,38 +36,6 @@ def covering_seeds(LA, mixture, n=10):
     seeds = list(range(s0, s0 + n))
     assert set(LA.mixture_choices(seeds, 0, w).tolist()) == want       # the coverage the tests below rely on
     return seeds
-
-
-_CLIPS = {}
-
-
-def clips_for(O, lengths):
-    key = tuple(lengths)
-    if key not in _CLIPS:
-        pairs = [make_clip(200 + i, n) for i, n in enumerate(lengths)]
-        _CLIPS[key] = ([p[0] for p in pairs], np.stack([O.bits_to_bipolar(p[1]) for p in pairs]).astype(np.float32))
-    return _CLIPS[key]
-
-
-def session(rt, O, lengths, seeds=None, mixture=None, chain=None, **kw):
-    """A session on the shared clips of these lengths, begun, with a mixture, a chain or neither."""
-    audio, wm = clips_for(O, lengths)
-    batch = rt.Batch(lengths)
-    sess = rt.EmbedSession(plan_for(rt), det_for(rt, O), batch, **kw)
-    if mixture is not None:
-        sess.set_loop_mixture(mixture, seeds)
-    elif chain is not None:
-        sess.set_loop_attacks(chain, seeds)
-    sess.begin(batch.pack(audio), torch.from_numpy(wm).cuda())
-    return sess, batch
-
-
-def rows(batch, b):
-    return slice(batch.frame_offsets[b], batch.frame_offsets[b + 1])
-
-
-def span(batch, b):
-    return slice(batch.out_offsets[b], batch.out_offsets[b] + batch.out_lengths[b])
 
 
 # ---- 1. the draw ------------------------------------------------------------------------------------------------------------------
@@ -306,7 +249,6 @@ def test_workspace_and_error_codes(rt, O, LA):
         return (LoopChain * len(keep))(*[LoopChain(C.cast(a, C.POINTER(LoopAttackEx)), len(e), w)
                                          for a, (e, w) in zip(keep, entries_and_weights)]), keep
 
-    NO, SU, RV = (0, 1.0, [10.0]), (1, 1.0, [4800.0]), (2, 1.0, [1600.0, 8000.0, -3.0])
     DS, SP = (7, 1.0, [1.0, 512.0, 1.0]), (3, 1.0, [-3678.0, 3896.0])
     assert call(arr, 4) == 0 and lib.aware_embed_buffer(sess.h, 14) and lib.aware_embed_buffer(sess.h, 12) and lib.aware_embed_buffer(sess.h, 13)
     assert call(arr, 4, wsb=nbytes - 1) == -4

@@ -8,26 +8,20 @@ Shapes: clips [8000] * 2 (7936 output samples), [16000] * 2 (15872, more than on
 
 Run on the MI355X box:  python -m pytest tests/test_gpu_loop_pitch.py -m gpu -q -s"""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 import torch
-import yaml
 
-from conftest import ROOT, make_clip
-from test_gpu_loop_attacks import attacked, attacked_oracle, norm2, sampled, session, synthesis
-from test_gpu_loop_reverb import CHAIN_BOUND
-from test_gpu_loop_stretch import PARENT_WORKSPACE, ex_entries
+from loop_support import CHAIN_BOUND, KINK, LA, LONG, NO, NOISE10, O, PS, RAGGED, RV, SHORT, SP, ST, SU, SUP, ex_entries
+from loop_support import first_gradient, forward_at_steps_0_2_17, graph_replay_bits, norm2, older_chains_workspace
+from loop_support import prob_0_is_the_plain_loop, rt, sampled, session, step_0_is_the_stand_alone_entry, value_claim_setup
 
 pytestmark = pytest.mark.gpu
 
 M_MIN, M_MAX = -13520, 17034                               # the speed offsets of -+400 cents
 M_MID = 3000
-SHORT, LONG, RAGGED = [8000] * 2, [16000] * 2, [16000, 8000]
 PITCH = {"kind": "pitch_shift", "cents": 100.0}
-NOISE10 = {"kind": "gaussian_noise", "snr_db": 10.0}
-SUP = {"kind": "sample_suppression", "seconds": 0.3}
 CHAINS = {"pitch": [PITCH], "pitch_noise": [PITCH, NOISE10], "suppression_pitch": [SUP, PITCH]}
 assert CHAIN_BOUND == 1.13e-6                              # the project's bound for the loop's attacked signal (DESIGN 16)
 
@@ -39,26 +33,6 @@ assert CHAIN_BOUND == 1.13e-6                              # the project's bound
 # dependence): 1.83e-7 over the twelve cases, forward 1.83e-7 (at m = -13520) and adjoint 1.60e-7 (at m = -1) at most.
 CAP = 4e-6
 PITCH_BOUND = 7.3e-7
-
-
-@pytest.fixture(scope="module")
-def rt():
-    from aware_amd import runtime
-    from aware_amd._lib import require_gpu
-    require_gpu()
-    return runtime
-
-
-@pytest.fixture(scope="module")
-def O():
-    from oracle import aware_oracle
-    return aware_oracle
-
-
-@pytest.fixture(scope="module")
-def LA():
-    from aware_amd.embedding import loop_attacks
-    return loop_attacks
 
 
 def one_value(LA, m):
@@ -181,16 +155,7 @@ def test_forward_matches_the_restatement(rt, O, LA, lengths, name):
     """Buffer 12 (sess.attacked) against apply_chain(N(N(buffer 9))) at steps 0, 2 and 17, within the project's bound for the
     loop's attacked signal (1.13e-6 of the peak).  Measured: 1.96e-7 at most over the 54 comparisons."""
     chain = LA.parse_chain(CHAINS[name])
-    seeds = [11 + 3 * i for i in range(len(lengths))]
-    sess, batch, _, _ = session(rt, O, lengths, list(range(20, 20 + len(lengths))), chain, seeds, num_iterations=20)
-    assert sorted(batch.out_lengths)[0] in (7936, 15872)
-    sess.gradient()
-    check_forward(LA, sess, batch, chain, seeds, 0, name)
-    sess.iterate(3)
-    check_forward(LA, sess, batch, chain, seeds, 2, name)
-    sess.iterate(15)
-    assert int(sess.step.cpu()[0]) == 18
-    check_forward(LA, sess, batch, chain, seeds, 17, name)
+    batch, seeds = forward_at_steps_0_2_17(rt, O, LA, chain, lengths, name, check_forward)
     assert len({drawn(LA, chain, seeds[0], s) for s in (0, 2, 17)}) == 3
 
 
@@ -200,53 +165,23 @@ def test_step_0_is_the_stand_alone_entry(rt, O, LA, lengths, m):
     """With a range that holds one offset, buffer 12 at step 0 is aware_pitch_shift_ola on the same input, bit for bit: the
     loop's kernel and the stand-alone one share their arithmetic, whatever the partition into tiles.  The input x = N(N(y)) in
     the device's own rounding is buffer 12 of a second session whose entry never fires."""
-    e = one_value(LA, m)
-    clips = list(range(30, 30 + len(lengths)))
-    on, batch, _, _ = session(rt, O, lengths, clips, [e], [3, 4])
-    off, _, _, _ = session(rt, O, lengths, clips, [dict(e, prob=0.0)], [3, 4])
-    on.gradient()
-    off.gradient()
-    torch.cuda.synchronize()
-    assert torch.equal(on._view(9, (batch.total_out,)), off._view(9, (batch.total_out,)))
-    x = rt.Ragged(off.attacked.clone(), batch.out_lengths)
-    for xi, y in zip(x.to_list(), synthesis(off, batch)):
-        assert float(np.abs(xi - norm2(y.double()).numpy()).max()) < 2e-7
-    z = rt.pitch_shift_ola(x, m)
-    assert torch.equal(z.data, on.attacked)
-    assert not torch.equal(z.data, x.data)
+    step_0_is_the_stand_alone_entry(rt, O, lengths, one_value(LA, m), lambda x: rt.pitch_shift_ola(x, m))
 
 
 # ---- 3. first gradient ----------------------------------------------------------------------------------------------------------
 # First clip seed of the gradient cases, chosen on the CPU so that the float64 restatement keeps every LeakyReLU argument of both
 # clips at least 8e-6 from its kink: seeds 85 and 86: 4.4e-5 / 9.0e-5 (of the seeds 80 to 99 tried, 83 as the long clip was at
 # 4.9e-8, 88 at 2.3e-7, 81 at 2.6e-6).  The case between two other entries, on two long clips: seeds 90 and 91: 3.5e-5 / 1.6e-5.
-KINK = 8e-6
+assert KINK == 8e-6
 SEED0 = 85
 SEED0_BETWEEN = 90
 
 
-def check_gradient(rt, O, LA, chain, lengths, clip_seed0, **kw):
-    """As check_gradient of test_gpu_loop_stretch.py, with the bounds of the two sibling kinds: relative L2 of the gradient at
-    most 2e-5 for every clip, loss and prediction within 1e-6, and no clip closer than KINK to a LeakyReLU kink."""
-    from test_gpu_kernels import _min_kink_distance
-    clip_seeds = list(range(clip_seed0, clip_seed0 + len(lengths)))
-    seeds = [5 + 2 * i for i in range(len(lengths))]
-    sess, batch, pairs, wm = session(rt, O, lengths, clip_seeds, chain, seeds, use_graph=False, **kw)
-    g = sess.gradient()
-    torch.cuda.synchronize()
-    g = g.cpu()
-    loss, pred = sess.loss.cpu().numpy(), sess.pred.cpu().numpy()
-    for i, (clip, _) in enumerate(pairs):
-        emb = attacked_oracle(O, LA, chain, seeds[i], 0)
-        mag0, phase = emb.analyse(torch.from_numpy(clip)[None])
-        c0 = mag0[:, emb.band].clone().requires_grad_(True)
-        l, p = emb.forward_loss(c0, mag0, phase, torch.from_numpy(wm[i])[None])
-        l.sum().backward()
-        ref = c0.grad[0]
-        mine = g[batch.frame_offsets[i]: batch.frame_offsets[i + 1], :225].T
-        rel = (mine - ref).norm().item() / ref.norm().item()
-        kink = _min_kink_distance(emb, mag0, phase)
-        lerr, perr = abs(loss[i] - float(l.detach())), float(np.abs(pred[i] - p[0].detach().numpy()).max())
+def check_first_gradient(rt, O, LA, chain, lengths, clip_seed0, **kw):
+    """The figures of loop_support.first_gradient, with the bounds of the two sibling kinds: relative L2 of the gradient at most
+    2e-5 for every clip, loss and prediction within 1e-6, and no clip closer than KINK to a LeakyReLU kink."""
+    _, seeds, figures = first_gradient(rt, O, LA, chain, lengths, list(range(clip_seed0, clip_seed0 + len(lengths))), **kw)
+    for i, (rel, kink, lerr, perr) in enumerate(figures):
         m = drawn(LA, chain, seeds[i], 0)
         print(f"{kw} clip {i} (n = {lengths[i]}, m = {m}): loss err {lerr:.1e}, pred err {perr:.1e}, "
               f"gradient rel L2 {rel:.2e}, nearest LeakyReLU kink {kink:.1e}")
@@ -261,85 +196,39 @@ def test_first_gradient(rt, O, LA, dsp_path):
     """aware_embed_gradient against torch autograd over the restatement composed with the oracle's loop body, ragged batch:
     2e-5 relative L2 per clip, loss and prediction 1e-6.  Measured over the gradient tests of this file: 2.50e-6 relative L2 at
     most, loss 1.8e-7, prediction 3.9e-7; no clip closer than 1.6e-5 to a kink."""
-    check_gradient(rt, O, LA, [PITCH], RAGGED, SEED0, dsp_path=dsp_path)
+    check_first_gradient(rt, O, LA, [PITCH], RAGGED, SEED0, dsp_path=dsp_path)
 
 
 def test_first_gradient_f32_dense(rt, O, LA):
-    check_gradient(rt, O, LA, [PITCH], RAGGED, SEED0, conv_pipe="f32", mel="dense")
+    check_first_gradient(rt, O, LA, [PITCH], RAGGED, SEED0, conv_pipe="f32", mel="dense")
 
 
 def test_first_gradient_between_other_entries(rt, O, LA):
     """A suppression in front and noise behind: the stages on both sides of the fused adjoint."""
-    check_gradient(rt, O, LA, [SUP, PITCH, NOISE10], LONG, SEED0_BETWEEN)
+    check_first_gradient(rt, O, LA, [SUP, PITCH, NOISE10], LONG, SEED0_BETWEEN)
 
 
 # ---- 4. graph replay, prob 0, workspace, error codes -------------------------------------------------------------------------------
 def test_graph_replay_is_bit_identical_and_redraws(rt, O, LA):
     chain = [dict(PITCH, prob=0.75)]
-    lengths = RAGGED
-    out = []
-    for use_graph in (True, False):
-        sess, batch, _, _ = session(rt, O, lengths, [50, 51], chain, num_iterations=40, use_graph=use_graph)
-        zs, losses = [], []
-        sess.iterate(32)
-        for _ in range(8):
-            sess.iterate(1)
-            zs.append(sess.attacked.clone())
-            losses.append(sess.loss.clone())
-        torch.cuda.synchronize()
-        out.append((sess.coef.cpu(), sess.best_coef.cpu(), sess.best_loss.cpu(), torch.stack(losses).cpu(), torch.stack(zs).cpu()))
-        assert int(sess.step.cpu()[0]) == 40
-    for a, b in zip(*out):
-        assert torch.equal(a, b)
+    out, _ = graph_replay_bits(rt, O, chain, RAGGED)
     # the draw is keyed by the device step counter: clip 0 (seed 0) at steps 32..39 is shifted by the offsets the host draws
     ms = [drawn(LA, chain, 0, s) for s in range(32, 40)]
     assert len(set(ms)) >= 5, ms
-    assert len({out[0][4][i].numpy().tobytes() for i in range(8)}) >= 5
+    assert len({out[4][i].numpy().tobytes() for i in range(8)}) >= 5
 
 
 def test_prob_0_is_the_plain_loop(rt, O):
     """A pitch shift that never fires, alone and between other entries that never fire either, against the loop without a
     chain: coefficients, best coefficients and losses after 20 steps and the gradient of step 20, bit for bit, on both
     dsp_paths (a clip on which no entry fires takes the plain loop's path)."""
-    lengths = [8000, 16000, 24000]
-    for dsp_path in ("stream", "staged"):
-        plain, _, _, _ = session(rt, O, lengths, [62, 63, 64], None, num_iterations=21, dsp_path=dsp_path)
-        plain.iterate(20)
-        gp = plain.gradient()
-        for chain in ([dict(PITCH, prob=0.0)], [dict(SUP, prob=0.0), dict(PITCH, prob=0.0), dict(NOISE10, prob=0.0)]):
-            att, batch, _, _ = session(rt, O, lengths, [62, 63, 64], chain, num_iterations=21, dsp_path=dsp_path)
-            att.iterate(20)
-            ga = att.gradient()
-            torch.cuda.synchronize()
-            for z, y in zip(attacked(att, batch), synthesis(att, batch)):
-                assert float((z.double() - norm2(y.double())).abs().max()) < 2e-7
-            print(f"{dsp_path}, prob 0 against the plain loop after 20 steps: max |coef difference| = "
-                  f"{float((plain.coef - att.coef).abs().max()):.3e}, loss difference {float((plain.loss - att.loss).abs().max()):.3e}")
-            assert torch.equal(plain.coef, att.coef) and torch.equal(plain.best_coef, att.best_coef)
-            assert torch.equal(plain.loss, att.loss) and torch.equal(plain.best_loss, att.best_loss)
-            assert torch.equal(gp, ga)
-
-
-PS = (5, 0.75, [-3678.0, 3896.0])
-ST = (4, 0.75, [-9830.0, 9830.0])
-SP = (3, 0.75, [-3678.0, 3896.0])
-RV = (2, 1.0, [1600.0, 8000.0, -3.0])
-NO = (0, 1.0, [10.0])
-SU = (1, 1.0, [4800.0])
+    prob_0_is_the_plain_loop(rt, O, ([dict(PITCH, prob=0.0)], [dict(SUP, prob=0.0), dict(PITCH, prob=0.0), dict(NOISE10, prob=0.0)]))
 
 
 def test_workspace_bytes(rt, O):
-    """Chains of the older kinds need what they needed (the byte counts test_gpu_loop_stretch.py holds); a chain with the new
+    """Chains of the older kinds need what they needed (the byte counts loop_support.PARENT_WORKSPACE holds); a chain with the new
     kind needs what the same chain with a speed change in its place needs."""
-    sess, batch, _, _ = session(rt, O, RAGGED, [64, 65], None, num_iterations=20, use_graph=False)
-    lib = sess.lib
-    size = lambda ent: lib.aware_embed_loop_attack_workspace_bytes_ex(batch.h, ex_entries(ent), len(ent))
-    nb = {name: size(ent)
-          for name, ent in (("noise", [NO]), ("noise_suppression", [NO, SU]), ("reverb", [RV]), ("suppression_reverb_noise", [SU, RV, NO]),
-                            ("speed", [SP]), ("noise_speed", [NO, SP]), ("four", [NO, SU, SP, NO]))}
-    print("workspace bytes:", nb)
-    assert nb == PARENT_WORKSPACE
-    assert lib.aware_embed_loop_attack_workspace_bytes(batch.h, 2) == PARENT_WORKSPACE["noise_suppression"]
+    size, nb, batch = older_chains_workspace(rt, O)
     assert size([ST]) == nb["speed"] and 4 * batch.total_out <= size([ST, SP]) - size([ST]) < 4 * batch.total_out + 256
     for with_ps, with_sp in (([PS], [SP]), ([NO, PS], [NO, SP]), ([NO, SU, PS, NO], [NO, SU, SP, NO]), ([PS, SU], [SP, SU])):
         assert size(with_ps) == size(with_sp) > nb["noise"]
@@ -400,29 +289,9 @@ def test_value_claim_on_the_device(rt, O, tmp_path):
     26.25, mean 35.00 / 26.56.  SNR against the normalised host, dB: plain 15.93, 15.12, 15.88, 16.08; pitch-aware 15.29, 15.53,
     16.15, 15.58."""
     from aware_amd import attacks as A
-    from aware_amd.utils.models import load
-    from aware_amd.embedding.loop_attacks import parse_chain
     from test_loop_pitch_host import AWARE_CHAIN, RATES, CENTS
     from test_loop_speed_host import snr_db
-    with open(os.path.join(ROOT, "aware_amd", "cards", "config.yaml")) as f:
-        card = yaml.safe_load(f)
-    pairs = [make_clip(s, 16000) for s in range(4)]
-    clips, bits = [p[0] for p in pairs], np.stack([p[1] for p in pairs])
-    wm = np.stack([O.bits_to_bipolar(b) for b in bits]).astype(np.float32)
-
-    def embed(chain):
-        c = dict(card)
-        if chain:
-            c["loop_attacks"] = chain
-        p = tmp_path / "card.yaml"
-        p.write_text(yaml.safe_dump(c))
-        emb, det = load(str(p))
-        assert emb.loop_attacks == parse_chain(chain)
-        return [o.cpu().numpy() for o in emb.embed_batch(clips, 16000, wm)], det
-
-    def ber(det, ys):
-        vals = det.detect_batch(ys.to_list() if hasattr(ys, "to_list") else ys, 16000).cpu().numpy()
-        return 100.0 * float((O.decode_bits(vals) != bits).mean())
+    clips, bits, embed, ber = value_claim_setup(O, tmp_path)
 
     ys = {}
     ys["plain"], det = embed(None)

@@ -14,28 +14,21 @@ clips [8000] * 2 (7936 output samples), [16000] * 2 (15872, more than one synthe
 
 Run on the MI355X box:  python -m pytest tests/test_gpu_loop_pv.py -m gpu -q -s"""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 import torch
-import yaml
 
-from conftest import ROOT, make_clip
-from test_gpu_loop_attacks import attacked, norm2, sampled, session, synthesis
-from test_gpu_loop_reverb import CHAIN_BOUND
-from test_gpu_loop_stretch import PARENT_WORKSPACE, ex_entries
+from loop_support import CHAIN_BOUND, KINK, LA, LONG, NO, NOISE10, O, PS, PV, RAGGED, RV, SHORT, SP, ST, SU, SUP, attacked
+from loop_support import check_gradient, ex_entries, forward_at_steps_0_2_17, graph_replay_bits, norm2, older_chains_workspace
+from loop_support import prob_0_is_the_plain_loop, rt, sampled, session, stereo_round_trip, value_claim_setup
 
 pytestmark = pytest.mark.gpu
 
 Q_MIN, Q_MAX, Q_MID = -16384, 21845, 4464                  # the stretch's range of offsets, and one inside
-SHORT, LONG, RAGGED = [8000] * 2, [16000] * 2, [16000, 8000]
 PV_RATE = {"kind": "phase_vocoder", "rate": [0.85, 1.15]}
 PV_CENTS = {"kind": "phase_vocoder", "cents": 150.0}
 PV_BOTH = {"kind": "phase_vocoder", "rate": [0.85, 1.15], "cents": 150.0}
-NOISE10 = {"kind": "gaussian_noise", "snr_db": 10.0}
-SUP = {"kind": "sample_suppression", "seconds": 0.3}
-SPEED = {"kind": "speed_change", "cents": 100.0}
 CHAINS = {"stretch": [PV_RATE], "pitch": [PV_CENTS], "both": [PV_BOTH], "suppression_both_noise": [SUP, PV_BOTH, NOISE10]}
 assert CHAIN_BOUND == 1.13e-6                              # the project's bound for the loop's attacked signal (DESIGN 16)
 
@@ -51,26 +44,6 @@ assert CHAIN_BOUND == 1.13e-6                              # the project's bound
 CAP = (32 * 10 + 8) * 2.0 ** -24
 MEASURED = 3.42e-7
 PV_BOUND = 4 * MEASURED
-
-
-@pytest.fixture(scope="module")
-def rt():
-    from aware_amd import runtime
-    from aware_amd._lib import require_gpu
-    require_gpu()
-    return runtime
-
-
-@pytest.fixture(scope="module")
-def O():
-    from oracle import aware_oracle
-    return aware_oracle
-
-
-@pytest.fixture(scope="module")
-def LA():
-    from aware_amd.embedding import loop_attacks
-    return loop_attacks
 
 
 @pytest.fixture(scope="module")
@@ -222,16 +195,7 @@ def check_forward(LA, sess, batch, chain, seeds, step, tag, sample=None):
 def test_forward_matches_the_restatement(rt, O, LA, lengths, name):
     """Buffer 12 (sess.attacked) against apply_chain(N(N(buffer 9))) at steps 0, 2 and 17."""
     chain = LA.parse_chain(CHAINS[name])
-    seeds = [11 + 3 * i for i in range(len(lengths))]
-    sess, batch, _, _ = session(rt, O, lengths, list(range(20, 20 + len(lengths))), chain, seeds, num_iterations=20)
-    assert sorted(batch.out_lengths)[0] in (7936, 15872)
-    sess.gradient()
-    check_forward(LA, sess, batch, chain, seeds, 0, name)
-    sess.iterate(3)
-    check_forward(LA, sess, batch, chain, seeds, 2, name)
-    sess.iterate(15)
-    assert int(sess.step.cpu()[0]) == 18
-    check_forward(LA, sess, batch, chain, seeds, 17, name)
+    batch, seeds = forward_at_steps_0_2_17(rt, O, LA, chain, lengths, name, check_forward)
     assert len({drawn(LA, chain, seeds[0], s) for s in (0, 2, 17)}) == 3
 
 
@@ -247,79 +211,31 @@ def test_both_modes_occur_in_the_loop(LA):
 # (81 as the long clip was at 1.5e-6, 90 at 9.0e-7, 85 as the short one at 8.2e-7); both clips draw the stretch mode.  Two long
 # clips between a suppression and noise: seeds 83 and 84, 2.9e-5 / 4.8e-5; the first draws the pitch mode, the second the
 # stretch mode.
-KINK = 8e-6
+assert KINK == 8e-6
 SEED0 = 83
 SEED0_BETWEEN = 83
 
 
-def pv_oracle(O, LA, chain, seed, step, dtype):
-    class Attacked(O.Embedder):
-        def recompute_magnitude(self, mag_full, phase):
-            y = O.istft(mag_full * torch.exp(1j * phase))
-            y = y / torch.amax(torch.abs(y) + 1e-8, dim=-1, keepdim=True)
-            y = y / torch.amax(torch.abs(y) + 1e-8, dim=-1, keepdim=True)
-            y = LA.apply_chain(y, chain, [seed], step)
-            y = y / torch.amax(torch.abs(y) + 1e-8, dim=-1, keepdim=True)
-            y = y / torch.amax(torch.abs(y) + 1e-8, dim=-1, keepdim=True)
-            return torch.abs(O.stft(y)), y
-    return Attacked(dtype=dtype)
-
-
-def oracle_gradient(O, LA, chain, seed, clip, wm, dtype):
-    from test_gpu_kernels import _min_kink_distance
-    emb = pv_oracle(O, LA, chain, seed, 0, dtype)
-    mag0, phase = emb.analyse(torch.from_numpy(clip).to(dtype)[None])
-    c0 = mag0[:, emb.band].clone().requires_grad_(True)
-    l, p = emb.forward_loss(c0, mag0, phase, torch.from_numpy(wm).to(dtype)[None])
-    l.sum().backward()
-    return c0.grad[0].double(), float(l.detach()), p[0].detach().double().numpy(), _min_kink_distance(emb, mag0, phase)
-
-
-def check_gradient(rt, O, LA, chain, lengths, clip_seed0, modes, **kw):
-    """aware_embed_gradient against autograd over the float64 restatement composed with the oracle's loop body.  The bound on
-    the relative L2 distance of a clip's gradient is four times the distance of the same composition in float32 from it,
-    computed here on the CPU, and at least the 2e-5 the older kinds hold.  Loss and prediction are held the same way: within four
-    times the float32 composition's own distance from the float64 one, and at least the 1e-6 the older kinds hold.  The older
-    kinds' 1e-6 alone is not a floor here: behind the vocoder's STFT the float32 torch restatement itself, with no device code
-    involved, lands up to 8.9e-7 (prediction) and 2.4e-7 (loss) from the float64 one on these clips.  No
-    clip closer than KINK to a LeakyReLU kink in either precision."""
-    clip_seeds = list(range(clip_seed0, clip_seed0 + len(lengths)))
-    seeds = [5 + 2 * i for i in range(len(lengths))]
-    sess, batch, pairs, wm = session(rt, O, lengths, clip_seeds, chain, seeds, use_graph=False, **kw)
-    g = sess.gradient()
-    torch.cuda.synchronize()
-    g = g.cpu()
-    loss, pred = sess.loss.cpu().numpy(), sess.pred.cpu().numpy()
-    for i, (clip, _) in enumerate(pairs):
-        ref, l, p, kink = oracle_gradient(O, LA, chain, seeds[i], clip, wm[i], torch.float64)
-        r32, l32, p32, kink32 = oracle_gradient(O, LA, chain, seeds[i], clip, wm[i], torch.float32)
-        floor = float((r32 - ref).norm() / ref.norm())
-        lfloor, pfloor = abs(l32 - l), float(np.abs(p32 - p).max())
-        mine = g[batch.frame_offsets[i]: batch.frame_offsets[i + 1], :225].T.double()
-        rel = float((mine - ref).norm() / ref.norm())
-        lerr, perr = abs(loss[i] - l), float(np.abs(pred[i] - p).max())
-        on, mq, m = drawn(LA, chain, seeds[i], 0)
-        print(f"{kw} clip {i} (n = {lengths[i]}, mq = {mq}, m = {m}): loss err {lerr:.1e} (float32 restatement {lfloor:.1e}), pred err "
-              f"{perr:.1e} ({pfloor:.1e}), gradient rel L2 {rel:.2e} ({floor:.2e}), nearest LeakyReLU kink {kink:.1e} / {kink32:.1e}")
-        assert on and mq != 0 and (m != 0) == modes[i], "the case is to exercise the operator in this mode"
-        assert min(kink, kink32) >= KINK, (i, kink, kink32)
-        assert lerr <= max(4 * lfloor, 1e-6) and perr <= max(4 * pfloor, 1e-6), (i, lerr, lfloor, perr, pfloor)
-        assert rel <= max(4 * floor, 2e-5), (i, rel, floor)
+def gradient_case(modes):
+    """The module's pieces of loop_support.check_gradient (the rule and its bounds are stated there):
+    modes[i] says whether clip i is to draw the pitch mode."""
+    return dict(drawn=lambda LA, chain, seed, step, ny: drawn(LA, chain, seed, step), describe=lambda d: f"mq = {d[1]}, m = {d[2]}",
+                exercised=lambda d, i, ny: d[0] and d[1] != 0 and (d[2] != 0) == modes[i])
 
 
 @pytest.mark.parametrize("dsp_path", ["stream", "staged"])
 def test_first_gradient(rt, O, LA, dsp_path):
-    check_gradient(rt, O, LA, [PV_BOTH], RAGGED, SEED0, [False, False], dsp_path=dsp_path)
+    check_gradient(rt, O, LA, [PV_BOTH], RAGGED, SEED0, **gradient_case([False, False]), dsp_path=dsp_path)
 
 
 def test_first_gradient_f32_dense(rt, O, LA):
-    check_gradient(rt, O, LA, [PV_BOTH], RAGGED, SEED0, [False, False], conv_pipe="f32", mel="dense")
+    check_gradient(rt, O, LA, [PV_BOTH], RAGGED, SEED0, **gradient_case([False, False]), conv_pipe="f32", mel="dense")
 
 
 @pytest.mark.parametrize("dsp_path", ["stream", "staged"])
 def test_first_gradient_between_other_entries(rt, O, LA, dsp_path):
     """A suppression in front and noise behind: the stages on both sides; the first clip is in pitch mode."""
-    check_gradient(rt, O, LA, [SUP, PV_BOTH, NOISE10], LONG, SEED0_BETWEEN, [True, False], dsp_path=dsp_path)
+    check_gradient(rt, O, LA, [SUP, PV_BOTH, NOISE10], LONG, SEED0_BETWEEN, **gradient_case([True, False]), dsp_path=dsp_path)
 
 
 # ---- 5. invariants ----------------------------------------------------------------------------------------------------------------
@@ -349,66 +265,25 @@ def test_a_clip_that_does_not_fire_keeps_its_bits(rt, O, LA):
 def test_prob_0_is_the_plain_loop(rt, O):
     """A vocoder that never fires, alone and between two older entries that never fire either, against the loop without a chain:
     coefficients, best coefficients and losses after 20 steps and the gradient of step 20, bit for bit, on both dsp_paths."""
-    lengths = [8000, 16000, 24000]
-    for dsp_path in ("stream", "staged"):
-        plain, _, _, _ = session(rt, O, lengths, [62, 63, 64], None, num_iterations=21, dsp_path=dsp_path)
-        plain.iterate(20)
-        gp = plain.gradient()
-        for chain in ([dict(PV_BOTH, prob=0.0)], [dict(SUP, prob=0.0), dict(PV_BOTH, prob=0.0), dict(NOISE10, prob=0.0)]):
-            att, batch, _, _ = session(rt, O, lengths, [62, 63, 64], chain, num_iterations=21, dsp_path=dsp_path)
-            att.iterate(20)
-            ga = att.gradient()
-            torch.cuda.synchronize()
-            for z, y in zip(attacked(att, batch), synthesis(att, batch)):
-                assert float((z.double() - norm2(y.double())).abs().max()) < 2e-7
-            assert torch.equal(plain.coef, att.coef) and torch.equal(plain.best_coef, att.best_coef)
-            assert torch.equal(plain.loss, att.loss) and torch.equal(plain.best_loss, att.best_loss)
-            assert torch.equal(gp, ga)
+    prob_0_is_the_plain_loop(rt, O, ([dict(PV_BOTH, prob=0.0)], [dict(SUP, prob=0.0), dict(PV_BOTH, prob=0.0), dict(NOISE10, prob=0.0)]))
 
 
 def test_graph_replay_is_bit_identical_and_redraws(rt, O, LA):
     chain = [dict(PV_BOTH, prob=0.75)]
-    out = []
-    for use_graph in (True, False):
-        sess, batch, _, _ = session(rt, O, RAGGED, [50, 51], chain, num_iterations=40, use_graph=use_graph)
-        zs, losses = [], []
-        sess.iterate(32)
-        for _ in range(8):
-            sess.iterate(1)
-            zs.append(sess.attacked.clone())
-            losses.append(sess.loss.clone())
-        torch.cuda.synchronize()
-        out.append((sess.coef.cpu(), sess.best_coef.cpu(), sess.best_loss.cpu(), torch.stack(losses).cpu(), torch.stack(zs).cpu()))
-        assert int(sess.step.cpu()[0]) == 40
-    for a, b in zip(*out):
-        assert torch.equal(a, b)
+    out, _ = graph_replay_bits(rt, O, chain, RAGGED)
     ds = [drawn(LA, chain, 0, s) for s in range(32, 40)]
     assert len(set(ds)) >= 5, ds
-    assert len({out[0][4][i].numpy().tobytes() for i in range(8)}) >= 5
+    assert len({out[4][i].numpy().tobytes() for i in range(8)}) >= 5
 
 
-PV = (6, 0.9, [-9830.0, 9830.0, -5435.0, 5930.0])
 PVQ = (6, 0.75, [-9830.0, 9830.0, 0.0, -1.0])
 PVM = (6, 0.75, [0.0, -1.0, -5435.0, 5930.0])
-PS = (5, 0.75, [-3678.0, 3896.0])
-ST = (4, 0.75, [-9830.0, 9830.0])
-SP = (3, 0.75, [-3678.0, 3896.0])
-RV = (2, 1.0, [1600.0, 8000.0, -3.0])
-NO = (0, 1.0, [10.0])
-SU = (1, 1.0, [4800.0])
 
 
 def test_workspace_bytes(rt, O):
     """The seven older chains need what they needed; a chain with the kind needs what the same chain with a speed change in its
     place needs and the two spectra of [total frames][520] complex values, each starting on a multiple of 256 bytes."""
-    sess, batch, _, _ = session(rt, O, RAGGED, [64, 65], None, num_iterations=20, use_graph=False)
-    lib = sess.lib
-    size = lambda ent: lib.aware_embed_loop_attack_workspace_bytes_ex(batch.h, ex_entries(ent), len(ent))
-    nb = {name: size(ent)
-          for name, ent in (("noise", [NO]), ("noise_suppression", [NO, SU]), ("reverb", [RV]), ("suppression_reverb_noise", [SU, RV, NO]),
-                            ("speed", [SP]), ("noise_speed", [NO, SP]), ("four", [NO, SU, SP, NO]))}
-    assert nb == PARENT_WORKSPACE
-    assert lib.aware_embed_loop_attack_workspace_bytes(batch.h, 2) == PARENT_WORKSPACE["noise_suppression"]
+    size, nb, batch = older_chains_workspace(rt, O)
     spec = batch.total_frames * 520 * 8
     spectra = (spec + 255) // 256 * 256 + spec
     print(f"workspace bytes: speed change {size([SP])}, phase vocoder {size([PV])}, two spectra {spectra}")
@@ -466,23 +341,7 @@ def test_entry_point_error_codes(rt, O):
 def test_stereo_service_round_trip_with_the_card_key(rt, tmp_path):
     """load() of a card with the phase vocoder in loop_attacks, then embed_watermark / detect_watermark on a stereo clip: every
     channel carries the payload."""
-    from aware_amd.embedding.loop_attacks import parse_chain
-    from aware_amd.service import detect_watermark, embed_watermark
-    from aware_amd.utils.models import load
-    with open(os.path.join(ROOT, "aware_amd", "cards", "config.yaml")) as f:
-        card = yaml.safe_load(f)
-    card["loop_attacks"] = yaml.safe_load("[{kind: phase_vocoder, rate: [0.85, 1.15], cents: 150.0, prob: 0.9}]")
-    p = tmp_path / "card.yaml"
-    p.write_text(yaml.safe_dump(card))
-    emb, det = load(str(p))
-    assert emb.loop_attacks == parse_chain([dict(PV_BOTH, prob=0.9)])
-    bits = np.random.default_rng(29).integers(0, 2, 20).astype(np.int32)
-    stereo = np.column_stack([make_clip(51, 16000)[0], make_clip(52, 16000)[0]])
-    out = embed_watermark(stereo, 16000, bits, emb)
-    assert out.shape[1] == 2 and np.isfinite(out).all()
-    got = detect_watermark(out, 16000, det)
-    for ch in (got if isinstance(got, (list, tuple)) else [got]):
-        np.testing.assert_array_equal(np.asarray(ch).reshape(-1)[:20].astype(np.int32), bits)
+    stereo_round_trip(tmp_path, "[{kind: phase_vocoder, rate: [0.85, 1.15], cents: 150.0, prob: 0.9}]", dict(PV_BOTH, prob=0.9))
 
 
 # ---- 6. the value claim on the device ---------------------------------------------------------------------------------------------
@@ -492,29 +351,9 @@ def test_value_claim_on_the_device(rt, O, tmp_path):
     host test's asserts: clean 0 %; plain means at least 25 % and 10 %; the stretch-aware stretch mean at most half the plain
     one; the pitch-aware pitch mean at most two thirds of the plain one; both keys meet both.  Figures: DESIGN.md section 20."""
     from aware_amd import attacks as A
-    from aware_amd.utils.models import load
-    from aware_amd.embedding.loop_attacks import parse_chain
     from test_loop_pv_host import CHAINS as VALUE_CHAINS, RATES, CENTS
     from test_loop_speed_host import snr_db
-    with open(os.path.join(ROOT, "aware_amd", "cards", "config.yaml")) as f:
-        card = yaml.safe_load(f)
-    pairs = [make_clip(s, 16000) for s in range(4)]
-    clips, bits = [p[0] for p in pairs], np.stack([p[1] for p in pairs])
-    wm = np.stack([O.bits_to_bipolar(b) for b in bits]).astype(np.float32)
-
-    def embed(chain):
-        c = dict(card)
-        if chain:
-            c["loop_attacks"] = chain
-        p = tmp_path / "card.yaml"
-        p.write_text(yaml.safe_dump(c))
-        emb, det = load(str(p))
-        assert emb.loop_attacks == parse_chain(chain)
-        return [o.cpu().numpy() for o in emb.embed_batch(clips, 16000, wm)], det
-
-    def ber(det, ys):
-        vals = det.detect_batch(ys.to_list() if hasattr(ys, "to_list") else ys, 16000).cpu().numpy()
-        return 100.0 * float((O.decode_bits(vals) != bits).mean())
+    clips, bits, embed, ber = value_claim_setup(O, tmp_path)
 
     ys = {}
     ys["plain"], det = embed(None)

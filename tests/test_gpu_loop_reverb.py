@@ -7,23 +7,19 @@ of 600, 2048, 2049 and 8192 taps (one partition, exactly one, one tap more, all 
 
 Run on the MI355X box:  python -m pytest tests/test_gpu_loop_reverb.py -m gpu -q -s"""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 import torch
-import yaml
 
-from conftest import ROOT, make_clip
-from test_gpu_loop_attacks import attacked, check_first_gradient, norm2, sampled, session, synthesis
+from loop_support import CHAIN_BOUND, LA, NOISE10, O, RV, SUP, attacked, check_first_gradient, ex_entries, graph_replay_bits
+from loop_support import norm2, prob_0_is_the_plain_loop, rt, sampled, session, synthesis, value_claim_setup
 
 pytestmark = pytest.mark.gpu
 
 # rt60 in seconds -> taps at 16 kHz; every test that uses one asserts int(rt60 * 16000)
 RT60 = {600: 0.0375, 2048: 0.128, 2049: 0.12807, 8192: 0.512}
 UNIFORM, RAGGED = [8000] * 4, [8000, 16000, 40000]
-NOISE10 = {"kind": "gaussian_noise", "snr_db": 10.0}
-SUP = {"kind": "sample_suppression", "seconds": 0.3}
 
 # Largest error of the device against the float64 reference as a fraction of each clip's reference peak: four times the
 # largest value measured over the cases of the test (for input dependence), and never above CAP = 5e-6 -- 1.6e-7 per rfft and
@@ -32,7 +28,7 @@ SUP = {"kind": "sample_suppression", "seconds": 0.3}
 # over the ninety comparisons of buffer 12 with the restatement.
 CAP = 5e-6
 CONV_BOUND = 1.2e-6
-CHAIN_BOUND = 1.13e-6
+assert CHAIN_BOUND == 1.13e-6                              # four times the 2.81e-7 above, rounded; held by every later kind as well
 # The device draws its normals in f32: each within 8 ulp of its magnitude (log, sqrt, sincospi and a product; the largest of
 # 8192 draws is below 5.5: 8 * 2^-23 * 5.5 = 5.2e-6), under an envelope <= 1.  The direct path is a root of their sum of
 # squares (f64, fixed order): at worst all 8 ulp one way, and the rounding of the result to f32.
@@ -55,26 +51,6 @@ def reverb(taps=None, **kw):
 def chains(taps=None, **kw):
     r = reverb(taps, **kw)
     return {"reverb": [r], "reverb_noise": [r, NOISE10], "suppression_reverb": [SUP, r]}
-
-
-@pytest.fixture(scope="module")
-def rt():
-    from aware_amd import runtime
-    from aware_amd._lib import require_gpu
-    require_gpu()
-    return runtime
-
-
-@pytest.fixture(scope="module")
-def O():
-    from oracle import aware_oracle
-    return aware_oracle
-
-
-@pytest.fixture(scope="module")
-def LA():
-    from aware_amd.embedding import loop_attacks
-    return loop_attacks
 
 
 def responses(LA, seeds, step, entry, taps, drr=-3.0):
@@ -257,23 +233,8 @@ def test_first_gradient_f32_dense(rt, O, LA):
 @pytest.mark.parametrize("lengths", [UNIFORM, RAGGED], ids=["uniform", "ragged"])
 def test_graph_replay_is_bit_identical_and_redraws(rt, O, lengths):
     chain = [reverb(None, prob=0.75), NOISE10]
-    out = []
-    for use_graph in (True, False):
-        sess, batch, _, _ = session(rt, O, lengths, list(range(50, 50 + len(lengths))), chain, num_iterations=40, use_graph=use_graph)
-        zs, hs, losses = [], [], []
-        sess.iterate(32)
-        for _ in range(8):
-            sess.iterate(1)
-            zs.append(sess.attacked.clone())
-            hs.append(sess.impulse_responses.clone())
-            losses.append(sess.loss.clone())
-        torch.cuda.synchronize()
-        out.append((sess.coef.cpu(), sess.best_coef.cpu(), sess.best_loss.cpu(), torch.stack(losses).cpu(), torch.stack(zs).cpu(),
-                    torch.stack(hs).cpu()))
-        assert int(sess.step.cpu()[0]) == 40
-    for a, b in zip(*out):
-        assert torch.equal(a, b)
-    hs = out[0][5]
+    out, _ = graph_replay_bits(rt, O, chain, lengths, more=("impulse_responses",))
+    hs = out[5]
     for i in range(7):
         assert float((hs[i + 1] - hs[i]).abs().max()) > 1e-2        # the draw is keyed by the device step counter
 
@@ -285,36 +246,15 @@ def test_prob_0_is_the_plain_loop(rt, O):
     N(N(y)) (buffer 12), its maxima are recorded as 1, so the analysis' normalisers are the identity, and the backward stages
     pass the synthesis adjoint's gradient, partial sums and reflect pads through.  (A first version ran the normalisers'
     backward twice for such a clip and differed from the plain loop by 9.2e-5 in the coefficients after 20 steps.)"""
-    lengths = [8000, 16000, 24000]
-    for dsp_path in ("stream", "staged"):
-        plain, _, _, _ = session(rt, O, lengths, [62, 63, 64], None, num_iterations=21, dsp_path=dsp_path)
-        plain.iterate(20)
-        gp = plain.gradient()
-        for chain in ([reverb(None, prob=0.0)], [dict(SUP, prob=0.0), reverb(8192, prob=0.0), dict(NOISE10, prob=0.0)]):
-            att, batch, _, _ = session(rt, O, lengths, [62, 63, 64], chain, num_iterations=21, dsp_path=dsp_path)
-            att.iterate(20)
-            ga = att.gradient()
-            torch.cuda.synchronize()
-            for z, y in zip(attacked(att, batch), synthesis(att, batch)):
-                assert float((z.double() - norm2(y.double())).abs().max()) < 2e-7
-            print(f"{dsp_path}, prob 0 against the plain loop after 20 steps: max |coef difference| = "
-                  f"{float((plain.coef - att.coef).abs().max()):.3e}, loss difference {float((plain.loss - att.loss).abs().max()):.3e}")
-            assert torch.equal(plain.coef, att.coef) and torch.equal(plain.best_coef, att.best_coef)
-            assert torch.equal(plain.loss, att.loss) and torch.equal(plain.best_loss, att.best_loss)
-            assert torch.equal(gp, ga)
+    prob_0_is_the_plain_loop(rt, O, ([reverb(None, prob=0.0)], [dict(SUP, prob=0.0), reverb(8192, prob=0.0), dict(NOISE10, prob=0.0)]))
 
 
 def test_entry_point_error_codes_and_old_kinds(rt, O):
-    from aware_amd._lib import LoopAttack, LoopAttackEx
+    from aware_amd._lib import LoopAttack
     lengths = [16000, 8000]
     sess, batch, _, _ = session(rt, O, lengths, [64, 65], None, num_iterations=20, use_graph=False)
     lib = sess.lib
-
-    def ex(entries):
-        return (LoopAttackEx * max(1, len(entries)))(*[LoopAttackEx(k, pr, (C.c_float * 4)(*(list(p) + [0.0] * (4 - len(p)))))
-                                                       for k, pr, p in entries])
-
-    rv = (2, 1.0, [1600.0, 8000.0, -3.0])
+    ex, rv = ex_entries, RV
     nb_old = lib.aware_embed_loop_attack_workspace_bytes(batch.h, 1)
     nb0 = lib.aware_embed_loop_attack_workspace_bytes_ex(batch.h, ex([(0, 1.0, [10.0])]), 1)
     nb = lib.aware_embed_loop_attack_workspace_bytes_ex(batch.h, ex([rv]), 1)
@@ -366,28 +306,8 @@ def test_value_claim_on_the_device(rt, O, tmp_path):
     three fixed responses of rt60 0.3 s from numpy's generator (the CPU test's) the plain BER is at least 10 % and the
     reverberation-aware one at most half of it; the same under the echo y[1600:] += 0.7 y[:-1600].  Measured: 40.42 % against 11.67 % under the
     responses, 30.00 % against 6.25 % under the echo, clean 0 % for both."""
-    from aware_amd.utils.models import load
-    from aware_amd.embedding.loop_attacks import parse_chain
     from test_loop_reverb_host import AWARE_CHAIN, room_response
-    with open(os.path.join(ROOT, "aware_amd", "cards", "config.yaml")) as f:
-        card = yaml.safe_load(f)
-    pairs = [make_clip(s, 16000) for s in range(4)]
-    clips, bits = [p[0] for p in pairs], np.stack([p[1] for p in pairs])
-    wm = np.stack([O.bits_to_bipolar(b) for b in bits]).astype(np.float32)
-
-    def embed(chain):
-        c = dict(card)
-        if chain:
-            c["loop_attacks"] = chain
-        p = tmp_path / "card.yaml"
-        p.write_text(yaml.safe_dump(c))
-        emb, det = load(str(p))
-        assert emb.loop_attacks == parse_chain(chain)
-        return [o.cpu().numpy() for o in emb.embed_batch(clips, 16000, wm)], det
-
-    def ber(det, ys):
-        vals = det.detect_batch(ys.to_list() if hasattr(ys, "to_list") else ys, 16000).cpu().numpy()
-        return 100.0 * float((O.decode_bits(vals) != bits).mean())
+    clips, bits, embed, ber = value_claim_setup(O, tmp_path)
 
     def rooms(det, ys):
         x = rt.Ragged.from_list(ys)

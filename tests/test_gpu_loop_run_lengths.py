@@ -19,15 +19,17 @@ import pytest
 import torch
 
 from conftest import make_clip
-from test_gpu_loop_attacks import check_forward as forward_01, det_for, plan_for
+from loop_support import KINK, LA, NOISE10, O, det_for, mixture_session, oracle_gradient, plan_for, rows, rt, span, weights
+# this module is about every kind at once: each kind's entries and its forward check come from the module that owns them
+from test_gpu_loop_attacks import check_forward as forward_01
 from test_gpu_loop_reverb import check_forward as forward_reverb, reverb
 from test_gpu_loop_speed import SPEED, check_forward as forward_speed
 from test_gpu_loop_stretch import CHAINS as STRETCH_CHAINS, STRETCH, check_forward as forward_stretch
 from test_gpu_loop_pitch import PITCH, check_forward as forward_pitch
-from test_gpu_loop_pv import KINK, PV_BOTH, check_forward as forward_pv, oracle_gradient
+from test_gpu_loop_pv import PV_BOTH, check_forward as forward_pv
 from test_gpu_loop_delete import ANY, CROP, check_forward as forward_delete
 from test_gpu_loop_gain import ENV_SHORT
-from test_gpu_loop_filter import BF, NOISE10, SUP, check_forward as forward_filter
+from test_gpu_loop_filter import BF, SUP, check_forward as forward_filter
 from test_loop_run_rule_host import BATCHES, HEAD, expected_synth_run
 
 pytestmark = pytest.mark.gpu
@@ -87,26 +89,6 @@ SEEDS = {
     "four": {18432: 81, 16000: 80, 8000: 81, 24000: 82, 513: None},
 }
 DEFAULT_SEED = 80
-
-
-@pytest.fixture(scope="module")
-def rt():
-    from aware_amd import runtime
-    from aware_amd._lib import require_gpu
-    require_gpu()
-    return runtime
-
-
-@pytest.fixture(scope="module")
-def O():
-    from oracle import aware_oracle
-    return aware_oracle
-
-
-@pytest.fixture(scope="module")
-def LA():
-    from aware_amd.embedding import loop_attacks
-    return loop_attacks
 
 
 # ---- the batches ----------------------------------------------------------------------------------------------------------------
@@ -244,7 +226,7 @@ GRADIENT_CASES = [("R12", c, d) for c in CHAINS for d in ("stream", "staged")] +
 @pytest.mark.parametrize("bname,cname,dsp_path", GRADIENT_CASES, ids=[f"{b}-{c}-{d}" for b, c, d in GRADIENT_CASES])
 def test_first_gradient(rt, O, LA, bname, cname, dsp_path):
     """aware_embed_gradient, loss and prediction of the compared clips against autograd over the float64 restatement composed
-    with the oracle's loop body, by the rule of test_gpu_loop_pv.check_gradient: within four times the float32 composition's own
+    with the oracle's loop body, by the rule of loop_support.check_gradient: within four times the float32 composition's own
     distance from the float64 one, at least 2e-5 (gradient, relative L2) and 1e-6 (loss, prediction); no compared clip within
     KINK of a LeakyReLU kink in either precision."""
     lengths = BATCHES[bname][0]
@@ -343,7 +325,6 @@ def test_a_mixture_is_its_chains(rt, O, LA):
     """A mixture of [pitch shift, noise] and [envelope of 64 samples] on R12 at step 0 against, per head clip, a session on the
     same batch that holds only the chain the clip drew: buffers 12 and 9, loss, prediction and the rows of the gradient, bit
     for bit."""
-    from test_gpu_loop_mixture import rows, session as mix_session, span, weights
     lengths, run = BATCHES["R12"]
     mixture = LA.parse_mixture([{"weight": 0.5, "chain": [PITCH, NOISE10]}, {"weight": 0.5, "chain": [ENV_SHORT]}])
     s0 = 0
@@ -352,14 +333,14 @@ def test_a_mixture_is_its_chains(rt, O, LA):
     seeds = list(range(s0, s0 + len(lengths)))
     choice = LA.mixture_choices(seeds[:len(HEAD)], 0, weights(mixture))
     kw = dict(num_iterations=4)
-    mix, batch = mix_session(rt, O, lengths, seeds, mixture=mixture, **kw)
+    mix, batch = mixture_session(rt, O, lengths, seeds, mixture=mixture, **kw)
     assert batch.synth_run == run
     g = mix.gradient()
     torch.cuda.synchronize()
     np.testing.assert_array_equal(mix.choices.cpu().numpy()[:len(HEAD)], choice)
     z, y, loss, pred = mix.attacked.clone(), mix._view(9, (batch.total_out,)).clone(), mix.loss.clone(), mix.pred.clone()
     for c in (0, 1):
-        one, _ = mix_session(rt, O, lengths, seeds, chain=mixture[c]["chain"], **kw)
+        one, _ = mixture_session(rt, O, lengths, seeds, chain=mixture[c]["chain"], **kw)
         g1 = one.gradient()
         torch.cuda.synchronize()
         y1 = one._view(9, (batch.total_out,))

@@ -7,25 +7,20 @@ Shapes: clips [8000] * 2 (7936 output samples), [16000] * 2 (15872, more than on
 
 Run on the MI355X box:  python -m pytest tests/test_gpu_loop_speed.py -m gpu -q -s"""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 import torch
-import yaml
 
-from conftest import ROOT, make_clip
-from test_gpu_loop_attacks import attacked, attacked_oracle, norm2, sampled, session, synthesis
-from test_gpu_loop_reverb import CAP as CHAIN_CAP, CHAIN_BOUND
+from loop_support import CHAIN_BOUND, LA, LONG, NOISE10, O, RAGGED, RV, SHORT, SUP, ex_entries, first_gradient
+from loop_support import forward_at_steps_0_2_17, graph_replay_bits, norm2, prob_0_is_the_plain_loop, rt, sampled, session
+from loop_support import step_0_is_the_stand_alone_entry, value_claim_setup
 
 pytestmark = pytest.mark.gpu
 
 M_MIN, M_MAX = -13520, 17034                               # ceil / floor of 65536 (2^(-+400 / 1200) - 1)
 M_MID = 3000
-SHORT, LONG, RAGGED = [8000] * 2, [16000] * 2, [16000, 8000]
 SPEED = {"kind": "speed_change", "cents": 200.0}
-NOISE10 = {"kind": "gaussian_noise", "snr_db": 10.0}
-SUP = {"kind": "sample_suppression", "seconds": 0.3}
 CHAINS = {"speed": [SPEED], "speed_noise": [SPEED, NOISE10], "suppression_speed": [SUP, SPEED]}
 
 # Largest error of the stand-alone operator against the float64 restatement on the same f32 operands, as a fraction of each
@@ -37,26 +32,7 @@ CHAINS = {"speed": [SPEED], "speed_noise": [SPEED, NOISE10], "suppression_speed"
 # the test (for input dependence): 1.42e-7 over the twelve cases, forward 1.10e-7 and adjoint 1.42e-7 at most.
 CAP = 2e-6
 SPEED_BOUND = 5.7e-7
-
-
-@pytest.fixture(scope="module")
-def rt():
-    from aware_amd import runtime
-    from aware_amd._lib import require_gpu
-    require_gpu()
-    return runtime
-
-
-@pytest.fixture(scope="module")
-def O():
-    from oracle import aware_oracle
-    return aware_oracle
-
-
-@pytest.fixture(scope="module")
-def LA():
-    from aware_amd.embedding import loop_attacks
-    return loop_attacks
+CHAIN_CAP = 5e-6                                           # the reverberation's ceiling for the loop's attacked signal (its CAP)
 
 
 def one_value(LA, m):
@@ -170,16 +146,7 @@ def test_forward_matches_the_restatement(rt, O, LA, lengths, name):
     """Buffer 12 against apply_chain(N(N(buffer 9))) at steps 0, 2 and 17, within the bound of the reverberation's
     corresponding test (1.13e-6 of the peak).  Measured: 1.57e-7 at most over the 81 comparisons."""
     chain = LA.parse_chain(CHAINS[name])
-    seeds = [11 + 3 * i for i in range(len(lengths))]
-    sess, batch, _, _ = session(rt, O, lengths, list(range(20, 20 + len(lengths))), chain, seeds, num_iterations=20)
-    assert sorted(batch.out_lengths)[0] in (7936, 15872)
-    sess.gradient()
-    check_forward(LA, sess, batch, chain, seeds, 0, name)
-    sess.iterate(3)
-    check_forward(LA, sess, batch, chain, seeds, 2, name)
-    sess.iterate(15)
-    assert int(sess.step.cpu()[0]) == 18
-    check_forward(LA, sess, batch, chain, seeds, 17, name)
+    batch, seeds = forward_at_steps_0_2_17(rt, O, LA, chain, lengths, name, check_forward)
     assert len({drawn(LA, chain, seeds[0], s) for s in (0, 2, 17)}) == 3
 
 
@@ -189,20 +156,7 @@ def test_step_0_is_the_stand_alone_entry(rt, O, LA, lengths, m):
     """With a range that holds one offset, buffer 12 at step 0 is aware_speed_change on the same input, bit for bit: the loop's
     kernel and the stand-alone one share their arithmetic.  The input x = N(N(y)) in the device's own rounding is buffer 12
     of a second session whose entry never fires."""
-    e = one_value(LA, m)
-    clips = list(range(30, 30 + len(lengths)))
-    on, batch, _, _ = session(rt, O, lengths, clips, [e], [3, 4])
-    off, _, _, _ = session(rt, O, lengths, clips, [dict(e, prob=0.0)], [3, 4])
-    on.gradient()
-    off.gradient()
-    torch.cuda.synchronize()
-    assert torch.equal(on._view(9, (batch.total_out,)), off._view(9, (batch.total_out,)))
-    x = rt.Ragged(off.attacked.clone(), batch.out_lengths)
-    for xi, y in zip(x.to_list(), synthesis(off, batch)):
-        assert float(np.abs(xi - norm2(y.double()).numpy()).max()) < 2e-7
-    z = rt.speed_change(x, m)
-    assert torch.equal(z.data, on.attacked)
-    assert not torch.equal(z.data, x.data)
+    step_0_is_the_stand_alone_entry(rt, O, lengths, one_value(LA, m), lambda x: rt.speed_change(x, m))
 
 
 # ---- 3. first gradient ----------------------------------------------------------------------------------------------------------
@@ -215,27 +169,10 @@ SEED0 = {"speed": 83, "speed_noise": 80, "suppression_speed": 86, "three": 83}
 
 
 def check_first_gradient(rt, O, LA, chain, lengths, clip_seed0, **kw):
-    from test_gpu_kernels import _min_kink_distance
-    clip_seeds = list(range(clip_seed0, clip_seed0 + len(lengths)))
-    seeds = [5 + 2 * i for i in range(len(lengths))]
-    sess, batch, pairs, wm = session(rt, O, lengths, clip_seeds, chain, seeds, use_graph=False, **kw)
-    g = sess.gradient()
-    torch.cuda.synchronize()
-    g = g.cpu()
-    loss, pred = sess.loss.cpu().numpy(), sess.pred.cpu().numpy()
+    _, seeds, figures = first_gradient(rt, O, LA, chain, lengths, list(range(clip_seed0, clip_seed0 + len(lengths))), **kw)
     near = 0
-    for i, (clip, _) in enumerate(pairs):
-        emb = attacked_oracle(O, LA, chain, seeds[i], 0)
-        mag0, phase = emb.analyse(torch.from_numpy(clip)[None])
-        c0 = mag0[:, emb.band].clone().requires_grad_(True)
-        l, p = emb.forward_loss(c0, mag0, phase, torch.from_numpy(wm[i])[None])
-        l.sum().backward()
-        ref = c0.grad[0]
-        mine = g[batch.frame_offsets[i]: batch.frame_offsets[i + 1], :225].T
-        rel = (mine - ref).norm().item() / ref.norm().item()
-        kink = _min_kink_distance(emb, mag0, phase)
+    for i, (rel, kink, lerr, perr) in enumerate(figures):
         near += int(kink <= KINK)
-        lerr, perr = abs(loss[i] - float(l.detach())), float(np.abs(pred[i] - p[0].detach().numpy()).max())
         print(f"{kw} clip {i} (n = {lengths[i]}, m = {drawn(LA, chain, seeds[i], 0)}): loss err {lerr:.1e}, pred err {perr:.1e}, "
               f"gradient rel L2 {rel:.2e}, nearest LeakyReLU kink {kink:.1e}")
         assert lerr < 1e-5 and perr < 1e-5, (i, lerr, perr)
@@ -267,26 +204,13 @@ def test_first_gradient_f32_dense(rt, O, LA):
 @pytest.mark.parametrize("lengths", [LONG, RAGGED], ids=["long", "ragged"])
 def test_graph_replay_is_bit_identical_and_redraws(rt, O, LA, lengths):
     chain = [dict(SPEED, prob=0.75), NOISE10]
-    out = []
-    for use_graph in (True, False):
-        sess, batch, _, _ = session(rt, O, lengths, list(range(50, 50 + len(lengths))), chain, num_iterations=40, use_graph=use_graph)
-        zs, losses = [], []
-        sess.iterate(32)
-        for _ in range(8):
-            sess.iterate(1)
-            zs.append(sess.attacked.clone())
-            losses.append(sess.loss.clone())
-        torch.cuda.synchronize()
-        out.append((sess.coef.cpu(), sess.best_coef.cpu(), sess.best_loss.cpu(), torch.stack(losses).cpu(), torch.stack(zs).cpu()))
-        assert int(sess.step.cpu()[0]) == 40
-    for a, b in zip(*out):
-        assert torch.equal(a, b)
+    out, batch = graph_replay_bits(rt, O, chain, lengths)
     # the draw is keyed by the device step counter: clip 0 (seed 0) at steps 32..39 is resampled at the offsets the host draws
     ms = [drawn(LA, chain, 0, s) for s in range(32, 40)]
     assert len(set(ms)) >= 6, ms
     n0 = batch.out_lengths[0]
     for i, m in enumerate(ms):
-        z = out[0][4][i, :n0]
+        z = out[4][i, :n0]
         live = LA.speed_length(n0, m)
         if m > 0:
             # behind a faster clip's end there is nothing but the noise entry's draw: far below the signal's level
@@ -297,23 +221,7 @@ def test_prob_0_is_the_plain_loop(rt, O):
     """A speed change that never fires against the loop without a chain: coefficients, best coefficients and losses after 20
     steps and the gradient of step 20, bit for bit, alone and between two older entries that never fire either, on both
     dsp_paths (a clip on which no entry fires takes the plain loop's path, as in chains with a reverberation)."""
-    lengths = [8000, 16000, 24000]
-    for dsp_path in ("stream", "staged"):
-        plain, _, _, _ = session(rt, O, lengths, [62, 63, 64], None, num_iterations=21, dsp_path=dsp_path)
-        plain.iterate(20)
-        gp = plain.gradient()
-        for chain in ([dict(SPEED, prob=0.0)], [dict(SUP, prob=0.0), dict(SPEED, prob=0.0), dict(NOISE10, prob=0.0)]):
-            att, batch, _, _ = session(rt, O, lengths, [62, 63, 64], chain, num_iterations=21, dsp_path=dsp_path)
-            att.iterate(20)
-            ga = att.gradient()
-            torch.cuda.synchronize()
-            for z, y in zip(attacked(att, batch), synthesis(att, batch)):
-                assert float((z.double() - norm2(y.double())).abs().max()) < 2e-7
-            print(f"{dsp_path}, prob 0 against the plain loop after 20 steps: max |coef difference| = "
-                  f"{float((plain.coef - att.coef).abs().max()):.3e}, loss difference {float((plain.loss - att.loss).abs().max()):.3e}")
-            assert torch.equal(plain.coef, att.coef) and torch.equal(plain.best_coef, att.best_coef)
-            assert torch.equal(plain.loss, att.loss) and torch.equal(plain.best_loss, att.best_loss)
-            assert torch.equal(gp, ga)
+    prob_0_is_the_plain_loop(rt, O, ([dict(SPEED, prob=0.0)], [dict(SUP, prob=0.0), dict(SPEED, prob=0.0), dict(NOISE10, prob=0.0)]))
 
 
 def test_partly_idle_clips_and_older_kinds_keep_their_bits(rt, O, LA):
@@ -338,17 +246,12 @@ def test_partly_idle_clips_and_older_kinds_keep_their_bits(rt, O, LA):
 
 
 def test_entry_point_error_codes(rt, O):
-    from aware_amd._lib import LoopAttack, LoopAttackEx
+    from aware_amd._lib import LoopAttack
     lengths = [16000, 8000]
     sess, batch, _, _ = session(rt, O, lengths, [64, 65], None, num_iterations=20, use_graph=False)
     lib = sess.lib
-
-    def ex(entries):
-        return (LoopAttackEx * max(1, len(entries)))(*[LoopAttackEx(k, pr, (C.c_float * 4)(*(list(p) + [0.0] * (4 - len(p)))))
-                                                       for k, pr, p in entries])
-
+    ex, rv = ex_entries, RV
     sp = (3, 0.75, [-7150.0, 8025.0])
-    rv = (2, 1.0, [1600.0, 8000.0, -3.0])
     nb_old = lib.aware_embed_loop_attack_workspace_bytes(batch.h, 1)
     nb0 = lib.aware_embed_loop_attack_workspace_bytes_ex(batch.h, ex([(0, 1.0, [10.0]), (1, 1.0, [4800.0])]), 2)
     nb_rv = lib.aware_embed_loop_attack_workspace_bytes_ex(batch.h, ex([rv]), 1)
@@ -395,28 +298,8 @@ def test_value_claim_on_the_device(rt, O, tmp_path):
     46.25 / 20.00; mean of the last four 48.44 % against 11.25 %.  SNR against the normalised host: plain 15.93, 15.12, 15.88,
     16.08 dB; speed-aware 15.66, 15.84, 16.18, 15.53 dB."""
     from aware_amd import attacks as A
-    from aware_amd.utils.models import load
-    from aware_amd.embedding.loop_attacks import parse_chain
     from test_loop_speed_host import AWARE_CHAIN, RATIOS, snr_db
-    with open(os.path.join(ROOT, "aware_amd", "cards", "config.yaml")) as f:
-        card = yaml.safe_load(f)
-    pairs = [make_clip(s, 16000) for s in range(4)]
-    clips, bits = [p[0] for p in pairs], np.stack([p[1] for p in pairs])
-    wm = np.stack([O.bits_to_bipolar(b) for b in bits]).astype(np.float32)
-
-    def embed(chain):
-        c = dict(card)
-        if chain:
-            c["loop_attacks"] = chain
-        p = tmp_path / "card.yaml"
-        p.write_text(yaml.safe_dump(c))
-        emb, det = load(str(p))
-        assert emb.loop_attacks == parse_chain(chain)
-        return [o.cpu().numpy() for o in emb.embed_batch(clips, 16000, wm)], det
-
-    def ber(det, ys):
-        vals = det.detect_batch(ys.to_list() if hasattr(ys, "to_list") else ys, 16000).cpu().numpy()
-        return 100.0 * float((O.decode_bits(vals) != bits).mean())
+    clips, bits, embed, ber = value_claim_setup(O, tmp_path)
 
     y0, det = embed(None)
     y1, _ = embed(AWARE_CHAIN)

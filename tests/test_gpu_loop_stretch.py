@@ -7,26 +7,21 @@ Shapes: clips [8000] * 2 (7936 output samples), [16000] * 2 (15872, more than on
 
 Run on the MI355X box:  python -m pytest tests/test_gpu_loop_stretch.py -m gpu -q -s"""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 import torch
-import yaml
 
-from conftest import ROOT, make_clip
-from test_gpu_loop_attacks import attacked, attacked_oracle, norm2, sampled, session, synthesis
-from test_gpu_loop_reverb import CHAIN_BOUND
+from loop_support import CHAIN_BOUND, KINK, LA, LONG, NO, NOISE10, O, RAGGED, RV, SHORT, SP, ST, SU, SUP, ex_entries
+from loop_support import first_gradient, forward_at_steps_0_2_17, graph_replay_bits, norm2, older_chains_workspace
+from loop_support import prob_0_is_the_plain_loop, rt, sampled, session, step_0_is_the_stand_alone_entry, value_claim_setup
 
 pytestmark = pytest.mark.gpu
 
 M_MIN, M_MAX = -16384, 21845                               # ceil of 65536 (0.75 - 1), floor of 65536 (4 / 3 - 1)
 M_MID = 3000
-SHORT, LONG, RAGGED = [8000] * 2, [16000] * 2, [16000, 8000]
 STRETCH = {"kind": "time_stretch", "rate": [0.85, 1.15]}
 SPEED = {"kind": "speed_change", "cents": 100.0}
-NOISE10 = {"kind": "gaussian_noise", "snr_db": 10.0}
-SUP = {"kind": "sample_suppression", "seconds": 0.3}
 CHAINS = {"stretch": [STRETCH], "stretch_noise": [STRETCH, NOISE10], "suppression_stretch": [SUP, STRETCH],
           "pair": [STRETCH, SPEED]}
 assert CHAIN_BOUND == 1.13e-6                              # the project's bound for the loop's attacked signal (DESIGN 16)
@@ -40,26 +35,6 @@ assert CHAIN_BOUND == 1.13e-6                              # the project's bound
 # 1.16e-7 over the twelve cases, forward 9.01e-8 and adjoint 1.16e-7 at most.
 CAP = 2e-6
 STRETCH_BOUND = 4.7e-7
-
-
-@pytest.fixture(scope="module")
-def rt():
-    from aware_amd import runtime
-    from aware_amd._lib import require_gpu
-    require_gpu()
-    return runtime
-
-
-@pytest.fixture(scope="module")
-def O():
-    from oracle import aware_oracle
-    return aware_oracle
-
-
-@pytest.fixture(scope="module")
-def LA():
-    from aware_amd.embedding import loop_attacks
-    return loop_attacks
 
 
 def one_value(LA, m):
@@ -180,16 +155,7 @@ def test_forward_matches_the_restatement(rt, O, LA, lengths, name):
     """Buffer 12 (sess.attacked) against apply_chain(N(N(buffer 9))) at steps 0, 2 and 17, within the project's bound for the
     loop's attacked signal (1.13e-6 of the peak).  Measured: 1.82e-7 at most over the 72 comparisons."""
     chain = LA.parse_chain(CHAINS[name])
-    seeds = [11 + 3 * i for i in range(len(lengths))]
-    sess, batch, _, _ = session(rt, O, lengths, list(range(20, 20 + len(lengths))), chain, seeds, num_iterations=20)
-    assert sorted(batch.out_lengths)[0] in (7936, 15872)
-    sess.gradient()
-    check_forward(LA, sess, batch, chain, seeds, 0, name)
-    sess.iterate(3)
-    check_forward(LA, sess, batch, chain, seeds, 2, name)
-    sess.iterate(15)
-    assert int(sess.step.cpu()[0]) == 18
-    check_forward(LA, sess, batch, chain, seeds, 17, name)
+    batch, seeds = forward_at_steps_0_2_17(rt, O, LA, chain, lengths, name, check_forward)
     assert len({drawn(LA, chain, seeds[0], s) for s in (0, 2, 17)}) == 3
     if name == "pair":                                                     # tempo and pitch are drawn independently
         assert len({drawn(LA, chain, seeds[0], s, "speed_change") for s in (0, 2, 17)}) == 3
@@ -201,52 +167,22 @@ def test_step_0_is_the_stand_alone_entry(rt, O, LA, lengths, m):
     """With a range that holds one offset, buffer 12 at step 0 is aware_stretch_ola on the same input, bit for bit: the loop's
     kernel and the stand-alone one share their arithmetic.  The input x = N(N(y)) in the device's own rounding is buffer 12
     of a second session whose entry never fires."""
-    e = one_value(LA, m)
-    clips = list(range(30, 30 + len(lengths)))
-    on, batch, _, _ = session(rt, O, lengths, clips, [e], [3, 4])
-    off, _, _, _ = session(rt, O, lengths, clips, [dict(e, prob=0.0)], [3, 4])
-    on.gradient()
-    off.gradient()
-    torch.cuda.synchronize()
-    assert torch.equal(on._view(9, (batch.total_out,)), off._view(9, (batch.total_out,)))
-    x = rt.Ragged(off.attacked.clone(), batch.out_lengths)
-    for xi, y in zip(x.to_list(), synthesis(off, batch)):
-        assert float(np.abs(xi - norm2(y.double()).numpy()).max()) < 2e-7
-    z = rt.stretch_ola(x, m)
-    assert torch.equal(z.data, on.attacked)
-    assert not torch.equal(z.data, x.data)
+    step_0_is_the_stand_alone_entry(rt, O, lengths, one_value(LA, m), lambda x: rt.stretch_ola(x, m))
 
 
 # ---- 3. first gradient ----------------------------------------------------------------------------------------------------------
 # First clip seed of each gradient case, chosen on the CPU so that the float64 restatement keeps every LeakyReLU argument of
 # both clips at least 8e-6 from its kink: stretch, seeds 82 and 83: 1.5e-5 / 5.0e-5 (80 had a clip at 1.3e-6, 81 one at 3.4e-6);
 # pair, seeds 80 and 81: 3.3e-5 / 5.5e-5.
-KINK = 8e-6
+assert KINK == 8e-6
 SEED0 = {"stretch": 82, "pair": 80}
 
 
-def check_gradient(rt, O, LA, chain, lengths, clip_seed0, **kw):
-    """As check_first_gradient of test_gpu_loop_speed.py, with the bounds this operator is held to: relative L2 of the gradient
-    at most 2e-5 for every clip, loss and prediction within 1e-6, and no clip closer than KINK to a LeakyReLU kink."""
-    from test_gpu_kernels import _min_kink_distance
-    clip_seeds = list(range(clip_seed0, clip_seed0 + len(lengths)))
-    seeds = [5 + 2 * i for i in range(len(lengths))]
-    sess, batch, pairs, wm = session(rt, O, lengths, clip_seeds, chain, seeds, use_graph=False, **kw)
-    g = sess.gradient()
-    torch.cuda.synchronize()
-    g = g.cpu()
-    loss, pred = sess.loss.cpu().numpy(), sess.pred.cpu().numpy()
-    for i, (clip, _) in enumerate(pairs):
-        emb = attacked_oracle(O, LA, chain, seeds[i], 0)
-        mag0, phase = emb.analyse(torch.from_numpy(clip)[None])
-        c0 = mag0[:, emb.band].clone().requires_grad_(True)
-        l, p = emb.forward_loss(c0, mag0, phase, torch.from_numpy(wm[i])[None])
-        l.sum().backward()
-        ref = c0.grad[0]
-        mine = g[batch.frame_offsets[i]: batch.frame_offsets[i + 1], :225].T
-        rel = (mine - ref).norm().item() / ref.norm().item()
-        kink = _min_kink_distance(emb, mag0, phase)
-        lerr, perr = abs(loss[i] - float(l.detach())), float(np.abs(pred[i] - p[0].detach().numpy()).max())
+def check_first_gradient(rt, O, LA, chain, lengths, clip_seed0, **kw):
+    """The figures of loop_support.first_gradient, with the bounds this operator is held to: relative L2 of the gradient at most
+    2e-5 for every clip, loss and prediction within 1e-6, and no clip closer than KINK to a LeakyReLU kink."""
+    _, seeds, figures = first_gradient(rt, O, LA, chain, lengths, list(range(clip_seed0, clip_seed0 + len(lengths))), **kw)
+    for i, (rel, kink, lerr, perr) in enumerate(figures):
         ms = [drawn(LA, chain, seeds[i], 0, a["kind"]) for a in LA.parse_chain(chain) if a["kind"] in ("time_stretch", "speed_change")]
         print(f"{kw} clip {i} (n = {lengths[i]}, m = {ms}): loss err {lerr:.1e}, pred err {perr:.1e}, "
               f"gradient rel L2 {rel:.2e}, nearest LeakyReLU kink {kink:.1e}")
@@ -262,33 +198,19 @@ def test_first_gradient(rt, O, LA, name, dsp_path):
     """aware_embed_gradient against torch autograd over the restatement composed with the oracle's loop body, ragged batch:
     2e-5 relative L2 per clip, loss and prediction 1e-6.  Measured over the gradient tests of this file: 3.95e-6 relative L2 at
     most, loss 1.2e-7, prediction 3.9e-7; no clip closer than 1.5e-5 to a kink."""
-    check_gradient(rt, O, LA, CHAINS[name], RAGGED, SEED0[name], dsp_path=dsp_path)
+    check_first_gradient(rt, O, LA, CHAINS[name], RAGGED, SEED0[name], dsp_path=dsp_path)
 
 
 @pytest.mark.parametrize("name", ["stretch", "pair"])
 def test_first_gradient_f32_dense(rt, O, LA, name):
-    check_gradient(rt, O, LA, CHAINS[name], RAGGED, SEED0[name], conv_pipe="f32", mel="dense")
+    check_first_gradient(rt, O, LA, CHAINS[name], RAGGED, SEED0[name], conv_pipe="f32", mel="dense")
 
 
 # ---- 4. graph replay, prob 0, workspace, error codes -------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", ["stretch", "pair"])
 def test_graph_replay_is_bit_identical_and_redraws(rt, O, LA, name):
     chain = [dict(a, prob=0.75) for a in CHAINS[name]]
-    lengths = RAGGED
-    out = []
-    for use_graph in (True, False):
-        sess, batch, _, _ = session(rt, O, lengths, [50, 51], chain, num_iterations=40, use_graph=use_graph)
-        zs, losses = [], []
-        sess.iterate(32)
-        for _ in range(8):
-            sess.iterate(1)
-            zs.append(sess.attacked.clone())
-            losses.append(sess.loss.clone())
-        torch.cuda.synchronize()
-        out.append((sess.coef.cpu(), sess.best_coef.cpu(), sess.best_loss.cpu(), torch.stack(losses).cpu(), torch.stack(zs).cpu()))
-        assert int(sess.step.cpu()[0]) == 40
-    for a, b in zip(*out):
-        assert torch.equal(a, b)
+    out, batch = graph_replay_bits(rt, O, chain, RAGGED)
     # the draw is keyed by the device step counter: clip 0 (seed 0) at steps 32..39 is stretched at the offsets the host draws
     ms = [drawn(LA, chain, 0, s) for s in range(32, 40)]
     assert len(set(ms)) >= 5, ms
@@ -296,62 +218,22 @@ def test_graph_replay_is_bit_identical_and_redraws(rt, O, LA, name):
     if name == "stretch":
         for i, m in enumerate(ms):
             if m > 0:
-                assert float(out[0][4][i, LA.stretch_length(n0, m) + 512:n0].abs().max()) == 0.0
-    assert len({out[0][4][i].numpy().tobytes() for i in range(8)}) >= 5
+                assert float(out[4][i, LA.stretch_length(n0, m) + 512:n0].abs().max()) == 0.0
+    assert len({out[4][i].numpy().tobytes() for i in range(8)}) >= 5
 
 
 def test_prob_0_is_the_plain_loop(rt, O):
     """A stretch that never fires, alone and in front of a speed change that never fires either, against the loop without a
     chain: coefficients, best coefficients and losses after 20 steps and the gradient of step 20, bit for bit, on both
     dsp_paths (a clip on which no entry fires takes the plain loop's path)."""
-    lengths = [8000, 16000, 24000]
-    for dsp_path in ("stream", "staged"):
-        plain, _, _, _ = session(rt, O, lengths, [62, 63, 64], None, num_iterations=21, dsp_path=dsp_path)
-        plain.iterate(20)
-        gp = plain.gradient()
-        for chain in ([dict(STRETCH, prob=0.0)], [dict(SUP, prob=0.0), dict(STRETCH, prob=0.0), dict(SPEED, prob=0.0), dict(NOISE10, prob=0.0)]):
-            att, batch, _, _ = session(rt, O, lengths, [62, 63, 64], chain, num_iterations=21, dsp_path=dsp_path)
-            att.iterate(20)
-            ga = att.gradient()
-            torch.cuda.synchronize()
-            for z, y in zip(attacked(att, batch), synthesis(att, batch)):
-                assert float((z.double() - norm2(y.double())).abs().max()) < 2e-7
-            print(f"{dsp_path}, prob 0 against the plain loop after 20 steps: max |coef difference| = "
-                  f"{float((plain.coef - att.coef).abs().max()):.3e}, loss difference {float((plain.loss - att.loss).abs().max()):.3e}")
-            assert torch.equal(plain.coef, att.coef) and torch.equal(plain.best_coef, att.best_coef)
-            assert torch.equal(plain.loss, att.loss) and torch.equal(plain.best_loss, att.best_loss)
-            assert torch.equal(gp, ga)
-
-
-def ex_entries(entries):
-    from aware_amd._lib import LoopAttackEx
-    return (LoopAttackEx * max(1, len(entries)))(*[LoopAttackEx(k, pr, (C.c_float * 4)(*(list(p) + [0.0] * (4 - len(p)))))
-                                                   for k, pr, p in entries])
-
-
-ST = (4, 0.75, [-9830.0, 9830.0])
-SP = (3, 0.75, [-3678.0, 3896.0])
-RV = (2, 1.0, [1600.0, 8000.0, -3.0])
-NO = (0, 1.0, [10.0])
-SU = (1, 1.0, [4800.0])
-# aware_embed_loop_attack_workspace_bytes_ex for the batch [16000, 8000], computed with the library of the commit before the
-# time stretch: chains without the new kind need exactly these
-PARENT_WORKSPACE = {"noise": 104968, "noise_suppression": 104968, "reverb": 685824, "suppression_reverb_noise": 685824,
-                    "speed": 200448, "noise_speed": 200448, "four": 200448}
+    prob_0_is_the_plain_loop(rt, O, ([dict(STRETCH, prob=0.0)],
+                                     [dict(SUP, prob=0.0), dict(STRETCH, prob=0.0), dict(SPEED, prob=0.0), dict(NOISE10, prob=0.0)]))
 
 
 def test_chains_without_the_kind_need_the_workspace_they_needed(rt, O):
-    sess, batch, _, _ = session(rt, O, RAGGED, [64, 65], None, num_iterations=20, use_graph=False)
-    lib = sess.lib
-    nb = {name: lib.aware_embed_loop_attack_workspace_bytes_ex(batch.h, ex_entries(ent), len(ent))
-          for name, ent in (("noise", [NO]), ("noise_suppression", [NO, SU]), ("reverb", [RV]), ("suppression_reverb_noise", [SU, RV, NO]),
-                            ("speed", [SP]), ("noise_speed", [NO, SP]), ("four", [NO, SU, SP, NO]))}
-    print("workspace bytes:", nb)
-    assert nb == PARENT_WORKSPACE
-    assert lib.aware_embed_loop_attack_workspace_bytes(batch.h, 2) == PARENT_WORKSPACE["noise_suppression"]
+    size, nb, batch = older_chains_workspace(rt, O)
     # the new kind: the one signal u of the speed change; the pair: one more
-    one = lib.aware_embed_loop_attack_workspace_bytes_ex(batch.h, ex_entries([ST]), 1)
-    two = lib.aware_embed_loop_attack_workspace_bytes_ex(batch.h, ex_entries([ST, SP]), 2)
+    one, two = size([ST]), size([ST, SP])
     assert one == nb["speed"] and 4 * batch.total_out <= two - one < 4 * batch.total_out + 256
 
 
@@ -410,29 +292,9 @@ def test_value_claim_on_the_device(rt, O, tmp_path):
     nothing is asserted about it).  SNR against the normalised host, dB: plain 15.93, 15.12, 15.88, 16.08; stretch-aware 15.09,
     13.83, 15.26, 13.98; pair 15.31, 15.49, 16.02, 15.69."""
     from aware_amd import attacks as A
-    from aware_amd.utils.models import load
-    from aware_amd.embedding.loop_attacks import parse_chain
     from test_loop_stretch_host import AWARE_CHAIN, PAIR_CHAIN, RATES, CENTS
     from test_loop_speed_host import snr_db
-    with open(os.path.join(ROOT, "aware_amd", "cards", "config.yaml")) as f:
-        card = yaml.safe_load(f)
-    pairs = [make_clip(s, 16000) for s in range(4)]
-    clips, bits = [p[0] for p in pairs], np.stack([p[1] for p in pairs])
-    wm = np.stack([O.bits_to_bipolar(b) for b in bits]).astype(np.float32)
-
-    def embed(chain):
-        c = dict(card)
-        if chain:
-            c["loop_attacks"] = chain
-        p = tmp_path / "card.yaml"
-        p.write_text(yaml.safe_dump(c))
-        emb, det = load(str(p))
-        assert emb.loop_attacks == parse_chain(chain)
-        return [o.cpu().numpy() for o in emb.embed_batch(clips, 16000, wm)], det
-
-    def ber(det, ys):
-        vals = det.detect_batch(ys.to_list() if hasattr(ys, "to_list") else ys, 16000).cpu().numpy()
-        return 100.0 * float((O.decode_bits(vals) != bits).mean())
+    clips, bits, embed, ber = value_claim_setup(O, tmp_path)
 
     ys = {}
     ys["plain"], det = embed(None)

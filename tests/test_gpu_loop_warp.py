@@ -23,51 +23,26 @@ chunks.  Sessions: clips of 16128 and 16384 samples (64 and 65 frames; 63 and 64
 
 Run on the MI355X box:  python -m pytest tests/test_gpu_loop_warp.py -m gpu -q -s"""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 import torch
-import yaml
 
-from conftest import ROOT, make_clip
-from test_gpu_loop_attacks import attacked, attacked_oracle, norm2, sampled, session, synthesis
-from test_gpu_loop_reverb import CHAIN_BOUND
-from test_gpu_loop_speed import CAP
-from test_gpu_loop_stretch import ex_entries
-from test_gpu_loop_delete import bits_equal
+from loop_support import CHAIN_BOUND, DS, EV, FB, LA, NO, NOISE10, O, PS, PV, RV, SP, ST, SU, SUP, WC, XC, attacked, bits_equal
+from loop_support import ex_entries, first_gradient, forward_at_run_length, mixture_is_its_chains, norm2
+from loop_support import prob_0_is_the_plain_loop, rt, sampled, session, step_0_is_the_stand_alone_entry, synthesis
+from loop_support import value_claim_setup
 
 pytestmark = pytest.mark.gpu
 
 RAGGED = [16128, 16384]                                    # 64 and 65 frames
 TW = {"kind": "time_warp", "depth": 0.04, "period": [0.032, 0.512]}
-NOISE10 = {"kind": "gaussian_noise", "snr_db": 10.0}
-SUP = {"kind": "sample_suppression", "seconds": 0.3}
 ENV = {"kind": "gain_envelope", "period": [0.05, 0.5], "floor": 0.25}
 CHAINS = {"warp": [TW], "noise_warp_noise": [NOISE10, TW, NOISE10], "envelope_warp_suppression": [ENV, TW, SUP]}
-KINK = 1e-6
-assert CAP == 2e-6 and CHAIN_BOUND == 1.13e-6
+KINK = 1e-6                                                # the speed change's rule, not the pv rule's 8e-6
+CAP = 2e-6                                                 # derived above
+assert CHAIN_BOUND == 1.13e-6
 ALONE = [513, 4099, 7937, 16000, 70000]
-
-
-@pytest.fixture(scope="module")
-def rt():
-    from aware_amd import runtime
-    from aware_amd._lib import require_gpu
-    require_gpu()
-    return runtime
-
-
-@pytest.fixture(scope="module")
-def O():
-    from oracle import aware_oracle
-    return aware_oracle
-
-
-@pytest.fixture(scope="module")
-def LA():
-    from aware_amd.embedding import loop_attacks
-    return loop_attacks
 
 
 def drawn(LA, chain, seed, step, ny):
@@ -245,19 +220,12 @@ def test_step_0_is_the_stand_alone_entry(rt, O, LA):
     """Buffer 12 at step 0 is aware_time_warp with the host's draw on the same input, bit for bit: the loop's kernels and the
     stand-alone ones share their arithmetic, and the table kernel's draws are the host's.  The input x = N(N(y)) in the device's
     own rounding is buffer 12 of a second session whose entry never fires, which is therefore a copy."""
-    on, batch, _, _ = session(rt, O, RAGGED, [30, 31], [TW], [3, 4])
-    off, _, _, _ = session(rt, O, RAGGED, [30, 31], [dict(TW, prob=0.0)], [3, 4])
-    on.gradient()
-    off.gradient()
-    torch.cuda.synchronize()
-    assert torch.equal(on._view(9, (batch.total_out,)), off._view(9, (batch.total_out,)))
-    x = rt.Ragged(off.attacked.clone(), batch.out_lengths)
-    for xi, y in zip(x.to_list(), synthesis(off, batch)):
-        assert float(np.abs(xi - norm2(y.double()).numpy()).max()) < 2e-7
-    d = [drawn(LA, [TW], sd, 0, n) for sd, n in zip([3, 4], batch.out_lengths)]
-    assert all(v[0] for v in d)
-    z = rt.time_warp(x, [v[1] for v in d], [v[2] for v in d], [v[3] for v in d])
-    assert torch.equal(z.data, on.attacked) and not torch.equal(z.data, x.data)
+    def alone(x):
+        d = [drawn(LA, [TW], sd, 0, n) for sd, n in zip([3, 4], x.lengths)]
+        assert all(v[0] for v in d)
+        return rt.time_warp(x, [v[1] for v in d], [v[2] for v in d], [v[3] for v in d])
+
+    step_0_is_the_stand_alone_entry(rt, O, RAGGED, TW, alone)
 
 
 # ---- 3. first gradient ----------------------------------------------------------------------------------------------------------
@@ -269,27 +237,10 @@ SEED0 = {"warp": 80, "noise_warp_noise": 81, "envelope_warp_suppression": 80}
 
 
 def check_first_gradient(rt, O, LA, chain, lengths, clip_seed0, **kw):
-    from test_gpu_kernels import _min_kink_distance
-    clip_seeds = list(range(clip_seed0, clip_seed0 + len(lengths)))
-    seeds = [5 + 2 * i for i in range(len(lengths))]
-    sess, batch, pairs, wm = session(rt, O, lengths, clip_seeds, chain, seeds, use_graph=False, **kw)
-    g = sess.gradient()
-    torch.cuda.synchronize()
-    g = g.cpu()
-    loss, pred = sess.loss.cpu().numpy(), sess.pred.cpu().numpy()
+    batch, seeds, figures = first_gradient(rt, O, LA, chain, lengths, list(range(clip_seed0, clip_seed0 + len(lengths))), **kw)
     near = 0
-    for i, (clip, _) in enumerate(pairs):
-        emb = attacked_oracle(O, LA, chain, seeds[i], 0)
-        mag0, phase = emb.analyse(torch.from_numpy(clip)[None])
-        c0 = mag0[:, emb.band].clone().requires_grad_(True)
-        l, p = emb.forward_loss(c0, mag0, phase, torch.from_numpy(wm[i])[None])
-        l.sum().backward()
-        ref = c0.grad[0]
-        mine = g[batch.frame_offsets[i]: batch.frame_offsets[i + 1], :225].T
-        rel = (mine - ref).norm().item() / ref.norm().item()
-        kink = _min_kink_distance(emb, mag0, phase)
+    for i, (rel, kink, lerr, perr) in enumerate(figures):
         near += int(kink <= KINK)
-        lerr, perr = abs(loss[i] - float(l.detach())), float(np.abs(pred[i] - p[0].detach().numpy()).max())
         on, e, ph, m = drawn(LA, chain, seeds[i], 0, batch.out_lengths[i])
         print(f"{kw} clip {i} (n = {lengths[i]}, fires {on}, e = {e}, ph = {ph}): loss err {lerr:.1e}, pred err {perr:.1e}, "
               f"gradient rel L2 {rel:.2e}, nearest LeakyReLU kink {kink:.1e}")
@@ -312,19 +263,8 @@ def test_first_gradient(rt, O, LA, name, dsp_path):
 def test_prob_0_is_the_plain_loop(rt, O):
     """A time warp that never fires against the loop without a chain: coefficients, best coefficients and losses after 20 steps
     and the gradient of step 20, bit for bit, alone and between two older entries that never fire either, on both dsp_paths."""
-    lengths = [8000, 16128, 16384]
-    for dsp_path in ("stream", "staged"):
-        plain, _, _, _ = session(rt, O, lengths, [62, 63, 64], None, num_iterations=21, dsp_path=dsp_path)
-        plain.iterate(20)
-        gp = plain.gradient()
-        for chain in ([dict(TW, prob=0.0)], [dict(SUP, prob=0.0), dict(TW, prob=0.0), dict(NOISE10, prob=0.0)]):
-            att, batch, _, _ = session(rt, O, lengths, [62, 63, 64], chain, num_iterations=21, dsp_path=dsp_path)
-            att.iterate(20)
-            ga = att.gradient()
-            torch.cuda.synchronize()
-            assert torch.equal(plain.coef, att.coef) and torch.equal(plain.best_coef, att.best_coef)
-            assert torch.equal(plain.loss, att.loss) and torch.equal(plain.best_loss, att.best_loss)
-            assert torch.equal(gp, ga)
+    prob_0_is_the_plain_loop(rt, O, ([dict(TW, prob=0.0)], [dict(SUP, prob=0.0), dict(TW, prob=0.0), dict(NOISE10, prob=0.0)]),
+                             lengths=[8000, 16128, 16384])
 
 
 def test_a_clip_that_does_not_fire_keeps_its_bits(rt, O, LA):
@@ -381,33 +321,8 @@ def test_a_mixture_is_its_chains(rt, O, LA):
     """A mixture of {time warp, noise} and {reverberation} at step 0: buffer 14 holds the host's choices, and every clip's buffer
     12 (with buffer 9, loss, prediction and its rows of the coefficient gradient) is bit for bit that of a session that holds only
     the chain the clip drew; the clips of the warp chain are within CHAIN_BOUND of the float64 restatement."""
-    from test_gpu_loop_mixture import rows, session as mix_session, span
-    lengths = [16128, 8000, 16384, 8000]
-    mixture = LA.parse_mixture([{"weight": 0.5, "chain": [TW, NOISE10]}, {"weight": 0.5, "chain": [{"kind": "reverberation", "rt60": [0.1, 0.3]}]}])
-    s0 = 0
-    while set(LA.mixture_choices(list(range(s0, s0 + 4)), 0, [0.5, 0.5]).tolist()) != {0, 1}:
-        s0 += 1
-    seeds = list(range(s0, s0 + 4))
-    choice = LA.mixture_choices(seeds, 0, [0.5, 0.5])
-    kw = dict(num_iterations=4)
-    mix, batch = mix_session(rt, O, lengths, seeds, mixture=mixture, **kw)
-    g = mix.gradient()
-    torch.cuda.synchronize()
-    np.testing.assert_array_equal(mix.choices.cpu().numpy(), choice)
-    z, y, loss, pred = mix.attacked.clone(), mix._view(9, (batch.total_out,)).clone(), mix.loss.clone(), mix.pred.clone()
-    for c in (0, 1):
-        one, _ = mix_session(rt, O, lengths, seeds, chain=mixture[c]["chain"], **kw)
-        g1 = one.gradient()
-        torch.cuda.synchronize()
-        y1 = one._view(9, (batch.total_out,))
-        for b in np.flatnonzero(choice == c):
-            assert torch.equal(y[span(batch, b)], y1[span(batch, b)]) and torch.equal(z[span(batch, b)], one.attacked[span(batch, b)]), (b, c)
-            assert torch.equal(loss[b], one.loss[b]) and torch.equal(pred[b], one.pred[b]), (b, c)
-            assert torch.equal(g[rows(batch, b)], g1[rows(batch, b)]) and float(g[rows(batch, b)].abs().max()) > 0.0, (b, c)
-    for b in np.flatnonzero(choice == 0):
-        yb, zb = y[span(batch, b)].cpu(), z[span(batch, b)].cpu()
-        ref = LA.apply_chain(norm2(yb.double())[None], mixture[0]["chain"], [seeds[b]], 0)[0]
-        assert float((zb.double() - ref).abs().max() / ref.abs().max()) < CHAIN_BOUND, b
+    mixture_is_its_chains(rt, O, LA, [TW, NOISE10], [{"kind": "reverberation", "rt60": [0.1, 0.3]}], lengths=[16128, 8000, 16384, 8000],
+                          bound=CHAIN_BOUND)
 
 
 @pytest.mark.parametrize("bname", ["R12", "R8", "R6"])
@@ -416,33 +331,10 @@ def test_forward_at_every_synthesis_run_length(rt, O, LA, bname):
     this module runs at 4): buffer 12 of the five head clips (18432, 16000, 8000, 24000 and 513 samples) at steps 0 and 2 within
     CHAIN_BOUND of the restatement on N(N(buffer 9)).  A workgroup's share of a clip then spans up to 3072 samples, several
     segments of the finest period."""
-    from test_gpu_loop_run_lengths import COMPARED, big_session
-    chain = LA.parse_chain([TW])
-    sess, batch, seeds = big_session(rt, O, bname, "warp", chain=chain, num_iterations=4)
-    sess.gradient()
-    check_forward(LA, sess, batch, chain, seeds, 0, f"{bname} warp", sample=COMPARED[bname])
-    sess.iterate(3)
-    assert int(sess.step.cpu()[0]) == 3
-    check_forward(LA, sess, batch, chain, seeds, 2, f"{bname} warp", sample=COMPARED[bname])
-    z = sess.attacked
-    assert bool(torch.isfinite(z).all()) and float(z.abs().max()) > 0.0
+    forward_at_run_length(rt, O, LA, bname, "warp", LA.parse_chain([TW]), check_forward)
 
 
 # ---- 5. workspace and error codes -------------------------------------------------------------------------------------------------
-WC = (11, 0.75, [9.0, 13.0, 2621.0, 0.0])
-XC = (10, 0.75, [3000.0, 10000.0, 0.0, 0.0])
-FB = (9, 0.75, [15.0, 2458.0, 15565.0, 1638.0])
-DS = (7, 0.75, [1.0, 512.0, 0.0])
-PV = (6, 0.9, [-9830.0, 9830.0, -5435.0, 5930.0])
-PS = (5, 0.75, [-3678.0, 3896.0])
-ST = (4, 0.75, [-9830.0, 9830.0])
-SP = (3, 0.75, [-3678.0, 3896.0])
-RV = (2, 1.0, [1600.0, 8000.0, -3.0])
-NO = (0, 1.0, [10.0])
-SU = (1, 1.0, [4800.0])
-EV = (8, 0.75, [800.0, 8000.0, 0.25])
-
-
 def test_entry_point_error_codes(rt, O, LA):
     from aware_amd._lib import LoopAttack
     sess, batch, _, _ = session(rt, O, RAGGED, [64, 65], None, num_iterations=20, use_graph=False)
@@ -514,30 +406,14 @@ def test_value_claim_on_the_device(rt, O, tmp_path):
     bounds: clean 0 % for all three, the plain mean at least 10 %, the warp-aware mean at most half of it and below the
     speed-aware mean.  Measured: means 40.62 / 16.41 / 5.00 % at depth 0.03, every cell 0 % at depth 0.01 (printed), clean 0 %,
     SNR 15.8 / 15.2 / 15.1 dB; the cells are in DESIGN.md section 35."""
-    from aware_amd.utils.models import load
-    from aware_amd.embedding.loop_attacks import parse_chain
     from test_loop_warp_host import AWARE_CHAIN, SPEED_CHAIN, flutter_table, report
     from test_loop_gain_host import snr_db
-    with open(os.path.join(ROOT, "aware_amd", "cards", "config.yaml")) as f:
-        card = yaml.safe_load(f)
-    pairs = [make_clip(s, 16000) for s in range(4)]
-    clips, bits = [p[0] for p in pairs], np.stack([p[1] for p in pairs])
-    wm = np.stack([O.bits_to_bipolar(b) for b in bits]).astype(np.float32)
-
-    def embed(chain):
-        c = dict(card)
-        if chain:
-            c["loop_attacks"] = chain
-        p = tmp_path / "card.yaml"
-        p.write_text(yaml.safe_dump(c))
-        emb, det = load(str(p))
-        assert emb.loop_attacks == parse_chain(chain)
-        return np.stack([o.cpu().numpy() for o in emb.embed_batch(clips, 16000, wm)]), det
+    clips, bits, embed, _ = value_claim_setup(O, tmp_path)
 
     ys, det = [], None
     for chain in (None, SPEED_CHAIN, AWARE_CHAIN):
         y, det = embed(chain)
-        ys.append(y)
+        ys.append(np.stack(y))
 
     def read(z):
         vals = det.detect_batch(list(z), 16000).cpu().numpy()

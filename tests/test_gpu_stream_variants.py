@@ -55,8 +55,7 @@ import pytest
 import torch
 
 from conftest import make_clip
-from test_gpu_loop_attacks import det_for, plan_for
-from test_gpu_loop_pv import KINK
+from loop_support import KINK, det_for, plan_for
 from test_gpu_wide_band import KINK_REL, _det, _oracle_first, _plan
 from test_loop_run_rule_host import HEAD, expected_synth_run
 from test_stream_variants_host import ALL_BATCHES, expected_analysis_run

@@ -16,8 +16,8 @@ from conftest import make_clip
 from test_detector_sizes_host import CARD, oracle_net
 from test_detector_variants_host import VariantDetector
 
-KINK = 8e-6            # the project's distance from a LeakyReLU kink (test_gpu_loop_pv.py)
-FLOOR = 2e-5           # the least bound on a relative L2 distance or a loss (test_gpu_loop_pv.py, test_gpu_seam.py)
+KINK = 8e-6            # the project's distance from a LeakyReLU kink (tests/loop_support.py)
+FLOOR = 2e-5           # the least bound on a relative L2 distance or a loss (loop_support.check_gradient, test_gpu_seam.py)
 
 NETWORKS = {
     "card": dict(),
