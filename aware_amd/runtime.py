@@ -802,6 +802,38 @@ def gemm_nt(a: torch.Tensor, bt: torch.Tensor, bias: torch.Tensor | None = None)
     return c
 
 
+def _pitched_f32(t: torch.Tensor, name: str, shape, dev):
+    if tuple(t.shape) != tuple(shape) or t.dtype != torch.float32 or t.device != dev or t.stride(1) != 1 or t.stride(0) < shape[1]:
+        raise ValueError(f"{name}: a {list(shape)} f32 view on a's device with unit column stride and a row pitch of at least "
+                         f"{shape[1]}")
+
+
+def gemm_nt_variant(a: torch.Tensor, bt: torch.Tensor, bias: torch.Tensor | None, variant: int, out=None) -> torch.Tensor:
+    """C = a @ bt^T + bias on one tile configuration of the f32-MFMA GEMM (aware_gemm_nt_variant; tests / roofline).
+    variant: 0 = the choice gemm_nt makes, 1..16 = the rows of gemm_dispatch (csrc/detector_kernels.hip); any other number is
+    refused (AwareHipError "bad argument").  a: [M, K], bt: [N, K] and out: [M, N] may be row-pitched views (unit column
+    stride, row pitch at least the row; the pitches of a and bt, like K, multiples of 4 as the ABI demands).  out=None
+    allocates a contiguous [M, N].  Returns out."""
+    lib = load_library()
+    if a.dim() != 2 or bt.dim() != 2 or not a.is_cuda:
+        raise ValueError("a: [M, K] and bt: [N, K] on the device")
+    M, K = a.shape
+    N = bt.shape[0]
+    dev = a.device
+    _pitched_f32(a, "a", (M, K), dev)
+    _pitched_f32(bt, "bt", (N, K), dev)
+    if bias is not None and (tuple(bias.shape) != (N,) or bias.dtype != torch.float32 or bias.device != dev
+                             or not bias.is_contiguous()):
+        raise ValueError("bias: a contiguous [N] f32 tensor on a's device")
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.float32, device=dev)
+    else:
+        _pitched_f32(out, "out", (M, N), dev)
+    check(lib.aware_gemm_nt_variant(_ptr(a), a.stride(0), _ptr(bt), bt.stride(0), _ptr(bias), _ptr(out), out.stride(0), M, N, K,
+                                    int(variant), _stream()), "aware_gemm_nt_variant")
+    return out
+
+
 def x3_pack(wt: torch.Tensor) -> torch.Tensor:
     """[N][K] f32 weights -> the three bf16 planes in MFMA fragment order (device uint8 tensor)."""
     lib = load_library()

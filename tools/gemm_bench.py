@@ -1,16 +1,14 @@
 """Micro-benchmark of the fp32 MFMA GEMM at the detector's shapes (development aid)."""
-import sys, os, ctypes as C
+import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from aware_amd._lib import load_library, check
-lib = load_library()
+from aware_amd import runtime as rt
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 64
 VARIANTS = [int(x) for x in sys.argv[2].split(',')] if len(sys.argv) > 2 else list(range(1, 13))
 NP, NF = B * 94, B * 188
 shapes = [("mel_f", NF, 128, 256), ("L0_f", NP, 512, 128), ("L1_f", NP, 1024, 512), ("L2", NP, 1024, 1024),
           ("L3_f", NP, 40, 1024), ("L3_b", NP, 1024, 40), ("L1_b", NP, 512, 1024), ("L0_b", NP, 128, 512),
           ("mel_b", NF, 256, 128)]
-st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
 tot = {0: 0.0}
 for name, M, N, K in shapes:
     a = torch.randn(M, K, device="cuda"); b = torch.randn(N, K, device="cuda"); c = torch.empty(M, N, device="cuda")
@@ -19,7 +17,7 @@ for name, M, N, K in shapes:
     best = (1e9, -1)
     for v in VARIANTS:
         def run():
-            check(lib.aware_gemm_nt_variant(C.c_void_p(a.data_ptr()), K, C.c_void_p(b.data_ptr()), K, None, C.c_void_p(c.data_ptr()), N, M, N, K, v, st))
+            rt.gemm_nt_variant(a, b, None, v, out=c)
         for _ in range(3): run()
         torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
