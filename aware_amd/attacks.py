@@ -281,6 +281,27 @@ class BandFilter(Attack):
         return rt.band_filter(x, RESPONSES[self.response], c1, c2)
 
 
+@register
+class FrequencyShift(Attack):
+    """EXTENSION (not in the reference, parity unpinned): the embed loop's frequency_shift operator at a fixed shift, applied
+    after embedding: every component moved by hz (positive: upwards) through the 255-tap Hilbert transformer
+    (embedding.loop_attacks.hilbert_taps), from the start phase `phase` in turns.  Single-sideband modulation: neither a pitch
+    shift nor a speed change.  The clip keeps its length."""
+
+    def __init__(self, hz, phase=0.0):
+        self.hz, self.phase = float(hz), float(phase)
+        if not (np.isfinite(self.hz) and np.isfinite(self.phase)):
+            raise ValueError(f"FrequencyShift: hz and phase have to be finite; got {hz!r}, {phase!r}")
+        self.name = f"frequency_shift_{hz}"
+
+    def apply_batch(self, x, sr):
+        from .embedding.loop_attacks import MAX_SHIFT, PHASE_ONE, shift_increment
+        d = shift_increment(self.hz, sr)
+        if abs(d) > MAX_SHIFT:
+            raise ValueError(f"FrequencyShift: {self.hz} Hz lies beyond +-{sr / 16:g} Hz, the widest shift at {sr} Hz")
+        return rt.frequency_shift(x, d, int(round((self.phase % 1.0) * PHASE_ONE)) % PHASE_ONE)
+
+
 def _excerpt_bounds(name, seconds, start_seconds, x, sr):
     """(starts, lengths) in samples of the excerpt of every clip of x: int(start_seconds * sr) and int(seconds * sr), inside it."""
     s, L = int(start_seconds * sr), int(seconds * sr)

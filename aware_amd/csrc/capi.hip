@@ -2145,6 +2145,18 @@ extern "C" int aware_band_filter(const float* in, const int* off, const int* len
     return AWARE_OK;
 }
 
+// ---- the frequency shift alone (EXTENSION; attacks.FrequencyShift, runtime.frequency_shift, tests) --------------------------
+extern "C" int aware_frequency_shift(const float* in, const int* off, const int* len, int B, int max_len, const int* d,
+                                     const int* p0, int adjoint, float* out, void* stream) {
+    if (!in || !off || !len || !d || !p0 || !out || in == out) return AWARE_E_BADARG;
+    if (!ragged_args_ok(B, max_len) || adjoint < 0 || adjoint > 1) return AWARE_E_BADARG;
+    ShiftLaunch L;
+    L.in = in; L.out = out; L.B = B; L.adjoint = adjoint; L.off = off; L.len = len; L.max_len = max_len; L.d = d; L.p0 = p0;
+    launch_frequency_shift(L, (hipStream_t)stream);
+    LAUNCHCHK();
+    return AWARE_OK;
+}
+
 // ---- the gain envelope alone (EXTENSION; attacks.GainEnvelope, runtime.gain_envelope, tests) ----------------------------------
 extern "C" int aware_gain_envelope(const float* in, const int* off, const int* len, int B, int max_len, const uint32_t* seeds,
                                    int step, int entry, int p_lo, int p_hi, float floor, float* out, float* gains, void* stream) {
@@ -2487,6 +2499,11 @@ static FilterLaunch filter_launch(const aware_embed* e, const LoopChainState& la
     S.mask = la.mask; S.c_lo = la.lo; S.c_hi = la.hi; S.w_min = la.w_min;
     return S;
 }
+static ShiftLaunch shift_launch(const aware_embed* e, const LoopChainState& la, const float* in, float* out, int adjoint, int step_back) {
+    ShiftLaunch S = stage_launch<ShiftLaunch>(e, la, in, out, adjoint, step_back);
+    S.d_lo = la.lo; S.d_hi = la.hi;
+    return S;
+}
 // the time stretch and the pitch shift: the window and one range of offsets
 static ResampleLaunch ola_launch(const aware_embed* e, const LoopChainState& la, const float* in, float* out, int adjoint, int step_back) {
     ResampleLaunch S = stage_launch<ResampleLaunch>(e, la, in, out, adjoint, step_back);
@@ -2595,6 +2612,7 @@ static void split_forward(const aware_embed* e, const LoopChainState& la, hipStr
         // gy is free until the synthesis adjoint writes it, and carries the vocoded signal to the resampling
         case AWARE_LOOP_PHASE_VOCODER: pv_stage_forward(e, la, e->gy, st); break;
         case AWARE_LOOP_BAND_FILTER: launch_band_filter(filter_launch(e, la, la.u, la.z, 0), st); break;
+        case AWARE_LOOP_FREQUENCY_SHIFT: launch_frequency_shift(shift_launch(e, la, la.u, la.z, 0, 0), st); break;
         case AWARE_LOOP_EXCERPT: launch_excerpt_tile(excerpt_launch(e, la, la.u, la.z, 0, 0), st); break;
         // the table of the drawn rates first, then the resampling; the backward pass reads that table
         case AWARE_LOOP_TIME_WARP: launch_time_warp(warp_launch(e, la, la.u, la.z, 0, 0), st); break;
@@ -2617,6 +2635,7 @@ static void split_backward(const aware_embed* e, const LoopChainState& la, int s
         case AWARE_LOOP_PITCH_SHIFT: launch_pitch_shift(ola_launch(e, la, la.u, e->gy, 1, step_back), st); break;
         case AWARE_LOOP_PHASE_VOCODER: pv_stage_backward(e, la, step_back, st); break;
         case AWARE_LOOP_BAND_FILTER: launch_band_filter(filter_launch(e, la, la.u, e->gy, step_back), st); break;      // its own adjoint
+        case AWARE_LOOP_FREQUENCY_SHIFT: launch_frequency_shift(shift_launch(e, la, la.u, e->gy, 1, step_back), st); break;
         case AWARE_LOOP_EXCERPT: launch_excerpt_tile(excerpt_launch(e, la, la.u, e->gy, 1, step_back), st); break;
         case AWARE_LOOP_TIME_WARP: launch_time_warp(warp_launch(e, la, la.u, e->gy, 1, step_back), st); break;
         default: launch_delete_samples(delete_launch(e, la, la.u, e->gy, 1, step_back), st); break;

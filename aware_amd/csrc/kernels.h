@@ -605,6 +605,23 @@ struct FilterLaunch {
 };
 void launch_band_filter(const FilterLaunch& L, hipStream_t st);
 
+// ---- loop_shift_kernels.hip: frequency shift (EXTENSION): single-sideband modulation, z = x cos phi - (Hx) sin phi with H a
+// Hilbert transformer of 2 kFilterHalf + 1 taps and phi_i = 2 pi ((p0 + i d) mod 2^20) / 2^20, inside the embed loop (chain
+// kind 12) and stand-alone (aware_frequency_shift), and its exact adjoint gx = g cos phi + H(g sin phi) ------------------------
+struct ShiftLaunch {
+    const float* in = nullptr; float* out = nullptr;      // never the same buffer
+    int B = 0, adjoint = 0;               // 0: out = z from in = x; 1: out = gx from in = gz
+    // the embed loop (draw.frame_off set): d and p0 drawn in the kernel
+    LoopDraw draw;
+    int d_lo = 0, d_hi = 0;               // -kShiftMax <= d_lo <= d_hi <= kShiftMax, in units of sr / 2^20 Hz
+    // or a ragged batch (draw.frame_off null): both sides are len[b] floats at off[b]; d[b] and p0[b] given
+    const int* off = nullptr; const int* len = nullptr;
+    int max_len = 0;                      // >= every length
+    const int* d = nullptr;               // [B]
+    const int* p0 = nullptr;              // [B] read modulo 2^20
+};
+void launch_frequency_shift(const ShiftLaunch& L, hipStream_t st);
+
 // ---- loop_excerpt_kernels.hip: tiled excerpt (EXTENSION): the excerpt [start, start + L) of the clip repeated periodically
 // until it fills the clip, inside the embed loop (chain kind 10) and stand-alone (aware_excerpt_tile), and its adjoint in
 // gather form: the sum over the periods in f32, m ascending ------------------------------------------------------------------

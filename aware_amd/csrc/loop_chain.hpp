@@ -2,10 +2,11 @@
 // chain's state, the parser with every AWARE_E_BADARG / AWARE_E_UNSUPPORTED of the setters, and the carving of the chains'
 // workspace.  Plain C++: no HIP header and no HIP call, so tests/host_sim/loop_chain_check.cpp runs it on the CPU.
 //
-// THE ONE-SPLIT RULE.  kLoopKindTable (loop_limits.hpp) says of every kind whether it is element-wise and runs inside the stage
-// kernels of loop_attack_kernels.hip, or needs launches of its own between two such stages: it SPLITS the chain.  A chain holds at
+// THE ONE-SPLIT RULE.  loop_kind_staged (loop_limits.hpp: kLoopKindTable's splitting rows and the kinds of kLoopStagedBeyond) says
+// of every kind whether it is element-wise and runs inside the stage kernels of loop_attack_kernels.hip, or needs launches of
+// its own between two such stages: it SPLITS the chain.  A chain holds at
 // most one splitting entry.  The one exception: a speed change directly behind a time stretch (j == split + 1) forms one stage
-// u -> v -> z with it.  The host twin is embedding/loop_attacks.py::parse_chain (TABLE, SPLITTING).
+// u -> v -> z with it.  The host twin is embedding/loop_attacks.py::parse_chain (TABLE, SPLITTING, STAGED).
 #pragma once
 #include <math.h>
 #include <stddef.h>
@@ -74,6 +75,7 @@ struct LoopChainState {
     //   tiled excerpt   lo..hi: samples of the excerpt
     //   time warp       lo..hi: exponents e of the 2^e samples between breakpoints; depth: the widest rate offset D; kmax:
     //                   breakpoints of the longest clip at 2^lo
+    //   frequency shift lo..hi: shifts d in units of sr / 2^20 Hz, signed
     int split = -1, split_kind = 0, pair_speed = -1;
     int lo = 0, hi = 0, lo2 = 0, hi2 = -1, at = 0, kmax = 0, mask = 0, w_min = 0, depth = 0;
     double gain = 0;
@@ -109,7 +111,8 @@ inline int parse_loop_chain(const LoopDims& d, const aware_loop_attack_ex* attac
                   AWARE_LOOP_TIME_STRETCH == kLoopTimeStretch && AWARE_LOOP_PITCH_SHIFT == kLoopPitchShift &&
                   AWARE_LOOP_PHASE_VOCODER == kLoopPhaseVocoder && AWARE_LOOP_DELETE_SAMPLES == kLoopDeleteSamples &&
                   AWARE_LOOP_GAIN_ENVELOPE == kLoopGainEnvelope && AWARE_LOOP_BAND_FILTER == kLoopBandFilter &&
-                  AWARE_LOOP_EXCERPT == kLoopExcerpt && AWARE_LOOP_TIME_WARP == kLoopTimeWarp, "");
+                  AWARE_LOOP_EXCERPT == kLoopExcerpt && AWARE_LOOP_TIME_WARP == kLoopTimeWarp &&
+                  AWARE_LOOP_FREQUENCY_SHIFT == kLoopFrequencyShift, "");
     if (!attacks || n_attacks < 1 || n_attacks > kMaxLoopAttacks) return AWARE_E_BADARG;
     la.split = -1; la.pair_speed = -1; la.h = nullptr; la.v = nullptr;
     for (int j = 0; j < n_attacks; ++j) {
@@ -119,7 +122,7 @@ inline int parse_loop_chain(const LoopDims& d, const aware_loop_attack_ex* attac
         la.kind[j] = a.kind; la.prob[j] = a.prob; la.k[j] = 0; la.inv_snr[j] = 0.0;
         la.p_lo[j] = 0; la.p_hi[j] = 0; la.floor[j] = 0.f;
         if (a.kind < 0 || a.kind >= kLoopKinds || (kLoopKindTable[a.kind].ex_only && !ex)) return AWARE_E_BADARG;
-        const bool splits = kLoopKindTable[a.kind].splits;
+        const bool splits = loop_kind_staged(a.kind);
         // the one-split rule
         const bool pair = chain_has(la, AWARE_LOOP_TIME_STRETCH) && a.kind == AWARE_LOOP_SPEED_CHANGE && j == la.split + 1;
         if (splits && chain_splits(la) && !pair) return AWARE_E_BADARG;
@@ -174,6 +177,9 @@ inline int parse_loop_chain(const LoopDims& d, const aware_loop_attack_ex* attac
                     return AWARE_E_BADARG;
                 la.depth = (int)p[2];
                 break;
+            case AWARE_LOOP_FREQUENCY_SHIFT:  // param = {d_lo, d_hi, 0, 0}, in units of sr / 2^20 Hz, signed
+                if (!int_range(p[0], p[1], -(float)kShiftMax, (float)kShiftMax) || p[2] != 0.f || p[3] != 0.f) return AWARE_E_BADARG;
+                break;
             default:    // AWARE_LOOP_DELETE_SAMPLES, param = {k_lo, k_hi, at, 0}
                 if (!int_range(p[0], p[1], 1.f, 2147483520.f) || !(p[2] == 0.f || p[2] == 1.f)) return AWARE_E_BADARG;
                 la.at = (int)p[2];
@@ -202,8 +208,8 @@ inline void size_refused_chain(const aware_loop_attack_ex* attacks, int n_attack
     la.split = -1; la.pair_speed = -1;
     for (int j = 0; j < n_attacks; ++j) {
         const int kind = attacks[j].kind;
-        if (kind < 0 || kind >= kLoopKinds || !kLoopKindTable[kind].splits) continue;
-        if (!chain_splits(la) || kLoopKindTable[kind].refused_rank < kLoopKindTable[la.split_kind].refused_rank) {
+        if (kind < 0 || kind >= kLoopKinds || !loop_kind_staged(kind)) continue;
+        if (!chain_splits(la) || loop_staged_rank(kind) < loop_staged_rank(la.split_kind)) {
             la.split = j; la.split_kind = kind;
         }
     }

@@ -1257,6 +1257,30 @@ def band_filter(x: Ragged, response, c1, c2, return_taps: bool = False, out: Rag
     return (out, taps) if return_taps else out
 
 
+def frequency_shift(x: Ragged, d, p0, adjoint: bool = False, out: Ragged | None = None):
+    """Per clip embedding.loop_attacks.frequency_shift (aware_frequency_shift): clip b moved by d[b] units of sr / 2^20 Hz
+    (signed, |d| <= 65536; positive is upwards) from the start phase p0[b] in units of 2^-20 turn, 0 <= p0 < 2^20, through the
+    255-tap Hilbert transformer (B integers each, or one for all).  Every clip keeps its length and zeros are read outside it.
+    With adjoint, x holds the gradient with respect to that output and the result is the gradient with respect to the input.
+    out: a Ragged of x's lengths in float32 to write into, never x itself."""
+    from .embedding.loop_attacks import MAX_SHIFT
+    lib = load_library()
+    ds, ps = ([int(v)] * x.B if np.isscalar(v) else [int(u) for u in v] for v in (d, p0))
+    if len(ds) != x.B or len(ps) != x.B or any(abs(v) > MAX_SHIFT for v in ds) or any(not 0 <= v < (1 << 20) for v in ps):
+        raise ValueError(f"frequency_shift: {x.B} shifts within +-{MAX_SHIFT} and start phases in [0, 2^20) are required; "
+                         f"got d = {ds}, p0 = {ps}")
+    xin = x.data if x.data.dtype == torch.float32 else x.data.float()
+    if out is None:
+        out = Ragged(torch.empty(sum(x.lengths), dtype=torch.float32, device=xin.device), x.lengths)
+    elif list(out.lengths) != list(x.lengths) or out.data.dtype != torch.float32 or out.data.data_ptr() == xin.data_ptr():
+        raise ValueError("frequency_shift: out needs x's lengths in float32 and a buffer of its own")
+    dev = lambda v: torch.tensor(v, dtype=torch.int32, device=xin.device)
+    dd, pd = dev(ds), dev(ps)
+    check(lib.aware_frequency_shift(_ptr(xin), _ptr(x.d_off), _ptr(x.d_len), x.B, x.max_len, _ptr(dd), _ptr(pd), int(bool(adjoint)),
+                                    _ptr(out.data), _stream()), "aware_frequency_shift")
+    return out
+
+
 def sync_select(values: torch.Tensor, n: int, centre: float = 0.0):
     """detection.sync.sync_select on the device (aware_sync_select): values [B * n, L] float32, clip-major, the n candidate
     views of each of the B clips -> (values [B, L] of the view with the largest mean |v - centre| per clip, the smallest j on

@@ -850,6 +850,33 @@ int aware_excerpt_tile(const float* in, const int* off, const int* len, int B, i
 int aware_time_warp(const float* in, const int* off, const int* len, int B, int max_len, const int* e, const int* ph,
                     const int* rates, int stride, int* table_r, long long* table_a, float* out, int adjoint, void* stream);
 
+/* ---- frequency shift inside the loop and alone (EXTENSION, parity unpinned: the reference has neither) ----------------------
+ * The _ex pair and the mixture's setter also accept (the older entry point keeps refusing every kind above 1)
+ *   AWARE_LOOP_FREQUENCY_SHIFT, param = { d_lo, d_hi, 0, 0 }: single-sideband modulation, every component of the clip moved by
+ *     the same number of Hz: a mistuned SSB or heterodyne link, an analogue carrier system.  Shifts are signed integers d in units
+ *     of sample_rate / 2^20 Hz, |d| <= 65536 (sample_rate / 16; the host converts Hz), phases integers in units of 2^-20 turn.
+ *     With r the entry's draw as above,
+ *     d = d_lo + ((r[1] * (d_hi - d_lo + 1)) >> 32), p0 = r[2] >> 12;
+ *     w[k] = 0.54 + 0.46 * cos(pi * k / 127), h[k] = w[k] * 2 / (pi * k) for odd k, 0 for even k, k = -127..127;
+ *     (Hx)[i] = sum_k h[k] * x[i - k], x zero outside the clip;  phi_i = 2 * pi * ((p0 + i * d) mod 2^20) / 2^20;
+ *     forward  z[i] = x[i] * cos(phi_i) - (Hx)[i] * sin(phi_i), 0 <= i < Ny_b: a positive d shifts upwards;
+ *     adjoint  gx[j] = g[j] * cos(phi_j) + (H(g * sin(phi)))[j]: exact, because h is antisymmetric and the extension is by zeros.
+ *   The clip keeps its length and there is no delay.  An entry that does not fire copies the clip; d and p0 are not
+ *   differentiated.  Below about 150 Hz the 255-tap transformer leaves some of the image sideband.
+ * AWARE_E_BADARG of the _ex setter, besides those above: a value that is not an integer, d_lo < -65536, d_lo > d_hi,
+ * d_hi > 65536, param[2] or param[3] not 0, a second frequency shift, a frequency shift together with any of kinds 2 to 7 and 9
+ * to 11 (in either order).  aware_embed_loop_attack_workspace_bytes_ex for a chain with the kind is that of the same chain with a
+ * sample deletion in its place: no private workspace.  aware_embed_buffer gains no index.  Added without a version step: callers
+ * detect the addition by symbol. */
+#define AWARE_LOOP_FREQUENCY_SHIFT 12    /* param = d_lo, d_hi, 0, 0 (sample_rate / 2^20 Hz, signed; the host converts Hz) */
+/* The same operator alone, on a ragged batch, always on: clip b is len[b] floats at float offset off[b] of `in` and of `out`
+ * (dev int [B], any offsets, every length <= max_len <= 2^30); d and p0 dev int [B], p0 read modulo 2^20.  adjoint 0: `in` holds
+ * x and `out` receives z.  adjoint 1: `in` holds gz and `out` receives gx.  in and out are distinct buffers.  One launch on
+ * `stream`.  AWARE_E_BADARG: a null argument, in == out, B < 1 or > 65535, max_len < 1 or > 2^30, adjoint outside 0..1 (checked
+ * before anything is launched). */
+int aware_frequency_shift(const float* in, const int* off, const int* len, int B, int max_len, const int* d, const int* p0,
+                          int adjoint, float* out, void* stream);
+
 /* ---- attack mixtures (EXTENSION, parity unpinned: the reference has no attacks in its loop) -------------------------------
  * A handle holds one chain, and the kinds that split a chain refuse each other.  A mixture is a list of 1..8 chains, each a
  * valid chain of aware_embed_set_loop_attacks_ex with a weight; at optimiser step s clip b draws

@@ -20,6 +20,11 @@ none of the above: it times the FIR kernel alone (aware_band_filter) on the batc
 from device events, 20 calls each after a warm-up (under rocprofv3 --kernel-trace --stats the two show per kernel).
 `--excerpt` adds the chains of EXCERPT_VARIANTS, which hold the tiled excerpt, in the same way.
 `--warp` adds the chains of WARP_VARIANTS, which hold the time warp, in the same way.
+`--shift` adds the chains of SHIFT_VARIANTS, which hold the frequency shift, in the same way; their
+`shift_p1` and `filter_p1` fire on every clip, for a per-kernel comparison of the two FIR kernels inside the loop.  `--ssb` does
+none of the above: it times the frequency shift's kernel alone (aware_frequency_shift, forward and adjoint) against the band
+filter's (aware_band_filter) on the batch, the three alternating, from device events around windows of 50 launches on buffers
+made beforehand: the median of three windows each.
 `--only-loop` runs a few steps of every variant and nothing else, for a per-kernel trace
 (rocprofv3 --kernel-trace --stats -- python tools/loop_attack_bench.py --only-loop)."""
 import argparse
@@ -85,6 +90,15 @@ EXCERPT_VARIANTS = {
 WARP_VARIANTS = {
     "warp": [{"kind": "time_warp", "depth": 0.04, "period": [0.032, 0.512], "prob": 0.75}],
     "warp_noise": [{"kind": "time_warp", "depth": 0.04, "period": [0.032, 0.512], "prob": 0.75}, {"kind": "gaussian_noise", "snr_db": 10.0}],
+}
+
+# The chains with a frequency shift (chain kind 12), in a table of their own for the same reason; the two that always fire are
+# what a kernel trace compares.
+SHIFT_VARIANTS = {
+    "shift": [{"kind": "frequency_shift", "hz": 120.0, "prob": 0.75}],
+    "shift_noise": [{"kind": "frequency_shift", "hz": 120.0, "prob": 0.75}, {"kind": "gaussian_noise", "snr_db": 10.0}],
+    "shift_p1": [{"kind": "frequency_shift", "hz": 120.0}],
+    "filter_p1": [{"kind": "band_filter", "response": ["lowpass", "highpass", "bandpass", "bandstop"], "freq": [600.0, 3800.0]}],
 }
 
 
@@ -219,6 +233,38 @@ def fir_timing(audio, B, n):
     return out
 
 
+def ssb_timing(audio, B, n, launches=50, windows=3):
+    """us per launch of aware_frequency_shift (forward and adjoint, +50 Hz) and of aware_band_filter (a band-pass of 1000 to
+    3000 Hz) on the batch: device events around `launches` launches on buffers made beforehand, the three alternating, the median
+    of `windows` windows each and the windows themselves."""
+    from aware_amd._lib import load_library
+    lib = load_library()
+    x = rt.Ragged(audio, [n] * B)
+    out = torch.empty_like(audio)
+    i32 = lambda v: torch.full((B,), v, dtype=torch.int32, device="cuda")
+    d, p0, rs, c1, c2 = i32(3277), i32(0), i32(4), i32(4096), i32(12288)
+    ptr = lambda t: t.data_ptr()
+    st = torch.cuda.current_stream().cuda_stream
+    head = (ptr(audio), ptr(x.d_off), ptr(x.d_len), B, n)
+    calls = {"frequency_shift": lambda: lib.aware_frequency_shift(*head, ptr(d), ptr(p0), 0, ptr(out), st),
+             "frequency_shift_adjoint": lambda: lib.aware_frequency_shift(*head, ptr(d), ptr(p0), 1, ptr(out), st),
+             "band_filter": lambda: lib.aware_band_filter(*head, ptr(rs), ptr(c1), ptr(c2), ptr(out), None, st)}
+    for fn in calls.values():
+        for _ in range(5):
+            assert fn() == 0
+    ts = {name: [] for name in calls}
+    for _ in range(windows):
+        for name, fn in calls.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(launches):
+                fn()
+            b.record()
+            b.synchronize()
+            ts[name].append(round(1e3 * a.elapsed_time(b) / launches, 2))
+    return {name: {"median": float(np.median(v)), "windows": v} for name, v in ts.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--clips", type=int, default=256)
@@ -237,6 +283,8 @@ def main():
     ap.add_argument("--fir", action="store_true")
     ap.add_argument("--excerpt", action="store_true")
     ap.add_argument("--warp", action="store_true")
+    ap.add_argument("--shift", action="store_true")
+    ap.add_argument("--ssb", action="store_true")
     args = ap.parse_args()
     B, n = args.clips, int(args.seconds * 16000)
     emb, det = load()
@@ -254,6 +302,12 @@ def main():
               f"(host calls included)")
         print(json.dumps({"clips": B, "seconds": args.seconds, "us_per_call": t}))
         return
+    if args.ssb:
+        t = ssb_timing(audio, B, n)
+        for name, v in t.items():
+            print(f"{name:24s} {v['median']:8.2f} us per launch on {B} x {n} samples (windows: {v['windows']})")
+        print(json.dumps({"clips": B, "seconds": args.seconds, "us_per_launch": t}))
+        return
     batch = rt.Batch([n] * B)
     result = {"clips": B, "seconds": args.seconds, "steps": args.steps}
 
@@ -267,6 +321,7 @@ def main():
     variants.update({k: v for k, v in FILTER_VARIANTS.items() if k in chosen or (args.filter and not args.variants)})
     variants.update({k: v for k, v in EXCERPT_VARIANTS.items() if k in chosen or (args.excerpt and not args.variants)})
     variants.update({k: v for k, v in WARP_VARIANTS.items() if k in chosen or (args.warp and not args.variants)})
+    variants.update({k: v for k, v in SHIFT_VARIANTS.items() if k in chosen or (args.shift and not args.variants)})
     mixtures = {}
     for m in [v for v in args.mixture.split(",") if v]:
         mixtures[f"mixture:{m}"] = MIXTURES[m]
