@@ -536,6 +536,7 @@ extern "C" int aware_stft_band(const aware_plan* plan, const aware_batch* b, con
     AnalysisLaunch L = analysis_launch(plan, b, audio, false);
     L.pmax = normalize ? pmax : nullptr;
     L.mag = mag; L.unit = phasor; L.unit_default = 1.f;
+    L.polar_exact = 1;       // the original audio: the decomposer's magnitudes and phasors, and the magnitudes detection reads
     run_analysis(L, 0, st);
     LAUNCHCHK();
     return AWARE_OK;
@@ -1315,7 +1316,7 @@ extern "C" int aware_detect(const aware_plan* plan, const aware_detector* d, con
     if (plan->general) {
         // the general route: normalised spectrum (stft_any.hip), then its band magnitudes in the detector's layout
         rc = gen_stft(plan, b, audio, 1, spec, pmax, st);
-        if (rc == AWARE_OK) { launch_band_mag(band_launch(plan, b), spec, mag, nullptr, st); LAUNCHCHK(); }
+        if (rc == AWARE_OK) { launch_band_mag(band_launch(plan, b), spec, mag, nullptr, true, st); LAUNCHCHK(); }
     } else
         rc = aware_stft_band(plan, b, audio, 1, mag, nullptr, pmax, stream);
     if (rc) return rc;
@@ -2346,7 +2347,7 @@ static int gen_embed_begin(aware_embed* e, const float* audio, hipStream_t st) {
     BandBegin G;
     G.unit = e->U; G.coef = e->coef; G.lo = e->lo; G.hi = e->hi; G.mom = e->mom; G.vel = e->vel; G.best = e->best; G.c0 = e->c0;
     G.ratio = box_ratio(e->cfg);
-    launch_band_mag(band_launch(e->plan, b), e->S0, e->mag, &G, st);
+    launch_band_mag(band_launch(e->plan, b), e->S0, e->mag, &G, true, st);
     LAUNCHCHK();
     return AWARE_OK;
 }
@@ -2377,7 +2378,7 @@ static int gen_embed_iteration(aware_embed* e, hipStream_t st, int do_step, floa
     LAUNCHCHK(); PROF(K_MISC);
     launch_gen_analysis(L, e->y2, e->S2, 0, st);
     LAUNCHCHK(); PROF(K_ANALYSIS);
-    launch_band_mag(BL, e->S2, e->mag, nullptr, st);
+    launch_band_mag(BL, e->S2, e->mag, nullptr, false, st);
     LAUNCHCHK(); PROF(K_MISC);
     // :107 detector forward, :109 loss, :120-122 best tracking, :111 backward through the detector
     const DetPlan p = det_plan(d, b, e->cfg.conv_pipe, e->cfg.readout, false, false, false, e->cfg.conv_tile);
@@ -2423,7 +2424,7 @@ extern "C" int aware_embed_begin(aware_embed* e, const float* audio, const float
     LAUNCHCHK();
     AnalysisLaunch L = analysis_launch(e->plan, b, audio, false);
     L.pmax = e->pmaxA;
-    L.mag = e->mag; L.unit = e->P; L.unit_default = 1.f;
+    L.mag = e->mag; L.unit = e->P; L.unit_default = 1.f; L.polar_exact = 1;
     run_analysis(L, e->cfg.dsp_path, st);
     LAUNCHCHK();
     // constant out-of-band part of every synthesis: x/m - istft(band of the original)

@@ -2,6 +2,7 @@
 // streaming wave kernels (dsp_stream.hip).
 #pragma once
 #include "common.hpp"
+#include "polar.hpp"
 
 namespace aware {
 
@@ -16,6 +17,11 @@ __device__ __forceinline__ float fast_sqrt(float x) { return __builtin_amdgcn_sq
 __device__ __forceinline__ float fast_rcp(float x) { return 1.0f / x; }
 __device__ __forceinline__ float fast_sqrt(float x) { return sqrtf(x); }
 #endif
+// the two as polar_exact takes them (polar.hpp)
+struct HwMath {
+    static __device__ __forceinline__ float sqrt(float x) { return fast_sqrt(x); }
+    static __device__ __forceinline__ float rcp(float x) { return fast_rcp(x); }
+};
 
 // torch.optim.NAdam single-tensor step (torch/optim/nadam.py _single_tensor_nadam) + clamp to the tolerance box
 // (embedding/multibit_embedder.py:112-117).  c_grad = -lr (1 - mu_t) / (1 - mu_product), c_mom = -lr mu_{t+1} /

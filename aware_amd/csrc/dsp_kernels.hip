@@ -48,8 +48,11 @@ __global__ __launch_bounds__(kThreads) void absmax_partial_kernel(const float* _
 // ---------------------------------------------------------------------------------
 
 // FULLOUT: write the full one-sided spectrum (generic STFT plug-in) instead of the band outputs
-template <int MODE, bool FULLOUT>
+// POLAR (AN_NORM band outputs only): magnitude and unit phasor by polar_exact (polar.hpp), for the decomposition of the
+// original audio; the loop's launches keep the plain form (POLAR = false: the code they had)
+template <int MODE, bool FULLOUT, bool POLAR = false>
 __global__ __launch_bounds__(kThreads) void analysis_kernel(AnalysisArgs a) {
+    static_assert(!POLAR || (MODE == AN_NORM && !FULLOUT), "the exact decomposition stores magnitudes and phasors");
     __shared__ float chunk[kChunk];
     __shared__ cf scratch[4][kFftScratch];
     __shared__ unsigned long long red[4];
@@ -225,7 +228,11 @@ __global__ __launch_bounds__(kThreads) void analysis_kernel(AnalysisArgs a) {
                     continue;
                 }
                 cf X = (r < 8) ? rfft_split_bin(k, v[r < 8 ? r : 0], s, a.plan.tw1024) : mk(rfft_split_nyquist(s), 0.f);
-                if (MODE == AN_NORM) {
+                if (MODE == AN_NORM && POLAR) {
+                    const Polar p = polar_exact<HwMath>(X.x, X.y);
+                    if (a.mag) a.mag[idx] = p.mag;
+                    if (a.unit) a.unit[idx] = (p.mag > 0.f) ? mk(p.ux, p.uy) : mk(a.unit_default, 0.f);
+                } else if (MODE == AN_NORM) {
                     const float mg = fast_sqrt(X.x * X.x + X.y * X.y);
                     const float im = fast_rcp(mg);
                     if (a.mag) a.mag[idx] = mg;
@@ -567,6 +574,8 @@ void launch_analysis(const AnalysisLaunch& L, hipStream_t st) {
         hipLaunchKernelGGL((analysis_kernel<AN_ADJ, false>), grid2(nx, L.B), dim3(kThreads), 0, st, a);
     else if (L.full)
         hipLaunchKernelGGL((analysis_kernel<AN_NORM, true>), grid2(nx, L.B), dim3(kThreads), 0, st, a);
+    else if (L.polar_exact)
+        hipLaunchKernelGGL((analysis_kernel<AN_NORM, false, true>), grid2(nx, L.B), dim3(kThreads), 0, st, a);
     else
         hipLaunchKernelGGL((analysis_kernel<AN_NORM, false>), grid2(nx, L.B), dim3(kThreads), 0, st, a);
 }

@@ -82,9 +82,13 @@ __device__ __forceinline__ float env_at(const PlanDev& pl, int p, int T) {
 // band columns, 450 non-zero weights in all for the card's bank -- and the frame's 128 mel values are written instead of its
 // 256 magnitudes (the dense K = 256 GEMM of the mel block and its operand never exist)
 // WIDE: the wide layout (see the top of the file): 9 bin slots per lane, rows of kFSWide columns, no mel fold
-template <int MODE, bool L1, bool MELF = false, bool WIDE = false>
+// POLAR (AN_NORM only): the decomposition of the original audio (aware_embed_begin, aware_stft_band and with it detection):
+// magnitude and unit phasor by polar_exact (polar.hpp), exact for bins of any amplitude.  The loop's own launches keep the
+// plain form (POLAR = false: the code they had)
+template <int MODE, bool L1, bool MELF = false, bool WIDE = false, bool POLAR = false>
 __global__ __launch_bounds__(kSThreads, MODE == AN_ADJ ? (WIDE ? 2 : 3) : 4) void analysis_stream_kernel(AnalysisArgs a, int run_frames) {
     static_assert(!(WIDE && MELF), "the wide layout takes the dense mel GEMM");
+    static_assert(!POLAR || (MODE == AN_NORM && !MELF), "the exact decomposition stores magnitudes and phasors");
     constexpr int S = WIDE ? kFSWide : kFS;        // floats per band row
     constexpr int NS = WIDE ? 9 : 5;               // bin slots per lane
     __shared__ float magrow_s[MELF ? kSW : 1][MELF ? kFS : 1];
@@ -272,7 +276,11 @@ __global__ __launch_bounds__(kSThreads, MODE == AN_ADJ ? (WIDE ? 2 : 3) : 4) voi
             const cf wd = cmul(w1024[r], d);
             const cf X = mk(e.x + wd.y, e.y - wd.x);
             const size_t idx = row * S + f;
-            if (MODE == AN_NORM) {
+            if (MODE == AN_NORM && POLAR) {
+                const Polar p = polar_exact<HwMath>(X.x, X.y);
+                if (a.mag) a.mag[idx] = p.mag;
+                if (a.unit) a.unit[idx] = (p.mag > 0.f) ? mk(p.ux, p.uy) : mk(a.unit_default, 0.f);
+            } else if (MODE == AN_NORM) {
                 const float mg = fast_sqrt(X.x * X.x + X.y * X.y);
                 const float im = fast_rcp(mg);
                 if (MELF) magrow_s[wave][f] = mg;
@@ -689,9 +697,11 @@ void launch_analysis_stream(const AnalysisLaunch& L, hipStream_t st) {
     if (L.plan.stride == kFSWide) {
         if (L.adjoint && a.l1_weight != 0.f) hipLaunchKernelGGL((analysis_stream_kernel<AN_ADJ, true, false, true>), grid, dim3(kSThreads), 0, st, a, R);
         else if (L.adjoint) hipLaunchKernelGGL((analysis_stream_kernel<AN_ADJ, false, false, true>), grid, dim3(kSThreads), 0, st, a, R);
+        else if (L.polar_exact) hipLaunchKernelGGL((analysis_stream_kernel<AN_NORM, false, false, true, true>), grid, dim3(kSThreads), 0, st, a, R);
         else hipLaunchKernelGGL((analysis_stream_kernel<AN_NORM, false, false, true>), grid, dim3(kSThreads), 0, st, a, R);
     } else if (L.adjoint && a.l1_weight != 0.f) hipLaunchKernelGGL((analysis_stream_kernel<AN_ADJ, true>), grid, dim3(kSThreads), 0, st, a, R);
     else if (L.adjoint) hipLaunchKernelGGL((analysis_stream_kernel<AN_ADJ, false>), grid, dim3(kSThreads), 0, st, a, R);
+    else if (L.polar_exact) hipLaunchKernelGGL((analysis_stream_kernel<AN_NORM, false, false, false, true>), grid, dim3(kSThreads), 0, st, a, R);
     else if (L.mel_out && L.melf_w && L.melf_s) {
         a.mel_out = L.mel_out; a.melf_w = L.melf_w; a.melf_s = L.melf_s; a.mag = nullptr;
         hipLaunchKernelGGL((analysis_stream_kernel<AN_NORM, false, true>), grid, dim3(kSThreads), 0, st, a, R);

@@ -40,6 +40,8 @@ struct AnalysisLaunch {
     int pstride = 0;
     int double_norm = 0;
     float unit_default = 0.f;
+    int polar_exact = 0;              // forward, mag / unit: the kernel forms with polar_exact (polar.hpp), for the original audio
+                                      // (begin, aware_stft_band).  0: the plain form of the loop's launches
     float* mag = nullptr;
     void* unit = nullptr;
     void* full = nullptr;
@@ -356,8 +358,9 @@ struct BandBegin {
     float *coef = nullptr, *lo = nullptr, *hi = nullptr, *mom = nullptr, *vel = nullptr, *best = nullptr, *c0 = nullptr;
     float ratio = 0.f;                    // 10^(-tolerance_db / 20)
 };
-// mag[row][f] = |spec[row][band_lo + f]|, padding columns zero; begin != null: the arrays of BandBegin too
-void launch_band_mag(const BandLaunch& L, const void* spec, float* mag, const BandBegin* begin, hipStream_t st);
+// mag[row][f] = |spec[row][band_lo + f]|, padding columns zero; begin != null: the arrays of BandBegin too.  exact (always
+// with begin): by polar_exact (polar.hpp), for spectra of the original audio; false: the plain form of the loop's launch
+void launch_band_mag(const BandLaunch& L, const void* spec, float* mag, const BandBegin* begin, bool exact, hipStream_t st);
 // spec[row][band_lo + f] = coef[row][f] * unit[row][f]; every other bin of spec is left as it is
 void launch_band_assemble(const BandLaunch& L, const float* coef, const void* unit, void* spec, hipStream_t st);
 // gspec[row][band_lo + f] = gmag[row][f] * spec / |spec| (0 where |spec| == 0); every other bin of gspec is left as it is

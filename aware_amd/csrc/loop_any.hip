@@ -23,9 +23,12 @@ __device__ __forceinline__ bool band_thread(const BandLaunch& L, int& row, int& 
     return row < L.NF;
 }
 
-template <bool BEGIN>
+// EXACT: the magnitude (and BEGIN's unit phasor) by polar_exact (polar.hpp), exact for bins of any amplitude: the original
+// audio's decomposition at begin and the magnitudes detection reads.  The loop's own launch keeps the plain form.
+template <bool BEGIN, bool EXACT>
 __global__ __launch_bounds__(256) void band_mag_kernel(BandLaunch L, const cf* __restrict__ spec, float* __restrict__ mag,
                                                        BandBegin G) {
+    static_assert(EXACT || !BEGIN, "begin stores the exact decomposition");
     int row, f;
     if (!band_thread(L, row, f)) return;
     const size_t idx = (size_t)row * L.bstride + f;
@@ -33,10 +36,12 @@ __global__ __launch_bounds__(256) void band_mag_kernel(BandLaunch L, const cf* _
     cf u = mk(0.f, 0.f);
     if (f < L.nband) {
         const cf X = spec[(size_t)row * L.sstride + L.band_lo + f];
-        mg = fast_sqrt(X.x * X.x + X.y * X.y);
-        if (BEGIN) {
-            const float im = fast_rcp(mg);
-            u = (mg > 0.f) ? mk(X.x * im, X.y * im) : mk(1.f, 0.f);
+        if (EXACT) {
+            const Polar p = polar_exact<HwMath>(X.x, X.y);
+            mg = p.mag;
+            if (BEGIN) u = (mg > 0.f) ? mk(p.ux, p.uy) : mk(1.f, 0.f);           // angle(0) = 0
+        } else {
+            mg = fast_sqrt(X.x * X.x + X.y * X.y);
         }
     }
     mag[idx] = mg;
@@ -123,9 +128,10 @@ inline dim3 band_block() { return dim3(64, kBandRows); }
 
 }  // namespace
 
-void launch_band_mag(const BandLaunch& L, const void* spec, float* mag, const BandBegin* begin, hipStream_t st) {
-    if (begin) hipLaunchKernelGGL(band_mag_kernel<true>, band_grid(L), band_block(), 0, st, L, (const cf*)spec, mag, *begin);
-    else hipLaunchKernelGGL(band_mag_kernel<false>, band_grid(L), band_block(), 0, st, L, (const cf*)spec, mag, BandBegin());
+void launch_band_mag(const BandLaunch& L, const void* spec, float* mag, const BandBegin* begin, bool exact, hipStream_t st) {
+    if (begin) hipLaunchKernelGGL((band_mag_kernel<true, true>), band_grid(L), band_block(), 0, st, L, (const cf*)spec, mag, *begin);
+    else if (exact) hipLaunchKernelGGL((band_mag_kernel<false, true>), band_grid(L), band_block(), 0, st, L, (const cf*)spec, mag, BandBegin());
+    else hipLaunchKernelGGL((band_mag_kernel<false, false>), band_grid(L), band_block(), 0, st, L, (const cf*)spec, mag, BandBegin());
 }
 
 void launch_band_assemble(const BandLaunch& L, const float* coef, const void* unit, void* spec, hipStream_t st) {

@@ -191,7 +191,12 @@ SHAPES = {
 }
 # "within rounding of the kink", relative: the absolute 2e-6 of test_gpu_kernels.py at an ordinary clip's largest |u| (about 4)
 KINK_REL = 5e-7
-_ORACLE = {}                    # (clip key) -> oracle results, shared by the shapes whose clips coincide
+# The loop's own magnitude |S2| = sqrt(re^2 + im^2) runs on the hardware square root, which reads a subnormal sum of squares
+# as zero: bins with |S2| < 2^-63 come out as 0 (hot-path code, left as it is).  A clip is held to the
+# fp64 bars of check d when fewer than 0.1 % of its band bins of |S2| lie below that in the fp64 oracle at c0.
+MAG_FLOOR = 2.0 ** -63
+WEAK_SHARE = 1e-3
+_ORACLE = {}                   # (clip key) -> oracle results, shared by the shapes whose clips coincide
 
 
 def _special_clip(k, n):
@@ -247,10 +252,14 @@ def _oracle(O, key, audio, wm_row):
         det_in, _ = _block_inputs(O, emb, mag)
     e64 = O.Embedder(dtype=torch.float64)
     m64, p64 = e64.analyse(a.double())
+    with torch.no_grad():
+        s2 = e64.recompute_magnitude(m64, p64)[0][0, e64.band]
+        weak, bins = int((s2 < MAG_FLOOR).sum()), s2.numel()
     c0 = m64[:, e64.band].clone().requires_grad_(True)
     l, p = e64.forward_loss(c0, m64, p64, torch.from_numpy(wm_row).double()[None])
     l.sum().backward()
-    r = dict(loop_in=loop_in, det_in=det_in, kink=kink, loss=float(l.detach()), pred=p[0].detach().numpy(), grad=c0.grad[0])
+    r = dict(loop_in=loop_in, det_in=det_in, kink=kink, loss=float(l.detach()), pred=p[0].detach().numpy(), grad=c0.grad[0],
+             weak=weak, bins=bins)
     _ORACLE[key] = r
     return r
 
@@ -281,11 +290,19 @@ def test_mixed_amplitude_batch_first_iteration(rt, plan, det, O, name):
          5e-5, gradient 5e-5 relative L2 (kink-aware as in b), the bar of the ordinary clips.  Measured on the CPU, the f32
          oracle against fp64 on the special clips: loss <= 1.4e-7, prediction <= 1.8e-7, gradient <= 1.6e-6 (1.5e-3 on one
          clip next to a kink): the normalisations bring a tiny clip back to O(1) before the mel block or scale the linear
-         regime exactly, so the special clips are conditioned like ordinary ones.  The clips with peaks below 1e-20 (1e-30,
-         2^-130, 2^-143) are printed, not asserted: there the device's first gradient differs from fp64 autograd by 1.25 -
-         1.27 relative L2 (loss and prediction agree to 7.6e-4 / 3.7e-3 on the 2^-143 clip, to 1.6e-7 on the others) while
-         the f32 oracle agrees with fp64 to 1.6e-6 and the three conv pipes agree with one another (b).  The difference
-         therefore lies outside the conv blocks this file is about (in the stages before or after them, not bisected here);
+         regime exactly, so the special clips are conditioned like ordinary ones.  A clip with a peak below 1e-20 is held
+         to the same bars when fewer than 0.1 % of the band bins of its recomputed magnitude |S2| lie below 2^-63 in the fp64
+         oracle at c0 (MAG_FLOOR): 1e-30 and 2^-130 count 0 bins and are asserted, 2^-143 counts about 6 % (839 of 14175 on a
+         one-second clip) and is printed with its count -- its synthesis reaches the second analysis near 1e-19, where the
+         loop's own sqrt(re^2 + im^2) on the hardware square root reads a subnormal sum of squares as zero (hot-path code,
+         left as it is: DESIGN.md section 38).  Up to commit 3c94db7 all three were printed only, 1.25 - 1.27 relative L2
+         from fp64 with loss and prediction right: the analysis of the original audio at begin used the same plain form, so
+         with x / (max|x| + 1e-8) at about 1e8 p every band bin of a clip with peak p <= 1e-28 was stored as magnitude 0 with
+         the default phasor (1, 0) (bins lost, measured: 0.06 % at 1e-26, 4.56 % at 1e-27, 99.81 % at 1e-28, 100 % below;
+         first gradient 2.3e-2, 0.21, 1.26, 1.28), and aware_embed_gradient projected on (1, 0) instead of the bins' phases,
+         while the out-of-band residual, built from the same magnitudes and phasors, kept the first synthesis and with it
+         loss and prediction right.  Begin now decomposes with polar_exact (csrc/polar.hpp); tests/test_gpu_quiet_clips.py
+         holds the stage itself;
       e. the silent clip: prediction exactly 0, loss exactly the oracle's (1: push_extremes of a zero prediction), finite
          gradient."""
     t0 = time.time()
@@ -333,15 +350,17 @@ def test_mixed_amplitude_batch_first_iteration(rt, plan, det, O, name):
                   f"pred {np.max(np.abs(p4[s] - p0[s])):.1e} gradient rel L2 {rel:.2e} kink(rel) {kink:.1e}")
             assert abs(l4[s] - l0[s]) < 2e-6 and np.max(np.abs(p4[s] - p0[s])) < 2e-6, (pipe, k)
             assert rel < (2e-5 if kink > KINK_REL else 2e-2), (pipe, k, rel, kink)
-    # d. the f32 pipe against fp64 (clips with peaks below 1e-20: printed only, see the docstring)
+    # d. the f32 pipe against fp64 (a clip whose own |S2| underflows in the loop: printed only, see MAG_FLOOR and the docstring)
     for i in orc:
         o = orc[i]
         mine = g0[sl[i]][:, :225].T
         rn = o["grad"].norm().item()
         rel = (mine - o["grad"]).norm().item() / rn if rn > 0 else mine.norm().item()
-        sub = 0 < np.abs(test[i][0]).max() < 1e-20
-        print(f"{name} f32 pipe vs fp64, clip {i}{' (peak < 1e-20: printed only)' if sub else ''}: loss {abs(l0[i] - o['loss']):.1e} "
-              f"pred {np.max(np.abs(p0[i] - o['pred'])):.1e} gradient rel L2 {rel:.2e}")
+        peak = np.abs(test[i][0]).max()
+        sub = 0 < peak < 1e-20 and not o["weak"] < WEAK_SHARE * o["bins"]       # from 1e-20 on a clip is held whatever it counts
+        why = f" (fp64 oracle: {o['weak']} of {o['bins']} band bins of |S2| below 2^-63: printed only)" if sub else ""
+        print(f"{name} f32 pipe vs fp64, clip {i} peak {peak:.1e}{why}: loss {abs(l0[i] - o['loss']):.1e} "
+              f"pred {np.max(np.abs(p0[i] - o['pred'])):.1e} gradient rel L2 {rel:.2e}; |S2| < 2^-63 on {o['weak']} of {o['bins']}")
         if not sub:
             assert abs(l0[i] - o["loss"]) < 2e-5 and np.max(np.abs(p0[i] - o["pred"])) < 5e-5, i
             assert rel < (5e-5 if o["kink"] > KINK_REL else 2e-2), (i, rel, o["kink"])
