@@ -2192,7 +2192,17 @@ extern "C" int aware_speed_views(const float* in, const int* in_off, const int* 
     return AWARE_OK;
 }
 
-// ---- scanning long recordings (EXTENSION; AWAREDetector.scan, runtime.scan_select, runtime.scan_segments, tests) ------------
+// ---- the shift search's views (EXTENSION; AWAREDetector.detect_batch(shift_search=...), runtime.shift_views, tests) ---------
+extern "C" int aware_shift_views(const float* in, const int* in_off, const int* in_len, int B, const int* d, int n_views,
+                                 float* out, const int* out_off, int max_len, void* stream) {
+    if (!in || !in_off || !in_len || !d || !out || !out_off || in == out) return AWARE_E_BADARG;
+    if (!ragged_args_ok(B, max_len) || n_views < 1 || n_views > 63) return AWARE_E_BADARG;
+    launch_shift_views(in, in_off, in_len, B, d, n_views, out, out_off, max_len, (hipStream_t)stream);
+    LAUNCHCHK();
+    return AWARE_OK;
+}
+
+// ---- scanning long recordings (EXTENSION; AWAREDetector.scan,runtime.scan_select, runtime.scan_segments, tests) ------------
 // win_off is read on the host: B + 1 window offsets from 0, never falling, at least one window in all
 static bool scan_offsets_ok(const int* win_off, int B) {
     if (win_off[0] != 0) return false;

@@ -675,6 +675,12 @@ void launch_sync_select(const float* values, int B, int n, int L, float centre, 
 void launch_speed_views(const float* in, const int* in_off, const int* in_len, int B, const int* m, int n_views, float* out,
                         const int* out_off, int max_len, hipStream_t st);
 
+// ---- shift_search_kernels.hip: shift search in detection (EXTENSION): every clip of a ragged batch moved by n_views
+// frequency shifts d[j] (units of sr / 2^20 Hz, |d| <= kShiftMax, start phase 0) in one launch; view (b, j) is in_len[b]
+// floats at out_off[b * n_views + j], bit for bit what launch_frequency_shift gives at that d and p0 = 0 ---------------------
+void launch_shift_views(const float* in, const int* in_off, const int* in_len, int B, const int* d, int n_views, float* out,
+                        const int* out_off, int max_len, hipStream_t st);
+
 // ---- scan_kernels.hip: scanning long recordings (EXTENSION).  launch_scan_select: values [W][n][L] -> per window the
 // confidence, index, row and packed decision bits ([W][ceil(L / 32)]) of the most confident view; one wave per window.
 // launch_scan_segments: per file b (windows win_off[b] .. win_off[b + 1], dev int [B + 1]) the runs of marked windows that

@@ -20,30 +20,14 @@
 // packed FMA on both: 128 FMAs per output.  The two windows of 8 samples slide through registers.  LDS: plane index p lives at
 // p + (p >> 3), so thread t, which reads 8 t + const, has stride 9 and a wave's 32-lane groups touch 32 banks (unpadded: 8);
 // the plane of the even samples starts 16 banks (mod 32) from the other, so the staging store of 32 consecutive samples, 16 to
-// each plane, touches a bank twice at most, which a 4-byte store absorbs.  The taps are read at one address by the whole wave.
+// each plane, touches a bank twice at most, which a 4-byte store absorbs.  The taps are read at one address by the whole wave.  The tile body (staging, taps, accumulation)
+// is shift_hilbert.hpp, which the shift search's kernel (shift_search_kernels.hip) includes as well.
 #include "loop_stage.hpp"
+#include "shift_hilbert.hpp"
 
 namespace aware {
 
 namespace {
-
-constexpr int kFsThreads = 256;
-constexpr int kFsPer = 8;                       // outputs per thread and parity
-constexpr int kFsTile = 2 * kFsPer * kFsThreads;        // 4096 outputs per workgroup and pass
-constexpr int kFsTaps = kFilterHalf + 1;                // 128 steps of the window: the odd taps
-constexpr int kFsPlane = kFsTile / 2 + kFsTaps + 2 * kFsPer;    // staged samples per plane: tile, halo, the last window's overshoot
-constexpr int kFsPlanePhys = 2480;              // >= kFsPlane + (kFsPlane >> 3) + 1, and 16 mod 32
-static_assert(kFsPlanePhys >= kFsPlane + (kFsPlane >> 3) + 1 && kFsPlanePhys % 32 == 16, "the planes' padding and bank offset");
-
-typedef float v2f __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ int fs_phys(int p) { return p + (p >> 3); }
-
-// phi_i in half turns: theta_i 2^-19, exact in f32
-__device__ __forceinline__ float fs_phase(int p0, int d, int i) {
-    const unsigned theta = ((unsigned)p0 + (unsigned)i * (unsigned)d) & 0xFFFFFu;
-    return (float)theta * (1.f / 524288.f);
-}
 
 template <bool LOOP, bool ADJOINT>
 __global__ __launch_bounds__(kFsThreads) void frequency_shift_kernel(ShiftLaunch a) {
@@ -76,50 +60,19 @@ __global__ __launch_bounds__(kFsThreads) void frequency_shift_kernel(ShiftLaunch
         for (int i = i0 + t; i < i1; i += kFsThreads) y[i] = x[i];
         return;
     }
-    if (t < kFsTaps / 2) {                      // the 64 distinct magnitudes: k = 127 - 2 t, odd, 127 down to 1
-        const int k = kFilterHalf - 2 * t;
-        const float w = 0.54f + 0.46f * cospif((float)k * (1.f / 127.f));
-        const float h = w * 2.f / (3.14159265358979323846f * (float)k);
-        hs[t] = h; hs[kFsTaps - 1 - t] = -h;    // g[127 - u] = h[2 u - 127] = -g[u]
-    }
+    fs_taps(hs, t);
     float* p1 = xs;
     float* p0s = xs + kFsPlanePhys;
     for (int t0 = i0; t0 < i1; t0 += kFsTile) { // t0 is even: a multiple of the hop, or of the tile
         const int len = min(kFsTile, i1 - t0);
         const int na = (len + 1) >> 1;          // pairs of outputs
-        __syncthreads();                        // the pass before is done with xs
         // staged sample q is x[t0 - 128 + q], of the parity of q: zero outside the clip; the adjoint stages g sin phi
-        for (int q = t; q < len + 2 * kFsTaps + 4 * kFsPer; q += kFsThreads) {
-            const int i = t0 - kFsTaps + q;
-            float v = 0.f;
-            if (i >= 0 && i < n) {
-                v = x[i];
-                if (ADJOINT) v *= sinpif(fs_phase(p0, d, i));
-            }
-            ((q & 1) ? p1 : p0s)[fs_phys(q >> 1)] = v;
-        }
-        __syncthreads();
+        fs_stage<ADJOINT>(x, n, t0, len, p0, d, p1, p0s, t);
         const int o = kFsPer * t;
         if (o >= na) continue;                  // the whole wave, but for the last one of a ragged tile
         // pair a = o + m: .x is output 2 a from P1[a + u], .y is output 2 a + 1 from P0[a + 1 + u], u = 0..127
-        const float* lo = p1 + 9 * t;           // fs_phys(o + c) = 9 t + fs_phys(c)
-        const float* hi = p0s + 9 * t;
-        v2f acc[kFsPer], w[kFsPer];
-#pragma unroll
-        for (int m = 0; m < kFsPer; ++m) { acc[m] = (v2f){0.f, 0.f}; w[m] = (v2f){lo[fs_phys(m)], hi[fs_phys(m + 1)]}; }
-        for (int u = 0; u < kFsTaps / kFsPer; ++u) {
-            const float4 ha = ((const float4*)hs)[2 * u], hb = ((const float4*)hs)[2 * u + 1];
-            const float h8[kFsPer] = {ha.x, ha.y, ha.z, ha.w, hb.x, hb.y, hb.z, hb.w};
-#pragma unroll
-            for (int s = 0; s < kFsPer; ++s) {
-                const float h = h8[s];          // g[8 u + s]
-#pragma unroll
-                for (int m = 0; m < kFsPer; ++m) acc[m] += h * w[m];
-#pragma unroll
-                for (int m = 0; m < kFsPer - 1; ++m) w[m] = w[m + 1];
-                w[kFsPer - 1] = (v2f){lo[9 * (u + 1) + s], hi[9 * (u + 1) + fs_phys(s + 1)]};
-            }
-        }
+        v2f acc[kFsPer];
+        fs_hilbert(p1, p0s, hs, t, acc);
         // out = c cos phi -+ H sin phi with the centre sample c = x[i] read again (the adjoint's H already carries the sine)
         const int j0 = 2 * o;                   // the first of this thread's 16 outputs, from t0
         float out[2 * kFsPer];

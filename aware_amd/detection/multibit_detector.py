@@ -3,9 +3,10 @@
 Reference: src/AWARE/detection/multibit_detector.py:9-42 -- normalise, STFT, magnitude, zero the
 bins outside the embedding band, network forward.  Batched entry point: detect_batch.  EXTENSION: sync_search = n reads n views of every clip, 512 / n samples
 apart, and keeps the most confident one (detection/sync.py); off by default.  EXTENSION: speed_search reads every clip at
-candidate playback speeds as well (same module); off by default.  EXTENSION: scan reads a long file in windows and returns the
-marked spans with one payload each (same module); off unless called.  EXTENSION: payload_code names the
-channel code of the payload (utils/watermark/fec.py): decode_messages runs the Viterbi decoder over rows
+candidate playback speeds as well (same module); off by default.  EXTENSION: shift_search reads every clip at candidate
+frequency shifts (same module); off by default, and not together with speed_search.  EXTENSION: scan
+reads a long file in windows and returns the marked spans with one payload each (same module); off
+unless called.  EXTENSION: payload_code names the channel code of the payload (utils/watermark/fec.py): decode_messages runs the Viterbi decoder over rows
 of values, and scan() adds the decoded message to every span; absent = no code."""
 from __future__ import annotations
 
@@ -23,10 +24,10 @@ class AWAREDetector(BaseDetector):
     def __init__(self, model, threshold: float = 0.0, frame_length: int = 1024, hop_length: int = 256,
                  window: str = "hann", win_length: int = 1024, pattern_mode: str = "bits2bipolar",
                  embedding_bands=(500, 4000), sync_search: int = 0, speed_search=None, scan=None, payload_code=None,
-                 general_geometry: bool = False):
+                 general_geometry: bool = False, shift_search=None):
         """general_geometry (EXTENSION): detect at any frame_length in runtime.GENERAL_NFFT, any
         hop_length and win_length in 1..frame_length, on the general route; off: the card geometry only.  With it sync_search,
-        speed_search and scan raise NotImplementedError (their offsets assume the card's 512-sample pooling period)."""
+        speed_search, shift_search and scan raise NotImplementedError (their offsets assume the card's 512-sample pooling period)."""
         self.general_geometry = bool(general_geometry)
         rt.require_card_geometry("AWAREDetector", frame_length, hop_length, win_length, self.general_geometry, window)
         self.sync_search = sync.check_sync_search(sync_search)
@@ -35,6 +36,11 @@ class AWAREDetector(BaseDetector):
             rt.refuse_general_geometry("sync_search")
         if self.general_geometry and self.speed_search is not None:
             rt.refuse_general_geometry("speed_search")
+        self.shift_search = sync.check_shift_search(shift_search)
+        if self.general_geometry and self.shift_search is not None:
+            rt.refuse_general_geometry("shift_search")
+        if self.speed_search is not None and self.shift_search is not None:
+            raise ValueError("AWAREDetector: speed_search and shift_search are both on; the product of the two grids is not served")
         if self.general_geometry and model is not None and getattr(model, "n_fft", frame_length) != frame_length:
             raise ValueError(f"AWAREDetector: the detection net's n_fft = {model.n_fft} but frame_length = {frame_length}; "
                              f"with general_geometry the detector's mel bank follows the STFT")
@@ -95,24 +101,45 @@ class AWAREDetector(BaseDetector):
         offsets in samples [B] int32, their confidence mean |value - centre| [B] float32) instead.  speed_search (default: the
         detector's own, None = off): max_percent or {"max_percent", "step_percent"} of the speed search.  return_speed:
         (values, offsets [B] int32, the chosen views' speed offsets m [B] int32 -- the clip was played at sync.speed_of(m) --
-        confidence [B] float32) instead."""
+        confidence [B] float32) instead.  A detector with shift_search on reads through its shift search here as well (m is
+        then 0); detect_batch_shift takes that key per call and returns the chosen shifts."""
+        return self._detect_any(clips, sample_rate, sync_search, return_sync, speed_search, return_speed, None, False)
+
+    def detect_batch_shift(self, clips, sample_rate: int, shift_search=None, sync_search=None, return_shift: bool = False):
+        """detect_batch through the shift search.  shift_search (default: the detector's own, None =
+        off): max_hz or {"max_hz", "step_hz"}.  return_shift: (values, offsets [B] int32, the chosen views' shifts d [B] int32
+        in units of sample_rate / 2^20 Hz -- the clip carried a shift of sync.shift_of(d, sample_rate) Hz -- confidence [B]
+        float32) instead of the values.  ValueError, before any launch: the search together with the detector's speed_search
+        (the product of the two grids is not served), max_hz above sample_rate / 16, a clip of 512 samples or fewer."""
+        return self._detect_any(clips, sample_rate, sync_search, False, None, False, shift_search, return_shift)
+
+    def _detect_any(self, clips, sample_rate, sync_search, return_sync, speed_search, return_speed, shift_search, return_shift):
         n = self.sync_search if sync_search is None else sync.check_sync_search(sync_search)
         speed = self.speed_search if speed_search is None else sync.check_speed_search(speed_search)
+        shift = self.shift_search if shift_search is None else sync.check_shift_search(shift_search)
         if self.general_geometry and n:
             rt.refuse_general_geometry("sync_search")
         if self.general_geometry and speed is not None:
             rt.refuse_general_geometry("speed_search")
+        if self.general_geometry and shift is not None:
+            rt.refuse_general_geometry("shift_search")
+        if speed is not None and shift is not None:
+            raise ValueError("AWAREDetector: speed_search and shift_search are both on; the product of the two grids is not served")
         if self.general_geometry:                                 # ValueError naming the clip, before any plan or launch
             rt.check_general_clips("AWAREDetector", self.frame_length, self.hop_length, self.win_length, self.window,
                                    [len(c) for c in clips], embed=False)
-        if speed is None:
-            out = self._detect_sync(clips, sample_rate, n, return_sync or return_speed)
-            if return_speed:
+        four = return_speed or return_shift
+        if speed is None and shift is None:
+            out = self._detect_sync(clips, sample_rate, n, return_sync or four)
+            if four:
                 return out[0], out[1], torch.zeros(len(clips), dtype=torch.int32, device=out[0].device), out[2]
             return out
-        vals, offsets, m, conf = self._detect_speed(clips, sample_rate, n, speed)
-        if return_speed:
-            return vals, offsets, m, conf
+        if shift is not None:
+            vals, offsets, grid, conf = self._detect_shift(clips, sample_rate, n, shift)
+        else:
+            vals, offsets, grid, conf = self._detect_speed(clips, sample_rate, n, speed)
+        if four:                                                  # return_speed of a shift search: m = 0, the speed is the clip's own
+            return vals, offsets, grid if return_shift == (shift is not None) else torch.zeros_like(grid), conf
         return (vals, offsets, conf) if return_sync else vals
 
     def _detect_sync(self, clips, sample_rate: int, n: int, return_sync: bool):
@@ -148,22 +175,36 @@ class AWAREDetector(BaseDetector):
         every speed offset in one aware_speed_views launch per chunk, one aware_detect over all the views (with n > 0 over the
         n overlapping windows into each), then aware_sync_select over the sync views and once more over the speed views."""
         ms = sync.speed_offsets(speed)
-        ns, nw = len(ms), max(n, 1)
-        lengths = [len(c) for c in clips]
-        vlen = sync.speed_views(lengths, speed, n)                # ValueError for a clip too short or too long, before any launch
+        vlen = sync.speed_views([len(c) for c in clips], speed, n)             # ValueError for a clip too short or too long, before any launch
+        return self._detect_views(clips, sample_rate, n, ms, vlen, lambda sub: rt.speed_views(sub, ms), sync.SPEED_MAX_SAMPLES,
+                                  "speed_search")
+
+    def _detect_shift(self, clips, sample_rate: int, n: int, shift: dict):
+        """(values, offsets, d, confidence) of the shift search `shift`, times the offset search where n > 0: every clip at
+        every candidate shift in one aware_shift_views launch per chunk, then as _detect_speed."""
+        ds = sync.shift_offsets(shift, sample_rate)               # ValueError for max_hz above sample_rate / 16
+        vlen = sync.shift_views([len(c) for c in clips], shift, sample_rate, n)            # ValueError for a clip too short or too long
+        return self._detect_views(clips, sample_rate, n, ds, vlen, lambda sub: rt.shift_views(sub, ds), sync.SHIFT_MAX_SAMPLES,
+                                  "shift_search")
+
+    def _detect_views(self, clips, sample_rate: int, n: int, grid, vlen, views, max_samples: int, what: str):
+        """What the speed and the shift search share: `views(sub)` writes the len(grid) views of every clip of a chunk (their
+        lengths vlen, clip-major), one aware_detect reads all rows (with n > 0 the n overlapping windows into each view), and
+        aware_sync_select picks over the sync views and then over the grid -> (values, offsets, grid value, confidence)."""
+        ns, nw = len(grid), max(n, 1)
         if ns * nw > sync.SYNC_MAX_ROWS:
-            raise ValueError(f"speed_search with sync_search = {n}: {ns} x {nw} views per clip; at most {sync.SYNC_MAX_ROWS}")
+            raise ValueError(f"{what} with sync_search = {n}: {ns} x {nw} views per clip; at most {sync.SYNC_MAX_ROWS}")
         plan = self._plan(sample_rate)
         det = self.detection_net.device_weights(plan)
         x = rt.Ragged.from_list([np.asarray(c, dtype=np.float32) for c in clips])
         offs = sync.sync_offsets(n)
         centre = self._centre()
-        md = torch.tensor(ms, dtype=torch.int32, device=x.data.device)
+        md = torch.tensor(grid, dtype=torch.int32, device=x.data.device)
         # chunks of whole clips: at most SYNC_MAX_ROWS rows per aware_detect call and 2^30 view samples per buffer
         padded = [sum((v + 3) // 4 * 4 for v in vlen[b * ns:(b + 1) * ns]) for b in range(len(clips))]
         chunks, b0, size = [], 0, 0
         for b in range(len(clips)):
-            if b > b0 and ((b - b0 + 1) * ns * nw > sync.SYNC_MAX_ROWS or size + padded[b] > sync.SPEED_MAX_SAMPLES):
+            if b > b0 and ((b - b0 + 1) * ns * nw > sync.SYNC_MAX_ROWS or size + padded[b] > max_samples):
                 chunks.append((b0, b))
                 b0, size = b, 0
             size += padded[b]
@@ -171,17 +212,17 @@ class AWAREDetector(BaseDetector):
         outs = []
         for b0, b1 in chunks:
             sub = x if (b0, b1) == (0, x.B) else rt.Ragged(x.data[x.offsets[b0]:x.offsets[b1 - 1] + x.lengths[b1 - 1]], x.lengths[b0:b1])
-            flat, sl, so = rt.speed_views(sub, ms)
+            flat, sl, so = views(sub)
             rows = rt.Batch([v - e for v in sl for e in offs], [o + e for o in so for e in offs])
             vals = rt.detect(plan, det, rows, flat)               # [(b1 - b0) * ns * nw, n_bits]
             if n:
-                vals, isync, _ = rt.sync_select(vals, n, centre)  # round one: the sync views of every (clip, speed view)
-            best, ispeed, conf = rt.sync_select(vals, ns, centre)             # round two: the speed views of every clip
+                vals, isync, _ = rt.sync_select(vals, n, centre)  # round one: the sync views of every (clip, grid view)
+            best, igrid, conf = rt.sync_select(vals, ns, centre)  # round two: the grid views of every clip
             if n:
-                chosen = isync.view(b1 - b0, ns).gather(1, ispeed.long()[:, None])[:, 0] * (sync.SYNC_PERIOD // n)
+                chosen = isync.view(b1 - b0, ns).gather(1, igrid.long()[:, None])[:, 0] * (sync.SYNC_PERIOD // n)
             else:
                 chosen = torch.zeros(b1 - b0, dtype=torch.int32, device=best.device)
-            outs.append((best, chosen.to(torch.int32), md[ispeed.long()], conf))
+            outs.append((best, chosen.to(torch.int32), md[igrid.long()], conf))
         return tuple(torch.cat([o[i] for o in outs]) for i in range(4))
 
     def scan(self, clips, sample_rate: int, window_seconds=None, hop_samples=None, sync_search=None, min_confidence=None,
@@ -199,11 +240,14 @@ class AWAREDetector(BaseDetector):
         detector also `message`, `valid` and `corrected` of decode_messages (valid informs; it does not filter).  return_profile: (spans,
         profiles) instead, a profile per file being a dict of `starts` (the window starts), `length` (samples per window),
         `win_conf`, `win_view` and `win_values` (numpy, per window: the best view's confidence, index and row) and `n_segments` (the true span count, which max_segments may have cut).
-        ValueError, before any launch: a parameter check_scan refuses, a file too short (by its index), speed_search on."""
+        ValueError, before any launch: a parameter check_scan refuses, a file too short (by its index), speed_search or
+        shift_search on."""
         if self.general_geometry:
             rt.refuse_general_geometry("scan")
         if self.speed_search is not None:
             raise ValueError("scan: speed_search is on for this detector; scanning at candidate speeds is not supported")
+        if self.shift_search is not None:
+            raise ValueError("scan: shift_search is on for this detector; scanning at candidate frequency shifts is not supported")
         d = self.scan_defaults
         par = sync.check_scan(d["window_seconds"] if window_seconds is None else window_seconds,
                               d["hop_samples"] if hop_samples is None else hop_samples,

@@ -20,7 +20,21 @@ detector reads every clip at 2 K + 1 candidate speeds and keeps the most confide
 
 the existing operator (Catmull-Rom at the 16.16 positions i (65536 + m_j)) at the length that keeps every position inside the
 clip.  The device writes all views in one launch (csrc/speed_search_kernels.hip, aware_speed_views).  With the offset search on
-as well, every speed view is read at the n sync offsets, and `speed_select` states the selection over all of them."""
+as well, every speed view is read at the n sync offsets, and `speed_select` states the selection over all of them.
+
+Shift search (EXTENSION as well).  A clip whose every component was moved by the same number of Hz
+(single-sideband modulation: a detuned receiver, an analogue carrier) loses its bits, a quarter to a third of them at 20 Hz and
+all of them at 50 Hz, and reads them again once it is moved back.  With shift_search on, the detector reads every clip at
+2 K + 1 candidate shifts and keeps the most confident view, by the same rule:
+
+    delta = loop_attacks.shift_increment(step_hz, sample_rate),  K = floor(max_hz / step_hz + 1e-9),  K delta <= MAX_SHIFT,
+    d_0 = 0,  d_{2i-1} = -i delta,  d_{2i} = +i delta,  i = 1 .. K          (ordered by |d|: a tie prefers the plain read)
+    view j of a clip = loop_attacks.frequency_shift(x, d_j, 0)
+
+the existing operator (the 255-tap Hilbert transformer and the integer phase (i d_j) mod 2^20) from the start phase 0; every
+view has the clip's length.  The device writes all views in one launch (csrc/shift_search_kernels.hip, aware_shift_views), the
+Hilbert transform once per clip.  `shift_select` is `speed_select`'s rule, sync views included.  The search is not served
+together with the speed search: the product of the two grids is not read."""
 from __future__ import annotations
 
 import math
@@ -33,6 +47,9 @@ SYNC_MAX_ROWS = 4096                    # views per aware_detect call: larger se
 SPEED_MAX_VIEWS = 63                    # speed views per clip: the second round of aware_sync_select takes n <= 64
 SPEED_MAX_SAMPLES = 1 << 30             # samples of the views of one aware_speed_views call
 SPEED_STEP_DEFAULT = 0.5                # percent: the confidence peak is about +-0.35 % wide at half height
+SHIFT_MAX_VIEWS = 63                    # shift views per clip: the second round of aware_sync_select takes n <= 64
+SHIFT_MAX_SAMPLES = 1 << 30             # samples of the views of one aware_shift_views call
+SHIFT_STEP_DEFAULT = 10.0               # Hz: a residual of 5 Hz keeps 0.161 of the confidence 0.264 at 0 Hz, one of 13 Hz 0.044
 
 
 def check_sync_search(n) -> int:
@@ -163,6 +180,85 @@ def speed_select(values, n_speed: int, n_sync: int = 0, centre: float = 0.0):
     idx_speed * n_sync + idx_sync [B] int32; that mean [B] float32).  It equals two rounds of sync_select, over the sync views
     of every (clip, speed view) and then over the speed views, which is how the device selects."""
     return sync_select(values, int(n_speed) * max(int(n_sync), 1), centre)
+
+
+# ---- shift search -------------------------------------------------------------------------------------------------------------------
+def check_shift_search(search):
+    """None for off (None, 0, False or {}), {"max_hz", "step_hz"} in floats otherwise.  A number is max_hz with step_hz = 10.
+    ValueError for anything else: values that are not finite numbers, 1 <= step_hz <= 20 and step_hz <= max_hz violated, an
+    unknown key, more than 63 views.  (max_hz <= sample_rate / 16 is shift_offsets' to check: it needs the sample rate.)"""
+    def number(v, what):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(float(v)):
+            raise ValueError(f"shift_search: {what} = {v!r}: a finite number is expected")
+        return float(v)
+
+    if search is None or search is False:
+        return None
+    if isinstance(search, dict):
+        if not search:
+            return None
+        unknown = sorted(set(search) - {"max_hz", "step_hz"}, key=str)
+        if unknown or "max_hz" not in search:
+            raise ValueError(f"shift_search = {search!r}: the keys are max_hz and, optionally, step_hz")
+        mx = number(search["max_hz"], "max_hz")
+        step = number(search.get("step_hz", SHIFT_STEP_DEFAULT), "step_hz")
+    else:
+        mx, step = number(search, "max_hz"), SHIFT_STEP_DEFAULT
+        if mx == 0.0:
+            return None
+    if not 1.0 <= step <= 20.0:
+        raise ValueError(f"shift_search: step_hz = {step}: 1 <= step_hz <= 20 is expected")
+    if not step <= mx:
+        raise ValueError(f"shift_search: max_hz = {mx}: step_hz = {step} <= max_hz is expected")
+    views = 2 * int(math.floor(mx / step + 1e-9)) + 1
+    if views > SHIFT_MAX_VIEWS:
+        raise ValueError(f"shift_search: max_hz = {mx} at step_hz = {step} is {views} views; at most {SHIFT_MAX_VIEWS}")
+    return {"max_hz": mx, "step_hz": step}
+
+
+def shift_offsets(search, sample_rate: int) -> list[int]:
+    """The shifts d_j of the views in units of sample_rate / 2^20 Hz, ordered by |d|: [0, -delta, +delta, -2 delta, ...] with
+    delta = shift_increment(step_hz, sample_rate); [0] where the search is off.  ValueError where K delta exceeds MAX_SHIFT
+    (max_hz above sample_rate / 16) or delta is 0."""
+    from ..embedding.loop_attacks import MAX_SHIFT, shift_increment
+    s = check_shift_search(search)
+    if s is None:
+        return [0]
+    delta = shift_increment(s["step_hz"], int(sample_rate))
+    k = int(math.floor(s["max_hz"] / s["step_hz"] + 1e-9))
+    if delta < 1 or k * delta > MAX_SHIFT:
+        raise ValueError(f"shift_search: max_hz = {s['max_hz']} at step_hz = {s['step_hz']} is +-{k * delta} in units of "
+                         f"{int(sample_rate)} / 2^20 Hz, outside 1..{MAX_SHIFT} (+-{int(sample_rate) / 16:g} Hz)")
+    return [0] + [sign * i * delta for i in range(1, k + 1) for sign in (-1, 1)]
+
+
+def shift_of(d: int, sample_rate: int) -> float:
+    """The shift in Hz a received clip carried, if the view at d restores it: -d sample_rate / 2^20."""
+    return -int(d) * float(sample_rate) / float(1 << 20)
+
+
+def shift_views(lengths, search, sample_rate: int, sync_n: int = 0) -> list[int]:
+    """The view lengths, clip-major, of clips `lengths` long: every view of clip b has n_b samples.  ValueError, naming the
+    clip, where n_b less the largest offset of the offset search sync_n is 512 or fewer (the STFT's reflect padding needs
+    more), or where the views of one clip, each padded to a multiple of four samples, exceed 2^30."""
+    nv = len(shift_offsets(search, sample_rate))
+    drop = sync_offsets(sync_n)[-1]
+    out = []
+    for b, nb in enumerate(lengths):
+        nb = int(nb)
+        if nb - drop <= SYNC_PERIOD:
+            raise ValueError(f"shift_search: clip {b} has {nb} samples; its views ({nb}"
+                             + (f", less {drop} for sync_search = {sync_n}" if drop else "") + f") need more than {SYNC_PERIOD}")
+        if nv * ((nb + 3) // 4 * 4) > SHIFT_MAX_SAMPLES:
+            raise ValueError(f"shift_search: the {nv} views of clip {b} ({nb} samples) exceed 2^30 samples")
+        out += [nb] * nv
+    return out
+
+
+def shift_select(values, n_shift: int, n_sync: int = 0, centre: float = 0.0):
+    """speed_select's rule for the shift search: values [B * n_shift * max(n_sync, 1), L], clip-major, then the shift view, then
+    the sync view -> (out [B, L], the flat index idx_shift * n_sync + idx_sync [B] int32, the confidence [B] float32)."""
+    return speed_select(values, n_shift, n_sync, centre)
 
 
 # ---- scanning long recordings -------------------------------------------------------------------------------------------------------

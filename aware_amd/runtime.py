@@ -1419,6 +1419,37 @@ def speed_views(x: Ragged, ms, out: torch.Tensor | None = None):
     return flat, vlen, voff[:-1].tolist()
 
 
+def shift_views(x: Ragged, d, out: torch.Tensor | None = None):
+    """The views of detection.sync's shift search (aware_shift_views): every clip of x at every frequency shift of d (units of
+    sr / 2^20 Hz, signed, |d| <= 65536), in one launch -> (flat float32 device tensor, view lengths, view offsets into it),
+    both clip-major lists of x.B * len(d); view (b, j) is x.lengths[b] samples, bit for bit frequency_shift(x, d[j], 0).  The
+    offsets are multiples of four floats; the up to three floats between two rows are not written.  out: a float32 device
+    tensor of at least the views' size to write into."""
+    from .embedding.loop_attacks import MAX_SHIFT
+    lib = load_library()
+    ds = [int(v) for v in d]
+    if not 1 <= len(ds) <= 63 or any(abs(v) > MAX_SHIFT for v in ds):
+        raise ValueError(f"shift_views: 1 to 63 shifts within +-{MAX_SHIFT} are required; got {ds}")
+    if min(x.lengths) < 1:
+        raise ValueError(f"shift_views: every clip needs a sample; got {x.lengths}")
+    vlen = [int(n) for n in x.lengths for _ in ds]
+    voff = np.concatenate([[0], np.cumsum([(n + 3) // 4 * 4 for n in vlen])]).astype(np.int64)
+    if int(voff[-1]) > 1 << 30:
+        raise ValueError(f"shift_views: the views hold {int(voff[-1])} samples; at most 2^30 per call")
+    xin = x.data if x.data.dtype == torch.float32 else x.data.float()
+    if out is None:
+        flat = torch.empty(int(voff[-1]), dtype=torch.float32, device=xin.device)
+    elif out.dtype != torch.float32 or out.dim() != 1 or out.numel() < int(voff[-1]) or not out.is_contiguous() or out.device != xin.device:
+        raise ValueError(f"shift_views: out needs {int(voff[-1])} contiguous float32 values on x's device")
+    else:
+        flat = out
+    dd = torch.tensor(ds, dtype=torch.int32, device=xin.device)
+    od = torch.tensor(voff[:-1], dtype=torch.int32, device=xin.device)
+    check(lib.aware_shift_views(_ptr(xin), _ptr(x.d_off), _ptr(x.d_len), x.B, _ptr(dd), len(ds), _ptr(flat), _ptr(od),
+                                max(vlen), _stream()), "aware_shift_views")
+    return flat, vlen, voff[:-1].tolist()
+
+
 def stretch_ola(x: Ragged, m, adjoint: bool = False, out_lengths=None) -> Ragged:
     """Per clip embedding.loop_attacks.time_stretch at the offsets m (B integers, or one for all): clip b stretched in time at
     the rate (65536 + m[b]) / 65536 by plain overlap-add (aware_stretch_ola), out_lengths[b] samples long (default: the clip's

@@ -2,6 +2,7 @@
 stereo [N,2] (per bit, the channel with the larger |value| wins, :23-37), then PatternDecoder.
 EXTENSION: sync_search = n runs the detector's offset search (detection/sync.py); None keeps the detector's own setting.
 EXTENSION: speed_search runs its speed search (same module), likewise.
+EXTENSION: a detector with shift_search on (the card key) runs its shift search in every function here.
 EXTENSION: scan_watermark reads a long recording in windows and returns its marked spans, one payload each (same module).
 EXTENSION: detect_message reads the message of a coded payload (utils/watermark/fec.py), and with a
 payload_code on the detector every span of a scan carries its decoded message."""
@@ -14,7 +15,7 @@ from ..utils.watermark import PatternDecoder
 def _searches(detector, sync_search, speed_search) -> bool:
     """Whether a search is asked for, here or by the detector."""
     return (sync_search is not None or speed_search is not None or bool(getattr(detector, "sync_search", 0))
-            or bool(getattr(detector, "speed_search", None)))
+            or bool(getattr(detector, "speed_search", None)) or bool(getattr(detector, "shift_search", None)))
 
 
 def _detect(detector, clips, sample_rate, sync_search, speed_search=None):
@@ -22,6 +23,11 @@ def _detect(detector, clips, sample_rate, sync_search, speed_search=None):
     speed search's keyword goes only to a detector that is asked for it."""
     if not _searches(detector, sync_search, speed_search):
         return detector.detect_batch(clips, sample_rate)
+    if getattr(detector, "shift_search", None) and speed_search is None:
+        vals, offsets, d, conf = detector.detect_batch_shift(clips, sample_rate, sync_search=sync_search, return_shift=True)
+        logger.debug(f"shift search: shifts {d.cpu().tolist()} x {sample_rate} / 2^20 Hz, offsets {offsets.cpu().tolist()} samples, "
+                     f"confidence {[round(float(c), 4) for c in conf.cpu()]}")
+        return vals
     if speed_search is None and not getattr(detector, "speed_search", None):
         vals, offsets, conf = detector.detect_batch(clips, sample_rate, sync_search=sync_search, return_sync=True)
         logger.debug(f"sync search: offsets {offsets.cpu().tolist()} samples, confidence {[round(float(c), 4) for c in conf.cpu()]}")

@@ -31,6 +31,8 @@ _DETECTOR = {"threshold": ("threshold", 0.0), "pattern_mode": ("pattern_mode", "
              "sync_search": ("sync_search", 0),
              # EXTENSION (detection/sync.py): speed search in detection; absent = off
              "speed_search": ("speed_search", None),
+             # EXTENSION (detection/sync.py): shift search in detection; absent = off
+             "shift_search": ("shift_search", None),
              # EXTENSION (detection/sync.py): the defaults of AWAREDetector.scan; absent = window_seconds 1.0,
              # hop_samples 4096, min_confidence 0.06, max_segments 16
              "scan": ("scan", None),

@@ -933,7 +933,24 @@ int aware_sync_select(const float* values, int B, int n, int L, float centre, fl
 int aware_speed_views(const float* in, const int* in_off, const int* in_len, int B, const int* m, int n_views, float* out,
                       const int* out_off, int max_len, void* stream);
 
-/* ---- scanning long recordings (EXTENSION, parity unpinned: the reference reads one payload per clip) ----------------------
+/* ---- shift search in detection (EXTENSION, parity unpinned: the reference detects a clip as it is) -------------------------
+ * A clip whose every component was moved by the same number of Hz (single-sideband modulation) reads its bits again once it
+ * is moved back.  The host detects n_views shifted views of each clip, d[0] = 0 first (one aware_detect on a batch of
+ * B * n_views rows, times the views of the offset search where that is on), and keeps the best view per clip with
+ * aware_sync_select.  This entry writes the views, all in one launch on `stream`:
+ *   clip b is in_len[b] floats at float offset in_off[b] of `in` (dev int [B], any offsets); d dev int [n_views], shifts in
+ *   units of sample_rate / 2^20 Hz, signed, positive upwards;
+ *   view (b, j): in_len[b] floats at out + out_off[b * n_views + j] (dev int [B * n_views], from the host: rows that start
+ *   at multiples of 4 floats are stored 16 bytes at a time), equal bit for bit to aware_frequency_shift at d[j] with
+ *   p0 = 0; d[j] = 0 gives the clip itself.  The Hilbert transform is computed once per clip and shared by its views.
+ *   max_len >= every in_len[b].  Floats of `out` outside the rows are not written.  A view whose d[j] lies outside
+ *   -65536..65536 is not written.
+ * AWARE_E_BADARG, before anything is launched: a null pointer, in == out, B outside 1..65535, n_views outside 1..63,
+ * max_len outside 1..2^30.  Added without a version step: callers detect the addition by symbol. */
+int aware_shift_views(const float* in, const int* in_off, const int* in_len, int B, const int* d, int n_views, float* out,
+                      const int* out_off, int max_len, void* stream);
+
+/* ---- scanning long recordings (EXTENSION, parity unpinned: the reference reads one payload per clip)----------------------
  * A file in which only a part is marked reads nothing as a whole.  The host detects every file in windows, window w at the
  * n_sync views of the offset search (aware_detect on rows with overlapping in_offsets, window-major, file after file), and
  * these two entries, one launch each on `stream`, read one payload per marked span.  win_off is a HOST int [B + 1]: file b owns
