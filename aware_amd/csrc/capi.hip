@@ -140,7 +140,23 @@ struct aware_detector {
     int act = kActLRelu, norm = kNormInstance, final_act = kActTanh;
     std::vector<float*> nscale, nshift;   // affine norm (BatchNorm1d in eval mode, folded): u = z * nscale[l][c] + nshift[l][c]
     float* normmem = nullptr;
+    // temporal convolutions (aware_detector_create_conv with kernel_size / stride / padding other than 1 / 1 / 0; conv_taps.hpp):
+    // every block is Conv1d over tk taps, stride ts, padding tp.  w[l] is then [Cout][tk Cin] (column j Cin + ci = tap j of
+    // input channel ci), wT[l] its transpose and wpk / wTpk their packed forms: the operands of the plain GEMM on the unfolded
+    // rows.  Such a detector is never card_arch: it runs the staged route in every block, whatever its activations are
+    bool taps = false;
+    int tk = 1, ts = 1, tp = 0;
+    int max_cin = 0;         // the widest block input (stored), for the unfold scratch [NP][tk max_cin]
 };
+// the rows a kernel behind `blocks` blocks of the detector works on
+static TapRows det_rows(const aware_detector* d, int blocks) { return d->taps ? TapRows{blocks, d->tk, d->ts, d->tp} : TapRows(); }
+// every clip keeps at least one row through every block (torch's conv1d raises where one does not)
+static bool det_clips_ok(const aware_detector* d, const aware_batch* b) {
+    if (!d->taps) return true;
+    for (int i = 0; i < b->B; ++i)
+        if (conv_rows(b->T[i] / 2, d->n_layers, d->tk, d->ts, d->tp) < 1) return false;
+    return true;
+}
 static_assert(AWARE_ACT_RELU == kActRelu && AWARE_ACT_LEAKY_RELU == kActLRelu && AWARE_ACT_GELU == kActGelu &&
               AWARE_ACT_SWISH == kActSwish && AWARE_FINAL_TANH == kActTanh && AWARE_FINAL_SIGMOID == kActSigmoid &&
               AWARE_FINAL_RELU == kActRelu && AWARE_FINAL_LEAKY_RELU == kActLRelu && AWARE_FINAL_GELU == kActGelu &&
@@ -641,7 +657,8 @@ static int detector_upload(aware_detector* d, const float* mel_basis, const floa
     const int Mp = channels[0];
     const int S = d->stride;
     size_t total = (size_t)Mp * S * 2;
-    for (int i = 0; i < n_layers; ++i) total += (size_t)channels[i] * channels[i + 1] * 2 + channels[i + 1];
+    const int K = d->tk;      // taps per block (1: the 1x1 convolutions)
+    for (int i = 0; i < n_layers; ++i) total += (size_t)K * channels[i] * channels[i + 1] * 2 + channels[i + 1];
     std::vector<float> h(total, 0.f);
     size_t o = 0;
     const int nbins = d->n_fft / 2 + 1;
@@ -708,17 +725,18 @@ static int detector_upload(aware_detector* d, const float* mel_basis, const floa
     }
     std::vector<size_t> o_w(n_layers), o_wT(n_layers), o_b(n_layers);
     for (int l = 0; l < n_layers; ++l) {
-        const int ci = channels[l], co = channels[l + 1];
-        const int uci = uch[l], rows = uch[l + 1];   // the caller's shape [rows][uci]; padding rows and columns stay zero
-        o_w[l] = o; o += (size_t)ci * co;
-        o_wT[l] = o; o += (size_t)ci * co;
+        const int ci = channels[l], co = channels[l + 1], kc = K * ci;
+        const int uci = uch[l], rows = uch[l + 1];   // the caller's shape [rows][uci][K]; padding rows and columns stay zero
+        o_w[l] = o; o += (size_t)kc * co;
+        o_wT[l] = o; o += (size_t)kc * co;
         o_b[l] = o; o += co;
         for (int r = 0; r < rows; ++r)
-            for (int c = 0; c < uci; ++c) {
-                float v = weights[l][(size_t)r * uci + c];
-                h[o_w[l] + (size_t)r * ci + c] = v;
-                h[o_wT[l] + (size_t)c * co + r] = v;
-            }
+            for (int c = 0; c < uci; ++c)
+                for (int j = 0; j < K; ++j) {
+                    float v = weights[l][((size_t)r * uci + c) * K + j];
+                    h[o_w[l] + (size_t)r * kc + (size_t)j * ci + c] = v;
+                    h[o_wT[l] + ((size_t)j * ci + c) * co + r] = v;
+                }
         for (int r = 0; r < rows; ++r) h[o_b[l] + r] = biases && biases[l] ? biases[l][r] : 0.f;
     }
     if (alloc) HIPCHK(hipMalloc((void**)&d->mem, total * sizeof(float)));
@@ -730,7 +748,7 @@ static int detector_upload(aware_detector* d, const float* mel_basis, const floa
         size_t pk_total = 0;
         std::vector<size_t> o_pk(n_layers), o_pkT(n_layers);
         for (int l = 0; l < n_layers; ++l) {
-            const int ci = channels[l], co = channels[l + 1];
+            const int ci = K * channels[l], co = channels[l + 1];
             o_pk[l] = o_pkT[l] = (size_t)-1;
             if (co % 128 == 0 && ci % 64 == 0) { o_pk[l] = pk_total; pk_total += x3_packed_bytes(co, ci); }
             if (ci % 128 == 0 && co % 64 == 0) { o_pkT[l] = pk_total; pk_total += x3_packed_bytes(ci, co); }
@@ -741,7 +759,7 @@ static int detector_upload(aware_detector* d, const float* mel_basis, const floa
         const size_t o_mB = pk_total; if (mB) pk_total += x3_packed_bytes(S, Mp);
         // read-out kernel operands (last conv block, C <= 64 channels)
         const int cil = channels[n_layers - 1], col = channels[n_layers], colp = 16 * ((col + 15) / 16);
-        const bool ro = n_layers >= 2 && readout_x3_supported(1, cil, col);
+        const bool ro = !d->taps && n_layers >= 2 && readout_x3_supported(1, cil, col);   // (the fused read-out: 1x1 blocks only)
         size_t o_lp = 0, o_lT = 0;
         if (ro) {
             o_lp = pk_total; pk_total += x3_packed_bytes(colp, cil);
@@ -762,7 +780,7 @@ static int detector_upload(aware_detector* d, const float* mel_basis, const floa
         if (mT) x3_pack(h.data() + o_melT, Mp, S, hp.data() + o_mT / 2);
         if (mB) x3_pack(h.data() + o_melB, S, Mp, hp.data() + o_mB / 2);
         for (int l = 0; l < n_layers; ++l) {
-            const int ci = channels[l], co = channels[l + 1];
+            const int ci = K * channels[l], co = channels[l + 1];
             if (o_pk[l] != (size_t)-1) x3_pack(h.data() + o_w[l], co, ci, hp.data() + o_pk[l] / 2);
             if (o_pkT[l] != (size_t)-1) x3_pack(h.data() + o_wT[l], ci, co, hp.data() + o_pkT[l] / 2);
         }
@@ -780,7 +798,7 @@ static int detector_upload(aware_detector* d, const float* mel_basis, const floa
         // f16 two-term images, packed on the device from the f32 copies just uploaded
         size_t total2 = 0;
         std::vector<size_t> o_h(n_layers), o_hT(n_layers);
-        for (int l = 0; l < n_layers; ++l) {
+        for (int l = 0; l < n_layers && !d->taps; ++l) {      // (the f16 two-term kernels serve the fused conv blocks only)
             const int ci = channels[l], co = channels[l + 1];
             o_h[l] = o_hT[l] = (size_t)-1;
             if (gemm_clip_h2_supported(1, co, ci, ci)) { o_h[l] = total2; total2 += (h2_packed_bytes(co, ci) + 255) & ~(size_t)255; }
@@ -802,7 +820,7 @@ static int detector_upload(aware_detector* d, const float* mel_basis, const floa
 
 static int detector_create(aware_detector** out, const aware_plan* plan, const float* mel_basis, int n_mels, int n_layers,
                            const int* channels, const float* const* weights, const float* const* biases,
-                           const aware_detector_arch* arch) {
+                           const aware_detector_arch* arch, int tk = 1, int ts = 1, int tp = 0) {
     if (!out || !plan || !mel_basis || !channels || !weights) return AWARE_E_BADARG;
     // a general plan made for the transforms alone (no AWARE_PLAN_GENERAL), or a band outside bins 0..n_fft/2
     if (plan->general && (!plan->loop || !plan->band_ok)) return AWARE_E_UNSUPPORTED;
@@ -820,7 +838,10 @@ static int detector_create(aware_detector** out, const aware_plan* plan, const f
     for (int i = 0; i <= n_layers; ++i) {
         d->ch[i] = stored_channels(i, n_layers, channels[i]);
         if (d->ch[i] > d->maxc) d->maxc = d->ch[i];
+        if (i < n_layers && d->ch[i] > d->max_cin) d->max_cin = d->ch[i];
     }
+    d->taps = tk != 1 || ts != 1 || tp != 0;
+    d->tk = tk; d->ts = ts; d->tp = tp;
     d->w.assign(n_layers, nullptr); d->wT.assign(n_layers, nullptr); d->bias.assign(n_layers, nullptr);
     d->wpk.assign(n_layers, nullptr); d->wTpk.assign(n_layers, nullptr);
     d->wh2.assign(n_layers, nullptr); d->wTh2.assign(n_layers, nullptr);
@@ -829,6 +850,7 @@ static int detector_create(aware_detector** out, const aware_plan* plan, const f
         d->act = arch->activation; d->norm = arch->norm; d->final_act = arch->final_activation;
         d->card_arch = d->act == kActLRelu && d->norm == kNormInstance && d->final_act == kActTanh;
     }
+    if (d->taps) d->card_arch = false;
     int rc = detector_upload(d.get(), mel_basis, weights, biases, true);
     if (rc == AWARE_OK && d->norm == kNormAffine) {
         // padding channels (stored_channels) get scale 0 and shift 0: their pre-activation is 0 and their output act(0) = 0
@@ -864,19 +886,74 @@ extern "C" int aware_detector_create(aware_detector** out, const aware_plan* pla
                                      const float* const* biases) {
     return detector_create(out, plan, mel_basis, n_mels, n_layers, channels, weights, biases, nullptr);
 }
+// an aware_detector_arch with its enum values in range and, for BatchNorm, the folded map of every block
+static bool arch_ok(const aware_detector_arch* arch, int n_layers) {
+    if (!arch) return false;
+    if (arch->activation < AWARE_ACT_RELU || arch->activation > AWARE_ACT_SWISH) return false;
+    if (arch->norm < AWARE_NORM_INSTANCE || arch->norm > AWARE_NORM_NONE) return false;
+    if (arch->final_activation < AWARE_FINAL_RELU || arch->final_activation > AWARE_FINAL_SIGMOID) return false;
+    if (arch->norm == AWARE_NORM_BATCH) {
+        if (!arch->norm_scale || !arch->norm_shift || n_layers < 1 || n_layers > kMaxLayers) return false;
+        for (int l = 0; l < n_layers; ++l)
+            if (!arch->norm_scale[l] || !arch->norm_shift[l]) return false;
+    }
+    return true;
+}
 extern "C" int aware_detector_create_ex(aware_detector** out, const aware_plan* plan, const float* mel_basis, int n_mels,
                                         int n_layers, const int* channels, const float* const* weights,
                                         const float* const* biases, const aware_detector_arch* arch) {
-    if (!arch) return AWARE_E_BADARG;
-    if (arch->activation < AWARE_ACT_RELU || arch->activation > AWARE_ACT_SWISH) return AWARE_E_BADARG;
-    if (arch->norm < AWARE_NORM_INSTANCE || arch->norm > AWARE_NORM_NONE) return AWARE_E_BADARG;
-    if (arch->final_activation < AWARE_FINAL_RELU || arch->final_activation > AWARE_FINAL_SIGMOID) return AWARE_E_BADARG;
-    if (arch->norm == AWARE_NORM_BATCH) {
-        if (!arch->norm_scale || !arch->norm_shift || n_layers < 1 || n_layers > kMaxLayers) return AWARE_E_BADARG;
-        for (int l = 0; l < n_layers; ++l)
-            if (!arch->norm_scale[l] || !arch->norm_shift[l]) return AWARE_E_BADARG;
-    }
+    if (!arch_ok(arch, n_layers)) return AWARE_E_BADARG;
     return detector_create(out, plan, mel_basis, n_mels, n_layers, channels, weights, biases, arch);
+}
+// The same for a detector of temporal convolutions: every block Conv1d(C_in, C_out, kernel_size, stride, padding) along the
+// pooled frames (conv_taps.hpp); weights[l] is [Cout][Cin][kernel_size].  1 / 1 / 0 is aware_detector_create_ex.
+extern "C" int aware_detector_create_conv(aware_detector** out, const aware_plan* plan, const float* mel_basis, int n_mels,
+                                          int n_layers, const int* channels, const float* const* weights,
+                                          const float* const* biases, const aware_detector_arch* arch, int kernel_size, int stride,
+                                          int padding) {
+    if (kernel_size < 1 || stride < 1 || padding < 0) return AWARE_E_BADARG;
+    if (kernel_size > kMaxTapKernel || stride > kMaxTapStride || 2 * padding > kernel_size - 1) return AWARE_E_UNSUPPORTED;
+    if (kernel_size == 1 && stride == 1)
+        return aware_detector_create_ex(out, plan, mel_basis, n_mels, n_layers, channels, weights, biases, arch);
+    if (!arch_ok(arch, n_layers)) return AWARE_E_BADARG;
+    return detector_create(out, plan, mel_basis, n_mels, n_layers, channels, weights, biases, arch, kernel_size, stride, padding);
+}
+extern "C" int aware_detector_conv(const aware_detector* d, int* kernel_size, int* stride, int* padding) {
+    if (!d) return AWARE_E_BADARG;
+    if (kernel_size) *kernel_size = d->tk;
+    if (stride) *stride = d->ts;
+    if (padding) *padding = d->tp;
+    return AWARE_OK;
+}
+// The row rule and the two data-movement kernels of the temporal convolutions on their own (conv_taps.hpp), for callers that
+// check them: x / dx [total pooled rows][channels], u / du [total pooled rows][kernel_size * channels], channels % 4 == 0
+extern "C" int aware_conv_rows(int rows, int blocks, int kernel_size, int stride, int padding) {
+    if (rows < 0 || blocks < 0 || kernel_size < 1 || stride < 1 || padding < 0) return AWARE_E_BADARG;
+    return conv_rows(rows, blocks, kernel_size, stride, padding);
+}
+static int conv_taps_args(const aware_batch* b, const void* in, const void* out, int channels, int block, int k, int s, int p) {
+    if (!b || !in || !out || channels < 4 || channels % 4 || block < 0 || block >= kMaxLayers) return AWARE_E_BADARG;
+    if (k < 1 || s < 1 || p < 0) return AWARE_E_BADARG;
+    if (k > kMaxTapKernel || s > kMaxTapStride || 2 * p > k - 1) return AWARE_E_UNSUPPORTED;
+    return AWARE_OK;
+}
+extern "C" int aware_conv_unfold(const aware_batch* b, const float* x, float* u, int channels, int block, int kernel_size,
+                                 int stride, int padding, void* stream) {
+    const int rc = conv_taps_args(b, x, u, channels, block, kernel_size, stride, padding);
+    if (rc) return rc;
+    launch_conv_unfold(x, u, b->d_frame_off, b->d_pool_off, channels, b->B, b->max_frames / 2, block, kernel_size, stride, padding,
+                       (hipStream_t)stream);
+    LAUNCHCHK();
+    return AWARE_OK;
+}
+extern "C" int aware_conv_fold(const aware_batch* b, const float* du, float* dx, int channels, int block, int kernel_size,
+                               int stride, int padding, void* stream) {
+    const int rc = conv_taps_args(b, du, dx, channels, block, kernel_size, stride, padding);
+    if (rc) return rc;
+    launch_conv_fold(du, dx, b->d_frame_off, b->d_pool_off, channels, b->B, b->max_frames / 2, block, kernel_size, stride, padding,
+                     (hipStream_t)stream);
+    LAUNCHCHK();
+    return AWARE_OK;
 }
 extern "C" int aware_detector_is_card(const aware_detector* d) { return d ? (d->card_arch ? 1 : 0) : AWARE_E_BADARG; }
 // EXTENSION (detector training, BASELINE north_star; the reference never changes the weights): replace the parameters of a
@@ -960,6 +1037,9 @@ struct DetBufs {
     // dL/dZ_l in gmax[l & 1]
     std::vector<float*> amax;
     float* gmax[2];
+    // a detector of temporal convolutions: the unfolded rows of the block at hand [NP][tk max_cin], forward (U) and backward
+    // (dL/dU) alike -- the weights are frozen, so U is not kept; else null
+    float* unf = nullptr;
 };
 constexpr int kTailSplit = 4;
 // slabs of split-K partials of the last conv: 4 from the split-K GEMM, Cin/128 from the fused forward epilogue
@@ -989,6 +1069,7 @@ static void carve_det(Carver& c, const aware_batch* b, const aware_detector* d, 
     for (int l = 0; l <= d->n_layers; ++l) o.amax[l] = c.take<float>((size_t)b->B * 64);
     o.gmax[0] = c.take<float>((size_t)b->B * 64);
     o.gmax[1] = c.take<float>((size_t)b->B * 64);
+    o.unf = d->taps ? c.take<float>((size_t)b->NP * d->tk * d->max_cin) : nullptr;
 }
 
 // number of 32-row groups per clip when the fused clip-aligned GEMM applies (uniform batch,
@@ -1217,13 +1298,20 @@ static int det_forward(const aware_detector* d, const aware_batch* b, const DetP
             // conv + bias, then the block's norm and activation (a variant's pre-activation kept in the stash).  The card's
             // InstanceNorm + LeakyReLU keeps its own kernels: norm_act_bwd_kernel<0, 1, 80> holds the clip in AGPRs too and
             // runs one wave per SIMD where in_lrelu_bwd_reg_kernel<80> runs two
-            gemm_plain(p.pipe, x, ci, d->w[l], ci, d->wpk[l], d->bias[l], o.act[l], co, b->NP, co, ci, st);
+            // temporal convolutions: the same GEMM on the unfolded rows (K = tk ci), the norm over the block's own rows
+            if (d->taps) {
+                launch_conv_unfold(x, o.unf, b->d_frame_off, b->d_pool_off, ci, b->B, b->max_frames / 2, l, d->tk, d->ts, d->tp, st);
+                LAUNCHCHK(); PROF(K_MISC);
+                gemm_plain(p.pipe, o.unf, d->tk * ci, d->w[l], d->tk * ci, d->wpk[l], d->bias[l], o.act[l], co, b->NP, co,
+                           d->tk * ci, st);
+            } else
+                gemm_plain(p.pipe, x, ci, d->w[l], ci, d->wpk[l], d->bias[l], o.act[l], co, b->NP, co, ci, st);
             LAUNCHCHK(); PROF(K_GEMM);
             if (d->card_arch)
                 launch_in_lrelu_fwd(o.act[l], b->d_frame_off, b->d_pool_off, o.rstd[l], co, b->B, b->max_frames / 2, st);
             else
                 launch_norm_act_fwd(d->norm, d->act, o.act[l], b->d_frame_off, b->d_pool_off, o.rstd[l], d->nscale[l],
-                                    d->nshift[l], o.stash[l], co, b->B, b->max_frames / 2, st);
+                                    d->nshift[l], o.stash[l], co, b->B, b->max_frames / 2, st, det_rows(d, l + 1));
             LAUNCHCHK(); PROF(K_INLRELU);
         }
         x = o.act[l];
@@ -1240,10 +1328,10 @@ static void readout_forward(const aware_detector* d, const aware_batch* b, const
                     nullptr, nullptr, nullptr, nullptr, nullptr, 0, d->nbits, b->B, b->max_frames / 2, st, nullptr, 0, C);
     else if (p.readout == Readout::Wide)
         launch_readout_wide(o.act[nl - 1], C, b->d_frame_off, b->d_pool_off, nullptr, nullptr, values, nullptr, nullptr, nullptr,
-                            nullptr, nullptr, nullptr, 0, d->nbits, b->B, st, nullptr, d->final_act, false);
+                            nullptr, nullptr, nullptr, 0, d->nbits, b->B, st, nullptr, d->final_act, false, det_rows(d, nl));
     else
         launch_head(o.act[nl - 1], b->d_frame_off, b->d_pool_off, nullptr, values, nullptr, nullptr, nullptr, nullptr, nullptr, 0,
-                    d->nbits, b->B, st, nullptr, d->final_act, C);
+                    d->nbits, b->B, st, nullptr, d->final_act, C, det_rows(d, nl));
 }
 
 // the general route's band kernels (loop_any.hip) for a plan and its batch
@@ -1282,6 +1370,7 @@ extern "C" size_t aware_detect_workspace_bytes(const aware_batch* b, const aware
 extern "C" int aware_detector_forward(const aware_detector* d, const aware_batch* b, const float* mag, float* values,
                                       void* workspace, size_t workspace_bytes, void* stream) {
     if (!d || !b || b->general || !mag || !values || !workspace) return AWARE_E_BADARG;
+    if (!det_clips_ok(d, b)) return AWARE_E_BADARG;           // a clip too short for the detector's temporal convolutions
     hipStream_t st = (hipStream_t)stream;
     Carver c(workspace, workspace_bytes);
     DetBufs o;
@@ -1303,6 +1392,7 @@ extern "C" int aware_detect(const aware_plan* plan, const aware_detector* d, con
     if (plan->general ? !gen_loop_matches(plan, b, d) : (b->general || d->general)) return AWARE_E_BADARG;
     // the magnitude rows are carved at the detector's stride and written at the plan's: one band layout
     if (d->band_lo != plan->dev.band_lo || d->nband != plan->dev.nband || d->stride != plan->dev.stride) return AWARE_E_BADARG;
+    if (!det_clips_ok(d, b)) return AWARE_E_BADARG;           // a clip too short for the detector's temporal convolutions
     hipStream_t st = (hipStream_t)stream;
     Carver c(workspace, workspace_bytes);
     DetBufs o;
@@ -1373,11 +1463,11 @@ static int det_forward_backward(const aware_detector* d, const aware_batch* b, c
     case Readout::Wide:
         launch_readout_wide(db.act[nl - 1], d->ch[nl], b->d_frame_off, b->d_pool_off, db.rstd[nl - 1], G.target, db.pred, G.loss,
                             G.best_loss, G.improved, dA, gmax(nl - 1, p.g_max[nl - 1]), G.step, G.loss_kind, d->nbits, b->B, st,
-                            G.loss_add, d->final_act, p.dz[nl - 1]);
+                            G.loss_add, d->final_act, p.dz[nl - 1], det_rows(d, nl));
         break;
     default:
         launch_head(db.act[nl - 1], b->d_frame_off, b->d_pool_off, G.target, db.pred, G.loss, G.best_loss,
-                    G.improved, dA, G.step, G.loss_kind, d->nbits, b->B, st, G.loss_add, d->final_act, d->ch[nl]);
+                    G.improved, dA, G.step, G.loss_kind, d->nbits, b->B, st, G.loss_add, d->final_act, d->ch[nl], det_rows(d, nl));
     }
     LAUNCHCHK(); PROF(K_HEAD);
     for (int l = p.top; l >= 0; --l) {
@@ -1387,7 +1477,7 @@ static int det_forward_backward(const aware_detector* d, const aware_batch* b, c
                 launch_in_lrelu_bwd(dA, db.act[l], b->d_frame_off, b->d_pool_off, db.rstd[l], co, b->B, b->max_frames / 2, st);
             else
                 launch_norm_act_bwd(d->norm, d->act, dA, db.act[l], db.stash[l], b->d_frame_off, b->d_pool_off, db.rstd[l],
-                                    d->nscale[l], co, b->B, b->max_frames / 2, st);
+                                    d->nscale[l], co, b->B, b->max_frames / 2, st, det_rows(d, l + 1));
             LAUNCHCHK(); PROF(K_INLRELU);
         }
         // dA = dL/dZ_l [NP][co] (zero in padding rows), X = input of the block [NP][ci]:  dW = dZ^T X as an NT GEMM over
@@ -1454,8 +1544,16 @@ static int det_forward_backward(const aware_detector* d, const aware_batch* b, c
             LAUNCHCHK(); PROF(K_MELNORM);
             break;
         default:
-            gemm_plain(p.pipe, dA, co, d->wT[l], co, d->wTpk[l], nullptr, dB, ci, b->NP, ci, co, st);
-            LAUNCHCHK(); PROF(K_GEMM);
+            // temporal convolutions: the GEMM to dL/dU [NP][tk ci], then the fold to dL/dX (the adjoint of the unfold)
+            if (d->taps) {
+                gemm_plain(p.pipe, dA, co, d->wT[l], co, d->wTpk[l], nullptr, db.unf, d->tk * ci, b->NP, d->tk * ci, co, st);
+                LAUNCHCHK(); PROF(K_GEMM);
+                launch_conv_fold(db.unf, dB, b->d_frame_off, b->d_pool_off, ci, b->B, b->max_frames / 2, l, d->tk, d->ts, d->tp, st);
+                LAUNCHCHK(); PROF(K_MISC);
+            } else {
+                gemm_plain(p.pipe, dA, co, d->wT[l], co, d->wTpk[l], nullptr, dB, ci, b->NP, ci, co, st);
+                LAUNCHCHK(); PROF(K_GEMM);
+            }
         }
         float* t = dA; dA = dB; dB = t;
     }
@@ -1505,6 +1603,7 @@ extern "C" int aware_detector_backward(const aware_detector* d, const aware_batc
                                        const float* grad_values, float* values, float* grad_mag, void* workspace,
                                        size_t workspace_bytes, void* stream) {
     if (!d || !b || b->general || !mag || !grad_values || !grad_mag || !workspace) return AWARE_E_BADARG;
+    if (!det_clips_ok(d, b)) return AWARE_E_BADARG;           // a clip too short for the detector's temporal convolutions
     hipStream_t st = (hipStream_t)stream;
     Carver c(workspace, workspace_bytes);
     DetBufs o;
@@ -1786,6 +1885,7 @@ extern "C" int aware_embed_create(aware_embed** out, const aware_plan* plan, con
     if (cfg->dsp_path < 0 || cfg->dsp_path > 1 || cfg->conv_tile < 0 || cfg->conv_tile > 2) return AWARE_E_BADARG;
     // the detector's mel operands have the layout of the plan it was created for
     if (det->band_lo != plan->dev.band_lo || det->nband != plan->dev.nband || det->stride != plan->dev.stride) return AWARE_E_BADARG;
+    if (!det_clips_ok(det, b)) return AWARE_E_BADARG;         // a clip too short for the detector's temporal convolutions
     // the L1 term lives in the streaming DSP kernels only
     const bool l1 = cfg->loss == AWARE_LOSS_PUSH_L1;
     if (l1 && (plan->general || cfg->dsp_path != 0 || !stream_supported(plan->dev))) return AWARE_E_UNSUPPORTED;
@@ -1836,6 +1936,14 @@ extern "C" int aware_embed_create(aware_embed** out, const aware_plan* plan, con
         if (f32_shape(b->NF, S, Mp, Mp)) gemm_autotune(e->db.xm, Mp, det->melB, Mp, e->gmag, S, b->NF, S, Mp, st);
         for (int l = 0; l < det->n_layers; ++l) {
             const int ci = det->ch[l], co = det->ch[l + 1];
+            if (det->taps) {
+                // temporal convolutions: the two GEMMs run on the unfolded rows, K and N = tk ci (the scratch is their operand)
+                const int kc = det->tk * ci;
+                if (l == 0) HIPCHK(hipMemsetAsync(e->db.unf, 0, (size_t)b->NP * det->tk * det->max_cin * sizeof(float), st));
+                if (f32_shape(b->NP, co, kc, kc)) gemm_autotune(e->db.unf, kc, det->w[l], kc, e->d2, co, b->NP, co, kc, st);
+                if (f32_shape(b->NP, kc, co, co)) gemm_autotune(e->d1, co, det->wT[l], co, e->db.unf, kc, b->NP, kc, co, st);
+                continue;
+            }
             if (f32_shape(b->NP, co, ci, ci)) gemm_autotune(e->d1, ci, det->w[l], ci, e->d2, co, b->NP, co, ci, st);
             if (f32_shape(b->NP, ci, co, co)) gemm_autotune(e->d1, co, det->wT[l], co, e->d2, ci, b->NP, ci, co, st);
         }

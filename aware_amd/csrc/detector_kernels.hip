@@ -1005,10 +1005,10 @@ template <int NORM, int ACT, int R>
 __global__ __launch_bounds__(256) void norm_act_fwd_kernel(float* __restrict__ z, const int* __restrict__ frame_off,
                                                            const int* __restrict__ pool_off, float* __restrict__ rstd,
                                                            const float* __restrict__ scale, const float* __restrict__ shift,
-                                                           float* __restrict__ stash, int C) {
+                                                           float* __restrict__ stash, int C, TapRows rows) {
     __shared__ float s[4][64];
     const int b = blockIdx.y, c0 = blockIdx.x * 64;
-    const int r0 = pool_off[b], Tp = (frame_off[b + 1] - frame_off[b]) / 2;   // rows are 32-aligned per clip
+    const int r0 = pool_off[b], Tp = rows.of((frame_off[b + 1] - frame_off[b]) / 2);   // rows are 32-aligned per clip
     const int cl = threadIdx.x & 63, g = threadIdx.x >> 6, c = c0 + cl;
     if (Tp <= 0) return;
     const bool ok = c < C;
@@ -1068,10 +1068,10 @@ template <int NORM, int ACT, int R>
 __global__ __launch_bounds__(256) void norm_act_bwd_kernel(float* __restrict__ dA, const float* __restrict__ A,
                                                            const float* __restrict__ stash, const int* __restrict__ frame_off,
                                                            const int* __restrict__ pool_off, const float* __restrict__ rstd,
-                                                           const float* __restrict__ scale, int C) {
+                                                           const float* __restrict__ scale, int C, TapRows rows) {
     __shared__ float s1[4][64], s2[4][64];
     const int b = blockIdx.y, c0 = blockIdx.x * 64;
-    const int r0 = pool_off[b], Tp = (frame_off[b + 1] - frame_off[b]) / 2;   // rows are 32-aligned per clip
+    const int r0 = pool_off[b], Tp = rows.of((frame_off[b + 1] - frame_off[b]) / 2);   // rows are 32-aligned per clip
     const int cl = threadIdx.x & 63, g = threadIdx.x >> 6, c = c0 + cl;
     if (Tp <= 0) return;
     const bool ok = c < C;
@@ -1139,37 +1139,37 @@ __global__ __launch_bounds__(256) void norm_act_bwd_kernel(float* __restrict__ d
 
 template <int NORM, int ACT>
 static void norm_act_launch(bool fwd, float* z, const float* A, const int* frame_off, const int* pool_off, float* rstd,
-                            const float* scale, const float* shift, float* stash, int C, int B, int max_pooled, hipStream_t st) {
+                            const float* scale, const float* shift, float* stash, int C, int B, int max_pooled, hipStream_t st, TapRows rows) {
     const dim3 grid((C + 63) / 64, B), block(256);
     if (NORM == kNormInstance && max_pooled <= 128) {
-        if (fwd) hipLaunchKernelGGL((norm_act_fwd_kernel<NORM, ACT, 32>), grid, block, 0, st, z, frame_off, pool_off, rstd, scale, shift, stash, C);
-        else hipLaunchKernelGGL((norm_act_bwd_kernel<NORM, ACT, 32>), grid, block, 0, st, z, A, stash, frame_off, pool_off, rstd, scale, C);
+        if (fwd) hipLaunchKernelGGL((norm_act_fwd_kernel<NORM, ACT, 32>), grid, block, 0, st, z, frame_off, pool_off, rstd, scale, shift, stash, C, rows);
+        else hipLaunchKernelGGL((norm_act_bwd_kernel<NORM, ACT, 32>), grid, block, 0, st, z, A, stash, frame_off, pool_off, rstd, scale, C, rows);
     } else if (NORM == kNormInstance && max_pooled <= 320) {
-        if (fwd) hipLaunchKernelGGL((norm_act_fwd_kernel<NORM, ACT, 80>), grid, block, 0, st, z, frame_off, pool_off, rstd, scale, shift, stash, C);
-        else hipLaunchKernelGGL((norm_act_bwd_kernel<NORM, ACT, 80>), grid, block, 0, st, z, A, stash, frame_off, pool_off, rstd, scale, C);
+        if (fwd) hipLaunchKernelGGL((norm_act_fwd_kernel<NORM, ACT, 80>), grid, block, 0, st, z, frame_off, pool_off, rstd, scale, shift, stash, C, rows);
+        else hipLaunchKernelGGL((norm_act_bwd_kernel<NORM, ACT, 80>), grid, block, 0, st, z, A, stash, frame_off, pool_off, rstd, scale, C, rows);
     } else {
-        if (fwd) hipLaunchKernelGGL((norm_act_fwd_kernel<NORM, ACT, 0>), grid, block, 0, st, z, frame_off, pool_off, rstd, scale, shift, stash, C);
-        else hipLaunchKernelGGL((norm_act_bwd_kernel<NORM, ACT, 0>), grid, block, 0, st, z, A, stash, frame_off, pool_off, rstd, scale, C);
+        if (fwd) hipLaunchKernelGGL((norm_act_fwd_kernel<NORM, ACT, 0>), grid, block, 0, st, z, frame_off, pool_off, rstd, scale, shift, stash, C, rows);
+        else hipLaunchKernelGGL((norm_act_bwd_kernel<NORM, ACT, 0>), grid, block, 0, st, z, A, stash, frame_off, pool_off, rstd, scale, C, rows);
     }
 }
 template <int NORM>
 static void norm_act_dispatch(int act, bool fwd, float* z, const float* A, const int* frame_off, const int* pool_off, float* rstd,
-                              const float* scale, const float* shift, float* stash, int C, int B, int max_pooled, hipStream_t st) {
+                              const float* scale, const float* shift, float* stash, int C, int B, int max_pooled, hipStream_t st, TapRows rows) {
     switch (act) {
-        case kActRelu: norm_act_launch<NORM, kActRelu>(fwd, z, A, frame_off, pool_off, rstd, scale, shift, stash, C, B, max_pooled, st); break;
-        case kActLRelu: norm_act_launch<NORM, kActLRelu>(fwd, z, A, frame_off, pool_off, rstd, scale, shift, stash, C, B, max_pooled, st); break;
-        case kActGelu: norm_act_launch<NORM, kActGelu>(fwd, z, A, frame_off, pool_off, rstd, scale, shift, stash, C, B, max_pooled, st); break;
-        default: norm_act_launch<NORM, kActSwish>(fwd, z, A, frame_off, pool_off, rstd, scale, shift, stash, C, B, max_pooled, st); break;
+        case kActRelu: norm_act_launch<NORM, kActRelu>(fwd, z, A, frame_off, pool_off, rstd, scale, shift, stash, C, B, max_pooled, st, rows); break;
+        case kActLRelu: norm_act_launch<NORM, kActLRelu>(fwd, z, A, frame_off, pool_off, rstd, scale, shift, stash, C, B, max_pooled, st, rows); break;
+        case kActGelu: norm_act_launch<NORM, kActGelu>(fwd, z, A, frame_off, pool_off, rstd, scale, shift, stash, C, B, max_pooled, st, rows); break;
+        default: norm_act_launch<NORM, kActSwish>(fwd, z, A, frame_off, pool_off, rstd, scale, shift, stash, C, B, max_pooled, st, rows); break;
     }
 }
 static void norm_act(int norm, int act, bool fwd, float* z, const float* A, const int* frame_off, const int* pool_off, float* rstd,
-                     const float* scale, const float* shift, float* stash, int C, int B, int max_pooled, hipStream_t st) {
+                     const float* scale, const float* shift, float* stash, int C, int B, int max_pooled, hipStream_t st, TapRows rows) {
     if (norm == kNormInstance)
-        norm_act_dispatch<kNormInstance>(act, fwd, z, A, frame_off, pool_off, rstd, scale, shift, stash, C, B, max_pooled, st);
+        norm_act_dispatch<kNormInstance>(act, fwd, z, A, frame_off, pool_off, rstd, scale, shift, stash, C, B, max_pooled, st, rows);
     else if (norm == kNormAffine)
-        norm_act_dispatch<kNormAffine>(act, fwd, z, A, frame_off, pool_off, rstd, scale, shift, stash, C, B, max_pooled, st);
+        norm_act_dispatch<kNormAffine>(act, fwd, z, A, frame_off, pool_off, rstd, scale, shift, stash, C, B, max_pooled, st, rows);
     else
-        norm_act_dispatch<kNormNone>(act, fwd, z, A, frame_off, pool_off, rstd, scale, shift, stash, C, B, max_pooled, st);
+        norm_act_dispatch<kNormNone>(act, fwd, z, A, frame_off, pool_off, rstd, scale, shift, stash, C, B, max_pooled, st, rows);
 }
 
 // ---------------------------------------------------------------------------------
@@ -1183,12 +1183,13 @@ __global__ __launch_bounds__(256) void head_kernel(const float* __restrict__ a3,
                                                     const float* __restrict__ target, float* __restrict__ pred,
                                                     float* __restrict__ loss_out, float* __restrict__ best_loss,
                                                     int* __restrict__ improved, float* __restrict__ dA3, int* __restrict__ step,
-                                                    int loss_kind, int nbits, const float* __restrict__ loss_add, int C) {
+                                                    int loss_kind, int nbits, const float* __restrict__ loss_add, int C,
+                                                    TapRows rows) {
     // C: channel pitch of a3 / dA3, 2 * nbits or the detector's padded count (channels 2 * nbits .. C-1 are never read out;
     // their dA3 is zero)
     __shared__ float part[4][64], mean[64], dm[64];
     const int b = blockIdx.x, c = threadIdx.x & 63, g = threadIdx.x >> 6;
-    const int r0 = pool_off[b], Tp = (frame_off[b + 1] - frame_off[b]) / 2;   // rows are 32-aligned per clip
+    const int r0 = pool_off[b], Tp = rows.of((frame_off[b + 1] - frame_off[b]) / 2);   // rows are 32-aligned per clip
     float m = 0.f;
     if (c < C)
         for (int t = g; t < Tp; t += 4) m += a3[(size_t)(r0 + t) * C + c];
@@ -1385,13 +1386,13 @@ __global__ __launch_bounds__(256) void readout_wide_kernel(const float* __restri
                                                             float* __restrict__ loss_out, float* __restrict__ best_loss,
                                                             int* __restrict__ improved, float* __restrict__ dout,
                                                             float* __restrict__ gmax, int* __restrict__ step, int loss_kind,
-                                                            int nbits, const float* __restrict__ loss_add) {
+                                                            int nbits, const float* __restrict__ loss_add, TapRows rows) {
     __shared__ float s_a[kWideMaxC], s_l[kWideMaxC], s_lu[kWideMaxC];
     __shared__ float red[4];
     const int b = blockIdx.x, tid = threadIdx.x;
     const int CW = Cp < 256 ? Cp : 256, NG = 256 / CW;
     const int cl = tid % CW, g = tid / CW;
-    const int r0 = pool_off[b], Tp = (frame_off[b + 1] - frame_off[b]) / 2;   // rows are 32-aligned per clip
+    const int r0 = pool_off[b], Tp = rows.of((frame_off[b + 1] - frame_off[b]) / 2);   // rows are 32-aligned per clip
     const int C = 2 * nbits;
     const float invT = 1.0f / (float)Tp;
     float sa[kWideNJ], sl[kWideNJ], slu[kWideNJ];
@@ -1517,11 +1518,12 @@ __global__ __launch_bounds__(256) void readout_wide_kernel(const float* __restri
 
 void launch_readout_wide(const float* A, int Cp, const int* frame_off, const int* pool_off, const float* rstd, const float* target,
                          float* pred, float* loss, float* best_loss, int* improved, float* dout, float* gmax, int* step,
-                         int loss_kind, int nbits, int B, hipStream_t st, const float* loss_add, int final_act, bool card_bwd) {
+                         int loss_kind, int nbits, int B, hipStream_t st, const float* loss_add, int final_act, bool card_bwd,
+                         TapRows rows) {
     const int mode = !target ? 0 : (card_bwd ? 2 : 1);
 #define AW_WIDE(FA, M)                                                                                                       \
     hipLaunchKernelGGL((readout_wide_kernel<FA, M>), dim3(B), dim3(256), 0, st, A, Cp, frame_off, pool_off, rstd, target, pred, \
-                       loss, best_loss, improved, dout, gmax, step, loss_kind, nbits, loss_add)
+                       loss, best_loss, improved, dout, gmax, step, loss_kind, nbits, loss_add, rows)
 #define AW_WIDE_FA(FA) \
     do { if (mode == 0) AW_WIDE(FA, 0); else if (mode == 1) AW_WIDE(FA, 1); else AW_WIDE(FA, 2); } while (0)
     switch (final_act) {
@@ -1849,11 +1851,11 @@ void launch_in_lrelu_bwd(float* dA, const float* A, const int* frame_off, const 
 }
 void launch_head(const float* a3, const int* frame_off, const int* pool_off, const float* target, float* pred, float* loss,
                  float* best_loss, int* improved, float* dA3, int* step, int loss_kind, int nbits, int B,
-                 hipStream_t st, const float* loss_add, int final_act, int C) {
+                 hipStream_t st, const float* loss_add, int final_act, int C, TapRows rows) {
     if (C < 2 * nbits) C = 2 * nbits;
 #define AW_HEAD(FA)                                                                                                         \
     hipLaunchKernelGGL(head_kernel<FA>, dim3(B), dim3(256), 0, st, a3, frame_off, pool_off, target, pred, loss, best_loss, improved, \
-                       dA3, step, loss_kind, nbits, loss_add, C)
+                       dA3, step, loss_kind, nbits, loss_add, C, rows)
     switch (final_act) {
         case kActRelu: AW_HEAD(kActRelu); break;
         case kActLRelu: AW_HEAD(kActLRelu); break;
@@ -1865,13 +1867,13 @@ void launch_head(const float* a3, const int* frame_off, const int* pool_off, con
 #undef AW_HEAD
 }
 void launch_norm_act_fwd(int norm, int act, float* z, const int* frame_off, const int* pool_off, float* rstd, const float* scale,
-                         const float* shift, float* stash, int C, int B, int max_pooled, hipStream_t st) {
-    norm_act(norm, act, true, z, nullptr, frame_off, pool_off, rstd, scale, shift, stash, C, B, max_pooled, st);
+                         const float* shift, float* stash, int C, int B, int max_pooled, hipStream_t st, TapRows rows) {
+    norm_act(norm, act, true, z, nullptr, frame_off, pool_off, rstd, scale, shift, stash, C, B, max_pooled, st, rows);
 }
 void launch_norm_act_bwd(int norm, int act, float* dA, const float* A, const float* stash, const int* frame_off, const int* pool_off,
-                         const float* rstd, const float* scale, int C, int B, int max_pooled, hipStream_t st) {
+                         const float* rstd, const float* scale, int C, int B, int max_pooled, hipStream_t st, TapRows rows) {
     norm_act(norm, act, false, dA, A, frame_off, pool_off, const_cast<float*>(rstd), scale, nullptr, const_cast<float*>(stash), C, B,
-             max_pooled, st);
+             max_pooled, st, rows);
 }
 
 }  // namespace aware

@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include "common.hpp"
 #include "loop_limits.hpp"
+#include "conv_taps.hpp"
 
 namespace aware {
 
@@ -221,14 +222,16 @@ AW_HD bool norm_act_needs_stash(int norm, int act) {
 // conv block tail of a variant, in place on z [NP][C]: u = norm(z) (InstanceNorm over time, saves rstd [B][C]; affine
 // u = z * scale[c] + shift[c]; or identity), z = act(u); stash [NP][C] receives u (null: not written)
 void launch_norm_act_fwd(int norm, int act, float* z, const int* frame_off, const int* pool_off, float* rstd, const float* scale,
-                         const float* shift, float* stash, int C, int B, int max_pooled, hipStream_t st);
+                         const float* shift, float* stash, int C, int B, int max_pooled, hipStream_t st, TapRows rows = TapRows());
 // backward of the same, in place on dA: u read from stash, or recovered from the output A (norm_act_needs_stash false)
 void launch_norm_act_bwd(int norm, int act, float* dA, const float* A, const float* stash, const int* frame_off, const int* pool_off,
-                         const float* rstd, const float* scale, int C, int B, int max_pooled, hipStream_t st);
+                         const float* rstd, const float* scale, int C, int B, int max_pooled, hipStream_t st, TapRows rows = TapRows());
+// (rows: the block whose rows the kernel normalises, for a detector of temporal convolutions -- conv_taps.hpp; the default is
+//  the clip's pooled frames, and with it every instantiation computes what it always did)
 // BRH + loss + dL/dA3; also best-loss tracking.  final_act: kActRelu .. kActSigmoid applied to even - odd (the card: tanh)
 void launch_head(const float* a3, const int* frame_off, const int* pool_off, const float* target, float* pred, float* loss,
                  float* best_loss, int* improved, float* dA3, int* step, int loss_kind, int nbits, int B,
-                 hipStream_t st, const float* loss_add = nullptr, int final_act = kActTanh, int C = 0);
+                 hipStream_t st, const float* loss_add = nullptr, int final_act = kActTanh, int C = 0, TapRows rows = TapRows());
 // (C: channel pitch of a3 / dA3; 0 = 2*nbits.  Channels 2*nbits .. C-1 are padding: never read out, dA3 zero)
 void launch_gemm_nt_splitk(const float* A, int lda, const float* Bt, int ldb, float* Cpart, int ldc, int M, int N, int K,
                            int ksplit, hipStream_t st);
@@ -244,7 +247,8 @@ void launch_tail(const float* zpart, int nsplit, size_t slab, const float* bias,
 // block with its InstanceNorm + LeakyReLU backward folded in (rstd of the block) plus gmax [B][64] partial maxima (or null)
 void launch_readout_wide(const float* A, int Cp, const int* frame_off, const int* pool_off, const float* rstd, const float* target,
                          float* pred, float* loss, float* best_loss, int* improved, float* dout, float* gmax, int* step,
-                         int loss_kind, int nbits, int B, hipStream_t st, const float* loss_add, int final_act, bool card_bwd);
+                         int loss_kind, int nbits, int B, hipStream_t st, const float* loss_add, int final_act, bool card_bwd,
+                         TapRows rows = TapRows());
 
 // ---- seam_kernels.hip: element-wise pieces of the differentiable plug-in seam -----------------------------
 void launch_polar_decompose(const void* spec, float* mag, float* phase, size_t n, hipStream_t st);

@@ -71,11 +71,18 @@ class AWAREDetector(BaseDetector):
     def make_batch(self, lengths, sample_rate: int) -> "rt.Batch":
         """The batch geometry of this detector's plan for clips of `lengths` samples (with general_geometry: ValueError
         naming a clip of n_fft/2 samples or fewer)."""
+        self._check_tap_clips(lengths)
         if not self.general_geometry:
             return rt.Batch(list(lengths))
         rt.check_general_clips("AWAREDetector", self.frame_length, self.hop_length, self.win_length, self.window, lengths,
                                embed=False)
         return rt.Batch(list(lengths), plan=self._plan(sample_rate))
+
+    def _check_tap_clips(self, lengths):
+        """A net of temporal convolutions: ValueError naming the first clip that some block leaves without a row."""
+        check = getattr(self.detection_net, "check_clip_frames", None)
+        if check is not None:
+            check("AWAREDetector", [1 + int(n) // self.hop_length for n in lengths])
 
     def _centre(self) -> float:
         """What an undecided read-out value is: 0.5 behind a sigmoid, 0 otherwise."""
@@ -128,6 +135,7 @@ class AWAREDetector(BaseDetector):
         if self.general_geometry:                                 # ValueError naming the clip, before any plan or launch
             rt.check_general_clips("AWAREDetector", self.frame_length, self.hop_length, self.win_length, self.window,
                                    [len(c) for c in clips], embed=False)
+        self._check_tap_clips([len(c) for c in clips])
         four = return_speed or return_shift
         if speed is None and shift is None:
             out = self._detect_sync(clips, sample_rate, n, return_sync or four)

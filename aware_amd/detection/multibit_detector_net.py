@@ -1,5 +1,7 @@
 """AWAREDetectorNet: frozen, seed-initialised detector (mel -> InstanceNorm -> global standardise
--> pool -> 4 x [conv1x1, norm, activation] -> bitwise read-out head with its final activation).
+-> pool -> (num_blocks + 1) x [conv1d, norm, activation] -> bitwise read-out head with its final activation).
+The model card's convolutions are 1x1; with the key temporal_convs every block is Conv1d(kernel_size, stride, padding)
+along the pooled frames (aware_detector_create_conv).
 
 The model card's blocks are InstanceNorm + LeakyReLU with a tanh read-out; the other choices of the
 reference's detection_net_cfg (activation, norm_layer, final_activation; modules/conv1d.py:8-36,
@@ -15,6 +17,7 @@ import numpy as np
 import torch
 
 from ..interfaces import BaseDetectorNet
+from ..runtime import check_tap_clips, conv_rows
 from .mel import mel_filter_bank
 
 DETECTOR_SEED = 328656719      # multibit_detector_net.py:78
@@ -55,6 +58,10 @@ MAX_OUTPUT_LENGTH = 512
 MAX_N_MELS = 512
 MAX_FILTERS = 4096
 MAX_NUM_BLOCKS = 32
+# the temporal convolutions aware_detector_create_conv takes (key temporal_convs): 2 * padding <= kernel_size - 1, so that no
+# block is longer than its input
+MAX_KERNEL_SIZE = 7
+MAX_STRIDE = 4
 
 
 class AWAREDetectorNet(BaseDetectorNet):
@@ -62,20 +69,38 @@ class AWAREDetectorNet(BaseDetectorNet):
                  initial_pool_size: int = 2, initial_pool_stride: int = 2, num_blocks: int = 3,
                  n_filters=(512, 1024, 1024), kernel_size: int = 1, stride: int = 1, padding: int = 0,
                  norm_layer: str = "instance", activation: str = "leaky_relu", output_length: int = 20,
-                 final_activation: str = "tanh"):
+                 final_activation: str = "tanh", temporal_convs: bool = False):
+        """temporal_convs (EXTENSION; `temporal_convs: true` in the card): serve kernel_size 1..7,
+        stride 1..4 and padding with 2 * padding <= kernel_size - 1 in every block.  Off, anything but 1 / 1 / 0 raises
+        NotImplementedError; on with 1 / 1 / 0 the net is the same net on the same kernels."""
         n_filters = list(n_filters)
         assert len(n_filters) == num_blocks, "Number of filters must match number of blocks"
         # the reference's own validation, in its order: the blocks' norm layers (ValueError), then the final activation
         self.norm_layer = norm_layer_name(norm_layer)
         self.activation = block_activation(activation)
         self.final_activation = final_activation_name(final_activation)
+        self.temporal_convs = bool(temporal_convs)
         unsupported = []
-        if (kernel_size, stride, padding) != (1, 1, 0):
-            unsupported.append("kernel_size/stride/padding other than 1/1/0")
+        if (kernel_size, stride, padding) != (1, 1, 0) and not self.temporal_convs:
+            unsupported.append("kernel_size/stride/padding other than 1/1/0 (served with the key temporal_convs: "
+                               "temporal_convs=True, or `temporal_convs: true` in the card)")
         if (initial_pool_size, initial_pool_stride) != (2, 2):
             unsupported.append("initial pool other than (2, 2)")
         if unsupported:
             raise NotImplementedError("the HIP detector implements 1x1 convolutions after a (2, 2) pool only: " + "; ".join(unsupported))
+        if self.temporal_convs:
+            kernel_size, stride, padding = int(kernel_size), int(stride), int(padding)
+            if kernel_size < 1 or stride < 1 or padding < 0:
+                raise ValueError(f"kernel_size / stride / padding = {kernel_size} / {stride} / {padding}: kernel_size and "
+                                 "stride must be positive and padding non-negative")
+            if kernel_size > MAX_KERNEL_SIZE:
+                raise NotImplementedError(f"kernel_size = {kernel_size}: temporal_convs serves kernel_size 1..{MAX_KERNEL_SIZE}")
+            if stride > MAX_STRIDE:
+                raise NotImplementedError(f"stride = {stride}: temporal_convs serves stride 1..{MAX_STRIDE}")
+            if 2 * padding > kernel_size - 1:
+                raise NotImplementedError(f"padding = {padding} with kernel_size = {kernel_size}: temporal_convs serves "
+                                          "2 * padding <= kernel_size - 1 (no block longer than its input)")
+        self.kernel_size, self.stride, self.padding = kernel_size, stride, padding
         if n_mels < 1 or num_blocks < 0 or any(f < 1 for f in n_filters) or output_length < 1:
             raise ValueError(f"detector sizes must be positive: n_mels = {n_mels}, num_blocks = {num_blocks}, "
                              f"n_filters = {n_filters}, output_length = {output_length}")
@@ -98,10 +123,11 @@ class AWAREDetectorNet(BaseDetectorNet):
         # seed draws the same mt19937 stream without reseeding the caller's global RNG.
         gen = torch.Generator().manual_seed(DETECTOR_SEED)
         self.weights, self.biases = [], []
+        # weights[i]: [cout, cin] for 1x1 convolutions, [cout, cin, kernel_size] for a net of temporal convolutions
         for cin, cout in zip(self.channels[:-1], self.channels[1:]):
-            w = torch.empty(cout, cin, 1)
+            w = torch.empty(cout, cin, kernel_size)
             torch.nn.init.xavier_uniform_(w, generator=gen)
-            self.weights.append(w[:, :, 0].contiguous().numpy())
+            self.weights.append((w if self.has_taps else w[:, :, 0]).contiguous().numpy())
             self.biases.append(np.zeros(cout, dtype=np.float32))
         # BatchNorm1d parameters and running statistics of every block (eval mode: both reference entry points call .eval());
         # a fresh net's values.  BatchNorm has no Conv / Linear weight, so the xavier draws above do not depend on the norm
@@ -115,9 +141,24 @@ class AWAREDetectorNet(BaseDetectorNet):
         self.embedding_bands = None
 
     @property
+    def has_taps(self) -> bool:
+        """Whether the blocks are temporal convolutions (anything but kernel_size / stride / padding 1 / 1 / 0)."""
+        return (self.kernel_size, self.stride, self.padding) != (1, 1, 0)
+
+    @property
     def is_card_arch(self) -> bool:
-        """Whether the blocks and the read-out are the model card's (the fused kernels); else the staged route."""
-        return (self.activation, self.norm_layer, self.final_activation) == CARD_ARCH
+        """Whether the blocks and the read-out are the model card's (the fused kernels); else the staged route, which a net
+        of temporal convolutions always takes."""
+        return (self.activation, self.norm_layer, self.final_activation) == CARD_ARCH and not self.has_taps
+
+    def block_rows(self, pooled_rows: int) -> list:
+        """[L_0 .. L_{num_blocks + 1}]: the rows of a clip of L_0 pooled rows behind every block."""
+        return [conv_rows(int(pooled_rows), i, self.kernel_size, self.stride, self.padding) for i in range(len(self.channels))]
+
+    def check_clip_frames(self, who: str, frames):
+        """ValueError naming the first clip (of `frames` STFT frames each) that some block leaves without a row, where
+        torch's conv1d raises too; a net of 1x1 convolutions takes every clip."""
+        check_tap_clips(who, frames, len(self.channels) - 1, (self.kernel_size, self.stride, self.padding))
 
     def architecture(self):
         """The aware_detector_arch of this network: enum values, and for BatchNorm the folded eval-mode map
@@ -158,7 +199,8 @@ class AWAREDetectorNet(BaseDetectorNet):
         """Device copy (aware_detector) bound to a plan; created on first use."""
         from ..runtime import DetectorWeights
         if self._dev is None or self._dev.plan is not plan:
-            self._dev = DetectorWeights(plan, self.mel_basis, self.weights, self.biases, arch=self.architecture())
+            conv = (self.kernel_size, self.stride, self.padding) if self.has_taps else None
+            self._dev = DetectorWeights(plan, self.mel_basis, self.weights, self.biases, arch=self.architecture(), conv=conv)
         return self._dev
 
     def forward(self, stft_magnitude: torch.Tensor) -> torch.Tensor:
@@ -174,7 +216,8 @@ class AWAREDetectorNet(BaseDetectorNet):
         return {"sample_rate": self.sample_rate, "n_fft": self.n_fft, "n_mels": self.n_mels,
                 "num_blocks": self.num_blocks, "output_length": self.output_length,
                 "activation": self.activation, "norm_layer": self.norm_layer,
-                "final_activation": self.final_activation, "total_parameters": total, "trainable_parameters": 0}
+                "final_activation": self.final_activation, "kernel_size": self.kernel_size, "stride": self.stride,
+                "padding": self.padding, "total_parameters": total, "trainable_parameters": 0}
 
 
 def _frames_batch(B, T):

@@ -111,7 +111,7 @@ the loop's new stage.  For clip b (length Ny) at optimiser step s with seed_b:
         L = min(L_lo + ((r[2] * (L_hi - L_lo + 1)) >> 32), Ny), and L = Ny where the entry does not fire;
         start = (r[1] * (Ny - L + 1)) >> 32, so 0 <= start <= Ny - L (excerpt_draw);
         z[i] = x[start + (i mod L)] (excerpt_tile): the excerpt repeated periodically until it fills the clip, which keeps its
-        length.  The detector's convolutions are 1 x 1, so time couples only through the norms' statistics and the read-out's
+        length.  The model card's convolutions are 1 x 1, so time couples only through the norms' statistics and the read-out's
         mean, and the periodic repetition has both as the excerpt alone has them, up to the frames at the seams; zeros
         outside the excerpt would enter those statistics.  Every value is a copy, so host and device agree bit for bit.  The
         backward pass is the exact adjoint in gather form (excerpt_tile_adjoint): gx[i] = sum_m gz[(i - start) + m L] for

@@ -30,7 +30,7 @@ class AWAREEmbedder(BaseEmbedder):
                  num_iterations: int = 400, detection_net_cfg: dict = None, optimizer_cfg: dict = None,
                  scheduler_cfg: dict = None, loss: str = "push", verbose: bool = True, use_graph: bool = True,
                  loop_attacks=None, loop_attack_seed: int = 0, loop_attack_mixture=None, payload_code=None,
-                 general_geometry: bool = False):
+                 general_geometry: bool = False, temporal_convs: bool = False):
         """loop_attacks (EXTENSION, see embedding/loop_attacks.py): a chain of attacks applied inside the optimisation loop,
         e.g. [{"kind": "gaussian_noise", "snr_db": 10.0}, {"kind": "sample_suppression", "seconds": 0.3, "prob": 0.75}];
         clip i of a batch draws with seed loop_attack_seed + i.  None: the reference's loop (clean synthesis only).
@@ -42,7 +42,9 @@ class AWAREEmbedder(BaseEmbedder):
         general_geometry (EXTENSION): embed at any frame_length in runtime.GENERAL_NFFT, any
         hop_length and win_length in 1..frame_length, on the general route (the card geometry included); off: the card
         geometry only, on the card kernels.  With it, loop_attacks, loop_attack_mixture and the loss push_extremes_l1 raise
-        NotImplementedError, and detection_net_cfg.n_fft has to equal frame_length."""
+        NotImplementedError, and detection_net_cfg.n_fft has to equal frame_length.
+        temporal_convs (EXTENSION): handed to the detection net built from detection_net_cfg, where it
+        opens kernel_size / stride / padding other than 1 / 1 / 0 (AWAREDetectorNet); off: 1x1 convolutions only."""
         self.general_geometry = bool(general_geometry)
         rt.require_card_geometry("AWAREEmbedder", frame_length, hop_length, win_length, self.general_geometry, window)
         self.frame_length, self.hop_length, self.window, self.win_length = frame_length, hop_length, window, win_length
@@ -51,7 +53,11 @@ class AWAREEmbedder(BaseEmbedder):
         self.tolerance_db = tolerance_db
         self.num_iterations = num_iterations
         self.pattern_mode = pattern_mode
-        self.detection_net = AWAREDetectorNet(**(detection_net_cfg or {}))
+        self.temporal_convs = bool(temporal_convs)
+        net_cfg = dict(detection_net_cfg or {})
+        if self.temporal_convs:
+            net_cfg["temporal_convs"] = True
+        self.detection_net = AWAREDetectorNet(**net_cfg)
         self.detection_net.embedding_bands = self.embedding_bands
         if self.general_geometry and self.detection_net.n_fft != frame_length:
             # the mel bank is [n_mels, n_fft/2 + 1] and multiplies spectra of frame_length/2 + 1 bins
@@ -104,6 +110,8 @@ class AWAREEmbedder(BaseEmbedder):
         short, NOLA); needs no GPU.  Without the key the card batch checks its clips itself."""
         if self.general_geometry:
             rt.check_general_clips("AWAREEmbedder", self.frame_length, self.hop_length, self.win_length, self.window, lengths)
+        # a net of temporal convolutions: every clip keeps a row through every block (T = 1 + n // hop frames)
+        self.detection_net.check_clip_frames("AWAREEmbedder", [1 + int(n) // self.hop_length for n in lengths])
 
     def make_batch(self, lengths, sample_rate: int) -> "rt.Batch":
         """The batch geometry of this embedder's plan for clips of `lengths` samples."""

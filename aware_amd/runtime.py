@@ -148,6 +148,32 @@ def check_general_clips(who: str, n_fft: int, hop: int, win_length: int, window:
                              f"second STFT needs more than n_fft/2 = {n_fft // 2}")
 
 
+def conv_rows(rows: int, blocks: int, kernel_size: int, stride: int, padding: int) -> int:
+    """Rows left of `rows` pooled rows behind `blocks` blocks of a detector of temporal convolutions: L -> floor((L + 2 p -
+    k) / s) + 1 per block, 0 once a block has no output row (torch's conv1d raises there).  Mirror of conv_rows in
+    csrc/conv_taps.hpp (aware_conv_rows)."""
+    for _ in range(blocks):
+        a = rows + 2 * padding - kernel_size
+        rows = 0 if a < 0 else a // stride + 1
+    return rows
+
+
+def check_tap_clips(who: str, frames, blocks: int, conv):
+    """The clips a detector of `blocks` blocks with conv = (kernel_size, stride, padding) takes, checked on the host before any
+    launch: ValueError naming the first clip (of `frames` STFT frames each) that some block leaves without a row.  The C ABI
+    returns AWARE_E_BADARG for such a batch.  1x1 convolutions take every clip."""
+    k, s, p = conv
+    if (k, s, p) == (1, 1, 0):
+        return
+    for i, t in enumerate(int(x) for x in frames):
+        rows = [conv_rows(t // 2, j, k, s, p) for j in range(blocks + 1)]
+        if rows[-1] < 1:
+            blk = next(j for j in range(1, blocks + 1) if rows[j] < 1)
+            raise ValueError(f"{who}: clip {i} has {rows[0]} pooled rows ({t} frames), and block {blk - 1} of the detector "
+                             f"(kernel_size {k}, stride {s}, padding {p}) leaves 0 rows of its {rows[blk - 1]}; rows per "
+                             f"block: {rows[:blk + 1]}")
+
+
 class Plan:
     """FFT tables + window + embedding band (aware_plan).  The card geometry (1024 / 256 / 1024) gives the card plan of the
     embed / detect loop; any other supported geometry (or general=True) a general plan: stft / istft / stft_bwd / istft_bwd
@@ -400,6 +426,7 @@ class NAdamClamp:
 
 def detector_backward(plan: Plan, det: "DetectorWeights", batch: Batch, mag: torch.Tensor, grad_values: torch.Tensor):
     """(values [B, n_bits], grad_mag [total_frames, plan.band_stride]) = forward and J^T grad_values of the frozen network."""
+    det.check_clips("aware_detector_backward", batch)
     nbytes = plan.lib.aware_detector_backward_workspace_bytes(batch.h, det.h)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=mag.device)
     vals = torch.empty((batch.B, det.n_bits), dtype=torch.float32, device=mag.device)
@@ -469,8 +496,10 @@ def detector_train_gradients(plan: Plan, det: "DetectorWeights", batch: Batch, m
 class DetectorWeights:
     """Device copy of the frozen detector (aware_detector)."""
 
-    def __init__(self, plan: Plan, mel_basis: np.ndarray, weights, biases, arch: dict = None):
-        """arch: AWAREDetectorNet.architecture() (aware_detector_create_ex), or None for the model card's network."""
+    def __init__(self, plan: Plan, mel_basis: np.ndarray, weights, biases, arch: dict = None, conv=None):
+        """arch: AWAREDetectorNet.architecture() (aware_detector_create_ex), or None for the model card's network.
+        conv: (kernel_size, stride, padding) of a net of temporal convolutions, weights [cout, cin, kernel_size] per block
+        (aware_detector_create_conv; needs arch), or None for 1x1 convolutions."""
         require_gpu()
         self.lib = load_library()
         self.plan = plan
@@ -485,6 +514,11 @@ class DetectorWeights:
         wp = (C.c_void_p * nl)(*[w.ctypes.data for w in ws])
         bp = (C.c_void_p * nl)(*[b.ctypes.data for b in bs])
         h = C.c_void_p()
+        self.conv = tuple(int(v) for v in conv) if conv is not None else (1, 1, 0)
+        if conv is not None and arch is None:
+            raise ValueError("DetectorWeights: conv needs arch (aware_detector_create_conv)")
+        if any(w.ndim != (3 if conv is not None else 2) or (conv is not None and w.shape[2] != self.conv[0]) for w in ws):
+            raise ValueError("DetectorWeights: weights are [cout, cin] per block, or [cout, cin, kernel_size] with conv")
         if arch is None:
             rc = self.lib.aware_detector_create(C.byref(h), plan.h, C.c_void_p(mel.ctypes.data), mel.shape[0], nl,
                                                 (C.c_int * (nl + 1))(*chans), wp, bp)
@@ -495,11 +529,20 @@ class DetectorWeights:
                 self._norm = [np.ascontiguousarray(v, dtype=np.float32) for v in list(arch["scale"]) + list(arch["shift"])]
                 a.norm_scale = (C.c_void_p * nl)(*[v.ctypes.data for v in self._norm[:nl]])
                 a.norm_shift = (C.c_void_p * nl)(*[v.ctypes.data for v in self._norm[nl:]])
-            rc = self.lib.aware_detector_create_ex(C.byref(h), plan.h, C.c_void_p(mel.ctypes.data), mel.shape[0], nl,
-                                                   (C.c_int * (nl + 1))(*chans), wp, bp, C.byref(a))
-            check(rc, "aware_detector_create_ex")
+            if conv is not None:
+                rc = self.lib.aware_detector_create_conv(C.byref(h), plan.h, C.c_void_p(mel.ctypes.data), mel.shape[0], nl,
+                                                         (C.c_int * (nl + 1))(*chans), wp, bp, C.byref(a), *self.conv)
+                check(rc, "aware_detector_create_conv")
+            else:
+                rc = self.lib.aware_detector_create_ex(C.byref(h), plan.h, C.c_void_p(mel.ctypes.data), mel.shape[0], nl,
+                                                       (C.c_int * (nl + 1))(*chans), wp, bp, C.byref(a))
+                check(rc, "aware_detector_create_ex")
         self.h = h
         self.is_card = bool(self.lib.aware_detector_is_card(h))
+
+    def check_clips(self, who: str, batch: "Batch"):
+        """check_tap_clips on the batch's clips, in front of every entry point that takes this detector."""
+        check_tap_clips(who, batch.frames, len(self.channels) - 1, self.conv)
 
     def update(self, weights, biases):
         """EXTENSION (detector training): replace the parameters in place (same shapes), aware_detector_update."""
@@ -532,6 +575,7 @@ class DetectorWeights:
 
 def detect(plan: Plan, det: DetectorWeights, batch: Batch, audio: torch.Tensor) -> torch.Tensor:
     """AWAREDetector.detect for a ragged batch -> [B, n_bits] raw values (device)."""
+    det.check_clips("aware_detect", batch)
     nbytes = plan.lib.aware_detect_workspace_bytes(batch.h, det.h)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=audio.device)
     out = torch.empty((batch.B, det.n_bits), dtype=torch.float32, device=audio.device)
@@ -540,6 +584,7 @@ def detect(plan: Plan, det: DetectorWeights, batch: Batch, audio: torch.Tensor) 
 
 
 def detector_forward(plan: Plan, det: DetectorWeights, batch: Batch, mag: torch.Tensor) -> torch.Tensor:
+    det.check_clips("aware_detector_forward", batch)
     nbytes = plan.lib.aware_detect_workspace_bytes(batch.h, det.h)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=mag.device)
     out = torch.empty((batch.B, det.n_bits), dtype=torch.float32, device=mag.device)
@@ -588,6 +633,7 @@ class EmbedSession:
         (8 waves x 16 columns, 128-column slabs) or "wide" (4 waves x 64 columns, 256-column slabs, wherever it can run; the
         library refuses a session in which no launch can take it).  The forms give the same bits; conv_tiles() reports them."""
         self.lib = load_library()
+        det.check_clips("aware_embed_create", batch)
         self.plan, self.det, self.batch = plan, det, batch
         if loss not in LOSS_KINDS:
             raise ValueError(f"Unknown loss type: {loss}. Available on the HIP path: {list(LOSS_KINDS)}")

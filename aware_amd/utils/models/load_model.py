@@ -25,7 +25,9 @@ _EMBEDDER = {"pattern_mode": ("pattern_mode", "bits2bipolar"), "tolerance_db": (
              # EXTENSION: one of several chains drawn per clip and step; absent = none, and not beside loop_attacks
              "loop_attack_mixture": ("loop_attack_mixture", None),
              # EXTENSION (utils/watermark/fec.py): the channel code of service.embed_message / detect_message; absent = none
-             "payload_code": ("payload_code", None)}
+             "payload_code": ("payload_code", None),
+             # EXTENSION: kernel_size / stride / padding of detection_net_cfg; absent = 1x1 convolutions only
+             "temporal_convs": ("temporal_convs", False)}
 _DETECTOR = {"threshold": ("threshold", 0.0), "pattern_mode": ("pattern_mode", "bipolar"),
              # EXTENSION (detection/sync.py): offset search in detection; absent = off
              "sync_search": ("sync_search", 0),

@@ -263,6 +263,36 @@ int aware_detector_create_ex(aware_detector** out, const aware_plan* plan, const
 /* 1 when the detector has the model card's architecture (fused kernels), 0 for a variant (staged route) */
 int aware_detector_is_card(const aware_detector* det);
 
+/* Temporal convolutions (kernel_size, stride and padding of detection_net_cfg; modules/conv1d.py; added without a version
+ * step, so a caller detects them by symbol): every one of the n_layers blocks is Conv1d(channels[l], channels[l+1],
+ * kernel_size, stride, padding) -> norm -> activation along the pooled frames.  A clip of L_0 = floor(frames / 2) pooled rows
+ * leaves block l with L_{l+1} = floor((L_l + 2 padding - kernel_size) / stride) + 1 rows; InstanceNorm runs over the block's
+ * rows and the read-out mean over the last block's.  weights[l]: host [channels[l+1]][channels[l]][kernel_size] (torch's
+ * Conv1d layout).  Served: kernel_size 1..7, stride 1..4, 2 padding <= kernel_size - 1 (no block is then longer than its
+ * input); outside that AWARE_E_UNSUPPORTED, non-positive sizes AWARE_E_BADARG.  1 / 1 / 0 is aware_detector_create_ex.
+ * Every other detector made here runs the staged route in every block whatever its arch is: unfold, plain GEMM with K =
+ * kernel_size * channels[l], the norm / activation kernel, the read-out kernel; aware_detector_is_card is 0, the training
+ * extension returns AWARE_E_UNSUPPORTED, and the *_workspace_bytes functions count one scratch of total pooled rows x
+ * kernel_size x the widest block input.  A batch with a clip that some block leaves without a row (torch raises there) is
+ * refused with AWARE_E_BADARG by aware_detect, aware_detector_forward / _backward and aware_embed_create. */
+int aware_detector_create_conv(aware_detector** out, const aware_plan* plan, const float* mel_basis, int n_mels,
+                               int n_layers, const int* channels, const float* const* weights,
+                               const float* const* biases, const aware_detector_arch* arch, int kernel_size, int stride,
+                               int padding);
+/* the kernel_size, stride and padding of a detector (1 / 1 / 0 for one of 1x1 convolutions); any pointer may be NULL */
+int aware_detector_conv(const aware_detector* det, int* kernel_size, int* stride, int* padding);
+/* rows left of `rows` pooled rows behind `blocks` blocks (0 once a block has no output row) */
+int aware_conv_rows(int rows, int blocks, int kernel_size, int stride, int padding);
+/* The two data-movement kernels of such a block on their own.  x / dx: dev f32 [total pooled rows][channels], u / du: dev f32
+ * [total pooled rows][kernel_size * channels], channels % 4 == 0; clip b's rows start at its 32-aligned pooled offset.
+ * unfold (block's input -> GEMM operand): u[r0 + t][j * channels + c] = x[r0 + t * stride - padding + j][c] inside the
+ * clip's L_block rows, else 0, for t < L_{block+1}; the rows up to the clip's 32-row boundary are written as zeros.  fold:
+ * its adjoint, dx[r0 + q][c] = the sum over j ascending of du[r0 + t][j * channels + c] with t * stride - padding + j = q. */
+int aware_conv_unfold(const aware_batch* batch, const float* x, float* u, int channels, int block, int kernel_size,
+                      int stride, int padding, void* stream);
+int aware_conv_fold(const aware_batch* batch, const float* du, float* dx, int channels, int block, int kernel_size,
+                    int stride, int padding, void* stream);
+
 /* AWAREDetector.detect (detection/multibit_detector.py:28-42), batched: normalise, STFT, |.|,
  * zero the out-of-band bins, network forward.  values: dev f32 [B][n_bits].
  * workspace: dev, >= aware_detect_workspace_bytes(). */
