@@ -54,7 +54,7 @@ template <int MODE, bool FULLOUT, bool POLAR = false>
 __global__ __launch_bounds__(kThreads) void analysis_kernel(AnalysisArgs a) {
     static_assert(!POLAR || (MODE == AN_NORM && !FULLOUT), "the exact decomposition stores magnitudes and phasors");
     __shared__ float chunk[kChunk];
-    __shared__ cf scratch[4][kFftScratch];
+    __shared__ alignas(8) cf scratch[4][kFftScratch];
     __shared__ unsigned long long red[4];
     __shared__ double dred[4];
 
@@ -277,7 +277,7 @@ __global__ __launch_bounds__(kThreads) void analysis_kernel(AnalysisArgs a) {
 template <int MODE, int INP>
 __global__ __launch_bounds__(kThreads) void synth_kernel(SynthArgs a) {
     __shared__ float ola[kSynthChunk];
-    __shared__ cf scratch[4][kFftScratch];
+    __shared__ alignas(8) cf scratch[4][kFftScratch];
     __shared__ unsigned long long red[4];
     __shared__ double dred[4];
 
@@ -307,8 +307,8 @@ __global__ __launch_bounds__(kThreads) void synth_kernel(SynthArgs a) {
     if (MODE == SY_ADJ && a.pmax_in) cn = clip_norm_from_partials(a.pmax_in + (size_t)b * a.pstride, a.pcount[b], red);
 
     // twiddles live in LDS in this kernel (28 VGPRs less per lane -> one more wave per SIMD)
-    __shared__ cf tw1s[512];
-    __shared__ cf tw2s[64];
+    __shared__ alignas(8) cf tw1s[512];
+    __shared__ alignas(8) cf tw2s[64];
     fft_fill_tables(tid, kThreads, a.plan.tw512, tw1s, tw2s);
     for (int i = tid; i < kSynthChunk; i += kThreads) ola[i] = 0.f;
     __syncthreads();

@@ -32,6 +32,7 @@
 // 512 in an extra slot r = 8 of lane 0: 9 bins per lane.  DC and Nyquist are real for a real signal; the inverse transform
 // ignores their imaginary parts and enters them once where an interior bin enters twice (torch's C2R), which the wide
 // synthesis and both adjoints restate.
+#define AWARE_LDS_SINGLE_READS 1        // fft512.hpp, lds_cf: every 8-byte LDS read of this file is one ds_read_b64
 #include "common.hpp"
 #include "dsp_args.hpp"
 #include "kernels.h"
@@ -40,6 +41,12 @@ namespace aware {
 
 constexpr int kSW = kStreamWaves;      // waves per workgroup (they share only the read-only tables)
 constexpr int kSThreads = 64 * kSW;
+
+// a float2 table entry as one ds_read_b64 (lds_cf, fft512.hpp)
+__device__ __forceinline__ float2 lds_f2(const float2* p) {
+    const cf t = lds_cf(reinterpret_cast<const cf*>(p));
+    return make_float2(t.x, t.y);
+}
 
 // per-clip normaliser state from the per-run partial maxima, reduced by ONE wave (no barrier)
 __device__ __forceinline__ ClipNorm clip_norm_wave(const unsigned long long* part, int nseg, int lane) {
@@ -92,10 +99,10 @@ __global__ __launch_bounds__(kSThreads, MODE == AN_ADJ ? (WIDE ? 2 : 3) : 4) voi
     constexpr int S = WIDE ? kFSWide : kFS;        // floats per band row
     constexpr int NS = WIDE ? 9 : 5;               // bin slots per lane
     __shared__ float magrow_s[MELF ? kSW : 1][MELF ? kFS : 1];
-    __shared__ cf tw1s[512];
-    __shared__ cf tw2s[64];
+    __shared__ alignas(8) cf tw1s[512];
+    __shared__ alignas(8) cf tw2s[64];
     __shared__ float2 wins[512];
-    __shared__ cf scratch[kSW][kFftScratch];
+    __shared__ alignas(8) cf scratch[kSW][kFftScratch];
     const int tid = threadIdx.x;
     fft_fill_tables(tid, kSThreads, a.plan.tw512, tw1s, tw2s);
     for (int i = tid; i < 512; i += kSThreads) wins[i] = make_float2(a.plan.window[2 * i], a.plan.window[2 * i + 1]);
@@ -248,7 +255,7 @@ __global__ __launch_bounds__(kSThreads, MODE == AN_ADJ ? (WIDE ? 2 : 3) : 4) voi
         cf v[8];
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
-            const float2 w = wins[lane + 64 * r];
+            const float2 w = lds_f2(wins + lane + 64 * r);
             v[r] = mk(raw[r].x * w.x, raw[r].y * w.y);
         }
         // the next frame shares three quarters with this one: roll, and request its new quarter now
@@ -360,11 +367,11 @@ __global__ __launch_bounds__(kSThreads, WIDE ? 3 : 4) void synth_stream_kernel(S
     constexpr int NS = WIDE ? 9 : 8;               // input slots per lane
     __shared__ float2 melw_s[MELG ? kFS : 1];
     __shared__ float melrow_s[MELG ? kSW : 1][MELG ? 128 : 1];
-    __shared__ cf tw1s[512];
-    __shared__ cf tw2s[64];
+    __shared__ alignas(8) cf tw1s[512];
+    __shared__ alignas(8) cf tw2s[64];
     __shared__ float2 wins[512];             // window * irfft scale, as sample pairs
-    __shared__ cf mcs[512];                  // irfft merge constants of bin k (narrow: band inside bins 1..256; wide: A_k)
-    __shared__ cf scratch[kSW][kFftScratch];
+    __shared__ alignas(8) cf mcs[512];                  // irfft merge constants of bin k (narrow: band inside bins 1..256; wide: A_k)
+    __shared__ alignas(8) cf scratch[kSW][kFftScratch];
     const int tid = threadIdx.x;
     // irfft's 1/1024 (1/2 in the merge, 1/512 here); the adjoint of the forward rfft is 512*irfft
     const float scale = (MODE == SY_FWD) ? (1.0f / 512.0f) : 1.0f;
@@ -455,7 +462,7 @@ __global__ __launch_bounds__(kSThreads, WIDE ? 3 : 4) void synth_stream_kernel(S
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
             const unsigned m = (mtap[r >> 2] >> (8 * (r & 3))) & 0xFFu;
-            const float2 w = melw_s[MELG ? fo[r] : 0];
+            const float2 w = lds_f2(melw_s + (MELG ? fo[r] : 0));
             const float v = w.x * mr[m] + w.y * mr[m + 1];
             inA[r] = ((inband >> r) & 1u) ? v : 0.f;
             if (r == 3) __builtin_amdgcn_sched_barrier(0);      // two rounds of four slots: 16, not 32, registers in flight
@@ -585,7 +592,7 @@ __global__ __launch_bounds__(kSThreads, WIDE ? 3 : 4) void synth_stream_kernel(S
                 for (int r = 0; r < 8; ++r) {
                     cf xp = mk(__shfl(xo[7 - r].x, src_lane), __shfl(xo[7 - r].y, src_lane));
                     if (lane == 0) xp = xo[8 - r];
-                    const cf A = mcs[lane + 64 * r];
+                    const cf A = lds_cf(mcs + lane + 64 * r);
                     const cf Bm = mk(1.f - A.x, -A.y);
                     const cf xk = xo[r];
                     // xk * A + conj(xp) * Bm
@@ -597,7 +604,7 @@ __global__ __launch_bounds__(kSThreads, WIDE ? 3 : 4) void synth_stream_kernel(S
             //   k < 256:  Z[k] = X[k] * (1 + i conj W^k)/2        k >= 256:  Z[k] = conj(X[512-k]) * (1 - i conj W^k)/2
 #pragma unroll
             for (int r = 0; r < 8; ++r) {
-                const cf mc = mcs[lane + 64 * r];
+                const cf mc = lds_cf(mcs + lane + 64 * r);
                 const float xr = inA[r] * inP[r].x, xi = (r < 4) ? inA[r] * inP[r].y : -(inA[r] * inP[r].y);
                 v[r] = mk(xr * mc.x - xi * mc.y, xr * mc.y + xi * mc.x);
             }
@@ -606,7 +613,7 @@ __global__ __launch_bounds__(kSThreads, WIDE ? 3 : 4) void synth_stream_kernel(S
             fft512_wave_t<1>(lane, v, tw1s, tw2s, s);
 #pragma unroll
             for (int r = 0; r < 8; ++r) {
-                const float2 w = wins[lane + 64 * r];
+                const float2 w = lds_f2(wins + lane + 64 * r);
                 c[r] = make_float2(v[r].x * w.x, v[r].y * w.y);
             }
         }
