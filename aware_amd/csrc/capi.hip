@@ -135,7 +135,7 @@ struct aware_detector {
     unsigned char* melf_s = nullptr;
     // architecture (aware_detector_arch).  card_arch: InstanceNorm + LeakyReLU(0.2) blocks and a tanh read-out, the model card's
     // network and the only one the fused kernels serve (conv-block epilogues, read-out, tail); every other detector takes the
-    // staged route: plain GEMM + bias, launch_norm_act_fwd / _bwd, launch_head
+    // staged route: plain GEMM + bias, launch_norm_act, launch_head
     bool card_arch = true;
     int act = kActLRelu, norm = kNormInstance, final_act = kActTanh;
     std::vector<float*> nscale, nshift;   // affine norm (BatchNorm1d in eval mode, folded): u = z * nscale[l][c] + nshift[l][c]
@@ -1109,7 +1109,7 @@ enum class MelFwd : unsigned char {
 // a conv block's forward (GEMM + norm + activation), or its data-gradient GEMM with the previous block's norm and activation
 // backward fused in where the kind is not Plain
 enum class Conv : unsigned char {
-    Plain,         // gemm_plain, then launch_norm_act_fwd (forward) / launch_norm_act_bwd of block l - 1 (next layer down)
+    Plain,         // gemm_plain, then launch_norm_act (forward) / its backward for block l - 1 (next layer down)
     ClipF32,       // clip-aligned GEMM, norm / activation in the epilogue (uniform batch, f32 MFMA)
     ClipX3,        // the same on the bf16 three-term kernel
     ClipH2,        // the same on the f16 two-term kernel (per-clip operand scales from partial maxima)
@@ -1141,7 +1141,7 @@ struct DetPlan {
     // l (otherwise that block launches the maxima kernel first); g_max[l]: the same for dL/dZ_l in gmax[l & 1]
     bool x_max[kMaxLayers + 1] = {}, g_max[kMaxLayers] = {};
     // dz[l]: the backward reaches block l with dL/dZ_l (its norm and activation backward fused into the kernel before), else
-    // with dL/dA_l and launches launch_norm_act_bwd first
+    // with dL/dA_l and launches the backward of launch_norm_act first
     bool dz[kMaxLayers] = {};
 };
 static bool is_h2(Conv k) { return k == Conv::ClipH2 || k == Conv::RaggedH2; }
@@ -1237,6 +1237,19 @@ static DetPlan det_plan(const aware_detector* d, const aware_batch* b, int pipe,
     return p;
 }
 
+// norm and activation of block l, in place on x: the conv's output (forward) or dL/dA_l (backward).  The model card's blocks are
+// the struct's defaults with no stash and the default rows.
+static NormActLaunch det_norm_act(const aware_detector* d, const aware_batch* b, const DetBufs& o, int l, float* x) {
+    NormActLaunch L;
+    L.norm = d->norm; L.act = d->act;
+    L.x = x; L.out = o.act[l]; L.stash = o.stash[l]; L.rstd = o.rstd[l];
+    L.scale = d->nscale[l]; L.shift = d->nshift[l];
+    L.frame_off = b->d_frame_off; L.pool_off = b->d_pool_off;
+    L.C = d->ch[l + 1]; L.B = b->B; L.max_pooled = b->max_frames / 2;
+    L.rows = det_rows(d, l + 1);
+    return L;
+}
+
 // forward through the network; mag [NF][stride] -> act, pred (mag is not read when the plan's mel stage is folded)
 static int det_forward(const aware_detector* d, const aware_batch* b, const DetPlan& p, const float* mag, DetBufs& o,
                        hipStream_t st) {
@@ -1295,9 +1308,7 @@ static int det_forward(const aware_detector* d, const aware_batch* b, const DetP
             LAUNCHCHK(); PROF(K_GEMM_X3_FWD);
             break;
         default:
-            // conv + bias, then the block's norm and activation (a variant's pre-activation kept in the stash).  The card's
-            // InstanceNorm + LeakyReLU keeps its own kernels: norm_act_bwd_kernel<0, 1, 80> holds the clip in AGPRs too and
-            // runs one wave per SIMD where in_lrelu_bwd_reg_kernel<80> runs two
+            // conv + bias, then the block's norm and activation (a variant's pre-activation kept in the stash)
             // temporal convolutions: the same GEMM on the unfolded rows (K = tk ci), the norm over the block's own rows
             if (d->taps) {
                 launch_conv_unfold(x, o.unf, b->d_frame_off, b->d_pool_off, ci, b->B, b->max_frames / 2, l, d->tk, d->ts, d->tp, st);
@@ -1307,11 +1318,7 @@ static int det_forward(const aware_detector* d, const aware_batch* b, const DetP
             } else
                 gemm_plain(p.pipe, x, ci, d->w[l], ci, d->wpk[l], d->bias[l], o.act[l], co, b->NP, co, ci, st);
             LAUNCHCHK(); PROF(K_GEMM);
-            if (d->card_arch)
-                launch_in_lrelu_fwd(o.act[l], b->d_frame_off, b->d_pool_off, o.rstd[l], co, b->B, b->max_frames / 2, st);
-            else
-                launch_norm_act_fwd(d->norm, d->act, o.act[l], b->d_frame_off, b->d_pool_off, o.rstd[l], d->nscale[l],
-                                    d->nshift[l], o.stash[l], co, b->B, b->max_frames / 2, st, det_rows(d, l + 1));
+            launch_norm_act(det_norm_act(d, b, o, l, o.act[l]), false, st);
             LAUNCHCHK(); PROF(K_INLRELU);
         }
         x = o.act[l];
@@ -1473,11 +1480,7 @@ static int det_forward_backward(const aware_detector* d, const aware_batch* b, c
     for (int l = p.top; l >= 0; --l) {
         const int ci = d->ch[l], co = d->ch[l + 1];
         if (!p.dz[l]) {
-            if (d->card_arch)
-                launch_in_lrelu_bwd(dA, db.act[l], b->d_frame_off, b->d_pool_off, db.rstd[l], co, b->B, b->max_frames / 2, st);
-            else
-                launch_norm_act_bwd(d->norm, d->act, dA, db.act[l], db.stash[l], b->d_frame_off, b->d_pool_off, db.rstd[l],
-                                    d->nscale[l], co, b->B, b->max_frames / 2, st, det_rows(d, l + 1));
+            launch_norm_act(det_norm_act(d, b, db, l, dA), true, st);
             LAUNCHCHK(); PROF(K_INLRELU);
         }
         // dA = dL/dZ_l [NP][co] (zero in padding rows), X = input of the block [NP][ci]:  dW = dZ^T X as an NT GEMM over

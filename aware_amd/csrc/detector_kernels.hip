@@ -813,167 +813,22 @@ __global__ __launch_bounds__(256) void mel_bwd_apply_kernel(const float* __restr
 }
 
 // ---------------------------------------------------------------------------------
-// conv block tail: InstanceNorm1d over time (biased var, eps 1e-5) + LeakyReLU(0.2),
-// in place.  Workgroup = (64 channels) x (4 row groups) of one clip.
+// Conv block tail: the block's norm over time and its activation, in place, and their backward.  The activation, its
+// derivative (torch's values at the kinks: ReLU'(0) = 0, LeakyReLU'(0) = 0.2) and the norm are a compile-time policy
+// (modules/conv1d.py:8-36, multibit_detector_net.py:82-96).  The model card's blocks are <kNormInstance, kActLRelu>:
+// InstanceNorm1d over time (biased var, eps 1e-5) + LeakyReLU(0.2); the fused GEMM epilogues serve those alone.
 // ---------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void in_lrelu_fwd_kernel(float* __restrict__ z, const int* __restrict__ frame_off, const int* __restrict__ pool_off,
-                                                            float* __restrict__ rstd, int C) {
-    __shared__ float s[4][64];
-    const int b = blockIdx.y, c0 = blockIdx.x * 64;
-    const int r0 = pool_off[b], Tp = (frame_off[b + 1] - frame_off[b]) / 2;   // rows are 32-aligned per clip
-    const int cl = threadIdx.x & 63, g = threadIdx.x >> 6, c = c0 + cl;
-    if (Tp <= 0) return;
-    const bool ok = c < C;
-    float* x = z + (size_t)r0 * C + c;
-    float a = 0.f;
-    if (ok) for (int t = g; t < Tp; t += 4) a += x[(size_t)t * C];
-    s[g][cl] = a;
-    __syncthreads();
-    const float mu = (s[0][cl] + s[1][cl] + s[2][cl] + s[3][cl]) / (float)Tp;
-    __syncthreads();
-    float q = 0.f;
-    if (ok) for (int t = g; t < Tp; t += 4) { float d = x[(size_t)t * C] - mu; q += d * d; }
-    s[g][cl] = q;
-    __syncthreads();
-    const float rs = 1.0f / sqrtf((s[0][cl] + s[1][cl] + s[2][cl] + s[3][cl]) / (float)Tp + 1e-5f);
-    if (ok && g == 0) rstd[(size_t)b * C + c] = rs;
-    if (ok) for (int t = g; t < Tp; t += 4) {
-        float u = (x[(size_t)t * C] - mu) * rs;
-        x[(size_t)t * C] = u > 0.f ? u : 0.2f * u;
-    }
-}
-
-// Register-resident variants for clips of up to 4*R pooled frames (R rows per thread): the
-// activation is read once and written once.
-template <int R>
-__global__ __launch_bounds__(256) void in_lrelu_fwd_reg_kernel(float* __restrict__ z, const int* __restrict__ frame_off, const int* __restrict__ pool_off,
-                                                                float* __restrict__ rstd, int C) {
-    __shared__ float s[4][64];
-    const int b = blockIdx.y, c0 = blockIdx.x * 64;
-    const int r0 = pool_off[b], Tp = (frame_off[b + 1] - frame_off[b]) / 2;   // rows are 32-aligned per clip
-    const int cl = threadIdx.x & 63, g = threadIdx.x >> 6, c = c0 + cl;
-    if (Tp <= 0) return;
-    const bool ok = c < C;
-    float* x = z + (size_t)r0 * C + c;
-    float v[R];
-    float a = 0.f;
-#pragma unroll
-    for (int i = 0; i < R; ++i) {
-        const int t = g + 4 * i;
-        v[i] = (ok && t < Tp) ? x[(size_t)t * C] : 0.f;
-        a += v[i];
-    }
-    s[g][cl] = a;
-    __syncthreads();
-    const float mu = (s[0][cl] + s[1][cl] + s[2][cl] + s[3][cl]) / (float)Tp;
-    __syncthreads();
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < R; ++i) {
-        const int t = g + 4 * i;
-        if (t < Tp) { float d = v[i] - mu; q += d * d; }
-    }
-    s[g][cl] = q;
-    __syncthreads();
-    const float rs = 1.0f / sqrtf((s[0][cl] + s[1][cl] + s[2][cl] + s[3][cl]) / (float)Tp + 1e-5f);
-    if (ok && g == 0) rstd[(size_t)b * C + c] = rs;
-#pragma unroll
-    for (int i = 0; i < R; ++i) {
-        const int t = g + 4 * i;
-        if (ok && t < Tp) {
-            float u = (v[i] - mu) * rs;
-            x[(size_t)t * C] = u > 0.f ? u : 0.2f * u;
-        }
-    }
-}
-
-template <int R>
-__global__ __launch_bounds__(256) void in_lrelu_bwd_reg_kernel(float* __restrict__ dA, const float* __restrict__ A,
-                                                                const int* __restrict__ frame_off, const int* __restrict__ pool_off, const float* __restrict__ rstd,
-                                                                int C) {
-    __shared__ float s1[4][64], s2[4][64];
-    const int b = blockIdx.y, c0 = blockIdx.x * 64;
-    const int r0 = pool_off[b], Tp = (frame_off[b + 1] - frame_off[b]) / 2;   // rows are 32-aligned per clip
-    const int cl = threadIdx.x & 63, g = threadIdx.x >> 6, c = c0 + cl;
-    if (Tp <= 0) return;
-    const bool ok = c < C;
-    const int cc = ok ? c : C - 1;
-    float* d = dA + (size_t)r0 * C + cc;
-    const float* a = A + (size_t)r0 * C + cc;
-    float du[R], u[R];
-    float p1 = 0.f, p2 = 0.f;
-    // loads from clamped indices, masked afterwards: a load inside a per-row branch waits for its own latency
-#pragma unroll
-    for (int i = 0; i < R; ++i) {
-        const int t = g + 4 * i;
-        const int tc = t < Tp ? t : Tp - 1;
-        u[i] = a[(size_t)tc * C];
-        du[i] = d[(size_t)tc * C];
-    }
-#pragma unroll
-    for (int i = 0; i < R; ++i) {
-        const bool valid = ok && g + 4 * i < Tp;
-        const float av = u[i];
-        u[i] = valid ? (av > 0.f ? av : av * 5.0f) : 0.f;            // invert LeakyReLU(0.2)
-        du[i] = valid ? du[i] * (av > 0.f ? 1.f : 0.2f) : 0.f;
-        p1 += du[i]; p2 += du[i] * u[i];
-    }
-    s1[g][cl] = p1; s2[g][cl] = p2;
-    __syncthreads();
-    const float m1 = (s1[0][cl] + s1[1][cl] + s1[2][cl] + s1[3][cl]) / (float)Tp;
-    const float m2 = (s2[0][cl] + s2[1][cl] + s2[2][cl] + s2[3][cl]) / (float)Tp;
-    const float rs = ok ? rstd[(size_t)b * C + c] : 0.f;
-#pragma unroll
-    for (int i = 0; i < R; ++i) {
-        const int t = g + 4 * i;
-        if (ok && t < Tp) d[(size_t)t * C] = rs * (du[i] - m1 - u[i] * m2);
-    }
-}
-
-// a * b rounded to float before any use, never fused into a following add or subtract.  The from-memory backward kernels
-// compute dL/du in both of their sweeps; fused into `du - m1` the second sweep would see the unrounded product, and a clip of
-// one pooled frame (m1 == du, gradient exactly 0) would get the rounding residue of the product instead of 0.
+// a * b rounded to float before any use, never fused into a following add or subtract.  The from-memory backward kernel
+// computes dL/du in both of its sweeps; fused into `du - m1` the second sweep would see the unrounded product, and a clip of
+// one pooled frame (m1 == du, gradient exactly 0) would get the rounding residue of the product instead of 0.  Its other two
+// products are written out as well (the sum of du * u from rounded products, u * m2 fused into the subtraction): left to the
+// compiler, the pairing of a row's two products into one packed multiply decides which of them is fused, and the pairing moves
+// with the shape of the loop around it.
 __device__ __forceinline__ float mul_rounded(float a, float b) {
 #pragma clang fp contract(off)
     return a * b;
 }
 
-__global__ __launch_bounds__(256) void in_lrelu_bwd_kernel(float* __restrict__ dA, const float* __restrict__ A,
-                                                            const int* __restrict__ frame_off, const int* __restrict__ pool_off, const float* __restrict__ rstd,
-                                                            int C) {
-    __shared__ float s1[4][64], s2[4][64];
-    const int b = blockIdx.y, c0 = blockIdx.x * 64;
-    const int r0 = pool_off[b], Tp = (frame_off[b + 1] - frame_off[b]) / 2;   // rows are 32-aligned per clip
-    const int cl = threadIdx.x & 63, g = threadIdx.x >> 6, c = c0 + cl;
-    if (Tp <= 0) return;
-    const bool ok = c < C;
-    float* d = dA + (size_t)r0 * C + c;
-    const float* a = A + (size_t)r0 * C + c;
-    float p1 = 0.f, p2 = 0.f;
-    if (ok) for (int t = g; t < Tp; t += 4) {
-        float av = a[(size_t)t * C];
-        float u = av > 0.f ? av : av * 5.0f;            // invert LeakyReLU(0.2)
-        float du = mul_rounded(d[(size_t)t * C], av > 0.f ? 1.f : 0.2f);
-        p1 += du; p2 += du * u;
-    }
-    s1[g][cl] = p1; s2[g][cl] = p2;
-    __syncthreads();
-    const float m1 = (s1[0][cl] + s1[1][cl] + s1[2][cl] + s1[3][cl]) / (float)Tp;
-    const float m2 = (s2[0][cl] + s2[1][cl] + s2[2][cl] + s2[3][cl]) / (float)Tp;
-    const float rs = ok ? rstd[(size_t)b * C + c] : 0.f;
-    if (ok) for (int t = g; t < Tp; t += 4) {
-        float av = a[(size_t)t * C];
-        float u = av > 0.f ? av : av * 5.0f;
-        float du = mul_rounded(d[(size_t)t * C], av > 0.f ? 1.f : 0.2f);
-        d[(size_t)t * C] = rs * (du - m1 - u * m2);
-    }
-}
-
-// ---------------------------------------------------------------------------------
-// Architecture variants (modules/conv1d.py:8-36, multibit_detector_net.py:82-96): the activation, its derivative (torch's
-// values at the kinks: ReLU'(0) = 0, LeakyReLU'(0) = 0.2) and the norm of a conv block, as a compile-time policy.  The
-// model card's blocks (InstanceNorm + LeakyReLU) keep the in_lrelu kernels above and the fused GEMM epilogues.
-// ---------------------------------------------------------------------------------
 template <int ACT>
 __device__ __forceinline__ float act_fwd(float u) {
     if (ACT == kActRelu) return u > 0.f ? u : 0.f;
@@ -998,22 +853,25 @@ __device__ __forceinline__ float act_grad(float u, float a) {
     return a * (1.f - a);
 }
 
-// Conv block tail of a variant, in place: u = norm(z), z = act(u), u -> stash (if given).  Workgroup = (64 channels) x
-// (4 row groups) of one clip, as in_lrelu_fwd_kernel.  R > 0: InstanceNorm with the clip's column in registers (clips of up
-// to 4 R pooled frames); R = 0: from memory (any length; the only form of the element-wise norms).
-template <int NORM, int ACT, int R>
+// In place: u = norm(z), z = act(u), u -> stash (if given).  Workgroup = (64 channels) x (4 row groups) of one clip.
+// R > 0: InstanceNorm with the clip's column in registers (clips of up to 4 R pooled frames: the activation is read once and
+// written once); R = 0: from memory (any length; the only form of the element-wise norms).  TAPS: the rows are those of a
+// block of temporal convolutions (TapRows); off, the kernel never looks at `rows` -- the rule costs registers.
+template <int NORM, int ACT, int R, bool TAPS>
 __global__ __launch_bounds__(256) void norm_act_fwd_kernel(float* __restrict__ z, const int* __restrict__ frame_off,
                                                            const int* __restrict__ pool_off, float* __restrict__ rstd,
                                                            const float* __restrict__ scale, const float* __restrict__ shift,
                                                            float* __restrict__ stash, int C, TapRows rows) {
     __shared__ float s[4][64];
     const int b = blockIdx.y, c0 = blockIdx.x * 64;
-    const int r0 = pool_off[b], Tp = rows.of((frame_off[b + 1] - frame_off[b]) / 2);   // rows are 32-aligned per clip
+    const int L0 = (frame_off[b + 1] - frame_off[b]) / 2;
+    const int r0 = pool_off[b], Tp = TAPS ? rows.of(L0) : L0;   // rows are 32-aligned per clip
     const int cl = threadIdx.x & 63, g = threadIdx.x >> 6, c = c0 + cl;
     if (Tp <= 0) return;
     const bool ok = c < C;
     float* x = z + (size_t)r0 * C + c;
-    float* sx = stash ? stash + (size_t)r0 * C + c : nullptr;
+    // (a block that needs no stash never gets one: for those the rows' stores carry no test)
+    float* sx = (norm_act_needs_stash(NORM, ACT) && stash) ? stash + (size_t)r0 * C + c : nullptr;
     float v[R > 0 ? R : 1];
     float mu = 0.f, rs = 1.f, sc = 1.f, sh = 0.f;
     if (NORM == kNormInstance) {
@@ -1062,31 +920,42 @@ __global__ __launch_bounds__(256) void norm_act_fwd_kernel(float* __restrict__ z
     }
 }
 
-// backward of norm_act_fwd_kernel, in place on dA.  u from the stash, or from the output A where the activation can be
-// inverted (LeakyReLU; ReLU after an element-wise norm, whose derivative only needs the sign of u).
-template <int NORM, int ACT, int R>
+// backward of norm_act_fwd_kernel, in place on dA.  u from the stash where the block keeps one (norm_act_needs_stash, a
+// function of the policy alone), else from the output A: LeakyReLU inverted; ReLU after an element-wise norm as it is, since
+// its derivative only needs the sign of u.
+template <int NORM, int ACT, int R, bool TAPS>
 __global__ __launch_bounds__(256) void norm_act_bwd_kernel(float* __restrict__ dA, const float* __restrict__ A,
                                                            const float* __restrict__ stash, const int* __restrict__ frame_off,
                                                            const int* __restrict__ pool_off, const float* __restrict__ rstd,
                                                            const float* __restrict__ scale, int C, TapRows rows) {
+    constexpr bool kStash = norm_act_needs_stash(NORM, ACT);
     __shared__ float s1[4][64], s2[4][64];
     const int b = blockIdx.y, c0 = blockIdx.x * 64;
-    const int r0 = pool_off[b], Tp = rows.of((frame_off[b + 1] - frame_off[b]) / 2);   // rows are 32-aligned per clip
+    const int L0 = (frame_off[b + 1] - frame_off[b]) / 2;
+    const int r0 = pool_off[b], Tp = TAPS ? rows.of(L0) : L0;   // rows are 32-aligned per clip
     const int cl = threadIdx.x & 63, g = threadIdx.x >> 6, c = c0 + cl;
     if (Tp <= 0) return;
     const bool ok = c < C;
-    const int cc = ok ? c : C - 1;
+    const int cc = (R > 0 && !ok) ? C - 1 : c;      // the register form loads in every lane, from a clamped column
     float* d = dA + (size_t)r0 * C + cc;
-    const float* a = A + (size_t)r0 * C + cc;
-    const float* su = stash ? stash + (size_t)r0 * C + cc : nullptr;
-    // (u, dL/du) at row t
-    // (with a stash the output is not read: the block activations' derivatives need u only)
+    const float* a = (kStash ? stash : A) + (size_t)r0 * C + cc;
+    // (u, f'(u)) from the value v kept at a row.  LeakyReLU's output has the sign of u: one test inverts it and picks the slope
+    auto kept = [](float v, float& u, float& slope) {
+        if (!kStash && ACT == kActLRelu) {
+            const bool pos = v > 0.f;
+            u = pos ? v : v * 5.0f;
+            slope = pos ? 1.f : 0.2f;
+        } else {
+            u = v;
+            slope = act_grad<ACT>(u, 0.f);
+        }
+    };
+    // (u, dL/du) at row t, from memory
     auto load = [&](int t, float& u, float& du) {
-        const float av = su ? 0.f : a[(size_t)t * C];
-        u = su ? su[(size_t)t * C] : (ACT == kActLRelu ? (av > 0.f ? av : av * 5.0f) : av);
+        float slope;
+        kept(a[(size_t)t * C], u, slope);
         // (the from-memory InstanceNorm form runs this in both sweeps: see mul_rounded)
-        du = (NORM == kNormInstance && R == 0) ? mul_rounded(d[(size_t)t * C], act_grad<ACT>(u, av))
-                                                : d[(size_t)t * C] * act_grad<ACT>(u, av);
+        du = (NORM == kNormInstance && R == 0) ? mul_rounded(d[(size_t)t * C], slope) : d[(size_t)t * C] * slope;
     };
     if (NORM != kNormInstance) {
         if (!ok) return;
@@ -1101,75 +970,88 @@ __global__ __launch_bounds__(256) void norm_act_bwd_kernel(float* __restrict__ d
     float uu[R > 0 ? R : 1], dd[R > 0 ? R : 1];
     float p1 = 0.f, p2 = 0.f;
     if (R > 0) {
+        // loads from clamped indices, masked afterwards: a load inside a per-row branch waits for its own latency
 #pragma unroll
         for (int i = 0; i < R; ++i) {
             const int t = g + 4 * i;
-            const bool valid = ok && t < Tp;
-            load(t < Tp ? t : Tp - 1, uu[i], dd[i]);
-            if (!valid) { uu[i] = 0.f; dd[i] = 0.f; }
+            const int tc = t < Tp ? t : Tp - 1;
+            uu[i] = a[(size_t)tc * C];
+            dd[i] = d[(size_t)tc * C];
+        }
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+            const bool valid = ok && g + 4 * i < Tp;
+            float u, slope;
+            kept(uu[i], u, slope);
+            uu[i] = valid ? u : 0.f;
+            dd[i] = valid ? dd[i] * slope : 0.f;
             p1 += dd[i]; p2 += dd[i] * uu[i];
         }
     } else if (ok) {
         for (int t = g; t < Tp; t += 4) {
             float u, du;
             load(t, u, du);
-            p1 += du; p2 += du * u;
+            p1 += du; p2 += mul_rounded(du, u);
         }
     }
     s1[g][cl] = p1; s2[g][cl] = p2;
     __syncthreads();
     const float m1 = (s1[0][cl] + s1[1][cl] + s1[2][cl] + s1[3][cl]) / (float)Tp;
     const float m2 = (s2[0][cl] + s2[1][cl] + s2[2][cl] + s2[3][cl]) / (float)Tp;
-    if (!ok) return;
-    const float rs = rstd[(size_t)b * C + c];
+    const float rs = ok ? rstd[(size_t)b * C + c] : 0.f;
     if (R > 0) {
 #pragma unroll
         for (int i = 0; i < R; ++i) {
             const int t = g + 4 * i;
-            if (t < Tp) d[(size_t)t * C] = rs * (dd[i] - m1 - uu[i] * m2);
+            if (ok && t < Tp) d[(size_t)t * C] = rs * (dd[i] - m1 - uu[i] * m2);
         }
-    } else {
+    } else if (ok) {
         for (int t = g; t < Tp; t += 4) {
             float u, du;
             load(t, u, du);
-            d[(size_t)t * C] = rs * (du - m1 - u * m2);
+            d[(size_t)t * C] = rs * fmaf(-u, m2, du - m1);
         }
     }
 }
 
+// the instantiation a launch takes: the policy from L.norm / L.act, the form from the batch's longest clip (the register
+// forms are InstanceNorm's alone), TAPS from the rows
+template <int NORM, int ACT, int R, bool TAPS>
+static void norm_act_go(const NormActLaunch& L, bool backward, hipStream_t st) {
+    const dim3 grid((L.C + 63) / 64, L.B), block(256);
+    if (backward)
+        hipLaunchKernelGGL((norm_act_bwd_kernel<NORM, ACT, R, TAPS>), grid, block, 0, st, L.x, L.out, L.stash, L.frame_off,
+                           L.pool_off, L.rstd, L.scale, L.C, L.rows);
+    else
+        hipLaunchKernelGGL((norm_act_fwd_kernel<NORM, ACT, R, TAPS>), grid, block, 0, st, L.x, L.frame_off, L.pool_off, L.rstd,
+                           L.scale, L.shift, L.stash, L.C, L.rows);
+}
+template <int NORM, int ACT, int R>
+static void norm_act_rows(const NormActLaunch& L, bool backward, hipStream_t st) {
+    if (L.rows.layer != 0) norm_act_go<NORM, ACT, R, true>(L, backward, st);
+    else norm_act_go<NORM, ACT, R, false>(L, backward, st);
+}
 template <int NORM, int ACT>
-static void norm_act_launch(bool fwd, float* z, const float* A, const int* frame_off, const int* pool_off, float* rstd,
-                            const float* scale, const float* shift, float* stash, int C, int B, int max_pooled, hipStream_t st, TapRows rows) {
-    const dim3 grid((C + 63) / 64, B), block(256);
-    if (NORM == kNormInstance && max_pooled <= 128) {
-        if (fwd) hipLaunchKernelGGL((norm_act_fwd_kernel<NORM, ACT, 32>), grid, block, 0, st, z, frame_off, pool_off, rstd, scale, shift, stash, C, rows);
-        else hipLaunchKernelGGL((norm_act_bwd_kernel<NORM, ACT, 32>), grid, block, 0, st, z, A, stash, frame_off, pool_off, rstd, scale, C, rows);
-    } else if (NORM == kNormInstance && max_pooled <= 320) {
-        if (fwd) hipLaunchKernelGGL((norm_act_fwd_kernel<NORM, ACT, 80>), grid, block, 0, st, z, frame_off, pool_off, rstd, scale, shift, stash, C, rows);
-        else hipLaunchKernelGGL((norm_act_bwd_kernel<NORM, ACT, 80>), grid, block, 0, st, z, A, stash, frame_off, pool_off, rstd, scale, C, rows);
-    } else {
-        if (fwd) hipLaunchKernelGGL((norm_act_fwd_kernel<NORM, ACT, 0>), grid, block, 0, st, z, frame_off, pool_off, rstd, scale, shift, stash, C, rows);
-        else hipLaunchKernelGGL((norm_act_bwd_kernel<NORM, ACT, 0>), grid, block, 0, st, z, A, stash, frame_off, pool_off, rstd, scale, C, rows);
+static void norm_act_form(const NormActLaunch& L, bool backward, hipStream_t st) {
+    if constexpr (NORM == kNormInstance) {
+        if (L.max_pooled <= 128) return norm_act_rows<NORM, ACT, 32>(L, backward, st);
+        if (L.max_pooled <= 320) return norm_act_rows<NORM, ACT, 80>(L, backward, st);
     }
+    norm_act_rows<NORM, ACT, 0>(L, backward, st);
 }
 template <int NORM>
-static void norm_act_dispatch(int act, bool fwd, float* z, const float* A, const int* frame_off, const int* pool_off, float* rstd,
-                              const float* scale, const float* shift, float* stash, int C, int B, int max_pooled, hipStream_t st, TapRows rows) {
-    switch (act) {
-        case kActRelu: norm_act_launch<NORM, kActRelu>(fwd, z, A, frame_off, pool_off, rstd, scale, shift, stash, C, B, max_pooled, st, rows); break;
-        case kActLRelu: norm_act_launch<NORM, kActLRelu>(fwd, z, A, frame_off, pool_off, rstd, scale, shift, stash, C, B, max_pooled, st, rows); break;
-        case kActGelu: norm_act_launch<NORM, kActGelu>(fwd, z, A, frame_off, pool_off, rstd, scale, shift, stash, C, B, max_pooled, st, rows); break;
-        default: norm_act_launch<NORM, kActSwish>(fwd, z, A, frame_off, pool_off, rstd, scale, shift, stash, C, B, max_pooled, st, rows); break;
+static void norm_act_policy(const NormActLaunch& L, bool backward, hipStream_t st) {
+    switch (L.act) {
+        case kActRelu: norm_act_form<NORM, kActRelu>(L, backward, st); break;
+        case kActLRelu: norm_act_form<NORM, kActLRelu>(L, backward, st); break;
+        case kActGelu: norm_act_form<NORM, kActGelu>(L, backward, st); break;
+        default: norm_act_form<NORM, kActSwish>(L, backward, st); break;
     }
 }
-static void norm_act(int norm, int act, bool fwd, float* z, const float* A, const int* frame_off, const int* pool_off, float* rstd,
-                     const float* scale, const float* shift, float* stash, int C, int B, int max_pooled, hipStream_t st, TapRows rows) {
-    if (norm == kNormInstance)
-        norm_act_dispatch<kNormInstance>(act, fwd, z, A, frame_off, pool_off, rstd, scale, shift, stash, C, B, max_pooled, st, rows);
-    else if (norm == kNormAffine)
-        norm_act_dispatch<kNormAffine>(act, fwd, z, A, frame_off, pool_off, rstd, scale, shift, stash, C, B, max_pooled, st, rows);
-    else
-        norm_act_dispatch<kNormNone>(act, fwd, z, A, frame_off, pool_off, rstd, scale, shift, stash, C, B, max_pooled, st, rows);
+void launch_norm_act(const NormActLaunch& L, bool backward, hipStream_t st) {
+    if (L.norm == kNormInstance) norm_act_policy<kNormInstance>(L, backward, st);
+    else if (L.norm == kNormAffine) norm_act_policy<kNormAffine>(L, backward, st);
+    else norm_act_policy<kNormNone>(L, backward, st);
 }
 
 // ---------------------------------------------------------------------------------
@@ -1370,7 +1252,7 @@ void launch_tail(const float* zpart, int nsplit, size_t slab, const float* bias,
 // slot cl of CW = min(Cp, 256) and time group g of 256 / CW; it owns channels cl, cl + CW, ... (at most kWideNJ).
 //   pass 1: per-channel time sums of the block output A (card: also of lrelu'(u) and lrelu'(u) u, u recovered from A)
 //   read-out: mean -> even - odd -> final activation -> loss / best-loss bookkeeping / step counter, as head_kernel
-//   pass 2: MODE 1: dL/dA [rows][Cp] (staged route: launch_norm_act_bwd consumes it)
+//   pass 2: MODE 1: dL/dA [rows][Cp] (staged route: the backward of launch_norm_act consumes it)
 //           MODE 2: dL/dZ of the card block, the InstanceNorm + LeakyReLU backward folded in (dA is constant in time, so
 //                   mean_t dU = dA mean_t lrelu' and mean_t dU u = dA mean_t lrelu' u come from pass 1), and the per-clip
 //                   partial maxima of |dZ| for the f16 two-term data-gradient GEMM (gmax [B][64]: entry 0 the maximum,
@@ -1832,23 +1714,6 @@ void launch_mel_norm_bwd(const float* dx0, float* xm, const int* frame_off, cons
     else
         mel_chunked_bwd<MelBankAny>(dx0, xm, frame_off, pool_off, stats, gstat, part, pstride, B, max_frames, n_mels, Mp, st);
 }
-void launch_in_lrelu_fwd(float* z, const int* frame_off, const int* pool_off, float* rstd, int C, int B, int max_pooled, hipStream_t st) {
-    if (max_pooled <= 128)
-        hipLaunchKernelGGL(in_lrelu_fwd_reg_kernel<32>, dim3((C + 63) / 64, B), dim3(256), 0, st, z, frame_off, pool_off, rstd, C);
-    else if (max_pooled <= 320)
-        hipLaunchKernelGGL(in_lrelu_fwd_reg_kernel<80>, dim3((C + 63) / 64, B), dim3(256), 0, st, z, frame_off, pool_off, rstd, C);
-    else
-        hipLaunchKernelGGL(in_lrelu_fwd_kernel, dim3((C + 63) / 64, B), dim3(256), 0, st, z, frame_off, pool_off, rstd, C);
-}
-void launch_in_lrelu_bwd(float* dA, const float* A, const int* frame_off, const int* pool_off, const float* rstd, int C, int B,
-                         int max_pooled, hipStream_t st) {
-    if (max_pooled <= 128)
-        hipLaunchKernelGGL(in_lrelu_bwd_reg_kernel<32>, dim3((C + 63) / 64, B), dim3(256), 0, st, dA, A, frame_off, pool_off, rstd, C);
-    else if (max_pooled <= 320)
-        hipLaunchKernelGGL(in_lrelu_bwd_reg_kernel<80>, dim3((C + 63) / 64, B), dim3(256), 0, st, dA, A, frame_off, pool_off, rstd, C);
-    else
-        hipLaunchKernelGGL(in_lrelu_bwd_kernel, dim3((C + 63) / 64, B), dim3(256), 0, st, dA, A, frame_off, pool_off, rstd, C);
-}
 void launch_head(const float* a3, const int* frame_off, const int* pool_off, const float* target, float* pred, float* loss,
                  float* best_loss, int* improved, float* dA3, int* step, int loss_kind, int nbits, int B,
                  hipStream_t st, const float* loss_add, int final_act, int C, TapRows rows) {
@@ -1865,15 +1730,6 @@ void launch_head(const float* a3, const int* frame_off, const int* pool_off, con
         default: AW_HEAD(kActTanh); break;
     }
 #undef AW_HEAD
-}
-void launch_norm_act_fwd(int norm, int act, float* z, const int* frame_off, const int* pool_off, float* rstd, const float* scale,
-                         const float* shift, float* stash, int C, int B, int max_pooled, hipStream_t st, TapRows rows) {
-    norm_act(norm, act, true, z, nullptr, frame_off, pool_off, rstd, scale, shift, stash, C, B, max_pooled, st, rows);
-}
-void launch_norm_act_bwd(int norm, int act, float* dA, const float* A, const float* stash, const int* frame_off, const int* pool_off,
-                         const float* rstd, const float* scale, int C, int B, int max_pooled, hipStream_t st, TapRows rows) {
-    norm_act(norm, act, false, dA, A, frame_off, pool_off, const_cast<float*>(rstd), scale, nullptr, const_cast<float*>(stash), C, B,
-             max_pooled, st, rows);
 }
 
 }  // namespace aware

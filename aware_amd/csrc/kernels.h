@@ -204,30 +204,34 @@ void launch_mel_norm_fwd(const float* xm, const int* frame_off, const int* pool_
                          float* amax_out = nullptr);
 void launch_mel_norm_bwd(const float* dx0, float* xm_inout, const int* frame_off, const int* pool_off, const float* stats,
                          const float* gstat, float* part, int pstride, int B, int max_frames, int n_mels, int Mp, hipStream_t st);
-// conv block tail: InstanceNorm over time + LeakyReLU(0.2), in place; saves rstd
-void launch_in_lrelu_fwd(float* z, const int* frame_off, const int* pool_off, float* rstd, int C, int B, int max_pooled,
-                         hipStream_t st);
-// backward of the same, in place on dA (A is the post-activation output of the forward)
-void launch_in_lrelu_bwd(float* dA, const float* A, const int* frame_off, const int* pool_off, const float* rstd, int C, int B,
-                         int max_pooled, hipStream_t st);
 // ---- architecture variants of the detector (aware_detector_arch; the values are the header's AWARE_ACT_* / AWARE_NORM_* /
 // AWARE_FINAL_*): the norm and activation of every conv block and the read-out's final activation
 constexpr int kActRelu = 0, kActLRelu = 1, kActGelu = 2, kActSwish = 3, kActTanh = 4, kActSigmoid = 5;
 constexpr int kNormInstance = 0, kNormAffine = 1, kNormNone = 2;
 // whether the backward of a block needs its pre-activation u (the norm's output) kept from the forward: every activation but
 // LeakyReLU can not be inverted from its output, and the InstanceNorm backward needs u at every position (also where ReLU gave 0)
-AW_HD bool norm_act_needs_stash(int norm, int act) {
+AW_HD constexpr bool norm_act_needs_stash(int norm, int act) {
     return !(act == kActLRelu || (act == kActRelu && norm != kNormInstance));
 }
-// conv block tail of a variant, in place on z [NP][C]: u = norm(z) (InstanceNorm over time, saves rstd [B][C]; affine
-// u = z * scale[c] + shift[c]; or identity), z = act(u); stash [NP][C] receives u (null: not written)
-void launch_norm_act_fwd(int norm, int act, float* z, const int* frame_off, const int* pool_off, float* rstd, const float* scale,
-                         const float* shift, float* stash, int C, int B, int max_pooled, hipStream_t st, TapRows rows = TapRows());
-// backward of the same, in place on dA: u read from stash, or recovered from the output A (norm_act_needs_stash false)
-void launch_norm_act_bwd(int norm, int act, float* dA, const float* A, const float* stash, const int* frame_off, const int* pool_off,
-                         const float* rstd, const float* scale, int C, int B, int max_pooled, hipStream_t st, TapRows rows = TapRows());
-// (rows: the block whose rows the kernel normalises, for a detector of temporal convolutions -- conv_taps.hpp; the default is
-//  the clip's pooled frames, and with it every instantiation computes what it always did)
+// conv block tail, in place on x [NP][C].  Forward: u = norm(x) (InstanceNorm over time, biased var, eps 1e-5; affine
+// u = x * scale[c] + shift[c]; or identity), x = act(u).  Backward: x = dL/dA -> dL/dz, with u read from the stash or, where
+// norm_act_needs_stash is false, recovered from the forward's output.  The defaults are the model card's block.
+struct NormActLaunch {
+    int norm = kNormInstance, act = kActLRelu;
+    float* x = nullptr;
+    const float* out = nullptr;           // backward without a stash: the forward's output A [NP][C]
+    float* stash = nullptr;               // [NP][C] u: the forward writes it (null: not kept), the backward reads it
+    float* rstd = nullptr;                // [B][C], InstanceNorm: the forward writes it, the backward reads it
+    const float* scale = nullptr;         // [C] each, affine norm
+    const float* shift = nullptr;
+    const int* frame_off = nullptr;       // [B+1]
+    const int* pool_off = nullptr;        // [B]: clip b's rows start at pool_off[b]
+    int C = 0, B = 0, max_pooled = 0;
+    // the block whose rows the kernel normalises, for a detector of temporal convolutions (conv_taps.hpp); the default is the
+    // clip's pooled frames, and with it the kernels hold no trace of the row rule
+    TapRows rows;
+};
+void launch_norm_act(const NormActLaunch& L, bool backward, hipStream_t st);
 // BRH + loss + dL/dA3; also best-loss tracking.  final_act: kActRelu .. kActSigmoid applied to even - odd (the card: tanh)
 void launch_head(const float* a3, const int* frame_off, const int* pool_off, const float* target, float* pred, float* loss,
                  float* best_loss, int* improved, float* dA3, int* step, int loss_kind, int nbits, int B,

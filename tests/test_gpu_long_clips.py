@@ -5,12 +5,12 @@ batch, so one long clip moves every clip of its batch onto the branches below; n
   branch (condition on the batch)                                          pinned by
   ------------------------------------------------------------------------------------------------------------------------
   T >= 642: last card block Conv::Plain instead of SplitK, read-out        test_first_iteration_long[b, c, d], test_detect_long,
-    head_kernel, backward through launch_in_lrelu_bwd and a plain            test_trajectory_20_steps_graph
+    head_kernel, backward through launch_norm_act and a plain                test_trajectory_20_steps_graph
     data-gradient GEMM with K = 40 (det_plan)
-  pooled > 320: in_lrelu_fwd_kernel / in_lrelu_bwd_kernel (from memory);   test_first_iteration_long[b, c, d];
-    norm_act_{fwd,bwd}_kernel<NORM, ACT, 0> for the variants                 test_detector_entry_points_long, test_smooth_variants_embed_gradient_long
+  pooled > 320: norm_act_{fwd,bwd}_kernel<NORM, ACT, 0> (from memory),     test_first_iteration_long[b, c, d];
+    for the card's blocks and for the variants                               test_detector_entry_points_long, test_smooth_variants_embed_gradient_long
   pooled == 320 (T = 641): tail_kernel<., 80> and                          test_first_iteration_long[a]
-    in_lrelu_*_reg_kernel<80>, every register slot in use
+    norm_act_*_kernel<Instance, LeakyReLU, 80>, every register slot in use
   T = 192 / 193 and pooled 128 / 129: clip form <-> chunked form of the    test_first_iteration_long[e, f]
     mel norm (kMelClipFrames), clip_tile_groups 4 -> 0
   T >= 65 536: no flat workgroup table, (runs, B) grids of the stream      test_stft_and_detect_at_the_workgroup_table_limit
@@ -48,8 +48,8 @@ Measured on MI355X (every figure is printed before it is asserted; maxima over c
   test_stft_and_detect_at_the_workgroup_table_limit: STFT / band 2.3e-7, iSTFT 3.6e-7, detect 1.2e-6 (T = 65 536) and
     1.0e-6 (T = 65 535) against a bar of 5e-5
 No bar was raised: the reference-yardstick fallback (float32 against float64 oracle) was not needed anywhere.
-A kernel trace of this module shows in_lrelu_fwd_kernel, in_lrelu_bwd_kernel, head_kernel<4>, norm_act_{fwd,bwd}_kernel<0|1|2,
-., 0>, readout_wide_kernel<4, 2>, tail_kernel<4, 80>, in_lrelu_*_reg_kernel<80> and analysis_stream_kernel on 1024 x 1
+A kernel trace of this module shows head_kernel<4>, norm_act_{fwd,bwd}_kernel<0|1|2, ., 0, false> (the card's blocks at
+<0, 1, 0, false>), readout_wide_kernel<4, 2>, tail_kernel<4, 80>, norm_act_*_kernel<0, 1, 80, false> and analysis_stream_kernel on 1024 x 1
 workgroups (run length 16, T = 65 536) next to 1366 from the table (run length 12, T = 65 535).
 """
 import numpy as np
@@ -164,7 +164,7 @@ def check_first_iteration(rt, plan, det, O, lengths, seeds, **session):
 def test_first_iteration_long(rt, plan, det, O, name, pipe):
     """Loss, prediction and dL/dcoef of the first loop body on the card detector at the dispatch boundaries, against torch
     autograd on the float32 oracle: loss 2e-5, prediction 5e-5, gradient 5e-5 relative L2 for every clip, every clip clear
-    of a kink.  In (c) and (d) the short clips run on the long-clip kernels (head_kernel, in_lrelu_* from memory, chunked
+    of a kink.  In (c) and (d) the short clips run on the long-clip kernels (head_kernel, norm_act_* from memory, chunked
     mel norm) and are held to the same bars.  The 513-sample clip has one pooled frame: its gradient is exactly zero."""
     check_first_iteration(rt, plan, det, O, *BATCHES[name], conv_pipe=pipe)
 
