@@ -14,7 +14,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AWARE_HIP_LIB") or os.path.join(_HERE, "libaware_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["capi.hip", "dsp_kernels.hip", "dsp_stream.hip", "seam_kernels.hip", "detector_kernels.hip", "gemm_x3.hip", "gemm_h2.hip", "attack_kernels.hip", "stft_any.hip", "loop_any.hip", "stoi_kernels.hip", "loop_attack_kernels.hip", "loop_reverb_kernels.hip", "loop_speed_kernels.hip", "loop_stretch_kernels.hip", "loop_pitch_kernels.hip", "loop_pv_kernels.hip", "loop_delete_kernels.hip", "loop_filter_kernels.hip", "loop_shift_kernels.hip", "loop_excerpt_kernels.hip", "loop_warp_kernels.hip", "sync_kernels.hip", "loop_mix_kernels.hip", "loop_gain_kernels.hip", "speed_search_kernels.hip", "shift_search_kernels.hip", "scan_kernels.hip", "viterbi_kernels.hip", "conv_taps_kernels.hip"]
+SOURCES = ["capi.hip", "dsp_kernels.hip", "dsp_stream.hip", "seam_kernels.hip", "detector_kernels.hip", "gemm_x3.hip", "gemm_h2.hip", "attack_kernels.hip", "stft_any.hip", "loop_any.hip", "stoi_kernels.hip", "loop_attack_kernels.hip", "loop_reverb_kernels.hip", "loop_speed_kernels.hip", "loop_stretch_kernels.hip", "loop_pitch_kernels.hip", "loop_pv_kernels.hip", "loop_delete_kernels.hip", "loop_filter_kernels.hip", "loop_shift_kernels.hip", "loop_excerpt_kernels.hip", "loop_warp_kernels.hip", "sync_kernels.hip", "loop_mix_kernels.hip", "loop_gain_kernels.hip", "speed_search_kernels.hip", "shift_search_kernels.hip", "scan_kernels.hip", "viterbi_kernels.hip", "conv_taps_kernels.hip", "mel_pool_kernels.hip"]
 
 AWARE_OK = 0
 ERRORS = {-1: "bad argument", -2: "unsupported configuration", -3: "HIP runtime error", -4: "workspace too small"}
@@ -142,6 +142,10 @@ SIGNATURES = {
     "aware_detector_create_conv": (_i, [C.POINTER(_vp), _vp, _vp, _i, _i, _pi, C.POINTER(_vp), C.POINTER(_vp),
                                        C.POINTER(DetectorArch), _i, _i, _i]),
     "aware_detector_conv": (_i, [_vp, _pi, _pi, _pi]),
+    "aware_detector_create_pool": (_i, [C.POINTER(_vp), _vp, _vp, _i, _i, _pi, C.POINTER(_vp), C.POINTER(_vp),
+                                       C.POINTER(DetectorArch), _i, _i, _i, _i, _i]),
+    "aware_detector_pool": (_i, [_vp, _pi, _pi]),
+    "aware_pool_rows": (_i, [_i, _i, _i]),
     "aware_conv_rows": (_i, [_i, _i, _i, _i, _i]),
     "aware_conv_unfold": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "aware_conv_fold": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),

@@ -147,14 +147,24 @@ struct aware_detector {
     bool taps = false;
     int tk = 1, ts = 1, tp = 0;
     int max_cin = 0;         // the widest block input (stored), for the unfold scratch [NP][tk max_cin]
+    // the initial pool between the mel stage and block 0 (aware_detector_create_pool; conv_taps.hpp: pool_rows): AvgPool1d(psize,
+    // pstride).  Other than (2, 2) the detector is `pooled` and, like one of temporal convolutions, never card_arch: the mel
+    // stage runs mel_pool_kernels.hip and every block the staged route on the clip's pool_rows rows -- the fused kernels, the
+    // clip-form mel kernels and mel_front_x3 / mel_back_x3 all hold floor(T / 2)
+    bool pooled = false;
+    int psize = 2, pstride = 2;
 };
 // the rows a kernel behind `blocks` blocks of the detector works on
-static TapRows det_rows(const aware_detector* d, int blocks) { return d->taps ? TapRows{blocks, d->tk, d->ts, d->tp} : TapRows(); }
-// every clip keeps at least one row through every block (torch's conv1d raises where one does not)
+static TapRows det_rows(const aware_detector* d, int blocks) {
+    TapRows r = d->taps ? TapRows{blocks, d->tk, d->ts, d->tp} : TapRows();
+    r.psize = d->psize; r.pstride = d->pstride;
+    return r;
+}
+// every clip keeps at least one row behind the pool and through every block (torch's avg_pool1d / conv1d raise where one does not)
 static bool det_clips_ok(const aware_detector* d, const aware_batch* b) {
-    if (!d->taps) return true;
+    if (!d->taps && !d->pooled) return true;
     for (int i = 0; i < b->B; ++i)
-        if (conv_rows(b->T[i] / 2, d->n_layers, d->tk, d->ts, d->tp) < 1) return false;
+        if (conv_rows(pool_rows(b->T[i], d->psize, d->pstride), d->n_layers, d->tk, d->ts, d->tp) < 1) return false;
     return true;
 }
 static_assert(AWARE_ACT_RELU == kActRelu && AWARE_ACT_LEAKY_RELU == kActLRelu && AWARE_ACT_GELU == kActGelu &&
@@ -759,7 +769,8 @@ static int detector_upload(aware_detector* d, const float* mel_basis, const floa
         const size_t o_mB = pk_total; if (mB) pk_total += x3_packed_bytes(S, Mp);
         // read-out kernel operands (last conv block, C <= 64 channels)
         const int cil = channels[n_layers - 1], col = channels[n_layers], colp = 16 * ((col + 15) / 16);
-        const bool ro = !d->taps && n_layers >= 2 && readout_x3_supported(1, cil, col);   // (the fused read-out: 1x1 blocks only)
+        // (the fused read-out: 1x1 blocks after the (2, 2) pool only)
+        const bool ro = !d->taps && !d->pooled && n_layers >= 2 && readout_x3_supported(1, cil, col);
         size_t o_lp = 0, o_lT = 0;
         if (ro) {
             o_lp = pk_total; pk_total += x3_packed_bytes(colp, cil);
@@ -798,7 +809,7 @@ static int detector_upload(aware_detector* d, const float* mel_basis, const floa
         // f16 two-term images, packed on the device from the f32 copies just uploaded
         size_t total2 = 0;
         std::vector<size_t> o_h(n_layers), o_hT(n_layers);
-        for (int l = 0; l < n_layers && !d->taps; ++l) {      // (the f16 two-term kernels serve the fused conv blocks only)
+        for (int l = 0; l < n_layers && !d->taps && !d->pooled; ++l) {   // (the f16 two-term kernels serve the fused conv blocks only)
             const int ci = channels[l], co = channels[l + 1];
             o_h[l] = o_hT[l] = (size_t)-1;
             if (gemm_clip_h2_supported(1, co, ci, ci)) { o_h[l] = total2; total2 += (h2_packed_bytes(co, ci) + 255) & ~(size_t)255; }
@@ -820,7 +831,7 @@ static int detector_upload(aware_detector* d, const float* mel_basis, const floa
 
 static int detector_create(aware_detector** out, const aware_plan* plan, const float* mel_basis, int n_mels, int n_layers,
                            const int* channels, const float* const* weights, const float* const* biases,
-                           const aware_detector_arch* arch, int tk = 1, int ts = 1, int tp = 0) {
+                           const aware_detector_arch* arch, int tk = 1, int ts = 1, int tp = 0, int psize = 2, int pstride = 2) {
     if (!out || !plan || !mel_basis || !channels || !weights) return AWARE_E_BADARG;
     // a general plan made for the transforms alone (no AWARE_PLAN_GENERAL), or a band outside bins 0..n_fft/2
     if (plan->general && (!plan->loop || !plan->band_ok)) return AWARE_E_UNSUPPORTED;
@@ -842,6 +853,8 @@ static int detector_create(aware_detector** out, const aware_plan* plan, const f
     }
     d->taps = tk != 1 || ts != 1 || tp != 0;
     d->tk = tk; d->ts = ts; d->tp = tp;
+    d->pooled = psize != 2 || pstride != 2;
+    d->psize = psize; d->pstride = pstride;
     d->w.assign(n_layers, nullptr); d->wT.assign(n_layers, nullptr); d->bias.assign(n_layers, nullptr);
     d->wpk.assign(n_layers, nullptr); d->wTpk.assign(n_layers, nullptr);
     d->wh2.assign(n_layers, nullptr); d->wTh2.assign(n_layers, nullptr);
@@ -850,7 +863,7 @@ static int detector_create(aware_detector** out, const aware_plan* plan, const f
         d->act = arch->activation; d->norm = arch->norm; d->final_act = arch->final_activation;
         d->card_arch = d->act == kActLRelu && d->norm == kNormInstance && d->final_act == kActTanh;
     }
-    if (d->taps) d->card_arch = false;
+    if (d->taps || d->pooled) d->card_arch = false;
     int rc = detector_upload(d.get(), mel_basis, weights, biases, true);
     if (rc == AWARE_OK && d->norm == kNormAffine) {
         // padding channels (stored_channels) get scale 0 and shift 0: their pre-activation is 0 and their output act(0) = 0
@@ -917,6 +930,33 @@ extern "C" int aware_detector_create_conv(aware_detector** out, const aware_plan
         return aware_detector_create_ex(out, plan, mel_basis, n_mels, n_layers, channels, weights, biases, arch);
     if (!arch_ok(arch, n_layers)) return AWARE_E_BADARG;
     return detector_create(out, plan, mel_basis, n_mels, n_layers, channels, weights, biases, arch, kernel_size, stride, padding);
+}
+// The same with the initial pool AvgPool1d(pool_size, pool_stride) between the mel stage and block 0 (conv_taps.hpp: pool_rows).
+// 2 / 2 is aware_detector_create_conv.
+extern "C" int aware_detector_create_pool(aware_detector** out, const aware_plan* plan, const float* mel_basis, int n_mels,
+                                          int n_layers, const int* channels, const float* const* weights,
+                                          const float* const* biases, const aware_detector_arch* arch, int kernel_size, int stride,
+                                          int padding, int pool_size, int pool_stride) {
+    if (pool_size < 1 || pool_stride < 1) return AWARE_E_BADARG;
+    if (pool_size < kMinPool || pool_size > kMaxPool || pool_stride < kMinPool || pool_stride > kMaxPool) return AWARE_E_UNSUPPORTED;
+    if (pool_size == 2 && pool_stride == 2)
+        return aware_detector_create_conv(out, plan, mel_basis, n_mels, n_layers, channels, weights, biases, arch, kernel_size,
+                                          stride, padding);
+    if (kernel_size < 1 || stride < 1 || padding < 0) return AWARE_E_BADARG;
+    if (kernel_size > kMaxTapKernel || stride > kMaxTapStride || 2 * padding > kernel_size - 1) return AWARE_E_UNSUPPORTED;
+    if (!arch_ok(arch, n_layers)) return AWARE_E_BADARG;
+    return detector_create(out, plan, mel_basis, n_mels, n_layers, channels, weights, biases, arch, kernel_size, stride, padding,
+                           pool_size, pool_stride);
+}
+extern "C" int aware_detector_pool(const aware_detector* d, int* pool_size, int* pool_stride) {
+    if (!d) return AWARE_E_BADARG;
+    if (pool_size) *pool_size = d->psize;
+    if (pool_stride) *pool_stride = d->pstride;
+    return AWARE_OK;
+}
+extern "C" int aware_pool_rows(int frames, int pool_size, int pool_stride) {
+    if (frames < 0 || pool_size < 1 || pool_stride < 1) return AWARE_E_BADARG;
+    return pool_rows(frames, pool_size, pool_stride);
 }
 extern "C" int aware_detector_conv(const aware_detector* d, int* kernel_size, int* stride, int* padding) {
     if (!d) return AWARE_E_BADARG;
@@ -1160,7 +1200,7 @@ static DetPlan det_plan(const aware_detector* d, const aware_batch* b, int pipe,
     // block 0's data gradient
     bool same_T = true;
     for (int i = 1; i < b->B; ++i) same_T = same_T && b->T[i] == b->T[0];
-    const bool mel_front = pipe != 1 && d->n_mels == 128 && d->melTpk && same_T && b->B >= kMelFrontMinClips &&
+    const bool mel_front = !d->pooled && pipe != 1 && d->n_mels == 128 && d->melTpk && same_T && b->B >= kMelFrontMinClips &&
                            mel_front_x3_supported(b->T[0], d->stride, d->stride);
     p.mel = mel_folded ? MelFwd::Folded : mel_front ? MelFwd::Front : MelFwd::Gemm;
     p.mel_amax = p.mel == MelFwd::Front || (p.mel == MelFwd::Folded && pipe == 0 && nwm);
@@ -1262,8 +1302,12 @@ static int det_forward(const aware_detector* d, const aware_batch* b, const DetP
             gemm_plain(p.pipe, mag, d->stride, d->melT, d->stride, d->melTpk, nullptr, o.xm, Mp, b->NF, Mp, d->stride, st);
             LAUNCHCHK(); PROF(K_GEMM);
         }
-        launch_mel_norm_fwd(o.xm, b->d_frame_off, b->d_pool_off, o.x0, o.mstats, o.gstat, o.mpart, o.mstride, b->B, b->max_frames,
-                            d->n_mels, Mp, st, p.mel_amax ? o.amax[0] : nullptr);
+        if (d->pooled)      // any other initial pool: mel_pool_kernels.hip (no maxima: the staged route never asks for them)
+            launch_mel_pool_fwd(o.xm, b->d_frame_off, b->d_pool_off, o.x0, o.mstats, o.gstat, o.mpart, o.mstride, b->B,
+                                b->max_frames, d->n_mels, Mp, d->psize, d->pstride, st);
+        else
+            launch_mel_norm_fwd(o.xm, b->d_frame_off, b->d_pool_off, o.x0, o.mstats, o.gstat, o.mpart, o.mstride, b->B,
+                                b->max_frames, d->n_mels, Mp, st, p.mel_amax ? o.amax[0] : nullptr);
     }
     LAUNCHCHK(); PROF(K_MELNORM);
     const float* x = o.x0;
@@ -1311,7 +1355,8 @@ static int det_forward(const aware_detector* d, const aware_batch* b, const DetP
             // conv + bias, then the block's norm and activation (a variant's pre-activation kept in the stash)
             // temporal convolutions: the same GEMM on the unfolded rows (K = tk ci), the norm over the block's own rows
             if (d->taps) {
-                launch_conv_unfold(x, o.unf, b->d_frame_off, b->d_pool_off, ci, b->B, b->max_frames / 2, l, d->tk, d->ts, d->tp, st);
+                launch_conv_unfold(x, o.unf, b->d_frame_off, b->d_pool_off, ci, b->B, b->max_frames / 2, l, d->tk, d->ts, d->tp, st,
+                                   d->psize, d->pstride);
                 LAUNCHCHK(); PROF(K_MISC);
                 gemm_plain(p.pipe, o.unf, d->tk * ci, d->w[l], d->tk * ci, d->wpk[l], d->bias[l], o.act[l], co, b->NP, co,
                            d->tk * ci, st);
@@ -1377,7 +1422,7 @@ extern "C" size_t aware_detect_workspace_bytes(const aware_batch* b, const aware
 extern "C" int aware_detector_forward(const aware_detector* d, const aware_batch* b, const float* mag, float* values,
                                       void* workspace, size_t workspace_bytes, void* stream) {
     if (!d || !b || b->general || !mag || !values || !workspace) return AWARE_E_BADARG;
-    if (!det_clips_ok(d, b)) return AWARE_E_BADARG;           // a clip too short for the detector's temporal convolutions
+    if (!det_clips_ok(d, b)) return AWARE_E_BADARG;           // a clip too short for the detector's pool or temporal convolutions
     hipStream_t st = (hipStream_t)stream;
     Carver c(workspace, workspace_bytes);
     DetBufs o;
@@ -1399,7 +1444,7 @@ extern "C" int aware_detect(const aware_plan* plan, const aware_detector* d, con
     if (plan->general ? !gen_loop_matches(plan, b, d) : (b->general || d->general)) return AWARE_E_BADARG;
     // the magnitude rows are carved at the detector's stride and written at the plan's: one band layout
     if (d->band_lo != plan->dev.band_lo || d->nband != plan->dev.nband || d->stride != plan->dev.stride) return AWARE_E_BADARG;
-    if (!det_clips_ok(d, b)) return AWARE_E_BADARG;           // a clip too short for the detector's temporal convolutions
+    if (!det_clips_ok(d, b)) return AWARE_E_BADARG;           // a clip too short for the detector's pool or temporal convolutions
     hipStream_t st = (hipStream_t)stream;
     Carver c(workspace, workspace_bytes);
     DetBufs o;
@@ -1551,7 +1596,8 @@ static int det_forward_backward(const aware_detector* d, const aware_batch* b, c
             if (d->taps) {
                 gemm_plain(p.pipe, dA, co, d->wT[l], co, d->wTpk[l], nullptr, db.unf, d->tk * ci, b->NP, d->tk * ci, co, st);
                 LAUNCHCHK(); PROF(K_GEMM);
-                launch_conv_fold(db.unf, dB, b->d_frame_off, b->d_pool_off, ci, b->B, b->max_frames / 2, l, d->tk, d->ts, d->tp, st);
+                launch_conv_fold(db.unf, dB, b->d_frame_off, b->d_pool_off, ci, b->B, b->max_frames / 2, l, d->tk, d->ts, d->tp, st,
+                                 d->psize, d->pstride);
                 LAUNCHCHK(); PROF(K_MISC);
             } else {
                 gemm_plain(p.pipe, dA, co, d->wT[l], co, d->wTpk[l], nullptr, dB, ci, b->NP, ci, co, st);
@@ -1561,7 +1607,11 @@ static int det_forward_backward(const aware_detector* d, const aware_batch* b, c
         float* t = dA; dA = dB; dB = t;
     }
     const int Mp = d->ch[0];
-    if (p.bwd[0] != Conv::MelBack) {
+    if (d->pooled) {
+        launch_mel_pool_bwd(dA, db.xm, b->d_frame_off, b->d_pool_off, db.mstats, db.gstat, db.mpart, db.mstride, b->B,
+                            b->max_frames, d->n_mels, Mp, d->psize, d->pstride, st);
+        LAUNCHCHK(); PROF(K_MELNORM);
+    } else if (p.bwd[0] != Conv::MelBack) {
         launch_mel_norm_bwd(dA, db.xm, b->d_frame_off, b->d_pool_off, db.mstats, db.gstat, db.mpart, db.mstride, b->B,
                             b->max_frames, d->n_mels, Mp, st);
         LAUNCHCHK(); PROF(K_MELNORM);
@@ -1606,7 +1656,7 @@ extern "C" int aware_detector_backward(const aware_detector* d, const aware_batc
                                        const float* grad_values, float* values, float* grad_mag, void* workspace,
                                        size_t workspace_bytes, void* stream) {
     if (!d || !b || b->general || !mag || !grad_values || !grad_mag || !workspace) return AWARE_E_BADARG;
-    if (!det_clips_ok(d, b)) return AWARE_E_BADARG;           // a clip too short for the detector's temporal convolutions
+    if (!det_clips_ok(d, b)) return AWARE_E_BADARG;           // a clip too short for the detector's pool or temporal convolutions
     hipStream_t st = (hipStream_t)stream;
     Carver c(workspace, workspace_bytes);
     DetBufs o;
@@ -1888,7 +1938,7 @@ extern "C" int aware_embed_create(aware_embed** out, const aware_plan* plan, con
     if (cfg->dsp_path < 0 || cfg->dsp_path > 1 || cfg->conv_tile < 0 || cfg->conv_tile > 2) return AWARE_E_BADARG;
     // the detector's mel operands have the layout of the plan it was created for
     if (det->band_lo != plan->dev.band_lo || det->nband != plan->dev.nband || det->stride != plan->dev.stride) return AWARE_E_BADARG;
-    if (!det_clips_ok(det, b)) return AWARE_E_BADARG;         // a clip too short for the detector's temporal convolutions
+    if (!det_clips_ok(det, b)) return AWARE_E_BADARG;         // a clip too short for the detector's pool or temporal convolutions
     // the L1 term lives in the streaming DSP kernels only
     const bool l1 = cfg->loss == AWARE_LOSS_PUSH_L1;
     if (l1 && (plan->general || cfg->dsp_path != 0 || !stream_supported(plan->dev))) return AWARE_E_UNSUPPORTED;

@@ -10,14 +10,16 @@ namespace aware {
 constexpr int kTapRowsPerBlock = 8;
 
 // grid (row tiles of the longest clip, B), 256 threads: a tile of kTapRowsPerBlock rows of U, walked float4 by float4
+template <bool POOL>
 __global__ __launch_bounds__(256) void conv_unfold_kernel(const float* __restrict__ X, float* __restrict__ U,
                                                           const int* __restrict__ frame_off, const int* __restrict__ pool_off,
-                                                          int Cs, int layer, int k, int s, int p) {
+                                                          int Cs, int layer, int k, int s, int p, int psize, int pstride) {
     const int b = blockIdx.y;
     const int r0 = pool_off[b], rows = pool_off[b + 1] - r0;            // the clip's rows up to its 32-row boundary
     const int t0 = blockIdx.x * kTapRowsPerBlock;
     if (t0 >= rows) return;
-    const int L0 = (frame_off[b + 1] - frame_off[b]) / 2;
+    const int T = frame_off[b + 1] - frame_off[b];
+    const int L0 = POOL ? pool_rows(T, psize, pstride) : T / 2;
     const int Lin = conv_rows(L0, layer, k, s, p), Lout = conv_rows(L0, layer + 1, k, s, p);
     const int C4 = Cs >> 2, W4 = k * C4;
     const int nt = rows - t0 < kTapRowsPerBlock ? rows - t0 : kTapRowsPerBlock;
@@ -35,14 +37,16 @@ __global__ __launch_bounds__(256) void conv_unfold_kernel(const float* __restric
 
 // grid (row tiles of the longest clip, B), 256 threads: a tile of kTapRowsPerBlock rows of dX; every value the sum of at most
 // k values of dU, taken j ascending
+template <bool POOL>
 __global__ __launch_bounds__(256) void conv_fold_kernel(const float* __restrict__ dU, float* __restrict__ dX,
                                                         const int* __restrict__ frame_off, const int* __restrict__ pool_off,
-                                                        int Cs, int layer, int k, int s, int p) {
+                                                        int Cs, int layer, int k, int s, int p, int psize, int pstride) {
     const int b = blockIdx.y;
     const int r0 = pool_off[b], rows = pool_off[b + 1] - r0;
     const int q0 = blockIdx.x * kTapRowsPerBlock;
     if (q0 >= rows) return;
-    const int L0 = (frame_off[b + 1] - frame_off[b]) / 2;
+    const int T = frame_off[b + 1] - frame_off[b];
+    const int L0 = POOL ? pool_rows(T, psize, pstride) : T / 2;
     const int Lin = conv_rows(L0, layer, k, s, p), Lout = conv_rows(L0, layer + 1, k, s, p);
     const int C4 = Cs >> 2, W4 = k * C4;
     const int nq = rows - q0 < kTapRowsPerBlock ? rows - q0 : kTapRowsPerBlock;
@@ -71,15 +75,25 @@ static dim3 tap_grid(int B, int max_pooled) {
 }
 
 void launch_conv_unfold(const float* X, float* U, const int* frame_off, const int* pool_off, int Cs, int B, int max_pooled,
-                        int layer, int k, int s, int p, hipStream_t st) {
+                        int layer, int k, int s, int p, hipStream_t st, int psize, int pstride) {
     if (B < 1 || max_pooled < 1) return;
-    hipLaunchKernelGGL(conv_unfold_kernel, tap_grid(B, max_pooled), dim3(256), 0, st, X, U, frame_off, pool_off, Cs, layer, k, s, p);
+    if (psize != 2 || pstride != 2)
+        hipLaunchKernelGGL(conv_unfold_kernel<true>, tap_grid(B, max_pooled), dim3(256), 0, st, X, U, frame_off, pool_off, Cs, layer,
+                           k, s, p, psize, pstride);
+    else
+        hipLaunchKernelGGL(conv_unfold_kernel<false>, tap_grid(B, max_pooled), dim3(256), 0, st, X, U, frame_off, pool_off, Cs, layer,
+                           k, s, p, 2, 2);
 }
 
 void launch_conv_fold(const float* dU, float* dX, const int* frame_off, const int* pool_off, int Cs, int B, int max_pooled,
-                      int layer, int k, int s, int p, hipStream_t st) {
+                      int layer, int k, int s, int p, hipStream_t st, int psize, int pstride) {
     if (B < 1 || max_pooled < 1) return;
-    hipLaunchKernelGGL(conv_fold_kernel, tap_grid(B, max_pooled), dim3(256), 0, st, dU, dX, frame_off, pool_off, Cs, layer, k, s, p);
+    if (psize != 2 || pstride != 2)
+        hipLaunchKernelGGL(conv_fold_kernel<true>, tap_grid(B, max_pooled), dim3(256), 0, st, dU, dX, frame_off, pool_off, Cs, layer,
+                           k, s, p, psize, pstride);
+    else
+        hipLaunchKernelGGL(conv_fold_kernel<false>, tap_grid(B, max_pooled), dim3(256), 0, st, dU, dX, frame_off, pool_off, Cs, layer,
+                           k, s, p, 2, 2);
 }
 
 }  // namespace aware

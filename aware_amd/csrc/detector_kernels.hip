@@ -19,6 +19,7 @@
 #include "common.hpp"
 #include "kernels.h"
 #include "mel_norm.hpp"
+#include "mel_chunked.hpp"
 
 namespace aware {
 
@@ -543,18 +544,7 @@ void launch_gemm_nt(const float* A, int lda, const float* Bt, int ldb, const flo
 // ---------------------------------------------------------------------------------
 // block reductions
 // ---------------------------------------------------------------------------------
-// every wave's sum of v into red[wave]
-__device__ __forceinline__ void wave_partials(float v, float* red) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-}
-// 256 threads (the four partials in sequence: the pairwise order of mel_sum8 would change the bits of every caller)
-__device__ __forceinline__ float block_sum(float v, float* red) {
-    wave_partials(v, red);
-    return red[0] + red[1] + red[2] + red[3];
-}
+// (wave_partials and the 256-thread block_sum: mel_chunked.hpp)
 // 512 threads
 __device__ __forceinline__ float mel_block_sum(float v, float* red8) {
     wave_partials(v, red8);
@@ -574,16 +564,7 @@ __device__ __forceinline__ float mel_block_sum(float v, float* red8) {
 // constants; MelBankAny takes them at run time.  Row loops have a fixed trip count, loads first (clamped indices), stores
 // masked: no per-iteration load/wait chain.
 // ---------------------------------------------------------------------------------
-struct MelBank128 {
-    static constexpr int kGroups = 1;
-    static constexpr int n_mels = 128, Mp = 128, ng = 1;
-    __device__ MelBank128(int, int) {}
-};
-struct MelBankAny {
-    static constexpr int kGroups = 4;               // 128-channel groups: Mp <= 512
-    int n_mels, Mp, ng;
-    __device__ MelBankAny(int n_mels_, int Mp_) : n_mels(n_mels_), Mp(Mp_), ng((Mp_ + 127) / 128) {}
-};
+// (MelBank128 and MelBankAny: mel_chunked.hpp, shared with the pooled nets' kernels of mel_pool_kernels.hip)
 
 // per-chunk (mean, M2) of every channel
 template <class Bank>
@@ -855,17 +836,18 @@ __device__ __forceinline__ float act_grad(float u, float a) {
 
 // In place: u = norm(z), z = act(u), u -> stash (if given).  Workgroup = (64 channels) x (4 row groups) of one clip.
 // R > 0: InstanceNorm with the clip's column in registers (clips of up to 4 R pooled frames: the activation is read once and
-// written once); R = 0: from memory (any length; the only form of the element-wise norms).  TAPS: the rows are those of a
-// block of temporal convolutions (TapRows); off, the kernel never looks at `rows` -- the rule costs registers.
-template <int NORM, int ACT, int R, bool TAPS>
+// written once); R = 0: from memory (any length; the only form of the element-wise norms).  RULE: kRowsTaps, the rows are those
+// of a block of temporal convolutions (TapRows); kRowsPool, those behind an initial pool other than (2, 2) as well; kRowsHalf,
+// the kernel never looks at `rows` -- the rule costs registers.
+template <int NORM, int ACT, int R, int RULE>
 __global__ __launch_bounds__(256) void norm_act_fwd_kernel(float* __restrict__ z, const int* __restrict__ frame_off,
                                                            const int* __restrict__ pool_off, float* __restrict__ rstd,
                                                            const float* __restrict__ scale, const float* __restrict__ shift,
                                                            float* __restrict__ stash, int C, TapRows rows) {
     __shared__ float s[4][64];
     const int b = blockIdx.y, c0 = blockIdx.x * 64;
-    const int L0 = (frame_off[b + 1] - frame_off[b]) / 2;
-    const int r0 = pool_off[b], Tp = TAPS ? rows.of(L0) : L0;   // rows are 32-aligned per clip
+    const int L0 = rows_l0<RULE>(frame_off[b + 1] - frame_off[b], rows);
+    const int r0 = pool_off[b], Tp = RULE != kRowsHalf ? rows.of(L0) : L0;   // rows are 32-aligned per clip
     const int cl = threadIdx.x & 63, g = threadIdx.x >> 6, c = c0 + cl;
     if (Tp <= 0) return;
     const bool ok = c < C;
@@ -923,7 +905,7 @@ __global__ __launch_bounds__(256) void norm_act_fwd_kernel(float* __restrict__ z
 // backward of norm_act_fwd_kernel, in place on dA.  u from the stash where the block keeps one (norm_act_needs_stash, a
 // function of the policy alone), else from the output A: LeakyReLU inverted; ReLU after an element-wise norm as it is, since
 // its derivative only needs the sign of u.
-template <int NORM, int ACT, int R, bool TAPS>
+template <int NORM, int ACT, int R, int RULE>
 __global__ __launch_bounds__(256) void norm_act_bwd_kernel(float* __restrict__ dA, const float* __restrict__ A,
                                                            const float* __restrict__ stash, const int* __restrict__ frame_off,
                                                            const int* __restrict__ pool_off, const float* __restrict__ rstd,
@@ -931,8 +913,8 @@ __global__ __launch_bounds__(256) void norm_act_bwd_kernel(float* __restrict__ d
     constexpr bool kStash = norm_act_needs_stash(NORM, ACT);
     __shared__ float s1[4][64], s2[4][64];
     const int b = blockIdx.y, c0 = blockIdx.x * 64;
-    const int L0 = (frame_off[b + 1] - frame_off[b]) / 2;
-    const int r0 = pool_off[b], Tp = TAPS ? rows.of(L0) : L0;   // rows are 32-aligned per clip
+    const int L0 = rows_l0<RULE>(frame_off[b + 1] - frame_off[b], rows);
+    const int r0 = pool_off[b], Tp = RULE != kRowsHalf ? rows.of(L0) : L0;   // rows are 32-aligned per clip
     const int cl = threadIdx.x & 63, g = threadIdx.x >> 6, c = c0 + cl;
     if (Tp <= 0) return;
     const bool ok = c < C;
@@ -1015,21 +997,24 @@ __global__ __launch_bounds__(256) void norm_act_bwd_kernel(float* __restrict__ d
 }
 
 // the instantiation a launch takes: the policy from L.norm / L.act, the form from the batch's longest clip (the register
-// forms are InstanceNorm's alone), TAPS from the rows
-template <int NORM, int ACT, int R, bool TAPS>
+// forms are InstanceNorm's alone), the rule from the rows
+template <int NORM, int ACT, int R, int RULE>
 static void norm_act_go(const NormActLaunch& L, bool backward, hipStream_t st) {
     const dim3 grid((L.C + 63) / 64, L.B), block(256);
     if (backward)
-        hipLaunchKernelGGL((norm_act_bwd_kernel<NORM, ACT, R, TAPS>), grid, block, 0, st, L.x, L.out, L.stash, L.frame_off,
+        hipLaunchKernelGGL((norm_act_bwd_kernel<NORM, ACT, R, RULE>), grid, block, 0, st, L.x, L.out, L.stash, L.frame_off,
                            L.pool_off, L.rstd, L.scale, L.C, L.rows);
     else
-        hipLaunchKernelGGL((norm_act_fwd_kernel<NORM, ACT, R, TAPS>), grid, block, 0, st, L.x, L.frame_off, L.pool_off, L.rstd,
+        hipLaunchKernelGGL((norm_act_fwd_kernel<NORM, ACT, R, RULE>), grid, block, 0, st, L.x, L.frame_off, L.pool_off, L.rstd,
                            L.scale, L.shift, L.stash, L.C, L.rows);
 }
 template <int NORM, int ACT, int R>
 static void norm_act_rows(const NormActLaunch& L, bool backward, hipStream_t st) {
-    if (L.rows.layer != 0) norm_act_go<NORM, ACT, R, true>(L, backward, st);
-    else norm_act_go<NORM, ACT, R, false>(L, backward, st);
+    switch (rows_rule(L.rows)) {
+        case kRowsPool: norm_act_go<NORM, ACT, R, kRowsPool>(L, backward, st); break;
+        case kRowsTaps: norm_act_go<NORM, ACT, R, kRowsTaps>(L, backward, st); break;
+        default: norm_act_go<NORM, ACT, R, kRowsHalf>(L, backward, st);
+    }
 }
 template <int NORM, int ACT>
 static void norm_act_form(const NormActLaunch& L, bool backward, hipStream_t st) {
@@ -1060,7 +1045,7 @@ void launch_norm_act(const NormActLaunch& L, bool backward, hipStream_t st) {
 // FA: the final activation (act_fwd / act_grad; the model card's tanh is written out as it always was).
 // If dA3 == nullptr only the prediction is produced (detect path).
 // ---------------------------------------------------------------------------------
-template <int FA>
+template <int FA, bool POOL>
 __global__ __launch_bounds__(256) void head_kernel(const float* __restrict__ a3, const int* __restrict__ frame_off, const int* __restrict__ pool_off,
                                                     const float* __restrict__ target, float* __restrict__ pred,
                                                     float* __restrict__ loss_out, float* __restrict__ best_loss,
@@ -1071,7 +1056,8 @@ __global__ __launch_bounds__(256) void head_kernel(const float* __restrict__ a3,
     // their dA3 is zero)
     __shared__ float part[4][64], mean[64], dm[64];
     const int b = blockIdx.x, c = threadIdx.x & 63, g = threadIdx.x >> 6;
-    const int r0 = pool_off[b], Tp = rows.of((frame_off[b + 1] - frame_off[b]) / 2);   // rows are 32-aligned per clip
+    // rows are 32-aligned per clip (POOL: an initial pool other than (2, 2))
+    const int r0 = pool_off[b], Tp = rows.of(rows_l0<POOL ? kRowsPool : kRowsHalf>(frame_off[b + 1] - frame_off[b], rows));
     float m = 0.f;
     if (c < C)
         for (int t = g; t < Tp; t += 4) m += a3[(size_t)(r0 + t) * C + c];
@@ -1261,7 +1247,7 @@ void launch_tail(const float* zpart, int nsplit, size_t slab, const float* bias,
 // ---------------------------------------------------------------------------------
 constexpr int kWideNJ = 4;
 constexpr int kWideMaxC = 1024;
-template <int FA, int MODE>
+template <int FA, int MODE, bool POOL>
 __global__ __launch_bounds__(256) void readout_wide_kernel(const float* __restrict__ A, int Cp, const int* __restrict__ frame_off,
                                                             const int* __restrict__ pool_off, const float* __restrict__ rstd,
                                                             const float* __restrict__ target, float* __restrict__ pred,
@@ -1274,7 +1260,8 @@ __global__ __launch_bounds__(256) void readout_wide_kernel(const float* __restri
     const int b = blockIdx.x, tid = threadIdx.x;
     const int CW = Cp < 256 ? Cp : 256, NG = 256 / CW;
     const int cl = tid % CW, g = tid / CW;
-    const int r0 = pool_off[b], Tp = rows.of((frame_off[b + 1] - frame_off[b]) / 2);   // rows are 32-aligned per clip
+    // rows are 32-aligned per clip (POOL: an initial pool other than (2, 2))
+    const int r0 = pool_off[b], Tp = rows.of(rows_l0<POOL ? kRowsPool : kRowsHalf>(frame_off[b + 1] - frame_off[b], rows));
     const int C = 2 * nbits;
     const float invT = 1.0f / (float)Tp;
     float sa[kWideNJ], sl[kWideNJ], slu[kWideNJ];
@@ -1403,11 +1390,18 @@ void launch_readout_wide(const float* A, int Cp, const int* frame_off, const int
                          int loss_kind, int nbits, int B, hipStream_t st, const float* loss_add, int final_act, bool card_bwd,
                          TapRows rows) {
     const int mode = !target ? 0 : (card_bwd ? 2 : 1);
-#define AW_WIDE(FA, M)                                                                                                       \
-    hipLaunchKernelGGL((readout_wide_kernel<FA, M>), dim3(B), dim3(256), 0, st, A, Cp, frame_off, pool_off, rstd, target, pred, \
+    // (a detector with an initial pool other than (2, 2) is never the card's: its instantiations are modes 0 and 1 alone)
+    const bool pool = rows.pooled();
+#define AW_WIDE(FA, M, P)                                                                                                    \
+    hipLaunchKernelGGL((readout_wide_kernel<FA, M, P>), dim3(B), dim3(256), 0, st, A, Cp, frame_off, pool_off, rstd, target, pred, \
                        loss, best_loss, improved, dout, gmax, step, loss_kind, nbits, loss_add, rows)
-#define AW_WIDE_FA(FA) \
-    do { if (mode == 0) AW_WIDE(FA, 0); else if (mode == 1) AW_WIDE(FA, 1); else AW_WIDE(FA, 2); } while (0)
+#define AW_WIDE_FA(FA)                                                                     \
+    do {                                                                                   \
+        if (pool) { if (mode == 0) AW_WIDE(FA, 0, true); else AW_WIDE(FA, 1, true); }      \
+        else if (mode == 0) AW_WIDE(FA, 0, false);                                         \
+        else if (mode == 1) AW_WIDE(FA, 1, false);                                         \
+        else AW_WIDE(FA, 2, false);                                                        \
+    } while (0)
     switch (final_act) {
         case kActRelu: AW_WIDE_FA(kActRelu); break;
         case kActLRelu: AW_WIDE_FA(kActLRelu); break;
@@ -1681,6 +1675,16 @@ static void mel_chunked_bwd(const float* dx0, float* xm, const int* frame_off, c
                        pstride, n_mels, Mp);
 }
 
+// the chunked form's first launch on its own, for the pooled nets' kernels (mel_pool_kernels.hip), which share it
+void launch_mel_partial_stats(const float* xm, const int* frame_off, float* part, int pstride, int B, int max_frames, int n_mels,
+                              int Mp, hipStream_t st) {
+    const dim3 grid((max_frames + kMelChunk - 1) / kMelChunk, B);
+    if (n_mels == 128)
+        hipLaunchKernelGGL(mel_partial_stats_kernel<MelBank128>, grid, dim3(256), 0, st, xm, frame_off, part, pstride, n_mels, Mp);
+    else
+        hipLaunchKernelGGL(mel_partial_stats_kernel<MelBankAny>, grid, dim3(256), 0, st, xm, frame_off, part, pstride, n_mels, Mp);
+}
+
 // One launcher per direction: the clip form up to kMelClipFrames frames, else the chunked two-launch form; the 128-band
 // instantiations for the card's bank, else the any-bank ones.  n_mels <= 512 bands in rows of Mp >= n_mels floats
 // (Mp % 4 == 0); stats [B][Mp][4], part [B][pstride][2 Mp].
@@ -1718,9 +1722,10 @@ void launch_head(const float* a3, const int* frame_off, const int* pool_off, con
                  float* best_loss, int* improved, float* dA3, int* step, int loss_kind, int nbits, int B,
                  hipStream_t st, const float* loss_add, int final_act, int C, TapRows rows) {
     if (C < 2 * nbits) C = 2 * nbits;
-#define AW_HEAD(FA)                                                                                                         \
-    hipLaunchKernelGGL(head_kernel<FA>, dim3(B), dim3(256), 0, st, a3, frame_off, pool_off, target, pred, loss, best_loss, improved, \
-                       dA3, step, loss_kind, nbits, loss_add, C, rows)
+#define AW_HEAD_P(FA, P)                                                                                                    \
+    hipLaunchKernelGGL((head_kernel<FA, P>), dim3(B), dim3(256), 0, st, a3, frame_off, pool_off, target, pred, loss, best_loss, \
+                       improved, dA3, step, loss_kind, nbits, loss_add, C, rows)
+#define AW_HEAD(FA) do { if (rows.pooled()) AW_HEAD_P(FA, true); else AW_HEAD_P(FA, false); } while (0)
     switch (final_act) {
         case kActRelu: AW_HEAD(kActRelu); break;
         case kActLRelu: AW_HEAD(kActLRelu); break;
@@ -1730,6 +1735,7 @@ void launch_head(const float* a3, const int* frame_off, const int* pool_off, con
         default: AW_HEAD(kActTanh); break;
     }
 #undef AW_HEAD
+#undef AW_HEAD_P
 }
 
 }  // namespace aware

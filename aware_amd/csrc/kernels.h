@@ -204,6 +204,14 @@ void launch_mel_norm_fwd(const float* xm, const int* frame_off, const int* pool_
                          float* amax_out = nullptr);
 void launch_mel_norm_bwd(const float* dx0, float* xm_inout, const int* frame_off, const int* pool_off, const float* stats,
                          const float* gstat, float* part, int pstride, int B, int max_frames, int n_mels, int Mp, hipStream_t st);
+// ---- mel_pool_kernels.hip: the same stage for a detector with an initial pool other than (2, 2) -- AvgPool1d(size, stride),
+// size and stride kMinPool..kMaxPool (conv_taps.hpp: pool_rows).  Same buffers; clips of every length take the chunked form
+// (part is always written); x0 rows pool_rows(T) .. the clip's 32-row boundary are written as zeros
+void launch_mel_pool_fwd(const float* xm, const int* frame_off, const int* pool_off, float* x0, float* stats, float* gstat,
+                         float* part, int pstride, int B, int max_frames, int n_mels, int Mp, int size, int stride, hipStream_t st);
+void launch_mel_pool_bwd(const float* dx0, float* xm_inout, const int* frame_off, const int* pool_off, const float* stats,
+                         const float* gstat, float* part, int pstride, int B, int max_frames, int n_mels, int Mp, int size,
+                         int stride, hipStream_t st);
 // ---- architecture variants of the detector (aware_detector_arch; the values are the header's AWARE_ACT_* / AWARE_NORM_* /
 // AWARE_FINAL_*): the norm and activation of every conv block and the read-out's final activation
 constexpr int kActRelu = 0, kActLRelu = 1, kActGelu = 2, kActSwish = 3, kActTanh = 4, kActSigmoid = 5;

@@ -27,7 +27,9 @@ class AWAREDetector(BaseDetector):
                  general_geometry: bool = False, shift_search=None):
         """general_geometry (EXTENSION): detect at any frame_length in runtime.GENERAL_NFFT, any
         hop_length and win_length in 1..frame_length, on the general route; off: the card geometry only.  With it sync_search,
-        speed_search, shift_search and scan raise NotImplementedError (their offsets assume the card's 512-sample pooling period)."""
+        speed_search, shift_search and scan raise NotImplementedError (their offsets assume the card's 512-sample pooling period).
+        The same four refuse a detection net whose initial pool is not (2, 2) (key initial_pools), here
+        and per call: its read-out period is 256 * initial_pool_stride samples."""
         self.general_geometry = bool(general_geometry)
         rt.require_card_geometry("AWAREDetector", frame_length, hop_length, win_length, self.general_geometry, window)
         self.sync_search = sync.check_sync_search(sync_search)
@@ -41,6 +43,10 @@ class AWAREDetector(BaseDetector):
             rt.refuse_general_geometry("shift_search")
         if self.speed_search is not None and self.shift_search is not None:
             raise ValueError("AWAREDetector: speed_search and shift_search are both on; the product of the two grids is not served")
+        self.detection_net = model
+        self._refuse_pool(self.sync_search, self.speed_search, self.shift_search)
+        if scan is not None:
+            self._refuse_pool(scan=True)
         if self.general_geometry and model is not None and getattr(model, "n_fft", frame_length) != frame_length:
             raise ValueError(f"AWAREDetector: the detection net's n_fft = {model.n_fft} but frame_length = {frame_length}; "
                              f"with general_geometry the detector's mel bank follows the STFT")
@@ -78,8 +84,19 @@ class AWAREDetector(BaseDetector):
                                embed=False)
         return rt.Batch(list(lengths), plan=self._plan(sample_rate))
 
+    def _refuse_pool(self, n: int = 0, speed=None, shift=None, scan: bool = False):
+        """NotImplementedError where a search is on and the net's initial pool is not (2, 2)."""
+        pool = tuple(getattr(self.detection_net, "pool", (2, 2)))
+        if pool == (2, 2):
+            return
+        for on, what in ((n, "sync_search"), (speed is not None, "speed_search"), (shift is not None, "shift_search"),
+                         (scan, "scan")):
+            if on:
+                rt.refuse_initial_pool(what, pool)
+
     def _check_tap_clips(self, lengths):
-        """A net of temporal convolutions: ValueError naming the first clip that some block leaves without a row."""
+        """A net of temporal convolutions or with another initial pool: ValueError naming the first clip that the pool or some
+        block leaves without a row."""
         check = getattr(self.detection_net, "check_clip_frames", None)
         if check is not None:
             check("AWAREDetector", [1 + int(n) // self.hop_length for n in lengths])
@@ -132,6 +149,7 @@ class AWAREDetector(BaseDetector):
             rt.refuse_general_geometry("shift_search")
         if speed is not None and shift is not None:
             raise ValueError("AWAREDetector: speed_search and shift_search are both on; the product of the two grids is not served")
+        self._refuse_pool(n, speed, shift)
         if self.general_geometry:                                 # ValueError naming the clip, before any plan or launch
             rt.check_general_clips("AWAREDetector", self.frame_length, self.hop_length, self.win_length, self.window,
                                    [len(c) for c in clips], embed=False)
@@ -252,6 +270,7 @@ class AWAREDetector(BaseDetector):
         shift_search on."""
         if self.general_geometry:
             rt.refuse_general_geometry("scan")
+        self._refuse_pool(scan=True)
         if self.speed_search is not None:
             raise ValueError("scan: speed_search is on for this detector; scanning at candidate speeds is not supported")
         if self.shift_search is not None:

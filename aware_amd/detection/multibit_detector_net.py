@@ -1,7 +1,8 @@
 """AWAREDetectorNet: frozen, seed-initialised detector (mel -> InstanceNorm -> global standardise
 -> pool -> (num_blocks + 1) x [conv1d, norm, activation] -> bitwise read-out head with its final activation).
 The model card's convolutions are 1x1; with the key temporal_convs every block is Conv1d(kernel_size, stride, padding)
-along the pooled frames (aware_detector_create_conv).
+along the pooled frames (aware_detector_create_conv), and with the key initial_pools the pool is
+AvgPool1d(initial_pool_size, initial_pool_stride) for sizes and strides 2..8 (aware_detector_create_pool).
 
 The model card's blocks are InstanceNorm + LeakyReLU with a tanh read-out; the other choices of the
 reference's detection_net_cfg (activation, norm_layer, final_activation; modules/conv1d.py:8-36,
@@ -17,7 +18,7 @@ import numpy as np
 import torch
 
 from ..interfaces import BaseDetectorNet
-from ..runtime import check_tap_clips, conv_rows
+from ..runtime import check_tap_clips, conv_rows, pool_rows
 from .mel import mel_filter_bank
 
 DETECTOR_SEED = 328656719      # multibit_detector_net.py:78
@@ -62,6 +63,10 @@ MAX_NUM_BLOCKS = 32
 # block is longer than its input
 MAX_KERNEL_SIZE = 7
 MAX_STRIDE = 4
+# the initial pools aware_detector_create_pool takes (key initial_pools), size and stride alike.  From 2 on a clip of T frames
+# has at most T // 2 pooled rows, what every batch allocates; a size or stride of 1 can give more
+MIN_POOL = 2
+MAX_POOL = 8
 
 
 class AWAREDetectorNet(BaseDetectorNet):
@@ -69,8 +74,11 @@ class AWAREDetectorNet(BaseDetectorNet):
                  initial_pool_size: int = 2, initial_pool_stride: int = 2, num_blocks: int = 3,
                  n_filters=(512, 1024, 1024), kernel_size: int = 1, stride: int = 1, padding: int = 0,
                  norm_layer: str = "instance", activation: str = "leaky_relu", output_length: int = 20,
-                 final_activation: str = "tanh", temporal_convs: bool = False):
-        """temporal_convs (EXTENSION; `temporal_convs: true` in the card): serve kernel_size 1..7,
+                 final_activation: str = "tanh", temporal_convs: bool = False, initial_pools: bool = False):
+        """initial_pools (EXTENSION; `initial_pools: true` in the card): serve initial_pool_size 2..8 and
+        initial_pool_stride 2..8 in any combination.  Off, anything but (2, 2) raises NotImplementedError; on with (2, 2) the
+        net is the same net on the same kernels.
+        temporal_convs (EXTENSION; `temporal_convs: true` in the card): serve kernel_size 1..7,
         stride 1..4 and padding with 2 * padding <= kernel_size - 1 in every block.  Off, anything but 1 / 1 / 0 raises
         NotImplementedError; on with 1 / 1 / 0 the net is the same net on the same kernels."""
         n_filters = list(n_filters)
@@ -84,8 +92,10 @@ class AWAREDetectorNet(BaseDetectorNet):
         if (kernel_size, stride, padding) != (1, 1, 0) and not self.temporal_convs:
             unsupported.append("kernel_size/stride/padding other than 1/1/0 (served with the key temporal_convs: "
                                "temporal_convs=True, or `temporal_convs: true` in the card)")
-        if (initial_pool_size, initial_pool_stride) != (2, 2):
-            unsupported.append("initial pool other than (2, 2)")
+        self.initial_pools = bool(initial_pools)
+        if (initial_pool_size, initial_pool_stride) != (2, 2) and not self.initial_pools:
+            unsupported.append("initial pool other than (2, 2) (served with the key initial_pools: initial_pools=True, or "
+                               "`initial_pools: true` in the card)")
         if unsupported:
             raise NotImplementedError("the HIP detector implements 1x1 convolutions after a (2, 2) pool only: " + "; ".join(unsupported))
         if self.temporal_convs:
@@ -101,6 +111,17 @@ class AWAREDetectorNet(BaseDetectorNet):
                 raise NotImplementedError(f"padding = {padding} with kernel_size = {kernel_size}: temporal_convs serves "
                                           "2 * padding <= kernel_size - 1 (no block longer than its input)")
         self.kernel_size, self.stride, self.padding = kernel_size, stride, padding
+        if self.initial_pools:
+            initial_pool_size, initial_pool_stride = int(initial_pool_size), int(initial_pool_stride)
+            if initial_pool_size < 1 or initial_pool_stride < 1:
+                raise ValueError(f"initial_pool_size / initial_pool_stride = {initial_pool_size} / {initial_pool_stride}: both "
+                                 "must be positive")
+            if not MIN_POOL <= initial_pool_size <= MAX_POOL:
+                raise NotImplementedError(f"initial_pool_size = {initial_pool_size}: initial_pools serves initial_pool_size "
+                                          f"{MIN_POOL}..{MAX_POOL}")
+            if not MIN_POOL <= initial_pool_stride <= MAX_POOL:
+                raise NotImplementedError(f"initial_pool_stride = {initial_pool_stride}: initial_pools serves "
+                                          f"initial_pool_stride {MIN_POOL}..{MAX_POOL}")
         if n_mels < 1 or num_blocks < 0 or any(f < 1 for f in n_filters) or output_length < 1:
             raise ValueError(f"detector sizes must be positive: n_mels = {n_mels}, num_blocks = {num_blocks}, "
                              f"n_filters = {n_filters}, output_length = {output_length}")
@@ -116,6 +137,7 @@ class AWAREDetectorNet(BaseDetectorNet):
                                       f"{MAX_OUTPUT_LENGTH} bits (a last block of at most {2 * MAX_OUTPUT_LENGTH} channels)")
         self.sample_rate, self.n_fft, self.n_mels = sample_rate, n_fft, n_mels
         self.num_blocks, self.initial_pool_size, self.output_length = num_blocks, initial_pool_size, output_length
+        self.initial_pool_stride = initial_pool_stride
         self.channels = [n_mels] + n_filters + [2 * output_length]
         self.mel_basis = mel_filter_bank(sample_rate, n_fft, n_mels)
         # torch.manual_seed(seed); self.apply(_init_weights): xavier-uniform on each Conv1d weight
@@ -146,19 +168,34 @@ class AWAREDetectorNet(BaseDetectorNet):
         return (self.kernel_size, self.stride, self.padding) != (1, 1, 0)
 
     @property
+    def pool(self) -> tuple:
+        """(initial_pool_size, initial_pool_stride)."""
+        return (self.initial_pool_size, self.initial_pool_stride)
+
+    @property
+    def has_pool(self) -> bool:
+        """Whether the initial pool is anything but the model card's (2, 2)."""
+        return self.pool != (2, 2)
+
+    @property
     def is_card_arch(self) -> bool:
         """Whether the blocks and the read-out are the model card's (the fused kernels); else the staged route, which a net
-        of temporal convolutions always takes."""
-        return (self.activation, self.norm_layer, self.final_activation) == CARD_ARCH and not self.has_taps
+        of temporal convolutions or with another initial pool always takes."""
+        return ((self.activation, self.norm_layer, self.final_activation) == CARD_ARCH and not self.has_taps
+                and not self.has_pool)
+
+    def pooled_rows(self, frames: int) -> int:
+        """L_0: the rows a clip of `frames` STFT frames enters block 0 with (runtime.pool_rows)."""
+        return pool_rows(int(frames), *self.pool)
 
     def block_rows(self, pooled_rows: int) -> list:
         """[L_0 .. L_{num_blocks + 1}]: the rows of a clip of L_0 pooled rows behind every block."""
         return [conv_rows(int(pooled_rows), i, self.kernel_size, self.stride, self.padding) for i in range(len(self.channels))]
 
     def check_clip_frames(self, who: str, frames):
-        """ValueError naming the first clip (of `frames` STFT frames each) that some block leaves without a row, where
-        torch's conv1d raises too; a net of 1x1 convolutions takes every clip."""
-        check_tap_clips(who, frames, len(self.channels) - 1, (self.kernel_size, self.stride, self.padding))
+        """ValueError naming the first clip (of `frames` STFT frames each) that the pool or some block leaves without a row,
+        where torch's avg_pool1d / conv1d raise too; a net of 1x1 convolutions after the (2, 2) pool takes every clip."""
+        check_tap_clips(who, frames, len(self.channels) - 1, (self.kernel_size, self.stride, self.padding), self.pool)
 
     def architecture(self):
         """The aware_detector_arch of this network: enum values, and for BatchNorm the folded eval-mode map
@@ -200,7 +237,8 @@ class AWAREDetectorNet(BaseDetectorNet):
         from ..runtime import DetectorWeights
         if self._dev is None or self._dev.plan is not plan:
             conv = (self.kernel_size, self.stride, self.padding) if self.has_taps else None
-            self._dev = DetectorWeights(plan, self.mel_basis, self.weights, self.biases, arch=self.architecture(), conv=conv)
+            self._dev = DetectorWeights(plan, self.mel_basis, self.weights, self.biases, arch=self.architecture(), conv=conv,
+                                        pool=self.pool if self.has_pool else None)
         return self._dev
 
     def forward(self, stft_magnitude: torch.Tensor) -> torch.Tensor:
@@ -217,7 +255,8 @@ class AWAREDetectorNet(BaseDetectorNet):
                 "num_blocks": self.num_blocks, "output_length": self.output_length,
                 "activation": self.activation, "norm_layer": self.norm_layer,
                 "final_activation": self.final_activation, "kernel_size": self.kernel_size, "stride": self.stride,
-                "padding": self.padding, "total_parameters": total, "trainable_parameters": 0}
+                "padding": self.padding, "initial_pool_size": self.initial_pool_size,
+                "initial_pool_stride": self.initial_pool_stride, "total_parameters": total, "trainable_parameters": 0}
 
 
 def _frames_batch(B, T):

@@ -30,7 +30,7 @@ class AWAREEmbedder(BaseEmbedder):
                  num_iterations: int = 400, detection_net_cfg: dict = None, optimizer_cfg: dict = None,
                  scheduler_cfg: dict = None, loss: str = "push", verbose: bool = True, use_graph: bool = True,
                  loop_attacks=None, loop_attack_seed: int = 0, loop_attack_mixture=None, payload_code=None,
-                 general_geometry: bool = False, temporal_convs: bool = False):
+                 general_geometry: bool = False, temporal_convs: bool = False, initial_pools: bool = False):
         """loop_attacks (EXTENSION, see embedding/loop_attacks.py): a chain of attacks applied inside the optimisation loop,
         e.g. [{"kind": "gaussian_noise", "snr_db": 10.0}, {"kind": "sample_suppression", "seconds": 0.3, "prob": 0.75}];
         clip i of a batch draws with seed loop_attack_seed + i.  None: the reference's loop (clean synthesis only).
@@ -44,7 +44,9 @@ class AWAREEmbedder(BaseEmbedder):
         geometry only, on the card kernels.  With it, loop_attacks, loop_attack_mixture and the loss push_extremes_l1 raise
         NotImplementedError, and detection_net_cfg.n_fft has to equal frame_length.
         temporal_convs (EXTENSION): handed to the detection net built from detection_net_cfg, where it
-        opens kernel_size / stride / padding other than 1 / 1 / 0 (AWAREDetectorNet); off: 1x1 convolutions only."""
+        opens kernel_size / stride / padding other than 1 / 1 / 0 (AWAREDetectorNet); off: 1x1 convolutions only.
+        initial_pools (EXTENSION): handed to the detection net in the same way, where it opens
+        initial_pool_size / initial_pool_stride 2..8; off: the (2, 2) pool only."""
         self.general_geometry = bool(general_geometry)
         rt.require_card_geometry("AWAREEmbedder", frame_length, hop_length, win_length, self.general_geometry, window)
         self.frame_length, self.hop_length, self.window, self.win_length = frame_length, hop_length, window, win_length
@@ -57,6 +59,9 @@ class AWAREEmbedder(BaseEmbedder):
         net_cfg = dict(detection_net_cfg or {})
         if self.temporal_convs:
             net_cfg["temporal_convs"] = True
+        self.initial_pools = bool(initial_pools)
+        if self.initial_pools:
+            net_cfg["initial_pools"] = True
         self.detection_net = AWAREDetectorNet(**net_cfg)
         self.detection_net.embedding_bands = self.embedding_bands
         if self.general_geometry and self.detection_net.n_fft != frame_length:

@@ -148,6 +148,15 @@ def check_general_clips(who: str, n_fft: int, hop: int, win_length: int, window:
                              f"second STFT needs more than n_fft/2 = {n_fft // 2}")
 
 
+def refuse_initial_pool(feature: str, pool):
+    """What a detector with an initial pool other than (2, 2) does not serve: the searches, whose offsets and minimum lengths
+    are built on the 512-sample period of the (2, 2) pool (hop 256 times the pool's stride).  NotImplementedError naming the
+    feature and the pool."""
+    raise NotImplementedError(f"{feature} is not supported with the initial pool (size {pool[0]}, stride {pool[1]}): its "
+                              f"offsets assume the 512-sample read-out period of the (2, 2) pool, and this detector's is "
+                              f"{256 * pool[1]} samples")
+
+
 def conv_rows(rows: int, blocks: int, kernel_size: int, stride: int, padding: int) -> int:
     """Rows left of `rows` pooled rows behind `blocks` blocks of a detector of temporal convolutions: L -> floor((L + 2 p -
     k) / s) + 1 per block, 0 once a block has no output row (torch's conv1d raises there).  Mirror of conv_rows in
@@ -158,15 +167,27 @@ def conv_rows(rows: int, blocks: int, kernel_size: int, stride: int, padding: in
     return rows
 
 
-def check_tap_clips(who: str, frames, blocks: int, conv):
-    """The clips a detector of `blocks` blocks with conv = (kernel_size, stride, padding) takes, checked on the host before any
-    launch: ValueError naming the first clip (of `frames` STFT frames each) that some block leaves without a row.  The C ABI
-    returns AWARE_E_BADARG for such a batch.  1x1 convolutions take every clip."""
+def pool_rows(frames: int, size: int, stride: int) -> int:
+    """Rows a clip of `frames` STFT frames enters block 0 with, behind the detector's initial pool AvgPool1d(size, stride):
+    floor((frames - size) / stride) + 1, and 0 for frames < size (torch's avg_pool1d raises there).  pool_rows(T, 2, 2) ==
+    T // 2.  Mirror of pool_rows in csrc/conv_taps.hpp (aware_pool_rows)."""
+    return 0 if frames < size else (frames - size) // stride + 1
+
+
+def check_tap_clips(who: str, frames, blocks: int, conv, pool=(2, 2)):
+    """The clips a detector of `blocks` blocks with conv = (kernel_size, stride, padding) behind the initial pool = (size,
+    stride) takes, checked on the host before any launch: ValueError naming the first clip (of `frames` STFT frames each) that
+    the pool or some block leaves without a row.  The C ABI returns AWARE_E_BADARG for such a batch.  1x1 convolutions after
+    the (2, 2) pool take every clip."""
     k, s, p = conv
-    if (k, s, p) == (1, 1, 0):
+    pool = tuple(pool)
+    if (k, s, p) == (1, 1, 0) and pool == (2, 2):
         return
     for i, t in enumerate(int(x) for x in frames):
-        rows = [conv_rows(t // 2, j, k, s, p) for j in range(blocks + 1)]
+        rows = [conv_rows(pool_rows(t, *pool), j, k, s, p) for j in range(blocks + 1)]
+        if rows[0] < 1:
+            raise ValueError(f"{who}: clip {i} has {t} frames, and the initial pool of the detector (size {pool[0]}, stride "
+                             f"{pool[1]}) leaves 0 rows of them: it needs at least {pool[0]} frames")
         if rows[-1] < 1:
             blk = next(j for j in range(1, blocks + 1) if rows[j] < 1)
             raise ValueError(f"{who}: clip {i} has {rows[0]} pooled rows ({t} frames), and block {blk - 1} of the detector "
@@ -496,10 +517,12 @@ def detector_train_gradients(plan: Plan, det: "DetectorWeights", batch: Batch, m
 class DetectorWeights:
     """Device copy of the frozen detector (aware_detector)."""
 
-    def __init__(self, plan: Plan, mel_basis: np.ndarray, weights, biases, arch: dict = None, conv=None):
+    def __init__(self, plan: Plan, mel_basis: np.ndarray, weights, biases, arch: dict = None, conv=None, pool=None):
         """arch: AWAREDetectorNet.architecture() (aware_detector_create_ex), or None for the model card's network.
         conv: (kernel_size, stride, padding) of a net of temporal convolutions, weights [cout, cin, kernel_size] per block
-        (aware_detector_create_conv; needs arch), or None for 1x1 convolutions."""
+        (aware_detector_create_conv; needs arch), or None for 1x1 convolutions.
+        pool: (initial_pool_size, initial_pool_stride) of a net with another initial pool (aware_detector_create_pool; needs
+        arch), or None for the (2, 2) pool."""
         require_gpu()
         self.lib = load_library()
         self.plan = plan
@@ -515,8 +538,11 @@ class DetectorWeights:
         bp = (C.c_void_p * nl)(*[b.ctypes.data for b in bs])
         h = C.c_void_p()
         self.conv = tuple(int(v) for v in conv) if conv is not None else (1, 1, 0)
+        self.pool = tuple(int(v) for v in pool) if pool is not None else (2, 2)
         if conv is not None and arch is None:
             raise ValueError("DetectorWeights: conv needs arch (aware_detector_create_conv)")
+        if pool is not None and arch is None:
+            raise ValueError("DetectorWeights: pool needs arch (aware_detector_create_pool)")
         if any(w.ndim != (3 if conv is not None else 2) or (conv is not None and w.shape[2] != self.conv[0]) for w in ws):
             raise ValueError("DetectorWeights: weights are [cout, cin] per block, or [cout, cin, kernel_size] with conv")
         if arch is None:
@@ -529,7 +555,11 @@ class DetectorWeights:
                 self._norm = [np.ascontiguousarray(v, dtype=np.float32) for v in list(arch["scale"]) + list(arch["shift"])]
                 a.norm_scale = (C.c_void_p * nl)(*[v.ctypes.data for v in self._norm[:nl]])
                 a.norm_shift = (C.c_void_p * nl)(*[v.ctypes.data for v in self._norm[nl:]])
-            if conv is not None:
+            if pool is not None:
+                rc = self.lib.aware_detector_create_pool(C.byref(h), plan.h, C.c_void_p(mel.ctypes.data), mel.shape[0], nl,
+                                                         (C.c_int * (nl + 1))(*chans), wp, bp, C.byref(a), *self.conv, *self.pool)
+                check(rc, "aware_detector_create_pool")
+            elif conv is not None:
                 rc = self.lib.aware_detector_create_conv(C.byref(h), plan.h, C.c_void_p(mel.ctypes.data), mel.shape[0], nl,
                                                          (C.c_int * (nl + 1))(*chans), wp, bp, C.byref(a), *self.conv)
                 check(rc, "aware_detector_create_conv")
@@ -542,7 +572,7 @@ class DetectorWeights:
 
     def check_clips(self, who: str, batch: "Batch"):
         """check_tap_clips on the batch's clips, in front of every entry point that takes this detector."""
-        check_tap_clips(who, batch.frames, len(self.channels) - 1, self.conv)
+        check_tap_clips(who, batch.frames, len(self.channels) - 1, self.conv, self.pool)
 
     def update(self, weights, biases):
         """EXTENSION (detector training): replace the parameters in place (same shapes), aware_detector_update."""

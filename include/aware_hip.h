@@ -293,6 +293,29 @@ int aware_conv_unfold(const aware_batch* batch, const float* x, float* u, int ch
 int aware_conv_fold(const aware_batch* batch, const float* du, float* dx, int channels, int block, int kernel_size,
                     int stride, int padding, void* stream);
 
+/* Initial pools (initial_pool_size and initial_pool_stride of detection_net_cfg; multibit_detector_net.py:53, 131; added
+ * without a version step, so a caller detects them by symbol): the AvgPool1d(pool_size, pool_stride) between the mel stage
+ * and block 0.  A clip of T frames enters block 0 with L_0 = aware_pool_rows(T, pool_size, pool_stride) =
+ * floor((T - pool_size) / pool_stride) + 1 rows, 0 for T < pool_size; the frames from (L_0 - 1) pool_stride + pool_size on are
+ * dropped by the pool and still count in the mel stage's InstanceNorm and GlobalStandardize.  Served: pool_size 2..8 and
+ * pool_stride 2..8 in any combination (windows overlap where pool_size > pool_stride and leave gaps where it is smaller);
+ * outside that AWARE_E_UNSUPPORTED, non-positive values AWARE_E_BADARG.  From 2 on L_0 <= floor(T / 2), so batches and
+ * workspaces are what they are for every other detector; a size or stride of 1 is not served.  The other arguments are those
+ * of aware_detector_create_conv, and 2 / 2 is that function.  Every other detector made here runs the staged route whatever
+ * its arch is: the mel stage's normalise-and-pool kernels for any pool, then per block the plain GEMM (behind the unfold for
+ * temporal convolutions) and the norm / activation kernel over the block's own rows, then the read-out kernel;
+ * aware_detector_is_card is 0 and the training extension returns AWARE_E_UNSUPPORTED.  A batch with a clip that the pool or
+ * a later block leaves without a row is refused with AWARE_E_BADARG by aware_detect, aware_detector_forward / _backward and
+ * aware_embed_create. */
+int aware_detector_create_pool(aware_detector** out, const aware_plan* plan, const float* mel_basis, int n_mels,
+                               int n_layers, const int* channels, const float* const* weights,
+                               const float* const* biases, const aware_detector_arch* arch, int kernel_size, int stride,
+                               int padding, int pool_size, int pool_stride);
+/* the initial pool of a detector (2 / 2 for every detector not made by aware_detector_create_pool); either pointer may be NULL */
+int aware_detector_pool(const aware_detector* det, int* pool_size, int* pool_stride);
+/* rows a clip of `frames` frames has behind the pool (0 for frames < pool_size); aware_pool_rows(T, 2, 2) == T / 2 */
+int aware_pool_rows(int frames, int pool_size, int pool_stride);
+
 /* AWAREDetector.detect (detection/multibit_detector.py:28-42), batched: normalise, STFT, |.|,
  * zero the out-of-band bins, network forward.  values: dev f32 [B][n_bits].
  * workspace: dev, >= aware_detect_workspace_bytes(). */
