@@ -1932,7 +1932,11 @@ extern "C" int aware_embed_create(aware_embed** out, const aware_plan* plan, con
         for (int i = 0; i < b->B; ++i)
             if (b->out_len[i] < 1) return AWARE_E_BADARG;
     }
-    if (cfg->num_iterations < 1 || cfg->num_iterations > 4096 || cfg->loss < 0 || cfg->loss > AWARE_LOSS_PUSH_L1) return AWARE_E_BADARG;
+    if (cfg->num_iterations < 1 || cfg->num_iterations > 4096 || cfg->loss < 0 || cfg->loss > AWARE_LOSS_BCE ||
+        cfg->loss == AWARE_LOSS_EXTERNAL)
+        return AWARE_E_BADARG;
+    // binary cross-entropy reads probabilities: torch raises on a prediction outside [0, 1], which only a sigmoid read-out rules out
+    if (cfg->loss == AWARE_LOSS_BCE && det->final_act != kActSigmoid) return AWARE_E_UNSUPPORTED;
     if (cfg->conv_pipe < 0 || cfg->conv_pipe > 2 || cfg->readout < 0 || cfg->readout > 1 || cfg->mel < 0 || cfg->mel > 1)
         return AWARE_E_BADARG;
     if (cfg->dsp_path < 0 || cfg->dsp_path > 1 || cfg->conv_tile < 0 || cfg->conv_tile > 2) return AWARE_E_BADARG;

@@ -139,7 +139,20 @@ __device__ __forceinline__ int ola_envelope_index(int p, int T) {
 // Per-bit loss term and its derivative at the read-out (embedding/losses.py; kinds as AWARE_LOSS_* in aware_hip.h):
 // 0 push_extremes :38-42, 1 mse :23-25, 2 hinge :12-14, 3 sign :68-70, 4 push_sigmoid :55-59, 5 ber :90-92 (no
 // gradient), 6 push_extremes + L1 on the coefficients (EXTENSION; the L1 part is added by the caller), 7 external:
-// `tg` is dL/dp itself.  inv = 1 / n_bits (the losses average over the bits).
+// `tg` is dL/dp itself, 8 bce :79-81 (sigmoid read-outs only: p in [0, 1], targets 0 / 1).  inv = 1 / n_bits (the losses
+// average over the bits).
+
+// torch.nn.functional.binary_cross_entropy per bit: both logarithms clamped at -100 (a saturated p costs 100, not inf),
+// the derivative (p - t) / max(p (1 - p), 1e-12).  At p exactly 0 or 1 the derivative is finite (at most 1e12) and the
+// sigmoid's own derivative p (1 - p) is exactly 0, so the read-out's product of the two is 0, never 0 * inf.
+// Contraction off: with a 0 / 1 target one of the two products is exact, and the sum is torch's in either order.
+__device__ __forceinline__ void loss_term_bce(float p, float tg, float inv, float& lterm, float& dp) {
+#pragma clang fp contract(off)
+    const float lp = fmaxf(logf(p), -100.f), lq = fmaxf(log1pf(-p), -100.f);
+    lterm = ((tg - 1.f) * lq - tg * lp) * inv;
+    dp = (p - tg) / fmaxf((1.f - p) * p, 1e-12f) * inv;
+}
+
 __device__ __forceinline__ void loss_term(int kind, float p, float tg, float inv, float& lterm, float& dp) {
     if (kind == 0 || kind == 6) {
         lterm = ((p - tg) * (p - tg) - 0.1f * fabsf(p)) * inv;
@@ -162,6 +175,8 @@ __device__ __forceinline__ void loss_term(int kind, float p, float tg, float inv
         const float sp = (p > 0.f) ? 1.f : (p < 0.f ? -1.f : 0.f), st_ = (tg > 0.f) ? 1.f : (tg < 0.f ? -1.f : 0.f);
         lterm = (sp != st_ ? 1.f : 0.f) * inv;
         dp = 0.f;
+    } else if (kind == 8) {
+        loss_term_bce(p, tg, inv, lterm, dp);
     } else {
         lterm = 0.f;
         dp = tg;

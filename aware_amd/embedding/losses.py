@@ -4,6 +4,7 @@ On the HIP path the loss, its gradient and the best-loss bookkeeping are evaluat
 inside the read-out kernel (csrc/detector_kernels.hip: head_kernel); the classes here carry the
 name -> kernel id mapping and a host-side forward for inspection."""
 import torch
+import torch.nn.functional as F
 
 from ..interfaces import Loss
 
@@ -82,16 +83,36 @@ class PushToExtremesL1Loss(_KernelLoss):
         return torch.mean((predicted - target_pattern) ** 2) - 0.1 * torch.mean(torch.abs(predicted))
 
 
+class BinaryCrossEntropyLoss(_KernelLoss):
+    """F.binary_cross_entropy(pred, target), mean over the bits (losses.py:79-81): predictions in [0, 1], i.e. a detector that
+    ends in sigmoid (get_loss_fn(..., final_activation="sigmoid")), targets in [0, 1] (pattern_mode bytes2bits)."""
+    kernel_id, name = 8, "bce"
+
+    def forward(self, predicted, target_pattern):
+        return F.binary_cross_entropy(predicted, target_pattern)
+
+
 registry = {"hinge": HingeLoss, "mse": MSELoss, "push_extremes": PushToExtremesLoss, "push_sigmoid": PushToExtremesSigmoidLoss,
             "sign": SignBasedLoss, "ber": BERLoss, "push_extremes_l1": PushToExtremesL1Loss}
-# F.binary_cross_entropy needs predictions in [0, 1]; the detector ends in tanh, so the reference's
-# "bce" entry (losses.py:79-81) raises inside torch for its own model card -- refused here by name
-_NOT_ON_HIP = ("bce",)
+# Losses that need something of the detector.  F.binary_cross_entropy raises inside torch on a prediction outside [0, 1]:
+# the reference's "bce" entry (losses.py:79-81) fails at the first step on its own model card (tanh) and runs on a detector
+# that ends in sigmoid (with 0 / 1 targets, pattern_mode bytes2bits).  A loss alone cannot know its detector, so the bare
+# name stays refused; get_loss_fn(..., final_activation="sigmoid") -- what AWAREEmbedder passes -- returns the class.
+_NEEDS_FINAL_ACTIVATION = {"bce": (BinaryCrossEntropyLoss, "sigmoid")}
 
 
-def get_loss_fn(loss_type: str, **kwargs) -> Loss:
-    if loss_type in _NOT_ON_HIP:
-        raise NotImplementedError(f"loss '{loss_type}' is registered by the reference but not implemented on the HIP path")
+def get_loss_fn(loss_type: str, *, final_activation=None, **kwargs) -> Loss:
+    """final_activation: the detector's (detection_net_cfg["final_activation"]); only the losses of _NEEDS_FINAL_ACTIVATION
+    look at it."""
+    if loss_type in _NEEDS_FINAL_ACTIVATION:
+        cls, needs = _NEEDS_FINAL_ACTIVATION[loss_type]
+        if final_activation is None:
+            raise NotImplementedError(f"loss '{loss_type}' needs a detector that ends in {needs}: "
+                                      f"get_loss_fn('{loss_type}', final_activation='{needs}')")
+        if str(final_activation).lower() != needs:
+            raise NotImplementedError(f"loss '{loss_type}' needs a detector that ends in {needs} (predictions in [0, 1]), "
+                                      f"not final_activation = '{final_activation}'")
+        return cls(**kwargs)
     if loss_type not in registry:
-        raise ValueError(f"Unknown loss type: {loss_type}. Available: {list(registry.keys()) + list(_NOT_ON_HIP)}")
+        raise ValueError(f"Unknown loss type: {loss_type}. Available: {list(registry.keys()) + list(_NEEDS_FINAL_ACTIVATION)}")
     return registry[loss_type](**kwargs)

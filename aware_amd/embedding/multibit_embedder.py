@@ -75,7 +75,9 @@ class AWAREEmbedder(BaseEmbedder):
         scheduler_cfg = scheduler_cfg or {"name": "reduce_lr_on_plateau", "params": {"factor": 0.9, "patience": 500}}
         self.optimizer_name, self.optimizer_params = optimizer_cfg["name"], optimizer_cfg.get("params", {}) or {}
         self.scheduler_name, self.scheduler_params = scheduler_cfg["name"], scheduler_cfg.get("params", {}) or {}
-        self.loss = get_loss_fn(loss)                     # ValueError on an unknown name, as the reference
+        # ValueError on an unknown name, as the reference; bce on a detector that does not end in sigmoid raises here
+        # (NotImplementedError), where the reference raises inside torch at the first step
+        self.loss = get_loss_fn(loss, final_activation=self.detection_net.final_activation)
         if self.general_geometry and getattr(self.loss, "l1_weight", 0.0):
             rt.refuse_general_geometry("the loss push_extremes_l1 (its L1 term lives in the streaming kernels)")
         self._opt = get_optimizer(self.optimizer_name, None, **self.optimizer_params)
@@ -117,6 +119,17 @@ class AWAREEmbedder(BaseEmbedder):
             rt.check_general_clips("AWAREEmbedder", self.frame_length, self.hop_length, self.win_length, self.window, lengths)
         # a net of temporal convolutions: every clip keeps a row through every block (T = 1 + n // hop frames)
         self.detection_net.check_clip_frames("AWAREEmbedder", [1 + int(n) // self.hop_length for n in lengths])
+
+    def check_targets(self, watermarks):
+        """With the loss bce: ValueError for a target outside [0, 1], as F.binary_cross_entropy refuses one (the device would
+        take it without a word); needs no GPU.  embed and embed_batch call it before anything is launched; embed_device takes
+        device targets as they are."""
+        if self.loss.name != "bce":
+            return
+        wm = np.asarray(watermarks, dtype=np.float32)
+        if not np.all((wm >= 0.0) & (wm <= 1.0)):            # a NaN fails it too
+            raise ValueError("AWAREEmbedder: the loss bce takes targets between 0 and 1 (pattern_mode bytes2bits), got values "
+                             f"from {np.nanmin(wm)} to {np.nanmax(wm)}")
 
     def make_batch(self, lengths, sample_rate: int) -> "rt.Batch":
         """The batch geometry of this embedder's plan for clips of `lengths` samples."""
@@ -164,9 +177,10 @@ class AWAREEmbedder(BaseEmbedder):
         return sess.finish(rescale), sess
 
     def embed_batch(self, clips, sample_rate: int, watermarks, rescale=None):
-        """clips: list of 1-D float arrays; watermarks: [B, n_bits] bipolar.  Returns a list of
+        """clips: list of 1-D float arrays; watermarks: [B, n_bits] bipolar (0 / 1 for the unipolar losses).  Returns a list of
         device tensors (one per clip, length hop_length*(T_b-1) with T_b = 1 + n_b // hop_length)."""
         t0 = time.time()
+        self.check_targets(watermarks)
         batch = self.make_batch([len(c) for c in clips], sample_rate)
         wm = torch.as_tensor(np.asarray(watermarks), dtype=torch.float32, device="cuda")
         rs = None if rescale is None else torch.as_tensor(np.asarray(rescale), dtype=torch.float32, device="cuda")

@@ -132,7 +132,10 @@ class WatermarkPipeline:
             b = self.embedder.make_batch(x.lengths, self.sample_rate)
             self._sessions[key] = (b, self.embedder.start_session(b, self.sample_rate))
         batch, sess = self._sessions[key]
-        target = (2 * bits - 1).to(torch.float32)                                  # PatternEncoder bits2bipolar
+        if getattr(self.embedder, "pattern_mode", "bits2bipolar") in ("bytes2bits", "bits"):
+            target = bits.to(torch.float32)                                        # unipolar card: the bits themselves
+        else:
+            target = (2 * bits - 1).to(torch.float32)                              # PatternEncoder bits2bipolar
         out, _ = self.embedder.embed_device(x.data, batch, self.sample_rate, target, self._clip_max(x), session=sess)
         wm = rt.Ragged(out, batch.out_lengths)
         clean_bits, clean_vals = self._detect_bits(wm)

@@ -20,7 +20,8 @@ SPEC_STRIDE_WIDE = 576    # ... wide layout: a band outside bins 1..511 or wider
 FULL_STRIDE = 520
 CONV_PIPES = {"f16x2": 0, "f32": 1, "bf16x3": 2}
 CONV_TILES = {"auto": 0, "narrow": 1, "wide": 2}       # aware_embed_config::conv_tile
-LOSS_KINDS = {"push_extremes": 0, "mse": 1, "hinge": 2, "sign": 3, "push_sigmoid": 4, "ber": 5, "push_extremes_l1": 6}
+LOSS_KINDS = {"push_extremes": 0, "mse": 1, "hinge": 2, "sign": 3, "push_sigmoid": 4, "ber": 5, "push_extremes_l1": 6,
+              "bce": 8}
 
 
 def band_stride(band_lo: int, band_hi: int) -> int:
@@ -498,6 +499,9 @@ def detector_train_gradients(plan: Plan, det: "DetectorWeights", batch: Batch, m
     (aware_detector_train_gradients): (values [B, n_bits], per-clip losses [B], [dL/dW_l], [dL/db_l]) -- gradients of the SUM
     of the per-clip losses.  grad_weights / grad_biases: tensors to write into (e.g. views of one flat bucket)."""
     require_card_arch(det, "aware_detector_train_gradients")
+    if loss == "bce":
+        raise NotImplementedError("aware_detector_train_gradients: the loss bce needs a detector that ends in sigmoid, and "
+                                  "detector training supports the model card's tanh read-out only")
     lib = plan.lib
     nbytes = lib.aware_detector_train_workspace_bytes(batch.h, det.h)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=mag.device)

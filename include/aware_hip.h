@@ -51,6 +51,8 @@ extern "C" {
 #define AWARE_LOSS_BER 5            /* no gradient, losses.py:90-92 */
 #define AWARE_LOSS_PUSH_L1 6        /* EXTENSION (BASELINE config 3 "BER+L1"): push_extremes + l1_weight * mean|c - c0| */
 #define AWARE_LOSS_EXTERNAL 7       /* internal: `target` holds dL/dpred (aware_detector_backward) */
+#define AWARE_LOSS_BCE 8            /* losses.py:79-81, torch's binary_cross_entropy: targets 0 / 1; detectors whose final
+                                       activation is AWARE_FINAL_SIGMOID only (aware_embed_create: AWARE_E_UNSUPPORTED otherwise) */
 
 #define AWARE_SPEC_STRIDE 256      /* floats per frame row of a band-limited array (narrow layout) */
 #define AWARE_SPEC_STRIDE_WIDE 576 /* ... of a band with the wide layout (aware_plan_band_stride) */
@@ -363,8 +365,9 @@ int aware_detector_update_device(aware_detector* det, const float* const* dev_we
 /* ---- embedder -----------------------------------------------------------------------------------
  * AWAREEmbedder.embed / _optimize (embedding/multibit_embedder.py:70-197), batched and ragged:
  * every clip is its own optimisation problem.  loss: AWARE_LOSS_* above -- 0 push_extremes, 1 mse, 2 hinge, 3 sign,
- * 4 push_sigmoid, 5 ber (no gradient) (embedding/losses.py:95-103; bce needs sigmoid outputs), 6 push_extremes + L1
- * (EXTENSION, streaming DSP path only).  optimizer: NAdam (embedding/optimizers.py:5; torch.optim.NAdam
+ * 4 push_sigmoid, 5 ber (no gradient) (embedding/losses.py:95-103), 6 push_extremes + L1 (EXTENSION, streaming DSP path
+ * only), 8 bce (a detector that ends in AWARE_FINAL_SIGMOID only, on every route such a detector takes; the training entry
+ * points refuse it).  optimizer: NAdam (embedding/optimizers.py:5; torch.optim.NAdam
  * single-tensor semantics) with lr, beta1, beta2, eps, momentum_decay; the reference's
  * ReduceLROnPlateau(patience 500) never fires within 400 iterations and is not modelled. */
 typedef struct aware_embed_config {
