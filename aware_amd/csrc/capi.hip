@@ -18,6 +18,7 @@
 #define AWARE_LOOP_CF cf
 #include "loop_chain.hpp"
 #include "batch_layout.hpp"
+#include "detector_image.hpp"
 
 using namespace aware;
 
@@ -629,26 +630,6 @@ extern "C" int aware_istft_bwd(const aware_plan* plan, const aware_batch* b, con
 
 // ---------------------------------------------------------------------------------------------
 extern "C" void aware_detector_destroy(aware_detector* d);
-// the widest last block (payloads of up to 512 bits), the largest mel bank and hidden width, the deepest network
-constexpr int kMaxOutChannels = 1024;
-constexpr int kMaxMels = 512;
-constexpr int kMaxHidden = 4096;
-constexpr int kMaxLayers = 33;
-// The storage rule: the channel count layer boundary i (0 = the mel bank, n_layers = the last block) is stored with, for the
-// caller's count C.  The only place that knows the padding.
-//  - i = n_layers (C = 2 * payload bits): C itself where the read-out kernels for C <= 64 take it (a multiple of 4), C
-//    rounded up to a multiple of 4 below that, and above 64 C rounded up to a multiple of 128 so that the conv-block kernels
-//    take the block and the wide read-out (launch_readout_wide) reads it out;
-//  - i < n_layers (mel bank and hidden widths): a multiple of 4 as is, else rounded up to a multiple of 4 up to 64 and to a
-//    multiple of 128 above, so that the fused conv-block kernels take the block.
-// Stored widths are multiples of 4 (the f32 GEMMs load K in float4).  Padding channels have zero weights, zero bias, zero
-// weight columns in the next block and zero melT rows (and scale 0, shift 0 for BatchNorm): through every norm and
-// activation they stay exactly 0 and their gradient is 0.
-static int stored_channels(int i, int n_layers, int C) {
-    if (i < n_layers && C % 4 == 0) return C;
-    if (C <= 64) return (C + 3) & ~3;
-    return (C + 127) & ~127;
-}
 // whether the training extension serves the detector: the model card's architecture on 128 mel bands, hidden widths stored
 // as given and at most 7 layers (it adds no padding logic of its own)
 static bool det_trainable(const aware_detector* d) {
@@ -657,239 +638,125 @@ static bool det_trainable(const aware_detector* d) {
         if (d->ch[i] != d->uch[i]) return false;
     return true;
 }
+// detector_image.hpp does the host arithmetic of a detector's parameters; here are its arguments and the device calls
+static const DetectorLimits kDetLimits{kMaxTapKernel, kMaxTapStride, kMinPool, kMaxPool};
+static const MelTapShape kMelShape{kFS, kMelTapsA, kMelTapsB};
+static const PackRules kPackRules{x3_packed_bytes, h2_packed_bytes, gemm_clip_h2_supported, readout_x3_supported};
+// a host image into its device buffer, which is `room` bytes and allocated here where `alloc`
+static int det_put(void** mem, bool alloc, size_t room, const void* src, size_t bytes) {
+    if (alloc) HIPCHK(hipMalloc(mem, room));
+    HIPCHK(hipMemcpy(*mem, src, bytes, hipMemcpyHostToDevice));
+    return AWARE_OK;
+}
+static void* det_at(void* mem, const PackSlot& t) { return t.on ? (char*)mem + t.off : nullptr; }
+// the two sparse mel forms, one buffer: tw, fw, tm, fs (allocated the first time a basis has the two-tap form)
+static int upload_mel_forms(aware_detector* d, const MelForms& m) {
+    d->melw = nullptr; d->melm = nullptr; d->melf_w = nullptr; d->melf_s = nullptr;
+    if (!m.sparse) return AWARE_OK;
+    const size_t b_tw = m.tw.size() * sizeof(float), b_fw = m.fw.size() * sizeof(float);
+    if (!d->mel2mem) HIPCHK(hipMalloc(&d->mel2mem, b_tw + b_fw + m.tm.size() + m.fs.size() + 64));
+    char* base = (char*)d->mel2mem;
+    unsigned char* bytes = (unsigned char*)base + b_tw + b_fw;
+    HIPCHK(hipMemcpy(base, m.tw.data(), b_tw, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(bytes, m.tm.data(), m.tm.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(base + b_tw, m.fw.data(), b_fw, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(bytes + m.tm.size(), m.fs.data(), m.fs.size(), hipMemcpyHostToDevice));
+    d->melw = (float2*)base;
+    d->melm = bytes;
+    if (m.runs) { d->melf_w = (float*)(base + b_tw); d->melf_s = bytes + m.tm.size(); }
+    return AWARE_OK;
+}
+// the bf16x3 fragment images, packed on the host
+static int upload_x3(aware_detector* d, const DetectorImage& im, const PackedLayout& L, bool alloc) {
+    std::vector<uint16_t> hp(L.x3_total / 2 + 8, 0);
+    auto pack = [&](const PackSlot& t, const float* src) { if (t.on) x3_pack(src, t.N, t.K, hp.data() + t.off / 2); };
+    pack(L.last, L.last_rows.data());
+    pack(L.lastT, L.lastT_rows.data());
+    pack(L.melT, im.h.data() + im.o_melT);
+    pack(L.melB, im.h.data() + im.o_melB);
+    for (int l = 0; l < d->n_layers; ++l) {
+        pack(L.w[l], im.h.data() + im.o_w[l]);
+        pack(L.wT[l], im.h.data() + im.o_wT[l]);
+    }
+    const int rc = det_put(&d->pkmem, alloc, L.x3_total + 16, hp.data(), L.x3_total);
+    if (rc) return rc;
+    d->lastpk = det_at(d->pkmem, L.last); d->lastTpk = det_at(d->pkmem, L.lastT);
+    d->melTpk = det_at(d->pkmem, L.melT); d->melBpk = det_at(d->pkmem, L.melB);
+    for (int l = 0; l < d->n_layers; ++l) { d->wpk[l] = det_at(d->pkmem, L.w[l]); d->wTpk[l] = det_at(d->pkmem, L.wT[l]); }
+    return AWARE_OK;
+}
+// the f16 two-term images, packed on the device from the f32 copies just uploaded
+static int upload_h2(aware_detector* d, const PackedLayout& L, bool alloc) {
+    if (!L.h2_total) return AWARE_OK;
+    if (alloc) HIPCHK(hipMalloc(&d->h2mem, L.h2_total));
+    for (int l = 0; l < d->n_layers; ++l) {
+        d->wh2[l] = det_at(d->h2mem, L.wh2[l]); d->wTh2[l] = det_at(d->h2mem, L.wTh2[l]);
+        if (d->wh2[l]) launch_h2_pack(d->w[l], L.wh2[l].K, L.wh2[l].N, L.wh2[l].K, d->wh2[l], 0);
+        if (d->wTh2[l]) launch_h2_pack(d->wT[l], L.wTh2[l].K, L.wTh2[l].N, L.wTh2[l].K, d->wTh2[l], 0);
+    }
+    LAUNCHCHK();
+    HIPCHK(hipStreamSynchronize(0));
+    return AWARE_OK;
+}
 // host staging of the detector's parameters (plain + transposed f32 copies, bf16x3 fragment images) and upload; `alloc`
 // = false re-uses the device buffers of a detector created with the same shapes (aware_detector_update)
-static int detector_upload(aware_detector* d, const float* mel_basis, const float* const* weights,
+static int detector_upload(aware_detector* d, const DetectorSpec& s, const float* mel_basis, const float* const* weights,
                            const float* const* biases, bool alloc) {
-    const int n_mels = d->n_mels, n_layers = d->n_layers;
-    const int* channels = d->ch.data();
-    const int* uch = d->uch.data();
-    const int Mp = channels[0];
-    const int S = d->stride;
-    size_t total = (size_t)Mp * S * 2;
-    const int K = d->tk;      // taps per block (1: the 1x1 convolutions)
-    for (int i = 0; i < n_layers; ++i) total += (size_t)K * channels[i] * channels[i + 1] * 2 + channels[i + 1];
-    std::vector<float> h(total, 0.f);
-    size_t o = 0;
-    const int nbins = d->n_fft / 2 + 1;
-    const int lo = d->band_lo, nb = d->nband;
-    size_t o_melT = o; o += (size_t)Mp * S;
-    size_t o_melB = o; o += (size_t)S * Mp;
-    // only the in-band columns of the mel basis ever multiply non-zero magnitudes
-    // (multibit_embedder.py:104, multibit_detector.py:34-37 zero the rest)
-    for (int j = 0; j < n_mels; ++j)
-        for (int f = 0; f < nb; ++f) {
-            float v = mel_basis[(size_t)j * nbins + lo + f];
-            h[o_melT + (size_t)j * S + f] = v;
-            h[o_melB + (size_t)f * Mp + j] = v;
-        }
-    {
-        // two-tap form of the band's columns, if the basis has it (any triangular filter bank does)
-        std::vector<float2> tw(kFS, make_float2(0.f, 0.f));
-        std::vector<unsigned char> tm(kFS, 0);
-        bool sparse = n_mels == 128 && S == kFS && !d->general;
-        for (int f = 0; f < nb && sparse; ++f) {
-            int first = -1, count = 0, lastnz = -1;
-            for (int j = 0; j < n_mels; ++j)
-                if (h[o_melB + (size_t)f * Mp + j] != 0.f) { if (first < 0) first = j; lastnz = j; ++count; }
-            if (count == 0) continue;
-            if (count > 2 || lastnz - first > 1) { sparse = false; break; }
-            const int m1 = first < n_mels - 1 ? first : n_mels - 2;
-            tm[f] = (unsigned char)m1;
-            tw[f] = make_float2(h[o_melB + (size_t)f * Mp + m1], h[o_melB + (size_t)f * Mp + m1 + 1]);
-        }
-        // forward: filter m as kMelTapsA (m < 64) / kMelTapsB adjacent columns starting at fs[m]
-        std::vector<float> fw((size_t)128 * kMelTapsB, 0.f);
-        std::vector<unsigned char> fs(128, 0);
-        bool runs = sparse;
-        for (int m = 0; m < n_mels && runs; ++m) {
-            int first = -1, lastnz = -1;
-            for (int f = 0; f < nb; ++f)
-                if (h[o_melT + (size_t)m * S + f] != 0.f) { if (first < 0) first = f; lastnz = f; }
-            if (first < 0) continue;
-            const int taps = m < 64 ? kMelTapsA : kMelTapsB;
-            const int start = first <= kFS - kMelTapsB ? first : kFS - kMelTapsB;
-            if (lastnz - start >= taps) { runs = false; break; }
-            fs[m] = (unsigned char)start;
-            for (int j = 0; j < taps; ++j) fw[(size_t)m * kMelTapsB + j] = h[o_melT + (size_t)m * S + start + j];
-        }
-        if (sparse) {
-            const size_t bytes = kFS * (sizeof(float2) + 1) + 128 * (kMelTapsB * sizeof(float) + 1) + 64;
-            if (!d->mel2mem) HIPCHK(hipMalloc(&d->mel2mem, bytes));
-            char* base = (char*)d->mel2mem;
-            d->melw = (float2*)base;
-            d->melf_w = (float*)(base + kFS * sizeof(float2));
-            d->melm = (unsigned char*)(base + kFS * sizeof(float2) + 128 * kMelTapsB * sizeof(float));
-            d->melf_s = d->melm + kFS;
-            HIPCHK(hipMemcpy(d->melw, tw.data(), kFS * sizeof(float2), hipMemcpyHostToDevice));
-            HIPCHK(hipMemcpy(d->melm, tm.data(), kFS, hipMemcpyHostToDevice));
-            HIPCHK(hipMemcpy(d->melf_w, fw.data(), fw.size() * sizeof(float), hipMemcpyHostToDevice));
-            HIPCHK(hipMemcpy(d->melf_s, fs.data(), 128, hipMemcpyHostToDevice));
-            if (!runs) { d->melf_w = nullptr; d->melf_s = nullptr; }
-        } else {
-            d->melw = nullptr;
-            d->melm = nullptr;
-            d->melf_w = nullptr;
-            d->melf_s = nullptr;
-        }
-    }
-    std::vector<size_t> o_w(n_layers), o_wT(n_layers), o_b(n_layers);
-    for (int l = 0; l < n_layers; ++l) {
-        const int ci = channels[l], co = channels[l + 1], kc = K * ci;
-        const int uci = uch[l], rows = uch[l + 1];   // the caller's shape [rows][uci][K]; padding rows and columns stay zero
-        o_w[l] = o; o += (size_t)kc * co;
-        o_wT[l] = o; o += (size_t)kc * co;
-        o_b[l] = o; o += co;
-        for (int r = 0; r < rows; ++r)
-            for (int c = 0; c < uci; ++c)
-                for (int j = 0; j < K; ++j) {
-                    float v = weights[l][((size_t)r * uci + c) * K + j];
-                    h[o_w[l] + (size_t)r * kc + (size_t)j * ci + c] = v;
-                    h[o_wT[l] + ((size_t)j * ci + c) * co + r] = v;
-                }
-        for (int r = 0; r < rows; ++r) h[o_b[l] + r] = biases && biases[l] ? biases[l][r] : 0.f;
-    }
-    if (alloc) HIPCHK(hipMalloc((void**)&d->mem, total * sizeof(float)));
-    HIPCHK(hipMemcpy(d->mem, h.data(), total * sizeof(float), hipMemcpyHostToDevice));
-    d->melT = d->mem + o_melT;
-    d->melB = d->mem + o_melB;
-    for (int l = 0; l < n_layers; ++l) { d->w[l] = d->mem + o_w[l]; d->wT[l] = d->mem + o_wT[l]; d->bias[l] = d->mem + o_b[l]; }
-    {
-        size_t pk_total = 0;
-        std::vector<size_t> o_pk(n_layers), o_pkT(n_layers);
-        for (int l = 0; l < n_layers; ++l) {
-            const int ci = K * channels[l], co = channels[l + 1];
-            o_pk[l] = o_pkT[l] = (size_t)-1;
-            if (co % 128 == 0 && ci % 64 == 0) { o_pk[l] = pk_total; pk_total += x3_packed_bytes(co, ci); }
-            if (ci % 128 == 0 && co % 64 == 0) { o_pkT[l] = pk_total; pk_total += x3_packed_bytes(ci, co); }
-        }
-        // the mel operands where the bf16x3 kernel can take them (N % 128, K % 64): always for 128 bands
-        const bool mT = Mp % 128 == 0, mB = Mp % 64 == 0;
-        const size_t o_mT = pk_total; if (mT) pk_total += x3_packed_bytes(Mp, S);
-        const size_t o_mB = pk_total; if (mB) pk_total += x3_packed_bytes(S, Mp);
-        // read-out kernel operands (last conv block, C <= 64 channels)
-        const int cil = channels[n_layers - 1], col = channels[n_layers], colp = 16 * ((col + 15) / 16);
-        // (the fused read-out: 1x1 blocks after the (2, 2) pool only)
-        const bool ro = !d->taps && !d->pooled && n_layers >= 2 && readout_x3_supported(1, cil, col);
-        size_t o_lp = 0, o_lT = 0;
-        if (ro) {
-            o_lp = pk_total; pk_total += x3_packed_bytes(colp, cil);
-            o_lT = pk_total; pk_total += x3_packed_bytes(cil, 64);
-        }
-        std::vector<uint16_t> hp(pk_total / 2 + 8, 0);
-        if (ro) {
-            std::vector<float> wp((size_t)colp * cil, 0.f), wt((size_t)cil * 64, 0.f);
-            for (int r = 0; r < col; ++r)
-                for (int c = 0; c < cil; ++c) {
-                    const float v = h[o_w[n_layers - 1] + (size_t)r * cil + c];
-                    wp[(size_t)r * cil + c] = v;
-                    wt[(size_t)c * 64 + r] = v;
-                }
-            x3_pack(wp.data(), colp, cil, hp.data() + o_lp / 2);
-            x3_pack(wt.data(), cil, 64, hp.data() + o_lT / 2);
-        }
-        if (mT) x3_pack(h.data() + o_melT, Mp, S, hp.data() + o_mT / 2);
-        if (mB) x3_pack(h.data() + o_melB, S, Mp, hp.data() + o_mB / 2);
-        for (int l = 0; l < n_layers; ++l) {
-            const int ci = K * channels[l], co = channels[l + 1];
-            if (o_pk[l] != (size_t)-1) x3_pack(h.data() + o_w[l], co, ci, hp.data() + o_pk[l] / 2);
-            if (o_pkT[l] != (size_t)-1) x3_pack(h.data() + o_wT[l], ci, co, hp.data() + o_pkT[l] / 2);
-        }
-        if (alloc) HIPCHK(hipMalloc(&d->pkmem, pk_total + 16));
-        HIPCHK(hipMemcpy(d->pkmem, hp.data(), pk_total, hipMemcpyHostToDevice));
-        if (ro) { d->lastpk = (char*)d->pkmem + o_lp; d->lastTpk = (char*)d->pkmem + o_lT; }
-        d->melTpk = mT ? (char*)d->pkmem + o_mT : nullptr;
-        d->melBpk = mB ? (char*)d->pkmem + o_mB : nullptr;
-        for (int l = 0; l < n_layers; ++l) {
-            if (o_pk[l] != (size_t)-1) d->wpk[l] = (char*)d->pkmem + o_pk[l];
-            if (o_pkT[l] != (size_t)-1) d->wTpk[l] = (char*)d->pkmem + o_pkT[l];
-        }
-    }
-    {
-        // f16 two-term images, packed on the device from the f32 copies just uploaded
-        size_t total2 = 0;
-        std::vector<size_t> o_h(n_layers), o_hT(n_layers);
-        for (int l = 0; l < n_layers && !d->taps && !d->pooled; ++l) {   // (the f16 two-term kernels serve the fused conv blocks only)
-            const int ci = channels[l], co = channels[l + 1];
-            o_h[l] = o_hT[l] = (size_t)-1;
-            if (gemm_clip_h2_supported(1, co, ci, ci)) { o_h[l] = total2; total2 += (h2_packed_bytes(co, ci) + 255) & ~(size_t)255; }
-            if (gemm_clip_h2_supported(1, ci, co, co)) { o_hT[l] = total2; total2 += (h2_packed_bytes(ci, co) + 255) & ~(size_t)255; }
-        }
-        if (total2) {
-            if (alloc) HIPCHK(hipMalloc(&d->h2mem, total2));
-            for (int l = 0; l < n_layers; ++l) {
-                const int ci = channels[l], co = channels[l + 1];
-                if (o_h[l] != (size_t)-1) { d->wh2[l] = (char*)d->h2mem + o_h[l]; launch_h2_pack(d->w[l], ci, co, ci, d->wh2[l], 0); }
-                if (o_hT[l] != (size_t)-1) { d->wTh2[l] = (char*)d->h2mem + o_hT[l]; launch_h2_pack(d->wT[l], co, ci, co, d->wTh2[l], 0); }
-            }
-            LAUNCHCHK();
-            HIPCHK(hipStreamSynchronize(0));
-        }
-    }
+    const DetectorBand band{d->band_lo, d->nband, d->stride, d->n_fft, d->general};
+    const DetectorImage im = detector_image(s, band, mel_basis, weights, biases);
+    int rc = upload_mel_forms(d, mel_forms(s, band, im, kMelShape));
+    if (rc) return rc;
+    const size_t bytes = im.h.size() * sizeof(float);
+    if ((rc = det_put((void**)&d->mem, alloc, bytes, im.h.data(), bytes))) return rc;
+    d->melT = d->mem + im.o_melT;
+    d->melB = d->mem + im.o_melB;
+    for (int l = 0; l < d->n_layers; ++l) { d->w[l] = d->mem + im.o_w[l]; d->wT[l] = d->mem + im.o_wT[l]; d->bias[l] = d->mem + im.o_b[l]; }
+    const PackedLayout L = packed_layout(s, band, im, kPackRules);
+    if ((rc = upload_x3(d, im, L, alloc))) return rc;
+    return upload_h2(d, L, alloc);
+}
+// the folded BatchNorm map of every block
+static int upload_norm(aware_detector* d, const NormImage& n) {
+    const size_t bytes = n.h.size() * sizeof(float);
+    const int rc = det_put((void**)&d->normmem, true, bytes, n.h.data(), bytes);
+    if (rc) return rc;
+    for (int l = 0; l < d->n_layers; ++l) { d->nscale[l] = d->normmem + n.o_scale[l]; d->nshift[l] = d->normmem + n.o_shift[l]; }
     return AWARE_OK;
 }
 
-static int detector_create(aware_detector** out, const aware_plan* plan, const float* mel_basis, int n_mels, int n_layers,
-                           const int* channels, const float* const* weights, const float* const* biases,
-                           const aware_detector_arch* arch, int tk = 1, int ts = 1, int tp = 0, int psize = 2, int pstride = 2) {
-    if (!out || !plan || !mel_basis || !channels || !weights) return AWARE_E_BADARG;
-    // a general plan made for the transforms alone (no AWARE_PLAN_GENERAL), or a band outside bins 0..n_fft/2
-    if (plan->general && (!plan->loop || !plan->band_ok)) return AWARE_E_UNSUPPORTED;
-    if (n_mels < 1 || n_mels > kMaxMels || n_layers < 1 || n_layers > kMaxLayers || channels[0] != n_mels) return AWARE_E_UNSUPPORTED;
-    const int cl = channels[n_layers];
-    if (cl % 2 || cl < 2 || cl > kMaxOutChannels) return AWARE_E_UNSUPPORTED;
-    for (int i = 1; i < n_layers; ++i)
-        if (channels[i] < 1 || channels[i] > kMaxHidden) return AWARE_E_UNSUPPORTED;
+// the one create path: every aware_detector_create* fills a spec (detector_image.hpp: DetectorSpec) and comes here
+static int detector_create(aware_detector** out, const aware_plan* plan, const float* mel_basis, const DetectorSpec& s,
+                           const float* const* weights, const float* const* biases) {
+    // plan_ok: not a general plan made for the transforms alone (no AWARE_PLAN_GENERAL), or with a band outside bins 0..n_fft/2
+    int rc = detector_spec_check(s, kDetLimits, out && plan && mel_basis && weights,
+                                 !plan || !plan->general || (plan->loop && plan->band_ok));
+    if (rc) return rc;
+    const int n_layers = s.n_layers;
     Building<aware_detector, aware_detector_destroy> d(new aware_detector());
-    d->n_mels = n_mels; d->n_layers = n_layers; d->nbits = cl / 2;
+    d->n_mels = s.n_mels; d->n_layers = n_layers; d->nbits = s.channels[n_layers] / 2;
     d->band_lo = plan->dev.band_lo; d->nband = plan->dev.nband; d->stride = plan->dev.stride;
     d->n_fft = plan->n_fft; d->general = plan->general != 0;
-    d->uch.assign(channels, channels + n_layers + 1);
-    d->ch.resize(n_layers + 1);
+    d->uch.assign(s.channels, s.channels + n_layers + 1);
     for (int i = 0; i <= n_layers; ++i) {
-        d->ch[i] = stored_channels(i, n_layers, channels[i]);
-        if (d->ch[i] > d->maxc) d->maxc = d->ch[i];
-        if (i < n_layers && d->ch[i] > d->max_cin) d->max_cin = d->ch[i];
+        d->ch.push_back(s.stored(i));
+        d->maxc = std::max(d->maxc, d->ch[i]);
+        if (i < n_layers) d->max_cin = std::max(d->max_cin, d->ch[i]);
     }
-    d->taps = tk != 1 || ts != 1 || tp != 0;
-    d->tk = tk; d->ts = ts; d->tp = tp;
-    d->pooled = psize != 2 || pstride != 2;
-    d->psize = psize; d->pstride = pstride;
+    d->taps = s.taps();
+    d->tk = s.kernel_size; d->ts = s.stride; d->tp = s.padding;
+    d->pooled = s.pooled();
+    d->psize = s.pool_size; d->pstride = s.pool_stride;
     d->w.assign(n_layers, nullptr); d->wT.assign(n_layers, nullptr); d->bias.assign(n_layers, nullptr);
     d->wpk.assign(n_layers, nullptr); d->wTpk.assign(n_layers, nullptr);
     d->wh2.assign(n_layers, nullptr); d->wTh2.assign(n_layers, nullptr);
     d->nscale.assign(n_layers, nullptr); d->nshift.assign(n_layers, nullptr);
-    if (arch) {
-        d->act = arch->activation; d->norm = arch->norm; d->final_act = arch->final_activation;
+    if (s.arch) {
+        d->act = s.arch->activation; d->norm = s.arch->norm; d->final_act = s.arch->final_activation;
         d->card_arch = d->act == kActLRelu && d->norm == kNormInstance && d->final_act == kActTanh;
     }
     if (d->taps || d->pooled) d->card_arch = false;
-    int rc = detector_upload(d.get(), mel_basis, weights, biases, true);
-    if (rc == AWARE_OK && d->norm == kNormAffine) {
-        // padding channels (stored_channels) get scale 0 and shift 0: their pre-activation is 0 and their output act(0) = 0
-        // for every block activation.  They are never read out and their gradient is zero.
-        size_t n = 0;
-        for (int l = 0; l < n_layers; ++l) n += 2 * (size_t)d->ch[l + 1];
-        std::vector<float> h(n, 0.f);
-        size_t o = 0;
-        for (int l = 0; l < n_layers; ++l) {
-            const int co = d->ch[l + 1];
-            memcpy(h.data() + o, arch->norm_scale[l], channels[l + 1] * sizeof(float));
-            memcpy(h.data() + o + co, arch->norm_shift[l], channels[l + 1] * sizeof(float));
-            o += 2 * (size_t)co;
-        }
-        if (hipMalloc((void**)&d->normmem, n * sizeof(float)) != hipSuccess ||
-            hipMemcpy(d->normmem, h.data(), n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-            rc = AWARE_E_HIP;
-        } else {
-            o = 0;
-            for (int l = 0; l < n_layers; ++l) {
-                d->nscale[l] = d->normmem + o;
-                d->nshift[l] = d->normmem + o + d->ch[l + 1];
-                o += 2 * (size_t)d->ch[l + 1];
-            }
-        }
-    }
+    rc = detector_upload(d.get(), s, mel_basis, weights, biases, true);
+    if (rc == AWARE_OK && d->norm == kNormAffine) rc = upload_norm(d.get(), norm_image(s));
     if (rc) return rc;
     *out = d.release();
     return AWARE_OK;
@@ -897,26 +764,12 @@ static int detector_create(aware_detector** out, const aware_plan* plan, const f
 extern "C" int aware_detector_create(aware_detector** out, const aware_plan* plan, const float* mel_basis, int n_mels,
                                      int n_layers, const int* channels, const float* const* weights,
                                      const float* const* biases) {
-    return detector_create(out, plan, mel_basis, n_mels, n_layers, channels, weights, biases, nullptr);
-}
-// an aware_detector_arch with its enum values in range and, for BatchNorm, the folded map of every block
-static bool arch_ok(const aware_detector_arch* arch, int n_layers) {
-    if (!arch) return false;
-    if (arch->activation < AWARE_ACT_RELU || arch->activation > AWARE_ACT_SWISH) return false;
-    if (arch->norm < AWARE_NORM_INSTANCE || arch->norm > AWARE_NORM_NONE) return false;
-    if (arch->final_activation < AWARE_FINAL_RELU || arch->final_activation > AWARE_FINAL_SIGMOID) return false;
-    if (arch->norm == AWARE_NORM_BATCH) {
-        if (!arch->norm_scale || !arch->norm_shift || n_layers < 1 || n_layers > kMaxLayers) return false;
-        for (int l = 0; l < n_layers; ++l)
-            if (!arch->norm_scale[l] || !arch->norm_shift[l]) return false;
-    }
-    return true;
+    return detector_create(out, plan, mel_basis, DetectorSpec{n_mels, n_layers, channels}, weights, biases);
 }
 extern "C" int aware_detector_create_ex(aware_detector** out, const aware_plan* plan, const float* mel_basis, int n_mels,
                                         int n_layers, const int* channels, const float* const* weights,
                                         const float* const* biases, const aware_detector_arch* arch) {
-    if (!arch_ok(arch, n_layers)) return AWARE_E_BADARG;
-    return detector_create(out, plan, mel_basis, n_mels, n_layers, channels, weights, biases, arch);
+    return detector_create(out, plan, mel_basis, DetectorSpec{n_mels, n_layers, channels, arch, true}, weights, biases);
 }
 // The same for a detector of temporal convolutions: every block Conv1d(C_in, C_out, kernel_size, stride, padding) along the
 // pooled frames (conv_taps.hpp); weights[l] is [Cout][Cin][kernel_size].  1 / 1 / 0 is aware_detector_create_ex.
@@ -924,12 +777,8 @@ extern "C" int aware_detector_create_conv(aware_detector** out, const aware_plan
                                           int n_layers, const int* channels, const float* const* weights,
                                           const float* const* biases, const aware_detector_arch* arch, int kernel_size, int stride,
                                           int padding) {
-    if (kernel_size < 1 || stride < 1 || padding < 0) return AWARE_E_BADARG;
-    if (kernel_size > kMaxTapKernel || stride > kMaxTapStride || 2 * padding > kernel_size - 1) return AWARE_E_UNSUPPORTED;
-    if (kernel_size == 1 && stride == 1)
-        return aware_detector_create_ex(out, plan, mel_basis, n_mels, n_layers, channels, weights, biases, arch);
-    if (!arch_ok(arch, n_layers)) return AWARE_E_BADARG;
-    return detector_create(out, plan, mel_basis, n_mels, n_layers, channels, weights, biases, arch, kernel_size, stride, padding);
+    return detector_create(out, plan, mel_basis, DetectorSpec{n_mels, n_layers, channels, arch, true, kernel_size, stride, padding},
+                           weights, biases);
 }
 // The same with the initial pool AvgPool1d(pool_size, pool_stride) between the mel stage and block 0 (conv_taps.hpp: pool_rows).
 // 2 / 2 is aware_detector_create_conv.
@@ -937,16 +786,8 @@ extern "C" int aware_detector_create_pool(aware_detector** out, const aware_plan
                                           int n_layers, const int* channels, const float* const* weights,
                                           const float* const* biases, const aware_detector_arch* arch, int kernel_size, int stride,
                                           int padding, int pool_size, int pool_stride) {
-    if (pool_size < 1 || pool_stride < 1) return AWARE_E_BADARG;
-    if (pool_size < kMinPool || pool_size > kMaxPool || pool_stride < kMinPool || pool_stride > kMaxPool) return AWARE_E_UNSUPPORTED;
-    if (pool_size == 2 && pool_stride == 2)
-        return aware_detector_create_conv(out, plan, mel_basis, n_mels, n_layers, channels, weights, biases, arch, kernel_size,
-                                          stride, padding);
-    if (kernel_size < 1 || stride < 1 || padding < 0) return AWARE_E_BADARG;
-    if (kernel_size > kMaxTapKernel || stride > kMaxTapStride || 2 * padding > kernel_size - 1) return AWARE_E_UNSUPPORTED;
-    if (!arch_ok(arch, n_layers)) return AWARE_E_BADARG;
-    return detector_create(out, plan, mel_basis, n_mels, n_layers, channels, weights, biases, arch, kernel_size, stride, padding,
-                           pool_size, pool_stride);
+    return detector_create(out, plan, mel_basis, DetectorSpec{n_mels, n_layers, channels, arch, true, kernel_size, stride, padding,
+                                                              pool_size, pool_stride}, weights, biases);
 }
 extern "C" int aware_detector_pool(const aware_detector* d, int* pool_size, int* pool_stride) {
     if (!d) return AWARE_E_BADARG;
@@ -1003,7 +844,8 @@ extern "C" int aware_detector_update(aware_detector* d, const float* mel_basis, 
                                      const float* const* biases) {
     if (!d || !mel_basis || !weights) return AWARE_E_BADARG;
     if (!det_trainable(d)) return AWARE_E_UNSUPPORTED;   // the training extension serves the model card's network only
-    return detector_upload(d, mel_basis, weights, biases, false);
+    const DetectorSpec s{d->n_mels, d->n_layers, d->uch.data()};   // (a trainable detector has 1x1 blocks and the (2, 2) pool)
+    return detector_upload(d, s, mel_basis, weights, biases, false);
 }
 // EXTENSION (detector training): the same refresh from DEVICE arrays, asynchronous on `stream` -- no host round trip of the
 // 1.68 M parameters: copies, transposes, bf16 three-term and f16 two-term images all rebuilt by kernels.  dev_weights[l]:

@@ -38,9 +38,10 @@ def general_band_stride(nband: int) -> int:
 
 def stored_channels(channels: Sequence[int]) -> list[int]:
     """Channel counts a detector stores for the caller's `channels` = [n_mels, hidden widths..., 2 * payload bits]
-    (stored_channels, csrc/capi.hip): the mel bank and every hidden width as is when a multiple of 4, else rounded up to a
-    multiple of 4 up to 64 and of 128 above; the last block rounded up to a multiple of 4 up to 64 and of 128 above.  The
-    padding channels are zero and invisible in every result."""
+    (stored_channels, csrc/detector_image.hpp; tests/test_detector_image_host.py holds the two against each other): the mel
+    bank and every hidden width as is when a multiple of 4, else rounded up to a multiple of 4 up to 64 and of 128 above; the
+    last block rounded up to a multiple of 4 up to 64 and of 128 above.  The padding channels are zero and invisible in every
+    result."""
     n = len(channels) - 1
     out = []
     for i, c in enumerate(channels):
@@ -518,6 +519,13 @@ def detector_train_gradients(plan: Plan, det: "DetectorWeights", batch: Batch, m
     return vals, losses, gw, gb
 
 
+def _host_arrays(arrays):
+    """The float32 C-contiguous form of each of `arrays` and the C array of pointers to them, as the detector's entry points
+    take weights, biases and BatchNorm maps (keep the first alive while the second is in use)."""
+    keep = [np.ascontiguousarray(a, dtype=np.float32) for a in arrays]
+    return keep, (C.c_void_p * len(keep))(*[a.ctypes.data for a in keep])
+
+
 class DetectorWeights:
     """Device copy of the frozen detector (aware_detector)."""
 
@@ -530,17 +538,13 @@ class DetectorWeights:
         require_gpu()
         self.lib = load_library()
         self.plan = plan
-        mel = np.ascontiguousarray(mel_basis, dtype=np.float32)
-        self._mel = mel
-        ws = [np.ascontiguousarray(w, dtype=np.float32) for w in weights]
-        bs = [np.ascontiguousarray(b, dtype=np.float32) for b in biases]
+        mel = self._mel = _host_arrays([mel_basis])[0][0]
+        ws, wp = _host_arrays(weights)
+        bs, bp = _host_arrays(biases)
         chans = [ws[0].shape[1]] + [w.shape[0] for w in ws]
         self.channels = chans
         self.n_bits = chans[-1] // 2
         nl = len(ws)
-        wp = (C.c_void_p * nl)(*[w.ctypes.data for w in ws])
-        bp = (C.c_void_p * nl)(*[b.ctypes.data for b in bs])
-        h = C.c_void_p()
         self.conv = tuple(int(v) for v in conv) if conv is not None else (1, 1, 0)
         self.pool = tuple(int(v) for v in pool) if pool is not None else (2, 2)
         if conv is not None and arch is None:
@@ -549,28 +553,22 @@ class DetectorWeights:
             raise ValueError("DetectorWeights: pool needs arch (aware_detector_create_pool)")
         if any(w.ndim != (3 if conv is not None else 2) or (conv is not None and w.shape[2] != self.conv[0]) for w in ws):
             raise ValueError("DetectorWeights: weights are [cout, cin] per block, or [cout, cin, kernel_size] with conv")
-        if arch is None:
-            rc = self.lib.aware_detector_create(C.byref(h), plan.h, C.c_void_p(mel.ctypes.data), mel.shape[0], nl,
-                                                (C.c_int * (nl + 1))(*chans), wp, bp)
-            check(rc, "aware_detector_create")
-        else:
+        # the shortest entry point that takes the arguments given
+        name, more = "aware_detector_create", []
+        if arch is not None:
             a = DetectorArch(arch["activation"], arch["norm"], arch["final_activation"], None, None)
             if arch.get("scale") is not None:
-                self._norm = [np.ascontiguousarray(v, dtype=np.float32) for v in list(arch["scale"]) + list(arch["shift"])]
-                a.norm_scale = (C.c_void_p * nl)(*[v.ctypes.data for v in self._norm[:nl]])
-                a.norm_shift = (C.c_void_p * nl)(*[v.ctypes.data for v in self._norm[nl:]])
+                self._norm, a.norm_scale = _host_arrays(arch["scale"])
+                shift, a.norm_shift = _host_arrays(arch["shift"])
+                self._norm += shift
+            name, more = "aware_detector_create_ex", [C.byref(a)]
             if pool is not None:
-                rc = self.lib.aware_detector_create_pool(C.byref(h), plan.h, C.c_void_p(mel.ctypes.data), mel.shape[0], nl,
-                                                         (C.c_int * (nl + 1))(*chans), wp, bp, C.byref(a), *self.conv, *self.pool)
-                check(rc, "aware_detector_create_pool")
+                name, more = "aware_detector_create_pool", more + [*self.conv, *self.pool]
             elif conv is not None:
-                rc = self.lib.aware_detector_create_conv(C.byref(h), plan.h, C.c_void_p(mel.ctypes.data), mel.shape[0], nl,
-                                                         (C.c_int * (nl + 1))(*chans), wp, bp, C.byref(a), *self.conv)
-                check(rc, "aware_detector_create_conv")
-            else:
-                rc = self.lib.aware_detector_create_ex(C.byref(h), plan.h, C.c_void_p(mel.ctypes.data), mel.shape[0], nl,
-                                                       (C.c_int * (nl + 1))(*chans), wp, bp, C.byref(a))
-                check(rc, "aware_detector_create_ex")
+                name, more = "aware_detector_create_conv", more + [*self.conv]
+        h = C.c_void_p()
+        check(getattr(self.lib, name)(C.byref(h), plan.h, C.c_void_p(mel.ctypes.data), mel.shape[0], nl, (C.c_int * (nl + 1))(*chans),
+                                      wp, bp, *more), name)
         self.h = h
         self.is_card = bool(self.lib.aware_detector_is_card(h))
 
@@ -582,10 +580,8 @@ class DetectorWeights:
         """EXTENSION (detector training): replace the parameters in place (same shapes), aware_detector_update."""
         require_card_arch(self, "aware_detector_update")
         torch.cuda.synchronize()
-        ws = [np.ascontiguousarray(w, dtype=np.float32) for w in weights]
-        bs = [np.ascontiguousarray(b, dtype=np.float32) for b in biases]
-        wp = (C.c_void_p * len(ws))(*[w.ctypes.data for w in ws])
-        bp = (C.c_void_p * len(bs))(*[b.ctypes.data for b in bs])
+        ws, wp = _host_arrays(weights)
+        bs, bp = _host_arrays(biases)
         check(self.lib.aware_detector_update(self.h, C.c_void_p(self._mel.ctypes.data), wp, bp), "aware_detector_update")
 
     def update_device(self, weights, biases):
