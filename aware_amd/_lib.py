@@ -14,7 +14,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AWARE_HIP_LIB") or os.path.join(_HERE, "libaware_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["capi.hip", "dsp_kernels.hip", "dsp_stream.hip", "seam_kernels.hip", "detector_kernels.hip", "gemm_x3.hip", "gemm_h2.hip", "attack_kernels.hip", "stft_any.hip", "loop_any.hip", "stoi_kernels.hip", "loop_attack_kernels.hip", "loop_reverb_kernels.hip", "loop_speed_kernels.hip", "loop_stretch_kernels.hip", "loop_pitch_kernels.hip", "loop_pv_kernels.hip", "loop_delete_kernels.hip", "loop_filter_kernels.hip", "loop_shift_kernels.hip", "loop_excerpt_kernels.hip", "loop_warp_kernels.hip", "sync_kernels.hip", "loop_mix_kernels.hip", "loop_gain_kernels.hip", "speed_search_kernels.hip", "shift_search_kernels.hip", "scan_kernels.hip", "viterbi_kernels.hip", "conv_taps_kernels.hip", "mel_pool_kernels.hip"]
+SOURCES = ["capi.hip", "dsp_kernels.hip", "dsp_stream.hip", "seam_kernels.hip", "detector_kernels.hip", "gemm_x3.hip", "gemm_h2.hip", "attack_kernels.hip", "stft_any.hip", "loop_any.hip", "loop_any_chain.hip", "stoi_kernels.hip", "loop_attack_kernels.hip", "loop_reverb_kernels.hip", "loop_speed_kernels.hip", "loop_stretch_kernels.hip", "loop_pitch_kernels.hip", "loop_pv_kernels.hip", "loop_delete_kernels.hip", "loop_filter_kernels.hip", "loop_shift_kernels.hip", "loop_excerpt_kernels.hip", "loop_warp_kernels.hip", "sync_kernels.hip", "loop_mix_kernels.hip", "loop_gain_kernels.hip", "speed_search_kernels.hip", "shift_search_kernels.hip", "scan_kernels.hip", "viterbi_kernels.hip", "conv_taps_kernels.hip", "mel_pool_kernels.hip"]
 
 AWARE_OK = 0
 ERRORS = {-1: "bad argument", -2: "unsupported configuration", -3: "HIP runtime error", -4: "workspace too small"}
@@ -165,6 +165,8 @@ SIGNATURES = {
     "aware_embed_loop_mixture_workspace_bytes": (_sz, [_vp, C.POINTER(LoopChain), _i]),
     "aware_embed_set_loop_mixture": (_i, [_vp, C.POINTER(LoopChain), _i, C.POINTER(C.c_uint32), _vp, _sz, _vp]),
     "aware_loop_mixture_draw": (_i, [_vp, _i, _i, C.POINTER(C.c_float), _i, _vp, _vp]),
+    "aware_embed_general_chain_workspace_bytes": (_sz, [_vp, C.POINTER(LoopAttackEx), _i]),
+    "aware_embed_set_general_chain": (_i, [_vp, C.POINTER(LoopAttackEx), _i, C.POINTER(C.c_uint32), _vp, _sz, _vp]),
     "aware_convolve_workspace_bytes": (_sz, [_i, _i, C.c_longlong, _i]),
     "aware_convolve": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _sz, _vp]),
     "aware_reverb_ir": (_i, [_vp, _i, _i, _i, _i, _i, _f, _vp, _i, _vp, _vp]),

@@ -17,6 +17,7 @@
 #include "kernels.h"
 #define AWARE_LOOP_CF cf
 #include "loop_chain.hpp"
+#include "loop_any_chain.hpp"
 #include "batch_layout.hpp"
 #include "detector_image.hpp"
 
@@ -1630,6 +1631,9 @@ struct aware_embed {
     // signals with the gradient of the first [NS]
     cf *S0 = nullptr, *S2 = nullptr, *GS = nullptr;
     float *y1 = nullptr, *y2 = nullptr, *gy1 = nullptr;
+    // attack-aware embedding on the general route (aware_embed_set_general_chain; EXTENSION): the chain and its buffers in the
+    // caller's second workspace.  n == 0: the loop issues exactly the launches of the plain general route
+    GenChainState gc;
 };
 
 // the embed loop's workspace: the detector's buffers, then the loop state; iters: num_iterations, l1: the L1 term's buffers
@@ -1963,6 +1967,31 @@ extern "C" int aware_embed_set_loop_attacks(aware_embed* e, const aware_loop_att
 extern "C" int aware_embed_set_loop_attacks_ex(aware_embed* e, const aware_loop_attack_ex* attacks, int n_attacks,
                                                const uint32_t* seeds, void* workspace, size_t workspace_bytes, void* stream) {
     return set_loop_attacks(e, attacks, n_attacks, true, seeds, workspace, workspace_bytes, stream);
+}
+
+// ---- the general route's chain (EXTENSION): the element-wise kinds at any geometry (loop_any_chain.hip);
+// parser and carver are loop_any_chain.hpp's
+extern "C" size_t aware_embed_general_chain_workspace_bytes(const aware_batch* b, const aware_loop_attack_ex* attacks, int n_attacks) {
+    return (b && b->general) ? gen_chain_workspace_bytes(loop_dims(b), attacks, n_attacks) : 0;
+}
+extern "C" int aware_embed_set_general_chain(aware_embed* e, const aware_loop_attack_ex* attacks, int n_attacks, const uint32_t* seeds,
+                                             void* workspace, size_t workspace_bytes, void* stream) {
+    if (!e || n_attacks < 0 || n_attacks > kMaxLoopAttacks) return AWARE_E_BADARG;
+    if (e->gexec || e->la.locked) return AWARE_E_BADARG;          // before the first aware_embed_iterate, as the card's setters
+    const aware_batch* b = e->b;
+    if (!b->general) return AWARE_E_UNSUPPORTED;                  // the card route has its own setters
+    if (n_attacks == 0) { e->gc = GenChainState(); return AWARE_OK; }
+    if (!attacks || !seeds || !workspace || ((uintptr_t)workspace & 255)) return AWARE_E_BADARG;
+    GenChainState gc;
+    if (int rc = parse_gen_chain(loop_dims(b), attacks, n_attacks, gc)) return rc;
+    Carver c(workspace, workspace_bytes);
+    carve_gen_chain(c, loop_dims(b), gc);
+    if (!c.ok) return AWARE_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    HIPCHK(hipMemcpyAsync(gc.seeds, seeds, (size_t)b->B * sizeof(unsigned), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    e->gc = gc;
+    return AWARE_OK;
 }
 
 // ---- attack mixtures (EXTENSION): one of several chains drawn per clip and step (loop_mix_kernels.hip)
@@ -2314,7 +2343,9 @@ extern "C" void* aware_embed_buffer(aware_embed* e, int which) {
         case 9: return e->yraw;
         case 10: return e->mag;
         case 11: return e->opt.active ? e->opt.d_lr : nullptr;      // per-clip learning rate (double; ReduceLROnPlateau state)
-        case 12: return (e->la.n || e->mix_n) ? e->la.z : nullptr;  // the attacked signal of the last forward pass
+        case 12:                                                    // the attacked signal of the last forward pass
+            if (e->gc.n) return e->gc.z;
+            return (e->la.n || e->mix_n) ? e->la.z : nullptr;
         case 13:                                                    // its impulse responses, f32 [B][8192]
             if (e->mix_n) return e->mix_rv >= 0 ? e->mix[e->mix_rv].h : nullptr;
             return (e->la.n && chain_has(e->la, AWARE_LOOP_REVERBERATION)) ? e->la.h : nullptr;
@@ -2379,6 +2410,21 @@ static int gen_synthesise(aware_embed* e, const float* coef, hipStream_t st) {
     LAUNCHCHK(); PROF(K_MISC);
     return AWARE_OK;
 }
+// the launches of the general route's chain (loop_any_chain.hip) on the loop's buffers
+static GenChainLaunch gen_chain_launch(const aware_embed* e) {
+    const aware_batch* b = e->b;
+    const GenChainState& g = e->gc;
+    GenChainLaunch C;
+    C.sig_off = b->d_out_off; C.sig_len = b->d_out_len; C.pc_out = b->d_pc_out; C.B = b->B; C.pstride = b->pstride;
+    C.pieces = g.pieces; C.step = e->step; C.seeds = g.seeds; C.n = g.n;
+    for (int j = 0; j < g.n; ++j) {
+        C.kind[j] = g.kind[j]; C.k[j] = g.k[j]; C.inv_snr[j] = g.inv_snr[j]; C.prob[j] = g.prob[j];
+        C.p_lo[j] = g.p_lo[j]; C.p_hi[j] = g.p_hi[j]; C.floor[j] = g.floor[j];
+    }
+    C.yraw = e->yraw; C.pmaxY = e->pmaxY; C.psq = g.psq; C.z = g.z; C.pmaxZ = g.pmaxZ; C.a = e->y2;
+    C.gy = e->gy; C.pdotA = g.pdotA; C.pdotX = g.pdotX;
+    return C;
+}
 // one loop body of AWAREEmbedder._optimize (multibit_embedder.py:95-122), every stage its own launch, one chain
 static int gen_embed_iteration(aware_embed* e, hipStream_t st, int do_step, float* grad_out) {
     const aware_batch* b = e->b;
@@ -2389,9 +2435,17 @@ static int gen_embed_iteration(aware_embed* e, hipStream_t st, int do_step, floa
     // list starts with one), STFT and |.| on the band (:104 zeroes the rest)
     int rc = gen_synthesise(e, e->coef, st);
     if (rc) return rc;
-    launch_normalize(e->yraw, e->y1, b->d_out_off, b->d_out_len, e->pmaxY, b->d_pc_out, b->pstride, b->B, b->max_len, st);
-    launch_absmax_partials(e->y1, b->d_out_off, b->d_out_len, e->pmaxY, b->pstride, b->B, b->max_len, st);
-    launch_normalize(e->y1, e->y2, b->d_out_off, b->d_out_len, e->pmaxY, b->d_pc_out, b->pstride, b->B, b->max_len, st);
+    // attack-aware embedding (EXTENSION): x = N(N(yraw)), the chain's z, and a = N(N(z)) in y2, which the analysis reads
+    const bool attacked = e->gc.n > 0;
+    GenChainLaunch C;
+    if (attacked) {
+        C = gen_chain_launch(e);
+        launch_gen_chain_forward(C, st);
+    } else {
+        launch_normalize(e->yraw, e->y1, b->d_out_off, b->d_out_len, e->pmaxY, b->d_pc_out, b->pstride, b->B, b->max_len, st);
+        launch_absmax_partials(e->y1, b->d_out_off, b->d_out_len, e->pmaxY, b->pstride, b->B, b->max_len, st);
+        launch_normalize(e->y1, e->y2, b->d_out_off, b->d_out_len, e->pmaxY, b->d_pc_out, b->pstride, b->B, b->max_len, st);
+    }
     LAUNCHCHK(); PROF(K_MISC);
     launch_gen_analysis(L, e->y2, e->S2, 0, st);
     LAUNCHCHK(); PROF(K_ANALYSIS);
@@ -2406,8 +2460,14 @@ static int gen_embed_iteration(aware_embed* e, hipStream_t st, int do_step, floa
     LAUNCHCHK(); PROF(K_MISC);
     launch_gen_synthesis(L, e->GS, e->gy, 1, st);
     LAUNCHCHK(); PROF(K_SYNTH_ADJ);
-    launch_normalize_bwd(e->y1, e->gy, e->gy1, b->d_out_off, b->d_out_len, b->B, st);
-    launch_normalize_bwd(e->yraw, e->gy1, e->gy, b->d_out_off, b->d_out_len, b->B, st);
+    if (attacked) {
+        // gy: dL/da -> dL/dyraw in place, at the step the forward pass drew at
+        C.step_back = do_step ? 1 : 0;                  // the read-out kernel has advanced the counter
+        launch_gen_chain_backward(C, st);
+    } else {
+        launch_normalize_bwd(e->y1, e->gy, e->gy1, b->d_out_off, b->d_out_len, b->B, st);
+        launch_normalize_bwd(e->yraw, e->gy1, e->gy, b->d_out_off, b->d_out_len, b->B, st);
+    }
     LAUNCHCHK(); PROF(K_MISC);
     launch_gen_analysis(L, e->gy, e->S2, 1, st);
     LAUNCHCHK(); PROF(K_ANALYSIS_ADJ);

@@ -401,6 +401,41 @@ void launch_rescale_normalize(const float* in, float* out, const int* off, const
 void launch_band_coef_grad(const BandLaunch& L, const void* gspec, const void* unit, float* grad_out, const BandStep* step,
                            hipStream_t st);
 
+// ---- loop_any_chain.hip: attack-aware embedding on the general route (EXTENSION, aware_embed_set_general_chain): the
+// element-wise kinds of a chain between the general loop's synthesis and its analysis, on pieces of kGenChainPiece samples
+// (loop_any_chain.hpp) of signals at any float offset -------------------------------------------------------------------
+struct GenChainLaunch {
+    const int* sig_off = nullptr;         // [B] out_off: any float offset
+    const int* sig_len = nullptr;         // [B] Ny_b
+    const int* pc_out = nullptr;          // [B] 4096-sample pieces of clip b: the partials of pmaxY
+    int B = 0, pstride = 0;               // pstride: stride of pmaxY
+    int pieces = 0;                       // pieces of the longest clip: the grid, and the stride of the chain's partial arrays
+    const int* step = nullptr;            // device step counter; step_back = 1 once the read-out kernel has advanced it
+    int step_back = 0;
+    const unsigned* seeds = nullptr;      // [B]
+    int n = 0;
+    int kind[kMaxLoopAttacks] = {0};
+    int k[kMaxLoopAttacks] = {0};
+    double inv_snr[kMaxLoopAttacks] = {0};
+    float prob[kMaxLoopAttacks] = {0};
+    int p_lo[kMaxLoopAttacks] = {0}, p_hi[kMaxLoopAttacks] = {0};
+    float floor[kMaxLoopAttacks] = {0};
+    const float* yraw = nullptr;          // the raw synthesis and its partial maxima (4096-sample pieces)
+    const unsigned long long* pmaxY = nullptr;
+    double* psq = nullptr;                // [kMaxLoopAttacks][B][pieces]
+    float* z = nullptr;                   // the attacked signal and its partial maxima
+    unsigned long long* pmaxZ = nullptr;  // [B][pieces]
+    float* a = nullptr;                   // N(N(z)): what the loop's analysis reads
+    float* gy = nullptr;                  // backward: dL/da in, dL/dyraw out
+    double* pdotA = nullptr;              // [B][pieces] partial sums of dL/da * a
+    double* pdotX = nullptr;              // [B][pieces] partial sums of dL/dx * x
+};
+// x = N(N(yraw)), the chain, z and its partial maxima, a = N(N(z)): one reduction launch per noise entry, then two passes
+void launch_gen_chain_forward(const GenChainLaunch& L, hipStream_t st);
+// gy: dL/da -> dL/dyraw in place, in three passes: the partial sums of dL/da * a; the normalisers at z and the chain's masks
+// and gains with the partial sums of dL/dx * x; the normalisers in front of the chain
+void launch_gen_chain_backward(const GenChainLaunch& L, hipStream_t st);
+
 // ---- stoi_kernels.hip: batched short-time objective intelligibility (metrics/audio.py::stoi) at 10 kHz -------------
 constexpr int kStoiFrame = 256, kStoiHop = 128, kStoiBands = 15, kStoiRow = 16, kStoiN = 30;
 constexpr int kStoiSegChunk = 64;         // segments per partial sum of the last stage

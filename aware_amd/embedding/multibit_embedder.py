@@ -30,7 +30,8 @@ class AWAREEmbedder(BaseEmbedder):
                  num_iterations: int = 400, detection_net_cfg: dict = None, optimizer_cfg: dict = None,
                  scheduler_cfg: dict = None, loss: str = "push", verbose: bool = True, use_graph: bool = True,
                  loop_attacks=None, loop_attack_seed: int = 0, loop_attack_mixture=None, payload_code=None,
-                 general_geometry: bool = False, temporal_convs: bool = False, initial_pools: bool = False):
+                 general_geometry: bool = False, temporal_convs: bool = False, initial_pools: bool = False,
+                 general_loop_attacks: bool = False):
         """loop_attacks (EXTENSION, see embedding/loop_attacks.py): a chain of attacks applied inside the optimisation loop,
         e.g. [{"kind": "gaussian_noise", "snr_db": 10.0}, {"kind": "sample_suppression", "seconds": 0.3, "prob": 0.75}];
         clip i of a batch draws with seed loop_attack_seed + i.  None: the reference's loop (clean synthesis only).
@@ -43,6 +44,10 @@ class AWAREEmbedder(BaseEmbedder):
         hop_length and win_length in 1..frame_length, on the general route (the card geometry included); off: the card
         geometry only, on the card kernels.  With it, loop_attacks, loop_attack_mixture and the loss push_extremes_l1 raise
         NotImplementedError, and detection_net_cfg.n_fft has to equal frame_length.
+        general_loop_attacks (EXTENSION): beside general_geometry, loop_attacks may hold up to four
+        entries of the kinds that do not split a chain (runtime.GENERAL_CHAIN_KINDS: gaussian_noise, sample_suppression,
+        gain_envelope), in any order, and the session runs them on the general route; every other kind and
+        loop_attack_mixture still raise NotImplementedError.  Without general_geometry the key changes nothing.
         temporal_convs (EXTENSION): handed to the detection net built from detection_net_cfg, where it
         opens kernel_size / stride / padding other than 1 / 1 / 0 (AWAREDetectorNet); off: 1x1 convolutions only.
         initial_pools (EXTENSION): handed to the detection net in the same way, where it opens
@@ -88,8 +93,12 @@ class AWAREEmbedder(BaseEmbedder):
         self.loop_attack_mixture = parse_mixture(loop_attack_mixture)      # ValueError with the index of the offending chain
         if self.loop_attacks and self.loop_attack_mixture:
             raise ValueError("AWAREEmbedder: loop_attacks or loop_attack_mixture, not both")
+        self.general_loop_attacks = bool(general_loop_attacks)
         if self.general_geometry and self.loop_attacks:
-            rt.refuse_general_geometry("loop_attacks")
+            if not self.general_loop_attacks:
+                rt.refuse_general_geometry("loop_attacks", "; the key general_loop_attacks opens the kinds "
+                                           + ", ".join(rt.GENERAL_CHAIN_KINDS) + " on the general route")
+            rt.check_general_chain(self.loop_attacks)
         if self.general_geometry and self.loop_attack_mixture:
             rt.refuse_general_geometry("loop_attack_mixture")
         self.loop_attack_seed = int(loop_attack_seed)
@@ -139,7 +148,10 @@ class AWAREEmbedder(BaseEmbedder):
     # ---- batched hot path ----------------------------------------------------------------------
     def start_session(self, batch: "rt.Batch", sample_rate: int, attack_seeds=None) -> "rt.EmbedSession":
         sess = self._start_session(batch, sample_rate)
-        if self.loop_attacks:
+        if self.loop_attacks and self.general_geometry:
+            seeds = attack_seeds if attack_seeds is not None else [self.loop_attack_seed + i for i in range(batch.B)]
+            sess.set_general_chain(self.loop_attacks, seeds, sample_rate)
+        elif self.loop_attacks:
             seeds = attack_seeds if attack_seeds is not None else [self.loop_attack_seed + i for i in range(batch.B)]
             sess.set_loop_attacks(self.loop_attacks, seeds, sample_rate)
         elif self.loop_attack_mixture:

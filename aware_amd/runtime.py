@@ -122,11 +122,26 @@ def require_card_geometry(who: str, n_fft: int, hop: int, win_length: int, gener
                                   f"general_geometry is set (general_geometry=True, or `general_geometry: true` in the card)")
 
 
-def refuse_general_geometry(feature: str):
+def refuse_general_geometry(feature: str, hint: str = ""):
     """What the general route does not serve: its kernels or its offsets are built on the card geometry (hop 256, a
-    512-sample pooling period).  NotImplementedError naming the feature and the key."""
+    512-sample pooling period).  NotImplementedError naming the feature and the key; `hint` follows the message."""
     raise NotImplementedError(f"{feature} is not supported with general_geometry=True: it runs on the model card's STFT "
-                              f"geometry {CARD_GEOMETRY[0]} / {CARD_GEOMETRY[1]} / {CARD_GEOMETRY[2]} only (key general_geometry off)")
+                              f"geometry {CARD_GEOMETRY[0]} / {CARD_GEOMETRY[1]} / {CARD_GEOMETRY[2]} only (key general_geometry off)"
+                              + hint)
+
+
+# the chain kinds the general route serves (aware_embed_set_general_chain): those that do not split a chain
+GENERAL_CHAIN_KINDS = ("gaussian_noise", "sample_suppression", "gain_envelope")
+
+
+def check_general_chain(chain):
+    """A parsed chain for the general route (keys general_geometry and general_loop_attacks): NotImplementedError naming the
+    first entry of a kind its kernels do not serve."""
+    for j, a in enumerate(chain):
+        if a["kind"] not in GENERAL_CHAIN_KINDS:
+            raise NotImplementedError(f"loop_attacks[{j}] ({a['kind']}) is not supported with general_geometry=True: the general "
+                                      f"route serves the kinds {', '.join(GENERAL_CHAIN_KINDS)} (key general_loop_attacks); "
+                                      f"every other kind runs on the model card's STFT geometry only")
 
 
 def check_general_clips(who: str, n_fft: int, hop: int, win_length: int, window: str, lengths, embed: bool = True):
@@ -747,6 +762,35 @@ class EmbedSession:
         if rc == -1:
             raise ValueError("set_loop_attacks: refused (it has to precede the first iterate(); see aware_hip.h)")
         check(rc, "aware_embed_set_loop_attacks")
+        self.loop_attacks, self._la_ws = chain, ws
+
+    def set_general_chain(self, chain, seeds, sample_rate: int = 16000):
+        """Attack-aware embedding on the general route (EXTENSION; aware_embed_set_general_chain): as
+        set_loop_attacks for a session on a general plan, with the kinds of GENERAL_CHAIN_KINDS (NotImplementedError naming any
+        other).  `seconds` and `period` become samples at `sample_rate`.  Before the first iterate(); an empty chain clears
+        it, and the session launches what it launched before.  The attacked signal of the last forward pass is `attacked`."""
+        from .embedding import loop_attacks as la
+        chain = la.parse_chain(chain, sample_rate)
+        if not chain:
+            rc = self.lib.aware_embed_set_general_chain(self.h, None, 0, None, None, 0, _stream())
+            if rc == -1:
+                raise ValueError("set_general_chain: refused (it has to precede the first iterate(); see aware_hip.h)")
+            check(rc, "aware_embed_set_general_chain")
+            self.loop_attacks, self._la_ws = [], None
+            return
+        check_general_chain(chain)
+        if len(seeds) != self.batch.B:
+            raise ValueError(f"set_general_chain: {self.batch.B} clips but {len(seeds)} seeds")
+        la.check_lengths(chain, sample_rate, self.batch.out_lengths)      # ValueError naming the clip, before any launch
+        sd = (C.c_uint32 * self.batch.B)(*[int(s) & 0xFFFFFFFF for s in seeds])
+        ent = la.device_entries_ex(chain, sample_rate)
+        arr = (_lib.LoopAttackEx * len(ent))(*[_lib.LoopAttackEx(k, pr, (C.c_float * 4)(*p)) for k, pr, p in ent])
+        nbytes = self.lib.aware_embed_general_chain_workspace_bytes(self.batch.h, arr, len(ent))
+        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=_dev())
+        rc = self.lib.aware_embed_set_general_chain(self.h, arr, len(ent), sd, _ptr(ws), nbytes, _stream())
+        if rc == -1:
+            raise ValueError("set_general_chain: refused (it has to precede the first iterate(); see aware_hip.h)")
+        check(rc, "aware_embed_set_general_chain")
         self.loop_attacks, self._la_ws = chain, ws
 
     def set_loop_mixture(self, mixture, seeds, sample_rate: int = 16000):

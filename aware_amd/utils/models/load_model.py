@@ -24,6 +24,8 @@ _EMBEDDER = {"pattern_mode": ("pattern_mode", "bits2bipolar"), "tolerance_db": (
              "loop_attacks": ("loop_attacks", None), "loop_attack_seed": ("loop_attack_seed", 0),
              # EXTENSION: one of several chains drawn per clip and step; absent = none, and not beside loop_attacks
              "loop_attack_mixture": ("loop_attack_mixture", None),
+             # EXTENSION: loop_attacks of the element-wise kinds beside general_geometry; absent = refused there
+             "general_loop_attacks": ("general_loop_attacks", False),
              # EXTENSION (utils/watermark/fec.py): the channel code of service.embed_message / detect_message; absent = none
              "payload_code": ("payload_code", None),
              # EXTENSION: kernel_size / stride / padding of detection_net_cfg; absent = 1x1 convolutions only

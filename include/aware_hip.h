@@ -479,7 +479,8 @@ int aware_embed_finish(aware_embed* e, const float* rescale, float* out, void* s
 /* device pointers to internal state for inspection: 0 loss[B], 1 best_loss[B], 2 pred[B][n_bits],
  * 3 coef [frames][band stride], 4 best coef, 5 lo, 6 hi, 7 phasor (complex64), 8 step counter (int32), 9 un-normalised synthesis,
  * 10 band magnitudes of the last analysis, 11 per-clip learning rates (f64 [B]; NULL unless aware_embed_set_optimizer ran),
- * 12 the attacked signal z of the last forward pass (layout of 9; NULL unless aware_embed_set_loop_attacks set a chain)
+ * 12 the attacked signal z of the last forward pass (layout of 9; NULL unless aware_embed_set_loop_attacks or, on a
+ *    general plan, aware_embed_set_general_chain set a chain)
  * 13 the impulse responses of the last forward pass (NULL unless the chain has a reverberation; see below)
  * 14 the choices of the last forward pass, int32 [B] (NULL unless aware_embed_set_loop_mixture set a mixture; see below) */
 void* aware_embed_buffer(aware_embed* e, int which);
@@ -961,6 +962,31 @@ int aware_embed_set_loop_mixture(aware_embed* e, const aware_loop_chain* chains,
                                  void* workspace, size_t workspace_bytes, void* stream);
 int aware_loop_mixture_draw(const uint32_t* seeds, int B, int step, const float* weights, int n_chains, int* choice,
                             void* stream);
+
+/* ---- attack-aware embedding at any STFT geometry (EXTENSION, parity unpinned) ------------------------
+ * The setters above serve the card geometry only and refuse a session on a general plan (AWARE_PLAN_GENERAL).  This one
+ * serves such a session, with the kinds that do not split a chain: AWARE_LOOP_GAUSSIAN_NOISE, AWARE_LOOP_SAMPLE_SUPPRESSION
+ * and AWARE_LOOP_GAIN_ENVELOPE, up to four entries in any order, parameters as aware_embed_set_loop_attacks_ex takes them.
+ * The model is the card's: at optimiser step s (aware_embed_buffer 8) clip b (Ny_b = hop * (T_b - 1) samples) goes through
+ *     x = N(N(yraw)),  z = chain(x) with the draws of the card route (sample i of a clip uses the counter word it uses there),
+ *     a = N(N(z)),     N(v) = v / (max|v| + 1e-8)
+ * and the loop's analysis reads a; the backward pass is the adjoint of exactly that, with the noise amplitude, the mask and
+ * the gains as constants.  At the card geometry a general session therefore sees the very draws a card session sees with the
+ * same chain and seeds.  aware_embed_iterate (eager and recorded), aware_embed_gradient (at the current step, which it does not
+ * advance) and aware_embed_profile honour the chain; aware_embed_buffer 12 is z of the last forward pass, 9 stays yraw.
+ * Calling rules as aware_embed_set_loop_attacks_ex: before the first aware_embed_iterate; n_attacks = 0 clears the chain, and
+ * the session then launches what it launched before; seeds: host uint32 [B]; workspace: device memory, 256-byte aligned, alive
+ * as long as the handle, aware_embed_general_chain_workspace_bytes large (z, and per piece of 3072 samples of every clip the
+ * partial maxima, sums of squares and dot products the kernels exchange).
+ * AWARE_E_BADARG: what the card's setter calls a bad argument (a null or misaligned pointer, n_attacks outside 0..4, a kind
+ * outside the table, prob outside [0, 1], a parameter outside its range, a call after the first iterate).
+ * AWARE_E_UNSUPPORTED: a session that is not on a general plan; a well-formed entry of any other kind; a suppression with
+ * k >= Ny_b for some clip.  AWARE_E_WORKSPACE: a workspace smaller than the size function says.  The size function returns 0
+ * for a card batch and for a chain that is AWARE_E_BADARG.  Added without a version step: callers detect the addition by
+ * symbol. */
+size_t aware_embed_general_chain_workspace_bytes(const aware_batch* batch, const aware_loop_attack_ex* attacks, int n_attacks);
+int aware_embed_set_general_chain(aware_embed* e, const aware_loop_attack_ex* attacks, int n_attacks, const uint32_t* seeds,
+                                  void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- offset search in detection (EXTENSION, parity unpinned: the reference detects at the clip's own start only) -----------
  * The detector pools pairs of frames of hop 256, so its read-out has a period of 512 samples in where the clip starts, and a
